@@ -19,9 +19,15 @@ that any K is a whole number of steady-state batches.  `value` is frames/s.
 The input of a stream is a closed-loop clip of `--clip-frames` (128) DISTINCT
 frames rendered on the device (796 MB at 1080p: three times the 256 MB Infinity
 Cache) and played in a cycle, so the warp reads every source frame from HBM;
-the results go to a ring of 3 x batch output frames (1.2 GB).  The timed region
-of exactly K steps is repeated `--regions` (9) times, each bracketed by barrier +
-device sync; `value` is the MEDIAN region (all of them are in `regions`).
+the results go to a ring of 3 x batch output frames (1.2 GB).  Exactly K steps
+are timed: one region (or K / `--regions` steps in each of `--regions` regions),
+each bracketed by barrier + device sync; `value` is the MEDIAN region (all of
+them are in `regions`) and `ms_per_step` the time of one step in it.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last
+timed step (the stabilized frames of that step) as float32 .npy files, 64 MB at
+most; the clips are rendered from fixed seeds, so equal arguments give equal
+inputs and two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0; at N = 1 it also carries the PCIe-inclusive rate
 of the host-pointer entry point, BASELINE configs[2] (3840x2160) and the CPU
@@ -43,6 +49,8 @@ sys.path.insert(0, os.path.join(ROOT, "video-stab_amd"))
 from vsamd import capi, dist as vsdist, synth  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 measured copy rate
+DUMP_BYTES = 60 * 10**6  # --dump-outputs: the arrays of one run together (under 64 MB, .npy headers included)
+DUMP_SEED = 0x5EED00D5   # --dump-outputs: the element positions of frames_sample.npy
 # algorithmic bytes of the WHOLE step per 1080p BGR8 frame (downscale+gray, pyramid, GFTT every 2nd frame,
 # LK gathers, warp)
 WHOLE_STEP_BYTES_1080P = 22.7e6
@@ -235,6 +243,34 @@ class StreamSet:
                 b.free()
 
 
+def dump_outputs(ss, out_dir):
+    """--dump-outputs: the frames the last step handed its caller (the results of the last `BT` pushes of every stream of this
+    rank, still in the output ring after the timed regions) as float32 arrays of their uint8 values, DUMP_BYTES at most:
+      last_frame.npy      the step's last frame of the first stream, in full (when it fits in half of DUMP_BYTES)
+      frames_sample.npy   [stream, push, k]: the same k elements of every frame of the step (flat positions drawn without
+                          replacement by np.random.default_rng(DUMP_SEED), ascending), k as large as the rest allows
+    Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    shape = (ss.h, ss.w, 3) if ss.fmt == capi.FMT_BGR8 else (ss.h * 3 // 2, ss.w)
+    slots = [(ss.i - ss.BT + t) % ss.NOUT for t in range(ss.BT)]
+    files = {}
+    budget = DUMP_BYTES
+    if 4 * ss.fb <= DUMP_BYTES // 2:
+        last = ss.d_out[0][slots[-1]].download(shape, np.uint8).astype(np.float32)
+        np.save(os.path.join(out_dir, "last_frame.npy"), last)
+        files["last_frame"] = list(last.shape)
+        budget -= last.nbytes
+    k = min(ss.fb, budget // (4 * len(ss.d_out) * ss.BT))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(ss.fb, k, replace=False))
+    sample = np.empty((len(ss.d_out), ss.BT, k), np.float32)
+    for j, bufs in enumerate(ss.d_out):
+        for t, oi in enumerate(slots):
+            sample[j, t] = bufs[oi].download((ss.fb,), np.uint8)[idx]
+    np.save(os.path.join(out_dir, "frames_sample.npy"), sample)
+    files["frames_sample"] = list(sample.shape)
+    return files
+
+
 def timed_regions(ss, comm, steps, regions):
     """`regions` timed regions of exactly `steps` steps each, every one bracketed by barrier + device sync on both sides;
     elapsed = max over ranks.  Returns the list of elapsed seconds."""
@@ -418,8 +454,9 @@ def run_stream_workload(comm, ss, steps, warmup, regions, preroll_batches, profi
     return elapsed, roof, stage_ms, stage_n
 
 
-def config2(vs, comm, device, args, full=True):
-    """BASELINE configs[2]: 3840x2160, 400 corners, RollCorrection + AutoZoomCrop enabled."""
+def config2(vs, comm, device, args, full=True, workload=False):
+    """BASELINE configs[2]: 3840x2160, 400 corners, RollCorrection + AutoZoomCrop enabled.  workload=True (--workload configs2):
+    --steps / --regions time the NV12 stream and --dump-outputs applies to it."""
     W, H = 3840, 2160
     out = {"workload": "configs[2]: 1 stream 3840x2160, 400 corners, 3-level LK 21x21; frames resident in HBM"}
     p = make_params(vs, max_corners=400)
@@ -428,16 +465,23 @@ def config2(vs, comm, device, args, full=True):
     clip = synth.make_clip_dev(vs, synth.SEED_CONFIG3, W, H, NF, nv12=True)
     BT = int(os.environ.get("VS_BENCH_4K_BATCH", "64"))
     ss = StreamSet(vs, device, p, [clip], NF, W, H, capi.FMT_NV12, BT, BT, True)
-    steps = int(os.environ.get("VS_BENCH_4K_TIMED", "20"))
-    regions = int(os.environ.get("VS_BENCH_4K_REGIONS", str(args.regions)))
+    if workload:
+        regions = args.regions
+        steps = args.steps // regions        # (steps per region)
+    else:
+        steps = int(os.environ.get("VS_BENCH_4K_TIMED", "20"))
+        regions = int(os.environ.get("VS_BENCH_4K_REGIONS", "9"))
     fb = W * H * 3 // 2
     elapsed, roof, _, _ = run_stream_workload(comm, ss, steps, 4, regions, int(os.environ.get("VS_BENCH_4K_WARM", "40")),
                                               False, 2.0 * fb, "warp_nv12_kernel (luma and interleaved chroma tiles of 32 surfaces in one launch)")
     med = statistics.median(elapsed)
+    if workload and args.dump_outputs and comm.rank == 0:
+        out["dump_outputs"] = dump_outputs(ss, args.dump_outputs)
     tables_pass(ss, roof, steps)
     traffic_from_counters(vs, roof, "configs2")
     roof["distinct_input_MB"] = round(NF * fb / 1e6, 1)
     out["nv12_stabilize"] = {"value": round(steps * BT / med, 1), "unit": "frames/s", "batch": BT, "steps": steps,
+                             "ms_per_step": round(med / steps * 1e3, 5),
                              "regions": [round(steps * BT / e, 1) for e in elapsed], "roofline": roof}
     ss.close()
     if not full:
@@ -570,9 +614,10 @@ def config2_chain(vs, device, p, W, H, chunks_timed=10, chunks_warm=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20, help="timed steps per region; a step = one batch of --batch frames per stream")
+    ap.add_argument("--steps", type=int, default=20, help="timed steps in all; a step = one batch of --batch frames per stream")
     ap.add_argument("--warmup", type=int, default=5, help="untimed steps in front of the first region")
-    ap.add_argument("--regions", type=int, default=9, help="the timed region of --steps steps is repeated this often; value = the median")
+    ap.add_argument("--regions", type=int, default=1,
+                    help="the --steps timed steps are split into this many regions of equal length; value = the median region")
     ap.add_argument("--streams", type=int, default=1, help="independent streams per GPU (batch mode)")
     ap.add_argument("--group", type=int, default=1,
                     help="--streams > 1: 1 = the streams of a GPU as ONE vs_batch group (one launch per stage over the frames of all "
@@ -599,7 +644,13 @@ def main():
     ap.add_argument("--fanout", action="store_true",
                     help="N > 1 only: rank 0 owns ingest - it renders the clips of ALL streams and scatters them to the "
                          "owning ranks (RCCL send/recv over xGMI) before the timed region; timed separately, reported as `fanout`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames the last timed step produced (rank 0's streams) to DIR as float32 .npy files "
+                         "(64 MB at most: the step's last frame in full, a seeded sample of every frame of the step)")
     args = ap.parse_args()
+    if args.steps < 1 or args.regions < 1 or args.steps % args.regions:
+        ap.error("--steps must be a positive multiple of --regions")
+    per_region = args.steps // args.regions
 
     comm = vsdist.Comm()           # nccl (= RCCL) when WORLD_SIZE > 1 (or VS_DIST_FORCE=1), nothing otherwise
     rank, local_rank, world = comm.rank, comm.local_rank, comm.world
@@ -615,7 +666,7 @@ def main():
     vs.check(vs.lib.vs_dev_set_device(local_rank))
 
     if args.workload == "configs2":
-        out = config2(vs, comm, local_rank, args, full=os.environ.get("VS_BENCH_CHAIN") == "1")   # (VS_BENCH_CHAIN=1: and the chain)
+        out = config2(vs, comm, local_rank, args, full=os.environ.get("VS_BENCH_CHAIN") == "1", workload=True)   # (VS_BENCH_CHAIN=1: and the chain)
         if rank == 0:
             print(json.dumps(out), flush=True)
         comm.close()
@@ -666,19 +717,20 @@ def main():
     ss = StreamSet(vs, local_rank, params, clips, NF, W, H, capi.FMT_BGR8, args.batch, args.warp_batch, args.zero_copy, group=args.group)
     BT = ss.BT
     elapsed, roof, stage_ms, stage_n = run_stream_workload(
-        comm, ss, args.steps, args.warmup, args.regions, int(os.environ.get("VS_BENCH_PREROLL_BATCHES", "200")),
+        comm, ss, per_region, args.warmup, args.regions, int(os.environ.get("VS_BENCH_PREROLL_BATCHES", "200")),
         args.profile_stages, 2.0 * fb, "warp_tab_kernel" if BT >= 4 else "warp_affine_kernel<3>")
     med = statistics.median(elapsed)
     # throughput counters of every rank (the only inter-GPU traffic of the path)
-    per_rank = comm.gather_counters([rank, args.steps * BT * S, ss.frames_out()])
+    per_rank = comm.gather_counters([rank, per_region * BT * S, ss.frames_out()])
 
     out = None
+    dumped = dump_outputs(ss, args.dump_outputs) if rank == 0 and args.dump_outputs else None    # (before tables_pass refills the ring)
     if rank == 0:
-        tables_pass(ss, roof, args.steps)
+        tables_pass(ss, roof, per_region)
         traffic_from_counters(vs, roof, "configs1")
         roof["copy_yardstick_GBps"] = copy_yardstick(vs, roof["bytes_per_launch"] / 2)
         roof["distinct_input_MB"] = round(NF * fb / 1e6, 1)
-        total_frames = args.steps * BT * S * n_gpus
+        total_frames = per_region * BT * S * n_gpus      # (of one region)
         whole_bytes = WHOLE_STEP_BYTES_1080P * (W * H) / (1920.0 * 1080.0)
         whole = whole_bytes * total_frames / med / 1e9
         out = {
@@ -688,7 +740,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(med / args.steps * 1e3, 5),
+            "ms_per_step": round(med / per_region * 1e3, 5),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -704,7 +756,7 @@ def main():
                        "clip": "%d distinct frames per stream rendered on the device, played in a cycle" % NF,
                        "warp_batch": ss.WB, "zero_copy": bool(args.zero_copy),
                        "timed_frames_per_region_per_rank": [int(r[1]) for r in per_rank], "timed_regions": args.regions, "build": vs.lib.vs_build_tag().decode()},
-            "regions": {"count": args.regions, "value": "median", "frames_per_s": [round(total_frames / e, 1) for e in elapsed]},
+            "regions": {"count": args.regions, "steps_per_region": per_region, "value": "median", "frames_per_s": [round(total_frames / e, 1) for e in elapsed]},
             "roofline": roof,
             "whole_step": {"bytes_per_frame": round(whole_bytes), "achieved": round(whole, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                            "frac": round(whole / HBM_PEAK_GBPS, 4),
@@ -713,6 +765,8 @@ def main():
         }
         if fanout is not None:
             out["fanout"] = fanout
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.profile_stages:
             names = ["copy_in", "gray", "pyramid", "lk", "ransac", "traj", "gftt", "warp", "warp_tables"]
             out["stage_us_per_launch"] = {names[k]: round(stage_ms[k] / max(stage_n[k], 1) * 1e3, 2) for k in range(capi.STAGE_COUNT)}

@@ -51,7 +51,7 @@ def test_rccl_collectives_on_device_tensors(gpu, tmp_path):
 
 
 def test_bench_step_through_the_rccl_communicator(gpu):
-    r = _run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--regions", "2", "--clip-frames", "16",
+    r = _run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--regions", "2", "--clip-frames", "16",
               "--no-extras", "--no-cpu-baseline"])
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
