@@ -27,9 +27,6 @@
 
 namespace vsd {
 
-int launch_warp_affine_inv(const uint8_t* d_src, size_t sstride, int sw, int sh, uint8_t* d_dst, size_t dstride,
-                           int dw, int dh, int cn, const double* h_Minv, int border, hipStream_t st);
-
 namespace {
 
 typedef unsigned long long u64;
@@ -398,7 +395,8 @@ static int azc_emit(vs_azc* a, const void* d_data, int w, int h, size_t stride, 
     double Mi[6];
     warp_invert(Mf, Mi);
     const uint8_t* roi = (const uint8_t*)d_data + (size_t)cy * stride + (size_t)cx * cn;
-    A_TRY(a, launch_warp_affine_inv(roi, stride, cw, ch, (uint8_t*)d_out, out_stride, 640, 360, cn, Mi, VS_BORDER_BLACK, a->st));
+    uint8_t* out = (uint8_t*)d_out;
+    A_TRY(a, launch_warp_plane(&roi, &out, 1, stride, cw, ch, out_stride, 640, 360, cn, WarpMaps{Mi, 6, true}, VS_BORDER_BLACK, WarpTabs{}, a->st));
     return VS_OK;
 }
 

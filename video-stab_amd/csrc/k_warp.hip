@@ -44,7 +44,7 @@ constexpr int PX = 4;        // consecutive output pixels per lane
 constexpr int NT = 256;      // threads per workgroup
 constexpr int TXN = TW / PX; // 32 lanes along x
 constexpr int TYN = NT / TXN;// 8 lane-rows
-constexpr int MAXB = 32;     // frames per launch (frame pointers and, for host matrices, the maps travel as kernel arguments)
+constexpr int MAXB = WARP_BATCH_MAX;   // frames per launch (frame pointers and, for host matrices, the maps travel as kernel arguments)
 // fast path (near-identity maps): the source box of a tile is staged with a FIXED row pitch, so
 // the lower taps sit at an immediate offset and the tap address is one multiply-add
 constexpr int FDATA = 136;   // staged pixels of a row (128 + tap + shear + 12-byte alignment slack)
@@ -67,14 +67,10 @@ struct WarpCore {                // what the staging and output code needs of a 
 };
 
 struct WarpArgs {
-    const uint8_t* src;
-    uint8_t* dst;
-    size_t sframe, dframe;
     WarpCore c;
     const double* Minv_dev;      // inverse maps on the device (minv_stride doubles apart), or nullptr
     double Minv_val[MAXB * 6];   // used when Minv_dev == nullptr
     int minv_stride;             // doubles between the maps of consecutive frames in Minv_dev
-    int use_list;                // frames given one by one (srcs/dsts) instead of base + k*frame
     int32_t* tabs;               // coordinate tables of the frames of this launch (warp_tables_kernel), or nullptr
     int tab_stride;              // ints between the tables of consecutive frames
     int tab_row, tab_ad;         // offsets inside a frame's table (TabLayout)
@@ -380,8 +376,7 @@ __global__ __launch_bounds__(NT) void warp_tables_kernel(WarpArgs a) {
     L.row = a.tab_row; L.ad = a.tab_ad; L.stride = a.tab_stride;
     const int j = blockIdx.x * NT + threadIdx.x;
     if (j < wt_entries(a.c.dw, a.c.dh))
-        wt_build_entry(a.tabs + (size_t)bz * a.tab_stride, L, m, a.c.dw, a.c.dh, a.use_list ? a.srcs[bz] : a.src + (size_t)bz * a.sframe,
-                       a.use_list ? a.dsts[bz] : a.dst + (size_t)bz * a.dframe, j);
+        wt_build_entry(a.tabs + (size_t)bz * a.tab_stride, L, m, a.c.dw, a.c.dh, a.srcs[bz], a.dsts[bz], j);
 }
 
 // The table blocks of up to NVT_MAX NV12 surfaces, both planes, from inverse maps given on the host, in ONE launch
@@ -418,8 +413,8 @@ __global__ __launch_bounds__(NT) void warp_affine_kernel(WarpArgs a) {
     __shared__ int s_ad[TW], s_bd[TW], s_x0[TH], s_y0[TH];
     __shared__ __attribute__((aligned(16))) uint8_t lut[CN == 3 ? 32 * LUT_STRIDE : 16];
     const int bz = blockIdx.z;
-    const uint8_t* __restrict__ src = a.use_list ? a.srcs[bz] : a.src + (size_t)bz * a.sframe;
-    uint8_t* __restrict__ dst = a.use_list ? a.dsts[bz] : a.dst + (size_t)bz * a.dframe;
+    const uint8_t* __restrict__ src = a.srcs[bz];
+    uint8_t* __restrict__ dst = a.dsts[bz];
     const int tid = threadIdx.x, wave = tid >> 6;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     const int x1 = min(x0 + TW, a.c.dw) - 1, y1 = min(y0 + TH, a.c.dh) - 1;
@@ -1255,21 +1250,6 @@ void launch_cn(WarpArgs& a, dim3 grid, int cn, int32_t* d_tabs, hipStream_t st, 
     else launch_one<2>(a, grid, d_tabs, what, st, tab_stride);
 }
 
-void fill_common(WarpArgs& a, const uint8_t* d_src, size_t sstride, size_t sframe, int sw, int sh, uint8_t* d_dst,
-                 size_t dstride, size_t dframe, int dw, int dh, int cn) {
-    a.src = d_src; a.dst = d_dst;
-    a.c.sstride = sstride; a.sframe = sframe; a.c.dstride = dstride; a.dframe = dframe;
-    a.c.sw = sw; a.c.sh = sh; a.c.dw = dw; a.c.dh = dh;
-    a.c.border = VS_BORDER_BLACK;
-    a.minv_stride = 6;
-    a.use_list = 0;
-    a.tabs = nullptr; a.tab_stride = 0; a.tab_row = 0; a.tab_ad = 0;
-    for (int i = 0; i < MAXB; i++) { a.srcs[i] = nullptr; a.dsts[i] = nullptr; }
-    const int galign = cn == 2 ? 8 : 4;
-    a.c.src_aligned = ((uintptr_t)d_src % galign == 0) && (sstride % galign == 0) && (sframe % galign == 0);
-    a.c.dst_aligned = ((uintptr_t)d_dst % galign == 0) && (dstride % galign == 0) && (dframe % galign == 0);
-}
-
 bool bad_args(const void* d_src, const void* d_dst, const void* M, size_t sstride, int sw, int sh, size_t dstride,
               int dw, int dh, int cn, int batch) {
     return !d_src || !d_dst || !M || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || batch <= 0 ||
@@ -1277,8 +1257,18 @@ bool bad_args(const void* d_src, const void* d_dst, const void* M, size_t sstrid
            dh > 65535 * TH;
 }
 
-// Table scratch of the standalone operator (vs_op_warp_affine): one grow-only device buffer per stream.  Launches on
-// a stream run in order, so the tables of a call are consumed before the next call on that stream rewrites them.
+// Validation shared by the two launchers: the border, the table choice, and no null frame in the lists.
+bool bad_call(const uint8_t* const* srcs, uint8_t* const* dsts, int n, int border, const WarpTabs& tabs) {
+    if ((border != VS_BORDER_BLACK && border != VS_BORDER_REPLICATE) || (tabs.kind == WarpTabs::CALLER && !tabs.tabs) ||
+        (tabs.kind != WarpTabs::CALLER && tabs.what != VS_WARP_ALL))
+        return true;
+    for (int i = 0; i < n; i++)
+        if (!srcs[i] || !dsts[i]) return true;
+    return false;
+}
+
+// Table scratch of the standalone operators (vs_op_warp_affine*, the roll correction): one grow-only device buffer per stream.
+// Launches on a stream run in order, so the tables of a call are consumed before the next call on that stream rewrites them.
 // (hipMallocAsync memory is not used: with it, in-flight builds of round 2 read zeroed tables for the later frames of a launch
 // and faulted on the null source pointers; the cause was not established - DESIGN.md section 8 has the evidence.)
 struct OpScratch { int32_t* p = nullptr; size_t bytes = 0; };
@@ -1303,65 +1293,39 @@ int op_tabs(hipStream_t st, size_t bytes, int32_t** out) {
     return VS_OK;
 }
 
-}  // namespace
+// The maps of the frames from the k-th on.
+WarpMaps maps_from(WarpMaps m, int k) { m.m += (size_t)m.stride * k; return m; }
 
-// Ints of workspace the table form of a launch over `frames` frames of dw x dh needs (d_tabs of the launchers).
-size_t warp_tabs_ints(int dw, int dh, int frames) { return (size_t)tab_stride_of(dw, dh) * (size_t)(frames > 0 ? frames : 1); }
-
-int launch_warp_affine(const uint8_t* d_src, size_t sstride, size_t sframe, int sw, int sh,
-                       uint8_t* d_dst, size_t dstride, size_t dframe, int dw, int dh, int cn,
-                       const double* d_Minv, int batch, int32_t* d_tabs, hipStream_t st) {
-    if (bad_args(d_src, d_dst, d_Minv, sstride, sw, sh, dstride, dw, dh, cn, batch) || batch > 65535) {
-        set_last_error("warp_affine: invalid argument");
-        return VS_ERR_INVALID_ARG;
-    }
+// ONE launch over n <= MAXB frames of one plane.  d_tabs: the launch's tables (tab_stride ints apart, 0 = packed), or nullptr.
+int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw, int dh,
+                 int cn, WarpMaps maps, int border, int32_t* d_tabs, int tab_stride, int what, hipStream_t st) {
     WarpArgs a;
-    fill_common(a, d_src, sstride, sframe, sw, sh, d_dst, dstride, dframe, dw, dh, cn);
-    a.Minv_dev = d_Minv;
-    dim3 grid((dw + TW - 1) / TW, (dh + TH - 1) / TH, batch);
-    launch_cn(a, grid, cn, d_tabs, st);
-    VS_HIP_TRY(hipGetLastError());
-    return VS_OK;
-}
-
-// Frames given one by one (deferred output of a stream: each result goes to its caller's buffer);
-// all share one geometry.  d_Minv: inverse maps on the device, minv_stride doubles apart.
-int launch_warp_affine_list(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh,
-                            size_t dstride, int dw, int dh, int cn, const double* d_Minv, int minv_stride, int32_t* d_tabs,
-                            hipStream_t st, int what, int tab_stride) {
-    if ((what != VS_WARP_ALL && !d_tabs) || n < 1 || n > MAXB || !srcs || !dsts || bad_args(srcs[0], dsts[0], d_Minv, sstride, sw, sh, dstride, dw, dh, cn, n)) {
-        set_last_error("warp_affine_list: invalid argument");
-        return VS_ERR_INVALID_ARG;
-    }
-    WarpArgs a;
-    fill_common(a, srcs[0], sstride, 0, sw, sh, dsts[0], dstride, 0, dw, dh, cn);
+    a.c.sstride = sstride; a.c.dstride = dstride;
+    a.c.sw = sw; a.c.sh = sh; a.c.dw = dw; a.c.dh = dh;
+    a.c.border = border;
     const int galign = cn == 2 ? 8 : 4;
+    a.c.src_aligned = sstride % galign == 0;
+    a.c.dst_aligned = dstride % galign == 0;
     for (int i = 0; i < MAXB; i++) {
         a.srcs[i] = srcs[i < n ? i : 0]; a.dsts[i] = dsts[i < n ? i : 0];
-        if (!a.srcs[i] || !a.dsts[i]) { set_last_error("warp_affine_list: null frame"); return VS_ERR_INVALID_ARG; }
         if ((uintptr_t)a.srcs[i] % galign) a.c.src_aligned = 0;
         if ((uintptr_t)a.dsts[i] % galign) a.c.dst_aligned = 0;
     }
-    a.use_list = 1;
-    a.Minv_dev = d_Minv;
-    a.minv_stride = minv_stride;
+    a.Minv_dev = maps.host ? nullptr : maps.m;
+    a.minv_stride = maps.stride;
+    for (int b = 0; b < MAXB; b++)
+        for (int i = 0; i < 6; i++) a.Minv_val[6 * b + i] = maps.host && b < n ? maps.m[(size_t)maps.stride * b + i] : 0.;
     dim3 grid((dw + TW - 1) / TW, (dh + TH - 1) / TH, n);
     launch_cn(a, grid, cn, d_tabs, st, what, tab_stride);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }
 
-// NV12 surfaces of one geometry and pitch, luma and chroma planes in ONE launch (warp_nv12_kernel).  ys / yd: the surfaces (luma
-// plane first), the interleaved chroma plane src_uv / dst_uv bytes behind them.  d_tabs: the frames' table blocks (warp_tab.h:
-// luma table, then chroma table; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT (the release workgroups of the batch tail,
-// or launch_warp_affine_list(.., VS_WARP_TABLES_ONLY, nv12_tab_ints) per plane).  Returns VS_ERR_UNSUPPORTED when the geometry
-// is outside what the kernel packs (the caller then launches the planes one by one).
-int launch_warp_nv12_list(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstride, size_t dstride, int w, int h, size_t src_uv,
-                          size_t dst_uv, const int32_t* d_tabs, hipStream_t st, int border) {
-    if (!ys || !yd || !d_tabs || n < 1 || w < 2 || h < 2 || (w & 1) || (h & 1) || (border != VS_BORDER_BLACK && border != VS_BORDER_REPLICATE)) {
-        set_last_error("warp_nv12_list: invalid argument");
-        return VS_ERR_INVALID_ARG;
-    }
+// NV12 surfaces of one geometry and pitch, luma and chroma planes in ONE launch (warp_nv12_kernel), from the frames' table blocks
+// (warp_tab.h: luma table, then chroma table; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  The chroma planes lie src_uv /
+// dst_uv bytes behind the luma planes.  Returns VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
+int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstride, size_t dstride, int w, int h, size_t src_uv,
+                size_t dst_uv, const int32_t* d_tabs, int border, hipStream_t st) {
     typedef PlaneCfg<1> P1;
     typedef PlaneCfg<2> P2;
     const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + P1::THP - 1) / P1::THP, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + P2::THP - 1) / P2::THP;
@@ -1374,7 +1338,6 @@ int launch_warp_nv12_list(const uint8_t* const* ys, uint8_t* const* yd, int n, s
     if (sstride % 8 || src_uv % 8) al &= ~4u;
     if (dstride % 8 || dst_uv % 8) al &= ~8u;
     for (int i = 0; i < n; i++) {
-        if (!ys[i] || !yd[i]) { set_last_error("warp_nv12_list: null frame"); return VS_ERR_INVALID_ARG; }
         if ((uintptr_t)ys[i] % 4) al &= ~1u;
         if ((uintptr_t)yd[i] % 4) al &= ~2u;
         if ((uintptr_t)ys[i] % 8) al &= ~4u;
@@ -1393,183 +1356,84 @@ int launch_warp_nv12_list(const uint8_t* const* ys, uint8_t* const* yd, int n, s
     return VS_OK;
 }
 
-// Host-matrix form used by vs_op_warp_affine: matrices travel as kernel
-// arguments (MAXB per launch), so no staging buffer or sync is needed.
-int launch_warp_affine_hostM(const uint8_t* d_src, size_t sstride, size_t sframe, int sw, int sh,
-                             uint8_t* d_dst, size_t dstride, size_t dframe, int dw, int dh, int cn,
-                             const float* h_M, int batch, hipStream_t st) {
-    if (bad_args(d_src, d_dst, h_M, sstride, sw, sh, dstride, dw, dh, cn, batch)) {
+}  // namespace
+
+// Ints of workspace the table form of a launch over `frames` frames of dw x dh needs (d_tabs of the launchers).
+size_t warp_tabs_ints(int dw, int dh, int frames) { return (size_t)tab_stride_of(dw, dh) * (size_t)(frames > 0 ? frames : 1); }
+
+int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw,
+                      int dh, int cn, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st) {
+    if (n < 1 || !srcs || !dsts || bad_args(srcs[0], dsts[0], maps.m, sstride, sw, sh, dstride, dw, dh, cn, n) ||
+        bad_call(srcs, dsts, n, border, tabs)) {
         set_last_error("warp_affine: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
-    // coordinate tables for launches of several frames
-    int32_t* d_tabs = nullptr;
-    if (batch >= 4) VS_TRY(op_tabs(st, warp_tabs_ints(dw, dh, batch < MAXB ? batch : MAXB) * sizeof(int32_t), &d_tabs));
-    for (int b0 = 0; b0 < batch; b0 += MAXB) {
-        const int nb = batch - b0 < MAXB ? batch - b0 : MAXB;
-        WarpArgs a;
-        fill_common(a, d_src + (size_t)b0 * sframe, sstride, sframe, sw, sh, d_dst + (size_t)b0 * dframe, dstride,
-                    dframe, dw, dh, cn);
-        a.Minv_dev = nullptr;
-        for (int b = 0; b < MAXB; b++) {
-            if (b < nb) warp_invert(h_M + (size_t)(b0 + b) * 6, a.Minv_val + 6 * b);   // cv::warpAffine inverts on the host too
-            else for (int i = 0; i < 6; i++) a.Minv_val[6 * b + i] = 0.;
-        }
-        dim3 grid((dw + TW - 1) / TW, (dh + TH - 1) / TH, nb);
-        launch_cn(a, grid, cn, d_tabs, st);
-        VS_HIP_TRY(hipGetLastError());
+    if (tabs.kind == WarpTabs::SCRATCH && n >= WARP_TAB_MIN)
+        VS_TRY(op_tabs(st, warp_tabs_ints(dw, dh, std::min(n, MAXB)) * sizeof(int32_t), &tabs.tabs));
+    // the caller's buffer holds the tables of all frames, the scratch those of one launch
+    const size_t tab_step = tabs.kind != WarpTabs::CALLER ? 0 : tabs.stride > 0 ? (size_t)tabs.stride : (size_t)tab_stride_of(dw, dh);
+    for (int b0 = 0; b0 < n; b0 += MAXB) {
+        const int nb = std::min(MAXB, n - b0);
+        int32_t* T = tabs.kind != WarpTabs::NONE && nb >= WARP_TAB_MIN ? tabs.tabs + b0 * tab_step : nullptr;
+        if (!T && tabs.what == VS_WARP_TABLES_ONLY) continue;
+        VS_TRY(plane_launch(srcs + b0, dsts + b0, nb, sstride, sw, sh, dstride, dw, dh, cn, maps_from(maps, b0), border, T, tabs.stride,
+                            T ? tabs.what : VS_WARP_ALL, st));
     }
     return VS_OK;
 }
 
-// NV12 surfaces (luma plane, interleaved chroma plane h * pitch behind it), host matrices: launches of four and more frames build
-// both planes' tables (chroma: the map with the halved translation) and warp them in ONE grid; fewer frames go plane by plane.
-int launch_warp_nv12_hostM(const uint8_t* d_src, size_t sstride, size_t sframe, uint8_t* d_dst, size_t dstride, size_t dframe, int w, int h,
-                           const float* h_M, int batch, hipStream_t st) {
-    if (!d_src || !d_dst || !h_M || w < 2 || h < 2 || (w & 1) || (h & 1) || batch <= 0 || sstride < (size_t)w || dstride < (size_t)w) {
-        set_last_error("warp_affine_nv12: invalid argument (w and h must be even)");
+// Per launch: the tables of both planes (host maps: one launch for up to NVT_MAX surfaces; else one per plane), then both planes in
+// ONE grid; plane by plane when the launch has no tables, when the chroma planes do not all lie one offset behind the luma planes
+// (the one-launch kernel and the table launch take one offset), or when the geometry is outside what the one-launch kernel packs.
+int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t* const* us, uint8_t* const* ud, int n, size_t sstride,
+                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st) {
+    if (n < 1 || !ys || !yd || !us || !ud || w < 2 || h < 2 || (w & 1) || (h & 1) ||
+        bad_args(ys[0], yd[0], maps.m, sstride, w, h, dstride, w, h, 1, n) || bad_call(ys, yd, n, border, tabs) ||
+        bad_call(us, ud, n, border, tabs)) {
+        set_last_error("warp_nv12: invalid argument (w and h must be even)");
         return VS_ERR_INVALID_ARG;
     }
-    std::vector<float> Mc((size_t)batch * 6);
-    for (int b = 0; b < batch; b++) {
-        const float* m = h_M + 6 * b;
-        float* c = &Mc[6 * (size_t)b];
-        c[0] = m[0]; c[1] = m[1]; c[2] = m[2] * 0.5f;
-        c[3] = m[3]; c[4] = m[4]; c[5] = m[5] * 0.5f;
-    }
-    const size_t suv = (size_t)h * sstride, duv = (size_t)h * dstride;
     const int block = nv12_tab_ints(w, h), sy = tab_layout(w, h).stride;
-    for (int b0 = 0; b0 < batch; b0 += MAXB) {
-        const int nb = std::min(MAXB, batch - b0);
-        int one = VS_ERR_UNSUPPORTED;
-        if (nb >= 4) {
-            int32_t* d_tabs = nullptr;
-            VS_TRY(op_tabs(st, (size_t)block * nb * sizeof(int32_t), &d_tabs));
-            const uint8_t* ys[MAXB];
-            uint8_t* yd[MAXB];
-            for (int plane = 0; plane < 2; plane++) {
-                WarpArgs a;
-                fill_common(a, d_src + (size_t)b0 * sframe + (plane ? suv : 0), sstride, sframe, plane ? w / 2 : w, plane ? h / 2 : h,
-                            d_dst + (size_t)b0 * dframe + (plane ? duv : 0), dstride, dframe, plane ? w / 2 : w, plane ? h / 2 : h, plane ? 2 : 1);
-                a.Minv_dev = nullptr;
-                const float* Ms = plane ? Mc.data() : h_M;
-                for (int b = 0; b < MAXB; b++) {
-                    if (b < nb) warp_invert(Ms + (size_t)(b0 + b) * 6, a.Minv_val + 6 * b);
-                    else for (int i = 0; i < 6; i++) a.Minv_val[6 * b + i] = 0.;
+    if (tabs.kind == WarpTabs::SCRATCH && n >= WARP_TAB_MIN)
+        VS_TRY(op_tabs(st, (size_t)block * std::min(n, MAXB) * sizeof(int32_t), &tabs.tabs));
+    const WarpMaps muv = {maps.m + 6, maps.stride, maps.host};
+    const size_t tab_step = tabs.kind == WarpTabs::CALLER ? block : 0;
+    for (int b0 = 0; b0 < n; b0 += MAXB) {
+        const int nb = std::min(MAXB, n - b0);
+        int32_t* T = tabs.kind != WarpTabs::NONE && nb >= WARP_TAB_MIN ? tabs.tabs + b0 * tab_step : nullptr;
+        if (!T && tabs.what == VS_WARP_TABLES_ONLY) continue;
+        const WarpMaps my = maps_from(maps, b0), mu = maps_from(muv, b0);
+        const size_t src_uv = (uintptr_t)us[b0] - (uintptr_t)ys[b0], dst_uv = (uintptr_t)ud[b0] - (uintptr_t)yd[b0];
+        bool one_uv = true;
+        for (int i = b0; i < b0 + nb; i++)
+            one_uv &= (uintptr_t)us[i] - (uintptr_t)ys[i] == src_uv && (uintptr_t)ud[i] - (uintptr_t)yd[i] == dst_uv;
+        if (T && tabs.what != VS_WARP_ONLY) {
+            if (maps.host && nb <= NVT_MAX && one_uv) {
+                NvTabArgs t;
+                t.tabs = T; t.block = block; t.chroma = sy; t.w = w; t.h = h; t.src_uv = src_uv; t.dst_uv = dst_uv;
+                for (int i = 0; i < NVT_MAX; i++) { t.ys[i] = ys[b0 + (i < nb ? i : 0)]; t.yd[i] = yd[b0 + (i < nb ? i : 0)]; }
+                for (int i = 0; i < NVT_MAX * 6; i++) {
+                    t.my[i] = i < 6 * nb ? my.m[(size_t)my.stride * (i / 6) + i % 6] : 0.;
+                    t.muv[i] = i < 6 * nb ? mu.m[(size_t)mu.stride * (i / 6) + i % 6] : 0.;
                 }
-                dim3 grid((a.c.dw + TW - 1) / TW, (a.c.dh + TH - 1) / TH, nb);
-                launch_cn(a, grid, plane ? 2 : 1, d_tabs + (plane ? sy : 0), st, VS_WARP_TABLES_ONLY, block);
+                const int entries = w + h + (w + TW - 1) / TW + (h + TH - 1) / TH;
+                hipLaunchKernelGGL(warp_tables_nv12_kernel, dim3((entries + NT - 1) / NT, nb, 2), dim3(NT), 0, st, t);
+            } else {
+                VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, VS_WARP_TABLES_ONLY, st));
+                VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T + sy, block,
+                                    VS_WARP_TABLES_ONLY, st));
             }
-            for (int b = 0; b < nb; b++) { ys[b] = d_src + (size_t)(b0 + b) * sframe; yd[b] = d_dst + (size_t)(b0 + b) * dframe; }
-            one = launch_warp_nv12_list(ys, yd, nb, sstride, dstride, w, h, suv, duv, d_tabs, st);
-            if (one != VS_OK && one != VS_ERR_UNSUPPORTED) return one;
         }
-        if (one == VS_ERR_UNSUPPORTED) {
-            VS_TRY(launch_warp_affine_hostM(d_src + (size_t)b0 * sframe, sstride, sframe, w, h, d_dst + (size_t)b0 * dframe, dstride, dframe, w, h, 1,
-                                            h_M + (size_t)b0 * 6, nb, st));
-            VS_TRY(launch_warp_affine_hostM(d_src + (size_t)b0 * sframe + suv, sstride, sframe, w / 2, h / 2, d_dst + (size_t)b0 * dframe + duv, dstride,
-                                            dframe, w / 2, h / 2, 2, Mc.data() + (size_t)b0 * 6, nb, st));
+        if (tabs.what == VS_WARP_TABLES_ONLY) continue;
+        const int one = T && one_uv ? nv12_launch(ys + b0, yd + b0, nb, sstride, dstride, w, h, src_uv, dst_uv, T, border, st) : VS_ERR_UNSUPPORTED;
+        if (one != VS_ERR_UNSUPPORTED) {
+            VS_TRY(one);
+            continue;
         }
+        const int what = T ? VS_WARP_ONLY : VS_WARP_ALL;
+        VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, what, st));
+        VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T ? T + sy : nullptr, block, what, st));
     }
-    VS_HIP_TRY(hipGetLastError());
-    return VS_OK;
-}
-
-// Frames given one by one, inverse maps given on the host in double (6 per frame), selectable border: the rotations of a batch
-// of roll-corrected frames (cv::warpAffine(..., BORDER_REPLICATE), RollCorrection.cpp:146-149) as ONE launch per plane.  Four
-// frames and more take the coordinate tables (scratch of the stream, op_tabs).
-int launch_warp_affine_list_inv(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw, int dh,
-                                int cn, const double* h_Minv, int border, hipStream_t st) {
-    if (n < 1 || n > MAXB || !srcs || !dsts || bad_args(srcs[0], dsts[0], h_Minv, sstride, sw, sh, dstride, dw, dh, cn, n) ||
-        (border != VS_BORDER_BLACK && border != VS_BORDER_REPLICATE)) {
-        set_last_error("warp_affine_list_inv: invalid argument");
-        return VS_ERR_INVALID_ARG;
-    }
-    WarpArgs a;
-    fill_common(a, srcs[0], sstride, 0, sw, sh, dsts[0], dstride, 0, dw, dh, cn);
-    const int galign = cn == 2 ? 8 : 4;
-    for (int i = 0; i < MAXB; i++) {
-        a.srcs[i] = srcs[i < n ? i : 0]; a.dsts[i] = dsts[i < n ? i : 0];
-        if (!a.srcs[i] || !a.dsts[i]) { set_last_error("warp_affine_list_inv: null frame"); return VS_ERR_INVALID_ARG; }
-        if ((uintptr_t)a.srcs[i] % galign) a.c.src_aligned = 0;
-        if ((uintptr_t)a.dsts[i] % galign) a.c.dst_aligned = 0;
-    }
-    a.use_list = 1;
-    a.Minv_dev = nullptr;
-    a.c.border = border;
-    for (int i = 0; i < MAXB * 6; i++) a.Minv_val[i] = i < 6 * n ? h_Minv[i] : 0.;
-    int32_t* d_tabs = nullptr;
-    if (n >= 4) VS_TRY(op_tabs(st, warp_tabs_ints(dw, dh, n) * sizeof(int32_t), &d_tabs));
-    dim3 grid((dw + TW - 1) / TW, (dh + TH - 1) / TH, n);
-    launch_cn(a, grid, cn, d_tabs, st);
-    VS_HIP_TRY(hipGetLastError());
-    return VS_OK;
-}
-
-// NV12 surfaces given one by one, inverse maps of both planes given on the host (6 doubles per frame and plane), selectable
-// border: four and more surfaces build their table blocks with one launch (more than 16: one per plane) and are warped in ONE
-// grid (the rotations of a batch of roll-corrected surfaces); fewer go plane by plane.
-int launch_warp_nv12_list_inv(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstride, size_t dstride, int w, int h, size_t src_uv,
-                              size_t dst_uv, const double* h_MinvY, const double* h_MinvUV, int border, hipStream_t st) {
-    if (n < 1 || n > MAXB || !ys || !yd || !h_MinvY || !h_MinvUV) { set_last_error("warp_nv12_list_inv: invalid argument"); return VS_ERR_INVALID_ARG; }
-    const uint8_t* us[MAXB];
-    uint8_t* ud[MAXB];
-    for (int i = 0; i < n; i++) {
-        if (!ys[i] || !yd[i]) { set_last_error("warp_nv12_list_inv: null frame"); return VS_ERR_INVALID_ARG; }
-        us[i] = ys[i] + src_uv; ud[i] = yd[i] + dst_uv;
-    }
-    int one = VS_ERR_UNSUPPORTED;
-    if (n >= 4) {
-        const int block = nv12_tab_ints(w, h), sy = tab_layout(w, h).stride;
-        int32_t* d_tabs = nullptr;
-        VS_TRY(op_tabs(st, (size_t)block * n * sizeof(int32_t), &d_tabs));
-        if (n <= NVT_MAX) {       // both planes' tables of every surface with one launch
-            NvTabArgs t;
-            t.tabs = d_tabs; t.block = block; t.chroma = sy; t.w = w; t.h = h; t.src_uv = src_uv; t.dst_uv = dst_uv;
-            for (int i = 0; i < NVT_MAX; i++) { t.ys[i] = ys[i < n ? i : 0]; t.yd[i] = yd[i < n ? i : 0]; }
-            for (int i = 0; i < NVT_MAX * 6; i++) { t.my[i] = i < 6 * n ? h_MinvY[i] : 0.; t.muv[i] = i < 6 * n ? h_MinvUV[i] : 0.; }
-            const int entries = w + h + (w + TW - 1) / TW + (h + TH - 1) / TH;
-            hipLaunchKernelGGL(warp_tables_nv12_kernel, dim3((entries + NT - 1) / NT, n, 2), dim3(NT), 0, st, t);
-        } else for (int plane = 0; plane < 2; plane++) {
-            WarpArgs a;
-            const int pw = plane ? w / 2 : w, ph = plane ? h / 2 : h;
-            fill_common(a, plane ? us[0] : ys[0], sstride, 0, pw, ph, plane ? ud[0] : yd[0], dstride, 0, pw, ph, plane ? 2 : 1);
-            for (int i = 0; i < MAXB; i++) { a.srcs[i] = plane ? us[i < n ? i : 0] : ys[i < n ? i : 0]; a.dsts[i] = plane ? ud[i < n ? i : 0] : yd[i < n ? i : 0]; }
-            a.use_list = 1;
-            a.Minv_dev = nullptr;
-            a.c.border = border;
-            const double* Mi = plane ? h_MinvUV : h_MinvY;
-            for (int i = 0; i < MAXB * 6; i++) a.Minv_val[i] = i < 6 * n ? Mi[i] : 0.;
-            dim3 grid((pw + TW - 1) / TW, (ph + TH - 1) / TH, n);
-            launch_cn(a, grid, plane ? 2 : 1, d_tabs + (plane ? sy : 0), st, VS_WARP_TABLES_ONLY, block);
-        }
-        one = launch_warp_nv12_list(ys, yd, n, sstride, dstride, w, h, src_uv, dst_uv, d_tabs, st, border);
-        if (one != VS_OK && one != VS_ERR_UNSUPPORTED) return one;
-    }
-    if (one == VS_ERR_UNSUPPORTED) {
-        VS_TRY(launch_warp_affine_list_inv(ys, yd, n, sstride, w, h, dstride, w, h, 1, h_MinvY, border, st));
-        VS_TRY(launch_warp_affine_list_inv(us, ud, n, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, h_MinvUV, border, st));
-    }
-    VS_HIP_TRY(hipGetLastError());
-    return VS_OK;
-}
-
-// One frame, inverse map given on the host in double, selectable border: used by the
-// roll-correction rotate (cv::warpAffine(..., BORDER_REPLICATE)) and AutoZoomCrop's scale.
-int launch_warp_affine_inv(const uint8_t* d_src, size_t sstride, int sw, int sh, uint8_t* d_dst, size_t dstride,
-                           int dw, int dh, int cn, const double* h_Minv, int border, hipStream_t st) {
-    if (bad_args(d_src, d_dst, h_Minv, sstride, sw, sh, dstride, dw, dh, cn, 1) ||
-        (border != VS_BORDER_BLACK && border != VS_BORDER_REPLICATE)) {
-        set_last_error("warp_affine: invalid argument");
-        return VS_ERR_INVALID_ARG;
-    }
-    WarpArgs a;
-    fill_common(a, d_src, sstride, 0, sw, sh, d_dst, dstride, 0, dw, dh, cn);
-    a.Minv_dev = nullptr;
-    a.c.border = border;
-    for (int i = 0; i < MAXB * 6; i++) a.Minv_val[i] = i < 6 ? h_Minv[i] : 0.;
-    dim3 grid((dw + TW - 1) / TW, (dh + TH - 1) / TH, 1);
-    launch_cn(a, grid, cn, nullptr, st);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }

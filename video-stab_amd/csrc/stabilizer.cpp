@@ -95,7 +95,6 @@ constexpr int FRAME_RING = 128;     // <= 35 queued frames (clamp(smoothingRadiu
 constexpr int FRAME_RING_MAX = 192; // the same for batches of more than 32 frames (s->ring_frames)
 constexpr int MAX_PYR = 8;
 constexpr int NPYR = 3;             // pyramid buffers: frame k writes k%3 while LK(k-1) still reads (k-1)%3,(k-2)%3
-constexpr int WARP_BATCH_MAX = 32;   // = the warp kernel's frames per launch (k_warp.hip MAXB)
 constexpr int BATCH_MAX = 64;        // frames analysed per launch in batch mode (vs_stab_set_batch)
 constexpr int EVR = 4;              // per-frame event ring
 
@@ -674,8 +673,8 @@ int flush_warps(vs_stab* s, bool on_main) {
     int rc;
     {
         StageScope t(s, VS_STAGE_WARP, ws);
-        rc = launch_warp_affine_list(srcs, dsts, n, s->src_pitch, s->w, s->h, s->pend_stride, s->w, s->h, s->cn,
-                                     s->d_MinvB[set], 12, n >= 4 ? s->d_tabs_def : nullptr, ws);
+        rc = launch_warp_plane(srcs, dsts, n, s->src_pitch, s->w, s->h, s->pend_stride, s->w, s->h, s->cn, WarpMaps{s->d_MinvB[set], 12, false},
+                               VS_BORDER_BLACK, WarpTabs{WarpTabs::CALLER, s->d_tabs_def}, ws);
     }
     if (hipEventRecord(s->ev_warp[set], ws) == hipSuccess) s->warp_valid[set] = true;
     for (int i = 0; i < n; i++) {
@@ -708,6 +707,11 @@ int defer_output(vs_stab* s, int idx, const uint8_t* frame, uint8_t* d_out, size
     s->pend_stride = out_stride;
     if ((int)s->pend.size() >= s->warp_batch) S_TRY(s, flush_warps(s));
     return VS_OK;
+}
+
+// One frame of the stream's channels by its current map (d_Minv), w x h in and out
+int warp_frame(const vs_stab* s, const uint8_t* src, size_t sstride, int w, int h, uint8_t* dst, size_t dstride, hipStream_t st) {
+    return launch_warp_plane(&src, &dst, 1, sstride, w, h, dstride, w, h, s->cn, WarpMaps{s->d_Minv, 6, false}, VS_BORDER_BLACK, WarpTabs{}, st);
 }
 
 // applyNextSmoothTransform (Stabilizer.cpp:763-1137) into d_out (device), on `main`
@@ -749,11 +753,10 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         rc = canvas_apply(s->canvas, p, frame, s->src_pitch, s->w, s->h, s->d_ct, s->d_traj, d_out, out_stride, st);
     } else if (s->fmt == VS_FMT_NV12) {
         StageScope t(s, VS_STAGE_WARP, st);
-        rc = launch_warp_affine(frame, s->src_pitch, 0, s->w, s->h, d_out, out_stride, 0, s->w, s->h, 1, s->d_Minv, 1, nullptr, st);
-        if (rc == VS_OK)
-            rc = launch_warp_affine(frame + src_uv(s), s->src_pitch, 0, s->w / 2, s->h / 2,
-                                    d_out + dst_uv(s, d_out, out_stride), out_stride, 0, s->w / 2, s->h / 2, 2,
-                                    s->d_Minv + 6, 1, nullptr, st);
+        const uint8_t* uv = frame + src_uv(s);
+        uint8_t* out_uv = d_out + dst_uv(s, d_out, out_stride);
+        rc = launch_warp_nv12(&frame, &d_out, &uv, &out_uv, 1, s->src_pitch, out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
+                              VS_BORDER_BLACK, WarpTabs{}, st);
     } else if (p.border_size > 0 && !p.crop_n_zoom && p.border_type == VS_BORDER_FADE) {     // :914-978, :1069-1106
         const int b = p.border_size, bw = s->w + 2 * b, bh = s->h + 2 * b;
         const size_t prow = (size_t)bw * s->cn, nb = prow * bh;
@@ -775,7 +778,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         if (rc == VS_OK) rc = launch_fade_blend(s->d_fade, s->d_tmp, (nb + 3) & ~(size_t)3, alpha, 1.0f - alpha, st);
         {
             StageScope t(s, VS_STAGE_WARP, st);
-            if (rc == VS_OK) rc = launch_warp_affine(s->d_tmp, prow, 0, bw, bh, d_out, out_stride, 0, bw, bh, s->cn, s->d_Minv, 1, nullptr, st);
+            if (rc == VS_OK) rc = warp_frame(s, s->d_tmp, prow, bw, bh, d_out, out_stride, st);
         }
         if (rc == VS_OK) rc = launch_fade_update(s->d_fade, d_out, out_stride, (int)prow, bh, st);
     } else if (p.border_size > 0 && !p.crop_n_zoom) {                                 // :981-990
@@ -783,17 +786,17 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         rc = launch_make_border(frame, s->src_pitch, s->w, s->h, s->cn, s->d_tmp, (size_t)bw * s->cn, b, p.border_type, st);
         StageScope t(s, VS_STAGE_WARP, st);
         if (rc == VS_OK)
-            rc = launch_warp_affine(s->d_tmp, (size_t)bw * s->cn, 0, bw, bh, d_out, out_stride, 0, bw, bh, s->cn, s->d_Minv, 1, nullptr, st);
+            rc = warp_frame(s, s->d_tmp, (size_t)bw * s->cn, bw, bh, d_out, out_stride, st);
     } else if (p.crop_n_zoom && p.border_size > 0 && s->w - 2 * p.border_size > 0 && s->h - 2 * p.border_size > 0) {  // :1108-1124
         const int b = p.border_size;
         StageScope t(s, VS_STAGE_WARP, st);
-        rc = launch_warp_affine(frame, s->src_pitch, 0, s->w, s->h, s->d_tmp, s->row_bytes, 0, s->w, s->h, s->cn, s->d_Minv, 1, nullptr, st);
+        rc = warp_frame(s, frame, s->src_pitch, s->w, s->h, s->d_tmp, s->row_bytes, st);
         if (rc == VS_OK)
             rc = launch_resize_linear(s->d_tmp + ((size_t)b * s->w + b) * s->cn, s->row_bytes, s->w - 2 * b, s->h - 2 * b,
                                       s->cn, d_out, out_stride, s->orig_w, s->orig_h, st);
     } else {                                                                          // :1056-1060
         StageScope t(s, VS_STAGE_WARP, st);
-        rc = launch_warp_affine(frame, s->src_pitch, 0, s->w, s->h, d_out, out_stride, 0, s->w, s->h, s->cn, s->d_Minv, 1, nullptr, st);
+        rc = warp_frame(s, frame, s->src_pitch, s->w, s->h, d_out, out_stride, st);
     }
     // the slot may be overwritten once this warp has read it
     if (slot >= 0) {
@@ -1640,12 +1643,9 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
     const int pw = pad ? s0->w + 2 * bsz : s0->w, ph = pad ? s0->h + 2 * bsz : s0->h;
     const size_t prow = (size_t)pw * s0->cn;
     int rc = VS_OK;
-    for (int i0 = 0; i0 < R.n && rc == VS_OK; i0 += WARP_BATCH_MAX) {      // the warp kernels take WARP_BATCH_MAX frames per launch
+    // (launch by launch: the pads of a launch's frames are queued right in front of it, their crops right behind it)
+    for (int i0 = 0; i0 < R.n && rc == VS_OK; i0 += WARP_BATCH_MAX) {
         const int m = std::min(WARP_BATCH_MAX, R.n - i0);
-        const bool tabs = m >= 4;
-        if (what == VS_WARP_TABLES_ONLY && !tabs) continue;
-        const int w = tabs ? what : VS_WARP_ALL;
-        int32_t* T = tabs ? g->d_tabs[R.set] + (size_t)i0 * g->tab_ints : nullptr;
         const uint8_t* srcs[WARP_BATCH_MAX];
         uint8_t* dsts[WARP_BATCH_MAX];
         for (int i = 0; i < m; i++) {
@@ -1656,40 +1656,18 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
                 rc = launch_make_border(R.srcs[i0 + i], s0->src_pitch, s0->w, s0->h, s0->cn, const_cast<uint8_t*>(e.src), prow, bsz, p.border_type, st);
         }
         if (rc != VS_OK) break;
+        const WarpMaps maps{g->d_MinvB[R.set] + 12 * i0, 12, false};
+        const WarpTabs tabs{WarpTabs::CALLER, g->d_tabs[R.set] + (size_t)i0 * g->tab_ints, g->tab_ints, what};
         if (s0->fmt == VS_FMT_NV12) {
             // interleaved chroma plane: half size, two channels, the map with the halved translation (Minv + 6)
-            const size_t suv = src_uv(s0);
             const uint8_t* us[WARP_BATCH_MAX];
             uint8_t* ud[WARP_BATCH_MAX];
-            bool same_duv = true;
-            for (int i = 0; i < m; i++) {
-                us[i] = srcs[i] + suv;
-                ud[i] = dsts[i] + dst_uv(s0, dsts[i], R.stride);
-                same_duv &= dst_uv(s0, dsts[i], R.stride) == dst_uv(s0, dsts[0], R.stride);
-            }
-            const int sy = tab_layout(s0->w, s0->h).stride;
-            if (tabs && w != VS_WARP_ONLY) {       // the tables by a launch per plane
-                rc = launch_warp_affine_list(srcs, dsts, m, s0->src_pitch, s0->w, s0->h, R.stride, s0->w, s0->h, 1, g->d_MinvB[R.set] + 12 * i0, 12, T, st,
-                                             VS_WARP_TABLES_ONLY, g->tab_ints);
-                if (rc == VS_OK)
-                    rc = launch_warp_affine_list(us, ud, m, s0->src_pitch, s0->w / 2, s0->h / 2, R.stride, s0->w / 2, s0->h / 2, 2,
-                                                 g->d_MinvB[R.set] + 12 * i0 + 6, 12, T + sy, st, VS_WARP_TABLES_ONLY, g->tab_ints);
-            }
-            if (w == VS_WARP_TABLES_ONLY || rc != VS_OK) continue;
-            // luma and chroma tiles of the launch's frames in ONE grid
-            int one = tabs && same_duv ? launch_warp_nv12_list(srcs, dsts, m, s0->src_pitch, R.stride, s0->w, s0->h, suv, dst_uv(s0, dsts[0], R.stride), T, st)
-                                       : VS_ERR_UNSUPPORTED;
-            if (one == VS_ERR_UNSUPPORTED) {       // (geometry outside what that kernel packs, or fewer than four frames: plane by plane)
-                rc = launch_warp_affine_list(srcs, dsts, m, s0->src_pitch, s0->w, s0->h, R.stride, s0->w, s0->h, 1, g->d_MinvB[R.set] + 12 * i0, 12, T, st,
-                                             tabs ? VS_WARP_ONLY : VS_WARP_ALL, g->tab_ints);
-                if (rc == VS_OK)
-                    rc = launch_warp_affine_list(us, ud, m, s0->src_pitch, s0->w / 2, s0->h / 2, R.stride, s0->w / 2, s0->h / 2, 2,
-                                                 g->d_MinvB[R.set] + 12 * i0 + 6, 12, tabs ? T + sy : nullptr, st, tabs ? VS_WARP_ONLY : VS_WARP_ALL, g->tab_ints);
-            } else rc = one;
+            for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + dst_uv(s0, dsts[i], R.stride); }
+            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st);
             continue;
         }
-        rc = launch_warp_affine_list(srcs, dsts, m, pad ? prow : s0->src_pitch, pw, ph, crop ? prow : R.stride, pw, ph, s0->cn,
-                                     g->d_MinvB[R.set] + 12 * i0, 12, T, st, w, g->tab_ints);
+        rc = launch_warp_plane(srcs, dsts, m, pad ? prow : s0->src_pitch, pw, ph, crop ? prow : R.stride, pw, ph, s0->cn, maps, VS_BORDER_BLACK,
+                               tabs, st);
         // crop-and-zoom: the inner part of the warped scratch frames is resized to the results
         for (int i = 0; crop && what != VS_WARP_TABLES_ONLY && i < m && rc == VS_OK; i++)
             rc = launch_resize_linear(dsts[i] + ((size_t)bsz * s0->w + bsz) * s0->cn, prow, s0->w - 2 * bsz, s0->h - 2 * bsz, s0->cn,
@@ -1818,7 +1796,7 @@ int group_run(vs_batch* g) {
                 minv = g->d_MinvB[set] + 12 * npend;
                 R.srcs[npend] = b.out_frame; R.dsts[npend] = b.d_out; R.slots[npend] = b.out_slot; R.owner[npend] = s; R.pad_idx[npend] = npad;
                 // (launches of fewer than four frames - the rest of a step's due frames beyond a multiple of 32 - run without tables)
-                if (all_apart && std::min(WARP_BATCH_MAX, ndue - npend / WARP_BATCH_MAX * WARP_BATCH_MAX) >= 4) {
+                if (all_apart && std::min(WARP_BATCH_MAX, ndue - npend / WARP_BATCH_MAX * WARP_BATCH_MAX) >= WARP_TAB_MIN) {
                     const WarpEnds e = warp_ends(s, b.out_frame, b.d_out, npad, pad, crop);
                     int32_t* T = g->d_tabs[set] + (size_t)npend * g->tab_ints;
                     jobs[0] = WarpTabJob{T, e.src, e.dst, pad ? s->w + 2 * p0.border_size : s->w, pad ? s->h + 2 * p0.border_size : s->h};

@@ -25,11 +25,6 @@ int ensure_device() {
     return VS_OK;
 }
 
-int launch_warp_nv12_hostM(const uint8_t* d_src, size_t sstride, size_t sframe, uint8_t* d_dst, size_t dstride, size_t dframe, int w, int h,
-                           const float* h_M, int batch, hipStream_t st);
-int launch_warp_affine_hostM(const uint8_t* d_src, size_t sstride, size_t sframe, int sw, int sh,
-                             uint8_t* d_dst, size_t dstride, size_t dframe, int dw, int dh, int cn,
-                             const float* h_M, int batch, hipStream_t st);
 int run_copy_rate(size_t bytes, int iters, double* gbps);
 int run_libm_checksum(int fn, uint64_t start, uint64_t count, uint64_t* result);
 int run_estimate_affine_partial2d(const float* d_from, const float* d_to, int n, double thr,
@@ -41,6 +36,14 @@ int run_pyr_lk_op(const uint8_t* d_prev, const uint8_t* d_next, size_t stride, i
 int run_gftt_op(const uint8_t* d_gray, size_t stride, int w, int h, int max_corners, double quality,
                 double min_distance, int block_size, float* d_pts, int32_t* d_count, float* d_eig,
                 hipStream_t st);
+
+// The frames base + k * frame_bytes + off, k < n, as the pointer list of the warp launchers.
+template <typename P>
+std::vector<P> frame_list(P base, size_t frame_bytes, int n, size_t off = 0) {
+    std::vector<P> v((size_t)n);
+    for (int k = 0; k < n; k++) v[k] = base + (size_t)k * frame_bytes + off;
+    return v;
+}
 
 }  // namespace vsd
 
@@ -201,18 +204,33 @@ int vs_op_warp_affine(const void* d_src, size_t src_stride, size_t src_frame_byt
                       size_t dst_stride, size_t dst_frame_bytes, int w, int h, int cn,
                       const float* M, int batch, void* stream) {
     VS_TRY(ensure_device());
-    return launch_warp_affine_hostM((const uint8_t*)d_src, src_stride, src_frame_bytes, w, h,
-                                    (uint8_t*)d_dst, dst_stride, dst_frame_bytes, w, h, cn, M, batch,
-                                    (hipStream_t)stream);
+    if (!d_src || !d_dst || !M || batch <= 0) { set_last_error("warp_affine: invalid argument"); return VS_ERR_INVALID_ARG; }
+    std::vector<double> Minv(6 * (size_t)batch);
+    for (int b = 0; b < batch; b++) warp_invert(M + 6 * (size_t)b, &Minv[6 * (size_t)b]);   // cv::warpAffine inverts on the host too
+    const auto srcs = frame_list((const uint8_t*)d_src, src_frame_bytes, batch);
+    const auto dsts = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch);
+    return launch_warp_plane(srcs.data(), dsts.data(), batch, src_stride, w, h, dst_stride, w, h, cn, WarpMaps{Minv.data(), 6, true},
+                             VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, (hipStream_t)stream);
 }
 
 int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst, size_t dst_stride,
                            int w, int h, const float* M, int batch, size_t src_frame_bytes,
                            size_t dst_frame_bytes, void* stream) {
     VS_TRY(ensure_device());
+    if (!d_src || !d_dst || !M || batch <= 0) { set_last_error("warp_affine_nv12: invalid argument"); return VS_ERR_INVALID_ARG; }
     // luma: the full matrix; chroma: the half-size two-channel plane, same rotation, translation halved
-    return launch_warp_nv12_hostM((const uint8_t*)d_src, src_stride, src_frame_bytes, (uint8_t*)d_dst, dst_stride, dst_frame_bytes, w, h, M, batch,
-                                  (hipStream_t)stream);
+    std::vector<double> Minv(12 * (size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const float* m = M + 6 * (size_t)b;
+        const float c[6] = {m[0], m[1], m[2] * 0.5f, m[3], m[4], m[5] * 0.5f};
+        warp_invert(m, &Minv[12 * (size_t)b]);
+        warp_invert(c, &Minv[12 * (size_t)b + 6]);
+    }
+    const size_t suv = (size_t)h * src_stride, duv = (size_t)h * dst_stride;
+    const auto ys = frame_list((const uint8_t*)d_src, src_frame_bytes, batch), us = frame_list((const uint8_t*)d_src, src_frame_bytes, batch, suv);
+    const auto yd = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch), ud = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch, duv);
+    return launch_warp_nv12(ys.data(), yd.data(), us.data(), ud.data(), batch, src_stride, dst_stride, w, h, WarpMaps{Minv.data(), 12, true},
+                            VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, (hipStream_t)stream);
 }
 
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt, void* d_dst,

@@ -66,10 +66,12 @@ inline const char* lab_env(const char* name) {
     return (e && e[0] == '1') ? std::getenv(name) : nullptr;
 }
 
+// T = float (CV_32F matrices) or double.
+template <typename T>
 #ifdef __HIPCC__
 __host__ __device__
 #endif
-inline void warp_invert(const float* Mf, double* inv) {
+inline void warp_invert(const T* Mf, double* inv) {
     double M[6];
     for (int i = 0; i < 6; i++) M[i] = (double)Mf[i];
     double D = M[0] * M[4] - M[1] * M[3];
@@ -84,16 +86,39 @@ inline void warp_invert(const float* Mf, double* inv) {
 }
 
 // ---- stage launchers (device pointers, asynchronous on `st`) -----------------
-// d_Minv: batch*6 doubles on the DEVICE: the INVERSE maps (warp_invert of the forward matrices).
-// d_tabs: nullptr, or warp_tabs_ints(dw, dh, frames of the launch) ints of device scratch: the coordinate terms are
-// then built once per frame by a small launch in front of the warp instead of once per tile inside it.  The scratch
-// is read by the warp launch only (stream order), so one buffer per stream and caller is enough.
+// Warps (k_warp.hip).  Frames are given one by one; all frames of a call share one geometry.  A call warps its frames in launches
+// of WARP_BATCH_MAX; a launch of WARP_TAB_MIN frames or more builds coordinate tables (warp_tab.h) when it is given a place for
+// them: the coordinate terms are then built once per frame by a small launch in front of the warp instead of once per tile.
+constexpr int WARP_BATCH_MAX = 32;
+constexpr int WARP_TAB_MIN = 4;
+// Ints of table workspace a launch over `frames` frames of dw x dh needs (packed tables).
 size_t warp_tabs_ints(int dw, int dh, int frames);
-int launch_warp_affine(const uint8_t* d_src, size_t sstride, size_t sframe, int sw, int sh,
-                       uint8_t* d_dst, size_t dstride, size_t dframe, int dw, int dh, int cn,
-                       const double* d_Minv, int batch, int32_t* d_tabs, hipStream_t st);
-// what: the whole launch, or its two halves apart (tables of the frames now, the warp later from the same d_tabs).
+// The INVERSE maps (warp_invert of the forward matrices), 6 doubles per frame and `stride` doubles from frame to frame: on the
+// device, or on the host (they then travel as kernel arguments).  NV12: the chroma plane's map follows the luma map (m + 6).
+struct WarpMaps {
+    const double* m;
+    int stride;
+    bool host;
+};
+// what: the whole launch, or its two halves apart (tables of the frames now, the warp later from the same tables).
 enum { VS_WARP_ALL = 0, VS_WARP_TABLES_ONLY = 1, VS_WARP_ONLY = 2 };
+// Where a call's coordinate tables go: nowhere; the caller's buffer (`stride` ints from frame to frame, 0 = packed; NV12 calls
+// take blocks of nv12_tab_ints); or a grow-only scratch block per stream (the standalone operators).
+struct WarpTabs {
+    enum Kind { NONE, CALLER, SCRATCH };
+    Kind kind = NONE;
+    int32_t* tabs = nullptr;
+    int stride = 0;
+    int what = VS_WARP_ALL;
+};
+// One plane of cn channels per frame (1 .. 3), border VS_BORDER_BLACK or VS_BORDER_REPLICATE.
+int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw,
+                      int dh, int cn, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st);
+// NV12 surfaces of w x h (even) luma pixels: luma planes ys -> yd, interleaved chroma planes us -> ud (half size, two channels).
+// Launches with tables warp both planes of their surfaces in ONE grid when the chroma planes lie one offset behind the luma
+// planes; other launches go plane by plane.
+int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t* const* us, uint8_t* const* ud, int n, size_t sstride,
+                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st);
 // One warp of a multi-job launch (launch_warp_jobs, k_warp.hip): any geometry, inverse map in double on the host.
 struct WarpJob {
     const uint8_t* src;
@@ -104,13 +129,6 @@ struct WarpJob {
 };
 constexpr int WARP_JOBS_MAX = 16;
 int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st);
-// tab_stride: ints between the tables of consecutive frames in d_tabs (0: packed, warp_tabs_ints(dw, dh, 1))
-int launch_warp_affine_list(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh,
-                            size_t dstride, int dw, int dh, int cn, const double* d_Minv, int minv_stride, int32_t* d_tabs,
-                            hipStream_t st, int what = VS_WARP_ALL, int tab_stride = 0);
-// NV12: both planes of n surfaces in one launch, from table blocks (warp_tab.h) that have been built
-int launch_warp_nv12_list(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstride, size_t dstride, int w, int h, size_t src_uv,
-                          size_t dst_uv, const int32_t* d_tabs, hipStream_t st, int border = VS_BORDER_BLACK);
 int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int fmt,
                        uint8_t* d_dst, size_t dstride, int dw, int dh, hipStream_t st);
 // Batched forms (batch mode): the images of `items` frames in one launch; d_pairs = device table of
