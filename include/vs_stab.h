@@ -327,7 +327,11 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
  *   vs_batch_push_dev    one frame per stream (d_frames[i] == NULL: none for stream i this time); device pointers, one geometry,
  *                        pitch and format for all; produced[i] = 1 when the push made an output of stream i due - it is complete
  *                        after vs_batch_sync, in d_outs[i].  A step runs when a member has frames_per_step frames queued.
- *   vs_batch_flush_dev   drains the group, then the next queued frame of every stream (Stabilizer::flush).
+ *                        A stream may get its first frame at any call, or never, and may stop early: the group takes its
+ *                        launch shape from the first stream(s) to deliver frames, and a stream that joins later with another
+ *                        geometry, pitch or launch shape is refused by the next step (VS_ERR_INVALID_ARG).
+ *   vs_batch_flush_dev   drains the group, then the next queued frame of every stream (Stabilizer::flush); a stream that
+ *                        never had a frame produces nothing.
  *   vs_batch_stream      the member instance i: for the per-stream getters (vs_stab_get_counters, vs_stab_get_debug, vs_stab_sync,
  *                        ...).  Its frames are pushed through the group only: vs_stab_push* / flush* / clean / set_* on a member
  *                        return VS_ERR_INVALID_ARG, vs_stab_destroy ignores it (the group owns its members).
@@ -351,7 +355,11 @@ const char* vs_batch_last_error(const vs_batch* b);
  * 2 = every stage, 3 = warp stage and the coordinate tables of batched warps.
  * vs_stab_get_stage_times() synchronises, adds the elapsed
  * time of every event pair recorded since the last call into total_ms[stage]
- * / launches[stage] (arrays of VS_STAGE_COUNT) and resets. */
+ * / launches[stage] (arrays of VS_STAGE_COUNT) and resets.  A vs_batch books
+ * the stages of its steps on ONE member: the lowest-numbered member that had
+ * frames queued when the group's first step ran (member 0 unless it started
+ * late); its profiling mode decides what is recorded.  The
+ * getter on a member that never had a frame reports zero. */
 enum {
     VS_STAGE_COPY_IN = 0,   /* frame into the queue ring                       */
     VS_STAGE_GRAY = 1,      /* resize + BGR2GRAY                               */

@@ -34,3 +34,21 @@ def noisy_gray(w, h, seed):
         g += np.where(d2 < r * r, rng.randint(10, 80), 0)
     g += rng.randint(0, 12, (h, w))
     return np.clip(g, 0, 255).astype(np.uint8)
+
+
+_chain_cache = {}
+
+
+def chain_surfaces(w, h, n):
+    """The configs[2] chain tests' input: n NV12 surfaces cycling through the seven frames of the SEED_CONFIG3 clip, each with a
+    400-row band of a tilted horizon at h / 3 (lines for the roll stage).  The seven distinct surfaces are built once per
+    session (at 3840x2160 that costs ~26 s of CPU) and the list repeats them: callers must not write into them."""
+    if (w, h) not in _chain_cache:
+        from vsamd import synth
+        base = [synth.bgr_to_nv12(f) for f in synth.make_clip(synth.SEED_CONFIG3, w, h, 7)]
+        tilt = synth.bgr_to_nv12(horizon_frame(w, h, 45, seed=7))
+        for s in base:
+            s[h // 3:h // 3 + 400] = tilt[h // 3:h // 3 + 400]
+        _chain_cache[(w, h)] = base
+    base = _chain_cache[(w, h)]
+    return [base[i % len(base)] for i in range(n)]

@@ -1081,6 +1081,114 @@ def test_streams_of_a_vs_batch_equal_their_solo_runs(gpu, fmt, n_streams, step, 
     b.close()
 
 
+# (name, streams, frames per step, first call of each stream, pushes of each stream, stream that sits out every fifth call)
+_LATE_CASES = [("stream0_starts_late", 3, 8, [8 + 3, 0, 0], [70, 70, 70], -1),
+               ("stream0_never_pushes", 3, 8, [0, 0, 0], [0, 70, 70], -1),
+               ("last_stream_ends_early", 4, 8, [0, 0, 0, 0], [70, 70, 70, 20], -1),
+               ("stream0_late_and_middle_sits_out", 5, 4, [4 + 3, 0, 0, 0, 0], [70, 70, 70, 70, 70], 2)]
+
+
+@pytest.mark.parametrize("fmt", [capi.FMT_BGR8, capi.FMT_NV12])
+@pytest.mark.parametrize("case", _LATE_CASES + ["late_joiner_of_another_shape"], ids=lambda c: c if isinstance(c, str) else c[0])
+def test_vs_batch_streams_that_start_late_or_end_early_equal_their_solo_runs(gpu, fmt, case):
+    """vs_batch_push_dev takes no frame for stream i when d_frames[i] is NULL - also before stream i's first frame and after its
+    last: a camera that connects late (member 0 included), one that never delivers, one that stops early.  The steps that run
+    without a member, and the flush, leave every stream's frames equal to a vs_stab instance's run on its own; a stream that
+    never pushed flushes to nothing and reports zero.  A late joiner whose geometry differs from the group's is refused by the
+    next step (VS_ERR_INVALID_ARG), and only then."""
+    w, h = 320, 240
+    refuse = case == "late_joiner_of_another_shape"
+    _, S, step, start, count, sitter = ("", 3, 8, [8 + 3, 0, 0], [70, 70, 70], -1) if refuse else case
+    clips = [synth.make_clip(synth.SEED_CONFIG1 + 90 + g, w, h, 16) for g in range(S)]
+    if fmt == capi.FMT_NV12:
+        clips = [[synth.bgr_to_nv12(f) for f in c] for c in clips]
+    n = max(count)
+    order = [i % 16 if (i // 16) % 2 == 0 else 15 - i % 16 for i in range(n)]
+    params = dict(smoothing_radius=7)
+    fb = clips[0][0].nbytes
+    stride = w * 3 if fmt == capi.FMT_BGR8 else w
+
+    def load(g):
+        buf = capi.DevBuf(gpu, fb * 16)
+        for i, f in enumerate(clips[g]):
+            buf.upload(f, i * fb)
+        return buf
+
+    b = gpu.batch(gpu.params(**params), S, step)
+    b.set_zero_copy(True)
+    d_in = [load(g) for g in range(S)]
+    d_out = [capi.DevBuf(gpu, fb * (n + 2)) for _ in range(S)]
+    if refuse:
+        # members 1 and 2 run a step on their own, then member 0 joins with frames of half the size (in calls of their own: one
+        # geometry per call); its first frame only opens its stream, the later ones wait for a step - and the next step, when
+        # members 1 and 2 have a step's frames queued again, refuses them
+        outs = [d_out[g].ptr for g in range(S)]
+        for call in range(start[0]):
+            b.push_dev([None] + [d_in[g].ptr + order[call] * fb for g in (1, 2)], w, h, stride, fmt, outs, stride)
+        with pytest.raises(capi.VsError, match="invalid argument: vs_batch: the streams of a group share one frame geometry"):
+            for call in range(start[0], start[0] + step):
+                b.push_dev([d_in[0].ptr + order[call] * fb, None, None], w // 2, h // 2, stride // 2, fmt, outs, stride // 2)
+                b.push_dev([None] + [d_in[g].ptr + order[call] * fb for g in (1, 2)], w, h, stride, fmt, outs, stride)
+        b.close()
+        for buf in d_in + d_out:
+            buf.free()
+        return
+
+    def solo(g):
+        s = gpu.stabilizer(gpu.params(**params))
+        s.set_batch(16)
+        s.set_zero_copy(True)
+        d_src, d_dst = load(g), capi.DevBuf(gpu, fb * (n + 2))
+        k = 0
+        for i in order[:count[g]]:
+            k += s.push_dev(d_src.ptr + i * fb, w, h, stride, fmt, d_dst.ptr + k * fb, stride)
+        while s.flush_dev(d_dst.ptr + k * fb, stride):
+            k += 1
+        s.sync()
+        out = d_dst.download((k,) + clips[g][0].shape, np.uint8)
+        s.close()
+        for buf in (d_src, d_dst):
+            buf.free()
+        return out
+    alone = [solo(g) for g in range(S)]
+    for g in range(S):
+        b.stream(g).set_profiling(2)
+    k, pos, call = [0] * S, [0] * S, 0
+    while any(pos[g] < count[g] for g in range(S)):
+        fr = [d_in[g].ptr + order[pos[g]] * fb if (call >= start[g] and pos[g] < count[g] and not (g == sitter and call % 5 == 4)) else None
+              for g in range(S)]
+        prod = b.push_dev(fr, w, h, stride, fmt, [d_out[g].ptr + k[g] * fb for g in range(S)], stride)
+        for g in range(S):
+            if fr[g] is not None:
+                pos[g] += 1
+                k[g] += prod[g]
+            else:
+                assert prod[g] == 0, (call, g)
+        call += 1
+    while True:
+        prod = b.flush_dev([d_out[g].ptr + k[g] * fb for g in range(S)], stride)
+        for g in range(S):
+            k[g] += prod[g]
+        if not any(prod):
+            break
+    b.sync()
+    for g in range(S):
+        got = d_out[g].download((k[g],) + clips[g][0].shape, np.uint8)
+        assert k[g] == count[g] == len(alone[g]) and np.array_equal(got, alone[g]), g
+        assert b.stream(g).counters().frames_out == count[g], g
+    # the group's stage times are booked on ONE member, the lowest-numbered one with frames in the group's first step; a member
+    # that never had a frame reports zero
+    ref = min(g for g in range(S) if start[g] == 0 and count[g] > 0)
+    for g in range(S):
+        ms, launches = b.stream(g).stage_times()
+        assert (launches[1] > 0) == (g == ref), g          # (VS_STAGE_GRAY: recorded by the group's steps only)
+        if count[g] == 0:
+            assert not any(ms) and not any(launches), g
+    b.close()
+    for buf in d_in + d_out:
+        buf.free()
+
+
 def test_vs_batch_refuses_per_stream_modes(gpu):
     """Modes whose outputs depend on each other or on a host decision per output stay with vs_stab_* (per-frame pipeline)."""
     for kw in (dict(adaptive_smoothing=1), dict(border_size=8, border_type=capi.BORDER_FADE), dict(enable_virtual_canvas=1)):
@@ -1281,13 +1389,7 @@ def test_config3_chain_4k_nv12_roll_stabilize_zoomcrop_against_oracle(gpu, oracl
     stages' states) against the oracle's chain on the same surfaces."""
     import roll_scene
     W, H, N = 3840, 2160, 14
-    base = [synth.bgr_to_nv12(f) for f in synth.make_clip(synth.SEED_CONFIG3, W, H, 7)]
-    tilt = synth.bgr_to_nv12(roll_scene.horizon_frame(W, H, 45, seed=7))
-    surfs = []
-    for i in range(N):
-        s = base[i % 7].copy()
-        s[H // 3:H // 3 + 400] = tilt[H // 3:H // 3 + 400]          # a band with a tilted horizon: lines for the roll stage
-        surfs.append(s)
+    surfs = roll_scene.chain_surfaces(W, H, N)      # the seven SEED_CONFIG3 frames with a tilted-horizon band, twice
     sb = W * H * 3 // 2
     params = dict(smoothing_radius=5, max_corners=400)
     # ---- oracle chain

@@ -1500,6 +1500,10 @@ struct vs_batch {
     int device = 0, S = 0, B = 0, cap = 0;
     bool own = false;                       // the private schedule of one standalone instance
     std::vector<vs_stab*> m;
+    // The member whose geometry shapes the group's launches and tables, and on which its stage times are booked: the
+    // lowest-numbered member with frames in the step that allocated the group (member 0 unless it had none yet).  Members
+    // cannot change their geometry (vs_stab_clean is refused on them): it stays the reference until the group is freed.
+    vs_stab* ref = nullptr;
     std::string err;
     hipStream_t st = nullptr, st_pre = nullptr, st_det = nullptr, st_up = nullptr;      // st_up: the table uploads (the pool's warp stream: idle in batch mode)
     bool allocated = false;
@@ -1555,6 +1559,7 @@ void group_free(vs_batch* g) {
     if (g->d_all) (void)hipFree(g->d_all);
     g->h_tables = nullptr; g->d_all = nullptr;
     g->allocated = false;
+    g->ref = nullptr;
 }
 
 bool group_make_events(vs_batch* g) {
@@ -1576,9 +1581,9 @@ bool same_launch_shape(const vs_stab* a, const vs_stab* b) {
            p.crop_n_zoom == q.crop_n_zoom && (p.border_size <= 0 || p.border_type == q.border_type);
 }
 
-// Tables and workspaces for cap = S * B frames per step, once the members know their geometry.
+// Tables and workspaces for cap = S * B frames per step, once the members know their geometry (g->ref's).
 int group_allocate(vs_batch* g) {
-    const vs_stab* s0 = g->m[0];
+    const vs_stab* s0 = g->ref;
     const int cap = g->cap, ngf = g->S * (g->B / 2 + 1);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -1635,7 +1640,7 @@ WarpEnds warp_ends(const vs_stab* o, const uint8_t* frame, uint8_t* d_out, int p
 // inside its tail workgroup).  The frames' tables lie tab_ints apart in d_tabs[set].
 int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
     vs_batch::Ready& R = g->ready;
-    const vs_stab* s0 = g->m[0];
+    const vs_stab* s0 = g->ref;
     const vs_params_c& p = s0->p;
     const int bsz = p.border_size;
     const bool pad = bsz > 0 && !p.crop_n_zoom;                                                       // Stabilizer.cpp:981-990
@@ -1685,7 +1690,6 @@ int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
     vs_batch::Ready& R = g->ready;
     if (!R.valid) return VS_OK;
     hipStream_t st = g->st_pre;
-    vs_stab* s0 = g->m[0];
     int rc;
     // what the warps wait for - the step's maps and tables (ev_rel), the wide launches of the detector (det_done) - is gathered on the
     // upload stream into ONE event: one packet in front of the warps on `pre` instead of two
@@ -1700,7 +1704,7 @@ int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
         g->rel_valid[R.set] = false;
     }
     {
-        StageScope t(s0, VS_STAGE_WARP, st);       // (stage times of a group are booked on its first member)
+        StageScope t(g->ref, VS_STAGE_WARP, st);   // (stage times of a group are booked on its reference member)
         rc = group_ready_launches(g, R.tabs_built ? VS_WARP_ONLY : VS_WARP_ALL, st);
     }
     if (hipEventRecord(g->ev_warp[R.set], st) == hipSuccess) { g->warp_valid[R.set] = true; g->last_warp_set = R.set; }
@@ -1727,13 +1731,18 @@ int group_run(vs_batch* g) {
         if (!s->bq.empty()) { act.push_back(s); n += (int)s->bq.size(); max_n = std::max(max_n, (int)s->bq.size()); }
     if (n == 0) return VS_OK;
     G_HIP(g, hipSetDevice(g->device));
-    const vs_stab* s0 = g->m[0];
+    // every member with frames in this step has the reference's launch shape; the group's first step makes its first active
+    // member the reference (a member that has had no frame yet - a camera that connects late - has no geometry to compare)
+    const vs_stab* s0 = g->ref ? g->ref : act[0];
     for (vs_stab* s : act)
-        if (!s->allocated || !s->batch_active || !s0->allocated || !same_launch_shape(s, s0))
+        if (!s->allocated || !s->batch_active || !same_launch_shape(s, s0))
             return gfail(g, VS_ERR_INVALID_ARG, "vs_batch: the streams of a group share one frame geometry, pitch, input mode and launch shape "
                                                 "(analysis size, pyramid depth, tracking window, hypothesis count, border mode)");
     if (n > g->cap || max_n > BATCH_MAX) return gfail(g, VS_ERR_CAPACITY, "vs_batch: more frames queued than a step holds");
-    if (!g->allocated) G_TRY(g, group_allocate(g));
+    if (!g->allocated) {
+        g->ref = act[0];
+        G_TRY(g, group_allocate(g));
+    }
     const int k = g->batch_id++;
     // host images of this step's tables: the set step k-4 used (its tail, the last reader of anything uploaded from it, has run
     // by now unless the host is four steps ahead of the GPU - then it waits here)
@@ -1814,7 +1823,7 @@ int group_run(vs_batch* g) {
         any_apart |= p.smoothing_method != VS_SMOOTH_KALMAN;
         nseg++;
         if (s->bq[0].prev_small) {   // Stabilizer.cpp:598-603 (once per stream: 480x270 -> analysis size)
-            StageScope t(g->m[0], VS_STAGE_PYRAMID, g->st_pre);
+            StageScope t(g->ref, VS_STAGE_PYRAMID, g->st_pre);
             G_TRY(g, launch_resize_gray(s->d_first_gray, 480, 480, 270, VS_FMT_GRAY8, s->pyr[s->bq[0].pv].img[0], s->aw, s->aw, s->ah, g->st_pre));
             G_TRY(g, build_pyramid(s, s->bq[0].pv, g->st_pre));
         }
@@ -1848,7 +1857,7 @@ int group_run(vs_batch* g) {
         G_HIP(g, hipEventRecord(g->ev_up[dset], g->st_up));
         G_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_up[dset], 0));
         {
-            StageScope t(g->m[0], VS_STAGE_GRAY, g->st_pre);
+            StageScope t(g->ref, VS_STAGE_GRAY, g->st_pre);
             // NV12: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline)
             const int gfmt = s0->fmt == VS_FMT_NV12 ? VS_FMT_GRAY8 : s0->fmt;
             const int n_a = (n_detect > 0 && n_detect < n) ? n_detect : n;
@@ -1857,7 +1866,7 @@ int group_run(vs_batch* g) {
             if (n_a < n)
                 G_TRY(g, launch_resize_gray_batch(d_pairs + n_a, n - n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));
         }
-        StageScope t(g->m[0], VS_STAGE_PYRAMID, g->st_pre);
+        StageScope t(g->ref, VS_STAGE_PYRAMID, g->st_pre);
         // One launch per level (pyr_level_kernel): derivatives of level l and the image of level l+1 from one staged read of
         // level l.  (83.0 k -> 92.2 k frames/s at 1080p against the two stencils as separate launches, round 2.)
         for (int l = 0; l <= L; l++)
@@ -1891,7 +1900,7 @@ int group_run(vs_batch* g) {
         G_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 1));
         G_HIP(g, hipStreamWaitEvent(sd, g->ev_bgray, 0));
         {
-            StageScope t(g->m[0], VS_STAGE_GFTT, sd);
+            StageScope t(g->ref, VS_STAGE_GFTT, sd);
             G_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 4));
             G_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 5));
             // the wide launches of the detection are through: the warps of the step before may go (below); the selection -
@@ -1919,11 +1928,11 @@ int group_run(vs_batch* g) {
         if (s->pts_pending[0]) { G_HIP(g, hipStreamWaitEvent(st, s->pts_event[0], 0)); s->pts_pending[0] = false; }
     if (wait_det) G_HIP(g, hipStreamWaitEvent(st, g->ev_bdet[g->last_det_batch % 4], 0));       // the tracker needs the selected corners
     {
-        StageScope t(g->m[0], VS_STAGE_LK, st);
+        StageScope t(g->ref, VS_STAGE_LK, st);
         G_TRY(g, launch_pyr_lk_batch(g->d_lk[dset], n, n_max, s0->p.lk_win_size, st));
     }
     {
-        StageScope t(g->m[0], VS_STAGE_RANSAC, st);
+        StageScope t(g->ref, VS_STAGE_RANSAC, st);
         G_TRY(g, launch_ransac_score_batch(g->d_rs[dset], n, s0->p.ransac_max_iters, n_max, st));
     }
     for (vs_stab* s : act)
@@ -1935,7 +1944,7 @@ int group_run(vs_batch* g) {
         g->warp_valid[set] = false;
     }
     {
-        StageScope t(g->m[0], VS_STAGE_TRAJ, st);
+        StageScope t(g->ref, VS_STAGE_TRAJ, st);
         G_TRY(g, launch_ransac_tail_group(g->d_rs[dset], g->d_tail[dset], g->d_seg[dset], g->d_tin[dset], nseg, max_n, n, any_apart, st));
     }
     // the keypoint and pyramid buffers of this step may be recycled (two steps on) once the tail, which still reads the points
@@ -1948,7 +1957,7 @@ int group_run(vs_batch* g) {
     if (g->ready.valid) {
         g->pend_set = set ^ 1;
         if (!g->ready.tabs_built) {          // (a Kalman stream in the step: the tables as a launch behind the tail)
-            StageScope t(g->m[0], VS_STAGE_WARP_TABLES, st);
+            StageScope t(g->ref, VS_STAGE_WARP_TABLES, st);
             G_TRY(g, group_ready_launches(g, VS_WARP_TABLES_ONLY, st));
             g->ready.tabs_built = true;
         }
