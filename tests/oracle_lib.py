@@ -557,8 +557,10 @@ class OracleStab:
         st = np.zeros(max(d.n_prev, 1), np.uint8)
         inl = np.zeros(max(d.n_valid, 1), np.uint8)
         det = np.zeros((max(d.n_detected, 1), 2), np.float32)
-        gray = np.zeros(960 * 540, np.uint8)
         aw, ah = C.c_int32(), C.c_int32()
+        # the analysis size first (drone mode can analyse images larger than any fixed buffer), then the arrays
+        self.lib.vso_stab_get_debug_arrays(self.h, None, None, None, None, None, None, C.byref(aw), C.byref(ah))
+        gray = np.zeros(max(aw.value * ah.value, 1), np.uint8)
         self.lib.vso_stab_get_debug_arrays(self.h, _p(prev, f32p), _p(cur, f32p), _p(st, u8p), _p(inl, u8p),
                                            _p(det, f32p), _p(gray, u8p), C.byref(aw), C.byref(ah))
         return dict(prev=prev[:d.n_prev], curr=cur[:d.n_prev], status=st[:d.n_prev], inliers=inl[:d.n_valid],

@@ -80,3 +80,43 @@ def test_device_atan2f_equals_the_host_libm(gpu, oracle):
     for start, count in ((0, 1 << 30), (1 << 40, 1 << 28)):
         gpu.check(gpu.lib.vs_op_libm_checksum(3, start, count, C.byref(got)))
         assert got.value == oracle.lib.vso_libm_checksum(3, start, count, threads), (start, count)
+
+
+# ---- checks that hold on every host: the host build of vs_libm.h against the double libm, and the device build against the host
+# build (no comparison with the host's float libm, so nothing here skips) --------------------------------------------------------
+
+
+def _libm_check():
+    os.makedirs(BUILD, exist_ok=True)
+    exe = os.path.join(BUILD, "libm_check")
+    src = os.path.join(ROOT, "tests", "cpp", "libm_check.cpp")
+    if not os.path.exists(exe) or os.path.getmtime(exe) < os.path.getmtime(src):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-o", exe, src])
+    return exe
+
+
+def test_host_build_is_within_one_ulp_of_the_double_libm():
+    """Every float through cosf_ref / sinf_ref / atanf_ref, and 2^27 atan2f_ref pairs, against (float)f((double)x): at most 1 ulp
+    (glibc's float functions are not all correctly rounded: the counts of values that are not are printed)."""
+    r = subprocess.run([_libm_check(), "ulp"], capture_output=True, text=True, timeout=1500)
+    print(r.stdout)
+    lines = [ln.split() for ln in r.stdout.splitlines()]
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert [(ln[0], ln[1], ln[2]) for ln in lines] == [("cosf", "4294967296", "0"), ("sinf", "4294967296", "0"),
+                                                       ("atanf", "4294967296", "0"), ("atan2f", "134217728", "0")], r.stdout
+
+
+def _host_build_checksum(fn, start, count):
+    r = subprocess.run([_libm_check(), "checksum", str(fn), str(start), str(count)], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr
+    return int(r.stdout.split()[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fn,start,count", [(0, 0, 1 << 32), (1, 0, 1 << 32), (2, 0, 1 << 32), (3, 0, 1 << 30),
+                                            (3, 1 << 40, 1 << 28)])
+def test_device_build_equals_the_host_build(gpu, fn, start, count):
+    got = C.c_uint64(0)
+    gpu.check(gpu.lib.vs_op_libm_checksum(fn, start, count, C.byref(got)))
+    assert got.value == _host_build_checksum(fn, start, count), (fn, start, count)

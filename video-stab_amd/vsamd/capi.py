@@ -980,8 +980,11 @@ class Stabilizer:
         st = np.zeros(max(d.n_prev, 1), np.uint8)
         inl = np.zeros(max(d.n_valid, 1), np.uint8)
         det = np.zeros((max(d.n_detected, 1), 2), np.float32)
-        gray = np.zeros(1920 * 1080, np.uint8)
         aw, ah = C.c_int32(), C.c_int32()
+        # the analysis size first (drone mode can analyse images larger than any fixed buffer), then the arrays
+        self.vs.check(self.lib.vs_stab_get_debug_arrays(self.h, None, None, None, None, None, None,
+                                                        C.byref(aw), C.byref(ah)), self.h)
+        gray = np.zeros(max(aw.value * ah.value, 1), np.uint8)
         self.vs.check(self.lib.vs_stab_get_debug_arrays(self.h, _p(prev, f32p), _p(cur, f32p), _p(st, u8p),
                                                         _p(inl, u8p), _p(det, f32p), _p(gray, u8p),
                                                         C.byref(aw), C.byref(ah)), self.h)
