@@ -89,14 +89,8 @@ __device__ __forceinline__ Weights make_weights(float a, float b) {
     return w;
 }
 
-__device__ __forceinline__ short2 load_deriv(const int16_t* __restrict__ d, int w, int h, int x, int y) {
-    if ((unsigned)x >= (unsigned)w || (unsigned)y >= (unsigned)h) return make_short2(0, 0);
-    return *reinterpret_cast<const short2*>(d + ((size_t)y * w + x) * 2);
-}
-
 // A pointer every lane of the wave holds the same value of, as a global-memory pointer in scalar registers.
 typedef const __attribute__((address_space(1))) uint8_t* gmem_u8;
-typedef const __attribute__((address_space(1))) int16_t* gmem_i16;
 __device__ __forceinline__ gmem_u8 uniform_global(const uint8_t* p) {
     const unsigned long long v = (unsigned long long)p;
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
@@ -117,46 +111,59 @@ __device__ __forceinline__ void divmod_small(int i, int d, float inv_d, int& q, 
 
 template <int NPX>
 __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
-    // Per level everything the wave will touch is staged into LDS with ONE round of
-    // global loads: the template patch of the previous image, its derivative patch,
-    // and the search region of the next image (pyramid padding already applied).
+    // Per level everything the wave will touch is staged into LDS with ONE round of global loads: the template patch of
+    // the previous image with a one-pixel rim, and the search region of the next image (pyramid padding already applied).
+    // The patch's Scharr derivatives are then computed in LDS from the staged bytes (the pyramid writes no derivative
+    // images: at 960 x 540 they were 2.7 MB per frame of HBM writes, read back here at 4 bytes per patch pixel).
     // sized by the window class of the instantiation (NPX pixels per lane: windows up to 16 / 21 / 31): with the
     // arrays of the largest class a 21x21 tracker held 7 KB, 22 waves fitted a CU and the 6400 points of a
     // 32-frame batch took two rounds on 5632 slots; 3.6 KB leaves the wave limit (32 per CU) as the only one
     constexpr int WM = NPX <= 4 ? 16 : (NPX <= 7 ? 21 : LK_WIN_MAX);
     constexpr int PWM = WM + 1, RWM = WM + 1 + 2 * LK_MARGIN;
+    // The staged patch holds rows and columns -1 .. PW of the template patch at a row pitch PP = PW + 2 rounded up to whole
+    // dwords (the derivative pass reads it as dwords).  The derivatives are stored at the same index as the pixel they belong
+    // to, so that one offset per window pixel serves both arrays.  A lane of the derivative pass takes DR rows x 4 columns,
+    // sized so that one round of the wave covers the patch.
+    constexpr int DR = NPX <= 7 ? 3 : 5;
+    constexpr int PPM = (PWM + 2 + 3) & ~3;
+    constexpr int SRM = (PWM + 1 + 3) / 4, NGM = (PWM + DR - 1) / DR;       // column strips, row groups
+    static_assert(SRM * NGM <= 64, "one derivative round per level");
     // elements per lane of the lane-strided staging walks; the arrays are padded to whole rounds of 64 so that the stores of a
-    // round need no bounds check (the padding is never read)
-    constexpr int PN = (PWM * PWM + 63) / 64, RN = (RWM * RWM + 63) / 64;
-    __shared__ uint8_t pI[PN * 64];
-    __shared__ short2 pD[PN * 64];
+    // round need no bounds check (the padding is never read).  The patch array also holds what the derivative pass reads
+    // beside the staged bytes (results that are not stored or never read): the dword in front of row 0, the rows past the
+    // last staged one up to the end of the last row group, and the dword past that.
+    constexpr int PN = (PPM * (PWM + 2) + 63) / 64, RN = (RWM * RWM + 63) / 64;
+    constexpr int PBYTES = (PN * 64 > PPM * (NGM * DR + 2) + 4 ? PN * 64 : PPM * (NGM * DR + 2) + 4);
+    __shared__ __attribute__((aligned(16))) uint8_t pI_[4 + PBYTES];
+    uint8_t* const pI = pI_ + 4;
+    __shared__ __attribute__((aligned(16))) short2 pD[(PWM + 1) * PPM];
     __shared__ uint8_t region[RN * 64];
     const int lane = threadIdx.x;
     int n = a.n;
     if (a.d_n) { int dn = *a.d_n; n = dn < n ? dn : n; }
     if (pt >= n) return;
     const int win = a.win, area = win * win;
-    const int PW = win + 1;
+    const int PW = win + 1, PP = (PW + 2 + 3) & ~3;
     const int RW = win + 1 + 2 * LK_MARGIN;
-    const float inv_pw = 1.0f / (float)PW, inv_rw = 1.0f / (float)RW, inv_win = 1.0f / (float)win;
-    // per window pixel of this lane: offsets into the template patch (low half) and the search region (high half);
-    // kept packed, and the (x, y) of a pixel is recomputed where the rare out-of-region path needs it: the register
-    // budget decides how many points a SIMD tracks at once
+    const float inv_pp = 1.0f / (float)PP, inv_rw = 1.0f / (float)RW, inv_win = 1.0f / (float)win;
+    // per window pixel of this lane: offsets into the staged patch and its derivatives (low half) and the search region
+    // (high half); kept packed, and the (x, y) of a pixel is recomputed where the rare
+    // out-of-region path needs it: the register budget decides how many points a SIMD tracks at once
     uint32_t off[NPX];
 #pragma unroll
     for (int k = 0; k < NPX; k++) {
         const int p = lane + 64 * k;
         int yy = 0, xx = 0;
         if (p < area) divmod_small(p, win, inv_win, yy, xx);
-        off[k] = (uint32_t)(yy * PW + xx) | ((uint32_t)(yy * RW + xx) << 16);
+        off[k] = (uint32_t)((yy + 1) * PP + xx + 1) | ((uint32_t)(yy * RW + xx) << 16);
     }
 #define LK_VALID(k) (lane + 64 * (k) < area)
 #define LK_POFF(k) ((int)(off[k] & 0xFFFFu))
 #define LK_ROFF(k) ((int)(off[k] >> 16))
-    // lane-strided walks over the PW x PW patch and the RW x RW region: start and step
+    // lane-strided walks over the PP x (PW + 2) patch and the RW x RW region: start and step
     int p_y0, p_x0, p_sy, p_sx, r_y0, r_x0, r_sy, r_sx;
-    divmod_small(lane, PW, inv_pw, p_y0, p_x0);
-    divmod_small(64, PW, inv_pw, p_sy, p_sx);
+    divmod_small(lane, PP, inv_pp, p_y0, p_x0);
+    divmod_small(64, PP, inv_pp, p_sy, p_sx);
     divmod_small(lane, RW, inv_rw, r_y0, r_x0);
     divmod_small(64, RW, inv_rw, r_sy, r_sx);
     const float halfWin = (win - 1) * 0.5f;
@@ -191,38 +198,33 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
         // (SQ_WAIT_ANY 68 % of its wave cycles, profiles/r03_c_configs1_pmc.txt).
         // (Batches of at most ten loads: the values and offsets of a batch are all that is live, 128 registers - four waves per
         // SIMD - hold without spills; three to four round trips per level instead of 26.)
-        const bool p_inside = ipx >= 0 && ipy >= 0 && ipx + PW <= L.w && ipy + PW <= L.h;
-        if (p_inside) {
-            // (the wave tracks ONE point: bases in scalar registers, global - not flat - loads with a 32-bit lane offset)
-            const gmem_u8 pbase = uniform_global(L.prev + ((size_t)ipy * L.stride + ipx));
-            const gmem_i16 dbase = (gmem_i16)uniform_global(reinterpret_cast<const uint8_t*>(L.deriv + ((size_t)ipy * L.w + ipx) * 2));
-            constexpr int PB_ = 5;             // elements per batch (two loads each)
+        const int pcount = PP * (PW + 2);
+        if (ipx >= 1 && ipy >= 1 && ipx - 1 + PP <= L.w && ipy + PW + 1 <= L.h) {
+            // (the wave tracks ONE point: base in scalar registers, global - not flat - loads with a 32-bit lane offset)
+            const gmem_u8 pbase = uniform_global(L.prev + ((size_t)(ipy - 1) * L.stride + (ipx - 1)));
+            constexpr int PB_ = 10;
             int y = p_y0, x = p_x0;
 #pragma unroll
             for (int k0 = 0; k0 < PN; k0 += PB_) {
                 uint8_t vI[PB_];
-                uint32_t vD[PB_];
 #pragma unroll
                 for (int k = k0; k < k0 + PB_ && k < PN; k++) {
-                    const bool ok = lane + 64 * k < PW * PW;
-                    const uint32_t eo = ok ? (uint32_t)(y * (int)L.stride + x) : 0u, dof = ok ? (uint32_t)((y * L.w + x) * 2) : 0u;
-                    vI[k - k0] = pbase[eo];
-                    vD[k - k0] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(dbase + dof);
+                    const bool ok = lane + 64 * k < pcount;
+                    vI[k - k0] = pbase[ok ? (uint32_t)(y * (int)L.stride + x) : 0u];
                     x += p_sx; y += p_sy;
-                    if (x >= PW) { x -= PW; y++; }
+                    if (x >= PP) { x -= PP; y++; }
                 }
 #pragma unroll
-                for (int k = k0; k < k0 + PB_ && k < PN; k++) { pI[lane + 64 * k] = vI[k - k0]; *reinterpret_cast<uint32_t*>(&pD[lane + 64 * k]) = vD[k - k0]; }
+                for (int k = k0; k < k0 + PB_ && k < PN; k++) pI[lane + 64 * k] = vI[k - k0];
                 __builtin_amdgcn_sched_barrier(0);
             }
-        } else {
+        } else {                               // REFLECT_101 intensities; the derivative pass masks what lies outside
             int y = p_y0, x = p_x0;
-            for (int i = lane; i < PW * PW; i += 64) {
-                const int X = ipx + x, Y = ipy + y;
+            for (int i = lane; i < pcount; i += 64) {
+                const int X = ipx - 1 + x, Y = ipy - 1 + y;
                 pI[i] = L.prev[(size_t)reflect101(Y, L.h) * L.stride + reflect101(X, L.w)];
-                pD[i] = load_deriv(L.deriv, L.w, L.h, X, Y);
                 x += p_sx; y += p_sy;
-                if (x >= PW) { x -= PW; y++; }
+                if (x >= PP) { x -= PP; y++; }
             }
         }
         // the search region of the next image around (rx0, ry0); staged again, re-centred, if the point walks out
@@ -259,7 +261,58 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
         };
         stage_region();
         __syncthreads();
+        // ---- Scharr derivatives of the patch (scharr_kernel's stencil and border rule: the staged rim is the REFLECT_101 of
+        // the image), 0 at positions outside the level image (cv::calcOpticalFlowPyrLK pads the derivative image with
+        // BORDER_CONSTANT).  Staged columns 4 c .. 4 c + 3 of rows y .. y + DR - 1 per lane: three dwords per staged row (the
+        // byte left of the group, the group, the byte right of it), a rolling window of three rows (one output row at a time
+        // keeps the pass inside the tracker's register budget), one 16-byte store per output row.
+        {
+            const int sr = (PW + 1 + 3) >> 2;
+            int g, c;
+            divmod_small(lane, sr, 1.0f / (float)sr, g, c);
+            const int y = 1 + g * DR, x = 4 * c;
+            if (y <= PW) {
+                // staged pixels (x .. x + 3, y + r) are inside the level image: all of them when the patch is
+                const bool masked = !(ipx >= 0 && ipy >= 0 && ipx + PW <= L.w && ipy + PW <= L.h);
+                int t[3][6];                                            // staged columns x - 1 .. x + 4
+                auto load_row = [&](int j, int* tj) {
+                    const uint32_t* q = reinterpret_cast<const uint32_t*>(pI + j * PP) + c;
+                    const uint32_t lo = q[-1], mid = q[0], hi = q[1];
+                    tj[0] = lo >> 24;
+                    tj[1] = mid & 255u; tj[2] = (mid >> 8) & 255u; tj[3] = (mid >> 16) & 255u; tj[4] = mid >> 24;
+                    tj[5] = hi & 255u;
+                };
+                load_row(y - 1, t[0]);
+                load_row(y, t[1]);
+#pragma unroll
+                for (int r = 0; r < DR; r++) {
+                    const int* t0 = t[r % 3];
+                    const int* t1 = t[(r + 1) % 3];
+                    int* t2 = t[(r + 2) % 3];
+                    load_row(y + r + 1, t2);
+                    int av[6], bv[6];                                   // vertical smoothing / difference per column
+#pragma unroll
+                    for (int k = 0; k < 6; k++) {
+                        av[k] = (t0[k] + t2[k]) * 3 + t1[k] * 10;
+                        bv[k] = t2[k] - t0[k];
+                    }
+                    uint32_t o[4];                                      // (dx, dy) as two 16-bit halves
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int dx = av[k + 2] - av[k], dy = (bv[k + 2] + bv[k]) * 3 + bv[k + 1] * 10;
+                        o[k] = ((uint32_t)dx & 0xFFFFu) | ((uint32_t)dy << 16);
+                        if (masked && ((unsigned)(ipx - 1 + x + k) >= (unsigned)L.w || (unsigned)(ipy - 1 + y + r) >= (unsigned)L.h)) o[k] = 0u;
+                    }
+                    if (y + r <= PW) *reinterpret_cast<uint4*>(&pD[(y + r) * PP + x]) = make_uint4(o[0], o[1], o[2], o[3]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        __syncthreads();
         // ---- template window, its gradients and the 2x2 matrix
+        // (the LDS addresses of the window pixels are derived here at every level: hoisted out of the level loop they cost 20 registers)
+#pragma unroll
+        for (int k = 0; k < NPX; k++) asm volatile("" : "+v"(off[k]));
         Weights wt = make_weights(prevx - ipx, prevy - ipy);
         short Iw[NPX], Ix[NPX], Iy[NPX];
         int pA11 = 0, pA12 = 0, pA22 = 0;
@@ -268,8 +321,8 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
             // invalid slots read offset 0 and are zeroed afterwards
             const int o = LK_POFF(k);
             int ival = descale(__mul24((int)pI[o], wt.w00) + __mul24((int)pI[o + 1], wt.w01) +
-                               __mul24((int)pI[o + PW], wt.w10) + __mul24((int)pI[o + PW + 1], wt.w11), 9);
-            const short2 d00 = pD[o], d01 = pD[o + 1], d10 = pD[o + PW], d11 = pD[o + PW + 1];
+                               __mul24((int)pI[o + PP], wt.w10) + __mul24((int)pI[o + PP + 1], wt.w11), 9);
+            const short2 d00 = pD[o], d01 = pD[o + 1], d10 = pD[o + PP], d11 = pD[o + PP + 1];
             int ixval = descale(__mul24((int)d00.x, wt.w00) + __mul24((int)d01.x, wt.w01) +
                                 __mul24((int)d10.x, wt.w10) + __mul24((int)d11.x, wt.w11), 14);
             int iyval = descale(__mul24((int)d00.y, wt.w00) + __mul24((int)d01.y, wt.w01) +
@@ -450,7 +503,7 @@ int launch_pyr_lk(const LKLevel* levels, int max_level, const float* d_prev_pts,
     return VS_OK;
 }
 
-// vs_op_pyr_lk: builds both pyramids and the derivative images, then tracks.
+// vs_op_pyr_lk: builds both pyramids, then tracks.
 int run_pyr_lk_op(const uint8_t* d_prev, const uint8_t* d_next, size_t stride, int w, int h,
                   const float* d_prev_pts, int n, float* d_next_pts, uint8_t* d_status,
                   float* d_err, int win, int max_level, int max_iters, double eps, hipStream_t st) {
@@ -470,16 +523,13 @@ int run_pyr_lk_op(const uint8_t* d_prev, const uint8_t* d_next, size_t stride, i
             if (sw <= win || sh <= win) break;
         }
     }
-    size_t img_bytes = 0, der_bytes = 0;
+    size_t img_bytes = 0;
     for (int i = 1; i <= levels; i++) img_bytes += (size_t)lw[i] * lh[i];
-    for (int i = 0; i <= levels; i++) der_bytes += (size_t)lw[i] * lh[i] * 4;
     uint8_t* scratch = nullptr;
-    const size_t total = 2 * img_bytes + der_bytes + 64;
-    VS_HIP_TRY(hipMalloc((void**)&scratch, total));
+    VS_HIP_TRY(hipMalloc((void**)&scratch, 2 * img_bytes + 64));
     LKLevel L[MAX_LEVELS];
     uint8_t* pp = scratch;
     uint8_t* pn = scratch + img_bytes;
-    int16_t* pd = reinterpret_cast<int16_t*>(scratch + ((2 * img_bytes + 15) & ~(size_t)15));
     int rc = VS_OK;
     for (int i = 0; i <= levels && rc == VS_OK; i++) {
         L[i].w = lw[i]; L[i].h = lh[i];
@@ -490,9 +540,6 @@ int run_pyr_lk_op(const uint8_t* d_prev, const uint8_t* d_next, size_t stride, i
             L[i].prev = pp; L[i].next = pn; L[i].stride = lw[i];
             pp += (size_t)lw[i] * lh[i]; pn += (size_t)lw[i] * lh[i];
         }
-        if (rc == VS_OK) rc = launch_scharr(L[i].prev, L[i].stride, lw[i], lh[i], pd, st);
-        L[i].deriv = pd;
-        pd += (size_t)lw[i] * lh[i] * 2;
     }
     if (rc == VS_OK) rc = launch_pyr_lk(L, levels, d_prev_pts, n, nullptr, d_next_pts, d_status, d_err, win, max_iters, eps, st);
     hipError_t e = hipStreamSynchronize(st);

@@ -61,24 +61,24 @@ __global__ __launch_bounds__(NT) void scharr_kernel(const uint8_t* __restrict__ 
 }
 
 // ---- one pyramid level per launch (batch mode) --------------------------------------------------------------
-// Level l of the LK pyramid needs two things of image l: its Scharr derivatives and, if there is a level l+1, its
-// pyrDown.  The two stencils above read the image separately (5 launches for 3 levels, 25 + 9 byte loads per output
-// pixel through L1).  Here a workgroup stages a 64 x 16 tile of image l with a 2-pixel rim (REFLECT_101 applied while
-// staging: both stencils use it on source coordinates) in LDS once - dword loads when the tile is inside the image -
-// and produces the tile's 64 x 16 derivative pairs (4 per lane, one 16-byte store) and its 32 x 8 pixels of level l+1
-// (1 per lane): 3 launches for 3 levels, every level read once.  The kernel is bound by dependent LDS round trips, not by
-// bytes or arithmetic: with one ds_read_u8 per tap (18 + 25 per lane) level 0 of a 32-frame batch took 73 - 81 us, with
-// the taps fetched as dwords (9 + 10 reads, bytes picked out in registers, the 1 4 6 4 row of pyrDown as one v_dot4) 25 - 35.
+// A workgroup stages a 64 x 16 tile of image l with a 2-pixel rim (REFLECT_101 applied while staging: both stencils use it
+// on source coordinates) in LDS once - dword loads when the tile is inside the image - and produces, per template flag, the
+// tile's 64 x 16 Scharr derivative pairs (DER: 4 per lane, one 16-byte store) and its 32 x 8 pixels of level l+1 (DOWN: 1 per
+// lane).  Batch mode launches the pyrDown-only form for levels 0 .. L-1: the tracker computes the derivatives it needs from
+// the images (k_lk.hip), so no derivative image is written.  The form with derivatives serves vs_op_pyr_level.  The kernel
+// is bound by dependent LDS round trips, not by bytes or arithmetic: with one ds_read_u8 per tap (18 + 25 per lane) level 0
+// of a 32-frame batch took 73 - 81 us, with the taps fetched as dwords (9 + 10 reads, bytes picked out in registers, the
+// 1 4 6 4 row of pyrDown as one v_dot4) 25 - 35.
 constexpr int FT_W = 64, FT_H = 16;                    // tile of image l
 constexpr int FT_PITCH = 72;                           // staged row: 68 bytes used (x0 - 2 .. x0 + 65), dword aligned
 constexpr int FT_ROWS = FT_H + 4;                      // y0 - 2 .. y0 + 17
 
-template <bool DOWN>
+template <bool DER, bool DOWN>
 __global__ __launch_bounds__(NT) void pyr_level_kernel(const ImgPair* __restrict__ sch, const ImgPair* __restrict__ pyr, size_t sstride,
                                                        int w, int h, size_t dstride, int dw, int dh) {
+    static_assert(DER || DOWN, "a level launch produces something");
     __shared__ __attribute__((aligned(16))) uint8_t tile[FT_ROWS * FT_PITCH];
-    const uint8_t* __restrict__ src = static_cast<const uint8_t*>(sch[blockIdx.z].src);
-    int16_t* __restrict__ der = static_cast<int16_t*>(sch[blockIdx.z].dst);
+    const uint8_t* __restrict__ src = static_cast<const uint8_t*>((DER ? sch : pyr)[blockIdx.z].src);
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * FT_W, y0 = blockIdx.y * FT_H;
     // ---- stage rows y0-2 .. y0+17, columns x0-4 .. x0+67 (the dword grid of the image; tile column c = x - (x0 - 4))
@@ -117,7 +117,8 @@ __global__ __launch_bounds__(NT) void pyr_level_kernel(const ImgPair* __restrict
     const uint32_t* T = reinterpret_cast<const uint32_t*>(tile);
     // ---- Scharr: lane -> row tid / 16, columns 4 * (tid % 16) .. + 3.  Three dwords per row (the byte left of the group,
     // the group, the byte right of it) instead of six byte reads: the kernel is bound by dependent LDS round trips
-    {
+    if (DER) {
+        int16_t* __restrict__ der = static_cast<int16_t*>(sch[blockIdx.z].dst);
         const int r = tid >> 4, c = (tid & 15) * 4;
         const int y = y0 + r, x = x0 + c;
         if (y < h && x < w) {
@@ -174,18 +175,21 @@ __global__ __launch_bounds__(NT) void pyr_level_kernel(const ImgPair* __restrict
 
 }  // namespace
 
-// Derivatives of level l (d_scharr_pairs: image l -> derivative image) and, when d_pyr_pairs is given, level l+1
-// (d_pyr_pairs: image l -> image l+1) of `items` frames.  w, h: size of image l (row pitch sstride); dstride: pitch of l+1.
+// Derivatives of level l (d_scharr_pairs: image l -> derivative image) and/or level l+1 (d_pyr_pairs: image l -> image l+1)
+// of `items` frames.  w, h: size of image l (row pitch sstride); dstride: pitch of l+1.
 int launch_pyr_level_batch(const ImgPair* d_scharr_pairs, const ImgPair* d_pyr_pairs, int items, size_t sstride, int w, int h,
                            size_t dstride, hipStream_t st) {
-    if (!d_scharr_pairs || items < 1 || items > 65535 || w <= 0 || h <= 0 || h > 65535) {
+    if ((!d_scharr_pairs && !d_pyr_pairs) || items < 1 || items > 65535 || w <= 0 || h <= 0 || h > 65535) {
         set_last_error("pyr_level_batch: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
     const int dw = (w + 1) / 2, dh = (h + 1) / 2;
     dim3 grid((w + FT_W - 1) / FT_W, (h + FT_H - 1) / FT_H, items);
-    if (d_pyr_pairs) hipLaunchKernelGGL(pyr_level_kernel<true>, grid, dim3(NT), 0, st, d_scharr_pairs, d_pyr_pairs, sstride, w, h, dstride, dw, dh);
-    else hipLaunchKernelGGL(pyr_level_kernel<false>, grid, dim3(NT), 0, st, d_scharr_pairs, d_pyr_pairs, sstride, w, h, dstride, dw, dh);
+    if (!d_scharr_pairs)
+        hipLaunchKernelGGL((pyr_level_kernel<false, true>), grid, dim3(NT), 0, st, d_scharr_pairs, d_pyr_pairs, sstride, w, h, dstride, dw, dh);
+    else if (d_pyr_pairs)
+        hipLaunchKernelGGL((pyr_level_kernel<true, true>), grid, dim3(NT), 0, st, d_scharr_pairs, d_pyr_pairs, sstride, w, h, dstride, dw, dh);
+    else hipLaunchKernelGGL((pyr_level_kernel<true, false>), grid, dim3(NT), 0, st, d_scharr_pairs, d_pyr_pairs, sstride, w, h, dstride, dw, dh);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }

@@ -100,7 +100,6 @@ constexpr int EVR = 4;              // per-frame event ring
 
 struct Pyramid {
     uint8_t* img[MAX_PYR] = {};
-    int16_t* der[MAX_PYR] = {};
 };
 
 }  // namespace vsd
@@ -427,12 +426,9 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     size_t o_first = take((size_t)480 * 270);
-    std::vector<std::array<size_t, MAX_PYR>> o_img(s->npyr), o_der(s->npyr);
+    std::vector<std::array<size_t, MAX_PYR>> o_img(s->npyr);
     for (int k = 0; k < s->npyr; k++)
-        for (int l = 0; l <= s->levels; l++) {
-            o_img[k][l] = take((size_t)s->lw[l] * s->lh[l]);
-            o_der[k][l] = take((size_t)s->lw[l] * s->lh[l] * 4);
-        }
+        for (int l = 0; l <= s->levels; l++) o_img[k][l] = take((size_t)s->lw[l] * s->lh[l]);
     std::vector<size_t> o_pts(nkp), o_npts(nkp);
     for (int k = 0; k < nkp; k++) { o_pts[k] = take((size_t)ncap * 8); o_npts[k] = take(16); }
     struct ItemOff { size_t next, err, vp, vc, status, inl, m, info, counts, model; };
@@ -454,10 +450,7 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     uint8_t* b = s->d_all;
     s->d_first_gray = b + o_first;
     for (int k = 0; k < s->npyr; k++)
-        for (int l = 0; l <= s->levels; l++) {
-            s->pyr[k].img[l] = b + o_img[k][l];
-            s->pyr[k].der[l] = (int16_t*)(b + o_der[k][l]);
-        }
+        for (int l = 0; l <= s->levels; l++) s->pyr[k].img[l] = b + o_img[k][l];
     for (int k = 0; k < nkp; k++) { s->d_pts[k] = (float*)(b + o_pts[k]); s->d_npts[k] = (int32_t*)(b + o_npts[k]); }
     for (int k = 0; k < B; k++) {
         vs_stab::ItemBufs& it = s->items[k];
@@ -540,8 +533,6 @@ int build_pyramid(vs_stab* s, int k, hipStream_t st) {
     Pyramid& P = s->pyr[k];
     for (int l = 1; l <= s->levels; l++)
         S_TRY(s, launch_pyr_down(P.img[l - 1], s->lw[l - 1], s->lw[l - 1], s->lh[l - 1], P.img[l], s->lw[l], st));
-    for (int l = 0; l <= s->levels; l++)
-        S_TRY(s, launch_scharr(P.img[l], s->lw[l], s->lw[l], s->lh[l], P.der[l], st));
     return VS_OK;
 }
 
@@ -625,7 +616,7 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     }
     LKLevel L[MAX_PYR];
     for (int l = 0; l <= s->levels; l++) {
-        L[l].prev = s->pyr[pv].img[l]; L[l].next = s->pyr[c].img[l]; L[l].deriv = s->pyr[pv].der[l];
+        L[l].prev = s->pyr[pv].img[l]; L[l].next = s->pyr[c].img[l];
         L[l].w = s->lw[l]; L[l].h = s->lh[l]; L[l].stride = s->lw[l];
     }
     const int cap = s->pts_cap[pp];
@@ -1591,7 +1582,7 @@ int group_allocate(vs_batch* g) {
     // a table set on the device = its image on the host (pairs, tracker items, scoring items, tail items, segments: ONE upload per step)
     size_t ho = 0;
     auto htake = [&](size_t bytes) { size_t o = ho; ho += (bytes + 255) & ~(size_t)255; return o; };
-    g->ho_pairs = htake(sizeof(ImgPair) * cap * (2 + 2 * MAX_PYR));
+    g->ho_pairs = htake(sizeof(ImgPair) * cap * MAX_PYR);
     g->ho_lk = htake(lk_item_bytes() * cap); g->ho_rs = htake(ransac_item_bytes() * cap);
     g->ho_tail = htake(tail_item_bytes() * cap); g->ho_seg = htake(tail_seg_bytes() * g->S);
     g->up_bytes = ho;
@@ -1786,7 +1777,7 @@ int group_run(vs_batch* g) {
             const vs_stab::ItemBufs& it = s->items[i];
             LKLevel L[MAX_PYR];
             for (int l = 0; l <= s->levels; l++) {
-                L[l].prev = s->pyr[b.pv].img[l]; L[l].next = s->pyr[b.c].img[l]; L[l].deriv = s->pyr[b.pv].der[l];
+                L[l].prev = s->pyr[b.pv].img[l]; L[l].next = s->pyr[b.c].img[l];
                 L[l].w = s->lw[l]; L[l].h = s->lh[l]; L[l].stride = s->lw[l];
             }
             const int cap = std::max(b.lk_cap, 0);
@@ -1829,7 +1820,7 @@ int group_run(vs_batch* g) {
         }
     }
     {
-        // pair tables: [0] frame -> img[0]; [1..levels] img[l-1] -> img[l]; [levels+1 ..] img[l] -> der[l]
+        // pair tables: [0] frame -> img[0]; [1..levels] img[l-1] -> img[l]
         const int L = s0->levels;
         int aligned = 1, n_detect = 0;
         // level-0 pairs: the frames that re-detect first, so that the detector can start after a first, smaller launch
@@ -1842,7 +1833,6 @@ int group_run(vs_batch* g) {
                 h_pairs[slot] = ImgPair{b.frame, P.img[0]};
                 if ((uintptr_t)b.frame % 8) aligned = 0;
                 for (int l = 1; l <= L; l++) h_pairs[(size_t)l * n + i] = ImgPair{P.img[l - 1], P.img[l]};
-                for (int l = 0; l <= L; l++) h_pairs[(size_t)(L + 1 + l) * n + i] = ImgPair{P.img[l], P.der[l]};
                 i++;
             }
         // ONE upload per step: the pair tables of the gray / pyramid launches and, behind them in the set, the tables of the tracker,
@@ -1867,11 +1857,9 @@ int group_run(vs_batch* g) {
                 G_TRY(g, launch_resize_gray_batch(d_pairs + n_a, n - n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));
         }
         StageScope t(g->ref, VS_STAGE_PYRAMID, g->st_pre);
-        // One launch per level (pyr_level_kernel): derivatives of level l and the image of level l+1 from one staged read of
-        // level l.  (83.0 k -> 92.2 k frames/s at 1080p against the two stencils as separate launches, round 2.)
-        for (int l = 0; l <= L; l++)
-            G_TRY(g, launch_pyr_level_batch(d_pairs + (size_t)(L + 1 + l) * n, l < L ? d_pairs + (size_t)(l + 1) * n : nullptr, n, s0->lw[l], s0->lw[l],
-                                            s0->lh[l], l < L ? s0->lw[l + 1] : 0, g->st_pre));
+        // One pyrDown launch per level (pyr_level_kernel): the tracker computes the derivatives it needs from the images.
+        for (int l = 0; l < L; l++)
+            G_TRY(g, launch_pyr_level_batch(nullptr, d_pairs + (size_t)(l + 1) * n, n, s0->lw[l], s0->lw[l], s0->lh[l], s0->lw[l + 1], g->st_pre));
     }
     // (`main` waits for the event behind this step's warps when there are any: it covers the pyramid, which lies in front of them)
     if (!g->ready.valid) G_HIP(g, hipEventRecord(g->ev_bpre, g->st_pre));

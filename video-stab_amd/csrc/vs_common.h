@@ -136,6 +136,8 @@ int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int
 struct ImgPair { const void* src; void* dst; };
 int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, int sw, int sh, int fmt, size_t dstride,
                              int dw, int dh, int aligned, hipStream_t st);
+// One pyramid level of `items` images: Scharr derivatives (d_scharr_pairs: image -> derivative image) and/or the pyrDown
+// (d_pyr_pairs: image -> next level); when both tables are given, their sources are the same images.
 int launch_pyr_level_batch(const ImgPair* d_scharr_pairs, const ImgPair* d_pyr_pairs, int items, size_t sstride, int w, int h,
                            size_t dstride, hipStream_t st);
 int launch_pyr_down(const uint8_t* d_src, size_t sstride, int sw, int sh, uint8_t* d_dst,
@@ -146,7 +148,6 @@ int launch_scharr(const uint8_t* d_src, size_t sstride, int w, int h, int16_t* d
 struct LKLevel {
     const uint8_t* prev;
     const uint8_t* next;
-    const int16_t* deriv;  // prev derivatives, w*h*2
     int w, h;
     size_t stride;
 };
