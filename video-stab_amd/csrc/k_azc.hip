@@ -244,7 +244,7 @@ struct vs_azc {
     bool waiting = false;                    // a worker waits for the oldest of them
     bool quit = false;
     long issued = 0, completed = 0;
-    int async_rc = 0;                    // first failure of a worker's launch (reported by vs_azc_sync)
+    FirstFailure failure;                // the first failed frame of the workers (reported by vs_azc_sync)
     // where the workers' time goes (vs_azc_worker_times): frames, and seconds waiting for a job / for a batch's masks / in the
     // contour logic / queueing launches and publishing
     double wt[5] = {0, 0, 0, 0, 0};
@@ -253,14 +253,6 @@ struct vs_azc {
 };
 
 static_assert(vs_azc::ZB <= SRC_LIST_MAX && 2 * vs_azc::ZB <= WARP_JOBS_MAX, "a batch's sources and warp jobs travel as kernel arguments");
-
-#define A_HIP(a, expr)                                                             \
-    do {                                                                           \
-        hipError_t _e = (expr);                                                    \
-        if (_e != hipSuccess) { (a)->err = std::string(#expr) + ": " + hipGetErrorString(_e); set_last_error((a)->err); return VS_ERR_HIP; } \
-    } while (0)
-#define A_TRY(a, expr)                                                             \
-    do { int _s = (expr); if (_s != VS_OK) { (a)->err = get_last_error(); return _s; } } while (0)
 
 extern "C" {
 
@@ -341,42 +333,41 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk);
 
 int vs_azc_sync(vs_azc* a) {
     if (!a) return VS_ERR_INVALID_ARG;
-    A_HIP(a, hipSetDevice(a->device));
+    VS_OBJ_HIP(a, hipSetDevice(a->device));
     if (!a->workers.empty()) {          // asynchronous NV12 frames: their host parts first, then what the workers queued
         std::unique_lock<std::mutex> lk(a->mu);
-        const int frc = azc_flush_pending(a, lk);
-        if (frc != VS_OK) return frc;
+        const int frc = azc_flush_pending(a, lk);      // (a failed flush completes its frames with the error)
         a->cv_done.wait(lk, [&] { return a->completed == a->issued; });
-        const int arc = a->async_rc;
-        a->async_rc = VS_OK;
+        const FirstFailure wf = a->failure.take();
         lk.unlock();
-        A_HIP(a, hipStreamSynchronize(a->st_out));
-        if (arc != VS_OK) { a->err = "auto zoom/crop: a worker's launch failed"; set_last_error(a->err); return arc; }
+        VS_OBJ_HIP(a, hipStreamSynchronize(a->st_out));
+        if (frc != VS_OK) return frc;
+        if (wf.rc != VS_OK) return vs_obj_fail(a, wf.rc, wf.msg);
     }
-    A_HIP(a, hipStreamSynchronize(a->st));
+    VS_OBJ_HIP(a, hipStreamSynchronize(a->st));
     return VS_OK;
 }
 
 // Mask on the device, contour logic on the host: fills a->info (:111-228).
 static int azc_plan(vs_azc* a, const void* d_data, int w, int h, size_t stride, int cn) {
-    if (w > 65535 || h > 32767) { a->err = "auto zoom/crop: image too large"; set_last_error(a->err); return VS_ERR_INVALID_ARG; }
+    if (w > 65535 || h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
     const size_t mb = BitFrame::words_for(w, h) * 8;
     if (a->mask_w != w || a->mask_h != h) {
         if (a->d_mask) (void)hipFree(a->d_mask);
         if (a->h_mask) (void)hipHostFree(a->h_mask);
         if (a->d_tbits) (void)hipFree(a->d_tbits);
         a->d_mask = a->h_mask = nullptr; a->d_tbits = nullptr; a->mask_w = a->mask_h = 0;
-        A_HIP(a, hipMalloc((void**)&a->d_mask, mb));
-        A_HIP(a, hipMalloc((void**)&a->d_tbits, (size_t)((w + 63) / 64) * h * 8));
-        A_HIP(a, hipHostMalloc((void**)&a->h_mask, mb, hipHostMallocDefault));
-        A_HIP(a, hipMemsetAsync(a->d_mask, 0, mb, a->st));          // the frame; the kernel rewrites the inside
+        VS_OBJ_HIP(a, hipMalloc((void**)&a->d_mask, mb));
+        VS_OBJ_HIP(a, hipMalloc((void**)&a->d_tbits, (size_t)((w + 63) / 64) * h * 8));
+        VS_OBJ_HIP(a, hipHostMalloc((void**)&a->h_mask, mb, hipHostMallocDefault));
+        VS_OBJ_HIP(a, hipMemsetAsync(a->d_mask, 0, mb, a->st));          // the frame; the kernel rewrites the inside
         a->mask_w = w; a->mask_h = h;
     }
     BitFrame bf;
     bf.w = w; bf.h = h; bf.pitch = BitFrame::pitch_for(w); bf.F = (const uint64_t*)a->h_mask;
-    A_TRY(a, launch_content_bits((const uint8_t*)d_data, stride, w, h, cn, a->d_tbits, (u64*)a->d_mask, bf.pitch, 1, a->st));   // :111-139
-    A_HIP(a, hipMemcpyAsync(a->h_mask, a->d_mask, mb, hipMemcpyDeviceToHost, a->st));                 // :142-143
-    A_HIP(a, hipStreamSynchronize(a->st));
+    VS_OBJ_TRY(a, launch_content_bits((const uint8_t*)d_data, stride, w, h, cn, a->d_tbits, (u64*)a->d_mask, bf.pitch, 1, a->st));   // :111-139
+    VS_OBJ_HIP(a, hipMemcpyAsync(a->h_mask, a->d_mask, mb, hipMemcpyDeviceToHost, a->st));                 // :142-143
+    VS_OBJ_HIP(a, hipStreamSynchronize(a->st));
     crop_from_mask(bf, a->scratch, a->info, nullptr);                                                 // :146-228
     return VS_OK;
 }
@@ -385,7 +376,7 @@ static int azc_plan(vs_azc* a, const void* d_data, int w, int h, size_t stride, 
 static int azc_emit(vs_azc* a, const void* d_data, int w, int h, size_t stride, int cn, void* d_out, size_t out_stride) {
     if (!a->info[7]) {
         if (out_stride < (size_t)w * cn) return VS_ERR_INVALID_ARG;
-        A_HIP(a, hipMemcpy2DAsync(d_out, out_stride, d_data, stride, (size_t)w * cn, h, hipMemcpyDeviceToDevice, a->st));
+        VS_OBJ_HIP(a, hipMemcpy2DAsync(d_out, out_stride, d_data, stride, (size_t)w * cn, h, hipMemcpyDeviceToDevice, a->st));
         return VS_OK;
     }
     if (out_stride < (size_t)640 * cn) return VS_ERR_INVALID_ARG;
@@ -396,7 +387,7 @@ static int azc_emit(vs_azc* a, const void* d_data, int w, int h, size_t stride, 
     warp_invert(Mf, Mi);
     const uint8_t* roi = (const uint8_t*)d_data + (size_t)cy * stride + (size_t)cx * cn;
     uint8_t* out = (uint8_t*)d_out;
-    A_TRY(a, launch_warp_plane(&roi, &out, 1, stride, cw, ch, out_stride, 640, 360, cn, WarpMaps{Mi, 6, true}, VS_BORDER_BLACK, WarpTabs{}, a->st));
+    VS_OBJ_TRY(a, launch_warp_plane(&roi, &out, 1, stride, cw, ch, out_stride, 640, 360, cn, WarpMaps{Mi, 6, true}, VS_BORDER_BLACK, WarpTabs{}, a->st));
     return VS_OK;
 }
 
@@ -407,7 +398,7 @@ int vs_azc_apply_dev(vs_azc* a, const void* d_data, int w, int h, size_t stride,
     if (!a || !d_data || !d_out || !out_w || !out_h || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || stride < (size_t)w * cn ||
         out_stride < (size_t)std::max(w, 640) * cn)
         return VS_ERR_INVALID_ARG;
-    A_HIP(a, hipSetDevice(a->device));
+    VS_OBJ_HIP(a, hipSetDevice(a->device));
     int rc = azc_plan(a, d_data, w, h, stride, cn);
     if (rc != VS_OK) return rc;
     rc = azc_emit(a, d_data, w, h, stride, cn, d_out, out_stride);
@@ -422,29 +413,36 @@ int vs_azc_apply_dev(vs_azc* a, const void* d_data, int w, int h, size_t stride,
 int vs_azc_apply(vs_azc* a, const uint8_t* data, int w, int h, size_t stride, int cn, uint8_t* out, int* out_w, int* out_h) {
     if (!a || !data || !out || !out_w || !out_h || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || stride < (size_t)w * cn)
         return VS_ERR_INVALID_ARG;
-    A_HIP(a, hipSetDevice(a->device));
+    VS_OBJ_HIP(a, hipSetDevice(a->device));
     const size_t row = (size_t)w * cn, bytes = std::max(row * h, (size_t)640 * 360 * cn);
     if (a->io_bytes < bytes) {
         if (a->d_in) (void)hipFree(a->d_in);
         if (a->d_out) (void)hipFree(a->d_out);
         a->d_in = a->d_out = nullptr; a->io_bytes = 0;
-        A_HIP(a, hipMalloc((void**)&a->d_in, bytes));
-        A_HIP(a, hipMalloc((void**)&a->d_out, bytes));
+        VS_OBJ_HIP(a, hipMalloc((void**)&a->d_in, bytes));
+        VS_OBJ_HIP(a, hipMalloc((void**)&a->d_out, bytes));
         a->io_bytes = bytes;
     }
-    A_HIP(a, hipMemcpy2DAsync(a->d_in, row, data, stride, row, h, hipMemcpyHostToDevice, a->st));
+    VS_OBJ_HIP(a, hipMemcpy2DAsync(a->d_in, row, data, stride, row, h, hipMemcpyHostToDevice, a->st));
     int rc = azc_plan(a, a->d_in, w, h, row, cn);
     if (rc != VS_OK) return rc;
     const int ow = a->info[7] ? 640 : w, oh = a->info[7] ? 360 : h;
     rc = azc_emit(a, a->d_in, w, h, row, cn, a->d_out, (size_t)ow * cn);
     if (rc != VS_OK) return rc;
-    A_HIP(a, hipMemcpyAsync(out, a->d_out, (size_t)ow * cn * oh, hipMemcpyDeviceToHost, a->st));
-    A_HIP(a, hipStreamSynchronize(a->st));
+    VS_OBJ_HIP(a, hipMemcpyAsync(out, a->d_out, (size_t)ow * cn * oh, hipMemcpyDeviceToHost, a->st));
+    VS_OBJ_HIP(a, hipStreamSynchronize(a->st));
     *out_w = ow; *out_h = oh;
     return VS_OK;
 }
 
 // ---- NV12, asynchronous ----------------------------------------------------------------------------------------------------
+// (a->mu held) A frame's outcome, the one place a worker publishes it: its result and, for a frame that failed (its masks did not
+// arrive, its copy or its batch's crop launch could not be queued), the object's first failure.
+static void azc_publish(vs_azc* a, const vs_azc::Result& res) {
+    a->results[res.ticket % vs_azc::NRES] = res;
+    a->failure.note(res.rc, "auto zoom/crop: a worker's launch failed");
+}
+
 // One frame's host part, on a worker thread: the contour logic on the frame's mask once its batch's masks have arrived, then its
 // crop-and-scale job (or, at once, the copy of the fall-back paths) for both planes on st_out; the worker that finishes a batch's
 // last frame queues the batch's jobs as one launch.  The content mask is taken from the luma plane (gray > 1, :121-127 on a picture
@@ -537,7 +535,7 @@ static void azc_worker(vs_azc* a) {
         WarpJob all[2 * vs_azc::ZB];
         {
             std::lock_guard<std::mutex> g(a->mu);
-            a->results[res.ticket % vs_azc::NRES] = res;
+            azc_publish(a, res);
             if (scaled) { b.wj[b.nwj++] = wj[0]; b.wj[b.nwj++] = wj[1]; }
             last = --b.todo == 0;
             if (last) { njobs = b.nwj; memcpy(all, b.wj, sizeof(WarpJob) * njobs); }
@@ -551,8 +549,11 @@ static void azc_worker(vs_azc* a) {
             a->wt[4] += secs(t_contour, t_end);
             if (!last) continue;
             if (lrc != VS_OK) {
-                a->async_rc = lrc;
-                for (int i = 0; i < b.n; i++) a->results[b.fr[i].ticket % vs_azc::NRES].rc = lrc;
+                for (int i = 0; i < b.n; i++) {
+                    vs_azc::Result r = a->results[b.fr[i].ticket % vs_azc::NRES];
+                    r.rc = lrc;
+                    azc_publish(a, r);
+                }
             }
             a->completed += b.n;
             b.left = 0;
@@ -563,8 +564,7 @@ static void azc_worker(vs_azc* a) {
 }
 
 // (a->mu held through lk) what has been handed over becomes a batch: mask kernels, one copy, a job per frame
-static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
-    if (a->pending.empty()) return VS_OK;
+static int azc_issue_batch(vs_azc* a, std::unique_lock<std::mutex>& lk) {
     vs_azc::BatchSlot& b = a->bslot[a->nbatches % vs_azc::NBS];
     {
         const auto t0 = std::chrono::steady_clock::now();
@@ -575,18 +575,18 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
     const int w = a->pending[0].w, h = a->pending[0].h;
     const size_t mb = BitFrame::words_for(w, h) * 8, tw = (size_t)((w + 63) / 64) * h;
     if (!b.ev) {
-        A_HIP(a, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming | hipEventBlockingSync));
-        A_HIP(a, hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking));
+        VS_OBJ_HIP(a, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming | hipEventBlockingSync));
+        VS_OBJ_HIP(a, hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking));
     }
     if (b.mw != w || b.mh != h) {
         if (b.d_masks) (void)hipFree(b.d_masks);
         if (b.h_masks) (void)hipHostFree(b.h_masks);
         if (b.d_tbits) (void)hipFree(b.d_tbits);
         b.d_masks = b.h_masks = nullptr; b.d_tbits = nullptr; b.mw = b.mh = 0;
-        A_HIP(a, hipMalloc((void**)&b.d_masks, mb * vs_azc::ZB));
-        A_HIP(a, hipMalloc((void**)&b.d_tbits, tw * 8 * vs_azc::ZB));
-        A_HIP(a, hipHostMalloc((void**)&b.h_masks, mb * vs_azc::ZB, hipHostMallocDefault));
-        A_HIP(a, hipMemsetAsync(b.d_masks, 0, mb * vs_azc::ZB, b.st));          // the frames of the BitFrames; the kernel rewrites the insides
+        VS_OBJ_HIP(a, hipMalloc((void**)&b.d_masks, mb * vs_azc::ZB));
+        VS_OBJ_HIP(a, hipMalloc((void**)&b.d_tbits, tw * 8 * vs_azc::ZB));
+        VS_OBJ_HIP(a, hipHostMalloc((void**)&b.h_masks, mb * vs_azc::ZB, hipHostMallocDefault));
+        VS_OBJ_HIP(a, hipMemsetAsync(b.d_masks, 0, mb * vs_azc::ZB, b.st));          // the frames of the BitFrames; the kernel rewrites the insides
         b.mw = w; b.mh = h;
     }
     int aligned = 1;
@@ -596,10 +596,10 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
         srcs[i] = a->pending[i].src;
         if ((uintptr_t)a->pending[i].src & 3) aligned = 0;
     }
-    A_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, 1, b.d_tbits, (u64*)b.d_masks, BitFrame::pitch_for(w), 1, b.st, srcs, n, tw,
+    VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, 1, b.d_tbits, (u64*)b.d_masks, BitFrame::pitch_for(w), 1, b.st, srcs, n, tw,
                                  mb / 8, aligned));                                                                              // :111-139 on the luma planes
-    A_HIP(a, hipMemcpyAsync(b.h_masks, b.d_masks, mb * n, hipMemcpyDeviceToHost, b.st));                                          // :142-143
-    A_HIP(a, hipEventRecord(b.ev, b.st));
+    VS_OBJ_HIP(a, hipMemcpyAsync(b.h_masks, b.d_masks, mb * n, hipMemcpyDeviceToHost, b.st));                                          // :142-143
+    VS_OBJ_HIP(a, hipEventRecord(b.ev, b.st));
     b.t_issue = std::chrono::steady_clock::now();
     b.n = n; b.left = n; b.todo = n; b.nwj = 0; b.arrived = 0;
     a->on_the_way.push_back((int)(a->nbatches % vs_azc::NBS));
@@ -607,6 +607,25 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
     a->pending.clear();
     a->cv_job.notify_all();
     return VS_OK;
+}
+
+// (a->mu held through lk) azc_issue_batch for the frames handed over.  When it fails, their tickets are out already: they complete
+// with the error (the calling API call reports it), and no later call issues them again.
+static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
+    if (a->pending.empty()) return VS_OK;
+    const int rc = azc_issue_batch(a, lk);
+    if (rc != VS_OK) {
+        for (const vs_azc::Frame& f : a->pending) {
+            vs_azc::Result& r = a->results[f.ticket % vs_azc::NRES];
+            r = vs_azc::Result{};
+            r.ticket = f.ticket;
+            r.rc = rc;
+        }
+        a->completed += (long)a->pending.size();
+        a->pending.clear();
+        a->cv_done.notify_all();
+    }
+    return rc;
 }
 
 // autoZoomCrop for an NV12 surface in HBM, ASYNCHRONOUS.  d_out receives the result - 640 x 360 (luma rows of out_pitch bytes,
@@ -620,17 +639,16 @@ int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t
     if (!a || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w || out_pitch < (size_t)std::max(w, 640) ||
         out_uv_offset < (size_t)std::max(h, 360) * out_pitch)
         return VS_ERR_INVALID_ARG;
-    if (w > 65535 || h > 32767) { a->err = "auto zoom/crop: image too large"; set_last_error(a->err); return VS_ERR_INVALID_ARG; }
+    if (w > 65535 || h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
     if (uv_offset == 0) uv_offset = (size_t)h * pitch;
-    A_HIP(a, hipSetDevice(a->device));
+    VS_OBJ_HIP(a, hipSetDevice(a->device));
     if (a->workers.empty()) {
-        A_HIP(a, hipStreamCreateWithFlags(&a->st_out, hipStreamNonBlocking));
+        VS_OBJ_HIP(a, hipStreamCreateWithFlags(&a->st_out, hipStreamNonBlocking));
         try {
             if (const char* e = std::getenv("VS_AZC_WORKERS")) a->nw = std::max(1, std::min(std::atoi(e), 16));
             for (int i = 0; i < a->nw; i++) a->workers.emplace_back(azc_worker, a);
         } catch (...) {
-            a->err = "auto zoom/crop: cannot start worker threads"; set_last_error(a->err);
-            return VS_ERR_HIP;
+            return vs_obj_fail(a, VS_ERR_HIP, "auto zoom/crop: cannot start worker threads");
         }
     }
     std::unique_lock<std::mutex> lk(a->mu);
@@ -671,7 +689,7 @@ int vs_azc_worker_times(vs_azc* a, double* out5) {      // (nine values: include
 int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* info8) {
     if (!a || ticket < 0) return VS_ERR_INVALID_ARG;
     std::unique_lock<std::mutex> lk(a->mu);
-    if (ticket >= a->issued || ticket + vs_azc::NRES <= a->issued) { a->err = "auto zoom/crop: no such ticket (results of the last 1024 frames are kept)"; set_last_error(a->err); return VS_ERR_INVALID_ARG; }
+    if (ticket >= a->issued || ticket + vs_azc::NRES <= a->issued) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: no such ticket (results of the last 1024 frames are kept)");
     if (!a->pending.empty() && ticket >= a->pending[0].ticket) {       // (still waiting for its batch to fill)
         const int frc = azc_flush_pending(a, lk);
         if (frc != VS_OK) return frc;
@@ -681,8 +699,8 @@ int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* in
     if (out_w) *out_w = r.out_w;
     if (out_h) *out_h = r.out_h;
     if (info8) memcpy(info8, r.info, sizeof r.info);
-    if (r.rc != VS_OK) { a->err = "auto zoom/crop: a worker's launch failed"; set_last_error(a->err); }
-    return r.rc;
+    if (r.rc != VS_OK) return vs_obj_fail(a, r.rc, "auto zoom/crop: a worker's launch failed");
+    return VS_OK;
 }
 
 }  // extern "C"

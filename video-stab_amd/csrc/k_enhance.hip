@@ -885,13 +885,6 @@ struct vs_enh {
     int passes = 0;                     // frame passes of the last apply (for tests / docs)
 };
 
-#define E_HIP(e, expr)                                                             \
-    do {                                                                           \
-        hipError_t _e = (expr);                                                    \
-        if (_e != hipSuccess) { (e)->err = std::string(#expr) + ": " + hipGetErrorString(_e); set_last_error((e)->err); return VS_ERR_HIP; } \
-    } while (0)
-#define E_FAIL(e, code, msg) do { (e)->err = (msg); set_last_error((e)->err); return (code); } while (0)
-
 namespace {
 
 struct Pending {
@@ -939,7 +932,7 @@ int run_pass(PlanCtx& c, Pending& pd, uint8_t* out, size_t out_stride) {
         dim3 grid((c.w + 255) / 256, (c.h + a.rows - 1) / a.rows, c.table ? c.frames : 1);
         hipLaunchKernelGGL(enh_point_kernel<false>, grid, dim3(256), 0, e->st, a);
     }
-    E_HIP(e, hipGetLastError());
+    VS_OBJ_HIP(e, hipGetLastError());
     e->passes++;
     return VS_OK;
 }
@@ -949,8 +942,8 @@ int other_tmp(PlanCtx& c, size_t bytes, int* which) {
     vs_enh* e = c.e;
     const int k = c.cur == e->d_tmp[0] ? 1 : 0;
     if (e->tmp_bytes[k] < bytes) {
-        if (e->d_tmp[k]) { E_HIP(e, hipStreamSynchronize(e->st)); (void)hipFree(e->d_tmp[k]); e->d_tmp[k] = nullptr; e->tmp_bytes[k] = 0; }
-        E_HIP(e, hipMalloc((void**)&e->d_tmp[k], bytes));
+        if (e->d_tmp[k]) { VS_OBJ_HIP(e, hipStreamSynchronize(e->st)); (void)hipFree(e->d_tmp[k]); e->d_tmp[k] = nullptr; e->tmp_bytes[k] = 0; }
+        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_tmp[k], bytes));
         e->tmp_bytes[k] = bytes;
     }
     *which = k;
@@ -959,7 +952,7 @@ int other_tmp(PlanCtx& c, size_t bytes, int* which) {
 
 // materialise the pending stages into an intermediate frame (single-frame mode only)
 int flush_mid(PlanCtx& c, Pending& pd) {
-    if (c.table) E_FAIL(c.e, VS_ERR_UNSUPPORTED, "enhancer: this stage list needs an intermediate frame (single-frame entry point only)");
+    if (c.table) return vs_obj_fail(c.e, VS_ERR_UNSUPPORTED, "enhancer: this stage list needs an intermediate frame (single-frame entry point only)");
     const size_t pitch = ((size_t)c.w * 3 + 3) & ~(size_t)3;
     int k;
     int rc = other_tmp(c, pitch * c.h, &k);
@@ -986,7 +979,7 @@ int refresh_luts(vs_enh* e, const vs_enh_params_c* p) {
     const bool cb_changed = !(e->cb_alpha == p->contrast && e->cb_beta == p->brightness);
     const bool g_changed = !(e->gamma == p->gamma);
     if (!cb_changed && !g_changed) return VS_OK;
-    E_HIP(e, hipStreamSynchronize(e->st));       // a previous upload may still read h_luts
+    VS_OBJ_HIP(e, hipStreamSynchronize(e->st));       // a previous upload may still read h_luts
     if (cb_changed) {
         const float a = (float)(double)p->contrast, b = (float)(double)p->brightness;   // convertTo(img, -1, contrast, brightness), :150
         for (int c = 0; c < 3; c++)
@@ -1002,24 +995,24 @@ int refresh_luts(vs_enh* e, const vs_enh_params_c* p) {
             }
         e->gamma = p->gamma;
     }
-    E_HIP(e, hipMemcpyAsync(e->d_luts, e->h_luts, 2 * SLOT_BYTES, hipMemcpyHostToDevice, e->st));
+    VS_OBJ_HIP(e, hipMemcpyAsync(e->d_luts, e->h_luts, 2 * SLOT_BYTES, hipMemcpyHostToDevice, e->st));
     return VS_OK;
 }
 
 int setup_unsharp(PlanCtx& c) {
     const vs_enh_params_c* p = c.p;
     const double sigma = (double)p->blur_sigma;
-    if (!(sigma > 0)) E_FAIL(c.e, VS_ERR_INVALID_ARG, "enhancer: blur_sigma must be > 0 (cv::GaussianBlur asserts)");
+    if (!(sigma > 0)) return vs_obj_fail(c.e, VS_ERR_INVALID_ARG, "enhancer: blur_sigma must be > 0 (cv::GaussianBlur asserts)");
     const int n = h_rne(sigma * 3 * 2 + 1) | 1;      // GaussianBlur(Size(0,0), sigma) on CV_8U
     const int R = n / 2;
-    if (R > MAX_R) E_FAIL(c.e, VS_ERR_UNSUPPORTED, "enhancer: blur_sigma needs more than 33 taps");
+    if (R > MAX_R) return vs_obj_fail(c.e, VS_ERR_UNSUPPORTED, "enhancer: blur_sigma needs more than 33 taps");
     uint16_t k[2 * MAX_R + 1];
     gaussian_kernel_q8(n, sigma, k);
     c.ident = k[R] >= 256;                            // all weight on the centre tap: blurred == source
     c.R = std::max(R, 1);
     memset(c.wq, 0, sizeof c.wq); memset(c.we, 0, sizeof c.we); memset(c.wo, 0, sizeof c.wo);
     if (!c.ident) {
-        if (R < 1) E_FAIL(c.e, VS_ERR_UNSUPPORTED, "enhancer: degenerate kernel");
+        if (R < 1) return vs_obj_fail(c.e, VS_ERR_UNSUPPORTED, "enhancer: degenerate kernel");
         for (int j = 0; j < n; j++) c.wq[j >> 2] |= (uint32_t)(k[j] & 255u) << (8 * (j & 3));
         for (int j = 0; j <= R; j++) {
             const uint32_t e0 = k[2 * j], e1 = (2 * j + 1 < n) ? k[2 * j + 1] : 0;
@@ -1035,7 +1028,7 @@ int setup_unsharp(PlanCtx& c) {
 
 int stats_wb(PlanCtx& c, Pending& pd) {
     vs_enh* e = c.e;
-    E_HIP(e, hipMemsetAsync(e->d_sums, 0, 3 * sizeof(unsigned long long), e->st));
+    VS_OBJ_HIP(e, hipMemsetAsync(e->d_sums, 0, 3 * sizeof(unsigned long long), e->st));
     PointArgs a{};
     a.src = c.cur; a.dst = nullptr; a.table = nullptr; a.sstride = c.cur_stride; a.w = c.w; a.h = c.h; a.luts = e->d_luts;
     a.chain = pd.pre; a.pc = c.pc; a.src_aligned = aligned4(c.cur, c.cur_stride); a.heavy = pd.pre_heavy; a.sums = e->d_sums;
@@ -1044,7 +1037,7 @@ int stats_wb(PlanCtx& c, Pending& pd) {
     hipLaunchKernelGGL(enh_point_kernel<true>, grid, dim3(256), 0, e->st, a);
     hipLaunchKernelGGL(enh_wb_lut_kernel, dim3(1), dim3(256), 0, e->st, e->d_sums, (unsigned long long)c.w * c.h, c.p->wb_strength,
                        e->d_luts + SLOT_WB * SLOT_BYTES);
-    E_HIP(e, hipGetLastError());
+    VS_OBJ_HIP(e, hipGetLastError());
     e->passes++;
     return VS_OK;
 }
@@ -1062,7 +1055,7 @@ int stats_clahe(PlanCtx& c, Pending& pd) {
         clip = (int)((double)c.p->clahe_clip_limit * tile_total / 256);
         clip = std::max(clip, 1);
     }
-    E_HIP(e, hipMemsetAsync(e->d_hist, 0, (size_t)tiles * tiles * 256 * sizeof(unsigned int), e->st));
+    VS_OBJ_HIP(e, hipMemsetAsync(e->d_hist, 0, (size_t)tiles * tiles * 256 * sizeof(unsigned int), e->st));
     HistArgs a{};
     a.src = c.cur; a.sstride = c.cur_stride; a.w = c.w; a.h = c.h; a.luts = e->d_luts; a.chain = pd.pre; a.pc = c.pc;
     a.heavy = pd.pre_heavy; a.tiles = tiles; a.tw = tw; a.th = th;
@@ -1071,7 +1064,7 @@ int stats_clahe(PlanCtx& c, Pending& pd) {
     dim3 grid(tiles * tiles, (th + a.rows_per_block - 1) / a.rows_per_block, 1);
     hipLaunchKernelGGL(enh_hist_kernel, grid, dim3(256), 0, e->st, a);
     hipLaunchKernelGGL(enh_clahe_lut_kernel, dim3(tiles * tiles), dim3(256), 0, e->st, e->d_hist, clip, lut_scale, e->d_clahe_lut);
-    E_HIP(e, hipGetLastError());
+    VS_OBJ_HIP(e, hipGetLastError());
     c.pc.tiles = tiles; c.pc.inv_tw = 1.0f / tw; c.pc.inv_th = 1.0f / th; c.pc.clahe_lut = e->d_clahe_lut;
     e->passes++;
     return VS_OK;
@@ -1099,14 +1092,14 @@ int refresh_nlm_table(vs_enh* e, int k, float h) {
         if (weight) tabn = a + 1;
     }
     if (e->nlm_cap[k] < std::max(tabn, 1)) {
-        E_HIP(e, hipStreamSynchronize(e->st));
+        VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
         if (e->d_nlm_tab[k]) (void)hipFree(e->d_nlm_tab[k]);
         e->d_nlm_tab[k] = nullptr; e->nlm_cap[k] = 0;
-        E_HIP(e, hipMalloc((void**)&e->d_nlm_tab[k], sizeof(int32_t) * std::max(tabn, 1)));
+        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_nlm_tab[k], sizeof(int32_t) * std::max(tabn, 1)));
         e->nlm_cap[k] = std::max(tabn, 1);
     }
-    E_HIP(e, hipStreamSynchronize(e->st));       // kernels of an earlier call may still read the table
-    E_HIP(e, hipMemcpy(e->d_nlm_tab[k], tab.data(), sizeof(int32_t) * std::max(tabn, 1), hipMemcpyHostToDevice));
+    VS_OBJ_HIP(e, hipStreamSynchronize(e->st));       // kernels of an earlier call may still read the table
+    VS_OBJ_HIP(e, hipMemcpy(e->d_nlm_tab[k], tab.data(), sizeof(int32_t) * std::max(tabn, 1), hipMemcpyHostToDevice));
     e->nlm_tabn[k] = tabn; e->nlm_h[k] = h; e->nlm_shift = shift;
     return VS_OK;
 }
@@ -1116,13 +1109,13 @@ int run_denoise(PlanCtx& c, Pending& pd) {
     vs_enh* e = c.e;
     int rc = VS_OK;
     if (pd.pre.n > 0 || pd.unsharp) { rc = flush_mid(c, pd); if (rc != VS_OK) return rc; }
-    else if (c.table) E_FAIL(e, VS_ERR_UNSUPPORTED, "enhancer: denoise runs frame by frame");
+    else if (c.table) return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: denoise runs frame by frame");
     const size_t n = (size_t)c.w * c.h;
     if (e->planes_bytes < 6 * n) {
-        E_HIP(e, hipStreamSynchronize(e->st));
+        VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
         if (e->d_planes) (void)hipFree(e->d_planes);
         e->d_planes = nullptr; e->planes_bytes = 0;
-        E_HIP(e, hipMalloc((void**)&e->d_planes, 6 * n));
+        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_planes, 6 * n));
         e->planes_bytes = 6 * n;
     }
     uint8_t *L = e->d_planes, *ab = L + n, *L2 = ab + 2 * n, *ab2 = L2 + n;
@@ -1140,7 +1133,7 @@ int run_denoise(PlanCtx& c, Pending& pd) {
     a.src = ab; a.dst = ab2; a.stride = a.dstride = (size_t)c.w * 2; a.wtab = e->d_nlm_tab[1]; a.tabn = e->nlm_tabn[1];
     hipLaunchKernelGGL(nlm_kernel<2>, tgrid, dim3(256), 0, e->st, a);
     hipLaunchKernelGGL(enh_merge_lab_kernel, pgrid, dim3(256), 0, e->st, e->d_tabs, L2, ab2, c.w, c.h, e->d_tmp[k], pitch);
-    E_HIP(e, hipGetLastError());
+    VS_OBJ_HIP(e, hipGetLastError());
     c.cur = e->d_tmp[k]; c.cur_stride = pitch;
     e->passes += 4;
     return VS_OK;
@@ -1155,11 +1148,11 @@ int enh_run(vs_enh* e, const vs_enh_params_c* p, const uint8_t* d_src, size_t ss
     const bool do_unsharp = p->enable_unsharp && p->sharpness > 0.f;
     const bool do_gamma = std::fabs(p->gamma - 1.f) > 1e-3;
     if ((unsigned long long)h * sstride >= (1ull << 32) || (unsigned long long)h * dstride >= (1ull << 32))
-        E_FAIL(e, VS_ERR_UNSUPPORTED, "enhancer: frames of 4 GiB and more are not supported (32-bit row offsets)");
+        return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: frames of 4 GiB and more are not supported (32-bit row offsets)");
     if (p->enable_clahe && (p->clahe_tile_grid_size < 1 || p->clahe_tile_grid_size > MAX_TILES))
-        E_FAIL(e, VS_ERR_UNSUPPORTED, "enhancer: clahe_tile_grid_size must be 1..16");
+        return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: clahe_tile_grid_size must be 1..16");
     if (table && (p->enable_white_balance || p->enable_clahe || do_denoise))
-        E_FAIL(e, VS_ERR_UNSUPPORTED, "enhancer: batch entry point supports table stages, vibrance and unsharp only");
+        return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: batch entry point supports table stages, vibrance and unsharp only");
     int rc = refresh_luts(e, p);
     if (rc != VS_OK) return rc;
     PlanCtx c{};
@@ -1288,8 +1281,8 @@ const char* vs_enh_last_error(const vs_enh* e) { return e ? e->err.c_str() : "";
 
 int vs_enh_sync(vs_enh* e) {
     if (!e) return VS_ERR_INVALID_ARG;
-    E_HIP(e, hipSetDevice(e->device));
-    E_HIP(e, hipStreamSynchronize(e->st));
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
+    VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
     return VS_OK;
 }
 
@@ -1299,7 +1292,7 @@ int vs_enh_apply_dev(vs_enh* e, const vs_enh_params_c* p, const void* d_data, in
                      size_t out_stride) {
     if (!e || !p || !d_data || !d_out || w <= 0 || h <= 0 || stride < (size_t)w * 3 || out_stride < (size_t)w * 3 || d_data == d_out)
         return VS_ERR_INVALID_ARG;
-    E_HIP(e, hipSetDevice(e->device));
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
     return enh_run(e, p, (const uint8_t*)d_data, stride, nullptr, 1, w, h, (uint8_t*)d_out, out_stride);
 }
 
@@ -1307,7 +1300,7 @@ int vs_enh_apply_batch_dev(vs_enh* e, const vs_enh_params_c* p, const void* cons
                            int h, size_t stride, size_t out_stride) {
     if (!e || !p || !d_frames || !d_outs || n <= 0 || w <= 0 || h <= 0 || stride < (size_t)w * 3 || out_stride < (size_t)w * 3)
         return VS_ERR_INVALID_ARG;
-    E_HIP(e, hipSetDevice(e->device));
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
     bool al = (stride & 3) == 0 && (out_stride & 3) == 0;
     for (int i = 0; i < n; i++) {
         if (!d_frames[i] || !d_outs[i] || d_frames[i] == d_outs[i]) return VS_ERR_INVALID_ARG;
@@ -1321,13 +1314,13 @@ int vs_enh_apply_batch_dev(vs_enh* e, const vs_enh_params_c* p, const void* cons
         return VS_OK;
     }
     if (e->table_cap < n) {
-        if (e->d_table) { E_HIP(e, hipStreamSynchronize(e->st)); (void)hipFree(e->d_table); e->d_table = nullptr; e->table_cap = 0; }
-        E_HIP(e, hipMalloc((void**)&e->d_table, (size_t)n * sizeof(ImgPair)));
+        if (e->d_table) { VS_OBJ_HIP(e, hipStreamSynchronize(e->st)); (void)hipFree(e->d_table); e->d_table = nullptr; e->table_cap = 0; }
+        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_table, (size_t)n * sizeof(ImgPair)));
         e->table_cap = n;
     }
     std::vector<ImgPair> hp(n);
     for (int i = 0; i < n; i++) { hp[i].src = d_frames[i]; hp[i].dst = d_outs[i]; }
-    E_HIP(e, hipMemcpyAsync(e->d_table, hp.data(), (size_t)n * sizeof(ImgPair), hipMemcpyHostToDevice, e->st));   // pageable: staged before return
+    VS_OBJ_HIP(e, hipMemcpyAsync(e->d_table, hp.data(), (size_t)n * sizeof(ImgPair), hipMemcpyHostToDevice, e->st));   // pageable: staged before return
     int rc = enh_run(e, p, nullptr, stride, e->d_table, n, w, h, nullptr, out_stride);
     if (rc == VS_ERR_UNSUPPORTED) {                                // stage list with an intermediate frame
         for (int i = 0; i < n; i++) {
@@ -1341,39 +1334,39 @@ int vs_enh_apply_batch_dev(vs_enh* e, const vs_enh_params_c* p, const void* cons
 int vs_enh_apply(vs_enh* e, const vs_enh_params_c* p, const uint8_t* data, int w, int h, size_t stride, uint8_t* out,
                  size_t out_stride) {
     if (!e || !p || !data || !out || w <= 0 || h <= 0 || stride < (size_t)w * 3 || out_stride < (size_t)w * 3) return VS_ERR_INVALID_ARG;
-    E_HIP(e, hipSetDevice(e->device));
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
     const size_t pitch = ((size_t)w * 3 + 3) & ~(size_t)3, bytes = pitch * h;
     if (e->io_bytes < bytes) {
-        E_HIP(e, hipStreamSynchronize(e->st));
+        VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
         if (e->d_in) (void)hipFree(e->d_in);
         if (e->d_out) (void)hipFree(e->d_out);
         e->d_in = e->d_out = nullptr; e->io_bytes = 0;
-        E_HIP(e, hipMalloc((void**)&e->d_in, bytes));
-        E_HIP(e, hipMalloc((void**)&e->d_out, bytes));
+        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_in, bytes));
+        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_out, bytes));
         e->io_bytes = bytes;
     }
-    E_HIP(e, hipMemcpy2DAsync(e->d_in, pitch, data, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, e->st));
+    VS_OBJ_HIP(e, hipMemcpy2DAsync(e->d_in, pitch, data, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, e->st));
     int rc = enh_run(e, p, e->d_in, pitch, nullptr, 1, w, h, e->d_out, pitch);
     if (rc != VS_OK) return rc;
-    E_HIP(e, hipMemcpy2DAsync(out, out_stride, e->d_out, pitch, (size_t)w * 3, h, hipMemcpyDeviceToHost, e->st));
-    E_HIP(e, hipStreamSynchronize(e->st));
+    VS_OBJ_HIP(e, hipMemcpy2DAsync(out, out_stride, e->d_out, pitch, (size_t)w * 3, h, hipMemcpyDeviceToHost, e->st));
+    VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
     return VS_OK;
 }
 
 int vs_enh_cvt_color(vs_enh* e, int code, const void* d_src, void* d_dst, size_t npix) {
     if (!e || !d_src || !d_dst || code < VS_CVT_BGR2HSV || code > VS_CVT_LAB2BGR) return VS_ERR_INVALID_ARG;
     if (npix == 0) return VS_OK;
-    E_HIP(e, hipSetDevice(e->device));
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
     hipLaunchKernelGGL(enh_cvt_color_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, e->st, e->d_tabs, (const uint8_t*)d_src,
                        (uint8_t*)d_dst, npix, code);
-    E_HIP(e, hipGetLastError());
+    VS_OBJ_HIP(e, hipGetLastError());
     return VS_OK;
 }
 
 int vs_enh_gaussian_blur(vs_enh* e, const void* d_src, size_t stride, int w, int h, double sigma, void* d_dst, size_t dstride) {
     if (!e || !d_src || !d_dst || w <= 0 || h <= 0 || stride < (size_t)w * 3 || dstride < (size_t)w * 3 || d_src == d_dst)
         return VS_ERR_INVALID_ARG;
-    E_HIP(e, hipSetDevice(e->device));
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
     vs_enh_params_c p;
     vs_enh_params_default(&p);
     p.blur_sigma = (float)sigma; p.enable_unsharp = 1; p.sharpness = 1.f;

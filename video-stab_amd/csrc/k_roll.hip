@@ -652,11 +652,10 @@ struct vs_roll {
     std::vector<Job> pending;            // handed over, not yet a batch
     long nbatches = 0;
     std::vector<std::thread> workers;
-    std::mutex mu;
+    mutable std::mutex mu;               // (mutable: vs_roll_get_state reads the angle the workers advance under it)
     std::condition_variable cv_job, cv_done;
     bool quit = false;
-    int worker_rc = VS_OK;
-    std::string worker_err;
+    FirstFailure failure;                // the workers' first failure (vs_roll_sync reports it)
     long nv_in = 0, nv_done = 0;          // frames handed over / closed (angle advanced, rotation queued)
     long slow_frames = 0;                 // frames whose edge set was still growing after the first group of passes
 };
@@ -768,31 +767,30 @@ void vs_roll_destroy(vs_roll* r) {
 
 const char* vs_roll_last_error(const vs_roll* r) { return r ? r->err.c_str() : ""; }
 
+// Asynchronous NV12 frames have been handed over and not all are closed yet.
+static bool roll_in_flight(const vs_roll* r) {
+    std::lock_guard<std::mutex> g(r->mu);
+    return r->nv_in != r->nv_done;
+}
+
 // The reference passes Parameters on every call while the smoothed angle persists (RollCorrection.cpp:13-19).
 int vs_roll_set_params(vs_roll* r, const vs_roll_params_c* params) {
     if (!r || !params || params->struct_size != (int32_t)sizeof(vs_roll_params_c)) return VS_ERR_INVALID_ARG;
-    if (params->canny_aperture != 3) { r->err = "roll: only cannyAperture 3 is supported"; set_last_error(r->err); return VS_ERR_UNSUPPORTED; }
-    if (r->nv_in != r->nv_done) { const int rc = vs_roll_sync(r); if (rc != VS_OK) return rc; }      // (frames in flight keep the parameters they were given)
+    if (params->canny_aperture != 3) return vs_obj_fail(r, VS_ERR_UNSUPPORTED, "roll: only cannyAperture 3 is supported");
+    if (roll_in_flight(r)) { const int rc = vs_roll_sync(r); if (rc != VS_OK) return rc; }      // (frames in flight keep the parameters they were given)
     r->p = *params;
     return VS_OK;
 }
 
 int vs_roll_get_state(const vs_roll* r, double* smoothed_deg, double* detected_deg, int* n_lines, int* n_used) {
     if (!r) return VS_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(r->mu);            // (the workers advance the angle)
     if (smoothed_deg) *smoothed_deg = r->smoothed;
     if (detected_deg) *detected_deg = r->last_detected;
     if (n_lines) *n_lines = r->last_lines;
     if (n_used) *n_used = r->last_used;
     return VS_OK;
 }
-
-#define R_HIP(r, expr)                                                             \
-    do {                                                                           \
-        hipError_t _e = (expr);                                                    \
-        if (_e != hipSuccess) { (r)->err = std::string(#expr) + ": " + hipGetErrorString(_e); set_last_error((r)->err); return VS_ERR_HIP; } \
-    } while (0)
-#define R_TRY(r, expr)                                                             \
-    do { int _s = (expr); if (_s != VS_OK) { (r)->err = get_last_error(); return _s; } } while (0)
 
 // The angle recurrence of RollCorrection.cpp:76-77, :106-135 on a frame's line statistics.
 static void roll_update(vs_roll* r, const RollResult& res) {
@@ -816,28 +814,28 @@ static void roll_update(vs_roll* r, const RollResult& res) {
 // autoCorrectRoll on device buffers (BGR8 in, BGR8 out, same size)
 int vs_roll_correct_dev(vs_roll* r, const void* d_data, int w, int h, size_t stride, void* d_out, size_t out_stride) {
     if (!r || !d_data || !d_out || w <= 0 || h <= 0 || stride < (size_t)w * 3 || out_stride < (size_t)w * 3) return VS_ERR_INVALID_ARG;
-    R_HIP(r, hipSetDevice(r->device));
-    if (r->nv_in != r->nv_done) R_TRY(r, vs_roll_sync(r));         // (asynchronous NV12 frames first: one angle, one order)
+    VS_OBJ_HIP(r, hipSetDevice(r->device));
+    if (roll_in_flight(r)) VS_OBJ_TRY(r, vs_roll_sync(r));         // (asynchronous NV12 frames first: one angle, one order)
     const vs_roll_params_c& p = r->p;
     if (r->first) { r->first = false; r->smoothed = 0.0; }                                       // :24-27
     int sw = (int)(w * p.scale_factor), sh = (int)(h * p.scale_factor);                         // :35-38
     if (!(sw > 0 && sh > 0)) { sw = w; sh = h; }                                                 // :40-45
-    R_TRY(r, roll_work_alloc(r->wk, sw, sh, p.hough_rho, p.hough_theta, r->st));
+    VS_OBJ_TRY(r, roll_work_alloc(r->wk, sw, sh, p.hough_rho, p.hough_theta, r->st));
     RollWork& k = r->wk;
     // resize + BGR2GRAY (:41,:51), Canny (:54-61), HoughLines (:66-73), angle statistics (:106-119)
-    R_TRY(r, launch_resize_gray((const uint8_t*)d_data, stride, w, h, VS_FMT_BGR8, k.gray, sw, sw, sh, r->st));
-    R_TRY(r, run_canny(k, k.gray, sw, p.canny_threshold_low, p.canny_threshold_high, nullptr, 0, r->st, /*unchecked=*/true));
-    R_TRY(r, run_hough(k, nullptr, 0, p.hough_threshold, p.angle_filter_min, p.angle_filter_max, r->st));
+    VS_OBJ_TRY(r, launch_resize_gray((const uint8_t*)d_data, stride, w, h, VS_FMT_BGR8, k.gray, sw, sw, sh, r->st));
+    VS_OBJ_TRY(r, run_canny(k, k.gray, sw, p.canny_threshold_low, p.canny_threshold_high, nullptr, 0, r->st, /*unchecked=*/true));
+    VS_OBJ_TRY(r, run_hough(k, nullptr, 0, p.hough_threshold, p.angle_filter_min, p.angle_filter_max, r->st));
     RollResult res;
     int32_t growing = 0;
-    R_HIP(r, hipMemcpyAsync(&res, k.res, sizeof res, hipMemcpyDeviceToHost, r->st));
-    R_HIP(r, hipMemcpyAsync(&growing, k.hflags + 3, 4, hipMemcpyDeviceToHost, r->st));
-    R_HIP(r, hipStreamSynchronize(r->st));
+    VS_OBJ_HIP(r, hipMemcpyAsync(&res, k.res, sizeof res, hipMemcpyDeviceToHost, r->st));
+    VS_OBJ_HIP(r, hipMemcpyAsync(&growing, k.hflags + 3, 4, hipMemcpyDeviceToHost, r->st));
+    VS_OBJ_HIP(r, hipStreamSynchronize(r->st));
     if (growing) {          // the edge set was still growing after four passes: finish it and redo the line search
-        R_TRY(r, hyst_finish(k, r->st));
-        R_TRY(r, run_hough(k, nullptr, 0, p.hough_threshold, p.angle_filter_min, p.angle_filter_max, r->st));
-        R_HIP(r, hipMemcpyAsync(&res, k.res, sizeof res, hipMemcpyDeviceToHost, r->st));
-        R_HIP(r, hipStreamSynchronize(r->st));
+        VS_OBJ_TRY(r, hyst_finish(k, r->st));
+        VS_OBJ_TRY(r, run_hough(k, nullptr, 0, p.hough_threshold, p.angle_filter_min, p.angle_filter_max, r->st));
+        VS_OBJ_HIP(r, hipMemcpyAsync(&res, k.res, sizeof res, hipMemcpyDeviceToHost, r->st));
+        VS_OBJ_HIP(r, hipStreamSynchronize(r->st));
     }
     roll_update(r, res);
     // cv::getRotationMatrix2D(center, angle, 1.0) (:141-144)
@@ -855,11 +853,11 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
     const int n = (int)jobs.size();
     const vs_roll::Job& j0 = jobs[0];
     if (!q.st) {
-        R_HIP(r, hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
-        R_HIP(r, hipEventCreateWithFlags(&q.ev, hipEventDisableTiming | hipEventBlockingSync));   // (a worker waiting for its batch spends no core on it)
-        R_HIP(r, hipHostMalloc((void**)&q.h_res, 320 * vs_roll::RB, hipHostMallocDefault));
-        R_HIP(r, hipHostMalloc((void**)&q.h_pairs, sizeof(ImgPair) * vs_roll::RB, hipHostMallocDefault));
-        R_HIP(r, hipMalloc((void**)&q.d_pairs, sizeof(ImgPair) * vs_roll::RB));
+        VS_HIP_TRY(hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
+        VS_HIP_TRY(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming | hipEventBlockingSync));   // (a worker waiting for its batch spends no core on it)
+        VS_HIP_TRY(hipHostMalloc((void**)&q.h_res, 320 * vs_roll::RB, hipHostMallocDefault));
+        VS_HIP_TRY(hipHostMalloc((void**)&q.h_pairs, sizeof(ImgPair) * vs_roll::RB, hipHostMallocDefault));
+        VS_HIP_TRY(hipMalloc((void**)&q.d_pairs, sizeof(ImgPair) * vs_roll::RB));
     }
     int sw = (int)(j0.w * p.scale_factor), sh = (int)(j0.h * p.scale_factor);                   // :35-38
     if (!(sw > 0 && sh > 0)) { sw = j0.w; sh = j0.h; }                                           // :40-45
@@ -946,7 +944,7 @@ static void roll_worker(vs_roll* r, int wi) {
             lk.lock();
             r->cv_done.wait(lk, [&] { return r->nv_done == jobs[0].seq; });
         }
-        if (rc != VS_OK && r->worker_rc == VS_OK) { r->worker_rc = rc; r->worker_err = get_last_error(); }
+        if (rc != VS_OK) r->failure.note(rc, get_last_error());
         r->nv_done += (long)jobs.size();
         lk.unlock();
         r->cv_done.notify_all();
@@ -972,14 +970,13 @@ int vs_roll_correct_nv12_dev(vs_roll* r, const void* d_surface, int w, int h, si
     if (!r || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w || out_pitch < (size_t)w) return VS_ERR_INVALID_ARG;
     if (uv_offset == 0) uv_offset = (size_t)h * pitch;
     if (out_uv_offset == 0) out_uv_offset = (size_t)h * out_pitch;
-    R_HIP(r, hipSetDevice(r->device));
+    VS_OBJ_HIP(r, hipSetDevice(r->device));
     if (r->workers.empty()) {
         try {
             if (const char* e = std::getenv("VS_ROLL_WORKERS")) r->nwk = std::max(1, std::min(std::atoi(e), (int)vs_roll::NWK));
             for (int i = 0; i < r->nwk; i++) r->workers.emplace_back(roll_worker, r, i);
         } catch (...) {
-            r->err = "roll: cannot start worker threads"; set_last_error(r->err);
-            return VS_ERR_HIP;
+            return vs_obj_fail(r, VS_ERR_HIP, "roll: cannot start worker threads");
         }
     }
     {
@@ -1008,40 +1005,37 @@ int vs_roll_correct_nv12_dev_n(vs_roll* r, const void* const* d_surfaces, void* 
 
 int vs_roll_sync(vs_roll* r) {
     if (!r) return VS_ERR_INVALID_ARG;
-    R_HIP(r, hipSetDevice(r->device));
+    VS_OBJ_HIP(r, hipSetDevice(r->device));
+    FirstFailure wf;
     if (!r->workers.empty()) {          // asynchronous NV12 frames: until the last one is closed
         std::unique_lock<std::mutex> lk(r->mu);
         roll_flush_pending(r);
         r->cv_job.notify_all();
         r->cv_done.wait(lk, [&] { return r->nv_done == r->nv_in; });
-        if (r->worker_rc != VS_OK) {
-            const int rc = r->worker_rc;
-            r->err = r->worker_err; set_last_error(r->err);
-            r->worker_rc = VS_OK;
-            return rc;
-        }
+        wf = r->failure.take();
     }
-    R_HIP(r, hipStreamSynchronize(r->st));
+    VS_OBJ_HIP(r, hipStreamSynchronize(r->st));       // (the rotations the workers queued, also when one of them failed)
+    if (wf.rc != VS_OK) return vs_obj_fail(r, wf.rc, wf.msg);
     return VS_OK;
 }
 
 int vs_roll_correct(vs_roll* r, const uint8_t* data, int w, int h, size_t stride, uint8_t* out, size_t out_stride) {
     if (!r || !data || !out || w <= 0 || h <= 0) return VS_ERR_INVALID_ARG;
-    R_HIP(r, hipSetDevice(r->device));
+    VS_OBJ_HIP(r, hipSetDevice(r->device));
     const size_t row = (size_t)w * 3, bytes = row * h;
     if (r->io_bytes < bytes) {
         if (r->d_in) (void)hipFree(r->d_in);
         if (r->d_out) (void)hipFree(r->d_out);
         r->d_in = r->d_out = nullptr;
-        R_HIP(r, hipMalloc((void**)&r->d_in, bytes));
-        R_HIP(r, hipMalloc((void**)&r->d_out, bytes));
+        VS_OBJ_HIP(r, hipMalloc((void**)&r->d_in, bytes));
+        VS_OBJ_HIP(r, hipMalloc((void**)&r->d_out, bytes));
         r->io_bytes = bytes;
     }
-    R_HIP(r, hipMemcpy2DAsync(r->d_in, row, data, stride, row, h, hipMemcpyHostToDevice, r->st));
+    VS_OBJ_HIP(r, hipMemcpy2DAsync(r->d_in, row, data, stride, row, h, hipMemcpyHostToDevice, r->st));
     int rc = vs_roll_correct_dev(r, r->d_in, w, h, row, r->d_out, row);
     if (rc != VS_OK) return rc;
-    R_HIP(r, hipMemcpy2DAsync(out, out_stride, r->d_out, row, row, h, hipMemcpyDeviceToHost, r->st));
-    R_HIP(r, hipStreamSynchronize(r->st));
+    VS_OBJ_HIP(r, hipMemcpy2DAsync(out, out_stride, r->d_out, row, row, h, hipMemcpyDeviceToHost, r->st));
+    VS_OBJ_HIP(r, hipStreamSynchronize(r->st));
     return VS_OK;
 }
 

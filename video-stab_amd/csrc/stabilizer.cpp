@@ -110,6 +110,7 @@ struct vs_batch;
 int group_drain(vs_batch* g);
 int group_run(vs_batch* g);
 bool group_holds_warps(const vs_batch* g);
+const FirstFailure& group_failure(const vs_batch* g);     // rc VS_OK: the group has not failed
 vs_batch* group_new_own(vs_stab* s);
 void group_delete(vs_batch* g);
 
@@ -280,25 +281,6 @@ struct StageScope {
     }
 };
 
-int fail(vs_stab* s, int code, const std::string& msg) {
-    s->err = msg;
-    set_last_error(msg);
-    return code;
-}
-
-#define S_HIP(s, expr)                                                                   \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess)                                                            \
-            return fail((s), VS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-#define S_TRY(s, expr)                                  \
-    do {                                                \
-        int _r = (expr);                                \
-        if (_r != VS_OK) { (s)->err = get_last_error(); return _r; } \
-    } while (0)
-
 int effective_radius(int r) { return std::max(5, std::min(r, 35)); }
 
 // enableVirtualCanvas acts where the reference reaches it: not behind the crop-and-zoom returns (Stabilizer.cpp:1108-1127)
@@ -322,14 +304,23 @@ int drain_batch(vs_stab* s) {
 }
 
 int sync_all(vs_stab* s) {
-    S_HIP(s, hipSetDevice(s->device));
-    S_TRY(s, drain_batch(s));
-    S_TRY(s, flush_warps(s));
-    if (s->st_warp) S_HIP(s, hipStreamSynchronize(s->st_warp));
-    if (s->st_pre) S_HIP(s, hipStreamSynchronize(s->st_pre));
-    if (s->st_det) S_HIP(s, hipStreamSynchronize(s->st_det));
-    if (s->st) S_HIP(s, hipStreamSynchronize(s->st));
+    VS_OBJ_HIP(s, hipSetDevice(s->device));
+    VS_OBJ_TRY(s, drain_batch(s));
+    VS_OBJ_TRY(s, flush_warps(s));
+    if (s->st_warp) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
+    if (s->st_pre) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));
+    if (s->st_det) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_det));
+    if (s->st) VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
     return VS_OK;
+}
+
+// Whatever the streams hold, failed or not, has run (before buffers go).
+void wait_streams(vs_stab* s) {
+    (void)hipSetDevice(s->device);
+    if (s->st_pre) (void)hipStreamSynchronize(s->st_pre);
+    if (s->st_det) (void)hipStreamSynchronize(s->st_det);
+    if (s->st) (void)hipStreamSynchronize(s->st);
+    if (s->st_warp) (void)hipStreamSynchronize(s->st_warp);
 }
 
 void free_all(vs_stab* s) {
@@ -383,9 +374,9 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     s->frame_bytes = s->row_bytes * s->rows_total;
     s->src_pitch = s->row_bytes;
     analysis_size(s, w, h, &s->aw, &s->ah);
-    if (s->aw < 3 || s->ah < 3) return fail(s, VS_ERR_INVALID_ARG, "analysis size too small");
+    if (s->aw < 3 || s->ah < 3) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "analysis size too small");
     // (the reference's cvtColor(BGR2GRAY) of the canvas, Stabilizer.cpp:2225, throws on anything but three channels)
-    if (canvas_on(s) && fmt != VS_FMT_BGR8) return fail(s, VS_ERR_UNSUPPORTED, "enableVirtualCanvas needs a BGR8 stream");
+    if (canvas_on(s) && fmt != VS_FMT_BGR8) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "enableVirtualCanvas needs a BGR8 stream");
     // buildOpticalFlowPyramid: levels that fit the window
     {
         int sw = s->aw, sh = s->ah;
@@ -412,7 +403,7 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     s->bq.clear(); s->kp_cur = 0; s->kp_next = 1;
     if (s->batch_active && !s->group) {            // a standalone instance: a group of one runs its batches
         s->own = group_new_own(s);
-        if (!s->own) return fail(s, VS_ERR_HIP, get_last_error());
+        if (!s->own) return vs_obj_fail(s, VS_ERR_HIP, get_last_error());
         s->group = s->own;
     }
     // (the frame queue ring - 128 frames, 3.2 GB at 4K BGR8 - is allocated by the first push that copies a frame in: a
@@ -445,8 +436,8 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     int tow, toh;
     out_size(s, w, h, &tow, &toh);
     const size_t o_tabs = take(warp_tabs_ints(std::max(w, tow), std::max(h, toh), WARP_BATCH_MAX) * sizeof(int32_t));
-    S_HIP(s, hipMalloc((void**)&s->d_all, off));
-    S_HIP(s, hipMemsetAsync(s->d_all, 0, off, s->st));
+    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_all, off));
+    VS_OBJ_HIP(s, hipMemsetAsync(s->d_all, 0, off, s->st));
     uint8_t* b = s->d_all;
     s->d_first_gray = b + o_first;
     for (int k = 0; k < s->npyr; k++)
@@ -473,25 +464,25 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     const int gmaxw = std::max(s->aw, 480), gmaxh = std::max(s->ah, 270);
     const int cap = gmaxw * gmaxh / 4 + 64;
     const size_t gwb = (gftt_work_bytes(gmaxw, gmaxh, cap) + 255) & ~(size_t)255;
-    S_HIP(s, hipMalloc(&s->d_gftt_scratch, gwb * ngw));
+    VS_OBJ_HIP(s, hipMalloc(&s->d_gftt_scratch, gwb * ngw));
     s->gws.assign(ngw, GfttWork());
     for (int k = 0; k < ngw; k++) gftt_work_carve((uint8_t*)s->d_gftt_scratch + gwb * k, gmaxw, gmaxh, cap, &s->gws[k]);
     s->gw = s->gws[0];
     s->dbg_gftt_counters = s->gw.counters;
-    S_TRY(s, get_ransac_tables(ncap, s->p.ransac_max_iters, &s->tab));
+    VS_OBJ_TRY(s, get_ransac_tables(ncap, s->p.ransac_max_iters, &s->tab));
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
     s->out_bytes = (size_t)ow * s->cn * (fmt == VS_FMT_NV12 ? oh * 3 / 2 : oh);
-    S_HIP(s, hipMalloc((void**)&s->d_out, s->out_bytes));
+    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_out, s->out_bytes));
     s->tmp_bytes = std::max(s->out_bytes, s->frame_bytes);
-    S_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
+    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
     if (s->batch_active && s->p.border_size > 0) {
         s->pad_frame_bytes = (s->tmp_bytes + 255) & ~(size_t)255;
-        S_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * B));
+        VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * B));
     }
-    S_TRY(s, launch_traj_reset(s->d_traj, s->p.smoothing_radius, s->st));
+    VS_OBJ_TRY(s, launch_traj_reset(s->d_traj, s->p.smoothing_radius, s->st));
     // the zero-fill and the reset ran on `main`; nothing may touch the buffers before that
-    S_HIP(s, hipStreamSynchronize(s->st));
+    VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
     for (int i = 0; i < EVR; i++) s->det_valid[i] = false;
     s->pts_pending[0] = s->pts_pending[1] = false;
     s->allocated = true;
@@ -532,7 +523,7 @@ void fill_traj_params(vs_stab* s) {
 int build_pyramid(vs_stab* s, int k, hipStream_t st) {
     Pyramid& P = s->pyr[k];
     for (int l = 1; l <= s->levels; l++)
-        S_TRY(s, launch_pyr_down(P.img[l - 1], s->lw[l - 1], s->lw[l - 1], s->lh[l - 1], P.img[l], s->lw[l], st));
+        VS_OBJ_TRY(s, launch_pyr_down(P.img[l - 1], s->lw[l - 1], s->lw[l - 1], s->lh[l - 1], P.img[l], s->lw[l], st));
     return VS_OK;
 }
 
@@ -544,16 +535,16 @@ inline size_t dst_uv(const vs_stab* s, const uint8_t* d_out, size_t out_stride) 
 
 // `pre` stream, part 1: the frame enters the queue ring (waits until the slot's last reader is done)
 int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMemcpyKind kind) {
-    if (s->slot_valid[slot]) S_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_slot[slot], 0));
+    if (s->slot_valid[slot]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_slot[slot], 0));
     StageScope t(s, VS_STAGE_COPY_IN, s->st_pre);
     uint8_t* dst = s->d_ring + (size_t)slot * s->frame_bytes;
     if (s->fmt == VS_FMT_NV12 && kind == hipMemcpyDeviceToDevice && s->in_uv_off) {      // decoder surface: planes apart
-        S_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->h, kind, s->st_pre));
-        S_HIP(s, hipMemcpy2DAsync(dst + (size_t)s->h * s->row_bytes, s->row_bytes, (const uint8_t*)src + s->in_uv_off, stride,
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->h, kind, s->st_pre));
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + (size_t)s->h * s->row_bytes, s->row_bytes, (const uint8_t*)src + s->in_uv_off, stride,
                                   s->row_bytes, s->h / 2, kind, s->st_pre));
         return VS_OK;
     }
-    S_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->rows_total, kind, s->st_pre));
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->rows_total, kind, s->st_pre));
     return VS_OK;
 }
 
@@ -563,23 +554,23 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     const int c = f % NPYR, pv = (f - 1) % NPYR;
     // ---- pre: gray + pyramid into buffer c.  Its previous readers were LK(f-2) (as "prev")
     // and, if frame f-3 re-detected, the detector.
-    if (f - 2 >= 1) S_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_lk[(f - 2) % EVR], 0));
-    if (f - 3 >= 1 && s->det_valid[(f - 3) % EVR]) S_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_det[(f - 3) % EVR], 0));
+    if (f - 2 >= 1) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_lk[(f - 2) % EVR], 0));
+    if (f - 3 >= 1 && s->det_valid[(f - 3) % EVR]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_det[(f - 3) % EVR], 0));
     {
         StageScope t(s, VS_STAGE_GRAY, s->st_pre);
-        S_TRY(s, launch_resize_gray(d_frame, s->src_pitch, s->w, s->h, s->fmt, s->pyr[c].img[0], s->aw, s->aw, s->ah, s->st_pre));  // :448-450
+        VS_OBJ_TRY(s, launch_resize_gray(d_frame, s->src_pitch, s->w, s->h, s->fmt, s->pyr[c].img[0], s->aw, s->aw, s->ah, s->st_pre));  // :448-450
     }
-    S_HIP(s, hipEventRecord(s->ev_gray[c], s->st_pre));
+    VS_OBJ_HIP(s, hipEventRecord(s->ev_gray[c], s->st_pre));
     {
         StageScope t(s, VS_STAGE_PYRAMID, s->st_pre);
-        S_TRY(s, build_pyramid(s, c, s->st_pre));
+        VS_OBJ_TRY(s, build_pyramid(s, c, s->st_pre));
         if (s->prev_small) {   // :598-603 (once: 480x270 -> analysis size)
-            S_TRY(s, launch_resize_gray(s->d_first_gray, 480, 480, 270, VS_FMT_GRAY8, s->pyr[pv].img[0], s->aw, s->aw, s->ah, s->st_pre));
-            S_TRY(s, build_pyramid(s, pv, s->st_pre));
+            VS_OBJ_TRY(s, launch_resize_gray(s->d_first_gray, 480, 480, 270, VS_FMT_GRAY8, s->pyr[pv].img[0], s->aw, s->aw, s->ah, s->st_pre));
+            VS_OBJ_TRY(s, build_pyramid(s, pv, s->st_pre));
             s->prev_small = false;
         }
     }
-    S_HIP(s, hipEventRecord(s->ev_pre[c], s->st_pre));
+    VS_OBJ_HIP(s, hipEventRecord(s->ev_pre[c], s->st_pre));
 
     // ---- det: every second call re-detects on the new gray image (:696-746).  Needs only
     // img[0]; its output buffer pts[pp^1] was last read by LK(f-2), which `pre` waited for.
@@ -590,13 +581,13 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     if ((++s->detect_counter % 2) == 0) {
         const int q = pp ^ 1;
         const int mc = std::min(p.max_corners, 200);
-        S_HIP(s, hipStreamWaitEvent(s->st_det, s->ev_gray[c], 0));
+        VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_det, s->ev_gray[c], 0));
         {
             StageScope t(s, VS_STAGE_GFTT, s->st_det);
-            S_TRY(s, launch_gftt(s->pyr[c].img[0], s->aw, s->aw, s->ah, mc, 0.02, 15.0, 3, s->gw, s->d_pts[q],
+            VS_OBJ_TRY(s, launch_gftt(s->pyr[c].img[0], s->aw, s->aw, s->ah, mc, 0.02, 15.0, 3, s->gw, s->d_pts[q],
                                  s->d_npts[q], s->st_det));
         }
-        S_HIP(s, hipEventRecord(s->ev_det[f % EVR], s->st_det));
+        VS_OBJ_HIP(s, hipEventRecord(s->ev_det[f % EVR], s->st_det));
         s->det_valid[f % EVR] = true;
         s->pts_event[q] = s->ev_det[f % EVR];
         s->pts_pending[q] = true;
@@ -609,9 +600,9 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     }
 
     // ---- main: LK needs this frame's pyramid and the keypoints of the last detection
-    S_HIP(s, hipStreamWaitEvent(s->st, s->ev_pre[c], 0));
+    VS_OBJ_HIP(s, hipStreamWaitEvent(s->st, s->ev_pre[c], 0));
     if (s->pts_pending[pp]) {
-        S_HIP(s, hipStreamWaitEvent(s->st, s->pts_event[pp], 0));
+        VS_OBJ_HIP(s, hipStreamWaitEvent(s->st, s->pts_event[pp], 0));
         s->pts_pending[pp] = false;
     }
     LKLevel L[MAX_PYR];
@@ -622,27 +613,37 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     const int cap = s->pts_cap[pp];
     {
         StageScope t(s, VS_STAGE_LK, s->st);
-        S_TRY(s, launch_pyr_lk(L, s->levels, s->d_pts[pp], cap, s->d_npts[pp], s->d_next, s->d_status, s->d_err,
+        VS_OBJ_TRY(s, launch_pyr_lk(L, s->levels, s->d_pts[pp], cap, s->d_npts[pp], s->d_next, s->d_status, s->d_err,
                                p.lk_win_size, p.lk_max_iters, p.lk_epsilon, s->st));   // :611-619
     }
     s->last_lk_pp = pp;
-    if (s->dbg_delay_us > 0) S_TRY(s, launch_spin(s->dbg_delay_us, s->st));        // test hook: widen the window between LK and RANSAC
+    if (s->dbg_delay_us > 0) VS_OBJ_TRY(s, launch_spin(s->dbg_delay_us, s->st));        // test hook: widen the window between LK and RANSAC
     {
         // status compaction (:629-641) + estimateAffinePartial2D (:644-659) + transform append (:660-693)
         StageScope t(s, VS_STAGE_RANSAC, s->st);
-        S_TRY(s, launch_ransac(s->d_pts[pp], s->d_next, s->d_status, std::max(cap, 0), s->d_npts[pp], s->d_vp, s->d_vc,
+        VS_OBJ_TRY(s, launch_ransac(s->d_pts[pp], s->d_next, s->d_status, std::max(cap, 0), s->d_npts[pp], s->d_vp, s->d_vc,
                                s->d_m, 4, p.ransac_threshold, p.ransac_max_iters, s->tab, s->d_counts, s->d_model,
                                s->d_inliers, s->d_info, s->d_traj, &s->tp, s->d_dbg, s->have_prev_gray ? 1 : 0, s->st));
     }
     // `pre` (pyramid buffers) and `det` (keypoint buffer pts[pp^1] two frames on) wait for this event: the tracker AND the
     // scoring / selection kernels have read pts[pp] and its count by then (recorded right behind the tracker, a re-detection
     // two frames later could overwrite the buffer under the RANSAC kernels)
-    S_HIP(s, hipEventRecord(s->ev_lk[f % EVR], s->st));
+    VS_OBJ_HIP(s, hipEventRecord(s->ev_lk[f % EVR], s->st));
     s->dbg_prev_pts = s->d_pts[pp]; s->dbg_next = s->d_next; s->dbg_status = s->d_status; s->dbg_inliers = s->d_inliers;
     s->n_transforms++;
     s->pp = next_pp;
     s->last_gray_buf = c;
     s->have_prev_gray = true;                                                         // :757-759
+    return VS_OK;
+}
+
+// A ring slot goes back to the free list behind the work on `st` that reads it.  A slot whose event cannot be recorded stays out
+// of the ring: its next writer would have nothing to wait for.
+int release_slot(vs_stab* s, int slot, hipStream_t st) {
+    if (slot < 0) return VS_OK;          // zero-copy: the frame is the caller's
+    VS_HIP_TRY(hipEventRecord(s->ev_slot[slot], st));
+    s->slot_valid[slot] = true;
+    s->free_slots.push_back(slot);
     return VS_OK;
 }
 
@@ -658,8 +659,8 @@ int flush_warps(vs_stab* s, bool on_main) {
     uint8_t* dsts[WARP_BATCH_MAX];
     for (int i = 0; i < n; i++) { srcs[i] = s->pend[i].src; dsts[i] = s->pend[i].dst; }
     if (!on_main) {
-        S_HIP(s, hipEventRecord(s->ev_emit, s->st));             // the maps of this batch are written on `main`
-        S_HIP(s, hipStreamWaitEvent(ws, s->ev_emit, 0));
+        VS_OBJ_HIP(s, hipEventRecord(s->ev_emit, s->st));             // the maps of this batch are written on `main`
+        VS_OBJ_HIP(s, hipStreamWaitEvent(ws, s->ev_emit, 0));
     }
     int rc;
     {
@@ -667,12 +668,12 @@ int flush_warps(vs_stab* s, bool on_main) {
         rc = launch_warp_plane(srcs, dsts, n, s->src_pitch, s->w, s->h, s->pend_stride, s->w, s->h, s->cn, WarpMaps{s->d_MinvB[set], 12, false},
                                VS_BORDER_BLACK, WarpTabs{WarpTabs::CALLER, s->d_tabs_def}, ws);
     }
-    if (hipEventRecord(s->ev_warp[set], ws) == hipSuccess) s->warp_valid[set] = true;
+    const hipError_t ew = hipEventRecord(s->ev_warp[set], ws);
+    if (ew == hipSuccess) s->warp_valid[set] = true;
+    else if (rc == VS_OK) rc = hip_fail(ew, "hipEventRecord(s->ev_warp[set], ws)");
     for (int i = 0; i < n; i++) {
-        const int slot = s->pend[i].slot;
-        if (slot < 0) continue;          // zero-copy: the frame is the caller's
-        if (hipEventRecord(s->ev_slot[slot], ws) == hipSuccess) s->slot_valid[slot] = true;
-        s->free_slots.push_back(slot);
+        const int rrc = release_slot(s, s->pend[i].slot, ws);
+        if (rc == VS_OK) rc = rrc;
     }
     s->pend.clear();
     s->pend_set = set ^ 1;
@@ -684,19 +685,19 @@ int flush_warps(vs_stab* s, bool on_main) {
 // joins the next batched launch.
 int defer_output(vs_stab* s, int idx, const uint8_t* frame, uint8_t* d_out, size_t out_stride, int slot) {
     hipStream_t st = s->st;
-    if (!s->pend.empty() && s->pend_stride != out_stride) S_TRY(s, flush_warps(s));
+    if (!s->pend.empty() && s->pend_stride != out_stride) VS_OBJ_TRY(s, flush_warps(s));
     const int set = s->pend_set, j = (int)s->pend.size();
     if (j == 0 && s->warp_valid[set]) {      // the previous user of this set of maps must have read them
-        S_HIP(s, hipStreamWaitEvent(st, s->ev_warp[set], 0));
+        VS_OBJ_HIP(s, hipStreamWaitEvent(st, s->ev_warp[set], 0));
         s->warp_valid[set] = false;
     }
     {
         StageScope t(s, VS_STAGE_TRAJ, st);
-        S_TRY(s, launch_traj_emit(s->d_traj, s->tp, idx, s->d_M, s->d_MinvB[set] + 12 * j, s->d_dbg, st));
+        VS_OBJ_TRY(s, launch_traj_emit(s->d_traj, s->tp, idx, s->d_M, s->d_MinvB[set] + 12 * j, s->d_dbg, st));
     }
     s->pend.push_back({frame, d_out, slot});
     s->pend_stride = out_stride;
-    if ((int)s->pend.size() >= s->warp_batch) S_TRY(s, flush_warps(s));
+    if ((int)s->pend.size() >= s->warp_batch) VS_OBJ_TRY(s, flush_warps(s));
     return VS_OK;
 }
 
@@ -717,29 +718,29 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
     s->last_out_w = ow; s->last_out_h = oh;
     const bool plain = idx < s->n_transforms && s->fmt != VS_FMT_NV12 && p.border_size <= 0 && !canvas_on(s);
     if (may_defer && plain && s->warp_batch > 1) {
-        S_TRY(s, defer_output(s, idx, frame, d_out, out_stride, slot));
+        VS_OBJ_TRY(s, defer_output(s, idx, frame, d_out, out_stride, slot));
         s->counters.frames_out++;
         return VS_OK;
     }
     {
         StageScope t(s, VS_STAGE_TRAJ, st);
-        if (canvas_on(s) && !s->d_ct) S_HIP(s, hipMalloc((void**)&s->d_ct, 4 * sizeof(float)));
-        S_TRY(s, launch_traj_emit(s->d_traj, s->tp, idx, s->d_M, s->d_Minv, s->d_dbg, st, canvas_on(s) ? s->d_ct : nullptr));
+        if (canvas_on(s) && !s->d_ct) VS_OBJ_HIP(s, hipMalloc((void**)&s->d_ct, 4 * sizeof(float)));
+        VS_OBJ_TRY(s, launch_traj_emit(s->d_traj, s->tp, idx, s->d_M, s->d_Minv, s->d_dbg, st, canvas_on(s) ? s->d_ct : nullptr));
     }
     int rc = VS_OK;
     if (idx >= s->n_transforms) {
         // Stabilizer.cpp:774-780: no transform exists for this frame (last frame of a
         // flush): the queued frame is returned as is, at its own size (no border pad).
         if (ow != s->w || oh != s->h)
-            S_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
-        S_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
+            VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
         if (s->fmt == VS_FMT_NV12)
-            S_HIP(s, hipMemcpy2DAsync(d_out + dst_uv(s, d_out, out_stride), out_stride, frame + src_uv(s), s->src_pitch, s->row_bytes,
+            VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out + dst_uv(s, d_out, out_stride), out_stride, frame + src_uv(s), s->src_pitch, s->row_bytes,
                                       s->h / 2, hipMemcpyDeviceToDevice, st));
         s->last_out_w = s->w; s->last_out_h = s->h;
     } else if (canvas_on(s)) {                                                        // :1130-1134
         // the canvas replaces the warped frame, so the warp (and a fade history behind it) cannot be observed and is not run
-        if (!s->canvas && !(s->canvas = canvas_new())) return fail(s, VS_ERR_HIP, "out of host memory");
+        if (!s->canvas && !(s->canvas = canvas_new())) return vs_obj_fail(s, VS_ERR_HIP, "out of host memory");
         StageScope t(s, VS_STAGE_WARP, st);
         rc = canvas_apply(s->canvas, p, frame, s->src_pitch, s->w, s->h, s->d_ct, s->d_traj, d_out, out_stride, st);
     } else if (s->fmt == VS_FMT_NV12) {
@@ -754,11 +755,11 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         rc = launch_make_border(frame, s->src_pitch, s->w, s->h, s->cn, s->d_tmp, prow, b, VS_BORDER_BLACK, st);
         if (rc == VS_OK && (!s->d_fade || s->fade_w != bw || s->fade_h != bh)) {     // :917-926 the first padded frame is the history
             if (s->d_fade) { (void)hipStreamSynchronize(st); (void)hipFree(s->d_fade); s->d_fade = nullptr; }
-            S_HIP(s, hipMalloc((void**)&s->d_fade, (nb + 3) & ~(size_t)3));
+            VS_OBJ_HIP(s, hipMalloc((void**)&s->d_fade, (nb + 3) & ~(size_t)3));
             s->fade_w = bw; s->fade_h = bh; s->fade_valid = false;
         }
         if (rc == VS_OK && !s->fade_valid) {
-            S_HIP(s, hipMemcpyAsync(s->d_fade, s->d_tmp, nb, hipMemcpyDeviceToDevice, st));
+            VS_OBJ_HIP(s, hipMemcpyAsync(s->d_fade, s->d_tmp, nb, hipMemcpyDeviceToDevice, st));
             s->fade_valid = true; s->fade_count = 0;
         }
         float alpha = p.fade_alpha;                                                       // :953-961
@@ -790,10 +791,8 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         rc = warp_frame(s, frame, s->src_pitch, s->w, s->h, d_out, out_stride, st);
     }
     // the slot may be overwritten once this warp has read it
-    if (slot >= 0) {
-        if (hipEventRecord(s->ev_slot[slot], st) == hipSuccess) s->slot_valid[slot] = true;
-        s->free_slots.push_back(slot);
-    }
+    const int rrc = release_slot(s, slot, st);
+    if (rc == VS_OK) rc = rrc;
     if (rc != VS_OK) { s->err = get_last_error(); return rc; }
     s->counters.frames_out++;
     return VS_OK;
@@ -807,9 +806,11 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
 int batch_enqueue(vs_stab* s, const uint8_t* frame, int slot, int f, uint8_t* d_out, size_t out_stride, int* produced) {
     const vs_params_c& p = s->p;
     const int N = s->npyr, c = f % N, pv = (f - 1) % N;
+    const FirstFailure& gf = group_failure(s->group);
+    if (gf.rc != VS_OK) return vs_obj_fail(s, gf.rc, gf.msg);
     // one output pitch per batched warp launch: a change of pitch closes the batch that is being collected
     for (const vs_stab::BFrame& q : s->bq)
-        if (q.out_due && q.out_stride != out_stride) { S_TRY(s, drain_batch(s)); break; }
+        if (q.out_due && q.out_stride != out_stride) { VS_OBJ_TRY(s, drain_batch(s)); break; }
     vs_stab::BFrame b;
     memset(&b, 0, sizeof b);
     b.f = f; b.c = c; b.pv = pv;
@@ -843,8 +844,7 @@ int batch_enqueue(vs_stab* s, const uint8_t* frame, int slot, int f, uint8_t* d_
     s->bq.push_back(b);
     // a full batch runs (a vs_batch runs the batches of its streams together: vs_batch_push_dev decides)
     if (s->group == s->own && (int)s->bq.size() >= s->batch) {
-        const int rc = group_run(s->group);
-        if (rc != VS_OK) { s->err = get_last_error(); return rc; }
+        VS_OBJ_TRY(s, group_run(s->group));
     }
     return VS_OK;
 }
@@ -886,12 +886,12 @@ int push_common(vs_stab* s, int slot, const uint8_t* zc_frame, uint8_t* d_out, s
     s->counters.frames_in++;
     if (p.crop_n_zoom && s->orig_w == 0) { s->orig_w = s->w; s->orig_h = s->h; }   // :267-269
     if (s->first) {                                                                  // :271-368
-        S_TRY(s, launch_resize_gray(frame, s->src_pitch, s->w, s->h, s->fmt, s->d_first_gray, 480, 480, 270, s->st_pre));  // :304-305
-        S_HIP(s, hipEventRecord(s->ev_first, s->st_pre));
-        S_HIP(s, hipStreamWaitEvent(s->st_det, s->ev_first, 0));
-        S_TRY(s, launch_gftt(s->d_first_gray, 480, 480, 270, p.max_corners, p.quality_level, p.min_distance,
+        VS_OBJ_TRY(s, launch_resize_gray(frame, s->src_pitch, s->w, s->h, s->fmt, s->d_first_gray, 480, 480, 270, s->st_pre));  // :304-305
+        VS_OBJ_HIP(s, hipEventRecord(s->ev_first, s->st_pre));
+        VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_det, s->ev_first, 0));
+        VS_OBJ_TRY(s, launch_gftt(s->d_first_gray, 480, 480, 270, p.max_corners, p.quality_level, p.min_distance,
                              p.block_size, s->gw, s->d_pts[0], s->d_npts[0], s->st_det));   // :354-358
-        S_HIP(s, hipEventRecord(s->ev_det[0], s->st_det));
+        VS_OBJ_HIP(s, hipEventRecord(s->ev_det[0], s->st_det));
         s->pts_event[0] = s->ev_det[0];
         s->pts_pending[0] = true;
         s->pp = 0; s->pts_cap[0] = p.max_corners;
@@ -904,32 +904,32 @@ int push_common(vs_stab* s, int slot, const uint8_t* zc_frame, uint8_t* d_out, s
         return VS_OK;
     }
     if (s->batch_active) {
-        S_TRY(s, batch_enqueue(s, frame, slot, s->next_index, d_out, out_stride, produced));
+        VS_OBJ_TRY(s, batch_enqueue(s, frame, slot, s->next_index, d_out, out_stride, produced));
         s->next_index++;
-        if (!may_defer) { S_TRY(s, drain_batch(s)); S_TRY(s, flush_warps(s)); }
+        if (!may_defer) { VS_OBJ_TRY(s, drain_batch(s)); VS_OBJ_TRY(s, flush_warps(s)); }
         return VS_OK;
     }
     s->q_slot.push_back(slot); s->q_idx.push_back(s->next_index); s->q_ptr.push_back(frame);   // :376-377
-    S_TRY(s, generate_transform(s, frame, s->next_index));                          // :380
+    VS_OBJ_TRY(s, generate_transform(s, frame, s->next_index));                          // :380
     if (p.adaptive_smoothing) {
         // params_.smoothingRadius is data dependent in this mode (:1482-1486) and
         // moves the warm-up threshold (:383): read it back (synchronises).
         int r = 0;
-        S_HIP(s, hipMemcpyAsync(&r, &s->d_traj->smoothing_radius, sizeof r, hipMemcpyDeviceToHost, s->st));
-        S_HIP(s, hipStreamSynchronize(s->st));
+        VS_OBJ_HIP(s, hipMemcpyAsync(&r, &s->d_traj->smoothing_radius, sizeof r, hipMemcpyDeviceToHost, s->st));
+        VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
         s->host_radius = r;
     }
     const int R = effective_radius(s->host_radius);                                 // :383
     if ((int)s->q_idx.size() < R) { s->next_index++; return VS_OK; }                // :384-387
-    S_TRY(s, apply_next(s, d_out, out_stride, may_defer));                          // :389
+    VS_OBJ_TRY(s, apply_next(s, d_out, out_stride, may_defer));                          // :389
     s->next_index++;
     *produced = 1;
     return VS_OK;
 }
 
 int take_slot(vs_stab* s, int* slot) {
-    if (!s->d_ring) S_HIP(s, hipMalloc((void**)&s->d_ring, s->frame_bytes * s->ring_frames));
-    if (s->free_slots.empty()) return fail(s, VS_ERR_CAPACITY, "frame ring exhausted");
+    if (!s->d_ring) VS_OBJ_HIP(s, hipMalloc((void**)&s->d_ring, s->frame_bytes * s->ring_frames));
+    if (s->free_slots.empty()) return vs_obj_fail(s, VS_ERR_CAPACITY, "frame ring exhausted");
     *slot = s->free_slots.front();
     s->free_slots.pop_front();
     return VS_OK;
@@ -937,14 +937,14 @@ int take_slot(vs_stab* s, int* slot) {
 
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
     if (w <= 0 || h <= 0 || (fmt != VS_FMT_BGR8 && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8))
-        return fail(s, VS_ERR_INVALID_ARG, "push: bad geometry/format");
-    if (fmt == VS_FMT_NV12 && ((w & 1) || (h & 1))) return fail(s, VS_ERR_INVALID_ARG, "NV12 needs even w,h");
-    if (fmt != VS_FMT_BGR8 && s->p.border_size > 0) return fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need BGR8 frames");
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: bad geometry/format");
+    if (fmt == VS_FMT_NV12 && ((w & 1) || (h & 1))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "NV12 needs even w,h");
+    if (fmt != VS_FMT_BGR8 && s->p.border_size > 0) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need BGR8 frames");
     const int cn = fmt == VS_FMT_BGR8 ? 3 : 1;
-    if (stride < (size_t)w * cn) return fail(s, VS_ERR_INVALID_ARG, "push: stride < row bytes");
-    S_HIP(s, hipSetDevice(s->device));
+    if (stride < (size_t)w * cn) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: stride < row bytes");
+    VS_OBJ_HIP(s, hipSetDevice(s->device));
     if (!s->allocated) return allocate(s, w, h, fmt);
-    if (w != s->w || h != s->h || fmt != s->fmt) return fail(s, VS_ERR_SIZE_CHANGED, "frame geometry changed; call vs_stab_clean()");
+    if (w != s->w || h != s->h || fmt != s->fmt) return vs_obj_fail(s, VS_ERR_SIZE_CHANGED, "frame geometry changed; call vs_stab_clean()");
     return VS_OK;
 }
 
@@ -961,13 +961,13 @@ void destroy_events(vs_stab* s) {
 
 int create_events(vs_stab* s) {
     auto mk = [&](hipEvent_t& e) { return hipEventCreateWithFlags(&e, hipEventDisableTiming); };
-    for (auto& e : s->ev_gray) S_HIP(s, mk(e));
-    for (auto& e : s->ev_pre) S_HIP(s, mk(e));
-    for (auto& e : s->ev_lk) S_HIP(s, mk(e));
-    for (auto& e : s->ev_det) S_HIP(s, mk(e));
-    for (auto& e : s->ev_slot) S_HIP(s, mk(e));
-    S_HIP(s, mk(s->ev_first)); S_HIP(s, mk(s->ev_hold));
-    S_HIP(s, mk(s->ev_emit)); S_HIP(s, mk(s->ev_warp[0])); S_HIP(s, mk(s->ev_warp[1]));
+    for (auto& e : s->ev_gray) VS_OBJ_HIP(s, mk(e));
+    for (auto& e : s->ev_pre) VS_OBJ_HIP(s, mk(e));
+    for (auto& e : s->ev_lk) VS_OBJ_HIP(s, mk(e));
+    for (auto& e : s->ev_det) VS_OBJ_HIP(s, mk(e));
+    for (auto& e : s->ev_slot) VS_OBJ_HIP(s, mk(e));
+    VS_OBJ_HIP(s, mk(s->ev_first)); VS_OBJ_HIP(s, mk(s->ev_hold));
+    VS_OBJ_HIP(s, mk(s->ev_emit)); VS_OBJ_HIP(s, mk(s->ev_warp[0])); VS_OBJ_HIP(s, mk(s->ev_warp[1]));
     return VS_OK;
 }
 
@@ -1055,12 +1055,8 @@ int vs_stab_create(const vs_params_c* params, int device, vs_stab** out) {
 
 void vs_stab_destroy(vs_stab* s) {
     if (!s || s->member) return;        // (a stream of a vs_batch goes with its group: vs_batch_destroy)
-    (void)hipSetDevice(s->device);
-    // the destructor may race in-flight work (vsg.cpp:1374): drain all three streams first
-    if (s->st_pre) (void)hipStreamSynchronize(s->st_pre);
-    if (s->st_det) (void)hipStreamSynchronize(s->st_det);
-    if (s->st) (void)hipStreamSynchronize(s->st);
-    if (s->st_warp) (void)hipStreamSynchronize(s->st_warp);
+    // the destructor may race in-flight work (vsg.cpp:1374): drain the streams first
+    wait_streams(s);
     free_all(s);
     if (s->d_fade) (void)hipFree(s->d_fade);
     if (s->d_ct) (void)hipFree(s->d_ct);
@@ -1074,8 +1070,9 @@ void vs_stab_destroy(vs_stab* s) {
 
 int vs_stab_clean(vs_stab* s) {   // Stabilizer.cpp:221-256
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
-    S_TRY(s, sync_all(s));
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (s->own && group_failure(s->own).rc != VS_OK) wait_streams(s);     // (a failed private group is not drained: it goes)
+    else VS_OBJ_TRY(s, sync_all(s));
     free_all(s);
     s->q_slot.clear(); s->q_idx.clear(); s->q_ptr.clear();
     s->hold_valid = false; s->hold_cur = 0;
@@ -1094,7 +1091,7 @@ int vs_stab_out_size(const vs_stab* s, int w, int h, int* out_w, int* out_h) {
 int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride, int fmt, void* d_out,
                      size_t out_stride, int* produced) {
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     *produced = 0;
     if (!d_data) return VS_OK;   // empty frame -> empty result (Stabilizer.cpp:263-265)
     int rc = prepare(s, w, h, fmt, stride);
@@ -1104,14 +1101,14 @@ int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride
         // one pitch for all frames in flight (the batched launches take it once): it may change when nothing is queued
         if (stride != s->src_pitch) {
             if (!s->q_slot.empty() || !s->bq.empty() || !s->pend.empty() || group_holds_warps(s->group))
-                return fail(s, VS_ERR_INVALID_ARG, "zero-copy mode: the row pitch may only change while no frame is queued");
+                return vs_obj_fail(s, VS_ERR_INVALID_ARG, "zero-copy mode: the row pitch may only change while no frame is queued");
             s->src_pitch = stride;
         }
         return push_common(s, -1, (const uint8_t*)d_data, (uint8_t*)d_out, out_stride, produced, true);
     }
     int slot;
-    S_TRY(s, take_slot(s, &slot));
-    S_TRY(s, enqueue_copy_in(s, slot, d_data, stride, hipMemcpyDeviceToDevice));
+    VS_OBJ_TRY(s, take_slot(s, &slot));
+    VS_OBJ_TRY(s, enqueue_copy_in(s, slot, d_data, stride, hipMemcpyDeviceToDevice));
     return push_common(s, slot, nullptr, (uint8_t*)d_out, out_stride, produced, true);
 }
 
@@ -1135,16 +1132,16 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
     if (!s || !produced) return VS_ERR_INVALID_ARG;
     *produced = 0;
     if (!s->allocated || s->q_slot.empty()) return VS_OK;
-    S_HIP(s, hipSetDevice(s->device));
-    S_TRY(s, drain_batch(s));
-    S_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
+    VS_OBJ_HIP(s, hipSetDevice(s->device));
+    VS_OBJ_TRY(s, drain_batch(s));
+    VS_OBJ_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
     *produced = 1;
     return VS_OK;
 }
 
 int vs_stab_flush_dev(vs_stab* s, void* d_out, size_t out_stride, int* produced) {   // Stabilizer.cpp:394-400
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     return flush_dev_impl(s, d_out, out_stride, produced, true);
 }
 
@@ -1160,9 +1157,9 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
     const bool have_prev = s->hold_valid;
     // (as in the synchronous call: the buffer is only looked at when a frame will be delivered into it; a held frame is
     // always a full-size one - pass-through frames only come out of vs_stab_flush's synchronous part)
-    if (have_prev && (!out || out_stride < orow)) return fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
+    if (have_prev && (!out || out_stride < orow)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
     for (auto& hld : s->d_hold)
-        if (!hld) S_HIP(s, hipMalloc((void**)&hld, s->out_bytes));
+        if (!hld) VS_OBJ_HIP(s, hipMalloc((void**)&hld, s->out_bytes));
     // A copy to or from PAGEABLE memory (the frames of a cv::Mat) keeps its caller inside hipMemcpy for the whole transfer -
     // about 0.2 ms per direction at 1080p, through the runtime's bounce buffers -, so download and upload issued from this
     // thread run one after the other: 2 520 frames/s against 4 730 with page-locked frames.  With a pageable output buffer the
@@ -1177,7 +1174,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
     } join;
     const int held_w = s->hold_w, held_h = s->hold_h;
     if (have_prev) {       // the held result: on its way while this call's frame comes in
-        S_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
+        VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
         const uint8_t* d_src = s->d_hold[s->hold_cur ^ 1];
 
         bool helped = false;
@@ -1199,21 +1196,21 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
             }
         }
         if (!helped) {
-            S_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, s->st_warp));
+            VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, s->st_warp));
         }
     }
     int slot;
-    S_TRY(s, take_slot(s, &slot));
-    S_TRY(s, enqueue_copy_in(s, slot, data, stride, hipMemcpyHostToDevice));
+    VS_OBJ_TRY(s, take_slot(s, &slot));
+    VS_OBJ_TRY(s, enqueue_copy_in(s, slot, data, stride, hipMemcpyHostToDevice));
     int now = 0;
     int rc = push_common(s, slot, nullptr, s->d_hold[s->hold_cur], orow, &now, false);
-    S_HIP(s, hipStreamSynchronize(s->st_pre));        // the caller's frame has been consumed
-    if (join.h) S_HIP(s, (hipError_t)join.wait());
-    else if (have_prev) S_HIP(s, hipStreamSynchronize(s->st_warp));
+    VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));        // the caller's frame has been consumed
+    if (join.h) VS_OBJ_HIP(s, (hipError_t)join.wait());
+    else if (have_prev) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
     if (rc != VS_OK) return rc;
     s->hold_valid = now != 0;
     if (now) {
-        S_HIP(s, hipEventRecord(s->ev_hold, s->st));
+        VS_OBJ_HIP(s, hipEventRecord(s->ev_hold, s->st));
         s->hold_cur ^= 1;
         s->hold_w = s->last_out_w; s->hold_h = s->last_out_h;
     }
@@ -1225,13 +1222,13 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
 int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, int fmt, uint8_t* out,
                  size_t out_stride, int* produced) {
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     *produced = 0;
     if (!data) return VS_OK;
     int rc = prepare(s, w, h, fmt, stride);
     if (rc != VS_OK) return rc;
     if (s->zero_copy && (s->src_pitch != s->row_bytes || (s->fmt == VS_FMT_NV12 && s->in_uv_off)))
-        return fail(s, VS_ERR_INVALID_ARG, "push: host frames cannot join a queue of pitched zero-copy surfaces");
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: host frames cannot join a queue of pitched zero-copy surfaces");
     if (s->host_pipe && !s->batch_active) return push_host_pipelined(s, data, w, h, stride, fmt, out, out_stride, produced);
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
@@ -1239,9 +1236,9 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
     // (the output buffer is checked before the frame is consumed: a bad call loses nothing)
     const int R = effective_radius(s->host_radius);
     if ((!out || out_stride < orow) && !s->first && (int)s->q_idx.size() + 1 >= R)
-        return fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
     int slot;
-    S_TRY(s, take_slot(s, &slot));
+    VS_OBJ_TRY(s, take_slot(s, &slot));
     rc = enqueue_copy_in(s, slot, data, stride, hipMemcpyHostToDevice);
     if (rc == VS_OK) rc = drain_batch(s);
     if (rc == VS_OK) rc = flush_warps(s);
@@ -1253,31 +1250,31 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
     if (*produced) {
         if (!out || out_stride < orow) {
             (void)hipStreamSynchronize(s->st_pre);
-            return fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
         }
         const int orows = fmt == VS_FMT_NV12 ? oh * 3 / 2 : oh;
-        S_HIP(s, hipStreamSynchronize(s->st_warp));   // (per-frame pipeline: the warp ran on the warp stream)
-        if (s->batch_active) S_HIP(s, hipStreamSynchronize(s->st_pre));     // batch mode: the warps run on `pre` (group_launch_ready)
-        S_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
+        VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));   // (per-frame pipeline: the warp ran on the warp stream)
+        if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));     // batch mode: the warps run on `pre` (group_launch_ready)
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
     }
     // the caller's frame must be consumed and its result delivered before returning
-    S_HIP(s, hipStreamSynchronize(s->st_pre));
-    S_HIP(s, hipStreamSynchronize(s->st));
+    VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));
+    VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
     return VS_OK;
 }
 
 int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     *produced = 0;
     if (!s->allocated) return VS_OK;
     if (s->hold_valid) {      // host pipeline: the frame the last push computed
         const size_t orow = (size_t)s->hold_w * s->cn;
-        if (!out || out_stride < orow) return fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
+        if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
         const int orows = s->fmt == VS_FMT_NV12 ? s->hold_h * 3 / 2 : s->hold_h;
-        S_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
-        S_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orow, orows, hipMemcpyDeviceToHost, s->st_warp));
-        S_HIP(s, hipStreamSynchronize(s->st_warp));
+        VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orow, orows, hipMemcpyDeviceToHost, s->st_warp));
+        VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
         s->hold_valid = false;
         s->last_out_w = s->hold_w; s->last_out_h = s->hold_h;
         *produced = 1;
@@ -1287,16 +1284,16 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     int ow, oh;
     out_size(s, s->w, s->h, &ow, &oh);
     const size_t orow = (size_t)ow * s->cn;
-    if (!out || out_stride < orow) return fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
-    S_TRY(s, drain_batch(s));
-    S_TRY(s, flush_warps(s));
+    if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
+    VS_OBJ_TRY(s, drain_batch(s));
+    VS_OBJ_TRY(s, flush_warps(s));
     int rc = flush_dev_impl(s, s->d_out, orow, produced, false);
     if (rc != VS_OK) return rc;
     const int orows = s->fmt == VS_FMT_NV12 ? oh * 3 / 2 : oh;
-    S_HIP(s, hipStreamSynchronize(s->st_warp));
-    if (s->batch_active) S_HIP(s, hipStreamSynchronize(s->st_pre));         // batch mode: the warps run on `pre`
-    S_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
-    S_HIP(s, hipStreamSynchronize(s->st));
+    VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
+    if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));         // batch mode: the warps run on `pre`
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
+    VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
     return VS_OK;
 }
 
@@ -1304,8 +1301,8 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
 // consecutive calls overlap each other and the device work.  To be chosen while no frame is queued.
 int vs_stab_set_host_pipeline(vs_stab* s, int enable) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
-    if (!s->q_slot.empty() || s->hold_valid) return fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_host_pipeline: the frame queue must be empty");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (!s->q_slot.empty() || s->hold_valid) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_host_pipeline: the frame queue must be empty");
     s->host_pipe = enable != 0;
     return VS_OK;
 }
@@ -1314,8 +1311,8 @@ int vs_stab_set_host_pipeline(vs_stab* s, int enable) {
 // launch.  A result is complete after vs_stab_sync(); every push must then be given its own d_out.
 int vs_stab_set_warp_batch(vs_stab* s, int frames) {
     if (!s || frames < 1 || frames > WARP_BATCH_MAX) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
-    if (s->allocated) { S_HIP(s, hipSetDevice(s->device)); S_TRY(s, flush_warps(s)); }
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (s->allocated) { VS_OBJ_HIP(s, hipSetDevice(s->device)); VS_OBJ_TRY(s, flush_warps(s)); }
     s->warp_batch = frames;
     return VS_OK;
 }
@@ -1325,8 +1322,8 @@ int vs_stab_set_warp_batch(vs_stab* s, int frames) {
 // vs_stab_set_warp_batch(frames)).  To be chosen before the first frame (or after vs_stab_clean).
 int vs_stab_set_batch(vs_stab* s, int frames) {
     if (!s || frames < 1 || frames > BATCH_MAX) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
-    if (s->allocated) return fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_batch: call before the first frame or after vs_stab_clean");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (s->allocated) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_batch: call before the first frame or after vs_stab_clean");
     s->batch = frames;
     if (frames > 1) s->warp_batch = std::min(frames, WARP_BATCH_MAX);
     return VS_OK;
@@ -1338,8 +1335,8 @@ int vs_stab_set_batch(vs_stab* s, int frames) {
 // the batch depth and a vs_stab_sync, or until vs_stab_flush_dev has drained the queue.  Tightly packed frames.
 int vs_stab_set_zero_copy(vs_stab* s, int enable) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
-    if (!s->q_slot.empty()) return fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_zero_copy: the frame queue must be empty");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_zero_copy: the frame queue must be empty");
     s->zero_copy = enable != 0;
     s->src_pitch = s->row_bytes;
     return VS_OK;
@@ -1349,8 +1346,8 @@ int vs_stab_set_zero_copy(vs_stab* s, int enable) {
 // UV plane with a common pitch, the UV plane `uv_offset` bytes behind the Y pointer.  0 = contiguous (h * pitch).
 int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offset) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
-    if (!s->q_slot.empty()) return fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: the frame queue must be empty");
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: the frame queue must be empty");
     s->in_uv_off = in_uv_offset;
     s->out_uv_off = out_uv_offset;
     return VS_OK;
@@ -1365,11 +1362,11 @@ int vs_stab_get_counters(vs_stab* s, vs_counters* out) {
     if (!s || !out) return VS_ERR_INVALID_ARG;
     *out = s->counters;
     if (s->allocated) {
-        S_TRY(s, sync_all(s));
+        VS_OBJ_TRY(s, sync_all(s));
         vs_debug_frame d;
         int32_t c[4] = {0, 0, 0, 0};
-        S_HIP(s, hipMemcpy(&d, s->d_dbg, sizeof d, hipMemcpyDeviceToHost));
-        S_HIP(s, hipMemcpy(c, s->dbg_gftt_counters, sizeof c, hipMemcpyDeviceToHost));
+        VS_OBJ_HIP(s, hipMemcpy(&d, s->d_dbg, sizeof d, hipMemcpyDeviceToHost));
+        VS_OBJ_HIP(s, hipMemcpy(c, s->dbg_gftt_counters, sizeof c, hipMemcpyDeviceToHost));
         out->last_features = d.n_prev;
         out->last_tracked = d.n_valid;
         out->last_inliers = d.n_inliers;
@@ -1390,13 +1387,13 @@ int vs_stab_get_debug(vs_stab* s, vs_debug_frame* out) {
     memset(out, 0, sizeof *out);
     out->out_index = -1;
     if (!s->allocated) return VS_OK;
-    S_TRY(s, sync_all(s));
-    S_HIP(s, hipMemcpy(out, s->d_dbg, sizeof *out, hipMemcpyDeviceToHost));
+    VS_OBJ_TRY(s, sync_all(s));
+    VS_OBJ_HIP(s, hipMemcpy(out, s->d_dbg, sizeof *out, hipMemcpyDeviceToHost));
     out->detected = s->last_detected ? 1 : 0;
     out->n_detected = 0;
     if (s->last_detected) {
         int32_t n = 0;
-        S_HIP(s, hipMemcpy(&n, s->dbg_det_n, sizeof n, hipMemcpyDeviceToHost));
+        VS_OBJ_HIP(s, hipMemcpy(&n, s->dbg_det_n, sizeof n, hipMemcpyDeviceToHost));
         out->n_detected = n;
     }
     if (s->counters.frames_in <= 1) { out->n_prev = 0; out->n_valid = 0; out->out_index = -1; }
@@ -1412,19 +1409,19 @@ int vs_stab_get_debug_arrays(vs_stab* s, float* prev_pts, float* curr_pts, uint8
     if (!s->allocated) return VS_OK;
     const bool first_only = s->counters.frames_in <= 1;
     if (d.n_prev > 0 && !first_only) {
-        if (prev_pts) S_HIP(s, hipMemcpy(prev_pts, s->dbg_prev_pts, (size_t)d.n_prev * 8, hipMemcpyDeviceToHost));
-        if (curr_pts) S_HIP(s, hipMemcpy(curr_pts, s->dbg_next, (size_t)d.n_prev * 8, hipMemcpyDeviceToHost));
-        if (status) S_HIP(s, hipMemcpy(status, s->dbg_status, (size_t)d.n_prev, hipMemcpyDeviceToHost));
+        if (prev_pts) VS_OBJ_HIP(s, hipMemcpy(prev_pts, s->dbg_prev_pts, (size_t)d.n_prev * 8, hipMemcpyDeviceToHost));
+        if (curr_pts) VS_OBJ_HIP(s, hipMemcpy(curr_pts, s->dbg_next, (size_t)d.n_prev * 8, hipMemcpyDeviceToHost));
+        if (status) VS_OBJ_HIP(s, hipMemcpy(status, s->dbg_status, (size_t)d.n_prev, hipMemcpyDeviceToHost));
     }
-    if (d.n_valid > 0 && inliers && !first_only) S_HIP(s, hipMemcpy(inliers, s->dbg_inliers, (size_t)d.n_valid, hipMemcpyDeviceToHost));
+    if (d.n_valid > 0 && inliers && !first_only) VS_OBJ_HIP(s, hipMemcpy(inliers, s->dbg_inliers, (size_t)d.n_valid, hipMemcpyDeviceToHost));
     if (d.n_detected > 0 && detected_pts)
-        S_HIP(s, hipMemcpy(detected_pts, s->dbg_det_pts, (size_t)d.n_detected * 8, hipMemcpyDeviceToHost));
+        VS_OBJ_HIP(s, hipMemcpy(detected_pts, s->dbg_det_pts, (size_t)d.n_detected * 8, hipMemcpyDeviceToHost));
     if (first_only) {
-        if (gray) S_HIP(s, hipMemcpy(gray, s->d_first_gray, (size_t)480 * 270, hipMemcpyDeviceToHost));
+        if (gray) VS_OBJ_HIP(s, hipMemcpy(gray, s->d_first_gray, (size_t)480 * 270, hipMemcpyDeviceToHost));
         if (aw) *aw = 480;
         if (ah) *ah = 270;
     } else {
-        if (gray) S_HIP(s, hipMemcpy(gray, s->pyr[s->last_gray_buf].img[0], (size_t)s->aw * s->ah, hipMemcpyDeviceToHost));
+        if (gray) VS_OBJ_HIP(s, hipMemcpy(gray, s->pyr[s->last_gray_buf].img[0], (size_t)s->aw * s->ah, hipMemcpyDeviceToHost));
         if (aw) *aw = s->aw;
         if (ah) *ah = s->ah;
     }
@@ -1450,7 +1447,7 @@ int vs_stab_get_stage_times(vs_stab* s, double* total_ms, int64_t* launches) {
     if (!s || !total_ms || !launches) return VS_ERR_INVALID_ARG;
     for (int i = 0; i < VS_STAGE_COUNT; i++) { total_ms[i] = 0; launches[i] = 0; }
     if (!s->st) return VS_OK;
-    S_TRY(s, sync_all(s));
+    VS_OBJ_TRY(s, sync_all(s));
     for (auto& pe : s->pending) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, pe.a, pe.b) == hipSuccess && pe.stage >= 0 && pe.stage < VS_STAGE_COUNT) {
@@ -1496,6 +1493,10 @@ struct vs_batch {
     // cannot change their geometry (vs_stab_clean is refused on them): it stays the reference until the group is freed.
     vs_stab* ref = nullptr;
     std::string err;
+    // A step that failed after it was numbered leaves its tables and events half done: the group stays failed, and every later
+    // step, drain or push of its members returns this first error.  (A standalone instance starts again with vs_stab_clean, which
+    // deletes its private group; vs_batch_destroy and vs_stab_destroy work on a failed group.)
+    FirstFailure failure;
     hipStream_t st = nullptr, st_pre = nullptr, st_det = nullptr, st_up = nullptr;      // st_up: the table uploads (the pool's warp stream: idle in batch mode)
     bool allocated = false;
     // Host images of the argument tables of a step, in page-locked memory so that their uploads are asynchronous (from pageable
@@ -1528,22 +1529,6 @@ struct vs_batch {
 };
 
 namespace {
-
-int gfail(vs_batch* g, int code, const std::string& msg) {
-    g->err = msg;
-    set_last_error(msg);
-    return code;
-}
-#define G_HIP(g, expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) return gfail((g), VS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-#define G_TRY(g, expr)                                  \
-    do {                                                \
-        int _r = (expr);                                \
-        if (_r != VS_OK) { (g)->err = get_last_error(); return _r; } \
-    } while (0)
 
 void group_free(vs_batch* g) {
     if (g->h_tables) (void)hipHostFree(g->h_tables);
@@ -1596,8 +1581,8 @@ int group_allocate(vs_batch* g) {
     g->tab_ints = s0->fmt == VS_FMT_NV12 ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
     size_t o_tabs[2];
     for (auto& o : o_tabs) o = take((size_t)g->tab_ints * cap * sizeof(int32_t));
-    G_HIP(g, hipMalloc((void**)&g->d_all, off));
-    G_HIP(g, hipMemsetAsync(g->d_all, 0, off, g->st));
+    VS_OBJ_HIP(g, hipMalloc((void**)&g->d_all, off));
+    VS_OBJ_HIP(g, hipMemsetAsync(g->d_all, 0, off, g->st));
     uint8_t* b = g->d_all;
     g->d_gf = b + o_gf;
     for (int i = 0; i < 2; i++) {
@@ -1607,9 +1592,9 @@ int group_allocate(vs_batch* g) {
         g->d_MinvB[i] = (double*)(b + o_minv[i]);
     }
     for (int i = 0; i < 2; i++) g->d_tabs[i] = (int32_t*)(b + o_tabs[i]);
-    G_HIP(g, hipHostMalloc((void**)&g->h_tables, 4 * ho));
+    VS_OBJ_HIP(g, hipHostMalloc((void**)&g->h_tables, 4 * ho));
     memset(g->h_tables, 0, 4 * ho);
-    G_HIP(g, hipStreamSynchronize(g->st));
+    VS_OBJ_HIP(g, hipStreamSynchronize(g->st));
     for (vs_batch::Ready* r : {&g->ready, &g->next}) {
         r->srcs.assign(cap, nullptr); r->dsts.assign(cap, nullptr); r->slots.assign(cap, -1); r->pad_idx.assign(cap, 0); r->owner.assign(cap, nullptr);
     }
@@ -1690,7 +1675,7 @@ int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
         if (e == hipSuccess && g->rel_valid[R.set]) e = hipStreamWaitEvent(g->st_up, g->ev_rel[R.set], 0);
         if (e == hipSuccess) e = hipEventRecord(g->ev_go, g->st_up);
         if (e == hipSuccess) e = hipStreamWaitEvent(st, g->ev_go, 0);
-        if (e != hipSuccess) return gfail(g, VS_ERR_HIP, "hipStreamWaitEvent failed");
+        if (e != hipSuccess) return vs_obj_fail(g, VS_ERR_HIP, "hipStreamWaitEvent failed");
         if (g->rel_valid[R.set]) g->pre_rel_step = std::max(g->pre_rel_step, R.step);
         g->rel_valid[R.set] = false;
     }
@@ -1698,15 +1683,16 @@ int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
         StageScope t(g->ref, VS_STAGE_WARP, st);   // (stage times of a group are booked on its reference member)
         rc = group_ready_launches(g, R.tabs_built ? VS_WARP_ONLY : VS_WARP_ALL, st);
     }
-    if (hipEventRecord(g->ev_warp[R.set], st) == hipSuccess) { g->warp_valid[R.set] = true; g->last_warp_set = R.set; }
+    const hipError_t ew = hipEventRecord(g->ev_warp[R.set], st);
+    if (ew == hipSuccess) { g->warp_valid[R.set] = true; g->last_warp_set = R.set; }
+    else if (rc == VS_OK) rc = hip_fail(ew, "hipEventRecord(g->ev_warp[R.set], st)");
     for (int i = 0; i < R.n; i++) {
-        const int slot = R.slots[i];
-        vs_stab* o = R.owner[i];
-        if (slot < 0 || !o) continue;              // zero-copy: the frame is the caller's
-        if (hipEventRecord(o->ev_slot[slot], st) == hipSuccess) o->slot_valid[slot] = true;
-        o->free_slots.push_back(slot);
+        if (!R.owner[i]) continue;
+        const int rrc = release_slot(R.owner[i], R.slots[i], st);
+        if (rc == VS_OK) rc = rrc;
     }
     R.valid = false;
+    if (rc != VS_OK) g->err = get_last_error();
     return rc;
 }
 
@@ -1714,30 +1700,14 @@ int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
 
 bool group_holds_warps(const vs_batch* g) { return g && (g->ready.valid || g->next.valid); }
 
-// One step: everything the members have queued.
-int group_run(vs_batch* g) {
-    std::vector<vs_stab*> act;
-    int n = 0, max_n = 0;
-    for (vs_stab* s : g->m)
-        if (!s->bq.empty()) { act.push_back(s); n += (int)s->bq.size(); max_n = std::max(max_n, (int)s->bq.size()); }
-    if (n == 0) return VS_OK;
-    G_HIP(g, hipSetDevice(g->device));
-    // every member with frames in this step has the reference's launch shape; the group's first step makes its first active
-    // member the reference (a member that has had no frame yet - a camera that connects late - has no geometry to compare)
-    const vs_stab* s0 = g->ref ? g->ref : act[0];
-    for (vs_stab* s : act)
-        if (!s->allocated || !s->batch_active || !same_launch_shape(s, s0))
-            return gfail(g, VS_ERR_INVALID_ARG, "vs_batch: the streams of a group share one frame geometry, pitch, input mode and launch shape "
-                                                "(analysis size, pyramid depth, tracking window, hypothesis count, border mode)");
-    if (n > g->cap || max_n > BATCH_MAX) return gfail(g, VS_ERR_CAPACITY, "vs_batch: more frames queued than a step holds");
-    if (!g->allocated) {
-        g->ref = act[0];
-        G_TRY(g, group_allocate(g));
-    }
-    const int k = g->batch_id++;
+const FirstFailure& group_failure(const vs_batch* g) { return g->failure; }
+
+// The step numbered k over the frames of `act` (n in all, at most max_n per stream), once group_run has accepted them.
+static int group_step(vs_batch* g, const std::vector<vs_stab*>& act, int n, int max_n, int k) {
+    const vs_stab* s0 = g->ref;
     // host images of this step's tables: the set step k-4 used (its tail, the last reader of anything uploaded from it, has run
     // by now unless the host is four steps ahead of the GPU - then it waits here)
-    if (k >= 4) G_HIP(g, hipEventSynchronize(g->ev_blk[k % 4]));
+    if (k >= 4) VS_OBJ_HIP(g, hipEventSynchronize(g->ev_blk[k % 4]));
     uint8_t* hset = g->h_tables + (size_t)(k % 4) * g->h_set_bytes;
     ImgPair* h_pairs = reinterpret_cast<ImgPair*>(hset + g->ho_pairs);
     uint8_t *h_lk = hset + g->ho_lk, *h_rs = hset + g->ho_rs, *h_tail = hset + g->ho_tail, *h_gf = hset + g->ho_gf, *h_seg = hset + g->ho_seg;
@@ -1746,8 +1716,8 @@ int group_run(vs_batch* g) {
     if (k >= 2 && g->pre_rel_step < k - 2) {
         // ring reuse: these pyramid slots were read by the analysis two steps ago (npyr = 2 * batch + 2).  (When that step had
         // outputs this stream has waited for its tail already, in front of its warps: nothing to wait for.)
-        G_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_blk[(k - 2) % 4], 0));
-        if (g->bdet_valid[(k - 2) % 4]) G_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_bdet[(k - 2) % 4], 0));
+        VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_blk[(k - 2) % 4], 0));
+        if (g->bdet_valid[(k - 2) % 4]) VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_bdet[(k - 2) % 4], 0));
     }
     // (The HBM-bound warps stay alone on the GPU although the host runs steps ahead: they are launches on this stream, behind the
     // pyramid of the step that issues them and in front of the next step's gray kernels - group_launch_ready.  Round 3 had them on
@@ -1782,9 +1752,9 @@ int group_run(vs_batch* g) {
             }
             const int cap = std::max(b.lk_cap, 0);
             n_max = std::max(n_max, cap);
-            G_TRY(g, lk_fill_item(h_lk + lk_item_bytes() * idx, L, s->levels, s->d_pts[b.lk_buf], cap, s->d_npts[b.lk_buf], it.next, it.status, it.err,
+            VS_OBJ_TRY(g, lk_fill_item(h_lk + lk_item_bytes() * idx, L, s->levels, s->d_pts[b.lk_buf], cap, s->d_npts[b.lk_buf], it.next, it.status, it.err,
                                   p.lk_win_size, p.lk_max_iters, p.lk_epsilon));                                    // :611-619
-            G_TRY(g, ransac_fill_item(h_rs + ransac_item_bytes() * idx, s->d_pts[b.lk_buf], it.next, it.status, cap, s->d_npts[b.lk_buf], it.vp, it.vc,
+            VS_OBJ_TRY(g, ransac_fill_item(h_rs + ransac_item_bytes() * idx, s->d_pts[b.lk_buf], it.next, it.status, cap, s->d_npts[b.lk_buf], it.vp, it.vc,
                                       it.m, 4, p.ransac_threshold, p.ransac_max_iters, s->tab, it.counts, it.model, it.inliers, it.info, s->d_traj,
                                       &s->tp, s->d_dbg, b.have_prev_gray));
             ransac_item_set_last(h_rs + ransac_item_bytes() * idx, i == ns - 1 ? 1 : 0);
@@ -1792,7 +1762,6 @@ int group_run(vs_batch* g) {
             double* minv = nullptr;
             WarpTabJob jobs[2] = {{nullptr, nullptr, nullptr, 0, 0}, {nullptr, nullptr, nullptr, 0, 0}};
             if (b.out_due) {
-                if (npend > 0 && pend_stride != b.out_stride) return gfail(g, VS_ERR_INVALID_ARG, "batch mode: one output pitch per step");
                 minv = g->d_MinvB[set] + 12 * npend;
                 R.srcs[npend] = b.out_frame; R.dsts[npend] = b.d_out; R.slots[npend] = b.out_slot; R.owner[npend] = s; R.pad_idx[npend] = npad;
                 // (launches of fewer than four frames - the rest of a step's due frames beyond a multiple of 32 - run without tables)
@@ -1815,8 +1784,8 @@ int group_run(vs_batch* g) {
         nseg++;
         if (s->bq[0].prev_small) {   // Stabilizer.cpp:598-603 (once per stream: 480x270 -> analysis size)
             StageScope t(g->ref, VS_STAGE_PYRAMID, g->st_pre);
-            G_TRY(g, launch_resize_gray(s->d_first_gray, 480, 480, 270, VS_FMT_GRAY8, s->pyr[s->bq[0].pv].img[0], s->aw, s->aw, s->ah, g->st_pre));
-            G_TRY(g, build_pyramid(s, s->bq[0].pv, g->st_pre));
+            VS_OBJ_TRY(g, launch_resize_gray(s->d_first_gray, 480, 480, 270, VS_FMT_GRAY8, s->pyr[s->bq[0].pv].img[0], s->aw, s->aw, s->ah, g->st_pre));
+            VS_OBJ_TRY(g, build_pyramid(s, s->bq[0].pv, g->st_pre));
         }
     }
     {
@@ -1842,34 +1811,34 @@ int group_run(vs_batch* g) {
         // gets to this step (as a copy on `pre` it stood between the warps and the gray kernels: 26 us of hand-over to the copy engine
         // and back on the step's longest chain).  The set was last used by step k - 2: its tail must have run.
         ImgPair* const d_pairs = g->d_pairs[dset];
-        if (k >= 2) G_HIP(g, hipStreamWaitEvent(g->st_up, g->ev_blk[(k - 2) % 4], 0));
-        G_HIP(g, hipMemcpyAsync(g->d_pairs[dset], hset, g->up_bytes, hipMemcpyHostToDevice, g->st_up));
-        G_HIP(g, hipEventRecord(g->ev_up[dset], g->st_up));
-        G_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_up[dset], 0));
+        if (k >= 2) VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_up, g->ev_blk[(k - 2) % 4], 0));
+        VS_OBJ_HIP(g, hipMemcpyAsync(g->d_pairs[dset], hset, g->up_bytes, hipMemcpyHostToDevice, g->st_up));
+        VS_OBJ_HIP(g, hipEventRecord(g->ev_up[dset], g->st_up));
+        VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_up[dset], 0));
         {
             StageScope t(g->ref, VS_STAGE_GRAY, g->st_pre);
             // NV12: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline)
             const int gfmt = s0->fmt == VS_FMT_NV12 ? VS_FMT_GRAY8 : s0->fmt;
             const int n_a = (n_detect > 0 && n_detect < n) ? n_detect : n;
-            G_TRY(g, launch_resize_gray_batch(d_pairs, n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));  // :448-450
-            G_HIP(g, hipEventRecord(g->ev_bgray, g->st_pre));      // the detector needs the analysis images of its frames only
+            VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs, n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));  // :448-450
+            VS_OBJ_HIP(g, hipEventRecord(g->ev_bgray, g->st_pre));      // the detector needs the analysis images of its frames only
             if (n_a < n)
-                G_TRY(g, launch_resize_gray_batch(d_pairs + n_a, n - n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));
+                VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs + n_a, n - n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));
         }
         StageScope t(g->ref, VS_STAGE_PYRAMID, g->st_pre);
         // One pyrDown launch per level (pyr_level_kernel): the tracker computes the derivatives it needs from the images.
         for (int l = 0; l < L; l++)
-            G_TRY(g, launch_pyr_level_batch(nullptr, d_pairs + (size_t)(l + 1) * n, n, s0->lw[l], s0->lw[l], s0->lh[l], s0->lw[l + 1], g->st_pre));
+            VS_OBJ_TRY(g, launch_pyr_level_batch(nullptr, d_pairs + (size_t)(l + 1) * n, n, s0->lw[l], s0->lw[l], s0->lh[l], s0->lw[l + 1], g->st_pre));
     }
     // (`main` waits for the event behind this step's warps when there are any: it covers the pyramid, which lies in front of them)
-    if (!g->ready.valid) G_HIP(g, hipEventRecord(g->ev_bpre, g->st_pre));
+    if (!g->ready.valid) VS_OBJ_HIP(g, hipEventRecord(g->ev_bpre, g->st_pre));
     // ---- det: every frame of the step that re-detects, one launch per GFTT stage
     int ndet = 0;
     for (vs_stab* s : act) {
         int local = 0;
         for (const vs_stab::BFrame& b : s->bq) {
             if (!b.detect) continue;
-            G_TRY(g, gftt_fill_item(h_gf + gftt_item_bytes() * ndet, s->pyr[b.c].img[0], s->aw, s->aw, s->ah, s->pts_cap[b.det_buf], 0.02, 15.0, 3,
+            VS_OBJ_TRY(g, gftt_fill_item(h_gf + gftt_item_bytes() * ndet, s->pyr[b.c].img[0], s->aw, s->aw, s->ah, s->pts_cap[b.det_buf], 0.02, 15.0, 3,
                                     s->gws[local], s->d_pts[b.det_buf], s->d_npts[b.det_buf]));                      // :740-744
             s->dbg_det_pts = s->d_pts[b.det_buf]; s->dbg_det_n = s->d_npts[b.det_buf];
             s->dbg_gftt_counters = s->gws[local].counters;
@@ -1881,22 +1850,22 @@ int group_run(vs_batch* g) {
     if (ndet > 0) {
         // starts as soon as the analysis images of its frames exist, next to the pyramid levels of this step and the tracking of
         // the previous one (the table and the reset of the counters first: they are through by the time the images are)
-        G_HIP(g, hipMemcpyAsync(g->d_gf, h_gf, gftt_item_bytes() * ndet, hipMemcpyHostToDevice, sd));
+        VS_OBJ_HIP(g, hipMemcpyAsync(g->d_gf, h_gf, gftt_item_bytes() * ndet, hipMemcpyHostToDevice, sd));
         // keypoint buffers are recycled after B + 4 detections (two steps): the tracking of the step before the previous one
         // must have read them (the GFTT scratch is only touched on this stream)
-        if (k >= 2) G_HIP(g, hipStreamWaitEvent(sd, g->ev_blk[(k - 2) % 4], 0));
-        G_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 1));
-        G_HIP(g, hipStreamWaitEvent(sd, g->ev_bgray, 0));
+        if (k >= 2) VS_OBJ_HIP(g, hipStreamWaitEvent(sd, g->ev_blk[(k - 2) % 4], 0));
+        VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 1));
+        VS_OBJ_HIP(g, hipStreamWaitEvent(sd, g->ev_bgray, 0));
         {
             StageScope t(g->ref, VS_STAGE_GFTT, sd);
-            G_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 4));
-            G_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 5));
+            VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 4));
+            VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 5));
             // the wide launches of the detection are through: the warps of the step before may go (below); the selection -
             // one workgroup per image - runs beside them
-            G_HIP(g, hipEventRecord(g->ev_bnms, sd));
-            G_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 3));
+            VS_OBJ_HIP(g, hipEventRecord(g->ev_bnms, sd));
+            VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 3));
         }
-        G_HIP(g, hipEventRecord(g->ev_bdet[k % 4], sd));
+        VS_OBJ_HIP(g, hipEventRecord(g->ev_bdet[k % 4], sd));
         g->last_det_batch = k;
     }
     g->bdet_valid[k % 4] = ndet > 0;
@@ -1907,37 +1876,37 @@ int group_run(vs_batch* g) {
     // The warps of the PREVIOUS step go out here, on `pre` behind this step's pyramid, once the wide launches of this step's
     // detection are through: nothing but the corner selection (a workgroup per image) runs beside them.
     const bool warps_go = g->ready.valid;
-    G_TRY(g, group_launch_ready(g, early ? g->ev_bnms : (wait_det ? g->ev_bdet[g->last_det_batch % 4] : (hipEvent_t) nullptr)));
+    VS_OBJ_TRY(g, group_launch_ready(g, early ? g->ev_bnms : (wait_det ? g->ev_bdet[g->last_det_batch % 4] : (hipEvent_t) nullptr)));
     // ---- main: waits for this step's gray / pyramid work, its corners and - the tracker takes every vector register of every SIMD,
     // beside it the warps would crawl - the warps just issued
-    if (warps_go && g->last_warp_set >= 0) G_HIP(g, hipStreamWaitEvent(st, g->ev_warp[g->last_warp_set], 0));
-    else G_HIP(g, hipStreamWaitEvent(st, g->ev_bpre, 0));
+    if (warps_go && g->last_warp_set >= 0) VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_warp[g->last_warp_set], 0));
+    else VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_bpre, 0));
     for (vs_stab* s : act)
-        if (s->pts_pending[0]) { G_HIP(g, hipStreamWaitEvent(st, s->pts_event[0], 0)); s->pts_pending[0] = false; }
-    if (wait_det) G_HIP(g, hipStreamWaitEvent(st, g->ev_bdet[g->last_det_batch % 4], 0));       // the tracker needs the selected corners
+        if (s->pts_pending[0]) { VS_OBJ_HIP(g, hipStreamWaitEvent(st, s->pts_event[0], 0)); s->pts_pending[0] = false; }
+    if (wait_det) VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_bdet[g->last_det_batch % 4], 0));       // the tracker needs the selected corners
     {
         StageScope t(g->ref, VS_STAGE_LK, st);
-        G_TRY(g, launch_pyr_lk_batch(g->d_lk[dset], n, n_max, s0->p.lk_win_size, st));
+        VS_OBJ_TRY(g, launch_pyr_lk_batch(g->d_lk[dset], n, n_max, s0->p.lk_win_size, st));
     }
     {
         StageScope t(g->ref, VS_STAGE_RANSAC, st);
-        G_TRY(g, launch_ransac_score_batch(g->d_rs[dset], n, s0->p.ransac_max_iters, n_max, st));
+        VS_OBJ_TRY(g, launch_ransac_score_batch(g->d_rs[dset], n, s0->p.ransac_max_iters, n_max, st));
     }
     for (vs_stab* s : act)
-        if (s->dbg_delay_us > 0) { G_TRY(g, launch_spin(s->dbg_delay_us, st)); break; }
+        if (s->dbg_delay_us > 0) { VS_OBJ_TRY(g, launch_spin(s->dbg_delay_us, st)); break; }
     // ---- ordered tails, ONE launch (a workgroup per stream): per frame in push order the trajectory append (:644-693), then
     // the map of the output that has become due (applyNextSmoothTransform sees exactly the transforms appended so far)
     if (npend > 0 && g->warp_valid[set]) {         // the previous user of this set of maps must have read them
-        G_HIP(g, hipStreamWaitEvent(st, g->ev_warp[set], 0));
+        VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_warp[set], 0));
         g->warp_valid[set] = false;
     }
     {
         StageScope t(g->ref, VS_STAGE_TRAJ, st);
-        G_TRY(g, launch_ransac_tail_group(g->d_rs[dset], g->d_tail[dset], g->d_seg[dset], g->d_tin[dset], nseg, max_n, n, any_apart, st));
+        VS_OBJ_TRY(g, launch_ransac_tail_group(g->d_rs[dset], g->d_tail[dset], g->d_seg[dset], g->d_tin[dset], nseg, max_n, n, any_apart, st));
     }
     // the keypoint and pyramid buffers of this step may be recycled (two steps on) once the tail, which still reads the points
     // and their counts, has run
-    G_HIP(g, hipEventRecord(g->ev_blk[k % 4], st));
+    VS_OBJ_HIP(g, hipEventRecord(g->ev_blk[k % 4], st));
     // the warps of this step wait for the next one (or a drain); their maps exist once the tail has run: the coordinate tables
     // are built right behind it
     R.n = npend; R.set = set; R.stride = pend_stride; R.valid = npend > 0; R.tabs_built = all_apart != 0; R.step = k;
@@ -1946,10 +1915,10 @@ int group_run(vs_batch* g) {
         g->pend_set = set ^ 1;
         if (!g->ready.tabs_built) {          // (a Kalman stream in the step: the tables as a launch behind the tail)
             StageScope t(g->ref, VS_STAGE_WARP_TABLES, st);
-            G_TRY(g, group_ready_launches(g, VS_WARP_TABLES_ONLY, st));
+            VS_OBJ_TRY(g, group_ready_launches(g, VS_WARP_TABLES_ONLY, st));
             g->ready.tabs_built = true;
         }
-        G_HIP(g, hipEventRecord(g->ev_rel[set], st));          // maps and tables of this step's warps exist
+        VS_OBJ_HIP(g, hipEventRecord(g->ev_rel[set], st));          // maps and tables of this step's warps exist
         g->rel_valid[set] = true;
     }
     for (vs_stab* s : act) {
@@ -1962,13 +1931,51 @@ int group_run(vs_batch* g) {
     return VS_OK;
 }
 
+// One step: everything the members have queued.  What refuses a step is decided before it is numbered; a failure after that
+// leaves the group failed (group_failure).
+int group_run(vs_batch* g) {
+    if (g->failure.rc != VS_OK) return vs_obj_fail(g, g->failure.rc, g->failure.msg);
+    std::vector<vs_stab*> act;
+    int n = 0, max_n = 0;
+    for (vs_stab* s : g->m)
+        if (!s->bq.empty()) { act.push_back(s); n += (int)s->bq.size(); max_n = std::max(max_n, (int)s->bq.size()); }
+    if (n == 0) return VS_OK;
+    VS_OBJ_HIP(g, hipSetDevice(g->device));
+    // every member with frames in this step has the reference's launch shape; the group's first step makes its first active
+    // member the reference (a member that has had no frame yet - a camera that connects late - has no geometry to compare)
+    const vs_stab* s0 = g->ref ? g->ref : act[0];
+    size_t out_stride = 0;
+    int ndue = 0;
+    for (vs_stab* s : act) {
+        if (!s->allocated || !s->batch_active || !same_launch_shape(s, s0))
+            return vs_obj_fail(g, VS_ERR_INVALID_ARG, "vs_batch: the streams of a group share one frame geometry, pitch, input mode and launch shape "
+                                                "(analysis size, pyramid depth, tracking window, hypothesis count, border mode)");
+        for (const vs_stab::BFrame& b : s->bq) {
+            if (!b.out_due) continue;
+            if (ndue++ > 0 && out_stride != b.out_stride) return vs_obj_fail(g, VS_ERR_INVALID_ARG, "batch mode: one output pitch per step");
+            out_stride = b.out_stride;
+        }
+    }
+    if (n > g->cap || max_n > BATCH_MAX) return vs_obj_fail(g, VS_ERR_CAPACITY, "vs_batch: more frames queued than a step holds");
+    if (!g->allocated) {
+        g->ref = act[0];
+        const int rc = group_allocate(g);
+        if (rc != VS_OK) { group_free(g); return rc; }
+    }
+    const int rc = group_step(g, act, n, max_n, g->batch_id++);
+    g->failure.note(rc, g->err);
+    return rc;
+}
+
 // Everything the members have queued is analysed and its warps are issued.  (The warps of a step normally go out with the NEXT
 // step, between its detection and its tracking; group_run issues the pending ones itself, so the step before the drained one is
 // covered too.)
 int group_drain(vs_batch* g) {
-    G_HIP(g, hipSetDevice(g->device));
-    G_TRY(g, group_run(g));                 // (issues the warps of the step before on its way; nothing queued: nothing done)
-    return group_launch_ready(g);
+    VS_OBJ_HIP(g, hipSetDevice(g->device));
+    VS_OBJ_TRY(g, group_run(g));                 // (issues the warps of the step before on its way; nothing queued: nothing done)
+    const int rc = group_launch_ready(g);
+    g->failure.note(rc, g->err);
+    return rc;
 }
 
 void group_delete(vs_batch* g) {
@@ -2076,6 +2083,7 @@ int vs_batch_push_dev(vs_batch* g, const void* const* d_frames, int w, int h, si
                       int* produced) {
     if (!g || !d_frames || !d_outs || !produced) return VS_ERR_INVALID_ARG;
     for (int i = 0; i < g->S; i++) produced[i] = 0;
+    if (g->failure.rc != VS_OK) return vs_obj_fail(g, g->failure.rc, g->failure.msg);
     bool full = false;
     for (int i = 0; i < g->S; i++) {
         if (!d_frames[i]) continue;                       // no frame for this stream in this call

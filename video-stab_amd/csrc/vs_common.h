@@ -8,25 +8,42 @@
 #include <cfloat>
 #include <cmath>
 #include <string>
+#include <utility>
 
 #include "../../include/vs_stab.h"
 
 namespace vsd {
 
 // ---- error plumbing ---------------------------------------------------------
+// One policy for the whole library.  A failed call returns a status; its message goes to the calling thread's last error
+// (vs_last_error), for a failed HIP call as "<expr>: <hipGetErrorString>".  Ops use VS_HIP_TRY / VS_TRY.  A call on an object
+// (vs_stab, vs_batch, vs_roll, vs_azc, vs_enh) uses VS_OBJ_HIP / VS_OBJ_TRY / vs_obj_fail, which also copy the message into
+// the object's `err` (vs_<obj>_last_error).
+// Thread rule: an object's `err` is written only inside that object's API calls, on the caller's thread.  Worker threads use
+// the op-level macros only and hand their first failure over in a FirstFailure under the object's mutex; the API call that
+// reports it (vs_roll_sync, vs_azc_sync) copies it into `err`.
 void set_last_error(const std::string& msg);
 const char* get_last_error();
 
-#define VS_HIP_TRY(expr)                                                                   \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess) {                                                            \
-            vsd::set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));        \
-            return (_e == hipErrorNoDevice || _e == hipErrorInvalidDevice ||               \
-                    _e == hipErrorInsufficientDriver || _e == hipErrorNoBinaryForGpu)      \
-                       ? VS_ERR_NO_DEVICE                                                  \
-                       : VS_ERR_HIP;                                                       \
-        }                                                                                  \
+// Sets the last error for the failed HIP call `expr` and returns its status.
+inline int hip_fail(hipError_t e, const char* expr) {
+    set_last_error(std::string(expr) + ": " + hipGetErrorString(e));
+    return (e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorInsufficientDriver || e == hipErrorNoBinaryForGpu)
+               ? VS_ERR_NO_DEVICE
+               : VS_ERR_HIP;
+}
+
+template <typename Obj>
+int vs_obj_fail(Obj* o, int code, const std::string& msg) {
+    o->err = msg;
+    set_last_error(msg);
+    return code;
+}
+
+#define VS_HIP_TRY(expr)                                     \
+    do {                                                     \
+        hipError_t _e = (expr);                              \
+        if (_e != hipSuccess) return vsd::hip_fail(_e, #expr); \
     } while (0)
 
 #define VS_TRY(expr)                      \
@@ -34,6 +51,36 @@ const char* get_last_error();
         int _s = (expr);                  \
         if (_s != VS_OK) return _s;       \
     } while (0)
+
+#define VS_OBJ_HIP(o, expr)                                                            \
+    do {                                                                               \
+        hipError_t _e = (expr);                                                        \
+        if (_e != hipSuccess) {                                                        \
+            const int _s = vsd::hip_fail(_e, #expr);                                   \
+            (o)->err = vsd::get_last_error();                                          \
+            return _s;                                                                 \
+        }                                                                              \
+    } while (0)
+
+#define VS_OBJ_TRY(o, expr)                                                            \
+    do {                                                                               \
+        int _s = (expr);                                                               \
+        if (_s != VS_OK) { (o)->err = vsd::get_last_error(); return _s; }             \
+    } while (0)
+
+// The first failure of an object's worker threads; noted and taken under the object's mutex.
+struct FirstFailure {
+    int rc = VS_OK;
+    std::string msg;
+    void note(int code, const std::string& m) {
+        if (rc == VS_OK && code != VS_OK) { rc = code; msg = m; }
+    }
+    FirstFailure take() {   // the record for the reporting call; this one starts again
+        FirstFailure f;
+        std::swap(f, *this);
+        return f;
+    }
+};
 
 int ensure_device();  // VS_OK when a gfx950-class device is usable
 
