@@ -153,7 +153,7 @@ namespace vs {
         Stabilizer(const Stabilizer &other);
         Stabilizer &operator=(const Stabilizer &other);
 
-        /// BGR CV_8UC3 frame in; stabilized frame out, or an empty Mat while the
+        /// BGR CV_8UC3 or BGRA (BGRx) 8-bit four-channel frame in; stabilized frame of the same type out, or an empty Mat while the
         /// first clamp(smoothingRadius,5,35)-1 frames are queued (reference Stabilizer.cpp:258-392).
         cv::Mat stabilize(const cv::Mat &frame);
 
@@ -175,6 +175,7 @@ namespace vs {
         vs_stab *impl_ = nullptr;
         int device_ = 0;
         int frameWidth_ = 0, frameHeight_ = 0;   // geometry of the stream (set by the first frame)
+        int frameType_ = CV_8UC3;                // its cv::Mat type: CV_8UC3 (BGR) or four channels (BGRA)
         // page-locked host memory (Parameters::pinHostFrames): ring of output frames, registered input buffers
         struct OutSlot { cv::Mat m; bool pinned = false; };
         struct InPin { const unsigned char *p = nullptr; size_t bytes = 0; int seen = 0; int idle = 0; bool pinned = false; };

@@ -30,7 +30,8 @@ extern "C" {
 /* 2: VS_STAGE_COUNT grew to 9 (VS_STAGE_WARP_TABLES: the arrays of vs_stab_get_stage_times), vs_stab_enable_graph is gone
  *    (round 2), vs_batch_* and vs_dev_copy_rate / vs_dev_memcpy_d2d added.  (The pipelined host call is chosen with
  *    vs_stab_set_host_pipeline - Parameters::hostPipeline of the C++ class - not through vs_params_c, whose layout is unchanged.)
- *    Added since without a layout change: vs_batch_create_params (round 4). */
+ *    Added since without a layout change: vs_batch_create_params (round 4); the pixel formats VS_FMT_BGRA8,
+ *    VS_FMT_RGBA8 and VS_FMT_RGB8. */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -46,7 +47,10 @@ typedef enum vs_status {
 typedef enum vs_pixfmt {
     VS_FMT_BGR8 = 0,          /* interleaved B,G,R  (cv::Mat CV_8UC3)         */
     VS_FMT_NV12 = 1,          /* Y plane (h rows) followed by UV plane (h/2)  */
-    VS_FMT_GRAY8 = 2
+    VS_FMT_GRAY8 = 2,
+    VS_FMT_BGRA8 = 3,         /* interleaved B,G,R,A (cv::Mat CV_8UC4; BGRx) */
+    VS_FMT_RGBA8 = 4,         /* interleaved R,G,B,A                          */
+    VS_FMT_RGB8 = 5           /* interleaved R,G,B                            */
 } vs_pixfmt;
 
 /* Stabilizer.cpp:31-38 mapBorderMode() */
@@ -397,7 +401,8 @@ const char* vs_last_error(void);           /* thread-local, op-level calls    */
 /* cv::warpAffine(src,dst,T,size,INTER_LINEAR,BORDER_CONSTANT) -
  * Stabilizer.cpp:1056-1060.  M = forward 2x3 float matrix as the reference
  * builds it (:902-908).  `batch` frames of identical geometry, frame b at
- * d_src + b*src_frame_bytes with matrix M + 6*b.  cn = 3 (BGR8) or 1. */
+ * d_src + b*src_frame_bytes with matrix M + 6*b.  cn = 3 (BGR8, RGB8), 4 (BGRA8,
+ * RGBA8: every channel warped alike) or 1. */
 int vs_op_warp_affine(const void* d_src, size_t src_stride, size_t src_frame_bytes,
                       void* d_dst, size_t dst_stride, size_t dst_frame_bytes,
                       int w, int h, int cn, const float* M, int batch, void* stream);
@@ -413,7 +418,8 @@ int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst,
  * fn 3 atan2f: pair i of a fixed generator.  tests/test_libm.py compares it with the same sum over the host libm's values. */
 int vs_op_libm_checksum(int fn, uint64_t start, uint64_t count, uint64_t* result);
 /* cv::resize(INTER_LINEAR) + cv::cvtColor(BGR2GRAY) - Stabilizer.cpp:304-305,
- * 448-450.  fmt BGR8 (resize then gray), GRAY8 / NV12 (luma plane resize). */
+ * 448-450.  fmt BGR8 / BGRA8 / RGBA8 / RGB8 (resize per channel, then gray from
+ * B, G, R; alpha ignored), GRAY8 / NV12 (luma plane resize). */
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt,
                       void* d_dst, size_t dst_stride, int dw, int dh, void* stream);
 /* cv::pyrDown as used inside calcOpticalFlowPyrLK - Stabilizer.cpp:611 */

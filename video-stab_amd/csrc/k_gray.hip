@@ -9,6 +9,9 @@
 //  * otherwise 11-bit horizontal coefficients, vertical pass
 //      (((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2
 //  * gray = (B*3735 + G*19235 + R*9798 + 2^14) >> 15
+// Colour frames come as BGR8, RGB8, BGRA8 or RGBA8: BI is the byte of B inside a pixel (0 or 2; R sits at 2 - BI), PS the
+// pixel's size (3 or 4).  Every channel is resized as it is and the gray value read from the B, G and R results, as
+// cv::resize + cv::cvtColor(BGR2GRAY / BGRA2GRAY) do on the same Mat; the fourth byte is never read into the gray image.
 #include "vs_common.h"
 
 namespace vsd {
@@ -21,6 +24,7 @@ __device__ __forceinline__ uint32_t bgr_to_gray(uint32_t b, uint32_t g, uint32_t
 }
 
 // ---- exact 2x, BGR -> gray: 4 output pixels per lane --------------------------
+template <int BI, int PS>
 __global__ __launch_bounds__(NT) void half_bgr_gray_kernel(const uint8_t* __restrict__ src_,
                                                            size_t sstride, uint8_t* __restrict__ dst_,
                                                            size_t dstride, int dw, int dh, int vec_ok,
@@ -32,16 +36,16 @@ __global__ __launch_bounds__(NT) void half_bgr_gray_kernel(const uint8_t* __rest
     const int y = blockIdx.y;
     const int x = gx * 4;
     if (x >= dw || y >= dh) return;
-    const uint8_t* r0 = src + (size_t)(2 * y) * sstride + (size_t)x * 6;
+    const uint8_t* r0 = src + (size_t)(2 * y) * sstride + (size_t)x * (2 * PS);
     const uint8_t* r1 = r0 + sstride;
     uint8_t* d = dst + (size_t)y * dstride + x;
     if (vec_ok && x + 3 < dw) {
-        // 24 contiguous bytes per row and lane (8-byte aligned)
-        uint32_t a[6], b[6];
+        // 8 source pixels = 24 / 32 contiguous bytes per row and lane (8-byte aligned)
+        uint32_t a[2 * PS], b[2 * PS];
         const uint2* p0 = reinterpret_cast<const uint2*>(r0);
         const uint2* p1 = reinterpret_cast<const uint2*>(r1);
 #pragma unroll
-        for (int i = 0; i < 3; i++) {
+        for (int i = 0; i < PS; i++) {
             uint2 u = p0[i], v = p1[i];
             a[2 * i] = u.x; a[2 * i + 1] = u.y;
             b[2 * i] = v.x; b[2 * i + 1] = v.y;
@@ -53,17 +57,17 @@ __global__ __launch_bounds__(NT) void half_bgr_gray_kernel(const uint8_t* __rest
             uint32_t c[3];
 #pragma unroll
             for (int k = 0; k < 3; k++)
-                c[k] = (byte_of(a, 6 * i + k) + byte_of(a, 6 * i + 3 + k) + byte_of(b, 6 * i + k) +
-                        byte_of(b, 6 * i + 3 + k) + 2u) >> 2;
-            out |= bgr_to_gray(c[0], c[1], c[2]) << (8 * i);
+                c[k] = (byte_of(a, 2 * PS * i + k) + byte_of(a, 2 * PS * i + PS + k) + byte_of(b, 2 * PS * i + k) +
+                        byte_of(b, 2 * PS * i + PS + k) + 2u) >> 2;
+            out |= bgr_to_gray(c[BI], c[1], c[2 - BI]) << (8 * i);
         }
         *reinterpret_cast<uint32_t*>(d) = out;
     } else {
         for (int i = 0; i < 4 && x + i < dw; i++) {
             uint32_t c[3];
             for (int k = 0; k < 3; k++)
-                c[k] = (r0[6 * i + k] + r0[6 * i + 3 + k] + r1[6 * i + k] + r1[6 * i + 3 + k] + 2u) >> 2;
-            d[i] = (uint8_t)bgr_to_gray(c[0], c[1], c[2]);
+                c[k] = (r0[2 * PS * i + k] + r0[2 * PS * i + PS + k] + r1[2 * PS * i + k] + r1[2 * PS * i + PS + k] + 2u) >> 2;
+            d[i] = (uint8_t)bgr_to_gray(c[BI], c[1], c[2 - BI]);
         }
     }
 }
@@ -75,6 +79,7 @@ __global__ __launch_bounds__(NT) void half_bgr_gray_kernel(const uint8_t* __rest
 // eight independent loads per lane in flight, 2-byte stores.
 constexpr int HG_ROWS = 4;
 struct __attribute__((aligned(4))) G3 { uint32_t a, b, c; };
+template <int BI>
 __global__ __launch_bounds__(NT) void half_bgr_gray12_kernel(size_t sstride, size_t dstride, int dw, int dh, const ImgPair* __restrict__ table) {
     const uint8_t* __restrict__ src = static_cast<const uint8_t*>(table[blockIdx.z].src);
     uint8_t* __restrict__ dst = static_cast<uint8_t*>(table[blockIdx.z].dst);
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(NT) void half_bgr_gray12_kernel(size_t sstride, siz
 #pragma unroll
             for (int k = 0; k < 3; k++)
                 c[k] = (byte_of(t[r], 6 * i + k) + byte_of(t[r], 6 * i + 3 + k) + byte_of(u[r], 6 * i + k) + byte_of(u[r], 6 * i + 3 + k) + 2u) >> 2;
-            g[i] = bgr_to_gray(c[0], c[1], c[2]);
+            g[i] = bgr_to_gray(c[BI], c[1], c[2 - BI]);
         }
         uint8_t* d = dst + (size_t)y * dstride + x;
         if (x + 1 < dw) *reinterpret_cast<uint16_t*>(d) = (uint16_t)(g[0] | (g[1] << 8));
@@ -116,8 +121,55 @@ __global__ __launch_bounds__(NT) void half_bgr_gray12_kernel(size_t sstride, siz
     }
 }
 
-// ---- general bilinear (any scale), CN = 3 (-> gray) or 1 ----------------------
-template <int CN, bool TO_GRAY>
+// ---- exact 2x, four-byte pixels -> gray, batched launches: one 16-byte load per row and lane -----------------------------
+// The 12-byte kernel's scheme for BGRA8 / RGBA8: a lane takes TWO output pixels = 4 source pixels = 16 bytes per row (one dwordx4
+// load; a wave's load is 1 KiB contiguous) of HG_ROWS output rows, eight loads per lane in flight.  The fourth byte of every pixel
+// is loaded with the others and never summed.
+template <int BI>
+__global__ __launch_bounds__(NT) void half_bgra_gray16_kernel(size_t sstride, size_t dstride, int dw, int dh, const ImgPair* __restrict__ table) {
+    const uint8_t* __restrict__ src = static_cast<const uint8_t*>(table[blockIdx.z].src);
+    uint8_t* __restrict__ dst = static_cast<uint8_t*>(table[blockIdx.z].dst);
+    const int x = (blockIdx.x * NT + threadIdx.x) * 2;             // first of this lane's two output pixels
+    const int y0 = blockIdx.y * HG_ROWS;
+    if (x >= dw) return;
+    uint4 t[HG_ROWS], u[HG_ROWS];
+#pragma unroll
+    for (int r = 0; r < HG_ROWS; r++) {
+        const int y = min(y0 + r, dh - 1);                          // rows past the image repeat the last one (not stored)
+        const uint8_t* p = src + (size_t)(2 * y) * sstride + (size_t)x * 8;
+        if (x + 1 < dw) {
+            t[r] = *reinterpret_cast<const uint4*>(p);
+            u[r] = *reinterpret_cast<const uint4*>(p + sstride);
+        } else {                                                    // odd width: the last lane has one pixel (8 bytes per row)
+            const uint2 a = *reinterpret_cast<const uint2*>(p), b = *reinterpret_cast<const uint2*>(p + sstride);
+            t[r] = make_uint4(a.x, a.y, 0u, 0u);
+            u[r] = make_uint4(b.x, b.y, 0u, 0u);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < HG_ROWS; r++) {
+        const int y = y0 + r;
+        if (y >= dh) break;
+        // source pixels 2i and 2i + 1 of the two rows are the dwords (x, y) / (z, w)
+        const uint32_t w[2][4] = {{t[r].x, t[r].y, u[r].x, u[r].y}, {t[r].z, t[r].w, u[r].z, u[r].w}};
+        uint32_t g[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            uint32_t c[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                c[k] = (((w[i][0] >> (8 * k)) & 255u) + ((w[i][1] >> (8 * k)) & 255u) + ((w[i][2] >> (8 * k)) & 255u) +
+                        ((w[i][3] >> (8 * k)) & 255u) + 2u) >> 2;
+            g[i] = bgr_to_gray(c[BI], c[1], c[2 - BI]);
+        }
+        uint8_t* d = dst + (size_t)y * dstride + x;
+        if (x + 1 < dw) *reinterpret_cast<uint16_t*>(d) = (uint16_t)(g[0] | (g[1] << 8));
+        else d[0] = (uint8_t)g[0];
+    }
+}
+
+// ---- general bilinear (any scale), CN = 3 / 4 (-> gray, B at byte BI) or 1 ------
+template <int CN, bool TO_GRAY, int BI = 0>
 __global__ __launch_bounds__(NT) void resize_gray_kernel(const uint8_t* __restrict__ src_, size_t sstride,
                                                          int sw, int sh, uint8_t* __restrict__ dst_,
                                                          size_t dstride, int dw, int dh, double scale_x,
@@ -167,7 +219,7 @@ __global__ __launch_bounds__(NT) void resize_gray_kernel(const uint8_t* __restri
         }
     }
     if (TO_GRAY) {
-        dst[(size_t)dy * dstride + dx] = (uint8_t)(CN == 3 ? bgr_to_gray(v[0], v[1], v[2]) : v[0]);
+        dst[(size_t)dy * dstride + dx] = (uint8_t)(CN >= 3 ? bgr_to_gray(v[BI], v[1], v[2 - BI]) : v[0]);
     } else {
 #pragma unroll
         for (int k = 0; k < CN; k++) dst[(size_t)dy * dstride + (size_t)dx * CN + k] = (uint8_t)v[k];
@@ -203,12 +255,51 @@ __global__ __launch_bounds__(NT) void quarter_gray_kernel(size_t sstride, size_t
     }
 }
 
+// Byte of B inside a pixel and the pixel's size of a colour format; false for GRAY8 / NV12 / anything else.
+bool color_layout(int fmt, int* bi, int* ps) {
+    switch (fmt) {
+        case VS_FMT_BGR8: *bi = 0; *ps = 3; return true;
+        case VS_FMT_RGB8: *bi = 2; *ps = 3; return true;
+        case VS_FMT_BGRA8: *bi = 0; *ps = 4; return true;
+        case VS_FMT_RGBA8: *bi = 2; *ps = 4; return true;
+        default: return false;
+    }
+}
+
+// The general resize -> gray of a colour format (any scale; area2: the exact 2x2 decimation).
+void launch_resize_color(int bi, int ps, dim3 grid, const uint8_t* src, size_t sstride, int sw, int sh, uint8_t* dst, size_t dstride, int dw,
+                         int dh, double scale_x, double scale_y, int area2, const ImgPair* table, hipStream_t st) {
+    if (ps == 3 && bi == 0)
+        hipLaunchKernelGGL((resize_gray_kernel<3, true>), grid, dim3(NT), 0, st, src, sstride, sw, sh, dst, dstride, dw, dh, scale_x, scale_y, area2, table);
+    else if (ps == 3)
+        hipLaunchKernelGGL((resize_gray_kernel<3, true, 2>), grid, dim3(NT), 0, st, src, sstride, sw, sh, dst, dstride, dw, dh, scale_x, scale_y, area2, table);
+    else if (bi == 0)
+        hipLaunchKernelGGL((resize_gray_kernel<4, true>), grid, dim3(NT), 0, st, src, sstride, sw, sh, dst, dstride, dw, dh, scale_x, scale_y, area2, table);
+    else
+        hipLaunchKernelGGL((resize_gray_kernel<4, true, 2>), grid, dim3(NT), 0, st, src, sstride, sw, sh, dst, dstride, dw, dh, scale_x, scale_y, area2, table);
+}
+
+// The exact 2x decimation -> gray of a colour format, 4 output pixels per lane.
+void launch_half_color(int bi, int ps, dim3 grid, const uint8_t* src, size_t sstride, uint8_t* dst, size_t dstride, int dw, int dh, int vec_ok,
+                       const ImgPair* table, hipStream_t st) {
+    if (ps == 3 && bi == 0)
+        hipLaunchKernelGGL((half_bgr_gray_kernel<0, 3>), grid, dim3(NT), 0, st, src, sstride, dst, dstride, dw, dh, vec_ok, table);
+    else if (ps == 3)
+        hipLaunchKernelGGL((half_bgr_gray_kernel<2, 3>), grid, dim3(NT), 0, st, src, sstride, dst, dstride, dw, dh, vec_ok, table);
+    else if (bi == 0)
+        hipLaunchKernelGGL((half_bgr_gray_kernel<0, 4>), grid, dim3(NT), 0, st, src, sstride, dst, dstride, dw, dh, vec_ok, table);
+    else
+        hipLaunchKernelGGL((half_bgr_gray_kernel<2, 4>), grid, dim3(NT), 0, st, src, sstride, dst, dstride, dw, dh, vec_ok, table);
+}
+
 }  // namespace
 
 int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, int sw, int sh, int fmt, size_t dstride,
                              int dw, int dh, int aligned, hipStream_t st) {
+    int bi = 0, ps = 1;
+    const bool color = color_layout(fmt, &bi, &ps);
     if (!d_pairs || items < 1 || items > 65535 || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 ||
-        (fmt != VS_FMT_BGR8 && fmt != VS_FMT_GRAY8)) {
+        (!color && fmt != VS_FMT_GRAY8)) {
         set_last_error("resize_gray_batch: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
@@ -219,25 +310,27 @@ int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, 
                        isx == 2 && isy == 2;
     const uint8_t* np = nullptr;
     uint8_t* nd = nullptr;
-    if (fmt == VS_FMT_BGR8 && area2) {
+    if (color && area2) {
         const int vec_ok = aligned && (sstride % 8 == 0) && (dstride % 4 == 0);
         if (aligned && sstride % 4 == 0 && dstride % 2 == 0) {
             // (aligned: every frame of the table starts on an 8-byte boundary; the analysis images come from the library's own
             // allocation, 256-byte aligned)
             dim3 grid(((dw + 1) / 2 + NT - 1) / NT, (dh + HG_ROWS - 1) / HG_ROWS, items);
-            hipLaunchKernelGGL(half_bgr_gray12_kernel, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
+            if (ps == 3 && bi == 0) hipLaunchKernelGGL(half_bgr_gray12_kernel<0>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
+            else if (ps == 3) hipLaunchKernelGGL(half_bgr_gray12_kernel<2>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
+            else if (bi == 0) hipLaunchKernelGGL(half_bgra_gray16_kernel<0>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
+            else hipLaunchKernelGGL(half_bgra_gray16_kernel<2>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
         } else {
             dim3 grid(((dw + 3) / 4 + NT - 1) / NT, dh, items);
-            hipLaunchKernelGGL(half_bgr_gray_kernel, grid, dim3(NT), 0, st, np, sstride, nd, dstride, dw, dh, vec_ok, d_pairs);
+            launch_half_color(bi, ps, grid, np, sstride, nd, dstride, dw, dh, vec_ok, d_pairs, st);
         }
     } else if (fmt == VS_FMT_GRAY8 && sw == 4 * dw && sh == 4 * dh) {
         dim3 grid((dw + 255) / 256, (dh + QG_ROWS - 1) / QG_ROWS, items);
         hipLaunchKernelGGL(quarter_gray_kernel, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
     } else {
         dim3 grid((dw + NT - 1) / NT, dh, items);
-        if (fmt == VS_FMT_BGR8)
-            hipLaunchKernelGGL((resize_gray_kernel<3, true>), grid, dim3(NT), 0, st, np, sstride, sw, sh, nd, dstride, dw, dh,
-                               scale_x, scale_y, area2 ? 1 : 0, d_pairs);
+        if (color)
+            launch_resize_color(bi, ps, grid, np, sstride, sw, sh, nd, dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, d_pairs, st);
         else
             hipLaunchKernelGGL((resize_gray_kernel<1, true>), grid, dim3(NT), 0, st, np, sstride, sw, sh, nd, dstride, dw, dh,
                                scale_x, scale_y, area2 ? 1 : 0, d_pairs);
@@ -248,8 +341,10 @@ int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, 
 
 int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int fmt,
                        uint8_t* d_dst, size_t dstride, int dw, int dh, hipStream_t st) {
+    int bi = 0, ps = 1;
+    const bool color = color_layout(fmt, &bi, &ps);
     if (!d_src || !d_dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 ||
-        (fmt != VS_FMT_BGR8 && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8)) {
+        (!color && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8)) {
         set_last_error("resize_gray: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
@@ -260,16 +355,16 @@ int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int
     const int isx = (int)lrint(scale_x), isy = (int)lrint(scale_y);
     const bool area2 = std::abs(scale_x - isx) < DBL_EPSILON && std::abs(scale_y - isy) < DBL_EPSILON &&
                        isx == 2 && isy == 2;
-    if (fmt == VS_FMT_BGR8 && area2) {
+    if (color && area2) {
         const int vec_ok = ((uintptr_t)d_src % 8 == 0) && (sstride % 8 == 0) && ((uintptr_t)d_dst % 4 == 0) &&
                            (dstride % 4 == 0);
         dim3 grid(((dw + 3) / 4 + NT - 1) / NT, dh);
-        hipLaunchKernelGGL(half_bgr_gray_kernel, grid, dim3(NT), 0, st, d_src, sstride, d_dst, dstride, dw, dh, vec_ok, (const ImgPair*)nullptr);
+        launch_half_color(bi, ps, grid, d_src, sstride, d_dst, dstride, dw, dh, vec_ok, (const ImgPair*)nullptr, st);
     } else {
         dim3 grid((dw + NT - 1) / NT, dh);
-        if (fmt == VS_FMT_BGR8)
-            hipLaunchKernelGGL((resize_gray_kernel<3, true>), grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst,
-                               dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, (const ImgPair*)nullptr);
+        if (color)
+            launch_resize_color(bi, ps, grid, d_src, sstride, sw, sh, d_dst, dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0,
+                                (const ImgPair*)nullptr, st);
         else
             hipLaunchKernelGGL((resize_gray_kernel<1, true>), grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst,
                                dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, (const ImgPair*)nullptr);
@@ -281,7 +376,7 @@ int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int
 // cv::resize(INTER_LINEAR) keeping the channels (crop-n-zoom, Stabilizer.cpp:1121)
 int launch_resize_linear(const uint8_t* d_src, size_t sstride, int sw, int sh, int cn, uint8_t* d_dst,
                          size_t dstride, int dw, int dh, hipStream_t st) {
-    if (!d_src || !d_dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || (cn != 1 && cn != 3)) {
+    if (!d_src || !d_dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || (cn != 1 && cn != 3 && cn != 4)) {
         set_last_error("resize_linear: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
@@ -290,7 +385,10 @@ int launch_resize_linear(const uint8_t* d_src, size_t sstride, int sw, int sh, i
     const int isx = (int)lrint(scale_x), isy = (int)lrint(scale_y);
     const int area2 = std::abs(scale_x - isx) < DBL_EPSILON && std::abs(scale_y - isy) < DBL_EPSILON && isx == 2 && isy == 2;
     dim3 grid((dw + NT - 1) / NT, dh);
-    if (cn == 3)
+    if (cn == 4)
+        hipLaunchKernelGGL((resize_gray_kernel<4, false>), grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst, dstride,
+                           dw, dh, scale_x, scale_y, area2, (const ImgPair*)nullptr);
+    else if (cn == 3)
         hipLaunchKernelGGL((resize_gray_kernel<3, false>), grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst, dstride,
                            dw, dh, scale_x, scale_y, area2, (const ImgPair*)nullptr);
     else

@@ -91,6 +91,7 @@ __device__ __forceinline__ uint32_t load_px_checked(const uint8_t* src, size_t s
     uint32_t v = p[0];
     if (CN > 1) v |= (uint32_t)p[1] << 8;
     if (CN > 2) v |= (uint32_t)p[2] << 16;
+    if (CN > 3) v |= (uint32_t)p[3] << 24;
     return v;
 }
 
@@ -117,11 +118,18 @@ __device__ __forceinline__ uint32_t blend(uint32_t p00, uint32_t p01, uint32_t p
         out |= ((__umul24(t, wy0) + __umul24(b, wy1) + 512u) >> 10) << 8;
     }
     if (CN > 2) {
-        const uint32_t y0 = __builtin_amdgcn_perm(p01, p00, 0x0C0C0602u);   // (c2_a, c2_b, 0, 0)
-        const uint32_t y1 = __builtin_amdgcn_perm(p11, p10, 0x0C0C0602u);
+        // (c2_a, c2_b, 0, 0); four channels: (c2_a, c2_b, c3_a, c3_b)
+        const uint32_t sel = CN > 3 ? 0x07030602u : 0x0C0C0602u;
+        const uint32_t y0 = __builtin_amdgcn_perm(p01, p00, sel);
+        const uint32_t y1 = __builtin_amdgcn_perm(p11, p10, sel);
         const uint32_t t = __builtin_amdgcn_udot4(y0, wlo, 0u, false);
         const uint32_t b = __builtin_amdgcn_udot4(y1, wlo, 0u, false);
         out |= ((__umul24(t, wy0) + __umul24(b, wy1) + 512u) >> 10) << 16;
+        if (CN > 3) {
+            const uint32_t ta = __builtin_amdgcn_udot4(y0, whi, 0u, false);
+            const uint32_t ba = __builtin_amdgcn_udot4(y1, whi, 0u, false);
+            out |= ((__umul24(ta, wy0) + __umul24(ba, wy1) + 512u) >> 10) << 24;
+        }
     }
     return out;
 }
@@ -150,6 +158,8 @@ __device__ __forceinline__ uint4 stage_group(const WarpCore& c, const uint8_t* _
             } else if (CN == 1) {
                 const uint32_t d = *reinterpret_cast<const uint32_t*>(p);
                 px.x = d & 255u; px.y = (d >> 8) & 255u; px.z = (d >> 16) & 255u; px.w = d >> 24;
+            } else if (CN == 4) {
+                px = *reinterpret_cast<const uint4*>(p);
             } else {
                 const uint2 d = *reinterpret_cast<const uint2*>(p);
                 px.x = d.x & 0xFFFFu; px.y = d.x >> 16; px.z = d.y & 0xFFFFu; px.w = d.y >> 16;
@@ -215,6 +225,9 @@ __device__ __forceinline__ void emit_rows(const WarpCore& c, const uint8_t* __re
                 store_nt3(d, v);
             } else if (CN == 1) {
                 __builtin_nontemporal_store(o[r][0] | (o[r][1] << 8) | (o[r][2] << 16) | (o[r][3] << 24), reinterpret_cast<uint32_t*>(d));
+            } else if (CN == 4) {
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                __builtin_nontemporal_store(u32x4{o[r][0], o[r][1], o[r][2], o[r][3]}, reinterpret_cast<u32x4*>(d));
             } else {
                 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
                 __builtin_nontemporal_store(u32x2{o[r][0] | (o[r][1] << 16), o[r][2] | (o[r][3] << 16)}, reinterpret_cast<u32x2*>(d));
@@ -883,22 +896,22 @@ __device__ __forceinline__ uint4 load_chunk_replicate(const uint8_t* rowp, int x
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int xx = xb + 4 * q + k;
-            const int px = min(max(CN == 1 ? xx : xx >> 1, 0), sw - 1);
-            wq[q] |= (uint32_t)rowp[CN == 1 ? px : 2 * px + (xx & 1)] << (8 * k);
+            const int px = min(max(CN == 1 ? xx : CN == 2 ? xx >> 1 : xx >> 2, 0), sw - 1);     // (CN = 1, 2 or 4)
+            wq[q] |= (uint32_t)rowp[CN == 1 ? px : CN * px + (xx & (CN - 1))] << (8 * k);
         }
     }
     return make_uint4(wq[0], wq[1], wq[2], wq[3]);
 }
 
 template <int CN> struct PlaneCfg {
-    static constexpr int THP = 64 / CN;                  // rows of a tile
+    static constexpr int THP = 64 / CN;                  // rows of a tile (four channels: 16, the rows of a table record)
     static constexpr int DB = 136 * CN + 8 * CN;         // staged bytes of a row (136 pixels + slack for the 8-byte tap read)
     // Row pitch of the staged box: a multiple of 128 bytes = of the 32 LDS banks.  The lanes of a tap read sit on consecutive dwords
     // of a row until the map's rotation moves them a source row down (or up), once per tile row for anything but a pure
     // translation; with a pitch of 144 bytes those lanes land 4 banks to the side, on banks their neighbours use, and every tap
     // read pays a second pass.  With this pitch a lane's bank does not depend on its row.  (scratch/blend_lab.sh: the tap reads
     // were 66 of the kernel's 209 us per 32 4K frames.)
-    static constexpr int PB = (DB + 127) / 128 * 128;    // 256 / 384
+    static constexpr int PB = (DB + 127) / 128 * 128;    // 256 / 384 / 640
     static constexpr int ROWS = THP + 9;                 // staged rows (rotations up to ~3.5 degrees)
     static constexpr int CPR = DB / 16;                  // 16-byte chunks per staged row
 };
@@ -919,9 +932,33 @@ template <int CN> struct PlaneCfg {
 // box, scratch/ab_lib.sh: the integer form - t | b << 16 against (64 (32 - f), 64 f) in one v_dot2_u32_u16 preset to 2^15, result
 // in byte 2: one instruction and 4 bytes of LDS weights less per pixel, bit-identical - 204 us against 198: its two
 // instructions are of the 4-cycle class, scratch/valu_rate.hip.)
+// Four channels (BGRA8 / RGBA8): a pixel is a dword of the staged row, so the four taps are aligned dword reads; the horizontal
+// lerps pair the same channel of the two taps of a row with v_perm - (c0, c0', c1, c1') and (c2, c2', c3, c3') - and take v_dot4
+// against the table's wlo (channels 0, 2) and whi (1, 3); the vertical lerp is vlerp's, and the four results' low bytes are
+// packed into one dword.
+__device__ __forceinline__ uint32_t plane_blend_px4(const uint8_t* tl, const uint8_t* lut, int SX, int SY) {
+    typedef PlaneCfg<4> P;
+    const int addr = __mul24(SY >> 10, P::PB) + ((SX >> 10) << 2);
+    const uint32_t* tp = reinterpret_cast<const uint32_t*>(tl + addr);
+    const uint32_t p00 = tp[0], p01 = tp[1], p10 = tp[P::PB / 4], p11 = tp[P::PB / 4 + 1];
+    const LutX wx = *reinterpret_cast<const LutX*>(lut + (SX & 0x3E0));
+    const LutY wy = *reinterpret_cast<const LutY*>(lut + 8 + (SY & 0x3E0));
+    const uint32_t t01 = __builtin_amdgcn_perm(p01, p00, 0x05010400u), b01 = __builtin_amdgcn_perm(p11, p10, 0x05010400u);
+    const uint32_t t23 = __builtin_amdgcn_perm(p01, p00, 0x07030602u), b23 = __builtin_amdgcn_perm(p11, p10, 0x07030602u);
+    float m0 = vlerp(__builtin_amdgcn_udot4(t01, wx.wlo, 0u, false), __builtin_amdgcn_udot4(b01, wx.wlo, 0u, false), wy);
+    float m1 = vlerp(__builtin_amdgcn_udot4(t01, wx.whi, 0u, false), __builtin_amdgcn_udot4(b01, wx.whi, 0u, false), wy);
+    float m2 = vlerp(__builtin_amdgcn_udot4(t23, wx.wlo, 0u, false), __builtin_amdgcn_udot4(b23, wx.wlo, 0u, false), wy);
+    float m3 = vlerp(__builtin_amdgcn_udot4(t23, wx.whi, 0u, false), __builtin_amdgcn_udot4(b23, wx.whi, 0u, false), wy);
+    asm("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3));
+    const uint32_t lo = __builtin_amdgcn_perm(__float_as_uint(m1), __float_as_uint(m0), 0x0C0C0400u);    // (c0, c1, 0, 0)
+    const uint32_t hi = __builtin_amdgcn_perm(__float_as_uint(m3), __float_as_uint(m2), 0x0C0C0400u);    // (c2, c3, 0, 0)
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+
 template <int CN>
 __device__ __forceinline__ uint32_t plane_blend_px(const uint8_t* tl, const uint8_t* lut, int SX, int SY) {
     typedef PlaneCfg<CN> P;
+    if (CN == 4) return plane_blend_px4(tl, lut, SX, SY);
     int addr;                                                     // byte of the upper-left tap: row * PB + column * CN
     if (P::PB == 256 && CN == 1) {          // (one shift-add; left to itself the compiler makes shift, mask, add of it)
         const int sy = SY >> 10, sx = SX >> 10;
@@ -946,10 +983,13 @@ __device__ __forceinline__ uint32_t plane_blend_px(const uint8_t* tl, const uint
 }
 
 template <int CN>
-__device__ __forceinline__ void plane_store4(uint8_t* dq, const uint32_t (&res)[4]) {       // four pixels = 4 / 8 aligned bytes
+__device__ __forceinline__ void plane_store4(uint8_t* dq, const uint32_t (&res)[4]) {       // four pixels = 4 / 8 / 16 aligned bytes
     if (CN == 1) {
         const uint32_t lo = __builtin_amdgcn_perm(res[1], res[0], 0x0C0C0400u), hi = __builtin_amdgcn_perm(res[3], res[2], 0x0C0C0400u);   // low bytes
         __builtin_nontemporal_store(__builtin_amdgcn_perm(hi, lo, 0x05040100u), reinterpret_cast<uint32_t*>(dq));
+    } else if (CN == 4) {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        __builtin_nontemporal_store(u32x4{res[0], res[1], res[2], res[3]}, reinterpret_cast<u32x4*>(dq));
     } else {
         typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
         __builtin_nontemporal_store(u32x2{res[0] | (res[1] << 16), res[2] | (res[3] << 16)}, reinterpret_cast<u32x2*>(dq));
@@ -1012,6 +1052,22 @@ __device__ __attribute__((noinline)) void plane_direct_tile(WarpCore c, const ui
     for (int j = 0; y0 + TH * j <= y1; j++)
         emit_rows<CN, false>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW + TH * j, s_tab + 2 * TW + P::THP + TH * j, x0, y0 + TH * j, x1,
                              min(y0 + TH * j + TH - 1, y1), bx0a, by0, bw, tid);
+}
+
+// Four channels: the tile is ONE 16-row pass of emit_rows, and inlined - the call's saved registers would be the kernel's only
+// scratch.
+__device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
+                                                int bx0a, int by0, int bw, int tid) {
+    static_assert(PlaneCfg<4>::THP == TH, "one pass of emit_rows per tile");
+    if (tid < TW) {
+        const int cx = min(x0 + tid, x1);
+        s_tab[tid] = Tg[cx]; s_tab[TW + tid] = Tg[c.dw + cx];
+    } else if (tid < TW + TH) {
+        const int r = min(y0 + (tid - TW), y1);
+        s_tab[2 * TW + (tid - TW)] = Tg[2 * c.dw + r]; s_tab[2 * TW + TH + (tid - TW)] = Tg[2 * c.dw + c.dh + r];
+    }
+    __syncthreads();
+    emit_rows<4, false>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW, s_tab + 2 * TW + TH, x0, y0, x1, y1, bx0a, by0, bw, tid);
 }
 
 // One tile of a plane: tile (tx, ty) of the frame whose plane table starts at Ts (column records) / Tg (the per-column and
@@ -1124,7 +1180,8 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
         }
     }
     if (!fit) {
-        plane_direct_tile<CN>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        if constexpr (CN == 4) plane_direct_tile4(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        else plane_direct_tile<CN>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
         return;
     }
     __syncthreads();
@@ -1246,6 +1303,7 @@ void launch_one(WarpArgs& a, dim3 grid, int32_t* d_tabs, int what, hipStream_t s
 
 void launch_cn(WarpArgs& a, dim3 grid, int cn, int32_t* d_tabs, hipStream_t st, int what = VS_WARP_ALL, int tab_stride = 0) {
     if (cn == 3) launch_one<3>(a, grid, d_tabs, what, st, tab_stride);
+    else if (cn == 4) launch_one<4>(a, grid, d_tabs, what, st, tab_stride);
     else if (cn == 1) launch_one<1>(a, grid, d_tabs, what, st, tab_stride);
     else launch_one<2>(a, grid, d_tabs, what, st, tab_stride);
 }
@@ -1253,7 +1311,7 @@ void launch_cn(WarpArgs& a, dim3 grid, int cn, int32_t* d_tabs, hipStream_t st, 
 bool bad_args(const void* d_src, const void* d_dst, const void* M, size_t sstride, int sw, int sh, size_t dstride,
               int dw, int dh, int cn, int batch) {
     return !d_src || !d_dst || !M || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || batch <= 0 ||
-           (cn != 1 && cn != 2 && cn != 3) || sstride < (size_t)sw * cn || dstride < (size_t)dw * cn ||
+           (cn < 1 || cn > 4) || sstride < (size_t)sw * cn || dstride < (size_t)dw * cn ||
            dh > 65535 * TH;
 }
 
@@ -1304,12 +1362,13 @@ int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t
     a.c.sw = sw; a.c.sh = sh; a.c.dw = dw; a.c.dh = dh;
     a.c.border = border;
     const int galign = cn == 2 ? 8 : 4;
+    const int dalign = cn == 4 ? 16 : galign;      // (four channels: a lane's four pixels are one aligned 16-byte store)
     a.c.src_aligned = sstride % galign == 0;
-    a.c.dst_aligned = dstride % galign == 0;
+    a.c.dst_aligned = dstride % dalign == 0;
     for (int i = 0; i < MAXB; i++) {
         a.srcs[i] = srcs[i < n ? i : 0]; a.dsts[i] = dsts[i < n ? i : 0];
         if ((uintptr_t)a.srcs[i] % galign) a.c.src_aligned = 0;
-        if ((uintptr_t)a.dsts[i] % galign) a.c.dst_aligned = 0;
+        if ((uintptr_t)a.dsts[i] % dalign) a.c.dst_aligned = 0;
     }
     a.Minv_dev = maps.host ? nullptr : maps.m;
     a.minv_stride = maps.stride;
@@ -1447,7 +1506,7 @@ int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st) {
         a.j[i] = jobs[i < n ? i : 0];
         if (i >= n) continue;
         const WarpJob& j = jobs[i];
-        if (bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn, 1) ||
+        if (bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn, 1) || j.cn > 3 ||
             (j.border != VS_BORDER_BLACK && j.border != VS_BORDER_REPLICATE)) {
             set_last_error("warp_jobs: invalid argument");
             return VS_ERR_INVALID_ARG;

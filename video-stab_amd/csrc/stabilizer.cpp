@@ -256,6 +256,16 @@ struct vs_stab {
 
 namespace {
 
+// Bytes per pixel of a frame format's first plane (NV12 / GRAY8: the luma bytes); 0 for an unknown format.
+int fmt_cn(int fmt) {
+    switch (fmt) {
+        case VS_FMT_BGR8: case VS_FMT_RGB8: return 3;
+        case VS_FMT_BGRA8: case VS_FMT_RGBA8: return 4;
+        case VS_FMT_NV12: case VS_FMT_GRAY8: return 1;
+        default: return 0;
+    }
+}
+
 // Records an event pair around one stage when profiling is on.
 struct StageScope {
     vs_stab* s;
@@ -368,7 +378,7 @@ int allocate(vs_stab* s, int w, int h, int fmt) {
 
 int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     s->w = w; s->h = h; s->fmt = fmt;
-    s->cn = fmt == VS_FMT_BGR8 ? 3 : 1;
+    s->cn = fmt_cn(fmt);
     s->rows_total = fmt == VS_FMT_NV12 ? h * 3 / 2 : h;
     s->row_bytes = (size_t)w * s->cn;
     s->frame_bytes = s->row_bytes * s->rows_total;
@@ -936,11 +946,11 @@ int take_slot(vs_stab* s, int* slot) {
 }
 
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
-    if (w <= 0 || h <= 0 || (fmt != VS_FMT_BGR8 && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: bad geometry/format");
+    const int cn = fmt_cn(fmt);
+    if (w <= 0 || h <= 0 || cn == 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: bad geometry/format");
     if (fmt == VS_FMT_NV12 && ((w & 1) || (h & 1))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "NV12 needs even w,h");
-    if (fmt != VS_FMT_BGR8 && s->p.border_size > 0) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need BGR8 frames");
-    const int cn = fmt == VS_FMT_BGR8 ? 3 : 1;
+    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8)
+    if (cn == 1 && s->p.border_size > 0) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need a colour format (BGR8, BGRA8, RGBA8, RGB8)");
     if (stride < (size_t)w * cn) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: stride < row bytes");
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     if (!s->allocated) return allocate(s, w, h, fmt);

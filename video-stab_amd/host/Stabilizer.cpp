@@ -66,6 +66,14 @@ vs_params_c to_c(const Stabilizer::Parameters &p) {
     return c;
 }
 
+// The library's pixel format of an 8-bit Mat: three channels are BGR, four BGRA (BGRx as capture delivers it); -1 otherwise.
+// (The four-channel type is spelled CV_MAKETYPE: it is all the minimal cv::Mat of the tests defines.)
+int frame_format(int type) {
+    if (type == CV_8UC3) return VS_FMT_BGR8;
+    if (type == CV_MAKETYPE(CV_8U, 4)) return VS_FMT_BGRA8;
+    return -1;
+}
+
 }  // namespace
 
 void Stabilizer::logMessage(const std::string &msg, bool isError) const {   // Stabilizer.cpp:40-46
@@ -95,19 +103,19 @@ void Stabilizer::create() {
 // (cv::Mat's own reference count: u->refcount == 1 means the ring is the only owner); a caller that keeps more than four
 // results alive simply gets ordinary Mats for the surplus.
 cv::Mat Stabilizer::outputFrame(int rows, int cols) {
-    if (!params_.pinHostFrames) return cv::Mat(rows, cols, CV_8UC3);
+    if (!params_.pinHostFrames) return cv::Mat(rows, cols, frameType_);
     for (OutSlot &s : outRing_) {
-        if (!s.m.empty() && s.m.rows == rows && s.m.cols == cols && s.m.u && s.m.u->refcount == 1) return s.m;
+        if (!s.m.empty() && s.m.rows == rows && s.m.cols == cols && s.m.type() == frameType_ && s.m.u && s.m.u->refcount == 1) return s.m;
     }
     for (OutSlot &s : outRing_) {
         if (s.m.empty() || (s.m.u && s.m.u->refcount == 1)) {       // an empty slot, or one of another size that nobody holds
             if (s.pinned) { (void)vs_host_unregister(s.m.data); s.pinned = false; }
-            s.m = cv::Mat(rows, cols, CV_8UC3);
+            s.m = cv::Mat(rows, cols, frameType_);
             s.pinned = vs_host_register(s.m.data, (size_t)s.m.step * (size_t)rows) == VS_OK;
             return s.m;
         }
     }
-    return cv::Mat(rows, cols, CV_8UC3);
+    return cv::Mat(rows, cols, frameType_);
 }
 
 // Parameters::pinInputFrames: the frame buffer a capture loop reads into comes back call after call; from its second
@@ -156,7 +164,8 @@ Stabilizer::~Stabilizer() {
 }
 
 Stabilizer::Stabilizer(Stabilizer &&o) noexcept
-    : params_(std::move(o.params_)), impl_(o.impl_), device_(o.device_), frameWidth_(o.frameWidth_), frameHeight_(o.frameHeight_) {
+    : params_(std::move(o.params_)), impl_(o.impl_), device_(o.device_), frameWidth_(o.frameWidth_), frameHeight_(o.frameHeight_),
+      frameType_(o.frameType_) {
     o.impl_ = nullptr;
     o.releaseHostPins();                 // (the rings are rebuilt on this side as frames come)
 }
@@ -168,7 +177,7 @@ Stabilizer &Stabilizer::operator=(Stabilizer &&o) noexcept {
         params_ = std::move(o.params_);
         impl_ = o.impl_;
         device_ = o.device_;
-        frameWidth_ = o.frameWidth_; frameHeight_ = o.frameHeight_;
+        frameWidth_ = o.frameWidth_; frameHeight_ = o.frameHeight_; frameType_ = o.frameType_;
         o.impl_ = nullptr;
         o.releaseHostPins();
     }
@@ -190,17 +199,19 @@ Stabilizer &Stabilizer::operator=(const Stabilizer &o) {
 
 cv::Mat Stabilizer::stabilize(const cv::Mat &frame) {
     if (frame.empty() || !impl_) return cv::Mat();                       // Stabilizer.cpp:263-265
-    if (frame.type() != CV_8UC3) {
-        if (params_.logging) logMessage("stabilize(): expected a CV_8UC3 BGR frame", true);
+    const int fmt = frame_format(frame.type());
+    if (fmt < 0) {
+        if (params_.logging) logMessage("stabilize(): expected a CV_8UC3 BGR or 8-bit four-channel BGRA frame", true);
         return frame;
     }
     int ow = 0, oh = 0;
-    frameWidth_ = frame.cols; frameHeight_ = frame.rows;
+    // (a frame of another type than the stream's is refused by the library like one of another size: SIZE_CHANGED)
+    frameWidth_ = frame.cols; frameHeight_ = frame.rows; frameType_ = frame.type();
     vs_stab_out_size(impl_, frame.cols, frame.rows, &ow, &oh);
     noteInput(frame);
     cv::Mat out = outputFrame(oh, ow);
     int produced = 0;
-    int rc = vs_stab_push(impl_, frame.data, frame.cols, frame.rows, (size_t)frame.step, VS_FMT_BGR8, out.data,
+    int rc = vs_stab_push(impl_, frame.data, frame.cols, frame.rows, (size_t)frame.step, fmt, out.data,
                           (size_t)out.step, &produced);
     if (rc != VS_OK) {
         if (params_.logging) logMessage(std::string("stabilize() failed: ") + vs_stab_last_error(impl_), true);
@@ -226,6 +237,7 @@ cv::Mat Stabilizer::flush() {
 void Stabilizer::clean() {
     if (impl_) vs_stab_clean(impl_);
     frameWidth_ = frameHeight_ = 0;
+    frameType_ = CV_8UC3;
     releaseHostPins();
 }
 

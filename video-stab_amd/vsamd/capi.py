@@ -18,6 +18,9 @@ f64p = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
 
 FMT_BGR8, FMT_NV12, FMT_GRAY8 = 0, 1, 2
+FMT_BGRA8, FMT_RGBA8, FMT_RGB8 = 3, 4, 5
+# bytes per pixel of a format's (first) plane; a colour format's frames are (h, w, channels) arrays
+FMT_CHANNELS = {FMT_BGR8: 3, FMT_NV12: 1, FMT_GRAY8: 1, FMT_BGRA8: 4, FMT_RGBA8: 4, FMT_RGB8: 3}
 BORDER_BLACK, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP, BORDER_FADE = range(6)
 SMOOTH_BOX, SMOOTH_GAUSSIAN, SMOOTH_KALMAN = range(3)
 STAGE_WARP, STAGE_WARP_TABLES, STAGE_COUNT = 7, 8, 9      # vs_stab.h VS_STAGE_*
@@ -377,7 +380,7 @@ class VsLib:
             fmt = FMT_BGR8 if img.ndim == 3 else FMT_GRAY8
         w = img.shape[1]
         h = img.shape[0] if fmt != FMT_NV12 else img.shape[0] * 2 // 3
-        cn = 3 if fmt == FMT_BGR8 else 1
+        cn = FMT_CHANNELS[fmt]
         d_in = DevBuf.from_array(self, img)
         d_out = DevBuf(self, dw * dh)
         self.check(self.lib.vs_op_resize_gray(d_in.ptr, w * cn, w, h, fmt, d_out.ptr, dw, dw, dh, None))
@@ -877,13 +880,13 @@ class Stabilizer:
     def _geom(self, frame, fmt):
         w = frame.shape[1]
         h = frame.shape[0] if fmt != FMT_NV12 else frame.shape[0] * 2 // 3
-        return w, h, (3 if fmt == FMT_BGR8 else 1)
+        return w, h, FMT_CHANNELS[fmt]
 
     def out_shape(self, w, h, fmt):
         ow, oh = C.c_int32(), C.c_int32()
         self.vs.check(self.lib.vs_stab_out_size(self.h, w, h, C.byref(ow), C.byref(oh)), self.h)
-        if fmt == FMT_BGR8:
-            return (oh.value, ow.value, 3)
+        if FMT_CHANNELS[fmt] > 1:
+            return (oh.value, ow.value, FMT_CHANNELS[fmt])
         if fmt == FMT_NV12:
             return (oh.value * 3 // 2, ow.value)
         return (oh.value, ow.value)
