@@ -1,0 +1,57 @@
+// Stage launchers of the stabilizer pipeline that vs_common.h does not declare: the per-frame RANSAC / trajectory / border
+// kernels and the batched forms, whose argument blocks are opaque to the host (sized and filled through *_bytes / *_fill_*).
+// Host-only: included by stabilizer.cpp and batch_schedule.cpp, defined in the k_*.hip file named with each group.
+#ifndef VS_LAUNCHERS_H
+#define VS_LAUNCHERS_H
+
+#include "traj_state.h"
+#include "vs_common.h"
+#include "warp_tab.h"
+
+namespace vsd {
+
+// ---- k_ransac.hip: estimateAffinePartial2D + trajectory append of one frame, and the batched scoring / ordered tail
+struct RansacTables;
+int get_ransac_tables(int max_m, int iters, const RansacTables** out);
+int launch_ransac(const float* d_from, const float* d_to, const uint8_t* d_status, int n, const int32_t* d_n, float* d_vp, float* d_vc, int32_t* d_m,
+                  int min_points, double thr, int iters, const RansacTables* tab, int32_t* d_counts, double* d_model, uint8_t* d_inliers,
+                  int32_t* d_info, TrajState* traj, const TrajParams* tp, vs_debug_frame* dbg, int have_prev_gray, hipStream_t st);
+size_t ransac_item_bytes();
+int ransac_fill_item(void* host_item, const float* d_from, const float* d_to, const uint8_t* d_status, int n, const int32_t* d_n, float* d_vp,
+                     float* d_vc, int32_t* d_m, int min_points, double thr, int iters, const RansacTables* tab, int32_t* d_counts, double* d_model,
+                     uint8_t* d_inliers, int32_t* d_info, TrajState* traj, const TrajParams* tp, vs_debug_frame* dbg, int have_prev_gray);
+void ransac_item_set_tail_in(void* host_item, void* d_tail_in);
+void ransac_item_set_last(void* host_item, int last);      // the last frame of its stream in the step
+int launch_ransac_score_batch(const void* d_table, int items, int iters, int n_max, hipStream_t st);
+size_t tail_item_bytes();
+void tail_fill_item(void* host_item, int out_due, int out_idx, double* d_Minv_out, const WarpTabJob* tabs);   // tabs: two jobs
+void tail_item_set_seg(void* host_item, int seg);
+size_t tail_in_bytes();
+size_t tail_seg_bytes();        // a segment = the frames of one stream in the step
+void tail_fill_seg(void* host_seg, int first, int n, float* d_M_out, TrajState* traj, vs_debug_frame* dbg, int smoothing_method);
+int launch_ransac_tail_group(const void* d_table, const void* d_tail, const void* d_segs, const void* d_tail_in, int nsegs, int max_n, int items,
+                             int any_apart, hipStream_t st);
+
+// ---- k_lk.hip, k_gftt.hip: batched tracker and detector (what: 1 reset, 4 min-eigen, 5 NMS, 3 selection)
+size_t lk_item_bytes();
+int lk_fill_item(void* host_item, const LKLevel* levels, int max_level, const float* d_prev_pts, int n, const int32_t* d_n, float* d_next_pts,
+                 uint8_t* d_status, float* d_err, int win, int max_iters, double eps);
+int launch_pyr_lk_batch(const void* d_table, int items, int n_max, int win, hipStream_t st);
+size_t gftt_item_bytes();
+int gftt_fill_item(void* host_item, const uint8_t* d_gray, size_t stride, int w, int h, int max_corners, double quality, double min_distance,
+                   int block_size, const GfttWork& wk, float* d_pts, int32_t* d_count);
+int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_size, hipStream_t st, int what);
+
+// ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
+int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,
+                     float* t_out = nullptr);
+int launch_traj_reset(TrajState* s, int smoothing_radius, hipStream_t st);
+int launch_spin(int microseconds, hipStream_t st);
+int launch_fade_blend(const uint8_t* d_hist, uint8_t* d_frame, size_t bytes, float alpha, float beta, hipStream_t st);
+int launch_fade_update(uint8_t* d_hist, const uint8_t* d_stab, size_t sstride, int row_bytes, int rows, hipStream_t st);
+int launch_make_border(const uint8_t* src, size_t sstride, int w, int h, int cn, uint8_t* dst, size_t dstride, int b, int border, hipStream_t st);
+// ---- k_gray.hip
+int launch_resize_linear(const uint8_t* d_src, size_t sstride, int sw, int sh, int cn, uint8_t* d_dst, size_t dstride, int dw, int dh, hipStream_t st);
+
+}  // namespace vsd
+#endif

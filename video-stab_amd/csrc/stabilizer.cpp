@@ -23,236 +23,20 @@
 // push, but the device work of `batch` consecutive frames is issued together - one
 // launch per stage over all frames (argument tables in device memory), one ordered
 // tail kernel (selection + trajectory append + smoothing, state in LDS), one warp
-// launch for the frames of a batch.  There is ONE batch schedule, group_run(): a vs_batch
-// group runs it over the frames of all its streams, and a standalone instance in batch mode
-// owns a private group of one.  DESIGN.md section 5 has the schedule.
-#include <algorithm>
+// launch for the frames of a batch.  This file only queues the frames (batch_enqueue); there is ONE
+// batch schedule, group_run() in batch_schedule.cpp: a vs_batch group runs it over the frames of all
+// its streams, and a standalone instance in batch mode owns a private group of one.  The stream
+// object itself is in stab_internal.h; DESIGN.md section 5 has the schedule.
 #include <array>
-#include <atomic>
 #include <cstring>
 #include <cstdlib>
-#include <deque>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <new>
-#include <vector>
 
-#include "canvas.h"
-#include "host_helper.h"
-#include "traj_state.h"
-#include "vs_common.h"
-#include "warp_tab.h"
-
-namespace vsd {
-
-struct RansacTables;
-int get_ransac_tables(int max_m, int iters, const RansacTables** out);
-int launch_ransac(const float* d_from, const float* d_to, const uint8_t* d_status, int n, const int32_t* d_n,
-                  float* d_vp, float* d_vc, int32_t* d_m, int min_points, double thr, int iters,
-                  const RansacTables* tab, int32_t* d_counts, double* d_model, uint8_t* d_inliers,
-                  int32_t* d_info, TrajState* traj, const TrajParams* tp, vs_debug_frame* dbg,
-                  int have_prev_gray, hipStream_t st);
-size_t lk_item_bytes();
-int lk_fill_item(void* host_item, const LKLevel* levels, int max_level, const float* d_prev_pts, int n,
-                 const int32_t* d_n, float* d_next_pts, uint8_t* d_status, float* d_err, int win, int max_iters,
-                 double eps);
-int launch_pyr_lk_batch(const void* d_table, int items, int n_max, int win, hipStream_t st);
-size_t ransac_item_bytes();
-int ransac_fill_item(void* host_item, const float* d_from, const float* d_to, const uint8_t* d_status, int n,
-                     const int32_t* d_n, float* d_vp, float* d_vc, int32_t* d_m, int min_points, double thr, int iters,
-                     const RansacTables* tab, int32_t* d_counts, double* d_model, uint8_t* d_inliers, int32_t* d_info,
-                     TrajState* traj, const TrajParams* tp, vs_debug_frame* dbg, int have_prev_gray);
-int launch_ransac_score_batch(const void* d_table, int items, int iters, int n_max, hipStream_t st);
-size_t tail_item_bytes();
-void tail_fill_item(void* host_item, int out_due, int out_idx, double* d_Minv_out, const WarpTabJob* tabs);
-size_t tail_in_bytes();
-void ransac_item_set_tail_in(void* host_item, void* d_tail_in);
-size_t tail_seg_bytes();
-void tail_fill_seg(void* host_seg, int first, int n, float* d_M_out, TrajState* traj, vs_debug_frame* dbg, int smoothing_method);
-void tail_item_set_seg(void* host_item, int seg);
-void ransac_item_set_last(void* host_item, int last);
-int launch_ransac_tail_group(const void* d_table, const void* d_tail, const void* d_segs, const void* d_tail_in, int nsegs, int max_n, int items,
-                             int any_apart, hipStream_t st);
-size_t gftt_item_bytes();
-int gftt_fill_item(void* host_item, const uint8_t* d_gray, size_t stride, int w, int h, int max_corners, double quality,
-                   double min_distance, int block_size, const GfttWork& wk, float* d_pts, int32_t* d_count);
-int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_size, hipStream_t st, int what = 0);
-int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg,
-                     hipStream_t st, float* t_out = nullptr);
-int launch_traj_reset(TrajState* s, int smoothing_radius, hipStream_t st);
-int launch_spin(int microseconds, hipStream_t st);
-int launch_fade_blend(const uint8_t* d_hist, uint8_t* d_frame, size_t bytes, float alpha, float beta, hipStream_t st);
-int launch_fade_update(uint8_t* d_hist, const uint8_t* d_stab, size_t sstride, int row_bytes, int rows, hipStream_t st);
-int launch_make_border(const uint8_t* src, size_t sstride, int w, int h, int cn, uint8_t* dst, size_t dstride,
-                       int b, int border, hipStream_t st);
-int launch_resize_linear(const uint8_t* d_src, size_t sstride, int sw, int sh, int cn, uint8_t* d_dst,
-                         size_t dstride, int dw, int dh, hipStream_t st);
-
-constexpr int FRAME_RING = 128;     // <= 35 queued frames (clamp(smoothingRadius,5,35)) + slack so that a
-                                    // slot is reused several frames after the warp that released it; in batch mode
-                                    // also the batch being collected and the one whose warps are still to come
-constexpr int FRAME_RING_MAX = 192; // the same for batches of more than 32 frames (s->ring_frames)
-constexpr int MAX_PYR = 8;
-constexpr int NPYR = 3;             // pyramid buffers: frame k writes k%3 while LK(k-1) still reads (k-1)%3,(k-2)%3
-constexpr int BATCH_MAX = 64;        // frames analysed per launch in batch mode (vs_stab_set_batch)
-constexpr int EVR = 4;              // per-frame event ring
-
-struct Pyramid {
-    uint8_t* img[MAX_PYR] = {};
-};
-
-}  // namespace vsd
+#include "stab_internal.h"
 
 using namespace vsd;
-
-struct vs_batch;
-int group_drain(vs_batch* g);
-int group_run(vs_batch* g);
-bool group_holds_warps(const vs_batch* g);
-const FirstFailure& group_failure(const vs_batch* g);     // rc VS_OK: the group has not failed
-vs_batch* group_new_own(vs_stab* s);
-void group_delete(vs_batch* g);
-
-struct vs_stab {
-    vs_params_c p;
-    int device = 0;
-    // batch mode: the schedule that runs this stream's batches (one launch per stage over the frames of all its streams) - the
-    // vs_batch the stream was created in, or the private group of one a standalone instance owns (`own`, made by allocate())
-    vs_batch* group = nullptr;
-    vs_batch* own = nullptr;
-    bool member = false;            // stream of a vs_batch_create group: driven through vs_batch_* only
-    bool group_call = false;        // ... which set this around the vs_stab_* calls they make on a member
-    hipStream_t st = nullptr;       // main
-    hipStream_t st_pre = nullptr;
-    hipStream_t st_det = nullptr;
-    hipStream_t st_warp = nullptr;  // deferred (batched) warps, high priority
-    bool shared_streams = false;    // the four streams belong to the per-device pool
-    std::string err;
-    // geometry, fixed by the first frame
-    bool allocated = false;
-    int w = 0, h = 0, fmt = VS_FMT_BGR8, cn = 3;
-    size_t row_bytes = 0, frame_bytes = 0;
-    size_t src_pitch = 0;               // row pitch of the frames the pipeline reads: row_bytes (queue ring) or the caller's (zero-copy)
-    size_t in_uv_off = 0, out_uv_off = 0;   // NV12 surfaces of the device entry points: UV plane offset, 0 = h * pitch
-    int rows_total = 0;
-    int aw = 960, ah = 540;
-    int levels = 0;                 // max pyramid level actually used
-    int lw[MAX_PYR], lh[MAX_PYR];
-    // frame queue (Stabilizer.h:311-312)
-    uint8_t* d_ring = nullptr;
-    std::deque<int> q_slot, q_idx;      // ring slot (-1: the caller's own buffer, zero-copy mode) and frame index
-    std::deque<const uint8_t*> q_ptr;   // where the queued frame lives
-    bool zero_copy = false;             // vs_stab_set_zero_copy
-    std::deque<int> free_slots;     // FIFO: the slot released longest ago is reused first
-    bool first = true;
-    int next_index = 0;             // index of the frame being pushed (nextFrameIndex_)
-    int detect_counter = 0;
-    int n_transforms = 0;           // transforms_.size(), mirrored on the host
-    int last_out_w = 0, last_out_h = 0;
-    int orig_w = 0, orig_h = 0;
-    int host_radius = 30;
-    int dbg_delay_us = 0;           // VS_STAB_DEBUG_DELAY_US: a spin kernel between tracking and RANSAC (ordering tests)
-    // analysis images
-    uint8_t* d_first_gray = nullptr;     // 480x270 (Stabilizer.cpp:277)
-    std::vector<Pyramid> pyr;           // ring: NPYR buffers, 2*batch+2 in batch mode
-    int npyr = NPYR;
-    bool prev_small = false;
-    bool have_prev_gray = false;
-    // keypoints (ping-pong: LK reads pts[pp], a re-detection writes pts[pp^1])
-    int ncap = 0;
-    // keypoint buffers: [0],[1] ping-pong per frame; batch mode cycles through all of them
-    std::vector<float*> d_pts;
-    std::vector<int32_t*> d_npts;
-    std::vector<int> pts_cap;
-    int pp = 0;
-    int last_lk_pp = 0;
-    float *d_next = nullptr, *d_err = nullptr, *d_vp = nullptr, *d_vc = nullptr;
-    uint8_t *d_status = nullptr, *d_inliers = nullptr;
-    int32_t *d_m = nullptr, *d_info = nullptr, *d_counts = nullptr;
-    double* d_model = nullptr;
-    void* d_gftt_scratch = nullptr;
-    GfttWork gw;
-    const RansacTables* tab = nullptr;
-    TrajState* d_traj = nullptr;
-    TrajParams tp;
-    float* d_M = nullptr;               // [0..5] frame matrix, [6..11] chroma matrix
-    double* d_Minv = nullptr;           // their inverse maps (what the warp kernels consume)
-    vs_debug_frame* d_dbg = nullptr;
-    int last_detect_pp = -1;            // buffer that holds the points detected on the last push
-    bool last_detected = false;
-    int last_gray_buf = 0;
-    // scratch for border / host I/O
-    uint8_t* d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-    uint8_t* d_fade = nullptr;          // borderType "fade": borderHistory_ (padded frame, packed rows)
-    bool fade_valid = false;
-    Canvas* canvas = nullptr;           // enableVirtualCanvas: temporal buffer and canvas geometry (outlive clean(), like the fade history)
-    float* d_ct = nullptr;              // the correction (dx, dy, da) of the output being produced, for the canvas
-    int fade_count = 0, fade_w = 0, fade_h = 0;     // fadeFrameCount_; geometry of the history
-    uint8_t* d_padB = nullptr;          // batch mode with a border: one padded (or to-be-cropped) frame per frame of a batch
-    size_t pad_frame_bytes = 0;
-    uint8_t* d_out = nullptr;
-    size_t out_bytes = 0;
-    // host pipeline (vs_stab_set_host_pipeline): the result of a call stays in d_hold[] and travels to the host during the
-    // NEXT call, next to that call's upload and ahead of its analysis
-    bool host_pipe = false, hold_valid = false;
-    uint8_t* d_hold[2] = {nullptr, nullptr};
-    int hold_cur = 0, hold_w = 0, hold_h = 0;
-    hipEvent_t ev_hold = nullptr;
-    std::unique_ptr<HostHelper> helper;     // issues the download when the caller's output buffer is pageable (push_host_pipelined)
-    uint8_t* d_all = nullptr;           // one allocation for the small buffers
-    vs_counters counters;
-    // cross-stream dependencies
-    hipEvent_t ev_gray[NPYR] = {}, ev_pre[NPYR] = {};
-    hipEvent_t ev_lk[EVR] = {}, ev_det[EVR] = {};
-    bool det_valid[EVR] = {false, false, false, false};
-    hipEvent_t ev_first = nullptr;
-    hipEvent_t ev_slot[FRAME_RING_MAX] = {};
-    bool slot_valid[FRAME_RING_MAX] = {};
-    int ring_frames = FRAME_RING;
-    hipEvent_t pts_event[2] = {nullptr, nullptr};   // recorded by the detection that filled pts[i]
-    bool pts_pending[2] = {false, false};
-    // deferred output (vs_stab_set_warp_batch): warps of consecutive outputs wait for each other and
-    // go out as ONE launch over up to WARP_BATCH_MAX frames, each into its caller's buffer
-    int warp_batch = 1;
-    struct PendWarp { const uint8_t* src; uint8_t* dst; int slot; };
-    std::vector<PendWarp> pend;
-    size_t pend_stride = 0;
-    double* d_MinvB[2] = {nullptr, nullptr};   // inverse maps of the pending frames, 12 doubles each; two sets
-    int32_t* d_tabs_def = nullptr;              // coordinate tables of a deferred warp launch
-    int pend_set = 0;
-    hipEvent_t ev_emit = nullptr, ev_warp[2] = {nullptr, nullptr};
-    bool warp_valid[2] = {false, false};
-    // batch mode (vs_stab_set_batch): the latency-bound analysis stages (GFTT, LK, RANSAC scoring) of `batch`
-    // consecutive frames run as ONE launch each; the ordered tail (selection + trajectory append, emit) stays
-    // per frame; the warps go out through the deferred list above.
-    int batch = 1;
-    bool batch_active = false;
-    struct BFrame {
-        int f, c, pv;
-        const uint8_t* frame; bool prev_small;
-        bool detect; int det_buf;
-        int lk_buf, lk_cap;
-        bool out_due; int out_slot, out_idx; const uint8_t* out_frame; uint8_t* d_out; size_t out_stride;
-        int have_prev_gray;
-    };
-    std::vector<BFrame> bq;
-    int kp_cur = 0, kp_next = 1;
-    std::vector<GfttWork> gws;                       // one GFTT scratch per detection of a batch
-    struct ItemBufs { float *next, *err, *vp, *vc; uint8_t *status, *inliers; int32_t *m, *info, *counts; double* model; };
-    std::vector<ItemBufs> items;
-    // what the debug getters read (last analysed frame)
-    const float* dbg_prev_pts = nullptr; const float* dbg_next = nullptr;
-    const uint8_t *dbg_status = nullptr, *dbg_inliers = nullptr;
-    const float* dbg_det_pts = nullptr; const int32_t* dbg_det_n = nullptr;
-    const int32_t* dbg_gftt_counters = nullptr;
-    // stage profiling (HIP events on the stream the stage runs on)
-    int prof_mode = 0;
-    struct Pending { hipEvent_t a, b; int stage; };
-    std::vector<Pending> pending;
-    std::vector<hipEvent_t> ev_pool;
-};
 
 namespace {
 
@@ -266,44 +50,8 @@ int fmt_cn(int fmt) {
     }
 }
 
-// Records an event pair around one stage when profiling is on.
-struct StageScope {
-    vs_stab* s;
-    int stage;
-    hipStream_t st;
-    bool on = false;
-    hipEvent_t a = nullptr, b = nullptr;
-    static hipEvent_t get(vs_stab* s) {
-        if (!s->ev_pool.empty()) { hipEvent_t e = s->ev_pool.back(); s->ev_pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        return e;
-    }
-    StageScope(vs_stab* s_, int stage_, hipStream_t st_) : s(s_), stage(stage_), st(st_) {
-        if (s->prof_mode == 2 || (s->prof_mode == 1 && stage == VS_STAGE_WARP) ||
-            (s->prof_mode == 3 && (stage == VS_STAGE_WARP || stage == VS_STAGE_WARP_TABLES))) {
-            a = get(s); b = get(s);
-            if (a && b && hipEventRecord(a, st) == hipSuccess) on = true;
-        }
-    }
-    ~StageScope() {
-        if (on && hipEventRecord(b, st) == hipSuccess) s->pending.push_back({a, b, stage});
-    }
-};
-
 int effective_radius(int r) { return std::max(5, std::min(r, 35)); }
-
-// enableVirtualCanvas acts where the reference reaches it: not behind the crop-and-zoom returns (Stabilizer.cpp:1108-1127)
-bool canvas_on(const vs_stab* s) { return s->p.enable_virtual_canvas && !s->p.crop_n_zoom; }
-
-void out_size(const vs_stab* s, int w, int h, int* ow, int* oh) {
-    const int b = s->p.border_size;
-    if (canvas_on(s)) { *ow = w; *oh = h; return; }     // the canvas window has the size of the unpadded frame (:2121-2126)
-    if (b > 0 && !s->p.crop_n_zoom) { *ow = w + 2 * b; *oh = h + 2 * b; return; }
-    *ow = w; *oh = h;   // crop+zoom resizes back to origSize_ == frame size
-}
-
-int flush_warps(vs_stab* s, bool on_main = false);
+int flush_warps(vs_stab* s);
 
 // Batch mode: everything queued so far is analysed and its warps are issued (nothing stays deferred).
 int drain_batch(vs_stab* s) {
@@ -317,20 +65,14 @@ int sync_all(vs_stab* s) {
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, flush_warps(s));
-    if (s->st_warp) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
-    if (s->st_pre) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));
-    if (s->st_det) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_det));
-    if (s->st) VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
+    VS_OBJ_HIP(s, sync_streams({s->st_warp, s->st_pre, s->st_det, s->st}));
     return VS_OK;
 }
 
 // Whatever the streams hold, failed or not, has run (before buffers go).
 void wait_streams(vs_stab* s) {
     (void)hipSetDevice(s->device);
-    if (s->st_pre) (void)hipStreamSynchronize(s->st_pre);
-    if (s->st_det) (void)hipStreamSynchronize(s->st_det);
-    if (s->st) (void)hipStreamSynchronize(s->st);
-    if (s->st_warp) (void)hipStreamSynchronize(s->st_warp);
+    (void)sync_streams({s->st_pre, s->st_det, s->st, s->st_warp});
 }
 
 void free_all(vs_stab* s) {
@@ -530,19 +272,6 @@ void fill_traj_params(vs_stab* s) {
     for (int i = 0; i < ks; i++) t.gauss_kernel[i] /= sum;
 }
 
-int build_pyramid(vs_stab* s, int k, hipStream_t st) {
-    Pyramid& P = s->pyr[k];
-    for (int l = 1; l <= s->levels; l++)
-        VS_OBJ_TRY(s, launch_pyr_down(P.img[l - 1], s->lw[l - 1], s->lw[l - 1], s->lh[l - 1], P.img[l], s->lw[l], st));
-    return VS_OK;
-}
-
-// NV12: where the interleaved UV plane of a queued frame / of an output surface starts
-inline size_t src_uv(const vs_stab* s) { return (s->zero_copy && s->in_uv_off) ? s->in_uv_off : (size_t)s->h * s->src_pitch; }
-inline size_t dst_uv(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
-    return (d_out != s->d_out && s->out_uv_off) ? s->out_uv_off : (size_t)s->h * out_stride;   // s->d_out: staging of the host entry points
-}
-
 // `pre` stream, part 1: the frame enters the queue ring (waits until the slot's last reader is done)
 int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMemcpyKind kind) {
     if (s->slot_valid[slot]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_slot[slot], 0));
@@ -616,10 +345,7 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
         s->pts_pending[pp] = false;
     }
     LKLevel L[MAX_PYR];
-    for (int l = 0; l <= s->levels; l++) {
-        L[l].prev = s->pyr[pv].img[l]; L[l].next = s->pyr[c].img[l];
-        L[l].w = s->lw[l]; L[l].h = s->lh[l]; L[l].stride = s->lw[l];
-    }
+    fill_lk_levels(s, pv, c, L);
     const int cap = s->pts_cap[pp];
     {
         StageScope t(s, VS_STAGE_LK, s->st);
@@ -647,31 +373,17 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     return VS_OK;
 }
 
-// A ring slot goes back to the free list behind the work on `st` that reads it.  A slot whose event cannot be recorded stays out
-// of the ring: its next writer would have nothing to wait for.
-int release_slot(vs_stab* s, int slot, hipStream_t st) {
-    if (slot < 0) return VS_OK;          // zero-copy: the frame is the caller's
-    VS_HIP_TRY(hipEventRecord(s->ev_slot[slot], st));
-    s->slot_valid[slot] = true;
-    s->free_slots.push_back(slot);
-    return VS_OK;
-}
-
-// One launch for all pending warps; releases their ring slots.  Per-frame pipeline: on the high-priority warp
-// stream, so that the analysis of the next frames is not held up.  Batch mode (on_main): in line on `main`,
-// between the tail of this batch and the tracking of the next - the tracking kernel keeps ~90 KB of LDS per
-// CU busy for its whole (latency-bound) run, which would leave room for 3 warp workgroups per CU instead of 8.
-int flush_warps(vs_stab* s, bool on_main) {
+// One launch for all pending warps of the per-frame pipeline; releases their ring slots.  On the high-priority warp
+// stream, so that the analysis of the next frames is not held up.
+int flush_warps(vs_stab* s) {
     if (s->pend.empty()) return VS_OK;
-    hipStream_t ws = on_main ? s->st : s->st_warp;
+    hipStream_t ws = s->st_warp;
     const int n = (int)s->pend.size(), set = s->pend_set;
     const uint8_t* srcs[WARP_BATCH_MAX];
     uint8_t* dsts[WARP_BATCH_MAX];
     for (int i = 0; i < n; i++) { srcs[i] = s->pend[i].src; dsts[i] = s->pend[i].dst; }
-    if (!on_main) {
-        VS_OBJ_HIP(s, hipEventRecord(s->ev_emit, s->st));             // the maps of this batch are written on `main`
-        VS_OBJ_HIP(s, hipStreamWaitEvent(ws, s->ev_emit, 0));
-    }
+    VS_OBJ_HIP(s, hipEventRecord(s->ev_emit, s->st));             // the maps of this batch are written on `main`
+    VS_OBJ_HIP(s, hipStreamWaitEvent(ws, s->ev_emit, 0));
     int rc;
     {
         StageScope t(s, VS_STAGE_WARP, ws);
@@ -727,6 +439,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
     out_size(s, s->w, s->h, &ow, &oh);
     s->last_out_w = ow; s->last_out_h = oh;
     const bool plain = idx < s->n_transforms && s->fmt != VS_FMT_NV12 && p.border_size <= 0 && !canvas_on(s);
+    const BorderPlan bp = border_plan(s);
     if (may_defer && plain && s->warp_batch > 1) {
         VS_OBJ_TRY(s, defer_output(s, idx, frame, d_out, out_stride, slot));
         s->counters.frames_out++;
@@ -759,10 +472,10 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         uint8_t* out_uv = d_out + dst_uv(s, d_out, out_stride);
         rc = launch_warp_nv12(&frame, &d_out, &uv, &out_uv, 1, s->src_pitch, out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
                               VS_BORDER_BLACK, WarpTabs{}, st);
-    } else if (p.border_size > 0 && !p.crop_n_zoom && p.border_type == VS_BORDER_FADE) {     // :914-978, :1069-1106
-        const int b = p.border_size, bw = s->w + 2 * b, bh = s->h + 2 * b;
-        const size_t prow = (size_t)bw * s->cn, nb = prow * bh;
-        rc = launch_make_border(frame, s->src_pitch, s->w, s->h, s->cn, s->d_tmp, prow, b, VS_BORDER_BLACK, st);
+    } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
+        const int bw = bp.pw, bh = bp.ph;
+        const size_t prow = bp.prow, nb = prow * bh;
+        rc = launch_make_border(frame, s->src_pitch, s->w, s->h, s->cn, s->d_tmp, prow, bp.b, VS_BORDER_BLACK, st);
         if (rc == VS_OK && (!s->d_fade || s->fade_w != bw || s->fade_h != bh)) {     // :917-926 the first padded frame is the history
             if (s->d_fade) { (void)hipStreamSynchronize(st); (void)hipFree(s->d_fade); s->d_fade = nullptr; }
             VS_OBJ_HIP(s, hipMalloc((void**)&s->d_fade, (nb + 3) & ~(size_t)3));
@@ -783,18 +496,15 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
             if (rc == VS_OK) rc = warp_frame(s, s->d_tmp, prow, bw, bh, d_out, out_stride, st);
         }
         if (rc == VS_OK) rc = launch_fade_update(s->d_fade, d_out, out_stride, (int)prow, bh, st);
-    } else if (p.border_size > 0 && !p.crop_n_zoom) {                                 // :981-990
-        const int b = p.border_size, bw = s->w + 2 * b, bh = s->h + 2 * b;
-        rc = launch_make_border(frame, s->src_pitch, s->w, s->h, s->cn, s->d_tmp, (size_t)bw * s->cn, b, p.border_type, st);
+    } else if (bp.pad) {                                                              // :981-990
+        rc = launch_make_border(frame, s->src_pitch, s->w, s->h, s->cn, s->d_tmp, bp.prow, bp.b, p.border_type, st);
         StageScope t(s, VS_STAGE_WARP, st);
-        if (rc == VS_OK)
-            rc = warp_frame(s, s->d_tmp, (size_t)bw * s->cn, bw, bh, d_out, out_stride, st);
-    } else if (p.crop_n_zoom && p.border_size > 0 && s->w - 2 * p.border_size > 0 && s->h - 2 * p.border_size > 0) {  // :1108-1124
-        const int b = p.border_size;
+        if (rc == VS_OK) rc = warp_frame(s, s->d_tmp, bp.prow, bp.pw, bp.ph, d_out, out_stride, st);
+    } else if (bp.crop) {                                                             // :1108-1124
         StageScope t(s, VS_STAGE_WARP, st);
-        rc = warp_frame(s, frame, s->src_pitch, s->w, s->h, s->d_tmp, s->row_bytes, st);
+        rc = warp_frame(s, frame, s->src_pitch, s->w, s->h, s->d_tmp, bp.prow, st);
         if (rc == VS_OK)
-            rc = launch_resize_linear(s->d_tmp + ((size_t)b * s->w + b) * s->cn, s->row_bytes, s->w - 2 * b, s->h - 2 * b,
+            rc = launch_resize_linear(s->d_tmp + ((size_t)bp.b * s->w + bp.b) * s->cn, bp.prow, s->w - 2 * bp.b, s->h - 2 * bp.b,
                                       s->cn, d_out, out_stride, s->orig_w, s->orig_h, st);
     } else {                                                                          // :1056-1060
         StageScope t(s, VS_STAGE_WARP, st);
@@ -1468,663 +1178,6 @@ int vs_stab_get_stage_times(vs_stab* s, double* total_ms, int64_t* launches) {
         s->ev_pool.push_back(pe.b);
     }
     s->pending.clear();
-    return VS_OK;
-}
-
-}  // extern "C"
-
-// ---- the batch schedule -------------------------------------------------------------------------------------------------
-// ONE schedule runs every batch: a vs_batch steps the frames that all its streams have queued (BASELINE configs[4]: 64 streams =
-// 8 per GPU), and a standalone instance in batch mode owns a private group of one (vs_stab::own).  N instances that each ran
-// their own batches took turns on the device's streams: every stage launched once per instance, the chains of one queued behind
-// the waits of another (8 instances: 101.7 k frames/s in total against 109.1 k for one, round 2).  A group goes through ONE
-// step for its members: the frames that all of them have queued since the last step go into one argument table per stage - the
-// tables hold one block per frame anyway, and a block names its frame's buffers, so a launch does not care whose frame it is -,
-// the ordered tails run as one launch with a workgroup per stream, and all due warps leave in launches of 32 frames.  The members
-// stay ordinary vs_stab instances (queues, pyramid rings, keypoint buffers, trajectory state, counters and debug records of
-// their own); host and device tables, the events of the schedule, the inverse maps and coordinate tables of the pending warps
-// belong to the group.
-//
-// One step (group_run), three streams:
-//   pre :  gray(n, two parts: re-detecting frames first) -> table uploads -> pyramid level(n) x levels
-//   det :  zero -> min_eigen -> nms -> select                 (starts behind the first gray part)
-//   main:  [warps of the PREVIOUS step] -> LK(n x 200 waves) -> RANSAC score -> select(n waves) -> ordered tail (1 WG per stream)
-//          -> releases (1 WG per push) -> coordinate tables of this step's warps
-// `main` waits for `pre` and for the wide launches of `det` of the same step, then issues the warps of the step before: at that
-// point the rest of pre/det of this step is done (it overlapped the tracking and tail of the step before) and its tracking has
-// not started, and `pre` of the next step waits for these warps - the HBM-bound warp has the GPU to itself (on a stream of its
-// own it overlapped the tracker, which holds ~90 KB of LDS per CU: 3 warp workgroups per CU instead of 8).
-struct vs_batch {
-    int device = 0, S = 0, B = 0, cap = 0;
-    bool own = false;                       // the private schedule of one standalone instance
-    std::vector<vs_stab*> m;
-    // The member whose geometry shapes the group's launches and tables, and on which its stage times are booked: the
-    // lowest-numbered member with frames in the step that allocated the group (member 0 unless it had none yet).  Members
-    // cannot change their geometry (vs_stab_clean is refused on them): it stays the reference until the group is freed.
-    vs_stab* ref = nullptr;
-    std::string err;
-    // A step that failed after it was numbered leaves its tables and events half done: the group stays failed, and every later
-    // step, drain or push of its members returns this first error.  (A standalone instance starts again with vs_stab_clean, which
-    // deletes its private group; vs_batch_destroy and vs_stab_destroy work on a failed group.)
-    FirstFailure failure;
-    hipStream_t st = nullptr, st_pre = nullptr, st_det = nullptr, st_up = nullptr;      // st_up: the table uploads (the pool's warp stream: idle in batch mode)
-    bool allocated = false;
-    // Host images of the argument tables of a step, in page-locked memory so that their uploads are asynchronous (from pageable
-    // memory hipMemcpyAsync holds the host until the stream gets to the copy, and the host then no longer runs ahead of the
-    // GPU): four sets, step k writes set k % 4 once the tail of step k-4 has run.  On the device the tracker / scoring / tail
-    // tables exist twice (k & 1): step k+1's are uploaded on `pre` while step k's are still read on `main`.
-    uint8_t* h_tables = nullptr;
-    size_t h_set_bytes = 0, ho_pairs = 0, ho_lk = 0, ho_rs = 0, ho_tail = 0, ho_gf = 0, ho_seg = 0;
-    uint8_t* d_all = nullptr;
-    uint8_t *d_lk[2] = {nullptr, nullptr}, *d_rs[2] = {nullptr, nullptr}, *d_tail[2] = {nullptr, nullptr}, *d_seg[2] = {nullptr, nullptr}, *d_gf = nullptr;
-    uint8_t* d_tin[2] = {nullptr, nullptr};         // per frame of a step: what the selection leaves for the tail
-    ImgPair* d_pairs[2] = {nullptr, nullptr};     // (per table set: a step's pair table goes up with its other tables, one copy)
-    size_t up_bytes = 0;                 // bytes of a table set that go to the device: pairs, tracker, scoring, tail, segments
-    int pre_rel_step = -1;               // the latest step whose tail `pre` has waited for (through the event of its warps' maps)
-    double* d_MinvB[2] = {nullptr, nullptr};        // inverse maps of the due frames of a step, 12 doubles each; two sets
-    int32_t* d_tabs[2] = {nullptr, nullptr};        // coordinate tables of those frames (warp_tab.h), tab_ints per frame; two sets
-    int tab_ints = 0;                               // one plane's table, or an NV12 surface's block of two
-    hipEvent_t ev_bpre = nullptr, ev_bgray = nullptr, ev_bnms = nullptr, ev_bdet[4] = {}, ev_blk[4] = {}, ev_warp[2] = {}, ev_rel[2] = {}, ev_up[2] = {}, ev_go = nullptr;
-    bool bdet_valid[4] = {false, false, false, false}, warp_valid[2] = {false, false}, rel_valid[2] = {false, false};
-    int last_det_batch = -1, last_warp_set = -1, batch_id = 0, pend_set = 0;
-    struct Ready {
-        bool valid = false, tabs_built = false;
-        int n = 0, set = 0, step = -1;         // step: the group_run that analysed these frames
-        size_t stride = 0;
-        std::vector<const uint8_t*> srcs;
-        std::vector<uint8_t*> dsts;
-        std::vector<int> slots, pad_idx;       // pad_idx: which of its owner's scratch frames (border pad / crop-and-zoom)
-        std::vector<vs_stab*> owner;
-    } ready, next;          // ready: the step whose tails are queued (its warps go out with the next step); next: the step being built
-};
-
-namespace {
-
-void group_free(vs_batch* g) {
-    if (g->h_tables) (void)hipHostFree(g->h_tables);
-    if (g->d_all) (void)hipFree(g->d_all);
-    g->h_tables = nullptr; g->d_all = nullptr;
-    g->allocated = false;
-    g->ref = nullptr;
-}
-
-bool group_make_events(vs_batch* g) {
-    auto mk = [&](hipEvent_t& e) { return hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; };
-    bool ok = mk(g->ev_bpre) && mk(g->ev_bgray) && mk(g->ev_bnms) && mk(g->ev_warp[0]) && mk(g->ev_warp[1]) && mk(g->ev_rel[0]) && mk(g->ev_rel[1]) && mk(g->ev_up[0]) && mk(g->ev_up[1]) && mk(g->ev_go);
-    for (auto& e : g->ev_bdet) ok = ok && mk(e);
-    for (auto& e : g->ev_blk) ok = ok && mk(e);
-    return ok;
-}
-
-// What the members must agree on: everything that shapes a launch (frame and analysis geometry, pitch, input mode, pyramid
-// depth, tracking window, hypothesis count, border mode).  Smoothing radius and method, horizon lock, the drone filters'
-// settings, corner count and thresholds are per stream: they live in each frame's argument block or in the stream's state.
-bool same_launch_shape(const vs_stab* a, const vs_stab* b) {
-    const vs_params_c &p = a->p, &q = b->p;
-    return a->w == b->w && a->h == b->h && a->fmt == b->fmt && a->src_pitch == b->src_pitch && a->zero_copy == b->zero_copy &&
-           a->in_uv_off == b->in_uv_off && a->out_uv_off == b->out_uv_off && a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
-           p.lk_win_size == q.lk_win_size && p.ransac_max_iters == q.ransac_max_iters && p.border_size == q.border_size &&
-           p.crop_n_zoom == q.crop_n_zoom && (p.border_size <= 0 || p.border_type == q.border_type);
-}
-
-// Tables and workspaces for cap = S * B frames per step, once the members know their geometry (g->ref's).
-int group_allocate(vs_batch* g) {
-    const vs_stab* s0 = g->ref;
-    const int cap = g->cap, ngf = g->S * (g->B / 2 + 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_gf = take(gftt_item_bytes() * ngf);
-    // a table set on the device = its image on the host (pairs, tracker items, scoring items, tail items, segments: ONE upload per step)
-    size_t ho = 0;
-    auto htake = [&](size_t bytes) { size_t o = ho; ho += (bytes + 255) & ~(size_t)255; return o; };
-    g->ho_pairs = htake(sizeof(ImgPair) * cap * MAX_PYR);
-    g->ho_lk = htake(lk_item_bytes() * cap); g->ho_rs = htake(ransac_item_bytes() * cap);
-    g->ho_tail = htake(tail_item_bytes() * cap); g->ho_seg = htake(tail_seg_bytes() * g->S);
-    g->up_bytes = ho;
-    g->ho_gf = htake(gftt_item_bytes() * ngf);
-    g->h_set_bytes = ho;
-    const size_t o_set[2] = {take(g->up_bytes), take(g->up_bytes)};
-    const size_t o_ti[2] = {take(tail_in_bytes() * cap), take(tail_in_bytes() * cap)};
-    const size_t o_minv[2] = {take((size_t)cap * 96), take((size_t)cap * 96)};
-    int tow, toh;
-    out_size(s0, s0->w, s0->h, &tow, &toh);
-    g->tab_ints = s0->fmt == VS_FMT_NV12 ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
-    size_t o_tabs[2];
-    for (auto& o : o_tabs) o = take((size_t)g->tab_ints * cap * sizeof(int32_t));
-    VS_OBJ_HIP(g, hipMalloc((void**)&g->d_all, off));
-    VS_OBJ_HIP(g, hipMemsetAsync(g->d_all, 0, off, g->st));
-    uint8_t* b = g->d_all;
-    g->d_gf = b + o_gf;
-    for (int i = 0; i < 2; i++) {
-        uint8_t* ds = b + o_set[i];
-        g->d_pairs[i] = (ImgPair*)(ds + g->ho_pairs);
-        g->d_lk[i] = ds + g->ho_lk; g->d_rs[i] = ds + g->ho_rs; g->d_tail[i] = ds + g->ho_tail; g->d_seg[i] = ds + g->ho_seg; g->d_tin[i] = b + o_ti[i];
-        g->d_MinvB[i] = (double*)(b + o_minv[i]);
-    }
-    for (int i = 0; i < 2; i++) g->d_tabs[i] = (int32_t*)(b + o_tabs[i]);
-    VS_OBJ_HIP(g, hipHostMalloc((void**)&g->h_tables, 4 * ho));
-    memset(g->h_tables, 0, 4 * ho);
-    VS_OBJ_HIP(g, hipStreamSynchronize(g->st));
-    for (vs_batch::Ready* r : {&g->ready, &g->next}) {
-        r->srcs.assign(cap, nullptr); r->dsts.assign(cap, nullptr); r->slots.assign(cap, -1); r->pad_idx.assign(cap, 0); r->owner.assign(cap, nullptr);
-    }
-    g->allocated = true;
-    return VS_OK;
-}
-
-// Where the frames of a step's warps come from and go to (border pad: the padded scratch frame is the source; crop-and-zoom: the
-// scratch frame is the destination, resized into the result afterwards).
-struct WarpEnds { const uint8_t* src; uint8_t* dst; };
-WarpEnds warp_ends(const vs_stab* o, const uint8_t* frame, uint8_t* d_out, int pad_idx, bool pad, bool crop) {
-    if (!pad && !crop) return {frame, d_out};
-    uint8_t* scratch = o->d_padB + (size_t)pad_idx * o->pad_frame_bytes;
-    return pad ? WarpEnds{scratch, d_out} : WarpEnds{frame, scratch};
-}
-
-// The warps of the step whose tails were queued last, 32 frames per launch (`what` = VS_WARP_ONLY / VS_WARP_ALL), or only their
-// coordinate tables (VS_WARP_TABLES_ONLY: steps whose release workgroups have not built them - a Kalman stream's releases stay
-// inside its tail workgroup).  The frames' tables lie tab_ints apart in d_tabs[set].
-int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
-    vs_batch::Ready& R = g->ready;
-    const vs_stab* s0 = g->ref;
-    const vs_params_c& p = s0->p;
-    const int bsz = p.border_size;
-    const bool pad = bsz > 0 && !p.crop_n_zoom;                                                       // Stabilizer.cpp:981-990
-    const bool crop = bsz > 0 && p.crop_n_zoom && s0->w - 2 * bsz > 0 && s0->h - 2 * bsz > 0;          // :1108-1124
-    const int pw = pad ? s0->w + 2 * bsz : s0->w, ph = pad ? s0->h + 2 * bsz : s0->h;
-    const size_t prow = (size_t)pw * s0->cn;
-    int rc = VS_OK;
-    // (launch by launch: the pads of a launch's frames are queued right in front of it, their crops right behind it)
-    for (int i0 = 0; i0 < R.n && rc == VS_OK; i0 += WARP_BATCH_MAX) {
-        const int m = std::min(WARP_BATCH_MAX, R.n - i0);
-        const uint8_t* srcs[WARP_BATCH_MAX];
-        uint8_t* dsts[WARP_BATCH_MAX];
-        for (int i = 0; i < m; i++) {
-            const WarpEnds e = warp_ends(R.owner[i0 + i], R.srcs[i0 + i], R.dsts[i0 + i], R.pad_idx[i0 + i], pad, crop);
-            srcs[i] = e.src; dsts[i] = e.dst;
-            // pad: the frames get their border first and the padded frames are warped into the (larger) results
-            if (pad && what != VS_WARP_TABLES_ONLY && rc == VS_OK)
-                rc = launch_make_border(R.srcs[i0 + i], s0->src_pitch, s0->w, s0->h, s0->cn, const_cast<uint8_t*>(e.src), prow, bsz, p.border_type, st);
-        }
-        if (rc != VS_OK) break;
-        const WarpMaps maps{g->d_MinvB[R.set] + 12 * i0, 12, false};
-        const WarpTabs tabs{WarpTabs::CALLER, g->d_tabs[R.set] + (size_t)i0 * g->tab_ints, g->tab_ints, what};
-        if (s0->fmt == VS_FMT_NV12) {
-            // interleaved chroma plane: half size, two channels, the map with the halved translation (Minv + 6)
-            const uint8_t* us[WARP_BATCH_MAX];
-            uint8_t* ud[WARP_BATCH_MAX];
-            for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + dst_uv(s0, dsts[i], R.stride); }
-            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st);
-            continue;
-        }
-        rc = launch_warp_plane(srcs, dsts, m, pad ? prow : s0->src_pitch, pw, ph, crop ? prow : R.stride, pw, ph, s0->cn, maps, VS_BORDER_BLACK,
-                               tabs, st);
-        // crop-and-zoom: the inner part of the warped scratch frames is resized to the results
-        for (int i = 0; crop && what != VS_WARP_TABLES_ONLY && i < m && rc == VS_OK; i++)
-            rc = launch_resize_linear(dsts[i] + ((size_t)bsz * s0->w + bsz) * s0->cn, prow, s0->w - 2 * bsz, s0->h - 2 * bsz, s0->cn,
-                                      R.dsts[i0 + i], R.stride, R.owner[i0 + i]->orig_w, R.owner[i0 + i]->orig_h, st);
-    }
-    if (rc != VS_OK) g->err = get_last_error();
-    return rc;
-}
-
-// The warps of the step in g->ready.  They run on `pre`, behind the gray / pyramid work of the step that issues them and in front of
-// the next step's: the cycle warps -> gray -> pyramid -> warps that sets the step time is then the order of ONE stream (as launches
-// on `main` with events in both directions - the pyramid's to `main`, the warps' back to `pre` - every period paid two event hand-overs,
-// 2 x 25 us of 545).  Their maps and tables come from the tail on `main`: ev_rel.
-int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
-    vs_batch::Ready& R = g->ready;
-    if (!R.valid) return VS_OK;
-    hipStream_t st = g->st_pre;
-    int rc;
-    // what the warps wait for - the step's maps and tables (ev_rel), the wide launches of the detector (det_done) - is gathered on the
-    // upload stream into ONE event: one packet in front of the warps on `pre` instead of two
-    if (g->rel_valid[R.set] || det_done) {
-        hipError_t e = hipSuccess;
-        if (det_done) e = hipStreamWaitEvent(g->st_up, det_done, 0);
-        if (e == hipSuccess && g->rel_valid[R.set]) e = hipStreamWaitEvent(g->st_up, g->ev_rel[R.set], 0);
-        if (e == hipSuccess) e = hipEventRecord(g->ev_go, g->st_up);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, g->ev_go, 0);
-        if (e != hipSuccess) return vs_obj_fail(g, VS_ERR_HIP, "hipStreamWaitEvent failed");
-        if (g->rel_valid[R.set]) g->pre_rel_step = std::max(g->pre_rel_step, R.step);
-        g->rel_valid[R.set] = false;
-    }
-    {
-        StageScope t(g->ref, VS_STAGE_WARP, st);   // (stage times of a group are booked on its reference member)
-        rc = group_ready_launches(g, R.tabs_built ? VS_WARP_ONLY : VS_WARP_ALL, st);
-    }
-    const hipError_t ew = hipEventRecord(g->ev_warp[R.set], st);
-    if (ew == hipSuccess) { g->warp_valid[R.set] = true; g->last_warp_set = R.set; }
-    else if (rc == VS_OK) rc = hip_fail(ew, "hipEventRecord(g->ev_warp[R.set], st)");
-    for (int i = 0; i < R.n; i++) {
-        if (!R.owner[i]) continue;
-        const int rrc = release_slot(R.owner[i], R.slots[i], st);
-        if (rc == VS_OK) rc = rrc;
-    }
-    R.valid = false;
-    if (rc != VS_OK) g->err = get_last_error();
-    return rc;
-}
-
-}  // namespace
-
-bool group_holds_warps(const vs_batch* g) { return g && (g->ready.valid || g->next.valid); }
-
-const FirstFailure& group_failure(const vs_batch* g) { return g->failure; }
-
-// The step numbered k over the frames of `act` (n in all, at most max_n per stream), once group_run has accepted them.
-static int group_step(vs_batch* g, const std::vector<vs_stab*>& act, int n, int max_n, int k) {
-    const vs_stab* s0 = g->ref;
-    // host images of this step's tables: the set step k-4 used (its tail, the last reader of anything uploaded from it, has run
-    // by now unless the host is four steps ahead of the GPU - then it waits here)
-    if (k >= 4) VS_OBJ_HIP(g, hipEventSynchronize(g->ev_blk[k % 4]));
-    uint8_t* hset = g->h_tables + (size_t)(k % 4) * g->h_set_bytes;
-    ImgPair* h_pairs = reinterpret_cast<ImgPair*>(hset + g->ho_pairs);
-    uint8_t *h_lk = hset + g->ho_lk, *h_rs = hset + g->ho_rs, *h_tail = hset + g->ho_tail, *h_gf = hset + g->ho_gf, *h_seg = hset + g->ho_seg;
-    const int dset = k & 1;
-    // ---- pre: gray images and pyramids of all frames of the step, one launch per stage and level
-    if (k >= 2 && g->pre_rel_step < k - 2) {
-        // ring reuse: these pyramid slots were read by the analysis two steps ago (npyr = 2 * batch + 2).  (When that step had
-        // outputs this stream has waited for its tail already, in front of its warps: nothing to wait for.)
-        VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_blk[(k - 2) % 4], 0));
-        if (g->bdet_valid[(k - 2) % 4]) VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_bdet[(k - 2) % 4], 0));
-    }
-    // (The HBM-bound warps stay alone on the GPU although the host runs steps ahead: they are launches on this stream, behind the
-    // pyramid of the step that issues them and in front of the next step's gray kernels - group_launch_ready.  Round 3 had them on
-    // `main` and an event from there that this stream waited for; without that guard 99.0 - 102.4 k frames/s against 112.4 - 114.2 k,
-    // warps 182 us instead of 86.)
-    // ---- argument tables of the tracker, the scoring and the tail (segment = stream): filled here (they do not depend on this
-    // step's images), uploaded in the middle of `pre`; which outputs become due and where their maps go is known on the host
-    const int set = g->pend_set;
-    vs_batch::Ready& R = g->next;           // (g->ready still holds the warps of the step before: they go out further down)
-    int idx = 0, n_max = 0, npend = 0, nseg = 0, any_apart = 0, all_apart = 1, ndue = 0;
-    size_t pend_stride = 0;
-    for (vs_stab* s : act) {
-        for (const vs_stab::BFrame& b : s->bq) ndue += b.out_due ? 1 : 0;
-        if (s->p.smoothing_method == VS_SMOOTH_KALMAN) all_apart = 0;
-    }
-    // the coordinate tables of a due frame's warp are built by the workgroup that releases the frame (every stream but a Kalman
-    // one: those maps come out of the tail workgroup, and the step's tables are a launch of their own behind it)
-    const vs_params_c& p0 = s0->p;
-    const bool pad = p0.border_size > 0 && !p0.crop_n_zoom;
-    const bool crop = p0.border_size > 0 && p0.crop_n_zoom && s0->w - 2 * p0.border_size > 0 && s0->h - 2 * p0.border_size > 0;
-    for (vs_stab* s : act) {
-        const vs_params_c& p = s->p;
-        const int ns = (int)s->bq.size(), first = idx;
-        int npad = 0;
-        for (int i = 0; i < ns; i++, idx++) {
-            const vs_stab::BFrame& b = s->bq[i];
-            const vs_stab::ItemBufs& it = s->items[i];
-            LKLevel L[MAX_PYR];
-            for (int l = 0; l <= s->levels; l++) {
-                L[l].prev = s->pyr[b.pv].img[l]; L[l].next = s->pyr[b.c].img[l];
-                L[l].w = s->lw[l]; L[l].h = s->lh[l]; L[l].stride = s->lw[l];
-            }
-            const int cap = std::max(b.lk_cap, 0);
-            n_max = std::max(n_max, cap);
-            VS_OBJ_TRY(g, lk_fill_item(h_lk + lk_item_bytes() * idx, L, s->levels, s->d_pts[b.lk_buf], cap, s->d_npts[b.lk_buf], it.next, it.status, it.err,
-                                  p.lk_win_size, p.lk_max_iters, p.lk_epsilon));                                    // :611-619
-            VS_OBJ_TRY(g, ransac_fill_item(h_rs + ransac_item_bytes() * idx, s->d_pts[b.lk_buf], it.next, it.status, cap, s->d_npts[b.lk_buf], it.vp, it.vc,
-                                      it.m, 4, p.ransac_threshold, p.ransac_max_iters, s->tab, it.counts, it.model, it.inliers, it.info, s->d_traj,
-                                      &s->tp, s->d_dbg, b.have_prev_gray));
-            ransac_item_set_last(h_rs + ransac_item_bytes() * idx, i == ns - 1 ? 1 : 0);
-            ransac_item_set_tail_in(h_rs + ransac_item_bytes() * idx, g->d_tin[dset] + tail_in_bytes() * idx);
-            double* minv = nullptr;
-            WarpTabJob jobs[2] = {{nullptr, nullptr, nullptr, 0, 0}, {nullptr, nullptr, nullptr, 0, 0}};
-            if (b.out_due) {
-                minv = g->d_MinvB[set] + 12 * npend;
-                R.srcs[npend] = b.out_frame; R.dsts[npend] = b.d_out; R.slots[npend] = b.out_slot; R.owner[npend] = s; R.pad_idx[npend] = npad;
-                // (launches of fewer than four frames - the rest of a step's due frames beyond a multiple of 32 - run without tables)
-                if (all_apart && std::min(WARP_BATCH_MAX, ndue - npend / WARP_BATCH_MAX * WARP_BATCH_MAX) >= WARP_TAB_MIN) {
-                    const WarpEnds e = warp_ends(s, b.out_frame, b.d_out, npad, pad, crop);
-                    int32_t* T = g->d_tabs[set] + (size_t)npend * g->tab_ints;
-                    jobs[0] = WarpTabJob{T, e.src, e.dst, pad ? s->w + 2 * p0.border_size : s->w, pad ? s->h + 2 * p0.border_size : s->h};
-                    if (s->fmt == VS_FMT_NV12)
-                        jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + dst_uv(s, e.dst, b.out_stride), s->w / 2, s->h / 2};
-                }
-                npad++;
-                pend_stride = b.out_stride;
-                npend++;
-            }
-            tail_fill_item(h_tail + tail_item_bytes() * idx, b.out_due ? 1 : 0, b.out_idx, minv, jobs);
-            tail_item_set_seg(h_tail + tail_item_bytes() * idx, nseg);
-        }
-        tail_fill_seg(h_seg + tail_seg_bytes() * nseg, first, ns, s->d_M, s->d_traj, s->d_dbg, p.smoothing_method);
-        any_apart |= p.smoothing_method != VS_SMOOTH_KALMAN;
-        nseg++;
-        if (s->bq[0].prev_small) {   // Stabilizer.cpp:598-603 (once per stream: 480x270 -> analysis size)
-            StageScope t(g->ref, VS_STAGE_PYRAMID, g->st_pre);
-            VS_OBJ_TRY(g, launch_resize_gray(s->d_first_gray, 480, 480, 270, VS_FMT_GRAY8, s->pyr[s->bq[0].pv].img[0], s->aw, s->aw, s->ah, g->st_pre));
-            VS_OBJ_TRY(g, build_pyramid(s, s->bq[0].pv, g->st_pre));
-        }
-    }
-    {
-        // pair tables: [0] frame -> img[0]; [1..levels] img[l-1] -> img[l]
-        const int L = s0->levels;
-        int aligned = 1, n_detect = 0;
-        // level-0 pairs: the frames that re-detect first, so that the detector can start after a first, smaller launch
-        for (vs_stab* s : act) for (const vs_stab::BFrame& b : s->bq) n_detect += b.detect ? 1 : 0;
-        int n_first = 0, n_rest = 0, i = 0;
-        for (vs_stab* s : act)
-            for (const vs_stab::BFrame& b : s->bq) {
-                const Pyramid& P = s->pyr[b.c];
-                const int slot = b.detect ? n_first++ : n_detect + n_rest++;
-                h_pairs[slot] = ImgPair{b.frame, P.img[0]};
-                if ((uintptr_t)b.frame % 8) aligned = 0;
-                for (int l = 1; l <= L; l++) h_pairs[(size_t)l * n + i] = ImgPair{P.img[l - 1], P.img[l]};
-                i++;
-            }
-        // ONE upload per step: the pair tables of the gray / pyramid launches and, behind them in the set, the tables of the tracker,
-        // the scoring and the tail (all filled above).  (As five copies - the four small ones in the middle of `pre`, which had slack
-        // while the warps ran on `main` - they stood 46 us on what is the step's longest chain since the warps run on this stream.)
-        // The copy runs on a stream of its own: the host is a step or two ahead of the GPU, so the tables are there long before `pre`
-        // gets to this step (as a copy on `pre` it stood between the warps and the gray kernels: 26 us of hand-over to the copy engine
-        // and back on the step's longest chain).  The set was last used by step k - 2: its tail must have run.
-        ImgPair* const d_pairs = g->d_pairs[dset];
-        if (k >= 2) VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_up, g->ev_blk[(k - 2) % 4], 0));
-        VS_OBJ_HIP(g, hipMemcpyAsync(g->d_pairs[dset], hset, g->up_bytes, hipMemcpyHostToDevice, g->st_up));
-        VS_OBJ_HIP(g, hipEventRecord(g->ev_up[dset], g->st_up));
-        VS_OBJ_HIP(g, hipStreamWaitEvent(g->st_pre, g->ev_up[dset], 0));
-        {
-            StageScope t(g->ref, VS_STAGE_GRAY, g->st_pre);
-            // NV12: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline)
-            const int gfmt = s0->fmt == VS_FMT_NV12 ? VS_FMT_GRAY8 : s0->fmt;
-            const int n_a = (n_detect > 0 && n_detect < n) ? n_detect : n;
-            VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs, n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));  // :448-450
-            VS_OBJ_HIP(g, hipEventRecord(g->ev_bgray, g->st_pre));      // the detector needs the analysis images of its frames only
-            if (n_a < n)
-                VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs + n_a, n - n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, aligned, g->st_pre));
-        }
-        StageScope t(g->ref, VS_STAGE_PYRAMID, g->st_pre);
-        // One pyrDown launch per level (pyr_level_kernel): the tracker computes the derivatives it needs from the images.
-        for (int l = 0; l < L; l++)
-            VS_OBJ_TRY(g, launch_pyr_level_batch(nullptr, d_pairs + (size_t)(l + 1) * n, n, s0->lw[l], s0->lw[l], s0->lh[l], s0->lw[l + 1], g->st_pre));
-    }
-    // (`main` waits for the event behind this step's warps when there are any: it covers the pyramid, which lies in front of them)
-    if (!g->ready.valid) VS_OBJ_HIP(g, hipEventRecord(g->ev_bpre, g->st_pre));
-    // ---- det: every frame of the step that re-detects, one launch per GFTT stage
-    int ndet = 0;
-    for (vs_stab* s : act) {
-        int local = 0;
-        for (const vs_stab::BFrame& b : s->bq) {
-            if (!b.detect) continue;
-            VS_OBJ_TRY(g, gftt_fill_item(h_gf + gftt_item_bytes() * ndet, s->pyr[b.c].img[0], s->aw, s->aw, s->ah, s->pts_cap[b.det_buf], 0.02, 15.0, 3,
-                                    s->gws[local], s->d_pts[b.det_buf], s->d_npts[b.det_buf]));                      // :740-744
-            s->dbg_det_pts = s->d_pts[b.det_buf]; s->dbg_det_n = s->d_npts[b.det_buf];
-            s->dbg_gftt_counters = s->gws[local].counters;
-            local++; ndet++;
-        }
-        s->last_detected = s->bq.back().detect;
-    }
-    hipStream_t sd = g->st_det;
-    if (ndet > 0) {
-        // starts as soon as the analysis images of its frames exist, next to the pyramid levels of this step and the tracking of
-        // the previous one (the table and the reset of the counters first: they are through by the time the images are)
-        VS_OBJ_HIP(g, hipMemcpyAsync(g->d_gf, h_gf, gftt_item_bytes() * ndet, hipMemcpyHostToDevice, sd));
-        // keypoint buffers are recycled after B + 4 detections (two steps): the tracking of the step before the previous one
-        // must have read them (the GFTT scratch is only touched on this stream)
-        if (k >= 2) VS_OBJ_HIP(g, hipStreamWaitEvent(sd, g->ev_blk[(k - 2) % 4], 0));
-        VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 1));
-        VS_OBJ_HIP(g, hipStreamWaitEvent(sd, g->ev_bgray, 0));
-        {
-            StageScope t(g->ref, VS_STAGE_GFTT, sd);
-            VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 4));
-            VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 5));
-            // the wide launches of the detection are through: the warps of the step before may go (below); the selection -
-            // one workgroup per image - runs beside them
-            VS_OBJ_HIP(g, hipEventRecord(g->ev_bnms, sd));
-            VS_OBJ_TRY(g, launch_gftt_batch(g->d_gf, ndet, s0->aw, s0->ah, 3, sd, 3));
-        }
-        VS_OBJ_HIP(g, hipEventRecord(g->ev_bdet[k % 4], sd));
-        g->last_det_batch = k;
-    }
-    g->bdet_valid[k % 4] = ndet > 0;
-    // ---- main: tracking and hypothesis scoring of all frames, one launch each
-    hipStream_t st = g->st;
-    const bool wait_det = g->last_det_batch >= 0 && g->last_det_batch >= k - 1;
-    const bool early = wait_det && g->last_det_batch == k;
-    // The warps of the PREVIOUS step go out here, on `pre` behind this step's pyramid, once the wide launches of this step's
-    // detection are through: nothing but the corner selection (a workgroup per image) runs beside them.
-    const bool warps_go = g->ready.valid;
-    VS_OBJ_TRY(g, group_launch_ready(g, early ? g->ev_bnms : (wait_det ? g->ev_bdet[g->last_det_batch % 4] : (hipEvent_t) nullptr)));
-    // ---- main: waits for this step's gray / pyramid work, its corners and - the tracker takes every vector register of every SIMD,
-    // beside it the warps would crawl - the warps just issued
-    if (warps_go && g->last_warp_set >= 0) VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_warp[g->last_warp_set], 0));
-    else VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_bpre, 0));
-    for (vs_stab* s : act)
-        if (s->pts_pending[0]) { VS_OBJ_HIP(g, hipStreamWaitEvent(st, s->pts_event[0], 0)); s->pts_pending[0] = false; }
-    if (wait_det) VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_bdet[g->last_det_batch % 4], 0));       // the tracker needs the selected corners
-    {
-        StageScope t(g->ref, VS_STAGE_LK, st);
-        VS_OBJ_TRY(g, launch_pyr_lk_batch(g->d_lk[dset], n, n_max, s0->p.lk_win_size, st));
-    }
-    {
-        StageScope t(g->ref, VS_STAGE_RANSAC, st);
-        VS_OBJ_TRY(g, launch_ransac_score_batch(g->d_rs[dset], n, s0->p.ransac_max_iters, n_max, st));
-    }
-    for (vs_stab* s : act)
-        if (s->dbg_delay_us > 0) { VS_OBJ_TRY(g, launch_spin(s->dbg_delay_us, st)); break; }
-    // ---- ordered tails, ONE launch (a workgroup per stream): per frame in push order the trajectory append (:644-693), then
-    // the map of the output that has become due (applyNextSmoothTransform sees exactly the transforms appended so far)
-    if (npend > 0 && g->warp_valid[set]) {         // the previous user of this set of maps must have read them
-        VS_OBJ_HIP(g, hipStreamWaitEvent(st, g->ev_warp[set], 0));
-        g->warp_valid[set] = false;
-    }
-    {
-        StageScope t(g->ref, VS_STAGE_TRAJ, st);
-        VS_OBJ_TRY(g, launch_ransac_tail_group(g->d_rs[dset], g->d_tail[dset], g->d_seg[dset], g->d_tin[dset], nseg, max_n, n, any_apart, st));
-    }
-    // the keypoint and pyramid buffers of this step may be recycled (two steps on) once the tail, which still reads the points
-    // and their counts, has run
-    VS_OBJ_HIP(g, hipEventRecord(g->ev_blk[k % 4], st));
-    // the warps of this step wait for the next one (or a drain); their maps exist once the tail has run: the coordinate tables
-    // are built right behind it
-    R.n = npend; R.set = set; R.stride = pend_stride; R.valid = npend > 0; R.tabs_built = all_apart != 0; R.step = k;
-    std::swap(g->ready, g->next);            // (the previous step's warps have been issued: g->ready was free)
-    if (g->ready.valid) {
-        g->pend_set = set ^ 1;
-        if (!g->ready.tabs_built) {          // (a Kalman stream in the step: the tables as a launch behind the tail)
-            StageScope t(g->ref, VS_STAGE_WARP_TABLES, st);
-            VS_OBJ_TRY(g, group_ready_launches(g, VS_WARP_TABLES_ONLY, st));
-            g->ready.tabs_built = true;
-        }
-        VS_OBJ_HIP(g, hipEventRecord(g->ev_rel[set], st));          // maps and tables of this step's warps exist
-        g->rel_valid[set] = true;
-    }
-    for (vs_stab* s : act) {
-        const vs_stab::BFrame& lb = s->bq.back();
-        const int nl = (int)s->bq.size();
-        s->dbg_prev_pts = s->d_pts[lb.lk_buf]; s->dbg_next = s->items[nl - 1].next;
-        s->dbg_status = s->items[nl - 1].status; s->dbg_inliers = s->items[nl - 1].inliers;
-        s->bq.clear();
-    }
-    return VS_OK;
-}
-
-// One step: everything the members have queued.  What refuses a step is decided before it is numbered; a failure after that
-// leaves the group failed (group_failure).
-int group_run(vs_batch* g) {
-    if (g->failure.rc != VS_OK) return vs_obj_fail(g, g->failure.rc, g->failure.msg);
-    std::vector<vs_stab*> act;
-    int n = 0, max_n = 0;
-    for (vs_stab* s : g->m)
-        if (!s->bq.empty()) { act.push_back(s); n += (int)s->bq.size(); max_n = std::max(max_n, (int)s->bq.size()); }
-    if (n == 0) return VS_OK;
-    VS_OBJ_HIP(g, hipSetDevice(g->device));
-    // every member with frames in this step has the reference's launch shape; the group's first step makes its first active
-    // member the reference (a member that has had no frame yet - a camera that connects late - has no geometry to compare)
-    const vs_stab* s0 = g->ref ? g->ref : act[0];
-    size_t out_stride = 0;
-    int ndue = 0;
-    for (vs_stab* s : act) {
-        if (!s->allocated || !s->batch_active || !same_launch_shape(s, s0))
-            return vs_obj_fail(g, VS_ERR_INVALID_ARG, "vs_batch: the streams of a group share one frame geometry, pitch, input mode and launch shape "
-                                                "(analysis size, pyramid depth, tracking window, hypothesis count, border mode)");
-        for (const vs_stab::BFrame& b : s->bq) {
-            if (!b.out_due) continue;
-            if (ndue++ > 0 && out_stride != b.out_stride) return vs_obj_fail(g, VS_ERR_INVALID_ARG, "batch mode: one output pitch per step");
-            out_stride = b.out_stride;
-        }
-    }
-    if (n > g->cap || max_n > BATCH_MAX) return vs_obj_fail(g, VS_ERR_CAPACITY, "vs_batch: more frames queued than a step holds");
-    if (!g->allocated) {
-        g->ref = act[0];
-        const int rc = group_allocate(g);
-        if (rc != VS_OK) { group_free(g); return rc; }
-    }
-    const int rc = group_step(g, act, n, max_n, g->batch_id++);
-    g->failure.note(rc, g->err);
-    return rc;
-}
-
-// Everything the members have queued is analysed and its warps are issued.  (The warps of a step normally go out with the NEXT
-// step, between its detection and its tracking; group_run issues the pending ones itself, so the step before the drained one is
-// covered too.)
-int group_drain(vs_batch* g) {
-    VS_OBJ_HIP(g, hipSetDevice(g->device));
-    VS_OBJ_TRY(g, group_run(g));                 // (issues the warps of the step before on its way; nothing queued: nothing done)
-    const int rc = group_launch_ready(g);
-    g->failure.note(rc, g->err);
-    return rc;
-}
-
-void group_delete(vs_batch* g) {
-    if (!g) return;
-    group_free(g);
-    auto kill = [](hipEvent_t& e) { if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-    kill(g->ev_bpre); kill(g->ev_bgray); kill(g->ev_bnms); kill(g->ev_warp[0]); kill(g->ev_warp[1]); kill(g->ev_rel[0]); kill(g->ev_rel[1]); kill(g->ev_up[0]); kill(g->ev_up[1]); kill(g->ev_go);
-    for (auto& e : g->ev_bdet) kill(e);
-    for (auto& e : g->ev_blk) kill(e);
-    delete g;
-}
-
-// The private schedule of a standalone instance in batch mode: a group of one, steps of `batch` frames.
-vs_batch* group_new_own(vs_stab* s) {
-    vs_batch* g = new (std::nothrow) vs_batch();
-    if (!g) { set_last_error("out of host memory"); return nullptr; }
-    g->device = s->device; g->S = 1; g->B = s->batch; g->cap = s->batch; g->own = true;
-    g->m.push_back(s);
-    g->st = s->st; g->st_pre = s->st_pre; g->st_det = s->st_det; g->st_up = s->st_warp;
-    if (!group_make_events(g)) { set_last_error("hipEventCreate failed"); group_delete(g); return nullptr; }
-    return g;
-}
-
-namespace {
-// vs_stab_* calls that vs_batch_* makes on a member
-struct MemberCall {
-    vs_stab* s;
-    explicit MemberCall(vs_stab* s_) : s(s_) { s->group_call = true; }
-    ~MemberCall() { s->group_call = false; }
-};
-}  // namespace
-
-extern "C" {
-
-// params: ONE block for all streams (per_stream = 0) or n_streams blocks.  Per-stream blocks may differ in everything that does
-// not shape a launch (same_launch_shape): smoothing radius and method, horizon lock, the drone filters' settings, corner count.
-static int batch_create(int device, int n_streams, const vs_params_c* params, int per_stream, int frames_per_step, vs_batch** out) {
-    if (!out) return VS_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!params || n_streams < 1 || n_streams > 256 || frames_per_step < 1 || frames_per_step > BATCH_MAX) {
-        set_last_error("vs_batch_create: 1..256 streams, 1..64 frames per stream and step");
-        return VS_ERR_INVALID_ARG;
-    }
-    for (int i = 0; i < (per_stream ? n_streams : 1); i++) {
-        const vs_params_c& p = params[i];
-        if (p.struct_size != (int32_t)sizeof(vs_params_c)) { set_last_error("params: struct_size mismatch"); return VS_ERR_INVALID_ARG; }
-        // modes whose outputs depend on each other or on a host decision per output run in the per-frame pipeline only
-        if (p.adaptive_smoothing || (p.border_size > 0 && !p.crop_n_zoom && p.border_type == VS_BORDER_FADE) || (p.enable_virtual_canvas && !p.crop_n_zoom)) {
-            set_last_error("vs_batch_create: adaptive smoothing, the fade border and the virtual canvas are per-stream modes (use vs_stab_*)");
-            return VS_ERR_UNSUPPORTED;
-        }
-    }
-    vs_batch* g = new (std::nothrow) vs_batch();
-    if (!g) return VS_ERR_HIP;
-    g->device = device; g->S = n_streams; g->B = frames_per_step; g->cap = n_streams * frames_per_step;
-    for (int i = 0; i < n_streams; i++) {
-        vs_stab* s = nullptr;
-        int rc = vs_stab_create(&params[per_stream ? i : 0], device, &s);
-        if (rc == VS_OK) rc = vs_stab_set_batch(s, frames_per_step);
-        if (rc != VS_OK) { if (s) vs_stab_destroy(s); vs_batch_destroy(g); return rc; }
-        s->group = g; s->member = true;
-        g->m.push_back(s);
-    }
-    g->st = g->m[0]->st; g->st_pre = g->m[0]->st_pre; g->st_det = g->m[0]->st_det; g->st_up = g->m[0]->st_warp;
-    if (!group_make_events(g)) { set_last_error("vs_batch_create: hipEventCreate failed"); vs_batch_destroy(g); return VS_ERR_HIP; }
-    *out = g;
-    return VS_OK;
-}
-
-int vs_batch_create(int device, int n_streams, const vs_params_c* params, int frames_per_step, vs_batch** out) {
-    return batch_create(device, n_streams, params, 0, frames_per_step, out);
-}
-
-int vs_batch_create_params(int device, int n_streams, const vs_params_c* params_per_stream, int frames_per_step, vs_batch** out) {
-    return batch_create(device, n_streams, params_per_stream, 1, frames_per_step, out);
-}
-
-void vs_batch_destroy(vs_batch* g) {
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    if (g->st_pre) (void)hipStreamSynchronize(g->st_pre);
-    if (g->st_det) (void)hipStreamSynchronize(g->st_det);
-    if (g->st) (void)hipStreamSynchronize(g->st);
-    for (vs_stab* s : g->m) { s->group = nullptr; s->member = false; s->bq.clear(); vs_stab_destroy(s); }
-    group_delete(g);
-}
-
-int vs_batch_streams(const vs_batch* g) { return g ? g->S : 0; }
-vs_stab* vs_batch_stream(vs_batch* g, int i) { return (g && i >= 0 && i < g->S) ? g->m[(size_t)i] : nullptr; }
-const char* vs_batch_last_error(const vs_batch* g) { return g ? g->err.c_str() : ""; }
-
-int vs_batch_set_zero_copy(vs_batch* g, int enable) {
-    if (!g) return VS_ERR_INVALID_ARG;
-    for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_zero_copy(s, enable); if (rc != VS_OK) { g->err = s->err; return rc; } }
-    return VS_OK;
-}
-
-int vs_batch_set_nv12_layout(vs_batch* g, size_t in_uv_offset, size_t out_uv_offset) {
-    if (!g) return VS_ERR_INVALID_ARG;
-    for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_nv12_layout(s, in_uv_offset, out_uv_offset); if (rc != VS_OK) { g->err = s->err; return rc; } }
-    return VS_OK;
-}
-
-int vs_batch_push_dev(vs_batch* g, const void* const* d_frames, int w, int h, size_t stride, int fmt, void* const* d_outs, size_t out_stride,
-                      int* produced) {
-    if (!g || !d_frames || !d_outs || !produced) return VS_ERR_INVALID_ARG;
-    for (int i = 0; i < g->S; i++) produced[i] = 0;
-    if (g->failure.rc != VS_OK) return vs_obj_fail(g, g->failure.rc, g->failure.msg);
-    bool full = false;
-    for (int i = 0; i < g->S; i++) {
-        if (!d_frames[i]) continue;                       // no frame for this stream in this call
-        vs_stab* s = g->m[(size_t)i];
-        MemberCall mc(s);
-        const int rc = vs_stab_push_dev(s, d_frames[i], w, h, stride, fmt, d_outs[i], out_stride, &produced[i]);
-        if (rc != VS_OK) { g->err = s->err; return rc; }
-        full |= (int)s->bq.size() >= g->B;
-    }
-    if (full) return group_run(g);
-    return VS_OK;
-}
-
-int vs_batch_flush_dev(vs_batch* g, void* const* d_outs, size_t out_stride, int* produced) {
-    if (!g || !d_outs || !produced) return VS_ERR_INVALID_ARG;
-    int rc = group_drain(g);
-    if (rc != VS_OK) return rc;
-    for (int i = 0; i < g->S; i++) {
-        produced[i] = 0;
-        MemberCall mc(g->m[(size_t)i]);
-        rc = vs_stab_flush_dev(g->m[(size_t)i], d_outs[i], out_stride, &produced[i]);
-        if (rc != VS_OK) { g->err = g->m[(size_t)i]->err; return rc; }
-    }
-    return VS_OK;
-}
-
-int vs_batch_sync(vs_batch* g) {
-    if (!g) return VS_ERR_INVALID_ARG;
-    int rc = group_drain(g);
-    if (rc != VS_OK) return rc;
-    for (vs_stab* s : g->m) { rc = vs_stab_sync(s); if (rc != VS_OK) { g->err = s->err; return rc; } }
     return VS_OK;
 }
 

@@ -1,6 +1,6 @@
 // C ABI of libvideo-stab (include/vs_stab.h): library-level entry points,
 // device memory helpers and the stage operators.  The per-stream pipeline
-// (vs_stab_*) lives in stabilizer.cpp.
+// (vs_stab_*) lives in stabilizer.cpp, the batch schedule (vs_batch_*) in batch_schedule.cpp.
 #include <cmath>
 #include <cstring>
 #include <mutex>
