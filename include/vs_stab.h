@@ -11,7 +11,8 @@
  * Conventions
  *  - plain pointers and sizes only; no C++/torch/OpenCV types cross this ABI;
  *  - every function returns a vs_status; nothing throws across the ABI;
- *  - images are 8-bit, row-major, with an explicit row stride in BYTES;
+ *  - images are 8-bit, row-major, with an explicit row stride in BYTES (the one exception: VS_FMT_P010
+ *    surfaces hold 16-bit samples; their strides and plane offsets are in BYTES all the same);
  *  - `*_dev` entry points take DEVICE pointers and are asynchronous on the
  *    instance's HIP stream; the host-pointer forms copy in/out and synchronise;
  *  - there is no CPU fallback: if no gfx950 device is usable every compute
@@ -31,7 +32,7 @@ extern "C" {
  *    (round 2), vs_batch_* and vs_dev_copy_rate / vs_dev_memcpy_d2d added.  (The pipelined host call is chosen with
  *    vs_stab_set_host_pipeline - Parameters::hostPipeline of the C++ class - not through vs_params_c, whose layout is unchanged.)
  *    Added since without a layout change: vs_batch_create_params (round 4); the pixel formats VS_FMT_BGRA8,
- *    VS_FMT_RGBA8 and VS_FMT_RGB8. */
+ *    VS_FMT_RGBA8 and VS_FMT_RGB8; VS_FMT_P010 (enum vs_pixfmt16) with vs_op_warp_affine_p010. */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -52,6 +53,27 @@ typedef enum vs_pixfmt {
     VS_FMT_RGBA8 = 4,         /* interleaved R,G,B,A                          */
     VS_FMT_RGB8 = 5           /* interleaved R,G,B                            */
 } vs_pixfmt;
+
+/* Formats with 16-bit samples, numbered on from vs_pixfmt in the same `int fmt`.
+ * P010 (rocDecode / VA-API output of HEVC Main10, AV1 10-bit, VP9 profile 2): the NV12 layout with one little-endian 16-bit
+ * word per sample, the ten significant bits at the top.  A surface of w x h (both even) is a luma plane of h rows of w uint16
+ * samples followed by an interleaved chroma plane of h/2 rows of w/2 (U, V) uint16 pairs.  Pitch and plane offset are in
+ * BYTES, exactly as for NV12 (`stride`, vs_stab_set_nv12_layout; offset 0 = h * pitch); pointers, pitches and the plane offset
+ * must be even (VS_ERR_INVALID_ARG otherwise).  Nothing assumes that the low six bits are zero: P012 / P016 content passes
+ * through the same code and the same definitions:
+ *  - analysis: the gray image is that of the 8-bit plane made of the luma samples' high bytes (sample >> 8: truncation, what
+ *    a decoder's own 8-bit export holds), resized as the luma plane of an NV12 frame is - so keypoints, tracks, model,
+ *    trajectory and warp matrix are bit-identical to those of the NV12 (or GRAY8) stream of the high bytes;
+ *  - warp: cv::warpAffine(INTER_LINEAR, BORDER_CONSTANT 0) on the CV_16UC1 luma plane and, with the translation halved, on the
+ *    CV_16UC2 chroma plane: source coordinates as for 8 bits (AB_BITS = 10, 1/32 px), blend = the exact integer
+ *    S = sum v_i n_i over the four taps (n = (32-fy)(32-fx), (32-fy)fx, fy(32-fx), fy fx; sum 1024; taps outside the picture
+ *    are 0, each by itself), rounded once, half to even: (S + 511 + ((S >> 10) & 1)) >> 10.  For ten-bit content that is
+ *    what OpenCV's float blend gives; for arbitrary 16-bit content it is the definition (docs/opencv_semantics.md);
+ *  - everything else follows NV12: the last frame of a flush comes back unwarped; border pad, crop-and-zoom, fade and the
+ *    virtual canvas are refused as for NV12. */
+typedef enum vs_pixfmt16 {
+    VS_FMT_P010 = 6           /* Y plane (h rows of w uint16) followed by UV plane (h/2 rows of w/2 uint16 pairs) */
+} vs_pixfmt16;
 
 /* Stabilizer.cpp:31-38 mapBorderMode() */
 typedef enum vs_border {
@@ -287,7 +309,7 @@ int vs_stab_set_warp_batch(vs_stab* s, int frames);
  * (at most 32 frames per warp launch: a batch of 64 is two launches back to back).
  * Results are bit-identical to frames = 1 and complete after vs_stab_sync(); every push must
  * be given its own d_out until then.  Must be chosen before the first frame (or after
- * vs_stab_clean).  BGR8, GRAY8 and NV12 frames; border padding and crop-and-zoom (BGR8
+ * vs_stab_clean).  BGR8, GRAY8, NV12 and P010 frames; border padding and crop-and-zoom (BGR8
  * only, like everywhere) run batched too; the "fade" border, the virtual canvas and
  * adaptive smoothing keep the per-frame path (each of their outputs depends on the one
  * before it or on a host decision).  Instances of one device share its HIP streams and
@@ -311,6 +333,7 @@ int vs_stab_set_zero_copy(vs_stab* s, int enable);
  * vs_stab_push_dev (`in`) and for the surfaces it fills (`out`); 0 = contiguous (h * pitch).
  * With zero-copy input the stabilizer then reads decoder surfaces and writes encoder surfaces
  * in place: no repacking blit on either side.  The frame queue must be empty. */
+/* P010 surfaces take the same call: the offsets are in bytes and must be even. */
 int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offset);
 
 /* ---- several streams of one device scheduled together (BASELINE configs[4]: 64 streams = 8 per GPU) ----------------------
@@ -412,6 +435,13 @@ int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst,
                            size_t dst_stride, int w, int h, const float* M,
                            int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
                            void* stream);
+/* P010 surface (vs_pixfmt16): the 16-bit luma plane warped with M, the interleaved 16-bit chroma plane at half resolution
+ * with the translation halved; blend rounded half to even (see vs_pixfmt16).  Strides and frame distances in BYTES, all
+ * even, as the pointers. */
+int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst,
+                           size_t dst_stride, int w, int h, const float* M,
+                           int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
+                           void* stream);
 /* std::cos / std::sin / std::atan2 on float as the reference calls them (Stabilizer.cpp:662, 902-908, 1689: the host libm's
  * cosf / sinf / atan2f), evaluated by the DEVICE build of the library's restatement: the sum over i in [start, start + count) of
  * a 64-bit mix of (i, bits of f(argument i)) - fn 0 cosf, 1 sinf, 2 atanf: argument i = the float with bit pattern (uint32_t)i;
@@ -419,7 +449,8 @@ int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst,
 int vs_op_libm_checksum(int fn, uint64_t start, uint64_t count, uint64_t* result);
 /* cv::resize(INTER_LINEAR) + cv::cvtColor(BGR2GRAY) - Stabilizer.cpp:304-305,
  * 448-450.  fmt BGR8 / BGRA8 / RGBA8 / RGB8 (resize per channel, then gray from
- * B, G, R; alpha ignored), GRAY8 / NV12 (luma plane resize). */
+ * B, G, R; alpha ignored), GRAY8 / NV12 (luma plane resize), P010 (resize of the luma
+ * samples' high bytes; the result is an 8-bit gray image). */
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt,
                       void* d_dst, size_t dst_stride, int dw, int dh, void* stream);
 /* cv::pyrDown as used inside calcOpticalFlowPyrLK - Stabilizer.cpp:611 */

@@ -146,7 +146,7 @@ int group_allocate(vs_batch* g) {
     const size_t o_minv[2] = {take((size_t)cap * 96), take((size_t)cap * 96)};
     int tow, toh;
     out_size(s0, s0->w, s0->h, &tow, &toh);
-    g->tab_ints = s0->fmt == VS_FMT_NV12 ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
+    g->tab_ints = fmt_two_planes(s0->fmt) ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
     size_t o_tabs[2];
     for (auto& o : o_tabs) o = take((size_t)g->tab_ints * cap * sizeof(int32_t));
     VS_OBJ_HIP(g, hipMalloc((void**)&g->d_all, off));
@@ -202,12 +202,12 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
         if (rc != VS_OK) break;
         const WarpMaps maps{g->d_MinvB[R.set] + 12 * i0, 12, false};
         const WarpTabs tabs{WarpTabs::CALLER, g->d_tabs[R.set] + (size_t)i0 * g->tab_ints, g->tab_ints, what};
-        if (s0->fmt == VS_FMT_NV12) {
+        if (fmt_two_planes(s0->fmt)) {
             // interleaved chroma plane: half size, two channels, the map with the halved translation (Minv + 6)
             const uint8_t* us[WARP_BATCH_MAX];
             uint8_t* ud[WARP_BATCH_MAX];
             for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + dst_uv(s0, dsts[i], R.stride); }
-            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st);
+            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, fmt_sample_bytes(s0->fmt));
             continue;
         }
         rc = launch_warp_plane(srcs, dsts, m, bp.pad ? bp.prow : s0->src_pitch, bp.pw, bp.ph, bp.crop ? bp.prow : R.stride, bp.pw, bp.ph, s0->cn, maps,
@@ -308,7 +308,7 @@ int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const
                 const WarpEnds e = warp_ends(s, b.out_frame, b.d_out, npad, bp);
                 int32_t* T = g->d_tabs[set] + (size_t)j * g->tab_ints;
                 jobs[0] = WarpTabJob{T, e.src, e.dst, bp.pw, bp.ph};
-                if (s->fmt == VS_FMT_NV12)
+                if (fmt_two_planes(s->fmt))
                     jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + dst_uv(s, e.dst, b.out_stride), s->w / 2, s->h / 2};
             }
             npad++;
@@ -410,7 +410,8 @@ int step_issue_pre(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan
     VS_OBJ_HIP(g, hipStreamWaitEvent(pre, g->ev_up[dset], 0));
     {
         StageScope t(g->ref, VS_STAGE_GRAY, pre);
-        // NV12: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline)
+        // NV12: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline); P010: the high bytes
+        // of the Y plane's samples are (the resize kernels read them in place)
         const int gfmt = s0->fmt == VS_FMT_NV12 ? VS_FMT_GRAY8 : s0->fmt;
         const int n_a = (P.ndet > 0 && P.ndet < n) ? P.ndet : n;
         VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs, n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, P.aligned, pre));  // :448-450

@@ -12,6 +12,8 @@
 // Colour frames come as BGR8, RGB8, BGRA8 or RGBA8: BI is the byte of B inside a pixel (0 or 2; R sits at 2 - BI), PS the
 // pixel's size (3 or 4).  Every channel is resized as it is and the gray value read from the B, G and R results, as
 // cv::resize + cv::cvtColor(BGR2GRAY / BGRA2GRAY) do on the same Mat; the fourth byte is never read into the gray image.
+// P010 luma planes: samples of SS = 2 bytes whose value is the second (high) byte - the gray image of a P010 frame is that of the
+// 8-bit plane of its luma samples' high bytes (sample >> 8), resized as a GRAY8 picture is; the low byte is never read into it.
 #include "vs_common.h"
 
 namespace vsd {
@@ -169,7 +171,8 @@ __global__ __launch_bounds__(NT) void half_bgra_gray16_kernel(size_t sstride, si
 }
 
 // ---- general bilinear (any scale), CN = 3 / 4 (-> gray, B at byte BI) or 1 ------
-template <int CN, bool TO_GRAY, int BI = 0>
+// SS: bytes of a source sample, the value in the last one (1; 2 = the luma plane of a P010 surface, CN = 1).
+template <int CN, bool TO_GRAY, int BI = 0, int SS = 1>
 __global__ __launch_bounds__(NT) void resize_gray_kernel(const uint8_t* __restrict__ src_, size_t sstride,
                                                          int sw, int sh, uint8_t* __restrict__ dst_,
                                                          size_t dstride, int dw, int dh, double scale_x,
@@ -181,10 +184,10 @@ __global__ __launch_bounds__(NT) void resize_gray_kernel(const uint8_t* __restri
     if (dx >= dw || dy >= dh) return;
     uint32_t v[CN];
     if (area2) {
-        const uint8_t* r0 = src + (size_t)(2 * dy) * sstride + (size_t)(2 * dx) * CN;
+        const uint8_t* r0 = src + (size_t)(2 * dy) * sstride + (size_t)(2 * dx) * (CN * SS) + (SS - 1);
         const uint8_t* r1 = r0 + sstride;
 #pragma unroll
-        for (int k = 0; k < CN; k++) v[k] = (r0[k] + r0[CN + k] + r1[k] + r1[CN + k] + 2u) >> 2;
+        for (int k = 0; k < CN; k++) v[k] = (r0[SS * k] + r0[SS * (CN + k)] + r1[SS * k] + r1[SS * (CN + k)] + 2u) >> 2;
     } else {
         float fx = (float)((dx + 0.5) * scale_x - 0.5);
         int sx = f_floor(fx);
@@ -203,17 +206,17 @@ __global__ __launch_bounds__(NT) void resize_gray_kernel(const uint8_t* __restri
         int sy0 = sy, sy1 = sy + 1;
         sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
         sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
-        const uint8_t* r0 = src + (size_t)sy0 * sstride + (size_t)sx * CN;
-        const uint8_t* r1 = src + (size_t)sy1 * sstride + (size_t)sx * CN;
+        const uint8_t* r0 = src + (size_t)sy0 * sstride + (size_t)sx * (CN * SS) + (SS - 1);
+        const uint8_t* r1 = src + (size_t)sy1 * sstride + (size_t)sx * (CN * SS) + (SS - 1);
 #pragma unroll
         for (int k = 0; k < CN; k++) {
             int h0, h1;
             if (!edge) {
-                h0 = r0[k] * a0 + r0[CN + k] * a1;
-                h1 = r1[k] * a0 + r1[CN + k] * a1;
+                h0 = r0[SS * k] * a0 + r0[SS * (CN + k)] * a1;
+                h1 = r1[SS * k] * a0 + r1[SS * (CN + k)] * a1;
             } else {
-                h0 = r0[k] * 2048;
-                h1 = r1[k] * 2048;
+                h0 = r0[SS * k] * 2048;
+                h1 = r1[SS * k] * 2048;
             }
             v[k] = (uint32_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
         }
@@ -232,17 +235,28 @@ __global__ __launch_bounds__(NT) void resize_gray_kernel(const uint8_t* __restri
 // resize_gray_kernel, ((1024 * ((1024 (p00 + p01)) >> 4)) >> 16 + the same of the row below + 2) >> 2, is the rounded mean of the
 // 2 x 2 block at (4 dx + 1, 4 dy + 1).  A lane takes four output pixels = the bytes 1, 2 / 5, 6 / 9, 10 / 13, 14 of two 16-byte loads.
 // (The general kernel - a pixel per lane, byte loads, the weights in double - took 2 x 176 us of the 845-us step at 3840 x 2160.)
+// SS = 2 (P010 luma, 3840 x 2160 -> 960 x 540): the four output pixels are 16 samples = two 16-byte loads per row, and the samples 1, 2 /
+// 5, 6 of a load are the high halves / low halves of its dwords x, y / z, w: their high bytes are bytes 3 and 1.
 constexpr int QG_ROWS = 4;      // output rows per workgroup (one per wave)
+template <int SS>
 __global__ __launch_bounds__(NT) void quarter_gray_kernel(size_t sstride, size_t dstride, int dw, int dh, const ImgPair* __restrict__ table) {
     const uint8_t* __restrict__ src = static_cast<const uint8_t*>(table[blockIdx.z].src);
     uint8_t* __restrict__ dst = static_cast<uint8_t*>(table[blockIdx.z].dst);
     const int lane = threadIdx.x & 63, dy = blockIdx.y * QG_ROWS + (threadIdx.x >> 6);
     const int x4 = (blockIdx.x * 64 + lane) * 4;
     if (dy >= dh || x4 >= dw) return;
-    const uint8_t* r0 = src + (size_t)(4 * dy + 1) * sstride + (size_t)4 * x4;
+    const uint8_t* r0 = src + (size_t)(4 * dy + 1) * sstride + (size_t)(4 * SS) * x4;
     const uint8_t* r1 = r0 + sstride;
     const bool vec = (((uintptr_t)src | sstride) & 15) == 0 && (((uintptr_t)dst | dstride) & 3) == 0 && x4 + 3 < dw;      // (the first two: per picture)
-    if (vec) {
+    if (vec && SS == 2) {
+        const uint4 a0 = *reinterpret_cast<const uint4*>(r0), a1 = *reinterpret_cast<const uint4*>(r0 + 16);
+        const uint4 b0 = *reinterpret_cast<const uint4*>(r1), b1 = *reinterpret_cast<const uint4*>(r1 + 16);
+        auto mean = [](uint32_t t0, uint32_t t1, uint32_t u0, uint32_t u1) {      // (t0, t1): the dwords that hold samples (0, 1) and (2, 3)
+            return ((t0 >> 24) + ((t1 >> 8) & 255u) + (u0 >> 24) + ((u1 >> 8) & 255u) + 2u) >> 2;
+        };
+        *reinterpret_cast<uint32_t*>(dst + (size_t)dy * dstride + x4) =
+            mean(a0.x, a0.y, b0.x, b0.y) | mean(a0.z, a0.w, b0.z, b0.w) << 8 | mean(a1.x, a1.y, b1.x, b1.y) << 16 | mean(a1.z, a1.w, b1.z, b1.w) << 24;
+    } else if (vec) {
         const uint4 a = *reinterpret_cast<const uint4*>(r0), b = *reinterpret_cast<const uint4*>(r1);
         auto mean = [](uint32_t t, uint32_t u) {
             return (((t >> 8) & 255u) + ((t >> 16) & 255u) + ((u >> 8) & 255u) + ((u >> 16) & 255u) + 2u) >> 2;
@@ -251,7 +265,8 @@ __global__ __launch_bounds__(NT) void quarter_gray_kernel(size_t sstride, size_t
             mean(a.x, b.x) | mean(a.y, b.y) << 8 | mean(a.z, b.z) << 16 | mean(a.w, b.w) << 24;
     } else {
         for (int i = 0; i < 4 && x4 + i < dw; i++)
-            dst[(size_t)dy * dstride + x4 + i] = (uint8_t)((r0[4 * i + 1] + r0[4 * i + 2] + r1[4 * i + 1] + r1[4 * i + 2] + 2u) >> 2);
+            dst[(size_t)dy * dstride + x4 + i] = (uint8_t)((r0[SS * (4 * i + 1) + SS - 1] + r0[SS * (4 * i + 2) + SS - 1] + r1[SS * (4 * i + 1) + SS - 1] +
+                                                            r1[SS * (4 * i + 2) + SS - 1] + 2u) >> 2);
     }
 }
 
@@ -299,7 +314,7 @@ int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, 
     int bi = 0, ps = 1;
     const bool color = color_layout(fmt, &bi, &ps);
     if (!d_pairs || items < 1 || items > 65535 || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 ||
-        (!color && fmt != VS_FMT_GRAY8)) {
+        (!color && fmt != VS_FMT_GRAY8 && fmt != VS_FMT_P010)) {
         set_last_error("resize_gray_batch: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
@@ -324,13 +339,17 @@ int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, 
             dim3 grid(((dw + 3) / 4 + NT - 1) / NT, dh, items);
             launch_half_color(bi, ps, grid, np, sstride, nd, dstride, dw, dh, vec_ok, d_pairs, st);
         }
-    } else if (fmt == VS_FMT_GRAY8 && sw == 4 * dw && sh == 4 * dh) {
+    } else if (!color && sw == 4 * dw && sh == 4 * dh) {
         dim3 grid((dw + 255) / 256, (dh + QG_ROWS - 1) / QG_ROWS, items);
-        hipLaunchKernelGGL(quarter_gray_kernel, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
+        if (fmt == VS_FMT_P010) hipLaunchKernelGGL(quarter_gray_kernel<2>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
+        else hipLaunchKernelGGL(quarter_gray_kernel<1>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
     } else {
         dim3 grid((dw + NT - 1) / NT, dh, items);
         if (color)
             launch_resize_color(bi, ps, grid, np, sstride, sw, sh, nd, dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, d_pairs, st);
+        else if (fmt == VS_FMT_P010)
+            hipLaunchKernelGGL((resize_gray_kernel<1, true, 0, 2>), grid, dim3(NT), 0, st, np, sstride, sw, sh, nd, dstride, dw, dh,
+                               scale_x, scale_y, area2 ? 1 : 0, d_pairs);
         else
             hipLaunchKernelGGL((resize_gray_kernel<1, true>), grid, dim3(NT), 0, st, np, sstride, sw, sh, nd, dstride, dw, dh,
                                scale_x, scale_y, area2 ? 1 : 0, d_pairs);
@@ -344,8 +363,12 @@ int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int
     int bi = 0, ps = 1;
     const bool color = color_layout(fmt, &bi, &ps);
     if (!d_src || !d_dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 ||
-        (!color && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8)) {
+        (!color && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8 && fmt != VS_FMT_P010)) {
         set_last_error("resize_gray: invalid argument");
+        return VS_ERR_INVALID_ARG;
+    }
+    if (fmt == VS_FMT_P010 && (((uintptr_t)d_src | sstride) & 1)) {
+        set_last_error("resize_gray: P010 pointers and pitches must be even");
         return VS_ERR_INVALID_ARG;
     }
     // cv::resize: scale = 1/(dsize/ssize); INTER_LINEAR with an exact 2x2
@@ -365,6 +388,9 @@ int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int
         if (color)
             launch_resize_color(bi, ps, grid, d_src, sstride, sw, sh, d_dst, dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0,
                                 (const ImgPair*)nullptr, st);
+        else if (fmt == VS_FMT_P010)
+            hipLaunchKernelGGL((resize_gray_kernel<1, true, 0, 2>), grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst,
+                               dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, (const ImgPair*)nullptr);
         else
             hipLaunchKernelGGL((resize_gray_kernel<1, true>), grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst,
                                dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, (const ImgPair*)nullptr);

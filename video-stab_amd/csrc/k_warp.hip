@@ -80,13 +80,20 @@ struct WarpArgs {
 
 // One source pixel as a dword; outside the image: 0 (BORDER_CONSTANT) or the nearest
 // edge pixel (BORDER_REPLICATE, remapBilinear's clip()).
-template <int CN>
+// SB = 2: 16-bit samples (P010 planes; CN = 1 or 2): the sample, or the (U, V) pair, as the dword's halves.
+template <int CN, int SB = 1>
 __device__ __forceinline__ uint32_t load_px_checked(const uint8_t* src, size_t sstride, int sw,
                                                     int sh, int sx, int sy, int border = VS_BORDER_BLACK) {
     if (border == VS_BORDER_REPLICATE) {
         sx = sx < 0 ? 0 : (sx >= sw ? sw - 1 : sx);
         sy = sy < 0 ? 0 : (sy >= sh ? sh - 1 : sy);
     } else if ((unsigned)sx >= (unsigned)sw || (unsigned)sy >= (unsigned)sh) return 0u;
+    if (SB == 2) {
+        const uint16_t* q = reinterpret_cast<const uint16_t*>(src + (size_t)sy * sstride) + (size_t)sx * CN;
+        uint32_t v16 = q[0];
+        if (CN > 1) v16 |= (uint32_t)q[1] << 16;
+        return v16;
+    }
     const uint8_t* p = src + (size_t)sy * sstride + (size_t)sx * CN;
     uint32_t v = p[0];
     if (CN > 1) v |= (uint32_t)p[1] << 8;
@@ -134,6 +141,34 @@ __device__ __forceinline__ uint32_t blend(uint32_t p00, uint32_t p01, uint32_t p
     return out;
 }
 
+// ---- 16-bit samples (P010) ---------------------------------------------------------------------------------------------------
+// cv::warpAffine on CV_16U data blends with the float table w = n / 1024, n = ((32-fy)(32-fx), (32-fy)fx, fy(32-fx), fy fx), and
+// saturate_cast<ushort> rounds half to even.  Here: the exact integer S = sum v_i n_i (< 2^26) in its separable form, rounded once,
+// half to even - for ten-bit content what the float form gives on any build, for arbitrary 16-bit content the definition.
+// The fp32-on-denormals vertical lerp of the 8-bit kernels does not carry over (S needs 26 bits): integer throughout.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+// pair = [v(x), v(x+1)] as the halves of a dword, w = (32 - fx) | fx << 16: the horizontal lerp in one v_dot2_u32_u16 (< 2^21)
+__device__ __forceinline__ uint32_t hlerp16(uint32_t pair, uint32_t w) {
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pair), __builtin_bit_cast(u16x2, w), 0u, false);
+}
+
+// t, b: the horizontal sums of the upper and the lower tap row; S = t (32 - fy) + b fy = 32 t + fy (b - t)
+__device__ __forceinline__ uint32_t vlerp16(uint32_t t, uint32_t b, uint32_t fy) {
+    const uint32_t S = (t << 5) + (uint32_t)__mul24((int)fy, (int)b - (int)t);
+    return (S + 511u + ((S >> 10) & 1u)) >> 10;
+}
+
+// Taps as load_px_checked<CN, 2> gives them -> the pixel in the same form.
+template <int CN>
+__device__ __forceinline__ uint32_t blend16(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, uint32_t fx, uint32_t fy) {
+    const uint32_t wx = (32u - fx) | (fx << 16);
+    uint32_t out = vlerp16(hlerp16(__builtin_amdgcn_perm(p01, p00, 0x05040100u), wx), hlerp16(__builtin_amdgcn_perm(p11, p10, 0x05040100u), wx), fy);
+    if (CN > 1)
+        out |= vlerp16(hlerp16(__builtin_amdgcn_perm(p01, p00, 0x07060302u), wx), hlerp16(__builtin_amdgcn_perm(p11, p10, 0x07060302u), wx), fy) << 16;
+    return out;
+}
+
 struct __attribute__((aligned(4))) U3 { uint32_t a, b, c; };
 struct __attribute__((aligned(4))) U4 { uint32_t a, b, c, d; };
 
@@ -174,7 +209,7 @@ __device__ __forceinline__ uint4 stage_group(const WarpCore& c, const uint8_t* _
     return px;
 }
 
-template <int CN, bool USE_LDS>
+template <int CN, bool USE_LDS, int SB = 1>
 __device__ __forceinline__ void emit_rows(const WarpCore& c, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                           const uint32_t* tile, const int* s_ad, const int* s_bd, const int* s_x0,
                                           const int* s_y0, int x0, int y0, int x1, int y1, int bx0a, int by0, int bw, int tid) {
@@ -202,20 +237,42 @@ __device__ __forceinline__ void emit_rows(const WarpCore& c, const uint8_t* __re
                 p00[i] = tile[idx]; p01[i] = tile[idx + 1];
                 p10[i] = tile[idx + bw]; p11[i] = tile[idx + bw + 1];
             } else {
-                p00[i] = load_px_checked<CN>(src, c.sstride, c.sw, c.sh, sx, sy, c.border);
-                p01[i] = load_px_checked<CN>(src, c.sstride, c.sw, c.sh, sx + 1, sy, c.border);
-                p10[i] = load_px_checked<CN>(src, c.sstride, c.sw, c.sh, sx, sy + 1, c.border);
-                p11[i] = load_px_checked<CN>(src, c.sstride, c.sw, c.sh, sx + 1, sy + 1, c.border);
+                p00[i] = load_px_checked<CN, SB>(src, c.sstride, c.sw, c.sh, sx, sy, c.border);
+                p01[i] = load_px_checked<CN, SB>(src, c.sstride, c.sw, c.sh, sx + 1, sy, c.border);
+                p10[i] = load_px_checked<CN, SB>(src, c.sstride, c.sw, c.sh, sx, sy + 1, c.border);
+                p11[i] = load_px_checked<CN, SB>(src, c.sstride, c.sw, c.sh, sx + 1, sy + 1, c.border);
             }
         }
 #pragma unroll
-        for (int i = 0; i < PX; i++) o[r][i] = blend<CN>(p00[i], p01[i], p10[i], p11[i], fx[i], fy[i]);
+        for (int i = 0; i < PX; i++) {
+            if constexpr (SB == 2) o[r][i] = blend16<CN>(p00[i], p01[i], p10[i], p11[i], fx[i], fy[i]);
+            else o[r][i] = blend<CN>(p00[i], p01[i], p10[i], p11[i], fx[i], fy[i]);
+        }
     }
 #pragma unroll
     for (int r = 0; r < TH / TYN; r++) {
         const int y = y0 + ty + TYN * r;
         if (y > y1) break;
-        uint8_t* d = dst + (size_t)y * c.dstride + (size_t)x * CN;
+        uint8_t* d = dst + (size_t)y * c.dstride + (size_t)x * (CN * SB);
+        if (SB == 2) {             // a pixel is one (luma) or two (chroma) 16-bit samples: four pixels = 8 / 16 aligned bytes
+            if (c.dst_aligned && x + PX - 1 <= x1) {
+                if (CN == 1) {
+                    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                    __builtin_nontemporal_store(u32x2{o[r][0] | (o[r][1] << 16), o[r][2] | (o[r][3] << 16)}, reinterpret_cast<u32x2*>(d));
+                } else {
+                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                    __builtin_nontemporal_store(u32x4{o[r][0], o[r][1], o[r][2], o[r][3]}, reinterpret_cast<u32x4*>(d));
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < PX; i++) {
+                    if (x + i > x1) break;
+#pragma unroll
+                    for (int c = 0; c < CN; c++) reinterpret_cast<uint16_t*>(d)[i * CN + c] = (uint16_t)(o[r][i] >> (16 * c));
+                }
+            }
+            continue;
+        }
         if (c.dst_aligned && x + PX - 1 <= x1) {
             if (CN == 3) {
                 U3 v;
@@ -550,6 +607,31 @@ __global__ __launch_bounds__(NT) void warp_affine_kernel(WarpArgs a) {
     if (CN == 3 && fast) emit_fast(a.c, dst, tile, obuf, lut, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, -(by0 * FPITCH + bx0a), tid);
     else if (use_lds) emit_rows<CN, true>(a.c, src, dst, tile, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, bx0a, by0, bw, tid);
     else emit_rows<CN, false>(a.c, src, dst, tile, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, bx0a, by0, bw, tid);
+}
+
+// The general form for planes of 16-bit samples (CN = 1: P010 luma, CN = 2: interleaved chroma): single surfaces, launches without
+// tables, chroma planes that do not lie one offset behind their luma planes, geometry outside what warp_nv12_kernel packs.  Terms
+// from the frame's inverse map as in the kernel above, taps read directly (no staging): emit_rows' arithmetic for 16-bit samples.
+template <int CN>
+__global__ __launch_bounds__(NT) void warp_affine16_kernel(WarpArgs a) {
+    __shared__ int s_ad[TW], s_bd[TW], s_x0[TH], s_y0[TH];
+    const int bz = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int x1 = min(x0 + TW, a.c.dw) - 1, y1 = min(y0 + TH, a.c.dh) - 1;
+    double m[6];
+    load_map(a, bz, m);
+    if (tid < TW) {
+        const double dv = (double)min(x0 + tid, x1);
+        s_ad[tid] = coord_term(m[0], 0.0, dv);
+        s_bd[tid] = coord_term(m[3], 0.0, dv);
+    } else if (tid < TW + TH) {
+        const double dv = (double)min(y0 + (tid - TW), y1);
+        s_x0[tid - TW] = coord_term(m[1], m[2], dv) + 16;
+        s_y0[tid - TW] = coord_term(m[4], m[5], dv) + 16;
+    }
+    __syncthreads();
+    emit_rows<CN, false, 2>(a.c, a.srcs[bz], a.dsts[bz], nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
 }
 
 // ---- several small warps of different geometry in ONE launch --------------------------------------------------------------
@@ -903,9 +985,14 @@ __device__ __forceinline__ uint4 load_chunk_replicate(const uint8_t* rowp, int x
     return make_uint4(wq[0], wq[1], wq[2], wq[3]);
 }
 
-template <int CN> struct PlaneCfg {
-    static constexpr int THP = 64 / CN;                  // rows of a tile (four channels: 16, the rows of a table record)
-    static constexpr int DB = 136 * CN + 8 * CN;         // staged bytes of a row (136 pixels + slack for the 8-byte tap read)
+// SB = 2: planes of 16-bit samples (P010).  The tables and the box stay in pixels; a pixel is PXB = CN * SB bytes, and the tile shape,
+// the staged box and the LDS budget follow from PXB alone: 16-bit luma (2 bytes) as the 8-bit two-channel plane - 128 x 32 pixels,
+// rows of 384 bytes, 41 of them, 15.4 KiB -, 16-bit chroma (4 bytes) as the four-channel plane - 128 x 16, 640 x 25, 15.6 KiB: eight
+// workgroups per CU as before.
+template <int CN, int SB = 1> struct PlaneCfg {
+    static constexpr int PXB = CN * SB;                  // bytes of a pixel
+    static constexpr int THP = 64 / PXB;                 // rows of a tile (four bytes per pixel: 16, the rows of a table record)
+    static constexpr int DB = 136 * PXB + 8 * PXB;       // staged bytes of a row (136 pixels + slack for the 8-byte tap read)
     // Row pitch of the staged box: a multiple of 128 bytes = of the 32 LDS banks.  The lanes of a tap read sit on consecutive dwords
     // of a row until the map's rotation moves them a source row down (or up), once per tile row for anything but a pure
     // translation; with a pitch of 144 bytes those lanes land 4 banks to the side, on banks their neighbours use, and every tap
@@ -982,9 +1069,38 @@ __device__ __forceinline__ uint32_t plane_blend_px(const uint8_t* tl, const uint
     return __builtin_amdgcn_perm(__float_as_uint(mv), __float_as_uint(mu), 0x0C0C0400u);     // (U, V, 0, 0)
 }
 
+// 16-bit samples.  Luma: the two horizontal taps are four adjacent bytes at a 2-byte aligned address: two dword reads and one
+// v_alignbyte give [p(x), p(x+1)] as the halves of a dword.  Chroma: a pixel (U, V) is an aligned dword; v_perm pairs the U halves and the
+// V halves of the two taps.  Horizontal lerp: v_dot2_u32_u16 against (32 - fx) | fx << 16 from the weight table; vertical lerp and
+// rounding in integers (vlerp16).  Result: the sample in the low half (luma) / (U, V) as the halves (chroma).
 template <int CN>
-__device__ __forceinline__ void plane_store4(uint8_t* dq, const uint32_t (&res)[4]) {       // four pixels = 4 / 8 / 16 aligned bytes
+__device__ __forceinline__ uint32_t plane_blend_px16(const uint8_t* tl, const uint8_t* lut, int SX, int SY) {
+    typedef PlaneCfg<CN, 2> P;
+    const int addr = __mul24(SY >> 10, P::PB) + (SX >> 10) * P::PXB;
+    const uint32_t* tp = reinterpret_cast<const uint32_t*>(tl + (addr & ~3));
+    const uint32_t wx = *reinterpret_cast<const uint32_t*>(lut + 16 + (SX & 0x3E0));   // (32 - fx) | fx << 16
+    const uint32_t fy = ((uint32_t)SY >> 5) & 31u;
     if (CN == 1) {
+        const uint32_t top = __builtin_amdgcn_alignbyte(tp[1], tp[0], (uint32_t)addr), bot = __builtin_amdgcn_alignbyte(tp[P::PB / 4 + 1], tp[P::PB / 4], (uint32_t)addr);
+        return vlerp16(hlerp16(top, wx), hlerp16(bot, wx), fy);
+    }
+    const uint32_t p00 = tp[0], p01 = tp[1], p10 = tp[P::PB / 4], p11 = tp[P::PB / 4 + 1];
+    const uint32_t u = vlerp16(hlerp16(__builtin_amdgcn_perm(p01, p00, 0x05040100u), wx), hlerp16(__builtin_amdgcn_perm(p11, p10, 0x05040100u), wx), fy);
+    const uint32_t v = vlerp16(hlerp16(__builtin_amdgcn_perm(p01, p00, 0x07060302u), wx), hlerp16(__builtin_amdgcn_perm(p11, p10, 0x07060302u), wx), fy);
+    return u | (v << 16);
+}
+
+template <int CN, int SB = 1>
+__device__ __forceinline__ void plane_store4(uint8_t* dq, const uint32_t (&res)[4]) {       // four pixels = 4 / 8 / 16 aligned bytes
+    if (SB == 2) {
+        if (CN == 1) {
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+            __builtin_nontemporal_store(u32x2{res[0] | (res[1] << 16), res[2] | (res[3] << 16)}, reinterpret_cast<u32x2*>(dq));
+        } else {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            __builtin_nontemporal_store(u32x4{res[0], res[1], res[2], res[3]}, reinterpret_cast<u32x4*>(dq));
+        }
+    } else if (CN == 1) {
         const uint32_t lo = __builtin_amdgcn_perm(res[1], res[0], 0x0C0C0400u), hi = __builtin_amdgcn_perm(res[3], res[2], 0x0C0C0400u);   // low bytes
         __builtin_nontemporal_store(__builtin_amdgcn_perm(hi, lo, 0x05040100u), reinterpret_cast<uint32_t*>(dq));
     } else if (CN == 4) {
@@ -996,22 +1112,28 @@ __device__ __forceinline__ void plane_store4(uint8_t* dq, const uint32_t (&res)[
     }
 }
 
-template <int CN>
+template <int CN, int SB>
+__device__ __forceinline__ uint32_t plane_px(const uint8_t* tl, const uint8_t* lut, int SX, int SY) {
+    if constexpr (SB == 2) return plane_blend_px16<CN>(tl, lut, SX, SY);
+    else return plane_blend_px<CN>(tl, lut, SX, SY);
+}
+
+template <int CN, int SB = 1>
 __device__ __forceinline__ void plane_blend_rows(const WarpCore& c, const uint8_t* tl, const uint8_t* lut, const int2* s_row,
                                                  const int (&ad)[4], const int (&bd)[4], int L, int ty, uint8_t* dst, uint32_t dstride,
                                                  int x0, int y0, int x1, int y1) {
-    typedef PlaneCfg<CN> P;
+    typedef PlaneCfg<CN, SB> P;
     constexpr int NR = P::THP / TYN;
-    uint8_t* const dtile = dst + (size_t)y0 * dstride + (size_t)x0 * CN;      // wave-uniform base, 32-bit lane offsets
+    uint8_t* const dtile = dst + (size_t)y0 * dstride + (size_t)x0 * P::PXB;      // wave-uniform base, 32-bit lane offsets
     if (c.dst_aligned && x1 - x0 == TW - 1 && y1 - y0 == P::THP - 1) {         // (tile-uniform)
-        const uint32_t voff = __umul24((uint32_t)ty, dstride) + (uint32_t)(4 * CN) * L;
+        const uint32_t voff = __umul24((uint32_t)ty, dstride) + (uint32_t)(4 * P::PXB) * L;
 #pragma unroll
         for (int r = 0; r < NR; r++) {
             const int2 XY = s_row[ty + TYN * r];
             uint32_t res[4];
 #pragma unroll
-            for (int i = 0; i < 4; i++) res[i] = plane_blend_px<CN>(tl, lut, XY.x + ad[i], XY.y + bd[i]);
-            plane_store4<CN>(dtile + (size_t)(TYN * r) * dstride + voff, res);
+            for (int i = 0; i < 4; i++) res[i] = plane_px<CN, SB>(tl, lut, XY.x + ad[i], XY.y + bd[i]);
+            plane_store4<CN, SB>(dtile + (size_t)(TYN * r) * dstride + voff, res);
         }
         return;
     }
@@ -1022,14 +1144,17 @@ __device__ __forceinline__ void plane_blend_rows(const WarpCore& c, const uint8_
         const int X0 = XY.x, Y0 = XY.y;
         uint32_t res[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) res[i] = plane_blend_px<CN>(tl, lut, X0 + ad[i], Y0 + bd[i]);
+        for (int i = 0; i < 4; i++) res[i] = plane_px<CN, SB>(tl, lut, X0 + ad[i], Y0 + bd[i]);
         const int y = y0 + yl;
         if (y > y1 || x > x1) continue;
-        uint8_t* dp = dst + (size_t)y * c.dstride + (size_t)x * CN;
-        if (c.dst_aligned && x + 3 <= x1) { plane_store4<CN>(dp, res); continue; }
+        uint8_t* dp = dst + (size_t)y * c.dstride + (size_t)x * P::PXB;
+        if (c.dst_aligned && x + 3 <= x1) { plane_store4<CN, SB>(dp, res); continue; }
         for (int i = 0; i < 4; i++) {
             if (x + i > x1) break;
-            for (int k = 0; k < CN; k++) dp[i * CN + k] = (uint8_t)(res[i] >> (8 * k));     // (one channel: the low byte of the float's bits)
+            for (int k = 0; k < CN; k++) {
+                if (SB == 2) reinterpret_cast<uint16_t*>(dp)[i * CN + k] = (uint16_t)(res[i] >> (16 * k));
+                else dp[i * CN + k] = (uint8_t)(res[i] >> (8 * k));     // (one channel: the low byte of the float's bits)
+            }
         }
     }
 }
@@ -1037,10 +1162,10 @@ __device__ __forceinline__ void plane_blend_rows(const WarpCore& c, const uint8_
 // A plane tile whose source box does not fit the staging area (large rotations, zooms, saturated coordinates, BORDER_REPLICATE): the
 // general path without staging (emit_rows works on 16 rows, terms as arrays: they go where the box would be).  Not inlined: as
 // part of the kernel body it costs the common path its eighth wave per SIMD or register spills.
-template <int CN>
+template <int CN, int SB = 1>
 __device__ __attribute__((noinline)) void plane_direct_tile(WarpCore c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
                                                             int bx0a, int by0, int bw, int tid) {
-    typedef PlaneCfg<CN> P;
+    typedef PlaneCfg<CN, SB> P;
     if (tid < TW) {           // ad[128] bd[128] x0[THP] y0[THP]
         const int cx = min(x0 + tid, x1);
         s_tab[tid] = Tg[cx]; s_tab[TW + tid] = Tg[c.dw + cx];
@@ -1050,7 +1175,7 @@ __device__ __attribute__((noinline)) void plane_direct_tile(WarpCore c, const ui
     }
     __syncthreads();
     for (int j = 0; y0 + TH * j <= y1; j++)
-        emit_rows<CN, false>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW + TH * j, s_tab + 2 * TW + P::THP + TH * j, x0, y0 + TH * j, x1,
+        emit_rows<CN, false, SB>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW + TH * j, s_tab + 2 * TW + P::THP + TH * j, x0, y0 + TH * j, x1,
                              min(y0 + TH * j + TH - 1, y1), bx0a, by0, bw, tid);
 }
 
@@ -1074,10 +1199,11 @@ __device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint
 // per-row terms).  tile / lut / s_row: the workgroup's LDS.
 // BORDER: what the staged box holds where it leaves the picture - zeros (cv::warpAffine BORDER_CONSTANT: the stabilizer's warp) or the
 // nearest picture pixel (BORDER_REPLICATE: the roll stage's rotation); a launch whose border is the other one takes the direct path.
-template <int CN, int BORDER = VS_BORDER_BLACK>
+template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1>
 __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
                                            uint8_t* tile, uint8_t* lut, int2* s_row, int tid) {
-    typedef PlaneCfg<CN> P;
+    typedef PlaneCfg<CN, SB> P;
+    static_assert(SB == 1 || (SB == 2 && CN <= 2 && BORDER == VS_BORDER_BLACK), "16-bit planes: one or two channels, constant border");
     typedef __attribute__((address_space(1))) uint8_t* gptr;
     const int L = tid & 31, ty = tid >> 5;
     int ad[4], bd[4];
@@ -1125,7 +1251,7 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
         // ---- staging: chunks of 16 bytes, (row, chunk) = (i / CPR, i % CPR); all loads of a lane first, then its stores
         constexpr int NCH = (P::ROWS * P::CPR + NT - 1) / NT;
         const int total = bh * P::CPR;
-        const long long rowbytes = (long long)c.sw * CN;
+        const long long rowbytes = (long long)c.sw * P::PXB;
         uint4 d[NCH];
 #pragma unroll
         for (int k = 0; k < NCH; k++) {
@@ -1134,8 +1260,8 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
             if (i < total) {
                 const int r = i / P::CPR, ch = i - r * P::CPR;
                 const int y = by0 + r;
-                const long long xb = (long long)bx0a * CN + 16 * ch;          // byte column of the chunk in the source row
-                if (BORDER == VS_BORDER_REPLICATE) {
+                const long long xb = (long long)bx0a * P::PXB + 16 * ch;      // byte column of the chunk in the source row
+                if constexpr (BORDER == VS_BORDER_REPLICATE) {
                     const uint8_t* row = src + (size_t)min(max(y, 0), c.sh - 1) * c.sstride;
                     if (xb >= 0 && xb + 16 <= rowbytes && c.src_aligned) d[k] = *reinterpret_cast<const uint4*>(row + xb);
                     else d[k] = load_chunk_replicate<CN>(row, (int)max(min(xb, (long long)rowbytes + 64), -64ll), c.sw);
@@ -1181,12 +1307,12 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
     }
     if (!fit) {
         if constexpr (CN == 4) plane_direct_tile4(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
-        else plane_direct_tile<CN>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        else plane_direct_tile<CN, SB>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
         return;
     }
     __syncthreads();
     // ---- output
-    plane_blend_rows<CN>(c, tile, lut, s_row, ad, bd, L, ty, dst, (uint32_t)c.dstride, x0, y0, x1, y1);
+    plane_blend_rows<CN, SB>(c, tile, lut, s_row, ad, bd, L, ty, dst, (uint32_t)c.dstride, x0, y0, x1, y1);
 }
 
 template <int CN>
@@ -1214,11 +1340,12 @@ __global__ __launch_bounds__(NT, 8) void warp_plane_kernel(gtab_t tabs, int tab_
 // c-th contiguous eighth).  A frame's tables lie in one block (warp_tab.h): luma table, then chroma table, `tab_stride` ints from
 // frame to frame.  The chroma plane's geometry is the luma plane's halved (surfaces share one pitch); flags as in the plane
 // kernels plus the frame count in bits 16...  mtpf = ceil(2^32 / tiles per frame), mgx1 / mgx2 likewise for the tile columns.
-template <int BORDER>
+// SB = 2: P010 surfaces - the same sequence, grid order, table blocks and prologue; planes of 16-bit samples (PlaneCfg<CN, 2>).
+template <int BORDER, int SB = 1>
 __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t swh, uint32_t dwh,
                                                        uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2) {
-    typedef PlaneCfg<1> P1;
-    typedef PlaneCfg<2> P2;
+    typedef PlaneCfg<1, SB> P1;
+    typedef PlaneCfg<2, SB> P2;
     constexpr int TILE_BYTES = P1::ROWS * P1::PB > P2::ROWS * P2::PB ? P1::ROWS * P1::PB : P2::ROWS * P2::PB;
     __shared__ __attribute__((aligned(16))) uint8_t tile[TILE_BYTES];
     __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
@@ -1244,7 +1371,7 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
     if (t < n1) {
         const TabLayout L = tab_layout(c.dw, c.dh);
         const uint32_t row = gx1 == 1 ? t : __umulhi(t, mgx1);
-        plane_tile<1, BORDER>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx1), (int)row, tile, lut, s_row, threadIdx.x);
+        plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx1), (int)row, tile, lut, s_row, threadIdx.x);
     } else {
         t -= n1;
         T += tab_layout(c.dw, c.dh).stride;
@@ -1252,7 +1379,7 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
         c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
         const TabLayout L = tab_layout(c.dw, c.dh);
         const uint32_t row = gx2 == 1 ? t : __umulhi(t, mgx2);
-        plane_tile<2, BORDER>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx2), (int)row, tile, lut, s_row, threadIdx.x);
+        plane_tile<2, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx2), (int)row, tile, lut, s_row, threadIdx.x);
     }
 }
 
@@ -1262,11 +1389,20 @@ inline int tab_stride_of(int dw, int dh) { return tab_layout(dw, dh).stride; }
 // what: VS_WARP_ALL = tables (when d_tabs is given) and warp; VS_WARP_TABLES_ONLY / VS_WARP_ONLY = the two halves apart, so
 // that a caller whose maps are ready long before it warps (the batch tail of the stabilizer) builds the tables then.
 // tab_stride: ints from one frame's table to the next (0: the tables are packed; NV12 blocks hold two planes' tables per frame)
+// sb = 2: a plane of 16-bit samples (cn = 1 or 2).  Its tables are built like any plane's (they are in pixels); the warp itself
+// is the general 16-bit kernel, which takes its terms from the maps.
 template <int CN>
-void launch_one(WarpArgs& a, dim3 grid, int32_t* d_tabs, int what, hipStream_t st, int tab_stride) {
+void launch_one(WarpArgs& a, dim3 grid, int32_t* d_tabs, int what, hipStream_t st, int tab_stride, int sb) {
     a.tabs = d_tabs;
     const TabLayout tl = tab_layout(a.c.dw, a.c.dh);
     a.tab_stride = tab_stride > 0 ? tab_stride : tl.stride; a.tab_row = tl.row; a.tab_ad = tl.ad;
+    if (sb == 2) {
+        if (d_tabs && what != VS_WARP_ONLY)
+            hipLaunchKernelGGL(warp_tables_kernel, dim3((a.c.dw + a.c.dh + grid.x + grid.y + NT - 1) / NT, grid.z), dim3(NT), 0, st, a);
+        if (d_tabs && what == VS_WARP_TABLES_ONLY) return;
+        if constexpr (CN <= 2) hipLaunchKernelGGL((warp_affine16_kernel<CN>), grid, dim3(NT), 0, st, a);
+        return;
+    }
     if (d_tabs) {
         if (what != VS_WARP_ONLY)
             hipLaunchKernelGGL(warp_tables_kernel, dim3((a.c.dw + a.c.dh + grid.x + grid.y + NT - 1) / NT, grid.z), dim3(NT), 0, st, a);
@@ -1301,18 +1437,27 @@ void launch_one(WarpArgs& a, dim3 grid, int32_t* d_tabs, int what, hipStream_t s
     }
 }
 
-void launch_cn(WarpArgs& a, dim3 grid, int cn, int32_t* d_tabs, hipStream_t st, int what = VS_WARP_ALL, int tab_stride = 0) {
-    if (cn == 3) launch_one<3>(a, grid, d_tabs, what, st, tab_stride);
-    else if (cn == 4) launch_one<4>(a, grid, d_tabs, what, st, tab_stride);
-    else if (cn == 1) launch_one<1>(a, grid, d_tabs, what, st, tab_stride);
-    else launch_one<2>(a, grid, d_tabs, what, st, tab_stride);
+void launch_cn(WarpArgs& a, dim3 grid, int cn, int32_t* d_tabs, hipStream_t st, int what = VS_WARP_ALL, int tab_stride = 0, int sb = 1) {
+    if (cn == 3) launch_one<3>(a, grid, d_tabs, what, st, tab_stride, sb);
+    else if (cn == 4) launch_one<4>(a, grid, d_tabs, what, st, tab_stride, sb);
+    else if (cn == 1) launch_one<1>(a, grid, d_tabs, what, st, tab_stride, sb);
+    else launch_one<2>(a, grid, d_tabs, what, st, tab_stride, sb);
 }
 
+// (cn: the bytes of a pixel - channels x bytes per sample)
 bool bad_args(const void* d_src, const void* d_dst, const void* M, size_t sstride, int sw, int sh, size_t dstride,
               int dw, int dh, int cn, int batch) {
     return !d_src || !d_dst || !M || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || batch <= 0 ||
            (cn < 1 || cn > 4) || sstride < (size_t)sw * cn || dstride < (size_t)dw * cn ||
            dh > 65535 * TH;
+}
+
+// 16-bit samples sit on even addresses: pointers, pitches (and with them the plane offsets).
+bool odd16(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, size_t dstride) {
+    if ((sstride | dstride) & 1) return true;
+    for (int i = 0; i < n; i++)
+        if (((uintptr_t)srcs[i] | (uintptr_t)dsts[i]) & 1) return true;
+    return false;
 }
 
 // Validation shared by the two launchers: the border, the table choice, and no null frame in the lists.
@@ -1356,13 +1501,13 @@ WarpMaps maps_from(WarpMaps m, int k) { m.m += (size_t)m.stride * k; return m; }
 
 // ONE launch over n <= MAXB frames of one plane.  d_tabs: the launch's tables (tab_stride ints apart, 0 = packed), or nullptr.
 int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw, int dh,
-                 int cn, WarpMaps maps, int border, int32_t* d_tabs, int tab_stride, int what, hipStream_t st) {
+                 int cn, WarpMaps maps, int border, int32_t* d_tabs, int tab_stride, int what, hipStream_t st, int sb = 1) {
     WarpArgs a;
     a.c.sstride = sstride; a.c.dstride = dstride;
     a.c.sw = sw; a.c.sh = sh; a.c.dw = dw; a.c.dh = dh;
     a.c.border = border;
-    const int galign = cn == 2 ? 8 : 4;
-    const int dalign = cn == 4 ? 16 : galign;      // (four channels: a lane's four pixels are one aligned 16-byte store)
+    const int galign = cn * sb == 2 ? 8 : 4;
+    const int dalign = cn * sb == 4 ? 16 : sb == 2 ? 8 : galign;      // (four bytes per pixel: a lane's four pixels are one aligned 16-byte store)
     a.c.src_aligned = sstride % galign == 0;
     a.c.dst_aligned = dstride % dalign == 0;
     for (int i = 0; i < MAXB; i++) {
@@ -1375,7 +1520,7 @@ int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t
     for (int b = 0; b < MAXB; b++)
         for (int i = 0; i < 6; i++) a.Minv_val[6 * b + i] = maps.host && b < n ? maps.m[(size_t)maps.stride * b + i] : 0.;
     dim3 grid((dw + TW - 1) / TW, (dh + TH - 1) / TH, n);
-    launch_cn(a, grid, cn, d_tabs, st, what, tab_stride);
+    launch_cn(a, grid, cn, d_tabs, st, what, tab_stride, sb);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }
@@ -1384,28 +1529,34 @@ int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t
 // (warp_tab.h: luma table, then chroma table; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  The chroma planes lie src_uv /
 // dst_uv bytes behind the luma planes.  Returns VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstride, size_t dstride, int w, int h, size_t src_uv,
-                size_t dst_uv, const int32_t* d_tabs, int border, hipStream_t st) {
-    typedef PlaneCfg<1> P1;
-    typedef PlaneCfg<2> P2;
-    const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + P1::THP - 1) / P1::THP, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + P2::THP - 1) / P2::THP;
+                size_t dst_uv, const int32_t* d_tabs, int border, hipStream_t st, int sb = 1) {
+    // (sb = 2, P010: tiles of half the rows; no BORDER_REPLICATE instance - no caller rotates P010 surfaces)
+    if (sb == 2 && border != VS_BORDER_BLACK) return VS_ERR_UNSUPPORTED;
+    const int thp1 = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP, thp2 = sb == 2 ? PlaneCfg<2, 2>::THP : PlaneCfg<2>::THP;
+    const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp1 - 1) / thp1, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + thp2 - 1) / thp2;
     const unsigned long long tpf = gx1 * gy1 + gx2 * gy2, total = tpf * (unsigned long long)n;
     if (w >= 65536 || h >= 65536 || sstride >= (1ull << 24) || dstride >= (1ull << 24) || n >= 65536 || total * std::max(tpf, std::max(gx1, gx2)) >= (1ull << 31))
         return VS_ERR_UNSUPPORTED;
     uint32_t al = 0xFu;          // bit 0 / 1: luma source / destination 4-byte aligned; bit 2 / 3: chroma 8-byte aligned
-    if (sstride % 4) al &= ~1u;
-    if (dstride % 4) al &= ~2u;
-    if (sstride % 8 || src_uv % 8) al &= ~4u;
-    if (dstride % 8 || dst_uv % 8) al &= ~8u;
+    // (P010: a lane's four pixels are 8 bytes of luma, 16 of chroma; the staging loads ask for 4-byte alignment on either plane)
+    const size_t a_ys = 4, a_yd = sb == 2 ? 8 : 4, a_us = sb == 2 ? 4 : 8, a_ud = sb == 2 ? 16 : 8;
+    if (sstride % a_ys) al &= ~1u;
+    if (dstride % a_yd) al &= ~2u;
+    if (sstride % a_us || src_uv % a_us) al &= ~4u;
+    if (dstride % a_ud || dst_uv % a_ud) al &= ~8u;
     for (int i = 0; i < n; i++) {
-        if ((uintptr_t)ys[i] % 4) al &= ~1u;
-        if ((uintptr_t)yd[i] % 4) al &= ~2u;
-        if ((uintptr_t)ys[i] % 8) al &= ~4u;
-        if ((uintptr_t)yd[i] % 8) al &= ~8u;
+        if ((uintptr_t)ys[i] % a_ys) al &= ~1u;
+        if ((uintptr_t)yd[i] % a_yd) al &= ~2u;
+        if ((uintptr_t)ys[i] % a_us) al &= ~4u;
+        if ((uintptr_t)yd[i] % a_ud) al &= ~8u;
     }
     const uint32_t flags = (al & 1u) | (al & 2u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    if (border == VS_BORDER_REPLICATE)
+    if (sb == 2)
+        hipLaunchKernelGGL((warp_nv12_kernel<VS_BORDER_BLACK, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
+                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
+    else if (border == VS_BORDER_REPLICATE)
         hipLaunchKernelGGL(warp_nv12_kernel<VS_BORDER_REPLICATE>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
                            (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
     else
@@ -1445,21 +1596,28 @@ int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, s
 // ONE grid; plane by plane when the launch has no tables, when the chroma planes do not all lie one offset behind the luma planes
 // (the one-launch kernel and the table launch take one offset), or when the geometry is outside what the one-launch kernel packs.
 int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t* const* us, uint8_t* const* ud, int n, size_t sstride,
-                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st) {
-    if (n < 1 || !ys || !yd || !us || !ud || w < 2 || h < 2 || (w & 1) || (h & 1) ||
-        bad_args(ys[0], yd[0], maps.m, sstride, w, h, dstride, w, h, 1, n) || bad_call(ys, yd, n, border, tabs) ||
+                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sb) {
+    if (n < 1 || !ys || !yd || !us || !ud || w < 2 || h < 2 || (w & 1) || (h & 1) || (sb != 1 && sb != 2) ||
+        bad_args(ys[0], yd[0], maps.m, sstride, w, h, dstride, w, h, sb, n) || bad_call(ys, yd, n, border, tabs) ||
         bad_call(us, ud, n, border, tabs)) {
-        set_last_error("warp_nv12: invalid argument (w and h must be even)");
+        set_last_error(sb == 2 ? "warp_p010: invalid argument (w and h must be even)" : "warp_nv12: invalid argument (w and h must be even)");
         return VS_ERR_INVALID_ARG;
     }
+    if (sb == 2 && (odd16(ys, yd, n, sstride, dstride) || odd16(us, ud, n, sstride, dstride))) {
+        set_last_error("warp_p010: P010 pointers, pitches and plane offsets must be even");
+        return VS_ERR_INVALID_ARG;
+    }
+    // (P010 with the scratch tables: every launch builds them - one kernel serves single surfaces and batches alike.  A caller's
+    // tables exist for launches of WARP_TAB_MIN frames and more only, whatever the format.)
+    const int tab_min = sb == 2 && tabs.kind == WarpTabs::SCRATCH ? 1 : WARP_TAB_MIN;
     const int block = nv12_tab_ints(w, h), sy = tab_layout(w, h).stride;
-    if (tabs.kind == WarpTabs::SCRATCH && n >= WARP_TAB_MIN)
+    if (tabs.kind == WarpTabs::SCRATCH && n >= tab_min)
         VS_TRY(op_tabs(st, (size_t)block * std::min(n, MAXB) * sizeof(int32_t), &tabs.tabs));
     const WarpMaps muv = {maps.m + 6, maps.stride, maps.host};
     const size_t tab_step = tabs.kind == WarpTabs::CALLER ? block : 0;
     for (int b0 = 0; b0 < n; b0 += MAXB) {
         const int nb = std::min(MAXB, n - b0);
-        int32_t* T = tabs.kind != WarpTabs::NONE && nb >= WARP_TAB_MIN ? tabs.tabs + b0 * tab_step : nullptr;
+        int32_t* T = tabs.kind != WarpTabs::NONE && nb >= tab_min ? tabs.tabs + b0 * tab_step : nullptr;
         if (!T && tabs.what == VS_WARP_TABLES_ONLY) continue;
         const WarpMaps my = maps_from(maps, b0), mu = maps_from(muv, b0);
         const size_t src_uv = (uintptr_t)us[b0] - (uintptr_t)ys[b0], dst_uv = (uintptr_t)ud[b0] - (uintptr_t)yd[b0];
@@ -1467,7 +1625,7 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
         for (int i = b0; i < b0 + nb; i++)
             one_uv &= (uintptr_t)us[i] - (uintptr_t)ys[i] == src_uv && (uintptr_t)ud[i] - (uintptr_t)yd[i] == dst_uv;
         if (T && tabs.what != VS_WARP_ONLY) {
-            if (maps.host && nb <= NVT_MAX && one_uv) {
+            if (maps.host && nb <= NVT_MAX && one_uv) {      // (the tables are in pixels: the same for either sample size)
                 NvTabArgs t;
                 t.tabs = T; t.block = block; t.chroma = sy; t.w = w; t.h = h; t.src_uv = src_uv; t.dst_uv = dst_uv;
                 for (int i = 0; i < NVT_MAX; i++) { t.ys[i] = ys[b0 + (i < nb ? i : 0)]; t.yd[i] = yd[b0 + (i < nb ? i : 0)]; }
@@ -1478,20 +1636,20 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
                 const int entries = w + h + (w + TW - 1) / TW + (h + TH - 1) / TH;
                 hipLaunchKernelGGL(warp_tables_nv12_kernel, dim3((entries + NT - 1) / NT, nb, 2), dim3(NT), 0, st, t);
             } else {
-                VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, VS_WARP_TABLES_ONLY, st));
+                VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, VS_WARP_TABLES_ONLY, st, sb));
                 VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T + sy, block,
-                                    VS_WARP_TABLES_ONLY, st));
+                                    VS_WARP_TABLES_ONLY, st, sb));
             }
         }
         if (tabs.what == VS_WARP_TABLES_ONLY) continue;
-        const int one = T && one_uv ? nv12_launch(ys + b0, yd + b0, nb, sstride, dstride, w, h, src_uv, dst_uv, T, border, st) : VS_ERR_UNSUPPORTED;
+        const int one = T && one_uv ? nv12_launch(ys + b0, yd + b0, nb, sstride, dstride, w, h, src_uv, dst_uv, T, border, st, sb) : VS_ERR_UNSUPPORTED;
         if (one != VS_ERR_UNSUPPORTED) {
             VS_TRY(one);
             continue;
         }
         const int what = T ? VS_WARP_ONLY : VS_WARP_ALL;
-        VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, what, st));
-        VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T ? T + sy : nullptr, block, what, st));
+        VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, what, st, sb));
+        VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T ? T + sy : nullptr, block, what, st, sb));
     }
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;

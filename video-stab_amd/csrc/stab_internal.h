@@ -60,7 +60,7 @@ struct vs_stab {
     int w = 0, h = 0, fmt = VS_FMT_BGR8, cn = 3;
     size_t row_bytes = 0, frame_bytes = 0;
     size_t src_pitch = 0;               // row pitch of the frames the pipeline reads: row_bytes (queue ring) or the caller's (zero-copy)
-    size_t in_uv_off = 0, out_uv_off = 0;   // NV12 surfaces of the device entry points: UV plane offset, 0 = h * pitch
+    size_t in_uv_off = 0, out_uv_off = 0;   // NV12 / P010 surfaces of the device entry points: UV plane offset in bytes, 0 = h * pitch
     int rows_total = 0;
     int aw = 960, ah = 540;
     int levels = 0;                 // max pyramid level actually used
@@ -251,7 +251,13 @@ inline void fill_lk_levels(const vs_stab* s, int pv, int c, LKLevel* L) {
     }
 }
 
-// NV12: where the interleaved UV plane of a queued frame / of an output surface starts
+// The two questions the host asks of a frame format beyond its first plane's bytes per pixel (s->cn): does an interleaved chroma
+// plane of half the rows follow the luma plane (NV12, P010), and how many bytes is a sample (2: P010).
+inline bool fmt_two_planes(int fmt) { return fmt == VS_FMT_NV12 || fmt == VS_FMT_P010; }
+inline int fmt_sample_bytes(int fmt) { return fmt == VS_FMT_P010 ? 2 : 1; }
+inline int fmt_rows(int fmt, int h) { return fmt_two_planes(fmt) ? h * 3 / 2 : h; }     // rows of `pitch` bytes of a whole frame
+
+// NV12 / P010: where the interleaved UV plane of a queued frame / of an output surface starts
 inline size_t src_uv(const vs_stab* s) { return (s->zero_copy && s->in_uv_off) ? s->in_uv_off : (size_t)s->h * s->src_pitch; }
 inline size_t dst_uv(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
     return (d_out != s->d_out && s->out_uv_off) ? s->out_uv_off : (size_t)s->h * out_stride;   // s->d_out: staging of the host entry points

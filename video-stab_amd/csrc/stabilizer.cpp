@@ -40,12 +40,13 @@ using namespace vsd;
 
 namespace {
 
-// Bytes per pixel of a frame format's first plane (NV12 / GRAY8: the luma bytes); 0 for an unknown format.
+// Bytes per pixel of a frame format's first plane (NV12 / GRAY8: the luma byte; P010: the 16-bit luma sample); 0 for an unknown format.
 int fmt_cn(int fmt) {
     switch (fmt) {
         case VS_FMT_BGR8: case VS_FMT_RGB8: return 3;
         case VS_FMT_BGRA8: case VS_FMT_RGBA8: return 4;
         case VS_FMT_NV12: case VS_FMT_GRAY8: return 1;
+        case VS_FMT_P010: return 2;
         default: return 0;
     }
 }
@@ -121,14 +122,15 @@ int allocate(vs_stab* s, int w, int h, int fmt) {
 int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     s->w = w; s->h = h; s->fmt = fmt;
     s->cn = fmt_cn(fmt);
-    s->rows_total = fmt == VS_FMT_NV12 ? h * 3 / 2 : h;
+    s->rows_total = fmt_rows(fmt, h);
     s->row_bytes = (size_t)w * s->cn;
     s->frame_bytes = s->row_bytes * s->rows_total;
     s->src_pitch = s->row_bytes;
     analysis_size(s, w, h, &s->aw, &s->ah);
     if (s->aw < 3 || s->ah < 3) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "analysis size too small");
     // (the reference's cvtColor(BGR2GRAY) of the canvas, Stabilizer.cpp:2225, throws on anything but three channels)
-    if (canvas_on(s) && fmt != VS_FMT_BGR8) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "enableVirtualCanvas needs a BGR8 stream");
+    if (canvas_on(s) && fmt != VS_FMT_BGR8)
+        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, fmt == VS_FMT_P010 ? "enableVirtualCanvas needs a BGR8 stream (not P010)" : "enableVirtualCanvas needs a BGR8 stream");
     // buildOpticalFlowPyramid: levels that fit the window
     {
         int sw = s->aw, sh = s->ah;
@@ -224,7 +226,7 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     VS_OBJ_TRY(s, get_ransac_tables(ncap, s->p.ransac_max_iters, &s->tab));
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
-    s->out_bytes = (size_t)ow * s->cn * (fmt == VS_FMT_NV12 ? oh * 3 / 2 : oh);
+    s->out_bytes = (size_t)ow * s->cn * fmt_rows(fmt, oh);
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_out, s->out_bytes));
     s->tmp_bytes = std::max(s->out_bytes, s->frame_bytes);
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
@@ -277,7 +279,7 @@ int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMem
     if (s->slot_valid[slot]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_slot[slot], 0));
     StageScope t(s, VS_STAGE_COPY_IN, s->st_pre);
     uint8_t* dst = s->d_ring + (size_t)slot * s->frame_bytes;
-    if (s->fmt == VS_FMT_NV12 && kind == hipMemcpyDeviceToDevice && s->in_uv_off) {      // decoder surface: planes apart
+    if (fmt_two_planes(s->fmt) && kind == hipMemcpyDeviceToDevice && s->in_uv_off) {      // decoder surface: planes apart
         VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->h, kind, s->st_pre));
         VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + (size_t)s->h * s->row_bytes, s->row_bytes, (const uint8_t*)src + s->in_uv_off, stride,
                                   s->row_bytes, s->h / 2, kind, s->st_pre));
@@ -438,7 +440,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
     int ow, oh;
     out_size(s, s->w, s->h, &ow, &oh);
     s->last_out_w = ow; s->last_out_h = oh;
-    const bool plain = idx < s->n_transforms && s->fmt != VS_FMT_NV12 && p.border_size <= 0 && !canvas_on(s);
+    const bool plain = idx < s->n_transforms && !fmt_two_planes(s->fmt) && p.border_size <= 0 && !canvas_on(s);
     const BorderPlan bp = border_plan(s);
     if (may_defer && plain && s->warp_batch > 1) {
         VS_OBJ_TRY(s, defer_output(s, idx, frame, d_out, out_stride, slot));
@@ -457,7 +459,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         if (ow != s->w || oh != s->h)
             VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
         VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
-        if (s->fmt == VS_FMT_NV12)
+        if (fmt_two_planes(s->fmt))
             VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out + dst_uv(s, d_out, out_stride), out_stride, frame + src_uv(s), s->src_pitch, s->row_bytes,
                                       s->h / 2, hipMemcpyDeviceToDevice, st));
         s->last_out_w = s->w; s->last_out_h = s->h;
@@ -466,12 +468,13 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         if (!s->canvas && !(s->canvas = canvas_new())) return vs_obj_fail(s, VS_ERR_HIP, "out of host memory");
         StageScope t(s, VS_STAGE_WARP, st);
         rc = canvas_apply(s->canvas, p, frame, s->src_pitch, s->w, s->h, s->d_ct, s->d_traj, d_out, out_stride, st);
-    } else if (s->fmt == VS_FMT_NV12) {
+    } else if (fmt_two_planes(s->fmt)) {
         StageScope t(s, VS_STAGE_WARP, st);
         const uint8_t* uv = frame + src_uv(s);
         uint8_t* out_uv = d_out + dst_uv(s, d_out, out_stride);
+        // (a P010 surface goes through the one-launch kernel even on its own: its tables are built in the stream's scratch)
         rc = launch_warp_nv12(&frame, &d_out, &uv, &out_uv, 1, s->src_pitch, out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
-                              VS_BORDER_BLACK, WarpTabs{}, st);
+                              VS_BORDER_BLACK, s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, fmt_sample_bytes(s->fmt));
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
         const size_t prow = bp.prow, nb = prow * bh;
@@ -659,7 +662,12 @@ int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
     const int cn = fmt_cn(fmt);
     if (w <= 0 || h <= 0 || cn == 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: bad geometry/format");
     if (fmt == VS_FMT_NV12 && ((w & 1) || (h & 1))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "NV12 needs even w,h");
-    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8)
+    if (fmt == VS_FMT_P010 && ((w & 1) || (h & 1))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even w,h");
+    if (fmt == VS_FMT_P010 && ((stride | s->in_uv_off | s->out_uv_off) & 1))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even pitches and plane offsets (16-bit samples)");
+    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8 / P010)
+    if (fmt == VS_FMT_P010 && s->p.border_size > 0)
+        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not P010");
     if (cn == 1 && s->p.border_size > 0) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need a colour format (BGR8, BGRA8, RGBA8, RGB8)");
     if (stride < (size_t)w * cn) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: stride < row bytes");
     VS_OBJ_HIP(s, hipSetDevice(s->device));
@@ -816,6 +824,8 @@ int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride
     if (!d_data) return VS_OK;   // empty frame -> empty result (Stabilizer.cpp:263-265)
     int rc = prepare(s, w, h, fmt, stride);
     if (rc != VS_OK) return rc;
+    if (fmt == VS_FMT_P010 && (((uintptr_t)d_data | (uintptr_t)d_out | out_stride) & 1))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
     if (s->zero_copy) {
         // the frame is read where it is: it must stay valid and unchanged until its own result has been produced
         // one pitch for all frames in flight (the batched launches take it once): it may change when nothing is queued
@@ -852,6 +862,8 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
     if (!s || !produced) return VS_ERR_INVALID_ARG;
     *produced = 0;
     if (!s->allocated || s->q_slot.empty()) return VS_OK;
+    if (s->fmt == VS_FMT_P010 && (((uintptr_t)d_out | out_stride) & 1))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
@@ -873,7 +885,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
     const size_t orow = (size_t)ow * s->cn;
-    const int orows = fmt == VS_FMT_NV12 ? oh * 3 / 2 : oh;
+    const int orows = fmt_rows(fmt, oh);
     const bool have_prev = s->hold_valid;
     // (as in the synchronous call: the buffer is only looked at when a frame will be delivered into it; a held frame is
     // always a full-size one - pass-through frames only come out of vs_stab_flush's synchronous part)
@@ -947,7 +959,7 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
     if (!data) return VS_OK;
     int rc = prepare(s, w, h, fmt, stride);
     if (rc != VS_OK) return rc;
-    if (s->zero_copy && (s->src_pitch != s->row_bytes || (s->fmt == VS_FMT_NV12 && s->in_uv_off)))
+    if (s->zero_copy && (s->src_pitch != s->row_bytes || (fmt_two_planes(s->fmt) && s->in_uv_off)))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: host frames cannot join a queue of pitched zero-copy surfaces");
     if (s->host_pipe && !s->batch_active) return push_host_pipelined(s, data, w, h, stride, fmt, out, out_stride, produced);
     int ow, oh;
@@ -972,7 +984,7 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
             (void)hipStreamSynchronize(s->st_pre);
             return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
         }
-        const int orows = fmt == VS_FMT_NV12 ? oh * 3 / 2 : oh;
+        const int orows = fmt_rows(fmt, oh);
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));   // (per-frame pipeline: the warp ran on the warp stream)
         if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));     // batch mode: the warps run on `pre` (group_launch_ready)
         VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
@@ -991,7 +1003,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     if (s->hold_valid) {      // host pipeline: the frame the last push computed
         const size_t orow = (size_t)s->hold_w * s->cn;
         if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
-        const int orows = s->fmt == VS_FMT_NV12 ? s->hold_h * 3 / 2 : s->hold_h;
+        const int orows = fmt_rows(s->fmt, s->hold_h);
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
         VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orow, orows, hipMemcpyDeviceToHost, s->st_warp));
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
@@ -1009,7 +1021,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     VS_OBJ_TRY(s, flush_warps(s));
     int rc = flush_dev_impl(s, s->d_out, orow, produced, false);
     if (rc != VS_OK) return rc;
-    const int orows = s->fmt == VS_FMT_NV12 ? oh * 3 / 2 : oh;
+    const int orows = fmt_rows(s->fmt, oh);
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
     if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));         // batch mode: the warps run on `pre`
     VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
@@ -1068,6 +1080,8 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
     if (!s) return VS_ERR_INVALID_ARG;
     if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: the frame queue must be empty");
+    if (s->allocated && s->fmt == VS_FMT_P010 && ((in_uv_offset | out_uv_offset) & 1))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: P010 needs even plane offsets (16-bit samples)");
     s->in_uv_off = in_uv_offset;
     s->out_uv_off = out_uv_offset;
     return VS_OK;

@@ -213,11 +213,18 @@ int vs_op_warp_affine(const void* d_src, size_t src_stride, size_t src_frame_byt
                              VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, (hipStream_t)stream);
 }
 
-int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst, size_t dst_stride,
-                           int w, int h, const float* M, int batch, size_t src_frame_bytes,
-                           size_t dst_frame_bytes, void* stream) {
+// NV12 (sample_bytes 1) and P010 (2) surfaces: one body, strides and frame distances in bytes
+static int warp_affine_two_planes(const void* d_src, size_t src_stride, void* d_dst, size_t dst_stride, int w, int h, const float* M, int batch,
+                                  size_t src_frame_bytes, size_t dst_frame_bytes, void* stream, int sample_bytes) {
     VS_TRY(ensure_device());
-    if (!d_src || !d_dst || !M || batch <= 0) { set_last_error("warp_affine_nv12: invalid argument"); return VS_ERR_INVALID_ARG; }
+    if (!d_src || !d_dst || !M || batch <= 0) {
+        set_last_error(sample_bytes == 2 ? "warp_affine_p010: invalid argument" : "warp_affine_nv12: invalid argument");
+        return VS_ERR_INVALID_ARG;
+    }
+    if (sample_bytes == 2 && ((src_frame_bytes | dst_frame_bytes) & 1)) {
+        set_last_error("warp_affine_p010: frame distances must be even (16-bit samples)");
+        return VS_ERR_INVALID_ARG;
+    }
     // luma: the full matrix; chroma: the half-size two-channel plane, same rotation, translation halved
     std::vector<double> Minv(12 * (size_t)batch);
     for (int b = 0; b < batch; b++) {
@@ -230,7 +237,19 @@ int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst, si
     const auto ys = frame_list((const uint8_t*)d_src, src_frame_bytes, batch), us = frame_list((const uint8_t*)d_src, src_frame_bytes, batch, suv);
     const auto yd = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch), ud = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch, duv);
     return launch_warp_nv12(ys.data(), yd.data(), us.data(), ud.data(), batch, src_stride, dst_stride, w, h, WarpMaps{Minv.data(), 12, true},
-                            VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, (hipStream_t)stream);
+                            VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, (hipStream_t)stream, sample_bytes);
+}
+
+int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst, size_t dst_stride,
+                           int w, int h, const float* M, int batch, size_t src_frame_bytes,
+                           size_t dst_frame_bytes, void* stream) {
+    return warp_affine_two_planes(d_src, src_stride, d_dst, dst_stride, w, h, M, batch, src_frame_bytes, dst_frame_bytes, stream, 1);
+}
+
+int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst, size_t dst_stride,
+                           int w, int h, const float* M, int batch, size_t src_frame_bytes,
+                           size_t dst_frame_bytes, void* stream) {
+    return warp_affine_two_planes(d_src, src_stride, d_dst, dst_stride, w, h, M, batch, src_frame_bytes, dst_frame_bytes, stream, 2);
 }
 
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt, void* d_dst,

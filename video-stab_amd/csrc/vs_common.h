@@ -164,8 +164,10 @@ int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, s
 // NV12 surfaces of w x h (even) luma pixels: luma planes ys -> yd, interleaved chroma planes us -> ud (half size, two channels).
 // Launches with tables warp both planes of their surfaces in ONE grid when the chroma planes lie one offset behind the luma
 // planes; other launches go plane by plane.
+// sample_bytes = 2: P010 surfaces - planes of 16-bit samples, pitches and pointers in bytes and even, VS_BORDER_BLACK; a call with
+// the scratch tables builds them for any number of surfaces.
 int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t* const* us, uint8_t* const* ud, int n, size_t sstride,
-                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st);
+                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sample_bytes = 1);
 // One warp of a multi-job launch (launch_warp_jobs, k_warp.hip): any geometry, inverse map in double on the host.
 struct WarpJob {
     const uint8_t* src;

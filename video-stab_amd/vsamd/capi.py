@@ -21,6 +21,25 @@ FMT_BGR8, FMT_NV12, FMT_GRAY8 = 0, 1, 2
 FMT_BGRA8, FMT_RGBA8, FMT_RGB8 = 3, 4, 5
 # bytes per pixel of a format's (first) plane; a colour format's frames are (h, w, channels) arrays
 FMT_CHANNELS = {FMT_BGR8: 3, FMT_NV12: 1, FMT_GRAY8: 1, FMT_BGRA8: 4, FMT_RGBA8: 4, FMT_RGB8: 3}
+# formats with 16-bit samples (vs_pixfmt16): bytes per sample.  A P010 frame is a (h * 3 / 2, w) uint16 array: h rows of luma, h / 2
+# rows of interleaved (U, V) pairs, the ten significant bits at the top of each sample.
+FMT_P010 = 6
+FMT_SAMPLE_BYTES = {FMT_P010: 2}
+
+
+def fmt_px_bytes(fmt):
+    """Bytes per pixel of a format's (first) plane."""
+    return FMT_SAMPLE_BYTES[fmt] if fmt in FMT_SAMPLE_BYTES else FMT_CHANNELS[fmt]
+
+
+def fmt_dtype(fmt):
+    return np.uint16 if FMT_SAMPLE_BYTES.get(fmt) == 2 else np.uint8
+
+
+def fmt_two_planes(fmt):
+    return fmt in (FMT_NV12, FMT_P010)
+
+
 BORDER_BLACK, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP, BORDER_FADE = range(6)
 SMOOTH_BOX, SMOOTH_GAUSSIAN, SMOOTH_KALMAN = range(3)
 STAGE_WARP, STAGE_WARP_TABLES, STAGE_COUNT = 7, 8, 9      # vs_stab.h VS_STAGE_*
@@ -238,6 +257,7 @@ class VsLib:
         L.vs_op_libm_checksum.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
         L.vs_op_warp_affine.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
                                         C.c_int, f32p, C.c_int, vp]
+        L.vs_op_warp_affine_p010.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_size_t, vp]
         L.vs_op_warp_affine_nv12.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, f32p, C.c_int,
                                              C.c_size_t, C.c_size_t, vp]
         L.vs_op_resize_gray.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp]
@@ -374,13 +394,25 @@ class VsLib:
         self.sync()
         return d_out.download(img.shape, np.uint8)
 
+    def warp_affine_p010(self, img, w, h, M):
+        """img: one P010 surface (h * 3 / 2 rows of w uint16) and one matrix, or a stack of n surfaces and n matrices."""
+        img = np.ascontiguousarray(img, np.uint16)
+        M = np.ascontiguousarray(M, np.float32).reshape(-1, 6)
+        n = M.shape[0]
+        fb = img.nbytes // n
+        d_in = DevBuf.from_array(self, img)
+        d_out = DevBuf(self, img.nbytes)
+        self.check(self.lib.vs_op_warp_affine_p010(d_in.ptr, 2 * w, d_out.ptr, 2 * w, w, h, _p(M, f32p), n, fb, fb, None))
+        self.sync()
+        return d_out.download(img.shape, np.uint16)
+
     def resize_gray(self, img, dw, dh, fmt=None):
         img = np.ascontiguousarray(img)
         if fmt is None:
             fmt = FMT_BGR8 if img.ndim == 3 else FMT_GRAY8
         w = img.shape[1]
-        h = img.shape[0] if fmt != FMT_NV12 else img.shape[0] * 2 // 3
-        cn = FMT_CHANNELS[fmt]
+        h = img.shape[0] if not fmt_two_planes(fmt) else img.shape[0] * 2 // 3
+        cn = fmt_px_bytes(fmt)
         d_in = DevBuf.from_array(self, img)
         d_out = DevBuf(self, dw * dh)
         self.check(self.lib.vs_op_resize_gray(d_in.ptr, w * cn, w, h, fmt, d_out.ptr, dw, dw, dh, None))
@@ -878,17 +910,18 @@ class Stabilizer:
             pass
 
     def _geom(self, frame, fmt):
+        """(w, h, bytes per pixel of the first plane) of a frame array of format fmt."""
         w = frame.shape[1]
-        h = frame.shape[0] if fmt != FMT_NV12 else frame.shape[0] * 2 // 3
-        return w, h, FMT_CHANNELS[fmt]
+        h = frame.shape[0] if not fmt_two_planes(fmt) else frame.shape[0] * 2 // 3
+        return w, h, fmt_px_bytes(fmt)
 
     def out_shape(self, w, h, fmt):
         ow, oh = C.c_int32(), C.c_int32()
         self.vs.check(self.lib.vs_stab_out_size(self.h, w, h, C.byref(ow), C.byref(oh)), self.h)
+        if fmt_two_planes(fmt):
+            return (oh.value * 3 // 2, ow.value)
         if FMT_CHANNELS[fmt] > 1:
             return (oh.value, ow.value, FMT_CHANNELS[fmt])
-        if fmt == FMT_NV12:
-            return (oh.value * 3 // 2, ow.value)
         return (oh.value, ow.value)
 
     def push(self, frame, fmt=FMT_BGR8, out=None):
@@ -897,7 +930,7 @@ class Stabilizer:
         frame = np.ascontiguousarray(frame)
         w, h, cn = self._geom(frame, fmt)
         if out is None:
-            out = np.zeros(self.out_shape(w, h, fmt), np.uint8)
+            out = np.zeros(self.out_shape(w, h, fmt), fmt_dtype(fmt))
         produced = C.c_int32(0)
         self.vs.check(self.lib.vs_stab_push(self.h, _p(frame, u8p), w, h, w * cn, fmt, _p(out, u8p),
                                             out.shape[1] * cn, C.byref(produced)), self.h)
@@ -905,7 +938,7 @@ class Stabilizer:
 
     def flush(self, like, fmt=FMT_BGR8):
         w, h, cn = self._geom(like, fmt)
-        out = np.zeros(self.out_shape(w, h, fmt), np.uint8)
+        out = np.zeros(self.out_shape(w, h, fmt), fmt_dtype(fmt))
         produced = C.c_int32(0)
         self.vs.check(self.lib.vs_stab_flush(self.h, _p(out, u8p), out.shape[1] * cn, C.byref(produced)), self.h)
         return out if produced.value else None

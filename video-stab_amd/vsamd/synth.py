@@ -133,6 +133,14 @@ def bgr_to_nv12(frame):
     return np.clip(np.vstack([yp, uv]), 0, 255).astype(np.uint8)
 
 
+def nv12_to_p010(nv12, seed=0):
+    """The P010 surface (uint16, same shape) whose samples' high bytes are the NV12 surface's bytes and whose ten-bit values carry
+    two live low bits: (nv12 << 8) | (r << 6) with r a seeded random 0..3.  Works on one surface or a stack of them."""
+    nv12 = np.asarray(nv12, np.uint8)
+    r = np.random.default_rng(seed).integers(0, 4, nv12.shape, np.uint16)
+    return (nv12.astype(np.uint16) << 8) | (r << 6)
+
+
 # ---- long clips rendered on the device (bench.py: more distinct input than the 256 MB Infinity Cache holds) -----------
 def loop_script(seed, n_frames, pan_q8=512, jitter_q8=384, rot_1e5=200):
     """Per-frame camera pose of a CLOSED pan path: n/4 frames right, down, left, up at pan_q8 per frame (the same jitter
