@@ -447,6 +447,28 @@ int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst,
  * a 64-bit mix of (i, bits of f(argument i)) - fn 0 cosf, 1 sinf, 2 atanf: argument i = the float with bit pattern (uint32_t)i;
  * fn 3 atan2f: pair i of a fixed generator.  tests/test_libm.py compares it with the same sum over the host libm's values. */
 int vs_op_libm_checksum(int fn, uint64_t start, uint64_t count, uint64_t* result);
+
+/* Test hook: the library's trajectory kernels driven with given models instead of a RANSAC result; no arithmetic of its own.
+ * Stream s has n_push[s] pushes (frames 1 .. n_push[s]; frame 0 only enters the queue), push i with the refined model
+ * models[s] + 6 i and kinds[s][i] = 1 (model), 0 (estimation failed: the identity) or -1 (nothing to track: no estimate).
+ * form 0, per frame (n_streams == 1): traj_append_device per push through a one-lane kernel, then the per-frame emit kernel for a
+ *   due release.  dbg_out[s] receives the record after every push.
+ * form 1, batch: steps of steps[k % n_steps] (1 .. 64) pushes per stream through the ordered tail kernel, one workgroup per
+ *   stream, and the release kernel where the library runs releases apart (every smoother but Kalman).  dbg_out[s] receives the
+ *   record after every step the stream took part in.  Adaptive smoothing has no batch form (VS_ERR_UNSUPPORTED).
+ * Which push releases which frame is the stabilizer's own rule.  After the last push the queue is flushed through the per-frame
+ * emit kernel, as vs_stab_flush_dev does; every flushed frame appends its record to dbg_out[s] too.
+ * rel_out[s] receives every release in order (push = -1: flush).  has_M: M (frame matrix, chroma matrix) is valid - in batch
+ * form only for the last release of a step; Minv (the two inverse maps) always is.
+ * Capacity: dbg_out[s] 2 * n_push[s] + 2 records, rel_out[s] n_push[s] + 1. */
+typedef struct vs_traj_release {
+    int32_t push, idx, n_seen, has_M;
+    float   M[12];
+    double  Minv[12];
+} vs_traj_release;
+int vs_op_trajectory(const vs_params_c* params, int n_streams, const double* const* models, const int32_t* const* kinds,
+                     const int32_t* n_push, int form, const int32_t* steps, int n_steps, vs_debug_frame* const* dbg_out,
+                     int32_t* n_dbg, vs_traj_release* const* rel_out, int32_t* n_rel);
 /* cv::resize(INTER_LINEAR) + cv::cvtColor(BGR2GRAY) - Stabilizer.cpp:304-305,
  * 448-450.  fmt BGR8 / BGRA8 / RGBA8 / RGB8 (resize per channel, then gray from
  * B, G, R; alpha ignored), GRAY8 / NV12 (luma plane resize), P010 (resize of the luma

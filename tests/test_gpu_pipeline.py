@@ -20,7 +20,8 @@ def bits(a):
     return np.asarray(a, np.float32).view(np.uint32)
 
 
-def run_both(gpu, oracle, clip, fmt=0, **params):
+def run_both(gpu, oracle, clip, fmt=0, intents=None, **params):
+    """intents: a set that receives the intent of every output the device reported."""
     ps = gpu.params(**params)
     po = oracle.params(**params)
     sg = gpu.stabilizer(ps)
@@ -54,6 +55,8 @@ def run_both(gpu, oracle, clip, fmt=0, **params):
             n_out += 1
             assert dg.out_index == do.out_index, k
             assert dg.box_radius == do.box_radius and dg.intent == do.intent, k
+            if intents is not None:
+                intents.add(dg.intent)
             assert np.array_equal(bits(dg.smoothed), bits(do.smoothed)), k
             assert np.array_equal(bits(dg.warp_matrix), bits(do.warp_matrix)), k
             assert np.array_equal(og, oo), k
@@ -77,11 +80,18 @@ def test_pipeline_box_default(gpu, oracle):
 
 
 def test_pipeline_intent_segments(gpu, oracle):
-    """fast pan / rotation jitter / direction changes: exercises all four intent gains."""
+    """fast pan / rotation jitter / direction changes; then the designed clip of traj_inputs.intent_clip (pan towards +x,
+    roll about the picture's corner with translation steps), on which all four intent gains are asserted to occur - the
+    segments clip alone reaches intents 0 and 3 only."""
+    import traj_inputs
     segs = [(0, 512, 0, 384, 200), (18, 2200, 0, 60, 20), (40, 200, 0, 40, 900), (56, 1000, 900, 700, 100)]
     clip = synth.make_clip(synth.SEED_CONFIG1 + 1, 320, 240, 72, segments=segs)
     n_out, worst = run_both(gpu, oracle, clip, smoothing_radius=6)
     assert n_out == 72
+    seen = set()
+    n_out, worst = run_both(gpu, oracle, traj_inputs.intent_clip(), intents=seen, smoothing_radius=6)
+    assert n_out == 72
+    assert seen == {0, 1, 2, 3}, seen
 
 
 @pytest.mark.parametrize("method", [capi.SMOOTH_GAUSSIAN, capi.SMOOTH_KALMAN])

@@ -679,6 +679,20 @@ void tail_fill_seg(void* host_seg, int first, int n, float* d_M_out, TrajState* 
     g.apart = smoothing_method != VS_SMOOTH_KALMAN ? 1 : 0; g.pad = 0;
 }
 size_t tail_in_bytes() { return sizeof(TailIn); }
+// vs_op_trajectory: what a frame's selection would have left for the tail, and an argument block that carries only what the tail
+// and the release kernels read of it (the stream's state, parameters and record)
+void tail_in_fill(void* host_tail_in, const double* model, int ok, int nprev, int have_prev_gray) {
+    TailIn& t = *static_cast<TailIn*>(host_tail_in);
+    memset(&t, 0, sizeof t);
+    for (int i = 0; i < 6; i++) t.model[i] = ok ? model[i] : __builtin_nan("");
+    t.info[0] = ok; t.info[1] = ok ? 0 : -1;
+    t.nprev = nprev; t.have_prev_gray = have_prev_gray;
+}
+void ransac_fill_item_traj(void* host_item, TrajState* traj, const TrajParams* tp, vs_debug_frame* dbg) {
+    RansacArgs& a = *static_cast<RansacArgs*>(host_item);
+    memset(&a, 0, sizeof a);
+    a.traj = traj; a.tp = *tp; a.dbg = dbg; a.have_prev_gray = 1;
+}
 void ransac_item_set_tail_in(void* host_item, void* d_tail_in) { static_cast<RansacArgs*>(host_item)->tail_in = static_cast<TailIn*>(d_tail_in); }
 void tail_item_set_seg(void* host_item, int seg) { static_cast<TailItem*>(host_item)->seg = seg; }
 void ransac_item_set_last(void* host_item, int last) { static_cast<RansacArgs*>(host_item)->last_of_stream = last; }

@@ -29,6 +29,15 @@ __global__ __launch_bounds__(64) void traj_emit_kernel(TrajState* s, TrajParams 
     traj_emit_device(s, p, idx, M_out, Minv_out, dbg, t_out);
 }
 
+// test hook (vs_op_trajectory): the append of one measured model without a RANSAC in front of it - one lane, the same device
+// function ransac_select_kernel ends with
+__global__ __launch_bounds__(64) void traj_append_kernel(TrajState* s, TrajParams p, const double* __restrict__ model, int ok, int nprev,
+                                                         int have_prev_gray, vs_debug_frame* dbg) {
+    if (threadIdx.x != 0) return;
+    const int32_t info[4] = {ok, ok ? 0 : -1, 0, 0};
+    traj_append_device(s, p, model, info, nprev, dbg, have_prev_gray);
+}
+
 // test hook (VS_STAB_DEBUG_DELAY_US): one wave that does nothing for about `ticks` of the 100 MHz clock
 __global__ void spin_kernel(unsigned long long ticks) {
     const unsigned long long t0 = wall_clock64();
@@ -177,6 +186,12 @@ int launch_fade_update(uint8_t* d_hist, const uint8_t* d_stab, size_t sstride, i
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg,
                      hipStream_t st, float* t_out) {
     hipLaunchKernelGGL(traj_emit_kernel, dim3(1), dim3(64), 0, st, s, p, idx, M_out, Minv_out, dbg, t_out);
+    VS_HIP_TRY(hipGetLastError());
+    return VS_OK;
+}
+int launch_traj_append(TrajState* s, const TrajParams& p, const double* d_model, int ok, int nprev, int have_prev_gray, vs_debug_frame* dbg,
+                       hipStream_t st) {
+    hipLaunchKernelGGL(traj_append_kernel, dim3(1), dim3(64), 0, st, s, p, d_model, ok, nprev, have_prev_gray, dbg);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }

@@ -27,6 +27,8 @@ size_t tail_item_bytes();
 void tail_fill_item(void* host_item, int out_due, int out_idx, double* d_Minv_out, const WarpTabJob* tabs);   // tabs: two jobs
 void tail_item_set_seg(void* host_item, int seg);
 size_t tail_in_bytes();
+void tail_in_fill(void* host_tail_in, const double* model, int ok, int nprev, int have_prev_gray);              // vs_op_trajectory
+void ransac_fill_item_traj(void* host_item, TrajState* traj, const TrajParams* tp, vs_debug_frame* dbg);         // vs_op_trajectory
 size_t tail_seg_bytes();        // a segment = the frames of one stream in the step
 void tail_fill_seg(void* host_seg, int first, int n, float* d_M_out, TrajState* traj, vs_debug_frame* dbg, int smoothing_method);
 int launch_ransac_tail_group(const void* d_table, const void* d_tail, const void* d_segs, const void* d_tail_in, int nsegs, int max_n, int items,
@@ -45,6 +47,8 @@ int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_si
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,
                      float* t_out = nullptr);
+int launch_traj_append(TrajState* s, const TrajParams& p, const double* d_model, int ok, int nprev, int have_prev_gray, vs_debug_frame* dbg,
+                       hipStream_t st);     // vs_op_trajectory
 int launch_traj_reset(TrajState* s, int smoothing_radius, hipStream_t st);
 int launch_spin(int microseconds, hipStream_t st);
 int launch_fade_blend(const uint8_t* d_hist, uint8_t* d_frame, size_t bytes, float alpha, float beta, hipStream_t st);

@@ -182,6 +182,13 @@ struct vs_stab {
 
 namespace vsd {
 
+// Stabilizer.cpp:383-389: a push lets the oldest queued frame go once the queue holds clamp(smoothingRadius, 5, 35) frames
+// (the per-frame path, the batch schedule and the trajectory operator all ask here)
+inline int effective_radius(int r) { return std::max(5, std::min(r, 35)); }
+inline bool release_due(size_t queued, int host_radius) { return (int)queued >= effective_radius(host_radius); }
+void fill_traj_params(const vs_params_c& p, TrajParams& t);
+
+
 // Records an event pair around one stage when profiling is on.
 struct StageScope {
     vs_stab* s;

@@ -51,7 +51,6 @@ int fmt_cn(int fmt) {
     }
 }
 
-int effective_radius(int r) { return std::max(5, std::min(r, 35)); }
 int flush_warps(vs_stab* s);
 
 // Batch mode: everything queued so far is analysed and its warps are issued (nothing stays deferred).
@@ -243,36 +242,6 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     return VS_OK;
 }
 
-void fill_traj_params(vs_stab* s) {
-    TrajParams& t = s->tp;
-    memset(&t, 0, sizeof t);
-    const vs_params_c& p = s->p;
-    t.method = p.smoothing_method;
-    t.horizon_lock = p.horizon_lock;
-    t.drone = p.drone_high_freq_mode;
-    t.adaptive = p.adaptive_smoothing;
-    t.min_radius = p.min_smoothing_radius;
-    t.max_radius = p.max_smoothing_radius;
-    t.hf_shake_px = p.hf_shake_px;
-    t.hf_rot_lp_alpha = p.hf_rot_lp_alpha;
-    t.hf_dead_zone = p.hf_dead_zone_threshold;
-    t.hf_decay = p.hf_motion_accumulator_decay;
-    t.hf_freeze_duration = p.hf_freeze_duration;
-    // gaussianFilterConvolve kernel (Stabilizer.cpp:1368-1386), built with the host libm
-    float sigma = (float)p.gaussian_sigma;
-    int ks = std::max(3, (int)std::ceil(6 * sigma));
-    if (ks % 2 == 0) ks++;
-    if (ks > GAUSS_MAX) ks = GAUSS_MAX;
-    t.gauss_ksize = ks;
-    float sum = 0.0f;
-    int center = ks / 2;
-    for (int i = 0; i < ks; i++) {
-        float x = (float)(i - center);
-        t.gauss_kernel[i] = std::exp(-(x * x) / (2 * sigma * sigma));
-        sum += t.gauss_kernel[i];
-    }
-    for (int i = 0; i < ks; i++) t.gauss_kernel[i] /= sum;
-}
 
 // `pre` stream, part 1: the frame enters the queue ring (waits until the slot's last reader is done)
 int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMemcpyKind kind) {
@@ -554,8 +523,7 @@ int batch_enqueue(vs_stab* s, const uint8_t* frame, int slot, int f, uint8_t* d_
     s->have_prev_gray = true;
     s->last_gray_buf = c;
     s->q_slot.push_back(slot); s->q_idx.push_back(f); s->q_ptr.push_back(frame);     // :376-377
-    const int R = effective_radius(s->host_radius);                                  // :383
-    if ((int)s->q_idx.size() >= R) {                                                 // :384-389
+    if (release_due(s->q_idx.size(), s->host_radius)) {                              // :383-389
         b.out_due = true;
         b.out_slot = s->q_slot.front(); b.out_idx = s->q_idx.front(); b.out_frame = s->q_ptr.front();
         s->q_slot.pop_front(); s->q_idx.pop_front(); s->q_ptr.pop_front();
@@ -642,8 +610,7 @@ int push_common(vs_stab* s, int slot, const uint8_t* zc_frame, uint8_t* d_out, s
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
         s->host_radius = r;
     }
-    const int R = effective_radius(s->host_radius);                                 // :383
-    if ((int)s->q_idx.size() < R) { s->next_index++; return VS_OK; }                // :384-387
+    if (!release_due(s->q_idx.size(), s->host_radius)) { s->next_index++; return VS_OK; }   // :383-387
     VS_OBJ_TRY(s, apply_next(s, d_out, out_stride, may_defer));                          // :389
     s->next_index++;
     *produced = 1;
@@ -700,6 +667,35 @@ int create_events(vs_stab* s) {
 }
 
 }  // namespace
+
+void vsd::fill_traj_params(const vs_params_c& p, TrajParams& t) {
+    memset(&t, 0, sizeof t);
+    t.method = p.smoothing_method;
+    t.horizon_lock = p.horizon_lock;
+    t.drone = p.drone_high_freq_mode;
+    t.adaptive = p.adaptive_smoothing;
+    t.min_radius = p.min_smoothing_radius;
+    t.max_radius = p.max_smoothing_radius;
+    t.hf_shake_px = p.hf_shake_px;
+    t.hf_rot_lp_alpha = p.hf_rot_lp_alpha;
+    t.hf_dead_zone = p.hf_dead_zone_threshold;
+    t.hf_decay = p.hf_motion_accumulator_decay;
+    t.hf_freeze_duration = p.hf_freeze_duration;
+    // gaussianFilterConvolve kernel (Stabilizer.cpp:1368-1386), built with the host libm
+    float sigma = (float)p.gaussian_sigma;
+    int ks = std::max(3, (int)std::ceil(6 * sigma));
+    if (ks % 2 == 0) ks++;
+    if (ks > GAUSS_MAX) ks = GAUSS_MAX;
+    t.gauss_ksize = ks;
+    float sum = 0.0f;
+    int center = ks / 2;
+    for (int i = 0; i < ks; i++) {
+        float x = (float)(i - center);
+        t.gauss_kernel[i] = std::exp(-(x * x) / (2 * sigma * sigma));
+        sum += t.gauss_kernel[i];
+    }
+    for (int i = 0; i < ks; i++) t.gauss_kernel[i] /= sum;
+}
 
 // All instances of a process on one device share ONE set of four HIP streams.  Every instance's launches are already wide in batch mode, and the runtime maps HIP streams onto a
 // handful of hardware queues: with four private streams per instance, 2 instances ran at 0.9x and 8 instances
@@ -770,7 +766,7 @@ int vs_stab_create(const vs_params_c* params, int device, vs_stab** out) {
     s->host_radius = params->smoothing_radius;
     if (const char* e = lab_env("VS_STAB_DEBUG_DELAY_US")) s->dbg_delay_us = std::max(0, std::min(std::atoi(e), 20000));
     memset(&s->counters, 0, sizeof s->counters);
-    fill_traj_params(s);
+    fill_traj_params(s->p, s->tp);
     hipError_t e = acquire_streams(s);
     if (e != hipSuccess || create_events(s) != VS_OK) {
         set_last_error(e != hipSuccess ? hipGetErrorString(e) : s->err);

@@ -84,6 +84,12 @@ class VsDebugFrame(C.Structure):
     ]
 
 
+class VsTrajRelease(C.Structure):
+    """vs_traj_release (include/vs_stab.h)"""
+    _fields_ = [("push", C.c_int32), ("idx", C.c_int32), ("n_seen", C.c_int32), ("has_M", C.c_int32),
+                ("M", C.c_float * 12), ("Minv", C.c_double * 12)]
+
+
 class VsRollParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("canny_aperture", C.c_int32), ("scale_factor", C.c_double),
@@ -255,6 +261,9 @@ class VsLib:
         L.vs_dev_memcpy_d2d.argtypes = [vp, vp, C.c_size_t]
         L.vs_dev_copy_rate.argtypes = [C.c_size_t, C.c_int, C.POINTER(C.c_double)]
         L.vs_op_libm_checksum.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.vs_op_trajectory.argtypes = [C.POINTER(VsParams), C.c_int, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_int32)),
+                                       C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.POINTER(VsDebugFrame)),
+                                       C.POINTER(C.c_int32), C.POINTER(C.POINTER(VsTrajRelease)), C.POINTER(C.c_int32)]
         L.vs_op_warp_affine.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
                                         C.c_int, f32p, C.c_int, vp]
         L.vs_op_warp_affine_p010.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_size_t, vp]
@@ -359,6 +368,26 @@ class VsLib:
         self.check(self.lib.vs_dev_sync())
 
     # ---- stage operators, numpy in / numpy out (device round trip) ----------
+    def trajectory(self, params, streams, steps=None):
+        """vs_op_trajectory.  streams: [(models (n, 6) float64, kinds (n,) int32: 1 model, 0 failed, -1 nothing to track)];
+        steps None: per-frame form (one stream), else the batch form with these step sizes in turn.
+        -> per stream (records [VsDebugFrame], releases [VsTrajRelease])."""
+        n = len(streams)
+        mods = [np.ascontiguousarray(m, np.float64).reshape(-1, 6) for m, _ in streams]
+        kinds = [np.ascontiguousarray(k, np.int32) for _, k in streams]
+        npush = (C.c_int32 * n)(*[len(k) for k in kinds])
+        dbg = [(VsDebugFrame * (2 * len(k) + 2))() for k in kinds]
+        rel = [(VsTrajRelease * (len(k) + 1))() for k in kinds]
+        n_dbg, n_rel = (C.c_int32 * n)(), (C.c_int32 * n)()
+        mp = (C.POINTER(C.c_double) * n)(*[m.ctypes.data_as(C.POINTER(C.c_double)) for m in mods])
+        kp = (C.POINTER(C.c_int32) * n)(*[k.ctypes.data_as(C.POINTER(C.c_int32)) for k in kinds])
+        dp = (C.POINTER(VsDebugFrame) * n)(*[C.cast(d, C.POINTER(VsDebugFrame)) for d in dbg])
+        rp = (C.POINTER(VsTrajRelease) * n)(*[C.cast(r, C.POINTER(VsTrajRelease)) for r in rel])
+        st = (C.c_int32 * len(steps))(*steps) if steps else None
+        self.check(self.lib.vs_op_trajectory(C.byref(params), n, mp, kp, npush, 0 if steps is None else 1, st, len(steps) if steps else 0,
+                                             dp, n_dbg, rp, n_rel))
+        return [(list(dbg[s][:n_dbg[s]]), list(rel[s][:n_rel[s]])) for s in range(n)]
+
     def warp_affine(self, img, M, batch=None):
         """img: (h,w[,3]) or (b,h,w,3) uint8; M: (6,) or (b,6).  batch=True / False settles what a 3-d array is: b planes of
         one channel, or one image of shape[2] channels."""
