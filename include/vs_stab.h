@@ -32,7 +32,8 @@ extern "C" {
  *    (round 2), vs_batch_* and vs_dev_copy_rate / vs_dev_memcpy_d2d added.  (The pipelined host call is chosen with
  *    vs_stab_set_host_pipeline - Parameters::hostPipeline of the C++ class - not through vs_params_c, whose layout is unchanged.)
  *    Added since without a layout change: vs_batch_create_params (round 4); the pixel formats VS_FMT_BGRA8,
- *    VS_FMT_RGBA8 and VS_FMT_RGB8; VS_FMT_P010 (enum vs_pixfmt16) with vs_op_warp_affine_p010. */
+ *    VS_FMT_RGBA8 and VS_FMT_RGB8; VS_FMT_P010 (enum vs_pixfmt16) with vs_op_warp_affine_p010; VS_FMT_I420 (enum
+ *    vs_pixfmt_planar) with vs_stab_set_i420_layout, vs_batch_set_i420_layout and vs_op_warp_affine_i420. */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -74,6 +75,27 @@ typedef enum vs_pixfmt {
 typedef enum vs_pixfmt16 {
     VS_FMT_P010 = 6           /* Y plane (h rows of w uint16) followed by UV plane (h/2 rows of w/2 uint16 pairs) */
 } vs_pixfmt16;
+
+/* Planar 4:2:0 - `yuv420p`, I420, YV12: what software decoders emit (FFmpeg / PyAV, libvpx, dav1d, GStreamer's
+ * video/x-raw,format=I420) and software encoders take -, numbered on in the same `int fmt`.  A frame of w x h (both even,
+ * VS_ERR_INVALID_ARG otherwise) has three planes: Y, h rows of w bytes at pitch `stride`; U and V, h/2 rows of w/2 bytes each.
+ * Packed default layout: chroma pitch = stride / 2 (`stride` and `out_stride` must be even, VS_ERR_INVALID_ARG otherwise), U
+ * starts h * stride bytes behind the Y pointer, V (h/2) * (chroma pitch) bytes behind U.  The host entry points take and fill
+ * this layout; device surfaces may differ from it: vs_stab_set_i420_layout.
+ *  - YV12 is I420 with the two plane offsets swapped (V first): give u_off = h * stride + (h/2) * c_pitch and v_off = h * stride.
+ *  - An FFmpeg AVFrame whose linesize[1] is not linesize[0] / 2 is described by c_pitch = linesize[1] (= linesize[2]), the
+ *    offsets being data[1] - data[0] and data[2] - data[0] when the three planes come from one allocation.
+ * Neither needs a format value of its own.  Definitions - every observable of an I420 stream is that of the NV12 stream that
+ * holds the same samples:
+ *  - analysis: the gray image is that of the Y plane, through the kernels an NV12 luma plane takes;
+ *  - warp: Y as an NV12 luma plane; U and V each as a CV_8UC1 plane of w/2 x h/2 under the matrix with the translation halved
+ *    in float (cv::warpAffine treats channels independently: these are the two channels of the NV12 chroma plane's warp),
+ *    INTER_LINEAR, BORDER_CONSTANT 0;
+ *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
+ *    are refused as for NV12 (VS_ERR_UNSUPPORTED); roll correction, AutoZoomCrop, the enhancer and the C++ class do not take it. */
+typedef enum vs_pixfmt_planar {
+    VS_FMT_I420 = 7           /* Y plane (h rows of w), U plane, V plane (h/2 rows of w/2 each) */
+} vs_pixfmt_planar;
 
 /* Stabilizer.cpp:31-38 mapBorderMode() */
 typedef enum vs_border {
@@ -309,7 +331,7 @@ int vs_stab_set_warp_batch(vs_stab* s, int frames);
  * (at most 32 frames per warp launch: a batch of 64 is two launches back to back).
  * Results are bit-identical to frames = 1 and complete after vs_stab_sync(); every push must
  * be given its own d_out until then.  Must be chosen before the first frame (or after
- * vs_stab_clean).  BGR8, GRAY8, NV12 and P010 frames; border padding and crop-and-zoom (BGR8
+ * vs_stab_clean).  BGR8, GRAY8, NV12, P010 and I420 frames; border padding and crop-and-zoom (BGR8
  * only, like everywhere) run batched too; the "fade" border, the virtual canvas and
  * adaptive smoothing keep the per-frame path (each of their outputs depends on the one
  * before it or on a host decision).  Instances of one device share its HIP streams and
@@ -335,6 +357,13 @@ int vs_stab_set_zero_copy(vs_stab* s, int enable);
  * in place: no repacking blit on either side.  The frame queue must be empty. */
 /* P010 surfaces take the same call: the offsets are in bytes and must be even. */
 int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offset);
+/* The same for I420 surfaces (vs_pixfmt_planar): where the U and the V plane start, in bytes behind the Y pointer, and the
+ * pitch of their rows - for the frames given to vs_stab_push_dev in zero-copy or copy-in mode (`in`) and for the device
+ * surfaces it fills (`out`), independently.  0 = the default of that field: c_pitch = stride / 2, u_off = h * stride,
+ * v_off = u_off + (h/2) * c_pitch (with the u_off and c_pitch in force).  A chroma pitch below w/2 is VS_ERR_INVALID_ARG (here
+ * when the geometry is known, else at the next push).  YV12: swap the two offsets.  The frame queue must be empty. */
+int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off,
+                            size_t out_c_pitch);
 
 /* ---- several streams of one device scheduled together (BASELINE configs[4]: 64 streams = 8 per GPU) ----------------------
  * The reference runs one Stabilizer per stream, each with its own cv::cuda::Stream objects (src/Stabilizer.cpp:102-104); here a
@@ -371,6 +400,8 @@ int vs_batch_streams(const vs_batch* b);
 vs_stab* vs_batch_stream(vs_batch* b, int i);
 int vs_batch_set_zero_copy(vs_batch* b, int enable);
 int vs_batch_set_nv12_layout(vs_batch* b, size_t in_uv_offset, size_t out_uv_offset);
+int vs_batch_set_i420_layout(vs_batch* b, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off,
+                             size_t out_c_pitch);
 int vs_batch_push_dev(vs_batch* b, const void* const* d_frames, int w, int h, size_t stride, int fmt, void* const* d_outs,
                       size_t out_stride, int* produced);
 int vs_batch_flush_dev(vs_batch* b, void* const* d_outs, size_t out_stride, int* produced);
@@ -442,6 +473,14 @@ int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst,
                            size_t dst_stride, int w, int h, const float* M,
                            int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
                            void* stream);
+/* I420 / YV12 surface (vs_pixfmt_planar): the Y plane warped with M, the U and the V plane - w/2 x h/2, one channel each -
+ * with the translation halved; all three planes of up to 32 surfaces in one launch.  Surface b at d_src + b * src_frame_bytes
+ * with matrix M + 6 * b.  *_u_off / *_v_off: bytes from a surface's Y pointer to its U / V plane, *_c_pitch: pitch of the chroma
+ * rows; 0 = the packed default of that field (vs_stab_set_i420_layout).  border: VS_BORDER_BLACK or VS_BORDER_REPLICATE. */
+int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch,
+                           void* d_dst, size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch,
+                           int w, int h, const float* M, int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
+                           int border, void* stream);
 /* std::cos / std::sin / std::atan2 on float as the reference calls them (Stabilizer.cpp:662, 902-908, 1689: the host libm's
  * cosf / sinf / atan2f), evaluated by the DEVICE build of the library's restatement: the sum over i in [start, start + count) of
  * a 64-bit mix of (i, bits of f(argument i)) - fn 0 cosf, 1 sinf, 2 atanf: argument i = the float with bit pattern (uint32_t)i;

@@ -57,7 +57,7 @@ struct vs_batch {
     int pre_rel_step = -1;               // the latest step whose tail `pre` has waited for (through the event of its warps' maps)
     double* d_MinvB[2] = {nullptr, nullptr};        // inverse maps of the due frames of a step, 12 doubles each; two sets
     int32_t* d_tabs[2] = {nullptr, nullptr};        // coordinate tables of those frames (warp_tab.h), tab_ints per frame; two sets
-    int tab_ints = 0;                               // one plane's table, or an NV12 surface's block of two
+    int tab_ints = 0;                               // one plane's table, or an NV12 / I420 surface's block of two
     hipEvent_t ev_bpre = nullptr, ev_bgray = nullptr, ev_bnms = nullptr, ev_bdet[4] = {}, ev_blk[4] = {}, ev_warp[2] = {}, ev_rel[2] = {}, ev_up[2] = {}, ev_go = nullptr;
     bool bdet_valid[4] = {false, false, false, false}, warp_valid[2] = {false, false}, rel_valid[2] = {false, false};
     int last_det_batch = -1, last_warp_set = -1, batch_id = 0, pend_set = 0;
@@ -120,7 +120,8 @@ bool group_make_events(vs_batch* g) {
 bool same_launch_shape(const vs_stab* a, const vs_stab* b) {
     const vs_params_c &p = a->p, &q = b->p;
     return a->w == b->w && a->h == b->h && a->fmt == b->fmt && a->src_pitch == b->src_pitch && a->zero_copy == b->zero_copy &&
-           a->in_uv_off == b->in_uv_off && a->out_uv_off == b->out_uv_off && a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
+           a->in_uv_off == b->in_uv_off && a->out_uv_off == b->out_uv_off && a->in_u_off == b->in_u_off && a->in_v_off == b->in_v_off &&
+           a->in_c_pitch == b->in_c_pitch && a->out_u_off == b->out_u_off && a->out_v_off == b->out_v_off && a->out_c_pitch == b->out_c_pitch && a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
            p.lk_win_size == q.lk_win_size && p.ransac_max_iters == q.ransac_max_iters && p.border_size == q.border_size &&
            p.crop_n_zoom == q.crop_n_zoom && (p.border_size <= 0 || p.border_type == q.border_type);
 }
@@ -146,7 +147,7 @@ int group_allocate(vs_batch* g) {
     const size_t o_minv[2] = {take((size_t)cap * 96), take((size_t)cap * 96)};
     int tow, toh;
     out_size(s0, s0->w, s0->h, &tow, &toh);
-    g->tab_ints = fmt_two_planes(s0->fmt) ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
+    g->tab_ints = fmt_two_planes(s0->fmt) || fmt_three_planes(s0->fmt) ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
     size_t o_tabs[2];
     for (auto& o : o_tabs) o = take((size_t)g->tab_ints * cap * sizeof(int32_t));
     VS_OBJ_HIP(g, hipMalloc((void**)&g->d_all, off));
@@ -208,6 +209,11 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
             uint8_t* ud[WARP_BATCH_MAX];
             for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + dst_uv(s0, dsts[i], R.stride); }
             rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, fmt_sample_bytes(s0->fmt));
+            continue;
+        }
+        if (fmt_three_planes(s0->fmt)) {
+            // I420: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
+            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st);
             continue;
         }
         rc = launch_warp_plane(srcs, dsts, m, bp.pad ? bp.prow : s0->src_pitch, bp.pw, bp.ph, bp.crop ? bp.prow : R.stride, bp.pw, bp.ph, s0->cn, maps,
@@ -310,6 +316,8 @@ int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const
                 jobs[0] = WarpTabJob{T, e.src, e.dst, bp.pw, bp.ph};
                 if (fmt_two_planes(s->fmt))
                     jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + dst_uv(s, e.dst, b.out_stride), s->w / 2, s->h / 2};
+                else if (fmt_three_planes(s->fmt))      // ONE chroma table, in pixels, naming the U planes: a V tile adds the launch's V - U
+                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + dst_i420(s, e.dst, b.out_stride).u, s->w / 2, s->h / 2};
             }
             npad++;
             P.pend_stride = b.out_stride;
@@ -410,9 +418,9 @@ int step_issue_pre(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan
     VS_OBJ_HIP(g, hipStreamWaitEvent(pre, g->ev_up[dset], 0));
     {
         StageScope t(g->ref, VS_STAGE_GRAY, pre);
-        // NV12: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline); P010: the high bytes
+        // NV12, I420: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline); P010: the high bytes
         // of the Y plane's samples are (the resize kernels read them in place)
-        const int gfmt = s0->fmt == VS_FMT_NV12 ? VS_FMT_GRAY8 : s0->fmt;
+        const int gfmt = fmt_gray_source(s0->fmt);
         const int n_a = (P.ndet > 0 && P.ndet < n) ? P.ndet : n;
         VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs, n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, P.aligned, pre));  // :448-450
         VS_OBJ_HIP(g, hipEventRecord(g->ev_bgray, pre));      // the detector needs the analysis images of its frames only
@@ -692,6 +700,16 @@ int vs_batch_set_zero_copy(vs_batch* g, int enable) {
 int vs_batch_set_nv12_layout(vs_batch* g, size_t in_uv_offset, size_t out_uv_offset) {
     if (!g) return VS_ERR_INVALID_ARG;
     for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_nv12_layout(s, in_uv_offset, out_uv_offset); if (rc != VS_OK) { g->err = s->err; return rc; } }
+    return VS_OK;
+}
+
+int vs_batch_set_i420_layout(vs_batch* g, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off, size_t out_c_pitch) {
+    if (!g) return VS_ERR_INVALID_ARG;
+    for (vs_stab* s : g->m) {
+        MemberCall mc(s);
+        const int rc = vs_stab_set_i420_layout(s, in_u_off, in_v_off, in_c_pitch, out_u_off, out_v_off, out_c_pitch);
+        if (rc != VS_OK) { g->err = s->err; return rc; }
+    }
     return VS_OK;
 }
 

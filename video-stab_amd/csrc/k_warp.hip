@@ -31,6 +31,7 @@
 #include <utility>
 #include <vector>
 
+#include "launchers.h"
 #include "vs_common.h"
 #include "warp_tab.h"
 
@@ -1196,12 +1197,13 @@ __device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint
 }
 
 // One tile of a plane: tile (tx, ty) of the frame whose plane table starts at Ts (column records) / Tg (the per-column and
-// per-row terms).  tile / lut / s_row: the workgroup's LDS.
+// per-row terms).  tile / lut / s_row: the workgroup's LDS.  src_add / dst_add: bytes from the plane the records name to the plane
+// this tile belongs to (wave-uniform).
 // BORDER: what the staged box holds where it leaves the picture - zeros (cv::warpAffine BORDER_CONSTANT: the stabilizer's warp) or the
 // nearest picture pixel (BORDER_REPLICATE: the roll stage's rotation); a launch whose border is the other one takes the direct path.
 template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1>
 __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
-                                           uint8_t* tile, uint8_t* lut, int2* s_row, int tid) {
+                                           uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add = 0, int dst_add = 0) {
     typedef PlaneCfg<CN, SB> P;
     static_assert(SB == 1 || (SB == 2 && CN <= 2 && BORDER == VS_BORDER_BLACK), "16-bit planes: one or two channels, constant border");
     typedef __attribute__((address_space(1))) uint8_t* gptr;
@@ -1223,6 +1225,8 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
         ad0 = cc[4]; ad1 = cc[5]; bd0 = cc[6]; bd1 = cc[7];
         Xa = r0[0]; Ya = r0[2]; Xb = r1[1]; Yb = r1[3];
     }
+    // (I420: the table's records name the U plane; a V tile is given the byte distances V - U.  Zero for every other caller.)
+    src += src_add; dst += dst_add;
     if (tid >= NT - 32) {      // vertical weights (the table of the BGR kernel: only W0 / W1 are read here)
         const uint32_t f = tid - (NT - 32);
         const uint32_t wlo = (32u - f) | (f << 8);
@@ -1381,6 +1385,63 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
         const uint32_t row = gx2 == 1 ? t : __umulhi(t, mgx2);
         plane_tile<2, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx2), (int)row, tile, lut, s_row, threadIdx.x);
     }
+}
+
+// ---- I420 / YV12 surfaces: Y, U and V tiles of all frames in ONE launch --------------------------------------------------------
+// The scheme of warp_nv12_kernel for planar 4:2:0: the launch is a sequence of tiles (frame, plane, tile row, tile column) - a
+// frame's Y tiles, then its U tiles, then its V tiles - in the same XCD-aware order.  All three planes are one-channel planes
+// (PlaneCfg<1>: tiles of 128 x 64 pixels); U and V have the half-size geometry, a pitch of their own (scpitch / dcpitch) and
+// alignment flags of their own (flags bits 5, 6).  A frame keeps the two table blocks of an NV12 surface (warp_tab.h): the luma
+// table and ONE chroma table, in pixels, built from the map with the halved translation; the chroma table's pointer records name
+// the U plane, and a V tile adds the byte distances V - U (svu / dvu: all surfaces of a launch share one layout; negative for
+// YV12).  The release workgroups of the batch schedule therefore build I420 tables exactly as they build NV12 tables.
+// Arguments: 14 dwords - what gfx950 preloads into scalar registers at wave launch - with source and destination geometry in
+// one dword (they are equal) and the plane distances as 32-bit values (the launcher sends surfaces whose V - U does not fit to
+// the per-plane kernels).  mtpf = ceil(2^32 / tiles per frame), mgx1 / mgx2 likewise for the tile columns of Y and of U / V.
+template <int BORDER>
+__global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
+                                                       uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
+    typedef PlaneCfg<1> P;
+    __shared__ __attribute__((aligned(16))) uint8_t tile[P::ROWS * P::PB];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
+    __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];
+    typedef const __attribute__((address_space(4))) int32_t* cptr;
+    const int w = wh & 0xFFFFu, h = wh >> 16;
+    const uint32_t gx1 = (uint32_t)(w + TW - 1) / TW, gy1 = (uint32_t)(h + P::THP - 1) / P::THP;
+    const uint32_t w2 = (uint32_t)w >> 1, h2 = (uint32_t)h >> 1;
+    const uint32_t gx2 = (w2 + TW - 1) / TW, gy2 = (h2 + P::THP - 1) / P::THP;
+    const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2, n = tpf * (flags >> 16);
+    const uint32_t lin = blockIdx.x;
+    uint32_t seq = lin;
+    if (flags & 0x100u) {
+        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
+        seq = cx * q + (cx < r ? cx : r) + k;
+    }
+    const uint32_t f = __umulhi(seq, mtpf);
+    uint32_t t = seq - f * tpf;
+    gtab_t T = tabs + (size_t)f * tab_stride;
+    // the tile's plane (workgroup-uniform): its geometry, pitches, alignment, table, tile columns, and for V the plane distances
+    WarpCore c;
+    c.border = (flags >> 2) & 7u;
+    uint32_t gx, mgx;
+    int sadd = 0, dadd = 0;
+    if (t < n1) {
+        c.sstride = sstride; c.dstride = dstride;
+        c.sw = c.dw = w; c.sh = c.dh = h;
+        c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u;
+        gx = gx1; mgx = mgx1;
+    } else {
+        t -= n1;
+        if (t >= n2) { t -= n2; sadd = svu; dadd = dvu; }
+        T += tab_layout(w, h).stride;
+        c.sstride = scpitch; c.dstride = dcpitch;
+        c.sw = c.dw = (int)w2; c.sh = c.dh = (int)h2;
+        c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
+        gx = gx2; mgx = mgx2;
+    }
+    const TabLayout L = tab_layout(c.dw, c.dh);
+    const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
+    plane_tile<1, BORDER>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
 }
 
 // Ints of table workspace per frame of dw x dh (see warp_tables_kernel).
@@ -1566,6 +1627,43 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
     return VS_OK;
 }
 
+// I420 surfaces of one geometry and layout, all three planes in ONE launch (warp_i420_kernel), from the frames' table blocks (luma
+// table, then the chroma table whose records name the U planes; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  Returns
+// VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
+int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420Layout& sl, const I420Layout& dl, int w, int h, const int32_t* d_tabs,
+                int border, hipStream_t st) {
+    const int thp = PlaneCfg<1>::THP;
+    const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp - 1) / thp, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + thp - 1) / thp;
+    const unsigned long long tpf = gx1 * gy1 + 2 * gx2 * gy2, total = tpf * (unsigned long long)n;
+    const long long svu = (long long)sl.v - (long long)sl.u, dvu = (long long)dl.v - (long long)dl.u;
+    if (w >= 65536 || h >= 65536 || sl.pitch >= (1ull << 24) || dl.pitch >= (1ull << 24) || sl.cpitch >= (1ull << 24) || dl.cpitch >= (1ull << 24) ||
+        n >= 65536 || total * std::max(tpf, std::max(gx1, gx2)) >= (1ull << 31) || svu != (int32_t)svu || dvu != (int32_t)dvu)
+        return VS_ERR_UNSUPPORTED;
+    // bit 0 / 1: luma source / destination 4-byte aligned; bit 2 / 3: both chroma planes (pointers and pitch)
+    uint32_t al = 0xFu;
+    if (sl.pitch % 4) al &= ~1u;
+    if (dl.pitch % 4) al &= ~2u;
+    if (sl.cpitch % 4 || sl.u % 4 || sl.v % 4) al &= ~4u;
+    if (dl.cpitch % 4 || dl.u % 4 || dl.v % 4) al &= ~8u;
+    for (int i = 0; i < n; i++) {
+        if ((uintptr_t)ys[i] % 4) al &= ~5u;
+        if ((uintptr_t)yd[i] % 4) al &= ~10u;
+    }
+    const uint32_t flags = (al & 3u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
+    const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
+                   mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
+    if (border == VS_BORDER_REPLICATE)
+        hipLaunchKernelGGL(warp_i420_kernel<VS_BORDER_REPLICATE>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
+                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
+                           (int32_t)dvu);
+    else
+        hipLaunchKernelGGL(warp_i420_kernel<VS_BORDER_BLACK>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
+                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
+                           (int32_t)dvu);
+    VS_HIP_TRY(hipGetLastError());
+    return VS_OK;
+}
+
 }  // namespace
 
 // Ints of workspace the table form of a launch over `frames` frames of dw x dh needs (d_tabs of the launchers).
@@ -1650,6 +1748,66 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
         const int what = T ? VS_WARP_ONLY : VS_WARP_ALL;
         VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, what, st, sb));
         VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T ? T + sy : nullptr, block, what, st, sb));
+    }
+    VS_HIP_TRY(hipGetLastError());
+    return VS_OK;
+}
+
+// Per launch of up to 32 surfaces: the luma table and the chroma table (pointer records: the U planes) of every surface - host maps:
+// the NV12 table launch; else one table launch per plane -, then all three planes in ONE grid.  A launch without tables (a caller's
+// tables exist for launches of WARP_TAB_MIN surfaces and more only; the scratch tables serve any number), or one whose geometry is
+// outside what warp_i420_kernel packs, goes plane by plane through the general kernels: V from the maps, without a table.
+int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout sl, I420Layout dl, int w, int h, WarpMaps maps, int border,
+                     WarpTabs tabs, hipStream_t st) {
+    if (n < 1 || !ys || !yd || w < 2 || h < 2 || (w & 1) || (h & 1) || bad_args(ys[0], yd[0], maps.m, sl.pitch, w, h, dl.pitch, w, h, 1, n) ||
+        sl.cpitch < (size_t)(w / 2) || dl.cpitch < (size_t)(w / 2) || !sl.u || !sl.v || !dl.u || !dl.v || sl.u == sl.v || dl.u == dl.v ||
+        bad_call(ys, yd, n, border, tabs)) {
+        set_last_error("warp_i420: invalid argument (w and h must be even, chroma pitches at least w / 2)");
+        return VS_ERR_INVALID_ARG;
+    }
+    const int tab_min = tabs.kind == WarpTabs::SCRATCH ? 1 : WARP_TAB_MIN;
+    const int block = nv12_tab_ints(w, h), sy = tab_layout(w, h).stride;
+    if (tabs.kind == WarpTabs::SCRATCH)
+        VS_TRY(op_tabs(st, (size_t)block * std::min(n, MAXB) * sizeof(int32_t), &tabs.tabs));
+    const WarpMaps muv = {maps.m + 6, maps.stride, maps.host};
+    const size_t tab_step = tabs.kind == WarpTabs::CALLER ? block : 0;
+    const uint8_t* ps[MAXB];
+    uint8_t* pd[MAXB];
+    for (int b0 = 0; b0 < n; b0 += MAXB) {
+        const int nb = std::min(MAXB, n - b0);
+        int32_t* T = tabs.kind != WarpTabs::NONE && nb >= tab_min ? tabs.tabs + b0 * tab_step : nullptr;
+        if (!T && tabs.what == VS_WARP_TABLES_ONLY) continue;
+        const WarpMaps my = maps_from(maps, b0), mu = maps_from(muv, b0);
+        auto plane = [&](size_t so, size_t d_o, size_t sp, size_t dp, int pw, int ph, WarpMaps m, int32_t* tab, int what) -> int {
+            for (int i = 0; i < nb; i++) { ps[i] = ys[b0 + i] + so; pd[i] = yd[b0 + i] + d_o; }
+            return plane_launch(ps, pd, nb, sp, pw, ph, dp, pw, ph, 1, m, border, tab, block, what, st);
+        };
+        if (T && tabs.what != VS_WARP_ONLY) {
+            if (maps.host && nb <= NVT_MAX) {
+                NvTabArgs t;
+                t.tabs = T; t.block = block; t.chroma = sy; t.w = w; t.h = h; t.src_uv = sl.u; t.dst_uv = dl.u;
+                for (int i = 0; i < NVT_MAX; i++) { t.ys[i] = ys[b0 + (i < nb ? i : 0)]; t.yd[i] = yd[b0 + (i < nb ? i : 0)]; }
+                for (int i = 0; i < NVT_MAX * 6; i++) {
+                    t.my[i] = i < 6 * nb ? my.m[(size_t)my.stride * (i / 6) + i % 6] : 0.;
+                    t.muv[i] = i < 6 * nb ? mu.m[(size_t)mu.stride * (i / 6) + i % 6] : 0.;
+                }
+                const int entries = w + h + (w + TW - 1) / TW + (h + TH - 1) / TH;
+                hipLaunchKernelGGL(warp_tables_nv12_kernel, dim3((entries + NT - 1) / NT, nb, 2), dim3(NT), 0, st, t);
+            } else {
+                VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, VS_WARP_TABLES_ONLY));
+                VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, w / 2, h / 2, mu, T + sy, VS_WARP_TABLES_ONLY));
+            }
+        }
+        if (tabs.what == VS_WARP_TABLES_ONLY) continue;
+        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st) : VS_ERR_UNSUPPORTED;
+        if (one != VS_ERR_UNSUPPORTED) {
+            VS_TRY(one);
+            continue;
+        }
+        const int what = T ? VS_WARP_ONLY : VS_WARP_ALL;
+        VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, what));
+        VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, w / 2, h / 2, mu, T ? T + sy : nullptr, what));
+        VS_TRY(plane(sl.v, dl.v, sl.cpitch, dl.cpitch, w / 2, h / 2, mu, nullptr, VS_WARP_ALL));
     }
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;

@@ -1,6 +1,6 @@
 // Stage launchers of the stabilizer pipeline that vs_common.h does not declare: the per-frame RANSAC / trajectory / border
 // kernels and the batched forms, whose argument blocks are opaque to the host (sized and filled through *_bytes / *_fill_*).
-// Host-only: included by stabilizer.cpp and batch_schedule.cpp, defined in the k_*.hip file named with each group.
+// Host-only: included by stabilizer.cpp, batch_schedule.cpp and vs_api.cpp, defined in the k_*.hip file named with each group.
 #ifndef VS_LAUNCHERS_H
 #define VS_LAUNCHERS_H
 
@@ -43,6 +43,25 @@ size_t gftt_item_bytes();
 int gftt_fill_item(void* host_item, const uint8_t* d_gray, size_t stride, int w, int h, int max_corners, double quality, double min_distance,
                    int block_size, const GfttWork& wk, float* d_pts, int32_t* d_count);
 int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_size, hipStream_t st, int what);
+
+// ---- k_warp.hip: I420 / YV12 surfaces (planar 4:2:0) of w x h (even) luma pixels
+// Where the planes of a surface lie: rows of `pitch` bytes of luma at the surface pointer, the U and V planes (h / 2 rows of w / 2
+// bytes, `cpitch` bytes apart) u and v bytes behind it.  One layout for all source surfaces of a call, one for all destinations.
+struct I420Layout { size_t pitch, cpitch, u, v; };
+// The layout a caller describes with 0 = default per field: chroma pitch = pitch / 2, U behind the h luma rows, V behind U.
+inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, size_t c_pitch) {
+    I420Layout l;
+    l.pitch = pitch;
+    l.cpitch = c_pitch ? c_pitch : pitch / 2;
+    l.u = u_off ? u_off : (size_t)h * pitch;
+    l.v = v_off ? v_off : l.u + (size_t)(h / 2) * l.cpitch;
+    return l;
+}
+// Launches with tables warp the three planes of their surfaces in ONE grid (warp_i420_kernel); the tables are an NV12 surface's
+// (nv12_tab_ints per frame: luma table, then one chroma table whose pointer records name the U planes), the maps as for NV12
+// (m: luma, m + 6: chroma).  A call with the scratch tables builds them for any number of surfaces.
+int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout src, I420Layout dst, int w, int h, WarpMaps maps, int border,
+                     WarpTabs tabs, hipStream_t st);
 
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,

@@ -40,12 +40,12 @@ using namespace vsd;
 
 namespace {
 
-// Bytes per pixel of a frame format's first plane (NV12 / GRAY8: the luma byte; P010: the 16-bit luma sample); 0 for an unknown format.
+// Bytes per pixel of a frame format's first plane (NV12 / GRAY8 / I420: the luma byte; P010: the 16-bit luma sample); 0 for an unknown format.
 int fmt_cn(int fmt) {
     switch (fmt) {
         case VS_FMT_BGR8: case VS_FMT_RGB8: return 3;
         case VS_FMT_BGRA8: case VS_FMT_RGBA8: return 4;
-        case VS_FMT_NV12: case VS_FMT_GRAY8: return 1;
+        case VS_FMT_NV12: case VS_FMT_GRAY8: case VS_FMT_I420: return 1;
         case VS_FMT_P010: return 2;
         default: return 0;
     }
@@ -129,7 +129,8 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     if (s->aw < 3 || s->ah < 3) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "analysis size too small");
     // (the reference's cvtColor(BGR2GRAY) of the canvas, Stabilizer.cpp:2225, throws on anything but three channels)
     if (canvas_on(s) && fmt != VS_FMT_BGR8)
-        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, fmt == VS_FMT_P010 ? "enableVirtualCanvas needs a BGR8 stream (not P010)" : "enableVirtualCanvas needs a BGR8 stream");
+        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, fmt == VS_FMT_P010 ? "enableVirtualCanvas needs a BGR8 stream (not P010)"
+                                                  : fmt == VS_FMT_I420 ? "enableVirtualCanvas needs a BGR8 stream (not I420)" : "enableVirtualCanvas needs a BGR8 stream");
     // buildOpticalFlowPyramid: levels that fit the window
     {
         int sw = s->aw, sh = s->ah;
@@ -243,6 +244,24 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
 }
 
 
+// The three planes of an I420 frame from one layout to another.
+int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src, const I420Layout& sl, hipMemcpyKind kind, hipStream_t st) {
+    const size_t cw = (size_t)s->w / 2;
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, s->w, s->h, kind, st));
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.u, dl.cpitch, src + sl.u, sl.cpitch, cw, s->h / 2, kind, st));
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.v, dl.cpitch, src + sl.v, sl.cpitch, cw, s->h / 2, kind, st));
+    return VS_OK;
+}
+
+// The result of a host call from its staging buffer (rows of `orow` bytes, `orows` of them; I420: the packed layout at that pitch)
+// into the caller's frame.
+int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st) {
+    if (fmt_three_planes(s->fmt))
+        return copy_i420(s, out, i420_layout(out_stride, s->h, 0, 0, 0), d_src, i420_layout(orow, s->h, 0, 0, 0), hipMemcpyDeviceToHost, st);
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, st));
+    return VS_OK;
+}
+
 // `pre` stream, part 1: the frame enters the queue ring (waits until the slot's last reader is done)
 int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMemcpyKind kind) {
     if (s->slot_valid[slot]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_slot[slot], 0));
@@ -252,6 +271,14 @@ int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMem
         VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->h, kind, s->st_pre));
         VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + (size_t)s->h * s->row_bytes, s->row_bytes, (const uint8_t*)src + s->in_uv_off, stride,
                                   s->row_bytes, s->h / 2, kind, s->st_pre));
+        return VS_OK;
+    }
+    if (fmt_three_planes(s->fmt)) {
+        // three planes into the slot's packed layout: from the caller's layout (device surfaces) or the packed default at the
+        // caller's pitch (host frames)
+        const I420Layout in = kind == hipMemcpyDeviceToDevice ? i420_layout(stride, s->h, s->in_u_off, s->in_v_off, s->in_c_pitch) : i420_layout(stride, s->h, 0, 0, 0);
+        const I420Layout q = i420_layout(s->row_bytes, s->h, 0, 0, 0);
+        VS_OBJ_TRY(s, copy_i420(s, dst, q, (const uint8_t*)src, in, kind, s->st_pre));
         return VS_OK;
     }
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->rows_total, kind, s->st_pre));
@@ -268,7 +295,7 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     if (f - 3 >= 1 && s->det_valid[(f - 3) % EVR]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_det[(f - 3) % EVR], 0));
     {
         StageScope t(s, VS_STAGE_GRAY, s->st_pre);
-        VS_OBJ_TRY(s, launch_resize_gray(d_frame, s->src_pitch, s->w, s->h, s->fmt, s->pyr[c].img[0], s->aw, s->aw, s->ah, s->st_pre));  // :448-450
+        VS_OBJ_TRY(s, launch_resize_gray(d_frame, s->src_pitch, s->w, s->h, fmt_gray_source(s->fmt), s->pyr[c].img[0], s->aw, s->aw, s->ah, s->st_pre));  // :448-450
     }
     VS_OBJ_HIP(s, hipEventRecord(s->ev_gray[c], s->st_pre));
     {
@@ -409,7 +436,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
     int ow, oh;
     out_size(s, s->w, s->h, &ow, &oh);
     s->last_out_w = ow; s->last_out_h = oh;
-    const bool plain = idx < s->n_transforms && !fmt_two_planes(s->fmt) && p.border_size <= 0 && !canvas_on(s);
+    const bool plain = idx < s->n_transforms && !fmt_two_planes(s->fmt) && !fmt_three_planes(s->fmt) && p.border_size <= 0 && !canvas_on(s);
     const BorderPlan bp = border_plan(s);
     if (may_defer && plain && s->warp_batch > 1) {
         VS_OBJ_TRY(s, defer_output(s, idx, frame, d_out, out_stride, slot));
@@ -427,7 +454,10 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // flush): the queued frame is returned as is, at its own size (no border pad).
         if (ow != s->w || oh != s->h)
             VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
+        if (fmt_three_planes(s->fmt))
+            VS_OBJ_TRY(s, copy_i420(s, d_out, dst_i420(s, d_out, out_stride), frame, src_i420(s), hipMemcpyDeviceToDevice, st));
+        else
+            VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
         if (fmt_two_planes(s->fmt))
             VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out + dst_uv(s, d_out, out_stride), out_stride, frame + src_uv(s), s->src_pitch, s->row_bytes,
                                       s->h / 2, hipMemcpyDeviceToDevice, st));
@@ -444,6 +474,11 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // (a P010 surface goes through the one-launch kernel even on its own: its tables are built in the stream's scratch)
         rc = launch_warp_nv12(&frame, &d_out, &uv, &out_uv, 1, s->src_pitch, out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
                               VS_BORDER_BLACK, s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, fmt_sample_bytes(s->fmt));
+    } else if (fmt_three_planes(s->fmt)) {
+        // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
+        StageScope t(s, VS_STAGE_WARP, st);
+        rc = launch_warp_i420(&frame, &d_out, 1, src_i420(s), dst_i420(s, d_out, out_stride), s->w, s->h, WarpMaps{s->d_Minv, 12, false}, VS_BORDER_BLACK,
+                              WarpTabs{WarpTabs::SCRATCH}, st);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
         const size_t prow = bp.prow, nb = prow * bh;
@@ -577,7 +612,7 @@ int push_common(vs_stab* s, int slot, const uint8_t* zc_frame, uint8_t* d_out, s
     s->counters.frames_in++;
     if (p.crop_n_zoom && s->orig_w == 0) { s->orig_w = s->w; s->orig_h = s->h; }   // :267-269
     if (s->first) {                                                                  // :271-368
-        VS_OBJ_TRY(s, launch_resize_gray(frame, s->src_pitch, s->w, s->h, s->fmt, s->d_first_gray, 480, 480, 270, s->st_pre));  // :304-305
+        VS_OBJ_TRY(s, launch_resize_gray(frame, s->src_pitch, s->w, s->h, fmt_gray_source(s->fmt), s->d_first_gray, 480, 480, 270, s->st_pre));  // :304-305
         VS_OBJ_HIP(s, hipEventRecord(s->ev_first, s->st_pre));
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_det, s->ev_first, 0));
         VS_OBJ_TRY(s, launch_gftt(s->d_first_gray, 480, 480, 270, p.max_corners, p.quality_level, p.min_distance,
@@ -632,7 +667,15 @@ int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
     if (fmt == VS_FMT_P010 && ((w & 1) || (h & 1))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even w,h");
     if (fmt == VS_FMT_P010 && ((stride | s->in_uv_off | s->out_uv_off) & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even pitches and plane offsets (16-bit samples)");
-    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8 / P010)
+    if (fmt == VS_FMT_I420) {
+        if ((w & 1) || (h & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs even w,h");
+        if (stride & 1) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even pitch (the default chroma pitch is half of it)");
+        if ((s->in_c_pitch && s->in_c_pitch < (size_t)w / 2) || (s->out_c_pitch && s->out_c_pitch < (size_t)w / 2))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420: the chroma pitch must be at least w / 2");
+        if (s->p.border_size > 0)
+            return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not I420");
+    }
+    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8 / P010 / I420)
     if (fmt == VS_FMT_P010 && s->p.border_size > 0)
         return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not P010");
     if (cn == 1 && s->p.border_size > 0) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need a colour format (BGR8, BGRA8, RGBA8, RGB8)");
@@ -822,6 +865,8 @@ int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride
     if (rc != VS_OK) return rc;
     if (fmt == VS_FMT_P010 && (((uintptr_t)d_data | (uintptr_t)d_out | out_stride) & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
+    if (fmt == VS_FMT_I420 && (out_stride & 1))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
     if (s->zero_copy) {
         // the frame is read where it is: it must stay valid and unchanged until its own result has been produced
         // one pitch for all frames in flight (the batched launches take it once): it may change when nothing is queued
@@ -860,6 +905,8 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
     if (!s->allocated || s->q_slot.empty()) return VS_OK;
     if (s->fmt == VS_FMT_P010 && (((uintptr_t)d_out | out_stride) & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
+    if (s->fmt == VS_FMT_I420 && (out_stride & 1))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
@@ -886,6 +933,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
     // (as in the synchronous call: the buffer is only looked at when a frame will be delivered into it; a held frame is
     // always a full-size one - pass-through frames only come out of vs_stab_flush's synchronous part)
     if (have_prev && (!out || out_stride < orow)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
+    if (fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
     for (auto& hld : s->d_hold)
         if (!hld) VS_OBJ_HIP(s, hipMalloc((void**)&hld, s->out_bytes));
     // A copy to or from PAGEABLE memory (the frames of a cv::Mat) keeps its caller inside hipMemcpy for the whole transfer -
@@ -906,7 +954,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
         const uint8_t* d_src = s->d_hold[s->hold_cur ^ 1];
 
         bool helped = false;
-        if (use_helper && !host_ptr_page_locked(out)) {
+        if (use_helper && !fmt_three_planes(s->fmt) && !host_ptr_page_locked(out)) {
             try {           // (no exception leaves the C ABI: without a helper thread the download goes out from this one)
                 if (!s->helper) s->helper.reset(new HostHelper);
                 const int dev = s->device;
@@ -924,7 +972,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
             }
         }
         if (!helped) {
-            VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, s->st_warp));
+            VS_OBJ_TRY(s, download_result(s, out, out_stride, d_src, orow, orows, s->st_warp));
         }
     }
     int slot;
@@ -955,8 +1003,11 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
     if (!data) return VS_OK;
     int rc = prepare(s, w, h, fmt, stride);
     if (rc != VS_OK) return rc;
-    if (s->zero_copy && (s->src_pitch != s->row_bytes || (fmt_two_planes(s->fmt) && s->in_uv_off)))
+    if (s->zero_copy && (s->src_pitch != s->row_bytes || (fmt_two_planes(s->fmt) && s->in_uv_off) ||
+                         (fmt_three_planes(s->fmt) && (s->in_u_off || s->in_v_off || s->in_c_pitch))))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: host frames cannot join a queue of pitched zero-copy surfaces");
+    if (fmt == VS_FMT_I420 && out && (out_stride & 1))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
     if (s->host_pipe && !s->batch_active) return push_host_pipelined(s, data, w, h, stride, fmt, out, out_stride, produced);
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
@@ -983,7 +1034,7 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
         const int orows = fmt_rows(fmt, oh);
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));   // (per-frame pipeline: the warp ran on the warp stream)
         if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));     // batch mode: the warps run on `pre` (group_launch_ready)
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
+        VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st));
     }
     // the caller's frame must be consumed and its result delivered before returning
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));
@@ -1001,7 +1052,8 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
         if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
         const int orows = fmt_rows(s->fmt, s->hold_h);
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orow, orows, hipMemcpyDeviceToHost, s->st_warp));
+        if (s->fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+        VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orows, s->st_warp));
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
         s->hold_valid = false;
         s->last_out_w = s->hold_w; s->last_out_h = s->hold_h;
@@ -1013,6 +1065,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     out_size(s, s->w, s->h, &ow, &oh);
     const size_t orow = (size_t)ow * s->cn;
     if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
+    if (s->fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, flush_warps(s));
     int rc = flush_dev_impl(s, s->d_out, orow, produced, false);
@@ -1020,7 +1073,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     const int orows = fmt_rows(s->fmt, oh);
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
     if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));         // batch mode: the warps run on `pre`
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, s->d_out, orow, orow, orows, hipMemcpyDeviceToHost, s->st));
+    VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st));
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
     return VS_OK;
 }
@@ -1080,6 +1133,19 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: P010 needs even plane offsets (16-bit samples)");
     s->in_uv_off = in_uv_offset;
     s->out_uv_off = out_uv_offset;
+    return VS_OK;
+}
+
+// I420 / YV12 surfaces of the device entry points: where the U and V planes start behind the Y pointer and the pitch of their rows,
+// for the frames pushed (`in`: zero-copy and copy-in alike) and for the surfaces filled (`out`).  0 = the packed default per field.
+int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off, size_t out_c_pitch) {
+    if (!s) return VS_ERR_INVALID_ARG;
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: the frame queue must be empty");
+    if (s->allocated && s->fmt == VS_FMT_I420 && ((in_c_pitch && in_c_pitch < (size_t)s->w / 2) || (out_c_pitch && out_c_pitch < (size_t)s->w / 2)))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I420: the chroma pitch must be at least w / 2");
+    s->in_u_off = in_u_off; s->in_v_off = in_v_off; s->in_c_pitch = in_c_pitch;
+    s->out_u_off = out_u_off; s->out_v_off = out_v_off; s->out_c_pitch = out_c_pitch;
     return VS_OK;
 }
 

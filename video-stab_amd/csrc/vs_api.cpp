@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "launchers.h"
 #include "vs_common.h"
 
 namespace vsd {
@@ -250,6 +251,31 @@ int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst, si
                            int w, int h, const float* M, int batch, size_t src_frame_bytes,
                            size_t dst_frame_bytes, void* stream) {
     return warp_affine_two_planes(d_src, src_stride, d_dst, dst_stride, w, h, M, batch, src_frame_bytes, dst_frame_bytes, stream, 2);
+}
+
+// I420 / YV12: luma under the full matrix; U and V - one-channel planes of half the size - under the matrix with the halved
+// translation.  0 = the packed default of a layout field.
+int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst, size_t dst_stride,
+                           size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch, size_t src_frame_bytes,
+                           size_t dst_frame_bytes, int border, void* stream) {
+    VS_TRY(ensure_device());
+    if (!d_src || !d_dst || !M || batch <= 0 || w < 2 || h < 2 || (w & 1) || (h & 1) || (!src_c_pitch && (src_stride & 1)) ||
+        (!dst_c_pitch && (dst_stride & 1))) {
+        set_last_error("warp_affine_i420: invalid argument (w, h and, for the default chroma pitch, the strides must be even)");
+        return VS_ERR_INVALID_ARG;
+    }
+    std::vector<double> Minv(12 * (size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const float* m = M + 6 * (size_t)b;
+        const float c[6] = {m[0], m[1], m[2] * 0.5f, m[3], m[4], m[5] * 0.5f};
+        warp_invert(m, &Minv[12 * (size_t)b]);
+        warp_invert(c, &Minv[12 * (size_t)b + 6]);
+    }
+    const I420Layout sl = i420_layout(src_stride, h, src_u_off, src_v_off, src_c_pitch), dl = i420_layout(dst_stride, h, dst_u_off, dst_v_off, dst_c_pitch);
+    const auto ys = frame_list((const uint8_t*)d_src, src_frame_bytes, batch);
+    const auto yd = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch);
+    return launch_warp_i420(ys.data(), yd.data(), batch, sl, dl, w, h, WarpMaps{Minv.data(), 12, true}, border, WarpTabs{WarpTabs::SCRATCH},
+                            (hipStream_t)stream);
 }
 
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt, void* d_dst,

@@ -25,10 +25,15 @@ FMT_CHANNELS = {FMT_BGR8: 3, FMT_NV12: 1, FMT_GRAY8: 1, FMT_BGRA8: 4, FMT_RGBA8:
 # rows of interleaved (U, V) pairs, the ten significant bits at the top of each sample.
 FMT_P010 = 6
 FMT_SAMPLE_BYTES = {FMT_P010: 2}
+# planar 4:2:0 (vs_pixfmt_planar).  A packed I420 frame is a (h * 3 / 2, w) uint8 array: h rows of Y, then the U plane and the V
+# plane, h / 2 rows of w / 2 bytes each (synth.nv12_to_i420).  YV12 and padded chroma rows are layouts of it (set_i420_layout).
+FMT_I420 = 7
 
 
 def fmt_px_bytes(fmt):
     """Bytes per pixel of a format's (first) plane."""
+    if fmt == FMT_I420:
+        return 1
     return FMT_SAMPLE_BYTES[fmt] if fmt in FMT_SAMPLE_BYTES else FMT_CHANNELS[fmt]
 
 
@@ -38,6 +43,11 @@ def fmt_dtype(fmt):
 
 def fmt_two_planes(fmt):
     return fmt in (FMT_NV12, FMT_P010)
+
+
+def fmt_420(fmt):
+    """A frame array of this format has h * 3 / 2 rows: h of luma, h / 2 of subsampled chroma."""
+    return fmt_two_planes(fmt) or fmt == FMT_I420
 
 
 BORDER_BLACK, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP, BORDER_FADE = range(6)
@@ -226,6 +236,7 @@ class VsLib:
         L.vs_stab_set_batch.argtypes = [vp, C.c_int]
         L.vs_stab_set_zero_copy.argtypes = [vp, C.c_int]
         L.vs_stab_set_nv12_layout.argtypes = [vp, C.c_size_t, C.c_size_t]
+        L.vs_stab_set_i420_layout.argtypes = [vp] + [C.c_size_t] * 6
         L.vs_stab_set_profiling.argtypes = [vp, C.c_int]
         L.vs_stab_get_stage_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         try:
@@ -238,6 +249,7 @@ class VsLib:
             L.vs_batch_stream.restype = vp
             L.vs_batch_set_zero_copy.argtypes = [vp, C.c_int]
             L.vs_batch_set_nv12_layout.argtypes = [vp, C.c_size_t, C.c_size_t]
+            L.vs_batch_set_i420_layout.argtypes = [vp] + [C.c_size_t] * 6
             L.vs_batch_push_dev.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(vp), C.c_size_t, i32p]
             L.vs_batch_flush_dev.argtypes = [vp, C.POINTER(vp), C.c_size_t, i32p]
             L.vs_batch_sync.argtypes = [vp]
@@ -269,6 +281,8 @@ class VsLib:
         L.vs_op_warp_affine_p010.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_size_t, vp]
         L.vs_op_warp_affine_nv12.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, f32p, C.c_int,
                                              C.c_size_t, C.c_size_t, vp]
+        L.vs_op_warp_affine_i420.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                             C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, vp]
         L.vs_op_resize_gray.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp]
         L.vs_op_pyr_down.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, vp]
         L.vs_op_scharr.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, vp]
@@ -434,6 +448,22 @@ class VsLib:
         self.check(self.lib.vs_op_warp_affine_p010(d_in.ptr, 2 * w, d_out.ptr, 2 * w, w, h, _p(M, f32p), n, fb, fb, None))
         self.sync()
         return d_out.download(img.shape, np.uint16)
+
+    def warp_affine_i420(self, img, w, h, M, border=BORDER_BLACK):
+        """img: one packed I420 surface (h * 3 / 2 rows of w bytes: Y, U plane, V plane) and one matrix, or a stack of n surfaces
+        and n matrices; all three planes of up to 32 surfaces per launch."""
+        img = np.ascontiguousarray(img, np.uint8)
+        M = np.ascontiguousarray(M, np.float32).reshape(-1, 6)
+        n = M.shape[0]
+        fb = img.nbytes // n
+        d_in = DevBuf.from_array(self, img)
+        d_out = DevBuf(self, img.nbytes)
+        try:
+            self.check(self.lib.vs_op_warp_affine_i420(d_in.ptr, w, 0, 0, 0, d_out.ptr, w, 0, 0, 0, w, h, _p(M, f32p), n, fb, fb, border, None))
+            self.sync()
+            return d_out.download(img.shape, np.uint8)
+        finally:
+            d_in.free(); d_out.free()
 
     def resize_gray(self, img, dw, dh, fmt=None):
         img = np.ascontiguousarray(img)
@@ -941,13 +971,13 @@ class Stabilizer:
     def _geom(self, frame, fmt):
         """(w, h, bytes per pixel of the first plane) of a frame array of format fmt."""
         w = frame.shape[1]
-        h = frame.shape[0] if not fmt_two_planes(fmt) else frame.shape[0] * 2 // 3
+        h = frame.shape[0] if not fmt_420(fmt) else frame.shape[0] * 2 // 3
         return w, h, fmt_px_bytes(fmt)
 
     def out_shape(self, w, h, fmt):
         ow, oh = C.c_int32(), C.c_int32()
         self.vs.check(self.lib.vs_stab_out_size(self.h, w, h, C.byref(ow), C.byref(oh)), self.h)
-        if fmt_two_planes(fmt):
+        if fmt_420(fmt):
             return (oh.value * 3 // 2, ow.value)
         if FMT_CHANNELS[fmt] > 1:
             return (oh.value, ow.value, FMT_CHANNELS[fmt])
@@ -1006,6 +1036,10 @@ class Stabilizer:
 
     def set_nv12_layout(self, in_uv_offset=0, out_uv_offset=0):
         self.vs.check(self.lib.vs_stab_set_nv12_layout(self.h, in_uv_offset, out_uv_offset), self.h)
+
+    def set_i420_layout(self, in_u_off=0, in_v_off=0, in_c_pitch=0, out_u_off=0, out_v_off=0, out_c_pitch=0):
+        """Plane offsets (bytes behind the Y pointer) and chroma pitch of the I420 surfaces pushed / filled; 0 = packed default."""
+        self.vs.check(self.lib.vs_stab_set_i420_layout(self.h, in_u_off, in_v_off, in_c_pitch, out_u_off, out_v_off, out_c_pitch), self.h)
 
     def set_zero_copy(self, on=True):
         self.vs.check(self.lib.vs_stab_set_zero_copy(self.h, int(on)), self.h)
@@ -1103,6 +1137,9 @@ class Batch:
 
     def set_nv12_layout(self, in_uv_offset=0, out_uv_offset=0):
         self._check(self.lib.vs_batch_set_nv12_layout(self.h, in_uv_offset, out_uv_offset))
+
+    def set_i420_layout(self, in_u_off=0, in_v_off=0, in_c_pitch=0, out_u_off=0, out_v_off=0, out_c_pitch=0):
+        self._check(self.lib.vs_batch_set_i420_layout(self.h, in_u_off, in_v_off, in_c_pitch, out_u_off, out_v_off, out_c_pitch))
 
     def push_dev(self, d_frames, w, h, stride, fmt, d_outs, out_stride):
         """d_frames / d_outs: one device pointer per stream (None: no frame for that stream).  Returns produced[]."""

@@ -141,6 +141,43 @@ def nv12_to_p010(nv12, seed=0):
     return (nv12.astype(np.uint16) << 8) | (r << 6)
 
 
+def i420_layout(w, h, pitch=None, c_pitch=None, u_off=None, v_off=None):
+    """(pitch, c_pitch, u_off, v_off) of an I420 surface with the library's defaults filled in (vs_stab_set_i420_layout): chroma pitch
+    = pitch / 2, U behind the h luma rows, V behind U.  YV12: give the two offsets swapped."""
+    pitch = pitch or w
+    c_pitch = c_pitch or pitch // 2
+    u_off = u_off or h * pitch
+    v_off = v_off or u_off + (h // 2) * c_pitch
+    return pitch, c_pitch, u_off, v_off
+
+
+def nv12_to_i420(nv12, pitch=None, c_pitch=None, u_off=None, v_off=None, size=None, fill=0):
+    """The I420 surface that holds the samples of one NV12 surface (h * 3 / 2, w).  Packed (no layout given): a (h * 3 / 2, w)
+    array - h rows of Y, then the U plane, then the V plane, h / 2 rows of w / 2 bytes each.  With a layout: a flat buffer of
+    `size` bytes (default: up to the end of the last plane), `fill` wherever no sample lies."""
+    nv12 = np.asarray(nv12, np.uint8)
+    w, h = nv12.shape[1], nv12.shape[0] * 2 // 3
+    packed = not (pitch or c_pitch or u_off or v_off or size)
+    pitch, c_pitch, u_off, v_off = i420_layout(w, h, pitch, c_pitch, u_off, v_off)
+    end = max(h * pitch, u_off + (h // 2) * c_pitch, v_off + (h // 2) * c_pitch)
+    buf = np.full(size or end, fill, np.uint8)
+    buf[:h * pitch].reshape(h, pitch)[:, :w] = nv12[:h]
+    buf[u_off:u_off + (h // 2) * c_pitch].reshape(h // 2, c_pitch)[:, :w // 2] = nv12[h:, 0::2]
+    buf[v_off:v_off + (h // 2) * c_pitch].reshape(h // 2, c_pitch)[:, :w // 2] = nv12[h:, 1::2]
+    return buf.reshape(h * 3 // 2, w) if packed else buf
+
+
+def i420_to_nv12(buf, w, h, pitch=None, c_pitch=None, u_off=None, v_off=None):
+    """The NV12 surface (h * 3 / 2, w) of an I420 surface's samples; buf: what nv12_to_i420 returns for the same layout."""
+    buf = np.asarray(buf, np.uint8).reshape(-1)
+    pitch, c_pitch, u_off, v_off = i420_layout(w, h, pitch, c_pitch, u_off, v_off)
+    out = np.empty((h * 3 // 2, w), np.uint8)
+    out[:h] = buf[:h * pitch].reshape(h, pitch)[:, :w]
+    out[h:, 0::2] = buf[u_off:u_off + (h // 2) * c_pitch].reshape(h // 2, c_pitch)[:, :w // 2]
+    out[h:, 1::2] = buf[v_off:v_off + (h // 2) * c_pitch].reshape(h // 2, c_pitch)[:, :w // 2]
+    return out
+
+
 # ---- long clips rendered on the device (bench.py: more distinct input than the 256 MB Infinity Cache holds) -----------
 def loop_script(seed, n_frames, pan_q8=512, jitter_q8=384, rot_1e5=200):
     """Per-frame camera pose of a CLOSED pan path: n/4 frames right, down, left, up at pan_q8 per frame (the same jitter
