@@ -33,7 +33,8 @@ extern "C" {
  *    vs_stab_set_host_pipeline - Parameters::hostPipeline of the C++ class - not through vs_params_c, whose layout is unchanged.)
  *    Added since without a layout change: vs_batch_create_params (round 4); the pixel formats VS_FMT_BGRA8,
  *    VS_FMT_RGBA8 and VS_FMT_RGB8; VS_FMT_P010 (enum vs_pixfmt16) with vs_op_warp_affine_p010; VS_FMT_I420 (enum
- *    vs_pixfmt_planar) with vs_stab_set_i420_layout, vs_batch_set_i420_layout and vs_op_warp_affine_i420. */
+ *    vs_pixfmt_planar) with vs_stab_set_i420_layout, vs_batch_set_i420_layout and vs_op_warp_affine_i420; VS_FMT_I010 and
+ *    VS_FMT_I012 (enum vs_pixfmt_planar16) with vs_op_warp_affine_i010. */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -96,6 +97,28 @@ typedef enum vs_pixfmt16 {
 typedef enum vs_pixfmt_planar {
     VS_FMT_I420 = 7           /* Y plane (h rows of w), U plane, V plane (h/2 rows of w/2 each) */
 } vs_pixfmt_planar;
+
+/* Planar 4:2:0 with 16-bit samples - `yuv420p10le` / `yuv420p12le`, GStreamer's I420_10LE / I420_12LE: what software decoders of
+ * 10- and 12-bit video emit (dav1d, libde265, FFmpeg's HEVC decoder, libvpx profile 2) -, numbered on in the same `int fmt`.
+ * The planes of I420 with the samples of P010: one little-endian 16-bit word per sample, but the value in the LOW bits.
+ * `stride`, the chroma pitch and the plane offsets are in BYTES; pointers, pitches and offsets must be even (VS_ERR_INVALID_ARG
+ * otherwise).  Packed default layout: chroma pitch = stride / 2 (so `stride` and `out_stride` must be multiples of 4), U starts
+ * h * stride bytes behind the Y pointer, V (h/2) * (chroma pitch) bytes behind U; other layouts - a linesize[1] of its own,
+ * planes apart, V before U - through vs_stab_set_i420_layout / vs_batch_set_i420_layout.  A chroma pitch below w bytes is
+ * VS_ERR_INVALID_ARG.  Definitions:
+ *  - analysis: the gray image is that of the 8-bit plane min(sample >> (bits - 8), 255) of the Y plane (shift 2 for I010, 4 for
+ *    I012), resized as the luma plane of an NV12 frame is.  The saturation says what out-of-range content does: nothing assumes
+ *    that the high bits are zero.  Keypoints, tracks, model, trajectory and warp matrix are bit-identical to those of the NV12 /
+ *    GRAY8 stream of those bytes, and for in-range content to those of the P010 stream that holds sample << (16 - bits);
+ *  - warp: Y as a CV_16UC1 plane under M; U and V each as a CV_16UC1 plane of w/2 x h/2 under the matrix with the translation
+ *    halved in float; INTER_LINEAR, BORDER_CONSTANT 0, the blend of P010 to the letter (S rounded once, half to even).  The warp
+ *    does not depend on the bit depth;
+ *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
+ *    are VS_ERR_UNSUPPORTED; roll correction, AutoZoomCrop, the enhancer and the C++ class do not take these formats. */
+typedef enum vs_pixfmt_planar16 {
+    VS_FMT_I010 = 8,          /* yuv420p10le: Y (h rows of w uint16), U, V (h/2 rows of w/2 uint16 each); value in bits 0..9  */
+    VS_FMT_I012 = 9           /* yuv420p12le: the same planes, value in bits 0..11 */
+} vs_pixfmt_planar16;
 
 /* Stabilizer.cpp:31-38 mapBorderMode() */
 typedef enum vs_border {
@@ -331,7 +354,7 @@ int vs_stab_set_warp_batch(vs_stab* s, int frames);
  * (at most 32 frames per warp launch: a batch of 64 is two launches back to back).
  * Results are bit-identical to frames = 1 and complete after vs_stab_sync(); every push must
  * be given its own d_out until then.  Must be chosen before the first frame (or after
- * vs_stab_clean).  BGR8, GRAY8, NV12, P010 and I420 frames; border padding and crop-and-zoom (BGR8
+ * vs_stab_clean).  BGR8, GRAY8, NV12, P010, I420 and I010 / I012 frames; border padding and crop-and-zoom (BGR8
  * only, like everywhere) run batched too; the "fade" border, the virtual canvas and
  * adaptive smoothing keep the per-frame path (each of their outputs depends on the one
  * before it or on a host decision).  Instances of one device share its HIP streams and
@@ -361,7 +384,8 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
  * pitch of their rows - for the frames given to vs_stab_push_dev in zero-copy or copy-in mode (`in`) and for the device
  * surfaces it fills (`out`), independently.  0 = the default of that field: c_pitch = stride / 2, u_off = h * stride,
  * v_off = u_off + (h/2) * c_pitch (with the u_off and c_pitch in force).  A chroma pitch below w/2 is VS_ERR_INVALID_ARG (here
- * when the geometry is known, else at the next push).  YV12: swap the two offsets.  The frame queue must be empty. */
+ * when the geometry is known, else at the next push).  YV12: swap the two offsets.  The frame queue must be empty.
+ * I010 / I012 surfaces (vs_pixfmt_planar16) take the same call: offsets and pitch in bytes and even, the pitch at least w bytes. */
 int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off,
                             size_t out_c_pitch);
 
@@ -481,6 +505,13 @@ int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_of
                            void* d_dst, size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch,
                            int w, int h, const float* M, int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
                            int border, void* stream);
+/* I010 / I012 surface (vs_pixfmt_planar16): the same three planes with 16-bit samples, one call for either depth (the warp does
+ * not depend on it).  Strides, offsets and frame distances in bytes and even; a default chroma pitch needs a stride that is a
+ * multiple of 4.  The blend is that of vs_op_warp_affine_p010. */
+int vs_op_warp_affine_i010(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch,
+                           void* d_dst, size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch,
+                           int w, int h, const float* M, int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
+                           int border, void* stream);
 /* std::cos / std::sin / std::atan2 on float as the reference calls them (Stabilizer.cpp:662, 902-908, 1689: the host libm's
  * cosf / sinf / atan2f), evaluated by the DEVICE build of the library's restatement: the sum over i in [start, start + count) of
  * a 64-bit mix of (i, bits of f(argument i)) - fn 0 cosf, 1 sinf, 2 atanf: argument i = the float with bit pattern (uint32_t)i;
@@ -511,7 +542,8 @@ int vs_op_trajectory(const vs_params_c* params, int n_streams, const double* con
 /* cv::resize(INTER_LINEAR) + cv::cvtColor(BGR2GRAY) - Stabilizer.cpp:304-305,
  * 448-450.  fmt BGR8 / BGRA8 / RGBA8 / RGB8 (resize per channel, then gray from
  * B, G, R; alpha ignored), GRAY8 / NV12 (luma plane resize), P010 (resize of the luma
- * samples' high bytes; the result is an 8-bit gray image). */
+ * samples' high bytes; the result is an 8-bit gray image), I010 / I012 (resize of
+ * min(sample >> 2, 255) / min(sample >> 4, 255) of the luma samples). */
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt,
                       void* d_dst, size_t dst_stride, int dw, int dh, void* stream);
 /* cv::pyrDown as used inside calcOpticalFlowPyrLK - Stabilizer.cpp:611 */

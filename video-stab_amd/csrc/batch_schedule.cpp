@@ -212,8 +212,8 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
             continue;
         }
         if (fmt_three_planes(s0->fmt)) {
-            // I420: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
-            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st);
+            // I420, I010, I012: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
+            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, fmt_sample_bytes(s0->fmt));
             continue;
         }
         rc = launch_warp_plane(srcs, dsts, m, bp.pad ? bp.prow : s0->src_pitch, bp.pw, bp.ph, bp.crop ? bp.prow : R.stride, bp.pw, bp.ph, s0->cn, maps,
@@ -419,7 +419,7 @@ int step_issue_pre(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan
     {
         StageScope t(g->ref, VS_STAGE_GRAY, pre);
         // NV12, I420: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline); P010: the high bytes
-        // of the Y plane's samples are (the resize kernels read them in place)
+        // of the Y plane's samples are, I010 / I012: their values shifted down to 8 bits (the resize kernels read them in place)
         const int gfmt = fmt_gray_source(s0->fmt);
         const int n_a = (P.ndet > 0 && P.ndet < n) ? P.ndet : n;
         VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs, n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, P.aligned, pre));  // :448-450

@@ -14,6 +14,9 @@
 // cv::resize + cv::cvtColor(BGR2GRAY / BGRA2GRAY) do on the same Mat; the fourth byte is never read into the gray image.
 // P010 luma planes: samples of SS = 2 bytes whose value is the second (high) byte - the gray image of a P010 frame is that of the
 // 8-bit plane of its luma samples' high bytes (sample >> 8), resized as a GRAY8 picture is; the low byte is never read into it.
+// I010 / I012 luma planes: 16-bit samples with the value in the low bits - the gray image is that of the 8-bit plane
+// min(sample >> shift, 255), shift = bits - 8 (2 / 4), resized as a GRAY8 picture is (the *_lo16 kernels: the shift is an argument,
+// one kernel for both depths; the saturation says what a sample beyond its depth does).
 #include "vs_common.h"
 
 namespace vsd {
@@ -270,6 +273,85 @@ __global__ __launch_bounds__(NT) void quarter_gray_kernel(size_t sstride, size_t
     }
 }
 
+// ---- I010 / I012 luma: the 8-bit value of a low-aligned 16-bit sample, then the arithmetic of the two kernels above ----------------
+__device__ __forceinline__ uint32_t lo16_byte(uint32_t sample, int shift) { return min(sample >> shift, 255u); }
+
+// resize_gray_kernel<1, true> over the plane of lo16_byte values (any scale; area2: the exact 2 x 2 decimation).
+__global__ __launch_bounds__(NT) void resize_gray_lo16_kernel(const uint8_t* __restrict__ src_, size_t sstride, int sw, int sh, uint8_t* __restrict__ dst_,
+                                                              size_t dstride, int dw, int dh, double scale_x, double scale_y, int area2,
+                                                              const ImgPair* __restrict__ table, int shift) {
+    const uint8_t* __restrict__ src = table ? static_cast<const uint8_t*>(table[blockIdx.z].src) : src_;
+    uint8_t* __restrict__ dst = table ? static_cast<uint8_t*>(table[blockIdx.z].dst) : dst_;
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int dy = blockIdx.y;
+    if (dx >= dw || dy >= dh) return;
+    auto row = [&](int y) { return reinterpret_cast<const uint16_t*>(src + (size_t)y * sstride); };
+    uint32_t v;
+    if (area2) {
+        const uint16_t *r0 = row(2 * dy) + 2 * dx, *r1 = row(2 * dy + 1) + 2 * dx;
+        v = (lo16_byte(r0[0], shift) + lo16_byte(r0[1], shift) + lo16_byte(r1[0], shift) + lo16_byte(r1[1], shift) + 2u) >> 2;
+    } else {
+        float fx = (float)((dx + 0.5) * scale_x - 0.5);
+        int sx = f_floor(fx);
+        fx -= sx;
+        if (sx < 0) { fx = 0; sx = 0; }
+        bool edge = false;
+        if (sx + 1 >= sw) {
+            edge = true;
+            if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
+        }
+        const int a0 = sat_s16(f_round((1.f - fx) * 2048.f)), a1 = sat_s16(f_round(fx * 2048.f));
+        float fy = (float)((dy + 0.5) * scale_y - 0.5);
+        int sy = f_floor(fy);
+        fy -= sy;
+        const int b0 = sat_s16(f_round((1.f - fy) * 2048.f)), b1 = sat_s16(f_round(fy * 2048.f));
+        int sy0 = sy, sy1 = sy + 1;
+        sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
+        sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
+        const uint16_t *r0 = row(sy0) + sx, *r1 = row(sy1) + sx;
+        int h0, h1;
+        if (!edge) {
+            h0 = (int)lo16_byte(r0[0], shift) * a0 + (int)lo16_byte(r0[1], shift) * a1;
+            h1 = (int)lo16_byte(r1[0], shift) * a0 + (int)lo16_byte(r1[1], shift) * a1;
+        } else {
+            h0 = (int)lo16_byte(r0[0], shift) * 2048;
+            h1 = (int)lo16_byte(r1[0], shift) * 2048;
+        }
+        v = (uint32_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+    }
+    dst[(size_t)dy * dstride + dx] = (uint8_t)v;
+}
+
+// quarter_gray_kernel<2> over the plane of lo16_byte values: the same two 16-byte loads per row; the samples 1, 2 / 5, 6 of a load
+// are the high half of dword x / the low half of dword y, and of z / w.
+__global__ __launch_bounds__(NT) void quarter_gray_lo16_kernel(size_t sstride, size_t dstride, int dw, int dh, const ImgPair* __restrict__ table, int shift) {
+    const uint8_t* __restrict__ src = static_cast<const uint8_t*>(table[blockIdx.z].src);
+    uint8_t* __restrict__ dst = static_cast<uint8_t*>(table[blockIdx.z].dst);
+    const int lane = threadIdx.x & 63, dy = blockIdx.y * QG_ROWS + (threadIdx.x >> 6);
+    const int x4 = (blockIdx.x * 64 + lane) * 4;
+    if (dy >= dh || x4 >= dw) return;
+    const uint8_t* r0 = src + (size_t)(4 * dy + 1) * sstride + (size_t)8 * x4;
+    const uint8_t* r1 = r0 + sstride;
+    const bool vec = (((uintptr_t)src | sstride) & 15) == 0 && (((uintptr_t)dst | dstride) & 3) == 0 && x4 + 3 < dw;      // (the first two: per picture)
+    if (vec) {
+        const uint4 a0 = *reinterpret_cast<const uint4*>(r0), a1 = *reinterpret_cast<const uint4*>(r0 + 16);
+        const uint4 b0 = *reinterpret_cast<const uint4*>(r1), b1 = *reinterpret_cast<const uint4*>(r1 + 16);
+        auto mean = [shift](uint32_t t0, uint32_t t1, uint32_t u0, uint32_t u1) {      // (t0, t1): the dwords that hold samples (0, 1) and (2, 3)
+            return (lo16_byte(t0 >> 16, shift) + lo16_byte(t1 & 0xFFFFu, shift) + lo16_byte(u0 >> 16, shift) + lo16_byte(u1 & 0xFFFFu, shift) + 2u) >> 2;
+        };
+        *reinterpret_cast<uint32_t*>(dst + (size_t)dy * dstride + x4) =
+            mean(a0.x, a0.y, b0.x, b0.y) | mean(a0.z, a0.w, b0.z, b0.w) << 8 | mean(a1.x, a1.y, b1.x, b1.y) << 16 | mean(a1.z, a1.w, b1.z, b1.w) << 24;
+    } else {
+        const uint16_t *s0 = reinterpret_cast<const uint16_t*>(r0), *s1 = reinterpret_cast<const uint16_t*>(r1);
+        for (int i = 0; i < 4 && x4 + i < dw; i++)
+            dst[(size_t)dy * dstride + x4 + i] = (uint8_t)((lo16_byte(s0[4 * i + 1], shift) + lo16_byte(s0[4 * i + 2], shift) + lo16_byte(s1[4 * i + 1], shift) +
+                                                            lo16_byte(s1[4 * i + 2], shift) + 2u) >> 2);
+    }
+}
+
+// The shift of a format whose luma samples carry their value in the low bits (I010: 2, I012: 4); 0 for every other format.
+int lo16_shift(int fmt) { return fmt == VS_FMT_I010 ? 2 : fmt == VS_FMT_I012 ? 4 : 0; }
+
 // Byte of B inside a pixel and the pixel's size of a colour format; false for GRAY8 / NV12 / anything else.
 bool color_layout(int fmt, int* bi, int* ps) {
     switch (fmt) {
@@ -314,7 +396,7 @@ int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, 
     int bi = 0, ps = 1;
     const bool color = color_layout(fmt, &bi, &ps);
     if (!d_pairs || items < 1 || items > 65535 || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 ||
-        (!color && fmt != VS_FMT_GRAY8 && fmt != VS_FMT_P010)) {
+        (!color && fmt != VS_FMT_GRAY8 && fmt != VS_FMT_P010 && !lo16_shift(fmt))) {
         set_last_error("resize_gray_batch: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
@@ -341,12 +423,16 @@ int launch_resize_gray_batch(const ImgPair* d_pairs, int items, size_t sstride, 
         }
     } else if (!color && sw == 4 * dw && sh == 4 * dh) {
         dim3 grid((dw + 255) / 256, (dh + QG_ROWS - 1) / QG_ROWS, items);
-        if (fmt == VS_FMT_P010) hipLaunchKernelGGL(quarter_gray_kernel<2>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
+        if (lo16_shift(fmt)) hipLaunchKernelGGL(quarter_gray_lo16_kernel, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs, lo16_shift(fmt));
+        else if (fmt == VS_FMT_P010) hipLaunchKernelGGL(quarter_gray_kernel<2>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
         else hipLaunchKernelGGL(quarter_gray_kernel<1>, grid, dim3(NT), 0, st, sstride, dstride, dw, dh, d_pairs);
     } else {
         dim3 grid((dw + NT - 1) / NT, dh, items);
         if (color)
             launch_resize_color(bi, ps, grid, np, sstride, sw, sh, nd, dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, d_pairs, st);
+        else if (lo16_shift(fmt))
+            hipLaunchKernelGGL(resize_gray_lo16_kernel, grid, dim3(NT), 0, st, np, sstride, sw, sh, nd, dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0,
+                               d_pairs, lo16_shift(fmt));
         else if (fmt == VS_FMT_P010)
             hipLaunchKernelGGL((resize_gray_kernel<1, true, 0, 2>), grid, dim3(NT), 0, st, np, sstride, sw, sh, nd, dstride, dw, dh,
                                scale_x, scale_y, area2 ? 1 : 0, d_pairs);
@@ -363,12 +449,12 @@ int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int
     int bi = 0, ps = 1;
     const bool color = color_layout(fmt, &bi, &ps);
     if (!d_src || !d_dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dh > 65535 ||
-        (!color && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8 && fmt != VS_FMT_P010)) {
+        (!color && fmt != VS_FMT_NV12 && fmt != VS_FMT_GRAY8 && fmt != VS_FMT_P010 && !lo16_shift(fmt))) {
         set_last_error("resize_gray: invalid argument");
         return VS_ERR_INVALID_ARG;
     }
-    if (fmt == VS_FMT_P010 && (((uintptr_t)d_src | sstride) & 1)) {
-        set_last_error("resize_gray: P010 pointers and pitches must be even");
+    if ((fmt == VS_FMT_P010 || lo16_shift(fmt)) && (((uintptr_t)d_src | sstride) & 1)) {
+        set_last_error("resize_gray: P010 / I010 / I012 pointers and pitches must be even");
         return VS_ERR_INVALID_ARG;
     }
     // cv::resize: scale = 1/(dsize/ssize); INTER_LINEAR with an exact 2x2
@@ -388,6 +474,9 @@ int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int
         if (color)
             launch_resize_color(bi, ps, grid, d_src, sstride, sw, sh, d_dst, dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0,
                                 (const ImgPair*)nullptr, st);
+        else if (lo16_shift(fmt))
+            hipLaunchKernelGGL(resize_gray_lo16_kernel, grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst, dstride, dw, dh, scale_x, scale_y,
+                               area2 ? 1 : 0, (const ImgPair*)nullptr, lo16_shift(fmt));
         else if (fmt == VS_FMT_P010)
             hipLaunchKernelGGL((resize_gray_kernel<1, true, 0, 2>), grid, dim3(NT), 0, st, d_src, sstride, sw, sh, d_dst,
                                dstride, dw, dh, scale_x, scale_y, area2 ? 1 : 0, (const ImgPair*)nullptr);

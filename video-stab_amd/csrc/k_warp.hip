@@ -1398,10 +1398,13 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
 // Arguments: 14 dwords - what gfx950 preloads into scalar registers at wave launch - with source and destination geometry in
 // one dword (they are equal) and the plane distances as 32-bit values (the launcher sends surfaces whose V - U does not fit to
 // the per-plane kernels).  mtpf = ceil(2^32 / tiles per frame), mgx1 / mgx2 likewise for the tile columns of Y and of U / V.
-template <int BORDER>
+// SB = 2: I010 / I012 surfaces - the same sequence, grid order, table blocks and arguments; three planes of 16-bit samples
+// (PlaneCfg<1, 2>: tiles of 128 x 32 pixels, the staged box of the P010 luma plane).  Pitches, V - U and the alignment flags stay
+// in bytes: plane_tile adds the plane distances to byte pointers.
+template <int BORDER, int SB = 1>
 __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
                                                        uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
-    typedef PlaneCfg<1> P;
+    typedef PlaneCfg<1, SB> P;
     __shared__ __attribute__((aligned(16))) uint8_t tile[P::ROWS * P::PB];
     __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
     __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];
@@ -1441,7 +1444,7 @@ __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_s
     }
     const TabLayout L = tab_layout(c.dw, c.dh);
     const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
-    plane_tile<1, BORDER>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
+    plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
 }
 
 // Ints of table workspace per frame of dw x dh (see warp_tables_kernel).
@@ -1631,28 +1634,36 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
 // table, then the chroma table whose records name the U planes; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  Returns
 // VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420Layout& sl, const I420Layout& dl, int w, int h, const int32_t* d_tabs,
-                int border, hipStream_t st) {
-    const int thp = PlaneCfg<1>::THP;
+                int border, hipStream_t st, int sb = 1) {
+    // (sb = 2, I010 / I012: tiles of half the rows; no BORDER_REPLICATE instance, as for P010)
+    if (sb == 2 && border != VS_BORDER_BLACK) return VS_ERR_UNSUPPORTED;
+    const int thp = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP;
     const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp - 1) / thp, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + thp - 1) / thp;
     const unsigned long long tpf = gx1 * gy1 + 2 * gx2 * gy2, total = tpf * (unsigned long long)n;
     const long long svu = (long long)sl.v - (long long)sl.u, dvu = (long long)dl.v - (long long)dl.u;
     if (w >= 65536 || h >= 65536 || sl.pitch >= (1ull << 24) || dl.pitch >= (1ull << 24) || sl.cpitch >= (1ull << 24) || dl.cpitch >= (1ull << 24) ||
         n >= 65536 || total * std::max(tpf, std::max(gx1, gx2)) >= (1ull << 31) || svu != (int32_t)svu || dvu != (int32_t)dvu)
         return VS_ERR_UNSUPPORTED;
-    // bit 0 / 1: luma source / destination 4-byte aligned; bit 2 / 3: both chroma planes (pointers and pitch)
+    // bit 0 / 1: luma source / destination aligned - 4 bytes for the staging loads, a lane's four pixels (4 bytes; 16-bit samples: 8)
+    // for the stores; bit 2 / 3: both chroma planes (pointers and pitch)
+    const size_t a_s = 4, a_d = sb == 2 ? 8 : 4;
     uint32_t al = 0xFu;
-    if (sl.pitch % 4) al &= ~1u;
-    if (dl.pitch % 4) al &= ~2u;
-    if (sl.cpitch % 4 || sl.u % 4 || sl.v % 4) al &= ~4u;
-    if (dl.cpitch % 4 || dl.u % 4 || dl.v % 4) al &= ~8u;
+    if (sl.pitch % a_s) al &= ~1u;
+    if (dl.pitch % a_d) al &= ~2u;
+    if (sl.cpitch % a_s || sl.u % a_s || sl.v % a_s) al &= ~4u;
+    if (dl.cpitch % a_d || dl.u % a_d || dl.v % a_d) al &= ~8u;
     for (int i = 0; i < n; i++) {
-        if ((uintptr_t)ys[i] % 4) al &= ~5u;
-        if ((uintptr_t)yd[i] % 4) al &= ~10u;
+        if ((uintptr_t)ys[i] % a_s) al &= ~5u;
+        if ((uintptr_t)yd[i] % a_d) al &= ~10u;
     }
     const uint32_t flags = (al & 3u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    if (border == VS_BORDER_REPLICATE)
+    if (sb == 2)
+        hipLaunchKernelGGL((warp_i420_kernel<VS_BORDER_BLACK, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
+                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
+                           (int32_t)dvu);
+    else if (border == VS_BORDER_REPLICATE)
         hipLaunchKernelGGL(warp_i420_kernel<VS_BORDER_REPLICATE>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
                            (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
                            (int32_t)dvu);
@@ -1757,12 +1768,19 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
 // the NV12 table launch; else one table launch per plane -, then all three planes in ONE grid.  A launch without tables (a caller's
 // tables exist for launches of WARP_TAB_MIN surfaces and more only; the scratch tables serve any number), or one whose geometry is
 // outside what warp_i420_kernel packs, goes plane by plane through the general kernels: V from the maps, without a table.
+// sb = 2: I010 / I012 surfaces - the layouts stay in bytes; a launch with BORDER_REPLICATE goes plane by plane.
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout sl, I420Layout dl, int w, int h, WarpMaps maps, int border,
-                     WarpTabs tabs, hipStream_t st) {
-    if (n < 1 || !ys || !yd || w < 2 || h < 2 || (w & 1) || (h & 1) || bad_args(ys[0], yd[0], maps.m, sl.pitch, w, h, dl.pitch, w, h, 1, n) ||
-        sl.cpitch < (size_t)(w / 2) || dl.cpitch < (size_t)(w / 2) || !sl.u || !sl.v || !dl.u || !dl.v || sl.u == sl.v || dl.u == dl.v ||
+                     WarpTabs tabs, hipStream_t st, int sb) {
+    if (n < 1 || !ys || !yd || w < 2 || h < 2 || (w & 1) || (h & 1) || (sb != 1 && sb != 2) ||
+        bad_args(ys[0], yd[0], maps.m, sl.pitch, w, h, dl.pitch, w, h, sb, n) ||
+        sl.cpitch < (size_t)(w / 2) * sb || dl.cpitch < (size_t)(w / 2) * sb || !sl.u || !sl.v || !dl.u || !dl.v || sl.u == sl.v || dl.u == dl.v ||
         bad_call(ys, yd, n, border, tabs)) {
-        set_last_error("warp_i420: invalid argument (w and h must be even, chroma pitches at least w / 2)");
+        set_last_error(sb == 2 ? "warp_i010: invalid argument (w and h must be even, chroma pitches at least w bytes)"
+                               : "warp_i420: invalid argument (w and h must be even, chroma pitches at least w / 2)");
+        return VS_ERR_INVALID_ARG;
+    }
+    if (sb == 2 && (odd16(ys, yd, n, sl.pitch, dl.pitch) || ((sl.cpitch | sl.u | sl.v | dl.cpitch | dl.u | dl.v) & 1))) {
+        set_last_error("warp_i010: I010 / I012 pointers, pitches and plane offsets must be even");
         return VS_ERR_INVALID_ARG;
     }
     const int tab_min = tabs.kind == WarpTabs::SCRATCH ? 1 : WARP_TAB_MIN;
@@ -1780,7 +1798,7 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
         const WarpMaps my = maps_from(maps, b0), mu = maps_from(muv, b0);
         auto plane = [&](size_t so, size_t d_o, size_t sp, size_t dp, int pw, int ph, WarpMaps m, int32_t* tab, int what) -> int {
             for (int i = 0; i < nb; i++) { ps[i] = ys[b0 + i] + so; pd[i] = yd[b0 + i] + d_o; }
-            return plane_launch(ps, pd, nb, sp, pw, ph, dp, pw, ph, 1, m, border, tab, block, what, st);
+            return plane_launch(ps, pd, nb, sp, pw, ph, dp, pw, ph, 1, m, border, tab, block, what, st, sb);
         };
         if (T && tabs.what != VS_WARP_ONLY) {
             if (maps.host && nb <= NVT_MAX) {
@@ -1799,7 +1817,7 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
             }
         }
         if (tabs.what == VS_WARP_TABLES_ONLY) continue;
-        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st) : VS_ERR_UNSUPPORTED;
+        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st, sb) : VS_ERR_UNSUPPORTED;
         if (one != VS_ERR_UNSUPPORTED) {
             VS_TRY(one);
             continue;

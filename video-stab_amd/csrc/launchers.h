@@ -60,8 +60,9 @@ inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, s
 // Launches with tables warp the three planes of their surfaces in ONE grid (warp_i420_kernel); the tables are an NV12 surface's
 // (nv12_tab_ints per frame: luma table, then one chroma table whose pointer records name the U planes), the maps as for NV12
 // (m: luma, m + 6: chroma).  A call with the scratch tables builds them for any number of surfaces.
+// sample_bytes = 2: I010 / I012 surfaces - the same planes with 16-bit samples; layouts in bytes, pointers, pitches and offsets even.
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout src, I420Layout dst, int w, int h, WarpMaps maps, int border,
-                     WarpTabs tabs, hipStream_t st);
+                     WarpTabs tabs, hipStream_t st, int sample_bytes = 1);
 
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,

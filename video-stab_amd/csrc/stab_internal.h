@@ -61,7 +61,7 @@ struct vs_stab {
     size_t row_bytes = 0, frame_bytes = 0;
     size_t src_pitch = 0;               // row pitch of the frames the pipeline reads: row_bytes (queue ring) or the caller's (zero-copy)
     size_t in_uv_off = 0, out_uv_off = 0;   // NV12 / P010 surfaces of the device entry points: UV plane offset in bytes, 0 = h * pitch
-    // I420 surfaces of the device entry points: U / V plane offsets and chroma pitch in bytes, 0 = the packed default of the field
+    // I420 / I010 / I012 surfaces of the device entry points: U / V plane offsets and chroma pitch in bytes, 0 = the packed default of the field
     size_t in_u_off = 0, in_v_off = 0, in_c_pitch = 0, out_u_off = 0, out_v_off = 0, out_c_pitch = 0;
     int rows_total = 0;
     int aw = 960, ah = 540;
@@ -261,10 +261,12 @@ inline void fill_lk_levels(const vs_stab* s, int pv, int c, LKLevel* L) {
 }
 
 // The two questions the host asks of a frame format beyond its first plane's bytes per pixel (s->cn): does an interleaved chroma
-// plane of half the rows follow the luma plane (NV12, P010), and how many bytes is a sample (2: P010).
+// plane of half the rows follow the luma plane (NV12, P010), and how many bytes is a sample (2: P010, I010, I012).
 inline bool fmt_two_planes(int fmt) { return fmt == VS_FMT_NV12 || fmt == VS_FMT_P010; }
-inline int fmt_sample_bytes(int fmt) { return fmt == VS_FMT_P010 ? 2 : 1; }
-inline int fmt_rows(int fmt, int h) { return fmt_two_planes(fmt) || fmt == VS_FMT_I420 ? h * 3 / 2 : h; }     // rows of `pitch` bytes of a whole (packed) frame
+inline bool fmt_planar16(int fmt) { return fmt == VS_FMT_I010 || fmt == VS_FMT_I012; }
+inline int fmt_sample_bytes(int fmt) { return fmt == VS_FMT_P010 || fmt_planar16(fmt) ? 2 : 1; }
+inline bool fmt_three_planes(int fmt);
+inline int fmt_rows(int fmt, int h) { return fmt_two_planes(fmt) || fmt_three_planes(fmt) ? h * 3 / 2 : h; }     // rows of `pitch` bytes of a whole (packed) frame
 
 // NV12 / P010: where the interleaved UV plane of a queued frame / of an output surface starts
 inline size_t src_uv(const vs_stab* s) { return (s->zero_copy && s->in_uv_off) ? s->in_uv_off : (size_t)s->h * s->src_pitch; }
@@ -274,8 +276,8 @@ inline size_t dst_uv(const vs_stab* s, const uint8_t* d_out, size_t out_stride) 
 
 // I420: three planes - Y, then U and V of half the size, one channel each, with a pitch of their own.  A question of its own (an
 // NV12 / P010 frame's chroma part is ONE interleaved plane at the luma pitch: fmt_two_planes), though a whole frame has the same
-// number of bytes.
-inline bool fmt_three_planes(int fmt) { return fmt == VS_FMT_I420; }
+// number of bytes.  I010 / I012: the same three planes with 16-bit samples; offsets and pitches stay in bytes.
+inline bool fmt_three_planes(int fmt) { return fmt == VS_FMT_I420 || fmt_planar16(fmt); }
 // ... where the planes of a queued frame / of an output surface lie.  The queue ring and the staging of the host entry points hold
 // the packed default layout; the caller's layout (vs_stab_set_i420_layout) applies to zero-copy input and to device outputs.
 inline I420Layout src_i420(const vs_stab* s) {
@@ -284,7 +286,8 @@ inline I420Layout src_i420(const vs_stab* s) {
 inline I420Layout dst_i420(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
     return d_out != s->d_out ? i420_layout(out_stride, s->h, s->out_u_off, s->out_v_off, s->out_c_pitch) : i420_layout(out_stride, s->h, 0, 0, 0);
 }
-// The format the gray kernels are asked for: the Y plane of an NV12 or I420 frame is a GRAY8 image.
+// The format the gray kernels are asked for: the Y plane of an NV12 or I420 frame is a GRAY8 image (P010, I010 and I012 name the
+// byte the kernels take from a 16-bit luma sample).
 inline int fmt_gray_source(int fmt) { return fmt == VS_FMT_NV12 || fmt == VS_FMT_I420 ? VS_FMT_GRAY8 : fmt; }
 
 // A ring slot goes back to the free list behind the work on `st` that reads it.  A slot whose event cannot be recorded stays out

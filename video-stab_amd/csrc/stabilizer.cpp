@@ -40,13 +40,13 @@ using namespace vsd;
 
 namespace {
 
-// Bytes per pixel of a frame format's first plane (NV12 / GRAY8 / I420: the luma byte; P010: the 16-bit luma sample); 0 for an unknown format.
+// Bytes per pixel of a frame format's first plane (NV12 / GRAY8 / I420: the luma byte; P010 / I010 / I012: the 16-bit luma sample); 0 for an unknown format.
 int fmt_cn(int fmt) {
     switch (fmt) {
         case VS_FMT_BGR8: case VS_FMT_RGB8: return 3;
         case VS_FMT_BGRA8: case VS_FMT_RGBA8: return 4;
         case VS_FMT_NV12: case VS_FMT_GRAY8: case VS_FMT_I420: return 1;
-        case VS_FMT_P010: return 2;
+        case VS_FMT_P010: case VS_FMT_I010: case VS_FMT_I012: return 2;
         default: return 0;
     }
 }
@@ -130,7 +130,8 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     // (the reference's cvtColor(BGR2GRAY) of the canvas, Stabilizer.cpp:2225, throws on anything but three channels)
     if (canvas_on(s) && fmt != VS_FMT_BGR8)
         return vs_obj_fail(s, VS_ERR_UNSUPPORTED, fmt == VS_FMT_P010 ? "enableVirtualCanvas needs a BGR8 stream (not P010)"
-                                                  : fmt == VS_FMT_I420 ? "enableVirtualCanvas needs a BGR8 stream (not I420)" : "enableVirtualCanvas needs a BGR8 stream");
+                                                  : fmt == VS_FMT_I420 ? "enableVirtualCanvas needs a BGR8 stream (not I420)"
+                                                  : fmt_planar16(fmt) ? "enableVirtualCanvas needs a BGR8 stream (not I010 / I012)" : "enableVirtualCanvas needs a BGR8 stream");
     // buildOpticalFlowPyramid: levels that fit the window
     {
         int sw = s->aw, sh = s->ah;
@@ -244,10 +245,10 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
 }
 
 
-// The three planes of an I420 frame from one layout to another.
+// The three planes of an I420 / I010 / I012 frame from one layout to another: rows of w and w / 2 samples.
 int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src, const I420Layout& sl, hipMemcpyKind kind, hipStream_t st) {
-    const size_t cw = (size_t)s->w / 2;
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, s->w, s->h, kind, st));
+    const size_t cw = s->row_bytes / 2;
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, s->row_bytes, s->h, kind, st));
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.u, dl.cpitch, src + sl.u, sl.cpitch, cw, s->h / 2, kind, st));
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.v, dl.cpitch, src + sl.v, sl.cpitch, cw, s->h / 2, kind, st));
     return VS_OK;
@@ -478,7 +479,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
         StageScope t(s, VS_STAGE_WARP, st);
         rc = launch_warp_i420(&frame, &d_out, 1, src_i420(s), dst_i420(s, d_out, out_stride), s->w, s->h, WarpMaps{s->d_Minv, 12, false}, VS_BORDER_BLACK,
-                              WarpTabs{WarpTabs::SCRATCH}, st);
+                              WarpTabs{WarpTabs::SCRATCH}, st, fmt_sample_bytes(s->fmt));
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
         const size_t prow = bp.prow, nb = prow * bh;
@@ -660,6 +661,10 @@ int take_slot(vs_stab* s, int* slot) {
     return VS_OK;
 }
 
+// I010 / I012: a pitch in bytes holds 16-bit samples, and with the default chroma pitch - half of it - so does that.
+bool planar16_bad_pitch(size_t pitch, size_t c_pitch) { return (pitch & 1) || (!c_pitch && (pitch & 3)); }
+const char* const PLANAR16_OUT = "I010 / I012 need even surface pointers and pitches (16-bit samples; a default chroma pitch is half the pitch)";
+
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
     const int cn = fmt_cn(fmt);
     if (w <= 0 || h <= 0 || cn == 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: bad geometry/format");
@@ -675,7 +680,16 @@ int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
         if (s->p.border_size > 0)
             return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not I420");
     }
-    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8 / P010 / I420)
+    if (fmt_planar16(fmt)) {
+        if ((w & 1) || (h & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012 need even w,h");
+        if (planar16_bad_pitch(stride, s->in_c_pitch) || ((s->in_u_off | s->in_v_off | s->in_c_pitch | s->out_u_off | s->out_v_off | s->out_c_pitch) & 1))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012 need even pitches and plane offsets (16-bit samples; a default chroma pitch is half the pitch)");
+        if ((s->in_c_pitch && s->in_c_pitch < (size_t)w) || (s->out_c_pitch && s->out_c_pitch < (size_t)w))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012: the chroma pitch must be at least w bytes");
+        if (s->p.border_size > 0)
+            return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not I010 / I012");
+    }
+    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8 / P010 / I420 / I010 / I012)
     if (fmt == VS_FMT_P010 && s->p.border_size > 0)
         return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not P010");
     if (cn == 1 && s->p.border_size > 0) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need a colour format (BGR8, BGRA8, RGBA8, RGB8)");
@@ -867,6 +881,8 @@ int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
     if (fmt == VS_FMT_I420 && (out_stride & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+    if (fmt_planar16(fmt) && ((((uintptr_t)d_data | (uintptr_t)d_out) & 1) || planar16_bad_pitch(out_stride, s->out_c_pitch)))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
     if (s->zero_copy) {
         // the frame is read where it is: it must stay valid and unchanged until its own result has been produced
         // one pitch for all frames in flight (the batched launches take it once): it may change when nothing is queued
@@ -907,6 +923,8 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
     if (s->fmt == VS_FMT_I420 && (out_stride & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+    if (fmt_planar16(s->fmt) && (((uintptr_t)d_out & 1) || planar16_bad_pitch(out_stride, d_out != s->d_out ? s->out_c_pitch : 0)))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
@@ -934,6 +952,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
     // always a full-size one - pass-through frames only come out of vs_stab_flush's synchronous part)
     if (have_prev && (!out || out_stride < orow)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
     if (fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+    if (fmt_planar16(fmt) && (out_stride & 3)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
     for (auto& hld : s->d_hold)
         if (!hld) VS_OBJ_HIP(s, hipMalloc((void**)&hld, s->out_bytes));
     // A copy to or from PAGEABLE memory (the frames of a cv::Mat) keeps its caller inside hipMemcpy for the whole transfer -
@@ -1008,6 +1027,8 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: host frames cannot join a queue of pitched zero-copy surfaces");
     if (fmt == VS_FMT_I420 && out && (out_stride & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+    // (host frames hold the packed default layout at their pitch: the chroma pitch is half of it)
+    if (fmt_planar16(fmt) && ((stride & 3) || (out && (out_stride & 3)))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
     if (s->host_pipe && !s->batch_active) return push_host_pipelined(s, data, w, h, stride, fmt, out, out_stride, produced);
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
@@ -1053,6 +1074,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
         const int orows = fmt_rows(s->fmt, s->hold_h);
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
         if (s->fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+        if (fmt_planar16(s->fmt) && (out_stride & 3)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
         VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orows, s->st_warp));
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
         s->hold_valid = false;
@@ -1066,6 +1088,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     const size_t orow = (size_t)ow * s->cn;
     if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
     if (s->fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+    if (fmt_planar16(s->fmt) && (out_stride & 3)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, flush_warps(s));
     int rc = flush_dev_impl(s, s->d_out, orow, produced, false);
@@ -1136,7 +1159,7 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
     return VS_OK;
 }
 
-// I420 / YV12 surfaces of the device entry points: where the U and V planes start behind the Y pointer and the pitch of their rows,
+// I420 / YV12 (and I010 / I012) surfaces of the device entry points: where the U and V planes start behind the Y pointer and the pitch of their rows,
 // for the frames pushed (`in`: zero-copy and copy-in alike) and for the surfaces filled (`out`).  0 = the packed default per field.
 int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off, size_t out_c_pitch) {
     if (!s) return VS_ERR_INVALID_ARG;
@@ -1144,6 +1167,12 @@ int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: the frame queue must be empty");
     if (s->allocated && s->fmt == VS_FMT_I420 && ((in_c_pitch && in_c_pitch < (size_t)s->w / 2) || (out_c_pitch && out_c_pitch < (size_t)s->w / 2)))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I420: the chroma pitch must be at least w / 2");
+    if (s->allocated && fmt_planar16(s->fmt)) {
+        if ((in_u_off | in_v_off | in_c_pitch | out_u_off | out_v_off | out_c_pitch) & 1)
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I010 / I012 need even plane offsets and pitches (16-bit samples)");
+        if ((in_c_pitch && in_c_pitch < (size_t)s->w) || (out_c_pitch && out_c_pitch < (size_t)s->w))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I010 / I012: the chroma pitch must be at least w bytes");
+    }
     s->in_u_off = in_u_off; s->in_v_off = in_v_off; s->in_c_pitch = in_c_pitch;
     s->out_u_off = out_u_off; s->out_v_off = out_v_off; s->out_c_pitch = out_c_pitch;
     return VS_OK;

@@ -253,15 +253,22 @@ int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst, si
     return warp_affine_two_planes(d_src, src_stride, d_dst, dst_stride, w, h, M, batch, src_frame_bytes, dst_frame_bytes, stream, 2);
 }
 
-// I420 / YV12: luma under the full matrix; U and V - one-channel planes of half the size - under the matrix with the halved
-// translation.  0 = the packed default of a layout field.
-int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst, size_t dst_stride,
-                           size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch, size_t src_frame_bytes,
-                           size_t dst_frame_bytes, int border, void* stream) {
+// I420 / YV12 (sample_bytes 1) and I010 / I012 (2): luma under the full matrix; U and V - one-channel planes of half the size -
+// under the matrix with the halved translation.  0 = the packed default of a layout field; everything in bytes.
+static int warp_affine_three_planes(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst,
+                                    size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch,
+                                    size_t src_frame_bytes, size_t dst_frame_bytes, int border, void* stream, int sample_bytes) {
     VS_TRY(ensure_device());
-    if (!d_src || !d_dst || !M || batch <= 0 || w < 2 || h < 2 || (w & 1) || (h & 1) || (!src_c_pitch && (src_stride & 1)) ||
-        (!dst_c_pitch && (dst_stride & 1))) {
-        set_last_error("warp_affine_i420: invalid argument (w, h and, for the default chroma pitch, the strides must be even)");
+    // (the default chroma pitch is half the stride, and holds whole samples)
+    const size_t half = 2 * (size_t)sample_bytes - 1;
+    if (!d_src || !d_dst || !M || batch <= 0 || w < 2 || h < 2 || (w & 1) || (h & 1) || (!src_c_pitch && (src_stride & half)) ||
+        (!dst_c_pitch && (dst_stride & half))) {
+        set_last_error(sample_bytes == 2 ? "warp_affine_i010: invalid argument (w and h must be even and, for the default chroma pitch, the strides multiples of 4)"
+                                         : "warp_affine_i420: invalid argument (w, h and, for the default chroma pitch, the strides must be even)");
+        return VS_ERR_INVALID_ARG;
+    }
+    if (sample_bytes == 2 && ((src_frame_bytes | dst_frame_bytes) & 1)) {
+        set_last_error("warp_affine_i010: frame distances must be even (16-bit samples)");
         return VS_ERR_INVALID_ARG;
     }
     std::vector<double> Minv(12 * (size_t)batch);
@@ -275,7 +282,21 @@ int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_of
     const auto ys = frame_list((const uint8_t*)d_src, src_frame_bytes, batch);
     const auto yd = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch);
     return launch_warp_i420(ys.data(), yd.data(), batch, sl, dl, w, h, WarpMaps{Minv.data(), 12, true}, border, WarpTabs{WarpTabs::SCRATCH},
-                            (hipStream_t)stream);
+                            (hipStream_t)stream, sample_bytes);
+}
+
+int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst, size_t dst_stride,
+                           size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch, size_t src_frame_bytes,
+                           size_t dst_frame_bytes, int border, void* stream) {
+    return warp_affine_three_planes(d_src, src_stride, src_u_off, src_v_off, src_c_pitch, d_dst, dst_stride, dst_u_off, dst_v_off, dst_c_pitch, w, h, M,
+                                    batch, src_frame_bytes, dst_frame_bytes, border, stream, 1);
+}
+
+int vs_op_warp_affine_i010(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst, size_t dst_stride,
+                           size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch, size_t src_frame_bytes,
+                           size_t dst_frame_bytes, int border, void* stream) {
+    return warp_affine_three_planes(d_src, src_stride, src_u_off, src_v_off, src_c_pitch, d_dst, dst_stride, dst_u_off, dst_v_off, dst_c_pitch, w, h, M,
+                                    batch, src_frame_bytes, dst_frame_bytes, border, stream, 2);
 }
 
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt, void* d_dst,

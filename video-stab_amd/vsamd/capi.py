@@ -28,17 +28,22 @@ FMT_SAMPLE_BYTES = {FMT_P010: 2}
 # planar 4:2:0 (vs_pixfmt_planar).  A packed I420 frame is a (h * 3 / 2, w) uint8 array: h rows of Y, then the U plane and the V
 # plane, h / 2 rows of w / 2 bytes each (synth.nv12_to_i420).  YV12 and padded chroma rows are layouts of it (set_i420_layout).
 FMT_I420 = 7
+# planar 4:2:0 with 16-bit samples, the value in the low bits (vs_pixfmt_planar16: yuv420p10le / yuv420p12le).  A packed frame is a
+# (h * 3 / 2, w) uint16 array laid out as an I420 frame is (synth.p010_to_i010); other layouts through set_i420_layout, in bytes.
+FMT_I010, FMT_I012 = 8, 9
 
 
 def fmt_px_bytes(fmt):
     """Bytes per pixel of a format's (first) plane."""
     if fmt == FMT_I420:
         return 1
+    if fmt in (FMT_I010, FMT_I012):
+        return 2
     return FMT_SAMPLE_BYTES[fmt] if fmt in FMT_SAMPLE_BYTES else FMT_CHANNELS[fmt]
 
 
 def fmt_dtype(fmt):
-    return np.uint16 if FMT_SAMPLE_BYTES.get(fmt) == 2 else np.uint8
+    return np.uint16 if fmt_px_bytes(fmt) == 2 and fmt not in FMT_CHANNELS else np.uint8
 
 
 def fmt_two_planes(fmt):
@@ -47,7 +52,7 @@ def fmt_two_planes(fmt):
 
 def fmt_420(fmt):
     """A frame array of this format has h * 3 / 2 rows: h of luma, h / 2 of subsampled chroma."""
-    return fmt_two_planes(fmt) or fmt == FMT_I420
+    return fmt_two_planes(fmt) or fmt in (FMT_I420, FMT_I010, FMT_I012)
 
 
 BORDER_BLACK, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP, BORDER_FADE = range(6)
@@ -283,6 +288,7 @@ class VsLib:
                                              C.c_size_t, C.c_size_t, vp]
         L.vs_op_warp_affine_i420.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                              C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, vp]
+        L.vs_op_warp_affine_i010.argtypes = L.vs_op_warp_affine_i420.argtypes
         L.vs_op_resize_gray.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp]
         L.vs_op_pyr_down.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, vp]
         L.vs_op_scharr.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, vp]
@@ -462,6 +468,22 @@ class VsLib:
             self.check(self.lib.vs_op_warp_affine_i420(d_in.ptr, w, 0, 0, 0, d_out.ptr, w, 0, 0, 0, w, h, _p(M, f32p), n, fb, fb, border, None))
             self.sync()
             return d_out.download(img.shape, np.uint8)
+        finally:
+            d_in.free(); d_out.free()
+
+    def warp_affine_i010(self, img, w, h, M, border=BORDER_BLACK):
+        """img: one packed I010 / I012 surface (h * 3 / 2 rows of w uint16: Y, U plane, V plane) and one matrix, or a stack of n
+        surfaces and n matrices.  One call for both depths: the warp does not depend on the depth."""
+        img = np.ascontiguousarray(img, np.uint16)
+        M = np.ascontiguousarray(M, np.float32).reshape(-1, 6)
+        n = M.shape[0]
+        fb = img.nbytes // n
+        d_in = DevBuf.from_array(self, img)
+        d_out = DevBuf(self, img.nbytes)
+        try:
+            self.check(self.lib.vs_op_warp_affine_i010(d_in.ptr, 2 * w, 0, 0, 0, d_out.ptr, 2 * w, 0, 0, 0, w, h, _p(M, f32p), n, fb, fb, border, None))
+            self.sync()
+            return d_out.download(img.shape, np.uint16)
         finally:
             d_in.free(); d_out.free()
 
@@ -1038,7 +1060,8 @@ class Stabilizer:
         self.vs.check(self.lib.vs_stab_set_nv12_layout(self.h, in_uv_offset, out_uv_offset), self.h)
 
     def set_i420_layout(self, in_u_off=0, in_v_off=0, in_c_pitch=0, out_u_off=0, out_v_off=0, out_c_pitch=0):
-        """Plane offsets (bytes behind the Y pointer) and chroma pitch of the I420 surfaces pushed / filled; 0 = packed default."""
+        """Plane offsets (bytes behind the Y pointer) and chroma pitch (bytes) of the I420 / I010 / I012 surfaces pushed / filled;
+        0 = packed default."""
         self.vs.check(self.lib.vs_stab_set_i420_layout(self.h, in_u_off, in_v_off, in_c_pitch, out_u_off, out_v_off, out_c_pitch), self.h)
 
     def set_zero_copy(self, on=True):

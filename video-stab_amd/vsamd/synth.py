@@ -178,6 +178,35 @@ def i420_to_nv12(buf, w, h, pitch=None, c_pitch=None, u_off=None, v_off=None):
     return out
 
 
+def p010_to_i010(surface, w, h, bits=10, pitch=None, c_pitch=None, u_off=None, v_off=None, size=None, fill=0):
+    """The I010 (bits = 10) / I012 (12) surface that holds the samples of one P010 / P012 surface (h * 3 / 2, w) uint16: every sample
+    shifted down to the low bits (sample >> (16 - bits)), U and V de-interleaved.  Packed (no layout given): a (h * 3 / 2, w) uint16
+    array - Y, then the U plane, then the V plane.  With a layout - pitch, c_pitch, u_off, v_off and size in BYTES, even, defaults as
+    i420_layout's at pitch = 2 w -: a flat uint16 buffer of size / 2 words, `fill` wherever no sample lies."""
+    s = np.asarray(surface, np.uint16) >> (16 - bits)
+    packed = not (pitch or c_pitch or u_off or v_off or size)
+    pitch, c_pitch, u_off, v_off = i420_layout(2 * w, h, pitch, c_pitch, u_off, v_off)
+    end = max(h * pitch, u_off + (h // 2) * c_pitch, v_off + (h // 2) * c_pitch)
+    assert not ((pitch | c_pitch | u_off | v_off | (size or 0)) & 1), "16-bit samples: the layout is in even bytes"
+    buf = np.full((size or end) // 2, fill, np.uint16)
+    buf[:h * pitch // 2].reshape(h, pitch // 2)[:, :w] = s[:h]
+    buf[u_off // 2:(u_off + (h // 2) * c_pitch) // 2].reshape(h // 2, c_pitch // 2)[:, :w // 2] = s[h:, 0::2]
+    buf[v_off // 2:(v_off + (h // 2) * c_pitch) // 2].reshape(h // 2, c_pitch // 2)[:, :w // 2] = s[h:, 1::2]
+    return buf.reshape(h * 3 // 2, w) if packed else buf
+
+
+def i010_to_p010(buf, w, h, bits=10, pitch=None, c_pitch=None, u_off=None, v_off=None):
+    """The P010 / P012 surface (h * 3 / 2, w) of an I010 / I012 surface's samples (sample << (16 - bits)); buf: what p010_to_i010
+    returns for the same layout."""
+    buf = np.asarray(buf, np.uint16).reshape(-1)
+    pitch, c_pitch, u_off, v_off = i420_layout(2 * w, h, pitch, c_pitch, u_off, v_off)
+    out = np.empty((h * 3 // 2, w), np.uint16)
+    out[:h] = buf[:h * pitch // 2].reshape(h, pitch // 2)[:, :w]
+    out[h:, 0::2] = buf[u_off // 2:(u_off + (h // 2) * c_pitch) // 2].reshape(h // 2, c_pitch // 2)[:, :w // 2]
+    out[h:, 1::2] = buf[v_off // 2:(v_off + (h // 2) * c_pitch) // 2].reshape(h // 2, c_pitch // 2)[:, :w // 2]
+    return out << (16 - bits)
+
+
 # ---- long clips rendered on the device (bench.py: more distinct input than the 256 MB Infinity Cache holds) -----------
 def loop_script(seed, n_frames, pan_q8=512, jitter_q8=384, rot_1e5=200):
     """Per-frame camera pose of a CLOSED pan path: n/4 frames right, down, left, up at pan_q8 per frame (the same jitter
