@@ -34,7 +34,9 @@ extern "C" {
  *    Added since without a layout change: vs_batch_create_params (round 4); the pixel formats VS_FMT_BGRA8,
  *    VS_FMT_RGBA8 and VS_FMT_RGB8; VS_FMT_P010 (enum vs_pixfmt16) with vs_op_warp_affine_p010; VS_FMT_I420 (enum
  *    vs_pixfmt_planar) with vs_stab_set_i420_layout, vs_batch_set_i420_layout and vs_op_warp_affine_i420; VS_FMT_I010 and
- *    VS_FMT_I012 (enum vs_pixfmt_planar16) with vs_op_warp_affine_i010. */
+ *    VS_FMT_I012 (enum vs_pixfmt_planar16) with vs_op_warp_affine_i010; roll correction and auto zoom/crop on P010 surfaces:
+ *    vs_roll_correct_p010_dev, vs_roll_correct_p010_dev_n, vs_azc_apply_p010_dev, vs_azc_apply_p010_dev_n and
+ *    vs_op_warp_affine16_ex. */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -72,7 +74,21 @@ typedef enum vs_pixfmt {
  *    are 0, each by itself), rounded once, half to even: (S + 511 + ((S >> 10) & 1)) >> 10.  For ten-bit content that is
  *    what OpenCV's float blend gives; for arbitrary 16-bit content it is the definition (docs/opencv_semantics.md);
  *  - everything else follows NV12: the last frame of a flush comes back unwarped; border pad, crop-and-zoom, fade and the
- *    virtual canvas are refused as for NV12. */
+ *    virtual canvas are refused as for NV12.
+ * The two stages around the stabilizer take P010 surfaces too (vs_roll_correct_p010_dev, vs_azc_apply_p010_dev):
+ *  - analysis plane: both analyse the 8-bit plane of the luma samples' high bytes (sample >> 8), the plane the stabilizer analyses.
+ *    Smoothed and detected angle, line counts, content mask, contours, info8 and the crop rectangle are bit-identical to those of
+ *    the NV12 call on the high-byte surface; the mask rule gray > 1 reads (sample >> 8) > 1;
+ *  - roll rotation: the matrix the NV12 path builds (centre, angle; the chroma plane with the translation halved), applied to the
+ *    CV_16UC1 luma plane and the CV_16UC2 chroma plane: INTER_LINEAR, BORDER_REPLICATE (a tap outside the plane takes the nearest
+ *    edge sample, each tap by itself), the coordinate path of 8 bits (AB_BITS = 10, 1/32 px), the blend above: S over the four
+ *    taps, rounded once, half to even;
+ *  - zoom crop-and-scale: the rectangle as found for luma, halved for the chroma plane (x/2, y/2, max(1, w/2), max(1, h/2)); each
+ *    plane scaled to its share of 640 x 360 by the reference's scale matrix; BORDER_CONSTANT 0, the same blend.  On the fall-back
+ *    paths the surface comes back unchanged, all 16 bits;
+ *  - low bits: nothing here assumes that the low six bits are zero either.
+ * Not built: the C++ classes vs::RollCorrection / vs::AutoZoomCrop keep taking 8-bit cv::Mats, and I420 / I010 / I012 surfaces
+ * do not go through these two stages. */
 typedef enum vs_pixfmt16 {
     VS_FMT_P010 = 6           /* Y plane (h rows of w uint16) followed by UV plane (h/2 rows of w/2 uint16 pairs) */
 } vs_pixfmt16;
@@ -610,6 +626,14 @@ int vs_roll_correct_nv12_dev(vs_roll* r, const void* d_surface, int w, int h, si
 /* n surfaces of one layout, in call order (n calls of the above in one) */
 int vs_roll_correct_nv12_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                                size_t pitch, size_t uv_offset, size_t out_pitch, size_t out_uv_offset);
+/* The same for P010 surfaces (vs_pixfmt16: the definitions are there).  pitch, out_pitch >= 2 * w; pointers, pitches and offsets
+ * in bytes and even (VS_ERR_INVALID_ARG otherwise).  Batches of eight, the worker threads, VS_ROLL_WORKERS, vs_roll_sync and
+ * vs_roll_get_state as for NV12.  One object may receive NV12 and P010 calls: a change of sample size closes the pending batch,
+ * exactly as a change of geometry does, and the smoothed angle - per-object state - carries across. */
+int vs_roll_correct_p010_dev(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset,
+                             void* d_out, size_t out_pitch, size_t out_uv_offset);
+int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
+                               size_t pitch, size_t uv_offset, size_t out_pitch, size_t out_uv_offset);
 /* smoothed angle (sSmoothedAngle), the angle detected on the last frame, lines found / used */
 int vs_roll_get_state(const vs_roll* r, double* smoothed_deg, double* detected_deg,
                       int* n_lines, int* n_used);
@@ -626,6 +650,12 @@ int vs_op_hough_lines(const void* d_edges, size_t stride, int w, int h, float rh
 int vs_op_warp_affine_ex(const void* d_src, size_t src_stride, int sw, int sh, void* d_dst,
                          size_t dst_stride, int dw, int dh, int cn, const double* M, int border,
                          void* stream);
+/* cv::warpAffine on a plane of 16-bit samples: cn 1 or 2 (the planes of a P010 surface), a destination size of its own, double
+ * forward matrix, VS_BORDER_BLACK | VS_BORDER_REPLICATE, P010's blend (vs_pixfmt16).  Strides in bytes; pointers and strides
+ * must be even (VS_ERR_INVALID_ARG).  The 16-bit counterpart of vs_op_warp_affine_ex. */
+int vs_op_warp_affine16_ex(const void* d_src, size_t src_stride, int sw, int sh, void* d_dst,
+                           size_t dst_stride, int dw, int dh, int cn, const double* M, int border,
+                           void* stream);
 
 /* ---- auto zoom/crop: vs::AutoZoomCrop (AutoZoomCrop.h:7-17, AutoZoomCrop.cpp:102-283) ---- */
 typedef struct vs_azc vs_azc;
@@ -658,6 +688,14 @@ int vs_azc_sync(vs_azc* a);
 int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset,
                           void* d_out, size_t out_pitch, size_t out_uv_offset, int64_t* ticket);
 int vs_azc_apply_nv12_dev_n(vs_azc* a, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
+                            size_t pitch, size_t uv_offset, size_t out_pitch, size_t out_uv_offset, int64_t* tickets);
+/* The same for P010 surfaces (vs_pixfmt16: the definitions are there).  pitch >= 2 * w, out_pitch >= 2 * max(w, 640),
+ * out_uv_offset >= max(h, 360) * out_pitch; pointers, pitches and offsets in bytes and even (VS_ERR_INVALID_ARG otherwise).
+ * Batches, worker threads, VS_AZC_WORKERS, tickets, vs_azc_result, vs_azc_worker_times and vs_azc_sync as for NV12; one object
+ * may receive NV12 and P010 calls, a change of sample size closes the pending batch. */
+int vs_azc_apply_p010_dev(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset,
+                          void* d_out, size_t out_pitch, size_t out_uv_offset, int64_t* ticket);
+int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                             size_t pitch, size_t uv_offset, size_t out_pitch, size_t out_uv_offset, int64_t* tickets);
 int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* info8);
 /* Diagnostics of the asynchronous path: out9 = {frames through the worker threads; seconds, summed over the threads: without a

@@ -109,6 +109,41 @@ __global__ __launch_bounds__(256) void threshold_bits_gray16_kernel(size_t strid
     if ((lane & 3) == 0 && word < wpr) T[(size_t)y * wpr + word] = bits;
 }
 
+// Pass 1 for the luma planes of P010 surfaces: the content mask of a P010 surface is that of the 8-bit plane of its luma samples' high
+// bytes, (sample >> 8) > 1 - the low byte is never looked at.  A lane takes 8 samples - WIDE: with ONE 16-byte load (width a multiple
+// of 8 samples, rows 16-byte aligned); else sample by sample, any width and any even pitch -, tests the high bytes (bytes 1 and 3 of a
+// dword) with the carry-free byte trick of above1_nibble, and its 8 bits meet its seven neighbours' through three lane exchanges:
+// a wave 512 samples of a row = eight of the words close5_bits_kernel reads, a workgroup four rows; no LDS, no barrier.
+__device__ __forceinline__ uint32_t above1_high_bytes(uint32_t d) {     // bit k = the high byte of sample k (half k of d) > 1
+    const uint32_t t = (d | ((d & 0x7F7F7F7Fu) + 0x7E7E7E7Eu)) & 0x80008000u;      // bit 7 of bytes 1 and 3: byte >= 2 (no carries between bytes)
+    return ((t >> 15) & 1u) | ((t >> 30) & 2u);
+}
+template <bool WIDE>
+__global__ __launch_bounds__(256) void threshold_bits_p010_kernel(size_t stride, int w, int h, u64* __restrict__ T, int wpr, SrcList srcs, size_t tfb) {
+    const uint8_t* __restrict__ src = srcs.p[blockIdx.z];
+    T += (size_t)blockIdx.z * tfb;
+    const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x = blockIdx.x * 512 + lane * 8, word = blockIdx.x * 8 + (lane >> 3);
+    if (y >= h) return;                                                  // (wave-uniform)
+    uint32_t m = 0;
+    const uint8_t* row = src + (size_t)y * stride;
+    if (WIDE) {
+        if (x < w) {                                                     // (w is a multiple of 8: the lane's samples are all inside or all outside)
+            const uint4 d = *reinterpret_cast<const uint4*>(row + (size_t)x * 2);
+            m = above1_high_bytes(d.x) | above1_high_bytes(d.y) << 2 | above1_high_bytes(d.z) << 4 | above1_high_bytes(d.w) << 6;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (x + i < w) m |= ((reinterpret_cast<const uint16_t*>(row)[x + i] >> 8) > 1u ? 1u : 0u) << i;
+    }
+    u64 bits = (u64)m << (8 * (lane & 7));
+    bits |= __shfl_xor(bits, 1);
+    bits |= __shfl_xor(bits, 2);
+    bits |= __shfl_xor(bits, 4);
+    if ((lane & 7) == 0 && word < wpr) T[(size_t)y * wpr + word] = bits;
+}
+
 constexpr int MC_ROWS = 56;      // rows a wave of the morphology pass owns (lanes 4..59; halo 4 above and below)
 
 // OR / AND of a row with itself moved by -2..2 pixels; l, r: the words left and right of it
@@ -167,10 +202,11 @@ __global__ __launch_bounds__(256) void expand_bits_kernel(const u64* __restrict_
 // oframe rows and words (1 for a BitFrame whose frame is already zero, 0 for a plain bit plane).
 // srcs (optional, d_src == nullptr): `frames` <= SRC_LIST_MAX source pointers on the HOST, one geometry and pitch; the pictures'
 // bit planes / results lie tfb / ofb words apart.
+// sb = 2 (a table of sources, cn 1): luma planes of 16-bit samples, the mask of their high bytes; stride in bytes, everything even.
 int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int cn, u64* d_T, u64* d_out, int opitch,
                         int oframe, hipStream_t st, const uint8_t* const* srcs = nullptr, int frames = 1, size_t tfb = 0, size_t ofb = 0,
-                        int srcs_aligned = 0) {
-    if ((!d_src && !srcs) || (!d_src && frames > SRC_LIST_MAX) || !d_T || !d_out || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || frames < 1) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
+                        int srcs_aligned = 0, int sb = 1) {
+    if ((sb != 1 && sb != 2) || (sb == 2 && (d_src || cn != 1)) || (!d_src && !srcs) || (!d_src && frames > SRC_LIST_MAX) || !d_T || !d_out || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || frames < 1) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
     if (h > 65535) { set_last_error("content_mask: image too tall"); return VS_ERR_INVALID_ARG; }
     const int wpr = (w + 63) / 64;
     // (a table of sources: srcs_aligned = every one of them is 4-byte aligned)
@@ -178,9 +214,13 @@ int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int c
     SrcList sl;
     for (int i = 0; i < SRC_LIST_MAX; i++) sl.p[i] = !d_src ? srcs[i < frames ? i : 0] : nullptr;
     dim3 g1((w + 1023) / 1024, h, frames);
-    bool wide = !d_src && cn == 1 && (w & 15) == 0 && (stride & 15) == 0;
+    bool wide = !d_src && cn == 1 && (w & (sb == 2 ? 7 : 15)) == 0 && (stride & 15) == 0;
     for (int i = 0; wide && i < frames; i++) wide = ((uintptr_t)srcs[i] & 15) == 0;
-    if (wide) hipLaunchKernelGGL(threshold_bits_gray16_kernel, dim3((w + 1023) / 1024, (h + 3) / 4, frames), dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
+    if (sb == 2) {
+        const dim3 g((w + 511) / 512, (h + 3) / 4, frames);
+        if (wide) hipLaunchKernelGGL(threshold_bits_p010_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
+        else hipLaunchKernelGGL(threshold_bits_p010_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
+    } else if (wide) hipLaunchKernelGGL(threshold_bits_gray16_kernel, dim3((w + 1023) / 1024, (h + 3) / 4, frames), dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
     else if (cn == 3) hipLaunchKernelGGL(threshold_bits_kernel<3>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
     else hipLaunchKernelGGL(threshold_bits_kernel<1>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
     dim3 g2(wpr, (h + MC_ROWS - 1) / MC_ROWS, frames);
@@ -216,7 +256,7 @@ struct vs_azc {
     // one launch.  NBS batches in flight.
     static constexpr int ZB = 8, NBS = 4, NRES = 1024;      // (ZB <= SRC_LIST_MAX, 2 ZB <= WARP_JOBS_MAX)
     int nw = 12;                         // worker threads (VS_AZC_WORKERS, 1 .. 16): 31 k frames/s alone with eight, 41 k with twelve
-    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; };
+    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; };     // sb: bytes of a sample (1 NV12, 2 P010)
     struct BatchSlot {
         uint8_t* d_masks = nullptr;      // ZB BitFrames
         uint8_t* h_masks = nullptr;      // page-locked
@@ -508,8 +548,8 @@ static void azc_worker(vs_azc* a) {
             t_contour = clk::now();
             if (!res.info[7]) {                                                                            // :149-152, :238-249
                 res.out_w = q.w; res.out_h = q.h;
-                if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
-                    hipMemcpy2DAsync(q.dst + q.ouv, q.opitch, q.src + q.uv, q.pitch, (size_t)q.w, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
+                if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
+                    hipMemcpy2DAsync(q.dst + q.ouv, q.opitch, q.src + q.uv, q.pitch, (size_t)q.w * q.sb, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
                     rc = VS_ERR_HIP;
             } else {
                 res.out_w = 640; res.out_h = 360;
@@ -519,11 +559,11 @@ static void azc_worker(vs_azc* a) {
                 const float Mu[6] = {(float)(320.0 / uw), 0.f, 0.f, 0.f, (float)(180.0 / uh), 0.f};
                 warp_invert(My, wj[0].m);
                 warp_invert(Mu, wj[1].m);
-                wj[0].src = q.src + (size_t)cy * q.pitch + cx; wj[0].dst = q.dst;
+                wj[0].src = q.src + (size_t)cy * q.pitch + (size_t)cx * q.sb; wj[0].dst = q.dst;
                 wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = 640; wj[0].dh = 360; wj[0].cn = 1;
-                wj[1].src = q.src + q.uv + (size_t)uy * q.pitch + (size_t)ux * 2; wj[1].dst = q.dst + q.ouv;
+                wj[1].src = q.src + q.uv + (size_t)uy * q.pitch + (size_t)ux * 2 * q.sb; wj[1].dst = q.dst + q.ouv;
                 wj[1].sw = uw; wj[1].sh = uh; wj[1].dw = 320; wj[1].dh = 180; wj[1].cn = 2;
-                for (WarpJob& w : wj) { w.sstride = (uint32_t)q.pitch; w.dstride = (uint32_t)q.opitch; w.border = VS_BORDER_BLACK; }
+                for (WarpJob& w : wj) { w.sstride = (uint32_t)q.pitch; w.dstride = (uint32_t)q.opitch; w.border = VS_BORDER_BLACK; w.sb = q.sb; }
                 scaled = true;
             }
         }
@@ -597,7 +637,7 @@ static int azc_issue_batch(vs_azc* a, std::unique_lock<std::mutex>& lk) {
         if ((uintptr_t)a->pending[i].src & 3) aligned = 0;
     }
     VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, 1, b.d_tbits, (u64*)b.d_masks, BitFrame::pitch_for(w), 1, b.st, srcs, n, tw,
-                                 mb / 8, aligned));                                                                              // :111-139 on the luma planes
+                                 mb / 8, aligned, a->pending[0].sb));                                                                              // :111-139 on the luma planes
     VS_OBJ_HIP(a, hipMemcpyAsync(b.h_masks, b.d_masks, mb * n, hipMemcpyDeviceToHost, b.st));                                          // :142-143
     VS_OBJ_HIP(a, hipEventRecord(b.ev, b.st));
     b.t_issue = std::chrono::steady_clock::now();
@@ -634,11 +674,14 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
 // ticket; eight consecutive frames of one geometry form a batch (vs_azc_sync and vs_azc_result close an incomplete one).
 // vs_azc_result(ticket) tells what came out (it waits for that frame's host part), the pixels are complete after vs_azc_sync.
 // Surface and result buffer must stay untouched until then; results of the last 1024 tickets are kept.
-int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                          size_t out_uv_offset, int64_t* ticket) {
-    if (!a || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w || out_pitch < (size_t)std::max(w, 640) ||
+// (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
+static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                         size_t out_uv_offset, int64_t* ticket, int sb) {
+    if (!a || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)std::max(w, 640) * sb ||
         out_uv_offset < (size_t)std::max(h, 360) * out_pitch)
         return VS_ERR_INVALID_ARG;
+    if (sb == 2 && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: P010 pointers, pitches and plane offsets must be even");
     if (w > 65535 || h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
     if (uv_offset == 0) uv_offset = (size_t)h * pitch;
     VS_OBJ_HIP(a, hipSetDevice(a->device));
@@ -652,14 +695,40 @@ int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t
         }
     }
     std::unique_lock<std::mutex> lk(a->mu);
-    if (!a->pending.empty() && (a->pending[0].w != w || a->pending[0].h != h || a->pending[0].pitch != pitch)) {
+    // (a change of geometry or of sample size closes the pending batch: a batch's launches take one of each)
+    if (!a->pending.empty() && (a->pending[0].w != w || a->pending[0].h != h || a->pending[0].pitch != pitch || a->pending[0].sb != sb)) {
         const int rc = azc_flush_pending(a, lk);
         if (rc != VS_OK) return rc;
     }
-    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued});
+    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb});
     if (ticket) *ticket = a->issued;
     a->issued++;
     if ((int)a->pending.size() >= vs_azc::ZB) return azc_flush_pending(a, lk);
+    return VS_OK;
+}
+
+int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                          size_t out_uv_offset, int64_t* ticket) {
+    return azc_hand_over(a, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, ticket, 1);
+}
+
+// The same for a P010 surface (vs_pixfmt16; pitches and offsets in bytes, everything even: out_pitch >= 2 * max(w, 640)).  The content
+// mask is that of the 8-bit plane of the luma samples' high bytes, (sample >> 8) > 1 - mask, contours, info8 and the crop rectangle are
+// those of the NV12 call on that plane -; crop-and-scale on the 16-bit planes with P010's blend (S rounded once, half to even),
+// BORDER_CONSTANT 0; on the fall-back paths the surface comes back unchanged, all 16 bits.  NV12 and P010 surfaces may alternate on one
+// object: a change of sample size closes the pending batch as a change of geometry does.
+int vs_azc_apply_p010_dev(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                          size_t out_uv_offset, int64_t* ticket) {
+    return azc_hand_over(a, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, ticket, 2);
+}
+
+int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
+                            size_t out_pitch, size_t out_uv_offset, int64_t* tickets) {
+    if (!a || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) {
+        const int rc = vs_azc_apply_p010_dev(a, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset, tickets ? tickets + i : nullptr);
+        if (rc != VS_OK) return rc;
+    }
     return VS_OK;
 }
 

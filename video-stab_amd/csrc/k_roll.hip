@@ -639,7 +639,7 @@ struct vs_roll {
     int nwk = 5;                         // worker threads in use (VS_ROLL_WORKERS, 1 .. NWK): alone three are as fast as eight (36 - 38 k
                                          // frames/s); beside a stabilizer on the same GPU a batch's launches wait behind its workgroups, and five
                                          // batches in flight keep the stage at 3.4 ms per 128 surfaces where three need 5.5 (gpurun_out/r04_ai)
-    struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; };
+    struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; int sb; };      // sb: bytes of a sample (1 NV12, 2 P010)
     struct Slot {
         RollWork wk;                     // RB frames
         hipStream_t st = nullptr;
@@ -722,6 +722,19 @@ int vs_op_warp_affine_ex(const void* d_src, size_t src_stride, int sw, int sh, v
     uint8_t* dst = (uint8_t*)d_dst;
     return launch_warp_plane(&src, &dst, 1, src_stride, sw, sh, dst_stride, dw, dh, cn, WarpMaps{Mi, 6, true}, border, WarpTabs{},
                              (hipStream_t)stream);
+}
+
+// The same on a plane of 16-bit samples (cn 1 or 2: the planes of a P010 surface), P010's blend.
+int vs_op_warp_affine16_ex(const void* d_src, size_t src_stride, int sw, int sh, void* d_dst, size_t dst_stride, int dw,
+                           int dh, int cn, const double* M, int border, void* stream) {
+    VS_TRY(ensure_device());
+    if (!M) return VS_ERR_INVALID_ARG;
+    double Mi[6];
+    warp_invert(M, Mi);
+    const uint8_t* src = (const uint8_t*)d_src;
+    uint8_t* dst = (uint8_t*)d_dst;
+    return launch_warp_plane(&src, &dst, 1, src_stride, sw, sh, dst_stride, dw, dh, cn, WarpMaps{Mi, 6, true}, border, WarpTabs{},
+                             (hipStream_t)stream, 2);
 }
 
 int vs_roll_create(const vs_roll_params_c* params, int device, vs_roll** out) {
@@ -866,7 +879,8 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
     k.base = nullptr; k.frames = n;
     for (int f = 0; f < n; f++) { q.h_pairs[f].src = jobs[f].src; q.h_pairs[f].dst = k.gray + (size_t)f * k.fb; }
     VS_HIP_TRY(hipMemcpyAsync(q.d_pairs, q.h_pairs, sizeof(ImgPair) * n, hipMemcpyHostToDevice, q.st));
-    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, VS_FMT_GRAY8, sw, sw, sh, 0, q.st));                     // :41
+    // (P010: the analysis image is that of the luma samples' high bytes - the 16-bit gray kernels of k_gray.hip read nothing else)
+    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, j0.sb == 2 ? (int)VS_FMT_P010 : (int)VS_FMT_GRAY8, sw, sw, sh, 0, q.st));   // :41
     // (twelve hysteresis passes per batch - a pass whose predecessor changed nothing for its frame returns at once: with four, 40 % of
     // the bench clip's frames had to finish their growth one by one behind the batch, 30 us per frame)
     constexpr int PASSES = 12;
@@ -914,14 +928,15 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
         one_launch &= j.opitch == j0.opitch && j.uv == j0.uv && j.ouv == j0.ouv;
     }
     // the rotations of the batch (:146-149): luma and chroma tiles of all its surfaces in ONE grid (warp_nv12_kernel with the
-    // BORDER_REPLICATE staging) when the results share one layout (the surfaces do), else frame by frame
+    // BORDER_REPLICATE staging; P010: its instance for 16-bit samples) when the results share one layout (the surfaces do), else
+    // frame by frame
     if (one_launch)
         return launch_warp_nv12(ys, yd, us, ud, n, j0.pitch, j0.opitch, j0.w, j0.h, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE,
-                                WarpTabs{WarpTabs::SCRATCH}, r->st);
+                                WarpTabs{WarpTabs::SCRATCH}, r->st, j0.sb);
     for (int f = 0; f < n; f++) {
         const vs_roll::Job& j = jobs[f];
         VS_TRY(launch_warp_nv12(ys + f, yd + f, us + f, ud + f, 1, j.pitch, j.opitch, j.w, j.h, WarpMaps{Minv + 12 * f, 12, true},
-                                VS_BORDER_REPLICATE, WarpTabs{}, r->st));
+                                VS_BORDER_REPLICATE, WarpTabs{}, r->st, j.sb));
     }
     return VS_OK;
 }
@@ -965,9 +980,12 @@ static void roll_flush_pending(vs_roll* r) {
 // consecutive frames of one geometry form a batch that a worker thread analyses with one launch per stage.  Results are complete
 // after vs_roll_sync (which also closes an incomplete batch).  The surface and the result buffer of a call must stay untouched
 // until then.
-int vs_roll_correct_nv12_dev(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                             size_t out_uv_offset) {
-    if (!r || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w || out_pitch < (size_t)w) return VS_ERR_INVALID_ARG;
+// (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
+static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                          size_t out_uv_offset, int sb) {
+    if (!r || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)w * sb) return VS_ERR_INVALID_ARG;
+    if (sb == 2 && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
+        return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: P010 pointers, pitches and plane offsets must be even");
     if (uv_offset == 0) uv_offset = (size_t)h * pitch;
     if (out_uv_offset == 0) out_uv_offset = (size_t)h * out_pitch;
     VS_OBJ_HIP(r, hipSetDevice(r->device));
@@ -983,12 +1001,37 @@ int vs_roll_correct_nv12_dev(vs_roll* r, const void* d_surface, int w, int h, si
         std::unique_lock<std::mutex> lk(r->mu);
         if (r->first) { r->first = false; r->smoothed = 0.0; }                                   // :24-27
         r->cv_done.wait(lk, [&] { return r->nv_in - r->nv_done < vs_roll::QMAX; });
-        if (!r->pending.empty() && (r->pending[0].w != w || r->pending[0].h != h || r->pending[0].pitch != pitch)) roll_flush_pending(r);
-        r->pending.push_back(vs_roll::Job{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, r->nv_in});
+        // (a change of geometry or of sample size closes the pending batch: a batch's launches take one of each)
+        if (!r->pending.empty() && (r->pending[0].w != w || r->pending[0].h != h || r->pending[0].pitch != pitch || r->pending[0].sb != sb)) roll_flush_pending(r);
+        r->pending.push_back(vs_roll::Job{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, r->nv_in, sb});
         r->nv_in++;
         if ((int)r->pending.size() >= vs_roll::RB) roll_flush_pending(r);
     }
     r->cv_job.notify_all();
+    return VS_OK;
+}
+
+int vs_roll_correct_nv12_dev(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                             size_t out_uv_offset) {
+    return roll_hand_over(r, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, 1);
+}
+
+// The same for a P010 surface (vs_pixfmt16; pitches and offsets in bytes, everything even): the line search runs on the 8-bit plane
+// of the luma samples' high bytes - angle and line counts are those of the NV12 call on that plane -, the rotation is applied to
+// the 16-bit planes with P010's blend (S rounded once, half to even), BORDER_REPLICATE.  NV12 and P010 surfaces may alternate on one
+// object: a change of sample size closes the pending batch as a change of geometry does, the smoothed angle carries across.
+int vs_roll_correct_p010_dev(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                             size_t out_uv_offset) {
+    return roll_hand_over(r, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, 2);
+}
+
+int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
+                               size_t out_pitch, size_t out_uv_offset) {
+    if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) {
+        const int rc = vs_roll_correct_p010_dev(r, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset);
+        if (rc != VS_OK) return rc;
+    }
     return VS_OK;
 }
 

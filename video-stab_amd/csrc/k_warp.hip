@@ -640,9 +640,12 @@ __global__ __launch_bounds__(NT) void warp_affine16_kernel(WarpArgs a) {
 // with its own crop rectangle, as one launch instead of sixteen (a launch costs the host 6 - 7 us on this runtime).  The jobs
 // travel as kernel arguments; blockIdx.z = job, a job's tiles beyond its own size return at once.  Terms and taps as the
 // general kernel's direct path (no staging: a scale map spreads the taps of a tile over a box that no staging area holds).
+// SB = 2: jobs on planes of 16-bit samples (the crop-and-scale of P010 surfaces: cn 1 and 2, P010's blend) - a kernel of its own,
+// so that the 8-bit launch keeps its code and its registers; the jobs of a launch share one sample size.
 struct WarpJobsArg { WarpJob j[WARP_JOBS_MAX]; };
 
-__global__ __launch_bounds__(NT) void warp_jobs_kernel(WarpJobsArg a) {
+template <int SB>
+__device__ __forceinline__ void warp_jobs_tile(const WarpJobsArg& a) {
     __shared__ int s_ad[TW], s_bd[TW], s_x0[TH], s_y0[TH];
     const WarpJob& j = a.j[blockIdx.z];
     const int tid = threadIdx.x;
@@ -663,13 +666,16 @@ __global__ __launch_bounds__(NT) void warp_jobs_kernel(WarpJobsArg a) {
     c.sstride = j.sstride; c.dstride = j.dstride;
     c.sw = j.sw; c.sh = j.sh; c.dw = j.dw; c.dh = j.dh;
     c.src_aligned = 0;
-    const int galign = j.cn == 2 ? 8 : 4;
+    const int galign = SB == 2 ? 8 * j.cn : j.cn == 2 ? 8 : 4;        // (a lane's four pixels in one store)
     c.dst_aligned = ((uintptr_t)j.dst % galign == 0) && (j.dstride % galign == 0);
     c.border = j.border;
-    if (j.cn == 1) emit_rows<1, false>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
-    else if (j.cn == 2) emit_rows<2, false>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
-    else emit_rows<3, false>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
+    if (j.cn == 1) emit_rows<1, false, SB>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
+    else if (j.cn == 2 || SB == 2) emit_rows<2, false, SB>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
+    else if constexpr (SB == 1) emit_rows<3, false>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
 }
+
+__global__ __launch_bounds__(NT) void warp_jobs_kernel(WarpJobsArg a) { warp_jobs_tile<1>(a); }
+__global__ __launch_bounds__(NT) void warp_jobs16_kernel(WarpJobsArg a) { warp_jobs_tile<2>(a); }
 
 // ---- tile building blocks shared by the table kernels ------------------------------------------------------------
 constexpr int TABN = 2 * TW + 2 * TH;     // ints of coordinate terms per tile: ad[128] bd[128] x0[16] y0[16]
@@ -971,6 +977,8 @@ __device__ __forceinline__ uint4 load_chunk_straddling(const uint8_t* rowp, int 
 
 // The same chunk under BORDER_REPLICATE (remapBilinear's clip()): a byte outside the row is the byte of the same channel of the
 // row's first / last pixel.  (Chunks of tiles at the picture's edge only.)
+// CN: the BYTES of a pixel (1, 2 or 4) - the channels of an 8-bit plane, or one / two 16-bit samples (P010 luma / chroma: a byte outside the
+// row is the byte of the same sample at the same place in the edge pixel).
 template <int CN>
 __device__ __forceinline__ uint4 load_chunk_replicate(const uint8_t* rowp, int xb, int sw) {
     uint32_t wq[4] = {0u, 0u, 0u, 0u};
@@ -1163,7 +1171,9 @@ __device__ __forceinline__ void plane_blend_rows(const WarpCore& c, const uint8_
 // A plane tile whose source box does not fit the staging area (large rotations, zooms, saturated coordinates, BORDER_REPLICATE): the
 // general path without staging (emit_rows works on 16 rows, terms as arrays: they go where the box would be).  Not inlined: as
 // part of the kernel body it costs the common path its eighth wave per SIMD or register spills.
-template <int CN, int SB = 1>
+// (OWN: a copy of its own for the kernel that names it - the BORDER_REPLICATE instance for 16-bit samples -, so that the kernels
+// that existed before it keep their callee, and with it their code, as they were.)
+template <int CN, int SB = 1, int OWN = 0>
 __device__ __attribute__((noinline)) void plane_direct_tile(WarpCore c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
                                                             int bx0a, int by0, int bw, int tid) {
     typedef PlaneCfg<CN, SB> P;
@@ -1205,7 +1215,7 @@ template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1>
 __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
                                            uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add = 0, int dst_add = 0) {
     typedef PlaneCfg<CN, SB> P;
-    static_assert(SB == 1 || (SB == 2 && CN <= 2 && BORDER == VS_BORDER_BLACK), "16-bit planes: one or two channels, constant border");
+    static_assert(SB == 1 || (SB == 2 && CN <= 2), "16-bit planes: one or two channels");
     typedef __attribute__((address_space(1))) uint8_t* gptr;
     const int L = tid & 31, ty = tid >> 5;
     int ad[4], bd[4];
@@ -1268,7 +1278,7 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
                 if constexpr (BORDER == VS_BORDER_REPLICATE) {
                     const uint8_t* row = src + (size_t)min(max(y, 0), c.sh - 1) * c.sstride;
                     if (xb >= 0 && xb + 16 <= rowbytes && c.src_aligned) d[k] = *reinterpret_cast<const uint4*>(row + xb);
-                    else d[k] = load_chunk_replicate<CN>(row, (int)max(min(xb, (long long)rowbytes + 64), -64ll), c.sw);
+                    else d[k] = load_chunk_replicate<P::PXB>(row, (int)max(min(xb, (long long)rowbytes + 64), -64ll), c.sw);
                 } else if ((unsigned)y < (unsigned)c.sh) {
                     const uint8_t* row = src + (size_t)y * c.sstride;
                     if (xb >= 0 && xb + 16 <= rowbytes && c.src_aligned) {
@@ -1311,7 +1321,7 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
     }
     if (!fit) {
         if constexpr (CN == 4) plane_direct_tile4(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
-        else plane_direct_tile<CN, SB>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        else plane_direct_tile<CN, SB, (SB == 2 && BORDER == VS_BORDER_REPLICATE ? 1 : 0)>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
         return;
     }
     __syncthreads();
@@ -1594,8 +1604,7 @@ int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t
 // dst_uv bytes behind the luma planes.  Returns VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstride, size_t dstride, int w, int h, size_t src_uv,
                 size_t dst_uv, const int32_t* d_tabs, int border, hipStream_t st, int sb = 1) {
-    // (sb = 2, P010: tiles of half the rows; no BORDER_REPLICATE instance - no caller rotates P010 surfaces)
-    if (sb == 2 && border != VS_BORDER_BLACK) return VS_ERR_UNSUPPORTED;
+    // (sb = 2, P010: tiles of half the rows; BORDER_REPLICATE: the roll stage's rotation of P010 surfaces)
     const int thp1 = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP, thp2 = sb == 2 ? PlaneCfg<2, 2>::THP : PlaneCfg<2>::THP;
     const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp1 - 1) / thp1, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + thp2 - 1) / thp2;
     const unsigned long long tpf = gx1 * gy1 + gx2 * gy2, total = tpf * (unsigned long long)n;
@@ -1617,7 +1626,10 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
     const uint32_t flags = (al & 1u) | (al & 2u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    if (sb == 2)
+    if (sb == 2 && border == VS_BORDER_REPLICATE)
+        hipLaunchKernelGGL((warp_nv12_kernel<VS_BORDER_REPLICATE, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
+                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
+    else if (sb == 2)
         hipLaunchKernelGGL((warp_nv12_kernel<VS_BORDER_BLACK, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
                            (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
     else if (border == VS_BORDER_REPLICATE)
@@ -1681,10 +1693,14 @@ int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420L
 size_t warp_tabs_ints(int dw, int dh, int frames) { return (size_t)tab_stride_of(dw, dh) * (size_t)(frames > 0 ? frames : 1); }
 
 int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw,
-                      int dh, int cn, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st) {
-    if (n < 1 || !srcs || !dsts || bad_args(srcs[0], dsts[0], maps.m, sstride, sw, sh, dstride, dw, dh, cn, n) ||
-        bad_call(srcs, dsts, n, border, tabs)) {
-        set_last_error("warp_affine: invalid argument");
+                      int dh, int cn, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sb) {
+    if (n < 1 || !srcs || !dsts || (sb != 1 && sb != 2) || (sb == 2 && (cn < 1 || cn > 2 || tabs.kind != WarpTabs::NONE)) ||
+        bad_args(srcs[0], dsts[0], maps.m, sstride, sw, sh, dstride, dw, dh, cn * sb, n) || bad_call(srcs, dsts, n, border, tabs)) {
+        set_last_error(sb == 2 ? "warp_affine16: invalid argument (planes of 16-bit samples, as those of P010: cn 1 or 2)" : "warp_affine: invalid argument");
+        return VS_ERR_INVALID_ARG;
+    }
+    if (sb == 2 && odd16(srcs, dsts, n, sstride, dstride)) {
+        set_last_error("warp_affine16: pointers and strides of 16-bit planes (P010's) must be even");
         return VS_ERR_INVALID_ARG;
     }
     if (tabs.kind == WarpTabs::SCRATCH && n >= WARP_TAB_MIN)
@@ -1696,7 +1712,7 @@ int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, s
         int32_t* T = tabs.kind != WarpTabs::NONE && nb >= WARP_TAB_MIN ? tabs.tabs + b0 * tab_step : nullptr;
         if (!T && tabs.what == VS_WARP_TABLES_ONLY) continue;
         VS_TRY(plane_launch(srcs + b0, dsts + b0, nb, sstride, sw, sh, dstride, dw, dh, cn, maps_from(maps, b0), border, T, tabs.stride,
-                            T ? tabs.what : VS_WARP_ALL, st));
+                            T ? tabs.what : VS_WARP_ALL, st, sb));
     }
     return VS_OK;
 }
@@ -1831,7 +1847,7 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
     return VS_OK;
 }
 
-// n <= WARP_JOBS_MAX warps of any geometry (inverse maps in double on the host) as one launch.
+// n <= WARP_JOBS_MAX warps of any geometry (inverse maps in double on the host) as one launch; one sample size for all of them.
 int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st) {
     if (!jobs || n < 1 || n > WARP_JOBS_MAX) { set_last_error("warp_jobs: invalid argument"); return VS_ERR_INVALID_ARG; }
     WarpJobsArg a;
@@ -1840,15 +1856,18 @@ int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st) {
         a.j[i] = jobs[i < n ? i : 0];
         if (i >= n) continue;
         const WarpJob& j = jobs[i];
-        if (bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn, 1) || j.cn > 3 ||
-            (j.border != VS_BORDER_BLACK && j.border != VS_BORDER_REPLICATE)) {
+        if ((j.sb != 1 && j.sb != 2) || j.sb != jobs[0].sb || j.cn < 1 || j.cn > (j.sb == 2 ? 2 : 3) ||
+            bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn * j.sb, 1) ||
+            (j.border != VS_BORDER_BLACK && j.border != VS_BORDER_REPLICATE) ||
+            (j.sb == 2 && (((uintptr_t)j.src | (uintptr_t)j.dst | j.sstride | j.dstride) & 1))) {
             set_last_error("warp_jobs: invalid argument");
             return VS_ERR_INVALID_ARG;
         }
         gw = std::max(gw, (j.dw + TW - 1) / TW);
         gh = std::max(gh, (j.dh + TH - 1) / TH);
     }
-    hipLaunchKernelGGL(warp_jobs_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
+    if (jobs[0].sb == 2) hipLaunchKernelGGL(warp_jobs16_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL(warp_jobs_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }

@@ -159,13 +159,14 @@ struct WarpTabs {
     int what = VS_WARP_ALL;
 };
 // One plane of cn channels per frame (1 .. 3), border VS_BORDER_BLACK or VS_BORDER_REPLICATE.
+// sample_bytes = 2: planes of 16-bit samples (cn 1 or 2, strides in bytes, pointers and strides even, no tables): P010's blend.
 int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw,
-                      int dh, int cn, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st);
+                      int dh, int cn, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sample_bytes = 1);
 // NV12 surfaces of w x h (even) luma pixels: luma planes ys -> yd, interleaved chroma planes us -> ud (half size, two channels).
 // Launches with tables warp both planes of their surfaces in ONE grid when the chroma planes lie one offset behind the luma
 // planes; other launches go plane by plane.
-// sample_bytes = 2: P010 surfaces - planes of 16-bit samples, pitches and pointers in bytes and even, VS_BORDER_BLACK; a call with
-// the scratch tables builds them for any number of surfaces.
+// sample_bytes = 2: P010 surfaces - planes of 16-bit samples, pitches and pointers in bytes and even; a call with the scratch tables
+// builds them for any number of surfaces.
 int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t* const* us, uint8_t* const* ud, int n, size_t sstride,
                      size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sample_bytes = 1);
 // One warp of a multi-job launch (launch_warp_jobs, k_warp.hip): any geometry, inverse map in double on the host.
@@ -175,6 +176,7 @@ struct WarpJob {
     uint32_t sstride, dstride;
     int32_t sw, sh, dw, dh, cn, border;
     double m[6];
+    int32_t sb = 1;              // bytes of a sample: 1, or 2 (planes of 16-bit samples, cn 1 or 2, P010's blend); one value per launch
 };
 constexpr int WARP_JOBS_MAX = 16;
 int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st);

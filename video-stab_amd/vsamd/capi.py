@@ -368,6 +368,11 @@ class VsLib:
         L.vs_enh_gaussian_blur.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_double, vp, C.c_size_t]
         L.vs_op_warp_affine_ex.argtypes =[vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int,
                                            C.c_int, f64p, C.c_int, vp]
+        L.vs_op_warp_affine16_ex.argtypes = L.vs_op_warp_affine_ex.argtypes
+        L.vs_roll_correct_p010_dev.argtypes = L.vs_roll_correct_nv12_dev.argtypes
+        L.vs_roll_correct_p010_dev_n.argtypes = L.vs_roll_correct_nv12_dev_n.argtypes
+        L.vs_azc_apply_p010_dev.argtypes = L.vs_azc_apply_nv12_dev.argtypes
+        L.vs_azc_apply_p010_dev_n.argtypes = L.vs_azc_apply_nv12_dev_n.argtypes
 
     # ---- helpers ----------------------------------------------------------
     def check(self, status, inst=None):
@@ -615,6 +620,20 @@ class VsLib:
         self.sync()
         return d_out.download((dh, dw) if img.ndim == 2 else (dh, dw, cn), np.uint8)
 
+    def warp_affine16_ex(self, img, M, border=BORDER_BLACK, dsize=None):
+        """cv::warpAffine on a plane of 16-bit samples, (h, w) or (h, w, 2) uint16, with P010's blend (vs_op_warp_affine16_ex)."""
+        img = np.ascontiguousarray(img, np.uint16)
+        h, w = img.shape[:2]
+        cn = 1 if img.ndim == 2 else img.shape[2]
+        dw, dh = dsize if dsize else (w, h)
+        M = np.ascontiguousarray(M, np.float64).reshape(6)
+        d_in = DevBuf.from_array(self, img)
+        d_out = DevBuf(self, dw * dh * cn * 2)
+        self.check(self.lib.vs_op_warp_affine16_ex(d_in.ptr, w * cn * 2, w, h, d_out.ptr, dw * cn * 2, dw, dh, cn,
+                                                   _p(M, f64p), border, None))
+        self.sync()
+        return d_out.download((dh, dw) if img.ndim == 2 else (dh, dw, cn), np.uint16)
+
     def content_mask(self, img):
         img = np.ascontiguousarray(img)
         h, w = img.shape[:2]
@@ -716,6 +735,21 @@ class AutoZoomCrop:
         b = (C.c_void_p * n)(*d_outs)
         t = (C.c_int64 * n)()
         self._check(self.lib.vs_azc_apply_nv12_dev_n(self.h, a, b, n, w, h, pitch, uv_offset, out_pitch, out_uv_offset, t))
+        return list(t)
+
+    def apply_p010_dev(self, d_in, w, h, pitch, d_out, out_pitch, out_uv_offset, uv_offset=0):
+        """apply_nv12_dev for a P010 surface (vs_azc_apply_p010_dev): pitches and offsets in bytes, even."""
+        t = C.c_int64(-1)
+        self._check(self.lib.vs_azc_apply_p010_dev(self.h, d_in, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, C.byref(t)))
+        return t.value
+
+    def apply_p010_dev_n(self, d_ins, w, h, pitch, d_outs, out_pitch, out_uv_offset, uv_offset=0):
+        """n P010 surfaces in call order, one trip through the binding; returns the tickets."""
+        n = len(d_ins)
+        a = (C.c_void_p * n)(*d_ins)
+        b = (C.c_void_p * n)(*d_outs)
+        t = (C.c_int64 * n)()
+        self._check(self.lib.vs_azc_apply_p010_dev_n(self.h, a, b, n, w, h, pitch, uv_offset, out_pitch, out_uv_offset, t))
         return list(t)
 
     def result(self, ticket):
@@ -958,6 +992,17 @@ class RollCorrection:
     def correct_nv12_dev(self, d_in, w, h, pitch, d_out, out_pitch, uv_offset=0, out_uv_offset=0):
         """Asynchronous (vs_roll_correct_nv12_dev): the result is complete after sync()."""
         self._check(self.lib.vs_roll_correct_nv12_dev(self.h, d_in, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset))
+
+    def correct_p010_dev_n(self, d_ins, w, h, pitch, d_outs, out_pitch, uv_offset=0, out_uv_offset=0):
+        """n P010 surfaces in call order (lists of device pointers), one trip through the binding."""
+        n = len(d_ins)
+        a = (C.c_void_p * n)(*d_ins)
+        b = (C.c_void_p * n)(*d_outs)
+        self._check(self.lib.vs_roll_correct_p010_dev_n(self.h, a, b, n, w, h, pitch, uv_offset, out_pitch, out_uv_offset))
+
+    def correct_p010_dev(self, d_in, w, h, pitch, d_out, out_pitch, uv_offset=0, out_uv_offset=0):
+        """correct_nv12_dev for a P010 surface (vs_roll_correct_p010_dev): pitches and offsets in bytes, even."""
+        self._check(self.lib.vs_roll_correct_p010_dev(self.h, d_in, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset))
 
     def sync(self):
         self._check(self.lib.vs_roll_sync(self.h))
