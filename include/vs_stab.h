@@ -36,7 +36,9 @@ extern "C" {
  *    vs_pixfmt_planar) with vs_stab_set_i420_layout, vs_batch_set_i420_layout and vs_op_warp_affine_i420; VS_FMT_I010 and
  *    VS_FMT_I012 (enum vs_pixfmt_planar16) with vs_op_warp_affine_i010; roll correction and auto zoom/crop on P010 surfaces:
  *    vs_roll_correct_p010_dev, vs_roll_correct_p010_dev_n, vs_azc_apply_p010_dev, vs_azc_apply_p010_dev_n and
- *    vs_op_warp_affine16_ex. */
+ *    vs_op_warp_affine16_ex; the same two stages on I420 / I010 / I012 surfaces: struct vs_i420_layout with
+ *    vs_roll_correct_i420_dev, vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev and vs_azc_apply_i420_dev_n (new entry points
+ *    and a new struct only: no existing struct or entry point changed, so the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -87,8 +89,8 @@ typedef enum vs_pixfmt {
  *    plane scaled to its share of 640 x 360 by the reference's scale matrix; BORDER_CONSTANT 0, the same blend.  On the fall-back
  *    paths the surface comes back unchanged, all 16 bits;
  *  - low bits: nothing here assumes that the low six bits are zero either.
- * Not built: the C++ classes vs::RollCorrection / vs::AutoZoomCrop keep taking 8-bit cv::Mats, and I420 / I010 / I012 surfaces
- * do not go through these two stages. */
+ * Not built: the C++ classes vs::RollCorrection / vs::AutoZoomCrop keep taking 8-bit cv::Mats.  (I420 / I010 / I012 surfaces go
+ * through these two stages with entry points of their own: vs_pixfmt_planar, vs_pixfmt_planar16.) */
 typedef enum vs_pixfmt16 {
     VS_FMT_P010 = 6           /* Y plane (h rows of w uint16) followed by UV plane (h/2 rows of w/2 uint16 pairs) */
 } vs_pixfmt16;
@@ -109,7 +111,15 @@ typedef enum vs_pixfmt16 {
  *    in float (cv::warpAffine treats channels independently: these are the two channels of the NV12 chroma plane's warp),
  *    INTER_LINEAR, BORDER_CONSTANT 0;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are refused as for NV12 (VS_ERR_UNSUPPORTED); roll correction, AutoZoomCrop, the enhancer and the C++ class do not take it. */
+ *    are refused as for NV12 (VS_ERR_UNSUPPORTED); the enhancer and the C++ classes do not take it.
+ * The two stages around the stabilizer take I420 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev; layouts as
+ * struct vs_i420_layout): every observable is again that of the NV12 call on the same samples, the planes de-interleaved -
+ *  - analysis plane: Y itself (line search of the roll stage, content mask of the zoom stage);
+ *  - roll rotation: about the picture centre, BORDER_REPLICATE; Y under M, U and V each as a CV_8UC1 plane of w/2 x h/2 under M with
+ *    the translation halved (the chroma matrix of the NV12 path), vs_op_warp_affine_ex's arithmetic;
+ *  - zoom crop-and-scale: the rectangle as found for Y, halved for U and for V (x/2, y/2, max(1, w/2), max(1, h/2)); Y scaled to
+ *    640 x 360, U and V to 320 x 180 each by the reference's scale matrix, BORDER_CONSTANT 0; on the fall-back paths the surface
+ *    comes back unchanged, all three planes. */
 typedef enum vs_pixfmt_planar {
     VS_FMT_I420 = 7           /* Y plane (h rows of w), U plane, V plane (h/2 rows of w/2 each) */
 } vs_pixfmt_planar;
@@ -130,7 +140,17 @@ typedef enum vs_pixfmt_planar {
  *    halved in float; INTER_LINEAR, BORDER_CONSTANT 0, the blend of P010 to the letter (S rounded once, half to even).  The warp
  *    does not depend on the bit depth;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are VS_ERR_UNSUPPORTED; roll correction, AutoZoomCrop, the enhancer and the C++ class do not take these formats. */
+ *    are VS_ERR_UNSUPPORTED; the enhancer and the C++ classes do not take these formats.
+ * The two stages around the stabilizer take I010 / I012 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev with fmt
+ * VS_FMT_I010 / VS_FMT_I012):
+ *  - analysis plane: min(sample >> (bits - 8), 255) of Y, exactly the byte the stabilizer's analysis uses.  Smoothed and detected
+ *    angle, line counts, content mask (byte > 1), contours, info8 and the crop rectangle are those of the NV12 / GRAY8 call on
+ *    that plane;
+ *  - roll rotation: BORDER_REPLICATE, Y under M, U and V each as a CV_16UC1 plane of w/2 x h/2 under M with the translation
+ *    halved; P010's blend, S rounded once, half to even (vs_op_warp_affine16_ex, cn 1).  The rotation does not depend on the bit
+ *    depth, and it is NOT the P010 round trip's picture for out-of-range content (the one rounding does not commute with a shift);
+ *  - zoom crop-and-scale: the rectangle for Y, halved for U and V; 640 x 360 / 320 x 180 / 320 x 180, BORDER_CONSTANT 0, the same
+ *    blend; on the fall-back paths the surface comes back unchanged, all three planes, all 16 bits. */
 typedef enum vs_pixfmt_planar16 {
     VS_FMT_I010 = 8,          /* yuv420p10le: Y (h rows of w uint16), U, V (h/2 rows of w/2 uint16 each); value in bits 0..9  */
     VS_FMT_I012 = 9           /* yuv420p12le: the same planes, value in bits 0..11 */
@@ -634,6 +654,29 @@ int vs_roll_correct_p010_dev(vs_roll* r, const void* d_surface, int w, int h, si
                              void* d_out, size_t out_pitch, size_t out_uv_offset);
 int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                                size_t pitch, size_t uv_offset, size_t out_pitch, size_t out_uv_offset);
+/* Where the three planes of a planar 4:2:0 surface (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012) lie, in BYTES: rows of `pitch` bytes of
+ * Y at the surface pointer; U and V rows `c_pitch` bytes apart, the planes u_off / v_off bytes behind the surface pointer.  0 means
+ * the packed default for c_pitch (pitch / 2), u_off (behind the Y rows) and v_off (behind U) - the fields of
+ * vs_stab_set_i420_layout.  YV12: give both offsets, V first.  The roll and zoom entry points take one such struct for the surface
+ * and one for the result (a small POD by pointer, read during the call - not the eight plain size_t arguments the two layouts would
+ * otherwise be; vs_stab_set_i420_layout keeps its six plain arguments, its pitches travel with every push). */
+typedef struct vs_i420_layout {
+    size_t pitch;             /* bytes per Y row */
+    size_t c_pitch;           /* bytes per U / V row; 0 = pitch / 2 */
+    size_t u_off, v_off;      /* bytes from the surface pointer to the U / V plane; 0 = packed behind the plane before */
+} vs_i420_layout;
+/* autoCorrectRoll for planar 4:2:0 surfaces in HBM, ASYNCHRONOUS: vs_roll_correct_nv12_dev for fmt = VS_FMT_I420 (YV12 through the
+ * offsets), VS_FMT_I010 or VS_FMT_I012 (definitions: vs_pixfmt_planar, vs_pixfmt_planar16).  w and h even; for the 16-bit formats
+ * pointers, pitches and offsets even and the chroma pitch at least w bytes, for I420 at least w / 2; with c_pitch = 0 the pitch must
+ * be even (16-bit: a multiple of 4); the planes of a layout may not overlap.  Violations: VS_ERR_INVALID_ARG with a text that names the
+ * format (vs_roll_last_error).  Y, U and V of a batch's surfaces are rotated by ONE launch when the batch's results share a
+ * layout.  Batches of eight, worker threads, VS_ROLL_WORKERS, vs_roll_sync and vs_roll_get_state as for NV12.  One object may
+ * receive NV12, P010 and planar calls in any order: a change of format or of layout closes the pending batch exactly as a change
+ * of geometry does, the smoothed angle carries across. */
+int vs_roll_correct_i420_dev(vs_roll* r, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in,
+                             void* d_out, const vs_i420_layout* out);
+int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
+                               const vs_i420_layout* in, const vs_i420_layout* out);
 /* smoothed angle (sSmoothedAngle), the angle detected on the last frame, lines found / used */
 int vs_roll_get_state(const vs_roll* r, double* smoothed_deg, double* detected_deg,
                       int* n_lines, int* n_used);
@@ -697,6 +740,16 @@ int vs_azc_apply_p010_dev(vs_azc* a, const void* d_surface, int w, int h, size_t
                           void* d_out, size_t out_pitch, size_t out_uv_offset, int64_t* ticket);
 int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                             size_t pitch, size_t uv_offset, size_t out_pitch, size_t out_uv_offset, int64_t* tickets);
+/* The same for planar 4:2:0 surfaces: fmt = VS_FMT_I420 (YV12 through the offsets), VS_FMT_I010 or VS_FMT_I012; layouts and their
+ * rules as for vs_roll_correct_i420_dev.  d_out receives Y 640 x 360, U and V 320 x 180 each - or the unchanged surface - with the
+ * planes where `out` puts them whichever size comes out, so `out` describes a surface of max(w, 640) x max(h, 360): pitch >=
+ * max(w, 640) samples, u_off >= max(h, 360) * pitch, v_off >= u_off + max(h, 360) / 2 * c_pitch (or U behind V), and its zero
+ * fields default to the packed layout of that size.  The three planes of a batch's surfaces are cropped and scaled by ONE launch.
+ * Tickets, vs_azc_result, batches, worker threads and vs_azc_sync as for NV12; NV12, P010 and planar calls may alternate. */
+int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in,
+                          void* d_out, const vs_i420_layout* out, int64_t* ticket);
+int vs_azc_apply_i420_dev_n(vs_azc* a, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
+                            const vs_i420_layout* in, const vs_i420_layout* out, int64_t* tickets);
 int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* info8);
 /* Diagnostics of the asynchronous path: out9 = {frames through the worker threads; seconds, summed over the threads: without a
  * frame to work on, waiting for the masks of the batches on their way (one worker at a time does), in the contour logic, queueing

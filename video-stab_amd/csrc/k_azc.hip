@@ -23,7 +23,7 @@
 #include <deque>
 #include <thread>
 
-#include "vs_common.h"
+#include "launchers.h"
 
 namespace vsd {
 
@@ -144,6 +144,39 @@ __global__ __launch_bounds__(256) void threshold_bits_p010_kernel(size_t stride,
     if ((lane & 7) == 0 && word < wpr) T[(size_t)y * wpr + word] = bits;
 }
 
+// Pass 1 for the Y planes of I010 / I012 surfaces: the content mask is that of the 8-bit analysis plane min(sample >> shift, 255) (shift =
+// bits - 8: 2 or 4, a kernel argument as in k_gray.hip) - min(sample >> shift, 255) > 1, which is (sample >> shift) > 1: the saturation
+// cannot undo it.  All sixteen bits of a sample are looked at: out-of-range content is content.  The lane / wave / workgroup layout of
+// threshold_bits_p010_kernel: a lane takes 8 samples - WIDE: with ONE 16-byte load (width a multiple of 8 samples, rows 16-byte aligned);
+// else sample by sample, any width and any even pitch.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void threshold_bits_lo16_kernel(size_t stride, int w, int h, u64* __restrict__ T, int wpr, SrcList srcs, size_t tfb,
+                                                                  int shift) {
+    const uint8_t* __restrict__ src = srcs.p[blockIdx.z];
+    T += (size_t)blockIdx.z * tfb;
+    const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x = blockIdx.x * 512 + lane * 8, word = blockIdx.x * 8 + (lane >> 3);
+    if (y >= h) return;                                                  // (wave-uniform)
+    uint32_t m = 0;
+    const uint8_t* row = src + (size_t)y * stride;
+    if (WIDE) {
+        if (x < w) {                                                     // (w is a multiple of 8: the lane's samples are all inside or all outside)
+            const uint4 d = *reinterpret_cast<const uint4*>(row + (size_t)x * 2);
+            auto pair = [shift](uint32_t v) { return (((v & 0xFFFFu) >> shift) > 1u ? 1u : 0u) | ((v >> (16 + shift)) > 1u ? 2u : 0u); };
+            m = pair(d.x) | pair(d.y) << 2 | pair(d.z) << 4 | pair(d.w) << 6;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (x + i < w) m |= (((uint32_t)reinterpret_cast<const uint16_t*>(row)[x + i] >> shift) > 1u ? 1u : 0u) << i;
+    }
+    u64 bits = (u64)m << (8 * (lane & 7));
+    bits |= __shfl_xor(bits, 1);
+    bits |= __shfl_xor(bits, 2);
+    bits |= __shfl_xor(bits, 4);
+    if ((lane & 7) == 0 && word < wpr) T[(size_t)y * wpr + word] = bits;
+}
+
 constexpr int MC_ROWS = 56;      // rows a wave of the morphology pass owns (lanes 4..59; halo 4 above and below)
 
 // OR / AND of a row with itself moved by -2..2 pixels; l, r: the words left and right of it
@@ -202,11 +235,12 @@ __global__ __launch_bounds__(256) void expand_bits_kernel(const u64* __restrict_
 // oframe rows and words (1 for a BitFrame whose frame is already zero, 0 for a plain bit plane).
 // srcs (optional, d_src == nullptr): `frames` <= SRC_LIST_MAX source pointers on the HOST, one geometry and pitch; the pictures'
 // bit planes / results lie tfb / ofb words apart.
-// sb = 2 (a table of sources, cn 1): luma planes of 16-bit samples, the mask of their high bytes; stride in bytes, everything even.
+// sb = 2 (a table of sources, cn 1): luma planes of 16-bit samples, the mask of their high bytes - or, lo_shift > 0 (I010: 2, I012: 4),
+// of min(sample >> lo_shift, 255); stride in bytes, everything even.
 int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int cn, u64* d_T, u64* d_out, int opitch,
                         int oframe, hipStream_t st, const uint8_t* const* srcs = nullptr, int frames = 1, size_t tfb = 0, size_t ofb = 0,
-                        int srcs_aligned = 0, int sb = 1) {
-    if ((sb != 1 && sb != 2) || (sb == 2 && (d_src || cn != 1)) || (!d_src && !srcs) || (!d_src && frames > SRC_LIST_MAX) || !d_T || !d_out || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || frames < 1) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
+                        int srcs_aligned = 0, int sb = 1, int lo_shift = 0) {
+    if ((sb != 1 && sb != 2) || lo_shift < 0 || lo_shift > 8 || (lo_shift && sb != 2) || (sb == 2 && (d_src || cn != 1)) || (!d_src && !srcs) || (!d_src && frames > SRC_LIST_MAX) || !d_T || !d_out || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || frames < 1) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
     if (h > 65535) { set_last_error("content_mask: image too tall"); return VS_ERR_INVALID_ARG; }
     const int wpr = (w + 63) / 64;
     // (a table of sources: srcs_aligned = every one of them is 4-byte aligned)
@@ -216,7 +250,11 @@ int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int c
     dim3 g1((w + 1023) / 1024, h, frames);
     bool wide = !d_src && cn == 1 && (w & (sb == 2 ? 7 : 15)) == 0 && (stride & 15) == 0;
     for (int i = 0; wide && i < frames; i++) wide = ((uintptr_t)srcs[i] & 15) == 0;
-    if (sb == 2) {
+    if (sb == 2 && lo_shift) {
+        const dim3 g((w + 511) / 512, (h + 3) / 4, frames);
+        if (wide) hipLaunchKernelGGL(threshold_bits_lo16_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb, lo_shift);
+        else hipLaunchKernelGGL(threshold_bits_lo16_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb, lo_shift);
+    } else if (sb == 2) {
         const dim3 g((w + 511) / 512, (h + 3) / 4, frames);
         if (wide) hipLaunchKernelGGL(threshold_bits_p010_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
         else hipLaunchKernelGGL(threshold_bits_p010_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
@@ -254,9 +292,11 @@ struct vs_azc {
     // cv::findContours) - runs on worker threads, a frame each (frames do not depend on each other; 0.3 ms per 4K frame and
     // thread); the worker that finishes a batch's last contour queues the crop-and-scale of the batch's surfaces, both planes, as
     // one launch.  NBS batches in flight.
-    static constexpr int ZB = 8, NBS = 4, NRES = 1024;      // (ZB <= SRC_LIST_MAX, 2 ZB <= WARP_JOBS_MAX)
+    static constexpr int ZB = 8, NBS = 4, NRES = 1024;      // (ZB <= SRC_LIST_MAX, 3 ZB <= WARP_JOBS_MAX: three planes of a planar surface)
     int nw = 12;                         // worker threads (VS_AZC_WORKERS, 1 .. 16): 31 k frames/s alone with eight, 41 k with twelve
-    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; };     // sb: bytes of a sample (1 NV12, 2 P010)
+    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420,
+    // VS_FMT_I010, VS_FMT_I012) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
+    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; int planar; I420Layout sl, dl; };
     struct BatchSlot {
         uint8_t* d_masks = nullptr;      // ZB BitFrames
         uint8_t* h_masks = nullptr;      // page-locked
@@ -267,7 +307,7 @@ struct vs_azc {
         int mw = 0, mh = 0;
         int n = 0, left = 0;             // frames of the batch / n until the batch's crop-and-scale has been queued, then 0 (slot free)
         int todo = 0, nwj = 0;           // host parts not yet through / crop-and-scale jobs collected (wj)
-        WarpJob wj[2 * ZB];
+        WarpJob wj[3 * ZB];
         int arrived = 0;                 // the masks: 0 on their way, 2 there, 3 the wait for them failed
         std::chrono::steady_clock::time_point t_issue, t_arrive;
         Frame fr[ZB];
@@ -292,7 +332,7 @@ struct vs_azc {
                                          // the caller waited for a free batch slot
 };
 
-static_assert(vs_azc::ZB <= SRC_LIST_MAX && 2 * vs_azc::ZB <= WARP_JOBS_MAX, "a batch's sources and warp jobs travel as kernel arguments");
+static_assert(vs_azc::ZB <= SRC_LIST_MAX && 3 * vs_azc::ZB <= WARP_JOBS_MAX, "a batch's sources and warp jobs travel as kernel arguments");
 
 extern "C" {
 
@@ -535,8 +575,8 @@ static void azc_worker(vs_azc* a) {
         vs_azc::Result res;
         res.ticket = q.ticket;
         int rc = b.arrived == 3 ? VS_ERR_HIP : VS_OK;
-        WarpJob wj[2];
-        bool scaled = false;
+        WarpJob wj[3];
+        int nscaled = 0;                 // crop-and-scale jobs of this frame: 2 (NV12 / P010), 3 (planar), 0 on the fall-back paths
         const clk::time_point t_masks = clk::now();
         clk::time_point t_contour = t_masks;
         t_job = t_job > t_masks ? t_masks : t_job;
@@ -548,7 +588,13 @@ static void azc_worker(vs_azc* a) {
             t_contour = clk::now();
             if (!res.info[7]) {                                                                            // :149-152, :238-249
                 res.out_w = q.w; res.out_h = q.h;
-                if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
+                if (q.planar) {          // the unchanged surface, all three planes
+                    const size_t cw = (size_t)(q.w / 2) * q.sb;
+                    if (hipMemcpy2DAsync(q.dst, q.dl.pitch, q.src, q.sl.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
+                        hipMemcpy2DAsync(q.dst + q.dl.u, q.dl.cpitch, q.src + q.sl.u, q.sl.cpitch, cw, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
+                        hipMemcpy2DAsync(q.dst + q.dl.v, q.dl.cpitch, q.src + q.sl.v, q.sl.cpitch, cw, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
+                        rc = VS_ERR_HIP;
+                } else if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
                     hipMemcpy2DAsync(q.dst + q.ouv, q.opitch, q.src + q.uv, q.pitch, (size_t)q.w * q.sb, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
                     rc = VS_ERR_HIP;
             } else {
@@ -561,10 +607,21 @@ static void azc_worker(vs_azc* a) {
                 warp_invert(Mu, wj[1].m);
                 wj[0].src = q.src + (size_t)cy * q.pitch + (size_t)cx * q.sb; wj[0].dst = q.dst;
                 wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = 640; wj[0].dh = 360; wj[0].cn = 1;
-                wj[1].src = q.src + q.uv + (size_t)uy * q.pitch + (size_t)ux * 2 * q.sb; wj[1].dst = q.dst + q.ouv;
-                wj[1].sw = uw; wj[1].sh = uh; wj[1].dw = 320; wj[1].dh = 180; wj[1].cn = 2;
                 for (WarpJob& w : wj) { w.sstride = (uint32_t)q.pitch; w.dstride = (uint32_t)q.opitch; w.border = VS_BORDER_BLACK; w.sb = q.sb; }
-                scaled = true;
+                if (q.planar) {          // U and V: one-channel planes of half the size, the halved rectangle, rows of their own pitch
+                    warp_invert(Mu, wj[2].m);
+                    wj[1].src = q.src + q.sl.u + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[1].dst = q.dst + q.dl.u;
+                    wj[2].src = q.src + q.sl.v + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[2].dst = q.dst + q.dl.v;
+                    for (int k = 1; k < 3; k++) {
+                        wj[k].sw = uw; wj[k].sh = uh; wj[k].dw = 320; wj[k].dh = 180; wj[k].cn = 1;
+                        wj[k].sstride = (uint32_t)q.sl.cpitch; wj[k].dstride = (uint32_t)q.dl.cpitch;
+                    }
+                    nscaled = 3;
+                } else {
+                    wj[1].src = q.src + q.uv + (size_t)uy * q.pitch + (size_t)ux * 2 * q.sb; wj[1].dst = q.dst + q.ouv;
+                    wj[1].sw = uw; wj[1].sh = uh; wj[1].dw = 320; wj[1].dh = 180; wj[1].cn = 2;
+                    nscaled = 2;
+                }
             }
         }
         res.rc = rc;
@@ -572,11 +629,11 @@ static void azc_worker(vs_azc* a) {
         // last contour; a frame counts as complete (vs_azc_sync) when that launch has been queued.
         bool last;
         int njobs = 0;
-        WarpJob all[2 * vs_azc::ZB];
+        WarpJob all[3 * vs_azc::ZB];
         {
             std::lock_guard<std::mutex> g(a->mu);
             azc_publish(a, res);
-            if (scaled) { b.wj[b.nwj++] = wj[0]; b.wj[b.nwj++] = wj[1]; }
+            for (int k = 0; k < nscaled; k++) b.wj[b.nwj++] = wj[k];
             last = --b.todo == 0;
             if (last) { njobs = b.nwj; memcpy(all, b.wj, sizeof(WarpJob) * njobs); }
         }
@@ -637,7 +694,8 @@ static int azc_issue_batch(vs_azc* a, std::unique_lock<std::mutex>& lk) {
         if ((uintptr_t)a->pending[i].src & 3) aligned = 0;
     }
     VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, 1, b.d_tbits, (u64*)b.d_masks, BitFrame::pitch_for(w), 1, b.st, srcs, n, tw,
-                                 mb / 8, aligned, a->pending[0].sb));                                                                              // :111-139 on the luma planes
+                                 mb / 8, aligned, a->pending[0].sb,
+                                 a->pending[0].planar == VS_FMT_I010 ? 2 : a->pending[0].planar == VS_FMT_I012 ? 4 : 0));                                                                              // :111-139 on the luma planes
     VS_OBJ_HIP(a, hipMemcpyAsync(b.h_masks, b.d_masks, mb * n, hipMemcpyDeviceToHost, b.st));                                          // :142-143
     VS_OBJ_HIP(a, hipEventRecord(b.ev, b.st));
     b.t_issue = std::chrono::steady_clock::now();
@@ -675,12 +733,14 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
 // vs_azc_result(ticket) tells what came out (it waits for that frame's host part), the pixels are complete after vs_azc_sync.
 // Surface and result buffer must stay untouched until then; results of the last 1024 tickets are kept.
 // (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
+// (planar: 0, or the format of a three-plane surface whose layouts are sl / dl, checked by the caller - uv_offset / out_uv_offset repeat
+// their U offsets)
 static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                         size_t out_uv_offset, int64_t* ticket, int sb) {
+                         size_t out_uv_offset, int64_t* ticket, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout()) {
     if (!a || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)std::max(w, 640) * sb ||
         out_uv_offset < (size_t)std::max(h, 360) * out_pitch)
         return VS_ERR_INVALID_ARG;
-    if (sb == 2 && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
+    if (sb == 2 && !planar && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: P010 pointers, pitches and plane offsets must be even");
     if (w > 65535 || h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
     if (uv_offset == 0) uv_offset = (size_t)h * pitch;
@@ -695,12 +755,17 @@ static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t 
         }
     }
     std::unique_lock<std::mutex> lk(a->mu);
-    // (a change of geometry or of sample size closes the pending batch: a batch's launches take one of each)
-    if (!a->pending.empty() && (a->pending[0].w != w || a->pending[0].h != h || a->pending[0].pitch != pitch || a->pending[0].sb != sb)) {
-        const int rc = azc_flush_pending(a, lk);
-        if (rc != VS_OK) return rc;
+    // (a change of geometry, of sample size, of format or of a planar surface's layouts closes the pending batch: a batch's launches
+    // take one of each)
+    if (!a->pending.empty()) {
+        const vs_azc::Frame& p0 = a->pending[0];
+        auto same = [](const I420Layout& x, const I420Layout& y) { return x.pitch == y.pitch && x.cpitch == y.cpitch && x.u == y.u && x.v == y.v; };
+        if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar || (planar && (!same(p0.sl, sl) || !same(p0.dl, dl)))) {
+            const int rc = azc_flush_pending(a, lk);
+            if (rc != VS_OK) return rc;
+        }
     }
-    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb});
+    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb, planar, sl, dl});
     if (ticket) *ticket = a->issued;
     a->issued++;
     if ((int)a->pending.size() >= vs_azc::ZB) return azc_flush_pending(a, lk);
@@ -727,6 +792,35 @@ int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* cons
     if (!a || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
     for (int i = 0; i < n; i++) {
         const int rc = vs_azc_apply_p010_dev(a, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset, tickets ? tickets + i : nullptr);
+        if (rc != VS_OK) return rc;
+    }
+    return VS_OK;
+}
+
+// The same for a planar 4:2:0 surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010 or VS_FMT_I012; in / out: where
+// the three planes lie (vs_i420_layout: bytes, 0 = the packed default for the chroma pitch and the offsets).  The content mask comes from
+// the 8-bit analysis plane of Y - Y itself, or min(sample >> (bits - 8), 255) -; the rectangle applies to Y as it is and, halved, to U and
+// to V, each scaled to 320 x 180 as a one-channel plane: the three planes of a batch's surfaces are one launch.  The result's planes lie
+// where `out` puts them whichever size comes out, so `out` must hold max(w, 640) x max(h, 360): its defaults are those of a surface of
+// that size.  An I420 result is the de-interleaved result of vs_azc_apply_nv12_dev on the same samples.
+int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in, void* d_out, const vs_i420_layout* out,
+                          int64_t* ticket) {
+    if (!a || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
+    if (fmt != VS_FMT_I420 && fmt != VS_FMT_I010 && fmt != VS_FMT_I012)
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: the planar entry point takes VS_FMT_I420, VS_FMT_I010 or VS_FMT_I012");
+    I420Layout sl, dl;
+    std::string msg;
+    if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "auto zoom/crop", &sl, &msg) != VS_OK ||
+        planar_layout_check(fmt, d_out, w, h, out, std::max(w, 640), std::max(h, 360), "auto zoom/crop (result: max(w, 640) x max(h, 360))", &dl, &msg) != VS_OK)
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, msg.c_str());
+    return azc_hand_over(a, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, ticket, fmt == VS_FMT_I420 ? 1 : 2, fmt, sl, dl);
+}
+
+int vs_azc_apply_i420_dev_n(vs_azc* a, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, const vs_i420_layout* in,
+                            const vs_i420_layout* out, int64_t* tickets) {
+    if (!a || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) {
+        const int rc = vs_azc_apply_i420_dev(a, fmt, d_surfaces[i], w, h, in, d_outs[i], out, tickets ? tickets + i : nullptr);
         if (rc != VS_OK) return rc;
     }
     return VS_OK;

@@ -33,7 +33,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "vs_common.h"
+#include "launchers.h"
 
 namespace vsd {
 
@@ -639,7 +639,9 @@ struct vs_roll {
     int nwk = 5;                         // worker threads in use (VS_ROLL_WORKERS, 1 .. NWK): alone three are as fast as eight (36 - 38 k
                                          // frames/s); beside a stabilizer on the same GPU a batch's launches wait behind its workgroups, and five
                                          // batches in flight keep the stage at 3.4 ms per 128 surfaces where three need 5.5 (gpurun_out/r04_ai)
-    struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; int sb; };      // sb: bytes of a sample (1 NV12, 2 P010)
+    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420,
+    // VS_FMT_I010, VS_FMT_I012) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
+    struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; int sb; int planar; I420Layout sl, dl; };
     struct Slot {
         RollWork wk;                     // RB frames
         hipStream_t st = nullptr;
@@ -879,8 +881,10 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
     k.base = nullptr; k.frames = n;
     for (int f = 0; f < n; f++) { q.h_pairs[f].src = jobs[f].src; q.h_pairs[f].dst = k.gray + (size_t)f * k.fb; }
     VS_HIP_TRY(hipMemcpyAsync(q.d_pairs, q.h_pairs, sizeof(ImgPair) * n, hipMemcpyHostToDevice, q.st));
-    // (P010: the analysis image is that of the luma samples' high bytes - the 16-bit gray kernels of k_gray.hip read nothing else)
-    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, j0.sb == 2 ? (int)VS_FMT_P010 : (int)VS_FMT_GRAY8, sw, sw, sh, 0, q.st));   // :41
+    // (P010: the analysis image is that of the luma samples' high bytes - the 16-bit gray kernels of k_gray.hip read nothing else;
+    // I010 / I012: that of min(sample >> (bits - 8), 255), the low-bits kernels; the Y plane of an I420 surface is a gray picture)
+    const int gfmt = j0.planar && j0.sb == 2 ? j0.planar : j0.sb == 2 ? (int)VS_FMT_P010 : (int)VS_FMT_GRAY8;
+    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, gfmt, sw, sw, sh, 0, q.st));   // :41
     // (twelve hysteresis passes per batch - a pass whose predecessor changed nothing for its frame returns at once: with four, 40 % of
     // the bench clip's frames had to finish their growth one by one behind the batch, 30 us per frame)
     constexpr int PASSES = 12;
@@ -926,6 +930,21 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
         warp_invert(Mc, Minv + 12 * f + 6);
         ys[f] = j.src; us[f] = j.src + j.uv; yd[f] = j.dst; ud[f] = j.dst + j.ouv;
         one_launch &= j.opitch == j0.opitch && j.uv == j0.uv && j.ouv == j0.ouv;
+        if (j0.planar) one_launch &= j.dl.cpitch == j0.dl.cpitch && j.dl.u == j0.dl.u && j.dl.v == j0.dl.v;
+    }
+    // planar 4:2:0 (a batch holds one format and one source layout): Y, U and V tiles of all its surfaces in ONE grid (warp_i420_kernel
+    // with the BORDER_REPLICATE staging, 8- or 16-bit samples) when the results share one layout, else frame by frame; U and V both
+    // take the chroma map
+    if (j0.planar) {
+        if (one_launch)
+            return launch_warp_i420(ys, yd, n, j0.sl, j0.dl, j0.w, j0.h, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE, WarpTabs{WarpTabs::SCRATCH},
+                                    r->st, j0.sb);
+        for (int f = 0; f < n; f++) {
+            const vs_roll::Job& j = jobs[f];
+            VS_TRY(launch_warp_i420(ys + f, yd + f, 1, j.sl, j.dl, j.w, j.h, WarpMaps{Minv + 12 * f, 12, true}, VS_BORDER_REPLICATE,
+                                    WarpTabs{WarpTabs::SCRATCH}, r->st, j.sb));
+        }
+        return VS_OK;
     }
     // the rotations of the batch (:146-149): luma and chroma tiles of all its surfaces in ONE grid (warp_nv12_kernel with the
     // BORDER_REPLICATE staging; P010: its instance for 16-bit samples) when the results share one layout (the surfaces do), else
@@ -981,10 +1000,11 @@ static void roll_flush_pending(vs_roll* r) {
 // after vs_roll_sync (which also closes an incomplete batch).  The surface and the result buffer of a call must stay untouched
 // until then.
 // (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
+// (planar: 0, or the format of a three-plane surface whose layouts are sl / dl - uv_offset / out_uv_offset are then unused)
 static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                          size_t out_uv_offset, int sb) {
+                          size_t out_uv_offset, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout()) {
     if (!r || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)w * sb) return VS_ERR_INVALID_ARG;
-    if (sb == 2 && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
+    if (sb == 2 && !planar && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
         return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: P010 pointers, pitches and plane offsets must be even");
     if (uv_offset == 0) uv_offset = (size_t)h * pitch;
     if (out_uv_offset == 0) out_uv_offset = (size_t)h * out_pitch;
@@ -1001,9 +1021,15 @@ static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_
         std::unique_lock<std::mutex> lk(r->mu);
         if (r->first) { r->first = false; r->smoothed = 0.0; }                                   // :24-27
         r->cv_done.wait(lk, [&] { return r->nv_in - r->nv_done < vs_roll::QMAX; });
-        // (a change of geometry or of sample size closes the pending batch: a batch's launches take one of each)
-        if (!r->pending.empty() && (r->pending[0].w != w || r->pending[0].h != h || r->pending[0].pitch != pitch || r->pending[0].sb != sb)) roll_flush_pending(r);
-        r->pending.push_back(vs_roll::Job{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, r->nv_in, sb});
+        // (a change of geometry, of sample size, of format or of a planar surface's source layout closes the pending batch: a batch's
+        // launches take one of each)
+        if (!r->pending.empty()) {
+            const vs_roll::Job& p0 = r->pending[0];
+            if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar ||
+                (planar && (p0.sl.cpitch != sl.cpitch || p0.sl.u != sl.u || p0.sl.v != sl.v)))
+                roll_flush_pending(r);
+        }
+        r->pending.push_back(vs_roll::Job{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, r->nv_in, sb, planar, sl, dl});
         r->nv_in++;
         if ((int)r->pending.size() >= vs_roll::RB) roll_flush_pending(r);
     }
@@ -1030,6 +1056,32 @@ int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* 
     if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
     for (int i = 0; i < n; i++) {
         const int rc = vs_roll_correct_p010_dev(r, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset);
+        if (rc != VS_OK) return rc;
+    }
+    return VS_OK;
+}
+
+// The same for a planar 4:2:0 surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010 or VS_FMT_I012; in / out: where
+// the three planes lie (vs_i420_layout: bytes, 0 = the packed default for the chroma pitch and the offsets).  The line search runs on the
+// 8-bit analysis plane of Y - Y itself, or min(sample >> (bits - 8), 255) -, the rotation is applied to Y with M and to U and V, each a
+// one-channel plane of half the size, with the translation halved: Y, U and V tiles of a batch in one launch.  An I420 result is the
+// de-interleaved result of vs_roll_correct_nv12_dev on the same samples.  NV12, P010 and planar surfaces may alternate on one object.
+int vs_roll_correct_i420_dev(vs_roll* r, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in, void* d_out, const vs_i420_layout* out) {
+    if (!r || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
+    if (fmt != VS_FMT_I420 && fmt != VS_FMT_I010 && fmt != VS_FMT_I012)
+        return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: the planar entry point takes VS_FMT_I420, VS_FMT_I010 or VS_FMT_I012");
+    I420Layout sl, dl;
+    std::string msg;
+    if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "roll", &sl, &msg) != VS_OK || planar_layout_check(fmt, d_out, w, h, out, w, h, "roll (result)", &dl, &msg) != VS_OK)
+        return vs_obj_fail(r, VS_ERR_INVALID_ARG, msg.c_str());
+    return roll_hand_over(r, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, fmt == VS_FMT_I420 ? 1 : 2, fmt, sl, dl);
+}
+
+int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, const vs_i420_layout* in,
+                               const vs_i420_layout* out) {
+    if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) {
+        const int rc = vs_roll_correct_i420_dev(r, fmt, d_surfaces[i], w, h, in, d_outs[i], out);
         if (rc != VS_OK) return rc;
     }
     return VS_OK;

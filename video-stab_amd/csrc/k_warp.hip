@@ -642,6 +642,7 @@ __global__ __launch_bounds__(NT) void warp_affine16_kernel(WarpArgs a) {
 // general kernel's direct path (no staging: a scale map spreads the taps of a tile over a box that no staging area holds).
 // SB = 2: jobs on planes of 16-bit samples (the crop-and-scale of P010 surfaces: cn 1 and 2, P010's blend) - a kernel of its own,
 // so that the 8-bit launch keeps its code and its registers; the jobs of a launch share one sample size.
+// Planar 4:2:0 surfaces (I420 / I010 / I012) are three jobs of cn 1 each: 3 x 8 = WARP_JOBS_MAX jobs per batch, still one launch.
 struct WarpJobsArg { WarpJob j[WARP_JOBS_MAX]; };
 
 template <int SB>
@@ -1211,7 +1212,9 @@ __device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint
 // this tile belongs to (wave-uniform).
 // BORDER: what the staged box holds where it leaves the picture - zeros (cv::warpAffine BORDER_CONSTANT: the stabilizer's warp) or the
 // nearest picture pixel (BORDER_REPLICATE: the roll stage's rotation); a launch whose border is the other one takes the direct path.
-template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1>
+// OWN: the 16-bit BORDER_REPLICATE instance of the kernel that says so calls a plane_direct_tile copy of its own (sharing one copy
+// between two kernels changes the register allocation of both: the kernels that exist keep their code).
+template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1, int OWN = 0>
 __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
                                            uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add = 0, int dst_add = 0) {
     typedef PlaneCfg<CN, SB> P;
@@ -1321,7 +1324,7 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
     }
     if (!fit) {
         if constexpr (CN == 4) plane_direct_tile4(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
-        else plane_direct_tile<CN, SB, (SB == 2 && BORDER == VS_BORDER_REPLICATE ? 1 : 0)>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        else plane_direct_tile<CN, SB, (SB == 2 && BORDER == VS_BORDER_REPLICATE ? 1 + OWN : 0)>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
         return;
     }
     __syncthreads();
@@ -1410,7 +1413,8 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
 // the per-plane kernels).  mtpf = ceil(2^32 / tiles per frame), mgx1 / mgx2 likewise for the tile columns of Y and of U / V.
 // SB = 2: I010 / I012 surfaces - the same sequence, grid order, table blocks and arguments; three planes of 16-bit samples
 // (PlaneCfg<1, 2>: tiles of 128 x 32 pixels, the staged box of the P010 luma plane).  Pitches, V - U and the alignment flags stay
-// in bytes: plane_tile adds the plane distances to byte pointers.
+// in bytes: plane_tile adds the plane distances to byte pointers.  BORDER_REPLICATE with SB = 2 (the roll stage's rotation of
+// I010 / I012 surfaces) is plane_tile<1, VS_BORDER_REPLICATE, 2>, the luma half of warp_nv12_kernel<VS_BORDER_REPLICATE, 2>.
 template <int BORDER, int SB = 1>
 __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
                                                        uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
@@ -1454,7 +1458,11 @@ __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_s
     }
     const TabLayout L = tab_layout(c.dw, c.dh);
     const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
-    plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
+    // (the 16-bit BORDER_REPLICATE instance: a direct-path callee of its own, see plane_tile; the others instantiate what they did)
+    if constexpr (SB == 2 && BORDER == VS_BORDER_REPLICATE)
+        plane_tile<1, BORDER, SB, 1>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
+    else
+        plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
 }
 
 // Ints of table workspace per frame of dw x dh (see warp_tables_kernel).
@@ -1647,8 +1655,7 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
 // VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420Layout& sl, const I420Layout& dl, int w, int h, const int32_t* d_tabs,
                 int border, hipStream_t st, int sb = 1) {
-    // (sb = 2, I010 / I012: tiles of half the rows; no BORDER_REPLICATE instance, as for P010)
-    if (sb == 2 && border != VS_BORDER_BLACK) return VS_ERR_UNSUPPORTED;
+    // (sb = 2, I010 / I012: tiles of half the rows; BORDER_REPLICATE: the roll stage's rotation of I010 / I012 surfaces)
     const int thp = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP;
     const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp - 1) / thp, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + thp - 1) / thp;
     const unsigned long long tpf = gx1 * gy1 + 2 * gx2 * gy2, total = tpf * (unsigned long long)n;
@@ -1671,7 +1678,11 @@ int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420L
     const uint32_t flags = (al & 3u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    if (sb == 2)
+    if (sb == 2 && border == VS_BORDER_REPLICATE)
+        hipLaunchKernelGGL((warp_i420_kernel<VS_BORDER_REPLICATE, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
+                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
+                           (int32_t)dvu);
+    else if (sb == 2)
         hipLaunchKernelGGL((warp_i420_kernel<VS_BORDER_BLACK, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
                            (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
                            (int32_t)dvu);
@@ -1784,7 +1795,7 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
 // the NV12 table launch; else one table launch per plane -, then all three planes in ONE grid.  A launch without tables (a caller's
 // tables exist for launches of WARP_TAB_MIN surfaces and more only; the scratch tables serve any number), or one whose geometry is
 // outside what warp_i420_kernel packs, goes plane by plane through the general kernels: V from the maps, without a table.
-// sb = 2: I010 / I012 surfaces - the layouts stay in bytes; a launch with BORDER_REPLICATE goes plane by plane.
+// sb = 2: I010 / I012 surfaces - the layouts stay in bytes.
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout sl, I420Layout dl, int w, int h, WarpMaps maps, int border,
                      WarpTabs tabs, hipStream_t st, int sb) {
     if (n < 1 || !ys || !yd || w < 2 || h < 2 || (w & 1) || (h & 1) || (sb != 1 && sb != 2) ||

@@ -4,6 +4,9 @@
 #ifndef VS_LAUNCHERS_H
 #define VS_LAUNCHERS_H
 
+#include <algorithm>
+#include <string>
+
 #include "traj_state.h"
 #include "vs_common.h"
 #include "warp_tab.h"
@@ -63,6 +66,29 @@ inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, s
 // sample_bytes = 2: I010 / I012 surfaces - the same planes with 16-bit samples; layouts in bytes, pointers, pitches and offsets even.
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout src, I420Layout dst, int w, int h, WarpMaps maps, int border,
                      WarpTabs tabs, hipStream_t st, int sample_bytes = 1);
+
+// ---- k_roll.hip, k_azc.hip: planar 4:2:0 surfaces (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012) of the stages around the stabilizer
+inline const char* planar_name(int fmt) { return fmt == VS_FMT_I420 ? "I420" : fmt == VS_FMT_I010 ? "I010" : "I012"; }
+
+// The geometry and layout rules of a planar surface handed to the roll / zoom stages (those vs_stab enforces).  need_w / need_h: the
+// samples per row and the rows the layout must hold - the picture's, or for the zoom stage's result the larger of the picture's and
+// 640 x 360.  Fills *l with the defaults resolved, or *msg with a text that names the stage and the format.
+inline int planar_layout_check(int fmt, const void* ptr, int w, int h, const vs_i420_layout* in, int need_w, int need_h, const char* stage,
+                               I420Layout* l, std::string* msg) {
+    const int sb = fmt == VS_FMT_I420 ? 1 : 2;
+    const char* name = planar_name(fmt);
+    auto fail = [&](const char* what) { *msg = std::string(stage) + ": " + name + ": " + what; return (int)VS_ERR_INVALID_ARG; };
+    if ((w & 1) || (h & 1) || w < 2 || h < 2) return fail("w and h must be even");
+    if (!in || in->pitch < (size_t)need_w * sb) return fail("the pitch must hold a row of the picture");
+    if (sb == 2 && (((uintptr_t)ptr | in->pitch | in->c_pitch | in->u_off | in->v_off) & 1)) return fail("pointers, pitches and plane offsets must be even (16-bit samples)");
+    if (!in->c_pitch && (in->pitch & (size_t)(2 * sb - 1))) return fail(sb == 2 ? "the default chroma pitch needs a pitch that is a multiple of 4" : "the default chroma pitch needs an even pitch");
+    *l = i420_layout(in->pitch, need_h, in->u_off, in->v_off, in->c_pitch);
+    if (l->cpitch < (size_t)(need_w / 2) * sb) return fail(sb == 2 ? "the chroma pitch must be at least w bytes" : "the chroma pitch must be at least w / 2");
+    if (l->u < (size_t)need_h * l->pitch || l->v < (size_t)need_h * l->pitch) return fail("the chroma planes must start behind the luma rows");
+    const size_t cb = (size_t)(need_h / 2) * l->cpitch, lo = std::min(l->u, l->v), hi = std::max(l->u, l->v);
+    if (hi < lo + cb) return fail("the U and V planes overlap");
+    return VS_OK;
+}
 
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,

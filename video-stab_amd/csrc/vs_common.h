@@ -178,7 +178,9 @@ struct WarpJob {
     double m[6];
     int32_t sb = 1;              // bytes of a sample: 1, or 2 (planes of 16-bit samples, cn 1 or 2, P010's blend); one value per launch
 };
-constexpr int WARP_JOBS_MAX = 16;
+// (24: the three planes of eight planar 4:2:0 surfaces - the table travels as a kernel argument, 24 x 104 = 2496 of the 4096 bytes
+// a launch may carry)
+constexpr int WARP_JOBS_MAX = 24;
 int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st);
 int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int fmt,
                        uint8_t* d_dst, size_t dstride, int dw, int dh, hipStream_t st);

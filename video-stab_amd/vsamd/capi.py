@@ -373,6 +373,11 @@ class VsLib:
         L.vs_roll_correct_p010_dev_n.argtypes = L.vs_roll_correct_nv12_dev_n.argtypes
         L.vs_azc_apply_p010_dev.argtypes = L.vs_azc_apply_nv12_dev.argtypes
         L.vs_azc_apply_p010_dev_n.argtypes = L.vs_azc_apply_nv12_dev_n.argtypes
+        lp = C.POINTER(I420LayoutC)
+        L.vs_roll_correct_i420_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, lp, vp, lp]
+        L.vs_roll_correct_i420_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, lp, lp]
+        L.vs_azc_apply_i420_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, lp, vp, lp, C.POINTER(C.c_int64)]
+        L.vs_azc_apply_i420_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, lp, lp, C.POINTER(C.c_int64)]
 
     # ---- helpers ----------------------------------------------------------
     def check(self, status, inst=None):
@@ -685,6 +690,15 @@ class VsLib:
         return Stabilizer(self, params, device)
 
 
+class I420LayoutC(C.Structure):
+    """struct vs_i420_layout: where the planes of an I420 / I010 / I012 surface lie, in bytes (0 = the packed default of a field)."""
+    _fields_ = [("pitch", C.c_size_t), ("c_pitch", C.c_size_t), ("u_off", C.c_size_t), ("v_off", C.c_size_t)]
+
+
+def i420_layout(pitch, c_pitch=0, u_off=0, v_off=0):
+    return I420LayoutC(pitch, c_pitch, u_off, v_off)
+
+
 class AutoZoomCrop:
     """C-ABI mirror of vs::AutoZoomCrop::autoZoomCrop (AutoZoomCrop.cpp:102-283)."""
 
@@ -750,6 +764,21 @@ class AutoZoomCrop:
         b = (C.c_void_p * n)(*d_outs)
         t = (C.c_int64 * n)()
         self._check(self.lib.vs_azc_apply_p010_dev_n(self.h, a, b, n, w, h, pitch, uv_offset, out_pitch, out_uv_offset, t))
+        return list(t)
+
+    def apply_i420_dev(self, fmt, d_in, w, h, lin, d_out, lout):
+        """apply_nv12_dev for a planar surface (vs_azc_apply_i420_dev): fmt FMT_I420 / FMT_I010 / FMT_I012, lin / lout: i420_layout()."""
+        t = C.c_int64(-1)
+        self._check(self.lib.vs_azc_apply_i420_dev(self.h, fmt, d_in, w, h, C.byref(lin), d_out, C.byref(lout), C.byref(t)))
+        return t.value
+
+    def apply_i420_dev_n(self, fmt, d_ins, w, h, lin, d_outs, lout):
+        """n planar surfaces in call order, one trip through the binding; returns the tickets."""
+        n = len(d_ins)
+        a = (C.c_void_p * n)(*d_ins)
+        b = (C.c_void_p * n)(*d_outs)
+        t = (C.c_int64 * n)()
+        self._check(self.lib.vs_azc_apply_i420_dev_n(self.h, fmt, a, b, n, w, h, C.byref(lin), C.byref(lout), t))
         return list(t)
 
     def result(self, ticket):
@@ -1003,6 +1032,17 @@ class RollCorrection:
     def correct_p010_dev(self, d_in, w, h, pitch, d_out, out_pitch, uv_offset=0, out_uv_offset=0):
         """correct_nv12_dev for a P010 surface (vs_roll_correct_p010_dev): pitches and offsets in bytes, even."""
         self._check(self.lib.vs_roll_correct_p010_dev(self.h, d_in, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset))
+
+    def correct_i420_dev(self, fmt, d_in, w, h, lin, d_out, lout):
+        """correct_nv12_dev for a planar surface (vs_roll_correct_i420_dev): fmt FMT_I420 / FMT_I010 / FMT_I012, lin / lout: i420_layout()."""
+        self._check(self.lib.vs_roll_correct_i420_dev(self.h, fmt, d_in, w, h, C.byref(lin), d_out, C.byref(lout)))
+
+    def correct_i420_dev_n(self, fmt, d_ins, w, h, lin, d_outs, lout):
+        """n planar surfaces in call order (lists of device pointers), one trip through the binding."""
+        n = len(d_ins)
+        a = (C.c_void_p * n)(*d_ins)
+        b = (C.c_void_p * n)(*d_outs)
+        self._check(self.lib.vs_roll_correct_i420_dev_n(self.h, fmt, a, b, n, w, h, C.byref(lin), C.byref(lout)))
 
     def sync(self):
         self._check(self.lib.vs_roll_sync(self.h))

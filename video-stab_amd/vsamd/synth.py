@@ -207,6 +207,34 @@ def i010_to_p010(buf, w, h, bits=10, pitch=None, c_pitch=None, u_off=None, v_off
     return out << (16 - bits)
 
 
+def planar_planes(buf, w, h, pitch=None, c_pitch=None, u_off=None, v_off=None):
+    """(Y (h, w), U (h / 2, w / 2), V (h / 2, w / 2)) of a planar 4:2:0 surface, uint8 (I420) or uint16 (I010 / I012), as copies.  buf:
+    what nv12_to_i420 / p010_to_i010 return; the layout in BYTES, defaults as i420_layout's at pitch = w samples."""
+    buf = np.asarray(buf)
+    sb = buf.dtype.itemsize
+    flat = buf.reshape(-1)
+    pitch, c_pitch, u_off, v_off = i420_layout(sb * w, h, pitch, c_pitch, u_off, v_off)
+
+    def plane(off, p, pw, ph):
+        return flat[off // sb:(off + ph * p) // sb].reshape(ph, p // sb)[:, :pw].copy()
+    return plane(0, pitch, w, h), plane(u_off, c_pitch, w // 2, h // 2), plane(v_off, c_pitch, w // 2, h // 2)
+
+
+def planar_from_planes(y, u, v, pitch=None, c_pitch=None, u_off=None, v_off=None, size=None, fill=0):
+    """The inverse: a flat buffer (the packed (h * 3 / 2, w) array when no layout is given) that holds the three planes, `fill` elsewhere."""
+    y = np.asarray(y)
+    h, w = y.shape
+    sb = y.dtype.itemsize
+    packed = not (pitch or c_pitch or u_off or v_off or size)
+    pitch, c_pitch, u_off, v_off = i420_layout(sb * w, h, pitch, c_pitch, u_off, v_off)
+    end = max(h * pitch, u_off + (h // 2) * c_pitch, v_off + (h // 2) * c_pitch)
+    buf = np.full((size or end) // sb, fill, y.dtype)
+    buf[:h * pitch // sb].reshape(h, pitch // sb)[:, :w] = y
+    buf[u_off // sb:(u_off + (h // 2) * c_pitch) // sb].reshape(h // 2, c_pitch // sb)[:, :w // 2] = u
+    buf[v_off // sb:(v_off + (h // 2) * c_pitch) // sb].reshape(h // 2, c_pitch // sb)[:, :w // 2] = v
+    return buf.reshape(h * 3 // 2, w) if packed else buf
+
+
 # ---- long clips rendered on the device (bench.py: more distinct input than the 256 MB Infinity Cache holds) -----------
 def loop_script(seed, n_frames, pan_q8=512, jitter_q8=384, rot_1e5=200):
     """Per-frame camera pose of a CLOSED pan path: n/4 frames right, down, left, up at pan_q8 per frame (the same jitter
