@@ -685,7 +685,12 @@ int vs_op_canny(const void* d_gray, size_t stride, int w, int h, double low, dou
                 void* d_edges, size_t edges_stride, void* stream);
 /* cv::HoughLines(edges, lines, rho, theta, threshold) - RollCorrection.cpp:66-73.
  * d_lines: max_lines (rho,theta) float pairs in OpenCV order (votes descending),
- * d_count: one int32.  At most 8192 peaks are ranked. */
+ * d_count: one int32.
+ * At most 8192 lines: when more than 8192 accumulator cells are peaks, the 8192 that cv::HoughLines
+ * would list first are kept, in that order (votes descending, ties by ascending accumulator index),
+ * and *d_count is min(8192, max_lines).  The roll stage (vs_roll_*) takes its angle statistics over
+ * those 8192 and reports n_lines = 8192.  Either way the result is a function of the input alone.
+ * Such a frame takes a second round of launches and one more wait of the host (the exact selection). */
 int vs_op_hough_lines(const void* d_edges, size_t stride, int w, int h, float rho, float theta,
                       int threshold, float* d_lines, int max_lines, int32_t* d_count, void* stream);
 /* cv::warpAffine(src, dst, M(2x3 double, forward), dsize, INTER_LINEAR, border) -

@@ -68,7 +68,8 @@ void canny(const uint8_t* g, int w, int h, size_t stride, double low_thresh, dou
                     if (ay > tg67x) {
                         is_max = m > m0[-mw] && m >= m0[mw];
                     } else {
-                        const int s = (xs ^ ys) < 0 ? 1 : -1;
+                        // along the gradient: up-left / down-right when dx and dy have equal signs, else up-right / down-left
+                        const int s = (xs ^ ys) < 0 ? -1 : 1;
                         is_max = m > m0[-mw - s] && m > m0[mw + s];
                     }
                 }
@@ -148,6 +149,11 @@ void rotation_matrix(float cx, float cy, double angle_deg, double M[6]) {
 
 using namespace vso;
 
+// The library's line search keeps at most 8192 lines: the first 8192 of cv::HoughLines' order (include/vs_stab.h, vs_op_hough_lines).
+// The roll stage is DEFINED with that cap - statistics over those lines, n_lines = 8192 - so the oracle's stage applies it too;
+// vso_hough_lines itself lists every line, as cv::HoughLines does.
+static const int ROLL_MAX_LINES = 8192;
+
 struct vso_roll {
     vs_roll_params_c p;
     bool first = true;
@@ -224,7 +230,7 @@ int vso_roll_correct(vso_roll* r, const uint8_t* data, int w, int h, size_t stri
     bgr2gray(sb, aw, ah, sstride, gray.data(), aw);                              // :51
     canny(gray.data(), aw, ah, aw, p.canny_threshold_low, p.canny_threshold_high, edges.data());   // :54-61
     std::vector<float> lines;
-    const int n = hough_lines(edges.data(), aw, ah, aw, p.hough_rho, p.hough_theta, p.hough_threshold, lines);   // :66-73
+    const int n = std::min(hough_lines(edges.data(), aw, ah, aw, p.hough_rho, p.hough_theta, p.hough_threshold, lines), ROLL_MAX_LINES);   // :66-73
     r->last_lines = n; r->last_used = 0; r->last_detected = 0.0;
     if (n == 0) {
         r->smoothed *= p.angle_decay;                                             // :76-77
@@ -279,7 +285,7 @@ int vso_roll_correct_nv12(vso_roll* r, const uint8_t* data, int w, int h, size_t
     std::vector<uint8_t> edges((size_t)aw * ah);
     canny(g, aw, ah, gs, p.canny_threshold_low, p.canny_threshold_high, edges.data());
     std::vector<float> lines;
-    const int n = hough_lines(edges.data(), aw, ah, aw, p.hough_rho, p.hough_theta, p.hough_threshold, lines);
+    const int n = std::min(hough_lines(edges.data(), aw, ah, aw, p.hough_rho, p.hough_theta, p.hough_threshold, lines), ROLL_MAX_LINES);
     r->last_lines = n; r->last_used = 0; r->last_detected = 0.0;
     double sum = 0.0;
     int count = 0;

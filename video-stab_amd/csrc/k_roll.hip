@@ -23,6 +23,7 @@
 // The smoothed angle (EMA, clamp, decay) is host state of the vs_roll object; a frame needs ONE wait of the host:
 // the 24-byte result comes back together with the flag that says whether four hysteresis passes were enough
 // (if not, the growth is finished and the line search redone; the reference synchronises several times per frame).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -46,7 +47,7 @@ template <typename T> __device__ __forceinline__ T* frame_ptr(T* p, size_t fb) {
     return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + (size_t)blockIdx.z * fb);
 }
 
-constexpr int HOUGH_CAP = 8192;      // peaks kept for the sort (cv::HoughLines has no cap)
+constexpr int HOUGH_CAP = 8192;      // peaks kept for the sort: the first 8192 of cv::HoughLines' order (it has no cap)
 
 __global__ __launch_bounds__(NT) void sobel_kernel(const uint8_t* __restrict__ g, size_t stride, int w, int h,
                                                    short2* __restrict__ dxy, int* __restrict__ mag, int mw, size_t fb) {
@@ -91,7 +92,8 @@ __global__ __launch_bounds__(NT) void canny_nms_kernel(const short2* __restrict_
                 if (ay > tg67x) {
                     is_max = m > mag[p - mw] && m >= mag[p + mw];
                 } else {
-                    const int s = (xs ^ ys) < 0 ? 1 : -1;
+                    // along the gradient: up-left / down-right when dx and dy have equal signs, else up-right / down-left
+                    const int s = (xs ^ ys) < 0 ? -1 : 1;
                     is_max = m > mag[p - mw - s] && m > mag[p + mw + s];
                 }
             }
@@ -325,9 +327,108 @@ __global__ __launch_bounds__(NT) void hough_peaks_kernel(const int* __restrict__
     if (v > threshold && v > accum[base - 1] && v >= accum[base + 1] && v > accum[base - numrho - 2] &&
         v >= accum[base + numrho + 2]) {
         const int pos = atomicAdd(&counters[2], 1);
-        // sort key: votes descending, then index ascending (hough_cmp_gt)
+        // sort key: votes descending, then index ascending (hough_cmp_gt).  Past the cap the kept set is whatever arrived first:
+        // counters[3] tells the host, which then has the frame's peaks selected exactly (hough_overflow_redo)
         if (pos < HOUGH_CAP) keys[pos] = ((unsigned long long)(unsigned)v << 32) | (unsigned)(0x7FFFFFFF - base);
         else counters[3] = 1;
+    }
+}
+
+// ---- more than HOUGH_CAP peaks: the exact selection (hough_overflow_redo) ----
+// hough_peaks_kernel kept the peaks that reached its counter first.  Which HOUGH_CAP cv::HoughLines lists first is a selection by
+// the sort key (votes << 32 | 0x7FFFFFFF - index: keys are distinct), found digit by digit from the top: a pass counts, over the
+// peaks whose key agrees with the digits found so far, how many carry each value of the next digit (hough_digit_hist_kernel), and
+// one workgroup walks that histogram from its top to the value at which the count of larger keys reaches what is still to be taken
+// (hough_digit_cut_kernel).  After the last digit the HOUGH_CAP-th largest key is known; hough_peaks_cut_kernel lists the peaks at
+// or above it and hough_select_kernel sorts them as ever.  A frame's state: counters[8..9] the digits found (a key), counters[10]
+// what is still to be taken among the keys that agree with them, counters[11] the peaks listed.  Frames of a launch that did not
+// overflow (counters[3] == 0) return at once.
+constexpr int HOUGH_DIGIT_BINS = 1 << 16;
+
+__device__ __forceinline__ bool hough_peak_key(const int* __restrict__ accum, int numangle, int numrho, int threshold, u64* key) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
+    if (r >= numrho || n >= numangle) return false;
+    const int base = (n + 1) * (numrho + 2) + r + 1;
+    const int v = accum[base];
+    if (!(v > threshold && v > accum[base - 1] && v >= accum[base + 1] && v > accum[base - numrho - 2] && v >= accum[base + numrho + 2]))
+        return false;
+    *key = ((u64)(unsigned)v << 32) | (unsigned)(0x7FFFFFFF - base);
+    return true;
+}
+
+// digit = nbits bits of the key from bit `shift`; first: no digit is known yet (and the bits above this digit are zero in every key)
+__global__ __launch_bounds__(NT) void hough_digit_hist_kernel(const int* __restrict__ accum, int numangle, int numrho, int threshold,
+                                                              const int* __restrict__ counters, int* __restrict__ hist, int shift,
+                                                              int nbits, int first, size_t fb) {
+    accum = frame_ptr(accum, fb); counters = frame_ptr(counters, fb); hist = frame_ptr(hist, fb);
+    if (!counters[3]) return;
+    u64 key;
+    if (!hough_peak_key(accum, numangle, numrho, threshold, &key)) return;
+    if (!first) {
+        const u64 prefix = ((u64)(unsigned)counters[9] << 32) | (unsigned)counters[8];
+        if ((key >> (shift + nbits)) != (prefix >> (shift + nbits))) return;
+    }
+    atomicAdd(&hist[(unsigned)(key >> shift) & ((1u << nbits) - 1u)], 1);
+}
+
+__global__ __launch_bounds__(1024) void hough_digit_cut_kernel(int* __restrict__ counters, int* __restrict__ hist, int shift, int nbits,
+                                                               int first, size_t fb) {
+    counters = frame_ptr(counters, fb); hist = frame_ptr(hist, fb);
+    if (!counters[3]) return;                        // (the same for the whole workgroup)
+    __shared__ int s_sum[1024];
+    __shared__ int s_pick[2];                        // the digit, and the count of keys with a larger one
+    const int tid = threadIdx.x, nb = 1 << nbits, per = (nb + 1023) / 1024;
+    const int need = first ? HOUGH_CAP : counters[10];
+    // position q = 0 is the largest digit value: thread t owns positions t * per .. t * per + per - 1
+    int mine = 0;
+    for (int j = 0; j < per; j++) {
+        const int q = tid * per + j;
+        if (q < nb) mine += hist[nb - 1 - q];
+    }
+    s_sum[tid] = mine;
+    if (tid == 0) { s_pick[0] = 0; s_pick[1] = 0; }
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {             // inclusive scan
+        const int t = tid >= d ? s_sum[tid - d] : 0;
+        __syncthreads();
+        s_sum[tid] += t;
+        __syncthreads();
+    }
+    const int incl = s_sum[tid], excl = incl - mine;
+    if (excl < need && need <= incl) {               // one thread: the count crosses `need` inside its positions
+        int cum = excl;
+        for (int j = 0; j < per; j++) {
+            const int q = tid * per + j;
+            if (q >= nb) break;
+            const int c = hist[nb - 1 - q];
+            if (cum + c >= need) { s_pick[0] = nb - 1 - q; s_pick[1] = cum; break; }
+            cum += c;
+        }
+    }
+    __syncthreads();
+    for (int j = 0; j < per; j++) {                  // the histogram is left cleared for the next pass
+        const int q = tid * per + j;
+        if (q < nb) hist[nb - 1 - q] = 0;
+    }
+    if (tid == 0) {
+        u64 prefix = first ? 0ull : (((u64)(unsigned)counters[9] << 32) | (unsigned)counters[8]);
+        prefix |= (u64)(unsigned)s_pick[0] << shift;
+        counters[8] = (int)(unsigned)(prefix & 0xFFFFFFFFu);
+        counters[9] = (int)(unsigned)(prefix >> 32);
+        counters[10] = need - s_pick[1];
+    }
+}
+
+__global__ __launch_bounds__(NT) void hough_peaks_cut_kernel(const int* __restrict__ accum, int numangle, int numrho, int threshold,
+                                                             unsigned long long* __restrict__ keys, int* __restrict__ counters, size_t fb) {
+    accum = frame_ptr(accum, fb); keys = frame_ptr(keys, fb); counters = frame_ptr(counters, fb);
+    if (!counters[3]) return;
+    u64 key;
+    if (!hough_peak_key(accum, numangle, numrho, threshold, &key)) return;
+    const u64 cut = ((u64)(unsigned)counters[9] << 32) | (unsigned)counters[8];
+    if (key >= cut) {
+        const int pos = atomicAdd(&counters[11], 1);
+        if (pos < HOUGH_CAP) keys[pos] = key;
     }
 }
 
@@ -335,7 +436,7 @@ struct RollResult {
     double sum_deg;      // sum of the accepted angles (degrees), in cv::HoughLines order
     int count;           // accepted lines
     int n_lines;         // lines found
-    int overflow;
+    int overflow;        // more than HOUGH_CAP peaks; until hough_overflow_redo has run the statistics above are of an arbitrary subset
     int pad;
 };
 
@@ -425,6 +526,7 @@ struct RollWork {
     float* tabSin = nullptr;
     float* tabCos = nullptr;
     unsigned long long* keys = nullptr;
+    int* hist = nullptr;                 // digit histogram of the over-cap selection
     float* lines = nullptr;
     int* counters = nullptr;
     int* hflags = nullptr;               // hysteresis pass flags (16 words after the counters)
@@ -440,7 +542,7 @@ static RollWork frame_view(const RollWork& k, int f) {
     const size_t o = (size_t)f * k.fb;
     auto adv = [&](auto*& p) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uint8_t*>(p) + o); };
     adv(v.gray); adv(v.edges); adv(v.dxy); adv(v.mag); adv(v.E); adv(v.C); adv(v.queue); adv(v.list); adv(v.accum);
-    adv(v.tabSin); adv(v.tabCos); adv(v.keys); adv(v.lines); adv(v.counters); adv(v.hflags); adv(v.res);
+    adv(v.tabSin); adv(v.tabCos); adv(v.keys); adv(v.hist); adv(v.lines); adv(v.counters); adv(v.hflags); adv(v.res);
     v.base = nullptr; v.frames = 1; v.fb = 0;
     return v;
 }
@@ -470,13 +572,14 @@ static int roll_work_alloc(RollWork& k, int w, int h, float rho, float theta, hi
     const size_t o_queue = take(npx * 4 + 64), o_list = take(npx * 4 + 64), o_accum = take(k.accum_bytes);
     const size_t o_sin = take((size_t)k.geom.numangle * 4), o_cos = take((size_t)k.geom.numangle * 4);
     const size_t o_keys = take((size_t)HOUGH_CAP * 8), o_lines = take((size_t)HOUGH_CAP * 8), o_cnt = take(128), o_res = take(64);
+    const size_t o_hist = take((size_t)HOUGH_DIGIT_BINS * 4);
     VS_HIP_TRY(hipMalloc((void**)&k.base, off * frames));
     VS_HIP_TRY(hipMemsetAsync(k.base, 0, off * frames, st));
     k.frames = frames; k.fb = frames > 1 ? off : 0;
     uint8_t* b = k.base;
     k.gray = b + o_gray; k.edges = b + o_edges; k.dxy = (short2*)(b + o_dxy); k.mag = (int*)(b + o_mag);
     k.E = (unsigned long long*)(b + o_E); k.C = (unsigned long long*)(b + o_C); k.queue = (int*)(b + o_queue); k.list = (int*)(b + o_list); k.accum = (int*)(b + o_accum);
-    k.tabSin = (float*)(b + o_sin); k.tabCos = (float*)(b + o_cos); k.keys = (unsigned long long*)(b + o_keys);
+    k.tabSin = (float*)(b + o_sin); k.tabCos = (float*)(b + o_cos); k.keys = (unsigned long long*)(b + o_keys); k.hist = (int*)(b + o_hist);
     k.lines = (float*)(b + o_lines); k.counters = (int*)(b + o_cnt); k.hflags = k.counters + 16; k.res = (RollResult*)(b + o_res);
     // the frame of mag stays 0; its interior and the bit planes are rewritten every frame
     // createTrigTable: float angle accumulation, sin/cos in double (host libm, as the oracle)
@@ -610,6 +713,41 @@ static int run_hough(RollWork& k, const uint8_t* d_edges, size_t estride, int th
     return VS_OK;
 }
 
+// The frames of a work area with more than HOUGH_CAP peaks (RollResult::overflow after run_hough; the others' kernels return at once):
+// the exact selection described at hough_digit_hist_kernel, then the sort and the statistics again.  k: the work area run_hough ran on
+// (its accumulators as run_hough left them).  The caller reads k.res again afterwards.  Votes are below 2^B, B the bit length of the
+// pixel count, so the keys' digits are: the votes' top 16 bits and the rest of them (B > 16), or the votes at once; then the two halves
+// of the index part.  Frames below the cap never get here; the cost of this path is unmeasured.
+static int hough_overflow_redo(RollWork& k, int threshold, double amin, double amax, hipStream_t st) {
+    int B = 1;
+    while ((1ll << B) <= (long long)k.w * k.h) B++;
+    struct { int shift, nbits; } pass[4];
+    int np = 0;
+    if (B > 16) { pass[np++] = {32 + B - 16, 16}; pass[np++] = {32, B - 16}; }
+    else pass[np++] = {32, 16};
+    pass[np++] = {16, 16};
+    pass[np++] = {0, 16};
+    if (k.frames > 1) {
+        VS_HIP_TRY(hipMemset2DAsync(k.hist, k.fb, 0, (size_t)HOUGH_DIGIT_BINS * 4, k.frames, st));
+        VS_HIP_TRY(hipMemset2DAsync(k.counters + 11, k.fb, 0, 4, k.frames, st));
+    } else {
+        VS_HIP_TRY(hipMemsetAsync(k.hist, 0, (size_t)HOUGH_DIGIT_BINS * 4, st));
+        VS_HIP_TRY(hipMemsetAsync(k.counters + 11, 0, 4, st));
+    }
+    dim3 g2((k.geom.numrho + NT - 1) / NT, k.geom.numangle, k.frames);
+    for (int p = 0; p < np; p++) {
+        hipLaunchKernelGGL(hough_digit_hist_kernel, g2, dim3(NT), 0, st, k.accum, k.geom.numangle, k.geom.numrho, threshold, k.counters, k.hist,
+                           pass[p].shift, pass[p].nbits, p == 0, k.fb);
+        hipLaunchKernelGGL(hough_digit_cut_kernel, dim3(1, 1, k.frames), dim3(1024), 0, st, k.counters, k.hist, pass[p].shift, pass[p].nbits,
+                           p == 0, k.fb);
+    }
+    hipLaunchKernelGGL(hough_peaks_cut_kernel, g2, dim3(NT), 0, st, k.accum, k.geom.numangle, k.geom.numrho, threshold, k.keys, k.counters, k.fb);
+    hipLaunchKernelGGL(hough_select_kernel, dim3(1, 1, k.frames), dim3(1024), 0, st, k.keys, k.counters, k.geom.numrho, k.rho, k.theta,
+                       amin, amax, k.lines, HOUGH_CAP, k.res, k.fb);
+    VS_HIP_TRY(hipGetLastError());
+    return VS_OK;
+}
+
 }  // namespace vsd
 
 using namespace vsd;
@@ -708,6 +846,11 @@ int vs_op_hough_lines(const void* d_edges, size_t stride, int w, int h, float rh
     VS_HIP_TRY(hipStreamSynchronize(st));
     RollResult r;
     VS_HIP_TRY(hipMemcpy(&r, g_op_work.res, sizeof r, hipMemcpyDeviceToHost));
+    if (r.overflow) {                // more than 8192 peaks: the first 8192 of the order
+        VS_TRY(hough_overflow_redo(g_op_work, threshold, -1e30, 1e30, st));
+        VS_HIP_TRY(hipStreamSynchronize(st));
+        VS_HIP_TRY(hipMemcpy(&r, g_op_work.res, sizeof r, hipMemcpyDeviceToHost));
+    }
     const int n = r.n_lines < max_lines ? r.n_lines : max_lines;
     if (n > 0) VS_HIP_TRY(hipMemcpy(d_lines, g_op_work.lines, (size_t)n * 8, hipMemcpyDeviceToDevice));
     VS_HIP_TRY(hipMemcpy(d_count, &n, 4, hipMemcpyHostToDevice));
@@ -852,6 +995,11 @@ int vs_roll_correct_dev(vs_roll* r, const void* d_data, int w, int h, size_t str
         VS_OBJ_HIP(r, hipMemcpyAsync(&res, k.res, sizeof res, hipMemcpyDeviceToHost, r->st));
         VS_OBJ_HIP(r, hipStreamSynchronize(r->st));
     }
+    if (res.overflow) {     // more than 8192 peaks: the statistics of the first 8192 of the order
+        VS_OBJ_TRY(r, hough_overflow_redo(k, p.hough_threshold, p.angle_filter_min, p.angle_filter_max, r->st));
+        VS_OBJ_HIP(r, hipMemcpyAsync(&res, k.res, sizeof res, hipMemcpyDeviceToHost, r->st));
+        VS_OBJ_HIP(r, hipStreamSynchronize(r->st));
+    }
     roll_update(r, res);
     // cv::getRotationMatrix2D(center, angle, 1.0) (:141-144)
     const float cx = w / 2.0f, cy = h / 2.0f;
@@ -907,6 +1055,15 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
             VS_HIP_TRY(hipMemcpyAsync(&res[f], v.res, sizeof(RollResult), hipMemcpyDeviceToHost, q.st));
             VS_HIP_TRY(hipStreamSynchronize(q.st));
         }
+    }
+    bool over = false;
+    for (int f = 0; f < n; f++) over |= res[f].overflow != 0;
+    if (over) {             // frames with more than 8192 peaks: their statistics from the first 8192 of the order, one launch per step for all of them
+        VS_TRY(hough_overflow_redo(k, p.hough_threshold, p.angle_filter_min, p.angle_filter_max, q.st));
+        VS_HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(q.h_res) + 256, 320, k.res, k.fb, sizeof(RollResult), n, hipMemcpyDeviceToHost, q.st));
+        VS_HIP_TRY(hipStreamSynchronize(q.st));
+        for (int f = 0; f < n; f++)
+            if (res[f].overflow) memcpy(&res[f], reinterpret_cast<const uint8_t*>(q.h_res) + (size_t)320 * f + 256, sizeof(RollResult));
     }
     // ---- in frame order: the angle recurrence and the rotations
     lk.lock();
