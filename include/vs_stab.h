@@ -37,8 +37,10 @@ extern "C" {
  *    VS_FMT_I012 (enum vs_pixfmt_planar16) with vs_op_warp_affine_i010; roll correction and auto zoom/crop on P010 surfaces:
  *    vs_roll_correct_p010_dev, vs_roll_correct_p010_dev_n, vs_azc_apply_p010_dev, vs_azc_apply_p010_dev_n and
  *    vs_op_warp_affine16_ex; the same two stages on I420 / I010 / I012 surfaces: struct vs_i420_layout with
- *    vs_roll_correct_i420_dev, vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev and vs_azc_apply_i420_dev_n (new entry points
- *    and a new struct only: no existing struct or entry point changed, so the version stays). */
+ *    vs_roll_correct_i420_dev, vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev and vs_azc_apply_i420_dev_n; planar 4:2:2 and
+ *    4:4:4 - VS_FMT_I422, VS_FMT_I444, VS_FMT_I210, VS_FMT_I212, VS_FMT_I410, VS_FMT_I412 (enum vs_pixfmt_planar4xx) - with
+ *    vs_op_warp_affine_planar (new entry points, new values and a new struct only: no existing struct or entry point changed, so
+ *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -155,6 +157,47 @@ typedef enum vs_pixfmt_planar16 {
     VS_FMT_I010 = 8,          /* yuv420p10le: Y (h rows of w uint16), U, V (h/2 rows of w/2 uint16 each); value in bits 0..9  */
     VS_FMT_I012 = 9           /* yuv420p12le: the same planes, value in bits 0..11 */
 } vs_pixfmt_planar16;
+
+/* Planar 4:2:2 and 4:4:4, 8-, 10- and 12-bit, numbered on in the same `int fmt`: what software decoders emit for camera and drone
+ * masters, ProRes, DNxHR and XAVC (yuv422p10le) and for screen and graphics content (yuv444p).  Three planes, as I420 / I010:
+ *      value  name          FFmpeg / GStreamer            planes
+ *      10     VS_FMT_I422   yuv422p      / Y42B           Y w x h, U and V (w/2) x h, 8-bit
+ *      11     VS_FMT_I444   yuv444p      / Y444           three planes w x h, 8-bit
+ *      12     VS_FMT_I210   yuv422p10le  / I422_10LE      as I422, little-endian 16-bit words, value in bits 0..9
+ *      13     VS_FMT_I212   yuv422p12le  / I422_12LE      value in bits 0..11
+ *      14     VS_FMT_I410   yuv444p10le  / Y444_10LE      as I444, 16-bit words, value in bits 0..9
+ *      15     VS_FMT_I412   yuv444p12le  / Y444_12LE      value in bits 0..11
+ * With the chroma shifts (sx, sy) = (1, 0) for 4:2:2 and (0, 0) for 4:4:4 (4:2:0 is (1, 1)) a chroma plane has (w >> sx) x (h >> sy)
+ * samples.  4:2:2 needs an even w (h may be odd); 4:4:4 takes any w, h.  Pitches and offsets are in BYTES; for the 16-bit formats
+ * pointers, pitches and offsets must be even (VS_ERR_INVALID_ARG otherwise).
+ * Packed default layout: chroma pitch = stride >> sx (stride / 2 for 4:2:2, stride for 4:4:4), U starts h * stride bytes behind
+ * the Y pointer, V h * (chroma pitch) bytes behind U.  Because of the default chroma pitch `stride` and `out_stride` must be even
+ * for I422 and multiples of 4 for I210 / I212.  The host entry points take and fill this layout.  Other layouts - an AVFrame's
+ * linesize[1], planes apart, V before U (swap the offsets) - go through the unchanged vs_stab_set_i420_layout /
+ * vs_batch_set_i420_layout: 0 = the default of that field, for that format.  A chroma pitch below one chroma row's bytes is
+ * VS_ERR_INVALID_ARG, with a text that names the format.  Definitions:
+ *  - analysis: the gray image is that of the Y plane (8-bit formats), or of the 8-bit plane min(sample >> (bits - 8), 255) of Y
+ *    (16-bit formats: shift 2 for I210 / I410, 4 for I212 / I412), through the kernels I420 / I010 take.  Keypoints, tracks, model,
+ *    trajectory and warp matrix are bit-identical to those of the NV12 / GRAY8 stream of those bytes;
+ *  - warp: Y under M; U and V each as a one-channel plane under the chroma matrix Mc = S^-1 M S, M conjugated by the subsampling
+ *    S = diag(2^sx, 2^sy) - the convention that gives 4:2:0 its "translation halved":
+ *        4:4:4: Mc = M;      4:2:2: Mc = [[m0, m1 * 0.5f, m2 * 0.5f], [m3 * 2.0f, m4, m5]]    (every product exact in float).
+ *    cv::warpAffine then inverts Mc in double like any other matrix; INTER_LINEAR, BORDER_CONSTANT 0.  8-bit planes:
+ *    vs_op_warp_affine_ex's arithmetic (CV_8UC1); 16-bit planes: P010's blend to the letter - the exact integer S, rounded once,
+ *    half to even (vs_pixfmt16) - which does not depend on the bit depth.  (For 4:2:2, Mc is not a rotation.)
+ *  - the last frame of a flush comes back unwarped, all three planes;
+ *  - border pad, crop-and-zoom, fade and the virtual canvas are VS_ERR_UNSUPPORTED, with a text that names the format, exactly
+ *    where I420 is refused.  Roll correction and auto zoom/crop (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev) keep refusing
+ *    anything but I420 / I010 / I012; the enhancer and the C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16,
+ *    P210, NV24), yuv4xxp16le and big-endian samples are not built. */
+typedef enum vs_pixfmt_planar4xx {
+    VS_FMT_I422 = 10,         /* yuv422p:     Y (h rows of w), U, V (h rows of w/2 each) */
+    VS_FMT_I444 = 11,         /* yuv444p:     Y, U, V (h rows of w each) */
+    VS_FMT_I210 = 12,         /* yuv422p10le: the planes of I422, uint16, value in bits 0..9 */
+    VS_FMT_I212 = 13,         /* yuv422p12le: value in bits 0..11 */
+    VS_FMT_I410 = 14,         /* yuv444p10le: the planes of I444, uint16, value in bits 0..9 */
+    VS_FMT_I412 = 15          /* yuv444p12le: value in bits 0..11 */
+} vs_pixfmt_planar4xx;
 
 /* Stabilizer.cpp:31-38 mapBorderMode() */
 typedef enum vs_border {
@@ -421,7 +464,9 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
  * surfaces it fills (`out`), independently.  0 = the default of that field: c_pitch = stride / 2, u_off = h * stride,
  * v_off = u_off + (h/2) * c_pitch (with the u_off and c_pitch in force).  A chroma pitch below w/2 is VS_ERR_INVALID_ARG (here
  * when the geometry is known, else at the next push).  YV12: swap the two offsets.  The frame queue must be empty.
- * I010 / I012 surfaces (vs_pixfmt_planar16) take the same call: offsets and pitch in bytes and even, the pitch at least w bytes. */
+ * I010 / I012 surfaces (vs_pixfmt_planar16) take the same call: offsets and pitch in bytes and even, the pitch at least w bytes.
+ * Planar 4:2:2 / 4:4:4 surfaces (vs_pixfmt_planar4xx) take it too, the defaults being those of the format: c_pitch = stride >> sx,
+ * v_off = u_off + h * c_pitch; the chroma pitch at least one chroma row's bytes; everything even for the 16-bit formats. */
 int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off,
                             size_t out_c_pitch);
 
@@ -548,6 +593,13 @@ int vs_op_warp_affine_i010(const void* d_src, size_t src_stride, size_t src_u_of
                            void* d_dst, size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch,
                            int w, int h, const float* M, int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
                            int border, void* stream);
+/* Any planar surface: fmt = VS_FMT_I420 (7) ... VS_FMT_I412 (15); the arguments of vs_op_warp_affine_i010 behind it.  Y under M, U and V
+ * - (w >> sx) x (h >> sy), one channel each - under Mc = S^-1 M S (vs_pixfmt_planar4xx); both borders; all three planes of up to 32
+ * surfaces in one launch.  For fmt 7 ... 9 the result is that of vs_op_warp_affine_i420 / vs_op_warp_affine_i010. */
+int vs_op_warp_affine_planar(int fmt, const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch,
+                             void* d_dst, size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch,
+                             int w, int h, const float* M, int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
+                             int border, void* stream);
 /* std::cos / std::sin / std::atan2 on float as the reference calls them (Stabilizer.cpp:662, 902-908, 1689: the host libm's
  * cosf / sinf / atan2f), evaluated by the DEVICE build of the library's restatement: the sum over i in [start, start + count) of
  * a 64-bit mix of (i, bits of f(argument i)) - fn 0 cosf, 1 sinf, 2 atanf: argument i = the float with bit pattern (uint32_t)i;

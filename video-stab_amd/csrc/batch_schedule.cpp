@@ -147,7 +147,7 @@ int group_allocate(vs_batch* g) {
     const size_t o_minv[2] = {take((size_t)cap * 96), take((size_t)cap * 96)};
     int tow, toh;
     out_size(s0, s0->w, s0->h, &tow, &toh);
-    g->tab_ints = fmt_two_planes(s0->fmt) || fmt_three_planes(s0->fmt) ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
+    g->tab_ints = fmt_three_planes(s0->fmt) ? planar_tab_ints(s0->w, s0->h, fmt_chroma_sx(s0->fmt), fmt_chroma_sy(s0->fmt)) : fmt_two_planes(s0->fmt) ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
     size_t o_tabs[2];
     for (auto& o : o_tabs) o = take((size_t)g->tab_ints * cap * sizeof(int32_t));
     VS_OBJ_HIP(g, hipMalloc((void**)&g->d_all, off));
@@ -213,7 +213,8 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
         }
         if (fmt_three_planes(s0->fmt)) {
             // I420, I010, I012: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
-            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, fmt_sample_bytes(s0->fmt));
+            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, fmt_sample_bytes(s0->fmt),
+                                  fmt_chroma_sx(s0->fmt), fmt_chroma_sy(s0->fmt));
             continue;
         }
         rc = launch_warp_plane(srcs, dsts, m, bp.pad ? bp.prow : s0->src_pitch, bp.pw, bp.ph, bp.crop ? bp.prow : R.stride, bp.pw, bp.ph, s0->cn, maps,
@@ -317,7 +318,8 @@ int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const
                 if (fmt_two_planes(s->fmt))
                     jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + dst_uv(s, e.dst, b.out_stride), s->w / 2, s->h / 2};
                 else if (fmt_three_planes(s->fmt))      // ONE chroma table, in pixels, naming the U planes: a V tile adds the launch's V - U
-                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + dst_i420(s, e.dst, b.out_stride).u, s->w / 2, s->h / 2};
+                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + dst_i420(s, e.dst, b.out_stride).u, s->w >> fmt_chroma_sx(s->fmt),
+                                         s->h >> fmt_chroma_sy(s->fmt)};      // (sized for the format's chroma planes: 4:2:0 halves both)
             }
             npad++;
             P.pend_stride = b.out_stride;

@@ -349,8 +349,11 @@ __global__ __launch_bounds__(NT) void quarter_gray_lo16_kernel(size_t sstride, s
     }
 }
 
-// The shift of a format whose luma samples carry their value in the low bits (I010: 2, I012: 4); 0 for every other format.
-int lo16_shift(int fmt) { return fmt == VS_FMT_I010 ? 2 : fmt == VS_FMT_I012 ? 4 : 0; }
+// The shift of a format whose luma samples carry their value in the low bits (10-bit - I010, I210, I410: 2; 12-bit - I012, I212,
+// I412: 4); 0 for every other format.
+int lo16_shift(int fmt) {
+    return fmt == VS_FMT_I010 || fmt == VS_FMT_I210 || fmt == VS_FMT_I410 ? 2 : fmt == VS_FMT_I012 || fmt == VS_FMT_I212 || fmt == VS_FMT_I412 ? 4 : 0;
+}
 
 // Byte of B inside a pixel and the pixel's size of a colour format; false for GRAY8 / NV12 / anything else.
 bool color_layout(int fmt, int* bi, int* ps) {

@@ -558,7 +558,7 @@ __global__ __launch_bounds__(1024) void ransac_tail_batch_kernel(const RansacArg
     {
         if (tid < n && l_due[tid]) {
             float Mt[12];
-            traj_matrix_lane(l_t3[tid], Mt, l_minv[tid], nullptr);
+            traj_matrix_lane(l_t3[tid], Mt, l_minv[tid], nullptr, l_tp.chroma);
             if (tid == last_due) {
                 for (int i = 0; i < 12; i++) l_M[i] = Mt[i];
                 for (int i = 0; i < 6; i++) l_dbg.warp_matrix[i] = Mt[i];

@@ -1415,7 +1415,12 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
 // (PlaneCfg<1, 2>: tiles of 128 x 32 pixels, the staged box of the P010 luma plane).  Pitches, V - U and the alignment flags stay
 // in bytes: plane_tile adds the plane distances to byte pointers.  BORDER_REPLICATE with SB = 2 (the roll stage's rotation of
 // I010 / I012 surfaces) is plane_tile<1, VS_BORDER_REPLICATE, 2>, the luma half of warp_nv12_kernel<VS_BORDER_REPLICATE, 2>.
-template <int BORDER, int SB = 1>
+// CSX, CSY: the chroma shifts - U and V have (w >> CSX) x (h >> CSY) samples.  (1, 1) is planar 4:2:0, the code above to the letter;
+// (1, 0) is 4:2:2 (I422, I210, I212), (0, 0) is 4:4:4 (I444, I410, I412).  Nothing else differs: the chroma table is sized for that
+// plane and built from the chroma map Mc = S^-1 M S, which for 4:2:2 is not a rotation - its 2 m3 term makes the source box of a
+// chroma tile about 2 sin(angle) x 128 rows taller, so such tiles leave the staging area for plane_direct_tile at a smaller angle
+// than luma tiles do (DESIGN.md section 4 has the figure).
+template <int BORDER, int SB = 1, int CSX = 1, int CSY = 1>
 __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
                                                        uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
     typedef PlaneCfg<1, SB> P;
@@ -1425,7 +1430,7 @@ __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_s
     typedef const __attribute__((address_space(4))) int32_t* cptr;
     const int w = wh & 0xFFFFu, h = wh >> 16;
     const uint32_t gx1 = (uint32_t)(w + TW - 1) / TW, gy1 = (uint32_t)(h + P::THP - 1) / P::THP;
-    const uint32_t w2 = (uint32_t)w >> 1, h2 = (uint32_t)h >> 1;
+    const uint32_t w2 = (uint32_t)w >> CSX, h2 = (uint32_t)h >> CSY;
     const uint32_t gx2 = (w2 + TW - 1) / TW, gy2 = (h2 + P::THP - 1) / P::THP;
     const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2, n = tpf * (flags >> 16);
     const uint32_t lin = blockIdx.x;
@@ -1459,8 +1464,9 @@ __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_s
     const TabLayout L = tab_layout(c.dw, c.dh);
     const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
     // (the 16-bit BORDER_REPLICATE instance: a direct-path callee of its own, see plane_tile; the others instantiate what they did)
+    // (the 4:2:2 and 4:4:4 instances of it: a copy each - a callee shared between kernels changes the code of all of them)
     if constexpr (SB == 2 && BORDER == VS_BORDER_REPLICATE)
-        plane_tile<1, BORDER, SB, 1>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
+        plane_tile<1, BORDER, SB, (CSY == 1 ? 1 : CSX == 1 ? 2 : 3)>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
     else
         plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
 }
@@ -1654,14 +1660,14 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
 // table, then the chroma table whose records name the U planes; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  Returns
 // VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420Layout& sl, const I420Layout& dl, int w, int h, const int32_t* d_tabs,
-                int border, hipStream_t st, int sb = 1) {
+                int border, hipStream_t st, int sb = 1, int sx = 1, int sy = 1) {
     // (sb = 2, I010 / I012: tiles of half the rows; BORDER_REPLICATE: the roll stage's rotation of I010 / I012 surfaces)
     const int thp = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP;
-    const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp - 1) / thp, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + thp - 1) / thp;
+    const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp - 1) / thp, gx2 = ((w >> sx) + TW - 1) / TW, gy2 = ((h >> sy) + thp - 1) / thp;
     const unsigned long long tpf = gx1 * gy1 + 2 * gx2 * gy2, total = tpf * (unsigned long long)n;
     const long long svu = (long long)sl.v - (long long)sl.u, dvu = (long long)dl.v - (long long)dl.u;
     if (w >= 65536 || h >= 65536 || sl.pitch >= (1ull << 24) || dl.pitch >= (1ull << 24) || sl.cpitch >= (1ull << 24) || dl.cpitch >= (1ull << 24) ||
-        n >= 65536 || total * std::max(tpf, std::max(gx1, gx2)) >= (1ull << 31) || svu != (int32_t)svu || dvu != (int32_t)dvu)
+        (sx != 0 && sx != 1) || (sy != 0 && sy != 1) || sy > sx || n >= 65536 || total * std::max(tpf, std::max(gx1, gx2)) >= (1ull << 31) || svu != (int32_t)svu || dvu != (int32_t)dvu)
         return VS_ERR_UNSUPPORTED;
     // bit 0 / 1: luma source / destination aligned - 4 bytes for the staging loads, a lane's four pixels (4 bytes; 16-bit samples: 8)
     // for the stores; bit 2 / 3: both chroma planes (pointers and pitch)
@@ -1678,22 +1684,23 @@ int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420L
     const uint32_t flags = (al & 3u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    if (sb == 2 && border == VS_BORDER_REPLICATE)
-        hipLaunchKernelGGL((warp_i420_kernel<VS_BORDER_REPLICATE, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
-                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
-                           (int32_t)dvu);
-    else if (sb == 2)
-        hipLaunchKernelGGL((warp_i420_kernel<VS_BORDER_BLACK, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
-                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
-                           (int32_t)dvu);
-    else if (border == VS_BORDER_REPLICATE)
-        hipLaunchKernelGGL(warp_i420_kernel<VS_BORDER_REPLICATE>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
-                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
-                           (int32_t)dvu);
-    else
-        hipLaunchKernelGGL(warp_i420_kernel<VS_BORDER_BLACK>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sl.pitch,
-                           (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,
-                           (int32_t)dvu);
+    // (one instance per sample size, border and subsampling; 4:2:0 keeps the four it had)
+#define VS_I420_GO(B, S, X, Y)                                                                                                                              \
+    hipLaunchKernelGGL((warp_i420_kernel<B, S, X, Y>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, X, Y), (uint32_t)sl.pitch, \
+                       (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,    \
+                       (int32_t)dvu)
+#define VS_I420_SUB(B, S)                                \
+    do {                                                 \
+        if (sx == 1 && sy == 1) VS_I420_GO(B, S, 1, 1);  \
+        else if (sx == 1) VS_I420_GO(B, S, 1, 0);        \
+        else VS_I420_GO(B, S, 0, 0);                     \
+    } while (0)
+    if (sb == 2 && border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 2);
+    else if (sb == 2) VS_I420_SUB(VS_BORDER_BLACK, 2);
+    else if (border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 1);
+    else VS_I420_SUB(VS_BORDER_BLACK, 1);
+#undef VS_I420_SUB
+#undef VS_I420_GO
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }
@@ -1797,21 +1804,26 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
 // outside what warp_i420_kernel packs, goes plane by plane through the general kernels: V from the maps, without a table.
 // sb = 2: I010 / I012 surfaces - the layouts stay in bytes.
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout sl, I420Layout dl, int w, int h, WarpMaps maps, int border,
-                     WarpTabs tabs, hipStream_t st, int sb) {
-    if (n < 1 || !ys || !yd || w < 2 || h < 2 || (w & 1) || (h & 1) || (sb != 1 && sb != 2) ||
+                     WarpTabs tabs, hipStream_t st, int sb, int sx, int sy) {
+    const int cw = w >> sx, ch = h >> sy;             // a chroma plane's samples per row, and its rows
+    const char* const kind = sx == 0 ? "planar 4:4:4" : sy == 0 ? "planar 4:2:2" : sb == 2 ? "warp_i010" : "warp_i420";
+    if ((sx != 0 && sx != 1) || (sy != 0 && sy != 1) || sy > sx) { set_last_error("warp_planar: chroma shifts must be (1, 1), (1, 0) or (0, 0)"); return VS_ERR_INVALID_ARG; }
+    if (n < 1 || !ys || !yd || w < 1 || h < 1 || cw < 1 || ch < 1 || (w & ((1 << sx) - 1)) || (h & ((1 << sy) - 1)) || (sb != 1 && sb != 2) ||
         bad_args(ys[0], yd[0], maps.m, sl.pitch, w, h, dl.pitch, w, h, sb, n) ||
-        sl.cpitch < (size_t)(w / 2) * sb || dl.cpitch < (size_t)(w / 2) * sb || !sl.u || !sl.v || !dl.u || !dl.v || sl.u == sl.v || dl.u == dl.v ||
+        sl.cpitch < (size_t)cw * sb || dl.cpitch < (size_t)cw * sb || !sl.u || !sl.v || !dl.u || !dl.v || sl.u == sl.v || dl.u == dl.v ||
         bad_call(ys, yd, n, border, tabs)) {
-        set_last_error(sb == 2 ? "warp_i010: invalid argument (w and h must be even, chroma pitches at least w bytes)"
-                               : "warp_i420: invalid argument (w and h must be even, chroma pitches at least w / 2)");
+        if (sy == 0) set_last_error(std::string("warp_planar: ") + kind + ": invalid argument (4:2:2 needs an even w; chroma pitches must hold a chroma row)");
+        else set_last_error(sb == 2 ? "warp_i010: invalid argument (w and h must be even, chroma pitches at least w bytes)"
+                                    : "warp_i420: invalid argument (w and h must be even, chroma pitches at least w / 2)");
         return VS_ERR_INVALID_ARG;
     }
     if (sb == 2 && (odd16(ys, yd, n, sl.pitch, dl.pitch) || ((sl.cpitch | sl.u | sl.v | dl.cpitch | dl.u | dl.v) & 1))) {
-        set_last_error("warp_i010: I010 / I012 pointers, pitches and plane offsets must be even");
+        set_last_error(sy == 0 ? "warp_planar: pointers, pitches and plane offsets of 16-bit planar surfaces must be even"
+                               : "warp_i010: I010 / I012 pointers, pitches and plane offsets must be even");
         return VS_ERR_INVALID_ARG;
     }
     const int tab_min = tabs.kind == WarpTabs::SCRATCH ? 1 : WARP_TAB_MIN;
-    const int block = nv12_tab_ints(w, h), sy = tab_layout(w, h).stride;
+    const int block = planar_tab_ints(w, h, sx, sy), ty = tab_layout(w, h).stride;
     if (tabs.kind == WarpTabs::SCRATCH)
         VS_TRY(op_tabs(st, (size_t)block * std::min(n, MAXB) * sizeof(int32_t), &tabs.tabs));
     const WarpMaps muv = {maps.m + 6, maps.stride, maps.host};
@@ -1828,9 +1840,9 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
             return plane_launch(ps, pd, nb, sp, pw, ph, dp, pw, ph, 1, m, border, tab, block, what, st, sb);
         };
         if (T && tabs.what != VS_WARP_ONLY) {
-            if (maps.host && nb <= NVT_MAX) {
+            if (maps.host && nb <= NVT_MAX && sx == 1 && sy == 1) {     // (the NV12 table launch halves both sizes)
                 NvTabArgs t;
-                t.tabs = T; t.block = block; t.chroma = sy; t.w = w; t.h = h; t.src_uv = sl.u; t.dst_uv = dl.u;
+                t.tabs = T; t.block = block; t.chroma = ty; t.w = w; t.h = h; t.src_uv = sl.u; t.dst_uv = dl.u;
                 for (int i = 0; i < NVT_MAX; i++) { t.ys[i] = ys[b0 + (i < nb ? i : 0)]; t.yd[i] = yd[b0 + (i < nb ? i : 0)]; }
                 for (int i = 0; i < NVT_MAX * 6; i++) {
                     t.my[i] = i < 6 * nb ? my.m[(size_t)my.stride * (i / 6) + i % 6] : 0.;
@@ -1840,19 +1852,19 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
                 hipLaunchKernelGGL(warp_tables_nv12_kernel, dim3((entries + NT - 1) / NT, nb, 2), dim3(NT), 0, st, t);
             } else {
                 VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, VS_WARP_TABLES_ONLY));
-                VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, w / 2, h / 2, mu, T + sy, VS_WARP_TABLES_ONLY));
+                VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, cw, ch, mu, T + ty, VS_WARP_TABLES_ONLY));
             }
         }
         if (tabs.what == VS_WARP_TABLES_ONLY) continue;
-        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st, sb) : VS_ERR_UNSUPPORTED;
+        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st, sb, sx, sy) : VS_ERR_UNSUPPORTED;
         if (one != VS_ERR_UNSUPPORTED) {
             VS_TRY(one);
             continue;
         }
         const int what = T ? VS_WARP_ONLY : VS_WARP_ALL;
         VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, what));
-        VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, w / 2, h / 2, mu, T ? T + sy : nullptr, what));
-        VS_TRY(plane(sl.v, dl.v, sl.cpitch, dl.cpitch, w / 2, h / 2, mu, nullptr, VS_WARP_ALL));
+        VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, cw, ch, mu, T ? T + ty : nullptr, what));
+        VS_TRY(plane(sl.v, dl.v, sl.cpitch, dl.cpitch, cw, ch, mu, nullptr, VS_WARP_ALL));
     }
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;

@@ -47,28 +47,47 @@ int gftt_fill_item(void* host_item, const uint8_t* d_gray, size_t stride, int w,
                    int block_size, const GfttWork& wk, float* d_pts, int32_t* d_count);
 int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_size, hipStream_t st, int what);
 
-// ---- k_warp.hip: I420 / YV12 surfaces (planar 4:2:0) of w x h (even) luma pixels
-// Where the planes of a surface lie: rows of `pitch` bytes of luma at the surface pointer, the U and V planes (h / 2 rows of w / 2
-// bytes, `cpitch` bytes apart) u and v bytes behind it.  One layout for all source surfaces of a call, one for all destinations.
+// ---- k_warp.hip: planar surfaces (I420 / YV12, I010 / I012; 4:2:2 and 4:4:4: I422, I444, I210, I212, I410, I412) of w x h luma pixels
+// The three-plane formats in one table: the name of the format, the name the stream's messages use (the two 4:2:0 16-bit formats
+// have always been named together), the chroma shifts - a chroma plane has (w >> sx) x (h >> sy) samples: 4:2:0 (1, 1), 4:2:2 (1, 0),
+// 4:4:4 (0, 0) -, the bytes of a sample and the bits of its value (16-bit samples carry it in the low bits).
+struct PlanarFmt { int fmt; const char* name; const char* text; int sx, sy, sample_bytes, bits; };
+inline const PlanarFmt* planar_fmt(int fmt) {       // nullptr: not a three-plane format
+    static const PlanarFmt T[] = {
+        {VS_FMT_I420, "I420", "I420", 1, 1, 1, 8},        {VS_FMT_I010, "I010", "I010 / I012", 1, 1, 2, 10}, {VS_FMT_I012, "I012", "I010 / I012", 1, 1, 2, 12},
+        {VS_FMT_I422, "I422", "I422", 1, 0, 1, 8},        {VS_FMT_I444, "I444", "I444", 0, 0, 1, 8},
+        {VS_FMT_I210, "I210", "I210", 1, 0, 2, 10},       {VS_FMT_I212, "I212", "I212", 1, 0, 2, 12},
+        {VS_FMT_I410, "I410", "I410", 0, 0, 2, 10},       {VS_FMT_I412, "I412", "I412", 0, 0, 2, 12},
+    };
+    for (const PlanarFmt& f : T)
+        if (f.fmt == fmt) return &f;
+    return nullptr;
+}
+// (any other format: 4:2:0's shifts, which nobody asks for)
+inline int fmt_chroma_sx(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f ? f->sx : 1; }
+inline int fmt_chroma_sy(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f ? f->sy : 1; }
+// Where the planes of a surface lie: rows of `pitch` bytes of luma at the surface pointer, the U and V planes (h >> sy rows of
+// w >> sx samples, `cpitch` bytes apart) u and v bytes behind it.  One layout for all source surfaces of a call, one for all destinations.
 struct I420Layout { size_t pitch, cpitch, u, v; };
-// The layout a caller describes with 0 = default per field: chroma pitch = pitch / 2, U behind the h luma rows, V behind U.
-inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, size_t c_pitch) {
+// The layout a caller describes with 0 = default per field: chroma pitch = pitch >> sx, U behind the h luma rows, V behind U.
+inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, size_t c_pitch, int sx = 1, int sy = 1) {
     I420Layout l;
     l.pitch = pitch;
-    l.cpitch = c_pitch ? c_pitch : pitch / 2;
+    l.cpitch = c_pitch ? c_pitch : pitch >> sx;
     l.u = u_off ? u_off : (size_t)h * pitch;
-    l.v = v_off ? v_off : l.u + (size_t)(h / 2) * l.cpitch;
+    l.v = v_off ? v_off : l.u + (size_t)(h >> sy) * l.cpitch;
     return l;
 }
 // Launches with tables warp the three planes of their surfaces in ONE grid (warp_i420_kernel); the tables are an NV12 surface's
-// (nv12_tab_ints per frame: luma table, then one chroma table whose pointer records name the U planes), the maps as for NV12
+// (planar_tab_ints per frame: luma table, then one chroma table whose pointer records name the U planes), the maps as for NV12
 // (m: luma, m + 6: chroma).  A call with the scratch tables builds them for any number of surfaces.
 // sample_bytes = 2: I010 / I012 surfaces - the same planes with 16-bit samples; layouts in bytes, pointers, pitches and offsets even.
+// sx, sy: the chroma shifts (4:2:0 needs even w and h, 4:2:2 an even w, 4:4:4 takes any size).
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout src, I420Layout dst, int w, int h, WarpMaps maps, int border,
-                     WarpTabs tabs, hipStream_t st, int sample_bytes = 1);
+                     WarpTabs tabs, hipStream_t st, int sample_bytes = 1, int sx = 1, int sy = 1);
 
 // ---- k_roll.hip, k_azc.hip: planar 4:2:0 surfaces (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012) of the stages around the stabilizer
-inline const char* planar_name(int fmt) { return fmt == VS_FMT_I420 ? "I420" : fmt == VS_FMT_I010 ? "I010" : "I012"; }
+inline const char* planar_name(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f ? f->name : ""; }
 
 // The geometry and layout rules of a planar surface handed to the roll / zoom stages (those vs_stab enforces).  need_w / need_h: the
 // samples per row and the rows the layout must hold - the picture's, or for the zoom stage's result the larger of the picture's and

@@ -45,8 +45,8 @@ int fmt_cn(int fmt) {
     switch (fmt) {
         case VS_FMT_BGR8: case VS_FMT_RGB8: return 3;
         case VS_FMT_BGRA8: case VS_FMT_RGBA8: return 4;
-        case VS_FMT_NV12: case VS_FMT_GRAY8: case VS_FMT_I420: return 1;
-        case VS_FMT_P010: case VS_FMT_I010: case VS_FMT_I012: return 2;
+        case VS_FMT_NV12: case VS_FMT_GRAY8: case VS_FMT_I420: case VS_FMT_I422: case VS_FMT_I444: return 1;
+        case VS_FMT_P010: case VS_FMT_I010: case VS_FMT_I012: case VS_FMT_I210: case VS_FMT_I212: case VS_FMT_I410: case VS_FMT_I412: return 2;
         default: return 0;
     }
 }
@@ -125,9 +125,13 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     s->row_bytes = (size_t)w * s->cn;
     s->frame_bytes = s->row_bytes * s->rows_total;
     s->src_pitch = s->row_bytes;
+    // the chroma matrix that goes with the frame matrix (traj_matrix_lane): by the subsampling of the stream's chroma planes
+    s->tp.chroma = !fmt_three_planes(fmt) || fmt_chroma_sy(fmt) ? TRAJ_CHROMA_420 : fmt_chroma_sx(fmt) ? TRAJ_CHROMA_422 : TRAJ_CHROMA_444;
     analysis_size(s, w, h, &s->aw, &s->ah);
     if (s->aw < 3 || s->ah < 3) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "analysis size too small");
     // (the reference's cvtColor(BGR2GRAY) of the canvas, Stabilizer.cpp:2225, throws on anything but three channels)
+    if (canvas_on(s) && fmt_422_444(fmt))
+        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, std::string("enableVirtualCanvas needs a BGR8 stream (not ") + fmt_planar_name(fmt) + ")");
     if (canvas_on(s) && fmt != VS_FMT_BGR8)
         return vs_obj_fail(s, VS_ERR_UNSUPPORTED, fmt == VS_FMT_P010 ? "enableVirtualCanvas needs a BGR8 stream (not P010)"
                                                   : fmt == VS_FMT_I420 ? "enableVirtualCanvas needs a BGR8 stream (not I420)"
@@ -245,12 +249,14 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
 }
 
 
-// The three planes of an I420 / I010 / I012 frame from one layout to another: rows of w and w / 2 samples.
+// The three planes of a planar frame (I420 / I010 / I012; 4:2:2, 4:4:4) from one layout to another: rows of w samples, and chroma
+// rows of w >> sx samples, h >> sy of them.
 int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src, const I420Layout& sl, hipMemcpyKind kind, hipStream_t st) {
-    const size_t cw = s->row_bytes / 2;
+    const size_t cw = fmt_chroma_row_bytes(s->fmt, s->w);
+    const int ch = s->h >> fmt_chroma_sy(s->fmt);
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, s->row_bytes, s->h, kind, st));
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.u, dl.cpitch, src + sl.u, sl.cpitch, cw, s->h / 2, kind, st));
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.v, dl.cpitch, src + sl.v, sl.cpitch, cw, s->h / 2, kind, st));
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.u, dl.cpitch, src + sl.u, sl.cpitch, cw, ch, kind, st));
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.v, dl.cpitch, src + sl.v, sl.cpitch, cw, ch, kind, st));
     return VS_OK;
 }
 
@@ -258,7 +264,7 @@ int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src
 // into the caller's frame.
 int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st) {
     if (fmt_three_planes(s->fmt))
-        return copy_i420(s, out, i420_layout(out_stride, s->h, 0, 0, 0), d_src, i420_layout(orow, s->h, 0, 0, 0), hipMemcpyDeviceToHost, st);
+        return copy_i420(s, out, fmt_i420_layout(s->fmt, out_stride, s->h, 0, 0, 0), d_src, fmt_i420_layout(s->fmt, orow, s->h, 0, 0, 0), hipMemcpyDeviceToHost, st);
     VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, st));
     return VS_OK;
 }
@@ -277,8 +283,8 @@ int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMem
     if (fmt_three_planes(s->fmt)) {
         // three planes into the slot's packed layout: from the caller's layout (device surfaces) or the packed default at the
         // caller's pitch (host frames)
-        const I420Layout in = kind == hipMemcpyDeviceToDevice ? i420_layout(stride, s->h, s->in_u_off, s->in_v_off, s->in_c_pitch) : i420_layout(stride, s->h, 0, 0, 0);
-        const I420Layout q = i420_layout(s->row_bytes, s->h, 0, 0, 0);
+        const I420Layout in = kind == hipMemcpyDeviceToDevice ? fmt_i420_layout(s->fmt, stride, s->h, s->in_u_off, s->in_v_off, s->in_c_pitch) : fmt_i420_layout(s->fmt, stride, s->h, 0, 0, 0);
+        const I420Layout q = fmt_i420_layout(s->fmt, s->row_bytes, s->h, 0, 0, 0);
         VS_OBJ_TRY(s, copy_i420(s, dst, q, (const uint8_t*)src, in, kind, s->st_pre));
         return VS_OK;
     }
@@ -479,7 +485,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
         StageScope t(s, VS_STAGE_WARP, st);
         rc = launch_warp_i420(&frame, &d_out, 1, src_i420(s), dst_i420(s, d_out, out_stride), s->w, s->h, WarpMaps{s->d_Minv, 12, false}, VS_BORDER_BLACK,
-                              WarpTabs{WarpTabs::SCRATCH}, st, fmt_sample_bytes(s->fmt));
+                              WarpTabs{WarpTabs::SCRATCH}, st, fmt_sample_bytes(s->fmt), fmt_chroma_sx(s->fmt), fmt_chroma_sy(s->fmt));
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
         const size_t prow = bp.prow, nb = prow * bh;
@@ -662,8 +668,16 @@ int take_slot(vs_stab* s, int* slot) {
 }
 
 // I010 / I012: a pitch in bytes holds 16-bit samples, and with the default chroma pitch - half of it - so does that.
-bool planar16_bad_pitch(size_t pitch, size_t c_pitch) { return (pitch & 1) || (!c_pitch && (pitch & 3)); }
-const char* const PLANAR16_OUT = "I010 / I012 need even surface pointers and pitches (16-bit samples; a default chroma pitch is half the pitch)";
+// (4:4:4: the default chroma pitch is the pitch itself.)
+bool planar16_bad_pitch(int fmt, size_t pitch, size_t c_pitch) { return (pitch & 1) || (!c_pitch && fmt_chroma_sx(fmt) && (pitch & 3)); }
+std::string planar16_out(int fmt) {
+    return std::string(fmt_planar_name(fmt)) + (fmt_422_444(fmt) && !fmt_chroma_sx(fmt) ? " needs even surface pointers and pitches (16-bit samples)"
+                       : fmt_422_444(fmt) ? " needs even surface pointers and pitches (16-bit samples; a default chroma pitch is half the pitch)"
+                                          : " need even surface pointers and pitches (16-bit samples; a default chroma pitch is half the pitch)");
+}
+// I420 and I422: the default chroma pitch is half the pitch
+bool planar8_half_pitch(int fmt) { return fmt == VS_FMT_I420 || fmt == VS_FMT_I422; }
+std::string planar8_out(int fmt) { return std::string(fmt_planar_name(fmt)) + " needs an even output pitch (the default chroma pitch is half of it)"; }
 
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
     const int cn = fmt_cn(fmt);
@@ -680,14 +694,28 @@ int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
         if (s->p.border_size > 0)
             return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not I420");
     }
-    if (fmt_planar16(fmt)) {
+    if (fmt_planar16(fmt) && !fmt_422_444(fmt)) {
         if ((w & 1) || (h & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012 need even w,h");
-        if (planar16_bad_pitch(stride, s->in_c_pitch) || ((s->in_u_off | s->in_v_off | s->in_c_pitch | s->out_u_off | s->out_v_off | s->out_c_pitch) & 1))
+        if (planar16_bad_pitch(fmt, stride, s->in_c_pitch) || ((s->in_u_off | s->in_v_off | s->in_c_pitch | s->out_u_off | s->out_v_off | s->out_c_pitch) & 1))
             return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012 need even pitches and plane offsets (16-bit samples; a default chroma pitch is half the pitch)");
         if ((s->in_c_pitch && s->in_c_pitch < (size_t)w) || (s->out_c_pitch && s->out_c_pitch < (size_t)w))
             return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012: the chroma pitch must be at least w bytes");
         if (s->p.border_size > 0)
             return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not I010 / I012");
+    }
+    if (fmt_422_444(fmt)) {
+        const std::string name = fmt_planar_name(fmt);
+        const int sb = fmt_sample_bytes(fmt);
+        const size_t crow = fmt_chroma_row_bytes(fmt, w);
+        if (fmt_chroma_sx(fmt) && (w & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + " needs an even w");
+        if (sb == 1 && fmt_chroma_sx(fmt) && (stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + " needs an even pitch (the default chroma pitch is half of it)");
+        if (sb == 2 && (planar16_bad_pitch(fmt, stride, s->in_c_pitch) || ((s->in_u_off | s->in_v_off | s->in_c_pitch | s->out_u_off | s->out_v_off | s->out_c_pitch) & 1)))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + (fmt_chroma_sx(fmt) ? " needs even pitches and plane offsets (16-bit samples; a default chroma pitch is half the pitch)"
+                                                                                  : " needs even pitches and plane offsets (16-bit samples)"));
+        if ((s->in_c_pitch && s->in_c_pitch < crow) || (s->out_c_pitch && s->out_c_pitch < crow))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + ": the chroma pitch must hold a chroma row (" + std::to_string(crow) + " bytes)");
+        if (s->p.border_size > 0)
+            return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not " + name);
     }
     // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8 / P010 / I420 / I010 / I012)
     if (fmt == VS_FMT_P010 && s->p.border_size > 0)
@@ -879,10 +907,9 @@ int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride
     if (rc != VS_OK) return rc;
     if (fmt == VS_FMT_P010 && (((uintptr_t)d_data | (uintptr_t)d_out | out_stride) & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
-    if (fmt == VS_FMT_I420 && (out_stride & 1))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
-    if (fmt_planar16(fmt) && ((((uintptr_t)d_data | (uintptr_t)d_out) & 1) || planar16_bad_pitch(out_stride, s->out_c_pitch)))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
+    if (planar8_half_pitch(fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(fmt));
+    if (fmt_planar16(fmt) && ((((uintptr_t)d_data | (uintptr_t)d_out) & 1) || planar16_bad_pitch(fmt, out_stride, s->out_c_pitch)))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(fmt));
     if (s->zero_copy) {
         // the frame is read where it is: it must stay valid and unchanged until its own result has been produced
         // one pitch for all frames in flight (the batched launches take it once): it may change when nothing is queued
@@ -921,10 +948,9 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
     if (!s->allocated || s->q_slot.empty()) return VS_OK;
     if (s->fmt == VS_FMT_P010 && (((uintptr_t)d_out | out_stride) & 1))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
-    if (s->fmt == VS_FMT_I420 && (out_stride & 1))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
-    if (fmt_planar16(s->fmt) && (((uintptr_t)d_out & 1) || planar16_bad_pitch(out_stride, d_out != s->d_out ? s->out_c_pitch : 0)))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
+    if (planar8_half_pitch(s->fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(s->fmt));
+    if (fmt_planar16(s->fmt) && (((uintptr_t)d_out & 1) || planar16_bad_pitch(s->fmt, out_stride, d_out != s->d_out ? s->out_c_pitch : 0)))
+        return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(s->fmt));
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
@@ -951,8 +977,8 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
     // (as in the synchronous call: the buffer is only looked at when a frame will be delivered into it; a held frame is
     // always a full-size one - pass-through frames only come out of vs_stab_flush's synchronous part)
     if (have_prev && (!out || out_stride < orow)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
-    if (fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
-    if (fmt_planar16(fmt) && (out_stride & 3)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
+    if (planar8_half_pitch(fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(fmt));
+    if (fmt_planar16(fmt) && planar16_bad_pitch(fmt, out_stride, 0)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(fmt));
     for (auto& hld : s->d_hold)
         if (!hld) VS_OBJ_HIP(s, hipMalloc((void**)&hld, s->out_bytes));
     // A copy to or from PAGEABLE memory (the frames of a cv::Mat) keeps its caller inside hipMemcpy for the whole transfer -
@@ -1025,10 +1051,9 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
     if (s->zero_copy && (s->src_pitch != s->row_bytes || (fmt_two_planes(s->fmt) && s->in_uv_off) ||
                          (fmt_three_planes(s->fmt) && (s->in_u_off || s->in_v_off || s->in_c_pitch))))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: host frames cannot join a queue of pitched zero-copy surfaces");
-    if (fmt == VS_FMT_I420 && out && (out_stride & 1))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
+    if (planar8_half_pitch(fmt) && out && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(fmt));
     // (host frames hold the packed default layout at their pitch: the chroma pitch is half of it)
-    if (fmt_planar16(fmt) && ((stride & 3) || (out && (out_stride & 3)))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
+    if (fmt_planar16(fmt) && (planar16_bad_pitch(fmt, stride, 0) || (out && planar16_bad_pitch(fmt, out_stride, 0)))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(fmt));
     if (s->host_pipe && !s->batch_active) return push_host_pipelined(s, data, w, h, stride, fmt, out, out_stride, produced);
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
@@ -1073,8 +1098,8 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
         if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
         const int orows = fmt_rows(s->fmt, s->hold_h);
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
-        if (s->fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
-        if (fmt_planar16(s->fmt) && (out_stride & 3)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
+        if (planar8_half_pitch(s->fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(s->fmt));
+        if (fmt_planar16(s->fmt) && planar16_bad_pitch(s->fmt, out_stride, 0)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(s->fmt));
         VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orows, s->st_warp));
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
         s->hold_valid = false;
@@ -1087,8 +1112,8 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     out_size(s, s->w, s->h, &ow, &oh);
     const size_t orow = (size_t)ow * s->cn;
     if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
-    if (s->fmt == VS_FMT_I420 && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even output pitch (the default chroma pitch is half of it)");
-    if (fmt_planar16(s->fmt) && (out_stride & 3)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, PLANAR16_OUT);
+    if (planar8_half_pitch(s->fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(s->fmt));
+    if (fmt_planar16(s->fmt) && planar16_bad_pitch(s->fmt, out_stride, 0)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(s->fmt));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, flush_warps(s));
     int rc = flush_dev_impl(s, s->d_out, orow, produced, false);
@@ -1167,7 +1192,14 @@ int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: the frame queue must be empty");
     if (s->allocated && s->fmt == VS_FMT_I420 && ((in_c_pitch && in_c_pitch < (size_t)s->w / 2) || (out_c_pitch && out_c_pitch < (size_t)s->w / 2)))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I420: the chroma pitch must be at least w / 2");
-    if (s->allocated && fmt_planar16(s->fmt)) {
+    if (s->allocated && fmt_422_444(s->fmt)) {
+        const std::string name = fmt_planar_name(s->fmt);
+        const size_t crow = fmt_chroma_row_bytes(s->fmt, s->w);
+        if (fmt_sample_bytes(s->fmt) == 2 && ((in_u_off | in_v_off | in_c_pitch | out_u_off | out_v_off | out_c_pitch) & 1))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: " + name + " needs even plane offsets and pitches (16-bit samples)");
+        if ((in_c_pitch && in_c_pitch < crow) || (out_c_pitch && out_c_pitch < crow))
+            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: " + name + ": the chroma pitch must hold a chroma row (" + std::to_string(crow) + " bytes)");
+    } else if (s->allocated && fmt_planar16(s->fmt)) {
         if ((in_u_off | in_v_off | in_c_pitch | out_u_off | out_v_off | out_c_pitch) & 1)
             return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I010 / I012 need even plane offsets and pitches (16-bit samples)");
         if ((in_c_pitch && in_c_pitch < (size_t)s->w) || (out_c_pitch && out_c_pitch < (size_t)s->w))

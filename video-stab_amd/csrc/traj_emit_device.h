@@ -66,8 +66,9 @@ __device__ __forceinline__ float wave_consistency_of(float v, int n) {
 
 // One lane: T = [cos -sin dx; sin cos dy] (:902-908) from the smoothed transform t3 = {dx, dy, da, valid},
 // the chroma variant, and the inverse maps the warp kernels consume.  valid == 0: identity (:774-780).
+// chroma (TrajParams::chroma): the subsampling the chroma matrix is for - Mc = S^-1 M S, every product exact in float.
 __device__ __forceinline__ void traj_matrix_lane(const float* t3, float* __restrict__ M_out, double* __restrict__ Minv_out,
-                                                 vs_debug_frame* dbg) {
+                                                 vs_debug_frame* dbg, int chroma) {
     if (t3[3] == 0.f) {
         M_out[0] = 1.f; M_out[1] = 0.f; M_out[2] = 0.f; M_out[3] = 0.f; M_out[4] = 1.f; M_out[5] = 0.f;
         for (int i = 0; i < 6; i++) M_out[6 + i] = M_out[i];
@@ -76,9 +77,17 @@ __device__ __forceinline__ void traj_matrix_lane(const float* t3, float* __restr
         const float cs = vslibm::cosf_ref(da), sn = vslibm::sinf_ref(da);     // glibc's cosf / sinf, bit for bit (vs_libm.h)
         M_out[0] = cs; M_out[1] = -sn; M_out[2] = dx;
         M_out[3] = sn; M_out[4] = cs; M_out[5] = dy;
-        // chroma plane of an NV12 surface: same rotation, translation halved
-        M_out[6] = cs; M_out[7] = -sn; M_out[8] = dx * 0.5f;
-        M_out[9] = sn; M_out[10] = cs; M_out[11] = dy * 0.5f;
+        if (chroma == TRAJ_CHROMA_422) {
+            // chroma planes of half the width and all the rows: [[m0, m1 / 2, m2 / 2], [2 m3, m4, m5]] - not a rotation
+            M_out[6] = cs; M_out[7] = -sn * 0.5f; M_out[8] = dx * 0.5f;
+            M_out[9] = sn * 2.0f; M_out[10] = cs; M_out[11] = dy;
+        } else if (chroma == TRAJ_CHROMA_444) {
+            for (int i = 0; i < 6; i++) M_out[6 + i] = M_out[i];
+        } else {
+            // chroma plane of an NV12 surface: same rotation, translation halved
+            M_out[6] = cs; M_out[7] = -sn; M_out[8] = dx * 0.5f;
+            M_out[9] = sn; M_out[10] = cs; M_out[11] = dy * 0.5f;
+        }
     }
     warp_invert(M_out, Minv_out);
     warp_invert(M_out + 6, Minv_out + 6);
@@ -103,7 +112,7 @@ __device__ __forceinline__ void traj_emit_wave0(TrajState* s, const TrajParams& 
             for (int c = 0; c < 3; c++) dbg->smoothed[c] = 0.f;
             float id[4] = {0.f, 0.f, 0.f, 0.f};
             if (DEFER) { for (int c = 0; c < 4; c++) t3[c] = id[c]; }
-            else traj_matrix_lane(id, M_out, Minv_out, dbg);
+            else traj_matrix_lane(id, M_out, Minv_out, dbg, p.chroma);
         }
         return;
     }
@@ -239,7 +248,7 @@ __device__ __forceinline__ void traj_emit_wave0(TrajState* s, const TrajParams& 
     const float r4[4] = {dx, dy, da, 1.f};
     if (DEFER) { for (int c = 0; c < 4; c++) t3[c] = r4[c]; }
     else {
-        traj_matrix_lane(r4, M_out, Minv_out, dbg);
+        traj_matrix_lane(r4, M_out, Minv_out, dbg, p.chroma);
         if (t3) for (int c = 0; c < 3; c++) t3[c] = r4[c];       // the correction itself, for the virtual canvas
     }
 }

@@ -39,7 +39,12 @@ struct TrajParams {
     int hf_freeze_duration;
     int gauss_ksize;
     float gauss_kernel[GAUSS_MAX];
+    // The chroma matrix M[6..11] that goes with a frame matrix M: Mc = S^-1 M S for the subsampling S = diag(2^sx, 2^sy) of the
+    // stream's chroma planes.  TRAJ_CHROMA_420 (0, what every two-plane and 4:2:0 format has): translation halved; 422: sx 1, sy 0;
+    // 444: Mc = M.
+    int chroma;
 };
+enum { TRAJ_CHROMA_420 = 0, TRAJ_CHROMA_422 = 1, TRAJ_CHROMA_444 = 2 };
 
 }  // namespace vsd
 #endif

@@ -255,34 +255,40 @@ int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst, si
 
 // I420 / YV12 (sample_bytes 1) and I010 / I012 (2): luma under the full matrix; U and V - one-channel planes of half the size -
 // under the matrix with the halved translation.  0 = the packed default of a layout field; everything in bytes.
+// sx, sy: the chroma shifts of planar 4:2:2 (1, 0) and 4:4:4 (0, 0) surfaces - chroma planes of (w >> sx) x (h >> sy) samples under
+// Mc = S^-1 M S, S = diag(2^sx, 2^sy): every product exact in float, then inverted in double like any matrix.
 static int warp_affine_three_planes(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst,
                                     size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch,
-                                    size_t src_frame_bytes, size_t dst_frame_bytes, int border, void* stream, int sample_bytes) {
+                                    size_t src_frame_bytes, size_t dst_frame_bytes, int border, void* stream, int sample_bytes, int sx = 1, int sy = 1) {
     VS_TRY(ensure_device());
-    // (the default chroma pitch is half the stride, and holds whole samples)
-    const size_t half = 2 * (size_t)sample_bytes - 1;
-    if (!d_src || !d_dst || !M || batch <= 0 || w < 2 || h < 2 || (w & 1) || (h & 1) || (!src_c_pitch && (src_stride & half)) ||
-        (!dst_c_pitch && (dst_stride & half))) {
-        set_last_error(sample_bytes == 2 ? "warp_affine_i010: invalid argument (w and h must be even and, for the default chroma pitch, the strides multiples of 4)"
-                                         : "warp_affine_i420: invalid argument (w, h and, for the default chroma pitch, the strides must be even)");
+    // (the default chroma pitch is the stride >> sx, and holds whole samples)
+    const size_t half = sx ? 2 * (size_t)sample_bytes - 1 : 0;
+    if (!d_src || !d_dst || !M || batch <= 0 || w < 1 || h < 1 || (w >> sx) < 1 || (h >> sy) < 1 || (w & ((1 << sx) - 1)) || (h & ((1 << sy) - 1)) ||
+        (!src_c_pitch && (src_stride & half)) || (!dst_c_pitch && (dst_stride & half))) {
+        if (sy == 0) set_last_error(sx ? "warp_affine_planar: 4:2:2: invalid argument (w must be even and, for the default chroma pitch, the strides hold two chroma rows)"
+                                       : "warp_affine_planar: 4:4:4: invalid argument");
+        else set_last_error(sample_bytes == 2 ? "warp_affine_i010: invalid argument (w and h must be even and, for the default chroma pitch, the strides multiples of 4)"
+                                              : "warp_affine_i420: invalid argument (w, h and, for the default chroma pitch, the strides must be even)");
         return VS_ERR_INVALID_ARG;
     }
     if (sample_bytes == 2 && ((src_frame_bytes | dst_frame_bytes) & 1)) {
-        set_last_error("warp_affine_i010: frame distances must be even (16-bit samples)");
+        set_last_error(sy == 0 ? "warp_affine_planar: frame distances must be even (16-bit samples)" : "warp_affine_i010: frame distances must be even (16-bit samples)");
         return VS_ERR_INVALID_ARG;
     }
     std::vector<double> Minv(12 * (size_t)batch);
     for (int b = 0; b < batch; b++) {
         const float* m = M + 6 * (size_t)b;
-        const float c[6] = {m[0], m[1], m[2] * 0.5f, m[3], m[4], m[5] * 0.5f};
+        float c[6] = {m[0], m[1], m[2] * 0.5f, m[3], m[4], m[5] * 0.5f};
+        if (sx == 1 && sy == 0) { c[1] = m[1] * 0.5f; c[3] = m[3] * 2.0f; c[5] = m[5]; }
+        else if (sx == 0) { c[2] = m[2]; c[5] = m[5]; }
         warp_invert(m, &Minv[12 * (size_t)b]);
         warp_invert(c, &Minv[12 * (size_t)b + 6]);
     }
-    const I420Layout sl = i420_layout(src_stride, h, src_u_off, src_v_off, src_c_pitch), dl = i420_layout(dst_stride, h, dst_u_off, dst_v_off, dst_c_pitch);
+    const I420Layout sl = i420_layout(src_stride, h, src_u_off, src_v_off, src_c_pitch, sx, sy), dl = i420_layout(dst_stride, h, dst_u_off, dst_v_off, dst_c_pitch, sx, sy);
     const auto ys = frame_list((const uint8_t*)d_src, src_frame_bytes, batch);
     const auto yd = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch);
     return launch_warp_i420(ys.data(), yd.data(), batch, sl, dl, w, h, WarpMaps{Minv.data(), 12, true}, border, WarpTabs{WarpTabs::SCRATCH},
-                            (hipStream_t)stream, sample_bytes);
+                            (hipStream_t)stream, sample_bytes, sx, sy);
 }
 
 int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst, size_t dst_stride,
@@ -297,6 +303,20 @@ int vs_op_warp_affine_i010(const void* d_src, size_t src_stride, size_t src_u_of
                            size_t dst_frame_bytes, int border, void* stream) {
     return warp_affine_three_planes(d_src, src_stride, src_u_off, src_v_off, src_c_pitch, d_dst, dst_stride, dst_u_off, dst_v_off, dst_c_pitch, w, h, M,
                                     batch, src_frame_bytes, dst_frame_bytes, border, stream, 2);
+}
+
+// Any planar format (VS_FMT_I420 ... VS_FMT_I412): the arguments of vs_op_warp_affine_i010 with the format in front.
+int vs_op_warp_affine_planar(int fmt, const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst,
+                             size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch,
+                             size_t src_frame_bytes, size_t dst_frame_bytes, int border, void* stream) {
+    const PlanarFmt* pf = planar_fmt(fmt);
+    if (!pf) {
+        VS_TRY(ensure_device());
+        set_last_error("warp_affine_planar: fmt must be a planar format (VS_FMT_I420 ... VS_FMT_I412)");
+        return VS_ERR_INVALID_ARG;
+    }
+    return warp_affine_three_planes(d_src, src_stride, src_u_off, src_v_off, src_c_pitch, d_dst, dst_stride, dst_u_off, dst_v_off, dst_c_pitch, w, h, M,
+                                    batch, src_frame_bytes, dst_frame_bytes, border, stream, pf->sample_bytes, pf->sx, pf->sy);
 }
 
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt, void* d_dst,

@@ -42,6 +42,9 @@ inline TabLayout tab_layout(int dw, int dh) {
 
 // Ints per frame of an NV12 surface of w x h luma pixels: luma table, then chroma table.
 inline int nv12_tab_ints(int w, int h) { return tab_layout(w, h).stride + tab_layout(w / 2, h / 2).stride; }
+// The same for a three-plane surface whose chroma planes have (w >> sx) x (h >> sy) samples (4:2:0: nv12_tab_ints; 4:2:2: sx 1,
+// sy 0; 4:4:4: 0, 0): luma table, then the ONE chroma table that serves U and V.
+inline int planar_tab_ints(int w, int h, int sx, int sy) { return tab_layout(w, h).stride + tab_layout(w >> sx, h >> sy).stride; }
 
 // One plane of one due frame: where its table goes and what the table's pointer records name.  tabs == nullptr: no table.
 struct WarpTabJob {

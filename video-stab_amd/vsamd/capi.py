@@ -31,13 +31,21 @@ FMT_I420 = 7
 # planar 4:2:0 with 16-bit samples, the value in the low bits (vs_pixfmt_planar16: yuv420p10le / yuv420p12le).  A packed frame is a
 # (h * 3 / 2, w) uint16 array laid out as an I420 frame is (synth.p010_to_i010); other layouts through set_i420_layout, in bytes.
 FMT_I010, FMT_I012 = 8, 9
+# planar 4:2:2 and 4:4:4 (vs_pixfmt_planar4xx): yuv422p, yuv444p, yuv422p10le, yuv422p12le, yuv444p10le, yuv444p12le.  A packed frame
+# is a (2 h, w) (4:2:2) or (3 h, w) (4:4:4) array, uint8 or uint16: h rows of Y, then the U plane and the V plane, h rows of w / 2
+# (4:2:2) or w (4:4:4) samples each (synth.yuv_pack, synth.bgr_to_planar); other layouts through set_i420_layout, in bytes.
+FMT_I422, FMT_I444, FMT_I210, FMT_I212, FMT_I410, FMT_I412 = 10, 11, 12, 13, 14, 15
+# chroma shifts (sx, sy) of the three-plane formats: a chroma plane has (w >> sx) x (h >> sy) samples
+FMT_CHROMA_SHIFTS = {FMT_I420: (1, 1), FMT_I010: (1, 1), FMT_I012: (1, 1), FMT_I422: (1, 0), FMT_I210: (1, 0), FMT_I212: (1, 0),
+                     FMT_I444: (0, 0), FMT_I410: (0, 0), FMT_I412: (0, 0)}
+FMT_PLANAR_BITS = {FMT_I420: 8, FMT_I422: 8, FMT_I444: 8, FMT_I010: 10, FMT_I210: 10, FMT_I410: 10, FMT_I012: 12, FMT_I212: 12, FMT_I412: 12}
 
 
 def fmt_px_bytes(fmt):
     """Bytes per pixel of a format's (first) plane."""
-    if fmt == FMT_I420:
+    if fmt in (FMT_I420, FMT_I422, FMT_I444):
         return 1
-    if fmt in (FMT_I010, FMT_I012):
+    if fmt in (FMT_I010, FMT_I012, FMT_I210, FMT_I212, FMT_I410, FMT_I412):
         return 2
     return FMT_SAMPLE_BYTES[fmt] if fmt in FMT_SAMPLE_BYTES else FMT_CHANNELS[fmt]
 
@@ -53,6 +61,24 @@ def fmt_two_planes(fmt):
 def fmt_420(fmt):
     """A frame array of this format has h * 3 / 2 rows: h of luma, h / 2 of subsampled chroma."""
     return fmt_two_planes(fmt) or fmt in (FMT_I420, FMT_I010, FMT_I012)
+
+
+def fmt_frame_rows(fmt, h):
+    """Rows of a packed frame array of h picture rows (its columns: w)."""
+    if fmt in (FMT_I422, FMT_I210, FMT_I212):
+        return 2 * h
+    if fmt in (FMT_I444, FMT_I410, FMT_I412):
+        return 3 * h
+    return h * 3 // 2 if fmt_420(fmt) else h
+
+
+def fmt_picture_rows(fmt, rows):
+    """The picture's rows of a packed frame array with `rows` rows: the inverse of fmt_frame_rows."""
+    if fmt in (FMT_I422, FMT_I210, FMT_I212):
+        return rows // 2
+    if fmt in (FMT_I444, FMT_I410, FMT_I412):
+        return rows // 3
+    return rows * 2 // 3 if fmt_420(fmt) else rows
 
 
 BORDER_BLACK, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP, BORDER_FADE = range(6)
@@ -289,6 +315,7 @@ class VsLib:
         L.vs_op_warp_affine_i420.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                              C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, vp]
         L.vs_op_warp_affine_i010.argtypes = L.vs_op_warp_affine_i420.argtypes
+        L.vs_op_warp_affine_planar.argtypes = [C.c_int] + list(L.vs_op_warp_affine_i420.argtypes)
         L.vs_op_resize_gray.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp]
         L.vs_op_pyr_down.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, vp]
         L.vs_op_scharr.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, vp]
@@ -494,6 +521,24 @@ class VsLib:
             self.check(self.lib.vs_op_warp_affine_i010(d_in.ptr, 2 * w, 0, 0, 0, d_out.ptr, 2 * w, 0, 0, 0, w, h, _p(M, f32p), n, fb, fb, border, None))
             self.sync()
             return d_out.download(img.shape, np.uint16)
+        finally:
+            d_in.free(); d_out.free()
+
+    def warp_affine_planar(self, fmt, img, w, h, M, border=BORDER_BLACK):
+        """img: one packed surface of a planar format (FMT_I420 ... FMT_I412: fmt_frame_rows(fmt, h) rows of w samples) and one
+        matrix, or a stack of n surfaces and n matrices; all three planes of up to 32 surfaces per launch."""
+        dt = fmt_dtype(fmt)
+        img = np.ascontiguousarray(img, dt)
+        M = np.ascontiguousarray(M, np.float32).reshape(-1, 6)
+        n = M.shape[0]
+        fb = img.nbytes // n
+        sb = fmt_px_bytes(fmt)
+        d_in = DevBuf.from_array(self, img)
+        d_out = DevBuf(self, img.nbytes)
+        try:
+            self.check(self.lib.vs_op_warp_affine_planar(fmt, d_in.ptr, sb * w, 0, 0, 0, d_out.ptr, sb * w, 0, 0, 0, w, h, _p(M, f32p), n, fb, fb, border, None))
+            self.sync()
+            return d_out.download(img.shape, dt)
         finally:
             d_in.free(); d_out.free()
 
@@ -1078,14 +1123,13 @@ class Stabilizer:
     def _geom(self, frame, fmt):
         """(w, h, bytes per pixel of the first plane) of a frame array of format fmt."""
         w = frame.shape[1]
-        h = frame.shape[0] if not fmt_420(fmt) else frame.shape[0] * 2 // 3
-        return w, h, fmt_px_bytes(fmt)
+        return w, fmt_picture_rows(fmt, frame.shape[0]), fmt_px_bytes(fmt)
 
     def out_shape(self, w, h, fmt):
         ow, oh = C.c_int32(), C.c_int32()
         self.vs.check(self.lib.vs_stab_out_size(self.h, w, h, C.byref(ow), C.byref(oh)), self.h)
-        if fmt_420(fmt):
-            return (oh.value * 3 // 2, ow.value)
+        if fmt in FMT_CHROMA_SHIFTS or fmt_420(fmt):
+            return (fmt_frame_rows(fmt, oh.value), ow.value)
         if FMT_CHANNELS[fmt] > 1:
             return (oh.value, ow.value, FMT_CHANNELS[fmt])
         return (oh.value, ow.value)

@@ -235,6 +235,87 @@ def planar_from_planes(y, u, v, pitch=None, c_pitch=None, u_off=None, v_off=None
     return buf.reshape(h * 3 // 2, w) if packed else buf
 
 
+# ---- planar 4:2:2 / 4:4:4 (I422, I444 and their 10- / 12-bit forms): chroma planes of (w >> sx) x (h >> sy) samples -----------------
+def yuv_layout(w, h, sx, sy, sb=1, pitch=None, c_pitch=None, u_off=None, v_off=None):
+    """(pitch, c_pitch, u_off, v_off) in BYTES of a three-plane surface of w x h luma samples of sb bytes whose chroma planes have
+    (w >> sx) x (h >> sy) samples, the library's defaults filled in: chroma pitch = pitch >> sx, U behind the h luma rows, V behind U.
+    (sx, sy) = (1, 1): i420_layout; (1, 0): 4:2:2; (0, 0): 4:4:4."""
+    pitch = pitch or sb * w
+    c_pitch = c_pitch or pitch >> sx
+    u_off = u_off or h * pitch
+    v_off = v_off or u_off + (h >> sy) * c_pitch
+    return pitch, c_pitch, u_off, v_off
+
+
+def yuv_frame_rows(h, sx, sy):
+    """Rows of w samples of a packed frame: h of luma and two chroma planes of (h >> sy) rows of w >> sx samples."""
+    return h + ((2 * (h >> sy)) >> sx)
+
+
+def bgr_to_yuv_planes(frame, sx, sy):
+    """BT.601 limited-range integer BGR -> (Y (h, w), U, V ((h >> sy), (w >> sx))) uint8: bgr_to_nv12's luma and its chroma before the
+    subsampling, averaged (rounded) over blocks of 2^sx x 2^sy samples.  w a multiple of 2^sx, h of 2^sy."""
+    b = frame[:, :, 0].astype(np.int64)
+    g = frame[:, :, 1].astype(np.int64)
+    r = frame[:, :, 2].astype(np.int64)
+    yp = ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16
+    u = ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128
+    v = ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128
+
+    def sub(p):
+        h, w = p.shape
+        bx, by = 1 << sx, 1 << sy
+        t = p.reshape(h // by, by, w // bx, bx).sum(axis=(1, 3))
+        return (t + ((bx * by) >> 1)) >> (sx + sy)
+    return tuple(np.clip(p, 0, 255).astype(np.uint8) for p in (yp, sub(u), sub(v)))
+
+
+def yuv_to_depth(planes, bits, seed=0):
+    """The 10- / 12-bit form of 8-bit planes: uint16 samples (byte << (bits - 8)) | r with r seeded random low bits, the value in the
+    low bits of the word - so min(sample >> (bits - 8), 255) is the byte again and every low bit is live."""
+    rng = np.random.default_rng(seed)
+    return tuple((np.asarray(p, np.uint16) << (bits - 8)) | rng.integers(0, 1 << (bits - 8), np.shape(p), np.uint16) for p in planes)
+
+
+def yuv_pack(y, u, v, sx, sy, pitch=None, c_pitch=None, u_off=None, v_off=None, size=None, fill=0):
+    """A surface that holds the three planes (uint8 or uint16).  Packed (no layout given): the (yuv_frame_rows, w) array - Y, then the
+    U plane, then the V plane.  With a layout (bytes; see yuv_layout): a flat buffer of `size` bytes, `fill` wherever no sample lies."""
+    y = np.asarray(y)
+    h, w = y.shape
+    sb = y.dtype.itemsize
+    cw, ch = w >> sx, h >> sy
+    packed = not (pitch or c_pitch or u_off or v_off or size)
+    pitch, c_pitch, u_off, v_off = yuv_layout(w, h, sx, sy, sb, pitch, c_pitch, u_off, v_off)
+    end = max(h * pitch, u_off + ch * c_pitch, v_off + ch * c_pitch)
+    assert sb == 1 or not ((pitch | c_pitch | u_off | v_off | (size or 0)) & 1), "16-bit samples: the layout is in even bytes"
+    buf = np.full((size or end) // sb, fill, y.dtype)
+    buf[:h * pitch // sb].reshape(h, pitch // sb)[:, :w] = y
+    buf[u_off // sb:(u_off + ch * c_pitch) // sb].reshape(ch, c_pitch // sb)[:, :cw] = u
+    buf[v_off // sb:(v_off + ch * c_pitch) // sb].reshape(ch, c_pitch // sb)[:, :cw] = v
+    return buf.reshape(yuv_frame_rows(h, sx, sy), w) if packed else buf
+
+
+def yuv_unpack(buf, w, h, sx, sy, pitch=None, c_pitch=None, u_off=None, v_off=None):
+    """(Y, U, V) of a surface yuv_pack made, as copies; the layout as given there."""
+    buf = np.asarray(buf)
+    sb = buf.dtype.itemsize
+    flat = buf.reshape(-1)
+    pitch, c_pitch, u_off, v_off = yuv_layout(w, h, sx, sy, sb, pitch, c_pitch, u_off, v_off)
+
+    def plane(off, p, pw, ph):
+        return flat[off // sb:(off + ph * p) // sb].reshape(ph, p // sb)[:, :pw].copy()
+    return plane(0, pitch, w, h), plane(u_off, c_pitch, w >> sx, h >> sy), plane(v_off, c_pitch, w >> sx, h >> sy)
+
+
+def bgr_to_planar(frame, sx, sy, bits=8, seed=0):
+    """One frame of the clip generator as a packed planar frame: I422 (sx, sy = 1, 0) / I444 (0, 0) at bits = 8, I210 / I410 at 10,
+    I212 / I412 at 12.  The luma bytes - for the deeper forms min(sample >> (bits - 8), 255) - are those of bgr_to_nv12(frame)."""
+    planes = bgr_to_yuv_planes(frame, sx, sy)
+    if bits != 8:
+        planes = yuv_to_depth(planes, bits, seed)
+    return yuv_pack(*planes, sx, sy)
+
+
 # ---- long clips rendered on the device (bench.py: more distinct input than the 256 MB Infinity Cache holds) -----------
 def loop_script(seed, n_frames, pan_q8=512, jitter_q8=384, rot_1e5=200):
     """Per-frame camera pose of a CLOSED pan path: n/4 frames right, down, left, up at pan_q8 per frame (the same jitter
