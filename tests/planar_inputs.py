@@ -15,13 +15,13 @@ from vsamd import capi, synth
 BLACK, REPLICATE = ii.BLACK, ii.REPLICATE
 CANARY8, CANARY16 = 0xA5, ii.CANARY
 
-# name -> (format value, sx, sy, bits)
-FORMATS = {
-    "I422": (capi.FMT_I422, 1, 0, 8), "I444": (capi.FMT_I444, 0, 0, 8),
-    "I210": (capi.FMT_I210, 1, 0, 10), "I212": (capi.FMT_I212, 1, 0, 12),
-    "I410": (capi.FMT_I410, 0, 0, 10), "I412": (capi.FMT_I412, 0, 0, 12),
-}
-OLD = {"I420": (capi.FMT_I420, 1, 1, 8), "I010": (capi.FMT_I010, 1, 1, 10), "I012": (capi.FMT_I012, 1, 1, 12)}
+# name -> (format value, sx, sy, bits), from the binding's table
+def _rows(*names):
+    return {n: (capi.PIXFMT_BY_NAME[n].fmt, capi.PIXFMT_BY_NAME[n].sx, capi.PIXFMT_BY_NAME[n].sy, capi.PIXFMT_BY_NAME[n].bits) for n in names}
+
+
+FORMATS = _rows("I422", "I444", "I210", "I212", "I410", "I412")
+OLD = _rows("I420", "I010", "I012")
 
 
 def rotation(deg, tx=0.0, ty=0.0):

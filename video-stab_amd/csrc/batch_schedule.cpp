@@ -120,8 +120,8 @@ bool group_make_events(vs_batch* g) {
 bool same_launch_shape(const vs_stab* a, const vs_stab* b) {
     const vs_params_c &p = a->p, &q = b->p;
     return a->w == b->w && a->h == b->h && a->fmt == b->fmt && a->src_pitch == b->src_pitch && a->zero_copy == b->zero_copy &&
-           a->in_uv_off == b->in_uv_off && a->out_uv_off == b->out_uv_off && a->in_u_off == b->in_u_off && a->in_v_off == b->in_v_off &&
-           a->in_c_pitch == b->in_c_pitch && a->out_u_off == b->out_u_off && a->out_v_off == b->out_v_off && a->out_c_pitch == b->out_c_pitch && a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
+           a->in == b->in && a->out == b->out &&
+           a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
            p.lk_win_size == q.lk_win_size && p.ransac_max_iters == q.ransac_max_iters && p.border_size == q.border_size &&
            p.crop_n_zoom == q.crop_n_zoom && (p.border_size <= 0 || p.border_type == q.border_type);
 }
@@ -147,7 +147,7 @@ int group_allocate(vs_batch* g) {
     const size_t o_minv[2] = {take((size_t)cap * 96), take((size_t)cap * 96)};
     int tow, toh;
     out_size(s0, s0->w, s0->h, &tow, &toh);
-    g->tab_ints = fmt_three_planes(s0->fmt) ? planar_tab_ints(s0->w, s0->h, fmt_chroma_sx(s0->fmt), fmt_chroma_sy(s0->fmt)) : fmt_two_planes(s0->fmt) ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
+    g->tab_ints = s0->pf->three_planes() ? planar_tab_ints(s0->w, s0->h, s0->pf->sx, s0->pf->sy) : s0->pf->luma_uv() ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
     size_t o_tabs[2];
     for (auto& o : o_tabs) o = take((size_t)g->tab_ints * cap * sizeof(int32_t));
     VS_OBJ_HIP(g, hipMalloc((void**)&g->d_all, off));
@@ -203,18 +203,18 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
         if (rc != VS_OK) break;
         const WarpMaps maps{g->d_MinvB[R.set] + 12 * i0, 12, false};
         const WarpTabs tabs{WarpTabs::CALLER, g->d_tabs[R.set] + (size_t)i0 * g->tab_ints, g->tab_ints, what};
-        if (fmt_two_planes(s0->fmt)) {
+        if (s0->pf->luma_uv()) {
             // interleaved chroma plane: half size, two channels, the map with the halved translation (Minv + 6)
             const uint8_t* us[WARP_BATCH_MAX];
             uint8_t* ud[WARP_BATCH_MAX];
             for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + dst_uv(s0, dsts[i], R.stride); }
-            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, fmt_sample_bytes(s0->fmt));
+            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, s0->pf->sample_bytes);
             continue;
         }
-        if (fmt_three_planes(s0->fmt)) {
+        if (s0->pf->three_planes()) {
             // I420, I010, I012: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
-            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, fmt_sample_bytes(s0->fmt),
-                                  fmt_chroma_sx(s0->fmt), fmt_chroma_sy(s0->fmt));
+            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, s0->pf->sample_bytes,
+                                  s0->pf->sx, s0->pf->sy);
             continue;
         }
         rc = launch_warp_plane(srcs, dsts, m, bp.pad ? bp.prow : s0->src_pitch, bp.pw, bp.ph, bp.crop ? bp.prow : R.stride, bp.pw, bp.ph, s0->cn, maps,
@@ -315,11 +315,11 @@ int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const
                 const WarpEnds e = warp_ends(s, b.out_frame, b.d_out, npad, bp);
                 int32_t* T = g->d_tabs[set] + (size_t)j * g->tab_ints;
                 jobs[0] = WarpTabJob{T, e.src, e.dst, bp.pw, bp.ph};
-                if (fmt_two_planes(s->fmt))
+                if (s->pf->luma_uv())
                     jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + dst_uv(s, e.dst, b.out_stride), s->w / 2, s->h / 2};
-                else if (fmt_three_planes(s->fmt))      // ONE chroma table, in pixels, naming the U planes: a V tile adds the launch's V - U
-                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + dst_i420(s, e.dst, b.out_stride).u, s->w >> fmt_chroma_sx(s->fmt),
-                                         s->h >> fmt_chroma_sy(s->fmt)};      // (sized for the format's chroma planes: 4:2:0 halves both)
+                else if (s->pf->three_planes())      // ONE chroma table, in pixels, naming the U planes: a V tile adds the launch's V - U
+                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + dst_i420(s, e.dst, b.out_stride).u, s->w >> s->pf->sx,
+                                         s->h >> s->pf->sy};      // (sized for the format's chroma planes: 4:2:0 halves both)
             }
             npad++;
             P.pend_stride = b.out_stride;
@@ -422,7 +422,7 @@ int step_issue_pre(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan
         StageScope t(g->ref, VS_STAGE_GRAY, pre);
         // NV12, I420: the Y plane is the gray image (no reference path; same policy as the per-frame pipeline); P010: the high bytes
         // of the Y plane's samples are, I010 / I012: their values shifted down to 8 bits (the resize kernels read them in place)
-        const int gfmt = fmt_gray_source(s0->fmt);
+        const int gfmt = s0->pf->gray_source;
         const int n_a = (P.ndet > 0 && P.ndet < n) ? P.ndet : n;
         VS_OBJ_TRY(g, launch_resize_gray_batch(d_pairs, n_a, s0->src_pitch, s0->w, s0->h, gfmt, s0->aw, s0->aw, s0->ah, P.aligned, pre));  // :448-450
         VS_OBJ_HIP(g, hipEventRecord(g->ev_bgray, pre));      // the detector needs the analysis images of its frames only

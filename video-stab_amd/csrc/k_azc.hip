@@ -806,14 +806,15 @@ int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* cons
 int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in, void* d_out, const vs_i420_layout* out,
                           int64_t* ticket) {
     if (!a || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
-    if (fmt != VS_FMT_I420 && fmt != VS_FMT_I010 && fmt != VS_FMT_I012)
+    const PixFmt* f = pixfmt(fmt);
+    if (!f || !f->planar_420())
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: the planar entry point takes VS_FMT_I420, VS_FMT_I010 or VS_FMT_I012");
     I420Layout sl, dl;
     std::string msg;
     if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "auto zoom/crop", &sl, &msg) != VS_OK ||
         planar_layout_check(fmt, d_out, w, h, out, std::max(w, 640), std::max(h, 360), "auto zoom/crop (result: max(w, 640) x max(h, 360))", &dl, &msg) != VS_OK)
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, msg.c_str());
-    return azc_hand_over(a, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, ticket, fmt == VS_FMT_I420 ? 1 : 2, fmt, sl, dl);
+    return azc_hand_over(a, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, ticket, f->sample_bytes, fmt, sl, dl);
 }
 
 int vs_azc_apply_i420_dev_n(vs_azc* a, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, const vs_i420_layout* in,

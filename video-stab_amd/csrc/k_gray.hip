@@ -17,6 +17,7 @@
 // I010 / I012 luma planes: 16-bit samples with the value in the low bits - the gray image is that of the 8-bit plane
 // min(sample >> shift, 255), shift = bits - 8 (2 / 4), resized as a GRAY8 picture is (the *_lo16 kernels: the shift is an argument,
 // one kernel for both depths; the saturation says what a sample beyond its depth does).
+#include "pixfmt.h"
 #include "vs_common.h"
 
 namespace vsd {
@@ -352,7 +353,8 @@ __global__ __launch_bounds__(NT) void quarter_gray_lo16_kernel(size_t sstride, s
 // The shift of a format whose luma samples carry their value in the low bits (10-bit - I010, I210, I410: 2; 12-bit - I012, I212,
 // I412: 4); 0 for every other format.
 int lo16_shift(int fmt) {
-    return fmt == VS_FMT_I010 || fmt == VS_FMT_I210 || fmt == VS_FMT_I410 ? 2 : fmt == VS_FMT_I012 || fmt == VS_FMT_I212 || fmt == VS_FMT_I412 ? 4 : 0;
+    const PixFmt* f = pixfmt(fmt);
+    return f ? f->lo16_shift() : 0;
 }
 
 // Byte of B inside a pixel and the pixel's size of a colour format; false for GRAY8 / NV12 / anything else.

@@ -1225,13 +1225,14 @@ int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* 
 // de-interleaved result of vs_roll_correct_nv12_dev on the same samples.  NV12, P010 and planar surfaces may alternate on one object.
 int vs_roll_correct_i420_dev(vs_roll* r, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in, void* d_out, const vs_i420_layout* out) {
     if (!r || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
-    if (fmt != VS_FMT_I420 && fmt != VS_FMT_I010 && fmt != VS_FMT_I012)
+    const PixFmt* f = pixfmt(fmt);
+    if (!f || !f->planar_420())
         return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: the planar entry point takes VS_FMT_I420, VS_FMT_I010 or VS_FMT_I012");
     I420Layout sl, dl;
     std::string msg;
     if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "roll", &sl, &msg) != VS_OK || planar_layout_check(fmt, d_out, w, h, out, w, h, "roll (result)", &dl, &msg) != VS_OK)
         return vs_obj_fail(r, VS_ERR_INVALID_ARG, msg.c_str());
-    return roll_hand_over(r, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, fmt == VS_FMT_I420 ? 1 : 2, fmt, sl, dl);
+    return roll_hand_over(r, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, f->sample_bytes, fmt, sl, dl);
 }
 
 int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, const vs_i420_layout* in,

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <string>
 
+#include "pixfmt.h"
 #include "traj_state.h"
 #include "vs_common.h"
 #include "warp_tab.h"
@@ -48,24 +49,6 @@ int gftt_fill_item(void* host_item, const uint8_t* d_gray, size_t stride, int w,
 int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_size, hipStream_t st, int what);
 
 // ---- k_warp.hip: planar surfaces (I420 / YV12, I010 / I012; 4:2:2 and 4:4:4: I422, I444, I210, I212, I410, I412) of w x h luma pixels
-// The three-plane formats in one table: the name of the format, the name the stream's messages use (the two 4:2:0 16-bit formats
-// have always been named together), the chroma shifts - a chroma plane has (w >> sx) x (h >> sy) samples: 4:2:0 (1, 1), 4:2:2 (1, 0),
-// 4:4:4 (0, 0) -, the bytes of a sample and the bits of its value (16-bit samples carry it in the low bits).
-struct PlanarFmt { int fmt; const char* name; const char* text; int sx, sy, sample_bytes, bits; };
-inline const PlanarFmt* planar_fmt(int fmt) {       // nullptr: not a three-plane format
-    static const PlanarFmt T[] = {
-        {VS_FMT_I420, "I420", "I420", 1, 1, 1, 8},        {VS_FMT_I010, "I010", "I010 / I012", 1, 1, 2, 10}, {VS_FMT_I012, "I012", "I010 / I012", 1, 1, 2, 12},
-        {VS_FMT_I422, "I422", "I422", 1, 0, 1, 8},        {VS_FMT_I444, "I444", "I444", 0, 0, 1, 8},
-        {VS_FMT_I210, "I210", "I210", 1, 0, 2, 10},       {VS_FMT_I212, "I212", "I212", 1, 0, 2, 12},
-        {VS_FMT_I410, "I410", "I410", 0, 0, 2, 10},       {VS_FMT_I412, "I412", "I412", 0, 0, 2, 12},
-    };
-    for (const PlanarFmt& f : T)
-        if (f.fmt == fmt) return &f;
-    return nullptr;
-}
-// (any other format: 4:2:0's shifts, which nobody asks for)
-inline int fmt_chroma_sx(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f ? f->sx : 1; }
-inline int fmt_chroma_sy(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f ? f->sy : 1; }
 // Where the planes of a surface lie: rows of `pitch` bytes of luma at the surface pointer, the U and V planes (h >> sy rows of
 // w >> sx samples, `cpitch` bytes apart) u and v bytes behind it.  One layout for all source surfaces of a call, one for all destinations.
 struct I420Layout { size_t pitch, cpitch, u, v; };
@@ -87,15 +70,13 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
                      WarpTabs tabs, hipStream_t st, int sample_bytes = 1, int sx = 1, int sy = 1);
 
 // ---- k_roll.hip, k_azc.hip: planar 4:2:0 surfaces (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012) of the stages around the stabilizer
-inline const char* planar_name(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f ? f->name : ""; }
-
 // The geometry and layout rules of a planar surface handed to the roll / zoom stages (those vs_stab enforces).  need_w / need_h: the
 // samples per row and the rows the layout must hold - the picture's, or for the zoom stage's result the larger of the picture's and
 // 640 x 360.  Fills *l with the defaults resolved, or *msg with a text that names the stage and the format.
 inline int planar_layout_check(int fmt, const void* ptr, int w, int h, const vs_i420_layout* in, int need_w, int need_h, const char* stage,
                                I420Layout* l, std::string* msg) {
-    const int sb = fmt == VS_FMT_I420 ? 1 : 2;
-    const char* name = planar_name(fmt);
+    const int sb = pixfmt(fmt)->sample_bytes;
+    const char* name = pixfmt(fmt)->name;
     auto fail = [&](const char* what) { *msg = std::string(stage) + ": " + name + ": " + what; return (int)VS_ERR_INVALID_ARG; };
     if ((w & 1) || (h & 1) || w < 2 || h < 2) return fail("w and h must be even");
     if (!in || in->pitch < (size_t)need_w * sb) return fail("the pitch must hold a row of the picture");

@@ -13,6 +13,7 @@
 #include "canvas.h"
 #include "host_helper.h"
 #include "launchers.h"
+#include "pixfmt.h"
 
 namespace vsd {
 
@@ -58,11 +59,11 @@ struct vs_stab {
     // geometry, fixed by the first frame
     bool allocated = false;
     int w = 0, h = 0, fmt = VS_FMT_BGR8, cn = 3;
+    const vsd::PixFmt* pf = vsd::pixfmt(VS_FMT_BGR8);     // the table row of fmt (pixfmt.h), set with it in allocate_buffers
     size_t row_bytes = 0, frame_bytes = 0;
     size_t src_pitch = 0;               // row pitch of the frames the pipeline reads: row_bytes (queue ring) or the caller's (zero-copy)
-    size_t in_uv_off = 0, out_uv_off = 0;   // NV12 / P010 surfaces of the device entry points: UV plane offset in bytes, 0 = h * pitch
-    // I420 / I010 / I012 surfaces of the device entry points: U / V plane offsets and chroma pitch in bytes, 0 = the packed default of the field
-    size_t in_u_off = 0, in_v_off = 0, in_c_pitch = 0, out_u_off = 0, out_v_off = 0, out_c_pitch = 0;
+    // surfaces of the device entry points: where the chroma of the frames pushed (`in`) and of the surfaces filled (`out`) lies
+    vsd::ChromaLayout in, out;
     int rows_total = 0;
     int aw = 960, ah = 540;
     int levels = 0;                 // max pyramid level actually used
@@ -260,48 +261,23 @@ inline void fill_lk_levels(const vs_stab* s, int pv, int c, LKLevel* L) {
     }
 }
 
-// The two questions the host asks of a frame format beyond its first plane's bytes per pixel (s->cn): does an interleaved chroma
-// plane of half the rows follow the luma plane (NV12, P010), and how many bytes is a sample (2: P010, I010, I012).
-inline bool fmt_two_planes(int fmt) { return fmt == VS_FMT_NV12 || fmt == VS_FMT_P010; }
-inline bool fmt_planar16(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f && f->sample_bytes == 2; }
-inline int fmt_sample_bytes(int fmt) { return fmt == VS_FMT_P010 || fmt_planar16(fmt) ? 2 : 1; }
-inline bool fmt_three_planes(int fmt);
-// rows of `pitch` bytes of a whole (packed) frame: the h luma rows and two chroma planes of (pitch >> sx) x (h >> sy) bytes
-inline int fmt_rows(int fmt, int h) {
-    if (fmt_three_planes(fmt)) return h + (2 * (h >> fmt_chroma_sy(fmt)) >> fmt_chroma_sx(fmt));
-    return fmt_two_planes(fmt) ? h * 3 / 2 : h;
-}
-
 // NV12 / P010: where the interleaved UV plane of a queued frame / of an output surface starts
-inline size_t src_uv(const vs_stab* s) { return (s->zero_copy && s->in_uv_off) ? s->in_uv_off : (size_t)s->h * s->src_pitch; }
+inline size_t src_uv(const vs_stab* s) { return (s->zero_copy && s->in.uv_off) ? s->in.uv_off : (size_t)s->h * s->src_pitch; }
 inline size_t dst_uv(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
-    return (d_out != s->d_out && s->out_uv_off) ? s->out_uv_off : (size_t)s->h * out_stride;   // s->d_out: staging of the host entry points
+    return (d_out != s->d_out && s->out.uv_off) ? s->out.uv_off : (size_t)s->h * out_stride;   // s->d_out: staging of the host entry points
 }
 
-// I420: three planes - Y, then U and V of half the size, one channel each, with a pitch of their own.  A question of its own (an
-// NV12 / P010 frame's chroma part is ONE interleaved plane at the luma pitch: fmt_two_planes), though a whole frame has the same
-// number of bytes.  I010 / I012: the same three planes with 16-bit samples; offsets and pitches stay in bytes.
-// Planar 4:2:2 and 4:4:4 (I422, I444 and their 16-bit forms): the same three planes with chroma planes of (w >> sx) x (h >> sy)
-// samples; everything below reads the one table of these formats (planar_fmt, launchers.h).
-inline bool fmt_three_planes(int fmt) { return planar_fmt(fmt) != nullptr; }
-inline bool fmt_422_444(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f && f->sy == 0; }
-inline const char* fmt_planar_name(int fmt) { const PlanarFmt* f = planar_fmt(fmt); return f ? f->text : ""; }     // as the stream's messages name it
-// Bytes of one chroma row of a three-plane frame of w luma pixels.
-inline size_t fmt_chroma_row_bytes(int fmt, int w) { return (size_t)(w >> fmt_chroma_sx(fmt)) * (size_t)fmt_sample_bytes(fmt); }
-inline I420Layout fmt_i420_layout(int fmt, size_t pitch, int h, size_t u_off, size_t v_off, size_t c_pitch) {
-    return i420_layout(pitch, h, u_off, v_off, c_pitch, fmt_chroma_sx(fmt), fmt_chroma_sy(fmt));
+// The three-plane formats (I420 ... I412): Y, then U and V planes of (w >> sx) x (h >> sy) samples with a pitch of their own;
+// offsets and pitches in bytes whatever the sample.  c: the caller's layout, or ChromaLayout() for the packed default.
+inline I420Layout fmt_i420_layout(const PixFmt& f, size_t pitch, int h, const ChromaLayout& c = ChromaLayout()) {
+    return i420_layout(pitch, h, c.u_off, c.v_off, c.c_pitch, f.sx, f.sy);
 }
 // ... where the planes of a queued frame / of an output surface lie.  The queue ring and the staging of the host entry points hold
 // the packed default layout; the caller's layout (vs_stab_set_i420_layout) applies to zero-copy input and to device outputs.
-inline I420Layout src_i420(const vs_stab* s) {
-    return s->zero_copy ? fmt_i420_layout(s->fmt, s->src_pitch, s->h, s->in_u_off, s->in_v_off, s->in_c_pitch) : fmt_i420_layout(s->fmt, s->src_pitch, s->h, 0, 0, 0);
-}
+inline I420Layout src_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s->src_pitch, s->h, s->zero_copy ? s->in : ChromaLayout()); }
 inline I420Layout dst_i420(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
-    return d_out != s->d_out ? fmt_i420_layout(s->fmt, out_stride, s->h, s->out_u_off, s->out_v_off, s->out_c_pitch) : fmt_i420_layout(s->fmt, out_stride, s->h, 0, 0, 0);
+    return fmt_i420_layout(*s->pf, out_stride, s->h, d_out != s->d_out ? s->out : ChromaLayout());
 }
-// The format the gray kernels are asked for: the Y plane of an NV12 or I420 frame is a GRAY8 image (P010, I010 and I012 name the
-// byte the kernels take from a 16-bit luma sample).
-inline int fmt_gray_source(int fmt) { return fmt == VS_FMT_NV12 || fmt == VS_FMT_I420 || fmt == VS_FMT_I422 || fmt == VS_FMT_I444 ? VS_FMT_GRAY8 : fmt; }
 
 // A ring slot goes back to the free list behind the work on `st` that reads it.  A slot whose event cannot be recorded stays out
 // of the ring: its next writer would have nothing to wait for.

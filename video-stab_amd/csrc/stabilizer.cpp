@@ -40,16 +40,8 @@ using namespace vsd;
 
 namespace {
 
-// Bytes per pixel of a frame format's first plane (NV12 / GRAY8 / I420: the luma byte; P010 / I010 / I012: the 16-bit luma sample); 0 for an unknown format.
-int fmt_cn(int fmt) {
-    switch (fmt) {
-        case VS_FMT_BGR8: case VS_FMT_RGB8: return 3;
-        case VS_FMT_BGRA8: case VS_FMT_RGBA8: return 4;
-        case VS_FMT_NV12: case VS_FMT_GRAY8: case VS_FMT_I420: case VS_FMT_I422: case VS_FMT_I444: return 1;
-        case VS_FMT_P010: case VS_FMT_I010: case VS_FMT_I012: case VS_FMT_I210: case VS_FMT_I212: case VS_FMT_I410: case VS_FMT_I412: return 2;
-        default: return 0;
-    }
-}
+// A refusal of the rules (pixfmt.h) becomes the stream's error.
+#define VS_REFUSE(s, expr) do { const Refusal r_ = (expr); if (r_.rc != VS_OK) return vs_obj_fail((s), r_.rc, r_.text); } while (0)
 
 int flush_warps(vs_stab* s);
 
@@ -119,23 +111,18 @@ int allocate(vs_stab* s, int w, int h, int fmt) {
 }
 
 int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
-    s->w = w; s->h = h; s->fmt = fmt;
-    s->cn = fmt_cn(fmt);
-    s->rows_total = fmt_rows(fmt, h);
+    const PixFmt& f = *pixfmt(fmt);      // (prepare() has refused anything else)
+    s->w = w; s->h = h; s->fmt = fmt; s->pf = &f;
+    s->cn = f.cn;
+    s->rows_total = f.rows(h);
     s->row_bytes = (size_t)w * s->cn;
     s->frame_bytes = s->row_bytes * s->rows_total;
     s->src_pitch = s->row_bytes;
     // the chroma matrix that goes with the frame matrix (traj_matrix_lane): by the subsampling of the stream's chroma planes
-    s->tp.chroma = !fmt_three_planes(fmt) || fmt_chroma_sy(fmt) ? TRAJ_CHROMA_420 : fmt_chroma_sx(fmt) ? TRAJ_CHROMA_422 : TRAJ_CHROMA_444;
+    s->tp.chroma = !f.three_planes() || f.sy ? TRAJ_CHROMA_420 : f.sx ? TRAJ_CHROMA_422 : TRAJ_CHROMA_444;
     analysis_size(s, w, h, &s->aw, &s->ah);
     if (s->aw < 3 || s->ah < 3) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "analysis size too small");
-    // (the reference's cvtColor(BGR2GRAY) of the canvas, Stabilizer.cpp:2225, throws on anything but three channels)
-    if (canvas_on(s) && fmt_422_444(fmt))
-        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, std::string("enableVirtualCanvas needs a BGR8 stream (not ") + fmt_planar_name(fmt) + ")");
-    if (canvas_on(s) && fmt != VS_FMT_BGR8)
-        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, fmt == VS_FMT_P010 ? "enableVirtualCanvas needs a BGR8 stream (not P010)"
-                                                  : fmt == VS_FMT_I420 ? "enableVirtualCanvas needs a BGR8 stream (not I420)"
-                                                  : fmt_planar16(fmt) ? "enableVirtualCanvas needs a BGR8 stream (not I010 / I012)" : "enableVirtualCanvas needs a BGR8 stream");
+    VS_REFUSE(s, check_canvas(f, canvas_on(s)));
     // buildOpticalFlowPyramid: levels that fit the window
     {
         int sw = s->aw, sh = s->ah;
@@ -231,7 +218,7 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     VS_OBJ_TRY(s, get_ransac_tables(ncap, s->p.ransac_max_iters, &s->tab));
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
-    s->out_bytes = (size_t)ow * s->cn * fmt_rows(fmt, oh);
+    s->out_bytes = (size_t)ow * s->cn * f.rows(oh);
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_out, s->out_bytes));
     s->tmp_bytes = std::max(s->out_bytes, s->frame_bytes);
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
@@ -252,8 +239,8 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
 // The three planes of a planar frame (I420 / I010 / I012; 4:2:2, 4:4:4) from one layout to another: rows of w samples, and chroma
 // rows of w >> sx samples, h >> sy of them.
 int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src, const I420Layout& sl, hipMemcpyKind kind, hipStream_t st) {
-    const size_t cw = fmt_chroma_row_bytes(s->fmt, s->w);
-    const int ch = s->h >> fmt_chroma_sy(s->fmt);
+    const size_t cw = s->pf->chroma_row_bytes(s->w);
+    const int ch = s->h >> s->pf->sy;
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, s->row_bytes, s->h, kind, st));
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.u, dl.cpitch, src + sl.u, sl.cpitch, cw, ch, kind, st));
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.v, dl.cpitch, src + sl.v, sl.cpitch, cw, ch, kind, st));
@@ -263,8 +250,8 @@ int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src
 // The result of a host call from its staging buffer (rows of `orow` bytes, `orows` of them; I420: the packed layout at that pitch)
 // into the caller's frame.
 int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st) {
-    if (fmt_three_planes(s->fmt))
-        return copy_i420(s, out, fmt_i420_layout(s->fmt, out_stride, s->h, 0, 0, 0), d_src, fmt_i420_layout(s->fmt, orow, s->h, 0, 0, 0), hipMemcpyDeviceToHost, st);
+    if (s->pf->three_planes())
+        return copy_i420(s, out, fmt_i420_layout(*s->pf, out_stride, s->h), d_src, fmt_i420_layout(*s->pf, orow, s->h), hipMemcpyDeviceToHost, st);
     VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, st));
     return VS_OK;
 }
@@ -274,17 +261,17 @@ int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMem
     if (s->slot_valid[slot]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_slot[slot], 0));
     StageScope t(s, VS_STAGE_COPY_IN, s->st_pre);
     uint8_t* dst = s->d_ring + (size_t)slot * s->frame_bytes;
-    if (fmt_two_planes(s->fmt) && kind == hipMemcpyDeviceToDevice && s->in_uv_off) {      // decoder surface: planes apart
+    if (s->pf->luma_uv() && kind == hipMemcpyDeviceToDevice && s->in.uv_off) {      // decoder surface: planes apart
         VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->h, kind, s->st_pre));
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + (size_t)s->h * s->row_bytes, s->row_bytes, (const uint8_t*)src + s->in_uv_off, stride,
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + (size_t)s->h * s->row_bytes, s->row_bytes, (const uint8_t*)src + s->in.uv_off, stride,
                                   s->row_bytes, s->h / 2, kind, s->st_pre));
         return VS_OK;
     }
-    if (fmt_three_planes(s->fmt)) {
+    if (s->pf->three_planes()) {
         // three planes into the slot's packed layout: from the caller's layout (device surfaces) or the packed default at the
         // caller's pitch (host frames)
-        const I420Layout in = kind == hipMemcpyDeviceToDevice ? fmt_i420_layout(s->fmt, stride, s->h, s->in_u_off, s->in_v_off, s->in_c_pitch) : fmt_i420_layout(s->fmt, stride, s->h, 0, 0, 0);
-        const I420Layout q = fmt_i420_layout(s->fmt, s->row_bytes, s->h, 0, 0, 0);
+        const I420Layout in = fmt_i420_layout(*s->pf, stride, s->h, kind == hipMemcpyDeviceToDevice ? s->in : ChromaLayout());
+        const I420Layout q = fmt_i420_layout(*s->pf, s->row_bytes, s->h);
         VS_OBJ_TRY(s, copy_i420(s, dst, q, (const uint8_t*)src, in, kind, s->st_pre));
         return VS_OK;
     }
@@ -302,7 +289,7 @@ int generate_transform(vs_stab* s, const uint8_t* d_frame, int f) {
     if (f - 3 >= 1 && s->det_valid[(f - 3) % EVR]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_det[(f - 3) % EVR], 0));
     {
         StageScope t(s, VS_STAGE_GRAY, s->st_pre);
-        VS_OBJ_TRY(s, launch_resize_gray(d_frame, s->src_pitch, s->w, s->h, fmt_gray_source(s->fmt), s->pyr[c].img[0], s->aw, s->aw, s->ah, s->st_pre));  // :448-450
+        VS_OBJ_TRY(s, launch_resize_gray(d_frame, s->src_pitch, s->w, s->h, s->pf->gray_source, s->pyr[c].img[0], s->aw, s->aw, s->ah, s->st_pre));  // :448-450
     }
     VS_OBJ_HIP(s, hipEventRecord(s->ev_gray[c], s->st_pre));
     {
@@ -443,7 +430,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
     int ow, oh;
     out_size(s, s->w, s->h, &ow, &oh);
     s->last_out_w = ow; s->last_out_h = oh;
-    const bool plain = idx < s->n_transforms && !fmt_two_planes(s->fmt) && !fmt_three_planes(s->fmt) && p.border_size <= 0 && !canvas_on(s);
+    const bool plain = idx < s->n_transforms && s->pf->kind == PIX_INTERLEAVED && p.border_size <= 0 && !canvas_on(s);
     const BorderPlan bp = border_plan(s);
     if (may_defer && plain && s->warp_batch > 1) {
         VS_OBJ_TRY(s, defer_output(s, idx, frame, d_out, out_stride, slot));
@@ -461,11 +448,11 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // flush): the queued frame is returned as is, at its own size (no border pad).
         if (ow != s->w || oh != s->h)
             VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
-        if (fmt_three_planes(s->fmt))
+        if (s->pf->three_planes())
             VS_OBJ_TRY(s, copy_i420(s, d_out, dst_i420(s, d_out, out_stride), frame, src_i420(s), hipMemcpyDeviceToDevice, st));
         else
             VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
-        if (fmt_two_planes(s->fmt))
+        if (s->pf->luma_uv())
             VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out + dst_uv(s, d_out, out_stride), out_stride, frame + src_uv(s), s->src_pitch, s->row_bytes,
                                       s->h / 2, hipMemcpyDeviceToDevice, st));
         s->last_out_w = s->w; s->last_out_h = s->h;
@@ -474,18 +461,18 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         if (!s->canvas && !(s->canvas = canvas_new())) return vs_obj_fail(s, VS_ERR_HIP, "out of host memory");
         StageScope t(s, VS_STAGE_WARP, st);
         rc = canvas_apply(s->canvas, p, frame, s->src_pitch, s->w, s->h, s->d_ct, s->d_traj, d_out, out_stride, st);
-    } else if (fmt_two_planes(s->fmt)) {
+    } else if (s->pf->luma_uv()) {
         StageScope t(s, VS_STAGE_WARP, st);
         const uint8_t* uv = frame + src_uv(s);
         uint8_t* out_uv = d_out + dst_uv(s, d_out, out_stride);
         // (a P010 surface goes through the one-launch kernel even on its own: its tables are built in the stream's scratch)
         rc = launch_warp_nv12(&frame, &d_out, &uv, &out_uv, 1, s->src_pitch, out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
-                              VS_BORDER_BLACK, s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, fmt_sample_bytes(s->fmt));
-    } else if (fmt_three_planes(s->fmt)) {
+                              VS_BORDER_BLACK, s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, s->pf->sample_bytes);
+    } else if (s->pf->three_planes()) {
         // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
         StageScope t(s, VS_STAGE_WARP, st);
         rc = launch_warp_i420(&frame, &d_out, 1, src_i420(s), dst_i420(s, d_out, out_stride), s->w, s->h, WarpMaps{s->d_Minv, 12, false}, VS_BORDER_BLACK,
-                              WarpTabs{WarpTabs::SCRATCH}, st, fmt_sample_bytes(s->fmt), fmt_chroma_sx(s->fmt), fmt_chroma_sy(s->fmt));
+                              WarpTabs{WarpTabs::SCRATCH}, st, s->pf->sample_bytes, s->pf->sx, s->pf->sy);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
         const size_t prow = bp.prow, nb = prow * bh;
@@ -619,7 +606,7 @@ int push_common(vs_stab* s, int slot, const uint8_t* zc_frame, uint8_t* d_out, s
     s->counters.frames_in++;
     if (p.crop_n_zoom && s->orig_w == 0) { s->orig_w = s->w; s->orig_h = s->h; }   // :267-269
     if (s->first) {                                                                  // :271-368
-        VS_OBJ_TRY(s, launch_resize_gray(frame, s->src_pitch, s->w, s->h, fmt_gray_source(s->fmt), s->d_first_gray, 480, 480, 270, s->st_pre));  // :304-305
+        VS_OBJ_TRY(s, launch_resize_gray(frame, s->src_pitch, s->w, s->h, s->pf->gray_source, s->d_first_gray, 480, 480, 270, s->st_pre));  // :304-305
         VS_OBJ_HIP(s, hipEventRecord(s->ev_first, s->st_pre));
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_det, s->ev_first, 0));
         VS_OBJ_TRY(s, launch_gftt(s->d_first_gray, 480, 480, 270, p.max_corners, p.quality_level, p.min_distance,
@@ -667,61 +654,9 @@ int take_slot(vs_stab* s, int* slot) {
     return VS_OK;
 }
 
-// I010 / I012: a pitch in bytes holds 16-bit samples, and with the default chroma pitch - half of it - so does that.
-// (4:4:4: the default chroma pitch is the pitch itself.)
-bool planar16_bad_pitch(int fmt, size_t pitch, size_t c_pitch) { return (pitch & 1) || (!c_pitch && fmt_chroma_sx(fmt) && (pitch & 3)); }
-std::string planar16_out(int fmt) {
-    return std::string(fmt_planar_name(fmt)) + (fmt_422_444(fmt) && !fmt_chroma_sx(fmt) ? " needs even surface pointers and pitches (16-bit samples)"
-                       : fmt_422_444(fmt) ? " needs even surface pointers and pitches (16-bit samples; a default chroma pitch is half the pitch)"
-                                          : " need even surface pointers and pitches (16-bit samples; a default chroma pitch is half the pitch)");
-}
-// I420 and I422: the default chroma pitch is half the pitch
-bool planar8_half_pitch(int fmt) { return fmt == VS_FMT_I420 || fmt == VS_FMT_I422; }
-std::string planar8_out(int fmt) { return std::string(fmt_planar_name(fmt)) + " needs an even output pitch (the default chroma pitch is half of it)"; }
-
+// What every push asks first: the rules of the input side (pixfmt.h), then the stream allocates for its first frame.
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
-    const int cn = fmt_cn(fmt);
-    if (w <= 0 || h <= 0 || cn == 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: bad geometry/format");
-    if (fmt == VS_FMT_NV12 && ((w & 1) || (h & 1))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "NV12 needs even w,h");
-    if (fmt == VS_FMT_P010 && ((w & 1) || (h & 1))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even w,h");
-    if (fmt == VS_FMT_P010 && ((stride | s->in_uv_off | s->out_uv_off) & 1))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even pitches and plane offsets (16-bit samples)");
-    if (fmt == VS_FMT_I420) {
-        if ((w & 1) || (h & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs even w,h");
-        if (stride & 1) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420 needs an even pitch (the default chroma pitch is half of it)");
-        if ((s->in_c_pitch && s->in_c_pitch < (size_t)w / 2) || (s->out_c_pitch && s->out_c_pitch < (size_t)w / 2))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I420: the chroma pitch must be at least w / 2");
-        if (s->p.border_size > 0)
-            return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not I420");
-    }
-    if (fmt_planar16(fmt) && !fmt_422_444(fmt)) {
-        if ((w & 1) || (h & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012 need even w,h");
-        if (planar16_bad_pitch(fmt, stride, s->in_c_pitch) || ((s->in_u_off | s->in_v_off | s->in_c_pitch | s->out_u_off | s->out_v_off | s->out_c_pitch) & 1))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012 need even pitches and plane offsets (16-bit samples; a default chroma pitch is half the pitch)");
-        if ((s->in_c_pitch && s->in_c_pitch < (size_t)w) || (s->out_c_pitch && s->out_c_pitch < (size_t)w))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "I010 / I012: the chroma pitch must be at least w bytes");
-        if (s->p.border_size > 0)
-            return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not I010 / I012");
-    }
-    if (fmt_422_444(fmt)) {
-        const std::string name = fmt_planar_name(fmt);
-        const int sb = fmt_sample_bytes(fmt);
-        const size_t crow = fmt_chroma_row_bytes(fmt, w);
-        if (fmt_chroma_sx(fmt) && (w & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + " needs an even w");
-        if (sb == 1 && fmt_chroma_sx(fmt) && (stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + " needs an even pitch (the default chroma pitch is half of it)");
-        if (sb == 2 && (planar16_bad_pitch(fmt, stride, s->in_c_pitch) || ((s->in_u_off | s->in_v_off | s->in_c_pitch | s->out_u_off | s->out_v_off | s->out_c_pitch) & 1)))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + (fmt_chroma_sx(fmt) ? " needs even pitches and plane offsets (16-bit samples; a default chroma pitch is half the pitch)"
-                                                                                  : " needs even pitches and plane offsets (16-bit samples)"));
-        if ((s->in_c_pitch && s->in_c_pitch < crow) || (s->out_c_pitch && s->out_c_pitch < crow))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, name + ": the chroma pitch must hold a chroma row (" + std::to_string(crow) + " bytes)");
-        if (s->p.border_size > 0)
-            return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not " + name);
-    }
-    // (the border, fade and crop steps work per byte of an interleaved frame: any colour format; not NV12 / GRAY8 / P010 / I420 / I010 / I012)
-    if (fmt == VS_FMT_P010 && s->p.border_size > 0)
-        return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not P010");
-    if (cn == 1 && s->p.border_size > 0) return vs_obj_fail(s, VS_ERR_UNSUPPORTED, "border/crop modes need a colour format (BGR8, BGRA8, RGBA8, RGB8)");
-    if (stride < (size_t)w * cn) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: stride < row bytes");
+    VS_REFUSE(s, check_input(pixfmt(fmt), w, h, stride, s->in, s->out, s->p.border_size));
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     if (!s->allocated) return allocate(s, w, h, fmt);
     if (w != s->w || h != s->h || fmt != s->fmt) return vs_obj_fail(s, VS_ERR_SIZE_CHANGED, "frame geometry changed; call vs_stab_clean()");
@@ -905,11 +840,7 @@ int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride
     if (!d_data) return VS_OK;   // empty frame -> empty result (Stabilizer.cpp:263-265)
     int rc = prepare(s, w, h, fmt, stride);
     if (rc != VS_OK) return rc;
-    if (fmt == VS_FMT_P010 && (((uintptr_t)d_data | (uintptr_t)d_out | out_stride) & 1))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
-    if (planar8_half_pitch(fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(fmt));
-    if (fmt_planar16(fmt) && ((((uintptr_t)d_data | (uintptr_t)d_out) & 1) || planar16_bad_pitch(fmt, out_stride, s->out_c_pitch)))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(fmt));
+    VS_REFUSE(s, check_surface(*s->pf, true, (uintptr_t)d_data | (uintptr_t)d_out, out_stride, s->out.c_pitch));
     if (s->zero_copy) {
         // the frame is read where it is: it must stay valid and unchanged until its own result has been produced
         // one pitch for all frames in flight (the batched launches take it once): it may change when nothing is queued
@@ -946,11 +877,7 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
     if (!s || !produced) return VS_ERR_INVALID_ARG;
     *produced = 0;
     if (!s->allocated || s->q_slot.empty()) return VS_OK;
-    if (s->fmt == VS_FMT_P010 && (((uintptr_t)d_out | out_stride) & 1))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "P010 needs even surface pointers and pitches (16-bit samples)");
-    if (planar8_half_pitch(s->fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(s->fmt));
-    if (fmt_planar16(s->fmt) && (((uintptr_t)d_out & 1) || planar16_bad_pitch(s->fmt, out_stride, d_out != s->d_out ? s->out_c_pitch : 0)))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(s->fmt));
+    VS_REFUSE(s, check_surface(*s->pf, true, (uintptr_t)d_out, out_stride, d_out != s->d_out ? s->out.c_pitch : 0));   // (s->d_out: the staging of vs_stab_flush)
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
@@ -972,13 +899,12 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
     const size_t orow = (size_t)ow * s->cn;
-    const int orows = fmt_rows(fmt, oh);
+    const int orows = s->pf->rows(oh);
     const bool have_prev = s->hold_valid;
     // (as in the synchronous call: the buffer is only looked at when a frame will be delivered into it; a held frame is
     // always a full-size one - pass-through frames only come out of vs_stab_flush's synchronous part)
-    if (have_prev && (!out || out_stride < orow)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
-    if (planar8_half_pitch(fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(fmt));
-    if (fmt_planar16(fmt) && planar16_bad_pitch(fmt, out_stride, 0)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(fmt));
+    if (have_prev) VS_REFUSE(s, check_host_out("push", out != nullptr, out_stride, orow));
+    VS_REFUSE(s, check_surface(*s->pf, false, 0, out_stride, 0));
     for (auto& hld : s->d_hold)
         if (!hld) VS_OBJ_HIP(s, hipMalloc((void**)&hld, s->out_bytes));
     // A copy to or from PAGEABLE memory (the frames of a cv::Mat) keeps its caller inside hipMemcpy for the whole transfer -
@@ -999,7 +925,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
         const uint8_t* d_src = s->d_hold[s->hold_cur ^ 1];
 
         bool helped = false;
-        if (use_helper && !fmt_three_planes(s->fmt) && !host_ptr_page_locked(out)) {
+        if (use_helper && !s->pf->three_planes() && !host_ptr_page_locked(out)) {
             try {           // (no exception leaves the C ABI: without a helper thread the download goes out from this one)
                 if (!s->helper) s->helper.reset(new HostHelper);
                 const int dev = s->device;
@@ -1048,20 +974,18 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
     if (!data) return VS_OK;
     int rc = prepare(s, w, h, fmt, stride);
     if (rc != VS_OK) return rc;
-    if (s->zero_copy && (s->src_pitch != s->row_bytes || (fmt_two_planes(s->fmt) && s->in_uv_off) ||
-                         (fmt_three_planes(s->fmt) && (s->in_u_off || s->in_v_off || s->in_c_pitch))))
+    if (s->zero_copy && (s->src_pitch != s->row_bytes || (s->pf->luma_uv() && s->in.uv_off) || (s->pf->three_planes() && s->in.planar_bits())))
         return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: host frames cannot join a queue of pitched zero-copy surfaces");
-    if (planar8_half_pitch(fmt) && out && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(fmt));
-    // (host frames hold the packed default layout at their pitch: the chroma pitch is half of it)
-    if (fmt_planar16(fmt) && (planar16_bad_pitch(fmt, stride, 0) || (out && planar16_bad_pitch(fmt, out_stride, 0)))) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(fmt));
+    // (host frames hold the packed default layout at their pitch: the frame pushed, and the buffer of the result if there is one)
+    VS_REFUSE(s, check_surface(*s->pf, false, 0, stride, 0));
+    VS_REFUSE(s, check_surface(*s->pf, false, 0, out ? out_stride : 0, 0));
     if (s->host_pipe && !s->batch_active) return push_host_pipelined(s, data, w, h, stride, fmt, out, out_stride, produced);
     int ow, oh;
     out_size(s, w, h, &ow, &oh);
     const size_t orow = (size_t)ow * s->cn;
     // (the output buffer is checked before the frame is consumed: a bad call loses nothing)
     const int R = effective_radius(s->host_radius);
-    if ((!out || out_stride < orow) && !s->first && (int)s->q_idx.size() + 1 >= R)
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
+    if (!s->first && (int)s->q_idx.size() + 1 >= R) VS_REFUSE(s, check_host_out("push", out != nullptr, out_stride, orow));
     int slot;
     VS_OBJ_TRY(s, take_slot(s, &slot));
     rc = enqueue_copy_in(s, slot, data, stride, hipMemcpyHostToDevice);
@@ -1073,11 +997,12 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
         return rc;
     }
     if (*produced) {
-        if (!out || out_stride < orow) {
+        const Refusal small = check_host_out("push", out != nullptr, out_stride, orow);
+        if (small.rc != VS_OK) {
             (void)hipStreamSynchronize(s->st_pre);
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "push: output buffer/stride too small");
+            return vs_obj_fail(s, small.rc, small.text);
         }
-        const int orows = fmt_rows(fmt, oh);
+        const int orows = s->pf->rows(oh);
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));   // (per-frame pipeline: the warp ran on the warp stream)
         if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));     // batch mode: the warps run on `pre` (group_launch_ready)
         VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st));
@@ -1095,11 +1020,10 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     if (!s->allocated) return VS_OK;
     if (s->hold_valid) {      // host pipeline: the frame the last push computed
         const size_t orow = (size_t)s->hold_w * s->cn;
-        if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
-        const int orows = fmt_rows(s->fmt, s->hold_h);
+        VS_REFUSE(s, check_host_out("flush", out != nullptr, out_stride, orow));
+        const int orows = s->pf->rows(s->hold_h);
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
-        if (planar8_half_pitch(s->fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(s->fmt));
-        if (fmt_planar16(s->fmt) && planar16_bad_pitch(s->fmt, out_stride, 0)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(s->fmt));
+        VS_REFUSE(s, check_surface(*s->pf, false, 0, out_stride, 0));
         VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orows, s->st_warp));
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
         s->hold_valid = false;
@@ -1111,14 +1035,13 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     int ow, oh;
     out_size(s, s->w, s->h, &ow, &oh);
     const size_t orow = (size_t)ow * s->cn;
-    if (!out || out_stride < orow) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "flush: output buffer/stride too small");
-    if (planar8_half_pitch(s->fmt) && (out_stride & 1)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar8_out(s->fmt));
-    if (fmt_planar16(s->fmt) && planar16_bad_pitch(s->fmt, out_stride, 0)) return vs_obj_fail(s, VS_ERR_INVALID_ARG, planar16_out(s->fmt));
+    VS_REFUSE(s, check_host_out("flush", out != nullptr, out_stride, orow));
+    VS_REFUSE(s, check_surface(*s->pf, false, 0, out_stride, 0));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, flush_warps(s));
     int rc = flush_dev_impl(s, s->d_out, orow, produced, false);
     if (rc != VS_OK) return rc;
-    const int orows = fmt_rows(s->fmt, oh);
+    const int orows = s->pf->rows(oh);
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
     if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));         // batch mode: the warps run on `pre`
     VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st));
@@ -1177,10 +1100,9 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
     if (!s) return VS_ERR_INVALID_ARG;
     if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: the frame queue must be empty");
-    if (s->allocated && s->fmt == VS_FMT_P010 && ((in_uv_offset | out_uv_offset) & 1))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: P010 needs even plane offsets (16-bit samples)");
-    s->in_uv_off = in_uv_offset;
-    s->out_uv_off = out_uv_offset;
+    if (s->allocated) VS_REFUSE(s, check_set_nv12_layout(*s->pf, in_uv_offset, out_uv_offset));
+    s->in.uv_off = in_uv_offset;
+    s->out.uv_off = out_uv_offset;
     return VS_OK;
 }
 
@@ -1190,23 +1112,11 @@ int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t
     if (!s) return VS_ERR_INVALID_ARG;
     if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: the frame queue must be empty");
-    if (s->allocated && s->fmt == VS_FMT_I420 && ((in_c_pitch && in_c_pitch < (size_t)s->w / 2) || (out_c_pitch && out_c_pitch < (size_t)s->w / 2)))
-        return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I420: the chroma pitch must be at least w / 2");
-    if (s->allocated && fmt_422_444(s->fmt)) {
-        const std::string name = fmt_planar_name(s->fmt);
-        const size_t crow = fmt_chroma_row_bytes(s->fmt, s->w);
-        if (fmt_sample_bytes(s->fmt) == 2 && ((in_u_off | in_v_off | in_c_pitch | out_u_off | out_v_off | out_c_pitch) & 1))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: " + name + " needs even plane offsets and pitches (16-bit samples)");
-        if ((in_c_pitch && in_c_pitch < crow) || (out_c_pitch && out_c_pitch < crow))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: " + name + ": the chroma pitch must hold a chroma row (" + std::to_string(crow) + " bytes)");
-    } else if (s->allocated && fmt_planar16(s->fmt)) {
-        if ((in_u_off | in_v_off | in_c_pitch | out_u_off | out_v_off | out_c_pitch) & 1)
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I010 / I012 need even plane offsets and pitches (16-bit samples)");
-        if ((in_c_pitch && in_c_pitch < (size_t)s->w) || (out_c_pitch && out_c_pitch < (size_t)s->w))
-            return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: I010 / I012: the chroma pitch must be at least w bytes");
-    }
-    s->in_u_off = in_u_off; s->in_v_off = in_v_off; s->in_c_pitch = in_c_pitch;
-    s->out_u_off = out_u_off; s->out_v_off = out_v_off; s->out_c_pitch = out_c_pitch;
+    ChromaLayout in = s->in, out = s->out;       // (the NV12 offsets are the other setter's)
+    in.u_off = in_u_off; in.v_off = in_v_off; in.c_pitch = in_c_pitch;
+    out.u_off = out_u_off; out.v_off = out_v_off; out.c_pitch = out_c_pitch;
+    if (s->allocated) VS_REFUSE(s, check_set_i420_layout(*s->pf, s->w, in, out));
+    s->in = in; s->out = out;
     return VS_OK;
 }
 

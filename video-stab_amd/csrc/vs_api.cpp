@@ -309,8 +309,8 @@ int vs_op_warp_affine_i010(const void* d_src, size_t src_stride, size_t src_u_of
 int vs_op_warp_affine_planar(int fmt, const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst,
                              size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch,
                              size_t src_frame_bytes, size_t dst_frame_bytes, int border, void* stream) {
-    const PlanarFmt* pf = planar_fmt(fmt);
-    if (!pf) {
+    const PixFmt* pf = pixfmt(fmt);
+    if (!pf || !pf->three_planes()) {
         VS_TRY(ensure_device());
         set_last_error("warp_affine_planar: fmt must be a planar format (VS_FMT_I420 ... VS_FMT_I412)");
         return VS_ERR_INVALID_ARG;

@@ -4,6 +4,7 @@ This is plumbing for tests/bench: every call goes straight into the HIP
 library.  There is no Python or CPU fallback - if the library is missing, or
 no GPU is usable, calls raise.
 """
+import collections
 import ctypes as C
 import os
 
@@ -17,67 +18,78 @@ f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
 
-FMT_BGR8, FMT_NV12, FMT_GRAY8 = 0, 1, 2
-FMT_BGRA8, FMT_RGBA8, FMT_RGB8 = 3, 4, 5
-# bytes per pixel of a format's (first) plane; a colour format's frames are (h, w, channels) arrays
-FMT_CHANNELS = {FMT_BGR8: 3, FMT_NV12: 1, FMT_GRAY8: 1, FMT_BGRA8: 4, FMT_RGBA8: 4, FMT_RGB8: 3}
-# formats with 16-bit samples (vs_pixfmt16): bytes per sample.  A P010 frame is a (h * 3 / 2, w) uint16 array: h rows of luma, h / 2
-# rows of interleaved (U, V) pairs, the ten significant bits at the top of each sample.
-FMT_P010 = 6
-FMT_SAMPLE_BYTES = {FMT_P010: 2}
-# planar 4:2:0 (vs_pixfmt_planar).  A packed I420 frame is a (h * 3 / 2, w) uint8 array: h rows of Y, then the U plane and the V
-# plane, h / 2 rows of w / 2 bytes each (synth.nv12_to_i420).  YV12 and padded chroma rows are layouts of it (set_i420_layout).
-FMT_I420 = 7
-# planar 4:2:0 with 16-bit samples, the value in the low bits (vs_pixfmt_planar16: yuv420p10le / yuv420p12le).  A packed frame is a
-# (h * 3 / 2, w) uint16 array laid out as an I420 frame is (synth.p010_to_i010); other layouts through set_i420_layout, in bytes.
-FMT_I010, FMT_I012 = 8, 9
-# planar 4:2:2 and 4:4:4 (vs_pixfmt_planar4xx): yuv422p, yuv444p, yuv422p10le, yuv422p12le, yuv444p10le, yuv444p12le.  A packed frame
-# is a (2 h, w) (4:2:2) or (3 h, w) (4:4:4) array, uint8 or uint16: h rows of Y, then the U plane and the V plane, h rows of w / 2
-# (4:2:2) or w (4:4:4) samples each (synth.yuv_pack, synth.bgr_to_planar); other layouts through set_i420_layout, in bytes.
-FMT_I422, FMT_I444, FMT_I210, FMT_I212, FMT_I410, FMT_I412 = 10, 11, 12, 13, 14, 15
-# chroma shifts (sx, sy) of the three-plane formats: a chroma plane has (w >> sx) x (h >> sy) samples
-FMT_CHROMA_SHIFTS = {FMT_I420: (1, 1), FMT_I010: (1, 1), FMT_I012: (1, 1), FMT_I422: (1, 0), FMT_I210: (1, 0), FMT_I212: (1, 0),
-                     FMT_I444: (0, 0), FMT_I410: (0, 0), FMT_I412: (0, 0)}
-FMT_PLANAR_BITS = {FMT_I420: 8, FMT_I422: 8, FMT_I444: 8, FMT_I010: 10, FMT_I210: 10, FMT_I410: 10, FMT_I012: 12, FMT_I212: 12, FMT_I412: 12}
+# The pixel formats, one record each: the columns of the C table (csrc/pixfmt.h), which tests/test_pixfmt_table_cpu.py holds this
+# one to.  kind: 0 one plane of interleaved channels, 1 luma + interleaved (U, V) plane (NV12, P010), 2 three planes.  cn: bytes per
+# pixel of the first plane; a chroma plane has (w >> sx) x (h >> sy) samples; gray_source: the format the gray kernels are asked for.
+#
+# A colour format's frames are (h, w, channels) arrays.  The others are (rows, w) arrays, uint8 or uint16: h rows of luma, then
+# NV12 / P010: h / 2 rows of interleaved (U, V) pairs (P010: the ten significant bits at the top of each sample);
+# three planes: the U plane and the V plane, (h >> sy) rows of (w >> sx) samples each, the value in the low bits (I420: synth.nv12_to_i420;
+# I010 / I012: synth.p010_to_i010; 4:2:2 and 4:4:4: synth.yuv_pack, synth.bgr_to_planar).  YV12 and padded chroma rows are layouts
+# of a packed frame (set_i420_layout, in bytes).
+PixFmt = collections.namedtuple("PixFmt", "fmt name text kind cn sample_bytes bits sx sy gray_source border_modes")
+KIND_INTERLEAVED, KIND_LUMA_UV, KIND_THREE_PLANES = range(3)
+PIXFMTS = (
+    PixFmt(0, "BGR8", "BGR8", KIND_INTERLEAVED, 3, 1, 8, 0, 0, 0, True),
+    PixFmt(1, "NV12", "NV12", KIND_LUMA_UV, 1, 1, 8, 1, 1, 2, False),
+    PixFmt(2, "GRAY8", "GRAY8", KIND_INTERLEAVED, 1, 1, 8, 0, 0, 2, False),
+    PixFmt(3, "BGRA8", "BGRA8", KIND_INTERLEAVED, 4, 1, 8, 0, 0, 3, True),
+    PixFmt(4, "RGBA8", "RGBA8", KIND_INTERLEAVED, 4, 1, 8, 0, 0, 4, True),
+    PixFmt(5, "RGB8", "RGB8", KIND_INTERLEAVED, 3, 1, 8, 0, 0, 5, True),
+    PixFmt(6, "P010", "P010", KIND_LUMA_UV, 2, 2, 10, 1, 1, 6, False),
+    PixFmt(7, "I420", "I420", KIND_THREE_PLANES, 1, 1, 8, 1, 1, 2, False),
+    PixFmt(8, "I010", "I010 / I012", KIND_THREE_PLANES, 2, 2, 10, 1, 1, 8, False),       # yuv420p10le
+    PixFmt(9, "I012", "I010 / I012", KIND_THREE_PLANES, 2, 2, 12, 1, 1, 9, False),       # yuv420p12le
+    PixFmt(10, "I422", "I422", KIND_THREE_PLANES, 1, 1, 8, 1, 0, 2, False),              # yuv422p
+    PixFmt(11, "I444", "I444", KIND_THREE_PLANES, 1, 1, 8, 0, 0, 2, False),              # yuv444p
+    PixFmt(12, "I210", "I210", KIND_THREE_PLANES, 2, 2, 10, 1, 0, 12, False),            # yuv422p10le
+    PixFmt(13, "I212", "I212", KIND_THREE_PLANES, 2, 2, 12, 1, 0, 13, False),            # yuv422p12le
+    PixFmt(14, "I410", "I410", KIND_THREE_PLANES, 2, 2, 10, 0, 0, 14, False),            # yuv444p10le
+    PixFmt(15, "I412", "I412", KIND_THREE_PLANES, 2, 2, 12, 0, 0, 15, False),            # yuv444p12le
+)
+PIXFMT = {f.fmt: f for f in PIXFMTS}
+PIXFMT_BY_NAME = {f.name: f for f in PIXFMTS}
+globals().update({"FMT_" + f.name: f.fmt for f in PIXFMTS})        # FMT_BGR8 ... FMT_I412
+
+# the names the tests and synth.py use, read from the table
+FMT_CHANNELS = {f.fmt: f.cn for f in PIXFMTS if f.sample_bytes == 1 and f.kind != KIND_THREE_PLANES}   # 8-bit: bytes per pixel of the first plane
+FMT_SAMPLE_BYTES = {f.fmt: f.sample_bytes for f in PIXFMTS if f.kind == KIND_LUMA_UV and f.sample_bytes == 2}      # P010
+FMT_CHROMA_SHIFTS = {f.fmt: (f.sx, f.sy) for f in PIXFMTS if f.kind == KIND_THREE_PLANES}
+FMT_PLANAR_BITS = {f.fmt: f.bits for f in PIXFMTS if f.kind == KIND_THREE_PLANES}
 
 
 def fmt_px_bytes(fmt):
     """Bytes per pixel of a format's (first) plane."""
-    if fmt in (FMT_I420, FMT_I422, FMT_I444):
-        return 1
-    if fmt in (FMT_I010, FMT_I012, FMT_I210, FMT_I212, FMT_I410, FMT_I412):
-        return 2
-    return FMT_SAMPLE_BYTES[fmt] if fmt in FMT_SAMPLE_BYTES else FMT_CHANNELS[fmt]
+    return PIXFMT[fmt].cn
 
 
 def fmt_dtype(fmt):
-    return np.uint16 if fmt_px_bytes(fmt) == 2 and fmt not in FMT_CHANNELS else np.uint8
+    return np.uint16 if PIXFMT[fmt].sample_bytes == 2 else np.uint8
 
 
 def fmt_two_planes(fmt):
-    return fmt in (FMT_NV12, FMT_P010)
+    return PIXFMT[fmt].kind == KIND_LUMA_UV
 
 
 def fmt_420(fmt):
     """A frame array of this format has h * 3 / 2 rows: h of luma, h / 2 of subsampled chroma."""
-    return fmt_two_planes(fmt) or fmt in (FMT_I420, FMT_I010, FMT_I012)
+    f = PIXFMT[fmt]
+    return f.kind != KIND_INTERLEAVED and f.sy == 1
 
 
 def fmt_frame_rows(fmt, h):
     """Rows of a packed frame array of h picture rows (its columns: w)."""
-    if fmt in (FMT_I422, FMT_I210, FMT_I212):
-        return 2 * h
-    if fmt in (FMT_I444, FMT_I410, FMT_I412):
-        return 3 * h
+    f = PIXFMT[fmt]
+    if f.kind == KIND_THREE_PLANES and not f.sy:
+        return h + (2 * h >> f.sx)
     return h * 3 // 2 if fmt_420(fmt) else h
 
 
 def fmt_picture_rows(fmt, rows):
     """The picture's rows of a packed frame array with `rows` rows: the inverse of fmt_frame_rows."""
-    if fmt in (FMT_I422, FMT_I210, FMT_I212):
-        return rows // 2
-    if fmt in (FMT_I444, FMT_I410, FMT_I412):
-        return rows // 3
+    f = PIXFMT[fmt]
+    if f.kind == KIND_THREE_PLANES and not f.sy:
+        return rows // (1 + (2 >> f.sx))
     return rows * 2 // 3 if fmt_420(fmt) else rows
 
 
