@@ -39,8 +39,9 @@ extern "C" {
  *    vs_op_warp_affine16_ex; the same two stages on I420 / I010 / I012 surfaces: struct vs_i420_layout with
  *    vs_roll_correct_i420_dev, vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev and vs_azc_apply_i420_dev_n; planar 4:2:2 and
  *    4:4:4 - VS_FMT_I422, VS_FMT_I444, VS_FMT_I210, VS_FMT_I212, VS_FMT_I410, VS_FMT_I412 (enum vs_pixfmt_planar4xx) - with
- *    vs_op_warp_affine_planar (new entry points, new values and a new struct only: no existing struct or entry point changed, so
- *    the version stays). */
+ *    vs_op_warp_affine_planar; the output size of auto zoom/crop: vs_azc_set_output_size, vs_azc_get_output_size, struct
+ *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan (new entry points, new values and new structs only: no existing
+ *    struct or entry point changed, so the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -765,7 +766,7 @@ const char* vs_azc_last_error(const vs_azc* a);
 /* cv::Mat AutoZoomCrop::autoZoomCrop(const cv::Mat& corrected, double marginPercent)
  * (marginPercent is ignored by the reference, AutoZoomCrop.cpp:102).  BGR8 (cn 3) or gray
  * (cn 1).  `out` must hold max(w*h, 640*360)*cn bytes and receives packed rows; the
- * result is 640x360, or the unchanged w x h frame on the reference's fall-back paths
+ * result is 640x360 (ow x oh after vs_azc_set_output_size, here and below), or the unchanged w x h frame on the reference's fall-back paths
  * (no contour :149-152, empty crop :238-249).  Synchronous. */
 int vs_azc_apply(vs_azc* a, const uint8_t* data, int w, int h, size_t stride, int cn,
                  uint8_t* out, int* out_w, int* out_h);
@@ -808,6 +809,29 @@ int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int 
 int vs_azc_apply_i420_dev_n(vs_azc* a, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                             const vs_i420_layout* in, const vs_i420_layout* out, int64_t* tickets);
 int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* info8);
+/* The output size of the crop-and-scale: ow x oh wherever the comments above say 640 x 360 (the reference hard-codes its author's
+ * frame size, AutoZoomCrop.cpp:246-261; the stage means "crop the black corners and zoom back to the frame").  A new object has
+ * (640, 360).  (0, 0) = the size of the surface handed over: every result is w x h.  Otherwise both values even and in 2 .. 8192;
+ * anything else is VS_ERR_INVALID_ARG with a text in vs_azc_last_error.  The setting is the object's and every entry point obeys it:
+ * luma / BGR / gray scaled by [(float)((double)ow / cw), 0, 0; 0, (float)((double)oh / ch), 0] to ow x oh, the chroma planes of the
+ * 4:2:0 surfaces by [(float)((double)(ow / 2) / uw), 0, 0; 0, (float)((double)(oh / 2) / uh), 0] to (ow / 2) x (oh / 2); buffer and
+ * layout rules read max(w, ow) and max(h, oh).  The crop rectangle, info8, the mask and the contours do not depend on it; on the
+ * fall-back paths the surface comes back unchanged, w x h.  It applies to frames handed over after the call: like a change of
+ * geometry it closes the pending batch, and tickets already issued keep the size they were issued under. */
+int vs_azc_set_output_size(vs_azc* a, int out_w, int out_h);
+int vs_azc_get_output_size(const vs_azc* a, int* out_w, int* out_h);
+/* The stage's crop-and-scale as an operator (the call the stage itself makes for a batch): n <= 24 jobs of one sample size (1 or 2
+ * bytes; cn 1 or 2), src = the crop's first sample, each crop scaled to dw x dh by the matrix above (INTER_LINEAR, BORDER_CONSTANT 0:
+ * a tap outside the sw x sh crop is 0 even where the plane has samples there; 8-bit arithmetic of vs_op_warp_affine_ex, 16-bit
+ * P010's blend).  Sizes 1 .. 32767, strides in bytes, reserved = 0; 16-bit pointers and strides even.
+ * path 0: as the stage chooses per job - a job whose output tiles' source boxes fit the staging area (every zoom-in, downscales by
+ * less than 1.19 across and 1.4 down) goes to the staged kernel, the others to the direct one: one launch per class;
+ * path 1: every job through the direct kernel.  Both give the same bytes. */
+typedef struct vs_scale_job { const void* src; size_t src_stride; int32_t sw, sh;
+                              void* dst; size_t dst_stride; int32_t dw, dh; int32_t cn, reserved; } vs_scale_job;
+int vs_op_scale_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int path, void* stream);
+/* host only, needs no device: staged[i] = 1 where path 0 sends job i to the staged kernel */
+int vs_op_scale_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int32_t* staged);
 /* Diagnostics of the asynchronous path: out9 = {frames through the worker threads; seconds, summed over the threads: without a
  * frame to work on, waiting for the masks of the batches on their way (one worker at a time does), in the contour logic, queueing
  * launches and publishing; batches; seconds, summed over the batches: from a batch's launches to the arrival of its masks on the

@@ -8,7 +8,8 @@
 //   host    crop_from_mask      : border following on the bit mask (pointer chasing along one
 //                                 contour: serial by nature), filled interior as row spans, the
 //                                 shrink loop of :189-205 on the spans
-//   device  warp_affine_kernel  : crop + scale to 640x360 (cv::warpAffine semantics, k_warp.hip)
+//   device  warp_affine_kernel  : crop + scale to the output size, 640x360 unless vs_azc_set_output_size says otherwise
+//                                 (cv::warpAffine semantics, k_warp.hip; the batches of the asynchronous forms: launch_scale_jobs)
 // Only the mask (one bit per pixel) crosses PCIe between the two device stages; the frame stays in HBM.
 #include <algorithm>
 #include <climits>
@@ -285,6 +286,7 @@ struct vs_azc {
     size_t io_bytes = 0;
     CropScratch scratch;
     int32_t info[8] = {0};
+    int ow = 640, oh = 360;           // the output size (vs_azc_set_output_size): the reference's constants, or 0, 0 = the surface's own
     // ---- asynchronous NV12 path (vs_azc_apply_nv12_dev) ----
     // Eight consecutive frames form a batch: their mask kernels are ONE launch each (blockIdx.z = frame) and their bit masks come
     // to page-locked memory with one copy (a launch costs the host 6 - 7 us on this runtime: per frame they were half of the
@@ -296,7 +298,8 @@ struct vs_azc {
     int nw = 12;                         // worker threads (VS_AZC_WORKERS, 1 .. 16): 31 k frames/s alone with eight, 41 k with twelve
     // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420,
     // VS_FMT_I010, VS_FMT_I012) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
-    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; int planar; I420Layout sl, dl; };
+    // ow, oh: the output size the frame was handed over under, resolved (never 0)
+    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; int planar; I420Layout sl, dl; int ow, oh; };
     struct BatchSlot {
         uint8_t* d_masks = nullptr;      // ZB BitFrames
         uint8_t* h_masks = nullptr;      // page-locked
@@ -459,42 +462,43 @@ static int azc_emit(vs_azc* a, const void* d_data, int w, int h, size_t stride, 
         VS_OBJ_HIP(a, hipMemcpy2DAsync(d_out, out_stride, d_data, stride, (size_t)w * cn, h, hipMemcpyDeviceToDevice, a->st));
         return VS_OK;
     }
-    if (out_stride < (size_t)640 * cn) return VS_ERR_INVALID_ARG;
+    const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h;
+    if (out_stride < (size_t)ow * cn) return VS_ERR_INVALID_ARG;
     const int cx = a->info[2], cy = a->info[3], cw = a->info[4], ch = a->info[5];
     // M = [sx 0 0; 0 sy 0] held as CV_32F (:261-262); cv::warpAffine inverts it in double
-    const float Mf[6] = {(float)(640.0 / cw), 0.f, 0.f, 0.f, (float)(360.0 / ch), 0.f};
+    const float Mf[6] = {(float)((double)ow / cw), 0.f, 0.f, 0.f, (float)((double)oh / ch), 0.f};
     double Mi[6];
     warp_invert(Mf, Mi);
     const uint8_t* roi = (const uint8_t*)d_data + (size_t)cy * stride + (size_t)cx * cn;
     uint8_t* out = (uint8_t*)d_out;
-    VS_OBJ_TRY(a, launch_warp_plane(&roi, &out, 1, stride, cw, ch, out_stride, 640, 360, cn, WarpMaps{Mi, 6, true}, VS_BORDER_BLACK, WarpTabs{}, a->st));
+    VS_OBJ_TRY(a, launch_warp_plane(&roi, &out, 1, stride, cw, ch, out_stride, ow, oh, cn, WarpMaps{Mi, 6, true}, VS_BORDER_BLACK, WarpTabs{}, a->st));
     return VS_OK;
 }
 
-// Frame in HBM -> 640x360 crop in HBM (or an unchanged copy on the fallback paths).  out_stride must fit
-// either outcome (>= max(w, 640) * cn).  The result is left in flight on the object's stream (vs_azc_sync).
+// Frame in HBM -> the crop at the output size (ow x oh: 640 x 360, or what vs_azc_set_output_size said) in HBM (or an unchanged copy on
+// the fallback paths).  out_stride must fit either outcome (>= max(w, ow) * cn).  The result is left in flight on the object's stream (vs_azc_sync).
 int vs_azc_apply_dev(vs_azc* a, const void* d_data, int w, int h, size_t stride, int cn, void* d_out, size_t out_stride,
                      int* out_w, int* out_h) {
     if (!a || !d_data || !d_out || !out_w || !out_h || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || stride < (size_t)w * cn ||
-        out_stride < (size_t)std::max(w, 640) * cn)
+        out_stride < (size_t)std::max(w, a->ow) * cn)
         return VS_ERR_INVALID_ARG;
     VS_OBJ_HIP(a, hipSetDevice(a->device));
     int rc = azc_plan(a, d_data, w, h, stride, cn);
     if (rc != VS_OK) return rc;
     rc = azc_emit(a, d_data, w, h, stride, cn, d_out, out_stride);
     if (rc != VS_OK) return rc;
-    *out_w = a->info[7] ? 640 : w;
-    *out_h = a->info[7] ? 360 : h;
+    *out_w = a->info[7] && a->ow ? a->ow : w;
+    *out_h = a->info[7] && a->oh ? a->oh : h;
     return VS_OK;
 }
 
-// cv::Mat autoZoomCrop(const cv::Mat&, double) on host buffers.  `out` must hold max(w*h, 640*360)*cn bytes and
+// cv::Mat autoZoomCrop(const cv::Mat&, double) on host buffers.  `out` must hold max(w*h, ow*oh)*cn bytes and
 // receives packed rows of *out_w * cn bytes.
 int vs_azc_apply(vs_azc* a, const uint8_t* data, int w, int h, size_t stride, int cn, uint8_t* out, int* out_w, int* out_h) {
     if (!a || !data || !out || !out_w || !out_h || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || stride < (size_t)w * cn)
         return VS_ERR_INVALID_ARG;
     VS_OBJ_HIP(a, hipSetDevice(a->device));
-    const size_t row = (size_t)w * cn, bytes = std::max(row * h, (size_t)640 * 360 * cn);
+    const size_t row = (size_t)w * cn, bytes = std::max(row * h, (size_t)(a->ow ? a->ow : w) * (a->oh ? a->oh : h) * cn);
     if (a->io_bytes < bytes) {
         if (a->d_in) (void)hipFree(a->d_in);
         if (a->d_out) (void)hipFree(a->d_out);
@@ -506,7 +510,7 @@ int vs_azc_apply(vs_azc* a, const uint8_t* data, int w, int h, size_t stride, in
     VS_OBJ_HIP(a, hipMemcpy2DAsync(a->d_in, row, data, stride, row, h, hipMemcpyHostToDevice, a->st));
     int rc = azc_plan(a, a->d_in, w, h, row, cn);
     if (rc != VS_OK) return rc;
-    const int ow = a->info[7] ? 640 : w, oh = a->info[7] ? 360 : h;
+    const int ow = a->info[7] && a->ow ? a->ow : w, oh = a->info[7] && a->oh ? a->oh : h;
     rc = azc_emit(a, a->d_in, w, h, row, cn, a->d_out, (size_t)ow * cn);
     if (rc != VS_OK) return rc;
     VS_OBJ_HIP(a, hipMemcpyAsync(out, a->d_out, (size_t)ow * cn * oh, hipMemcpyDeviceToHost, a->st));
@@ -527,7 +531,7 @@ static void azc_publish(vs_azc* a, const vs_azc::Result& res) {
 // crop-and-scale job (or, at once, the copy of the fall-back paths) for both planes on st_out; the worker that finishes a batch's
 // last frame queues the batch's jobs as one launch.  The content mask is taken from the luma plane (gray > 1, :121-127 on a picture
 // that is gray already); the crop rectangle applies to the luma plane as it is and, halved, to the half-size chroma plane;
-// each plane is scaled to its share of 640 x 360 by the reference's scale matrix (:261-270).
+// each plane is scaled to its share of the frame's output size by the reference's scale matrix (:261-270, ow x oh for 640 x 360).
 static void azc_worker(vs_azc* a) {
     (void)hipSetDevice(a->device);
     CropScratch scratch;
@@ -598,35 +602,35 @@ static void azc_worker(vs_azc* a) {
                     hipMemcpy2DAsync(q.dst + q.ouv, q.opitch, q.src + q.uv, q.pitch, (size_t)q.w * q.sb, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
                     rc = VS_ERR_HIP;
             } else {
-                res.out_w = 640; res.out_h = 360;
+                res.out_w = q.ow; res.out_h = q.oh;
                 const int cx = res.info[2], cy = res.info[3], cw = res.info[4], ch = res.info[5];
                 const int ux = cx / 2, uy = cy / 2, uw = std::max(1, cw / 2), uh = std::max(1, ch / 2);
-                const float My[6] = {(float)(640.0 / cw), 0.f, 0.f, 0.f, (float)(360.0 / ch), 0.f};
-                const float Mu[6] = {(float)(320.0 / uw), 0.f, 0.f, 0.f, (float)(180.0 / uh), 0.f};
+                const float My[6] = {(float)((double)q.ow / cw), 0.f, 0.f, 0.f, (float)((double)q.oh / ch), 0.f};
+                const float Mu[6] = {(float)((double)(q.ow / 2) / uw), 0.f, 0.f, 0.f, (float)((double)(q.oh / 2) / uh), 0.f};
                 warp_invert(My, wj[0].m);
                 warp_invert(Mu, wj[1].m);
                 wj[0].src = q.src + (size_t)cy * q.pitch + (size_t)cx * q.sb; wj[0].dst = q.dst;
-                wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = 640; wj[0].dh = 360; wj[0].cn = 1;
+                wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = q.ow; wj[0].dh = q.oh; wj[0].cn = 1;
                 for (WarpJob& w : wj) { w.sstride = (uint32_t)q.pitch; w.dstride = (uint32_t)q.opitch; w.border = VS_BORDER_BLACK; w.sb = q.sb; }
                 if (q.planar) {          // U and V: one-channel planes of half the size, the halved rectangle, rows of their own pitch
                     warp_invert(Mu, wj[2].m);
                     wj[1].src = q.src + q.sl.u + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[1].dst = q.dst + q.dl.u;
                     wj[2].src = q.src + q.sl.v + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[2].dst = q.dst + q.dl.v;
                     for (int k = 1; k < 3; k++) {
-                        wj[k].sw = uw; wj[k].sh = uh; wj[k].dw = 320; wj[k].dh = 180; wj[k].cn = 1;
+                        wj[k].sw = uw; wj[k].sh = uh; wj[k].dw = q.ow / 2; wj[k].dh = q.oh / 2; wj[k].cn = 1;
                         wj[k].sstride = (uint32_t)q.sl.cpitch; wj[k].dstride = (uint32_t)q.dl.cpitch;
                     }
                     nscaled = 3;
                 } else {
                     wj[1].src = q.src + q.uv + (size_t)uy * q.pitch + (size_t)ux * 2 * q.sb; wj[1].dst = q.dst + q.ouv;
-                    wj[1].sw = uw; wj[1].sh = uh; wj[1].dw = 320; wj[1].dh = 180; wj[1].cn = 2;
+                    wj[1].sw = uw; wj[1].sh = uh; wj[1].dw = q.ow / 2; wj[1].dh = q.oh / 2; wj[1].cn = 2;
                     nscaled = 2;
                 }
             }
         }
         res.rc = rc;
-        // The crop-and-scale of the batch's frames is ONE launch (launch_warp_jobs), queued by the worker that finishes the batch's
-        // last contour; a frame counts as complete (vs_azc_sync) when that launch has been queued.
+        // The crop-and-scale of the batch's frames is ONE launch when its jobs are of one class, two when some can be staged and some
+        // cannot (launch_scale_jobs), queued by the worker that finishes the batch's last contour; a frame counts as complete (vs_azc_sync) when that launch has been queued.
         bool last;
         int njobs = 0;
         WarpJob all[3 * vs_azc::ZB];
@@ -638,7 +642,7 @@ static void azc_worker(vs_azc* a) {
             if (last) { njobs = b.nwj; memcpy(all, b.wj, sizeof(WarpJob) * njobs); }
         }
         a->cv_done.notify_all();          // (vs_azc_result waits for the host part only)
-        int lrc = last && njobs ? launch_warp_jobs(all, njobs, a->st_out) : VS_OK;
+        int lrc = last && njobs ? launch_scale_jobs(all, njobs, 0, a->st_out) : VS_OK;
         {
             std::lock_guard<std::mutex> g(a->mu);
             const clk::time_point t_end = clk::now();
@@ -726,9 +730,10 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
     return rc;
 }
 
-// autoZoomCrop for an NV12 surface in HBM, ASYNCHRONOUS.  d_out receives the result - 640 x 360 (luma rows of out_pitch bytes,
-// the 320 x 180 interleaved chroma plane out_uv_offset bytes behind) or, on the reference's fall-back paths, the unchanged
-// w x h surface - so out_pitch >= max(w, 640) and out_uv_offset >= max(h, 360) * out_pitch.  The call returns at once with a
+// autoZoomCrop for an NV12 surface in HBM, ASYNCHRONOUS.  d_out receives the result - ow x oh, the object's output size: 640 x 360
+// unless vs_azc_set_output_size said otherwise (luma rows of out_pitch bytes, the ow / 2 x oh / 2 interleaved chroma plane
+// out_uv_offset bytes behind) - or, on the reference's fall-back paths, the unchanged
+// w x h surface - so out_pitch >= max(w, ow) and out_uv_offset >= max(h, oh) * out_pitch.  The call returns at once with a
 // ticket; eight consecutive frames of one geometry form a batch (vs_azc_sync and vs_azc_result close an incomplete one).
 // vs_azc_result(ticket) tells what came out (it waits for that frame's host part), the pixels are complete after vs_azc_sync.
 // Surface and result buffer must stay untouched until then; results of the last 1024 tickets are kept.
@@ -737,9 +742,9 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
 // their U offsets)
 static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
                          size_t out_uv_offset, int64_t* ticket, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout()) {
-    if (!a || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)std::max(w, 640) * sb ||
-        out_uv_offset < (size_t)std::max(h, 360) * out_pitch)
-        return VS_ERR_INVALID_ARG;
+    if (!a || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb) return VS_ERR_INVALID_ARG;
+    const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h;
+    if (out_pitch < (size_t)std::max(w, ow) * sb || out_uv_offset < (size_t)std::max(h, oh) * out_pitch) return VS_ERR_INVALID_ARG;
     if (sb == 2 && !planar && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: P010 pointers, pitches and plane offsets must be even");
     if (w > 65535 || h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
@@ -756,7 +761,7 @@ static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t 
     }
     std::unique_lock<std::mutex> lk(a->mu);
     // (a change of geometry, of sample size, of format or of a planar surface's layouts closes the pending batch: a batch's launches
-    // take one of each)
+    // take one of each; a change of the output size has closed it already, vs_azc_set_output_size)
     if (!a->pending.empty()) {
         const vs_azc::Frame& p0 = a->pending[0];
         auto same = [](const I420Layout& x, const I420Layout& y) { return x.pitch == y.pitch && x.cpitch == y.cpitch && x.u == y.u && x.v == y.v; };
@@ -765,7 +770,7 @@ static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t 
             if (rc != VS_OK) return rc;
         }
     }
-    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb, planar, sl, dl});
+    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb, planar, sl, dl, ow, oh});
     if (ticket) *ticket = a->issued;
     a->issued++;
     if ((int)a->pending.size() >= vs_azc::ZB) return azc_flush_pending(a, lk);
@@ -777,7 +782,7 @@ int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t
     return azc_hand_over(a, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, ticket, 1);
 }
 
-// The same for a P010 surface (vs_pixfmt16; pitches and offsets in bytes, everything even: out_pitch >= 2 * max(w, 640)).  The content
+// The same for a P010 surface (vs_pixfmt16; pitches and offsets in bytes, everything even: out_pitch >= 2 * max(w, ow)).  The content
 // mask is that of the 8-bit plane of the luma samples' high bytes, (sample >> 8) > 1 - mask, contours, info8 and the crop rectangle are
 // those of the NV12 call on that plane -; crop-and-scale on the 16-bit planes with P010's blend (S rounded once, half to even),
 // BORDER_CONSTANT 0; on the fall-back paths the surface comes back unchanged, all 16 bits.  NV12 and P010 surfaces may alternate on one
@@ -800,9 +805,9 @@ int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* cons
 // The same for a planar 4:2:0 surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010 or VS_FMT_I012; in / out: where
 // the three planes lie (vs_i420_layout: bytes, 0 = the packed default for the chroma pitch and the offsets).  The content mask comes from
 // the 8-bit analysis plane of Y - Y itself, or min(sample >> (bits - 8), 255) -; the rectangle applies to Y as it is and, halved, to U and
-// to V, each scaled to 320 x 180 as a one-channel plane: the three planes of a batch's surfaces are one launch.  The result's planes lie
-// where `out` puts them whichever size comes out, so `out` must hold max(w, 640) x max(h, 360): its defaults are those of a surface of
-// that size.  An I420 result is the de-interleaved result of vs_azc_apply_nv12_dev on the same samples.
+// to V, each scaled to ow / 2 x oh / 2 as a one-channel plane: the three planes of a batch's surfaces are one launch (two when only some of
+// its jobs can be staged).  The result's planes lie where `out` puts them whichever size comes out, so `out` must hold max(w, ow) x
+// max(h, oh) - 640 x 360 unless vs_azc_set_output_size said otherwise -: its defaults are those of a surface of that size.  An I420 result is the de-interleaved result of vs_azc_apply_nv12_dev on the same samples.
 int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in, void* d_out, const vs_i420_layout* out,
                           int64_t* ticket) {
     if (!a || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
@@ -811,8 +816,10 @@ int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int 
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: the planar entry point takes VS_FMT_I420, VS_FMT_I010 or VS_FMT_I012");
     I420Layout sl, dl;
     std::string msg;
+    const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h;
+    const std::string what = "auto zoom/crop (result: max(w, " + std::to_string(ow) + ") x max(h, " + std::to_string(oh) + "))";
     if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "auto zoom/crop", &sl, &msg) != VS_OK ||
-        planar_layout_check(fmt, d_out, w, h, out, std::max(w, 640), std::max(h, 360), "auto zoom/crop (result: max(w, 640) x max(h, 360))", &dl, &msg) != VS_OK)
+        planar_layout_check(fmt, d_out, w, h, out, std::max(w, ow), std::max(h, oh), what.c_str(), &dl, &msg) != VS_OK)
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, msg.c_str());
     return azc_hand_over(a, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, ticket, f->sample_bytes, fmt, sl, dl);
 }
@@ -864,6 +871,70 @@ int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* in
     if (out_h) *out_h = r.out_h;
     if (info8) memcpy(info8, r.info, sizeof r.info);
     if (r.rc != VS_OK) return vs_obj_fail(a, r.rc, "auto zoom/crop: a worker's launch failed");
+    return VS_OK;
+}
+
+// The output size of the crop-and-scale (the reference's 640 x 360, :246-261, as a setting of the object): both even and in 2 .. 8192,
+// or 0, 0 = the size of the surface handed over.  It applies to what is handed over after the call: like a change of geometry it closes
+// the pending batch, and the tickets out already keep the size they were issued under (vs_azc::Frame carries it).
+int vs_azc_set_output_size(vs_azc* a, int out_w, int out_h) {
+    if (!a) return VS_ERR_INVALID_ARG;
+    const bool own = out_w == 0 && out_h == 0;
+    if (!own && (out_w < 2 || out_h < 2 || out_w > 8192 || out_h > 8192 || (out_w & 1) || (out_h & 1)))
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: the output size must be even and in 2 .. 8192 both ways, or 0 x 0 (the surface's own size)");
+    std::unique_lock<std::mutex> lk(a->mu);
+    int rc = VS_OK;
+    if (!a->pending.empty() && (a->ow != out_w || a->oh != out_h)) {
+        if (hipSetDevice(a->device) != hipSuccess) return vs_obj_fail(a, VS_ERR_HIP, "auto zoom/crop: cannot select the device");
+        rc = azc_flush_pending(a, lk);
+    }
+    a->ow = out_w; a->oh = out_h;
+    return rc;
+}
+
+int vs_azc_get_output_size(const vs_azc* a, int* out_w, int* out_h) {
+    if (!a || !out_w || !out_h) return VS_ERR_INVALID_ARG;
+    *out_w = a->ow; *out_h = a->oh;
+    return VS_OK;
+}
+
+// The stage's crop-and-scale as an operator: the call the batch's last worker makes (launch_scale_jobs), on the caller's jobs.
+static int scale_jobs_convert(const vs_scale_job* jobs, int n, int sample_bytes, WarpJob* out) {
+    if (!jobs || n < 1 || n > WARP_JOBS_MAX || (sample_bytes != 1 && sample_bytes != 2)) return VS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) {
+        const vs_scale_job& s = jobs[i];
+        if (!s.src || !s.dst || s.sw < 1 || s.sh < 1 || s.dw < 1 || s.dh < 1 || s.sw > 32767 || s.sh > 32767 || s.dw > 32767 || s.dh > 32767 ||
+            (s.cn != 1 && s.cn != 2) || s.reserved != 0 || s.src_stride > UINT32_MAX || s.dst_stride > UINT32_MAX ||
+            s.src_stride < (size_t)s.sw * s.cn * sample_bytes || s.dst_stride < (size_t)s.dw * s.cn * sample_bytes ||
+            (sample_bytes == 2 && (((uintptr_t)s.src | (uintptr_t)s.dst | s.src_stride | s.dst_stride) & 1)))
+            return VS_ERR_INVALID_ARG;
+        WarpJob& j = out[i];
+        j.src = (const uint8_t*)s.src; j.dst = (uint8_t*)s.dst;
+        j.sstride = (uint32_t)s.src_stride; j.dstride = (uint32_t)s.dst_stride;
+        j.sw = s.sw; j.sh = s.sh; j.dw = s.dw; j.dh = s.dh; j.cn = s.cn; j.border = VS_BORDER_BLACK; j.sb = sample_bytes;
+        const float M[6] = {(float)((double)s.dw / s.sw), 0.f, 0.f, 0.f, (float)((double)s.dh / s.sh), 0.f};      // :261-262
+        warp_invert(M, j.m);
+    }
+    return VS_OK;
+}
+
+int vs_op_scale_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int path, void* stream) {
+    WarpJob wj[WARP_JOBS_MAX];
+    if ((path != 0 && path != 1) || scale_jobs_convert(jobs, n, sample_bytes, wj) != VS_OK) {
+        set_last_error("scale_jobs: invalid argument (1 .. 24 jobs of one sample size, 1 or 2 bytes; cn 1 or 2; sizes 1 .. 32767; 16-bit pointers and strides even)");
+        return VS_ERR_INVALID_ARG;
+    }
+    VS_TRY(ensure_device());
+    return launch_scale_jobs(wj, n, path, (hipStream_t)stream);
+}
+
+int vs_op_scale_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int32_t* staged) {
+    WarpJob wj[WARP_JOBS_MAX];
+    if (!staged || scale_jobs_convert(jobs, n, sample_bytes, wj) != VS_OK) {
+        set_last_error("scale_jobs_plan: invalid argument");
+        return VS_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n; i++) staged[i] = scale_job_staged(wj[i]) ? 1 : 0;
     return VS_OK;
 }
 

@@ -25,6 +25,7 @@
 //   4. other tiles: a generic LDS path (variable pitch) or, when the box does not fit the
 //      LDS budget (large rotation / scale), direct global loads - the same arithmetic.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -677,6 +678,104 @@ __device__ __forceinline__ void warp_jobs_tile(const WarpJobsArg& a) {
 
 __global__ __launch_bounds__(NT) void warp_jobs_kernel(WarpJobsArg a) { warp_jobs_tile<1>(a); }
 __global__ __launch_bounds__(NT) void warp_jobs16_kernel(WarpJobsArg a) { warp_jobs_tile<2>(a); }
+
+// ---- the staged form of a scale job ------------------------------------------------------------------------------------------
+// A zoom stage that does not shrink (AutoZoomCrop at the surface's own size, k_azc.hip) turns the jobs above inside out: the source
+// box of an output tile is smaller than the tile, and every source sample is a tap of several output samples.  A scale map is
+// diagonal (m[1] = m[3] = 0): the source column sx(x) = (coord_term(m0, 0, x) + X0) >> 10 depends on the output column alone, the
+// source row on the output row alone, both monotone, so the box of a tile is [sx(x0), sx(x1) + 1] x [sy(y0), sy(y1) + 1] and
+//   sx(x1) - sx(x0) <= floor((a(x1) - a(x0)) / 1024) + 1,   a(x1) - a(x0) <= m0 (x1 - x0) 1024 + 1   (two roundings of 1/2; + 1 more
+// below for the rounding of the products), whatever X0 is: a bound from the inverse scale factor and the tile size alone
+// (scale_span).  Whether a job can be staged is therefore decided per job on the host (scale_job_staged): every tile of a staged
+// job fits the staging area, the kernel has no other path.
+// The box is staged as one dword per pixel, emit_rows' `tile` (load_px_checked's form of a pixel), a lane taking four pixels: ONE
+// aligned load of 4 (8-bit, cn 1), 8 (8-bit cn 2; 16-bit cn 1) or 16 bytes (16-bit cn 2) where the four lie inside the crop and the
+// job's rows keep that alignment; sample by sample, each checked, elsewhere.  The columns are counted from an origin bx0a <= sx(x0)
+// at which the loads are aligned; a group that reaches in front of the crop (or behind it, above, below) is of the second kind, so
+// NOTHING outside the crop rectangle is ever read - its neighbours in the plane are the border, 0, and are staged as 0.
+// Terms, taps, blend and stores are emit_rows' (USE_LDS).  8-bit and 16-bit samples are kernels of their own, as above.
+constexpr int SBW = 160;     // staged pixels of a row (a multiple of 4): an identity tile needs 130 + 3 (origin) + 3 (rounded up)
+constexpr int SBH = 24;      // staged rows: an identity tile needs 18.  160 x 24 dwords = 15 KiB: eight workgroups per CU
+
+template <int CN, int SB>
+__device__ __forceinline__ void scale_stage(const WarpJob& j, uint32_t* tile, int bx0a, int by0, int bw, int bh, int aligned, int tid) {
+    const int groups = bw >> 2, n = groups * bh;
+    for (int g = tid; g < n; g += NT) {
+        const int r = g / groups, gx = g - r * groups;
+        const int sx = bx0a + 4 * gx, sy = by0 + r;
+        uint4 px = make_uint4(0u, 0u, 0u, 0u);
+        if ((unsigned)sy < (unsigned)j.sh) {
+            if (aligned && sx >= 0 && sx + 3 < j.sw) {
+                const uint8_t* p = j.src + (size_t)sy * j.sstride + (size_t)sx * (CN * SB);
+                if (CN * SB == 1) {
+                    const uint32_t d = *reinterpret_cast<const uint32_t*>(p);
+                    px.x = d & 255u; px.y = (d >> 8) & 255u; px.z = (d >> 16) & 255u; px.w = d >> 24;
+                } else if (CN * SB == 2) {      // (two bytes per pixel: U, V of 8 bits or one 16-bit sample - the same halves of a dword)
+                    const uint2 d = *reinterpret_cast<const uint2*>(p);
+                    px.x = d.x & 0xFFFFu; px.y = d.x >> 16; px.z = d.y & 0xFFFFu; px.w = d.y >> 16;
+                } else {
+                    px = *reinterpret_cast<const uint4*>(p);
+                }
+            } else {
+                px.x = load_px_checked<CN, SB>(j.src, j.sstride, j.sw, j.sh, sx, sy);
+                px.y = load_px_checked<CN, SB>(j.src, j.sstride, j.sw, j.sh, sx + 1, sy);
+                px.z = load_px_checked<CN, SB>(j.src, j.sstride, j.sw, j.sh, sx + 2, sy);
+                px.w = load_px_checked<CN, SB>(j.src, j.sstride, j.sw, j.sh, sx + 3, sy);
+            }
+        }
+        *reinterpret_cast<uint4*>(tile + r * bw + 4 * gx) = px;
+    }
+}
+
+template <int SB>
+__device__ __forceinline__ void scale_jobs_tile(const WarpJobsArg& a) {
+    __shared__ int s_ad[TW], s_bd[TW], s_x0[TH], s_y0[TH];
+    __shared__ __attribute__((aligned(16))) uint32_t tile[SBW * SBH];
+    const WarpJob& j = a.j[blockIdx.z];
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    if (x0 >= j.dw || y0 >= j.dh) return;                 // (workgroup-uniform)
+    const int x1 = min(x0 + TW, j.dw) - 1, y1 = min(y0 + TH, j.dh) - 1;
+    if (tid < TW) {
+        const double dv = (double)min(x0 + tid, x1);
+        s_ad[tid] = coord_term(j.m[0], 0.0, dv);
+        s_bd[tid] = coord_term(j.m[3], 0.0, dv);
+    } else if (tid < TW + TH) {
+        const double dv = (double)min(y0 + (tid - TW), y1);
+        s_x0[tid - TW] = coord_term(j.m[1], j.m[2], dv) + 16;
+        s_y0[tid - TW] = coord_term(j.m[4], j.m[5], dv) + 16;
+    }
+    __syncthreads();
+    // the tile's box from its corner terms, by emit_rows' expressions (m[1] = m[3] = 0: s_x0 is one value, s_bd is 0)
+    const int bx0 = sat_s16(((s_x0[0] + s_ad[0]) >> 5) >> 5), bx1 = sat_s16(((s_x0[0] + s_ad[x1 - x0]) >> 5) >> 5);
+    const int by0 = sat_s16(((s_y0[0] + s_bd[0]) >> 5) >> 5), by1 = sat_s16(((s_y0[y1 - y0] + s_bd[0]) >> 5) >> 5);
+    // a lane's four pixels are one aligned load where the job's rows keep that alignment; k = the pixels between the aligned address
+    // at or in front of the crop's first sample and that sample: the columns x with (x + k) % 4 == 0 are aligned
+    const int pxb = j.cn * SB, lb = 4 * pxb;
+    const int aligned = (uintptr_t)j.src % pxb == 0 && j.sstride % lb == 0;
+    const int k = aligned ? (int)((uintptr_t)j.src % lb) / pxb : 0;
+    const int bx0a = ((bx0 + k) & ~3) - k;
+    const int bw = (bx1 + 2 - bx0a + 3) & ~3, bh = by1 + 2 - by0;
+    WarpCore c;
+    c.sstride = j.sstride; c.dstride = j.dstride;
+    c.sw = j.sw; c.sh = j.sh; c.dw = j.dw; c.dh = j.dh;
+    c.src_aligned = aligned;
+    const int galign = SB == 2 ? 8 * j.cn : j.cn == 2 ? 8 : 4;        // (a lane's four pixels in one store)
+    c.dst_aligned = ((uintptr_t)j.dst % galign == 0) && (j.dstride % galign == 0);
+    c.border = j.border;
+    if (j.cn == 1) {
+        scale_stage<1, SB>(j, tile, bx0a, by0, bw, bh, aligned, tid);
+        __syncthreads();
+        emit_rows<1, true, SB>(c, j.src, j.dst, tile, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, bx0a, by0, bw, tid);
+    } else {
+        scale_stage<2, SB>(j, tile, bx0a, by0, bw, bh, aligned, tid);
+        __syncthreads();
+        emit_rows<2, true, SB>(c, j.src, j.dst, tile, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, bx0a, by0, bw, tid);
+    }
+}
+
+__global__ __launch_bounds__(NT) void scale_jobs_kernel(WarpJobsArg a) { scale_jobs_tile<1>(a); }
+__global__ __launch_bounds__(NT) void scale_jobs16_kernel(WarpJobsArg a) { scale_jobs_tile<2>(a); }
 
 // ---- tile building blocks shared by the table kernels ------------------------------------------------------------
 constexpr int TABN = 2 * TW + 2 * TH;     // ints of coordinate terms per tile: ad[128] bd[128] x0[16] y0[16]
@@ -1893,6 +1992,49 @@ int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st) {
     else hipLaunchKernelGGL(warp_jobs_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
+}
+
+// Samples of a source row or column that a full tile of n output samples touches at most, taps included, under the inverse scale
+// factor inv (the bound in front of scale_jobs_tile).
+static int scale_span(double inv, int n) { return (int)std::floor((inv * (n - 1) * 1024 + 2) / 1024) + 3; }
+
+// Whether launch_scale_jobs sends a job to the staged kernel: a diagonal map that does not mirror, border 0, cn 1 or 2, and the box of
+// a full tile - widened by the 3 + 3 samples of the aligned origin and the rounded-up pitch - inside the staging area.  That is an
+// inverse factor below (SBW - 9) / (TW - 1) = 1.19 across and (SBH - 3) / (TH - 1) = 1.4 down: every zoom-in, and mild downscales.
+bool scale_job_staged(const WarpJob& j) {
+    if (j.border != VS_BORDER_BLACK || j.cn < 1 || j.cn > 2 || j.m[1] != 0 || j.m[3] != 0 || !(j.m[0] > 0) || !(j.m[4] > 0)) return false;
+    if (j.m[0] > 2 || j.m[4] > 2 || j.sw > 32767 || j.sh > 32767) return false;      // (far outside; sat_s16 never acts on a staged job)
+    return scale_span(j.m[0], TW) + 6 <= SBW && scale_span(j.m[4], TH) <= SBH;
+}
+
+// The crop-and-scale jobs of a batch: those that can be staged as ONE launch of the staged kernel, the others as ONE launch of
+// launch_warp_jobs - a batch of one class is one launch.  path 1: all of them through launch_warp_jobs.
+int launch_scale_jobs(const WarpJob* jobs, int n, int path, hipStream_t st) {
+    if (!jobs || n < 1 || n > WARP_JOBS_MAX || (path != 0 && path != 1)) { set_last_error("scale_jobs: invalid argument"); return VS_ERR_INVALID_ARG; }
+    WarpJob direct[WARP_JOBS_MAX];
+    WarpJobsArg a;
+    int ns = 0, nd = 0, gw = 1, gh = 1;
+    for (int i = 0; i < n; i++) {
+        const WarpJob& j = jobs[i];
+        if ((j.sb != 1 && j.sb != 2) || j.sb != jobs[0].sb || j.cn < 1 || j.cn > (j.sb == 2 ? 2 : 3) ||
+            bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn * j.sb, 1) ||
+            (j.border != VS_BORDER_BLACK && j.border != VS_BORDER_REPLICATE) ||
+            (j.sb == 2 && (((uintptr_t)j.src | (uintptr_t)j.dst | j.sstride | j.dstride) & 1))) {
+            set_last_error("scale_jobs: invalid argument");
+            return VS_ERR_INVALID_ARG;
+        }
+        if (path == 1 || !scale_job_staged(j)) { direct[nd++] = j; continue; }
+        a.j[ns++] = j;
+        gw = std::max(gw, (j.dw + TW - 1) / TW);
+        gh = std::max(gh, (j.dh + TH - 1) / TH);
+    }
+    if (ns) {
+        for (int i = ns; i < WARP_JOBS_MAX; i++) a.j[i] = a.j[0];
+        if (jobs[0].sb == 2) hipLaunchKernelGGL(scale_jobs16_kernel, dim3(gw, gh, ns), dim3(NT), 0, st, a);
+        else hipLaunchKernelGGL(scale_jobs_kernel, dim3(gw, gh, ns), dim3(NT), 0, st, a);
+        VS_HIP_TRY(hipGetLastError());
+    }
+    return nd ? launch_warp_jobs(direct, nd, st) : VS_OK;
 }
 
 }  // namespace vsd

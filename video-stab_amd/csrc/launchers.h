@@ -72,7 +72,7 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
 // ---- k_roll.hip, k_azc.hip: planar 4:2:0 surfaces (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012) of the stages around the stabilizer
 // The geometry and layout rules of a planar surface handed to the roll / zoom stages (those vs_stab enforces).  need_w / need_h: the
 // samples per row and the rows the layout must hold - the picture's, or for the zoom stage's result the larger of the picture's and
-// 640 x 360.  Fills *l with the defaults resolved, or *msg with a text that names the stage and the format.
+// the stage's output size (640 x 360 unless vs_azc_set_output_size said otherwise).  Fills *l with the defaults resolved, or *msg with a text that names the stage and the format.
 inline int planar_layout_check(int fmt, const void* ptr, int w, int h, const vs_i420_layout* in, int need_w, int need_h, const char* stage,
                                I420Layout* l, std::string* msg) {
     const int sb = pixfmt(fmt)->sample_bytes;

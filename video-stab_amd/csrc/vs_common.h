@@ -182,6 +182,11 @@ struct WarpJob {
 // a launch may carry)
 constexpr int WARP_JOBS_MAX = 24;
 int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st);
+// Crop-and-scale jobs (diagonal maps, as AutoZoomCrop builds them): those whose tiles' source boxes fit the staging area go to the
+// staged kernel as one launch, the others to launch_warp_jobs as one launch.  path 0: as scale_job_staged says per job; 1: all
+// through launch_warp_jobs.  scale_job_staged is host arithmetic on the job's inverse map alone.
+bool scale_job_staged(const WarpJob& j);
+int launch_scale_jobs(const WarpJob* jobs, int n, int path, hipStream_t st);
 int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int fmt,
                        uint8_t* d_dst, size_t dstride, int dw, int dh, hipStream_t st);
 // Batched forms (batch mode): the images of `items` frames in one launch; d_pairs = device table of

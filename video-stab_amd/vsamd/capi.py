@@ -166,6 +166,13 @@ class VsEnhParams(C.Structure):
     ]
 
 
+class VsScaleJob(C.Structure):
+    """struct vs_scale_job (include/vs_stab.h): one crop-and-scale of vs_op_scale_jobs."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_size_t), ("sw", C.c_int32), ("sh", C.c_int32),
+                ("dst", C.c_void_p), ("dst_stride", C.c_size_t), ("dw", C.c_int32), ("dh", C.c_int32),
+                ("cn", C.c_int32), ("reserved", C.c_int32)]
+
+
 class VsError(RuntimeError):
     pass
 
@@ -417,6 +424,10 @@ class VsLib:
         L.vs_roll_correct_i420_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, lp, lp]
         L.vs_azc_apply_i420_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, lp, vp, lp, C.POINTER(C.c_int64)]
         L.vs_azc_apply_i420_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, lp, lp, C.POINTER(C.c_int64)]
+        L.vs_azc_set_output_size.argtypes = [vp, C.c_int, C.c_int]
+        L.vs_azc_get_output_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.vs_op_scale_jobs.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, C.c_int, vp]
+        L.vs_op_scale_jobs_plan.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, i32p]
 
     # ---- helpers ----------------------------------------------------------
     def check(self, status, inst=None):
@@ -696,6 +707,23 @@ class VsLib:
         self.sync()
         return d_out.download((dh, dw) if img.ndim == 2 else (dh, dw, cn), np.uint16)
 
+    @staticmethod
+    def _scale_job_array(jobs):
+        arr = (VsScaleJob * max(1, len(jobs)))()
+        for i, (src, src_stride, sw, sh, dst, dst_stride, dw, dh, cn) in enumerate(jobs):
+            arr[i] = VsScaleJob(src, src_stride, sw, sh, dst, dst_stride, dw, dh, cn, 0)
+        return arr
+
+    def scale_jobs(self, jobs, sample_bytes=1, path=0, stream=None):
+        """vs_op_scale_jobs: jobs = tuples (src, src_stride, sw, sh, dst, dst_stride, dw, dh, cn) of device addresses; asynchronous."""
+        self.check(self.lib.vs_op_scale_jobs(self._scale_job_array(jobs), len(jobs), sample_bytes, path, stream))
+
+    def scale_jobs_plan(self, jobs, sample_bytes=1):
+        """vs_op_scale_jobs_plan (no device needed): 1 per job that path 0 sends to the staged kernel."""
+        staged = np.zeros(max(1, len(jobs)), np.int32)
+        self.check(self.lib.vs_op_scale_jobs_plan(self._scale_job_array(jobs), len(jobs), sample_bytes, _p(staged, i32p)))
+        return staged[:len(jobs)].copy()
+
     def content_mask(self, img):
         img = np.ascontiguousarray(img)
         h, w = img.shape[:2]
@@ -782,11 +810,22 @@ class AutoZoomCrop:
             raise VsError("%s: %s" % (self.lib.vs_status_string(status).decode(),
                                       (self.lib.vs_azc_last_error(self.h) or b"").decode()))
 
+    def set_output_size(self, out_w, out_h):
+        """vs_azc_set_output_size: the size of every later result; (640, 360) on a new object, (0, 0) = the surface's own size."""
+        self._check(self.lib.vs_azc_set_output_size(self.h, out_w, out_h))
+
+    @property
+    def output_size(self):
+        ow, oh = C.c_int(), C.c_int()
+        self._check(self.lib.vs_azc_get_output_size(self.h, C.byref(ow), C.byref(oh)))
+        return ow.value, oh.value
+
     def apply(self, frame):
         frame = np.ascontiguousarray(frame)
         h, w = frame.shape[:2]
         cn = 1 if frame.ndim == 2 else 3
-        buf = np.empty(max(w * h, 640 * 360) * cn, np.uint8)
+        sw, sh = self.output_size
+        buf = np.empty(max(w * h, (sw or w) * (sh or h)) * cn, np.uint8)
         ow, oh = C.c_int(), C.c_int()
         self._check(self.lib.vs_azc_apply(self.h, _p(frame, u8p), w, h, w * cn, cn, _p(buf, u8p),
                                           C.byref(ow), C.byref(oh)))
