@@ -40,7 +40,8 @@ extern "C" {
  *    vs_roll_correct_i420_dev, vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev and vs_azc_apply_i420_dev_n; planar 4:2:2 and
  *    4:4:4 - VS_FMT_I422, VS_FMT_I444, VS_FMT_I210, VS_FMT_I212, VS_FMT_I410, VS_FMT_I412 (enum vs_pixfmt_planar4xx) - with
  *    vs_op_warp_affine_planar; the output size of auto zoom/crop: vs_azc_set_output_size, vs_azc_get_output_size, struct
- *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan (new entry points, new values and new structs only: no existing
+ *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan; the compositing operators vs_op_copy_make_border, vs_op_fade_blend,
+ *    vs_op_fade_update and vs_op_canvas_create / apply / info / destroy (new entry points, new values and new structs only: no existing
  *    struct or entry point changed, so the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
@@ -854,6 +855,35 @@ int vs_azc_crop_from_mask(const uint8_t* mask, int w, int h, size_t stride, int3
  * max_boxes rectangles, *n_boxes the number found.  Needs no device. */
 int vs_op_external_boxes(const uint8_t* mask, int w, int h, size_t stride, int32_t* xywh, int max_boxes,
                          int32_t* n_boxes);
+
+/* ---- the compositing stages as operators (the calls the stream itself makes; tests/compref.py states what they compute) ---- */
+/* cv::copyMakeBorder (Stabilizer.cpp:981-990): w x h pixels of cn channels (1, 3 or 4) to (w + 2b) x (h + 2b), b >= 0 (b = 0
+ * copies), border = VS_BORDER_BLACK .. VS_BORDER_WRAP (VS_BORDER_FADE is no copyMakeBorder mode: VS_ERR_INVALID_ARG).  Pitches in
+ * bytes, at least a row each.  Asynchronous on `stream`. */
+int vs_op_copy_make_border(const void* d_src, size_t src_stride, int w, int h, int cn, void* d_dst, size_t dst_stride, int b,
+                           int border, void* stream);
+/* The fade blend (Stabilizer.cpp:914-978): frame = cv::addWeighted(history, alpha, frame, beta, 0) on 8-bit samples, in place,
+ * = fma(a, alpha, fl(b * beta)) in float, rounded half to even, saturated.  alpha, beta in [0, 1].  The kernel works on words of
+ * four samples: both buffers are 4-byte aligned and hold `bytes` rounded up to a multiple of 4, and the samples of that last
+ * word are blended like the rest.  Asynchronous on `stream`. */
+int vs_op_fade_blend(const void* d_hist, void* d_frame, size_t bytes, float alpha, float beta, void* stream);
+/* The fade history's update (Stabilizer.cpp:1086-1100): history = (uchar)((1 - 0.1f) * history + 0.1f * stabilized), in float,
+ * truncated.  The history is packed (rows of row_bytes), `d_stab` has pitch stab_stride >= row_bytes; the kernel works on single
+ * samples, so no size is rounded and nothing outside a row's row_bytes is written.  Asynchronous on `stream`. */
+int vs_op_fade_update(void* d_hist, const void* d_stab, size_t stab_stride, int row_bytes, int rows, void* stream);
+/* The virtual canvas of a BGR8 stream (Stabilizer.cpp:2066-2443) with a given correction in place of the trajectory kernel's.
+ * The object holds what the stream's canvas holds (temporal buffer, scale, canvas size) and a stream of its own.  apply: d_frame
+ * w x h at `pitch`, t = the correction (dx, dy, da) and transforms = the n >= 0 past transforms (n x 3, read when the adaptive
+ * scale is chosen), both HOST floats; the call builds the device trajectory ring the scale kernel reads (n may exceed the ring),
+ * writes the w x h result to d_out and is synchronous.  info8 (optional) as vs_stab_canvas_info.  The canvas rules of
+ * vs_stab_create hold for `params`; a frame for which a scale the call can choose (the factor, or min / max when adaptive) gives
+ * a canvas outside 1..65535 x 1..32767 is VS_ERR_UNSUPPORTED.  Every refusal happens before anything is launched. */
+typedef struct vs_canvas_op vs_canvas_op;
+int vs_op_canvas_create(vs_canvas_op** out);
+int vs_op_canvas_apply(vs_canvas_op* c, const vs_params_c* params, const void* d_frame, size_t pitch, int w, int h, const float* t,
+                       const float* transforms, int n, void* d_out, size_t out_pitch, int32_t* info8);
+int vs_op_canvas_info(const vs_canvas_op* c, int32_t info[8]);
+void vs_op_canvas_destroy(vs_canvas_op* c);
 
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */

@@ -100,6 +100,14 @@ void vso_stab_out_size(const vso_stab* s, int w, int h, int* ow, int* oh);
 void vso_stab_get_debug(const vso_stab* s, vs_debug_frame* d);
 /* {canvas w, h, scale (float bits), regions, regions filled, temporal index of the last fill, window x, y} */
 void vso_stab_canvas_info(const vso_stab* s, int32_t info[8]);
+/* The virtual canvas by itself (Stabilizer.cpp:2066-2443; vso_canvas.cpp): the object vso_stab_push drives, with the correction
+ * t = (dx, dy, da) and the n past transforms (n x 3, read when the adaptive scale is chosen) given by the caller */
+typedef struct vso_canvas vso_canvas;
+vso_canvas* vso_canvas_new(void);
+void vso_canvas_delete(vso_canvas* c);
+void vso_canvas_apply(vso_canvas* c, const vs_params_c* p, const uint8_t* frame, int w, int h, size_t stride, const float* t,
+                      const float* transforms, int n, uint8_t* out, size_t out_stride);
+void vso_canvas_info(const vso_canvas* c, int32_t info[8]);
 int  vso_stab_get_debug_arrays(const vso_stab* s, float* prev_pts, float* curr_pts,
                                uint8_t* status, uint8_t* inliers, float* detected_pts,
                                uint8_t* gray, int* aw, int* ah);

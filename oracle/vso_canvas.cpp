@@ -228,3 +228,16 @@ void canvas_apply(CanvasState* cs, const vs_params_c& p, const uint8_t* frame, i
 }
 
 }  // namespace vso
+
+using namespace vso;
+
+extern "C" {
+vso_canvas* vso_canvas_new(void) { return reinterpret_cast<vso_canvas*>(canvas_new()); }
+void vso_canvas_delete(vso_canvas* c) { if (c) canvas_delete(reinterpret_cast<CanvasState*>(c)); }
+void vso_canvas_info(const vso_canvas* c, int32_t info[8]) { canvas_info(reinterpret_cast<const CanvasState*>(c), info); }
+void vso_canvas_apply(vso_canvas* c, const vs_params_c* p, const uint8_t* frame, int w, int h, size_t stride, const float* t,
+                      const float* transforms, int n, uint8_t* out, size_t out_stride) {
+    const std::vector<float> tr(transforms, transforms + 3 * (size_t)(n > 0 ? n : 0));
+    canvas_apply(reinterpret_cast<CanvasState*>(c), *p, frame, w, h, stride, t, tr, out, out_stride);
+}
+}

@@ -457,6 +457,9 @@ class Oracle:
     def stabilizer(self, params):
         return OracleStab(self, params)
 
+    def canvas(self):
+        return OracleCanvas(self)
+
 
 class OracleRoll:
     """vs::RollCorrection::autoCorrectRoll restated on the CPU (oracle/vso_roll.cpp)."""
@@ -493,6 +496,43 @@ class OracleRoll:
         n, u = C.c_int32(), C.c_int32()
         self.lib.vso_roll_get(self.h, C.byref(s), C.byref(d), C.byref(n), C.byref(u))
         return s.value, d.value, n.value, u.value
+
+
+class OracleCanvas:
+    """The virtual canvas of vs::Stabilizer by itself (oracle/vso_canvas.cpp), with the correction and the past transforms given."""
+
+    def __init__(self, o):
+        self.lib = o.lib
+        self.lib.vso_canvas_new.restype = C.c_void_p
+        self.lib.vso_canvas_delete.argtypes = [C.c_void_p]
+        self.lib.vso_canvas_delete.restype = None
+        self.lib.vso_canvas_info.argtypes = [C.c_void_p, i32p]
+        self.lib.vso_canvas_info.restype = None
+        self.lib.vso_canvas_apply.argtypes = [C.c_void_p, C.POINTER(o.VsParams), u8p, C.c_int, C.c_int, C.c_size_t, f32p, f32p, C.c_int, u8p,
+                                              C.c_size_t]
+        self.lib.vso_canvas_apply.restype = None
+        self.h = self.lib.vso_canvas_new()
+
+    def close(self):
+        if self.h:
+            self.lib.vso_canvas_delete(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def apply(self, params, frame, t, transforms=None):
+        """-> (output (h, w, 3), info8)"""
+        frame = np.ascontiguousarray(frame, np.uint8)
+        h, w = frame.shape[:2]
+        t = np.ascontiguousarray(t, np.float32).reshape(3)
+        tr = np.ascontiguousarray(transforms if transforms is not None else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+        out = np.empty_like(frame)
+        self.lib.vso_canvas_apply(self.h, C.byref(params), _p(frame, u8p), w, h, w * 3, _p(t, f32p), _p(tr, f32p) if len(tr) else None, len(tr),
+                                  _p(out, u8p), w * 3)
+        info = np.zeros(8, np.int32)
+        self.lib.vso_canvas_info(self.h, _p(info, i32p))
+        return out, info
 
 
 class OracleStab:

@@ -1,8 +1,9 @@
 """The reference of roll correction and auto zoom/crop on P010 surfaces, in numpy integers, on top of tests/ref16.py.
 
 warp(): cv::warpAffine on a plane of 16-bit (or 8-bit) samples with a DOUBLE forward matrix, a destination size of its own and a
-constant or replicate border.  Coordinates are ref16.coords (the 8-bit path: AB_BITS 10, 1/32 px); a tap outside the source is 0
-(constant) or the nearest edge sample (replicate), each tap by itself; the blend is ref16's S with its HALF_EVEN / HALF_UP switch.
+constant, replicate or reflect border.  Coordinates are ref16.coords (the 8-bit path: AB_BITS 10, 1/32 px); a tap outside the source is 0
+(constant), the nearest edge sample (replicate) or the sample of the even extension (reflect: reflect_index, each axis by
+itself - the virtual canvas's compensation warp, tests/compref.py), each tap by itself; the blend is ref16's S with its HALF_EVEN / HALF_UP switch.
 
 On top of it the two stages as include/vs_stab.h defines them for P010 (vs_pixfmt16):
     rotate_surface      the roll stage's rotation for a given smoothed angle (the matrix of oracle/vso_roll.cpp: centre, angle;
@@ -21,7 +22,13 @@ import numpy as np
 import ref16
 from ref16 import HALF_EVEN, HALF_UP
 
-CONSTANT, REPLICATE = 0, 3          # VS_BORDER_BLACK, VS_BORDER_REPLICATE
+CONSTANT, REFLECT, REPLICATE = 0, 1, 3          # VS_BORDER_BLACK, VS_BORDER_REFLECT, VS_BORDER_REPLICATE
+
+
+def reflect_index(p, n):
+    """cv::borderInterpolate(BORDER_REFLECT) by its definition: the even extension  ... c b a | a b c | c b a ...  has period 2n."""
+    q = np.mod(np.asarray(p, np.int64), 2 * n)
+    return np.where(q >= n, 2 * n - 1 - q, q)
 
 
 def warp_sum(img, M, dsize=None, border=CONSTANT):
@@ -33,6 +40,8 @@ def warp_sum(img, M, dsize=None, border=CONSTANT):
     sx, sy, fx, fy = ref16.coords(np.asarray(M, np.float64), dw, dh)
 
     def tap(xx, yy):
+        if border == REFLECT:
+            return src[reflect_index(yy, sh), reflect_index(xx, sw)]
         v = src[np.clip(yy, 0, sh - 1), np.clip(xx, 0, sw - 1)]
         if border == REPLICATE:
             return v

@@ -466,6 +466,15 @@ def test_gpu_enhance_configs(oracle, enh, name, w, h):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name,w,h", [(n, w, h) for n in ("denoise_only", "denoise_strong", "denoise_after_unsharp") for w, h in ((9, 7), (13, 40), (1, 1))] +
+                         [("unsharp_wide", 3, 50)])
+def test_gpu_enhance_configs_small_pictures(oracle, enh, name, w, h):
+    """Pictures smaller than the reach of a stage: the 13 pixels of fastNlMeansDenoising (search 10 + template 3; the oracle is held
+    to nlm_numpy at 9 x 7 above), where the reflect-101 border folds more than once, and the 15-tap blur of sigma 2.5 on 3 columns."""
+    test_gpu_enhance_configs(oracle, enh, name, w, h)
+
+
+@pytest.mark.gpu
 def test_gpu_enhance_pass_counts(oracle, enh):
     """The stage list is compiled into the fewest passes over the frame the dependencies allow."""
     img = scene(128, 96)

@@ -87,6 +87,29 @@ def test_no_gpu_means_loud_failure_not_fallback(vs):
         vs.warp_affine(np.zeros((8, 8, 3), np.uint8), [1, 0, 0, 0, 1, 0])
 
 
+def test_compositing_operators_refuse_on_the_host(vs):
+    """vs_op_copy_make_border, vs_op_fade_blend, vs_op_fade_update and vs_op_canvas_*: a bad argument is answered before a device is
+    looked for, so the pointers below are never read; with good arguments and no device the answer is VS_ERR_NO_DEVICE."""
+    L, p, q = vs.lib, 0x10000, 0x20000
+    assert L.vs_op_copy_make_border(None, 24, 8, 4, 3, q, 36, 2, capi.BORDER_REFLECT, None) == 1
+    assert L.vs_op_copy_make_border(p, 24, 8, 4, 2, q, 36, 2, capi.BORDER_REFLECT, None) == 1
+    assert L.vs_op_copy_make_border(p, 24, 8, 4, 3, q, 36, -1, capi.BORDER_REFLECT, None) == 1
+    assert L.vs_op_copy_make_border(p, 24, 8, 4, 3, q, 36, 2, capi.BORDER_FADE, None) == 1
+    assert L.vs_op_copy_make_border(p, 24, 8, 4, 3, q, 35, 2, capi.BORDER_WRAP, None) == 1
+    assert L.vs_op_fade_blend(p, None, 16, 0.5, 0.5, None) == 1 and L.vs_op_fade_blend(p, q + 2, 16, 0.5, 0.5, None) == 1
+    assert L.vs_op_fade_blend(p, q, 0, 0.5, 0.5, None) == 1 and L.vs_op_fade_blend(p, q, 16, -0.1, 0.5, None) == 1
+    assert L.vs_op_fade_update(p, None, 16, 16, 1, None) == 1 and L.vs_op_fade_update(p, q, 15, 16, 1, None) == 1
+    assert L.vs_op_canvas_create(None) == 1 and L.vs_op_canvas_info(None, None) == 1
+    t = (C.c_float * 3)()
+    par = vs.params(enable_virtual_canvas=1)
+    assert L.vs_op_canvas_apply(None, C.byref(par), p, 24, 8, 4, t, None, 0, q, 24, None) == 1
+    if vs.lib.vs_device_count() <= 0:
+        assert L.vs_op_copy_make_border(p, 24, 8, 4, 3, q, 36, 2, capi.BORDER_REFLECT, None) == 2
+        assert L.vs_op_fade_blend(p, q, 16, 0.5, 0.5, None) == 2 and L.vs_op_fade_update(p, q, 16, 16, 1, None) == 2
+        h = C.c_void_p()
+        assert L.vs_op_canvas_create(C.byref(h)) == 2 and not h.value
+
+
 def test_product_does_not_link_or_load_the_oracle(vs):
     """The oracle is test infrastructure: the shipped library must not depend on it."""
     import subprocess

@@ -1,0 +1,123 @@
+// The compositing stages as operators (include/vs_stab.h): vs_op_copy_make_border, vs_op_fade_blend, vs_op_fade_update and the
+// vs_op_canvas_* object.  Nothing is computed here: each entry checks its arguments and calls what the pipeline calls
+// (launch_make_border, launch_fade_blend, launch_fade_update of k_traj.hip; canvas_apply of k_canvas.hip).
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "stab_internal.h"
+
+using namespace vsd;
+
+namespace {
+
+int refuse(int code, const char* why) {
+    set_last_error(why);
+    return code;
+}
+
+}  // namespace
+
+struct vs_canvas_op {
+    Canvas* canvas = nullptr;
+    hipStream_t st = nullptr;
+    TrajState* d_traj = nullptr;
+    float* d_t = nullptr;
+    TrajState h_traj;
+};
+
+extern "C" {
+
+int vs_op_copy_make_border(const void* d_src, size_t src_stride, int w, int h, int cn, void* d_dst, size_t dst_stride, int b, int border,
+                           void* stream) {
+    if (!d_src || !d_dst) return refuse(VS_ERR_INVALID_ARG, "vs_op_copy_make_border: null pointer");
+    if (cn != 1 && cn != 3 && cn != 4) return refuse(VS_ERR_INVALID_ARG, "vs_op_copy_make_border: cn must be 1, 3 or 4");
+    if (w < 1 || h < 1 || w > 32767 || h > 32767 || b < 0 || b > 8192) return refuse(VS_ERR_INVALID_ARG, "vs_op_copy_make_border: size out of range");
+    if (border < VS_BORDER_BLACK || border > VS_BORDER_WRAP) return refuse(VS_ERR_INVALID_ARG, "vs_op_copy_make_border: not a copyMakeBorder mode");
+    if (src_stride < (size_t)w * cn || dst_stride < (size_t)(w + 2 * b) * cn) return refuse(VS_ERR_INVALID_ARG, "vs_op_copy_make_border: pitch below a row");
+    VS_TRY(ensure_device());
+    return launch_make_border((const uint8_t*)d_src, src_stride, w, h, cn, (uint8_t*)d_dst, dst_stride, b, border, (hipStream_t)stream);
+}
+
+int vs_op_fade_blend(const void* d_hist, void* d_frame, size_t bytes, float alpha, float beta, void* stream) {
+    if (!d_hist || !d_frame) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_blend: null pointer");
+    if (bytes < 1 || bytes > ((size_t)1 << 31)) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_blend: size out of range");
+    if (((uintptr_t)d_hist | (uintptr_t)d_frame) & 3) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_blend: buffers must be 4-byte aligned");
+    if (!(alpha >= 0.0f && alpha <= 1.0f && beta >= 0.0f && beta <= 1.0f)) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_blend: weights must be in [0,1]");
+    VS_TRY(ensure_device());
+    return launch_fade_blend((const uint8_t*)d_hist, (uint8_t*)d_frame, (bytes + 3) & ~(size_t)3, alpha, beta, (hipStream_t)stream);
+}
+
+int vs_op_fade_update(void* d_hist, const void* d_stab, size_t stab_stride, int row_bytes, int rows, void* stream) {
+    if (!d_hist || !d_stab) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_update: null pointer");
+    if (row_bytes < 1 || rows < 1 || rows > 65535) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_update: size out of range");
+    if (stab_stride < (size_t)row_bytes) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_update: pitch below a row");
+    VS_TRY(ensure_device());
+    return launch_fade_update((uint8_t*)d_hist, (const uint8_t*)d_stab, stab_stride, row_bytes, rows, (hipStream_t)stream);
+}
+
+int vs_op_canvas_create(vs_canvas_op** out) {
+    if (!out) return refuse(VS_ERR_INVALID_ARG, "vs_op_canvas_create: null pointer");
+    *out = nullptr;
+    VS_TRY(ensure_device());
+    vs_canvas_op* c = new (std::nothrow) vs_canvas_op();
+    if (!c) return refuse(VS_ERR_HIP, "out of host memory");
+    c->canvas = canvas_new();
+    hipError_t e = c->canvas ? hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) : hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_traj, sizeof(TrajState));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_t, 4 * sizeof(float));
+    if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); vs_op_canvas_destroy(c); return VS_ERR_HIP; }
+    *out = c;
+    return VS_OK;
+}
+
+void vs_op_canvas_destroy(vs_canvas_op* c) {
+    if (!c) return;
+    if (c->st) (void)hipStreamSynchronize(c->st);
+    canvas_delete(c->canvas);
+    if (c->d_traj) (void)hipFree(c->d_traj);
+    if (c->d_t) (void)hipFree(c->d_t);
+    if (c->st) (void)hipStreamDestroy(c->st);
+    delete c;
+}
+
+int vs_op_canvas_info(const vs_canvas_op* c, int32_t info[8]) {
+    if (!c || !info) return refuse(VS_ERR_INVALID_ARG, "vs_op_canvas_info: null pointer");
+    canvas_info(c->canvas, info);
+    return VS_OK;
+}
+
+int vs_op_canvas_apply(vs_canvas_op* c, const vs_params_c* params, const void* d_frame, size_t pitch, int w, int h, const float* t,
+                       const float* transforms, int n, void* d_out, size_t out_pitch, int32_t* info8) {
+    if (!c || !params || !d_frame || !t || !d_out || (n > 0 && !transforms)) return refuse(VS_ERR_INVALID_ARG, "vs_op_canvas_apply: null pointer");
+    if (params->struct_size != (int32_t)sizeof(vs_params_c)) return refuse(VS_ERR_INVALID_ARG, "params: struct_size mismatch");
+    if (w < 1 || h < 1 || w > 32767 || h > 32767 || n < 0) return refuse(VS_ERR_INVALID_ARG, "vs_op_canvas_apply: size out of range");
+    if (pitch < (size_t)w * 3 || out_pitch < (size_t)w * 3) return refuse(VS_ERR_INVALID_ARG, "vs_op_canvas_apply: pitch below a row");
+    const vs_params_c& p = *params;
+    // the canvas rules of vs_stab_create (check_params)
+    if (p.temporal_buffer_size < 0 || p.temporal_buffer_size > 256) return refuse(VS_ERR_INVALID_ARG, "temporalBufferSize must be in [0,256]");
+    if (!(p.canvas_blend_weight >= 0.0f && p.canvas_blend_weight <= 1.0f)) return refuse(VS_ERR_UNSUPPORTED, "canvasBlendWeight must be in [0,1]");
+    if (!(p.canvas_scale_factor > 0.0f && p.canvas_scale_factor <= 16.0f) || !(p.min_canvas_scale > 0.0f) || !(p.max_canvas_scale <= 16.0f))
+        return refuse(VS_ERR_INVALID_ARG, "canvas scale factors must be in (0,16]");
+    // every scale the call can choose: the factor as given, or (adaptive, :2281-2314) a value clamped to [min, max]
+    const float scales[3] = {p.canvas_scale_factor, p.adaptive_canvas_size ? p.min_canvas_scale : p.canvas_scale_factor,
+                             p.adaptive_canvas_size ? p.max_canvas_scale : p.canvas_scale_factor};
+    for (float s : scales) {
+        const float fw = w * s, fh = h * s;
+        if (!(fw >= 1.0f && fw <= 65535.0f && fh >= 1.0f && fh <= 32767.0f))
+            return refuse(VS_ERR_UNSUPPORTED, "virtual canvas: canvas size out of range (1..65535 x 1..32767)");
+    }
+    // the trajectory state as canvas_motion_kernel reads it: n, and the last TRAJ_RING transforms in their ring slots
+    memset(&c->h_traj, 0, sizeof c->h_traj);
+    c->h_traj.n = n;
+    for (int i = n > TRAJ_RING ? n - TRAJ_RING : 0; i < n; i++) memcpy(c->h_traj.transforms[i & (TRAJ_RING - 1)], transforms + 3 * (size_t)i, 3 * sizeof(float));
+    VS_HIP_TRY(hipMemcpyAsync(c->d_traj, &c->h_traj, sizeof(TrajState), hipMemcpyHostToDevice, c->st));
+    VS_HIP_TRY(hipMemcpyAsync(c->d_t, t, 3 * sizeof(float), hipMemcpyHostToDevice, c->st));
+    VS_HIP_TRY(hipStreamSynchronize(c->st));         // (the host copies above were read from pageable memory)
+    const int rc = canvas_apply(c->canvas, p, (const uint8_t*)d_frame, pitch, w, h, c->d_t, c->d_traj, (uint8_t*)d_out, out_pitch, c->st);
+    VS_HIP_TRY(hipStreamSynchronize(c->st));
+    if (rc == VS_OK && info8) canvas_info(c->canvas, info8);
+    return rc;
+}
+
+}  // extern "C"

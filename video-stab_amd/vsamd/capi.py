@@ -224,6 +224,43 @@ class DevBuf:
             pass
 
 
+class CanvasOp:
+    """vs_op_canvas_*: the stream's virtual canvas driven with a given correction."""
+
+    def __init__(self, vs):
+        self.vs = vs
+        h = C.c_void_p()
+        vs.check(vs.lib.vs_op_canvas_create(C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.vs.lib.vs_op_canvas_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, params, frame, t, transforms=None, pitch=None):
+        """frame (h, w, 3) uint8 -> (output (h, w, 3), info8).  pitch: a row pitch of its own for the device frame."""
+        frame = np.ascontiguousarray(frame, np.uint8)
+        h, w = frame.shape[:2]
+        pitch = pitch or w * 3
+        rows = np.full((h, pitch), 0xA5, np.uint8)
+        rows[:, :w * 3] = frame.reshape(h, w * 3)
+        t = np.ascontiguousarray(t, np.float32).reshape(3)
+        tr = np.ascontiguousarray(transforms if transforms is not None else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+        d_in = DevBuf.from_array(self.vs, rows)
+        d_out = DevBuf(self.vs, w * h * 3)
+        info = np.zeros(8, np.int32)
+        self.vs.check(self.vs.lib.vs_op_canvas_apply(self.h, C.byref(params), d_in.ptr, pitch, w, h, _p(t, f32p),
+                                                     _p(tr, f32p) if len(tr) else None, len(tr), d_out.ptr, w * 3, _p(info, i32p)))
+        return d_out.download((h, w, 3), np.uint8), info
+
+
 class HostBuf:
     """Page-locked host memory (vs_host_alloc) as a numpy array: frames that the host entry points move by DMA."""
 
@@ -428,6 +465,14 @@ class VsLib:
         L.vs_azc_get_output_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.vs_op_scale_jobs.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, C.c_int, vp]
         L.vs_op_scale_jobs_plan.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, i32p]
+        L.vs_op_copy_make_border.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp]
+        L.vs_op_fade_blend.argtypes = [vp, vp, C.c_size_t, C.c_float, C.c_float, vp]
+        L.vs_op_fade_update.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
+        L.vs_op_canvas_create.argtypes = [C.POINTER(vp)]
+        L.vs_op_canvas_apply.argtypes = [vp, C.POINTER(VsParams), vp, C.c_size_t, C.c_int, C.c_int, f32p, f32p, C.c_int, vp, C.c_size_t, i32p]
+        L.vs_op_canvas_info.argtypes = [vp, i32p]
+        L.vs_op_canvas_destroy.argtypes = [vp]
+        L.vs_op_canvas_destroy.restype = None
 
     # ---- helpers ----------------------------------------------------------
     def check(self, status, inst=None):
@@ -723,6 +768,48 @@ class VsLib:
         staged = np.zeros(max(1, len(jobs)), np.int32)
         self.check(self.lib.vs_op_scale_jobs_plan(self._scale_job_array(jobs), len(jobs), sample_bytes, _p(staged, i32p)))
         return staged[:len(jobs)].copy()
+
+    def copy_make_border(self, img, b, border, src_pitch=None):
+        """vs_op_copy_make_border: img (h, w) or (h, w, cn); src_pitch: a source row pitch of its own, in bytes."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape[:2]
+        cn = 1 if img.ndim == 2 else img.shape[2]
+        pitch = src_pitch or w * cn
+        rows = np.full((h, pitch), 0xA5, np.uint8)
+        rows[:, :w * cn] = img.reshape(h, w * cn)
+        ow, oh = w + 2 * b, h + 2 * b
+        d_in = DevBuf.from_array(self, rows)
+        d_out = DevBuf(self, ow * oh * cn)
+        self.check(self.lib.vs_op_copy_make_border(d_in.ptr, pitch, w, h, cn, d_out.ptr, ow * cn, b, border, None))
+        self.sync()
+        return d_out.download((oh, ow) if img.ndim == 2 else (oh, ow, cn), np.uint8)
+
+    def fade_blend(self, hist, frame, alpha, beta):
+        """vs_op_fade_blend on two flat uint8 arrays of one size: the blended frame."""
+        hist = np.ascontiguousarray(hist, np.uint8).reshape(-1)
+        frame = np.ascontiguousarray(frame, np.uint8).reshape(-1)
+        assert hist.size == frame.size
+        pad = (-hist.size) % 4
+        d_h = DevBuf.from_array(self, np.concatenate([hist, np.zeros(pad, np.uint8)]))
+        d_f = DevBuf.from_array(self, np.concatenate([frame, np.zeros(pad, np.uint8)]))
+        self.check(self.lib.vs_op_fade_blend(d_h.ptr, d_f.ptr, hist.size, alpha, beta, None))
+        self.sync()
+        return d_f.download((hist.size,), np.uint8)
+
+    def fade_update(self, hist, stab, row_bytes, rows):
+        """vs_op_fade_update: hist a flat uint8 array of at least rows * row_bytes bytes (the whole array comes back, so that a
+        guard behind the history can be checked), stab (rows, pitch) uint8 with pitch >= row_bytes."""
+        hist = np.ascontiguousarray(hist, np.uint8).reshape(-1)
+        stab = np.ascontiguousarray(stab, np.uint8)
+        assert stab.shape[0] == rows and stab.shape[1] >= row_bytes and hist.size >= rows * row_bytes
+        d_h = DevBuf.from_array(self, hist)
+        d_s = DevBuf.from_array(self, stab)
+        self.check(self.lib.vs_op_fade_update(d_h.ptr, d_s.ptr, stab.shape[1], row_bytes, rows, None))
+        self.sync()
+        return d_h.download((hist.size,), np.uint8)
+
+    def canvas_op(self):
+        return CanvasOp(self)
 
     def content_mask(self, img):
         img = np.ascontiguousarray(img)
