@@ -41,7 +41,8 @@ extern "C" {
  *    4:4:4 - VS_FMT_I422, VS_FMT_I444, VS_FMT_I210, VS_FMT_I212, VS_FMT_I410, VS_FMT_I412 (enum vs_pixfmt_planar4xx) - with
  *    vs_op_warp_affine_planar; the output size of auto zoom/crop: vs_azc_set_output_size, vs_azc_get_output_size, struct
  *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan; the compositing operators vs_op_copy_make_border, vs_op_fade_blend,
- *    vs_op_fade_update and vs_op_canvas_create / apply / info / destroy (new entry points, new values and new structs only: no existing
+ *    vs_op_fade_update and vs_op_canvas_create / apply / info / destroy; colour conversion on the device: vs_op_cvt_yuv_to_rgb,
+ *    vs_op_cvt_rgb_to_yuv and vs_enh_apply_yuv_dev (new entry points, new values and new structs only: no existing
  *    struct or entry point changed, so the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
@@ -885,6 +886,47 @@ int vs_op_canvas_apply(vs_canvas_op* c, const vs_params_c* params, const void* d
 int vs_op_canvas_info(const vs_canvas_op* c, int32_t info[8]);
 void vs_op_canvas_destroy(vs_canvas_op* c);
 
+/* ---- colour conversion between YUV surfaces and interleaved 8-bit RGB in HBM (tests/cvtref.py states what they compute) ----
+ * The bridge between the decoder / encoder surfaces and the stages that take interleaved colour (the enhancer, border pad,
+ * crop-and-zoom, fade, the virtual canvas, the C++ classes): what the reference does with nvvidconv in front of its pipeline
+ * (src/CamCap.cpp:49-52,66-72) and with cv::cvtColor(COLOR_BGR2YUV_I420) plus a byte loop on the host behind it
+ * (examples/JetsonEncoder.cpp:199-241).
+ *
+ * yuv_fmt: any non-interleaved format - VS_FMT_NV12, VS_FMT_P010, VS_FMT_I420 (YV12 through the offsets), VS_FMT_I010, VS_FMT_I012,
+ * VS_FMT_I422, VS_FMT_I444, VS_FMT_I210, VS_FMT_I212, VS_FMT_I410, VS_FMT_I412; its chroma planes have (w >> sx) x (h >> sy) samples.
+ * rgb_fmt: VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8 or VS_FMT_RGBA8; alpha is written as 255 and ignored on input.
+ * n = 1 .. 32 surfaces of one geometry and layout are converted in ONE launch, asynchronous on `stream`; d_surfaces and d_rgb are
+ * HOST arrays of n device pointers, read during the call.
+ * Layout of the YUV side: struct vs_i420_layout with its defaults per format (c_pitch 0 = pitch >> sx, u_off 0 = behind the h luma
+ * rows, v_off 0 = behind U).  NV12 / P010: u_off is the offset of the interleaved (U, V) plane (0 = h * pitch), v_off must be 0 and
+ * c_pitch 0 or equal to pitch.  rgb_stride: bytes per row of the RGB side, at least w * 3 (w * 4 with alpha).
+ *
+ * Definition: ITU-R BT.601 limited range in the fixed-point arithmetic of OpenCV 4.x (imgproc/src/color_yuv.simd.hpp), the path of
+ * COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_I420 and COLOR_BGR2YUV_I420.  All arithmetic in 32-bit integers, >> an arithmetic shift,
+ * sat = clamp to 0 .. 255, H = 1 << 19.
+ *   YUV -> RGB, pixel (x, y) with the chroma sample at (x >> sx, y >> sy), nearest, no interpolation:
+ *     Y' = max(0, Y - 16) * 1220542;  u = U - 128;  v = V - 128
+ *     R = sat((Y' + H + 1673527 * v) >> 20)
+ *     G = sat((Y' + H - 852492 * v - 409993 * u) >> 20)
+ *     B = sat((Y' + H + 2116026 * u) >> 20)
+ *   RGB -> YUV: Y for every pixel; U and V from the ONE pixel at (cx << sx, cy << sy), the top-left of its block, no averaging
+ *   (that is what OpenCV does):
+ *     Y = sat((269484 * R + 528482 * G + 102760 * B + H + (16 << 20)) >> 20)
+ *     U = sat((-155188 * R - 305135 * G + 460324 * B + H + (128 << 20)) >> 20)
+ *     V = sat((460324 * R - 385875 * G - 74448 * B + H + (128 << 20)) >> 20)
+ *   16-bit samples are read as the byte their analysis uses - P010: sample >> 8; the low-bit formats: min(sample >> (bits - 8), 255) -
+ *   and written as byte << 8 (P010) or byte << (bits - 8).  OpenCV has no code for these samples, nor for planar 4:2:2 / 4:4:4:
+ *   there the formulas above with the format's (sx, sy) ARE the definition.
+ * Refusals (VS_ERR_INVALID_ARG, vs_last_error names the format), all decided before any device call: a null pointer; n outside
+ * 1 .. 32; w not a multiple of 1 << sx or h not one of 1 << sy (or a size above 65536); a pitch below a row's bytes; rgb_stride
+ * < w * cn; an odd pointer, pitch or offset of a 16-bit format; with c_pitch = 0 and sx = 1 an odd pitch (16-bit: one that is no
+ * multiple of 4); planes of a layout that overlap; a format of the wrong family on either side.  Valid arguments on a machine without
+ * a device: VS_ERR_NO_DEVICE.  Nothing outside a row's w samples is written (padding and gaps between planes keep their bytes). */
+int vs_op_cvt_yuv_to_rgb(int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in, int rgb_fmt, void* const* d_rgb,
+                         size_t rgb_stride, int n, int w, int h, void* stream);
+int vs_op_cvt_rgb_to_yuv(int rgb_fmt, const void* const* d_rgb, size_t rgb_stride, int yuv_fmt, void* const* d_surfaces,
+                         const vs_i420_layout* out, int n, int w, int h, void* stream);
+
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */
 void vs_enh_params_default(vs_enh_params_c* p);
@@ -911,6 +953,14 @@ int vs_enh_apply_dev(vs_enh* e, const vs_enh_params_c* params, const void* d_dat
 int vs_enh_apply_batch_dev(vs_enh* e, const vs_enh_params_c* params, const void* const* d_frames,
                            void* const* d_outs, int n, int w, int h, size_t stride,
                            size_t out_stride);
+/* The enhancer on one YUV surface in HBM (yuv_fmt, layouts and their rules as for vs_op_cvt_yuv_to_rgb).  The result is BY DEFINITION
+ * the composition of three calls: vs_op_cvt_yuv_to_rgb(..., VS_FMT_BGR8) into the object's scratch (rows padded to a multiple of 4
+ * bytes), the stages of vs_enh_apply_dev, vs_op_cvt_rgb_to_yuv into d_out.  All three run on the object's stream and are left in
+ * flight (vs_enh_sync).  d_out may be d_surface.  The two conversions are lossy - limited range, chroma decimated to one sample per
+ * block, the low bits of 16-bit samples dropped - so an enhancer with neutral settings does NOT return the surface bit for bit.
+ * Refusals: those of the two operators and of vs_enh_apply_dev, with the text in vs_enh_last_error.  (No batch form, no fused pass.) */
+int vs_enh_apply_yuv_dev(vs_enh* e, const vs_enh_params_c* params, int yuv_fmt, const void* d_surface,
+                         const vs_i420_layout* in, void* d_out, const vs_i420_layout* out, int w, int h);
 int vs_enh_sync(vs_enh* e);
 /* passes over the frame (kernel launches that read it) the last apply needed */
 int vs_enh_last_passes(const vs_enh* e);

@@ -1,8 +1,10 @@
-// The compositing stages as operators (include/vs_stab.h): vs_op_copy_make_border, vs_op_fade_blend, vs_op_fade_update and the
-// vs_op_canvas_* object.  Nothing is computed here: each entry checks its arguments and calls what the pipeline calls
-// (launch_make_border, launch_fade_blend, launch_fade_update of k_traj.hip; canvas_apply of k_canvas.hip).
+// The compositing stages as operators (include/vs_stab.h): vs_op_copy_make_border, vs_op_fade_blend, vs_op_fade_update, the
+// vs_op_canvas_* object and the colour conversions vs_op_cvt_yuv_to_rgb / vs_op_cvt_rgb_to_yuv.  Nothing is computed here: each
+// entry checks its arguments and calls what the pipeline calls (launch_make_border, launch_fade_blend, launch_fade_update of
+// k_traj.hip; canvas_apply of k_canvas.hip; launch_cvt_* of k_cvt.hip).
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "stab_internal.h"
@@ -16,7 +18,65 @@ int refuse(int code, const char* why) {
     return code;
 }
 
+// The RGB side of a conversion: the format, the n pointers, the pitch.
+int cvt_check_rgb(const char* call, int rgb_fmt, const void* const* rgb, size_t rgb_stride, int n, int w, const PixFmt** rf, std::string* msg) {
+    const PixFmt* f = pixfmt(rgb_fmt);
+    auto fail = [&](const std::string& what) { *msg = std::string(call) + ": " + what; return (int)VS_ERR_INVALID_ARG; };
+    if (!f || !f->border_modes)       // the interleaved colour formats: BGR8, BGRA8, RGBA8, RGB8
+        return fail((f ? std::string(f->name) : "format " + std::to_string(rgb_fmt)) + " is not an interleaved colour format (BGR8, RGB8, BGRA8, RGBA8)");
+    if (!rgb) return fail(std::string(f->name) + ": null pointer");
+    for (int k = 0; k < n; k++)
+        if (!rgb[k]) return fail(std::string(f->name) + ": null pointer");
+    if (rgb_stride < (size_t)w * f->cn) return fail(std::string(f->name) + ": the pitch must hold a row of the picture");
+    *rf = f;
+    return VS_OK;
+}
+
 }  // namespace
+
+namespace vsd {
+
+int cvt_check_yuv(const char* call, int yuv_fmt, const void* const* surfaces, int n, const vs_i420_layout* lay, int w, int h, I420Layout* l,
+                  std::string* msg) {
+    const PixFmt* f = pixfmt(yuv_fmt);
+    auto fail = [&](const std::string& what) { *msg = std::string(call) + ": " + what; return (int)VS_ERR_INVALID_ARG; };
+    if (!f || f->kind == PIX_INTERLEAVED)
+        return fail((f ? std::string(f->name) : "format " + std::to_string(yuv_fmt)) + " is not a YUV surface format (NV12, P010, I420 ... I412)");
+    const std::string name = f->name;
+    if (n < 1 || n > CVT_MAX_SURFACES) return fail(name + ": n must be 1 .. 32 surfaces");
+    if (!surfaces || !lay) return fail(name + ": null pointer");
+    uintptr_t ptr_bits = 0;
+    for (int k = 0; k < n; k++) {
+        if (!surfaces[k]) return fail(name + ": null pointer");
+        ptr_bits |= (uintptr_t)surfaces[k];
+    }
+    const int sb = f->sample_bytes;
+    if (w < 1 || h < 1 || w > 65536 || h > 65536) return fail(name + ": size out of range");
+    if ((w & ((1 << f->sx) - 1)) || (h & ((1 << f->sy) - 1))) return fail(name + (f->sy ? ": w and h must be even" : ": w must be even"));
+    if (lay->pitch < (size_t)w * sb) return fail(name + ": the pitch must hold a row of the picture");
+    if (sb == 2 && ((ptr_bits | lay->pitch | lay->c_pitch | lay->u_off | lay->v_off) & 1))
+        return fail(name + ": pointers, pitches and plane offsets must be even (16-bit samples)");
+    const size_t rows = (size_t)h, crows = (size_t)(h >> f->sy), crow_bytes = f->chroma_row_bytes(w) * (f->luma_uv() ? 2 : 1);
+    if (f->luma_uv()) {
+        if (lay->v_off) return fail(name + ": v_off must be 0 (U and V share one interleaved plane, at u_off)");
+        if (lay->c_pitch && lay->c_pitch != lay->pitch) return fail(name + ": c_pitch must be 0 or the pitch (the interleaved plane has the luma pitch)");
+        l->pitch = l->cpitch = lay->pitch;
+        l->u = lay->u_off ? lay->u_off : rows * lay->pitch;
+        l->v = l->u;
+    } else {
+        if (!lay->c_pitch && f->sx && (lay->pitch & (size_t)(2 * sb - 1)))
+            return fail(name + (sb == 2 ? ": the default chroma pitch needs a pitch that is a multiple of 4" : ": the default chroma pitch needs an even pitch"));
+        *l = i420_layout(lay->pitch, h, lay->u_off, lay->v_off, lay->c_pitch, f->sx, f->sy);
+        if (l->cpitch < crow_bytes) return fail(name + ": the chroma pitch must hold a chroma row");
+    }
+    // the bytes a plane's samples span: every row but the last in full, the last up to its last sample
+    const size_t y_end = (rows - 1) * l->pitch + (size_t)w * sb, c_span = (crows - 1) * l->cpitch + crow_bytes;
+    if (l->u < y_end || (!f->luma_uv() && l->v < y_end)) return fail(name + ": the chroma planes must start behind the luma rows");
+    if (!f->luma_uv() && std::max(l->u, l->v) < std::min(l->u, l->v) + c_span) return fail(name + ": the U and V planes overlap");
+    return VS_OK;
+}
+
+}  // namespace vsd
 
 struct vs_canvas_op {
     Canvas* canvas = nullptr;
@@ -54,6 +114,30 @@ int vs_op_fade_update(void* d_hist, const void* d_stab, size_t stab_stride, int 
     if (stab_stride < (size_t)row_bytes) return refuse(VS_ERR_INVALID_ARG, "vs_op_fade_update: pitch below a row");
     VS_TRY(ensure_device());
     return launch_fade_update((uint8_t*)d_hist, (const uint8_t*)d_stab, stab_stride, row_bytes, rows, (hipStream_t)stream);
+}
+
+int vs_op_cvt_yuv_to_rgb(int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in, int rgb_fmt, void* const* d_rgb, size_t rgb_stride,
+                         int n, int w, int h, void* stream) {
+    static const char call[] = "vs_op_cvt_yuv_to_rgb";
+    I420Layout l;
+    const PixFmt* rf = nullptr;
+    std::string msg;
+    if (cvt_check_yuv(call, yuv_fmt, d_surfaces, n, in, w, h, &l, &msg) != VS_OK || cvt_check_rgb(call, rgb_fmt, d_rgb, rgb_stride, n, w, &rf, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    VS_TRY(ensure_device());
+    return launch_cvt_yuv_to_rgb(*pixfmt(yuv_fmt), d_surfaces, l, *rf, d_rgb, rgb_stride, n, w, h, (hipStream_t)stream);
+}
+
+int vs_op_cvt_rgb_to_yuv(int rgb_fmt, const void* const* d_rgb, size_t rgb_stride, int yuv_fmt, void* const* d_surfaces, const vs_i420_layout* out,
+                         int n, int w, int h, void* stream) {
+    static const char call[] = "vs_op_cvt_rgb_to_yuv";
+    I420Layout l;
+    const PixFmt* rf = nullptr;
+    std::string msg;
+    if (cvt_check_yuv(call, yuv_fmt, d_surfaces, n, out, w, h, &l, &msg) != VS_OK || cvt_check_rgb(call, rgb_fmt, d_rgb, rgb_stride, n, w, &rf, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    VS_TRY(ensure_device());
+    return launch_cvt_rgb_to_yuv(*rf, d_rgb, rgb_stride, *pixfmt(yuv_fmt), d_surfaces, l, n, w, h, (hipStream_t)stream);
 }
 
 int vs_op_canvas_create(vs_canvas_op** out) {

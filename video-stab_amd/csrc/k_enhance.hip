@@ -22,6 +22,7 @@
 #include <new>
 #include <vector>
 
+#include "launchers.h"
 #include "vs_common.h"
 
 namespace vsd {
@@ -1207,6 +1208,19 @@ int enh_run(vs_enh* e, const vs_enh_params_c* p, const uint8_t* d_src, size_t ss
     return run_pass(c, pd, d_dst, dstride);
 }
 
+// d_in / d_out: the object's own BGR8 frames (vs_enh_apply's staging, vs_enh_apply_yuv_dev's conversions), grown on demand
+int enh_grow_io(vs_enh* e, size_t bytes) {
+    if (e->io_bytes >= bytes) return VS_OK;
+    VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
+    if (e->d_in) (void)hipFree(e->d_in);
+    if (e->d_out) (void)hipFree(e->d_out);
+    e->d_in = e->d_out = nullptr; e->io_bytes = 0;
+    VS_OBJ_HIP(e, hipMalloc((void**)&e->d_in, bytes));
+    VS_OBJ_HIP(e, hipMalloc((void**)&e->d_out, bytes));
+    e->io_bytes = bytes;
+    return VS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1335,21 +1349,37 @@ int vs_enh_apply(vs_enh* e, const vs_enh_params_c* p, const uint8_t* data, int w
                  size_t out_stride) {
     if (!e || !p || !data || !out || w <= 0 || h <= 0 || stride < (size_t)w * 3 || out_stride < (size_t)w * 3) return VS_ERR_INVALID_ARG;
     VS_OBJ_HIP(e, hipSetDevice(e->device));
-    const size_t pitch = ((size_t)w * 3 + 3) & ~(size_t)3, bytes = pitch * h;
-    if (e->io_bytes < bytes) {
-        VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
-        if (e->d_in) (void)hipFree(e->d_in);
-        if (e->d_out) (void)hipFree(e->d_out);
-        e->d_in = e->d_out = nullptr; e->io_bytes = 0;
-        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_in, bytes));
-        VS_OBJ_HIP(e, hipMalloc((void**)&e->d_out, bytes));
-        e->io_bytes = bytes;
-    }
+    const size_t pitch = ((size_t)w * 3 + 3) & ~(size_t)3;
+    VS_TRY(enh_grow_io(e, pitch * h));
     VS_OBJ_HIP(e, hipMemcpy2DAsync(e->d_in, pitch, data, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, e->st));
     int rc = enh_run(e, p, e->d_in, pitch, nullptr, 1, w, h, e->d_out, pitch);
     if (rc != VS_OK) return rc;
     VS_OBJ_HIP(e, hipMemcpy2DAsync(out, out_stride, e->d_out, pitch, (size_t)w * 3, h, hipMemcpyDeviceToHost, e->st));
     VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
+    return VS_OK;
+}
+
+int vs_enh_apply_yuv_dev(vs_enh* e, const vs_enh_params_c* p, int yuv_fmt, const void* d_surface, const vs_i420_layout* in, void* d_out,
+                         const vs_i420_layout* out, int w, int h) {
+    if (!e) return VS_ERR_INVALID_ARG;
+    if (!p) return vs_obj_fail(e, VS_ERR_INVALID_ARG, "vs_enh_apply_yuv_dev: null pointer");
+    I420Layout li, lo;
+    std::string msg;
+    const void* const src[1] = {d_surface};
+    void* const dst[1] = {d_out};
+    if (cvt_check_yuv("vs_enh_apply_yuv_dev", yuv_fmt, src, 1, in, w, h, &li, &msg) != VS_OK ||
+        cvt_check_yuv("vs_enh_apply_yuv_dev", yuv_fmt, dst, 1, out, w, h, &lo, &msg) != VS_OK)
+        return vs_obj_fail(e, VS_ERR_INVALID_ARG, msg);
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
+    const PixFmt& yf = *pixfmt(yuv_fmt);
+    const PixFmt& bgr = *pixfmt(VS_FMT_BGR8);
+    const size_t pitch = ((size_t)w * 3 + 3) & ~(size_t)3;
+    VS_TRY(enh_grow_io(e, pitch * h));
+    void* const bgr_in[1] = {e->d_in};
+    void* const bgr_out[1] = {e->d_out};
+    VS_OBJ_TRY(e, launch_cvt_yuv_to_rgb(yf, src, li, bgr, bgr_in, pitch, 1, w, h, e->st));
+    VS_OBJ_TRY(e, enh_run(e, p, e->d_in, pitch, nullptr, 1, w, h, e->d_out, pitch));
+    VS_OBJ_TRY(e, launch_cvt_rgb_to_yuv(bgr, bgr_out, pitch, yf, dst, lo, 1, w, h, e->st));
     return VS_OK;
 }
 

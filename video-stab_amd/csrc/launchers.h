@@ -90,6 +90,20 @@ inline int planar_layout_check(int fmt, const void* ptr, int w, int h, const vs_
     return VS_OK;
 }
 
+// ---- k_cvt.hip: YUV surfaces <-> interleaved 8-bit RGB (vs_op_cvt_yuv_to_rgb, vs_op_cvt_rgb_to_yuv, vs_enh_apply_yuv_dev)
+constexpr int CVT_MAX_SURFACES = 32;        // of one launch: their pointers are kernel arguments
+// What the conversions refuse about the YUV side - format family, geometry, pitches, 16-bit alignment, the planes of the layout -
+// decided on the host before any device call (comp_op.cpp).  n surface pointers (checked: non-null, even for 16-bit samples).
+// Fills *l with the defaults resolved (NV12 / P010: u = the interleaved plane, cpitch = pitch), or *msg with a text that names the
+// call and the format.
+int cvt_check_yuv(const char* call, int yuv_fmt, const void* const* surfaces, int n, const vs_i420_layout* lay, int w, int h, I420Layout* l,
+                  std::string* msg);
+// n <= CVT_MAX_SURFACES surfaces of one geometry and layout in one launch (grid z = surface); rf: BGR8, RGB8, BGRA8 or RGBA8
+int launch_cvt_yuv_to_rgb(const PixFmt& yf, const void* const* surfaces, const I420Layout& l, const PixFmt& rf, void* const* rgb, size_t rgb_stride,
+                          int n, int w, int h, hipStream_t st);
+int launch_cvt_rgb_to_yuv(const PixFmt& rf, const void* const* rgb, size_t rgb_stride, const PixFmt& yf, void* const* surfaces, const I420Layout& l,
+                          int n, int w, int h, hipStream_t st);
+
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,
                      float* t_out = nullptr);

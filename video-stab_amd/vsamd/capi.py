@@ -473,6 +473,12 @@ class VsLib:
         L.vs_op_canvas_info.argtypes = [vp, i32p]
         L.vs_op_canvas_destroy.argtypes = [vp]
         L.vs_op_canvas_destroy.restype = None
+        try:
+            L.vs_op_cvt_yuv_to_rgb.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
+            L.vs_op_cvt_rgb_to_yuv.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int, vp]
+            L.vs_enh_apply_yuv_dev.argtypes = [vp, ep, C.c_int, vp, lp, vp, lp, C.c_int, C.c_int]
+        except AttributeError:      # a library of an earlier build (A/B measurements)
+            pass
 
     # ---- helpers ----------------------------------------------------------
     def check(self, status, inst=None):
@@ -808,6 +814,61 @@ class VsLib:
         self.sync()
         return d_h.download((hist.size,), np.uint8)
 
+    def cvt_yuv_to_rgb(self, yuv_fmt, surfaces, w, h, rgb_fmt=FMT_BGR8, layout=None, rgb_stride=None, raw=False, fill=0xA5):
+        """vs_op_cvt_yuv_to_rgb.  surfaces: one surface of w x h pixels or a list of up to 32, converted in one launch - packed frames
+        ((rows, w) arrays of the format's dtype: synth.yuv_pack, synth.nv12_to_i420, the NV12 / P010 arrays) or flat buffers in
+        `layout` = (pitch, c_pitch, u_off, v_off) in bytes, 0 = the default of a field (NV12 / P010: u_off = the interleaved plane).
+        -> (h, w, cn) uint8 per surface; raw=True: the whole destination instead, h * rgb_stride + 16 bytes prefilled with `fill`."""
+        f, cn = PIXFMT[yuv_fmt], PIXFMT[rgb_fmt].cn
+        srcs, single = _surface_list(surfaces)
+        n = len(srcs)
+        lay = I420LayoutC(*(layout or (f.sample_bytes * w, 0, 0, 0)))
+        stride = rgb_stride or w * cn
+        nbytes = h * stride + 16
+        d_in = [DevBuf.from_array(self, s) for s in srcs]
+        d_out = [DevBuf.from_array(self, np.full(nbytes, fill, np.uint8)) for _ in range(n)]
+        try:
+            self.check(self.lib.vs_op_cvt_yuv_to_rgb(yuv_fmt, _ptr_array(d_in), C.byref(lay), rgb_fmt, _ptr_array(d_out), stride, n, w, h, None))
+            self.sync()
+            outs = [d.download((nbytes,), np.uint8) for d in d_out]
+        finally:
+            for d in d_in + d_out:
+                d.free()
+        if not raw:
+            outs = [o[:h * stride].reshape(h, stride)[:, :w * cn].reshape(h, w, cn).copy() for o in outs]
+        return outs[0] if single else outs
+
+    def cvt_rgb_to_yuv(self, frames, yuv_fmt, rgb_fmt=FMT_BGR8, layout=None, size=None, rgb_stride=None, raw=False, fill=0xA5):
+        """vs_op_cvt_rgb_to_yuv.  frames: one (h, w, cn) uint8 frame or a list of up to 32 of one size, converted in one launch.
+        -> per frame the packed surface ((rows, w) array of the format's dtype) or, with a `layout` (as above) and `size` in bytes, the
+        flat buffer of that layout; raw=True: the whole destination as bytes instead, `size` + 16 of them prefilled with `fill`."""
+        f = PIXFMT[yuv_fmt]
+        single = isinstance(frames, np.ndarray) and frames.ndim == 3
+        frames = [np.ascontiguousarray(x, np.uint8) for x in ([frames] if single else frames)]
+        n = len(frames)
+        h, w, cn = frames[0].shape
+        stride = rgb_stride or w * cn
+        lay = I420LayoutC(*(layout or (f.sample_bytes * w, 0, 0, 0)))
+        size = size or yuv_surface_bytes(yuv_fmt, w, h, *(layout or ()))
+        d_in = []
+        for x in frames:
+            rows = np.full((h, stride), fill, np.uint8)
+            rows[:, :w * cn] = x.reshape(h, w * cn)
+            d_in.append(DevBuf.from_array(self, rows))
+        d_out = [DevBuf.from_array(self, np.full(size + 16, fill, np.uint8)) for _ in range(n)]
+        try:
+            self.check(self.lib.vs_op_cvt_rgb_to_yuv(rgb_fmt, _ptr_array(d_in), stride, yuv_fmt, _ptr_array(d_out), C.byref(lay), n, w, h, None))
+            self.sync()
+            outs = [d.download((size + 16,), np.uint8) for d in d_out]
+        finally:
+            for d in d_in + d_out:
+                d.free()
+        if not raw:
+            outs = [o[:size].view(fmt_dtype(yuv_fmt)) for o in outs]
+            if not layout:
+                outs = [o.reshape(fmt_frame_rows(yuv_fmt, h), w) for o in outs]
+        return outs[0] if single else outs
+
     def canvas_op(self):
         return CanvasOp(self)
 
@@ -869,6 +930,28 @@ class I420LayoutC(C.Structure):
 
 def i420_layout(pitch, c_pitch=0, u_off=0, v_off=0):
     return I420LayoutC(pitch, c_pitch, u_off, v_off)
+
+
+def yuv_surface_bytes(fmt, w, h, pitch=0, c_pitch=0, u_off=0, v_off=0):
+    """Bytes up to the end of the last plane of a YUV surface in a layout (bytes, 0 = the library's default of a field)."""
+    f = PIXFMT[fmt]
+    pitch = pitch or f.sample_bytes * w
+    if f.kind == KIND_LUMA_UV:
+        return (u_off or h * pitch) + (h >> 1) * pitch
+    c_pitch = c_pitch or pitch >> f.sx
+    u_off = u_off or h * pitch
+    v_off = v_off or u_off + (h >> f.sy) * c_pitch
+    return max(u_off, v_off) + (h >> f.sy) * c_pitch
+
+
+def _surface_list(surfaces):
+    """([contiguous arrays], single): one surface - a flat buffer or a (rows, w) frame - or a list / stack of them."""
+    single = isinstance(surfaces, np.ndarray) and surfaces.ndim <= 2
+    return [np.ascontiguousarray(s) for s in ([surfaces] if single else surfaces)], single
+
+
+def _ptr_array(bufs):
+    return (C.c_void_p * len(bufs))(*[C.c_void_p(b.ptr) for b in bufs])
 
 
 class AutoZoomCrop:
@@ -1125,6 +1208,27 @@ class Enhancer:
 
     def apply_dev(self, params, d_in, w, h, stride, d_out, out_stride):
         self._check(self.lib.vs_enh_apply_dev(self.h, C.byref(params), d_in, w, h, stride, d_out, out_stride))
+
+    def apply_yuv_dev(self, params, yuv_fmt, surface, w, h, layout=None, out_layout=None, out_size=None, in_place=False, fill=0xA5):
+        """vs_enh_apply_yuv_dev on one surface: a packed frame or a flat buffer in `layout` (VsLib.cvt_yuv_to_rgb).  The result lies
+        in `out_layout` (default: the source's) in a buffer of out_size bytes prefilled with `fill`, or - in_place - in the source's
+        own device buffer.  -> the packed (rows, w) surface, or with a layout the flat buffer, in the format's dtype."""
+        f = PIXFMT[yuv_fmt]
+        src = np.ascontiguousarray(surface)
+        out_layout = out_layout or layout
+        lin = I420LayoutC(*(layout or (f.sample_bytes * w, 0, 0, 0)))
+        lout = I420LayoutC(*(out_layout or (f.sample_bytes * w, 0, 0, 0)))
+        size = src.nbytes if in_place else out_size or yuv_surface_bytes(yuv_fmt, w, h, *(out_layout or ()))
+        d_in = DevBuf.from_array(self.vs, src)
+        d_out = d_in if in_place else DevBuf.from_array(self.vs, np.full(size, fill, np.uint8))
+        try:
+            self._check(self.lib.vs_enh_apply_yuv_dev(self.h, C.byref(params), yuv_fmt, d_in.ptr, C.byref(lin), d_out.ptr, C.byref(lout), w, h))
+            self.sync()
+            out = d_out.download((size,), np.uint8).view(fmt_dtype(yuv_fmt))
+        finally:
+            d_in.free()
+            d_out.free()
+        return out if out_layout else out.reshape(fmt_frame_rows(yuv_fmt, h), w)
 
     def apply_batch_dev(self, params, d_ins, d_outs, w, h, stride, out_stride):
         n = len(d_ins)
