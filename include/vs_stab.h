@@ -42,8 +42,9 @@ extern "C" {
  *    vs_op_warp_affine_planar; the output size of auto zoom/crop: vs_azc_set_output_size, vs_azc_get_output_size, struct
  *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan; the compositing operators vs_op_copy_make_border, vs_op_fade_blend,
  *    vs_op_fade_update and vs_op_canvas_create / apply / info / destroy; colour conversion on the device: vs_op_cvt_yuv_to_rgb,
- *    vs_op_cvt_rgb_to_yuv and vs_enh_apply_yuv_dev (new entry points, new values and new structs only: no existing
- *    struct or entry point changed, so the version stays). */
+ *    vs_op_cvt_rgb_to_yuv and vs_enh_apply_yuv_dev; the enhancer on a batch of YUV surfaces in one fused launch:
+ *    vs_enh_apply_yuv_batch_dev, vs_enh_last_fused and vs_enh_yuv_plan (new entry points, new values and new structs only: no
+ *    existing struct or entry point changed, so the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -958,9 +959,32 @@ int vs_enh_apply_batch_dev(vs_enh* e, const vs_enh_params_c* params, const void*
  * bytes), the stages of vs_enh_apply_dev, vs_op_cvt_rgb_to_yuv into d_out.  All three run on the object's stream and are left in
  * flight (vs_enh_sync).  d_out may be d_surface.  The two conversions are lossy - limited range, chroma decimated to one sample per
  * block, the low bits of 16-bit samples dropped - so an enhancer with neutral settings does NOT return the surface bit for bit.
- * Refusals: those of the two operators and of vs_enh_apply_dev, with the text in vs_enh_last_error.  (No batch form, no fused pass.) */
+ * Refusals: those of the two operators and of vs_enh_apply_dev, with the text in vs_enh_last_error.  (The batch form, with a fused
+ * single pass where the stage list allows one: vs_enh_apply_yuv_batch_dev.) */
 int vs_enh_apply_yuv_dev(vs_enh* e, const vs_enh_params_c* params, int yuv_fmt, const void* d_surface,
                          const vs_i420_layout* in, void* d_out, const vs_i420_layout* out, int w, int h);
+/* n = 1 .. 32 surfaces of one format, geometry and layout (one `in` for every source, one `out` for every destination): the result
+ * of n calls of vs_enh_apply_yuv_dev, byte for byte - that composition of three calls stays the definition.  Where the stage list
+ * comes to ONE pass over the frame - table stages (brightness / contrast, gamma), optionally vibrance, or the unsharp mask with
+ * tables in front of and behind it; no white balance, CLAHE or denoiser - all n surfaces go through ONE launch that reads the
+ * YUV samples, converts them on the way in, runs the pass and converts the results back on the way out: no BGR8 frame in between.
+ * Every other stage list runs surface by surface through the three calls.  d_outs[i] may be d_surfaces[i] (in place; the unsharp
+ * pass then takes the three calls, since a tile reads its neighbours' samples); ANY OTHER overlap between an output and an input
+ * of the same call - two entries that share bytes, an output inside another surface's planes - is the caller's error and gives
+ * undefined bytes.  Left in flight on the object's stream (vs_enh_sync).  Refusals: VS_ERR_INVALID_ARG with a text in
+ * vs_enh_last_error that names this call and the format, for what vs_op_cvt_yuv_to_rgb refuses about either side (n outside
+ * 1 .. 32, a null entry, geometry, pitches, 16-bit alignment, overlapping planes, a format that is no YUV surface format); the
+ * code vs_enh_apply_dev gives for a stage list it refuses (blur_sigma, clahe_tile_grid_size).  All of them are decided before any
+ * device call: a refused call writes nothing and queues nothing. */
+int vs_enh_apply_yuv_batch_dev(vs_enh* e, const vs_enh_params_c* params, int yuv_fmt, const void* const* d_surfaces,
+                               const vs_i420_layout* in, void* const* d_outs, const vs_i420_layout* out, int n, int w, int h);
+/* how many surfaces of the last vs_enh_apply_yuv_batch_dev call went through the fused launch (0: the three-call path) */
+int vs_enh_last_fused(const vs_enh* e);
+/* Host only, needs no device: 1 if a vs_enh_apply_yuv_batch_dev call with these parameters would take the fused launch (in_place: some
+ * d_outs[i] is d_surfaces[i]), 0 if the three-call path, < 0 a refusal: minus the vs_status the call would return
+ * (-VS_ERR_INVALID_ARG: null params, not a YUV surface format, blur_sigma; -VS_ERR_UNSUPPORTED: clahe_tile_grid_size, a blur
+ * of more than 33 taps). */
+int vs_enh_yuv_plan(const vs_enh_params_c* params, int yuv_fmt, int in_place);
 int vs_enh_sync(vs_enh* e);
 /* passes over the frame (kernel launches that read it) the last apply needed */
 int vs_enh_last_passes(const vs_enh* e);

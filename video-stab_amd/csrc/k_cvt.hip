@@ -1,6 +1,7 @@
 // Colour conversion between YUV surfaces and interleaved 8-bit RGB in HBM: vs_op_cvt_yuv_to_rgb, vs_op_cvt_rgb_to_yuv (comp_op.cpp)
 // and the two ends of vs_enh_apply_yuv_dev (k_enhance.hip).  The definition is in include/vs_stab.h (ITU-R BT.601 limited range, the
-// fixed-point path of OpenCV's COLOR_YUV2BGR_NV12 / _I420 and COLOR_BGR2YUV_I420; tests/cvtref.py states it in numpy).
+// fixed-point path of OpenCV's COLOR_YUV2BGR_NV12 / _I420 and COLOR_BGR2YUV_I420; tests/cvtref.py states it in numpy).  The per-pixel
+// arithmetic is in cvt_px.h, shared with the enhancer's YUV form.
 //
 // Both kernels stream: a lane covers CVT_PX consecutive pixels in the 1 << SY rows that share a chroma row, so every chroma sample
 // is read (or computed and written) once; a wave covers 512 pixels of those rows, a block four chroma rows; blockIdx.z = surface,
@@ -10,6 +11,7 @@
 // kernel.  No LDS.
 #include <hip/hip_runtime.h>
 
+#include "cvt_px.h"
 #include "launchers.h"
 #include "vs_common.h"
 
@@ -33,8 +35,6 @@ struct CvtArgs {
     int rgb_order;                 // 1: R first (RGB8, RGBA8)
 };
 
-__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
-
 // N samples of SB bytes at p, the first `valid` of them inside the row, as bytes
 template <int SB, int N>
 __device__ __forceinline__ void load_run(const uint8_t* __restrict__ p, int valid, int shift, int (&v)[N]) {
@@ -49,7 +49,7 @@ __device__ __forceinline__ void load_run(const uint8_t* __restrict__ p, int vali
 #pragma unroll
         for (int i = 0; i < N; i++) {
             if constexpr (SB == 1) v[i] = (int)((q[i / 4] >> (8 * (i % 4))) & 255u);
-            else v[i] = min((int)((q[i / 2] >> (16 * (i % 2))) & 0xffffu) >> shift, 255);
+            else v[i] = cvt_sample_to_byte((int)((q[i / 2] >> (16 * (i % 2))) & 0xffffu), shift);
         }
     } else {
 #pragma unroll
@@ -57,7 +57,7 @@ __device__ __forceinline__ void load_run(const uint8_t* __restrict__ p, int vali
             v[i] = 0;
             if (i < valid) {
                 if constexpr (SB == 1) v[i] = p[i];
-                else v[i] = min((int)reinterpret_cast<const uint16_t*>(p)[i] >> shift, 255);
+                else v[i] = cvt_sample_to_byte((int)reinterpret_cast<const uint16_t*>(p)[i], shift);
             }
         }
     }
@@ -72,7 +72,7 @@ __device__ __forceinline__ void store_run(uint8_t* __restrict__ p, int valid, in
 #pragma unroll
         for (int i = 0; i < N; i++) {
             if constexpr (SB == 1) q[i / 4] |= (uint32_t)v[i] << (8 * (i % 4));
-            else q[i / 2] |= ((uint32_t)v[i] << shift) << (16 * (i % 2));
+            else q[i / 2] |= cvt_byte_to_sample((uint32_t)v[i], shift) << (16 * (i % 2));
         }
         if constexpr (BYTES == 2) __builtin_nontemporal_store((uint16_t)q[0], reinterpret_cast<uint16_t*>(p));
         else if constexpr (BYTES == 4) __builtin_nontemporal_store(q[0], reinterpret_cast<uint32_t*>(p));
@@ -83,7 +83,7 @@ __device__ __forceinline__ void store_run(uint8_t* __restrict__ p, int valid, in
         for (int i = 0; i < N; i++) {
             if (i < valid) {
                 if constexpr (SB == 1) p[i] = (uint8_t)v[i];
-                else reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)(v[i] << shift);
+                else reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)cvt_byte_to_sample((uint32_t)v[i], shift);
             }
         }
     }
@@ -171,12 +171,7 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_yuv_to_rgb_kernel(const C
     }
     int ru[NC], gu[NC], bu[NC];                 // the chroma terms, with the rounding half
 #pragma unroll
-    for (int k = 0; k < NC; k++) {
-        const int uu = u[k] - 128, vv = v[k] - 128;
-        ru[k] = (1 << 19) + 1673527 * vv;
-        gu[k] = (1 << 19) - 852492 * vv - 409993 * uu;
-        bu[k] = (1 << 19) + 2116026 * uu;
-    }
+    for (int k = 0; k < NC; k++) cvt_chroma_terms(u[k], v[k], ru[k], gu[k], bu[k]);
 #pragma unroll
     for (int r = 0; r < (1 << SY); r++) {
         const size_t y = ((size_t)cy << SY) + r;
@@ -184,8 +179,8 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_yuv_to_rgb_kernel(const C
         load_run<SB, CVT_PX>(s + y * a.pitch + (size_t)x0 * SB, valid, a.shift, yy);
 #pragma unroll
         for (int i = 0; i < CVT_PX; i++) {
-            const int yp = max(0, yy[i] - 16) * 1220542;
-            const int R = sat8((yp + ru[i >> SX]) >> 20), G = sat8((yp + gu[i >> SX]) >> 20), B = sat8((yp + bu[i >> SX]) >> 20);
+            int R, G, B;
+            cvt_yuv_px(yy[i], ru[i >> SX], gu[i >> SX], bu[i >> SX], R, G, B);
             c[i][0] = a.rgb_order ? R : B;
             c[i][1] = G;
             c[i][2] = a.rgb_order ? B : R;
@@ -205,7 +200,6 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_rgb_to_yuv_kernel(const C
     constexpr int NC = CVT_PX >> SX;
     const int cvalid = valid >> SX;
     const size_t cx0 = (size_t)(x0 >> SX);
-    constexpr int H = 1 << 19;
 #pragma unroll
     for (int r = 0; r < (1 << SY); r++) {
         const size_t y = ((size_t)cy << SY) + r;
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_rgb_to_yuv_kernel(const C
 #pragma unroll
         for (int i = 0; i < CVT_PX; i++) {
             const int R = a.rgb_order ? c[i][0] : c[i][2], G = c[i][1], B = a.rgb_order ? c[i][2] : c[i][0];
-            yy[i] = sat8((269484 * R + 528482 * G + 102760 * B + H + (16 << 20)) >> 20);
+            yy[i] = cvt_luma(R, G, B);
         }
         store_run<SB, CVT_PX>(d + y * a.pitch + (size_t)x0 * SB, valid, a.shift, yy);
         if (r == 0) {                            // chroma: the top-left pixel of each block, no averaging
@@ -223,8 +217,7 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_rgb_to_yuv_kernel(const C
             for (int k = 0; k < NC; k++) {
                 const int i = k << SX;
                 const int R = a.rgb_order ? c[i][0] : c[i][2], G = c[i][1], B = a.rgb_order ? c[i][2] : c[i][0];
-                u[k] = sat8((-155188 * R - 305135 * G + 460324 * B + H + (128 << 20)) >> 20);
-                v[k] = sat8((460324 * R - 385875 * G - 74448 * B + H + (128 << 20)) >> 20);
+                cvt_chroma(R, G, B, u[k], v[k]);
             }
             if constexpr (IL) {
                 int uv[2 * NC];

@@ -13,15 +13,20 @@
 //   * stages that need a whole-frame statistic (white balance: channel sums; CLAHE: tile
 //     histograms) get one extra read-only pass that evaluates the pending per-pixel stages on the fly;
 //   * vibrance (HSV round trip) and CLAHE (Lab round trip + tile-table interpolation) are per-pixel
-//     stages of enh_point_kernel.
+//     stages of enh_point_kernel;
+//   * both frame kernels also exist in a form that reads and writes YUV surfaces (IO = YuvIo; the conversion arithmetic of
+//     cvt_px.h on the way into the pass and out of it): a stage list that is ONE pass runs on up to 32 decoder surfaces
+//     in one launch, without a BGR8 frame in between (vs_enh_apply_yuv_batch_dev).
 // Nothing is computed on the host except 256-entry tables that depend on parameters only (the gamma
 // table needs libm's powf, as in the reference) and the colour-conversion tables built once per object.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
+#include "cvt_px.h"
 #include "launchers.h"
 #include "vs_common.h"
 
@@ -228,6 +233,202 @@ __device__ __forceinline__ void pack12(const int* b, const int* g, const int* r,
     d2 = (uint32_t)r[2] | ((uint32_t)b[3] << 8) | ((uint32_t)g[3] << 16) | ((uint32_t)r[3] << 24);
 }
 
+typedef const uint8_t __attribute__((address_space(1)))* gptr_c;   // global address space: global_load/store, not flat
+typedef uint8_t __attribute__((address_space(1)))* gptr;
+
+// ---- YUV surfaces as the source and the destination of the two frame kernels (vs_enh_apply_yuv_batch_dev) -----------------------
+// n surfaces of one format and geometry; the layouts are those cvt_check_yuv resolved (NV12 / P010: u = the interleaved plane).
+// Everything here is wave-uniform: the format's layout travels as kernel arguments, not as template parameters (the unsharp
+// kernel already has sixteen instances).  Row offsets inside a plane are 32-bit; the host sends larger surfaces the other way.
+struct YuvIo {
+    const uint8_t* src[CVT_MAX_SURFACES];
+    uint8_t* dst[CVT_MAX_SURFACES];
+    size_t su, sv, du, dv;                // plane offsets behind the surface pointer
+    uint32_t spitch, scpitch, dpitch, dcpitch;
+    int32_t sb, il, sx, sy, shift;        // bytes per sample; (U, V) interleaved; chroma plane (w >> sx) x (h >> sy); 16-bit: byte = min(sample >> shift, 255)
+};
+
+typedef const uint16_t __attribute__((address_space(1)))* gptr16_c;
+typedef uint16_t __attribute__((address_space(1)))* gptr16;
+typedef const uint32_t __attribute__((address_space(1)))* gptr32_c;
+typedef uint32_t __attribute__((address_space(1)))* gptr32;
+
+// one sample, and runs of two and of four consecutive samples, as bytes (sample i in byte i of the result).  A run whose address
+// is aligned moves as dwords (16-bit words for two 8-bit samples); any other goes sample by sample, as in k_cvt.hip.
+template <int SB>
+__device__ __forceinline__ uint32_t yuv_ld1(gptr_c p, int shift) {
+    if constexpr (SB == 1) return *p;
+    else return (uint32_t)cvt_sample_to_byte((int)*(gptr16_c)p, shift);
+}
+template <int SB>
+__device__ __forceinline__ uint32_t yuv_ld2(gptr_c p, int shift) {
+    if constexpr (SB == 1) {
+        if (((uintptr_t)p & 1) == 0) return *(gptr16_c)p;
+        return (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+    } else {
+        uint32_t a;
+        if (((uintptr_t)p & 3) == 0) a = *(gptr32_c)p;
+        else a = (uint32_t)((gptr16_c)p)[0] | ((uint32_t)((gptr16_c)p)[1] << 16);
+        return (uint32_t)cvt_sample_to_byte((int)(a & 0xffffu), shift) | ((uint32_t)cvt_sample_to_byte((int)(a >> 16), shift) << 8);
+    }
+}
+template <int SB>
+__device__ __forceinline__ uint32_t yuv_ld4(gptr_c p, int shift) {
+    if constexpr (SB == 1) {
+        if (((uintptr_t)p & 3) == 0) return *(gptr32_c)p;
+        return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    } else {
+        uint32_t a, b;
+        if (((uintptr_t)p & 3) == 0) { a = ((gptr32_c)p)[0]; b = ((gptr32_c)p)[1]; }
+        else {
+            gptr16_c q = (gptr16_c)p;
+            a = (uint32_t)q[0] | ((uint32_t)q[1] << 16);
+            b = (uint32_t)q[2] | ((uint32_t)q[3] << 16);
+        }
+        return (uint32_t)cvt_sample_to_byte((int)(a & 0xffffu), shift) | ((uint32_t)cvt_sample_to_byte((int)(a >> 16), shift) << 8) |
+               ((uint32_t)cvt_sample_to_byte((int)(b & 0xffffu), shift) << 16) | ((uint32_t)cvt_sample_to_byte((int)(b >> 16), shift) << 24);
+    }
+}
+// N = 2 or 4 samples from the bytes of v, the first `valid` of them inside the row: nothing beyond them is written
+template <int SB, int N>
+__device__ __forceinline__ void yuv_st(gptr p, int valid, int shift, uint32_t v) {
+    static_assert(N == 2 || N == 4, "runs of two or four samples");
+    if (valid == N && ((uintptr_t)p & (SB * N == 2 ? 1 : 3)) == 0) {
+        if constexpr (SB == 1 && N == 2) *(gptr16)p = (uint16_t)v;
+        else if constexpr (SB == 1) *(gptr32)p = v;
+        else {
+            ((gptr32)p)[0] = cvt_byte_to_sample(v & 255u, shift) | (cvt_byte_to_sample((v >> 8) & 255u, shift) << 16);
+            if constexpr (N == 4) ((gptr32)p)[1] = cvt_byte_to_sample((v >> 16) & 255u, shift) | (cvt_byte_to_sample(v >> 24, shift) << 16);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            if (i < valid) {
+                const uint32_t b = (v >> (8 * i)) & 255u;
+                if constexpr (SB == 1) p[i] = (uint8_t)b;
+                else ((gptr16)p)[i] = (uint16_t)cvt_byte_to_sample(b, shift);
+            }
+        }
+    }
+}
+
+// how the chroma of a format lies: one plane of interleaved (U, V) pairs, or two planes with a sample per two / per one pixel
+enum { YL_UV = 0, YL_HALF = 1, YL_FULL = 2 };
+template <int SB_, int LAY_> struct YuvLay { static constexpr int SB = SB_, LAY = LAY_; };
+// calls f with the layout of y as a type: six straight-line variants behind one wave-uniform branch
+template <class F>
+__device__ __forceinline__ void yuv_dispatch(const YuvIo& y, F&& f) {
+    if (y.sb == 1) {
+        if (y.il) f(YuvLay<1, YL_UV>{});
+        else if (y.sx) f(YuvLay<1, YL_HALF>{});
+        else f(YuvLay<1, YL_FULL>{});
+    } else {
+        if (y.il) f(YuvLay<2, YL_UV>{});
+        else if (y.sx) f(YuvLay<2, YL_HALF>{});
+        else f(YuvLay<2, YL_FULL>{});
+    }
+}
+
+struct YuvPlanes { gptr_c y, u, v; };          // v of an interleaved plane: the sample behind u
+struct YuvPlanesOut { gptr y, u, v; };
+
+// The unit of both kernels - pixels px .. px + 3 of luma row `row`, px a multiple of 4 - as three dwords: the four luma bytes and,
+// per pixel, the bytes of the chroma sample at (x >> sx, row >> sy) (CHROMA = false: the luma dword alone).  Inside the row the
+// samples move as runs; a unit that crosses an edge takes the pixels at reflect101(x, w), one by one.
+template <class L, bool CHROMA = true>
+__device__ __forceinline__ void yuv_load_unit(const YuvIo& io, const YuvPlanes& s, int row, int px, int w, uint32_t (&raw)[3]) {
+    constexpr int SB = L::SB;
+    const uint32_t yoff = (uint32_t)row * io.spitch, coff = (uint32_t)(row >> io.sy) * io.scpitch;
+    if (px >= 0 && px + 3 < w) {
+        raw[0] = yuv_ld4<SB>(s.y + (yoff + (uint32_t)px * SB), io.shift);
+        if constexpr (!CHROMA) {
+        } else if constexpr (L::LAY == YL_UV) {
+            const uint32_t t = yuv_ld4<SB>(s.u + (coff + (uint32_t)px * SB), io.shift);       // U0 V0 U1 V1
+            raw[1] = (t & 255u) * 0x0101u | ((t >> 16) & 255u) * 0x01010000u;
+            raw[2] = ((t >> 8) & 255u) * 0x0101u | (t >> 24) * 0x01010000u;
+        } else if constexpr (L::LAY == YL_HALF) {
+            const uint32_t cb = coff + (uint32_t)(px >> 1) * SB;
+            const uint32_t tu = yuv_ld2<SB>(s.u + cb, io.shift), tv = yuv_ld2<SB>(s.v + cb, io.shift);
+            raw[1] = (tu & 255u) * 0x0101u | (tu >> 8) * 0x01010000u;
+            raw[2] = (tv & 255u) * 0x0101u | (tv >> 8) * 0x01010000u;
+        } else {
+            raw[1] = yuv_ld4<SB>(s.u + (coff + (uint32_t)px * SB), io.shift);
+            raw[2] = yuv_ld4<SB>(s.v + (coff + (uint32_t)px * SB), io.shift);
+        }
+    } else {
+        constexpr int CSTEP = L::LAY == YL_UV ? 2 * SB : SB;
+        raw[0] = 0;
+        if constexpr (CHROMA) raw[1] = raw[2] = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int xi = reflect101(px + i, w);
+            raw[0] |= yuv_ld1<SB>(s.y + (yoff + (uint32_t)xi * SB), io.shift) << (8 * i);
+            if constexpr (CHROMA) {
+                const uint32_t cb = coff + (uint32_t)(L::LAY == YL_FULL ? xi : xi >> 1) * CSTEP;
+                raw[1] |= yuv_ld1<SB>(s.u + cb, io.shift) << (8 * i);
+                raw[2] |= yuv_ld1<SB>(s.v + cb, io.shift) << (8 * i);
+            }
+        }
+    }
+}
+
+// ... and as four B, G, R pixels (the YUV -> BGR formulas of the header)
+__device__ __forceinline__ void yuv_unit_to_bgr(const uint32_t (&raw)[3], int* b, int* g, int* r) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        int ru, gu, bu;
+        cvt_chroma_terms((int)((raw[1] >> (8 * i)) & 255u), (int)((raw[2] >> (8 * i)) & 255u), ru, gu, bu);
+        cvt_yuv_px((int)((raw[0] >> (8 * i)) & 255u), ru, gu, bu, r[i], g[i], b[i]);
+    }
+}
+
+// Four results of luma row `row` at pixels px .. px + 3 (px a multiple of 4) through the RGB -> YUV formulas: Y of every pixel; with
+// `chroma`, U and V of the pixel at the left of each chroma block of this row (the caller passes the top row of a block).
+template <class L>
+__device__ __forceinline__ void yuv_store_unit(const YuvIo& io, const YuvPlanesOut& d, int row, int px, int w, const int* b, const int* g,
+                                               const int* r, bool chroma) {
+    constexpr int SB = L::SB;
+    const int valid = min(4, w - px);
+    uint32_t y4 = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) y4 |= (uint32_t)cvt_luma(r[i], g[i], b[i]) << (8 * i);
+    yuv_st<SB, 4>(d.y + ((uint32_t)row * io.dpitch + (uint32_t)px * SB), valid, io.shift, y4);
+    if (!chroma) return;
+    const uint32_t coff = (uint32_t)(row >> io.sy) * io.dcpitch;
+    if constexpr (L::LAY == YL_FULL) {
+        uint32_t u4 = 0, v4 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            int u, v;
+            cvt_chroma(r[i], g[i], b[i], u, v);
+            u4 |= (uint32_t)u << (8 * i); v4 |= (uint32_t)v << (8 * i);
+        }
+        yuv_st<SB, 4>(d.u + (coff + (uint32_t)px * SB), valid, io.shift, u4);
+        yuv_st<SB, 4>(d.v + (coff + (uint32_t)px * SB), valid, io.shift, v4);
+    } else {
+        int u0, v0, u1, v1;
+        cvt_chroma(r[0], g[0], b[0], u0, v0);
+        cvt_chroma(r[2], g[2], b[2], u1, v1);
+        if constexpr (L::LAY == YL_UV) {
+            yuv_st<SB, 4>(d.u + (coff + (uint32_t)px * SB), 2 * (valid >> 1), io.shift,
+                          (uint32_t)u0 | ((uint32_t)v0 << 8) | ((uint32_t)u1 << 16) | ((uint32_t)v1 << 24));
+        } else {
+            const uint32_t cb = coff + (uint32_t)(px >> 1) * SB;
+            yuv_st<SB, 2>(d.u + cb, valid >> 1, io.shift, (uint32_t)u0 | ((uint32_t)u1 << 8));
+            yuv_st<SB, 2>(d.v + cb, valid >> 1, io.shift, (uint32_t)v0 | ((uint32_t)v1 << 8));
+        }
+    }
+}
+
+__device__ __forceinline__ YuvPlanes yuv_src_planes(const YuvIo& io, int k) {
+    gptr_c p = (gptr_c)io.src[k];
+    return YuvPlanes{p, p + io.su, io.il ? p + io.su + io.sb : p + io.sv};
+}
+__device__ __forceinline__ YuvPlanesOut yuv_dst_planes(const YuvIo& io, int k) {
+    gptr p = (gptr)io.dst[k];
+    return YuvPlanesOut{p, p + io.du, io.il ? p + io.du + io.sb : p + io.dv};
+}
+
 // ---- unsharp tile kernel ------------------------------------------------------------------------
 struct UnsharpArgs {
     const uint8_t* src; uint8_t* dst;
@@ -247,9 +448,6 @@ __device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b), c, false);
 }
 
-typedef const uint8_t __attribute__((address_space(1)))* gptr_c;   // global address space: global_load/store, not flat
-typedef uint8_t __attribute__((address_space(1)))* gptr;
-
 // One composed table per side of the blur at fixed LDS addresses: lookups need no address arithmetic.
 __device__ __forceinline__ void compose_luts(const Chain& ch, const uint8_t* g_lut, uint8_t* s_tab, int tid) {
 #pragma unroll
@@ -262,8 +460,14 @@ __device__ __forceinline__ void compose_luts(const Chain& ch, const uint8_t* g_l
     }
 }
 
-template <int R>
-__global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a) {
+struct NoYuv {};     // the BGR8 form: samples come from and go to a.src / a.dst (or a.table)
+
+// One tile of either form.  IO = NoYuv: interleaved BGR8 frames.  IO = YuvIo: blockIdx.z = surface (a.src, a.dst, a.table, the strides
+// and the alignment flags are not read); the staging converts the samples of a YUV surface on their way into the planes (which
+// hold B, G, R bytes as before: LDS does not grow), the store side converts the results back.
+template <int R, class IO>
+__global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a, const IO io) {
+    constexpr bool YUV = !std::is_same<IO, NoYuv>::value;
     constexpr int RA = (R + 3) / 4 * 4;             // halo along x rounded up to whole 4-px groups
     constexpr int SW = E_TW + 2 * RA, SH = E_TH + 2 * R, GW = SW / 4;
     constexpr int N = 2 * R + 1, NQ = (N + 3) / 4;
@@ -275,38 +479,59 @@ __global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a) 
     __shared__ uint8_t s_pre[SLOT_BYTES], s_post[SLOT_BYTES];
 
     const int tid = threadIdx.x;
-    gptr_c src = (gptr_c)a.src;
-    gptr dst = (gptr)a.dst;
-    if (a.table) { src = (gptr_c)a.table[blockIdx.z].src; dst = (gptr)a.table[blockIdx.z].dst; }
+    gptr_c src = nullptr;
+    gptr dst = nullptr;
+    if constexpr (!YUV) {
+        src = (gptr_c)a.src;
+        dst = (gptr)a.dst;
+        if (a.table) { src = (gptr_c)a.table[blockIdx.z].src; dst = (gptr)a.table[blockIdx.z].dst; }
+    }
     const int x0 = blockIdx.x * E_TW, y0 = blockIdx.y * E_TH;
     const bool has_pre = a.pre.n > 0, has_post = a.post.n > 0;
 
     // 1a. raw loads of tile + halo (all rounds in flight), table composition meanwhile
     uint32_t raw[NRND][3];
+    if constexpr (YUV) {
+        const YuvPlanes sp = yuv_src_planes(io, blockIdx.z);
+        yuv_dispatch(io, [&](auto lay) {
 #pragma unroll
-    for (int k = 0; k < NRND; k++) {
-        const int u = tid + k * E_NT;
-        raw[k][0] = raw[k][1] = raw[k][2] = 0;
-        if (NU % E_NT == 0 || u < NU) {
-            const int ry = u / GW, gx = u - ry * GW;
-            int sy = y0 - R + ry;
-            if ((unsigned)sy >= (unsigned)a.h) sy = reflect101(sy, a.h);
-            const int px = x0 - RA + 4 * gx;
-            const uint32_t roff = (uint32_t)sy * (uint32_t)a.sstride;
-            if (a.src_aligned && px >= 0 && px + 3 < a.w) {
-                const uint32_t __attribute__((address_space(1)))* p =
-                    (const uint32_t __attribute__((address_space(1)))*)(src + (roff + (uint32_t)px * 3u));
-                raw[k][0] = p[0]; raw[k][1] = p[1]; raw[k][2] = p[2];
-            } else {
-                uint32_t by[12];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    gptr_c q = src + (roff + (uint32_t)reflect101(px + i, a.w) * 3u);
-                    by[3 * i] = q[0]; by[3 * i + 1] = q[1]; by[3 * i + 2] = q[2];
+            for (int k = 0; k < NRND; k++) {
+                const int u = tid + k * E_NT;
+                raw[k][0] = raw[k][1] = raw[k][2] = 0;
+                if (NU % E_NT == 0 || u < NU) {
+                    const int ry = u / GW, gx = u - ry * GW;
+                    int sy = y0 - R + ry;
+                    if ((unsigned)sy >= (unsigned)a.h) sy = reflect101(sy, a.h);
+                    yuv_load_unit<decltype(lay)>(io, sp, sy, x0 - RA + 4 * gx, a.w, raw[k]);
                 }
-                raw[k][0] = by[0] | (by[1] << 8) | (by[2] << 16) | (by[3] << 24);
-                raw[k][1] = by[4] | (by[5] << 8) | (by[6] << 16) | (by[7] << 24);
-                raw[k][2] = by[8] | (by[9] << 8) | (by[10] << 16) | (by[11] << 24);
+            }
+        });
+    } else {
+#pragma unroll
+        for (int k = 0; k < NRND; k++) {
+            const int u = tid + k * E_NT;
+            raw[k][0] = raw[k][1] = raw[k][2] = 0;
+            if (NU % E_NT == 0 || u < NU) {
+                const int ry = u / GW, gx = u - ry * GW;
+                int sy = y0 - R + ry;
+                if ((unsigned)sy >= (unsigned)a.h) sy = reflect101(sy, a.h);
+                const int px = x0 - RA + 4 * gx;
+                const uint32_t roff = (uint32_t)sy * (uint32_t)a.sstride;
+                if (a.src_aligned && px >= 0 && px + 3 < a.w) {
+                    const uint32_t __attribute__((address_space(1)))* p =
+                        (const uint32_t __attribute__((address_space(1)))*)(src + (roff + (uint32_t)px * 3u));
+                    raw[k][0] = p[0]; raw[k][1] = p[1]; raw[k][2] = p[2];
+                } else {
+                    uint32_t by[12];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        gptr_c q = src + (roff + (uint32_t)reflect101(px + i, a.w) * 3u);
+                        by[3 * i] = q[0]; by[3 * i + 1] = q[1]; by[3 * i + 2] = q[2];
+                    }
+                    raw[k][0] = by[0] | (by[1] << 8) | (by[2] << 16) | (by[3] << 24);
+                    raw[k][1] = by[4] | (by[5] << 8) | (by[6] << 16) | (by[7] << 24);
+                    raw[k][2] = by[8] | (by[9] << 8) | (by[10] << 16) | (by[11] << 24);
+                }
             }
         }
     }
@@ -321,7 +546,8 @@ __global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a) 
         if (NU % E_NT == 0 || u < NU) {
             const int ry = u / GW, gx = u - ry * GW;
             int b[4], g[4], r[4];
-            unpack12(raw[k][0], raw[k][1], raw[k][2], b, g, r);
+            if constexpr (YUV) yuv_unit_to_bgr(raw[k], b, g, r);
+            else unpack12(raw[k][0], raw[k][1], raw[k][2], b, g, r);
             if (has_pre) {
 #pragma unroll
                 for (int i = 0; i < 4; i++) { b[i] = s_pre[b[i]]; g[i] = s_pre[256 + g[i]]; r[i] = s_pre[512 + r[i]]; }
@@ -413,16 +639,21 @@ __global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a) 
             og[i] = has_post ? s_post[256 + idx[rr][1][i]] : idx[rr][1][i];
             orr[i] = has_post ? s_post[512 + idx[rr][2][i]] : idx[rr][2][i];
         }
-        gptr drow = dst + ((uint32_t)(yA + rr) * (uint32_t)a.dstride + (uint32_t)xg * 3u);
-        if (a.dst_aligned && xg + 3 < a.w) {
-            uint32_t d0, d1, d2;
-            pack12(ob, og, orr, d0, d1, d2);
-            uint32_t __attribute__((address_space(1)))* q = (uint32_t __attribute__((address_space(1)))*)drow;
-            q[0] = d0; q[1] = d1; q[2] = d2;
+        if constexpr (YUV) {
+            const YuvPlanesOut dp = yuv_dst_planes(io, blockIdx.z);
+            yuv_dispatch(io, [&](auto lay) { yuv_store_unit<decltype(lay)>(io, dp, yA + rr, xg, a.w, ob, og, orr, rr == 0 || !io.sy); });
         } else {
+            gptr drow = dst + ((uint32_t)(yA + rr) * (uint32_t)a.dstride + (uint32_t)xg * 3u);
+            if (a.dst_aligned && xg + 3 < a.w) {
+                uint32_t d0, d1, d2;
+                pack12(ob, og, orr, d0, d1, d2);
+                uint32_t __attribute__((address_space(1)))* q = (uint32_t __attribute__((address_space(1)))*)drow;
+                q[0] = d0; q[1] = d1; q[2] = d2;
+            } else {
 #pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (xg + i < a.w) { drow[3 * i] = (uint8_t)ob[i]; drow[3 * i + 1] = (uint8_t)og[i]; drow[3 * i + 2] = (uint8_t)orr[i]; }
+                for (int i = 0; i < 4; i++)
+                    if (xg + i < a.w) { drow[3 * i] = (uint8_t)ob[i]; drow[3 * i + 1] = (uint8_t)og[i]; drow[3 * i + 2] = (uint8_t)orr[i]; }
+            }
         }
     }
 }
@@ -446,14 +677,24 @@ struct PointArgs {
     unsigned long long* sums;       // sums kernel: 3 accumulators
 };
 
-template <bool SUMS>
-__global__ __launch_bounds__(256) void enh_point_kernel(const PointArgs a) {
+// IO = NoYuv: interleaved BGR8 frames.  IO = YuvIo: blockIdx.z = surface (a.src, a.dst, a.table, the strides and the alignment flags
+// are not read); a thread covers its four pixels in the 1 << sy rows that share a chroma row (a.rows
+// and blockIdx.y count chroma rows) and holds every sample of that block in registers before it stores the first, so a surface
+// may be converted in place.
+template <bool SUMS, class IO>
+__global__ __launch_bounds__(256) void enh_point_kernel(const PointArgs a, const IO io) {
+    constexpr bool YUV = !std::is_same<IO, NoYuv>::value;
+    static_assert(!(SUMS && YUV), "the channel sums are taken on BGR8 frames");
     __shared__ __attribute__((aligned(16))) uint8_t s_lut[LUT_SLOTS * SLOT_BYTES];   // heavy chains: every slot; else [0,768): the composed table
     __shared__ unsigned long long s_sum[3];
     const int tid = threadIdx.x;
-    const uint8_t* src = a.src;
-    uint8_t* dst = a.dst;
-    if (a.table) { src = (const uint8_t*)a.table[blockIdx.z].src; dst = (uint8_t*)a.table[blockIdx.z].dst; }
+    const uint8_t* src = nullptr;
+    uint8_t* dst = nullptr;
+    if constexpr (!YUV) {
+        src = a.src;
+        dst = a.dst;
+        if (a.table) { src = (const uint8_t*)a.table[blockIdx.z].src; dst = (uint8_t*)a.table[blockIdx.z].dst; }
+    }
     if (a.heavy) load_luts(s_lut, a.luts, tid, 256);
     else compose_luts(a.chain, a.luts, s_lut, tid);
     if (SUMS && tid < 3) s_sum[tid] = 0;
@@ -461,6 +702,39 @@ __global__ __launch_bounds__(256) void enh_point_kernel(const PointArgs a) {
     const int gx = tid & 63, ry = tid >> 6;
     const int px = (blockIdx.x * 64 + gx) * 4;
     unsigned int acc[3] = {0, 0, 0};
+    if constexpr (YUV) {
+        if (px < a.w) {
+            const YuvPlanes sp = yuv_src_planes(io, blockIdx.z);
+            const YuvPlanesOut dp = yuv_dst_planes(io, blockIdx.z);
+            const int crows = a.h >> io.sy;
+            for (int k = 0; k < a.rows / 4; k++) {
+                const int cy = blockIdx.y * a.rows + k * 4 + ry;
+                if (cy >= crows) break;
+                const int y0 = cy << io.sy;
+                uint32_t raw0[3], raw1[3] = {0, 0, 0};
+                yuv_dispatch(io, [&](auto lay) {
+                    yuv_load_unit<decltype(lay)>(io, sp, y0, px, a.w, raw0);
+                    if (io.sy) yuv_load_unit<decltype(lay), false>(io, sp, y0 + 1, px, a.w, raw1);
+                });
+                raw1[1] = raw0[1]; raw1[2] = raw0[2];
+                auto row = [&](const uint32_t (&raw)[3], int y, bool chroma) {
+                    int b[4], g[4], r[4];
+                    yuv_unit_to_bgr(raw, b, g, r);
+                    if (a.heavy) {
+#pragma unroll
+                        for (int i = 0; i < 4; i++) apply_chain(a.chain, s_lut, a.pc, px + i, y, b[i], g[i], r[i]);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; i++) { b[i] = s_lut[b[i]]; g[i] = s_lut[256 + g[i]]; r[i] = s_lut[512 + r[i]]; }
+                    }
+                    yuv_dispatch(io, [&](auto lay) { yuv_store_unit<decltype(lay)>(io, dp, y, px, a.w, b, g, r, chroma); });
+                };
+                row(raw0, y0, true);
+                if (io.sy) row(raw1, y0 + 1, false);
+            }
+        }
+        return;
+    }
     if (px < a.w) {
         for (int k = 0; k < a.rows / 4; k++) {
             const int y = blockIdx.y * a.rows + k * 4 + ry;
@@ -516,6 +790,7 @@ __global__ __launch_bounds__(256) void enh_point_kernel(const PointArgs a) {
         if (tid < 3) atomicAdd(&a.sums[tid], s_sum[tid]);
     }
 }
+
 
 // whiteBalanceCPU (Enhancer.cpp:22-39): table of `ch *= scale` from the channel sums
 __global__ void enh_wb_lut_kernel(const unsigned long long* sums, unsigned long long npix, float alpha, uint8_t* lut) {
@@ -835,29 +1110,31 @@ void gaussian_kernel_q8(int n, double sigma, uint16_t* q) {
     q[n2] = (uint16_t)(256 - 2 * isum);
 }
 
+// io: the YUV form on its surfaces (nullptr: the BGR8 form on a.src / a.dst / a.table)
 template <int R>
-void launch_unsharp_r(const UnsharpArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL(enh_unsharp_kernel<R>, grid, dim3(E_NT), 0, st, a);
+void launch_unsharp_r(const UnsharpArgs& a, const YuvIo* io, dim3 grid, hipStream_t st) {
+    if (io) hipLaunchKernelGGL((enh_unsharp_kernel<R, YuvIo>), grid, dim3(E_NT), 0, st, a, *io);
+    else hipLaunchKernelGGL((enh_unsharp_kernel<R, NoYuv>), grid, dim3(E_NT), 0, st, a, NoYuv{});
 }
 
-void launch_unsharp(int R, const UnsharpArgs& a, dim3 grid, hipStream_t st) {
+void launch_unsharp(int R, const UnsharpArgs& a, const YuvIo* io, dim3 grid, hipStream_t st) {
     switch (R) {
-        case 1: launch_unsharp_r<1>(a, grid, st); break;
-        case 2: launch_unsharp_r<2>(a, grid, st); break;
-        case 3: launch_unsharp_r<3>(a, grid, st); break;
-        case 4: launch_unsharp_r<4>(a, grid, st); break;
-        case 5: launch_unsharp_r<5>(a, grid, st); break;
-        case 6: launch_unsharp_r<6>(a, grid, st); break;
-        case 7: launch_unsharp_r<7>(a, grid, st); break;
-        case 8: launch_unsharp_r<8>(a, grid, st); break;
-        case 9: launch_unsharp_r<9>(a, grid, st); break;
-        case 10: launch_unsharp_r<10>(a, grid, st); break;
-        case 11: launch_unsharp_r<11>(a, grid, st); break;
-        case 12: launch_unsharp_r<12>(a, grid, st); break;
-        case 13: launch_unsharp_r<13>(a, grid, st); break;
-        case 14: launch_unsharp_r<14>(a, grid, st); break;
-        case 15: launch_unsharp_r<15>(a, grid, st); break;
-        default: launch_unsharp_r<16>(a, grid, st); break;
+        case 1: launch_unsharp_r<1>(a, io, grid, st); break;
+        case 2: launch_unsharp_r<2>(a, io, grid, st); break;
+        case 3: launch_unsharp_r<3>(a, io, grid, st); break;
+        case 4: launch_unsharp_r<4>(a, io, grid, st); break;
+        case 5: launch_unsharp_r<5>(a, io, grid, st); break;
+        case 6: launch_unsharp_r<6>(a, io, grid, st); break;
+        case 7: launch_unsharp_r<7>(a, io, grid, st); break;
+        case 8: launch_unsharp_r<8>(a, io, grid, st); break;
+        case 9: launch_unsharp_r<9>(a, io, grid, st); break;
+        case 10: launch_unsharp_r<10>(a, io, grid, st); break;
+        case 11: launch_unsharp_r<11>(a, io, grid, st); break;
+        case 12: launch_unsharp_r<12>(a, io, grid, st); break;
+        case 13: launch_unsharp_r<13>(a, io, grid, st); break;
+        case 14: launch_unsharp_r<14>(a, io, grid, st); break;
+        case 15: launch_unsharp_r<15>(a, io, grid, st); break;
+        default: launch_unsharp_r<16>(a, io, grid, st); break;
     }
 }
 
@@ -884,6 +1161,7 @@ struct vs_enh {
     uint8_t* d_in = nullptr;   uint8_t* d_out = nullptr; size_t io_bytes = 0;
     ImgPair* d_table = nullptr; int table_cap = 0;
     int passes = 0;                     // frame passes of the last apply (for tests / docs)
+    int fused = 0;                      // surfaces of the last vs_enh_apply_yuv_batch_dev that went through the fused launch
 };
 
 namespace {
@@ -894,8 +1172,14 @@ struct Pending {
     bool pre_heavy = false;
 };
 
+// The walk over the stage list (enh_walk) either runs on an object - it launches every pass but the last, which it leaves to the
+// caller as a Pending - or, with e == nullptr, only plans: no device call, no object; it counts the passes and notes of which kind
+// they are (vs_enh_yuv_plan, the decision of vs_enh_apply_yuv_batch_dev).
 struct PlanCtx {
-    vs_enh* e;
+    vs_enh* e;                                   // nullptr: plan only
+    std::string msg;                             // the refusal of a plan
+    int passes = 0;                              // frame passes so far
+    bool stats = false, denoise = false, mid = false;   // a per-frame statistic, the denoiser, an intermediate frame were needed
     const vs_enh_params_c* p;
     int w, h;
     const uint8_t* cur; size_t cur_stride;       // single-frame mode
@@ -911,8 +1195,20 @@ struct PlanCtx {
 
 bool aligned4(const void* p, size_t stride) { return ((uintptr_t)p & 3) == 0 && (stride & 3) == 0; }
 
-int run_pass(PlanCtx& c, Pending& pd, uint8_t* out, size_t out_stride) {
+int plan_fail(PlanCtx& c, int code, const char* msg) {
+    if (c.e) return vs_obj_fail(c.e, code, msg);
+    c.msg = msg;
+    return code;
+}
+void count_passes(PlanCtx& c, int k) {
+    c.passes += k;
+    if (c.e) c.e->passes += k;
+}
+
+// io: the pass reads and writes YUV surfaces (the fused launch; out and out_stride are not used)
+int run_pass(PlanCtx& c, Pending& pd, uint8_t* out, size_t out_stride, const YuvIo* io = nullptr) {
     vs_enh* e = c.e;
+    if (!e) { count_passes(c, 1); return VS_OK; }
     // batch mode: geometry alignment was checked by the caller for all frames
     const bool sal = c.table ? true : aligned4(c.cur, c.cur_stride);
     const bool dal = c.table ? true : aligned4(out, out_stride);
@@ -922,19 +1218,21 @@ int run_pass(PlanCtx& c, Pending& pd, uint8_t* out, size_t out_stride) {
         a.w = c.w; a.h = c.h; a.luts = e->d_luts; a.pre = pd.pre; a.post = pd.post;
         memcpy(a.wq, c.wq, sizeof a.wq); memcpy(a.we, c.we, sizeof a.we); memcpy(a.wo, c.wo, sizeof a.wo);
         a.alpha = c.alpha; a.beta = c.beta; a.src_aligned = sal; a.dst_aligned = dal; a.ident = c.ident;
-        dim3 grid((c.w + E_TW - 1) / E_TW, (c.h + E_TH - 1) / E_TH, c.table ? c.frames : 1);
-        launch_unsharp(c.R, a, grid, e->st);
+        dim3 grid((c.w + E_TW - 1) / E_TW, (c.h + E_TH - 1) / E_TH, c.table || io ? c.frames : 1);
+        launch_unsharp(c.R, a, io, grid, e->st);
     } else {
         PointArgs a{};
         a.src = c.cur; a.dst = out; a.table = c.table; a.sstride = c.cur_stride; a.dstride = out_stride;
         a.w = c.w; a.h = c.h; a.luts = e->d_luts; a.chain = pd.pre; a.pc = c.pc; a.src_aligned = sal; a.dst_aligned = dal;
         a.heavy = pd.pre_heavy; a.sums = nullptr;
-        a.rows = (c.table && c.frames >= 4) ? P_ROWS_LARGE : P_ROWS_SMALL;
-        dim3 grid((c.w + 255) / 256, (c.h + a.rows - 1) / a.rows, c.table ? c.frames : 1);
-        hipLaunchKernelGGL(enh_point_kernel<false>, grid, dim3(256), 0, e->st, a);
+        a.rows = ((c.table || io) && c.frames >= 4) ? P_ROWS_LARGE : P_ROWS_SMALL;
+        const int rows = io ? c.h >> io->sy : c.h;         // the YUV form counts chroma rows
+        dim3 grid((c.w + 255) / 256, (rows + a.rows - 1) / a.rows, c.table || io ? c.frames : 1);
+        if (io) hipLaunchKernelGGL((enh_point_kernel<false, YuvIo>), grid, dim3(256), 0, e->st, a, *io);
+        else hipLaunchKernelGGL((enh_point_kernel<false, NoYuv>), grid, dim3(256), 0, e->st, a, NoYuv{});
     }
     VS_OBJ_HIP(e, hipGetLastError());
-    e->passes++;
+    count_passes(c, 1);
     return VS_OK;
 }
 
@@ -953,7 +1251,9 @@ int other_tmp(PlanCtx& c, size_t bytes, int* which) {
 
 // materialise the pending stages into an intermediate frame (single-frame mode only)
 int flush_mid(PlanCtx& c, Pending& pd) {
-    if (c.table) return vs_obj_fail(c.e, VS_ERR_UNSUPPORTED, "enhancer: this stage list needs an intermediate frame (single-frame entry point only)");
+    if (c.table) return plan_fail(c, VS_ERR_UNSUPPORTED, "enhancer: this stage list needs an intermediate frame (single-frame entry point only)");
+    c.mid = true;
+    if (!c.e) { count_passes(c, 1); pd = Pending{}; return VS_OK; }
     const size_t pitch = ((size_t)c.w * 3 + 3) & ~(size_t)3;
     int k;
     int rc = other_tmp(c, pitch * c.h, &k);
@@ -1003,17 +1303,17 @@ int refresh_luts(vs_enh* e, const vs_enh_params_c* p) {
 int setup_unsharp(PlanCtx& c) {
     const vs_enh_params_c* p = c.p;
     const double sigma = (double)p->blur_sigma;
-    if (!(sigma > 0)) return vs_obj_fail(c.e, VS_ERR_INVALID_ARG, "enhancer: blur_sigma must be > 0 (cv::GaussianBlur asserts)");
+    if (!(sigma > 0)) return plan_fail(c, VS_ERR_INVALID_ARG, "enhancer: blur_sigma must be > 0 (cv::GaussianBlur asserts)");
     const int n = h_rne(sigma * 3 * 2 + 1) | 1;      // GaussianBlur(Size(0,0), sigma) on CV_8U
     const int R = n / 2;
-    if (R > MAX_R) return vs_obj_fail(c.e, VS_ERR_UNSUPPORTED, "enhancer: blur_sigma needs more than 33 taps");
+    if (R > MAX_R) return plan_fail(c, VS_ERR_UNSUPPORTED, "enhancer: blur_sigma needs more than 33 taps");
     uint16_t k[2 * MAX_R + 1];
     gaussian_kernel_q8(n, sigma, k);
     c.ident = k[R] >= 256;                            // all weight on the centre tap: blurred == source
     c.R = std::max(R, 1);
     memset(c.wq, 0, sizeof c.wq); memset(c.we, 0, sizeof c.we); memset(c.wo, 0, sizeof c.wo);
     if (!c.ident) {
-        if (R < 1) return vs_obj_fail(c.e, VS_ERR_UNSUPPORTED, "enhancer: degenerate kernel");
+        if (R < 1) return plan_fail(c, VS_ERR_UNSUPPORTED, "enhancer: degenerate kernel");
         for (int j = 0; j < n; j++) c.wq[j >> 2] |= (uint32_t)(k[j] & 255u) << (8 * (j & 3));
         for (int j = 0; j <= R; j++) {
             const uint32_t e0 = k[2 * j], e1 = (2 * j + 1 < n) ? k[2 * j + 1] : 0;
@@ -1029,22 +1329,26 @@ int setup_unsharp(PlanCtx& c) {
 
 int stats_wb(PlanCtx& c, Pending& pd) {
     vs_enh* e = c.e;
+    c.stats = true;
+    if (!e) { count_passes(c, 1); return VS_OK; }
     VS_OBJ_HIP(e, hipMemsetAsync(e->d_sums, 0, 3 * sizeof(unsigned long long), e->st));
     PointArgs a{};
     a.src = c.cur; a.dst = nullptr; a.table = nullptr; a.sstride = c.cur_stride; a.w = c.w; a.h = c.h; a.luts = e->d_luts;
     a.chain = pd.pre; a.pc = c.pc; a.src_aligned = aligned4(c.cur, c.cur_stride); a.heavy = pd.pre_heavy; a.sums = e->d_sums;
     a.rows = P_ROWS_LARGE;
     dim3 grid((c.w + 255) / 256, (c.h + a.rows - 1) / a.rows, 1);
-    hipLaunchKernelGGL(enh_point_kernel<true>, grid, dim3(256), 0, e->st, a);
+    hipLaunchKernelGGL((enh_point_kernel<true, NoYuv>), grid, dim3(256), 0, e->st, a, NoYuv{});
     hipLaunchKernelGGL(enh_wb_lut_kernel, dim3(1), dim3(256), 0, e->st, e->d_sums, (unsigned long long)c.w * c.h, c.p->wb_strength,
                        e->d_luts + SLOT_WB * SLOT_BYTES);
     VS_OBJ_HIP(e, hipGetLastError());
-    e->passes++;
+    count_passes(c, 1);
     return VS_OK;
 }
 
 int stats_clahe(PlanCtx& c, Pending& pd) {
     vs_enh* e = c.e;
+    c.stats = true;
+    if (!e) { count_passes(c, 1); return VS_OK; }
     const int tiles = c.p->clahe_tile_grid_size;
     int ew = c.w, eh = c.h;
     if (c.w % tiles != 0 || c.h % tiles != 0) { ew = c.w + (tiles - c.w % tiles); eh = c.h + (tiles - c.h % tiles); }
@@ -1067,7 +1371,7 @@ int stats_clahe(PlanCtx& c, Pending& pd) {
     hipLaunchKernelGGL(enh_clahe_lut_kernel, dim3(tiles * tiles), dim3(256), 0, e->st, e->d_hist, clip, lut_scale, e->d_clahe_lut);
     VS_OBJ_HIP(e, hipGetLastError());
     c.pc.tiles = tiles; c.pc.inv_tw = 1.0f / tw; c.pc.inv_th = 1.0f / th; c.pc.clahe_lut = e->d_clahe_lut;
-    e->passes++;
+    count_passes(c, 1);
     return VS_OK;
 }
 
@@ -1110,7 +1414,9 @@ int run_denoise(PlanCtx& c, Pending& pd) {
     vs_enh* e = c.e;
     int rc = VS_OK;
     if (pd.pre.n > 0 || pd.unsharp) { rc = flush_mid(c, pd); if (rc != VS_OK) return rc; }
-    else if (c.table) return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: denoise runs frame by frame");
+    else if (c.table) return plan_fail(c, VS_ERR_UNSUPPORTED, "enhancer: denoise runs frame by frame");
+    c.denoise = true;
+    if (!e) { count_passes(c, 4); return VS_OK; }
     const size_t n = (size_t)c.w * c.h;
     if (e->planes_bytes < 6 * n) {
         VS_OBJ_HIP(e, hipStreamSynchronize(e->st));
@@ -1136,30 +1442,27 @@ int run_denoise(PlanCtx& c, Pending& pd) {
     hipLaunchKernelGGL(enh_merge_lab_kernel, pgrid, dim3(256), 0, e->st, e->d_tabs, L2, ab2, c.w, c.h, e->d_tmp[k], pitch);
     VS_OBJ_HIP(e, hipGetLastError());
     c.cur = e->d_tmp[k]; c.cur_stride = pitch;
-    e->passes += 4;
+    count_passes(c, 4);
     return VS_OK;
 }
 
 enum { ST_WB, ST_CB, ST_CLAHE, ST_VIB, ST_UNSHARP, ST_GAMMA, ST_DENOISE };
 
-// Enhancer::enhanceImage, :138-239.  Frames in HBM; everything is left in flight on e->st.
-int enh_run(vs_enh* e, const vs_enh_params_c* p, const uint8_t* d_src, size_t sstride, const ImgPair* table, int frames, int w, int h,
-            uint8_t* d_dst, size_t dstride) {
+// The stage list of Enhancer::enhanceImage, :138-239, compiled into passes.  c: the object (or none: plan only), the parameters and, on
+// an object, the source.  Every pass but the last has run (or is counted) on return; the last is left in pd.
+int enh_walk(PlanCtx& c, Pending& pd) {
+    vs_enh* e = c.e;
+    const vs_enh_params_c* p = c.p;
     const bool do_denoise = p->enable_denoise && p->denoise_strength > 0.f;
     const bool do_unsharp = p->enable_unsharp && p->sharpness > 0.f;
     const bool do_gamma = std::fabs(p->gamma - 1.f) > 1e-3;
-    if ((unsigned long long)h * sstride >= (1ull << 32) || (unsigned long long)h * dstride >= (1ull << 32))
-        return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: frames of 4 GiB and more are not supported (32-bit row offsets)");
     if (p->enable_clahe && (p->clahe_tile_grid_size < 1 || p->clahe_tile_grid_size > MAX_TILES))
-        return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: clahe_tile_grid_size must be 1..16");
-    if (table && (p->enable_white_balance || p->enable_clahe || do_denoise))
-        return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: batch entry point supports table stages, vibrance and unsharp only");
-    int rc = refresh_luts(e, p);
+        return plan_fail(c, VS_ERR_UNSUPPORTED, "enhancer: clahe_tile_grid_size must be 1..16");
+    if (c.table && (p->enable_white_balance || p->enable_clahe || do_denoise))
+        return plan_fail(c, VS_ERR_UNSUPPORTED, "enhancer: batch entry point supports table stages, vibrance and unsharp only");
+    int rc = e ? refresh_luts(e, p) : VS_OK;
     if (rc != VS_OK) return rc;
-    PlanCtx c{};
-    c.e = e; c.p = p; c.w = w; c.h = h; c.cur = d_src; c.cur_stride = sstride; c.table = table; c.frames = frames;
-    c.dst = d_dst; c.dst_stride = dstride;
-    c.pc.tabs = e->d_tabs; c.pc.clahe_lut = e->d_clahe_lut; c.pc.vib_alpha = p->vibrance_strength; c.pc.tiles = 1;
+    c.pc.tabs = e ? e->d_tabs : nullptr; c.pc.clahe_lut = e ? e->d_clahe_lut : nullptr; c.pc.vib_alpha = p->vibrance_strength; c.pc.tiles = 1;
     c.pc.inv_tw = c.pc.inv_th = 1.f;
     if (do_unsharp) { rc = setup_unsharp(c); if (rc != VS_OK) return rc; }
     int stages[8], ns = 0;
@@ -1180,8 +1483,8 @@ int enh_run(vs_enh* e, const vs_enh_params_c* p, const uint8_t* d_src, size_t ss
         if (p->enable_clahe) stages[ns++] = ST_CLAHE;
         if (do_gamma) stages[ns++] = ST_GAMMA;
     }
-    e->passes = 0;
-    Pending pd{};
+    if (e) e->passes = 0;
+    pd = Pending{};
     for (int i = 0; i < ns; i++) {
         switch (stages[i]) {
             case ST_CB: rc = add_point(c, pd, OP_LUT, SLOT_CB); break;
@@ -1205,7 +1508,36 @@ int enh_run(vs_enh* e, const vs_enh_params_c* p, const uint8_t* d_src, size_t ss
         }
         if (rc != VS_OK) return rc;
     }
+    return VS_OK;
+}
+
+// Enhancer::enhanceImage, :138-239.  Frames in HBM; everything is left in flight on e->st.
+int enh_run(vs_enh* e, const vs_enh_params_c* p, const uint8_t* d_src, size_t sstride, const ImgPair* table, int frames, int w, int h,
+            uint8_t* d_dst, size_t dstride) {
+    if ((unsigned long long)h * sstride >= (1ull << 32) || (unsigned long long)h * dstride >= (1ull << 32))
+        return vs_obj_fail(e, VS_ERR_UNSUPPORTED, "enhancer: frames of 4 GiB and more are not supported (32-bit row offsets)");
+    PlanCtx c{};
+    c.e = e; c.p = p; c.w = w; c.h = h; c.cur = d_src; c.cur_stride = sstride; c.table = table; c.frames = frames;
+    c.dst = d_dst; c.dst_stride = dstride;
+    Pending pd{};
+    const int rc = enh_walk(c, pd);
+    if (rc != VS_OK) return rc;
     return run_pass(c, pd, d_dst, dstride);
+}
+
+// What a stage list comes to, without an object or a device: rc != VS_OK is the refusal enh_run would give (text in c.msg).  The fused
+// YUV launch takes a plan of ONE pass that needs no per-frame statistic, no denoiser and no intermediate frame - its stages then
+// fit the pre / post chains of pd - and, where that pass is the unsharp pass, no surface in place: a tile reads its neighbours'
+// samples, which another workgroup may already have overwritten.  (The point pass owns whole chroma blocks per thread.)
+int enh_plan(const vs_enh_params_c* p, PlanCtx& c, Pending& pd) {
+    c = PlanCtx{};
+    c.p = p;
+    const int rc = enh_walk(c, pd);
+    if (rc != VS_OK) return rc;
+    return run_pass(c, pd, nullptr, 0);
+}
+bool plan_is_fused(const PlanCtx& c, const Pending& pd, bool in_place) {
+    return c.passes == 1 && !c.stats && !c.denoise && !c.mid && !(pd.unsharp && in_place);
 }
 
 // d_in / d_out: the object's own BGR8 frames (vs_enh_apply's staging, vs_enh_apply_yuv_dev's conversions), grown on demand
@@ -1218,6 +1550,23 @@ int enh_grow_io(vs_enh* e, size_t bytes) {
     VS_OBJ_HIP(e, hipMalloc((void**)&e->d_in, bytes));
     VS_OBJ_HIP(e, hipMalloc((void**)&e->d_out, bytes));
     e->io_bytes = bytes;
+    return VS_OK;
+}
+
+// vs_enh_apply_yuv_dev behind its checks - the definition of the enhancer on a YUV surface: conversion into the object's scratch,
+// the stages, conversion back
+int enh_yuv_three_calls(vs_enh* e, const vs_enh_params_c* p, const PixFmt& yf, const void* d_surface, const I420Layout& li, void* d_out,
+                        const I420Layout& lo, int w, int h) {
+    const PixFmt& bgr = *pixfmt(VS_FMT_BGR8);
+    const size_t pitch = ((size_t)w * 3 + 3) & ~(size_t)3;
+    VS_TRY(enh_grow_io(e, pitch * h));
+    const void* const src[1] = {d_surface};
+    void* const dst[1] = {d_out};
+    void* const bgr_in[1] = {e->d_in};
+    void* const bgr_out[1] = {e->d_out};
+    VS_OBJ_TRY(e, launch_cvt_yuv_to_rgb(yf, src, li, bgr, bgr_in, pitch, 1, w, h, e->st));
+    VS_OBJ_TRY(e, enh_run(e, p, e->d_in, pitch, nullptr, 1, w, h, e->d_out, pitch));
+    VS_OBJ_TRY(e, launch_cvt_rgb_to_yuv(bgr, bgr_out, pitch, yf, dst, lo, 1, w, h, e->st));
     return VS_OK;
 }
 
@@ -1371,15 +1720,58 @@ int vs_enh_apply_yuv_dev(vs_enh* e, const vs_enh_params_c* p, int yuv_fmt, const
         cvt_check_yuv("vs_enh_apply_yuv_dev", yuv_fmt, dst, 1, out, w, h, &lo, &msg) != VS_OK)
         return vs_obj_fail(e, VS_ERR_INVALID_ARG, msg);
     VS_OBJ_HIP(e, hipSetDevice(e->device));
+    return enh_yuv_three_calls(e, p, *pixfmt(yuv_fmt), d_surface, li, d_out, lo, w, h);
+}
+
+int vs_enh_yuv_plan(const vs_enh_params_c* p, int yuv_fmt, int in_place) {
+    const PixFmt* f = pixfmt(yuv_fmt);
+    if (!p || !f || f->kind == PIX_INTERLEAVED) return -VS_ERR_INVALID_ARG;
+    PlanCtx c;
+    Pending pd;
+    const int rc = enh_plan(p, c, pd);
+    if (rc != VS_OK) return -rc;
+    return plan_is_fused(c, pd, in_place != 0) ? 1 : 0;
+}
+
+int vs_enh_last_fused(const vs_enh* e) { return e ? e->fused : 0; }
+
+int vs_enh_apply_yuv_batch_dev(vs_enh* e, const vs_enh_params_c* p, int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in,
+                               void* const* d_outs, const vs_i420_layout* out, int n, int w, int h) {
+    static const char call[] = "vs_enh_apply_yuv_batch_dev";
+    if (!e) return VS_ERR_INVALID_ARG;
+    e->fused = 0;
+    if (!p) return vs_obj_fail(e, VS_ERR_INVALID_ARG, std::string(call) + ": null pointer");
+    I420Layout li, lo;
+    std::string msg;
+    if (cvt_check_yuv(call, yuv_fmt, d_surfaces, n, in, w, h, &li, &msg) != VS_OK ||
+        cvt_check_yuv(call, yuv_fmt, d_outs, n, out, w, h, &lo, &msg) != VS_OK)
+        return vs_obj_fail(e, VS_ERR_INVALID_ARG, msg);
     const PixFmt& yf = *pixfmt(yuv_fmt);
-    const PixFmt& bgr = *pixfmt(VS_FMT_BGR8);
-    const size_t pitch = ((size_t)w * 3 + 3) & ~(size_t)3;
-    VS_TRY(enh_grow_io(e, pitch * h));
-    void* const bgr_in[1] = {e->d_in};
-    void* const bgr_out[1] = {e->d_out};
-    VS_OBJ_TRY(e, launch_cvt_yuv_to_rgb(yf, src, li, bgr, bgr_in, pitch, 1, w, h, e->st));
-    VS_OBJ_TRY(e, enh_run(e, p, e->d_in, pitch, nullptr, 1, w, h, e->d_out, pitch));
-    VS_OBJ_TRY(e, launch_cvt_rgb_to_yuv(bgr, bgr_out, pitch, yf, dst, lo, 1, w, h, e->st));
+    bool in_place = false;
+    for (int k = 0; k < n; k++) in_place = in_place || d_outs[k] == d_surfaces[k];
+    PlanCtx c;
+    Pending pd;
+    const int rc = enh_plan(p, c, pd);                      // what the stage list refuses, before any device call
+    if (rc != VS_OK) return vs_obj_fail(e, rc, std::string(call) + ": " + yf.name + ": " + c.msg);
+    // 32-bit row offsets inside a plane
+    const unsigned long long span = (unsigned long long)h * std::max(std::max(li.pitch, li.cpitch), std::max(lo.pitch, lo.cpitch));
+    VS_OBJ_HIP(e, hipSetDevice(e->device));
+    if (!plan_is_fused(c, pd, in_place) || span >= (1ull << 32)) {
+        for (int k = 0; k < n; k++) VS_TRY(enh_yuv_three_calls(e, p, yf, d_surfaces[k], li, d_outs[k], lo, w, h));
+        return VS_OK;
+    }
+    VS_TRY(refresh_luts(e, p));
+    YuvIo io{};
+    for (int k = 0; k < n; k++) { io.src[k] = (const uint8_t*)d_surfaces[k]; io.dst[k] = (uint8_t*)d_outs[k]; }
+    io.su = li.u; io.sv = li.v; io.du = lo.u; io.dv = lo.v;
+    io.spitch = (uint32_t)li.pitch; io.scpitch = (uint32_t)li.cpitch; io.dpitch = (uint32_t)lo.pitch; io.dcpitch = (uint32_t)lo.cpitch;
+    io.sb = yf.sample_bytes; io.il = yf.luma_uv(); io.sx = yf.sx; io.sy = yf.sy;
+    io.shift = yf.sample_bytes == 2 ? (yf.luma_uv() ? 8 : yf.bits - 8) : 0;
+    c.e = e; c.w = w; c.h = h; c.frames = n;
+    c.pc.tabs = e->d_tabs; c.pc.clahe_lut = e->d_clahe_lut;
+    e->passes = 0;
+    VS_TRY(run_pass(c, pd, nullptr, 0, &io));
+    e->fused = n;
     return VS_OK;
 }
 

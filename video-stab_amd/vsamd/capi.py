@@ -477,6 +477,9 @@ class VsLib:
             L.vs_op_cvt_yuv_to_rgb.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
             L.vs_op_cvt_rgb_to_yuv.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int, vp]
             L.vs_enh_apply_yuv_dev.argtypes = [vp, ep, C.c_int, vp, lp, vp, lp, C.c_int, C.c_int]
+            L.vs_enh_apply_yuv_batch_dev.argtypes = [vp, ep, C.c_int, C.POINTER(vp), lp, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int]
+            L.vs_enh_last_fused.argtypes = [vp]
+            L.vs_enh_yuv_plan.argtypes = [ep, C.c_int, C.c_int]
         except AttributeError:      # a library of an earlier build (A/B measurements)
             pass
 
@@ -869,6 +872,11 @@ class VsLib:
                 outs = [o.reshape(fmt_frame_rows(yuv_fmt, h), w) for o in outs]
         return outs[0] if single else outs
 
+    def enh_yuv_plan(self, params, yuv_fmt, in_place=False):
+        """vs_enh_yuv_plan (host only): 1 = Enhancer.apply_yuv_batch_dev would take the fused launch, 0 = the three calls per surface,
+        < 0 = minus the status of the refusal.  params: VsEnhParams or None."""
+        return self.lib.vs_enh_yuv_plan(C.byref(params) if params is not None else None, yuv_fmt, int(bool(in_place)))
+
     def canvas_op(self):
         return CanvasOp(self)
 
@@ -1229,6 +1237,38 @@ class Enhancer:
             d_in.free()
             d_out.free()
         return out if out_layout else out.reshape(fmt_frame_rows(yuv_fmt, h), w)
+
+    def apply_yuv_batch_dev(self, params, yuv_fmt, surfaces, w, h, layout=None, out_layout=None, out_size=None, in_place=False, fill=0xA5,
+                            raw=False):
+        """vs_enh_apply_yuv_batch_dev on a list of up to 32 surfaces of one geometry (each as for apply_yuv_dev) -> a list: per surface
+        the packed (rows, w) surface or, with a layout, the flat buffer, in the format's dtype.  raw=True: the whole destination as
+        bytes instead - out_size + 16 of them prefilled with `fill` (in_place: the source's buffer and 16 bytes of `fill` behind it)."""
+        f = PIXFMT[yuv_fmt]
+        srcs = [np.ascontiguousarray(s) for s in surfaces]
+        n = len(srcs)
+        out_layout = out_layout or layout
+        lin = I420LayoutC(*(layout or (f.sample_bytes * w, 0, 0, 0)))
+        lout = I420LayoutC(*(out_layout or (f.sample_bytes * w, 0, 0, 0)))
+        guard = np.full(16, fill, np.uint8)
+        d_in = [DevBuf.from_array(self.vs, np.concatenate([s.reshape(-1).view(np.uint8), guard]) if in_place else s) for s in srcs]
+        size = srcs[0].nbytes if in_place else out_size or yuv_surface_bytes(yuv_fmt, w, h, *(out_layout or ()))
+        d_out = d_in if in_place else [DevBuf.from_array(self.vs, np.full(size + 16, fill, np.uint8)) for _ in range(n)]
+        try:
+            self._check(self.lib.vs_enh_apply_yuv_batch_dev(self.h, C.byref(params), yuv_fmt, _ptr_array(d_in), C.byref(lin), _ptr_array(d_out),
+                                                            C.byref(lout), n, w, h))
+            self.sync()
+            outs = [d.download((size + 16,), np.uint8) for d in d_out]
+        finally:
+            for d in d_in + ([] if in_place else d_out):
+                d.free()
+        if not raw:
+            outs = [o[:size].view(fmt_dtype(yuv_fmt)) for o in outs]
+            if not out_layout:
+                outs = [o.reshape(fmt_frame_rows(yuv_fmt, h), w) for o in outs]
+        return outs
+
+    def last_fused(self):
+        return self.lib.vs_enh_last_fused(self.h)
 
     def apply_batch_dev(self, params, d_ins, d_outs, w, h, stride, out_stride):
         n = len(d_ins)
