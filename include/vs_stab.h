@@ -43,8 +43,10 @@ extern "C" {
  *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan; the compositing operators vs_op_copy_make_border, vs_op_fade_blend,
  *    vs_op_fade_update and vs_op_canvas_create / apply / info / destroy; colour conversion on the device: vs_op_cvt_yuv_to_rgb,
  *    vs_op_cvt_rgb_to_yuv and vs_enh_apply_yuv_dev; the enhancer on a batch of YUV surfaces in one fused launch:
- *    vs_enh_apply_yuv_batch_dev, vs_enh_last_fused and vs_enh_yuv_plan (new entry points, new values and new structs only: no
- *    existing struct or entry point changed, so the version stays). */
+ *    vs_enh_apply_yuv_batch_dev, vs_enh_last_fused and vs_enh_yuv_plan; the colour space of the conversions: struct
+ *    vs_cvt_colorimetry with vs_op_cvt_yuv_to_rgb_cs, vs_op_cvt_rgb_to_yuv_cs, vs_enh_set_yuv_colorimetry, vs_cvt_coefficients and
+ *    vs_cvt_colorimetry_guess (new entry points, new values and new structs only: no existing struct or entry point changed, so
+ *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
 typedef enum vs_status {
@@ -928,6 +930,54 @@ int vs_op_cvt_yuv_to_rgb(int yuv_fmt, const void* const* d_surfaces, const vs_i4
 int vs_op_cvt_rgb_to_yuv(int rgb_fmt, const void* const* d_rgb, size_t rgb_stride, int yuv_fmt, void* const* d_surfaces,
                          const vs_i420_layout* out, int n, int w, int h, void* stream);
 
+/* ---- the colour space of a conversion: matrix, range, and how RGB -> YUV takes the chroma of a block ----------------------------
+ * The two calls above speak BT.601 limited range with the top-left pixel of a block as its chroma.  Decoder surfaces of 1280 x 720
+ * and above are BT.709 (HEVC / AV1 1080p, 2160p) or BT.2020 (UHD, 10-bit masters); MJPEG cameras and screen capture are full range.
+ * A descriptor names the space; a null pointer and the all-zero struct both mean what the calls above compute, bit for bit. */
+enum vs_cvt_matrix { VS_CVT_MATRIX_BT601 = 0, VS_CVT_MATRIX_BT709 = 1, VS_CVT_MATRIX_BT2020 = 2 };   /* BT.2020 non-constant luminance */
+enum vs_cvt_range  { VS_CVT_RANGE_LIMITED = 0, VS_CVT_RANGE_FULL = 1 };
+enum vs_cvt_chroma { VS_CVT_CHROMA_TOPLEFT = 0, VS_CVT_CHROMA_MEAN = 1 };                            /* RGB -> YUV only */
+typedef struct vs_cvt_colorimetry { int32_t matrix, range, chroma_down, reserved; } vs_cvt_colorimetry;  /* reserved must be 0 */
+/* Definition.  The shape is the one stated above: 32-bit integers, >> an arithmetic shift, sat = clamp to 0 .. 255, H = 1 << 19,
+ * the chroma sample at (x >> sx, y >> sy) on the way up (nearest), the same byte view of 16-bit samples.  With fifteen integers
+ * y_off, CY, RV, GV, GU, BU, YR, YG, YB, UR, UG, UB, VR, VG, VB:
+ *   YUV -> RGB:  Y' = max(0, Y - y_off) * CY;  u = U - 128;  v = V - 128
+ *                R = sat((Y' + H + RV*v) >> 20)   G = sat((Y' + H - GV*v - GU*u) >> 20)   B = sat((Y' + H + BU*u) >> 20)
+ *   RGB -> YUV:  Y = sat((YR*R + YG*G + YB*B + H + (y_off << 20)) >> 20)
+ *                U = sat((UR*R + UG*G + UB*B + H + (128 << 20)) >> 20)      V likewise with VR, VG, VB
+ * (BT.601, limited): the integers are OpenCV's, those written out above - they are not derived, so the default cannot move.
+ * The other five combinations: from the standard's Kr, Kb (Kg = 1 - Kr - Kb) in exact rational arithmetic, each value scaled by
+ * 2^20 and rounded half away from zero:
+ *   scales    ys = 219/255, cs = 224/255, y_off = 16 in limited range; ys = cs = 1, y_off = 0 in full range
+ *   YUV->RGB  CY = 1/ys, RV = 2(1-Kr)/cs, BU = 2(1-Kb)/cs, GV = 2(1-Kr)*Kr/Kg/cs, GU = 2(1-Kb)*Kb/Kg/cs
+ *   luma      YR, YG, YB = Kr*ys, Kg*ys, Kb*ys
+ *   U         UR = -Kr/(2(1-Kb))*cs, UG = -Kg/(2(1-Kb))*cs, UB = cs/2
+ *   V         VR = cs/2, VG = -Kg/(2(1-Kr))*cs, VB = -Kb/(2(1-Kr))*cs
+ *   Kr, Kb    BT.601 0.299, 0.114;  BT.709 0.2126, 0.0722;  BT.2020 0.2627, 0.0593
+ * Mean chroma (VS_CVT_CHROMA_MEAN, RGB -> YUV; luma is unchanged): with s = sx + sy and SR, SG, SB the sums of R, G, B over the
+ * (1 << sx) x (1 << sy) pixels of a chroma block,
+ *   U = sat((UR*SR + UG*SG + UB*SB + (H << s) + (128 << (20 + s))) >> (20 + s))      V likewise
+ * For 4:4:4 that is the top-left rule.  The sample sits at the block centre; left-sited filters and interpolation on the way up
+ * are not built.  Nothing overflows 32 bits: the largest intermediate is 2^30 (mean chroma, full range, s = 2).
+ * chroma_down is IGNORED by the YUV -> RGB direction (any value of the enum is accepted there and changes nothing).
+ *
+ * vs_op_cvt_yuv_to_rgb_cs / vs_op_cvt_rgb_to_yuv_cs: the calls above with the descriptor in front of `stream`; the same refusals,
+ * the same one launch for n = 1 .. 32; the calls above are these with cs = NULL.  Further refusals, VS_ERR_INVALID_ARG with a
+ * text in vs_last_error that names the call and the field, decided before any device call (so a bad descriptor on a machine
+ * without a device gives VS_ERR_INVALID_ARG, not VS_ERR_NO_DEVICE, and the refused call writes and queues nothing): matrix, range
+ * or chroma_down outside its enum; reserved != 0. */
+int vs_op_cvt_yuv_to_rgb_cs(int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in, int rgb_fmt, void* const* d_rgb,
+                            size_t rgb_stride, int n, int w, int h, const vs_cvt_colorimetry* cs, void* stream);
+int vs_op_cvt_rgb_to_yuv_cs(int rgb_fmt, const void* const* d_rgb, size_t rgb_stride, int yuv_fmt, void* const* d_surfaces,
+                            const vs_i420_layout* out, int n, int w, int h, const vs_cvt_colorimetry* cs, void* stream);
+/* Host only, needs no device: the integers the kernels use for a descriptor (NULL = the default), in the order
+ * y_off, CY, RV, GV, GU, BU, YR, YG, YB, UR, UG, UB, VR, VG, VB, 0.  VS_ERR_INVALID_ARG for a bad descriptor or a null `out`. */
+int vs_cvt_coefficients(const vs_cvt_colorimetry* cs, int32_t out[16]);
+/* Host only: the common convention for video whose container carries no tag - h > 576: BT.709 limited, otherwise BT.601 limited;
+ * never BT.2020, never full range; chroma_down = VS_CVT_CHROMA_TOPLEFT.  A convenience for the caller: the library itself never
+ * guesses. */
+void vs_cvt_colorimetry_guess(int w, int h, vs_cvt_colorimetry* out);
+
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */
 void vs_enh_params_default(vs_enh_params_c* p);
@@ -955,8 +1005,9 @@ int vs_enh_apply_batch_dev(vs_enh* e, const vs_enh_params_c* params, const void*
                            void* const* d_outs, int n, int w, int h, size_t stride,
                            size_t out_stride);
 /* The enhancer on one YUV surface in HBM (yuv_fmt, layouts and their rules as for vs_op_cvt_yuv_to_rgb).  The result is BY DEFINITION
- * the composition of three calls: vs_op_cvt_yuv_to_rgb(..., VS_FMT_BGR8) into the object's scratch (rows padded to a multiple of 4
- * bytes), the stages of vs_enh_apply_dev, vs_op_cvt_rgb_to_yuv into d_out.  All three run on the object's stream and are left in
+ * the composition of three calls: vs_op_cvt_yuv_to_rgb_cs(..., VS_FMT_BGR8) into the object's scratch (rows padded to a multiple of 4
+ * bytes), the stages of vs_enh_apply_dev, vs_op_cvt_rgb_to_yuv_cs into d_out - both with the object's colorimetry
+ * (vs_enh_set_yuv_colorimetry; none set: the default, BT.601 limited range and top-left chroma).  All three run on the object's stream and are left in
  * flight (vs_enh_sync).  d_out may be d_surface.  The two conversions are lossy - limited range, chroma decimated to one sample per
  * block, the low bits of 16-bit samples dropped - so an enhancer with neutral settings does NOT return the surface bit for bit.
  * Refusals: those of the two operators and of vs_enh_apply_dev, with the text in vs_enh_last_error.  (The batch form, with a fused
@@ -985,6 +1036,13 @@ int vs_enh_last_fused(const vs_enh* e);
  * (-VS_ERR_INVALID_ARG: null params, not a YUV surface format, blur_sigma; -VS_ERR_UNSUPPORTED: clahe_tile_grid_size, a blur
  * of more than 33 taps). */
 int vs_enh_yuv_plan(const vs_enh_params_c* params, int yuv_fmt, int in_place);
+/* The colour space of the object's YUV calls - a setting of the object, NULL = the default (BT.601 limited, top-left chroma).
+ * vs_enh_apply_yuv_dev and vs_enh_apply_yuv_batch_dev use it for BOTH of their conversions: the definition of vs_enh_apply_yuv_dev
+ * stays the composition of three calls, now vs_op_cvt_yuv_to_rgb_cs and vs_op_cvt_rgb_to_yuv_cs with this descriptor, and the fused
+ * launch is taken for exactly the stage lists for which it is taken with the default (vs_enh_yuv_plan does not depend on the
+ * descriptor).  Refusals as for vs_op_cvt_yuv_to_rgb_cs: VS_ERR_INVALID_ARG with a text in vs_last_error and vs_enh_last_error that
+ * names this call and the field; a refused call leaves the setting as it was.  Needs no device call. */
+int vs_enh_set_yuv_colorimetry(vs_enh* e, const vs_cvt_colorimetry* cs);
 int vs_enh_sync(vs_enh* e);
 /* passes over the frame (kernel launches that read it) the last apply needed */
 int vs_enh_last_passes(const vs_enh* e);

@@ -1,5 +1,6 @@
 // The compositing stages as operators (include/vs_stab.h): vs_op_copy_make_border, vs_op_fade_blend, vs_op_fade_update, the
-// vs_op_canvas_* object and the colour conversions vs_op_cvt_yuv_to_rgb / vs_op_cvt_rgb_to_yuv.  Nothing is computed here: each
+// vs_op_canvas_* object and the colour conversions vs_op_cvt_yuv_to_rgb[_cs] / vs_op_cvt_rgb_to_yuv[_cs], with the integers of
+// their colour spaces (cvt_resolve, vs_cvt_coefficients, vs_cvt_colorimetry_guess).  Nothing is computed here: each
 // entry checks its arguments and calls what the pipeline calls (launch_make_border, launch_fade_blend, launch_fade_update of
 // k_traj.hip; canvas_apply of k_canvas.hip; launch_cvt_* of k_cvt.hip).
 #include <cstring>
@@ -7,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "cvt_px.h"
 #include "stab_internal.h"
 
 using namespace vsd;
@@ -35,6 +37,38 @@ int cvt_check_rgb(const char* call, int rgb_fmt, const void* const* rgb, size_t 
 }  // namespace
 
 namespace vsd {
+
+// The fifteen integers per (matrix, range), in the order of vs_cvt_coefficients.  (BT.601, limited): OpenCV's, not derived - they
+// are cvt_coef_default() of cvt_px.h, and the zeros here are never read.  The other five: the rule of include/vs_stab.h - from Kr, Kb in exact rational arithmetic, scaled by 2^20, rounded half away from
+// zero; tests/test_cvt_colorimetry_cpu.py recomputes them with fractions.Fraction and holds this table to the rule.
+static const int32_t CVT_TABLE[3][2][15] = {
+    {{0},
+     {0, 1048576, 1470104, 748826, 360853, 1858077, 313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262}},
+    {{16, 1220945, 1879825, 558796, 223607, 2215014, 191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230},
+     {0, 1048576, 1651297, 490864, 196424, 1945738, 222927, 749942, 75707, -120138, -404150, 524288, 524288, -476214, -48074}},
+    {{16, 1220945, 1760217, 682019, 196426, 2245811, 236572, 610567, 53402, -128614, -331937, 460551, 460551, -423510, -37041},
+     {0, 1048576, 1546230, 599107, 172546, 1972791, 275461, 710935, 62181, -146413, -377875, 524288, 524288, -482120, -42168}},
+};
+
+int cvt_resolve(const char* call, const vs_cvt_colorimetry* cs, CvtCoef* k, std::string* msg) {
+    static const vs_cvt_colorimetry dflt = {VS_CVT_MATRIX_BT601, VS_CVT_RANGE_LIMITED, VS_CVT_CHROMA_TOPLEFT, 0};
+    if (!cs) cs = &dflt;
+    auto fail = [&](const char* field, int32_t v, const char* want) {
+        *msg = std::string(call) + ": colorimetry: " + field + " = " + std::to_string(v) + " " + want;
+        return (int)VS_ERR_INVALID_ARG;
+    };
+    if (cs->matrix < VS_CVT_MATRIX_BT601 || cs->matrix > VS_CVT_MATRIX_BT2020) return fail("matrix", cs->matrix, "is not a vs_cvt_matrix (0 .. 2)");
+    if (cs->range < VS_CVT_RANGE_LIMITED || cs->range > VS_CVT_RANGE_FULL) return fail("range", cs->range, "is not a vs_cvt_range (0, 1)");
+    if (cs->chroma_down < VS_CVT_CHROMA_TOPLEFT || cs->chroma_down > VS_CVT_CHROMA_MEAN)
+        return fail("chroma_down", cs->chroma_down, "is not a vs_cvt_chroma (0, 1)");
+    if (cs->reserved != 0) return fail("reserved", cs->reserved, "must be 0");
+    static_assert(sizeof(CvtCoef) == 16 * sizeof(int32_t) && offsetof(CvtCoef, mean) == 15 * sizeof(int32_t), "fifteen integers and the chroma rule");
+    *k = cvt_coef_default();
+    if (cs->matrix != VS_CVT_MATRIX_BT601 || cs->range != VS_CVT_RANGE_LIMITED)
+        memcpy(k, CVT_TABLE[cs->matrix][cs->range], 15 * sizeof(int32_t));
+    k->mean = cs->chroma_down == VS_CVT_CHROMA_MEAN;
+    return VS_OK;
+}
 
 int cvt_check_yuv(const char* call, int yuv_fmt, const void* const* surfaces, int n, const vs_i420_layout* lay, int w, int h, I420Layout* l,
                   std::string* msg) {
@@ -116,28 +150,61 @@ int vs_op_fade_update(void* d_hist, const void* d_stab, size_t stab_stride, int 
     return launch_fade_update((uint8_t*)d_hist, (const uint8_t*)d_stab, stab_stride, row_bytes, rows, (hipStream_t)stream);
 }
 
-int vs_op_cvt_yuv_to_rgb(int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in, int rgb_fmt, void* const* d_rgb, size_t rgb_stride,
-                         int n, int w, int h, void* stream) {
-    static const char call[] = "vs_op_cvt_yuv_to_rgb";
+int vs_op_cvt_yuv_to_rgb_cs(int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in, int rgb_fmt, void* const* d_rgb, size_t rgb_stride,
+                            int n, int w, int h, const vs_cvt_colorimetry* cs, void* stream) {
+    static const char call[] = "vs_op_cvt_yuv_to_rgb";       // refusals name the operator, with or without _cs
     I420Layout l;
     const PixFmt* rf = nullptr;
+    CvtCoef k;
     std::string msg;
-    if (cvt_check_yuv(call, yuv_fmt, d_surfaces, n, in, w, h, &l, &msg) != VS_OK || cvt_check_rgb(call, rgb_fmt, d_rgb, rgb_stride, n, w, &rf, &msg) != VS_OK)
+    if (cvt_check_yuv(call, yuv_fmt, d_surfaces, n, in, w, h, &l, &msg) != VS_OK || cvt_check_rgb(call, rgb_fmt, d_rgb, rgb_stride, n, w, &rf, &msg) != VS_OK ||
+        cvt_resolve(call, cs, &k, &msg) != VS_OK)
         return refuse(VS_ERR_INVALID_ARG, msg.c_str());
     VS_TRY(ensure_device());
-    return launch_cvt_yuv_to_rgb(*pixfmt(yuv_fmt), d_surfaces, l, *rf, d_rgb, rgb_stride, n, w, h, (hipStream_t)stream);
+    return launch_cvt_yuv_to_rgb(*pixfmt(yuv_fmt), d_surfaces, l, *rf, d_rgb, rgb_stride, n, w, h, k, (hipStream_t)stream);
+}
+
+int vs_op_cvt_rgb_to_yuv_cs(int rgb_fmt, const void* const* d_rgb, size_t rgb_stride, int yuv_fmt, void* const* d_surfaces, const vs_i420_layout* out,
+                            int n, int w, int h, const vs_cvt_colorimetry* cs, void* stream) {
+    static const char call[] = "vs_op_cvt_rgb_to_yuv";
+    I420Layout l;
+    const PixFmt* rf = nullptr;
+    CvtCoef k;
+    std::string msg;
+    if (cvt_check_yuv(call, yuv_fmt, d_surfaces, n, out, w, h, &l, &msg) != VS_OK || cvt_check_rgb(call, rgb_fmt, d_rgb, rgb_stride, n, w, &rf, &msg) != VS_OK ||
+        cvt_resolve(call, cs, &k, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    VS_TRY(ensure_device());
+    return launch_cvt_rgb_to_yuv(*rf, d_rgb, rgb_stride, *pixfmt(yuv_fmt), d_surfaces, l, n, w, h, k, (hipStream_t)stream);
+}
+
+int vs_op_cvt_yuv_to_rgb(int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in, int rgb_fmt, void* const* d_rgb, size_t rgb_stride,
+                         int n, int w, int h, void* stream) {
+    return vs_op_cvt_yuv_to_rgb_cs(yuv_fmt, d_surfaces, in, rgb_fmt, d_rgb, rgb_stride, n, w, h, nullptr, stream);
 }
 
 int vs_op_cvt_rgb_to_yuv(int rgb_fmt, const void* const* d_rgb, size_t rgb_stride, int yuv_fmt, void* const* d_surfaces, const vs_i420_layout* out,
                          int n, int w, int h, void* stream) {
-    static const char call[] = "vs_op_cvt_rgb_to_yuv";
-    I420Layout l;
-    const PixFmt* rf = nullptr;
+    return vs_op_cvt_rgb_to_yuv_cs(rgb_fmt, d_rgb, rgb_stride, yuv_fmt, d_surfaces, out, n, w, h, nullptr, stream);
+}
+
+int vs_cvt_coefficients(const vs_cvt_colorimetry* cs, int32_t out[16]) {
+    if (!out) return refuse(VS_ERR_INVALID_ARG, "vs_cvt_coefficients: null pointer");
+    CvtCoef k;
     std::string msg;
-    if (cvt_check_yuv(call, yuv_fmt, d_surfaces, n, out, w, h, &l, &msg) != VS_OK || cvt_check_rgb(call, rgb_fmt, d_rgb, rgb_stride, n, w, &rf, &msg) != VS_OK)
-        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
-    VS_TRY(ensure_device());
-    return launch_cvt_rgb_to_yuv(*rf, d_rgb, rgb_stride, *pixfmt(yuv_fmt), d_surfaces, l, n, w, h, (hipStream_t)stream);
+    if (cvt_resolve("vs_cvt_coefficients", cs, &k, &msg) != VS_OK) return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    memcpy(out, &k, 15 * sizeof(int32_t));
+    out[15] = 0;
+    return VS_OK;
+}
+
+void vs_cvt_colorimetry_guess(int w, int h, vs_cvt_colorimetry* out) {
+    (void)w;                          // the convention goes by the height alone
+    if (!out) return;
+    out->matrix = h > 576 ? VS_CVT_MATRIX_BT709 : VS_CVT_MATRIX_BT601;
+    out->range = VS_CVT_RANGE_LIMITED;
+    out->chroma_down = VS_CVT_CHROMA_TOPLEFT;
+    out->reserved = 0;
 }
 
 int vs_op_canvas_create(vs_canvas_op** out) {

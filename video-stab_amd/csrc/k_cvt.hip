@@ -1,7 +1,8 @@
-// Colour conversion between YUV surfaces and interleaved 8-bit RGB in HBM: vs_op_cvt_yuv_to_rgb, vs_op_cvt_rgb_to_yuv (comp_op.cpp)
-// and the two ends of vs_enh_apply_yuv_dev (k_enhance.hip).  The definition is in include/vs_stab.h (ITU-R BT.601 limited range, the
-// fixed-point path of OpenCV's COLOR_YUV2BGR_NV12 / _I420 and COLOR_BGR2YUV_I420; tests/cvtref.py states it in numpy).  The per-pixel
-// arithmetic is in cvt_px.h, shared with the enhancer's YUV form.
+// Colour conversion between YUV surfaces and interleaved 8-bit RGB in HBM: vs_op_cvt_yuv_to_rgb[_cs], vs_op_cvt_rgb_to_yuv[_cs]
+// (comp_op.cpp) and the two ends of vs_enh_apply_yuv_dev (k_enhance.hip).  The definition is in include/vs_stab.h (the fixed-point
+// path of OpenCV's COLOR_YUV2BGR_NV12 / _I420 and COLOR_BGR2YUV_I420 with the integers of a colour space; tests/cvtref.py and
+// tests/cvtref_cs.py state it in numpy).  The per-pixel arithmetic is in cvt_px.h, shared with the enhancer's YUV form; the
+// colour space is data (CvtArgs::k), not a kernel instance.
 //
 // Both kernels stream: a lane covers CVT_PX consecutive pixels in the 1 << SY rows that share a chroma row, so every chroma sample
 // is read (or computed and written) once; a wave covers 512 pixels of those rows, a block four chroma rows; blockIdx.z = surface,
@@ -33,6 +34,7 @@ struct CvtArgs {
     int w, h;
     int shift;                     // 16-bit samples: byte = min(sample >> shift, 255), sample = byte << shift
     int rgb_order;                 // 1: R first (RGB8, RGBA8)
+    CvtCoef k;                     // the integers of the colour space; k.mean: chroma of a block from the sums over its pixels
 };
 
 // N samples of SB bytes at p, the first `valid` of them inside the row, as bytes
@@ -171,7 +173,7 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_yuv_to_rgb_kernel(const C
     }
     int ru[NC], gu[NC], bu[NC];                 // the chroma terms, with the rounding half
 #pragma unroll
-    for (int k = 0; k < NC; k++) cvt_chroma_terms(u[k], v[k], ru[k], gu[k], bu[k]);
+    for (int k = 0; k < NC; k++) cvt_chroma_terms(a.k, u[k], v[k], ru[k], gu[k], bu[k]);
 #pragma unroll
     for (int r = 0; r < (1 << SY); r++) {
         const size_t y = ((size_t)cy << SY) + r;
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_yuv_to_rgb_kernel(const C
 #pragma unroll
         for (int i = 0; i < CVT_PX; i++) {
             int R, G, B;
-            cvt_yuv_px(yy[i], ru[i >> SX], gu[i >> SX], bu[i >> SX], R, G, B);
+            cvt_yuv_px(a.k, yy[i], ru[i >> SX], gu[i >> SX], bu[i >> SX], R, G, B);
             c[i][0] = a.rgb_order ? R : B;
             c[i][1] = G;
             c[i][2] = a.rgb_order ? B : R;
@@ -200,6 +202,10 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_rgb_to_yuv_kernel(const C
     constexpr int NC = CVT_PX >> SX;
     const int cvalid = valid >> SX;
     const size_t cx0 = (size_t)(x0 >> SX);
+    // chroma: of the top-left pixel of each block (stored with the block's first row), or - mean - of the sums over the block's
+    // pixels (stored behind its last row).  4:4:4 has one pixel per block: the two rules are one.
+    const bool mean = (SX + SY) != 0 && a.k.mean;
+    int sum[NC][3];
 #pragma unroll
     for (int r = 0; r < (1 << SY); r++) {
         const size_t y = ((size_t)cy << SY) + r;
@@ -208,16 +214,28 @@ __global__ __launch_bounds__(CVT_BX * CVT_BY) void cvt_rgb_to_yuv_kernel(const C
 #pragma unroll
         for (int i = 0; i < CVT_PX; i++) {
             const int R = a.rgb_order ? c[i][0] : c[i][2], G = c[i][1], B = a.rgb_order ? c[i][2] : c[i][0];
-            yy[i] = cvt_luma(R, G, B);
+            yy[i] = cvt_luma(a.k, R, G, B);
         }
         store_run<SB, CVT_PX>(d + y * a.pitch + (size_t)x0 * SB, valid, a.shift, yy);
-        if (r == 0) {                            // chroma: the top-left pixel of each block, no averaging
-            int u[NC], v[NC];
+        if (r == 0 || mean) {
 #pragma unroll
             for (int k = 0; k < NC; k++) {
                 const int i = k << SX;
-                const int R = a.rgb_order ? c[i][0] : c[i][2], G = c[i][1], B = a.rgb_order ? c[i][2] : c[i][0];
-                cvt_chroma(R, G, B, u[k], v[k]);
+                int t[3] = {c[i][0], c[i][1], c[i][2]};
+                if (mean) {
+                    if constexpr (SX) { t[0] += c[i + 1][0]; t[1] += c[i + 1][1]; t[2] += c[i + 1][2]; }
+                    if (r) { t[0] += sum[k][0]; t[1] += sum[k][1]; t[2] += sum[k][2]; }
+                }
+                sum[k][0] = t[0]; sum[k][1] = t[1]; sum[k][2] = t[2];
+            }
+        }
+        if (mean ? r == (1 << SY) - 1 : r == 0) {
+            const int sh = mean ? SX + SY : 0;
+            int u[NC], v[NC];
+#pragma unroll
+            for (int k = 0; k < NC; k++) {
+                const int R = a.rgb_order ? sum[k][0] : sum[k][2], G = sum[k][1], B = a.rgb_order ? sum[k][2] : sum[k][0];
+                cvt_chroma(a.k, R, G, B, sh, u[k], v[k]);
             }
             if constexpr (IL) {
                 int uv[2 * NC];
@@ -248,8 +266,9 @@ void launch_layout(const PixFmt& yf, dim3 grid, hipStream_t st, const CvtArgs& a
 
 template <bool TO_RGB>
 int launch_cvt(const PixFmt& yf, const I420Layout& l, const PixFmt& rf, size_t rgb_stride, const void* const* src, void* const* dst, int n, int w,
-               int h, hipStream_t st) {
+               int h, const CvtCoef& k, hipStream_t st) {
     CvtArgs a{};
+    a.k = k;
     for (int k = 0; k < n; k++) { a.src[k] = (const uint8_t*)src[k]; a.dst[k] = (uint8_t*)dst[k]; }
     a.pitch = l.pitch; a.cpitch = l.cpitch; a.u = l.u; a.v = l.v;
     a.rgb_stride = rgb_stride;
@@ -271,13 +290,13 @@ int launch_cvt(const PixFmt& yf, const I420Layout& l, const PixFmt& rf, size_t r
 }  // namespace
 
 int launch_cvt_yuv_to_rgb(const PixFmt& yf, const void* const* surfaces, const I420Layout& l, const PixFmt& rf, void* const* rgb, size_t rgb_stride,
-                          int n, int w, int h, hipStream_t st) {
-    return launch_cvt<true>(yf, l, rf, rgb_stride, surfaces, rgb, n, w, h, st);
+                          int n, int w, int h, const CvtCoef& k, hipStream_t st) {
+    return launch_cvt<true>(yf, l, rf, rgb_stride, surfaces, rgb, n, w, h, k, st);
 }
 
 int launch_cvt_rgb_to_yuv(const PixFmt& rf, const void* const* rgb, size_t rgb_stride, const PixFmt& yf, void* const* surfaces, const I420Layout& l,
-                          int n, int w, int h, hipStream_t st) {
-    return launch_cvt<false>(yf, l, rf, rgb_stride, rgb, surfaces, n, w, h, st);
+                          int n, int w, int h, const CvtCoef& k, hipStream_t st) {
+    return launch_cvt<false>(yf, l, rf, rgb_stride, rgb, surfaces, n, w, h, k, st);
 }
 
 }  // namespace vsd

@@ -14,9 +14,9 @@
 //     histograms) get one extra read-only pass that evaluates the pending per-pixel stages on the fly;
 //   * vibrance (HSV round trip) and CLAHE (Lab round trip + tile-table interpolation) are per-pixel
 //     stages of enh_point_kernel;
-//   * both frame kernels also exist in a form that reads and writes YUV surfaces (IO = YuvIo; the conversion arithmetic of
-//     cvt_px.h on the way into the pass and out of it): a stage list that is ONE pass runs on up to 32 decoder surfaces
-//     in one launch, without a BGR8 frame in between (vs_enh_apply_yuv_batch_dev).
+//   * both frame kernels also exist in a form that reads and writes YUV surfaces (IO = YuvIo, or YuvIoCs under a colorimetry
+//     descriptor; the conversion arithmetic of cvt_px.h on the way into the pass and out of it): a stage list that is ONE pass
+//     runs on up to 32 decoder surfaces in one launch, without a BGR8 frame in between (vs_enh_apply_yuv_batch_dev).
 // Nothing is computed on the host except 256-entry tables that depend on parameters only (the gamma
 // table needs libm's powf, as in the reference) and the colour-conversion tables built once per object.
 #include <algorithm>
@@ -247,6 +247,23 @@ struct YuvIo {
     uint32_t spitch, scpitch, dpitch, dcpitch;
     int32_t sb, il, sx, sy, shift;        // bytes per sample; (U, V) interleaved; chroma plane (w >> sx) x (h >> sy); 16-bit: byte = min(sample >> shift, 255)
 };
+// ... with a colour space of its own (vs_enh_set_yuv_colorimetry).  The default - BT.601 limited, top-left chroma - keeps YuvIo and
+// with it the literal constants and the code without block sums: reading the integers from the arguments cost the two kernels
+// 4 % and 10 % (DESIGN section 8 "Colorimetry"), which the surfaces that need no descriptor do not pay.
+struct YuvIoCs : YuvIo {
+    CvtCoef k;
+};
+// the integers an IO converts with, and whether chroma is the mean of a block
+template <class IO>
+__device__ __forceinline__ CvtCoef yuv_coef(const IO& io) {
+    if constexpr (std::is_same<IO, YuvIoCs>::value) return io.k;
+    else return cvt_coef_default();
+}
+template <class IO>
+__device__ __forceinline__ bool yuv_mean(const IO& io) {
+    if constexpr (std::is_same<IO, YuvIoCs>::value) return io.k.mean != 0;
+    else return false;
+}
 
 typedef const uint16_t __attribute__((address_space(1)))* gptr16_c;
 typedef uint16_t __attribute__((address_space(1)))* gptr16;
@@ -373,42 +390,61 @@ __device__ __forceinline__ void yuv_load_unit(const YuvIo& io, const YuvPlanes& 
 }
 
 // ... and as four B, G, R pixels (the YUV -> BGR formulas of the header)
-__device__ __forceinline__ void yuv_unit_to_bgr(const uint32_t (&raw)[3], int* b, int* g, int* r) {
+__device__ __forceinline__ void yuv_unit_to_bgr(const CvtCoef& k, const uint32_t (&raw)[3], int* b, int* g, int* r) {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         int ru, gu, bu;
-        cvt_chroma_terms((int)((raw[1] >> (8 * i)) & 255u), (int)((raw[2] >> (8 * i)) & 255u), ru, gu, bu);
-        cvt_yuv_px((int)((raw[0] >> (8 * i)) & 255u), ru, gu, bu, r[i], g[i], b[i]);
+        cvt_chroma_terms(k, (int)((raw[1] >> (8 * i)) & 255u), (int)((raw[2] >> (8 * i)) & 255u), ru, gu, bu);
+        cvt_yuv_px(k, (int)((raw[0] >> (8 * i)) & 255u), ru, gu, bu, r[i], g[i], b[i]);
     }
 }
 
-// Four results of luma row `row` at pixels px .. px + 3 (px a multiple of 4) through the RGB -> YUV formulas: Y of every pixel; with
-// `chroma`, U and V of the pixel at the left of each chroma block of this row (the caller passes the top row of a block).
-template <class L>
-__device__ __forceinline__ void yuv_store_unit(const YuvIo& io, const YuvPlanesOut& d, int row, int px, int w, const int* b, const int* g,
-                                               const int* r, bool chroma) {
+// Four results of luma row `row` at pixels px .. px + 3 (px a multiple of 4) through the RGB -> YUV formulas: Y of every pixel, and
+// the chroma of the blocks these pixels lie in.  top / last: `row` is the first / the last row of its chroma blocks (both with
+// sy = 0).  Top-left rule: U and V of the pixel at the left of each block, stored with the top row.  Mean rule (yuv_mean(io)): `sum`
+// carries the R, G, B sums of the two blocks from the top row to the last, where U and V are stored; the caller keeps it across
+// the rows of a block and reads nothing from it.
+template <class L, class IO>
+__device__ __forceinline__ void yuv_store_unit(const IO& io, const YuvPlanesOut& d, int row, int px, int w, const int* b, const int* g,
+                                               const int* r, bool top, bool last, int (&sum)[2][3]) {
     constexpr int SB = L::SB;
+    const CvtCoef k = yuv_coef(io);
     const int valid = min(4, w - px);
     uint32_t y4 = 0;
 #pragma unroll
-    for (int i = 0; i < 4; i++) y4 |= (uint32_t)cvt_luma(r[i], g[i], b[i]) << (8 * i);
+    for (int i = 0; i < 4; i++) y4 |= (uint32_t)cvt_luma(k, r[i], g[i], b[i]) << (8 * i);
     yuv_st<SB, 4>(d.y + ((uint32_t)row * io.dpitch + (uint32_t)px * SB), valid, io.shift, y4);
-    if (!chroma) return;
+    const bool mean = yuv_mean(io);
+    if (!mean && !top) return;
     const uint32_t coff = (uint32_t)(row >> io.sy) * io.dcpitch;
-    if constexpr (L::LAY == YL_FULL) {
+    if constexpr (L::LAY == YL_FULL) {                 // one pixel per block: the two rules are one
         uint32_t u4 = 0, v4 = 0;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             int u, v;
-            cvt_chroma(r[i], g[i], b[i], u, v);
+            cvt_chroma(k, r[i], g[i], b[i], 0, u, v);
             u4 |= (uint32_t)u << (8 * i); v4 |= (uint32_t)v << (8 * i);
         }
         yuv_st<SB, 4>(d.u + (coff + (uint32_t)px * SB), valid, io.shift, u4);
         yuv_st<SB, 4>(d.v + (coff + (uint32_t)px * SB), valid, io.shift, v4);
     } else {
+        if (mean) {
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int tr = r[2 * j] + r[2 * j + 1], tg = g[2 * j] + g[2 * j + 1], tb = b[2 * j] + b[2 * j + 1];
+                sum[j][0] = top ? tr : sum[j][0] + tr;
+                sum[j][1] = top ? tg : sum[j][1] + tg;
+                sum[j][2] = top ? tb : sum[j][2] + tb;
+            }
+            if (!last) return;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; j++) { sum[j][0] = r[2 * j]; sum[j][1] = g[2 * j]; sum[j][2] = b[2 * j]; }
+        }
+        const int sh = mean ? 1 + io.sy : 0;
         int u0, v0, u1, v1;
-        cvt_chroma(r[0], g[0], b[0], u0, v0);
-        cvt_chroma(r[2], g[2], b[2], u1, v1);
+        cvt_chroma(k, sum[0][0], sum[0][1], sum[0][2], sh, u0, v0);
+        cvt_chroma(k, sum[1][0], sum[1][1], sum[1][2], sh, u1, v1);
         if constexpr (L::LAY == YL_UV) {
             yuv_st<SB, 4>(d.u + (coff + (uint32_t)px * SB), 2 * (valid >> 1), io.shift,
                           (uint32_t)u0 | ((uint32_t)v0 << 8) | ((uint32_t)u1 << 16) | ((uint32_t)v1 << 24));
@@ -546,7 +582,7 @@ __global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a, 
         if (NU % E_NT == 0 || u < NU) {
             const int ry = u / GW, gx = u - ry * GW;
             int b[4], g[4], r[4];
-            if constexpr (YUV) yuv_unit_to_bgr(raw[k], b, g, r);
+            if constexpr (YUV) yuv_unit_to_bgr(yuv_coef(io), raw[k], b, g, r);
             else unpack12(raw[k][0], raw[k][1], raw[k][2], b, g, r);
             if (has_pre) {
 #pragma unroll
@@ -629,6 +665,7 @@ __global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a, 
             idx[1][c][i] = __builtin_amdgcn_cvt_pk_u8_f32(__fmaf_rn(fb[i], a.alpha, __fmul_rn(bb[i], a.beta)), 0, 0);
         }
     }
+    int csum[2][3] = {};                           // YUV, mean chroma: the block sums, carried from the top row to the last
 #pragma unroll
     for (int rr = 0; rr < 2; rr++) {
         if (yA + rr >= a.h) break;
@@ -641,7 +678,7 @@ __global__ __launch_bounds__(E_NT) void enh_unsharp_kernel(const UnsharpArgs a, 
         }
         if constexpr (YUV) {
             const YuvPlanesOut dp = yuv_dst_planes(io, blockIdx.z);
-            yuv_dispatch(io, [&](auto lay) { yuv_store_unit<decltype(lay)>(io, dp, yA + rr, xg, a.w, ob, og, orr, rr == 0 || !io.sy); });
+            yuv_dispatch(io, [&](auto lay) { yuv_store_unit<decltype(lay)>(io, dp, yA + rr, xg, a.w, ob, og, orr, rr == 0 || !io.sy, rr == 1 || !io.sy, csum); });
         } else {
             gptr drow = dst + ((uint32_t)(yA + rr) * (uint32_t)a.dstride + (uint32_t)xg * 3u);
             if (a.dst_aligned && xg + 3 < a.w) {
@@ -717,9 +754,10 @@ __global__ __launch_bounds__(256) void enh_point_kernel(const PointArgs a, const
                     if (io.sy) yuv_load_unit<decltype(lay), false>(io, sp, y0 + 1, px, a.w, raw1);
                 });
                 raw1[1] = raw0[1]; raw1[2] = raw0[2];
-                auto row = [&](const uint32_t (&raw)[3], int y, bool chroma) {
+                int csum[2][3] = {};                // mean chroma: the block sums, carried from the top row to the last
+                auto row = [&](const uint32_t (&raw)[3], int y, bool top, bool last) {
                     int b[4], g[4], r[4];
-                    yuv_unit_to_bgr(raw, b, g, r);
+                    yuv_unit_to_bgr(yuv_coef(io), raw, b, g, r);
                     if (a.heavy) {
 #pragma unroll
                         for (int i = 0; i < 4; i++) apply_chain(a.chain, s_lut, a.pc, px + i, y, b[i], g[i], r[i]);
@@ -727,10 +765,10 @@ __global__ __launch_bounds__(256) void enh_point_kernel(const PointArgs a, const
 #pragma unroll
                         for (int i = 0; i < 4; i++) { b[i] = s_lut[b[i]]; g[i] = s_lut[256 + g[i]]; r[i] = s_lut[512 + r[i]]; }
                     }
-                    yuv_dispatch(io, [&](auto lay) { yuv_store_unit<decltype(lay)>(io, dp, y, px, a.w, b, g, r, chroma); });
+                    yuv_dispatch(io, [&](auto lay) { yuv_store_unit<decltype(lay)>(io, dp, y, px, a.w, b, g, r, top, last, csum); });
                 };
-                row(raw0, y0, true);
-                if (io.sy) row(raw1, y0 + 1, false);
+                row(raw0, y0, true, !io.sy);
+                if (io.sy) row(raw1, y0 + 1, false, true);
             }
         }
         return;
@@ -1111,13 +1149,19 @@ void gaussian_kernel_q8(int n, double sigma, uint16_t* q) {
 }
 
 // io: the YUV form on its surfaces (nullptr: the BGR8 form on a.src / a.dst / a.table)
+// io: YUV surfaces; the default colour space takes the instance with the literal constants
+bool yuv_is_default(const YuvIoCs& io) {
+    const CvtCoef d = cvt_coef_default();
+    return memcmp(&io.k, &d, sizeof d) == 0;
+}
 template <int R>
-void launch_unsharp_r(const UnsharpArgs& a, const YuvIo* io, dim3 grid, hipStream_t st) {
-    if (io) hipLaunchKernelGGL((enh_unsharp_kernel<R, YuvIo>), grid, dim3(E_NT), 0, st, a, *io);
+void launch_unsharp_r(const UnsharpArgs& a, const YuvIoCs* io, dim3 grid, hipStream_t st) {
+    if (io && yuv_is_default(*io)) hipLaunchKernelGGL((enh_unsharp_kernel<R, YuvIo>), grid, dim3(E_NT), 0, st, a, static_cast<const YuvIo&>(*io));
+    else if (io) hipLaunchKernelGGL((enh_unsharp_kernel<R, YuvIoCs>), grid, dim3(E_NT), 0, st, a, *io);
     else hipLaunchKernelGGL((enh_unsharp_kernel<R, NoYuv>), grid, dim3(E_NT), 0, st, a, NoYuv{});
 }
 
-void launch_unsharp(int R, const UnsharpArgs& a, const YuvIo* io, dim3 grid, hipStream_t st) {
+void launch_unsharp(int R, const UnsharpArgs& a, const YuvIoCs* io, dim3 grid, hipStream_t st) {
     switch (R) {
         case 1: launch_unsharp_r<1>(a, io, grid, st); break;
         case 2: launch_unsharp_r<2>(a, io, grid, st); break;
@@ -1162,6 +1206,7 @@ struct vs_enh {
     ImgPair* d_table = nullptr; int table_cap = 0;
     int passes = 0;                     // frame passes of the last apply (for tests / docs)
     int fused = 0;                      // surfaces of the last vs_enh_apply_yuv_batch_dev that went through the fused launch
+    CvtCoef yuv_k = cvt_coef_default(); // the colour space of the YUV calls (vs_enh_set_yuv_colorimetry), resolved
 };
 
 namespace {
@@ -1206,7 +1251,7 @@ void count_passes(PlanCtx& c, int k) {
 }
 
 // io: the pass reads and writes YUV surfaces (the fused launch; out and out_stride are not used)
-int run_pass(PlanCtx& c, Pending& pd, uint8_t* out, size_t out_stride, const YuvIo* io = nullptr) {
+int run_pass(PlanCtx& c, Pending& pd, uint8_t* out, size_t out_stride, const YuvIoCs* io = nullptr) {
     vs_enh* e = c.e;
     if (!e) { count_passes(c, 1); return VS_OK; }
     // batch mode: geometry alignment was checked by the caller for all frames
@@ -1228,7 +1273,8 @@ int run_pass(PlanCtx& c, Pending& pd, uint8_t* out, size_t out_stride, const Yuv
         a.rows = ((c.table || io) && c.frames >= 4) ? P_ROWS_LARGE : P_ROWS_SMALL;
         const int rows = io ? c.h >> io->sy : c.h;         // the YUV form counts chroma rows
         dim3 grid((c.w + 255) / 256, (rows + a.rows - 1) / a.rows, c.table || io ? c.frames : 1);
-        if (io) hipLaunchKernelGGL((enh_point_kernel<false, YuvIo>), grid, dim3(256), 0, e->st, a, *io);
+        if (io && yuv_is_default(*io)) hipLaunchKernelGGL((enh_point_kernel<false, YuvIo>), grid, dim3(256), 0, e->st, a, static_cast<const YuvIo&>(*io));
+        else if (io) hipLaunchKernelGGL((enh_point_kernel<false, YuvIoCs>), grid, dim3(256), 0, e->st, a, *io);
         else hipLaunchKernelGGL((enh_point_kernel<false, NoYuv>), grid, dim3(256), 0, e->st, a, NoYuv{});
     }
     VS_OBJ_HIP(e, hipGetLastError());
@@ -1564,9 +1610,9 @@ int enh_yuv_three_calls(vs_enh* e, const vs_enh_params_c* p, const PixFmt& yf, c
     void* const dst[1] = {d_out};
     void* const bgr_in[1] = {e->d_in};
     void* const bgr_out[1] = {e->d_out};
-    VS_OBJ_TRY(e, launch_cvt_yuv_to_rgb(yf, src, li, bgr, bgr_in, pitch, 1, w, h, e->st));
+    VS_OBJ_TRY(e, launch_cvt_yuv_to_rgb(yf, src, li, bgr, bgr_in, pitch, 1, w, h, e->yuv_k, e->st));
     VS_OBJ_TRY(e, enh_run(e, p, e->d_in, pitch, nullptr, 1, w, h, e->d_out, pitch));
-    VS_OBJ_TRY(e, launch_cvt_rgb_to_yuv(bgr, bgr_out, pitch, yf, dst, lo, 1, w, h, e->st));
+    VS_OBJ_TRY(e, launch_cvt_rgb_to_yuv(bgr, bgr_out, pitch, yf, dst, lo, 1, w, h, e->yuv_k, e->st));
     return VS_OK;
 }
 
@@ -1735,6 +1781,19 @@ int vs_enh_yuv_plan(const vs_enh_params_c* p, int yuv_fmt, int in_place) {
 
 int vs_enh_last_fused(const vs_enh* e) { return e ? e->fused : 0; }
 
+int vs_enh_set_yuv_colorimetry(vs_enh* e, const vs_cvt_colorimetry* cs) {
+    CvtCoef k;
+    std::string msg;
+    if (cvt_resolve("vs_enh_set_yuv_colorimetry", cs, &k, &msg) != VS_OK) {          // before the object: the text reaches vs_last_error without one
+        if (e) return vs_obj_fail(e, VS_ERR_INVALID_ARG, msg);
+        set_last_error(msg);
+        return VS_ERR_INVALID_ARG;
+    }
+    if (!e) { set_last_error("vs_enh_set_yuv_colorimetry: null object"); return VS_ERR_INVALID_ARG; }
+    e->yuv_k = k;
+    return VS_OK;
+}
+
 int vs_enh_apply_yuv_batch_dev(vs_enh* e, const vs_enh_params_c* p, int yuv_fmt, const void* const* d_surfaces, const vs_i420_layout* in,
                                void* const* d_outs, const vs_i420_layout* out, int n, int w, int h) {
     static const char call[] = "vs_enh_apply_yuv_batch_dev";
@@ -1761,12 +1820,13 @@ int vs_enh_apply_yuv_batch_dev(vs_enh* e, const vs_enh_params_c* p, int yuv_fmt,
         return VS_OK;
     }
     VS_TRY(refresh_luts(e, p));
-    YuvIo io{};
+    YuvIoCs io{};
     for (int k = 0; k < n; k++) { io.src[k] = (const uint8_t*)d_surfaces[k]; io.dst[k] = (uint8_t*)d_outs[k]; }
     io.su = li.u; io.sv = li.v; io.du = lo.u; io.dv = lo.v;
     io.spitch = (uint32_t)li.pitch; io.scpitch = (uint32_t)li.cpitch; io.dpitch = (uint32_t)lo.pitch; io.dcpitch = (uint32_t)lo.cpitch;
     io.sb = yf.sample_bytes; io.il = yf.luma_uv(); io.sx = yf.sx; io.sy = yf.sy;
     io.shift = yf.sample_bytes == 2 ? (yf.luma_uv() ? 8 : yf.bits - 8) : 0;
+    io.k = e->yuv_k;
     c.e = e; c.w = w; c.h = h; c.frames = n;
     c.pc.tabs = e->d_tabs; c.pc.clahe_lut = e->d_clahe_lut;
     e->passes = 0;

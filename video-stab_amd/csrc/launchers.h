@@ -98,11 +98,15 @@ constexpr int CVT_MAX_SURFACES = 32;        // of one launch: their pointers are
 // call and the format.
 int cvt_check_yuv(const char* call, int yuv_fmt, const void* const* surfaces, int n, const vs_i420_layout* lay, int w, int h, I420Layout* l,
                   std::string* msg);
+// The integers of a colour space as the kernels take them (cvt_px.h).  cvt_resolve: what the conversions refuse about a descriptor
+// (a field outside its enum, reserved != 0; *msg names the call and the field), else its integers; cs == nullptr: the default.
+struct CvtCoef;
+int cvt_resolve(const char* call, const vs_cvt_colorimetry* cs, CvtCoef* k, std::string* msg);
 // n <= CVT_MAX_SURFACES surfaces of one geometry and layout in one launch (grid z = surface); rf: BGR8, RGB8, BGRA8 or RGBA8
 int launch_cvt_yuv_to_rgb(const PixFmt& yf, const void* const* surfaces, const I420Layout& l, const PixFmt& rf, void* const* rgb, size_t rgb_stride,
-                          int n, int w, int h, hipStream_t st);
+                          int n, int w, int h, const CvtCoef& k, hipStream_t st);
 int launch_cvt_rgb_to_yuv(const PixFmt& rf, const void* const* rgb, size_t rgb_stride, const PixFmt& yf, void* const* surfaces, const I420Layout& l,
-                          int n, int w, int h, hipStream_t st);
+                          int n, int w, int h, const CvtCoef& k, hipStream_t st);
 
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,

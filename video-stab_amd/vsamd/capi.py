@@ -480,6 +480,13 @@ class VsLib:
             L.vs_enh_apply_yuv_batch_dev.argtypes = [vp, ep, C.c_int, C.POINTER(vp), lp, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int]
             L.vs_enh_last_fused.argtypes = [vp]
             L.vs_enh_yuv_plan.argtypes = [ep, C.c_int, C.c_int]
+            csp = C.POINTER(CvtColorimetry)
+            L.vs_op_cvt_yuv_to_rgb_cs.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.c_int, csp, vp]
+            L.vs_op_cvt_rgb_to_yuv_cs.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int, csp, vp]
+            L.vs_enh_set_yuv_colorimetry.argtypes = [vp, csp]
+            L.vs_cvt_coefficients.argtypes = [csp, i32p]
+            L.vs_cvt_colorimetry_guess.argtypes = [C.c_int, C.c_int, csp]
+            L.vs_cvt_colorimetry_guess.restype = None
         except AttributeError:      # a library of an earlier build (A/B measurements)
             pass
 
@@ -817,11 +824,27 @@ class VsLib:
         self.sync()
         return d_h.download((hist.size,), np.uint8)
 
-    def cvt_yuv_to_rgb(self, yuv_fmt, surfaces, w, h, rgb_fmt=FMT_BGR8, layout=None, rgb_stride=None, raw=False, fill=0xA5):
+    def cvt_coefficients(self, colorimetry=None):
+        """vs_cvt_coefficients (host only): the sixteen integers of a descriptor - y_off, CY, RV, GV, GU, BU, YR, YG, YB, UR, UG, UB,
+        VR, VG, VB, 0.  colorimetry: None, a CvtColorimetry or (matrix, range[, chroma_down[, reserved]])."""
+        out = np.zeros(16, np.int32)
+        self.check(self.lib.vs_cvt_coefficients(_cs_ref(colorimetry), _p(out, i32p)))
+        return out
+
+    def cvt_colorimetry_guess(self, w, h):
+        """vs_cvt_colorimetry_guess (host only): the convention for untagged video -> CvtColorimetry."""
+        cs = CvtColorimetry(-1, -1, -1, -1)
+        self.lib.vs_cvt_colorimetry_guess(w, h, C.byref(cs))
+        return cs
+
+    def cvt_yuv_to_rgb(self, yuv_fmt, surfaces, w, h, rgb_fmt=FMT_BGR8, layout=None, rgb_stride=None, raw=False, fill=0xA5, colorimetry=None,
+                       use_cs=False):
         """vs_op_cvt_yuv_to_rgb.  surfaces: one surface of w x h pixels or a list of up to 32, converted in one launch - packed frames
         ((rows, w) arrays of the format's dtype: synth.yuv_pack, synth.nv12_to_i420, the NV12 / P010 arrays) or flat buffers in
         `layout` = (pitch, c_pitch, u_off, v_off) in bytes, 0 = the default of a field (NV12 / P010: u_off = the interleaved plane).
-        -> (h, w, cn) uint8 per surface; raw=True: the whole destination instead, h * rgb_stride + 16 bytes prefilled with `fill`."""
+        -> (h, w, cn) uint8 per surface; raw=True: the whole destination instead, h * rgb_stride + 16 bytes prefilled with `fill`.
+        colorimetry: None (the entry point without a descriptor), a CvtColorimetry or (matrix, range[, chroma_down]) through
+        vs_op_cvt_yuv_to_rgb_cs; use_cs=True: the _cs entry point with a null descriptor."""
         f, cn = PIXFMT[yuv_fmt], PIXFMT[rgb_fmt].cn
         srcs, single = _surface_list(surfaces)
         n = len(srcs)
@@ -831,7 +854,11 @@ class VsLib:
         d_in = [DevBuf.from_array(self, s) for s in srcs]
         d_out = [DevBuf.from_array(self, np.full(nbytes, fill, np.uint8)) for _ in range(n)]
         try:
-            self.check(self.lib.vs_op_cvt_yuv_to_rgb(yuv_fmt, _ptr_array(d_in), C.byref(lay), rgb_fmt, _ptr_array(d_out), stride, n, w, h, None))
+            if colorimetry is None and not use_cs:
+                self.check(self.lib.vs_op_cvt_yuv_to_rgb(yuv_fmt, _ptr_array(d_in), C.byref(lay), rgb_fmt, _ptr_array(d_out), stride, n, w, h, None))
+            else:
+                self.check(self.lib.vs_op_cvt_yuv_to_rgb_cs(yuv_fmt, _ptr_array(d_in), C.byref(lay), rgb_fmt, _ptr_array(d_out), stride, n, w, h,
+                                                            _cs_ref(colorimetry), None))
             self.sync()
             outs = [d.download((nbytes,), np.uint8) for d in d_out]
         finally:
@@ -841,10 +868,12 @@ class VsLib:
             outs = [o[:h * stride].reshape(h, stride)[:, :w * cn].reshape(h, w, cn).copy() for o in outs]
         return outs[0] if single else outs
 
-    def cvt_rgb_to_yuv(self, frames, yuv_fmt, rgb_fmt=FMT_BGR8, layout=None, size=None, rgb_stride=None, raw=False, fill=0xA5):
+    def cvt_rgb_to_yuv(self, frames, yuv_fmt, rgb_fmt=FMT_BGR8, layout=None, size=None, rgb_stride=None, raw=False, fill=0xA5, colorimetry=None,
+                       use_cs=False):
         """vs_op_cvt_rgb_to_yuv.  frames: one (h, w, cn) uint8 frame or a list of up to 32 of one size, converted in one launch.
         -> per frame the packed surface ((rows, w) array of the format's dtype) or, with a `layout` (as above) and `size` in bytes, the
-        flat buffer of that layout; raw=True: the whole destination as bytes instead, `size` + 16 of them prefilled with `fill`."""
+        flat buffer of that layout; raw=True: the whole destination as bytes instead, `size` + 16 of them prefilled with `fill`.
+        colorimetry, use_cs: as for cvt_yuv_to_rgb (vs_op_cvt_rgb_to_yuv_cs)."""
         f = PIXFMT[yuv_fmt]
         single = isinstance(frames, np.ndarray) and frames.ndim == 3
         frames = [np.ascontiguousarray(x, np.uint8) for x in ([frames] if single else frames)]
@@ -860,7 +889,11 @@ class VsLib:
             d_in.append(DevBuf.from_array(self, rows))
         d_out = [DevBuf.from_array(self, np.full(size + 16, fill, np.uint8)) for _ in range(n)]
         try:
-            self.check(self.lib.vs_op_cvt_rgb_to_yuv(rgb_fmt, _ptr_array(d_in), stride, yuv_fmt, _ptr_array(d_out), C.byref(lay), n, w, h, None))
+            if colorimetry is None and not use_cs:
+                self.check(self.lib.vs_op_cvt_rgb_to_yuv(rgb_fmt, _ptr_array(d_in), stride, yuv_fmt, _ptr_array(d_out), C.byref(lay), n, w, h, None))
+            else:
+                self.check(self.lib.vs_op_cvt_rgb_to_yuv_cs(rgb_fmt, _ptr_array(d_in), stride, yuv_fmt, _ptr_array(d_out), C.byref(lay), n, w, h,
+                                                            _cs_ref(colorimetry), None))
             self.sync()
             outs = [d.download((size + 16,), np.uint8) for d in d_out]
         finally:
@@ -934,6 +967,25 @@ class VsLib:
 class I420LayoutC(C.Structure):
     """struct vs_i420_layout: where the planes of an I420 / I010 / I012 surface lie, in bytes (0 = the packed default of a field)."""
     _fields_ = [("pitch", C.c_size_t), ("c_pitch", C.c_size_t), ("u_off", C.c_size_t), ("v_off", C.c_size_t)]
+
+
+class CvtColorimetry(C.Structure):
+    """struct vs_cvt_colorimetry: the colour space of a conversion (all zero = BT.601 limited, top-left chroma)."""
+    _fields_ = [("matrix", C.c_int32), ("range", C.c_int32), ("chroma_down", C.c_int32), ("reserved", C.c_int32)]
+
+
+CVT_MATRIX_BT601, CVT_MATRIX_BT709, CVT_MATRIX_BT2020 = 0, 1, 2
+CVT_RANGE_LIMITED, CVT_RANGE_FULL = 0, 1
+CVT_CHROMA_TOPLEFT, CVT_CHROMA_MEAN = 0, 1
+
+
+def _cs_ref(colorimetry):
+    """None -> a null pointer; a CvtColorimetry or a tuple of its leading fields -> a reference to the struct."""
+    if colorimetry is None:
+        return None
+    if not isinstance(colorimetry, CvtColorimetry):
+        colorimetry = CvtColorimetry(*colorimetry)
+    return C.byref(colorimetry)
 
 
 def i420_layout(pitch, c_pitch=0, u_off=0, v_off=0):
@@ -1269,6 +1321,10 @@ class Enhancer:
 
     def last_fused(self):
         return self.lib.vs_enh_last_fused(self.h)
+
+    def set_yuv_colorimetry(self, colorimetry=None):
+        """vs_enh_set_yuv_colorimetry: the colour space of apply_yuv_dev / apply_yuv_batch_dev; None = the default."""
+        self._check(self.lib.vs_enh_set_yuv_colorimetry(self.h, _cs_ref(colorimetry)))
 
     def apply_batch_dev(self, params, d_ins, d_outs, w, h, stride, out_stride):
         n = len(d_ins)
