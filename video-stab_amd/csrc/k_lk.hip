@@ -10,9 +10,15 @@
 // spread over the lanes (ceil(win^2/64) pixels per lane, kept in registers as
 // int16 I / dIx / dIy; every sample of the iteration comes from a search region staged in LDS, which
 // is staged again around the point if it walks out of it); the 2x2 normal-equation sums (A11,A12,A22 and per
-// iteration b1,b2) are exact int64 wave reductions, so the float solve that
-// follows is bit-identical to the oracle's.  Latency-bound gather kernel
+// iteration b1,b2) are exact integer wave reductions, so the float solve that
+// follows is bit-identical to the oracle's.  Bound by instruction issue
 // (SURVEY.md 8a L1): images are <= 0.5 MB and stay in L2.
+//
+// Staging: a template patch (PP bytes a row, PP a multiple of 4) and a search region (RW bytes a row) that lie inside the
+// level image are loaded as unaligned dwords - PP / 4 and RD = ceil(RW / 4) a row, lane-strided, all in flight before the
+// first LDS store - and stored at byte 4 i of their array (the region's LDS row pitch is 4 RD).  Whatever touches a border,
+// and a region whose last dword column would leave its row, is staged byte by byte with REFLECT_101.
+// Wave sums: the first butterfly steps in 32 bits (bound at wave_sum), then exact on 64-bit pairs.
 #include "vs_common.h"
 
 namespace vsd {
@@ -36,34 +42,47 @@ struct LKArgs {
 
 // ---- exact wave-wide integer sums without LDS traffic -----------------------
 // Butterfly inside each 16-lane row with DPP (xor 1, xor 2, half-mirror, mirror),
-// then the four row totals are read with v_readlane and added on the scalar unit.
+// then the group totals are read with v_readlane and added on the scalar unit.
 template <int CTRL>
 __device__ __forceinline__ int dpp_mov(int v) {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
 }
-__device__ __forceinline__ int wave_sum_i32(int v) {
-    v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);   // row_half_mirror
-    v += dpp_mov<0x140>(v);   // row_mirror
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) +
-           __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
-// 64-bit variant: the partner's (lo,hi) pair is fetched with two DPP moves and added
-// with a normal 64-bit add, four butterfly steps per 16-lane row, then the four row
-// totals are read with v_readlane and added on the scalar unit.  Per-lane partial
-// sums fit int32 (<= 16 px * 8160 * 4080); the wave total may not.
+// 64-bit step: the partner's (lo,hi) pair is fetched with two DPP moves and added
+// with a normal 64-bit add.  Per-lane partial sums fit int32; the wave total may not.
 template <int CTRL>
 __device__ __forceinline__ long long dpp_mov64(long long v) {
     const int lo = dpp_mov<CTRL>((int)(unsigned)(unsigned long long)v);
     const int hi = dpp_mov<CTRL>((int)((unsigned long long)v >> 32));
     return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
+// The first S butterfly steps run in 32 bits (one v_add_u32 with a DPP operand each).  Bound: a staged intensity is a byte,
+// so |diff| <= 8160 (Iw and the sample are descale(.., 9) of weights that sum to 2^14) and |Ix|, |Iy| <= 4081 (descale(.., 14)
+// of Scharr taps within +-4080); a lane's partial over NPX pixels is at most NPX * 8160 * 4081 in magnitude, and the total of
+// 2^S lanes stays below 2^31 - 1 for S = 4 (NPX = 4), 3 (NPX = 7) and 2 (NPX = 16).  The sum is widened once after that and
+// finished exactly: the remaining row steps run on 64-bit pairs as before, then the four row totals are read with v_readlane
+// and added on the scalar unit.  (Reading the 64 >> S group totals right after the 32-bit steps and adding them sign-extended
+// on the scalar unit has fewer vector but more instructions in all, and measured 3 us slower for 21 x 21: DESIGN 8, round 19.)
+constexpr long long LK_LANE_TERM_MAX = 8160ll * 4081ll;
+template <int NPX> struct WaveSumSteps {
+    static constexpr int S = NPX <= 4 ? 4 : (NPX <= 7 ? 3 : 2);
+    static_assert(NPX <= 16 && (long long)NPX * LK_LANE_TERM_MAX * (1 << S) <= 2147483647ll, "the 32-bit butterfly steps must not overflow");
+};
+template <int S>
 __device__ __forceinline__ long long wave_sum(int p) {
-    long long v = p;
-    v += dpp_mov64<0xB1>(v);
-    v += dpp_mov64<0x4E>(v);
-    v += dpp_mov64<0x141>(v);
+    static_assert(S >= 2 && S <= 4, "");
+    unsigned u = (unsigned)p;
+    u += (unsigned)dpp_mov<0xB1>((int)u);                  // quad_perm [1,0,3,2]
+    u += (unsigned)dpp_mov<0x4E>((int)u);                  // quad_perm [2,3,0,1]
+    if (S >= 3) u += (unsigned)dpp_mov<0x141>((int)u);     // row_half_mirror
+    if (S >= 4) u += (unsigned)dpp_mov<0x140>((int)u);     // row_mirror
+    if (S >= 4) {                                          // the row totals are 32-bit: sign-extended on the scalar unit
+        long long t = 0;
+#pragma unroll
+        for (int r = 0; r < 64; r += 16) t += (long long)__builtin_amdgcn_readlane((int)u, r);
+        return t;
+    }
+    long long v = (int)u;
+    if (S < 3) v += dpp_mov64<0x141>(v);
     v += dpp_mov64<0x140>(v);
     const int lo = (int)(unsigned)(unsigned long long)v, hi = (int)((unsigned long long)v >> 32);
     long long t = 0;
@@ -96,6 +115,10 @@ __device__ __forceinline__ gmem_u8 uniform_global(const uint8_t* p) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
     return (gmem_u8)(((unsigned long long)hi << 32) | lo);
 }
+
+// A dword at any byte address of global memory (gfx950 code objects assume unaligned access: one global_load_dword).
+typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+typedef const __attribute__((address_space(1))) u32_unaligned* gmem_u32u;
 
 constexpr int LK_MARGIN = 6;                       // search region = window + 1 + 2*margin
 constexpr int LK_WIN_MAX = 31;
@@ -132,12 +155,17 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
     // round need no bounds check (the padding is never read).  The patch array also holds what the derivative pass reads
     // beside the staged bytes (results that are not stored or never read): the dword in front of row 0, the rows past the
     // last staged one up to the end of the last row group, and the dword past that.
-    constexpr int PN = (PPM * (PWM + 2) + 63) / 64, RN = (RWM * RWM + 63) / 64;
-    constexpr int PBYTES = (PN * 64 > PPM * (NGM * DR + 2) + 4 ? PN * 64 : PPM * (NGM * DR + 2) + 4);
+    // The interior walks move dwords: PPM / 4 per patch row, RDM = ceil(RWM / 4) per region row; the region's row pitch in
+    // LDS is 4 * RD bytes, so that in both arrays element i of a walk lands at byte 4 * i.
+    constexpr int RDM = (RWM + 3) / 4;
+    constexpr int PN = ((PPM / 4) * (PWM + 2) + 63) / 64, RN = (RDM * RWM + 63) / 64;
+    constexpr int PBYTES = (PN * 256 > PPM * (NGM * DR + 2) + 4 ? PN * 256 : PPM * (NGM * DR + 2) + 4);
+    static_assert((WM - 1) * 4 * RDM + (WM - 1) < 65536 && (WM + 1) * PPM < 65536, "packed window offsets are 16 bits each");
+    constexpr int WS = WaveSumSteps<NPX>::S;
     __shared__ __attribute__((aligned(16))) uint8_t pI_[4 + PBYTES];
     uint8_t* const pI = pI_ + 4;
     __shared__ __attribute__((aligned(16))) short2 pD[(PWM + 1) * PPM];
-    __shared__ uint8_t region[RN * 64];
+    __shared__ __attribute__((aligned(16))) uint8_t region[RN * 256];
     const int lane = threadIdx.x;
     int n = a.n;
     if (a.d_n) { int dn = *a.d_n; n = dn < n ? dn : n; }
@@ -145,6 +173,7 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
     const int win = a.win, area = win * win;
     const int PW = win + 1, PP = (PW + 2 + 3) & ~3;
     const int RW = win + 1 + 2 * LK_MARGIN;
+    const int PD = PP >> 2, RD = (RW + 3) >> 2, RP = 4 * RD;    // dwords per staged row; the region's row pitch
     const float inv_pp = 1.0f / (float)PP, inv_rw = 1.0f / (float)RW, inv_win = 1.0f / (float)win;
     // per window pixel of this lane: offsets into the staged patch and its derivatives (low half) and the search region
     // (high half); kept packed, and the (x, y) of a pixel is recomputed where the rare
@@ -155,17 +184,17 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
         const int p = lane + 64 * k;
         int yy = 0, xx = 0;
         if (p < area) divmod_small(p, win, inv_win, yy, xx);
-        off[k] = (uint32_t)((yy + 1) * PP + xx + 1) | ((uint32_t)(yy * RW + xx) << 16);
+        off[k] = (uint32_t)((yy + 1) * PP + xx + 1) | ((uint32_t)(yy * RP + xx) << 16);
     }
 #define LK_VALID(k) (lane + 64 * (k) < area)
 #define LK_POFF(k) ((int)(off[k] & 0xFFFFu))
 #define LK_ROFF(k) ((int)(off[k] >> 16))
-    // lane-strided walks over the PP x (PW + 2) patch and the RW x RW region: start and step
+    // lane-strided dword walks over the PD x (PW + 2) patch and the RD x RW region: start and step
     int p_y0, p_x0, p_sy, p_sx, r_y0, r_x0, r_sy, r_sx;
-    divmod_small(lane, PP, inv_pp, p_y0, p_x0);
-    divmod_small(64, PP, inv_pp, p_sy, p_sx);
-    divmod_small(lane, RW, inv_rw, r_y0, r_x0);
-    divmod_small(64, RW, inv_rw, r_sy, r_sx);
+    divmod_small(lane, PD, 1.0f / (float)PD, p_y0, p_x0);
+    divmod_small(64, PD, 1.0f / (float)PD, p_sy, p_sx);
+    divmod_small(lane, RD, 1.0f / (float)RD, r_y0, r_x0);
+    divmod_small(64, RD, 1.0f / (float)RD, r_sy, r_sx);
     const float halfWin = (win - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);
     const float px0 = a.prev_pts[2 * pt], py0 = a.prev_pts[2 * pt + 1];
@@ -198,64 +227,58 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
         // (SQ_WAIT_ANY 68 % of its wave cycles, profiles/r03_c_configs1_pmc.txt).
         // (Batches of at most ten loads: the values and offsets of a batch are all that is live, 128 registers - four waves per
         // SIMD - hold without spills; three to four round trips per level instead of 26.)
+        // No load may touch a byte outside [0, w) of a row < h.  Patch: the condition below puts rows ipy - 1 .. ipy + PW and
+        // bytes ipx - 1 .. ipx - 2 + PP of each inside the image, and the PD dwords of a row are exactly those PP bytes.
+        // Region: rows ry0 .. ry0 + RW - 1 and bytes rx0 .. rx0 + 4 RD - 1, which the dword test of stage_region() demands.
         const int pcount = PP * (PW + 2);
         if (ipx >= 1 && ipy >= 1 && ipx - 1 + PP <= L.w && ipy + PW + 1 <= L.h) {
             // (the wave tracks ONE point: base in scalar registers, global - not flat - loads with a 32-bit lane offset)
             const gmem_u8 pbase = uniform_global(L.prev + ((size_t)(ipy - 1) * L.stride + (ipx - 1)));
-            constexpr int PB_ = 10;
+            uint32_t vI[PN];
             int y = p_y0, x = p_x0;
 #pragma unroll
-            for (int k0 = 0; k0 < PN; k0 += PB_) {
-                uint8_t vI[PB_];
-#pragma unroll
-                for (int k = k0; k < k0 + PB_ && k < PN; k++) {
-                    const bool ok = lane + 64 * k < pcount;
-                    vI[k - k0] = pbase[ok ? (uint32_t)(y * (int)L.stride + x) : 0u];
-                    x += p_sx; y += p_sy;
-                    if (x >= PP) { x -= PP; y++; }
-                }
-#pragma unroll
-                for (int k = k0; k < k0 + PB_ && k < PN; k++) pI[lane + 64 * k] = vI[k - k0];
-                __builtin_amdgcn_sched_barrier(0);
+            for (int k = 0; k < PN; k++) {
+                const bool ok = lane + 64 * k < (pcount >> 2);
+                vI[k] = *(gmem_u32u)(pbase + (ok ? (uint32_t)(y * (int)L.stride + 4 * x) : 0u));
+                x += p_sx; y += p_sy;
+                if (x >= PD) { x -= PD; y++; }
             }
+#pragma unroll
+            for (int k = 0; k < PN; k++) reinterpret_cast<uint32_t*>(pI)[lane + 64 * k] = vI[k];
+            __builtin_amdgcn_sched_barrier(0);
         } else {                               // REFLECT_101 intensities; the derivative pass masks what lies outside
-            int y = p_y0, x = p_x0;
             for (int i = lane; i < pcount; i += 64) {
+                int y, x;
+                divmod_small(i, PP, inv_pp, y, x);
                 const int X = ipx - 1 + x, Y = ipy - 1 + y;
                 pI[i] = L.prev[(size_t)reflect101(Y, L.h) * L.stride + reflect101(X, L.w)];
-                x += p_sx; y += p_sy;
-                if (x >= PP) { x -= PP; y++; }
             }
         }
         // the search region of the next image around (rx0, ry0); staged again, re-centred, if the point walks out
         // of it (more than LK_MARGIN pixels at one level), so every sample of the iteration comes from LDS
         auto stage_region = [&]() {
-            const bool inside = rx0 >= 0 && ry0 >= 0 && rx0 + RW <= L.w && ry0 + RW <= L.h;
+            // (a region whose last one to three dword columns would leave the row takes the byte walk below)
+            const bool inside = rx0 >= 0 && ry0 >= 0 && rx0 + RP <= L.w && ry0 + RW <= L.h;
             int y = r_y0, x = r_x0;
             asm volatile("" : "+v"(x), "+v"(y));       // (the offsets of the walk are recomputed at every call: hoisted out of the iteration loop they cost 40 registers)
             if (inside) {
                 const gmem_u8 rbase = uniform_global(L.next + ((size_t)ry0 * L.stride + rx0));
-                constexpr int RB_ = 10;
+                uint32_t vR[RN];
 #pragma unroll
-                for (int k0 = 0; k0 < RN; k0 += RB_) {
-                    uint8_t vR[RB_];
-#pragma unroll
-                    for (int k = k0; k < k0 + RB_ && k < RN; k++) {
-                        const bool ok = lane + 64 * k < RW * RW;
-                        vR[k - k0] = rbase[ok ? (uint32_t)(y * (int)L.stride + x) : 0u];
-                        x += r_sx; y += r_sy;
-                        if (x >= RW) { x -= RW; y++; }
-                    }
-#pragma unroll
-                    for (int k = k0; k < k0 + RB_ && k < RN; k++) region[lane + 64 * k] = vR[k - k0];
-                    __builtin_amdgcn_sched_barrier(0);
+                for (int k = 0; k < RN; k++) {
+                    const bool ok = lane + 64 * k < RD * RW;
+                    vR[k] = *(gmem_u32u)(rbase + (ok ? (uint32_t)(y * (int)L.stride + 4 * x) : 0u));
+                    x += r_sx; y += r_sy;
+                    if (x >= RD) { x -= RD; y++; }
                 }
+#pragma unroll
+                for (int k = 0; k < RN; k++) reinterpret_cast<uint32_t*>(region)[lane + 64 * k] = vR[k];
+                __builtin_amdgcn_sched_barrier(0);
             } else {                           // a region that leaves the image: element by element, reflected
                 for (int i = lane; i < RW * RW; i += 64) {
+                    divmod_small(i, RW, inv_rw, y, x);
                     const int X = rx0 + x, Y = ry0 + y;
-                    region[i] = L.next[(size_t)reflect101(Y, L.h) * L.stride + reflect101(X, L.w)];
-                    x += r_sx; y += r_sy;
-                    if (x >= RW) { x -= RW; y++; }
+                    region[y * RP + x] = L.next[(size_t)reflect101(Y, L.h) * L.stride + reflect101(X, L.w)];
                 }
             }
         };
@@ -333,7 +356,7 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
             pA12 += __mul24(ixval, iyval);
             pA22 += __mul24(iyval, iyval);
         }
-        const long long sA11 = wave_sum(pA11), sA12 = wave_sum(pA12), sA22 = wave_sum(pA22);
+        const long long sA11 = wave_sum<WS>(pA11), sA12 = wave_sum<WS>(pA12), sA22 = wave_sum<WS>(pA22);
         const float A11 = (float)sA11 * FLT_SCALE, A12 = (float)sA12 * FLT_SCALE, A22 = (float)sA22 * FLT_SCALE;
         float D = A11 * A22 - A12 * A12;
         const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
@@ -363,19 +386,19 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
             {
                 // every slot is computed unconditionally (invalid slots carry Ix = Iy = 0 and a
                 // safe offset), so the LDS reads of all pixels are in flight together
-                const int rbase = ly * RW + lx;
+                const int rbase = ly * RP + lx;
 #pragma unroll
                 for (int k = 0; k < NPX; k++) {
                     const uint8_t* r0 = &region[rbase + LK_ROFF(k)];
                     // signed 24-bit multiplies: w11 = 2^14 - w00 - w01 - w10 can be -1
                     const int v = descale(__mul24((int)r0[0], wt.w00) + __mul24((int)r0[1], wt.w01) +
-                                          __mul24((int)r0[RW], wt.w10) + __mul24((int)r0[RW + 1], wt.w11), 9);
+                                          __mul24((int)r0[RP], wt.w10) + __mul24((int)r0[RP + 1], wt.w11), 9);
                     const int diff = v - Iw[k];
                     pb1 += __mul24(diff, (int)Ix[k]);
                     pb2 += __mul24(diff, (int)Iy[k]);
                 }
             }
-            const long long sb1 = wave_sum(pb1), sb2 = wave_sum(pb2);
+            const long long sb1 = wave_sum<WS>(pb1), sb2 = wave_sum<WS>(pb2);
             const float b1 = (float)sb1 * FLT_SCALE, b2 = (float)sb2 * FLT_SCALE;
             const float dx = (A12 * b2 - A22 * b1) * D;
             const float dy = (A12 * b1 - A11 * b2) * D;
@@ -405,17 +428,17 @@ __device__ __forceinline__ void lk_track(const LKArgs& a, const int pt) {
                 }
                 int es = 0;
                 {
-                    const int rbase = ly * RW + lx;
+                    const int rbase = ly * RP + lx;
 #pragma unroll
                     for (int k = 0; k < NPX; k++) {
                         const uint8_t* r0 = &region[rbase + LK_ROFF(k)];
                         const int v = descale(__mul24((int)r0[0], wt.w00) + __mul24((int)r0[1], wt.w01) +
-                                              __mul24((int)r0[RW], wt.w10) + __mul24((int)r0[RW + 1], wt.w11), 9);
+                                              __mul24((int)r0[RP], wt.w10) + __mul24((int)r0[RP + 1], wt.w11), 9);
                         const int diff = v - Iw[k];
                         es += LK_VALID(k) ? (diff < 0 ? -diff : diff) : 0;
                     }
                 }
-                const long long est = wave_sum(es);
+                const long long est = wave_sum<WS>(es);
                 err = (float)est * 1.f / (float)(32 * win * win);
             }
         }
