@@ -39,7 +39,7 @@ extern "C" {
  *    vs_op_warp_affine16_ex; the same two stages on I420 / I010 / I012 surfaces: struct vs_i420_layout with
  *    vs_roll_correct_i420_dev, vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev and vs_azc_apply_i420_dev_n; planar 4:2:2 and
  *    4:4:4 - VS_FMT_I422, VS_FMT_I444, VS_FMT_I210, VS_FMT_I212, VS_FMT_I410, VS_FMT_I412 (enum vs_pixfmt_planar4xx) - with
- *    vs_op_warp_affine_planar; the output size of auto zoom/crop: vs_azc_set_output_size, vs_azc_get_output_size, struct
+ *    vs_op_warp_affine_planar, and as fmt of the four roll / zoom entry points above; the output size of auto zoom/crop: vs_azc_set_output_size, vs_azc_get_output_size, struct
  *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan; the compositing operators vs_op_copy_make_border, vs_op_fade_blend,
  *    vs_op_fade_update and vs_op_canvas_create / apply / info / destroy; colour conversion on the device: vs_op_cvt_yuv_to_rgb,
  *    vs_op_cvt_rgb_to_yuv and vs_enh_apply_yuv_dev; the enhancer on a batch of YUV surfaces in one fused launch:
@@ -193,9 +193,24 @@ typedef enum vs_pixfmt_planar16 {
  *    half to even (vs_pixfmt16) - which does not depend on the bit depth.  (For 4:2:2, Mc is not a rotation.)
  *  - the last frame of a flush comes back unwarped, all three planes;
  *  - border pad, crop-and-zoom, fade and the virtual canvas are VS_ERR_UNSUPPORTED, with a text that names the format, exactly
- *    where I420 is refused.  Roll correction and auto zoom/crop (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev) keep refusing
- *    anything but I420 / I010 / I012; the enhancer and the C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16,
- *    P210, NV24), yuv4xxp16le and big-endian samples are not built. */
+ *    where I420 is refused.  The C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16, P210, NV24),
+ *    yuv4xxp16le and big-endian samples are not built.
+ * The two stages around the stabilizer take these formats through the entry points of the 4:2:0 ones (vs_roll_correct_i420_dev,
+ * vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev, vs_azc_apply_i420_dev_n; layouts as struct vs_i420_layout, whose default chroma
+ * pitch is pitch >> sx).  In these two stages w and h are even for every format (odd-height 4:2:2 and odd 4:4:4 pictures are a stated
+ * limitation).  The definitions are those of vs_pixfmt_planar / vs_pixfmt_planar16 with the shifts made explicit:
+ *  - analysis, both stages: the 8-bit plane of Y - Y itself, or min(sample >> (bits - 8), 255).  Angle, line counts, content mask,
+ *    contours and info8 are those of the NV12 call on that plane; they do not depend on the chroma subsampling;
+ *  - roll rotation: Y under the double matrix M of cv::getRotationMatrix2D((w / 2.0f, h / 2.0f), angle, 1); U and V under
+ *    Mc = S^-1 M S in double, S = diag(2^sx, 2^sy):
+ *        [[m0, m1 * 2^(sy - sx), m2 / 2^sx], [m3 * 2^(sx - sy), m4, m5 / 2^sy]]      (exact products by powers of two;
+ *    (1, 1) is "the translation halved" to the letter).  BORDER_REPLICATE; 8-bit planes vs_op_warp_affine_ex's arithmetic, 16-bit
+ *    planes P010's blend (S rounded once, half to even);
+ *  - zoom crop-and-scale: the rectangle (x, y, cw, ch) applies to Y as found and as (x >> sx, y >> sy, uw = max(1, cw >> sx),
+ *    uh = max(1, ch >> sy)) to U and to V; Y is scaled to ow x oh, U and V each to (ow >> sx) x (oh >> sy) by
+ *    [(float)((double)(ow >> sx) / uw), 0, 0; 0, (float)((double)(oh >> sy) / uh), 0]; INTER_LINEAR, BORDER_CONSTANT 0 at the crop's
+ *    edge - vs_op_scale_jobs' arithmetic for that sample size.  On the fall-back paths (no contour, empty crop) the three planes
+ *    come back unchanged at their own sizes, laid where `out` puts them.  vs_azc_set_output_size applies as to the other formats. */
 typedef enum vs_pixfmt_planar4xx {
     VS_FMT_I422 = 10,         /* yuv422p:     Y (h rows of w), U, V (h rows of w/2 each) */
     VS_FMT_I444 = 11,         /* yuv444p:     Y, U, V (h rows of w each) */
@@ -712,15 +727,16 @@ int vs_roll_correct_p010_dev(vs_roll* r, const void* d_surface, int w, int h, si
                              void* d_out, size_t out_pitch, size_t out_uv_offset);
 int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                                size_t pitch, size_t uv_offset, size_t out_pitch, size_t out_uv_offset);
-/* Where the three planes of a planar 4:2:0 surface (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012) lie, in BYTES: rows of `pitch` bytes of
- * Y at the surface pointer; U and V rows `c_pitch` bytes apart, the planes u_off / v_off bytes behind the surface pointer.  0 means
- * the packed default for c_pitch (pitch / 2), u_off (behind the Y rows) and v_off (behind U) - the fields of
+/* Where the three planes of a planar surface (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012; VS_FMT_I422 ... VS_FMT_I412) lie, in BYTES: rows
+ * of `pitch` bytes of Y at the surface pointer; U and V rows `c_pitch` bytes apart, the planes u_off / v_off bytes behind the surface
+ * pointer.  0 means the packed default for c_pitch (pitch >> sx: pitch / 2, for 4:4:4 pitch), u_off (behind the Y rows) and v_off
+ * (behind the h >> sy rows of U) - the fields of
  * vs_stab_set_i420_layout.  YV12: give both offsets, V first.  The roll and zoom entry points take one such struct for the surface
  * and one for the result (a small POD by pointer, read during the call - not the eight plain size_t arguments the two layouts would
  * otherwise be; vs_stab_set_i420_layout keeps its six plain arguments, its pitches travel with every push). */
 typedef struct vs_i420_layout {
     size_t pitch;             /* bytes per Y row */
-    size_t c_pitch;           /* bytes per U / V row; 0 = pitch / 2 */
+    size_t c_pitch;           /* bytes per U / V row; 0 = pitch / 2 (4:4:4 formats: pitch) */
     size_t u_off, v_off;      /* bytes from the surface pointer to the U / V plane; 0 = packed behind the plane before */
 } vs_i420_layout;
 /* autoCorrectRoll for planar 4:2:0 surfaces in HBM, ASYNCHRONOUS: vs_roll_correct_nv12_dev for fmt = VS_FMT_I420 (YV12 through the
@@ -730,7 +746,12 @@ typedef struct vs_i420_layout {
  * format (vs_roll_last_error).  Y, U and V of a batch's surfaces are rotated by ONE launch when the batch's results share a
  * layout.  Batches of eight, worker threads, VS_ROLL_WORKERS, vs_roll_sync and vs_roll_get_state as for NV12.  One object may
  * receive NV12, P010 and planar calls in any order: a change of format or of layout closes the pending batch exactly as a change
- * of geometry does, the smoothed angle carries across. */
+ * of geometry does, the smoothed angle carries across.
+ * fmt may also be a 4:2:2 / 4:4:4 format - VS_FMT_I422, I444, I210, I212, I410, I412 (definitions: vs_pixfmt_planar4xx): w and h even
+ * all the same; a chroma plane holds h >> sy rows of w >> sx samples, so a chroma pitch holds at least (w >> sx) samples, the default
+ * chroma pitch is pitch >> sx (4:2:2: the pitch even, 16-bit a multiple of 4; 4:4:4: any pitch of whole samples) and U and V, in either
+ * order, lie behind the luma rows (h >> sy) * c_pitch bytes apart at least; the texts name the format.  NV12, P010 and any other
+ * value: VS_ERR_INVALID_ARG, the text names the three-plane formats. */
 int vs_roll_correct_i420_dev(vs_roll* r, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in,
                              void* d_out, const vs_i420_layout* out);
 int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
@@ -808,7 +829,9 @@ int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* cons
  * planes where `out` puts them whichever size comes out, so `out` describes a surface of max(w, 640) x max(h, 360): pitch >=
  * max(w, 640) samples, u_off >= max(h, 360) * pitch, v_off >= u_off + max(h, 360) / 2 * c_pitch (or U behind V), and its zero
  * fields default to the packed layout of that size.  The three planes of a batch's surfaces are cropped and scaled by ONE launch.
- * Tickets, vs_azc_result, batches, worker threads and vs_azc_sync as for NV12; NV12, P010 and planar calls may alternate. */
+ * Tickets, vs_azc_result, batches, worker threads and vs_azc_sync as for NV12; NV12, P010 and planar calls may alternate.
+ * fmt may also be a 4:2:2 / 4:4:4 format (vs_pixfmt_planar4xx): U and V come out at (640 >> sx) x (360 >> sy), `out` holds
+ * max(h, 360) >> sy chroma rows of max(w, 640) >> sx samples, and a fall-back surface comes back with its planes at their own sizes. */
 int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in,
                           void* d_out, const vs_i420_layout* out, int64_t* ticket);
 int vs_azc_apply_i420_dev_n(vs_azc* a, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
@@ -819,7 +842,8 @@ int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* in
  * (640, 360).  (0, 0) = the size of the surface handed over: every result is w x h.  Otherwise both values even and in 2 .. 8192;
  * anything else is VS_ERR_INVALID_ARG with a text in vs_azc_last_error.  The setting is the object's and every entry point obeys it:
  * luma / BGR / gray scaled by [(float)((double)ow / cw), 0, 0; 0, (float)((double)oh / ch), 0] to ow x oh, the chroma planes of the
- * 4:2:0 surfaces by [(float)((double)(ow / 2) / uw), 0, 0; 0, (float)((double)(oh / 2) / uh), 0] to (ow / 2) x (oh / 2); buffer and
+ * 4:2:0 surfaces by [(float)((double)(ow / 2) / uw), 0, 0; 0, (float)((double)(oh / 2) / uh), 0] to (ow / 2) x (oh / 2) (planar 4:2:2 /
+ * 4:4:4: ow >> sx and oh >> sy in place of the halves); buffer and
  * layout rules read max(w, ow) and max(h, oh).  The crop rectangle, info8, the mask and the contours do not depend on it; on the
  * fall-back paths the surface comes back unchanged, w x h.  It applies to frames handed over after the call: like a change of
  * geometry it closes the pending batch, and tickets already issued keep the size they were issued under. */

@@ -296,8 +296,8 @@ struct vs_azc {
     // one launch.  NBS batches in flight.
     static constexpr int ZB = 8, NBS = 4, NRES = 1024;      // (ZB <= SRC_LIST_MAX, 3 ZB <= WARP_JOBS_MAX: three planes of a planar surface)
     int nw = 12;                         // worker threads (VS_AZC_WORKERS, 1 .. 16): 31 k frames/s alone with eight, 41 k with twelve
-    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420,
-    // VS_FMT_I010, VS_FMT_I012) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
+    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420 ...
+    // VS_FMT_I412) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
     // ow, oh: the output size the frame was handed over under, resolved (never 0)
     struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; int planar; I420Layout sl, dl; int ow, oh; };
     struct BatchSlot {
@@ -580,6 +580,7 @@ static void azc_worker(vs_azc* a) {
         res.ticket = q.ticket;
         int rc = b.arrived == 3 ? VS_ERR_HIP : VS_OK;
         WarpJob wj[3];
+        const int csx = q.planar ? pixfmt(q.planar)->sx : 1, csy = q.planar ? pixfmt(q.planar)->sy : 1;     // the chroma shifts
         int nscaled = 0;                 // crop-and-scale jobs of this frame: 2 (NV12 / P010), 3 (planar), 0 on the fall-back paths
         const clk::time_point t_masks = clk::now();
         clk::time_point t_contour = t_masks;
@@ -592,11 +593,12 @@ static void azc_worker(vs_azc* a) {
             t_contour = clk::now();
             if (!res.info[7]) {                                                                            // :149-152, :238-249
                 res.out_w = q.w; res.out_h = q.h;
-                if (q.planar) {          // the unchanged surface, all three planes
-                    const size_t cw = (size_t)(q.w / 2) * q.sb;
+                if (q.planar) {          // the unchanged surface, all three planes: each its own row bytes and rows
+                    const size_t cw = (size_t)(q.w >> csx) * q.sb;
+                    const size_t crows = (size_t)(q.h >> csy);
                     if (hipMemcpy2DAsync(q.dst, q.dl.pitch, q.src, q.sl.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
-                        hipMemcpy2DAsync(q.dst + q.dl.u, q.dl.cpitch, q.src + q.sl.u, q.sl.cpitch, cw, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
-                        hipMemcpy2DAsync(q.dst + q.dl.v, q.dl.cpitch, q.src + q.sl.v, q.sl.cpitch, cw, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
+                        hipMemcpy2DAsync(q.dst + q.dl.u, q.dl.cpitch, q.src + q.sl.u, q.sl.cpitch, cw, crows, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
+                        hipMemcpy2DAsync(q.dst + q.dl.v, q.dl.cpitch, q.src + q.sl.v, q.sl.cpitch, cw, crows, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
                         rc = VS_ERR_HIP;
                 } else if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
                     hipMemcpy2DAsync(q.dst + q.ouv, q.opitch, q.src + q.uv, q.pitch, (size_t)q.w * q.sb, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
@@ -604,20 +606,20 @@ static void azc_worker(vs_azc* a) {
             } else {
                 res.out_w = q.ow; res.out_h = q.oh;
                 const int cx = res.info[2], cy = res.info[3], cw = res.info[4], ch = res.info[5];
-                const int ux = cx / 2, uy = cy / 2, uw = std::max(1, cw / 2), uh = std::max(1, ch / 2);
+                const int ux = cx >> csx, uy = cy >> csy, uw = std::max(1, cw >> csx), uh = std::max(1, ch >> csy);
                 const float My[6] = {(float)((double)q.ow / cw), 0.f, 0.f, 0.f, (float)((double)q.oh / ch), 0.f};
-                const float Mu[6] = {(float)((double)(q.ow / 2) / uw), 0.f, 0.f, 0.f, (float)((double)(q.oh / 2) / uh), 0.f};
+                const float Mu[6] = {(float)((double)(q.ow >> csx) / uw), 0.f, 0.f, 0.f, (float)((double)(q.oh >> csy) / uh), 0.f};
                 warp_invert(My, wj[0].m);
                 warp_invert(Mu, wj[1].m);
                 wj[0].src = q.src + (size_t)cy * q.pitch + (size_t)cx * q.sb; wj[0].dst = q.dst;
                 wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = q.ow; wj[0].dh = q.oh; wj[0].cn = 1;
                 for (WarpJob& w : wj) { w.sstride = (uint32_t)q.pitch; w.dstride = (uint32_t)q.opitch; w.border = VS_BORDER_BLACK; w.sb = q.sb; }
-                if (q.planar) {          // U and V: one-channel planes of half the size, the halved rectangle, rows of their own pitch
+                if (q.planar) {          // U and V: one-channel planes of (w >> sx) x (h >> sy), the shifted rectangle, rows of their own pitch
                     warp_invert(Mu, wj[2].m);
                     wj[1].src = q.src + q.sl.u + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[1].dst = q.dst + q.dl.u;
                     wj[2].src = q.src + q.sl.v + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[2].dst = q.dst + q.dl.v;
                     for (int k = 1; k < 3; k++) {
-                        wj[k].sw = uw; wj[k].sh = uh; wj[k].dw = q.ow / 2; wj[k].dh = q.oh / 2; wj[k].cn = 1;
+                        wj[k].sw = uw; wj[k].sh = uh; wj[k].dw = q.ow >> csx; wj[k].dh = q.oh >> csy; wj[k].cn = 1;
                         wj[k].sstride = (uint32_t)q.sl.cpitch; wj[k].dstride = (uint32_t)q.dl.cpitch;
                     }
                     nscaled = 3;
@@ -699,7 +701,7 @@ static int azc_issue_batch(vs_azc* a, std::unique_lock<std::mutex>& lk) {
     }
     VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, 1, b.d_tbits, (u64*)b.d_masks, BitFrame::pitch_for(w), 1, b.st, srcs, n, tw,
                                  mb / 8, aligned, a->pending[0].sb,
-                                 a->pending[0].planar == VS_FMT_I010 ? 2 : a->pending[0].planar == VS_FMT_I012 ? 4 : 0));                                                                              // :111-139 on the luma planes
+                                 a->pending[0].planar ? pixfmt(a->pending[0].planar)->lo16_shift() : 0));                                                                              // :111-139 on the luma planes
     VS_OBJ_HIP(a, hipMemcpyAsync(b.h_masks, b.d_masks, mb * n, hipMemcpyDeviceToHost, b.st));                                          // :142-143
     VS_OBJ_HIP(a, hipEventRecord(b.ev, b.st));
     b.t_issue = std::chrono::steady_clock::now();
@@ -802,18 +804,20 @@ int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* cons
     return VS_OK;
 }
 
-// The same for a planar 4:2:0 surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010 or VS_FMT_I012; in / out: where
-// the three planes lie (vs_i420_layout: bytes, 0 = the packed default for the chroma pitch and the offsets).  The content mask comes from
-// the 8-bit analysis plane of Y - Y itself, or min(sample >> (bits - 8), 255) -; the rectangle applies to Y as it is and, halved, to U and
-// to V, each scaled to ow / 2 x oh / 2 as a one-channel plane: the three planes of a batch's surfaces are one launch (two when only some of
+// The same for a three-plane surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010, VS_FMT_I012, or a 4:2:2 / 4:4:4
+// format (VS_FMT_I422, I444, I210, I212, I410, I412; (sx, sy): the format's chroma shifts, w and h even for every format); in / out: where
+// the three planes lie (vs_i420_layout: bytes, 0 = the packed default for the chroma pitch - pitch >> sx - and the offsets).  The content
+// mask comes from the 8-bit analysis plane of Y - Y itself, or min(sample >> (bits - 8), 255) -; the rectangle (x, y, cw, ch) applies to Y as
+// it is and as (x >> sx, y >> sy, max(1, cw >> sx), max(1, ch >> sy)) to U and to V, each scaled to (ow >> sx) x (oh >> sy) as a one-channel
+// plane (4:2:0: halved, ow / 2 x oh / 2): the three planes of a batch's surfaces are one launch (two when only some of
 // its jobs can be staged).  The result's planes lie where `out` puts them whichever size comes out, so `out` must hold max(w, ow) x
 // max(h, oh) - 640 x 360 unless vs_azc_set_output_size said otherwise -: its defaults are those of a surface of that size.  An I420 result is the de-interleaved result of vs_azc_apply_nv12_dev on the same samples.
 int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in, void* d_out, const vs_i420_layout* out,
                           int64_t* ticket) {
     if (!a || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
     const PixFmt* f = pixfmt(fmt);
-    if (!f || !f->planar_420())
-        return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: the planar entry point takes VS_FMT_I420, VS_FMT_I010 or VS_FMT_I012");
+    if (!f || !f->three_planes())
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: the planar entry point takes a three-plane format (VS_FMT_I420, I010, I012, I422, I444, I210, I212, I410, I412)");
     I420Layout sl, dl;
     std::string msg;
     const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h;

@@ -777,8 +777,8 @@ struct vs_roll {
     int nwk = 5;                         // worker threads in use (VS_ROLL_WORKERS, 1 .. NWK): alone three are as fast as eight (36 - 38 k
                                          // frames/s); beside a stabilizer on the same GPU a batch's launches wait behind its workgroups, and five
                                          // batches in flight keep the stage at 3.4 ms per 128 surfaces where three need 5.5 (gpurun_out/r04_ai)
-    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420,
-    // VS_FMT_I010, VS_FMT_I012) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
+    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420 ...
+    // VS_FMT_I412) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
     struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; int sb; int planar; I420Layout sl, dl; };
     struct Slot {
         RollWork wk;                     // RB frames
@@ -1030,7 +1030,8 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
     for (int f = 0; f < n; f++) { q.h_pairs[f].src = jobs[f].src; q.h_pairs[f].dst = k.gray + (size_t)f * k.fb; }
     VS_HIP_TRY(hipMemcpyAsync(q.d_pairs, q.h_pairs, sizeof(ImgPair) * n, hipMemcpyHostToDevice, q.st));
     // (P010: the analysis image is that of the luma samples' high bytes - the 16-bit gray kernels of k_gray.hip read nothing else;
-    // I010 / I012: that of min(sample >> (bits - 8), 255), the low-bits kernels; the Y plane of an I420 surface is a gray picture)
+    // the three-plane 16-bit formats: that of min(sample >> (bits - 8), 255), the low-bits kernels; the Y plane of an 8-bit three-plane
+    // surface is a gray picture - the chroma subsampling does not enter)
     const int gfmt = j0.planar && j0.sb == 2 ? j0.planar : j0.sb == 2 ? (int)VS_FMT_P010 : (int)VS_FMT_GRAY8;
     VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, gfmt, sw, sw, sh, 0, q.st));   // :41
     // (twelve hysteresis passes per batch - a pass whose predecessor changed nothing for its frame returns at once: with four, 40 % of
@@ -1077,29 +1078,33 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
         if (slow[f]) r->slow_frames++;
         roll_update(r, res[f]);
         // cv::getRotationMatrix2D(center, angle, 1.0) (:141-144); the interleaved chroma plane is the half-size picture: the same
-        // rotation with the translation halved
+        // rotation with the translation halved.  A three-plane surface's chroma planes take Mc = S^-1 M S, S = diag(2^sx, 2^sy) - exact
+        // products by powers of two; (1, 1) is the halved translation, (1, 0) shears (4:2:2), (0, 0) is M itself (4:4:4)
         const float cx = j.w / 2.0f, cy = j.h / 2.0f;
         const double a = r->smoothed * 3.1415926535897932384626433832795 / 180;
         const double alpha = std::cos(a), beta = std::sin(a);
         const double M[6] = {alpha, beta, (1 - alpha) * cx - beta * cy, -beta, alpha, beta * cx + (1 - alpha) * cy};
-        const double Mc[6] = {M[0], M[1], M[2] * 0.5, M[3], M[4], M[5] * 0.5};
+        const int csx = j.planar ? pixfmt(j.planar)->sx : 1, csy = j.planar ? pixfmt(j.planar)->sy : 1;
+        const double kx = csx ? 0.5 : 1.0, ky = csy ? 0.5 : 1.0;          // 2^-sx, 2^-sy
+        const double Mc[6] = {M[0], M[1] * (kx / ky), M[2] * kx, M[3] * (ky / kx), M[4], M[5] * ky};
         warp_invert(M, Minv + 12 * f);
         warp_invert(Mc, Minv + 12 * f + 6);
         ys[f] = j.src; us[f] = j.src + j.uv; yd[f] = j.dst; ud[f] = j.dst + j.ouv;
         one_launch &= j.opitch == j0.opitch && j.uv == j0.uv && j.ouv == j0.ouv;
         if (j0.planar) one_launch &= j.dl.cpitch == j0.dl.cpitch && j.dl.u == j0.dl.u && j.dl.v == j0.dl.v;
     }
-    // planar 4:2:0 (a batch holds one format and one source layout): Y, U and V tiles of all its surfaces in ONE grid (warp_i420_kernel
-    // with the BORDER_REPLICATE staging, 8- or 16-bit samples) when the results share one layout, else frame by frame; U and V both
-    // take the chroma map
+    // three planes (a batch holds one format and one source layout): Y, U and V tiles of all its surfaces in ONE grid (warp_i420_kernel
+    // with the BORDER_REPLICATE staging, 8- or 16-bit samples, the instance of the format's chroma shifts) when the results share one
+    // layout, else frame by frame; U and V both take the chroma map
     if (j0.planar) {
+        const int sx = pixfmt(j0.planar)->sx, sy = pixfmt(j0.planar)->sy;
         if (one_launch)
             return launch_warp_i420(ys, yd, n, j0.sl, j0.dl, j0.w, j0.h, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE, WarpTabs{WarpTabs::SCRATCH},
-                                    r->st, j0.sb);
+                                    r->st, j0.sb, sx, sy);
         for (int f = 0; f < n; f++) {
             const vs_roll::Job& j = jobs[f];
             VS_TRY(launch_warp_i420(ys + f, yd + f, 1, j.sl, j.dl, j.w, j.h, WarpMaps{Minv + 12 * f, 12, true}, VS_BORDER_REPLICATE,
-                                    WarpTabs{WarpTabs::SCRATCH}, r->st, j.sb));
+                                    WarpTabs{WarpTabs::SCRATCH}, r->st, j.sb, sx, sy));
         }
         return VS_OK;
     }
@@ -1218,16 +1223,18 @@ int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* 
     return VS_OK;
 }
 
-// The same for a planar 4:2:0 surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010 or VS_FMT_I012; in / out: where
-// the three planes lie (vs_i420_layout: bytes, 0 = the packed default for the chroma pitch and the offsets).  The line search runs on the
-// 8-bit analysis plane of Y - Y itself, or min(sample >> (bits - 8), 255) -, the rotation is applied to Y with M and to U and V, each a
-// one-channel plane of half the size, with the translation halved: Y, U and V tiles of a batch in one launch.  An I420 result is the
-// de-interleaved result of vs_roll_correct_nv12_dev on the same samples.  NV12, P010 and planar surfaces may alternate on one object.
+// The same for a three-plane surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010, VS_FMT_I012, or a 4:2:2 / 4:4:4
+// format (VS_FMT_I422, I444, I210, I212, I410, I412); in / out: where the three planes lie (vs_i420_layout: bytes, 0 = the packed default
+// for the chroma pitch - pitch >> sx - and the offsets).  The line search runs on the 8-bit analysis plane of Y - Y itself, or
+// min(sample >> (bits - 8), 255) -, the rotation is applied to Y with M and to U and V, each a one-channel plane of (w >> sx) x (h >> sy)
+// samples, with Mc = S^-1 M S, S = diag(2^sx, 2^sy) (4:2:0: the translation halved): Y, U and V tiles of a batch in one launch.  An I420
+// result is the de-interleaved result of vs_roll_correct_nv12_dev on the same samples.  NV12, P010 and planar surfaces of any format may
+// alternate on one object: a change of format closes the pending batch, the smoothed angle carries across.  w and h are even for every format.
 int vs_roll_correct_i420_dev(vs_roll* r, int fmt, const void* d_surface, int w, int h, const vs_i420_layout* in, void* d_out, const vs_i420_layout* out) {
     if (!r || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
     const PixFmt* f = pixfmt(fmt);
-    if (!f || !f->planar_420())
-        return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: the planar entry point takes VS_FMT_I420, VS_FMT_I010 or VS_FMT_I012");
+    if (!f || !f->three_planes())
+        return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: the planar entry point takes a three-plane format (VS_FMT_I420, I010, I012, I422, I444, I210, I212, I410, I412)");
     I420Layout sl, dl;
     std::string msg;
     if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "roll", &sl, &msg) != VS_OK || planar_layout_check(fmt, d_out, w, h, out, w, h, "roll (result)", &dl, &msg) != VS_OK)

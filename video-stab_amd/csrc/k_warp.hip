@@ -1570,6 +1570,168 @@ __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_s
         plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
 }
 
+// ---- planar 4:2:2 surfaces under host maps of a few degrees: a taller staged box ---------------------------------------------------
+// The roll stage and vs_op_warp_affine_planar rotate by degrees, and the 4:2:2 chroma map S^-1 M S has 2 sin(angle) where a rotation
+// has sin(angle): a full-width chroma tile's source box outgrows the THP + 9 rows of PlaneCfg at 1.80 - 2.04 degrees, where luma
+// tiles (and the tiles of a 4:2:0 surface) stay staged up to 3.61 - 4.07.  These instances stage THP + 17 rows: 254 sin(angle) < 16
+// keeps every full-width 4:2:2 chroma tile staged up to 3.61 degrees (and luma tiles up to 7.2).  BORDER_REPLICATE only, (CSX, CSY) =
+// (1, 0) only; the launcher picks them only where the maps are host doubles and some surface's chroma box needs the rows
+// (i420_needs_tall_box) - the stabilizer's launches, whose maps are on the device, keep the instances they have.
+// LDS: 8-bit 81 rows x 256 B + 1536 B = 22 272 B, seven workgroups per CU where the THP + 9 box allows eight; 16-bit 49 x 384 B + 1280 B
+// = 20 096 B, eight.  Everything here is a copy: plane_tile_tall is plane_tile<1, VS_BORDER_REPLICATE, SB> with the taller box and a
+// plane_direct_tile copy of its own (OWN 8), so that no kernel that existed before shares a callee with these.
+template <int SB> struct TallCfg {
+    static constexpr int ROWS = PlaneCfg<1, SB>::THP + 17;
+};
+
+template <int SB>
+__device__ __forceinline__ void plane_tile_tall(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
+                                                uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add, int dst_add) {
+    typedef PlaneCfg<1, SB> P;
+    constexpr int ROWS = TallCfg<SB>::ROWS;
+    typedef __attribute__((address_space(1))) uint8_t* gptr;
+    const int L = tid & 31, ty = tid >> 5;
+    int ad[4], bd[4];
+    const int x0 = tx * TW, y0 = tyl * P::THP;
+    const int x1 = min(x0 + TW, c.dw) - 1, y1 = min(y0 + P::THP, c.dh) - 1;
+    const uint8_t* src;
+    uint8_t* dst;
+    int ad0, ad1, bd0, bd1, Xa, Xb, Ya, Yb;
+    {
+        typedef int32_t i32x8 __attribute__((ext_vector_type(8)));
+        typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+        const i32x8 cc = *(const __attribute__((address_space(4))) i32x8*)(Ts + TAB_COL * tx);
+        const i32x4 r0 = *(const __attribute__((address_space(4))) i32x4*)(Ts + tab_row + 4 * (y0 / TH));
+        const i32x4 r1 = *(const __attribute__((address_space(4))) i32x4*)(Ts + tab_row + 4 * (y1 / TH));
+        src = (const uint8_t*)(gptr)((unsigned long long)(uint32_t)cc[0] | (unsigned long long)(uint32_t)cc[1] << 32);
+        dst = (uint8_t*)(gptr)((unsigned long long)(uint32_t)cc[2] | (unsigned long long)(uint32_t)cc[3] << 32);
+        ad0 = cc[4]; ad1 = cc[5]; bd0 = cc[6]; bd1 = cc[7];
+        Xa = r0[0]; Ya = r0[2]; Xb = r1[1]; Yb = r1[3];
+    }
+    src += src_add; dst += dst_add;
+    if (tid >= NT - 32) {      // vertical weights, as plane_tile writes them
+        const uint32_t f = tid - (NT - 32);
+        const uint32_t wlo = (32u - f) | (f << 8);
+        *reinterpret_cast<uint4*>(lut + f * LUT_STRIDE) =
+            make_uint4(wlo, wlo << 16, __float_as_uint((float)(32u - f) * 0x1p121f), __float_as_uint((float)f * 0x1p121f));
+        *reinterpret_cast<uint32_t*>(lut + f * LUT_STRIDE + 16) = (32u - f) | (f << 16);
+    }
+    // source box of the tile (the maps are monotone in x and in y separately)
+    int bx0a, by0, bw, bh;
+    bool fit;
+    {
+        const int sx00 = (Xa + ad0) >> 10, sx01 = (Xa + ad1) >> 10, sx10 = (Xb + ad0) >> 10, sx11 = (Xb + ad1) >> 10;
+        const int sy00 = (Ya + bd0) >> 10, sy01 = (Ya + bd1) >> 10, sy10 = (Yb + bd0) >> 10, sy11 = (Yb + bd1) >> 10;
+        const int rx0 = min(min(sx00, sx01), min(sx10, sx11)), rx1 = max(max(sx00, sx01), max(sx10, sx11));
+        const int ry0 = min(min(sy00, sy01), min(sy10, sy11)), ry1 = max(max(sy00, sy01), max(sy10, sy11));
+        const bool saturated = rx0 < -32768 || ry0 < -32768 || rx1 > 32767 || ry1 > 32767;
+        const int bx0 = max(rx0, -32768), bx1 = min(rx1, 32767) + 1;
+        by0 = max(ry0, -32768);
+        const int by1 = min(ry1, 32767) + 1;
+        bx0a = bx0 & ~3;
+        bw = bx1 - bx0a + 1;
+        bh = by1 - by0 + 1;
+        fit = !saturated && bw <= 136 && bh <= ROWS && c.border == VS_BORDER_REPLICATE;       // (bh <= ROWS: every staged row lies inside `tile`)
+    }
+    if (fit) {
+        constexpr int NCH = (ROWS * P::CPR + NT - 1) / NT;
+        const int total = bh * P::CPR;
+        const long long rowbytes = (long long)c.sw * P::PXB;
+        uint4 d[NCH];
+#pragma unroll
+        for (int k = 0; k < NCH; k++) {
+            const int i = tid + NT * k;
+            d[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (i < total) {
+                const int r = i / P::CPR, ch = i - r * P::CPR;
+                const int y = by0 + r;
+                const long long xb = (long long)bx0a * P::PXB + 16 * ch;
+                const uint8_t* row = src + (size_t)min(max(y, 0), c.sh - 1) * c.sstride;
+                if (xb >= 0 && xb + 16 <= rowbytes && c.src_aligned) d[k] = *reinterpret_cast<const uint4*>(row + xb);
+                else d[k] = load_chunk_replicate<P::PXB>(row, (int)max(min(xb, (long long)rowbytes + 64), -64ll), c.sw);
+            }
+        }
+        const int x = x0 + 4 * L;
+        if (x1 - x0 == TW - 1 && (c.dw & 3) == 0) {
+            typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+            typedef const __attribute__((address_space(1))) i32x4* g4;
+            const i32x4 a4 = *(g4)(Tg + x), b4 = *(g4)(Tg + c.dw + x);
+            ad[0] = a4.x; ad[1] = a4.y; ad[2] = a4.z; ad[3] = a4.w;
+            bd[0] = b4.x; bd[1] = b4.y; bd[2] = b4.z; bd[3] = b4.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int cx = min(x + i, x1);
+                ad[i] = Tg[cx]; bd[i] = Tg[c.dw + cx];
+            }
+        }
+        if (tid >= TW && tid < TW + P::THP) {
+            const int r = min(y0 + (tid - TW), y1);
+            s_row[tid - TW] = make_int2(Tg[2 * c.dw + r] - (bx0a << 10), Tg[2 * c.dw + c.dh + r] - (by0 << 10));
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; k++) {
+            const int i = tid + NT * k;
+            if (i < total) {
+                const int r = i / P::CPR;
+                *reinterpret_cast<uint4*>(tile + r * P::PB + 16 * (i - r * P::CPR)) = d[k];
+            }
+        }
+    }
+    if (!fit) {
+        plane_direct_tile<1, SB, 8>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        return;
+    }
+    __syncthreads();
+    plane_blend_rows<1, SB>(c, tile, lut, s_row, ad, bd, L, ty, dst, (uint32_t)c.dstride, x0, y0, x1, y1);
+}
+
+// warp_i420_kernel<VS_BORDER_REPLICATE, SB, 1, 0> with the taller box: the same tile sequence, grid order, table blocks and arguments.
+template <int SB>
+__global__ __launch_bounds__(NT, 7) void warp_i422_tall_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
+                                                            uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
+    typedef PlaneCfg<1, SB> P;
+    __shared__ __attribute__((aligned(16))) uint8_t tile[TallCfg<SB>::ROWS * P::PB];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
+    __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];
+    typedef const __attribute__((address_space(4))) int32_t* cptr;
+    const int w = wh & 0xFFFFu, h = wh >> 16;
+    const uint32_t gx1 = (uint32_t)(w + TW - 1) / TW, gy1 = (uint32_t)(h + P::THP - 1) / P::THP;
+    const uint32_t w2 = (uint32_t)w >> 1, h2 = (uint32_t)h;
+    const uint32_t gx2 = (w2 + TW - 1) / TW, gy2 = (h2 + P::THP - 1) / P::THP;
+    const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2, n = tpf * (flags >> 16);
+    const uint32_t lin = blockIdx.x;
+    uint32_t seq = lin;
+    if (flags & 0x100u) {
+        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
+        seq = cx * q + (cx < r ? cx : r) + k;
+    }
+    const uint32_t f = __umulhi(seq, mtpf);
+    uint32_t t = seq - f * tpf;
+    gtab_t T = tabs + (size_t)f * tab_stride;
+    WarpCore c;
+    c.border = (flags >> 2) & 7u;
+    uint32_t gx, mgx;
+    int sadd = 0, dadd = 0;
+    if (t < n1) {
+        c.sstride = sstride; c.dstride = dstride;
+        c.sw = c.dw = w; c.sh = c.dh = h;
+        c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u;
+        gx = gx1; mgx = mgx1;
+    } else {
+        t -= n1;
+        if (t >= n2) { t -= n2; sadd = svu; dadd = dvu; }
+        T += tab_layout(w, h).stride;
+        c.sstride = scpitch; c.dstride = dcpitch;
+        c.sw = c.dw = (int)w2; c.sh = c.dh = (int)h2;
+        c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
+        gx = gx2; mgx = mgx2;
+    }
+    const TabLayout L = tab_layout(c.dw, c.dh);
+    const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
+    plane_tile_tall<SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
+}
+
 // Ints of table workspace per frame of dw x dh (see warp_tables_kernel).
 inline int tab_stride_of(int dw, int dh) { return tab_layout(dw, dh).stride; }
 
@@ -1759,7 +1921,7 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
 // table, then the chroma table whose records name the U planes; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  Returns
 // VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420Layout& sl, const I420Layout& dl, int w, int h, const int32_t* d_tabs,
-                int border, hipStream_t st, int sb = 1, int sx = 1, int sy = 1) {
+                int border, hipStream_t st, int sb = 1, int sx = 1, int sy = 1, bool tall = false) {
     // (sb = 2, I010 / I012: tiles of half the rows; BORDER_REPLICATE: the roll stage's rotation of I010 / I012 surfaces)
     const int thp = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP;
     const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp - 1) / thp, gx2 = ((w >> sx) + TW - 1) / TW, gy2 = ((h >> sy) + thp - 1) / thp;
@@ -1794,10 +1956,20 @@ int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420L
         else if (sx == 1) VS_I420_GO(B, S, 1, 0);        \
         else VS_I420_GO(B, S, 0, 0);                     \
     } while (0)
-    if (sb == 2 && border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 2);
+    // (tall: 4:2:2, BORDER_REPLICATE, host maps that need the taller staged box - launch_warp_i420 decides)
+#define VS_I422_TALL(S)                                                                                                                                    \
+    hipLaunchKernelGGL((warp_i422_tall_kernel<S>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, 1, 0), (uint32_t)sl.pitch, \
+                       (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,    \
+                       (int32_t)dvu)
+    const bool use_tall = tall && sx == 1 && sy == 0 && border == VS_BORDER_REPLICATE;
+    if (use_tall) ;      // (below: the instances that came later are instantiated behind the others, which keep their place in the code object)
+    else if (sb == 2 && border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 2);
     else if (sb == 2) VS_I420_SUB(VS_BORDER_BLACK, 2);
     else if (border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 1);
     else VS_I420_SUB(VS_BORDER_BLACK, 1);
+    if (use_tall && sb == 2) VS_I422_TALL(2);
+    else if (use_tall) VS_I422_TALL(1);
+#undef VS_I422_TALL
 #undef VS_I420_SUB
 #undef VS_I420_GO
     VS_HIP_TRY(hipGetLastError());
@@ -1897,6 +2069,23 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
     return VS_OK;
 }
 
+// Whether a launch of 4:2:2 surfaces under host maps goes to the instances with the taller staged box (warp_i422_tall_kernel): some
+// surface's full-width chroma tile - min(cw, 128) columns, THP rows - has a source box of floor(D) + 2 or + 3 rows, D = (THP - 1) |d| +
+// (columns - 1) |c| under its inverse chroma map [a b; c d], that may outgrow the THP + 9 rows of PlaneCfg and can lie inside THP + 17.
+// Below that (every tile staged as it is) and above it (direct either way) the launch keeps the instance it has always had.
+static bool i420_needs_tall_box(const WarpMaps& mu, int nb, int cw, int sb) {
+    const int thp = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP;
+    const int cols = std::min(cw, TW);
+    for (int i = 0; i < nb; i++) {
+        const double* m = mu.m + (size_t)mu.stride * i;
+        const double D = (thp - 1) * std::fabs(m[4]) + (cols - 1) * std::fabs(m[3]);
+        if (!(D >= 0) || D > 1e6) continue;
+        const int rows = (int)std::floor(D);
+        if (rows + 3 > thp + 9 && rows + 2 <= thp + 17) return true;
+    }
+    return false;
+}
+
 // Per launch of up to 32 surfaces: the luma table and the chroma table (pointer records: the U planes) of every surface - host maps:
 // the NV12 table launch; else one table launch per plane -, then all three planes in ONE grid.  A launch without tables (a caller's
 // tables exist for launches of WARP_TAB_MIN surfaces and more only; the scratch tables serve any number), or one whose geometry is
@@ -1955,7 +2144,8 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
             }
         }
         if (tabs.what == VS_WARP_TABLES_ONLY) continue;
-        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st, sb, sx, sy) : VS_ERR_UNSUPPORTED;
+        const bool tall = maps.host && sx == 1 && sy == 0 && border == VS_BORDER_REPLICATE && i420_needs_tall_box(mu, nb, cw, sb);
+        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st, sb, sx, sy, tall) : VS_ERR_UNSUPPORTED;
         if (one != VS_ERR_UNSUPPORTED) {
             VS_TRY(one);
             continue;

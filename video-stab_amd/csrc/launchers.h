@@ -8,6 +8,7 @@
 #include <string>
 
 #include "pixfmt.h"
+#include "planar_layout.h"
 #include "traj_state.h"
 #include "vs_common.h"
 #include "warp_tab.h"
@@ -49,46 +50,18 @@ int gftt_fill_item(void* host_item, const uint8_t* d_gray, size_t stride, int w,
 int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_size, hipStream_t st, int what);
 
 // ---- k_warp.hip: planar surfaces (I420 / YV12, I010 / I012; 4:2:2 and 4:4:4: I422, I444, I210, I212, I410, I412) of w x h luma pixels
-// Where the planes of a surface lie: rows of `pitch` bytes of luma at the surface pointer, the U and V planes (h >> sy rows of
-// w >> sx samples, `cpitch` bytes apart) u and v bytes behind it.  One layout for all source surfaces of a call, one for all destinations.
-struct I420Layout { size_t pitch, cpitch, u, v; };
-// The layout a caller describes with 0 = default per field: chroma pitch = pitch >> sx, U behind the h luma rows, V behind U.
-inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, size_t c_pitch, int sx = 1, int sy = 1) {
-    I420Layout l;
-    l.pitch = pitch;
-    l.cpitch = c_pitch ? c_pitch : pitch >> sx;
-    l.u = u_off ? u_off : (size_t)h * pitch;
-    l.v = v_off ? v_off : l.u + (size_t)(h >> sy) * l.cpitch;
-    return l;
-}
+// (I420Layout, i420_layout: planar_layout.h)
 // Launches with tables warp the three planes of their surfaces in ONE grid (warp_i420_kernel); the tables are an NV12 surface's
 // (planar_tab_ints per frame: luma table, then one chroma table whose pointer records name the U planes), the maps as for NV12
 // (m: luma, m + 6: chroma).  A call with the scratch tables builds them for any number of surfaces.
 // sample_bytes = 2: I010 / I012 surfaces - the same planes with 16-bit samples; layouts in bytes, pointers, pitches and offsets even.
 // sx, sy: the chroma shifts (4:2:0 needs even w and h, 4:2:2 an even w, 4:4:4 takes any size).
+// Host maps, 4:2:2 and VS_BORDER_REPLICATE (the roll stage, vs_op_warp_affine_planar): a launch in which some surface's chroma tiles may
+// outgrow the staged box and can fit the taller one goes to the instances with THP + 17 staged rows (k_warp.hip, warp_i422_tall_kernel).
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout src, I420Layout dst, int w, int h, WarpMaps maps, int border,
                      WarpTabs tabs, hipStream_t st, int sample_bytes = 1, int sx = 1, int sy = 1);
 
-// ---- k_roll.hip, k_azc.hip: planar 4:2:0 surfaces (VS_FMT_I420, VS_FMT_I010, VS_FMT_I012) of the stages around the stabilizer
-// The geometry and layout rules of a planar surface handed to the roll / zoom stages (those vs_stab enforces).  need_w / need_h: the
-// samples per row and the rows the layout must hold - the picture's, or for the zoom stage's result the larger of the picture's and
-// the stage's output size (640 x 360 unless vs_azc_set_output_size said otherwise).  Fills *l with the defaults resolved, or *msg with a text that names the stage and the format.
-inline int planar_layout_check(int fmt, const void* ptr, int w, int h, const vs_i420_layout* in, int need_w, int need_h, const char* stage,
-                               I420Layout* l, std::string* msg) {
-    const int sb = pixfmt(fmt)->sample_bytes;
-    const char* name = pixfmt(fmt)->name;
-    auto fail = [&](const char* what) { *msg = std::string(stage) + ": " + name + ": " + what; return (int)VS_ERR_INVALID_ARG; };
-    if ((w & 1) || (h & 1) || w < 2 || h < 2) return fail("w and h must be even");
-    if (!in || in->pitch < (size_t)need_w * sb) return fail("the pitch must hold a row of the picture");
-    if (sb == 2 && (((uintptr_t)ptr | in->pitch | in->c_pitch | in->u_off | in->v_off) & 1)) return fail("pointers, pitches and plane offsets must be even (16-bit samples)");
-    if (!in->c_pitch && (in->pitch & (size_t)(2 * sb - 1))) return fail(sb == 2 ? "the default chroma pitch needs a pitch that is a multiple of 4" : "the default chroma pitch needs an even pitch");
-    *l = i420_layout(in->pitch, need_h, in->u_off, in->v_off, in->c_pitch);
-    if (l->cpitch < (size_t)(need_w / 2) * sb) return fail(sb == 2 ? "the chroma pitch must be at least w bytes" : "the chroma pitch must be at least w / 2");
-    if (l->u < (size_t)need_h * l->pitch || l->v < (size_t)need_h * l->pitch) return fail("the chroma planes must start behind the luma rows");
-    const size_t cb = (size_t)(need_h / 2) * l->cpitch, lo = std::min(l->u, l->v), hi = std::max(l->u, l->v);
-    if (hi < lo + cb) return fail("the U and V planes overlap");
-    return VS_OK;
-}
+// ---- k_roll.hip, k_azc.hip: the geometry and layout rules of their three-plane surfaces are planar_layout_check (planar_layout.h)
 
 // ---- k_cvt.hip: YUV surfaces <-> interleaved 8-bit RGB (vs_op_cvt_yuv_to_rgb, vs_op_cvt_rgb_to_yuv, vs_enh_apply_yuv_dev)
 constexpr int CVT_MAX_SURFACES = 32;        // of one launch: their pointers are kernel arguments

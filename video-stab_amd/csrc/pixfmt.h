@@ -34,7 +34,7 @@ struct PixFmt {
 
     bool luma_uv() const { return kind == PIX_LUMA_UV; }
     bool three_planes() const { return kind == PIX_THREE_PLANES; }
-    bool planar_420() const { return three_planes() && sy; }                    // what the roll and zoom/crop stages take
+    bool planar_420() const { return three_planes() && sy; }                    // the three-plane 4:2:0 formats
     bool default_chroma_pitch_is_half() const { return three_planes() && sx; }
     // rows of `pitch` bytes of a whole (packed) frame: the h luma rows and the chroma rows behind them
     int rows(int h) const { return three_planes() ? h + (2 * (h >> sy) >> sx) : luma_uv() ? h * 3 / 2 : h; }

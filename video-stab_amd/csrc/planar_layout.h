@@ -1,0 +1,56 @@
+// Where the planes of a three-plane surface (VS_FMT_I420 ... VS_FMT_I412) lie, and what the roll and zoom/crop stages refuse about
+// such a surface.  Plain C++ over integers like pixfmt.h: no HIP, no object - tests/cpp/planar_layout_check.cpp compiles this header
+// alone and asks the rules without a device.
+#ifndef VS_PLANAR_LAYOUT_H
+#define VS_PLANAR_LAYOUT_H
+
+#include <algorithm>
+#include <string>
+
+#include "pixfmt.h"
+
+namespace vsd {
+
+// Where the planes of a surface lie: rows of `pitch` bytes of luma at the surface pointer, the U and V planes (h >> sy rows of
+// w >> sx samples, `cpitch` bytes apart) u and v bytes behind it.  One layout for all source surfaces of a call, one for all destinations.
+struct I420Layout { size_t pitch, cpitch, u, v; };
+// The layout a caller describes with 0 = default per field: chroma pitch = pitch >> sx, U behind the h luma rows, V behind U.
+inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, size_t c_pitch, int sx = 1, int sy = 1) {
+    I420Layout l;
+    l.pitch = pitch;
+    l.cpitch = c_pitch ? c_pitch : pitch >> sx;
+    l.u = u_off ? u_off : (size_t)h * pitch;
+    l.v = v_off ? v_off : l.u + (size_t)(h >> sy) * l.cpitch;
+    return l;
+}
+
+// ---- k_roll.hip, k_azc.hip: three-plane surfaces (VS_FMT_I420 ... VS_FMT_I412) of the stages around the stabilizer
+// The geometry and layout rules of a planar surface handed to the roll / zoom stages (those vs_stab enforces).  need_w / need_h: the
+// samples per row and the rows the layout must hold - the picture's, or for the zoom stage's result the larger of the picture's and
+// the stage's output size (640 x 360 unless vs_azc_set_output_size said otherwise).  Fills *l with the defaults resolved, or *msg with a text that names the stage and the format.
+// (sx, sy): the format's chroma shifts - a chroma plane holds need_h >> sy rows of need_w >> sx samples, the default chroma pitch is
+// pitch >> sx.  The texts of the 4:2:0 formats are those they have always had; 4:2:2 and 4:4:4 word the chroma pitch as the stream does.
+inline int planar_layout_check(int fmt, const void* ptr, int w, int h, const vs_i420_layout* in, int need_w, int need_h, const char* stage,
+                               I420Layout* l, std::string* msg) {
+    const PixFmt& f = *pixfmt(fmt);
+    const int sb = f.sample_bytes, sx = f.sx, sy = f.sy;
+    const char* name = f.name;
+    auto fail = [&](const std::string& what) { *msg = std::string(stage) + ": " + name + ": " + what; return (int)VS_ERR_INVALID_ARG; };
+    if ((w & 1) || (h & 1) || w < 2 || h < 2) return fail("w and h must be even");
+    if (!in || in->pitch < (size_t)need_w * sb) return fail("the pitch must hold a row of the picture");
+    if (sb == 2 && (((uintptr_t)ptr | in->pitch | in->c_pitch | in->u_off | in->v_off) & 1)) return fail("pointers, pitches and plane offsets must be even (16-bit samples)");
+    if (!in->c_pitch && (in->pitch & (size_t)((sb << sx) - 1))) return fail(sb == 2 ? "the default chroma pitch needs a pitch that is a multiple of 4" : "the default chroma pitch needs an even pitch");
+    *l = i420_layout(in->pitch, need_h, in->u_off, in->v_off, in->c_pitch, sx, sy);
+    const size_t crow = (size_t)(need_w >> sx) * sb;
+    if (l->cpitch < crow) {
+        if (sy) return fail(sb == 2 ? "the chroma pitch must be at least w bytes" : "the chroma pitch must be at least w / 2");
+        return fail("the chroma pitch must hold a chroma row (" + std::to_string(crow) + " bytes)");
+    }
+    if (l->u < (size_t)need_h * l->pitch || l->v < (size_t)need_h * l->pitch) return fail("the chroma planes must start behind the luma rows");
+    const size_t cb = (size_t)(need_h >> sy) * l->cpitch, lo = std::min(l->u, l->v), hi = std::max(l->u, l->v);
+    if (hi < lo + cb) return fail("the U and V planes overlap");
+    return VS_OK;
+}
+
+}  // namespace vsd
+#endif

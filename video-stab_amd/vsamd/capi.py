@@ -965,7 +965,7 @@ class VsLib:
 
 
 class I420LayoutC(C.Structure):
-    """struct vs_i420_layout: where the planes of an I420 / I010 / I012 surface lie, in bytes (0 = the packed default of a field)."""
+    """struct vs_i420_layout: where the planes of a three-plane surface (I420 ... I412) lie, in bytes (0 = the packed default of a field)."""
     _fields_ = [("pitch", C.c_size_t), ("c_pitch", C.c_size_t), ("u_off", C.c_size_t), ("v_off", C.c_size_t)]
 
 
@@ -1093,7 +1093,8 @@ class AutoZoomCrop:
         return list(t)
 
     def apply_i420_dev(self, fmt, d_in, w, h, lin, d_out, lout):
-        """apply_nv12_dev for a planar surface (vs_azc_apply_i420_dev): fmt FMT_I420 / FMT_I010 / FMT_I012, lin / lout: i420_layout()."""
+        """apply_nv12_dev for a planar surface (vs_azc_apply_i420_dev): fmt any three-plane format (FMT_I420 ... FMT_I412), lin / lout:
+        i420_layout()."""
         t = C.c_int64(-1)
         self._check(self.lib.vs_azc_apply_i420_dev(self.h, fmt, d_in, w, h, C.byref(lin), d_out, C.byref(lout), C.byref(t)))
         return t.value
@@ -1417,7 +1418,8 @@ class RollCorrection:
         self._check(self.lib.vs_roll_correct_p010_dev(self.h, d_in, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset))
 
     def correct_i420_dev(self, fmt, d_in, w, h, lin, d_out, lout):
-        """correct_nv12_dev for a planar surface (vs_roll_correct_i420_dev): fmt FMT_I420 / FMT_I010 / FMT_I012, lin / lout: i420_layout()."""
+        """correct_nv12_dev for a planar surface (vs_roll_correct_i420_dev): fmt any three-plane format (FMT_I420 ... FMT_I412), lin / lout:
+        i420_layout()."""
         self._check(self.lib.vs_roll_correct_i420_dev(self.h, fmt, d_in, w, h, C.byref(lin), d_out, C.byref(lout)))
 
     def correct_i420_dev_n(self, fmt, d_ins, w, h, lin, d_outs, lout):
