@@ -45,7 +45,8 @@ extern "C" {
  *    vs_op_cvt_rgb_to_yuv and vs_enh_apply_yuv_dev; the enhancer on a batch of YUV surfaces in one fused launch:
  *    vs_enh_apply_yuv_batch_dev, vs_enh_last_fused and vs_enh_yuv_plan; the colour space of the conversions: struct
  *    vs_cvt_colorimetry with vs_op_cvt_yuv_to_rgb_cs, vs_op_cvt_rgb_to_yuv_cs, vs_enh_set_yuv_colorimetry, vs_cvt_coefficients and
- *    vs_cvt_colorimetry_guess (new entry points, new values and new structs only: no existing struct or entry point changed, so
+ *    vs_cvt_colorimetry_guess; conversion between the YUV surface formats: struct vs_yuv_cvt_desc with vs_op_cvt_yuv_to_yuv and
+ *    vs_yuv_surface_layout (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
@@ -1001,6 +1002,58 @@ int vs_cvt_coefficients(const vs_cvt_colorimetry* cs, int32_t out[16]);
  * never BT.2020, never full range; chroma_down = VS_CVT_CHROMA_TOPLEFT.  A convenience for the caller: the library itself never
  * guesses. */
 void vs_cvt_colorimetry_guess(int w, int h, vs_cvt_colorimetry* out);
+
+/* ---- conversion between YUV surface formats in HBM (tests/yuvref.py states what it computes) -------------------------------------
+ * Every stage returns the format it was given; what follows the library often takes another one - a hardware encoder NV12 and
+ * P010, x264 and libvpx I420 - and a software decoder delivers I420 / I010 / I210 where a hardware path delivers NV12 / P010.  The
+ * reference bridges this on the host (videoconvert ! video/x-raw,format=NV12, examples/vs.cpp:298, src/RTSPServer.cpp:85).  This
+ * call does it on the device without a colour matrix and without an RGB frame: samples keep every bit the destination can hold.
+ *
+ * vs_op_cvt_yuv_to_yuv converts n = 1 .. 32 surfaces of one geometry from src_fmt in layout `in` to dst_fmt in layout `out`, in ONE
+ * launch, asynchronous on `stream`; d_src and d_dst are HOST arrays of n device pointers, read during the call.  src_fmt and
+ * dst_fmt: any of the eleven non-interleaved formats (VS_FMT_NV12, VS_FMT_P010, VS_FMT_I420 ... VS_FMT_I412) in any pairing; the same
+ * format twice is a repack to another pitch or plane order (I420 <-> YV12 by swapping u_off and v_off).  Layouts, their defaults and
+ * their rules are those of vs_op_cvt_yuv_to_rgb, on both sides.  desc: NULL and the all-zero struct mean the same - truncate,
+ * top-left.
+ *
+ * Definition: exact integer arithmetic in two steps.
+ *  Step 1, depth, per sample and on every plane.  A format holds values of b bits: 8-bit formats b = 8; the low-bit formats b = 10
+ *  or 12, the value in the low bits; P010 b = 16 - the whole word, its most significant bits meaningful (P012 / P016 content passes
+ *  through, as everywhere in this header).  d = b_in - b_out.
+ *    d = 0: the word is unchanged (out-of-range high bits of a low-bit format are copied, not clamped).
+ *    otherwise v = sample, for a low-bit source v = min(sample, 2^b_in - 1), and
+ *    d < 0: out = v << -d
+ *    d > 0, VS_YUV_DEPTH_TRUNCATE: out = v >> d
+ *    d > 0, VS_YUV_DEPTH_ROUND:    out = min((v + (1 << (d - 1))) >> d, 2^b_out - 1)
+ *  Truncation is the default because it gives the byte that the analysis and vs_op_cvt_yuv_to_rgb read: P010 -> NV12 is sample >> 8,
+ *  I010 -> I420 is min(sample >> 2, 255).  Going up in depth and coming back down is the identity under either rule.
+ *  Step 2, chroma siting, on the step-1 values of U and V, with (sx, sy) of each side (the format set only ever moves both axes
+ *  the same way).
+ *    same shifts: copy.
+ *    down, dsx = sx_out - sx_in, dsy = sy_out - sy_in, s = dsx + dsy > 0:
+ *      VS_CVT_CHROMA_TOPLEFT: the sample at (cx << dsx, cy << dsy)
+ *      VS_CVT_CHROMA_MEAN:    (sum of the (1 << dsx) x (1 << dsy) block + (1 << (s - 1))) >> s; the largest intermediate is 4 * 65535 + 2
+ *    up, usx = sx_in - sx_out, usy = sy_in - sy_out: the sample at (cx >> usx, cy >> usy), nearest.  Interpolating filters and
+ *    left-sited down-filters are not built, as in the colour conversion.
+ *  NV12 / P010 interleave (U, V) pairs, the three-plane formats do not: that is layout only.
+ * Refusals (VS_ERR_INVALID_ARG, decided before any device call; vs_last_error names the call, the side - "source" / "destination" -
+ * and the format): everything vs_op_cvt_yuv_to_rgb refuses about a YUV side, for either side - so w must be a multiple of
+ * 1 << max(sx_in, sx_out) and h of 1 << max(sy_in, sy_out); d_src[i] == d_dst[j] for any i, j (surfaces may not overlap; equal
+ * pointers are the part that can be checked); a descriptor field outside its enum; a reserved field that is not 0.  Valid arguments
+ * on a machine without a device: VS_ERR_NO_DEVICE.  Nothing outside a row's samples is written (padding and gaps keep their bytes). */
+enum vs_yuv_depth_down { VS_YUV_DEPTH_TRUNCATE = 0, VS_YUV_DEPTH_ROUND = 1 };
+typedef struct vs_yuv_cvt_desc { int32_t depth_down;      /* vs_yuv_depth_down */
+                                 int32_t chroma_down;     /* vs_cvt_chroma: TOPLEFT / MEAN */
+                                 int32_t reserved[2];     /* must be 0 */ } vs_yuv_cvt_desc;
+int vs_op_cvt_yuv_to_yuv(int src_fmt, const void* const* d_src, const vs_i420_layout* in,
+                         int dst_fmt, void* const* d_dst, const vs_i420_layout* out,
+                         int n, int w, int h, const vs_yuv_cvt_desc* desc, void* stream);
+/* Host only, needs no device: the layout of a w x h surface of `fmt` with every default filled in (*resolved: for NV12 / P010
+ * c_pitch = pitch, u_off = the interleaved plane, v_off = 0 - a layout the conversions accept as it is), and the number of bytes
+ * from the surface pointer to the end of its last sample (*bytes) - what a caller allocates for a format it did not hold before.
+ * lay == NULL: all defaults at the tight pitch (w samples).  resolved and bytes may each be NULL.  Refuses exactly what
+ * vs_op_cvt_yuv_to_rgb refuses about a format, a size and a layout (VS_ERR_INVALID_ARG, the text in vs_last_error). */
+int vs_yuv_surface_layout(int fmt, int w, int h, const vs_i420_layout* lay, vs_i420_layout* resolved, size_t* bytes);
 
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */

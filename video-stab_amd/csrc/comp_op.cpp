@@ -1,8 +1,9 @@
 // The compositing stages as operators (include/vs_stab.h): vs_op_copy_make_border, vs_op_fade_blend, vs_op_fade_update, the
 // vs_op_canvas_* object and the colour conversions vs_op_cvt_yuv_to_rgb[_cs] / vs_op_cvt_rgb_to_yuv[_cs], with the integers of
-// their colour spaces (cvt_resolve, vs_cvt_coefficients, vs_cvt_colorimetry_guess).  Nothing is computed here: each
+// their colour spaces (cvt_resolve, vs_cvt_coefficients, vs_cvt_colorimetry_guess), and the conversion between YUV surface formats
+// vs_op_cvt_yuv_to_yuv with vs_yuv_surface_layout.  Nothing is computed here: each
 // entry checks its arguments and calls what the pipeline calls (launch_make_border, launch_fade_blend, launch_fade_update of
-// k_traj.hip; canvas_apply of k_canvas.hip; launch_cvt_* of k_cvt.hip).
+// k_traj.hip; canvas_apply of k_canvas.hip; launch_cvt_* of k_cvt.hip; launch_cvt_yuv_to_yuv of k_yuvcvt.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -186,6 +187,64 @@ int vs_op_cvt_yuv_to_rgb(int yuv_fmt, const void* const* d_surfaces, const vs_i4
 int vs_op_cvt_rgb_to_yuv(int rgb_fmt, const void* const* d_rgb, size_t rgb_stride, int yuv_fmt, void* const* d_surfaces, const vs_i420_layout* out,
                          int n, int w, int h, void* stream) {
     return vs_op_cvt_rgb_to_yuv_cs(rgb_fmt, d_rgb, rgb_stride, yuv_fmt, d_surfaces, out, n, w, h, nullptr, stream);
+}
+
+int vs_op_cvt_yuv_to_yuv(int src_fmt, const void* const* d_src, const vs_i420_layout* in, int dst_fmt, void* const* d_dst, const vs_i420_layout* out,
+                         int n, int w, int h, const vs_yuv_cvt_desc* desc, void* stream) {
+    static const char call[] = "vs_op_cvt_yuv_to_yuv";
+    static const vs_yuv_cvt_desc dflt = {VS_YUV_DEPTH_TRUNCATE, VS_CVT_CHROMA_TOPLEFT, {0, 0}};
+    I420Layout li, lo;
+    std::string msg;
+    // each side by the rules of the colour conversions; w and h are then multiples of 1 << sx, 1 << sy of the coarser side as well
+    if (cvt_check_yuv("vs_op_cvt_yuv_to_yuv: source", src_fmt, d_src, n, in, w, h, &li, &msg) != VS_OK ||
+        cvt_check_yuv("vs_op_cvt_yuv_to_yuv: destination", dst_fmt, d_dst, n, out, w, h, &lo, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    const PixFmt &sf = *pixfmt(src_fmt), &df = *pixfmt(dst_fmt);
+    const std::string pair = std::string(call) + ": source " + sf.name + ", destination " + df.name + ": ";
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++)
+            if (d_src[i] == d_dst[j])
+                return refuse(VS_ERR_INVALID_ARG, (pair + "source surface " + std::to_string(i) + " is destination surface " + std::to_string(j) +
+                                                   " (surfaces may not overlap)").c_str());
+    if (!desc) desc = &dflt;
+    auto bad = [&](const char* field, int32_t v, const char* want) {
+        return refuse(VS_ERR_INVALID_ARG, (pair + "descriptor: " + field + " = " + std::to_string(v) + " " + want).c_str());
+    };
+    if (desc->depth_down < VS_YUV_DEPTH_TRUNCATE || desc->depth_down > VS_YUV_DEPTH_ROUND)
+        return bad("depth_down", desc->depth_down, "is not a vs_yuv_depth_down (0, 1)");
+    if (desc->chroma_down < VS_CVT_CHROMA_TOPLEFT || desc->chroma_down > VS_CVT_CHROMA_MEAN)
+        return bad("chroma_down", desc->chroma_down, "is not a vs_cvt_chroma (0, 1)");
+    for (int k = 0; k < 2; k++)
+        if (desc->reserved[k] != 0) return bad(k ? "reserved[1]" : "reserved[0]", desc->reserved[k], "must be 0");
+    VS_TRY(ensure_device());
+    return launch_cvt_yuv_to_yuv(sf, d_src, li, df, d_dst, lo, n, w, h, yuv_depth(sf, df, desc->depth_down == VS_YUV_DEPTH_ROUND),
+                                 desc->chroma_down == VS_CVT_CHROMA_MEAN, (hipStream_t)stream);
+}
+
+int vs_yuv_surface_layout(int fmt, int w, int h, const vs_i420_layout* lay, vs_i420_layout* resolved, size_t* bytes) {
+    const PixFmt* f = pixfmt(fmt);
+    vs_i420_layout tight = {0, 0, 0, 0};
+    if (!lay && f && w > 0) {
+        tight.pitch = (size_t)w * f->sample_bytes;
+        lay = &tight;
+    }
+    // the rules are those of a conversion's side, asked about one surface at an address that no rule objects to
+    static const void* const aligned_surface[1] = {(const void*)(uintptr_t)4096};
+    I420Layout l;
+    std::string msg;
+    if (cvt_check_yuv("vs_yuv_surface_layout", fmt, aligned_surface, 1, lay ? lay : &tight, w, h, &l, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    if (resolved) {
+        resolved->pitch = l.pitch;
+        resolved->c_pitch = l.cpitch;
+        resolved->u_off = l.u;
+        resolved->v_off = f->luma_uv() ? 0 : l.v;       // NV12 / P010: one interleaved plane, at u_off
+    }
+    if (bytes) {
+        const size_t crow_bytes = f->chroma_row_bytes(w) * (f->luma_uv() ? 2 : 1);
+        *bytes = std::max(l.u, l.v) + (size_t)((h >> f->sy) - 1) * l.cpitch + crow_bytes;
+    }
+    return VS_OK;
 }
 
 int vs_cvt_coefficients(const vs_cvt_colorimetry* cs, int32_t out[16]) {

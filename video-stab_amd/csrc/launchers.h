@@ -81,6 +81,29 @@ int launch_cvt_yuv_to_rgb(const PixFmt& yf, const void* const* surfaces, const I
 int launch_cvt_rgb_to_yuv(const PixFmt& rf, const void* const* rgb, size_t rgb_stride, const PixFmt& yf, void* const* surfaces, const I420Layout& l,
                           int n, int w, int h, const CvtCoef& k, hipStream_t st);
 
+// ---- k_yuvcvt.hip: YUV surfaces of one format -> YUV surfaces of another (vs_op_cvt_yuv_to_yuv)
+// The depth step of a conversion as the kernel takes it: out = min(((min(sample, in_max) + add) >> down) << up, out_max).
+// yuv_depth: the values for a pair of formats (a format's b bits: 8; 10 / 12 in the low bits; P010: the whole word, 16) and a
+// vs_yuv_depth_down rule; equal depths copy the word (no clamp).
+struct YuvDepth { uint32_t in_max, add, down, up, out_max; };
+inline int yuv_value_bits(const PixFmt& f) { return f.luma_uv() && f.sample_bytes == 2 ? 16 : f.bits; }
+inline YuvDepth yuv_depth(const PixFmt& sf, const PixFmt& df, bool round) {
+    const int bi = yuv_value_bits(sf), bo = yuv_value_bits(df), d = bi - bo;
+    YuvDepth k = {0xffffu, 0u, 0u, 0u, 0xffffu};
+    if (d == 0) return k;
+    if (sf.three_planes() && sf.sample_bytes == 2) k.in_max = (1u << bi) - 1u;      // a low-bit source: bits above its range clamp
+    if (d < 0) k.up = (uint32_t)-d;
+    else {
+        k.down = (uint32_t)d;
+        k.add = round ? 1u << (d - 1) : 0u;
+        k.out_max = (1u << bo) - 1u;
+    }
+    return k;
+}
+// n <= CVT_MAX_SURFACES surfaces of one geometry in one launch (grid z = surface); the layouts as cvt_check_yuv resolved them
+int launch_cvt_yuv_to_yuv(const PixFmt& sf, const void* const* src, const I420Layout& in, const PixFmt& df, void* const* dst, const I420Layout& out,
+                          int n, int w, int h, const YuvDepth& depth, bool mean, hipStream_t st);
+
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,
                      float* t_out = nullptr);

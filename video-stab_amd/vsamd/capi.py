@@ -487,6 +487,9 @@ class VsLib:
             L.vs_cvt_coefficients.argtypes = [csp, i32p]
             L.vs_cvt_colorimetry_guess.argtypes = [C.c_int, C.c_int, csp]
             L.vs_cvt_colorimetry_guess.restype = None
+            L.vs_op_cvt_yuv_to_yuv.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(VsYuvCvtDesc), vp]
+            L.vs_yuv_surface_layout.argtypes = [C.c_int, C.c_int, C.c_int, lp, lp, C.POINTER(C.c_size_t)]
         except AttributeError:      # a library of an earlier build (A/B measurements)
             pass
 
@@ -905,6 +908,42 @@ class VsLib:
                 outs = [o.reshape(fmt_frame_rows(yuv_fmt, h), w) for o in outs]
         return outs[0] if single else outs
 
+    def yuv_surface_layout(self, fmt, w, h, layout=None):
+        """vs_yuv_surface_layout (host only): ((pitch, c_pitch, u_off, v_off), bytes) - the layout of a w x h surface with every default
+        filled in and the bytes from the surface pointer to the end of its last sample.  layout: None (all defaults at the tight
+        pitch) or (pitch[, c_pitch[, u_off[, v_off]]]) in bytes, 0 = the default of a field."""
+        res, nbytes = I420LayoutC(), C.c_size_t()
+        self.check(self.lib.vs_yuv_surface_layout(fmt, w, h, C.byref(I420LayoutC(*layout)) if layout else None, C.byref(res), C.byref(nbytes)))
+        return (res.pitch, res.c_pitch, res.u_off, res.v_off), nbytes.value
+
+    def cvt_yuv_to_yuv(self, src_fmt, surfaces, w, h, dst_fmt, in_layout=None, out_layout=None, desc=None, raw=False, fill=0xA5):
+        """vs_op_cvt_yuv_to_yuv.  surfaces: one surface of w x h pixels or a list of up to 32, converted in one launch - packed frames
+        or flat buffers in `in_layout`, as for cvt_yuv_to_rgb.  -> per surface the packed frame of dst_fmt ((rows, w) array of its
+        dtype) or, with an `out_layout`, the flat array of that layout up to its last sample (vs_yuv_surface_layout); raw=True: the
+        whole destination as bytes instead, those bytes + 16 prefilled with `fill`.  desc: None (a null descriptor), a VsYuvCvtDesc
+        or (depth_down[, chroma_down]) - YUV_DEPTH_TRUNCATE / YUV_DEPTH_ROUND, CVT_CHROMA_TOPLEFT / CVT_CHROMA_MEAN."""
+        fi, fo = PIXFMT[src_fmt], PIXFMT[dst_fmt]
+        srcs, single = _surface_list(surfaces)
+        n = len(srcs)
+        lin = I420LayoutC(*(in_layout or (fi.sample_bytes * w, 0, 0, 0)))
+        lout = I420LayoutC(*(out_layout or (fo.sample_bytes * w, 0, 0, 0)))
+        _, size = self.yuv_surface_layout(dst_fmt, w, h, out_layout)
+        d_in = [DevBuf.from_array(self, s) for s in srcs]
+        d_out = [DevBuf.from_array(self, np.full(size + 16, fill, np.uint8)) for _ in range(n)]
+        try:
+            self.check(self.lib.vs_op_cvt_yuv_to_yuv(src_fmt, _ptr_array(d_in), C.byref(lin), dst_fmt, _ptr_array(d_out), C.byref(lout), n, w, h,
+                                                     _yuv_desc_ref(desc), None))
+            self.sync()
+            outs = [d.download((size + 16,), np.uint8) for d in d_out]
+        finally:
+            for d in d_in + d_out:
+                d.free()
+        if not raw:
+            outs = [o[:size].view(fmt_dtype(dst_fmt)) for o in outs]
+            if not out_layout:
+                outs = [o.reshape(fmt_frame_rows(dst_fmt, h), w) for o in outs]
+        return outs[0] if single else outs
+
     def enh_yuv_plan(self, params, yuv_fmt, in_place=False):
         """vs_enh_yuv_plan (host only): 1 = Enhancer.apply_yuv_batch_dev would take the fused launch, 0 = the three calls per surface,
         < 0 = minus the status of the refusal.  params: VsEnhParams or None."""
@@ -986,6 +1025,23 @@ def _cs_ref(colorimetry):
     if not isinstance(colorimetry, CvtColorimetry):
         colorimetry = CvtColorimetry(*colorimetry)
     return C.byref(colorimetry)
+
+
+class VsYuvCvtDesc(C.Structure):
+    """struct vs_yuv_cvt_desc: how vs_op_cvt_yuv_to_yuv goes down in depth and in chroma resolution (all zero = truncate, top-left)."""
+    _fields_ = [("depth_down", C.c_int32), ("chroma_down", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+YUV_DEPTH_TRUNCATE, YUV_DEPTH_ROUND = 0, 1
+
+
+def _yuv_desc_ref(desc):
+    """None -> a null pointer; a VsYuvCvtDesc or (depth_down[, chroma_down]) -> a reference to the struct."""
+    if desc is None:
+        return None
+    if not isinstance(desc, VsYuvCvtDesc):
+        desc = VsYuvCvtDesc(*desc)
+    return C.byref(desc)
 
 
 def i420_layout(pitch, c_pitch=0, u_off=0, v_off=0):
