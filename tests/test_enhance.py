@@ -512,8 +512,10 @@ def test_gpu_enhance_device_entry_points(oracle, gpu, enh):
         enh.apply_batch_dev(p, [b.ptr for b in ins], [b.ptr for b in outs], w, h, pitch, pitch)
         enh.sync()
         for f, o in zip(frames, outs):
-            got = o.download((h, pitch), np.uint8)[:, :w * 3].reshape(h, w, 3)
+            rows = o.download((h, pitch), np.uint8)
+            got = rows[:, :w * 3].reshape(h, w, 3)
             assert (got == oracle.enhance(f, p)).all(), cfg
+            assert not rows[:, w * 3:].any(), (cfg, "the padding behind a row was written")
     with pytest.raises(Exception):
         enh.apply(frames[0], oracle.enh_params(enable_unsharp=1, sharpness=1.0, blur_sigma=9.0))   # 55 taps
 
