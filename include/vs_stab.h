@@ -46,7 +46,8 @@ extern "C" {
  *    vs_enh_apply_yuv_batch_dev, vs_enh_last_fused and vs_enh_yuv_plan; the colour space of the conversions: struct
  *    vs_cvt_colorimetry with vs_op_cvt_yuv_to_rgb_cs, vs_op_cvt_rgb_to_yuv_cs, vs_enh_set_yuv_colorimetry, vs_cvt_coefficients and
  *    vs_cvt_colorimetry_guess; conversion between the YUV surface formats: struct vs_yuv_cvt_desc with vs_op_cvt_yuv_to_yuv and
- *    vs_yuv_surface_layout (new entry points, new values and new structs only: no existing struct or entry point changed, so
+ *    vs_yuv_surface_layout; crop-and-zoom on YUV streams: vs_stab_set_yuv_crop_zoom, vs_batch_set_yuv_crop_zoom and vs_op_resize_jobs
+ *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
 
@@ -85,7 +86,7 @@ typedef enum vs_pixfmt {
  *    are 0, each by itself), rounded once, half to even: (S + 511 + ((S >> 10) & 1)) >> 10.  For ten-bit content that is
  *    what OpenCV's float blend gives; for arbitrary 16-bit content it is the definition (docs/opencv_semantics.md);
  *  - everything else follows NV12: the last frame of a flush comes back unwarped; border pad, crop-and-zoom, fade and the
- *    virtual canvas are refused as for NV12.
+ *    virtual canvas are refused as for NV12 (crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom).
  * The two stages around the stabilizer take P010 surfaces too (vs_roll_correct_p010_dev, vs_azc_apply_p010_dev):
  *  - analysis plane: both analyse the 8-bit plane of the luma samples' high bytes (sample >> 8), the plane the stabilizer analyses.
  *    Smoothed and detected angle, line counts, content mask, contours, info8 and the crop rectangle are bit-identical to those of
@@ -120,7 +121,8 @@ typedef enum vs_pixfmt16 {
  *    in float (cv::warpAffine treats channels independently: these are the two channels of the NV12 chroma plane's warp),
  *    INTER_LINEAR, BORDER_CONSTANT 0;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are refused as for NV12 (VS_ERR_UNSUPPORTED); the enhancer and the C++ classes do not take it.
+ *    are refused as for NV12 (VS_ERR_UNSUPPORTED; crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom); the
+ *    enhancer and the C++ classes do not take it.
  * The two stages around the stabilizer take I420 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev; layouts as
  * struct vs_i420_layout): every observable is again that of the NV12 call on the same samples, the planes de-interleaved -
  *  - analysis plane: Y itself (line search of the roll stage, content mask of the zoom stage);
@@ -149,7 +151,8 @@ typedef enum vs_pixfmt_planar {
  *    halved in float; INTER_LINEAR, BORDER_CONSTANT 0, the blend of P010 to the letter (S rounded once, half to even).  The warp
  *    does not depend on the bit depth;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are VS_ERR_UNSUPPORTED; the enhancer and the C++ classes do not take these formats.
+ *    are VS_ERR_UNSUPPORTED (crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom); the enhancer and the C++
+ *    classes do not take these formats.
  * The two stages around the stabilizer take I010 / I012 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev with fmt
  * VS_FMT_I010 / VS_FMT_I012):
  *  - analysis plane: min(sample >> (bits - 8), 255) of Y, exactly the byte the stabilizer's analysis uses.  Smoothed and detected
@@ -194,7 +197,7 @@ typedef enum vs_pixfmt_planar16 {
  *    half to even (vs_pixfmt16) - which does not depend on the bit depth.  (For 4:2:2, Mc is not a rotation.)
  *  - the last frame of a flush comes back unwarped, all three planes;
  *  - border pad, crop-and-zoom, fade and the virtual canvas are VS_ERR_UNSUPPORTED, with a text that names the format, exactly
- *    where I420 is refused.  The C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16, P210, NV24),
+ *    where I420 is refused (crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom).  The C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16, P210, NV24),
  *    yuv4xxp16le and big-endian samples are not built.
  * The two stages around the stabilizer take these formats through the entry points of the 4:2:0 ones (vs_roll_correct_i420_dev,
  * vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev, vs_azc_apply_i420_dev_n; layouts as struct vs_i420_layout, whose default chroma
@@ -455,8 +458,8 @@ int vs_stab_set_warp_batch(vs_stab* s, int frames);
  * (at most 32 frames per warp launch: a batch of 64 is two launches back to back).
  * Results are bit-identical to frames = 1 and complete after vs_stab_sync(); every push must
  * be given its own d_out until then.  Must be chosen before the first frame (or after
- * vs_stab_clean).  BGR8, GRAY8, NV12, P010, I420 and I010 / I012 frames; border padding and crop-and-zoom (BGR8
- * only, like everywhere) run batched too; the "fade" border, the virtual canvas and
+ * vs_stab_clean).  BGR8, GRAY8, NV12, P010, I420 and I010 / I012 frames; border padding and crop-and-zoom (BGR8;
+ * crop-and-zoom also on YUV streams that opted in, vs_stab_set_yuv_crop_zoom) run batched too; the "fade" border, the virtual canvas and
  * adaptive smoothing keep the per-frame path (each of their outputs depends on the one
  * before it or on a host decision).  Instances of one device share its HIP streams and
  * are to be driven from ONE host thread. */
@@ -491,6 +494,35 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
  * v_off = u_off + h * c_pitch; the chroma pitch at least one chroma row's bytes; everything even for the 16-bit formats. */
 int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off,
                             size_t out_c_pitch);
+/* Crop-and-zoom on YUV streams - the reference's shipped settings, crop_n_zoom with border_size 30 (examples/config.yaml:68-69:
+ * warp, cut the border off, resize back to the frame's size, Stabilizer.cpp:1108-1124), on NV12, P010 and the three-plane formats
+ * (I420 / YV12, I010, I012, I422, I444, I210, I212, I410, I412).  Off by default: such a stream is VS_ERR_UNSUPPORTED as ever, and
+ * allocates and launches exactly what it did.  The reference has no YUV path, so what the mode does is a DEFINITION of this
+ * library, which a caller opts into with this call (enable != 0; the frame queue must be empty).  With the mode on,
+ * crop_n_zoom != 0, border_size = b > 0, w - 2b > 0 and h - 2b > 0, every plane of a surface is processed on its own:
+ *  (a) warp: exactly as the stream warps the plane without a border (BORDER_CONSTANT 0, the same matrices), into a scratch surface;
+ *  (b) crop: (b, b, w - 2b, h - 2b) for Y and (b >> sx, b >> sy, (w - 2b) >> sx, (h - 2b) >> sy) for U, V or the interleaved UV
+ *      plane.  b must be a multiple of 2^sx and 2^sy - even for every subsampled format, anything for 4:4:4 -, so the chroma
+ *      rectangle is exactly the luma rectangle's; an odd b on a subsampled format is VS_ERR_INVALID_ARG with a text that names the
+ *      format;
+ *  (c) resize: cv::resize(crop, plane size, INTER_LINEAR) into the plane of the result, which has the size of the input plane.  The
+ *      taps clamp to the crop, not to the plane: a sample outside the rectangle never enters a result (a cv::Mat ROI).
+ *      Coordinates (float)((d + 0.5) * scale - 0.5) with scale = 1 / ((double)dst / src), as cv::resize computes it; coefficients
+ *      a0, a1 (columns) and b0, b1 (rows) of 11 bits, rounded and saturated to int16; from the first column whose right tap would
+ *      leave the crop on, the sample itself times 2048.
+ *      8-bit planes: OpenCV's CV_8U arithmetic (cn 1; cn 2 for the UV plane of NV12) - h = v0 * a0 + v1 * a1 per tap row, result
+ *      (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2.
+ *      16-bit planes: the same coordinates, coefficients and edge rule; the blend is the exact integer S = sum of v_ij * a_i * b_j
+ *      over the four taps with ONE rounding, half to even: min(65535, (S + 2^21 - 1 + ((S >> 22) & 1)) >> 22) - in the spirit of
+ *      the 16-bit warp blend, and NOT OpenCV's CV_16U resize, which blends with float coefficients.  Nothing depends on the bit
+ *      depth or on where the value sits in the word (P010: high bits, I010: low bits).
+ * w - 2b <= 0 or h - 2b <= 0: the frame is only warped, as for BGR8.  The last frame of a flush comes back unwarped and uncropped.
+ * Analysis, trajectory and warp matrix do not depend on border_size or crop_n_zoom: the debug values are those of the same stream
+ * with border_size = 0, bit for bit.  Border pad (crop_n_zoom = 0), the fade border and the virtual canvas stay refused on YUV
+ * streams, with their texts; GRAY8 is not touched by the mode.  Zero-copy input, the decoder layouts (vs_stab_set_nv12_layout,
+ * vs_stab_set_i420_layout) and the host entry points work as without the mode; in batch mode the warps of a launch (<= 32
+ * surfaces) fill scratch surfaces and ONE launch behind them resizes all their planes. */
+int vs_stab_set_yuv_crop_zoom(vs_stab* s, int enable);
 
 /* ---- several streams of one device scheduled together (BASELINE configs[4]: 64 streams = 8 per GPU) ----------------------
  * The reference runs one Stabilizer per stream, each with its own cv::cuda::Stream objects (src/Stabilizer.cpp:102-104); here a
@@ -529,6 +561,8 @@ int vs_batch_set_zero_copy(vs_batch* b, int enable);
 int vs_batch_set_nv12_layout(vs_batch* b, size_t in_uv_offset, size_t out_uv_offset);
 int vs_batch_set_i420_layout(vs_batch* b, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off,
                              size_t out_c_pitch);
+/* vs_stab_set_yuv_crop_zoom for every member (the members of a group must agree on the mode; a step refuses those that do not) */
+int vs_batch_set_yuv_crop_zoom(vs_batch* b, int enable);
 int vs_batch_push_dev(vs_batch* b, const void* const* d_frames, int w, int h, size_t stride, int fmt, void* const* d_outs,
                       size_t out_stride, int* produced);
 int vs_batch_flush_dev(vs_batch* b, void* const* d_outs, size_t out_stride, int* produced);
@@ -862,6 +896,15 @@ typedef struct vs_scale_job { const void* src; size_t src_stride; int32_t sw, sh
 int vs_op_scale_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int path, void* stream);
 /* host only, needs no device: staged[i] = 1 where path 0 sends job i to the staged kernel */
 int vs_op_scale_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int32_t* staged);
+/* The zoom of crop-and-zoom on YUV surfaces as an operator (the call a stream with vs_stab_set_yuv_crop_zoom makes behind its
+ * warps): n = 1 .. 96 jobs of one sample size (1 or 2 bytes; 32 surfaces of up to three planes) in ONE launch, cn 1 and 2 mixed.
+ * src = the crop's first sample, sw x sh the crop, dw x dh the destination, reserved = 0; the result is cv::resize(crop, (dw, dh),
+ * INTER_LINEAR) as vs_stab_set_yuv_crop_zoom defines it for that sample size - taps clamp to the crop; no byte outside the crop is
+ * read, none outside dw x dh written.  Sizes 1 .. 32767, strides in bytes; 16-bit pointers and strides even.  dw >= sw and
+ * dh >= sh: anything else is VS_ERR_UNSUPPORTED (this operator is the zoom-in of crop-and-zoom, not a general resize; unlike
+ * vs_op_scale_jobs, which is cv::warpAffine arithmetic).  Refusals are decided before any device call, with a text in
+ * vs_last_error that names the call and the job.  Asynchronous on `stream`. */
+int vs_op_resize_jobs(const vs_scale_job* jobs, int n, int sample_bytes, void* stream);
 /* Diagnostics of the asynchronous path: out9 = {frames through the worker threads; seconds, summed over the threads: without a
  * frame to work on, waiting for the masks of the batches on their way (one worker at a time does), in the contour logic, queueing
  * launches and publishing; batches; seconds, summed over the batches: from a batch's launches to the arrival of its masks on the

@@ -1,0 +1,196 @@
+"""Crop-and-zoom on YUV streams, the parts that need no GPU.
+
+1. tests/cropzoomref.py, the numpy statement of the zoom: resize_u8 equals the oracle's cv::resize(INTER_LINEAR) bit for bit on crops
+   that lie inside larger random planes (which pins the coordinate and coefficient code resize_u16 shares), and resize_u16 has the
+   properties of its definition - constants stay, results lie between their taps, the high byte follows the 8-bit result, and the
+   integer blend equals a float64 evaluation of the same sum rounded half to even.
+2. The refusal rules (video-stab_amd/csrc/pixfmt.h through tests/cpp/yuv_cropzoom_check.cpp): without the mode every answer is
+   today's; with it crop_n_zoom with an even border passes for the eleven YUV formats, an odd one fails for the nine subsampled
+   formats, and border pad, fade and canvas keep their texts.
+3. The ABI surface: the three new entry points are exported by the library and declared in include/vs_stab.h."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import cropzoomref as cz
+import refusal_cases
+from vsamd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (sw, sh) -> (dw, dh): the stream's test sizes less their borders, a tiny crop, crops of one and two samples, several tiles
+SIZES = [((126, 92), (130, 96)), ((310, 188), (322, 200)), ((20, 4), (64, 48)), ((2, 2), (64, 48)), ((1, 3), (32, 48)), ((644, 340), (704, 400))]
+SIZE_IDS = ["%dx%d-%dx%d" % (s + d) for s, d in SIZES]
+
+
+def roi_plane(seed, sw, sh, cn, dtype, hi=None):
+    """A crop of sw x sh pixels as a VIEW into a larger random plane (3 pixels left, 2 rows above, 5 pixels right, 3 rows below)."""
+    rng = np.random.default_rng(seed)
+    top = np.iinfo(dtype).max + 1 if hi is None else hi
+    parent = rng.integers(0, top, (sh + 5, (sw + 8) * cn), dtype=dtype)
+    return parent, parent[2:2 + sh, 3 * cn:(3 + sw) * cn]
+
+
+# ---- 1. the numpy statement --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cn", [1, 2])
+@pytest.mark.parametrize("size", SIZES, ids=SIZE_IDS)
+def test_resize_u8_is_the_oracles_resize(oracle, size, cn):
+    (sw, sh), (dw, dh) = size
+    parent, crop = roi_plane(sw * 31 + sh + cn, sw, sh, cn, np.uint8)
+    before = parent.copy()
+    got = cz.resize_u8(crop, cn, dw, dh)
+    src = np.ascontiguousarray(crop).reshape(sh, sw) if cn == 1 else np.ascontiguousarray(crop).reshape(sh, sw, cn)
+    want = oracle.resize(src, dw, dh)
+    assert got.shape == (dh, dw * cn) and np.array_equal(got, np.asarray(want).reshape(dh, dw * cn))
+    assert np.array_equal(parent, before)
+
+
+def test_an_equal_size_resize_is_the_identity():
+    _, crop = roi_plane(5, 37, 11, 2, np.uint8)
+    assert np.array_equal(cz.resize_u8(crop, 2, 37, 11), crop)
+    _, crop = roi_plane(6, 37, 11, 1, np.uint16)
+    assert np.array_equal(cz.resize_u16(crop, 1, 37, 11), crop)
+
+
+@pytest.mark.parametrize("cn", [1, 2])
+@pytest.mark.parametrize("size", SIZES, ids=SIZE_IDS)
+def test_resize_u16_keeps_constants(size, cn):
+    (sw, sh), (dw, dh) = size
+    for v in (0, 1, 1023, 4095, 65535):
+        got = cz.resize_u16(np.full((sh, sw * cn), v, np.uint16), cn, dw, dh)
+        assert got.shape == (dh, dw * cn) and np.all(got == v), v
+
+
+def _taps(plane, cn, dw, dh):
+    sh, sw = plane.shape[0], plane.shape[1] // cn
+    p = plane.reshape(sh, sw, cn).astype(np.int64)
+    x0, x1, a0, a1 = cz.axis_coefs(sw, dw, True)
+    y0, y1, b0, b1 = cz.axis_coefs(sh, dh, False)
+    t = [p[y][:, x] for y in (y0, y1) for x in (x0, x1)]                      # four (dh, dw, cn) arrays
+    wgt = [b[:, None, None] * a[None, :, None] for b in (b0, b1) for a in (a0, a1)]
+    return t, wgt
+
+
+@pytest.mark.parametrize("cn", [1, 2])
+@pytest.mark.parametrize("size", SIZES, ids=SIZE_IDS)
+def test_resize_u16_lies_between_its_taps_and_equals_the_float64_sum(size, cn):
+    (sw, sh), (dw, dh) = size
+    _, crop = roi_plane(sw * 17 + sh + cn, sw, sh, cn, np.uint16)
+    got = cz.resize_u16(crop, cn, dw, dh).reshape(dh, dw, cn).astype(np.int64)
+    t, wgt = _taps(np.ascontiguousarray(crop), cn, dw, dh)
+    used = [np.broadcast_to(g > 0, tt.shape) for g, tt in zip(wgt, t)]
+    lo = np.min([np.where(u, tt, 65535) for u, tt in zip(used, t)], axis=0)
+    hi = np.max([np.where(u, tt, 0) for u, tt in zip(used, t)], axis=0)
+    assert np.all(got >= lo) and np.all(got <= hi)
+    # the same sum in float64 (every product and the sum of four are exact below 2^53), rounded half to even by np.rint
+    S = sum(tt.astype(np.float64) * g.astype(np.float64) for tt, g in zip(t, wgt))
+    want = np.minimum(65535.0, np.rint(S / 4194304.0))
+    assert np.array_equal(got, want.astype(np.int64))
+
+
+@pytest.mark.parametrize("cn", [1, 2])
+@pytest.mark.parametrize("size", SIZES, ids=SIZE_IDS)
+def test_resize_u16_of_shifted_bytes_follows_resize_u8(size, cn):
+    (sw, sh), (dw, dh) = size
+    _, crop = roi_plane(sw * 13 + sh + cn, sw, sh, cn, np.uint8)
+    crop = np.ascontiguousarray(crop)
+    a = cz.resize_u8(crop, cn, dw, dh).astype(np.int64)
+    b = cz.resize_u16(crop.astype(np.uint16) << 8, cn, dw, dh).astype(np.int64) >> 8
+    assert np.max(np.abs(a - b)) <= 1
+
+
+def test_crop_zoom_surface_crops_every_plane_by_its_shifts():
+    rng = np.random.default_rng(3)
+    y, u, v = (rng.integers(0, 256, s, np.uint8) for s in ((48, 64), (48, 32), (48, 32)))        # 4:2:2
+    out = cz.crop_zoom_surface(("planar", 1, 0), [y, u, v], 6)
+    assert np.array_equal(out[0], cz.resize_u8(y[6:42, 6:58], 1, 64, 48))
+    assert np.array_equal(out[1], cz.resize_u8(u[6:42, 3:29], 1, 32, 48))
+    uv = rng.integers(0, 65536, (24, 64), np.uint16)                                            # the interleaved plane of a 64 x 48 P010 surface
+    out = cz.crop_zoom_surface(("uv", 1, 1), [y.astype(np.uint16), uv], 6)
+    assert np.array_equal(out[1], cz.resize_u16(uv[3:21, 6:58], 2, 32, 24))
+    same = cz.crop_zoom_surface(("uv", 1, 1), [y.astype(np.uint16), uv], 24)                     # h - 2b = 0: only warped
+    assert np.array_equal(same[0], y) and np.array_equal(same[1], uv)
+
+
+# ---- 2. the refusal rules ----------------------------------------------------------------------------------------------------
+YUV = ("NV12", "P010", "I420", "I010", "I012", "I422", "I444", "I210", "I212", "I410", "I412")
+SUBSAMPLED = ("NV12", "P010", "I420", "I010", "I012", "I422", "I210", "I212")      # (eight values; YV12 is I420 with the planes swapped)
+FULL = ("I444", "I410", "I412")
+assert sorted(SUBSAMPLED + FULL) == sorted(YUV)
+
+
+def _rules(cases):
+    """cases: [(fmt, w, h, pitch, border, crop, canvas, mode)] -> [((rc, text) with the mode, (rc, text) with the default argument)]"""
+    build = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(build, exist_ok=True)
+    src, exe = os.path.join(ROOT, "tests", "cpp", "yuv_cropzoom_check.cpp"), os.path.join(build, "yuv_cropzoom_check")
+    deps = [src, os.path.join(ROOT, "video-stab_amd", "csrc", "pixfmt.h"), os.path.join(ROOT, "include", "vs_stab.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(p) for p in deps):
+        subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", exe, src])
+    text = "".join(" ".join(str(int(v)) for v in c) + "\n" for c in cases)
+    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = [ln.split("|") for ln in r.stdout.splitlines()]
+    assert len(rows) == len(cases) and all(len(x) == 4 for x in rows), r.stdout
+    return [((int(a), b), (int(c), d)) for a, b, c, d in rows]
+
+
+def _pitch(name):
+    return 64 * capi.fmt_px_bytes(getattr(capi, "FMT_" + name))
+
+
+def test_without_the_mode_every_answer_is_todays():
+    """The recorded answers of the border cases (tests/golden/stream_refusals.json), asked with the mode off and with the argument
+    left out; and the mode alone (crop_n_zoom = 0) changes nothing either."""
+    golden = refusal_cases.load_golden(os.path.join(ROOT, "tests", "golden", "stream_refusals.json"))
+    todo = [c for c in refusal_cases.cases() if c.entry == "push_dev" and c.border > 0 and not refusal_cases.stateful(c) and not c.data_odd and not c.out_odd
+            and c.nv12 == (0, 0) and c.i420 == (0,) * 6 and c.out_pitch == c.pitch]
+    assert len(todo) >= 3 * 16
+    got = _rules([(c.fmt, c.w, c.h, c.pitch, c.border, c.crop, c.canvas, 0) for c in todo])
+    for c, (with_mode, default) in zip(todo, got):
+        assert with_mode == default == golden[c.id], c.id
+    pad = _rules([(c.fmt, c.w, c.h, c.pitch, c.border, 0, c.canvas, 1) for c in todo if not c.crop])
+    for c, (with_mode, default) in zip([c for c in todo if not c.crop], pad):
+        assert with_mode == default == golden[c.id], c.id
+
+
+@pytest.mark.parametrize("name", YUV)
+def test_with_the_mode_crop_and_zoom_passes_and_the_other_border_modes_keep_their_texts(name):
+    fmt, p = getattr(capi, "FMT_" + name), _pitch(name)
+    (even, d_even), (odd, d_odd), (pad, d_pad), (canvas, d_canvas), (both, _) = _rules(
+        [(fmt, 64, 48, p, 8, 1, 0, 1), (fmt, 64, 48, p, 5, 1, 0, 1), (fmt, 64, 48, p, 8, 0, 0, 1), (fmt, 64, 48, p, 0, 0, 1, 1), (fmt, 64, 48, p, 8, 1, 1, 1)])
+    assert even == (0, "") and both == (0, "")                   # (behind crop_n_zoom the canvas is not reached, as for BGR8)
+    assert d_even[0] == 4 and "colour format" in d_even[1]       # VS_ERR_UNSUPPORTED without the mode
+    if name in SUBSAMPLED:
+        assert odd[0] == 1 and name in odd[1] and "even border_size" in odd[1]
+    else:
+        assert odd == (0, "")
+    assert d_odd == d_even
+    assert pad == d_pad and pad[0] == 4 and "colour format" in pad[1]
+    assert canvas == d_canvas and canvas[0] == 4 and "enableVirtualCanvas needs a BGR8 stream" in canvas[1]
+
+
+def test_with_the_mode_gray8_and_the_colour_formats_answer_as_before():
+    for name in ("GRAY8", "BGR8", "BGRA8", "RGBA8", "RGB8"):
+        fmt, p = getattr(capi, "FMT_" + name), _pitch(name)
+        for a, d in _rules([(fmt, 64, 48, p, 8, 1, 0, 1), (fmt, 64, 48, p, 5, 1, 0, 1), (fmt, 64, 48, p, 8, 0, 0, 1)]):
+            assert a == d, name
+    assert _rules([(capi.FMT_GRAY8, 64, 48, 64, 8, 1, 0, 1)])[0][0][0] == 4
+
+
+# ---- 3. the ABI surface ------------------------------------------------------------------------------------------------------
+NEW = ("vs_stab_set_yuv_crop_zoom", "vs_batch_set_yuv_crop_zoom", "vs_op_resize_jobs")
+
+
+def test_the_new_entry_points_are_exported_and_declared():
+    vs = capi.load()
+    header = open(os.path.join(ROOT, "include", "vs_stab.h")).read()
+    for name in NEW:
+        assert hasattr(vs.lib, name), name + " is not exported by libvideo-stab.so"
+        assert re.search(r"^int %s\(" % name, header, re.M), name + " is not declared in include/vs_stab.h"
+    assert vs.lib.vs_abi_version() == 2
+    # refusals of the operator are decided on the host: no device is needed to get them
+    assert vs.lib.vs_op_resize_jobs(None, 1, 1, None) == 1 and b"vs_op_resize_jobs" in vs.lib.vs_last_error()

@@ -120,7 +120,7 @@ bool group_make_events(vs_batch* g) {
 bool same_launch_shape(const vs_stab* a, const vs_stab* b) {
     const vs_params_c &p = a->p, &q = b->p;
     return a->w == b->w && a->h == b->h && a->fmt == b->fmt && a->src_pitch == b->src_pitch && a->zero_copy == b->zero_copy &&
-           a->in == b->in && a->out == b->out &&
+           a->in == b->in && a->out == b->out && a->yuv_cz == b->yuv_cz &&
            a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
            p.lk_win_size == q.lk_win_size && p.ransac_max_iters == q.ransac_max_iters && p.border_size == q.border_size &&
            p.crop_n_zoom == q.crop_n_zoom && (p.border_size <= 0 || p.border_type == q.border_type);
@@ -176,7 +176,7 @@ int group_allocate(vs_batch* g) {
 struct WarpEnds { const uint8_t* src; uint8_t* dst; };
 WarpEnds warp_ends(const vs_stab* o, const uint8_t* frame, uint8_t* d_out, int pad_idx, const BorderPlan& bp) {
     if (!bp.pad && !bp.crop) return {frame, d_out};
-    uint8_t* scratch = o->d_padB + (size_t)pad_idx * o->pad_frame_bytes;
+    uint8_t* scratch = o->d_padB + (size_t)pad_idx * o->pad_frame_bytes;       // (a YUV stream: cz_scratch(o, pad_idx))
     return bp.pad ? WarpEnds{scratch, d_out} : WarpEnds{frame, scratch};
 }
 
@@ -187,6 +187,7 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
     vs_batch::Ready& R = g->ready;
     const vs_stab* s0 = g->ref;
     const BorderPlan bp = border_plan(s0);
+    const bool cz = yuv_cz_on(s0);      // a YUV stream with crop-and-zoom: bp.crop, the scratch surfaces in their own layout
     int rc = VS_OK;
     // (launch by launch: the pads of a launch's frames are queued right in front of it, their crops right behind it)
     for (int i0 = 0; i0 < R.n && rc == VS_OK; i0 += WARP_BATCH_MAX) {
@@ -207,14 +208,16 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
             // interleaved chroma plane: half size, two channels, the map with the halved translation (Minv + 6)
             const uint8_t* us[WARP_BATCH_MAX];
             uint8_t* ud[WARP_BATCH_MAX];
-            for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + dst_uv(s0, dsts[i], R.stride); }
-            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, s0->pf->sample_bytes);
-            continue;
-        }
-        if (s0->pf->three_planes()) {
+            for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + (cz ? cz_uv(s0) : dst_uv(s0, dsts[i], R.stride)); }
+            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, cz ? s0->cz_pitch : R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, s0->pf->sample_bytes);
+        } else if (s0->pf->three_planes()) {
             // I420, I010, I012: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
-            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, s0->pf->sample_bytes,
-                                  s0->pf->sx, s0->pf->sy);
+            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), cz ? cz_i420(s0) : dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st,
+                                  s0->pf->sample_bytes, s0->pf->sx, s0->pf->sy);
+        }
+        if (s0->pf->kind != PIX_INTERLEAVED) {
+            // crop-and-zoom on YUV surfaces: ONE launch behind the warps resizes the crops of all their planes into the results
+            if (cz && what != VS_WARP_TABLES_ONLY && rc == VS_OK) rc = cz_launch(s0, dsts, &R.dsts[i0], m, R.stride, st);
             continue;
         }
         rc = launch_warp_plane(srcs, dsts, m, bp.pad ? bp.prow : s0->src_pitch, bp.pw, bp.ph, bp.crop ? bp.prow : R.stride, bp.pw, bp.ph, s0->cn, maps,
@@ -315,11 +318,12 @@ int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const
                 const WarpEnds e = warp_ends(s, b.out_frame, b.d_out, npad, bp);
                 int32_t* T = g->d_tabs[set] + (size_t)j * g->tab_ints;
                 jobs[0] = WarpTabJob{T, e.src, e.dst, bp.pw, bp.ph};
+                const bool cz = yuv_cz_on(s);        // (the warp then fills a scratch surface, in the scratch layout)
                 if (s->pf->luma_uv())
-                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + dst_uv(s, e.dst, b.out_stride), s->w / 2, s->h / 2};
+                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + (cz ? cz_uv(s) : dst_uv(s, e.dst, b.out_stride)), s->w / 2, s->h / 2};
                 else if (s->pf->three_planes())      // ONE chroma table, in pixels, naming the U planes: a V tile adds the launch's V - U
-                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + dst_i420(s, e.dst, b.out_stride).u, s->w >> s->pf->sx,
-                                         s->h >> s->pf->sy};      // (sized for the format's chroma planes: 4:2:0 halves both)
+                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + (cz ? cz_i420(s) : dst_i420(s, e.dst, b.out_stride)).u,
+                                         s->w >> s->pf->sx, s->h >> s->pf->sy};      // (sized for the format's chroma planes: 4:2:0 halves both)
             }
             npad++;
             P.pend_stride = b.out_stride;
@@ -712,6 +716,12 @@ int vs_batch_set_i420_layout(vs_batch* g, size_t in_u_off, size_t in_v_off, size
         const int rc = vs_stab_set_i420_layout(s, in_u_off, in_v_off, in_c_pitch, out_u_off, out_v_off, out_c_pitch);
         if (rc != VS_OK) { g->err = s->err; return rc; }
     }
+    return VS_OK;
+}
+
+int vs_batch_set_yuv_crop_zoom(vs_batch* g, int enable) {
+    if (!g) return VS_ERR_INVALID_ARG;
+    for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_yuv_crop_zoom(s, enable); if (rc != VS_OK) { g->err = s->err; return rc; } }
     return VS_OK;
 }
 

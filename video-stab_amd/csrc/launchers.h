@@ -104,6 +104,13 @@ inline YuvDepth yuv_depth(const PixFmt& sf, const PixFmt& df, bool round) {
 int launch_cvt_yuv_to_yuv(const PixFmt& sf, const void* const* src, const I420Layout& in, const PixFmt& df, void* const* dst, const I420Layout& out,
                           int n, int w, int h, const YuvDepth& depth, bool mean, hipStream_t st);
 
+// ---- k_cropzoom.hip: the zoom of crop-and-zoom on YUV surfaces (vs_op_resize_jobs; a stream with vs_stab_set_yuv_crop_zoom)
+// n <= CZ_MAX_JOBS crops (src = the crop's first sample, sw x sh) resized to their planes (dw x dh, dw >= sw, dh >= sh) in ONE launch:
+// 32 surfaces of up to three planes; cn 1 and 2 may be mixed, the sample size is the launch's.  Checks every job on the host first
+// (a text in vs_last_error that names the job).
+constexpr int CZ_MAX_JOBS = 96;
+int launch_cropzoom(const vs_scale_job* jobs, int n, int sample_bytes, hipStream_t st);
+
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,
                      float* t_out = nullptr);

@@ -105,7 +105,10 @@ inline Refusal check_chroma_pitch(const PixFmt& f, int w, size_t in_c_pitch, siz
 }
 
 // The input side of a push, before the stream allocates: geometry, pitch, the stored layouts, the border modes.  f: pixfmt(fmt).
-inline Refusal check_input(const PixFmt* f, int w, int h, size_t pitch, const ChromaLayout& in, const ChromaLayout& out, int border_size) {
+// yuv_crop_zoom: the stream has crop-and-zoom on YUV surfaces turned on (vs_stab_set_yuv_crop_zoom) AND its parameters ask for
+// crop_n_zoom; 0 (the default) gives the answers of a stream without the mode.
+inline Refusal check_input(const PixFmt* f, int w, int h, size_t pitch, const ChromaLayout& in, const ChromaLayout& out, int border_size,
+                           int yuv_crop_zoom = 0) {
     if (w <= 0 || h <= 0 || !f) return refuse(VS_ERR_INVALID_ARG, "push: bad geometry/format");
     if ((f->sx && (w & 1)) || (f->sy && (h & 1))) return refuse(VS_ERR_INVALID_ARG, fmt_needs(*f) + (f->sy ? " even w,h" : " an even w"));
     if (f->luma_uv() && f->sample_bytes == 2 && ((pitch | in.uv_off | out.uv_off) & 1))
@@ -117,7 +120,11 @@ inline Refusal check_input(const PixFmt* f, int w, int h, size_t pitch, const Ch
         const Refusal r = check_chroma_pitch(*f, w, in.c_pitch, out.c_pitch, "");
         if (r.rc != VS_OK) return r;
     }
-    if (border_size > 0 && !f->border_modes) {
+    if (border_size > 0 && yuv_crop_zoom && f->kind != PIX_INTERLEAVED) {
+        // the crop of a chroma plane is the luma crop's: (b >> sx, b >> sy) must be exact
+        if (border_size & ((1 << (f->sx > f->sy ? f->sx : f->sy)) - 1))
+            return refuse(VS_ERR_INVALID_ARG, std::string("crop-and-zoom on ") + f->name + " needs an even border_size (the chroma planes are subsampled: their crop starts at border_size / 2)");
+    } else if (border_size > 0 && !f->border_modes) {
         // historical wording: two texts (the formats that came later name the fade mode and themselves)
         if (fmt_named_in_mode_texts(*f))
             return refuse(VS_ERR_UNSUPPORTED, std::string("border/crop/fade modes need a colour format (BGR8, BGRA8, RGBA8, RGB8), not ") + f->text);

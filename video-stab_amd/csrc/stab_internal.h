@@ -121,6 +121,12 @@ struct vs_stab {
     int fade_count = 0, fade_w = 0, fade_h = 0;     // fadeFrameCount_; geometry of the history
     uint8_t* d_padB = nullptr;          // batch mode with a border: one padded (or to-be-cropped) frame per frame of a batch
     size_t pad_frame_bytes = 0;
+    // crop-and-zoom on a YUV stream (vs_stab_set_yuv_crop_zoom): the warps go into scratch surfaces - d_padB again, the format's
+    // packed default layout at pitch cz_pitch, one per frame of a batch and one more (cz_own) for the per-frame path - and one
+    // k_cropzoom launch resizes their crops into the results
+    bool yuv_cz = false;
+    size_t cz_pitch = 0;
+    int cz_own = 0;
     uint8_t* d_out = nullptr;
     size_t out_bytes = 0;
     // host pipeline (vs_stab_set_host_pipeline): the result of a call stays in d_hold[] and travels to the host during the
@@ -246,6 +252,10 @@ inline BorderPlan border_plan(const vs_stab* s) {
     return bp;
 }
 
+// Crop-and-zoom on a YUV stream: the mode is on, the parameters ask for it and the crop is not empty (an empty crop: the frame is
+// only warped, as for BGR8).  Off, a YUV stream with a border never gets as far as its first allocation (pixfmt.h, check_input).
+inline bool yuv_cz_on(const vs_stab* s) { return s->yuv_cz && s->pf->kind != PIX_INTERLEAVED && border_plan(s).crop; }
+
 inline int build_pyramid(vs_stab* s, int k, hipStream_t st) {
     Pyramid& P = s->pyr[k];
     for (int l = 1; l <= s->levels; l++)
@@ -278,6 +288,14 @@ inline I420Layout src_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s-
 inline I420Layout dst_i420(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
     return fmt_i420_layout(*s->pf, out_stride, s->h, d_out != s->d_out ? s->out : ChromaLayout());
 }
+
+// The scratch surfaces of crop-and-zoom on a YUV stream: where the chroma of one lies, and surface `idx`
+inline size_t cz_uv(const vs_stab* s) { return (size_t)s->h * s->cz_pitch; }
+inline I420Layout cz_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s->cz_pitch, s->h); }
+inline uint8_t* cz_scratch(const vs_stab* s, int idx) { return s->d_padB + (size_t)idx * s->pad_frame_bytes; }
+// The zoom of n warped scratch surfaces into their results (device surfaces in the caller's output layout, or the staging of the
+// host entry points): ONE k_cropzoom launch over all their planes (stabilizer.cpp)
+int cz_launch(const vs_stab* s, const uint8_t* const* scratch, uint8_t* const* outs, int n, size_t out_stride, hipStream_t st);
 
 // A ring slot goes back to the free list behind the work on `st` that reads it.  A slot whose event cannot be recorded stays out
 // of the ring: its next writer would have nothing to wait for.

@@ -74,6 +74,7 @@ void free_all(vs_stab* s) {
     if (s->d_tmp) (void)hipFree(s->d_tmp);
     if (s->d_padB) (void)hipFree(s->d_padB);
     s->d_padB = nullptr;
+    s->cz_pitch = 0;
     if (s->own) {                       // the private schedule goes with the buffers it was sized for
         group_delete(s->own);
         s->own = nullptr; s->group = nullptr;
@@ -99,6 +100,17 @@ void analysis_size(const vs_stab* s, int w, int h, int* aw, int* ah) {
 }
 
 int allocate_buffers(vs_stab* s, int w, int h, int fmt);
+
+// The scratch surfaces of crop-and-zoom on a YUV stream (only with the mode on): the packed default layout at a pitch of whole
+// 256-byte lines, which keeps the warps' aligned stores whatever w is; one per frame of a batch, and one for the per-frame path
+// (the frames a flush hands out while the last step's warps may still run).
+int cz_allocate(vs_stab* s) {
+    s->cz_pitch = (s->row_bytes + 255) & ~(size_t)255;
+    s->pad_frame_bytes = s->cz_pitch * (size_t)s->rows_total;
+    s->cz_own = s->batch_active ? s->batch : 0;
+    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * (size_t)(s->cz_own + 1)));
+    return VS_OK;
+}
 
 // A failure half way leaves nothing behind: the next push starts from scratch instead of overwriting live pointers.
 int allocate(vs_stab* s, int w, int h, int fmt) {
@@ -222,7 +234,9 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_out, s->out_bytes));
     s->tmp_bytes = std::max(s->out_bytes, s->frame_bytes);
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
-    if (s->batch_active && s->p.border_size > 0) {
+    if (yuv_cz_on(s)) {
+        VS_OBJ_TRY(s, cz_allocate(s));
+    } else if (s->batch_active && s->p.border_size > 0) {
         s->pad_frame_bytes = (s->tmp_bytes + 255) & ~(size_t)255;
         VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * B));
     }
@@ -463,16 +477,23 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         rc = canvas_apply(s->canvas, p, frame, s->src_pitch, s->w, s->h, s->d_ct, s->d_traj, d_out, out_stride, st);
     } else if (s->pf->luma_uv()) {
         StageScope t(s, VS_STAGE_WARP, st);
+        // crop-and-zoom: the warp goes into the stream's scratch surface, whose crops one launch resizes into d_out
+        const bool cz = yuv_cz_on(s);
+        uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
         const uint8_t* uv = frame + src_uv(s);
-        uint8_t* out_uv = d_out + dst_uv(s, d_out, out_stride);
+        uint8_t* out_uv = wdst + (cz ? cz_uv(s) : dst_uv(s, d_out, out_stride));
         // (a P010 surface goes through the one-launch kernel even on its own: its tables are built in the stream's scratch)
-        rc = launch_warp_nv12(&frame, &d_out, &uv, &out_uv, 1, s->src_pitch, out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
+        rc = launch_warp_nv12(&frame, &wdst, &uv, &out_uv, 1, s->src_pitch, cz ? s->cz_pitch : out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
                               VS_BORDER_BLACK, s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, s->pf->sample_bytes);
+        if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
     } else if (s->pf->three_planes()) {
         // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
         StageScope t(s, VS_STAGE_WARP, st);
-        rc = launch_warp_i420(&frame, &d_out, 1, src_i420(s), dst_i420(s, d_out, out_stride), s->w, s->h, WarpMaps{s->d_Minv, 12, false}, VS_BORDER_BLACK,
-                              WarpTabs{WarpTabs::SCRATCH}, st, s->pf->sample_bytes, s->pf->sx, s->pf->sy);
+        const bool cz = yuv_cz_on(s);
+        uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
+        rc = launch_warp_i420(&frame, &wdst, 1, src_i420(s), cz ? cz_i420(s) : dst_i420(s, d_out, out_stride), s->w, s->h, WarpMaps{s->d_Minv, 12, false},
+                              VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, st, s->pf->sample_bytes, s->pf->sx, s->pf->sy);
+        if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
         const size_t prow = bp.prow, nb = prow * bh;
@@ -656,7 +677,7 @@ int take_slot(vs_stab* s, int* slot) {
 
 // What every push asks first: the rules of the input side (pixfmt.h), then the stream allocates for its first frame.
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
-    VS_REFUSE(s, check_input(pixfmt(fmt), w, h, stride, s->in, s->out, s->p.border_size));
+    VS_REFUSE(s, check_input(pixfmt(fmt), w, h, stride, s->in, s->out, s->p.border_size, s->yuv_cz && s->p.crop_n_zoom));
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     if (!s->allocated) return allocate(s, w, h, fmt);
     if (w != s->w || h != s->h || fmt != s->fmt) return vs_obj_fail(s, VS_ERR_SIZE_CHANGED, "frame geometry changed; call vs_stab_clean()");
@@ -687,6 +708,30 @@ int create_events(vs_stab* s) {
 }
 
 }  // namespace
+
+int vsd::cz_launch(const vs_stab* s, const uint8_t* const* scratch, uint8_t* const* outs, int n, size_t out_stride, hipStream_t st) {
+    const PixFmt& f = *s->pf;
+    const int b = s->p.border_size, sb = f.sample_bytes, w = s->w, h = s->h;
+    vs_scale_job jobs[CZ_MAX_JOBS];
+    int nj = 0;
+    // one plane: its crop (x, y, cw, ch) in the scratch surface -> the pw x ph plane of the result
+    auto add = [&](const uint8_t* src, size_t sstride, int x, int y, int cw, int ch, uint8_t* dst, size_t dstride, int pw, int ph, int cn) {
+        jobs[nj++] = vs_scale_job{src + (size_t)y * sstride + (size_t)x * cn * sb, sstride, cw, ch, dst, dstride, pw, ph, cn, 0};
+    };
+    for (int i = 0; i < n; i++) {
+        add(scratch[i], s->cz_pitch, b, b, w - 2 * b, h - 2 * b, outs[i], out_stride, w, h, 1);
+        if (f.luma_uv()) {
+            add(scratch[i] + cz_uv(s), s->cz_pitch, b >> 1, b >> 1, (w - 2 * b) >> 1, (h - 2 * b) >> 1, outs[i] + dst_uv(s, outs[i], out_stride), out_stride,
+                w / 2, h / 2, 2);
+            continue;
+        }
+        const I420Layout L = cz_i420(s), D = dst_i420(s, outs[i], out_stride);
+        for (int k = 0; k < 2; k++)
+            add(scratch[i] + (k ? L.v : L.u), L.cpitch, b >> f.sx, b >> f.sy, (w - 2 * b) >> f.sx, (h - 2 * b) >> f.sy, outs[i] + (k ? D.v : D.u), D.cpitch,
+                w >> f.sx, h >> f.sy, 1);
+    }
+    return launch_cropzoom(jobs, nj, sb, st);
+}
 
 void vsd::fill_traj_params(const vs_params_c& p, TrajParams& t) {
     memset(&t, 0, sizeof t);
@@ -1117,6 +1162,17 @@ int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t
     out.u_off = out_u_off; out.v_off = out_v_off; out.c_pitch = out_c_pitch;
     if (s->allocated) VS_REFUSE(s, check_set_i420_layout(*s->pf, s->w, in, out));
     s->in = in; s->out = out;
+    return VS_OK;
+}
+
+// Crop-and-zoom on YUV surfaces (NV12, P010 and the three-plane formats), off by default: with it a stream whose parameters say
+// crop_n_zoom with a border_size warps into scratch surfaces and resizes their crops back to the frame's size (k_cropzoom.hip);
+// without it such a stream is refused as ever.
+int vs_stab_set_yuv_crop_zoom(vs_stab* s, int enable) {
+    if (!s) return VS_ERR_INVALID_ARG;
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_crop_zoom: the frame queue must be empty");
+    s->yuv_cz = enable != 0;
     return VS_OK;
 }
 

@@ -490,6 +490,10 @@ class VsLib:
             L.vs_op_cvt_yuv_to_yuv.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(VsYuvCvtDesc), vp]
             L.vs_yuv_surface_layout.argtypes = [C.c_int, C.c_int, C.c_int, lp, lp, C.POINTER(C.c_size_t)]
+            # crop-and-zoom on YUV streams
+            L.vs_stab_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
+            L.vs_batch_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
+            L.vs_op_resize_jobs.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, vp]
         except AttributeError:      # a library of an earlier build (A/B measurements)
             pass
 
@@ -781,6 +785,10 @@ class VsLib:
     def scale_jobs(self, jobs, sample_bytes=1, path=0, stream=None):
         """vs_op_scale_jobs: jobs = tuples (src, src_stride, sw, sh, dst, dst_stride, dw, dh, cn) of device addresses; asynchronous."""
         self.check(self.lib.vs_op_scale_jobs(self._scale_job_array(jobs), len(jobs), sample_bytes, path, stream))
+
+    def resize_jobs(self, jobs, sample_bytes=1, stream=None):
+        """vs_op_resize_jobs (the zoom of crop-and-zoom on YUV surfaces): 1 .. 96 jobs, tuples as for scale_jobs; asynchronous."""
+        self.check(self.lib.vs_op_resize_jobs(self._scale_job_array(jobs), len(jobs), sample_bytes, stream))
 
     def scale_jobs_plan(self, jobs, sample_bytes=1):
         """vs_op_scale_jobs_plan (no device needed): 1 per job that path 0 sends to the staged kernel."""
@@ -1589,6 +1597,10 @@ class Stabilizer:
         0 = packed default."""
         self.vs.check(self.lib.vs_stab_set_i420_layout(self.h, in_u_off, in_v_off, in_c_pitch, out_u_off, out_v_off, out_c_pitch), self.h)
 
+    def set_yuv_crop_zoom(self, on=True):
+        """vs_stab_set_yuv_crop_zoom: crop_n_zoom with a border_size on NV12 / P010 / three-plane streams (off: refused)."""
+        self.vs.check(self.lib.vs_stab_set_yuv_crop_zoom(self.h, int(on)), self.h)
+
     def set_zero_copy(self, on=True):
         self.vs.check(self.lib.vs_stab_set_zero_copy(self.h, int(on)), self.h)
 
@@ -1688,6 +1700,9 @@ class Batch:
 
     def set_i420_layout(self, in_u_off=0, in_v_off=0, in_c_pitch=0, out_u_off=0, out_v_off=0, out_c_pitch=0):
         self._check(self.lib.vs_batch_set_i420_layout(self.h, in_u_off, in_v_off, in_c_pitch, out_u_off, out_v_off, out_c_pitch))
+
+    def set_yuv_crop_zoom(self, on=True):
+        self._check(self.lib.vs_batch_set_yuv_crop_zoom(self.h, int(on)))
 
     def push_dev(self, d_frames, w, h, stride, fmt, d_outs, out_stride):
         """d_frames / d_outs: one device pointer per stream (None: no frame for that stream).  Returns produced[]."""
