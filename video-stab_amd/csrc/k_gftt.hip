@@ -1,12 +1,17 @@
 // Shi-Tomasi corner detector for gfx950: device counterpart of
 //   cv::goodFeaturesToTrack(gray, corners, maxCorners, quality, minDistance,
 //                           noArray(), blockSize)
-// as called at /root/reference/src/Stabilizer.cpp:355-357 (first frame) and
+// as the reference calls it in src/Stabilizer.cpp:355-357 (first frame) and
 // :740-744 (every second frame; 200, 0.02, 15.0, 3).  Three launches:
 //
-//  1. min_eigen_kernel  - fused Sobel -> covariance -> box -> lambda_min on a
-//     64x16 tile staged through LDS (gray read once, the 2 MB eigenvalue map
-//     written once) + chip-wide max via one atomic per workgroup.
+//  1. min_eigen_kernel  - fused Sobel -> covariance -> box -> lambda_min, the 2 MB eigenvalue map written once, chip-wide
+//     max via atomics.  Two bodies:
+//     * min_eigen_tile: a TW x TH tile staged through LDS, any block size, REFLECT_101 at the borders.
+//     * min_eigen_walk3 (block size 3, images of at least 64 x 5): a wave owns 64 consecutive gray columns and walks down
+//       a strip of WALK_R output rows with a sliding window in registers - no LDS, every Sobel row term, covariance
+//       and box row sum computed once and shared between the three output rows that use it.  It covers the outputs
+//       [2, w-2) x [2, h-2), where no window position is a reflected one; the two-pixel frame around them is done by
+//       min_eigen_tile on thin tiles (128 x 2 and 2 x 128), by the first workgroups of the same launch.
 //  2. nms_kernel        - threshold(TOZERO, max*quality), 3x3 dilate compare,
 //     wave-aggregated append of (value,index) keys.
 //  3. select_kernel     - ONE workgroup: bitonic sort of the keys in LDS
@@ -19,7 +24,12 @@
 //
 // Float definitions (no FMA contraction, see oracle/vso_gftt.cpp header):
 //   Dx = ((r0+r2)*f1 + r1*f0), Dy = t2 - t0, f1=(float)(1/(4*bs*255)), f0=2*f1
-//   box sums in double (exact), lambda = (a+c) - sqrtf((a-c)*(a-c) + b*b).
+//   box sums in double, row sums left to right, rows top to bottom; lambda = (a+c) - sqrtf((a-c)*(a-c) + b*b).
+//   The order of the box sums is part of the definition: Dx is either 0 or at least ~f1 in magnitude, but Dy is the
+//   difference of two t values that are each a sum of two rounded products, and two rows with the same 2*centre + (left +
+//   right) split differently give t one rounding apart - Dy as small as 2^-33.  Dy*Dy and Dx*Dy then lie 60 - 90 bits under
+//   the large terms of the same sum, the 53-bit sum rounds, and its value depends on the order
+//   (tests/test_min_eigen_walk_cpu.py shows such a residue).
 #include <cstdio>
 #include <cstdlib>
 
@@ -30,7 +40,7 @@
 namespace vsd {
 namespace {
 
-constexpr int TW = 64, TH = 16, NT = 256;
+constexpr int NT = 256;
 constexpr int MAX_BS = 7;
 
 constexpr int SORT_CAP = 8192;
@@ -50,17 +60,17 @@ __device__ __forceinline__ float key_to_float(uint32_t k) {
 }
 
 // BS: block size known at compile time (loops unrolled, LDS arrays sized for it), 0: any block size up to MAX_BS
-template <int BS>
+// The tile's outputs: [x0, x0 + TW) x [y0, y0 + TH) clipped to x < x1, y < y1.
+template <int BS, int TW, int TH>
 __device__ __forceinline__ void min_eigen_tile(const uint8_t* __restrict__ gray, size_t stride, int w,
                                                int h, int bs_arg, float f1, float* __restrict__ eig,
-                                               uint32_t* __restrict__ max_key) {
+                                               uint32_t* __restrict__ max_key, int x0, int y0, int x1, int y1) {
     constexpr int BSM = BS ? BS : MAX_BS;
     __shared__ uint8_t g[TH + BSM - 1 + 2][TW + BSM - 1 + 2 + 2];
     __shared__ float cxx[TH + BSM - 1][TW + BSM - 1 + 1], cxy[TH + BSM - 1][TW + BSM - 1 + 1], cyy[TH + BSM - 1][TW + BSM - 1 + 1];
     __shared__ uint32_t smax[NT / 64];
     const int bs = BS ? BS : bs_arg;
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     const int anchor = bs / 2, hi = bs - 1 - anchor;
     const int gx0 = x0 - anchor - 1, gy0 = y0 - anchor - 1;   // image coords of g[0][0]
     const int GW = TW + bs - 1 + 2, GH = TH + bs - 1 + 2;
@@ -118,7 +128,7 @@ __device__ __forceinline__ void min_eigen_tile(const uint8_t* __restrict__ gray,
     for (int i = tid; i < TW * TH; i += NT) {
         const int ty = i / TW, tx = i - ty * TW;
         const int x = x0 + tx, y = y0 + ty;
-        if (x < w && y < h) {
+        if (x < x1 && y < y1) {
             double s0 = 0, s1 = 0, s2 = 0;
             for (int j = 0; j < bs; j++) {           // constant trip counts when BS != 0: unrolled
                 double r0 = 0, r1 = 0, r2 = 0;
@@ -151,11 +161,132 @@ __device__ __forceinline__ void min_eigen_tile(const uint8_t* __restrict__ gray,
     }
 }
 
+// ---- block size 3: the column walk
+constexpr int TW = 64, TH = 16;                  // tiles of the generic kernel
+constexpr int WALK_W = 60;                       // output columns of a strip: lanes 2 .. 61 of the wave that reads 64 gray columns
+constexpr int WALK_R = 32;                       // output rows of a strip (it reads WALK_R + 4 gray rows: a multiple of 3, see below)
+constexpr int FRAME_L = 128;                     // long side of the thin tiles of the two-pixel frame
+constexpr int WALK_MIN_W = 64, WALK_MIN_H = 5;
+
+// The value of the lane to the left / right (lane 0 / 63 have none and keep their own; their results are never used).
+// (DPP wave shifts instead of the shuffles were built and measured: 52.1 against 53.1 us per launch alone, inside the spread
+//  of the launches - profiles/r23_eig_levers.txt - and taken out again.)
+template <class T> __device__ __forceinline__ T from_left(T v) { return __shfl_up(v, 1, 64); }
+template <class T> __device__ __forceinline__ T from_right(T v) { return __shfl_down(v, 1, 64); }
+
+// What a lane carries down its column.  r, t: the Sobel row terms of the last three gray rows (t of the middle one is not
+// needed); xx, xy, yy: the box row sums of the last three covariance rows.
+struct WalkWin {
+    float r[3], t[3];
+    double xx[3], xy[3], yy[3];
+};
+
+// One gray row enters the window at slot N (slots A, B hold the two rows before it, oldest first): the covariance row
+// above it, that row's three row sums, and the output row above that (stored to `out` by the lanes with `store`) follow.
+// Row sums: (c[x-1] + c[x]) + c[x+1] without the oracle's leading 0.0: the only difference would be a sum of -0 terms, which
+// cxy alone can have; it would make b = -0, and b enters the result squared.  The same holds for the sum of the row sums.
+template <int A, int B, int N>
+__device__ __forceinline__ void walk_row(WalkWin& s, int gc, float f1, float f0, bool store, float* __restrict__ out,
+                                         uint32_t& kmax) {
+    const int gl = from_left(gc), gr = from_right(gc);
+    s.r[N] = (float)(gr - gl);
+    s.t[N] = (float)gc * f0 + (float)(gl + gr) * f1;
+    const float dx = (s.r[A] + s.r[N]) * f1 + s.r[B] * f0;
+    const float dy = s.t[N] - s.t[A];
+    const float vxx = dx * dx, vxy = dx * dy, vyy = dy * dy;
+    s.xx[N] = ((double)from_left(vxx) + (double)vxx) + (double)from_right(vxx);
+    s.xy[N] = ((double)from_left(vxy) + (double)vxy) + (double)from_right(vxy);
+    s.yy[N] = ((double)from_left(vyy) + (double)vyy) + (double)from_right(vyy);
+    const double s0 = (s.xx[A] + s.xx[B]) + s.xx[N], s1 = (s.xy[A] + s.xy[B]) + s.xy[N], s2 = (s.yy[A] + s.yy[B]) + s.yy[N];
+    const float a = (float)s0 * 0.5f, b = (float)s1, c = (float)s2 * 0.5f;
+    const float d = (a - c) * (a - c) + b * b;
+    const float e = (a + c) - sqrtf(d);
+    if (store) {
+        *out = e;
+        const uint32_t k = order_key(e);
+        kmax = k > kmax ? k : kmax;
+    }
+}
+
+__host__ __device__ __forceinline__ int walk_strips_x(int w) { return (w - 4 + WALK_W - 1) / WALK_W; }
+__host__ __device__ __forceinline__ int walk_strips_y(int h) { return (h - 4 + WALK_R - 1) / WALK_R; }
+__host__ __device__ __forceinline__ int frame_tiles_x(int w) { return (w + FRAME_L - 1) / FRAME_L; }
+__host__ __device__ __forceinline__ int frame_tiles_y(int h) { return (h - 4 + FRAME_L - 1) / FRAME_L; }
+
+// strip: index of the wave's strip (wave-uniform), below walk_strips_x(w) * walk_strips_y(h); w >= WALK_MIN_W, h >= WALK_MIN_H.
+// Strip (sx, sy) owns the outputs [2 + 60 sx, ..+60) x [2 + R sy, ..+R) clipped to x < w - 2, y < h - 2.  Its 64 gray columns
+// start two to the left of the outputs - the last strip of a row is moved left until its columns end at w, and its lanes left
+// of the strip's own first column store nothing.  Every byte it reads lies in [0, w) x [0, h).
+__device__ __forceinline__ void min_eigen_walk3(const uint8_t* __restrict__ gray, size_t stride, int w, int h, float f1,
+                                                float* __restrict__ eig, uint32_t* __restrict__ max_key, int strip) {
+    const int lane = threadIdx.x & 63;
+    const int nsx = walk_strips_x(w);
+    const int sy = strip / nsx, sx = strip - sy * nsx;
+    const int ox = 2 + WALK_W * sx;                              // first output column
+    const int gx = min(ox, w - 2 - WALK_W) - 2 + lane;           // the lane's column, in [0, w)
+    const int oy = 2 + WALK_R * sy, yend = min(oy + WALK_R, h - 2);   // output rows [oy, yend); gray rows [oy - 2, yend + 2)
+    const bool lane_out = lane >= 2 && lane < 2 + WALK_W && gx >= ox;
+    const float f0 = 2.f * f1;
+    const uint8_t* gp = gray + ((size_t)(oy - 2) * stride + gx);
+    float* ep = eig + gx;
+    const int last = yend + 1 - (oy - 2);                        // index of the strip's last gray row
+    WalkWin s = {};
+    uint32_t kmax = 0;
+    // three rows per trip: the window's slots rotate through the template arguments instead of through moves.  Trips past the
+    // last gray row read that row again and store nothing.
+    for (int k = 0; k <= last; k += 3) {
+        const int g0 = gp[(size_t)k * stride], g1 = gp[(size_t)min(k + 1, last) * stride], g2 = gp[(size_t)min(k + 2, last) * stride];
+        // gray row k completes output row oy - 4 + k: none during the first four (warm-up)
+        float* o = ep + (size_t)max(oy - 4 + k, 0) * w;
+        walk_row<1, 2, 0>(s, g0, f1, f0, lane_out && k >= 4 && k <= last, o, kmax);
+        walk_row<2, 0, 1>(s, g1, f1, f0, lane_out && k + 1 >= 4 && k + 1 <= last, o + w, kmax);
+        walk_row<0, 1, 2>(s, g2, f1, f0, lane_out && k + 2 >= 4 && k + 2 <= last, o + 2 * (size_t)w, kmax);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t o = __shfl_xor(kmax, off, 64);
+        kmax = o > kmax ? o : kmax;
+    }
+    if (lane == 0) atomicMax(max_key, kmax);
+}
+
+// Block size 3, w >= WALK_MIN_W, h >= WALK_MIN_H.  Workgroups along x: the frame first (thin tiles along the top and bottom
+// edges, then along the left and right ones), then the walk, one strip per wave.
+__device__ __forceinline__ void min_eigen_walk_block(const uint8_t* __restrict__ gray, size_t stride, int w, int h, float f1,
+                                                     float* __restrict__ eig, uint32_t* __restrict__ max_key) {
+    const int nbx = frame_tiles_x(w), nby = frame_tiles_y(h);
+    int b = blockIdx.x;
+    if (b < 2 * nbx) {                      // rows 0, 1 and h - 2, h - 1
+        const int y0 = b < nbx ? 0 : h - 2;
+        min_eigen_tile<3, FRAME_L, 2>(gray, stride, w, h, 3, f1, eig, max_key, (b < nbx ? b : b - nbx) * FRAME_L, y0, w, y0 + 2);
+        return;
+    }
+    b -= 2 * nbx;
+    if (b < 2 * nby) {                      // columns 0, 1 and w - 2, w - 1 of the rows between
+        const int x0 = b < nby ? 0 : w - 2;
+        min_eigen_tile<3, 2, FRAME_L>(gray, stride, w, h, 3, f1, eig, max_key, x0, 2 + (b < nby ? b : b - nby) * FRAME_L, x0 + 2, h - 2);
+        return;
+    }
+    b -= 2 * nby;
+    const int strip = b * (NT / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // in a scalar register: so is the row loop
+    if (strip < walk_strips_x(w) * walk_strips_y(h)) min_eigen_walk3(gray, stride, w, h, f1, eig, max_key, strip);
+}
+
+// min_eigen_kernel<3>: the walk (the launcher chose it by the image's size); <0>: tiles, any block size
 template <int BS>
 __global__ __launch_bounds__(NT) void min_eigen_kernel(const uint8_t* __restrict__ gray, size_t stride, int w,
                                                        int h, int bs, float f1, float* __restrict__ eig,
                                                        uint32_t* __restrict__ max_key) {
-    min_eigen_tile<BS>(gray, stride, w, h, bs, f1, eig, max_key);
+    if (BS == 3) min_eigen_walk_block(gray, stride, w, h, f1, eig, max_key);
+    else min_eigen_tile<0, TW, TH>(gray, stride, w, h, bs, f1, eig, max_key, blockIdx.x * TW, blockIdx.y * TH, w, h);
+}
+
+// grid of min_eigen_kernel / min_eigen_batch_kernel for images of w x h; *walk: the <3> instance applies
+dim3 min_eigen_grid(int w, int h, int block_size, int items, bool* walk) {
+    *walk = block_size == 3 && w >= WALK_MIN_W && h >= WALK_MIN_H;
+    if (!*walk) return dim3((w + TW - 1) / TW, (h + TH - 1) / TH, items);
+    const int strips = walk_strips_x(w) * walk_strips_y(h);
+    return dim3(2 * frame_tiles_x(w) + 2 * frame_tiles_y(h) + (strips + NT / 64 - 1) / (NT / 64), 1, items);
 }
 
 __device__ __forceinline__ void nms_row(const float* __restrict__ eig, int w, int h, double quality,
@@ -510,7 +641,8 @@ __global__ __launch_bounds__(64) void gftt_zero_batch_kernel(const GfttItem* __r
 template <int BS>
 __global__ __launch_bounds__(NT) void min_eigen_batch_kernel(const GfttItem* __restrict__ table) {
     const GfttItem& it = table[blockIdx.z];
-    min_eigen_tile<BS>(it.gray, it.stride, it.w, it.h, it.bs, it.f1, it.eig, (uint32_t*)&it.counters[1]);
+    if (BS == 3) min_eigen_walk_block(it.gray, it.stride, it.w, it.h, it.f1, it.eig, (uint32_t*)&it.counters[1]);
+    else min_eigen_tile<0, TW, TH>(it.gray, it.stride, it.w, it.h, it.bs, it.f1, it.eig, (uint32_t*)&it.counters[1], blockIdx.x * TW, blockIdx.y * TH, it.w, it.h);
 }
 __global__ __launch_bounds__(NT) void nms_batch_kernel(const GfttItem* __restrict__ table) {
     const GfttItem& it = table[blockIdx.z];
@@ -572,8 +704,9 @@ int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_si
     const GfttItem* t = static_cast<const GfttItem*>(d_table);
     if (what == 0 || what == 1) hipLaunchKernelGGL(gftt_zero_batch_kernel, dim3(items), dim3(64), 0, st, t);
     if (what == 0 || what == 2 || what == 4) {
-        const dim3 eg((w + TW - 1) / TW, (h + TH - 1) / TH, items);
-        if (block_size == 3) hipLaunchKernelGGL(min_eigen_batch_kernel<3>, eg, dim3(NT), 0, st, t);
+        bool walk;
+        const dim3 eg = min_eigen_grid(w, h, block_size, items, &walk);
+        if (walk) hipLaunchKernelGGL(min_eigen_batch_kernel<3>, eg, dim3(NT), 0, st, t);
         else hipLaunchKernelGGL(min_eigen_batch_kernel<0>, eg, dim3(NT), 0, st, t);
     }
     if (what == 0 || what == 2 || what == 5)
@@ -608,8 +741,9 @@ int launch_gftt(const uint8_t* d_gray, size_t stride, int w, int h, int max_corn
     double scale = (double)(1 << 2) * block_size * 255.0;
     scale = 1.0 / scale;
     const float f1 = (float)scale;
-    dim3 g1((w + TW - 1) / TW, (h + TH - 1) / TH);
-    if (block_size == 3)
+    bool walk;
+    const dim3 g1 = min_eigen_grid(w, h, block_size, 1, &walk);
+    if (walk)
         hipLaunchKernelGGL(min_eigen_kernel<3>, g1, dim3(NT), 0, st, d_gray, stride, w, h, block_size, f1, wk.eig, (uint32_t*)&wk.counters[1]);
     else
         hipLaunchKernelGGL(min_eigen_kernel<0>, g1, dim3(NT), 0, st, d_gray, stride, w, h, block_size, f1, wk.eig, (uint32_t*)&wk.counters[1]);
