@@ -40,7 +40,9 @@ extern "C" {
  *    vs_roll_correct_i420_dev, vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev and vs_azc_apply_i420_dev_n; planar 4:2:2 and
  *    4:4:4 - VS_FMT_I422, VS_FMT_I444, VS_FMT_I210, VS_FMT_I212, VS_FMT_I410, VS_FMT_I412 (enum vs_pixfmt_planar4xx) - with
  *    vs_op_warp_affine_planar, and as fmt of the four roll / zoom entry points above; the output size of auto zoom/crop: vs_azc_set_output_size, vs_azc_get_output_size, struct
- *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan; the compositing operators vs_op_copy_make_border, vs_op_fade_blend,
+ *    vs_scale_job with vs_op_scale_jobs and vs_op_scale_jobs_plan; roll correction and auto zoom/crop on interleaved colour frames (BGR8, RGB8, BGRA8,
+ *    RGBA8), asynchronous: vs_roll_correct_rgb_dev, vs_roll_correct_rgb_dev_n, vs_azc_apply_rgb_dev, vs_azc_apply_rgb_dev_n,
+ *    vs_op_scale_jobs_rgb and vs_op_scale_jobs_rgb_plan; the compositing operators vs_op_copy_make_border, vs_op_fade_blend,
  *    vs_op_fade_update and vs_op_canvas_create / apply / info / destroy; colour conversion on the device: vs_op_cvt_yuv_to_rgb,
  *    vs_op_cvt_rgb_to_yuv and vs_enh_apply_yuv_dev; the enhancer on a batch of YUV surfaces in one fused launch:
  *    vs_enh_apply_yuv_batch_dev, vs_enh_last_fused and vs_enh_yuv_plan; the colour space of the conversions: struct
@@ -791,6 +793,21 @@ int vs_roll_correct_i420_dev(vs_roll* r, int fmt, const void* d_surface, int w, 
                              void* d_out, const vs_i420_layout* out);
 int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                                const vs_i420_layout* in, const vs_i420_layout* out);
+/* The same for an interleaved colour frame in HBM, ASYNCHRONOUS with the semantics of vs_roll_correct_nv12_dev (batches of eight,
+ * worker threads, vs_roll_sync, vs_roll_get_state after it): fmt is VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8 or VS_FMT_RGBA8, the frame
+ * one plane of w x h pixels (w, h >= 1: no evenness rule, there is no chroma plane) with rows of `stride` bytes.
+ *  - analysis: resize + BGR2GRAY reads B, G, R at the format's positions; the fourth channel never enters.  For BGR8 angle, state and
+ *    pixels are those of vs_roll_correct_dev on the same frames, bit for bit; for the other formats the angle is that of the frame's BGR
+ *    permutation.
+ *  - pixels: every channel, the fourth included, goes through cv::warpAffine's arithmetic as a channel of its own, under
+ *    getRotationMatrix2D((w / 2.0f, h / 2.0f), smoothed, 1) with BORDER_REPLICATE.
+ * Colour frames, NV12, P010 and planar surfaces may alternate on one object in any order: a change of format, pixel size, geometry or
+ * stride closes the pending batch, the smoothed angle carries across; the synchronous vs_roll_correct_dev syncs what is in flight first.
+ * Refused before any device call with VS_ERR_INVALID_ARG and a text (vs_roll_last_error) that names the call and the four formats: any
+ * other fmt (GRAY8, NV12, P010, planar, out of range), stride or out_stride below w * cn, null pointers, w or h < 1, n < 1. */
+int vs_roll_correct_rgb_dev(vs_roll* r, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride);
+int vs_roll_correct_rgb_dev_n(vs_roll* r, int fmt, const void* const* d_frames, void* const* d_outs, int n, int w, int h,
+                              size_t stride, size_t out_stride);
 /* smoothed angle (sSmoothedAngle), the angle detected on the last frame, lines found / used */
 int vs_roll_get_state(const vs_roll* r, double* smoothed_deg, double* detected_deg,
                       int* n_lines, int* n_used);
@@ -871,6 +888,22 @@ int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int 
                           void* d_out, const vs_i420_layout* out, int64_t* ticket);
 int vs_azc_apply_i420_dev_n(vs_azc* a, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h,
                             const vs_i420_layout* in, const vs_i420_layout* out, int64_t* tickets);
+/* The same for an interleaved colour frame in HBM, ASYNCHRONOUS with the semantics of vs_azc_apply_nv12_dev (batches of eight, worker
+ * threads, tickets, vs_azc_result, vs_azc_sync): fmt is VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8 or VS_FMT_RGBA8, the frame one plane of
+ * w x h pixels (w, h >= 1) with rows of `stride` bytes.
+ *  - analysis: the content mask is BGR2GRAY > 1 on B, G, R at the format's positions; the fourth channel never enters.  For BGR8
+ *    info8 and pixels are those of vs_azc_apply_dev on the same frame; for the other formats info8 and the rectangle are those of the
+ *    frame's BGR permutation.
+ *  - pixels: the crop scaled to the object's output size by the reference's CV_32F scale matrix, every channel - the fourth too - as a
+ *    channel of its own, BORDER_CONSTANT 0 on the crop (a fourth channel is 0 there as well, as in the stabilizer's BGRA warp).
+ *  - fall-back paths (no contour, empty crop): the frame comes back unchanged, all channels, w x h.
+ * vs_azc_set_output_size applies as everywhere: out_stride >= max(w, ow) * cn, and d_out holds max(h, oh) rows.
+ * Refused before any device call with VS_ERR_INVALID_ARG and a text (vs_azc_last_error) that names the call and the four formats: any
+ * other fmt, stride below w * cn, out_stride too small, null pointers, w or h < 1, n < 1. */
+int vs_azc_apply_rgb_dev(vs_azc* a, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride,
+                         int64_t* ticket);
+int vs_azc_apply_rgb_dev_n(vs_azc* a, int fmt, const void* const* d_frames, void* const* d_outs, int n, int w, int h, size_t stride,
+                           size_t out_stride, int64_t* tickets);
 int vs_azc_result(vs_azc* a, int64_t ticket, int* out_w, int* out_h, int32_t* info8);
 /* The output size of the crop-and-scale: ow x oh wherever the comments above say 640 x 360 (the reference hard-codes its author's
  * frame size, AutoZoomCrop.cpp:246-261; the stage means "crop the black corners and zoom back to the frame").  A new object has
@@ -896,6 +929,11 @@ typedef struct vs_scale_job { const void* src; size_t src_stride; int32_t sw, sh
 int vs_op_scale_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int path, void* stream);
 /* host only, needs no device: staged[i] = 1 where path 0 sends job i to the staged kernel */
 int vs_op_scale_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int32_t* staged);
+/* The same two for crops of interleaved colour frames (the call a batch of vs_azc_apply_rgb_dev makes): 8-bit samples, cn 3 or 4 - a
+ * call may mix them -, every channel a channel of its own; the staging rule is that of vs_op_scale_jobs (a staged pixel is one dword
+ * whatever its size).  vs_op_scale_jobs itself keeps refusing cn 3 and 4. */
+int vs_op_scale_jobs_rgb(const vs_scale_job* jobs, int n, int path, void* stream);       /* 8-bit, cn 3 or 4 */
+int vs_op_scale_jobs_rgb_plan(const vs_scale_job* jobs, int n, int32_t* staged);              /* host only */
 /* The zoom of crop-and-zoom on YUV surfaces as an operator (the call a stream with vs_stab_set_yuv_crop_zoom makes behind its
  * warps): n = 1 .. 96 jobs of one sample size (1 or 2 bytes; 32 surfaces of up to three planes) in ONE launch, cn 1 and 2 mixed.
  * src = the crop's first sample, sw x sh the crop, dw x dh the destination, reserved = 0; the result is cv::resize(crop, (dw, dh),

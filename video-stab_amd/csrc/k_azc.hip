@@ -44,23 +44,31 @@ __device__ __forceinline__ unsigned content_bgr(uint32_t b, uint32_t g, uint32_t
 // the 4-bit results go through LDS and 16 lanes pack them into the 16 words.
 // (several pictures per launch: blockIdx.z selects the picture - its source from `srcs`, a kernel argument, its bit plane tfb
 // words behind T)
+// (BI: the byte of B inside a colour pixel - 0 BGR8 / BGRA8, 2 RGB8 / RGBA8: the first and the third byte change places in the
+// weights.  CN = 4: a lane's four pixels are ONE 16-byte load - `aligned` then says that the rows keep 16 bytes -, the fourth byte of
+// a pixel is never looked at.)
 constexpr int SRC_LIST_MAX = 8;
 struct SrcList { const uint8_t* p[SRC_LIST_MAX]; };
-template <int CN>
+template <int CN, int BI = 0>
 __global__ __launch_bounds__(256) void threshold_bits_kernel(const uint8_t* __restrict__ src, size_t stride, int w,
                                                              int aligned, u64* __restrict__ T, int wpr, SrcList srcs, size_t tfb) {
     __shared__ __attribute__((aligned(16))) uint8_t nib[256];
     if (!src) { src = srcs.p[blockIdx.z]; T += (size_t)blockIdx.z * tfb; }
     const int tid = threadIdx.x, x = (blockIdx.x * 256 + tid) * 4, y = blockIdx.y;
     const uint8_t* row = src + (size_t)y * stride;
+    auto content = [](uint32_t c0, uint32_t c1, uint32_t c2) { return BI ? content_bgr(c2, c1, c0) : content_bgr(c0, c1, c2); };
     unsigned n = 0;
     if (x + 3 < w && aligned) {
-        if (CN == 3) {
+        if (CN == 4) {
+            const uint4 d = *reinterpret_cast<const uint4*>(row + (size_t)x * 4);
+            auto px = [&](uint32_t v) { return content(v & 255u, (v >> 8) & 255u, (v >> 16) & 255u); };
+            n = px(d.x) | px(d.y) << 1 | px(d.z) << 2 | px(d.w) << 3;
+        } else if (CN == 3) {
             const U3 d = *reinterpret_cast<const U3*>(row + (size_t)x * 3);
-            n = content_bgr(d.a & 255u, (d.a >> 8) & 255u, (d.a >> 16) & 255u) |
-                content_bgr(d.a >> 24, d.b & 255u, (d.b >> 8) & 255u) << 1 |
-                content_bgr((d.b >> 16) & 255u, d.b >> 24, d.c & 255u) << 2 |
-                content_bgr((d.c >> 8) & 255u, (d.c >> 16) & 255u, d.c >> 24) << 3;
+            n = content(d.a & 255u, (d.a >> 8) & 255u, (d.a >> 16) & 255u) |
+                content(d.a >> 24, d.b & 255u, (d.b >> 8) & 255u) << 1 |
+                content((d.b >> 16) & 255u, d.b >> 24, d.c & 255u) << 2 |
+                content((d.c >> 8) & 255u, (d.c >> 16) & 255u, d.c >> 24) << 3;
         } else {
             const uint32_t d = *reinterpret_cast<const uint32_t*>(row + x);
             n = ((d & 255u) > 1u) | (((d >> 8) & 255u) > 1u) << 1 | (((d >> 16) & 255u) > 1u) << 2 | ((d >> 24) > 1u) << 3;
@@ -69,7 +77,7 @@ __global__ __launch_bounds__(256) void threshold_bits_kernel(const uint8_t* __re
         for (int i = 0; i < 4; i++) {
             if (x + i >= w) break;
             const uint8_t* p = row + (size_t)(x + i) * CN;
-            n |= (CN == 3 ? content_bgr(p[0], p[1], p[2]) : (p[0] > 1 ? 1u : 0u)) << i;
+            n |= (CN >= 3 ? content(p[0], p[1], p[2]) : (p[0] > 1 ? 1u : 0u)) << i;
         }
     }
     nib[tid] = (uint8_t)n;
@@ -238,14 +246,19 @@ __global__ __launch_bounds__(256) void expand_bits_kernel(const u64* __restrict_
 // bit planes / results lie tfb / ofb words apart.
 // sb = 2 (a table of sources, cn 1): luma planes of 16-bit samples, the mask of their high bytes - or, lo_shift > 0 (I010: 2, I012: 4),
 // of min(sample >> lo_shift, 255); stride in bytes, everything even.
+// cn 3 or 4 with bi (0 or 2): interleaved colour pictures with B in byte bi of a pixel (BGR8 / BGRA8: 0, RGB8 / RGBA8: 2).
 int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int cn, u64* d_T, u64* d_out, int opitch,
                         int oframe, hipStream_t st, const uint8_t* const* srcs = nullptr, int frames = 1, size_t tfb = 0, size_t ofb = 0,
-                        int srcs_aligned = 0, int sb = 1, int lo_shift = 0) {
-    if ((sb != 1 && sb != 2) || lo_shift < 0 || lo_shift > 8 || (lo_shift && sb != 2) || (sb == 2 && (d_src || cn != 1)) || (!d_src && !srcs) || (!d_src && frames > SRC_LIST_MAX) || !d_T || !d_out || w <= 0 || h <= 0 || (cn != 1 && cn != 3) || frames < 1) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
+                        int srcs_aligned = 0, int sb = 1, int lo_shift = 0, int bi = 0) {
+    if ((sb != 1 && sb != 2) || lo_shift < 0 || lo_shift > 8 || (lo_shift && sb != 2) || (sb == 2 && (d_src || cn != 1)) || (!d_src && !srcs) || (!d_src && frames > SRC_LIST_MAX) || !d_T || !d_out || w <= 0 || h <= 0 || (cn != 1 && cn != 3 && cn != 4) || (bi != 0 && (bi != 2 || cn < 3)) || frames < 1) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
     if (h > 65535) { set_last_error("content_mask: image too tall"); return VS_ERR_INVALID_ARG; }
     const int wpr = (w + 63) / 64;
-    // (a table of sources: srcs_aligned = every one of them is 4-byte aligned)
-    const int aligned = !d_src ? (srcs_aligned && (stride & 3) == 0) : ((((uintptr_t)d_src | stride) & 3) == 0);
+    // (a table of sources: srcs_aligned = every one of them is 4-byte aligned; four-byte pixels: a lane's load is 16 bytes, looked up here)
+    int aligned = !d_src ? (srcs_aligned && (stride & 3) == 0) : ((((uintptr_t)d_src | stride) & 3) == 0);
+    if (cn == 4) {
+        aligned = (stride & 15) == 0 && ((uintptr_t)d_src & 15) == 0;
+        for (int i = 0; !d_src && aligned && i < frames; i++) aligned = ((uintptr_t)srcs[i] & 15) == 0;
+    }
     SrcList sl;
     for (int i = 0; i < SRC_LIST_MAX; i++) sl.p[i] = !d_src ? srcs[i < frames ? i : 0] : nullptr;
     dim3 g1((w + 1023) / 1024, h, frames);
@@ -260,6 +273,9 @@ int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int c
         if (wide) hipLaunchKernelGGL(threshold_bits_p010_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
         else hipLaunchKernelGGL(threshold_bits_p010_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
     } else if (wide) hipLaunchKernelGGL(threshold_bits_gray16_kernel, dim3((w + 1023) / 1024, (h + 3) / 4, frames), dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
+    else if (cn == 4 && bi) hipLaunchKernelGGL((threshold_bits_kernel<4, 2>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
+    else if (cn == 4) hipLaunchKernelGGL((threshold_bits_kernel<4, 0>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
+    else if (cn == 3 && bi) hipLaunchKernelGGL((threshold_bits_kernel<3, 2>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
     else if (cn == 3) hipLaunchKernelGGL(threshold_bits_kernel<3>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
     else hipLaunchKernelGGL(threshold_bits_kernel<1>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
     dim3 g2(wpr, (h + MC_ROWS - 1) / MC_ROWS, frames);
@@ -299,7 +315,9 @@ struct vs_azc {
     // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420 ...
     // VS_FMT_I412) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
     // ow, oh: the output size the frame was handed over under, resolved (never 0)
-    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; int planar; I420Layout sl, dl; int ow, oh; };
+    // icn: 0, or the bytes of a pixel of an interleaved colour frame (3 BGR8 / RGB8, 4 BGRA8 / RGBA8: one plane, pitch / opitch its rows;
+    // uv / ouv unused), ibi: the byte of B inside such a pixel (0 or 2)
+    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; int planar; I420Layout sl, dl; int ow, oh; int icn, ibi; };
     struct BatchSlot {
         uint8_t* d_masks = nullptr;      // ZB BitFrames
         uint8_t* h_masks = nullptr;      // page-locked
@@ -344,7 +362,7 @@ extern "C" {
 int vs_op_content_mask(const void* d_src, size_t stride, int w, int h, int cn, void* d_mask, size_t mask_stride,
                        void* stream) {
     VS_TRY(ensure_device());
-    if (!d_mask || w <= 0 || h <= 0 || mask_stride < (size_t)w) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
+    if (!d_mask || w <= 0 || h <= 0 || mask_stride < (size_t)w || (cn != 1 && cn != 3)) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
     static std::mutex mu;
     static u64* planes = nullptr;
     static size_t plane_words = 0;
@@ -532,6 +550,8 @@ static void azc_publish(vs_azc* a, const vs_azc::Result& res) {
 // last frame queues the batch's jobs as one launch.  The content mask is taken from the luma plane (gray > 1, :121-127 on a picture
 // that is gray already); the crop rectangle applies to the luma plane as it is and, halved, to the half-size chroma plane;
 // each plane is scaled to its share of the frame's output size by the reference's scale matrix (:261-270, ow x oh for 640 x 360).
+// An interleaved colour frame (icn) is one plane of icn channels: the mask from B, G, R where the format has them (:121-127), one job
+// with the rectangle as it is, every channel - the fourth too - scaled as a channel of its own.
 static void azc_worker(vs_azc* a) {
     (void)hipSetDevice(a->device);
     CropScratch scratch;
@@ -593,7 +613,9 @@ static void azc_worker(vs_azc* a) {
             t_contour = clk::now();
             if (!res.info[7]) {                                                                            // :149-152, :238-249
                 res.out_w = q.w; res.out_h = q.h;
-                if (q.planar) {          // the unchanged surface, all three planes: each its own row bytes and rows
+                if (q.icn) {             // the unchanged frame, all channels
+                    if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w * q.icn, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess) rc = VS_ERR_HIP;
+                } else if (q.planar) {   // the unchanged surface, all three planes: each its own row bytes and rows
                     const size_t cw = (size_t)(q.w >> csx) * q.sb;
                     const size_t crows = (size_t)(q.h >> csy);
                     if (hipMemcpy2DAsync(q.dst, q.dl.pitch, q.src, q.sl.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
@@ -611,10 +633,12 @@ static void azc_worker(vs_azc* a) {
                 const float Mu[6] = {(float)((double)(q.ow >> csx) / uw), 0.f, 0.f, 0.f, (float)((double)(q.oh >> csy) / uh), 0.f};
                 warp_invert(My, wj[0].m);
                 warp_invert(Mu, wj[1].m);
-                wj[0].src = q.src + (size_t)cy * q.pitch + (size_t)cx * q.sb; wj[0].dst = q.dst;
-                wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = q.ow; wj[0].dh = q.oh; wj[0].cn = 1;
+                wj[0].src = q.src + (size_t)cy * q.pitch + (size_t)cx * (q.icn ? q.icn : q.sb); wj[0].dst = q.dst;
+                wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = q.ow; wj[0].dh = q.oh; wj[0].cn = q.icn ? q.icn : 1;
                 for (WarpJob& w : wj) { w.sstride = (uint32_t)q.pitch; w.dstride = (uint32_t)q.opitch; w.border = VS_BORDER_BLACK; w.sb = q.sb; }
-                if (q.planar) {          // U and V: one-channel planes of (w >> sx) x (h >> sy), the shifted rectangle, rows of their own pitch
+                if (q.icn) {
+                    nscaled = 1;
+                } else if (q.planar) {          // U and V: one-channel planes of (w >> sx) x (h >> sy), the shifted rectangle, rows of their own pitch
                     warp_invert(Mu, wj[2].m);
                     wj[1].src = q.src + q.sl.u + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[1].dst = q.dst + q.dl.u;
                     wj[2].src = q.src + q.sl.v + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[2].dst = q.dst + q.dl.v;
@@ -644,7 +668,8 @@ static void azc_worker(vs_azc* a) {
             if (last) { njobs = b.nwj; memcpy(all, b.wj, sizeof(WarpJob) * njobs); }
         }
         a->cv_done.notify_all();          // (vs_azc_result waits for the host part only)
-        int lrc = last && njobs ? launch_scale_jobs(all, njobs, 0, a->st_out) : VS_OK;
+        // (a batch holds one kind of frame: colour jobs go to the colour instances of the two kernels)
+        int lrc = !(last && njobs) ? VS_OK : q.icn ? launch_scale_jobs_rgb(all, njobs, 0, a->st_out) : launch_scale_jobs(all, njobs, 0, a->st_out);
         {
             std::lock_guard<std::mutex> g(a->mu);
             const clk::time_point t_end = clk::now();
@@ -699,9 +724,9 @@ static int azc_issue_batch(vs_azc* a, std::unique_lock<std::mutex>& lk) {
         srcs[i] = a->pending[i].src;
         if ((uintptr_t)a->pending[i].src & 3) aligned = 0;
     }
-    VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, 1, b.d_tbits, (u64*)b.d_masks, BitFrame::pitch_for(w), 1, b.st, srcs, n, tw,
-                                 mb / 8, aligned, a->pending[0].sb,
-                                 a->pending[0].planar ? pixfmt(a->pending[0].planar)->lo16_shift() : 0));                                                                              // :111-139 on the luma planes
+    VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, a->pending[0].icn ? a->pending[0].icn : 1, b.d_tbits, (u64*)b.d_masks,
+                                 BitFrame::pitch_for(w), 1, b.st, srcs, n, tw, mb / 8, aligned, a->pending[0].sb,
+                                 a->pending[0].planar ? pixfmt(a->pending[0].planar)->lo16_shift() : 0, a->pending[0].ibi));      // :111-139 on the luma planes / the colour frames
     VS_OBJ_HIP(a, hipMemcpyAsync(b.h_masks, b.d_masks, mb * n, hipMemcpyDeviceToHost, b.st));                                          // :142-143
     VS_OBJ_HIP(a, hipEventRecord(b.ev, b.st));
     b.t_issue = std::chrono::steady_clock::now();
@@ -742,11 +767,14 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
 // (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
 // (planar: 0, or the format of a three-plane surface whose layouts are sl / dl, checked by the caller - uv_offset / out_uv_offset repeat
 // their U offsets)
+// (icn, ibi: an interleaved colour frame, vs_azc::Frame - its caller has checked geometry and strides; there is no second plane)
 static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                         size_t out_uv_offset, int64_t* ticket, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout()) {
-    if (!a || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb) return VS_ERR_INVALID_ARG;
+                         size_t out_uv_offset, int64_t* ticket, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout(),
+                         int icn = 0, int ibi = 0) {
+    if (!a || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
+    if (!icn && (w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb)) return VS_ERR_INVALID_ARG;
     const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h;
-    if (out_pitch < (size_t)std::max(w, ow) * sb || out_uv_offset < (size_t)std::max(h, oh) * out_pitch) return VS_ERR_INVALID_ARG;
+    if (!icn && (out_pitch < (size_t)std::max(w, ow) * sb || out_uv_offset < (size_t)std::max(h, oh) * out_pitch)) return VS_ERR_INVALID_ARG;
     if (sb == 2 && !planar && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: P010 pointers, pitches and plane offsets must be even");
     if (w > 65535 || h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
@@ -767,12 +795,13 @@ static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t 
     if (!a->pending.empty()) {
         const vs_azc::Frame& p0 = a->pending[0];
         auto same = [](const I420Layout& x, const I420Layout& y) { return x.pitch == y.pitch && x.cpitch == y.cpitch && x.u == y.u && x.v == y.v; };
-        if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar || (planar && (!same(p0.sl, sl) || !same(p0.dl, dl)))) {
+        if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar || p0.icn != icn || p0.ibi != ibi ||
+            (planar && (!same(p0.sl, sl) || !same(p0.dl, dl)))) {
             const int rc = azc_flush_pending(a, lk);
             if (rc != VS_OK) return rc;
         }
     }
-    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb, planar, sl, dl, ow, oh});
+    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb, planar, sl, dl, ow, oh, icn, ibi});
     if (ticket) *ticket = a->issued;
     a->issued++;
     if ((int)a->pending.size() >= vs_azc::ZB) return azc_flush_pending(a, lk);
@@ -849,6 +878,47 @@ int vs_azc_apply_nv12_dev_n(vs_azc* a, const void* const* d_surfaces, void* cons
     return VS_OK;
 }
 
+// The same for an interleaved colour frame in HBM: fmt VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8 or VS_FMT_RGBA8, one plane of w x h pixels
+// (any w, h >= 1: there is no chroma plane), rows of `stride` bytes.  The content mask is that of BGR2GRAY on B, G, R where the format has
+// them - the fourth channel never enters -, so info8 and the rectangle are those of the frame's BGR permutation; the crop is scaled with
+// every channel, the fourth included, as a channel of its own (BORDER_CONSTANT 0 on the crop, also for the fourth); on the fall-back
+// paths the frame comes back unchanged, all channels.  out_stride >= max(w, ow) * cn, and d_out holds max(h, oh) rows.  A BGR8 result is
+// that of vs_azc_apply_dev on the same frame.  Colour frames, NV12, P010 and planar surfaces may alternate on one object.
+// Refused before any device call, with a text in vs_azc_last_error that names the call and the formats: another fmt, stride < w * cn,
+// out_stride too small, null pointers, w or h < 1, n < 1.
+static const char RGB_FORMATS[] = "VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8, VS_FMT_RGBA8";
+static int azc_rgb_hand_over(vs_azc* a, const char* call, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride,
+                             int64_t* ticket) {
+    const PixFmt* f = pixfmt(fmt);
+    const std::string head = std::string(call) + " (fmt: one of " + RGB_FORMATS + "): ";
+    if (!f || f->kind != PIX_INTERLEAVED || f->cn < 3) return vs_obj_fail(a, VS_ERR_INVALID_ARG, head + "not an interleaved colour format");
+    if (!d_frame || !d_out) return vs_obj_fail(a, VS_ERR_INVALID_ARG, head + "null frame or result pointer");
+    if (w < 1 || h < 1) return vs_obj_fail(a, VS_ERR_INVALID_ARG, head + "w and h must be at least 1");
+    const int ow = a->ow ? a->ow : w;
+    if (stride < (size_t)w * f->cn || out_stride < (size_t)std::max(w, ow) * f->cn)
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, head + "stride below w * cn, or out_stride below max(w, " + std::to_string(ow) + ") * cn");
+    if (stride > UINT32_MAX || out_stride > UINT32_MAX) return vs_obj_fail(a, VS_ERR_INVALID_ARG, head + "strides must be below 4 GiB");
+    return azc_hand_over(a, d_frame, w, h, stride, 0, d_out, out_stride, 0, ticket, 1, 0, I420Layout(), I420Layout(), f->cn,
+                         fmt == VS_FMT_RGB8 || fmt == VS_FMT_RGBA8 ? 2 : 0);
+}
+
+int vs_azc_apply_rgb_dev(vs_azc* a, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride, int64_t* ticket) {
+    if (!a) return VS_ERR_INVALID_ARG;
+    return azc_rgb_hand_over(a, "vs_azc_apply_rgb_dev", fmt, d_frame, w, h, stride, d_out, out_stride, ticket);
+}
+
+int vs_azc_apply_rgb_dev_n(vs_azc* a, int fmt, const void* const* d_frames, void* const* d_outs, int n, int w, int h, size_t stride, size_t out_stride,
+                           int64_t* tickets) {
+    if (!a) return VS_ERR_INVALID_ARG;
+    if (!d_frames || !d_outs || n < 1)
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, std::string("vs_azc_apply_rgb_dev_n (fmt: one of ") + RGB_FORMATS + "): null pointer lists, or n < 1");
+    for (int i = 0; i < n; i++) {
+        const int rc = azc_rgb_hand_over(a, "vs_azc_apply_rgb_dev_n", fmt, d_frames[i], w, h, stride, d_outs[i], out_stride, tickets ? tickets + i : nullptr);
+        if (rc != VS_OK) return rc;
+    }
+    return VS_OK;
+}
+
 // Diagnostics of the asynchronous path: frames through the workers so far and the seconds the workers spent, summed over the
 // threads, without a frame / waiting for the masks on their way / in the contour logic / queueing launches and publishing; then
 // batches and, summed over them, the seconds from launches to masks, from masks to the crop launch, and the caller's waits for a slot.
@@ -903,12 +973,13 @@ int vs_azc_get_output_size(const vs_azc* a, int* out_w, int* out_h) {
 }
 
 // The stage's crop-and-scale as an operator: the call the batch's last worker makes (launch_scale_jobs), on the caller's jobs.
-static int scale_jobs_convert(const vs_scale_job* jobs, int n, int sample_bytes, WarpJob* out) {
+// (rgb: the jobs of vs_op_scale_jobs_rgb - cn 3 or 4 where the others take 1 or 2)
+static int scale_jobs_convert(const vs_scale_job* jobs, int n, int sample_bytes, WarpJob* out, bool rgb = false) {
     if (!jobs || n < 1 || n > WARP_JOBS_MAX || (sample_bytes != 1 && sample_bytes != 2)) return VS_ERR_INVALID_ARG;
     for (int i = 0; i < n; i++) {
         const vs_scale_job& s = jobs[i];
         if (!s.src || !s.dst || s.sw < 1 || s.sh < 1 || s.dw < 1 || s.dh < 1 || s.sw > 32767 || s.sh > 32767 || s.dw > 32767 || s.dh > 32767 ||
-            (s.cn != 1 && s.cn != 2) || s.reserved != 0 || s.src_stride > UINT32_MAX || s.dst_stride > UINT32_MAX ||
+            (rgb ? s.cn != 3 && s.cn != 4 : s.cn != 1 && s.cn != 2) || s.reserved != 0 || s.src_stride > UINT32_MAX || s.dst_stride > UINT32_MAX ||
             s.src_stride < (size_t)s.sw * s.cn * sample_bytes || s.dst_stride < (size_t)s.dw * s.cn * sample_bytes ||
             (sample_bytes == 2 && (((uintptr_t)s.src | (uintptr_t)s.dst | s.src_stride | s.dst_stride) & 1)))
             return VS_ERR_INVALID_ARG;
@@ -939,6 +1010,28 @@ int vs_op_scale_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int
         return VS_ERR_INVALID_ARG;
     }
     for (int i = 0; i < n; i++) staged[i] = scale_job_staged(wj[i]) ? 1 : 0;
+    return VS_OK;
+}
+
+// The same operator for crops of interleaved colour frames: 8-bit samples, cn 3 or 4 (a call may mix them), every channel - a fourth one
+// included - a channel of its own.  (vs_op_scale_jobs keeps refusing them: its jobs are planes of YUV surfaces.)
+int vs_op_scale_jobs_rgb(const vs_scale_job* jobs, int n, int path, void* stream) {
+    WarpJob wj[WARP_JOBS_MAX];
+    if ((path != 0 && path != 1) || scale_jobs_convert(jobs, n, 1, wj, true) != VS_OK) {
+        set_last_error("scale_jobs_rgb: invalid argument (1 .. 24 jobs of 8-bit samples; cn 3 or 4; sizes 1 .. 32767; strides at least a row)");
+        return VS_ERR_INVALID_ARG;
+    }
+    VS_TRY(ensure_device());
+    return launch_scale_jobs_rgb(wj, n, path, (hipStream_t)stream);
+}
+
+int vs_op_scale_jobs_rgb_plan(const vs_scale_job* jobs, int n, int32_t* staged) {
+    WarpJob wj[WARP_JOBS_MAX];
+    if (!staged || scale_jobs_convert(jobs, n, 1, wj, true) != VS_OK) {
+        set_last_error("scale_jobs_rgb_plan: invalid argument");
+        return VS_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n; i++) staged[i] = scale_job_staged_rgb(wj[i]) ? 1 : 0;
     return VS_OK;
 }
 

@@ -779,7 +779,9 @@ struct vs_roll {
                                          // batches in flight keep the stage at 3.4 ms per 128 surfaces where three need 5.5 (gpurun_out/r04_ai)
     // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420 ...
     // VS_FMT_I412) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
-    struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; int sb; int planar; I420Layout sl, dl; };
+    // icn: 0, or the bytes of a pixel of an interleaved colour frame of format ifmt (VS_FMT_BGR8, RGB8: 3; BGRA8, RGBA8: 4) - one plane,
+    // pitch / opitch its rows; uv / ouv are unused
+    struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; int sb; int planar; I420Layout sl, dl; int icn, ifmt; };
     struct Slot {
         RollWork wk;                     // RB frames
         hipStream_t st = nullptr;
@@ -1027,13 +1029,15 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
     VS_TRY(roll_work_alloc(q.wk, sw, sh, p.hough_rho, p.hough_theta, q.st, vs_roll::RB));
     RollWork k = q.wk;               // the first n work areas
     k.base = nullptr; k.frames = n;
-    for (int f = 0; f < n; f++) { q.h_pairs[f].src = jobs[f].src; q.h_pairs[f].dst = k.gray + (size_t)f * k.fb; }
+    int src8 = 1;                    // every source of the batch on an 8-byte boundary (the colour kernels' wide loads)
+    for (int f = 0; f < n; f++) { q.h_pairs[f].src = jobs[f].src; q.h_pairs[f].dst = k.gray + (size_t)f * k.fb; src8 &= ((uintptr_t)jobs[f].src & 7) == 0; }
     VS_HIP_TRY(hipMemcpyAsync(q.d_pairs, q.h_pairs, sizeof(ImgPair) * n, hipMemcpyHostToDevice, q.st));
     // (P010: the analysis image is that of the luma samples' high bytes - the 16-bit gray kernels of k_gray.hip read nothing else;
     // the three-plane 16-bit formats: that of min(sample >> (bits - 8), 255), the low-bits kernels; the Y plane of an 8-bit three-plane
-    // surface is a gray picture - the chroma subsampling does not enter)
-    const int gfmt = j0.planar && j0.sb == 2 ? j0.planar : j0.sb == 2 ? (int)VS_FMT_P010 : (int)VS_FMT_GRAY8;
-    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, gfmt, sw, sw, sh, 0, q.st));   // :41
+    // surface is a gray picture - the chroma subsampling does not enter; an interleaved colour frame: resize + BGR2GRAY on B, G, R where
+    // its format has them, :41,:51 - the fourth channel does not enter)
+    const int gfmt = j0.icn ? j0.ifmt : j0.planar && j0.sb == 2 ? j0.planar : j0.sb == 2 ? (int)VS_FMT_P010 : (int)VS_FMT_GRAY8;
+    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, gfmt, sw, sw, sh, j0.icn ? src8 : 0, q.st));   // :41
     // (twelve hysteresis passes per batch - a pass whose predecessor changed nothing for its frame returns at once: with four, 40 % of
     // the bench clip's frames had to finish their growth one by one behind the batch, 30 us per frame)
     constexpr int PASSES = 12;
@@ -1092,6 +1096,19 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
         ys[f] = j.src; us[f] = j.src + j.uv; yd[f] = j.dst; ud[f] = j.dst + j.ouv;
         one_launch &= j.opitch == j0.opitch && j.uv == j0.uv && j.ouv == j0.ouv;
         if (j0.planar) one_launch &= j.dl.cpitch == j0.dl.cpitch && j.dl.u == j0.dl.u && j.dl.v == j0.dl.v;
+    }
+    // an interleaved colour frame is one plane of icn channels under M, every channel a channel of its own: the batch's rotations in ONE
+    // launch from the scratch tables when the results share a stride, else frame by frame
+    if (j0.icn) {
+        if (one_launch)
+            return launch_warp_plane(ys, yd, n, j0.pitch, j0.w, j0.h, j0.opitch, j0.w, j0.h, j0.icn, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE,
+                                     WarpTabs{WarpTabs::SCRATCH}, r->st);
+        for (int f = 0; f < n; f++) {
+            const vs_roll::Job& j = jobs[f];
+            VS_TRY(launch_warp_plane(ys + f, yd + f, 1, j.pitch, j.w, j.h, j.opitch, j.w, j.h, j.icn, WarpMaps{Minv + 12 * f, 12, true}, VS_BORDER_REPLICATE,
+                                     WarpTabs{}, r->st));
+        }
+        return VS_OK;
     }
     // three planes (a batch holds one format and one source layout): Y, U and V tiles of all its surfaces in ONE grid (warp_i420_kernel
     // with the BORDER_REPLICATE staging, 8- or 16-bit samples, the instance of the format's chroma shifts) when the results share one
@@ -1163,9 +1180,12 @@ static void roll_flush_pending(vs_roll* r) {
 // until then.
 // (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
 // (planar: 0, or the format of a three-plane surface whose layouts are sl / dl - uv_offset / out_uv_offset are then unused)
+// (icn, ifmt: an interleaved colour frame, vs_roll::Job - its caller has checked geometry and strides; there is no second plane)
 static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                          size_t out_uv_offset, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout()) {
-    if (!r || !d_surface || !d_out || w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)w * sb) return VS_ERR_INVALID_ARG;
+                          size_t out_uv_offset, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout(), int icn = 0,
+                          int ifmt = 0) {
+    if (!r || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
+    if (!icn && (w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)w * sb)) return VS_ERR_INVALID_ARG;
     if (sb == 2 && !planar && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
         return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: P010 pointers, pitches and plane offsets must be even");
     if (uv_offset == 0) uv_offset = (size_t)h * pitch;
@@ -1187,11 +1207,11 @@ static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_
         // launches take one of each)
         if (!r->pending.empty()) {
             const vs_roll::Job& p0 = r->pending[0];
-            if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar ||
+            if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar || p0.icn != icn || p0.ifmt != ifmt ||
                 (planar && (p0.sl.cpitch != sl.cpitch || p0.sl.u != sl.u || p0.sl.v != sl.v)))
                 roll_flush_pending(r);
         }
-        r->pending.push_back(vs_roll::Job{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, r->nv_in, sb, planar, sl, dl});
+        r->pending.push_back(vs_roll::Job{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, r->nv_in, sb, planar, sl, dl, icn, ifmt});
         r->nv_in++;
         if ((int)r->pending.size() >= vs_roll::RB) roll_flush_pending(r);
     }
@@ -1247,6 +1267,41 @@ int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surface
     if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
     for (int i = 0; i < n; i++) {
         const int rc = vs_roll_correct_i420_dev(r, fmt, d_surfaces[i], w, h, in, d_outs[i], out);
+        if (rc != VS_OK) return rc;
+    }
+    return VS_OK;
+}
+
+// The same for an interleaved colour frame: fmt VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8 or VS_FMT_RGBA8, one plane of w x h pixels (any
+// w, h >= 1: there is no chroma plane), rows of `stride` bytes.  The line search runs on resize + BGR2GRAY of B, G, R where the format
+// has them - the fourth channel never enters -, so angle and line counts are those of the frame's BGR permutation; the rotation is
+// applied to every channel, the fourth included, as a channel of its own, BORDER_REPLICATE.  A BGR8 result and the state after it are
+// those of vs_roll_correct_dev on the same frames.  Colour frames, NV12, P010 and planar surfaces may alternate on one object: a change
+// of format closes the pending batch, the smoothed angle carries across.
+// Refused before any device call, with a text in vs_roll_last_error that names the call and the formats: another fmt, a stride below
+// w * cn, null pointers, w or h < 1, n < 1.
+static const char RGB_FORMATS[] = "VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8, VS_FMT_RGBA8";
+static int roll_rgb_hand_over(vs_roll* r, const char* call, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride) {
+    const PixFmt* f = pixfmt(fmt);
+    const std::string head = std::string(call) + " (fmt: one of " + RGB_FORMATS + "): ";
+    if (!f || f->kind != PIX_INTERLEAVED || f->cn < 3) return vs_obj_fail(r, VS_ERR_INVALID_ARG, head + "not an interleaved colour format");
+    if (!d_frame || !d_out) return vs_obj_fail(r, VS_ERR_INVALID_ARG, head + "null frame or result pointer");
+    if (w < 1 || h < 1) return vs_obj_fail(r, VS_ERR_INVALID_ARG, head + "w and h must be at least 1");
+    if (stride < (size_t)w * f->cn || out_stride < (size_t)w * f->cn) return vs_obj_fail(r, VS_ERR_INVALID_ARG, head + "stride or out_stride below w * cn");
+    return roll_hand_over(r, d_frame, w, h, stride, 0, d_out, out_stride, 0, 1, 0, I420Layout(), I420Layout(), f->cn, fmt);
+}
+
+int vs_roll_correct_rgb_dev(vs_roll* r, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride) {
+    if (!r) return VS_ERR_INVALID_ARG;
+    return roll_rgb_hand_over(r, "vs_roll_correct_rgb_dev", fmt, d_frame, w, h, stride, d_out, out_stride);
+}
+
+int vs_roll_correct_rgb_dev_n(vs_roll* r, int fmt, const void* const* d_frames, void* const* d_outs, int n, int w, int h, size_t stride, size_t out_stride) {
+    if (!r) return VS_ERR_INVALID_ARG;
+    if (!d_frames || !d_outs || n < 1)
+        return vs_obj_fail(r, VS_ERR_INVALID_ARG, std::string("vs_roll_correct_rgb_dev_n (fmt: one of ") + RGB_FORMATS + "): null pointer lists, or n < 1");
+    for (int i = 0; i < n; i++) {
+        const int rc = roll_rgb_hand_over(r, "vs_roll_correct_rgb_dev_n", fmt, d_frames[i], w, h, stride, d_outs[i], out_stride);
         if (rc != VS_OK) return rc;
     }
     return VS_OK;

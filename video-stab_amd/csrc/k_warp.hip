@@ -646,7 +646,9 @@ __global__ __launch_bounds__(NT) void warp_affine16_kernel(WarpArgs a) {
 // Planar 4:2:0 surfaces (I420 / I010 / I012) are three jobs of cn 1 each: 3 x 8 = WARP_JOBS_MAX jobs per batch, still one launch.
 struct WarpJobsArg { WarpJob j[WARP_JOBS_MAX]; };
 
-template <int SB>
+// RGB: the jobs of interleaved colour frames (8-bit, cn 3 or 4: AutoZoomCrop on BGR8 / RGB8 / BGRA8 / RGBA8, every channel a channel
+// of its own) - a kernel of its own as well, for the same reason.
+template <int SB, bool RGB = false>
 __device__ __forceinline__ void warp_jobs_tile(const WarpJobsArg& a) {
     __shared__ int s_ad[TW], s_bd[TW], s_x0[TH], s_y0[TH];
     const WarpJob& j = a.j[blockIdx.z];
@@ -671,6 +673,12 @@ __device__ __forceinline__ void warp_jobs_tile(const WarpJobsArg& a) {
     const int galign = SB == 2 ? 8 * j.cn : j.cn == 2 ? 8 : 4;        // (a lane's four pixels in one store)
     c.dst_aligned = ((uintptr_t)j.dst % galign == 0) && (j.dstride % galign == 0);
     c.border = j.border;
+    if constexpr (RGB) {
+        c.dst_aligned = (((uintptr_t)j.dst | j.dstride) & (j.cn == 4 ? 15 : 3)) == 0;      // (a lane's four pixels: 16 bytes, or three dwords)
+        if (j.cn == 4) emit_rows<4, false>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
+        else emit_rows<3, false>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
+        return;
+    }
     if (j.cn == 1) emit_rows<1, false, SB>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
     else if (j.cn == 2 || SB == 2) emit_rows<2, false, SB>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
     else if constexpr (SB == 1) emit_rows<3, false>(c, j.src, j.dst, nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
@@ -678,6 +686,7 @@ __device__ __forceinline__ void warp_jobs_tile(const WarpJobsArg& a) {
 
 __global__ __launch_bounds__(NT) void warp_jobs_kernel(WarpJobsArg a) { warp_jobs_tile<1>(a); }
 __global__ __launch_bounds__(NT) void warp_jobs16_kernel(WarpJobsArg a) { warp_jobs_tile<2>(a); }
+__global__ __launch_bounds__(NT) void warp_jobs_rgb_kernel(WarpJobsArg a) { warp_jobs_tile<1, true>(a); }
 
 // ---- the staged form of a scale job ------------------------------------------------------------------------------------------
 // A zoom stage that does not shrink (AutoZoomCrop at the surface's own size, k_azc.hip) turns the jobs above inside out: the source
@@ -710,6 +719,12 @@ __device__ __forceinline__ void scale_stage(const WarpJob& j, uint32_t* tile, in
                 if (CN * SB == 1) {
                     const uint32_t d = *reinterpret_cast<const uint32_t*>(p);
                     px.x = d & 255u; px.y = (d >> 8) & 255u; px.z = (d >> 16) & 255u; px.w = d >> 24;
+                } else if (CN * SB == 3) {      // (three bytes per pixel: the four pixels are three dwords, stage_group's split)
+                    const U3 d = *reinterpret_cast<const U3*>(p);
+                    px.x = d.a & 0xFFFFFFu;
+                    px.y = (d.a >> 24) | ((d.b & 0xFFFFu) << 8);
+                    px.z = (d.b >> 16) | ((d.c & 0xFFu) << 16);
+                    px.w = d.c >> 8;
                 } else if (CN * SB == 2) {      // (two bytes per pixel: U, V of 8 bits or one 16-bit sample - the same halves of a dword)
                     const uint2 d = *reinterpret_cast<const uint2*>(p);
                     px.x = d.x & 0xFFFFu; px.y = d.x >> 16; px.z = d.y & 0xFFFFu; px.w = d.y >> 16;
@@ -727,7 +742,11 @@ __device__ __forceinline__ void scale_stage(const WarpJob& j, uint32_t* tile, in
     }
 }
 
-template <int SB>
+// RGB: interleaved colour jobs (8-bit, cn 3 or 4), a kernel of its own.  cn 4: ONE aligned 16-byte load as above.  cn 3: four
+// pixels are 12 bytes, three dwords, and the loads ask for dword alignment only: the rows keep it when the stride is a multiple of 4,
+// and since 3 = -1 (mod 4) the columns x with x = address of the crop's first sample (mod 4) are the aligned ones.  Every staged dword
+// is written as part of a lane's 16 bytes (ds_write_b128, consecutive lanes consecutive 16 bytes), whatever the pixel size.
+template <int SB, bool RGB = false>
 __device__ __forceinline__ void scale_jobs_tile(const WarpJobsArg& a) {
     __shared__ int s_ad[TW], s_bd[TW], s_x0[TH], s_y0[TH];
     __shared__ __attribute__((aligned(16))) uint32_t tile[SBW * SBH];
@@ -752,17 +771,30 @@ __device__ __forceinline__ void scale_jobs_tile(const WarpJobsArg& a) {
     // a lane's four pixels are one aligned load where the job's rows keep that alignment; k = the pixels between the aligned address
     // at or in front of the crop's first sample and that sample: the columns x with (x + k) % 4 == 0 are aligned
     const int pxb = j.cn * SB, lb = 4 * pxb;
-    const int aligned = (uintptr_t)j.src % pxb == 0 && j.sstride % lb == 0;
-    const int k = aligned ? (int)((uintptr_t)j.src % lb) / pxb : 0;
+    const bool rgb3 = RGB && j.cn == 3;
+    const int aligned = rgb3 ? j.sstride % 4 == 0 : (uintptr_t)j.src % pxb == 0 && j.sstride % lb == 0;
+    const int k = !aligned ? 0 : rgb3 ? (int)(-(uintptr_t)j.src & 3) : (int)((uintptr_t)j.src % lb) / pxb;
     const int bx0a = ((bx0 + k) & ~3) - k;
     const int bw = (bx1 + 2 - bx0a + 3) & ~3, bh = by1 + 2 - by0;
     WarpCore c;
     c.sstride = j.sstride; c.dstride = j.dstride;
     c.sw = j.sw; c.sh = j.sh; c.dw = j.dw; c.dh = j.dh;
     c.src_aligned = aligned;
-    const int galign = SB == 2 ? 8 * j.cn : j.cn == 2 ? 8 : 4;        // (a lane's four pixels in one store)
+    const int galign = SB == 2 ? 8 * j.cn : j.cn == 2 ? 8 : RGB && j.cn == 4 ? 16 : 4;        // (a lane's four pixels in one store; cn 3: three dwords)
     c.dst_aligned = ((uintptr_t)j.dst % galign == 0) && (j.dstride % galign == 0);
     c.border = j.border;
+    if constexpr (RGB) {
+        if (j.cn == 4) {
+            scale_stage<4, 1>(j, tile, bx0a, by0, bw, bh, aligned, tid);
+            __syncthreads();
+            emit_rows<4, true>(c, j.src, j.dst, tile, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, bx0a, by0, bw, tid);
+        } else {
+            scale_stage<3, 1>(j, tile, bx0a, by0, bw, bh, aligned, tid);
+            __syncthreads();
+            emit_rows<3, true>(c, j.src, j.dst, tile, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, bx0a, by0, bw, tid);
+        }
+        return;
+    }
     if (j.cn == 1) {
         scale_stage<1, SB>(j, tile, bx0a, by0, bw, bh, aligned, tid);
         __syncthreads();
@@ -776,6 +808,7 @@ __device__ __forceinline__ void scale_jobs_tile(const WarpJobsArg& a) {
 
 __global__ __launch_bounds__(NT) void scale_jobs_kernel(WarpJobsArg a) { scale_jobs_tile<1>(a); }
 __global__ __launch_bounds__(NT) void scale_jobs16_kernel(WarpJobsArg a) { scale_jobs_tile<2>(a); }
+__global__ __launch_bounds__(NT) void scale_jobs_rgb_kernel(WarpJobsArg a) { scale_jobs_tile<1, true>(a); }
 
 // ---- tile building blocks shared by the table kernels ------------------------------------------------------------
 constexpr int TABN = 2 * TW + 2 * TH;     // ints of coordinate terms per tile: ad[128] bd[128] x0[16] y0[16]
@@ -2159,8 +2192,18 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
     return VS_OK;
 }
 
+// What the job launchers refuse about a job (first: the launch's first job - one sample size per launch).  rgb: the launchers of
+// interleaved colour jobs, 8-bit samples, cn 3 or 4.
+static bool bad_job(const WarpJob& j, const WarpJob& first, bool rgb) {
+    const bool bad_cn = rgb ? j.sb != 1 || (j.cn != 3 && j.cn != 4) : j.cn < 1 || j.cn > (j.sb == 2 ? 2 : 3);
+    return (j.sb != 1 && j.sb != 2) || j.sb != first.sb || bad_cn ||
+           bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn * j.sb, 1) ||
+           (j.border != VS_BORDER_BLACK && j.border != VS_BORDER_REPLICATE) ||
+           (j.sb == 2 && (((uintptr_t)j.src | (uintptr_t)j.dst | j.sstride | j.dstride) & 1));
+}
+
 // n <= WARP_JOBS_MAX warps of any geometry (inverse maps in double on the host) as one launch; one sample size for all of them.
-int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st) {
+static int warp_jobs_go(const WarpJob* jobs, int n, hipStream_t st, bool rgb) {
     if (!jobs || n < 1 || n > WARP_JOBS_MAX) { set_last_error("warp_jobs: invalid argument"); return VS_ERR_INVALID_ARG; }
     WarpJobsArg a;
     int gw = 1, gh = 1;
@@ -2168,21 +2211,21 @@ int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st) {
         a.j[i] = jobs[i < n ? i : 0];
         if (i >= n) continue;
         const WarpJob& j = jobs[i];
-        if ((j.sb != 1 && j.sb != 2) || j.sb != jobs[0].sb || j.cn < 1 || j.cn > (j.sb == 2 ? 2 : 3) ||
-            bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn * j.sb, 1) ||
-            (j.border != VS_BORDER_BLACK && j.border != VS_BORDER_REPLICATE) ||
-            (j.sb == 2 && (((uintptr_t)j.src | (uintptr_t)j.dst | j.sstride | j.dstride) & 1))) {
+        if (bad_job(j, jobs[0], rgb)) {
             set_last_error("warp_jobs: invalid argument");
             return VS_ERR_INVALID_ARG;
         }
         gw = std::max(gw, (j.dw + TW - 1) / TW);
         gh = std::max(gh, (j.dh + TH - 1) / TH);
     }
-    if (jobs[0].sb == 2) hipLaunchKernelGGL(warp_jobs16_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
+    if (rgb) hipLaunchKernelGGL(warp_jobs_rgb_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
+    else if (jobs[0].sb == 2) hipLaunchKernelGGL(warp_jobs16_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
     else hipLaunchKernelGGL(warp_jobs_kernel, dim3(gw, gh, n), dim3(NT), 0, st, a);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }
+
+int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st) { return warp_jobs_go(jobs, n, st, false); }
 
 // Samples of a source row or column that a full tile of n output samples touches at most, taps included, under the inverse scale
 // factor inv (the bound in front of scale_jobs_tile).
@@ -2191,40 +2234,45 @@ static int scale_span(double inv, int n) { return (int)std::floor((inv * (n - 1)
 // Whether launch_scale_jobs sends a job to the staged kernel: a diagonal map that does not mirror, border 0, cn 1 or 2, and the box of
 // a full tile - widened by the 3 + 3 samples of the aligned origin and the rounded-up pitch - inside the staging area.  That is an
 // inverse factor below (SBW - 9) / (TW - 1) = 1.19 across and (SBH - 3) / (TH - 1) = 1.4 down: every zoom-in, and mild downscales.
-bool scale_job_staged(const WarpJob& j) {
-    if (j.border != VS_BORDER_BLACK || j.cn < 1 || j.cn > 2 || j.m[1] != 0 || j.m[3] != 0 || !(j.m[0] > 0) || !(j.m[4] > 0)) return false;
+// (the staging area is one dword per pixel whatever the pixel's size: the colour jobs, cn 3 and 4, are staged under the same bound)
+static bool scale_map_staged(const WarpJob& j) {
+    if (j.border != VS_BORDER_BLACK || j.m[1] != 0 || j.m[3] != 0 || !(j.m[0] > 0) || !(j.m[4] > 0)) return false;
     if (j.m[0] > 2 || j.m[4] > 2 || j.sw > 32767 || j.sh > 32767) return false;      // (far outside; sat_s16 never acts on a staged job)
     return scale_span(j.m[0], TW) + 6 <= SBW && scale_span(j.m[4], TH) <= SBH;
 }
+bool scale_job_staged(const WarpJob& j) { return j.cn >= 1 && j.cn <= 2 && scale_map_staged(j); }
+bool scale_job_staged_rgb(const WarpJob& j) { return j.sb == 1 && (j.cn == 3 || j.cn == 4) && scale_map_staged(j); }
 
 // The crop-and-scale jobs of a batch: those that can be staged as ONE launch of the staged kernel, the others as ONE launch of
 // launch_warp_jobs - a batch of one class is one launch.  path 1: all of them through launch_warp_jobs.
-int launch_scale_jobs(const WarpJob* jobs, int n, int path, hipStream_t st) {
+// rgb: interleaved colour jobs (cn 3 or 4, 8-bit) through the colour instances of both kernels.
+static int scale_jobs_go(const WarpJob* jobs, int n, int path, hipStream_t st, bool rgb) {
     if (!jobs || n < 1 || n > WARP_JOBS_MAX || (path != 0 && path != 1)) { set_last_error("scale_jobs: invalid argument"); return VS_ERR_INVALID_ARG; }
     WarpJob direct[WARP_JOBS_MAX];
     WarpJobsArg a;
     int ns = 0, nd = 0, gw = 1, gh = 1;
     for (int i = 0; i < n; i++) {
         const WarpJob& j = jobs[i];
-        if ((j.sb != 1 && j.sb != 2) || j.sb != jobs[0].sb || j.cn < 1 || j.cn > (j.sb == 2 ? 2 : 3) ||
-            bad_args(j.src, j.dst, j.m, j.sstride, j.sw, j.sh, j.dstride, j.dw, j.dh, j.cn * j.sb, 1) ||
-            (j.border != VS_BORDER_BLACK && j.border != VS_BORDER_REPLICATE) ||
-            (j.sb == 2 && (((uintptr_t)j.src | (uintptr_t)j.dst | j.sstride | j.dstride) & 1))) {
+        if (bad_job(j, jobs[0], rgb)) {
             set_last_error("scale_jobs: invalid argument");
             return VS_ERR_INVALID_ARG;
         }
-        if (path == 1 || !scale_job_staged(j)) { direct[nd++] = j; continue; }
+        if (path == 1 || !(rgb ? scale_job_staged_rgb(j) : scale_job_staged(j))) { direct[nd++] = j; continue; }
         a.j[ns++] = j;
         gw = std::max(gw, (j.dw + TW - 1) / TW);
         gh = std::max(gh, (j.dh + TH - 1) / TH);
     }
     if (ns) {
         for (int i = ns; i < WARP_JOBS_MAX; i++) a.j[i] = a.j[0];
-        if (jobs[0].sb == 2) hipLaunchKernelGGL(scale_jobs16_kernel, dim3(gw, gh, ns), dim3(NT), 0, st, a);
+        if (rgb) hipLaunchKernelGGL(scale_jobs_rgb_kernel, dim3(gw, gh, ns), dim3(NT), 0, st, a);
+        else if (jobs[0].sb == 2) hipLaunchKernelGGL(scale_jobs16_kernel, dim3(gw, gh, ns), dim3(NT), 0, st, a);
         else hipLaunchKernelGGL(scale_jobs_kernel, dim3(gw, gh, ns), dim3(NT), 0, st, a);
         VS_HIP_TRY(hipGetLastError());
     }
-    return nd ? launch_warp_jobs(direct, nd, st) : VS_OK;
+    return nd ? warp_jobs_go(direct, nd, st, rgb) : VS_OK;
 }
+
+int launch_scale_jobs(const WarpJob* jobs, int n, int path, hipStream_t st) { return scale_jobs_go(jobs, n, path, st, false); }
+int launch_scale_jobs_rgb(const WarpJob* jobs, int n, int path, hipStream_t st) { return scale_jobs_go(jobs, n, path, st, true); }
 
 }  // namespace vsd

@@ -187,6 +187,10 @@ int launch_warp_jobs(const WarpJob* jobs, int n, hipStream_t st);
 // through launch_warp_jobs.  scale_job_staged is host arithmetic on the job's inverse map alone.
 bool scale_job_staged(const WarpJob& j);
 int launch_scale_jobs(const WarpJob* jobs, int n, int path, hipStream_t st);
+// The same for jobs on interleaved colour frames: 8-bit samples, cn 3 or 4 (mixed freely), every channel a channel of its own - the
+// colour instances of the two kernels; one staging bound for all pixel sizes (a staged pixel is a dword).
+bool scale_job_staged_rgb(const WarpJob& j);
+int launch_scale_jobs_rgb(const WarpJob* jobs, int n, int path, hipStream_t st);
 int launch_resize_gray(const uint8_t* d_src, size_t sstride, int sw, int sh, int fmt,
                        uint8_t* d_dst, size_t dstride, int dw, int dh, hipStream_t st);
 // Batched forms (batch mode): the images of `items` frames in one launch; d_pairs = device table of

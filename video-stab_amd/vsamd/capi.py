@@ -494,6 +494,14 @@ class VsLib:
             L.vs_stab_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
             L.vs_batch_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
             L.vs_op_resize_jobs.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, vp]
+            # roll correction and auto zoom/crop on interleaved colour frames (BGR8, RGB8, BGRA8, RGBA8)
+            L.vs_roll_correct_rgb_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]
+            L.vs_roll_correct_rgb_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t]
+            L.vs_azc_apply_rgb_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int64)]
+            L.vs_azc_apply_rgb_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
+                                                 C.POINTER(C.c_int64)]
+            L.vs_op_scale_jobs_rgb.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, vp]
+            L.vs_op_scale_jobs_rgb_plan.argtypes = [C.POINTER(VsScaleJob), C.c_int, i32p]
         except AttributeError:      # a library of an earlier build (A/B measurements)
             pass
 
@@ -794,6 +802,16 @@ class VsLib:
         """vs_op_scale_jobs_plan (no device needed): 1 per job that path 0 sends to the staged kernel."""
         staged = np.zeros(max(1, len(jobs)), np.int32)
         self.check(self.lib.vs_op_scale_jobs_plan(self._scale_job_array(jobs), len(jobs), sample_bytes, _p(staged, i32p)))
+        return staged[:len(jobs)].copy()
+
+    def scale_jobs_rgb(self, jobs, path=0, stream=None):
+        """vs_op_scale_jobs_rgb: crops of interleaved colour frames (8-bit, cn 3 or 4), tuples as for scale_jobs; asynchronous."""
+        self.check(self.lib.vs_op_scale_jobs_rgb(self._scale_job_array(jobs), len(jobs), path, stream))
+
+    def scale_jobs_rgb_plan(self, jobs):
+        """vs_op_scale_jobs_rgb_plan (no device needed): 1 per job that path 0 sends to the staged kernel."""
+        staged = np.zeros(max(1, len(jobs)), np.int32)
+        self.check(self.lib.vs_op_scale_jobs_rgb_plan(self._scale_job_array(jobs), len(jobs), _p(staged, i32p)))
         return staged[:len(jobs)].copy()
 
     def copy_make_border(self, img, b, border, src_pitch=None):
@@ -1172,6 +1190,21 @@ class AutoZoomCrop:
         self._check(self.lib.vs_azc_apply_i420_dev_n(self.h, fmt, a, b, n, w, h, C.byref(lin), C.byref(lout), t))
         return list(t)
 
+    def apply_rgb_dev(self, fmt, d_in, w, h, stride, d_out, out_stride):
+        """apply_nv12_dev for an interleaved colour frame (vs_azc_apply_rgb_dev): fmt FMT_BGR8, FMT_RGB8, FMT_BGRA8 or FMT_RGBA8."""
+        t = C.c_int64(-1)
+        self._check(self.lib.vs_azc_apply_rgb_dev(self.h, fmt, d_in, w, h, stride, d_out, out_stride, C.byref(t)))
+        return t.value
+
+    def apply_rgb_dev_n(self, fmt, d_ins, w, h, stride, d_outs, out_stride):
+        """n colour frames in call order, one trip through the binding; returns the tickets."""
+        n = len(d_ins)
+        a = (C.c_void_p * max(1, n))(*d_ins)
+        b = (C.c_void_p * max(1, n))(*d_outs)
+        t = (C.c_int64 * max(1, n))()
+        self._check(self.lib.vs_azc_apply_rgb_dev_n(self.h, fmt, a, b, n, w, h, stride, out_stride, t))
+        return list(t)[:n]
+
     def result(self, ticket):
         ow, oh = C.c_int(), C.c_int()
         info = np.zeros(8, np.int32)
@@ -1492,6 +1525,16 @@ class RollCorrection:
         a = (C.c_void_p * n)(*d_ins)
         b = (C.c_void_p * n)(*d_outs)
         self._check(self.lib.vs_roll_correct_i420_dev_n(self.h, fmt, a, b, n, w, h, C.byref(lin), C.byref(lout)))
+
+    def correct_rgb_dev(self, fmt, d_in, w, h, stride, d_out, out_stride):
+        """correct_nv12_dev for an interleaved colour frame (vs_roll_correct_rgb_dev): fmt FMT_BGR8, FMT_RGB8, FMT_BGRA8 or FMT_RGBA8."""
+        self._check(self.lib.vs_roll_correct_rgb_dev(self.h, fmt, d_in, w, h, stride, d_out, out_stride))
+
+    def correct_rgb_dev_n(self, fmt, d_ins, w, h, stride, d_outs, out_stride):
+        n = len(d_ins)
+        a = (C.c_void_p * max(1, n))(*d_ins)
+        b = (C.c_void_p * max(1, n))(*d_outs)
+        self._check(self.lib.vs_roll_correct_rgb_dev_n(self.h, fmt, a, b, n, w, h, stride, out_stride))
 
     def sync(self):
         self._check(self.lib.vs_roll_sync(self.h))
