@@ -48,7 +48,9 @@ extern "C" {
  *    vs_enh_apply_yuv_batch_dev, vs_enh_last_fused and vs_enh_yuv_plan; the colour space of the conversions: struct
  *    vs_cvt_colorimetry with vs_op_cvt_yuv_to_rgb_cs, vs_op_cvt_rgb_to_yuv_cs, vs_enh_set_yuv_colorimetry, vs_cvt_coefficients and
  *    vs_cvt_colorimetry_guess; conversion between the YUV surface formats: struct vs_yuv_cvt_desc with vs_op_cvt_yuv_to_yuv and
- *    vs_yuv_surface_layout; crop-and-zoom on YUV streams: vs_stab_set_yuv_crop_zoom, vs_batch_set_yuv_crop_zoom and vs_op_resize_jobs
+ *    vs_yuv_surface_layout; crop-and-zoom on YUV streams: vs_stab_set_yuv_crop_zoom, vs_batch_set_yuv_crop_zoom and vs_op_resize_jobs;
+ *    border pad on YUV streams: struct vs_yuv_fill with vs_stab_set_yuv_border_pad, vs_batch_set_yuv_border_pad and
+ *    vs_yuv_video_black, struct vs_pad_job with vs_op_pad_jobs
  *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
@@ -88,7 +90,7 @@ typedef enum vs_pixfmt {
  *    are 0, each by itself), rounded once, half to even: (S + 511 + ((S >> 10) & 1)) >> 10.  For ten-bit content that is
  *    what OpenCV's float blend gives; for arbitrary 16-bit content it is the definition (docs/opencv_semantics.md);
  *  - everything else follows NV12: the last frame of a flush comes back unwarped; border pad, crop-and-zoom, fade and the
- *    virtual canvas are refused as for NV12 (crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom).
+ *    virtual canvas are refused as for NV12 (crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad).
  * The two stages around the stabilizer take P010 surfaces too (vs_roll_correct_p010_dev, vs_azc_apply_p010_dev):
  *  - analysis plane: both analyse the 8-bit plane of the luma samples' high bytes (sample >> 8), the plane the stabilizer analyses.
  *    Smoothed and detected angle, line counts, content mask, contours, info8 and the crop rectangle are bit-identical to those of
@@ -123,7 +125,7 @@ typedef enum vs_pixfmt16 {
  *    in float (cv::warpAffine treats channels independently: these are the two channels of the NV12 chroma plane's warp),
  *    INTER_LINEAR, BORDER_CONSTANT 0;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are refused as for NV12 (VS_ERR_UNSUPPORTED; crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom); the
+ *    are refused as for NV12 (VS_ERR_UNSUPPORTED; crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad); the
  *    enhancer and the C++ classes do not take it.
  * The two stages around the stabilizer take I420 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev; layouts as
  * struct vs_i420_layout): every observable is again that of the NV12 call on the same samples, the planes de-interleaved -
@@ -153,7 +155,7 @@ typedef enum vs_pixfmt_planar {
  *    halved in float; INTER_LINEAR, BORDER_CONSTANT 0, the blend of P010 to the letter (S rounded once, half to even).  The warp
  *    does not depend on the bit depth;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are VS_ERR_UNSUPPORTED (crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom); the enhancer and the C++
+ *    are VS_ERR_UNSUPPORTED (crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad); the enhancer and the C++
  *    classes do not take these formats.
  * The two stages around the stabilizer take I010 / I012 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev with fmt
  * VS_FMT_I010 / VS_FMT_I012):
@@ -199,7 +201,7 @@ typedef enum vs_pixfmt_planar16 {
  *    half to even (vs_pixfmt16) - which does not depend on the bit depth.  (For 4:2:2, Mc is not a rotation.)
  *  - the last frame of a flush comes back unwarped, all three planes;
  *  - border pad, crop-and-zoom, fade and the virtual canvas are VS_ERR_UNSUPPORTED, with a text that names the format, exactly
- *    where I420 is refused (crop-and-zoom unless the stream opts in: vs_stab_set_yuv_crop_zoom).  The C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16, P210, NV24),
+ *    where I420 is refused (crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad).  The C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16, P210, NV24),
  *    yuv4xxp16le and big-endian samples are not built.
  * The two stages around the stabilizer take these formats through the entry points of the 4:2:0 ones (vs_roll_correct_i420_dev,
  * vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev, vs_azc_apply_i420_dev_n; layouts as struct vs_i420_layout, whose default chroma
@@ -520,11 +522,46 @@ int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t
  *      depth or on where the value sits in the word (P010: high bits, I010: low bits).
  * w - 2b <= 0 or h - 2b <= 0: the frame is only warped, as for BGR8.  The last frame of a flush comes back unwarped and uncropped.
  * Analysis, trajectory and warp matrix do not depend on border_size or crop_n_zoom: the debug values are those of the same stream
- * with border_size = 0, bit for bit.  Border pad (crop_n_zoom = 0), the fade border and the virtual canvas stay refused on YUV
+ * with border_size = 0, bit for bit.  Border pad (crop_n_zoom = 0; a switch of its own, vs_stab_set_yuv_border_pad), the fade border and the virtual canvas stay refused on YUV
  * streams, with their texts; GRAY8 is not touched by the mode.  Zero-copy input, the decoder layouts (vs_stab_set_nv12_layout,
  * vs_stab_set_i420_layout) and the host entry points work as without the mode; in batch mode the warps of a launch (<= 32
  * surfaces) fill scratch surfaces and ONE launch behind them resizes all their planes. */
 int vs_stab_set_yuv_crop_zoom(vs_stab* s, int enable);
+/* Border pad on YUV streams - the reference's other border mode, crop_n_zoom = 0 with border_size = b > 0 and borderType black,
+ * reflect, reflect101, replicate or wrap (Stabilizer.cpp:981-990: the frame gets a border of b pixels, the padded frame is warped, the
+ * result has (w + 2b) x (h + 2b) pixels; the only mode that keeps every input pixel), on NV12, P010 and the three-plane formats.  Off
+ * by default: such a stream is VS_ERR_UNSUPPORTED as ever, and allocates and launches exactly what it did.  The reference has no YUV
+ * path, so what the mode does is a DEFINITION of this library, which a caller opts into with this call (enable != 0; the frame queue
+ * must be empty).  It is independent of vs_stab_set_yuv_crop_zoom.  With the mode on, crop_n_zoom == 0, border_size = b > 0 and
+ * border_type VS_BORDER_BLACK .. VS_BORDER_WRAP, every plane of a surface is processed on its own:
+ *  (a) pad: cv::copyMakeBorder per plane.  Y gets b columns and rows on every side, U and V (b >> sx) columns and (b >> sy) rows,
+ *      the interleaved UV plane of NV12 / P010 the same in (U, V) pairs.  b must be a multiple of 2^sx and 2^sy - even for every
+ *      subsampled format, anything for 4:4:4; an odd b on a subsampled format is VS_ERR_INVALID_ARG with a text that names the
+ *      format.  VS_BORDER_BLACK writes the plane's fill sample (below) where the reference writes 0; the other four modes index
+ *      the plane itself by cv::borderInterpolate, reflections that fold more than once (a chroma plane smaller than its border)
+ *      included.
+ *  (b) warp: the padded surface of (w + 2b) x (h + 2b) is warped exactly as the stream warps a surface of that size under the same
+ *      matrices (Y under M, chroma under the stream's chroma matrix) but with BORDER_REPLICATE: a tap outside the padded plane
+ *      takes the nearest edge sample, each tap by itself (8-bit: the arithmetic of vs_op_warp_affine_ex; 16-bit: P010's blend).
+ *      NOT BORDER_CONSTANT 0 as for BGR8: zero samples are not a colour in YUV - (0, 0, 0) is saturated green - whereas the edge
+ *      of a padded plane is its border.  With VS_BORDER_BLACK the whole surround of the picture is therefore exactly the fill
+ *      colour; with VS_BORDER_REPLICATE the result is the replicate-warp of the frame on a larger canvas.
+ * fill: the samples of the three planes as they lie in memory (reserved = 0); NULL = limited-range video black of the format
+ * (vs_yuv_video_black: Y = 16 << (bits - 8), U = V = 128 << (bits - 8); P010: in the high bits, 0x1000 and 0x8000).  A value above
+ * 255 on an 8-bit format is VS_ERR_INVALID_ARG, here when the format is known, else at the next push.
+ * The result has (w + 2b) x (h + 2b) pixels (vs_stab_last_out_dims): out_stride must hold a padded row, default plane offsets and
+ * the default chroma pitch are those of a packed surface of the padded size, an explicit output layout (vs_stab_set_nv12_layout,
+ * vs_stab_set_i420_layout) describes the padded surface, and an explicit output chroma pitch below a padded chroma row is
+ * VS_ERR_INVALID_ARG.  The last frame of a flush has no transform: it comes back unpadded, w x h, with the default offsets of
+ * that size at out_stride (vs_stab_last_out_dims reports (w, h)); nothing else of the output is written.  Analysis, trajectory,
+ * matrices and debug records do not depend on border_size: they are those of the stream with border_size = 0, bit for bit.
+ * The fade border and the virtual canvas stay refused on YUV streams, with their texts; GRAY8 and the interleaved formats are
+ * not touched.  Zero-copy input, the decoder layouts and the host entry points work as without the mode; in batch mode ONE launch
+ * in front of each warp launch (<= 32 surfaces) pads all their planes. */
+typedef struct vs_yuv_fill { uint16_t y, u, v, reserved; } vs_yuv_fill;   /* samples as they lie in memory */
+int vs_stab_set_yuv_border_pad(vs_stab* s, int enable, const vs_yuv_fill* fill);
+/* Limited-range video black of a YUV format, as above.  Host only; VS_ERR_INVALID_ARG for a format without chroma planes. */
+int vs_yuv_video_black(int fmt, vs_yuv_fill* out);
 
 /* ---- several streams of one device scheduled together (BASELINE configs[4]: 64 streams = 8 per GPU) ----------------------
  * The reference runs one Stabilizer per stream, each with its own cv::cuda::Stream objects (src/Stabilizer.cpp:102-104); here a
@@ -565,6 +602,8 @@ int vs_batch_set_i420_layout(vs_batch* b, size_t in_u_off, size_t in_v_off, size
                              size_t out_c_pitch);
 /* vs_stab_set_yuv_crop_zoom for every member (the members of a group must agree on the mode; a step refuses those that do not) */
 int vs_batch_set_yuv_crop_zoom(vs_batch* b, int enable);
+/* vs_stab_set_yuv_border_pad for every member (the members of a group must agree on the mode and the fill) */
+int vs_batch_set_yuv_border_pad(vs_batch* b, int enable, const vs_yuv_fill* fill);
 int vs_batch_push_dev(vs_batch* b, const void* const* d_frames, int w, int h, size_t stride, int fmt, void* const* d_outs,
                       size_t out_stride, int* produced);
 int vs_batch_flush_dev(vs_batch* b, void* const* d_outs, size_t out_stride, int* produced);
@@ -943,6 +982,18 @@ int vs_op_scale_jobs_rgb_plan(const vs_scale_job* jobs, int n, int32_t* staged);
  * vs_op_scale_jobs, which is cv::warpAffine arithmetic).  Refusals are decided before any device call, with a text in
  * vs_last_error that names the call and the job.  Asynchronous on `stream`. */
 int vs_op_resize_jobs(const vs_scale_job* jobs, int n, int sample_bytes, void* stream);
+/* The pad of border pad on YUV surfaces as an operator (the call a stream with vs_stab_set_yuv_border_pad makes in front of its
+ * warps): n = 1 .. 96 jobs of one sample size (1 or 2 bytes; 32 surfaces of up to three planes) in ONE launch, cn 1 and 2 mixed.
+ * A job pads the sw x sh samples (of cn channels) at src to (sw + 2 bx) x (sh + 2 by) at dst: cv::copyMakeBorder with
+ * border = VS_BORDER_BLACK .. VS_BORDER_WRAP, where VS_BORDER_BLACK writes fill[channel] instead of 0; bx = by = 0 copies.
+ * bx, by >= 0, padded sizes 1 .. 32767, strides in bytes and below 2^32, reserved = 0; 16-bit pointers and strides even; a fill above 255 with
+ * 8-bit samples is refused; source and destination must not overlap.  No byte outside the source plane is read, none outside
+ * the padded plane written.  Refusals (VS_ERR_INVALID_ARG) are decided before any device call, with a text in vs_last_error that
+ * names the call and the job.  Asynchronous on `stream`. */
+typedef struct vs_pad_job { const void* src; size_t src_stride; int32_t sw, sh;      /* samples of cn channels */
+                            void* dst; size_t dst_stride; int32_t bx, by;            /* dst is (sw + 2bx) x (sh + 2by) */
+                            int32_t cn, border; uint16_t fill[2]; int32_t reserved; } vs_pad_job;
+int vs_op_pad_jobs(const vs_pad_job* jobs, int n, int sample_bytes, void* stream);
 /* Diagnostics of the asynchronous path: out9 = {frames through the worker threads; seconds, summed over the threads: without a
  * frame to work on, waiting for the masks of the batches on their way (one worker at a time does), in the contour logic, queueing
  * launches and publishing; batches; seconds, summed over the batches: from a batch's launches to the arrival of its masks on the

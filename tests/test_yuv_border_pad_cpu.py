@@ -1,0 +1,207 @@
+"""Border pad on YUV streams, the parts that need no GPU.
+
+1. tests/yuvpadref.py, the numpy statement of the pad: equal to np.pad with compref.NP_PAD for the five modes, both sample sizes and
+   cn 1 and 2, planes smaller than their border included; equal to the oracle's cv::copyMakeBorder for 8-bit planes; and the
+   property the definition rests on - a constant plane padded BLACK with that constant and replicate-warped is the constant.
+2. The refusal rules (video-stab_amd/csrc/pixfmt.h through tests/cpp/yuv_pad_check.cpp): without the mode every answer is today's;
+   with it an even border passes for the eleven YUV formats, an odd one fails for the eight subsampled ones, fade and canvas keep
+   their texts, and the crop-and-zoom answers do not move.
+3. The ABI surface: the four new entry points are exported and declared, the operator refuses without a device, and
+   vs_yuv_video_black gives the stated values."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import compref
+import planar_inputs as pi
+import refusal_cases
+import yuvpadref as yp
+from vsamd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {yp.BLACK: "black", yp.REFLECT: "reflect", yp.REFLECT_101: "reflect101", yp.REPLICATE: "replicate", yp.WRAP: "wrap"}
+# (w, h), (bx, by): planes smaller than their border (reflections fold several times), the streams' sizes, unequal borders
+SHAPES = [((1, 1), (7, 7)), ((2, 3), (7, 7)), ((5, 4), (7, 7)), ((1, 1), (3, 3)), ((126, 92), (2, 2)), ((64, 48), (15, 30)), ((33, 17), (0, 0)), ((9, 20), (4, 0))]
+
+
+# ---- 1. the numpy statement --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cn", [1, 2])
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16], ids=["u8", "u16"])
+@pytest.mark.parametrize("mode", yp.MODES, ids=NAMES.get)
+def test_pad_plane_is_np_pad(mode, dtype, cn):
+    rng = np.random.default_rng(mode * 7 + cn)
+    for (w, h), (bx, by) in SHAPES:
+        plane = rng.integers(0, np.iinfo(dtype).max + 1, (h, w) if cn == 1 else (h, w, cn), dtype=dtype)
+        fill = [int(v) for v in rng.integers(1, np.iinfo(dtype).max + 1, cn)]
+        got = yp.pad_plane(plane, bx, by, mode, fill[0] if cn == 1 else fill)
+        widths = ((by, by), (bx, bx)) + (((0, 0),) if cn == 2 else ())
+        if mode == yp.BLACK:
+            want = np.stack([np.pad(plane.reshape(h, w, cn)[..., c], widths[:2], "constant", constant_values=fill[c]) for c in range(cn)], axis=-1).reshape(got.shape)
+        else:
+            want = np.pad(plane, widths, compref.NP_PAD[mode])
+        assert got.dtype == dtype and got.shape == want.shape and np.array_equal(got, want), ((w, h), (bx, by))
+
+
+@pytest.mark.parametrize("mode", yp.MODES, ids=NAMES.get)
+def test_pad_plane_is_the_oracles_copy_make_border(oracle, mode):
+    rng = np.random.default_rng(40 + mode)
+    for (w, h), (bx, by) in SHAPES:
+        if bx != by:
+            continue
+        plane = rng.integers(0, 256, (h, w), np.uint8)
+        assert np.array_equal(yp.pad_plane(plane, bx, by, mode, 0), oracle.copy_make_border(plane, bx, mode)), ((w, h), bx)
+
+
+def test_pad_surface_pads_every_plane_by_its_shifts():
+    rng = np.random.default_rng(8)
+    y, u, v = (rng.integers(0, 1024, s, np.uint16) for s in ((48, 64), (48, 32), (48, 32)))       # 4:2:2
+    py, pu, pv = yp.pad_surface([y, u, v], 1, 0, 6, yp.BLACK, (64, 512, 500))
+    assert py.shape == (60, 76) and pu.shape == (60, 38) == pv.shape
+    assert np.array_equal(py[6:-6, 6:-6], y) and np.array_equal(pu[6:-6, 3:-3], u) and np.array_equal(pv[6:-6, 3:-3], v)
+    assert py[0, 0] == 64 and pu[0, 0] == 512 and pv[59, 37] == 500
+    uv = rng.integers(0, 256, (24, 32, 2), np.uint8)                                             # the UV plane of a 64 x 48 NV12 surface
+    py, puv = yp.pad_surface([y.astype(np.uint8), uv], 1, 1, 30, yp.BLACK, yp.video_black(8))
+    assert puv.shape == (54, 62, 2) and np.all(puv[:15] == 128) and np.array_equal(puv[15:-15, 15:-15], uv) and py[0, 0] == 16
+    puv = yp.pad_surface([y.astype(np.uint8), uv], 1, 1, 30, yp.REFLECT, (0, 0, 0))[1]
+    assert np.array_equal(puv[14, 15:-15], uv[0]) and np.array_equal(puv[13, 15:-15], uv[1])
+    with pytest.raises(AssertionError):
+        yp.pad_surface([y, u, v], 1, 0, 5, yp.BLACK, (0, 0, 0))
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16], ids=["u8", "u16"])
+def test_a_constant_plane_padded_black_and_replicate_warped_is_the_constant(oracle, dtype):
+    """What makes the surround of a VS_BORDER_BLACK stream exactly the fill colour: every tap of the replicate warp of a constant
+    plane reads the constant, and the blend of four equal taps is the tap."""
+    for c in ((16, 128, 235) if dtype == np.uint8 else (64, 512, 0x8000, 65535)):
+        padded = yp.pad_plane(np.full((20, 36), c, dtype), 6, 6, yp.BLACK, c)
+        for name, M in pi.ALL_MATS.items():
+            got = pi.warp_plane(oracle, padded, M, pi.REPLICATE)
+            assert got.shape == (32, 48) and np.all(got == c), (name, c)
+
+
+# ---- 2. the refusal rules ----------------------------------------------------------------------------------------------------
+YUV = ("NV12", "P010", "I420", "I010", "I012", "I422", "I444", "I210", "I212", "I410", "I412")
+SUBSAMPLED = ("NV12", "P010", "I420", "I010", "I012", "I422", "I210", "I212")
+FULL = ("I444", "I410", "I412")
+assert sorted(SUBSAMPLED + FULL) == sorted(YUV)
+BLACKS = dict(NV12=(16, 128, 128), I420=(16, 128, 128), I422=(16, 128, 128), I444=(16, 128, 128), P010=(0x1000, 0x8000, 0x8000),
+              I010=(64, 512, 512), I210=(64, 512, 512), I410=(64, 512, 512), I012=(256, 2048, 2048), I212=(256, 2048, 2048), I412=(256, 2048, 2048))
+
+
+def _rules(cases):
+    """cases: [(fmt, w, h, pitch, border, crop, canvas, fade, cz_mode, pad_mode, out_c_pitch)] -> [((rc, text) with the modes, (rc,
+    text) with the default arguments, (y, u, v) video black)]"""
+    build = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(build, exist_ok=True)
+    src, exe = os.path.join(ROOT, "tests", "cpp", "yuv_pad_check.cpp"), os.path.join(build, "yuv_pad_check")
+    deps = [src, os.path.join(ROOT, "video-stab_amd", "csrc", "pixfmt.h"), os.path.join(ROOT, "include", "vs_stab.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(p) for p in deps):
+        subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", exe, src])
+    text = "".join(" ".join(str(int(v)) for v in c) + "\n" for c in cases)
+    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = [ln.split("|") for ln in r.stdout.splitlines()]
+    assert len(rows) == len(cases) and all(len(x) == 7 for x in rows), r.stdout
+    return [((int(a), b), (int(c), d), (int(y), int(u), int(v))) for a, b, c, d, y, u, v in rows]
+
+
+def _pitch(name):
+    return 64 * capi.fmt_px_bytes(getattr(capi, "FMT_" + name))
+
+
+def test_without_the_mode_every_answer_is_todays():
+    """The recorded answers of the border cases (tests/golden/stream_refusals.json), asked with the mode off and with the arguments
+    left out; the mode on changes none of the crop-and-zoom and fade answers."""
+    golden = refusal_cases.load_golden(os.path.join(ROOT, "tests", "golden", "stream_refusals.json"))
+    todo = [c for c in refusal_cases.cases() if c.entry == "push_dev" and c.border > 0 and not refusal_cases.stateful(c) and not c.data_odd and not c.out_odd
+            and c.nv12 == (0, 0) and c.i420 == (0,) * 6 and c.out_pitch == c.pitch]
+    assert len(todo) >= 3 * 16
+    got = _rules([(c.fmt, c.w, c.h, c.pitch, c.border, c.crop, c.canvas, c.fade, 0, 0, 0) for c in todo])
+    for c, (with_mode, default, _) in zip(todo, got):
+        assert with_mode == default == golden[c.id], c.id
+    same = [c for c in todo if c.crop or c.fade]
+    assert len(same) >= 2 * 16
+    for c, (with_mode, default, _) in zip(same, _rules([(c.fmt, c.w, c.h, c.pitch, c.border, c.crop, c.canvas, c.fade, 0, 1, 0) for c in same])):
+        assert with_mode == default == golden[c.id], c.id
+
+
+@pytest.mark.parametrize("name", YUV)
+def test_with_the_mode_a_pad_passes_and_the_other_border_modes_keep_their_texts(name):
+    fmt, p = getattr(capi, "FMT_" + name), _pitch(name)
+    rows = _rules([(fmt, 64, 48, p, 8, 0, 0, 0, 0, 1, 0),      # an even border
+                   (fmt, 64, 48, p, 5, 0, 0, 0, 0, 1, 0),      # an odd one
+                   (fmt, 64, 48, p, 8, 0, 0, 1, 0, 1, 0),      # the fade
+                   (fmt, 64, 48, p, 8, 0, 1, 0, 0, 1, 0),      # the canvas on a padded stream
+                   (fmt, 64, 48, p, 0, 0, 1, 0, 0, 1, 0),      # the canvas alone
+                   (fmt, 64, 48, p, 8, 1, 0, 0, 0, 1, 0),      # crop-and-zoom with only the pad mode on
+                   (fmt, 64, 48, p, 8, 1, 0, 0, 1, 1, 0),      # ... with both modes on
+                   (fmt, 64, 48, p, 8, 0, 0, 0, 1, 0, 0)])     # a pad with only the crop-and-zoom mode on
+    (even, d_even, black), (odd, d_odd, _), (fade, d_fade, _), (padcanvas, _, _), (canvas, d_canvas, _), (crop, d_crop, _), (crop2, _, _), (czpad, d_czpad, _) = rows
+    assert even == (0, "")
+    assert d_even[0] == 4 and "colour format" in d_even[1]       # VS_ERR_UNSUPPORTED without the mode
+    if name in SUBSAMPLED:
+        assert odd[0] == 1 and name in odd[1] and "border pad" in odd[1] and "even border_size" in odd[1]
+    else:
+        assert odd == (0, "")
+    assert d_odd == d_even
+    assert fade == d_fade and fade[0] == 4 and "colour format" in fade[1]
+    assert canvas == d_canvas and canvas[0] == 4 and "enableVirtualCanvas needs a BGR8 stream" in canvas[1]
+    assert padcanvas == canvas
+    assert crop == d_crop and crop[0] == 4
+    assert crop2 == (0, "")
+    assert czpad == d_czpad and czpad[0] == 4
+    assert black == BLACKS[name]
+
+
+@pytest.mark.parametrize("name", ["I420", "I210", "I444"])
+def test_an_explicit_output_chroma_pitch_holds_a_padded_chroma_row(name):
+    fmt, p = getattr(capi, "FMT_" + name), _pitch(name)
+    info = capi.PIXFMT_BY_NAME[name]
+    sb = 1 if info.bits == 8 else 2
+    row = ((64 + 16) >> info.sx) * sb                      # a chroma row of the padded surface
+    unpadded = (64 >> info.sx) * sb
+    short, fits = _rules([(fmt, 64, 48, p, 8, 0, 0, 0, 0, 1, row - 2), (fmt, 64, 48, p, 8, 0, 0, 0, 0, 1, row)])
+    assert row - 2 >= unpadded
+    assert short[0][0] == 1 and "padded chroma row" in short[0][1] and name in short[0][1]
+    assert fits[0] == (0, "")
+
+
+def test_with_the_mode_gray8_and_the_colour_formats_answer_as_before():
+    for name in ("GRAY8", "BGR8", "BGRA8", "RGBA8", "RGB8"):
+        fmt, p = getattr(capi, "FMT_" + name), _pitch(name)
+        for a, d, black in _rules([(fmt, 64, 48, p, 8, 0, 0, 0, 0, 1, 0), (fmt, 64, 48, p, 5, 0, 0, 0, 0, 1, 0), (fmt, 64, 48, p, 8, 0, 0, 1, 0, 1, 0)]):
+            assert a == d and black == (0, 0, 0), name
+    assert _rules([(capi.FMT_GRAY8, 64, 48, 64, 8, 0, 0, 0, 0, 1, 0)])[0][0][0] == 4
+
+
+# ---- 3. the ABI surface ------------------------------------------------------------------------------------------------------
+NEW = ("vs_stab_set_yuv_border_pad", "vs_batch_set_yuv_border_pad", "vs_yuv_video_black", "vs_op_pad_jobs")
+
+
+def test_the_new_entry_points_are_exported_and_declared():
+    vs = capi.load()
+    header = open(os.path.join(ROOT, "include", "vs_stab.h")).read()
+    for name in NEW:
+        assert hasattr(vs.lib, name), name + " is not exported by libvideo-stab.so"
+        assert re.search(r"^int %s\(" % name, header, re.M), name + " is not declared in include/vs_stab.h"
+    assert vs.lib.vs_abi_version() == 2
+    assert C.sizeof(capi.VsPadJob) == 64 and C.sizeof(capi.VsYuvFill) == 8
+    # refusals of the operator are decided on the host: no device is needed to get them
+    assert vs.lib.vs_op_pad_jobs(None, 1, 1, None) == 1 and b"vs_op_pad_jobs" in vs.lib.vs_last_error()
+
+
+def test_video_black_of_every_format():
+    vs = capi.load()
+    for name, want in BLACKS.items():
+        assert vs.yuv_video_black(getattr(capi, "FMT_" + name)) == want, name
+    for fmt in (capi.FMT_BGR8, capi.FMT_GRAY8, -1, 99):
+        assert vs.lib.vs_yuv_video_black(fmt, C.byref(capi.VsYuvFill())) == 1
+    assert vs.lib.vs_yuv_video_black(capi.FMT_NV12, None) == 1
+    for bits, names in ((8, ("NV12", "I420")), (10, ("I010",)), (12, ("I412",))):
+        for n in names:
+            assert yp.video_black(bits) == BLACKS[n]
+    assert yp.video_black(10, high_bits=True) == BLACKS["P010"]

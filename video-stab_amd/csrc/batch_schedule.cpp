@@ -117,10 +117,19 @@ bool group_make_events(vs_batch* g) {
 // What the members must agree on: everything that shapes a launch (frame and analysis geometry, pitch, input mode, pyramid
 // depth, tracking window, hypothesis count, border mode).  Smoothing radius and method, horizon lock, the drone filters'
 // settings, corner count and thresholds are per stream: they live in each frame's argument block or in the stream's state.
+// (border pad on YUV surfaces: whether it acts - a switch that cannot act, with border_size 0 or behind crop_n_zoom, shapes no
+// launch - and the colour its launches fill with: ONE pad launch serves the frames of all members, pad_launch)
+static bool same_yuv_pad(const vs_stab* a, const vs_stab* b) {
+    const bool on = yuv_pad_on(a);
+    if (on != yuv_pad_on(b)) return false;
+    if (!on) return true;
+    const vs_yuv_fill x = yuv_pad_fill(a), y = yuv_pad_fill(b);
+    return x.y == y.y && x.u == y.u && x.v == y.v;
+}
 bool same_launch_shape(const vs_stab* a, const vs_stab* b) {
     const vs_params_c &p = a->p, &q = b->p;
     return a->w == b->w && a->h == b->h && a->fmt == b->fmt && a->src_pitch == b->src_pitch && a->zero_copy == b->zero_copy &&
-           a->in == b->in && a->out == b->out && a->yuv_cz == b->yuv_cz &&
+           a->in == b->in && a->out == b->out && a->yuv_cz == b->yuv_cz && same_yuv_pad(a, b) &&
            a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
            p.lk_win_size == q.lk_win_size && p.ransac_max_iters == q.ransac_max_iters && p.border_size == q.border_size &&
            p.crop_n_zoom == q.crop_n_zoom && (p.border_size <= 0 || p.border_type == q.border_type);
@@ -147,7 +156,8 @@ int group_allocate(vs_batch* g) {
     const size_t o_minv[2] = {take((size_t)cap * 96), take((size_t)cap * 96)};
     int tow, toh;
     out_size(s0, s0->w, s0->h, &tow, &toh);
-    g->tab_ints = s0->pf->three_planes() ? planar_tab_ints(s0->w, s0->h, s0->pf->sx, s0->pf->sy) : s0->pf->luma_uv() ? nv12_tab_ints(s0->w, s0->h) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
+    // (a YUV stream: tow x toh is the frame's size, or with border pad the padded one, which its warps run at)
+    g->tab_ints = s0->pf->three_planes() ? planar_tab_ints(tow, toh, s0->pf->sx, s0->pf->sy) : s0->pf->luma_uv() ? nv12_tab_ints(tow, toh) : (int)warp_tabs_ints(std::max(s0->w, tow), std::max(s0->h, toh), 1);
     size_t o_tabs[2];
     for (auto& o : o_tabs) o = take((size_t)g->tab_ints * cap * sizeof(int32_t));
     VS_OBJ_HIP(g, hipMalloc((void**)&g->d_all, off));
@@ -188,6 +198,8 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
     const vs_stab* s0 = g->ref;
     const BorderPlan bp = border_plan(s0);
     const bool cz = yuv_cz_on(s0);      // a YUV stream with crop-and-zoom: bp.crop, the scratch surfaces in their own layout
+    const bool yp = yuv_pad_on(s0);     // a YUV stream with border pad: bp.pad, the padded scratch surfaces in their own layout
+    const int wb = yp ? VS_BORDER_REPLICATE : VS_BORDER_BLACK;      // (the edge of a padded plane is its border)
     int rc = VS_OK;
     // (launch by launch: the pads of a launch's frames are queued right in front of it, their crops right behind it)
     for (int i0 = 0; i0 < R.n && rc == VS_OK; i0 += WARP_BATCH_MAX) {
@@ -198,9 +210,11 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
             const WarpEnds e = warp_ends(R.owner[i0 + i], R.srcs[i0 + i], R.dsts[i0 + i], R.pad_idx[i0 + i], bp);
             srcs[i] = e.src; dsts[i] = e.dst;
             // pad: the frames get their border first and the padded frames are warped into the (larger) results
-            if (bp.pad && what != VS_WARP_TABLES_ONLY && rc == VS_OK)
+            if (bp.pad && !yp && what != VS_WARP_TABLES_ONLY && rc == VS_OK)
                 rc = launch_make_border(R.srcs[i0 + i], s0->src_pitch, s0->w, s0->h, s0->cn, const_cast<uint8_t*>(e.src), bp.prow, bp.b, s0->p.border_type, st);
         }
+        // border pad on YUV surfaces: ONE launch in front of the warps pads all the planes of their frames
+        if (yp && what != VS_WARP_TABLES_ONLY && rc == VS_OK) rc = pad_launch(s0, &R.srcs[i0], const_cast<uint8_t* const*>(srcs), m, st);
         if (rc != VS_OK) break;
         const WarpMaps maps{g->d_MinvB[R.set] + 12 * i0, 12, false};
         const WarpTabs tabs{WarpTabs::CALLER, g->d_tabs[R.set] + (size_t)i0 * g->tab_ints, g->tab_ints, what};
@@ -208,12 +222,13 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
             // interleaved chroma plane: half size, two channels, the map with the halved translation (Minv + 6)
             const uint8_t* us[WARP_BATCH_MAX];
             uint8_t* ud[WARP_BATCH_MAX];
-            for (int i = 0; i < m; i++) { us[i] = srcs[i] + src_uv(s0); ud[i] = dsts[i] + (cz ? cz_uv(s0) : dst_uv(s0, dsts[i], R.stride)); }
-            rc = launch_warp_nv12(srcs, dsts, us, ud, m, s0->src_pitch, cz ? s0->cz_pitch : R.stride, s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st, s0->pf->sample_bytes);
+            for (int i = 0; i < m; i++) { us[i] = srcs[i] + (yp ? pad_uv(s0) : src_uv(s0)); ud[i] = dsts[i] + (cz ? cz_uv(s0) : dst_uv(s0, dsts[i], R.stride)); }
+            rc = launch_warp_nv12(srcs, dsts, us, ud, m, yp ? s0->pad_pitch : s0->src_pitch, cz ? s0->cz_pitch : R.stride, bp.pw, bp.ph, maps, wb, tabs, st,
+                                  s0->pf->sample_bytes);
         } else if (s0->pf->three_planes()) {
             // I420, I010, I012: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
-            rc = launch_warp_i420(srcs, dsts, m, src_i420(s0), cz ? cz_i420(s0) : dst_i420(s0, dsts[0], R.stride), s0->w, s0->h, maps, VS_BORDER_BLACK, tabs, st,
-                                  s0->pf->sample_bytes, s0->pf->sx, s0->pf->sy);
+            rc = launch_warp_i420(srcs, dsts, m, yp ? pad_i420(s0) : src_i420(s0), cz ? cz_i420(s0) : dst_i420(s0, dsts[0], R.stride), bp.pw, bp.ph, maps, wb, tabs,
+                                  st, s0->pf->sample_bytes, s0->pf->sx, s0->pf->sy);
         }
         if (s0->pf->kind != PIX_INTERLEAVED) {
             // crop-and-zoom on YUV surfaces: ONE launch behind the warps resizes the crops of all their planes into the results
@@ -319,11 +334,14 @@ int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const
                 int32_t* T = g->d_tabs[set] + (size_t)j * g->tab_ints;
                 jobs[0] = WarpTabJob{T, e.src, e.dst, bp.pw, bp.ph};
                 const bool cz = yuv_cz_on(s);        // (the warp then fills a scratch surface, in the scratch layout)
+                const bool yp = yuv_pad_on(s);       // (the warp then reads a padded scratch surface, in the scratch layout, at bp.pw x bp.ph)
                 if (s->pf->luma_uv())
-                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_uv(s), e.dst + (cz ? cz_uv(s) : dst_uv(s, e.dst, b.out_stride)), s->w / 2, s->h / 2};
+                    jobs[1] = WarpTabJob{T + tab_layout(bp.pw, bp.ph).stride, e.src + (yp ? pad_uv(s) : src_uv(s)),
+                                         e.dst + (cz ? cz_uv(s) : dst_uv(s, e.dst, b.out_stride)), bp.pw / 2, bp.ph / 2};
                 else if (s->pf->three_planes())      // ONE chroma table, in pixels, naming the U planes: a V tile adds the launch's V - U
-                    jobs[1] = WarpTabJob{T + tab_layout(s->w, s->h).stride, e.src + src_i420(s).u, e.dst + (cz ? cz_i420(s) : dst_i420(s, e.dst, b.out_stride)).u,
-                                         s->w >> s->pf->sx, s->h >> s->pf->sy};      // (sized for the format's chroma planes: 4:2:0 halves both)
+                    jobs[1] = WarpTabJob{T + tab_layout(bp.pw, bp.ph).stride, e.src + (yp ? pad_i420(s) : src_i420(s)).u,
+                                         e.dst + (cz ? cz_i420(s) : dst_i420(s, e.dst, b.out_stride)).u,
+                                         bp.pw >> s->pf->sx, bp.ph >> s->pf->sy};      // (sized for the format's chroma planes: 4:2:0 halves both)
             }
             npad++;
             P.pend_stride = b.out_stride;
@@ -722,6 +740,12 @@ int vs_batch_set_i420_layout(vs_batch* g, size_t in_u_off, size_t in_v_off, size
 int vs_batch_set_yuv_crop_zoom(vs_batch* g, int enable) {
     if (!g) return VS_ERR_INVALID_ARG;
     for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_yuv_crop_zoom(s, enable); if (rc != VS_OK) { g->err = s->err; return rc; } }
+    return VS_OK;
+}
+
+int vs_batch_set_yuv_border_pad(vs_batch* g, int enable, const vs_yuv_fill* fill) {
+    if (!g) return VS_ERR_INVALID_ARG;
+    for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_yuv_border_pad(s, enable, fill); if (rc != VS_OK) { g->err = s->err; return rc; } }
     return VS_OK;
 }
 

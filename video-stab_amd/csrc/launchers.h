@@ -111,6 +111,13 @@ int launch_cvt_yuv_to_yuv(const PixFmt& sf, const void* const* src, const I420La
 constexpr int CZ_MAX_JOBS = 96;
 int launch_cropzoom(const vs_scale_job* jobs, int n, int sample_bytes, hipStream_t st);
 
+// ---- k_yuvpad.hip: the pad of border pad on YUV surfaces (vs_op_pad_jobs; a stream with vs_stab_set_yuv_border_pad)
+// n <= YP_MAX_JOBS planes (sw x sh samples) padded by bx columns and by rows on every side in ONE launch: 32 surfaces of up to three
+// planes; cn 1 and 2 may be mixed, the sample size is the launch's.  Checks every job on the host first (a text in vs_last_error
+// that names the job).
+constexpr int YP_MAX_JOBS = 96;
+int launch_yuvpad(const vs_pad_job* jobs, int n, int sample_bytes, hipStream_t st);
+
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,
                      float* t_out = nullptr);

@@ -127,6 +127,13 @@ struct vs_stab {
     bool yuv_cz = false;
     size_t cz_pitch = 0;
     int cz_own = 0;
+    // border pad on a YUV stream (vs_stab_set_yuv_border_pad): one k_yuvpad launch pads the planes of the frames into scratch
+    // surfaces - d_padB once more, the format's packed default layout of the padded size at pitch pad_pitch, one per frame of a
+    // batch and one more (pad_own) for the per-frame path - which the warps read under BORDER_REPLICATE
+    bool yuv_pad = false, pad_fill_given = false;
+    vs_yuv_fill pad_fill = {0, 0, 0, 0};        // the caller's; not given: the format's video black
+    size_t pad_pitch = 0;
+    int pad_own = 0;
     uint8_t* d_out = nullptr;
     size_t out_bytes = 0;
     // host pipeline (vs_stab_set_host_pipeline): the result of a call stays in d_hold[] and travels to the host during the
@@ -256,6 +263,14 @@ inline BorderPlan border_plan(const vs_stab* s) {
 // only warped, as for BGR8).  Off, a YUV stream with a border never gets as far as its first allocation (pixfmt.h, check_input).
 inline bool yuv_cz_on(const vs_stab* s) { return s->yuv_cz && s->pf->kind != PIX_INTERLEAVED && border_plan(s).crop; }
 
+// Border pad on a YUV stream: the mode is on and the parameters ask for a pad of cv::copyMakeBorder's (not the fade).  Off, a YUV
+// stream with a border never gets as far as its first allocation (pixfmt.h, check_input).
+inline bool yuv_pad_wanted(const vs_stab* s) { return s->yuv_pad && !s->p.crop_n_zoom && s->p.border_size > 0 && s->p.border_type <= VS_BORDER_WRAP; }
+inline bool yuv_pad_on(const vs_stab* s) { return yuv_pad_wanted(s) && s->pf->kind != PIX_INTERLEAVED; }
+// The rows of luma the layout of a result is counted from: the padded height where the result is padded
+inline int res_h(const vs_stab* s) { return yuv_pad_on(s) ? s->h + 2 * s->p.border_size : s->h; }
+inline vs_yuv_fill yuv_pad_fill(const vs_stab* s) { return s->pad_fill_given ? s->pad_fill : yuv_video_black(*s->pf); }
+
 inline int build_pyramid(vs_stab* s, int k, hipStream_t st) {
     Pyramid& P = s->pyr[k];
     for (int l = 1; l <= s->levels; l++)
@@ -274,7 +289,7 @@ inline void fill_lk_levels(const vs_stab* s, int pv, int c, LKLevel* L) {
 // NV12 / P010: where the interleaved UV plane of a queued frame / of an output surface starts
 inline size_t src_uv(const vs_stab* s) { return (s->zero_copy && s->in.uv_off) ? s->in.uv_off : (size_t)s->h * s->src_pitch; }
 inline size_t dst_uv(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
-    return (d_out != s->d_out && s->out.uv_off) ? s->out.uv_off : (size_t)s->h * out_stride;   // s->d_out: staging of the host entry points
+    return (d_out != s->d_out && s->out.uv_off) ? s->out.uv_off : (size_t)res_h(s) * out_stride;   // s->d_out: staging of the host entry points
 }
 
 // The three-plane formats (I420 ... I412): Y, then U and V planes of (w >> sx) x (h >> sy) samples with a pitch of their own;
@@ -286,7 +301,7 @@ inline I420Layout fmt_i420_layout(const PixFmt& f, size_t pitch, int h, const Ch
 // the packed default layout; the caller's layout (vs_stab_set_i420_layout) applies to zero-copy input and to device outputs.
 inline I420Layout src_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s->src_pitch, s->h, s->zero_copy ? s->in : ChromaLayout()); }
 inline I420Layout dst_i420(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
-    return fmt_i420_layout(*s->pf, out_stride, s->h, d_out != s->d_out ? s->out : ChromaLayout());
+    return fmt_i420_layout(*s->pf, out_stride, res_h(s), d_out != s->d_out ? s->out : ChromaLayout());
 }
 
 // The scratch surfaces of crop-and-zoom on a YUV stream: where the chroma of one lies, and surface `idx`
@@ -296,6 +311,13 @@ inline uint8_t* cz_scratch(const vs_stab* s, int idx) { return s->d_padB + (size
 // The zoom of n warped scratch surfaces into their results (device surfaces in the caller's output layout, or the staging of the
 // host entry points): ONE k_cropzoom launch over all their planes (stabilizer.cpp)
 int cz_launch(const vs_stab* s, const uint8_t* const* scratch, uint8_t* const* outs, int n, size_t out_stride, hipStream_t st);
+
+// The scratch surfaces of border pad on a YUV stream: where the chroma of one lies, and surface `idx`
+inline size_t pad_uv(const vs_stab* s) { return (size_t)res_h(s) * s->pad_pitch; }
+inline I420Layout pad_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s->pad_pitch, res_h(s)); }
+inline uint8_t* pad_scratch(const vs_stab* s, int idx) { return s->d_padB + (size_t)idx * s->pad_frame_bytes; }
+// The pad of n frames (in the stream's input layout) into their scratch surfaces: ONE k_yuvpad launch over all their planes (stabilizer.cpp)
+int pad_launch(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, hipStream_t st);
 
 // A ring slot goes back to the free list behind the work on `st` that reads it.  A slot whose event cannot be recorded stays out
 // of the ring: its next writer would have nothing to wait for.

@@ -75,6 +75,7 @@ void free_all(vs_stab* s) {
     if (s->d_padB) (void)hipFree(s->d_padB);
     s->d_padB = nullptr;
     s->cz_pitch = 0;
+    s->pad_pitch = 0;
     if (s->own) {                       // the private schedule goes with the buffers it was sized for
         group_delete(s->own);
         s->own = nullptr; s->group = nullptr;
@@ -109,6 +110,18 @@ int cz_allocate(vs_stab* s) {
     s->pad_frame_bytes = s->cz_pitch * (size_t)s->rows_total;
     s->cz_own = s->batch_active ? s->batch : 0;
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * (size_t)(s->cz_own + 1)));
+    return VS_OK;
+}
+
+// The scratch surfaces of border pad on a YUV stream (only with the mode on): the packed default layout of the PADDED size at a
+// pitch of whole 256-byte lines (16-byte stores for the pad, aligned loads for the warps); one per frame of a batch, and one for
+// the per-frame path.
+int pad_allocate(vs_stab* s) {
+    const BorderPlan bp = border_plan(s);
+    s->pad_pitch = (bp.prow + 255) & ~(size_t)255;
+    s->pad_frame_bytes = s->pad_pitch * (size_t)s->pf->rows(bp.ph);
+    s->pad_own = s->batch_active ? s->batch : 0;
+    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * (size_t)(s->pad_own + 1)));
     return VS_OK;
 }
 
@@ -236,6 +249,8 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
     if (yuv_cz_on(s)) {
         VS_OBJ_TRY(s, cz_allocate(s));
+    } else if (yuv_pad_on(s)) {
+        VS_OBJ_TRY(s, pad_allocate(s));
     } else if (s->batch_active && s->p.border_size > 0) {
         s->pad_frame_bytes = (s->tmp_bytes + 255) & ~(size_t)255;
         VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * B));
@@ -252,18 +267,28 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
 
 // The three planes of a planar frame (I420 / I010 / I012; 4:2:2, 4:4:4) from one layout to another: rows of w samples, and chroma
 // rows of w >> sx samples, h >> sy of them.
-int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src, const I420Layout& sl, hipMemcpyKind kind, hipStream_t st) {
-    const size_t cw = s->pf->chroma_row_bytes(s->w);
-    const int ch = s->h >> s->pf->sy;
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, s->row_bytes, s->h, kind, st));
+// (w, h: the size of the surface, where it is not the frame's - the padded result of border pad on a YUV stream)
+int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src, const I420Layout& sl, hipMemcpyKind kind, hipStream_t st, int w = 0,
+              int h = 0) {
+    if (!w) { w = s->w; h = s->h; }
+    const size_t cw = s->pf->chroma_row_bytes(w);
+    const int ch = h >> s->pf->sy;
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, (size_t)w * s->cn, h, kind, st));
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.u, dl.cpitch, src + sl.u, sl.cpitch, cw, ch, kind, st));
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.v, dl.cpitch, src + sl.v, sl.cpitch, cw, ch, kind, st));
     return VS_OK;
 }
 
 // The result of a host call from its staging buffer (rows of `orow` bytes, `orows` of them; I420: the packed layout at that pitch)
-// into the caller's frame.
-int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st) {
+// into the caller's frame.  rw x rh: the size of the frame delivered (vs_stab_last_out_dims), which border pad on a YUV stream goes
+// by: a padded result, or the unpadded last frame of a flush with the default offsets of ITS size.
+int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st, int rw, int rh) {
+    if (yuv_pad_on(s)) {
+        if (s->pf->three_planes())
+            return copy_i420(s, out, fmt_i420_layout(*s->pf, out_stride, rh), d_src, fmt_i420_layout(*s->pf, orow, rh), hipMemcpyDeviceToHost, st, rw, rh);
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, (size_t)rw * s->cn, s->pf->rows(rh), hipMemcpyDeviceToHost, st));
+        return VS_OK;
+    }
     if (s->pf->three_planes())
         return copy_i420(s, out, fmt_i420_layout(*s->pf, out_stride, s->h), d_src, fmt_i420_layout(*s->pf, orow, s->h), hipMemcpyDeviceToHost, st);
     VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, st));
@@ -460,15 +485,18 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
     if (idx >= s->n_transforms) {
         // Stabilizer.cpp:774-780: no transform exists for this frame (last frame of a
         // flush): the queued frame is returned as is, at its own size (no border pad).
-        if (ow != s->w || oh != s->h)
+        // (border pad on a YUV stream: the frame alone is written, with the default offsets of its own size)
+        const bool ypad = yuv_pad_on(s);
+        if (!ypad && (ow != s->w || oh != s->h))
             VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
         if (s->pf->three_planes())
-            VS_OBJ_TRY(s, copy_i420(s, d_out, dst_i420(s, d_out, out_stride), frame, src_i420(s), hipMemcpyDeviceToDevice, st));
+            VS_OBJ_TRY(s, copy_i420(s, d_out, ypad ? fmt_i420_layout(*s->pf, out_stride, s->h) : dst_i420(s, d_out, out_stride), frame, src_i420(s),
+                                    hipMemcpyDeviceToDevice, st));
         else
             VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
         if (s->pf->luma_uv())
-            VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out + dst_uv(s, d_out, out_stride), out_stride, frame + src_uv(s), s->src_pitch, s->row_bytes,
-                                      s->h / 2, hipMemcpyDeviceToDevice, st));
+            VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out + (ypad ? (size_t)s->h * out_stride : dst_uv(s, d_out, out_stride)), out_stride, frame + src_uv(s),
+                                      s->src_pitch, s->row_bytes, s->h / 2, hipMemcpyDeviceToDevice, st));
         s->last_out_w = s->w; s->last_out_h = s->h;
     } else if (canvas_on(s)) {                                                        // :1130-1134
         // the canvas replaces the warped frame, so the warp (and a fade history behind it) cannot be observed and is not run
@@ -480,19 +508,33 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // crop-and-zoom: the warp goes into the stream's scratch surface, whose crops one launch resizes into d_out
         const bool cz = yuv_cz_on(s);
         uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
-        const uint8_t* uv = frame + src_uv(s);
+        // border pad: one launch pads both planes into the stream's scratch surface, which is warped at the padded size, taps
+        // outside it taking its edge (the border)
+        const bool pad = yuv_pad_on(s);
+        uint8_t* psrc = pad ? pad_scratch(s, s->pad_own) : nullptr;
+        if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
+        const uint8_t* wsrc = pad ? psrc : frame;
+        const uint8_t* uv = pad ? psrc + pad_uv(s) : frame + src_uv(s);
         uint8_t* out_uv = wdst + (cz ? cz_uv(s) : dst_uv(s, d_out, out_stride));
         // (a P010 surface goes through the one-launch kernel even on its own: its tables are built in the stream's scratch)
-        rc = launch_warp_nv12(&frame, &wdst, &uv, &out_uv, 1, s->src_pitch, cz ? s->cz_pitch : out_stride, s->w, s->h, WarpMaps{s->d_Minv, 12, false},
-                              VS_BORDER_BLACK, s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, s->pf->sample_bytes);
+        if (rc == VS_OK)
+            rc = launch_warp_nv12(&wsrc, &wdst, &uv, &out_uv, 1, pad ? s->pad_pitch : s->src_pitch, cz ? s->cz_pitch : out_stride, bp.pw, bp.ph,
+                                  WarpMaps{s->d_Minv, 12, false}, pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK,
+                                  s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, s->pf->sample_bytes);
         if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
     } else if (s->pf->three_planes()) {
         // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
         StageScope t(s, VS_STAGE_WARP, st);
         const bool cz = yuv_cz_on(s);
         uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
-        rc = launch_warp_i420(&frame, &wdst, 1, src_i420(s), cz ? cz_i420(s) : dst_i420(s, d_out, out_stride), s->w, s->h, WarpMaps{s->d_Minv, 12, false},
-                              VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, st, s->pf->sample_bytes, s->pf->sx, s->pf->sy);
+        const bool pad = yuv_pad_on(s);      // (as above: pad into the scratch surface, warp that)
+        uint8_t* psrc = pad ? pad_scratch(s, s->pad_own) : nullptr;
+        if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
+        const uint8_t* wsrc = pad ? psrc : frame;
+        if (rc == VS_OK)
+            rc = launch_warp_i420(&wsrc, &wdst, 1, pad ? pad_i420(s) : src_i420(s), cz ? cz_i420(s) : dst_i420(s, d_out, out_stride), bp.pw, bp.ph,
+                                  WarpMaps{s->d_Minv, 12, false}, pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, st,
+                                  s->pf->sample_bytes, s->pf->sx, s->pf->sy);
         if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
@@ -677,11 +719,19 @@ int take_slot(vs_stab* s, int* slot) {
 
 // What every push asks first: the rules of the input side (pixfmt.h), then the stream allocates for its first frame.
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
-    VS_REFUSE(s, check_input(pixfmt(fmt), w, h, stride, s->in, s->out, s->p.border_size, s->yuv_cz && s->p.crop_n_zoom));
+    VS_REFUSE(s, check_input(pixfmt(fmt), w, h, stride, s->in, s->out, s->p.border_size, s->yuv_cz && s->p.crop_n_zoom, yuv_pad_wanted(s)));
+    if (yuv_pad_wanted(s) && s->pad_fill_given && pixfmt(fmt)->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*pixfmt(fmt), s->pad_fill));
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     if (!s->allocated) return allocate(s, w, h, fmt);
     if (w != s->w || h != s->h || fmt != s->fmt) return vs_obj_fail(s, VS_ERR_SIZE_CHANGED, "frame geometry changed; call vs_stab_clean()");
     return VS_OK;
+}
+
+// Border pad on a YUV stream: the pitch of a device surface that receives a result holds a padded row
+Refusal check_padded_out(const vs_stab* s, const char* call, size_t out_stride) {
+    if (!yuv_pad_on(s) || out_stride >= border_plan(s).prow) return Refusal();
+    return refuse(VS_ERR_INVALID_ARG, std::string(call) + ": border pad on " + s->pf->name + ": out_stride must hold a padded row (" +
+                                          std::to_string(border_plan(s).prow) + " bytes)");
 }
 
 void destroy_events(vs_stab* s) {
@@ -708,6 +758,28 @@ int create_events(vs_stab* s) {
 }
 
 }  // namespace
+
+int vsd::pad_launch(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, hipStream_t st) {
+    const PixFmt& f = *s->pf;
+    const int b = s->p.border_size, w = s->w, h = s->h, border = s->p.border_type;
+    const vs_yuv_fill c = yuv_pad_fill(s);
+    vs_pad_job jobs[YP_MAX_JOBS];
+    int nj = 0;
+    auto add = [&](const uint8_t* src, size_t sstride, int pw, int ph, uint8_t* dst, size_t dstride, int bx, int by, int cn, uint16_t f0, uint16_t f1) {
+        jobs[nj++] = vs_pad_job{src, sstride, pw, ph, dst, dstride, bx, by, cn, border, {f0, f1}, 0};
+    };
+    for (int i = 0; i < n; i++) {
+        add(frames[i], s->src_pitch, w, h, scratch[i], s->pad_pitch, b, b, 1, c.y, 0);
+        if (f.luma_uv()) {
+            add(frames[i] + src_uv(s), s->src_pitch, w / 2, h / 2, scratch[i] + pad_uv(s), s->pad_pitch, b >> 1, b >> 1, 2, c.u, c.v);
+            continue;
+        }
+        const I420Layout L = src_i420(s), D = pad_i420(s);
+        add(frames[i] + L.u, L.cpitch, w >> f.sx, h >> f.sy, scratch[i] + D.u, D.cpitch, b >> f.sx, b >> f.sy, 1, c.u, 0);
+        add(frames[i] + L.v, L.cpitch, w >> f.sx, h >> f.sy, scratch[i] + D.v, D.cpitch, b >> f.sx, b >> f.sy, 1, c.v, 0);
+    }
+    return launch_yuvpad(jobs, nj, f.sample_bytes, st);
+}
 
 int vsd::cz_launch(const vs_stab* s, const uint8_t* const* scratch, uint8_t* const* outs, int n, size_t out_stride, hipStream_t st) {
     const PixFmt& f = *s->pf;
@@ -886,6 +958,7 @@ int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride
     int rc = prepare(s, w, h, fmt, stride);
     if (rc != VS_OK) return rc;
     VS_REFUSE(s, check_surface(*s->pf, true, (uintptr_t)d_data | (uintptr_t)d_out, out_stride, s->out.c_pitch));
+    VS_REFUSE(s, check_padded_out(s, "push", out_stride));
     if (s->zero_copy) {
         // the frame is read where it is: it must stay valid and unchanged until its own result has been produced
         // one pitch for all frames in flight (the batched launches take it once): it may change when nothing is queued
@@ -923,6 +996,7 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
     *produced = 0;
     if (!s->allocated || s->q_slot.empty()) return VS_OK;
     VS_REFUSE(s, check_surface(*s->pf, true, (uintptr_t)d_out, out_stride, d_out != s->d_out ? s->out.c_pitch : 0));   // (s->d_out: the staging of vs_stab_flush)
+    VS_REFUSE(s, check_padded_out(s, "flush", out_stride));
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     VS_OBJ_TRY(s, drain_batch(s));
     VS_OBJ_TRY(s, apply_next(s, (uint8_t*)d_out, out_stride, may_defer_flush));
@@ -988,7 +1062,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
             }
         }
         if (!helped) {
-            VS_OBJ_TRY(s, download_result(s, out, out_stride, d_src, orow, orows, s->st_warp));
+            VS_OBJ_TRY(s, download_result(s, out, out_stride, d_src, orow, orows, s->st_warp, held_w, held_h));
         }
     }
     int slot;
@@ -1050,7 +1124,7 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
         const int orows = s->pf->rows(oh);
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));   // (per-frame pipeline: the warp ran on the warp stream)
         if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));     // batch mode: the warps run on `pre` (group_launch_ready)
-        VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st));
+        VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st, s->last_out_w, s->last_out_h));
     }
     // the caller's frame must be consumed and its result delivered before returning
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));
@@ -1069,7 +1143,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
         const int orows = s->pf->rows(s->hold_h);
         VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_warp, s->ev_hold, 0));
         VS_REFUSE(s, check_surface(*s->pf, false, 0, out_stride, 0));
-        VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orows, s->st_warp));
+        VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_hold[s->hold_cur ^ 1], orow, orows, s->st_warp, s->hold_w, s->hold_h));
         VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
         s->hold_valid = false;
         s->last_out_w = s->hold_w; s->last_out_h = s->hold_h;
@@ -1089,7 +1163,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     const int orows = s->pf->rows(oh);
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st_warp));
     if (s->batch_active) VS_OBJ_HIP(s, hipStreamSynchronize(s->st_pre));         // batch mode: the warps run on `pre`
-    VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st));
+    VS_OBJ_TRY(s, download_result(s, out, out_stride, s->d_out, orow, orows, s->st, s->last_out_w, s->last_out_h));
     VS_OBJ_HIP(s, hipStreamSynchronize(s->st));
     return VS_OK;
 }
@@ -1173,6 +1247,31 @@ int vs_stab_set_yuv_crop_zoom(vs_stab* s, int enable) {
     if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_crop_zoom: the frame queue must be empty");
     s->yuv_cz = enable != 0;
+    return VS_OK;
+}
+
+// Border pad on YUV surfaces (NV12, P010 and the three-plane formats), off by default: with it a stream whose parameters say
+// border_size without crop_n_zoom and a border type of cv::copyMakeBorder pads the planes of a frame into a scratch surface
+// (k_yuvpad.hip) and warps that at the padded size under BORDER_REPLICATE; without it such a stream is refused as ever.
+// fill: the colour VS_BORDER_BLACK writes; NULL: the format's video black.
+int vs_stab_set_yuv_border_pad(vs_stab* s, int enable, const vs_yuv_fill* fill) {
+    if (!s) return VS_ERR_INVALID_ARG;
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_border_pad: the frame queue must be empty");
+    if (fill && fill->reserved != 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_border_pad: fill->reserved must be 0");
+    if (enable && fill && s->allocated && s->pf->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*s->pf, *fill));
+    // (a stream whose parameters ask for a pad was allocated with the mode on - off, its first push was refused - so the scratch
+    // surfaces are there whenever the mode is on)
+    s->yuv_pad = enable != 0;
+    s->pad_fill_given = enable && fill;
+    if (s->pad_fill_given) s->pad_fill = *fill;
+    return VS_OK;
+}
+
+int vs_yuv_video_black(int fmt, vs_yuv_fill* out) {
+    const PixFmt* f = pixfmt(fmt);
+    if (!out || !f || f->kind == PIX_INTERLEAVED) { set_last_error("vs_yuv_video_black: fmt must be a YUV surface format (NV12, P010, I420 ... I412)"); return VS_ERR_INVALID_ARG; }
+    *out = yuv_video_black(*f);
     return VS_OK;
 }
 

@@ -166,6 +166,18 @@ class VsEnhParams(C.Structure):
     ]
 
 
+class VsYuvFill(C.Structure):
+    """struct vs_yuv_fill (include/vs_stab.h): the fill colour of border pad on YUV streams, samples as they lie in memory."""
+    _fields_ = [("y", C.c_uint16), ("u", C.c_uint16), ("v", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+class VsPadJob(C.Structure):
+    """struct vs_pad_job (include/vs_stab.h): one plane pad of vs_op_pad_jobs."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_size_t), ("sw", C.c_int32), ("sh", C.c_int32),
+                ("dst", C.c_void_p), ("dst_stride", C.c_size_t), ("bx", C.c_int32), ("by", C.c_int32),
+                ("cn", C.c_int32), ("border", C.c_int32), ("fill", C.c_uint16 * 2), ("reserved", C.c_int32)]
+
+
 class VsScaleJob(C.Structure):
     """struct vs_scale_job (include/vs_stab.h): one crop-and-scale of vs_op_scale_jobs."""
     _fields_ = [("src", C.c_void_p), ("src_stride", C.c_size_t), ("sw", C.c_int32), ("sh", C.c_int32),
@@ -494,6 +506,11 @@ class VsLib:
             L.vs_stab_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
             L.vs_batch_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
             L.vs_op_resize_jobs.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, vp]
+            # border pad on YUV streams
+            L.vs_stab_set_yuv_border_pad.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
+            L.vs_batch_set_yuv_border_pad.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
+            L.vs_yuv_video_black.argtypes = [C.c_int, C.POINTER(VsYuvFill)]
+            L.vs_op_pad_jobs.argtypes = [C.POINTER(VsPadJob), C.c_int, C.c_int, vp]
             # roll correction and auto zoom/crop on interleaved colour frames (BGR8, RGB8, BGRA8, RGBA8)
             L.vs_roll_correct_rgb_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]
             L.vs_roll_correct_rgb_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t]
@@ -797,6 +814,21 @@ class VsLib:
     def resize_jobs(self, jobs, sample_bytes=1, stream=None):
         """vs_op_resize_jobs (the zoom of crop-and-zoom on YUV surfaces): 1 .. 96 jobs, tuples as for scale_jobs; asynchronous."""
         self.check(self.lib.vs_op_resize_jobs(self._scale_job_array(jobs), len(jobs), sample_bytes, stream))
+
+    def pad_jobs(self, jobs, sample_bytes=1, stream=None):
+        """vs_op_pad_jobs (the pad of border pad on YUV surfaces): 1 .. 96 jobs, tuples (src, src_stride, sw, sh, dst, dst_stride, bx,
+        by, cn, border, (fill0, fill1)) of device addresses; asynchronous."""
+        arr = (VsPadJob * max(1, len(jobs)))()
+        for a, (src, ss, sw, sh, dst, ds, bx, by, cn, border, fill) in zip(arr, jobs):
+            a.src, a.src_stride, a.sw, a.sh, a.dst, a.dst_stride, a.bx, a.by, a.cn, a.border = src, ss, sw, sh, dst, ds, bx, by, cn, border
+            a.fill[0], a.fill[1] = fill
+        self.check(self.lib.vs_op_pad_jobs(arr, len(jobs), sample_bytes, stream))
+
+    def yuv_video_black(self, fmt):
+        """vs_yuv_video_black (no device needed): (y, u, v) of limited-range black, samples as they lie in memory."""
+        c = VsYuvFill()
+        self.check(self.lib.vs_yuv_video_black(fmt, C.byref(c)))
+        return c.y, c.u, c.v
 
     def scale_jobs_plan(self, jobs, sample_bytes=1):
         """vs_op_scale_jobs_plan (no device needed): 1 per job that path 0 sends to the staged kernel."""
@@ -1644,6 +1676,12 @@ class Stabilizer:
         """vs_stab_set_yuv_crop_zoom: crop_n_zoom with a border_size on NV12 / P010 / three-plane streams (off: refused)."""
         self.vs.check(self.lib.vs_stab_set_yuv_crop_zoom(self.h, int(on)), self.h)
 
+    def set_yuv_border_pad(self, on=True, fill=None):
+        """vs_stab_set_yuv_border_pad: border_size without crop_n_zoom on NV12 / P010 / three-plane streams (off: refused).
+        fill: (y, u, v) samples as they lie in memory; None: the format's video black."""
+        c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
+        self.vs.check(self.lib.vs_stab_set_yuv_border_pad(self.h, int(on), c), self.h)
+
     def set_zero_copy(self, on=True):
         self.vs.check(self.lib.vs_stab_set_zero_copy(self.h, int(on)), self.h)
 
@@ -1746,6 +1784,10 @@ class Batch:
 
     def set_yuv_crop_zoom(self, on=True):
         self._check(self.lib.vs_batch_set_yuv_crop_zoom(self.h, int(on)))
+
+    def set_yuv_border_pad(self, on=True, fill=None):
+        c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
+        self._check(self.lib.vs_batch_set_yuv_border_pad(self.h, int(on), c))
 
     def push_dev(self, d_frames, w, h, stride, fmt, d_outs, out_stride):
         """d_frames / d_outs: one device pointer per stream (None: no frame for that stream).  Returns produced[]."""
