@@ -50,7 +50,8 @@ extern "C" {
  *    vs_cvt_colorimetry_guess; conversion between the YUV surface formats: struct vs_yuv_cvt_desc with vs_op_cvt_yuv_to_yuv and
  *    vs_yuv_surface_layout; crop-and-zoom on YUV streams: vs_stab_set_yuv_crop_zoom, vs_batch_set_yuv_crop_zoom and vs_op_resize_jobs;
  *    border pad on YUV streams: struct vs_yuv_fill with vs_stab_set_yuv_border_pad, vs_batch_set_yuv_border_pad and
- *    vs_yuv_video_black, struct vs_pad_job with vs_op_pad_jobs
+ *    vs_yuv_video_black, struct vs_pad_job with vs_op_pad_jobs; the fade border on YUV streams: vs_stab_set_yuv_fade, struct
+ *    vs_fade_job with vs_op_fade_blend_jobs, struct vs_fade_update_job with vs_op_fade_update_jobs
  *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
@@ -90,7 +91,7 @@ typedef enum vs_pixfmt {
  *    are 0, each by itself), rounded once, half to even: (S + 511 + ((S >> 10) & 1)) >> 10.  For ten-bit content that is
  *    what OpenCV's float blend gives; for arbitrary 16-bit content it is the definition (docs/opencv_semantics.md);
  *  - everything else follows NV12: the last frame of a flush comes back unwarped; border pad, crop-and-zoom, fade and the
- *    virtual canvas are refused as for NV12 (crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad).
+ *    virtual canvas are refused as for NV12 (crop-and-zoom, border pad and fade unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad, vs_stab_set_yuv_fade).
  * The two stages around the stabilizer take P010 surfaces too (vs_roll_correct_p010_dev, vs_azc_apply_p010_dev):
  *  - analysis plane: both analyse the 8-bit plane of the luma samples' high bytes (sample >> 8), the plane the stabilizer analyses.
  *    Smoothed and detected angle, line counts, content mask, contours, info8 and the crop rectangle are bit-identical to those of
@@ -125,7 +126,7 @@ typedef enum vs_pixfmt16 {
  *    in float (cv::warpAffine treats channels independently: these are the two channels of the NV12 chroma plane's warp),
  *    INTER_LINEAR, BORDER_CONSTANT 0;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are refused as for NV12 (VS_ERR_UNSUPPORTED; crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad); the
+ *    are refused as for NV12 (VS_ERR_UNSUPPORTED; crop-and-zoom, border pad and fade unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad, vs_stab_set_yuv_fade); the
  *    enhancer and the C++ classes do not take it.
  * The two stages around the stabilizer take I420 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev; layouts as
  * struct vs_i420_layout): every observable is again that of the NV12 call on the same samples, the planes de-interleaved -
@@ -155,7 +156,7 @@ typedef enum vs_pixfmt_planar {
  *    halved in float; INTER_LINEAR, BORDER_CONSTANT 0, the blend of P010 to the letter (S rounded once, half to even).  The warp
  *    does not depend on the bit depth;
  *  - the last frame of a flush comes back unwarped, all three planes; border pad, crop-and-zoom, fade and the virtual canvas
- *    are VS_ERR_UNSUPPORTED (crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad); the enhancer and the C++
+ *    are VS_ERR_UNSUPPORTED (crop-and-zoom, border pad and fade unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad, vs_stab_set_yuv_fade); the enhancer and the C++
  *    classes do not take these formats.
  * The two stages around the stabilizer take I010 / I012 surfaces (vs_roll_correct_i420_dev, vs_azc_apply_i420_dev with fmt
  * VS_FMT_I010 / VS_FMT_I012):
@@ -201,7 +202,7 @@ typedef enum vs_pixfmt_planar16 {
  *    half to even (vs_pixfmt16) - which does not depend on the bit depth.  (For 4:2:2, Mc is not a rotation.)
  *  - the last frame of a flush comes back unwarped, all three planes;
  *  - border pad, crop-and-zoom, fade and the virtual canvas are VS_ERR_UNSUPPORTED, with a text that names the format, exactly
- *    where I420 is refused (crop-and-zoom and border pad unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad).  The C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16, P210, NV24),
+ *    where I420 is refused (crop-and-zoom, border pad and fade unless the stream opts in: vs_stab_set_yuv_crop_zoom, vs_stab_set_yuv_border_pad, vs_stab_set_yuv_fade).  The C++ classes do not take these formats.  Semi-planar 4:2:2 / 4:4:4 (NV16, P210, NV24),
  *    yuv4xxp16le and big-endian samples are not built.
  * The two stages around the stabilizer take these formats through the entry points of the 4:2:0 ones (vs_roll_correct_i420_dev,
  * vs_roll_correct_i420_dev_n, vs_azc_apply_i420_dev, vs_azc_apply_i420_dev_n; layouts as struct vs_i420_layout, whose default chroma
@@ -522,7 +523,7 @@ int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t
  *      depth or on where the value sits in the word (P010: high bits, I010: low bits).
  * w - 2b <= 0 or h - 2b <= 0: the frame is only warped, as for BGR8.  The last frame of a flush comes back unwarped and uncropped.
  * Analysis, trajectory and warp matrix do not depend on border_size or crop_n_zoom: the debug values are those of the same stream
- * with border_size = 0, bit for bit.  Border pad (crop_n_zoom = 0; a switch of its own, vs_stab_set_yuv_border_pad), the fade border and the virtual canvas stay refused on YUV
+ * with border_size = 0, bit for bit.  Border pad (crop_n_zoom = 0; a switch of its own, vs_stab_set_yuv_border_pad), the fade border (likewise: vs_stab_set_yuv_fade) and the virtual canvas stay refused on YUV
  * streams, with their texts; GRAY8 is not touched by the mode.  Zero-copy input, the decoder layouts (vs_stab_set_nv12_layout,
  * vs_stab_set_i420_layout) and the host entry points work as without the mode; in batch mode the warps of a launch (<= 32
  * surfaces) fill scratch surfaces and ONE launch behind them resizes all their planes. */
@@ -555,13 +556,45 @@ int vs_stab_set_yuv_crop_zoom(vs_stab* s, int enable);
  * VS_ERR_INVALID_ARG.  The last frame of a flush has no transform: it comes back unpadded, w x h, with the default offsets of
  * that size at out_stride (vs_stab_last_out_dims reports (w, h)); nothing else of the output is written.  Analysis, trajectory,
  * matrices and debug records do not depend on border_size: they are those of the stream with border_size = 0, bit for bit.
- * The fade border and the virtual canvas stay refused on YUV streams, with their texts; GRAY8 and the interleaved formats are
+ * The fade border (unless the stream opts in: vs_stab_set_yuv_fade) and the virtual canvas stay refused on YUV streams, with their texts; GRAY8 and the interleaved formats are
  * not touched.  Zero-copy input, the decoder layouts and the host entry points work as without the mode; in batch mode ONE launch
  * in front of each warp launch (<= 32 surfaces) pads all their planes. */
 typedef struct vs_yuv_fill { uint16_t y, u, v, reserved; } vs_yuv_fill;   /* samples as they lie in memory */
 int vs_stab_set_yuv_border_pad(vs_stab* s, int enable, const vs_yuv_fill* fill);
 /* Limited-range video black of a YUV format, as above.  Host only; VS_ERR_INVALID_ARG for a format without chroma planes. */
 int vs_yuv_video_black(int fmt, vs_yuv_fill* out);
+/* The fade border on YUV streams - the reference's third border mode, borderType "fade" (Stabilizer.cpp:914-978, 1069-1106: the
+ * padded frame is blended with a history of earlier results before the warp, and the history takes a tenth of the result after
+ * it), on NV12, P010 and the three-plane formats, at 8, 10 and 12 bits.  Off by default: such a stream is VS_ERR_UNSUPPORTED as
+ * ever, with the same text, and allocates and launches nothing.  The reference has no YUV path, so what the mode does is a
+ * DEFINITION of this library, which a caller opts into with this call (enable != 0; the frame queue must be empty).  It is
+ * independent of vs_stab_set_yuv_crop_zoom and vs_stab_set_yuv_border_pad, which go on governing crop_n_zoom and the five modes of
+ * cv::copyMakeBorder.  With the mode on, crop_n_zoom == 0, border_size = b > 0, border_type == VS_BORDER_FADE and the virtual
+ * canvas off, every plane of a surface is processed on its own, the interleaved UV plane in (U, V) pairs:
+ *  (a) pad: as border pad on YUV with VS_BORDER_BLACK.  Y gets b columns and rows on every side, chroma (b >> sx) columns and
+ *      (b >> sy) rows; the border holds the plane's fill sample.  b must be a multiple of 2^sx and 2^sy: an odd b on a subsampled
+ *      format is VS_ERR_INVALID_ARG with a text that names the format.
+ *  (b) history: one surface of the padded size per plane, which the library owns, in a layout of its own.  The first padded frame
+ *      IS the history, and the count is then 0 - also after any change of geometry or format, and after any accepted call of this
+ *      setter.  The history outlives vs_stab_clean (borderHistory_ outlives Stabilizer::clean()).
+ *  (c) blend: alpha = fade_alpha * (count / fade_duration) in float while count < fade_duration (the count then goes up by one),
+ *      fade_alpha afterwards; beta = 1.0f - alpha: exactly the BGR8 stream's.  Every sample of the padded plane (the reference's
+ *      mask is all 255): v = fmaf(hist, alpha, fl32(frame * beta)), rounded half to even, saturated to 0 .. 255 (8-bit samples) or
+ *      0 .. 65535 (16-bit) - cv::addWeighted.  Nothing depends on the bit depth or on where the value sits in the word.  (Weights
+ *      outside [0, 1] - a fade_alpha outside it - are VS_ERR_INVALID_ARG at the first blend.)
+ *  (d) warp: the blended padded surface is warped exactly as border pad on YUV warps its padded surface: the same matrices,
+ *      BORDER_REPLICATE, a result of (w + 2b) x (h + 2b).  Output layout rules, out_stride, the output chroma-pitch refusals and
+ *      vs_stab_last_out_dims are those of border pad.
+ *  (e) update: history = (T)((1.0f - 0.1f) * history + 0.1f * result): two float products, one float sum, a truncation, for
+ *      every sample of every plane (T: uint8_t or uint16_t).
+ * fill: as for vs_stab_set_yuv_border_pad; NULL = vs_yuv_video_black of the format; a sample above 255 on an 8-bit format is
+ * VS_ERR_INVALID_ARG, here when the format is known, else at the next push.
+ * The last frame of a flush has no transform: it comes back unpadded, as with border pad, and leaves history and count alone.
+ * Analysis, trajectory, matrices and debug records are those of the stream with border_size = 0, bit for bit.  The fade keeps the
+ * per-frame path, as for BGR8: a stream with vs_stab_set_batch(n) runs per frame and gives the same bytes; vs_batch_create goes on
+ * refusing the fade.  The virtual canvas stays refused on YUV streams.  Zero-copy input, the decoder layouts and the host entry
+ * points work as with border pad.  Three launches per frame: blend (pad and blend fused), warp, update. */
+int vs_stab_set_yuv_fade(vs_stab* s, int enable, const vs_yuv_fill* fill);
 
 /* ---- several streams of one device scheduled together (BASELINE configs[4]: 64 streams = 8 per GPU) ----------------------
  * The reference runs one Stabilizer per stream, each with its own cv::cuda::Stream objects (src/Stabilizer.cpp:102-104); here a
@@ -994,6 +1027,26 @@ typedef struct vs_pad_job { const void* src; size_t src_stride; int32_t sw, sh; 
                             void* dst; size_t dst_stride; int32_t bx, by;            /* dst is (sw + 2bx) x (sh + 2by) */
                             int32_t cn, border; uint16_t fill[2]; int32_t reserved; } vs_pad_job;
 int vs_op_pad_jobs(const vs_pad_job* jobs, int n, int sample_bytes, void* stream);
+/* The two launches of the fade border on YUV surfaces as operators (what a stream with vs_stab_set_yuv_fade queues around its
+ * warp): n = 1 .. 32 jobs of one sample size (1 or 2 bytes) in ONE launch, cn 1 and 2 mixed; a job is one plane.
+ * vs_op_fade_blend_jobs - pad and blend fused: dst, (sw + 2 bx) x (sh + 2 by) samples of cn channels, = addWeighted(hist, alpha,
+ * padded, beta) where padded is src (sw x sh) with a border of fill[channel]: v = fmaf(hist, alpha, fl32(padded * beta)), rounded
+ * half to even, saturated to the sample.  hist has the padded size; src, hist and dst have their own pitches.  One alpha and one
+ * beta serve the launch, both in [0, 1].
+ * vs_op_fade_update_jobs: hist = (T)((1.0f - 0.1f) * hist + 0.1f * res), in place, over w x h samples of cn channels.
+ * Sizes at least 1, bx, by >= 0, padded sizes at most 32767, strides in bytes, at least a row and below 2^32, reserved = 0; 16-bit
+ * pointers and strides even; a fill above 255 with 8-bit samples is refused; dst must not overlap src or hist, nor hist res.  No
+ * byte outside the source, history and result planes is read, none outside the destination (history) plane written.  Refusals
+ * (VS_ERR_INVALID_ARG) are decided before any device call, with a text in vs_last_error that names the call and the job.
+ * Asynchronous on `stream`. */
+typedef struct vs_fade_job { const void* src; size_t src_stride; int32_t sw, sh;      /* samples of cn channels */
+                             const void* hist; size_t hist_stride;                    /* (sw + 2bx) x (sh + 2by), as dst */
+                             void* dst; size_t dst_stride; int32_t bx, by;
+                             uint16_t fill[2]; int32_t cn; int64_t reserved; } vs_fade_job;
+typedef struct vs_fade_update_job { void* hist; size_t hist_stride; const void* res; size_t res_stride;
+                                    int32_t w, h, cn, reserved; } vs_fade_update_job;
+int vs_op_fade_blend_jobs(const vs_fade_job* jobs, int n, int sample_bytes, float alpha, float beta, void* stream);
+int vs_op_fade_update_jobs(const vs_fade_update_job* jobs, int n, int sample_bytes, void* stream);
 /* Diagnostics of the asynchronous path: out9 = {frames through the worker threads; seconds, summed over the threads: without a
  * frame to work on, waiting for the masks of the batches on their way (one worker at a time does), in the contour logic, queueing
  * launches and publishing; batches; seconds, summed over the batches: from a batch's launches to the arrival of its masks on the

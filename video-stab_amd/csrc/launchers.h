@@ -118,6 +118,14 @@ int launch_cropzoom(const vs_scale_job* jobs, int n, int sample_bytes, hipStream
 constexpr int YP_MAX_JOBS = 96;
 int launch_yuvpad(const vs_pad_job* jobs, int n, int sample_bytes, hipStream_t st);
 
+// ---- k_yuvfade.hip: the fade border on YUV surfaces (vs_op_fade_blend_jobs, vs_op_fade_update_jobs; a stream with vs_stab_set_yuv_fade)
+// blend: n <= YF_MAX_JOBS planes padded with their fill and blended with their history in ONE launch (dst = addWeighted(hist,
+// alpha, padded src, beta)); update: hist = (T)((1 - 0.1f) * hist + 0.1f * res) over n planes in ONE launch.  cn 1 and 2 may be
+// mixed, the sample size is the launch's.  Both check every job on the host first (a text in vs_last_error that names the job).
+constexpr int YF_MAX_JOBS = 32;
+int launch_yuvfade_blend(const vs_fade_job* jobs, int n, int sample_bytes, float alpha, float beta, hipStream_t st);
+int launch_yuvfade_update(const vs_fade_update_job* jobs, int n, int sample_bytes, hipStream_t st);
+
 // ---- k_traj.hip: the map of output `idx` (t_out: its correction, for the virtual canvas), the fade border, a test delay
 int launch_traj_emit(TrajState* s, const TrajParams& p, int idx, float* M_out, double* Minv_out, vs_debug_frame* dbg, hipStream_t st,
                      float* t_out = nullptr);

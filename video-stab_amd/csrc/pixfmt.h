@@ -110,8 +110,10 @@ inline Refusal check_chroma_pitch(const PixFmt& f, int w, size_t in_c_pitch, siz
 // yuv_border_pad: the stream has border pad on YUV surfaces turned on (vs_stab_set_yuv_border_pad) AND its parameters ask for a
 // pad (no crop_n_zoom, a border type of cv::copyMakeBorder - not the fade); 0 (the default) likewise.  The result then has
 // (w + 2 border_size) x (h + 2 border_size) pixels, and an explicit output chroma pitch must hold a chroma row of that.
+// yuv_fade: the stream has the fade border on YUV surfaces turned on (vs_stab_set_yuv_fade) AND its parameters ask for the fade (no
+// crop_n_zoom, border_type VS_BORDER_FADE); 0 (the default) likewise.  The result is padded as with yuv_border_pad.
 inline Refusal check_input(const PixFmt* f, int w, int h, size_t pitch, const ChromaLayout& in, const ChromaLayout& out, int border_size,
-                           int yuv_crop_zoom = 0, int yuv_border_pad = 0) {
+                           int yuv_crop_zoom = 0, int yuv_border_pad = 0, int yuv_fade = 0) {
     if (w <= 0 || h <= 0 || !f) return refuse(VS_ERR_INVALID_ARG, "push: bad geometry/format");
     if ((f->sx && (w & 1)) || (f->sy && (h & 1))) return refuse(VS_ERR_INVALID_ARG, fmt_needs(*f) + (f->sy ? " even w,h" : " an even w"));
     if (f->luma_uv() && f->sample_bytes == 2 && ((pitch | in.uv_off | out.uv_off) & 1))
@@ -134,6 +136,13 @@ inline Refusal check_input(const PixFmt* f, int w, int h, size_t pitch, const Ch
         if (f->three_planes() && out.c_pitch && out.c_pitch < f->chroma_row_bytes(w + 2 * border_size))
             return refuse(VS_ERR_INVALID_ARG, std::string("border pad on ") + f->name + ": the output chroma pitch must hold a padded chroma row (" +
                                                   std::to_string(f->chroma_row_bytes(w + 2 * border_size)) + " bytes)");
+    } else if (border_size > 0 && yuv_fade && f->kind != PIX_INTERLEAVED) {
+        // (as for border pad: the border of a chroma plane, and the padded result)
+        if (border_size & ((1 << (f->sx > f->sy ? f->sx : f->sy)) - 1))
+            return refuse(VS_ERR_INVALID_ARG, std::string("fade on ") + f->name + " needs an even border_size (the chroma planes are subsampled: their border is border_size / 2)");
+        if (f->three_planes() && out.c_pitch && out.c_pitch < f->chroma_row_bytes(w + 2 * border_size))
+            return refuse(VS_ERR_INVALID_ARG, std::string("fade on ") + f->name + ": the output chroma pitch must hold a padded chroma row (" +
+                                                  std::to_string(f->chroma_row_bytes(w + 2 * border_size)) + " bytes)");
     } else if (border_size > 0 && !f->border_modes) {
         // historical wording: two texts (the formats that came later name the fade mode and themselves)
         if (fmt_named_in_mode_texts(*f))
@@ -150,10 +159,10 @@ inline vs_yuv_fill yuv_video_black(const PixFmt& f) {
     const int sh = f.luma_uv() && f.sample_bytes == 2 ? 8 : f.bits - 8;
     return vs_yuv_fill{(uint16_t)(16 << sh), (uint16_t)(128 << sh), (uint16_t)(128 << sh), 0};
 }
-// A fill colour of border pad on a YUV stream: 8-bit formats hold 8-bit samples
-inline Refusal check_yuv_fill(const PixFmt& f, const vs_yuv_fill& c) {
+// A fill colour of border pad (or, with the setter's name given, of the fade) on a YUV stream: 8-bit formats hold 8-bit samples
+inline Refusal check_yuv_fill(const PixFmt& f, const vs_yuv_fill& c, const char* setter = "vs_stab_set_yuv_border_pad") {
     if (f.sample_bytes == 1 && (c.y > 255 || c.u > 255 || c.v > 255))
-        return refuse(VS_ERR_INVALID_ARG, std::string("vs_stab_set_yuv_border_pad: a fill sample above 255 on ") + f.name + " (8-bit samples)");
+        return refuse(VS_ERR_INVALID_ARG, std::string(setter) + ": a fill sample above 255 on " + f.name + " (8-bit samples)");
     return Refusal();
 }
 

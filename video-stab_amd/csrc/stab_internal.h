@@ -134,6 +134,14 @@ struct vs_stab {
     vs_yuv_fill pad_fill = {0, 0, 0, 0};        // the caller's; not given: the format's video black
     size_t pad_pitch = 0;
     int pad_own = 0;
+    // the fade border on a YUV stream (vs_stab_set_yuv_fade): one k_yuvfade launch pads the planes of a frame and blends them with
+    // the history into the padded scratch surface (d_padB, as above), the warp reads that under BORDER_REPLICATE, and a second
+    // launch folds the result into the history.  The history has the scratch surface's layout; like d_fade it outlives
+    // vs_stab_clean, so it remembers the geometry it was made for.
+    bool yuv_fade = false, yfade_fill_given = false, yfade_valid = false;
+    vs_yuv_fill yfade_fill = {0, 0, 0, 0};
+    uint8_t* d_yfade = nullptr;
+    int yfade_count = 0, yfade_w = 0, yfade_h = 0, yfade_b = 0, yfade_fmt = -1;
     uint8_t* d_out = nullptr;
     size_t out_bytes = 0;
     // host pipeline (vs_stab_set_host_pipeline): the result of a call stays in d_hold[] and travels to the host during the
@@ -268,8 +276,16 @@ inline bool yuv_cz_on(const vs_stab* s) { return s->yuv_cz && s->pf->kind != PIX
 inline bool yuv_pad_wanted(const vs_stab* s) { return s->yuv_pad && !s->p.crop_n_zoom && s->p.border_size > 0 && s->p.border_type <= VS_BORDER_WRAP; }
 inline bool yuv_pad_on(const vs_stab* s) { return yuv_pad_wanted(s) && s->pf->kind != PIX_INTERLEAVED; }
 // The rows of luma the layout of a result is counted from: the padded height where the result is padded
-inline int res_h(const vs_stab* s) { return yuv_pad_on(s) ? s->h + 2 * s->p.border_size : s->h; }
+// The fade border on a YUV stream: the mode is on and the parameters ask for the fade.  (With the virtual canvas on as well the
+// stream is refused at its first allocation: check_canvas.)
+inline bool yuv_fade_wanted(const vs_stab* s) { return s->yuv_fade && !s->p.crop_n_zoom && s->p.border_size > 0 && s->p.border_type == VS_BORDER_FADE; }
+inline bool yuv_fade_on(const vs_stab* s) { return yuv_fade_wanted(s) && s->pf->kind != PIX_INTERLEAVED; }
+// Either of the two: the stream's warp reads a padded scratch surface and its result is padded
+inline bool yuv_padded(const vs_stab* s) { return yuv_pad_on(s) || yuv_fade_on(s); }
+// The rows of luma the layout of a result is counted from: the padded height where the result is padded
+inline int res_h(const vs_stab* s) { return yuv_padded(s) ? s->h + 2 * s->p.border_size : s->h; }
 inline vs_yuv_fill yuv_pad_fill(const vs_stab* s) { return s->pad_fill_given ? s->pad_fill : yuv_video_black(*s->pf); }
+inline vs_yuv_fill yuv_fade_fill(const vs_stab* s) { return s->yfade_fill_given ? s->yfade_fill : yuv_video_black(*s->pf); }
 
 inline int build_pyramid(vs_stab* s, int k, hipStream_t st) {
     Pyramid& P = s->pyr[k];
@@ -318,6 +334,8 @@ inline I420Layout pad_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s-
 inline uint8_t* pad_scratch(const vs_stab* s, int idx) { return s->d_padB + (size_t)idx * s->pad_frame_bytes; }
 // The pad of n frames (in the stream's input layout) into their scratch surfaces: ONE k_yuvpad launch over all their planes (stabilizer.cpp)
 int pad_launch(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, hipStream_t st);
+// ... the same with the border mode and the fill given (the first history of the fade border: VS_BORDER_BLACK with the fade's fill)
+int pad_planes(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, int border, const vs_yuv_fill& c, hipStream_t st);
 
 // A ring slot goes back to the free list behind the work on `st` that reads it.  A slot whose event cannot be recorded stays out
 // of the ring: its next writer would have nothing to wait for.

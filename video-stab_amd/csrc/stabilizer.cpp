@@ -249,7 +249,7 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
     if (yuv_cz_on(s)) {
         VS_OBJ_TRY(s, cz_allocate(s));
-    } else if (yuv_pad_on(s)) {
+    } else if (yuv_padded(s)) {
         VS_OBJ_TRY(s, pad_allocate(s));
     } else if (s->batch_active && s->p.border_size > 0) {
         s->pad_frame_bytes = (s->tmp_bytes + 255) & ~(size_t)255;
@@ -283,7 +283,7 @@ int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src
 // into the caller's frame.  rw x rh: the size of the frame delivered (vs_stab_last_out_dims), which border pad on a YUV stream goes
 // by: a padded result, or the unpadded last frame of a flush with the default offsets of ITS size.
 int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st, int rw, int rh) {
-    if (yuv_pad_on(s)) {
+    if (yuv_padded(s)) {
         if (s->pf->three_planes())
             return copy_i420(s, out, fmt_i420_layout(*s->pf, out_stride, rh), d_src, fmt_i420_layout(*s->pf, orow, rh), hipMemcpyDeviceToHost, st, rw, rh);
         VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, (size_t)rw * s->cn, s->pf->rows(rh), hipMemcpyDeviceToHost, st));
@@ -459,6 +459,63 @@ int warp_frame(const vs_stab* s, const uint8_t* src, size_t sstride, int w, int 
     return launch_warp_plane(&src, &dst, 1, sstride, w, h, dstride, w, h, s->cn, WarpMaps{s->d_Minv, 6, false}, VS_BORDER_BLACK, WarpTabs{}, st);
 }
 
+// The fade border on a YUV stream, in front of the warp (Stabilizer.cpp:914-978 per plane): the first padded frame is the history
+// (:917-926; also after a change of geometry or format, and after vs_stab_set_yuv_fade), alpha ramps with the count (:953-961), and
+// ONE k_yuvfade launch pads the planes of `frame` and blends them with the history into the scratch surface `psrc`.
+int yuv_fade_blend(vs_stab* s, const uint8_t* frame, uint8_t* psrc, hipStream_t st) {
+    const PixFmt& f = *s->pf;
+    const vs_params_c& p = s->p;
+    const int b = p.border_size, w = s->w, h = s->h;
+    if (!s->d_yfade || s->yfade_w != w || s->yfade_h != h || s->yfade_b != b || s->yfade_fmt != s->fmt) {
+        if (s->d_yfade) { (void)hipStreamSynchronize(st); (void)hipFree(s->d_yfade); s->d_yfade = nullptr; }
+        VS_OBJ_HIP(s, hipMalloc((void**)&s->d_yfade, s->pad_frame_bytes));
+        s->yfade_w = w; s->yfade_h = h; s->yfade_b = b; s->yfade_fmt = s->fmt; s->yfade_valid = false;
+    }
+    const vs_yuv_fill c = yuv_fade_fill(s);
+    if (!s->yfade_valid) {
+        VS_OBJ_TRY(s, pad_planes(s, &frame, &s->d_yfade, 1, VS_BORDER_BLACK, c, st));
+        s->yfade_valid = true; s->yfade_count = 0;
+    }
+    float alpha = p.fade_alpha;
+    if (s->yfade_count < p.fade_duration) {
+        alpha = alpha * (static_cast<float>(s->yfade_count) / p.fade_duration);
+        s->yfade_count++;
+    }
+    vs_fade_job jobs[3];
+    int nj = 0;
+    auto add = [&](const uint8_t* src, size_t sstride, int pw, int ph, size_t off, size_t dstride, int bx, int by, int cn, uint16_t f0, uint16_t f1) {
+        jobs[nj++] = vs_fade_job{src, sstride, pw, ph, s->d_yfade + off, dstride, psrc + off, dstride, bx, by, {f0, f1}, cn, 0};
+    };
+    add(frame, s->src_pitch, w, h, 0, s->pad_pitch, b, b, 1, c.y, 0);
+    if (f.luma_uv()) {
+        add(frame + src_uv(s), s->src_pitch, w / 2, h / 2, pad_uv(s), s->pad_pitch, b >> 1, b >> 1, 2, c.u, c.v);
+    } else {
+        const I420Layout L = src_i420(s), D = pad_i420(s);
+        add(frame + L.u, L.cpitch, w >> f.sx, h >> f.sy, D.u, D.cpitch, b >> f.sx, b >> f.sy, 1, c.u, 0);
+        add(frame + L.v, L.cpitch, w >> f.sx, h >> f.sy, D.v, D.cpitch, b >> f.sx, b >> f.sy, 1, c.v, 0);
+    }
+    VS_OBJ_TRY(s, launch_yuvfade_blend(jobs, nj, f.sample_bytes, alpha, 1.0f - alpha, st));
+    return VS_OK;
+}
+
+// ... and behind it (:1086-1100 per plane): ONE launch folds the planes of the result, read through the output layout, into the history
+int yuv_fade_update(vs_stab* s, const uint8_t* d_out, size_t out_stride, hipStream_t st) {
+    const PixFmt& f = *s->pf;
+    const BorderPlan bp = border_plan(s);
+    vs_fade_update_job jobs[3];
+    int nj = 0;
+    jobs[nj++] = vs_fade_update_job{s->d_yfade, s->pad_pitch, d_out, out_stride, bp.pw, bp.ph, 1, 0};
+    if (f.luma_uv()) {
+        jobs[nj++] = vs_fade_update_job{s->d_yfade + pad_uv(s), s->pad_pitch, d_out + dst_uv(s, d_out, out_stride), out_stride, bp.pw / 2, bp.ph / 2, 2, 0};
+    } else {
+        const I420Layout H = pad_i420(s), D = dst_i420(s, d_out, out_stride);
+        jobs[nj++] = vs_fade_update_job{s->d_yfade + H.u, H.cpitch, d_out + D.u, D.cpitch, bp.pw >> f.sx, bp.ph >> f.sy, 1, 0};
+        jobs[nj++] = vs_fade_update_job{s->d_yfade + H.v, H.cpitch, d_out + D.v, D.cpitch, bp.pw >> f.sx, bp.ph >> f.sy, 1, 0};
+    }
+    VS_OBJ_TRY(s, launch_yuvfade_update(jobs, nj, f.sample_bytes, st));
+    return VS_OK;
+}
+
 // applyNextSmoothTransform (Stabilizer.cpp:763-1137) into d_out (device), on `main`
 int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
     const vs_params_c& p = s->p;
@@ -486,7 +543,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // Stabilizer.cpp:774-780: no transform exists for this frame (last frame of a
         // flush): the queued frame is returned as is, at its own size (no border pad).
         // (border pad on a YUV stream: the frame alone is written, with the default offsets of its own size)
-        const bool ypad = yuv_pad_on(s);
+        const bool ypad = yuv_padded(s);
         if (!ypad && (ow != s->w || oh != s->h))
             VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
         if (s->pf->three_planes())
@@ -510,9 +567,12 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
         // border pad: one launch pads both planes into the stream's scratch surface, which is warped at the padded size, taps
         // outside it taking its edge (the border)
-        const bool pad = yuv_pad_on(s);
+        // fade: one launch pads both planes and blends them with the history into that surface; one more, behind the warp, folds
+        // the result into the history
+        const bool fade = yuv_fade_on(s), pad = yuv_padded(s);
         uint8_t* psrc = pad ? pad_scratch(s, s->pad_own) : nullptr;
-        if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
+        if (fade) rc = yuv_fade_blend(s, frame, psrc, st);
+        else if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
         const uint8_t* wsrc = pad ? psrc : frame;
         const uint8_t* uv = pad ? psrc + pad_uv(s) : frame + src_uv(s);
         uint8_t* out_uv = wdst + (cz ? cz_uv(s) : dst_uv(s, d_out, out_stride));
@@ -522,20 +582,23 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
                                   WarpMaps{s->d_Minv, 12, false}, pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK,
                                   s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, s->pf->sample_bytes);
         if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
+        if (fade && rc == VS_OK) rc = yuv_fade_update(s, d_out, out_stride, st);
     } else if (s->pf->three_planes()) {
         // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
         StageScope t(s, VS_STAGE_WARP, st);
         const bool cz = yuv_cz_on(s);
         uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
-        const bool pad = yuv_pad_on(s);      // (as above: pad into the scratch surface, warp that)
+        const bool fade = yuv_fade_on(s), pad = yuv_padded(s);      // (as above: pad, or pad and blend, into the scratch surface, warp that)
         uint8_t* psrc = pad ? pad_scratch(s, s->pad_own) : nullptr;
-        if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
+        if (fade) rc = yuv_fade_blend(s, frame, psrc, st);
+        else if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
         const uint8_t* wsrc = pad ? psrc : frame;
         if (rc == VS_OK)
             rc = launch_warp_i420(&wsrc, &wdst, 1, pad ? pad_i420(s) : src_i420(s), cz ? cz_i420(s) : dst_i420(s, d_out, out_stride), bp.pw, bp.ph,
                                   WarpMaps{s->d_Minv, 12, false}, pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, st,
                                   s->pf->sample_bytes, s->pf->sx, s->pf->sy);
         if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
+        if (fade && rc == VS_OK) rc = yuv_fade_update(s, d_out, out_stride, st);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
         const int bw = bp.pw, bh = bp.ph;
         const size_t prow = bp.prow, nb = prow * bh;
@@ -719,7 +782,9 @@ int take_slot(vs_stab* s, int* slot) {
 
 // What every push asks first: the rules of the input side (pixfmt.h), then the stream allocates for its first frame.
 int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
-    VS_REFUSE(s, check_input(pixfmt(fmt), w, h, stride, s->in, s->out, s->p.border_size, s->yuv_cz && s->p.crop_n_zoom, yuv_pad_wanted(s)));
+    VS_REFUSE(s, check_input(pixfmt(fmt), w, h, stride, s->in, s->out, s->p.border_size, s->yuv_cz && s->p.crop_n_zoom, yuv_pad_wanted(s), yuv_fade_wanted(s)));
+    if (yuv_fade_wanted(s) && s->yfade_fill_given && pixfmt(fmt)->kind != PIX_INTERLEAVED)
+        VS_REFUSE(s, check_yuv_fill(*pixfmt(fmt), s->yfade_fill, "vs_stab_set_yuv_fade"));
     if (yuv_pad_wanted(s) && s->pad_fill_given && pixfmt(fmt)->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*pixfmt(fmt), s->pad_fill));
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     if (!s->allocated) return allocate(s, w, h, fmt);
@@ -727,10 +792,10 @@ int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
     return VS_OK;
 }
 
-// Border pad on a YUV stream: the pitch of a device surface that receives a result holds a padded row
+// Border pad or fade on a YUV stream: the pitch of a device surface that receives a result holds a padded row
 Refusal check_padded_out(const vs_stab* s, const char* call, size_t out_stride) {
-    if (!yuv_pad_on(s) || out_stride >= border_plan(s).prow) return Refusal();
-    return refuse(VS_ERR_INVALID_ARG, std::string(call) + ": border pad on " + s->pf->name + ": out_stride must hold a padded row (" +
+    if (!yuv_padded(s) || out_stride >= border_plan(s).prow) return Refusal();
+    return refuse(VS_ERR_INVALID_ARG, std::string(call) + (yuv_fade_on(s) ? ": fade on " : ": border pad on ") + s->pf->name + ": out_stride must hold a padded row (" +
                                           std::to_string(border_plan(s).prow) + " bytes)");
 }
 
@@ -760,9 +825,12 @@ int create_events(vs_stab* s) {
 }  // namespace
 
 int vsd::pad_launch(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, hipStream_t st) {
+    return pad_planes(s, frames, scratch, n, s->p.border_type, yuv_pad_fill(s), st);
+}
+
+int vsd::pad_planes(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, int border, const vs_yuv_fill& c, hipStream_t st) {
     const PixFmt& f = *s->pf;
-    const int b = s->p.border_size, w = s->w, h = s->h, border = s->p.border_type;
-    const vs_yuv_fill c = yuv_pad_fill(s);
+    const int b = s->p.border_size, w = s->w, h = s->h;
     vs_pad_job jobs[YP_MAX_JOBS];
     int nj = 0;
     auto add = [&](const uint8_t* src, size_t sstride, int pw, int ph, uint8_t* dst, size_t dstride, int bx, int by, int cn, uint16_t f0, uint16_t f1) {
@@ -920,6 +988,7 @@ void vs_stab_destroy(vs_stab* s) {
     wait_streams(s);
     free_all(s);
     if (s->d_fade) (void)hipFree(s->d_fade);
+    if (s->d_yfade) (void)hipFree(s->d_yfade);
     if (s->d_ct) (void)hipFree(s->d_ct);
     canvas_delete(s->canvas);
     for (auto& pe : s->pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
@@ -1265,6 +1334,25 @@ int vs_stab_set_yuv_border_pad(vs_stab* s, int enable, const vs_yuv_fill* fill) 
     s->yuv_pad = enable != 0;
     s->pad_fill_given = enable && fill;
     if (s->pad_fill_given) s->pad_fill = *fill;
+    return VS_OK;
+}
+
+// The fade border on YUV surfaces, off by default: with it a stream whose parameters say border_size without crop_n_zoom and
+// borderType "fade" pads and blends the planes of a frame with a history (k_yuvfade.hip), warps the padded surface under
+// BORDER_REPLICATE and folds the result into the history; without it such a stream is refused as ever.  Every accepted call drops
+// the history: the next padded frame is the history, count 0.
+int vs_stab_set_yuv_fade(vs_stab* s, int enable, const vs_yuv_fill* fill) {
+    if (!s) return VS_ERR_INVALID_ARG;
+    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_fade: the frame queue must be empty");
+    if (fill && fill->reserved != 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_fade: fill->reserved must be 0");
+    if (enable && fill && s->allocated && s->pf->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*s->pf, *fill, "vs_stab_set_yuv_fade"));
+    // (a stream whose parameters ask for the fade was allocated with the mode on - off, its first push was refused - so the scratch
+    // surface is there whenever the mode is on)
+    s->yuv_fade = enable != 0;
+    s->yfade_fill_given = enable && fill;
+    if (s->yfade_fill_given) s->yfade_fill = *fill;
+    s->yfade_valid = false; s->yfade_count = 0;
     return VS_OK;
 }
 

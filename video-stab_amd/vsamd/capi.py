@@ -178,6 +178,20 @@ class VsPadJob(C.Structure):
                 ("cn", C.c_int32), ("border", C.c_int32), ("fill", C.c_uint16 * 2), ("reserved", C.c_int32)]
 
 
+class VsFadeJob(C.Structure):
+    """struct vs_fade_job (include/vs_stab.h): one plane of vs_op_fade_blend_jobs."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_size_t), ("sw", C.c_int32), ("sh", C.c_int32),
+                ("hist", C.c_void_p), ("hist_stride", C.c_size_t),
+                ("dst", C.c_void_p), ("dst_stride", C.c_size_t), ("bx", C.c_int32), ("by", C.c_int32),
+                ("fill", C.c_uint16 * 2), ("cn", C.c_int32), ("reserved", C.c_int64)]
+
+
+class VsFadeUpdateJob(C.Structure):
+    """struct vs_fade_update_job (include/vs_stab.h): one plane of vs_op_fade_update_jobs."""
+    _fields_ = [("hist", C.c_void_p), ("hist_stride", C.c_size_t), ("res", C.c_void_p), ("res_stride", C.c_size_t),
+                ("w", C.c_int32), ("h", C.c_int32), ("cn", C.c_int32), ("reserved", C.c_int32)]
+
+
 class VsScaleJob(C.Structure):
     """struct vs_scale_job (include/vs_stab.h): one crop-and-scale of vs_op_scale_jobs."""
     _fields_ = [("src", C.c_void_p), ("src_stride", C.c_size_t), ("sw", C.c_int32), ("sh", C.c_int32),
@@ -511,6 +525,10 @@ class VsLib:
             L.vs_batch_set_yuv_border_pad.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
             L.vs_yuv_video_black.argtypes = [C.c_int, C.POINTER(VsYuvFill)]
             L.vs_op_pad_jobs.argtypes = [C.POINTER(VsPadJob), C.c_int, C.c_int, vp]
+            # the fade border on YUV streams
+            L.vs_stab_set_yuv_fade.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
+            L.vs_op_fade_blend_jobs.argtypes = [C.POINTER(VsFadeJob), C.c_int, C.c_int, C.c_float, C.c_float, vp]
+            L.vs_op_fade_update_jobs.argtypes = [C.POINTER(VsFadeUpdateJob), C.c_int, C.c_int, vp]
             # roll correction and auto zoom/crop on interleaved colour frames (BGR8, RGB8, BGRA8, RGBA8)
             L.vs_roll_correct_rgb_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]
             L.vs_roll_correct_rgb_dev_n.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t]
@@ -823,6 +841,24 @@ class VsLib:
             a.src, a.src_stride, a.sw, a.sh, a.dst, a.dst_stride, a.bx, a.by, a.cn, a.border = src, ss, sw, sh, dst, ds, bx, by, cn, border
             a.fill[0], a.fill[1] = fill
         self.check(self.lib.vs_op_pad_jobs(arr, len(jobs), sample_bytes, stream))
+
+    def fade_blend_jobs(self, jobs, alpha, beta, sample_bytes=1, stream=None):
+        """vs_op_fade_blend_jobs (pad and blend of the fade border on YUV surfaces): 1 .. 32 jobs, tuples (src, src_stride, sw, sh,
+        hist, hist_stride, dst, dst_stride, bx, by, cn, (fill0, fill1)) of device addresses; asynchronous."""
+        arr = (VsFadeJob * max(1, len(jobs)))()
+        for a, (src, ss, sw, sh, hist, hs, dst, ds, bx, by, cn, fill) in zip(arr, jobs):
+            a.src, a.src_stride, a.sw, a.sh, a.hist, a.hist_stride = src, ss, sw, sh, hist, hs
+            a.dst, a.dst_stride, a.bx, a.by, a.cn = dst, ds, bx, by, cn
+            a.fill[0], a.fill[1] = fill
+        self.check(self.lib.vs_op_fade_blend_jobs(arr, len(jobs), sample_bytes, alpha, beta, stream))
+
+    def fade_update_jobs(self, jobs, sample_bytes=1, stream=None):
+        """vs_op_fade_update_jobs (the history update of the fade border on YUV surfaces): 1 .. 32 jobs, tuples (hist, hist_stride,
+        res, res_stride, w, h, cn) of device addresses; asynchronous."""
+        arr = (VsFadeUpdateJob * max(1, len(jobs)))()
+        for a, (hist, hs, res, rs, w, h, cn) in zip(arr, jobs):
+            a.hist, a.hist_stride, a.res, a.res_stride, a.w, a.h, a.cn = hist, hs, res, rs, w, h, cn
+        self.check(self.lib.vs_op_fade_update_jobs(arr, len(jobs), sample_bytes, stream))
 
     def yuv_video_black(self, fmt):
         """vs_yuv_video_black (no device needed): (y, u, v) of limited-range black, samples as they lie in memory."""
@@ -1681,6 +1717,12 @@ class Stabilizer:
         fill: (y, u, v) samples as they lie in memory; None: the format's video black."""
         c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
         self.vs.check(self.lib.vs_stab_set_yuv_border_pad(self.h, int(on), c), self.h)
+
+    def set_yuv_fade(self, on=True, fill=None):
+        """vs_stab_set_yuv_fade: border_size with borderType "fade" on NV12 / P010 / three-plane streams (off: refused).
+        fill: (y, u, v) samples as they lie in memory; None: the format's video black.  Every accepted call drops the history."""
+        c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
+        self.vs.check(self.lib.vs_stab_set_yuv_fade(self.h, int(on), c), self.h)
 
     def set_zero_copy(self, on=True):
         self.vs.check(self.lib.vs_stab_set_zero_copy(self.h, int(on)), self.h)
