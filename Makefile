@@ -10,7 +10,8 @@
 #                       fuzz harnesses (scratch/fuzz): 20 000 mutated config documents, 5 000 random masks;
 #                     * vs_libm.h (host build) over 2^24 arguments per function against the host libm;
 #                     * the format table and the refusal rules (csrc/pixfmt.h) in tests/cpp/pixfmt_check over the whole case list
-#                       of tests/refusal_cases.py, and the rules of the fade border on YUV in tests/cpp/yuv_fade_check.
+#                       of tests/refusal_cases.py, the plane list of a YUV surface (csrc/planar_layout.h) in tests/cpp/planes_check,
+#                       and the rules of the fade border on YUV in tests/cpp/yuv_fade_check.
 #                   GPU sanitizers are not available on this pool; device code is covered by the parity tests instead.
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
 ASAN_LIB := $(shell gcc -print-file-name=libasan.so)
@@ -37,6 +38,7 @@ asan-host:
 	    scratch/fuzz/azc_fuzz.cpp scratch/fuzz/azc_stubs.cpp video-stab_amd/csrc/azc_contour.cpp -o scratch/fuzz/_asan/azc_fuzz
 	g++ -O1 -g -std=c++17 -ffp-contract=off -pthread $(SAN) -DLIBM_CHECK_QUICK tests/cpp/libm_check.cpp -o scratch/fuzz/_asan/libm_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/pixfmt_check.cpp -o scratch/fuzz/_asan/pixfmt_check
+	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/planes_check.cpp -o scratch/fuzz/_asan/planes_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/yuv_fade_check.cpp -o scratch/fuzz/_asan/yuv_fade_check
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/config_fuzz 20000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/azc_fuzz 5000
@@ -44,6 +46,8 @@ asan-host:
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/pixfmt_check table > /dev/null
 	PYTHONPATH=video-stab_amd:tests python3 -c "import refusal_cases as r; print('\n'.join(r.line(c) for c in r.cases() if not r.stateful(c)))" | \
 	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/pixfmt_check cases > /dev/null
+	for f in 1 6 7 8 9 10 11 12 13 14 15; do for s in "2 2" "6 4" "66 50"; do for l in "0 0 0 0" "8192 0 0 0" "0 12288 8192 0" "0 0 0 128"; do \
+	  echo "$$f $$s 256 $$l"; done; done; done | ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/planes_check > /dev/null
 	for f in 0 1 2 6 7 8 10 11 12 15; do for b in 0 5 8; do for m in 0 1; do echo "$$f 64 48 128 $$b 0 $$m 1 $$m 1 70"; done; done; done | \
 	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/yuv_fade_check > /dev/null
 

@@ -186,8 +186,7 @@ int group_allocate(vs_batch* g) {
 struct WarpEnds { const uint8_t* src; uint8_t* dst; };
 WarpEnds warp_ends(const vs_stab* o, const uint8_t* frame, uint8_t* d_out, int pad_idx, const BorderPlan& bp) {
     if (!bp.pad && !bp.crop) return {frame, d_out};
-    uint8_t* scratch = o->d_padB + (size_t)pad_idx * o->pad_frame_bytes;       // (a YUV stream: cz_scratch(o, pad_idx))
-    return bp.pad ? WarpEnds{scratch, d_out} : WarpEnds{frame, scratch};
+    return bp.pad ? WarpEnds{scratch(o, pad_idx), d_out} : WarpEnds{frame, scratch(o, pad_idx)};
 }
 
 // The warps of the step whose tails were queued last, 32 frames per launch (`what` = VS_WARP_ONLY / VS_WARP_ALL), or only their
@@ -218,19 +217,9 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
         if (rc != VS_OK) break;
         const WarpMaps maps{g->d_MinvB[R.set] + 12 * i0, 12, false};
         const WarpTabs tabs{WarpTabs::CALLER, g->d_tabs[R.set] + (size_t)i0 * g->tab_ints, g->tab_ints, what};
-        if (s0->pf->luma_uv()) {
-            // interleaved chroma plane: half size, two channels, the map with the halved translation (Minv + 6)
-            const uint8_t* us[WARP_BATCH_MAX];
-            uint8_t* ud[WARP_BATCH_MAX];
-            for (int i = 0; i < m; i++) { us[i] = srcs[i] + (yp ? pad_uv(s0) : src_uv(s0)); ud[i] = dsts[i] + (cz ? cz_uv(s0) : dst_uv(s0, dsts[i], R.stride)); }
-            rc = launch_warp_nv12(srcs, dsts, us, ud, m, yp ? s0->pad_pitch : s0->src_pitch, cz ? s0->cz_pitch : R.stride, bp.pw, bp.ph, maps, wb, tabs, st,
-                                  s0->pf->sample_bytes);
-        } else if (s0->pf->three_planes()) {
-            // I420, I010, I012: Y, U and V in one launch; the chroma table (the map with the halved translation, Minv + 6) serves both U and V
-            rc = launch_warp_i420(srcs, dsts, m, yp ? pad_i420(s0) : src_i420(s0), cz ? cz_i420(s0) : dst_i420(s0, dsts[0], R.stride), bp.pw, bp.ph, maps, wb, tabs,
-                                  st, s0->pf->sample_bytes, s0->pf->sx, s0->pf->sy);
-        }
         if (s0->pf->kind != PIX_INTERLEAVED) {
+            // (one output layout per launch: the due frames of a step are all the caller's surfaces or all the host staging)
+            rc = warp_yuv(srcs, dsts, m, warp_src_planes(s0), warp_dst_planes(s0, dsts[0], R.stride), maps, wb, tabs, st);
             // crop-and-zoom on YUV surfaces: ONE launch behind the warps resizes the crops of all their planes into the results
             if (cz && what != VS_WARP_TABLES_ONLY && rc == VS_OK) rc = cz_launch(s0, dsts, &R.dsts[i0], m, R.stride, st);
             continue;
@@ -333,15 +322,12 @@ int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const
                 const WarpEnds e = warp_ends(s, b.out_frame, b.d_out, npad, bp);
                 int32_t* T = g->d_tabs[set] + (size_t)j * g->tab_ints;
                 jobs[0] = WarpTabJob{T, e.src, e.dst, bp.pw, bp.ph};
-                const bool cz = yuv_cz_on(s);        // (the warp then fills a scratch surface, in the scratch layout)
-                const bool yp = yuv_pad_on(s);       // (the warp then reads a padded scratch surface, in the scratch layout, at bp.pw x bp.ph)
-                if (s->pf->luma_uv())
-                    jobs[1] = WarpTabJob{T + tab_layout(bp.pw, bp.ph).stride, e.src + (yp ? pad_uv(s) : src_uv(s)),
-                                         e.dst + (cz ? cz_uv(s) : dst_uv(s, e.dst, b.out_stride)), bp.pw / 2, bp.ph / 2};
-                else if (s->pf->three_planes())      // ONE chroma table, in pixels, naming the U planes: a V tile adds the launch's V - U
-                    jobs[1] = WarpTabJob{T + tab_layout(bp.pw, bp.ph).stride, e.src + (yp ? pad_i420(s) : src_i420(s)).u,
-                                         e.dst + (cz ? cz_i420(s) : dst_i420(s, e.dst, b.out_stride)).u,
-                                         bp.pw >> s->pf->sx, bp.ph >> s->pf->sy};      // (sized for the format's chroma planes: 4:2:0 halves both)
+                // the chroma table, in pixels of plane 1 of what the warp reads and fills (a scratch surface with border pad or
+                // crop-and-zoom): the UV plane, or the U plane - ONE table, a V tile adds the launch's V - U
+                if (s->pf->kind != PIX_INTERLEAVED) {
+                    const Planes S = warp_src_planes(s), D = warp_dst_planes(s, e.dst, b.out_stride);
+                    jobs[1] = WarpTabJob{T + tab_layout(bp.pw, bp.ph).stride, e.src + S[1].off, e.dst + D[1].off, S[1].w, S[1].h};
+                }
             }
             npad++;
             P.pend_stride = b.out_stride;

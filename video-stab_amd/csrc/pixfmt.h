@@ -125,23 +125,15 @@ inline Refusal check_input(const PixFmt* f, int w, int h, size_t pitch, const Ch
         const Refusal r = check_chroma_pitch(*f, w, in.c_pitch, out.c_pitch, "");
         if (r.rc != VS_OK) return r;
     }
-    if (border_size > 0 && yuv_crop_zoom && f->kind != PIX_INTERLEAVED) {
-        // the crop of a chroma plane is the luma crop's: (b >> sx, b >> sy) must be exact
+    // the YUV mode that acts on the border, in the words of its texts; crop-and-zoom keeps the frame's size, the other two pad the result
+    const char* const mode = yuv_crop_zoom ? "crop-and-zoom on " : yuv_border_pad ? "border pad on " : yuv_fade ? "fade on " : nullptr;
+    if (border_size > 0 && mode && f->kind != PIX_INTERLEAVED) {
+        // the crop / the border of a chroma plane is the luma one's: (b >> sx, b >> sy) must be exact
         if (border_size & ((1 << (f->sx > f->sy ? f->sx : f->sy)) - 1))
-            return refuse(VS_ERR_INVALID_ARG, std::string("crop-and-zoom on ") + f->name + " needs an even border_size (the chroma planes are subsampled: their crop starts at border_size / 2)");
-    } else if (border_size > 0 && yuv_border_pad && f->kind != PIX_INTERLEAVED) {
-        // the border of a chroma plane is the luma border's: (b >> sx, b >> sy) must be exact
-        if (border_size & ((1 << (f->sx > f->sy ? f->sx : f->sy)) - 1))
-            return refuse(VS_ERR_INVALID_ARG, std::string("border pad on ") + f->name + " needs an even border_size (the chroma planes are subsampled: their border is border_size / 2)");
-        if (f->three_planes() && out.c_pitch && out.c_pitch < f->chroma_row_bytes(w + 2 * border_size))
-            return refuse(VS_ERR_INVALID_ARG, std::string("border pad on ") + f->name + ": the output chroma pitch must hold a padded chroma row (" +
-                                                  std::to_string(f->chroma_row_bytes(w + 2 * border_size)) + " bytes)");
-    } else if (border_size > 0 && yuv_fade && f->kind != PIX_INTERLEAVED) {
-        // (as for border pad: the border of a chroma plane, and the padded result)
-        if (border_size & ((1 << (f->sx > f->sy ? f->sx : f->sy)) - 1))
-            return refuse(VS_ERR_INVALID_ARG, std::string("fade on ") + f->name + " needs an even border_size (the chroma planes are subsampled: their border is border_size / 2)");
-        if (f->three_planes() && out.c_pitch && out.c_pitch < f->chroma_row_bytes(w + 2 * border_size))
-            return refuse(VS_ERR_INVALID_ARG, std::string("fade on ") + f->name + ": the output chroma pitch must hold a padded chroma row (" +
+            return refuse(VS_ERR_INVALID_ARG, std::string(mode) + f->name + " needs an even border_size (the chroma planes are subsampled: their " +
+                                                  (yuv_crop_zoom ? "crop starts at border_size / 2)" : "border is border_size / 2)"));
+        if (!yuv_crop_zoom && f->three_planes() && out.c_pitch && out.c_pitch < f->chroma_row_bytes(w + 2 * border_size))
+            return refuse(VS_ERR_INVALID_ARG, std::string(mode) + f->name + ": the output chroma pitch must hold a padded chroma row (" +
                                                   std::to_string(f->chroma_row_bytes(w + 2 * border_size)) + " bytes)");
     } else if (border_size > 0 && !f->border_modes) {
         // historical wording: two texts (the formats that came later name the fade mode and themselves)

@@ -1,6 +1,7 @@
-// Where the planes of a three-plane surface (VS_FMT_I420 ... VS_FMT_I412) lie, and what the roll and zoom/crop stages refuse about
-// such a surface.  Plain C++ over integers like pixfmt.h: no HIP, no object - tests/cpp/planar_layout_check.cpp compiles this header
-// alone and asks the rules without a device.
+// Where the planes of a surface lie - the three-plane layout of the launchers (VS_FMT_I420 ... VS_FMT_I412) and the plane list of
+// any format that the stream and the batch schedule walk - and what the roll and zoom/crop stages refuse about a three-plane
+// surface.  Plain C++ over integers like pixfmt.h: no HIP, no object - tests/cpp/planar_layout_check.cpp and tests/cpp/planes_check.cpp
+// compile this header alone and ask it without a device.
 #ifndef VS_PLANAR_LAYOUT_H
 #define VS_PLANAR_LAYOUT_H
 
@@ -22,6 +23,42 @@ inline I420Layout i420_layout(size_t pitch, int h, size_t u_off, size_t v_off, s
     l.u = u_off ? u_off : (size_t)h * pitch;
     l.v = v_off ? v_off : l.u + (size_t)(h >> sy) * l.cpitch;
     return l;
+}
+
+// ---- the plane list: where every plane of a surface lies, stated once for the stream and the batch schedule (stab_internal.h)
+// One plane: `off` bytes behind the surface pointer, rows of `pitch` bytes, w x h pixels of cn channels (an interleaved (U, V)
+// pair is one pixel of two channels), subsampled by (sx, sy) against luma - which is also what a luma border or crop shifts by.
+struct Plane {
+    size_t off, pitch;
+    int w, h, cn, sx, sy;
+};
+// A surface: luma and the UV plane (NV12, P010), luma, U and V (I420 ... I412), or the one plane of an interleaved format.
+struct Planes {
+    int n = 0, sample_bytes = 1;
+    Plane p[3] = {};
+    const Plane& operator[](int k) const { return p[k]; }
+    size_t row_bytes(int k) const { return (size_t)p[k].w * p[k].cn * sample_bytes; }
+    I420Layout i420() const { return I420Layout{p[0].pitch, p[1].pitch, p[1].off, p[2].off}; }      // (three planes)
+};
+// The planes of a w x h surface of format f at `pitch`; c: the caller's chroma layout, 0 = the packed default per field (chroma
+// behind the h luma rows; three planes: i420_layout).
+inline Planes planes(const PixFmt& f, int w, int h, size_t pitch, const ChromaLayout& c = ChromaLayout()) {
+    Planes P;
+    P.sample_bytes = f.sample_bytes;
+    P.n = f.three_planes() ? 3 : f.luma_uv() ? 2 : 1;
+    P.p[0] = Plane{0, pitch, w, h, P.n == 1 ? f.cn : 1, 0, 0};
+    if (f.luma_uv()) P.p[1] = Plane{c.uv_off ? c.uv_off : (size_t)h * pitch, pitch, w >> f.sx, h >> f.sy, 2, f.sx, f.sy};
+    if (f.three_planes()) {
+        const I420Layout l = i420_layout(pitch, h, c.u_off, c.v_off, c.c_pitch, f.sx, f.sy);
+        P.p[1] = Plane{l.u, l.cpitch, w >> f.sx, h >> f.sy, 1, f.sx, f.sy};
+        P.p[2] = Plane{l.v, l.cpitch, w >> f.sx, h >> f.sy, 1, f.sx, f.sy};
+    }
+    return P;
+}
+// Channel ch of the fill sample of plane k: {y, 0}; {u, v} for the UV plane; {u, 0} and {v, 0} for planes of their own
+inline uint16_t plane_fill(const vs_yuv_fill& c, const Planes& P, int k, int ch) {
+    if (P[k].cn == 2) return ch ? c.v : c.u;
+    return ch ? 0 : k == 0 ? c.y : k == 1 ? c.u : c.v;
 }
 
 // ---- k_roll.hip, k_azc.hip: three-plane surfaces (VS_FMT_I420 ... VS_FMT_I412) of the stages around the stabilizer

@@ -121,23 +121,22 @@ struct vs_stab {
     int fade_count = 0, fade_w = 0, fade_h = 0;     // fadeFrameCount_; geometry of the history
     uint8_t* d_padB = nullptr;          // batch mode with a border: one padded (or to-be-cropped) frame per frame of a batch
     size_t pad_frame_bytes = 0;
-    // crop-and-zoom on a YUV stream (vs_stab_set_yuv_crop_zoom): the warps go into scratch surfaces - d_padB again, the format's
-    // packed default layout at pitch cz_pitch, one per frame of a batch and one more (cz_own) for the per-frame path - and one
-    // k_cropzoom launch resizes their crops into the results
+    // A YUV stream with crop-and-zoom, border pad or the fade border (at most one of them acts) has scratch surfaces in d_padB: the
+    // format's packed default layout of border_plan's size at scratch_pitch, one per frame of a batch and one more (scratch_own)
+    // for the per-frame path (scratch_planes, scratch_allocate).
+    size_t scratch_pitch = 0;
+    int scratch_own = 0;
+    // crop-and-zoom (vs_stab_set_yuv_crop_zoom): the warps go into the scratch surfaces and one k_cropzoom launch resizes their
+    // crops into the results
     bool yuv_cz = false;
-    size_t cz_pitch = 0;
-    int cz_own = 0;
-    // border pad on a YUV stream (vs_stab_set_yuv_border_pad): one k_yuvpad launch pads the planes of the frames into scratch
-    // surfaces - d_padB once more, the format's packed default layout of the padded size at pitch pad_pitch, one per frame of a
-    // batch and one more (pad_own) for the per-frame path - which the warps read under BORDER_REPLICATE
+    // border pad (vs_stab_set_yuv_border_pad): one k_yuvpad launch pads the planes of the frames into the scratch surfaces, which
+    // the warps read under BORDER_REPLICATE
     bool yuv_pad = false, pad_fill_given = false;
     vs_yuv_fill pad_fill = {0, 0, 0, 0};        // the caller's; not given: the format's video black
-    size_t pad_pitch = 0;
-    int pad_own = 0;
-    // the fade border on a YUV stream (vs_stab_set_yuv_fade): one k_yuvfade launch pads the planes of a frame and blends them with
-    // the history into the padded scratch surface (d_padB, as above), the warp reads that under BORDER_REPLICATE, and a second
-    // launch folds the result into the history.  The history has the scratch surface's layout; like d_fade it outlives
-    // vs_stab_clean, so it remembers the geometry it was made for.
+    // the fade border (vs_stab_set_yuv_fade): one k_yuvfade launch pads the planes of a frame and blends them with the history
+    // into the scratch surface, the warp reads that under BORDER_REPLICATE, and a second launch folds the result into the
+    // history.  The history has the scratch surface's layout; like d_fade it outlives vs_stab_clean, so it remembers the geometry
+    // it was made for.
     bool yuv_fade = false, yfade_fill_given = false, yfade_valid = false;
     vs_yuv_fill yfade_fill = {0, 0, 0, 0};
     uint8_t* d_yfade = nullptr;
@@ -275,15 +274,12 @@ inline bool yuv_cz_on(const vs_stab* s) { return s->yuv_cz && s->pf->kind != PIX
 // stream with a border never gets as far as its first allocation (pixfmt.h, check_input).
 inline bool yuv_pad_wanted(const vs_stab* s) { return s->yuv_pad && !s->p.crop_n_zoom && s->p.border_size > 0 && s->p.border_type <= VS_BORDER_WRAP; }
 inline bool yuv_pad_on(const vs_stab* s) { return yuv_pad_wanted(s) && s->pf->kind != PIX_INTERLEAVED; }
-// The rows of luma the layout of a result is counted from: the padded height where the result is padded
 // The fade border on a YUV stream: the mode is on and the parameters ask for the fade.  (With the virtual canvas on as well the
 // stream is refused at its first allocation: check_canvas.)
 inline bool yuv_fade_wanted(const vs_stab* s) { return s->yuv_fade && !s->p.crop_n_zoom && s->p.border_size > 0 && s->p.border_type == VS_BORDER_FADE; }
 inline bool yuv_fade_on(const vs_stab* s) { return yuv_fade_wanted(s) && s->pf->kind != PIX_INTERLEAVED; }
 // Either of the two: the stream's warp reads a padded scratch surface and its result is padded
 inline bool yuv_padded(const vs_stab* s) { return yuv_pad_on(s) || yuv_fade_on(s); }
-// The rows of luma the layout of a result is counted from: the padded height where the result is padded
-inline int res_h(const vs_stab* s) { return yuv_padded(s) ? s->h + 2 * s->p.border_size : s->h; }
 inline vs_yuv_fill yuv_pad_fill(const vs_stab* s) { return s->pad_fill_given ? s->pad_fill : yuv_video_black(*s->pf); }
 inline vs_yuv_fill yuv_fade_fill(const vs_stab* s) { return s->yfade_fill_given ? s->yfade_fill : yuv_video_black(*s->pf); }
 
@@ -302,36 +298,42 @@ inline void fill_lk_levels(const vs_stab* s, int pv, int c, LKLevel* L) {
     }
 }
 
-// NV12 / P010: where the interleaved UV plane of a queued frame / of an output surface starts
-inline size_t src_uv(const vs_stab* s) { return (s->zero_copy && s->in.uv_off) ? s->in.uv_off : (size_t)s->h * s->src_pitch; }
-inline size_t dst_uv(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
-    return (d_out != s->d_out && s->out.uv_off) ? s->out.uv_off : (size_t)res_h(s) * out_stride;   // s->d_out: staging of the host entry points
+// ---- the surfaces of a YUV stream as plane lists (planar_layout.h): the ONE place that says where their planes lie
+// A queued frame.  The queue ring holds the packed default layout; the caller's layout (vs_stab_set_nv12_layout,
+// vs_stab_set_i420_layout) applies to zero-copy input.
+inline Planes queued_planes(const vs_stab* s) { return planes(*s->pf, s->w, s->h, s->src_pitch, s->zero_copy ? s->in : ChromaLayout()); }
+// A scratch surface (crop-and-zoom: the frame's size; border pad and fade: the padded size), and surface `idx`
+inline Planes scratch_planes(const vs_stab* s) { const BorderPlan bp = border_plan(s); return planes(*s->pf, bp.pw, bp.ph, s->scratch_pitch); }
+inline uint8_t* scratch(const vs_stab* s, int idx) { return s->d_padB + (size_t)idx * s->pad_frame_bytes; }
+// A result: a device surface in the caller's output layout, or the staging of the host entry points (s->d_out), which holds the
+// packed default layout.  The padded size, and offsets counted from it, where the result is padded.
+inline Planes result_planes(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
+    const bool pad = yuv_padded(s);
+    return planes(*s->pf, pad ? border_plan(s).pw : s->w, pad ? border_plan(s).ph : s->h, out_stride, d_out != s->d_out ? s->out : ChromaLayout());
+}
+// What the warp of a YUV stream reads (the padded scratch surface, or the queued frame) and fills (the scratch surface whose crop
+// is zoomed into the result, or the result)
+inline Planes warp_src_planes(const vs_stab* s) { return yuv_padded(s) ? scratch_planes(s) : queued_planes(s); }
+inline Planes warp_dst_planes(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
+    return yuv_cz_on(s) ? scratch_planes(s) : result_planes(s, d_out, out_stride);
 }
 
-// The three-plane formats (I420 ... I412): Y, then U and V planes of (w >> sx) x (h >> sy) samples with a pitch of their own;
-// offsets and pitches in bytes whatever the sample.  c: the caller's layout, or ChromaLayout() for the packed default.
-inline I420Layout fmt_i420_layout(const PixFmt& f, size_t pitch, int h, const ChromaLayout& c = ChromaLayout()) {
-    return i420_layout(pitch, h, c.u_off, c.v_off, c.c_pitch, f.sx, f.sy);
-}
-// ... where the planes of a queued frame / of an output surface lie.  The queue ring and the staging of the host entry points hold
-// the packed default layout; the caller's layout (vs_stab_set_i420_layout) applies to zero-copy input and to device outputs.
-inline I420Layout src_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s->src_pitch, s->h, s->zero_copy ? s->in : ChromaLayout()); }
-inline I420Layout dst_i420(const vs_stab* s, const uint8_t* d_out, size_t out_stride) {
-    return fmt_i420_layout(*s->pf, out_stride, res_h(s), d_out != s->d_out ? s->out : ChromaLayout());
+// The warp of n <= WARP_BATCH_MAX YUV surfaces (planes S, at the size of S's luma) into surfaces with planes D, one launch: luma
+// and the interleaved chroma plane - half size, two channels, the map with the halved translation (m + 6) -, or Y, U and V,
+// whose one chroma table serves both U and V.
+inline int warp_yuv(const uint8_t* const* srcs, uint8_t* const* dsts, int n, const Planes& S, const Planes& D, WarpMaps maps, int border, WarpTabs tabs,
+                    hipStream_t st) {
+    if (S.n == 3)
+        return launch_warp_i420(srcs, dsts, n, S.i420(), D.i420(), S[0].w, S[0].h, maps, border, tabs, st, S.sample_bytes, S[1].sx, S[1].sy);
+    const uint8_t* us[WARP_BATCH_MAX];
+    uint8_t* ud[WARP_BATCH_MAX];
+    for (int i = 0; i < n; i++) { us[i] = srcs[i] + S[1].off; ud[i] = dsts[i] + D[1].off; }
+    return launch_warp_nv12(srcs, dsts, us, ud, n, S[0].pitch, D[0].pitch, S[0].w, S[0].h, maps, border, tabs, st, S.sample_bytes);
 }
 
-// The scratch surfaces of crop-and-zoom on a YUV stream: where the chroma of one lies, and surface `idx`
-inline size_t cz_uv(const vs_stab* s) { return (size_t)s->h * s->cz_pitch; }
-inline I420Layout cz_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s->cz_pitch, s->h); }
-inline uint8_t* cz_scratch(const vs_stab* s, int idx) { return s->d_padB + (size_t)idx * s->pad_frame_bytes; }
 // The zoom of n warped scratch surfaces into their results (device surfaces in the caller's output layout, or the staging of the
 // host entry points): ONE k_cropzoom launch over all their planes (stabilizer.cpp)
 int cz_launch(const vs_stab* s, const uint8_t* const* scratch, uint8_t* const* outs, int n, size_t out_stride, hipStream_t st);
-
-// The scratch surfaces of border pad on a YUV stream: where the chroma of one lies, and surface `idx`
-inline size_t pad_uv(const vs_stab* s) { return (size_t)res_h(s) * s->pad_pitch; }
-inline I420Layout pad_i420(const vs_stab* s) { return fmt_i420_layout(*s->pf, s->pad_pitch, res_h(s)); }
-inline uint8_t* pad_scratch(const vs_stab* s, int idx) { return s->d_padB + (size_t)idx * s->pad_frame_bytes; }
 // The pad of n frames (in the stream's input layout) into their scratch surfaces: ONE k_yuvpad launch over all their planes (stabilizer.cpp)
 int pad_launch(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, hipStream_t st);
 // ... the same with the border mode and the fill given (the first history of the fade border: VS_BORDER_BLACK with the fade's fill)

@@ -43,6 +43,10 @@ namespace {
 // A refusal of the rules (pixfmt.h) becomes the stream's error.
 #define VS_REFUSE(s, expr) do { const Refusal r_ = (expr); if (r_.rc != VS_OK) return vs_obj_fail((s), r_.rc, r_.text); } while (0)
 
+// A stream of a vs_batch is driven by its group (which sets group_call around the vs_stab_* calls it makes on a member).
+#define VS_CALLER_DRIVES(s) do { if ((s)->member && !(s)->group_call) return vs_obj_fail((s), VS_ERR_INVALID_ARG, \
+    "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)"); } while (0)
+
 int flush_warps(vs_stab* s);
 
 // Batch mode: everything queued so far is analysed and its warps are issued (nothing stays deferred).
@@ -74,8 +78,7 @@ void free_all(vs_stab* s) {
     if (s->d_tmp) (void)hipFree(s->d_tmp);
     if (s->d_padB) (void)hipFree(s->d_padB);
     s->d_padB = nullptr;
-    s->cz_pitch = 0;
-    s->pad_pitch = 0;
+    s->scratch_pitch = 0;
     if (s->own) {                       // the private schedule goes with the buffers it was sized for
         group_delete(s->own);
         s->own = nullptr; s->group = nullptr;
@@ -102,26 +105,16 @@ void analysis_size(const vs_stab* s, int w, int h, int* aw, int* ah) {
 
 int allocate_buffers(vs_stab* s, int w, int h, int fmt);
 
-// The scratch surfaces of crop-and-zoom on a YUV stream (only with the mode on): the packed default layout at a pitch of whole
-// 256-byte lines, which keeps the warps' aligned stores whatever w is; one per frame of a batch, and one for the per-frame path
+// The scratch surfaces of a YUV stream (only with crop-and-zoom, border pad or the fade border on): the packed default layout of
+// border_plan's size - the frame's for crop-and-zoom, the PADDED one otherwise - at a pitch of whole 256-byte lines (aligned stores
+// and loads for the warps, 16-byte stores for the pad, whatever w is); one per frame of a batch, and one for the per-frame path
 // (the frames a flush hands out while the last step's warps may still run).
-int cz_allocate(vs_stab* s) {
-    s->cz_pitch = (s->row_bytes + 255) & ~(size_t)255;
-    s->pad_frame_bytes = s->cz_pitch * (size_t)s->rows_total;
-    s->cz_own = s->batch_active ? s->batch : 0;
-    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * (size_t)(s->cz_own + 1)));
-    return VS_OK;
-}
-
-// The scratch surfaces of border pad on a YUV stream (only with the mode on): the packed default layout of the PADDED size at a
-// pitch of whole 256-byte lines (16-byte stores for the pad, aligned loads for the warps); one per frame of a batch, and one for
-// the per-frame path.
-int pad_allocate(vs_stab* s) {
+int scratch_allocate(vs_stab* s) {
     const BorderPlan bp = border_plan(s);
-    s->pad_pitch = (bp.prow + 255) & ~(size_t)255;
-    s->pad_frame_bytes = s->pad_pitch * (size_t)s->pf->rows(bp.ph);
-    s->pad_own = s->batch_active ? s->batch : 0;
-    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * (size_t)(s->pad_own + 1)));
+    s->scratch_pitch = (bp.prow + 255) & ~(size_t)255;
+    s->pad_frame_bytes = s->scratch_pitch * (size_t)s->pf->rows(bp.ph);
+    s->scratch_own = s->batch_active ? s->batch : 0;
+    VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * (size_t)(s->scratch_own + 1)));
     return VS_OK;
 }
 
@@ -247,10 +240,8 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_out, s->out_bytes));
     s->tmp_bytes = std::max(s->out_bytes, s->frame_bytes);
     VS_OBJ_HIP(s, hipMalloc((void**)&s->d_tmp, s->tmp_bytes + 16));
-    if (yuv_cz_on(s)) {
-        VS_OBJ_TRY(s, cz_allocate(s));
-    } else if (yuv_padded(s)) {
-        VS_OBJ_TRY(s, pad_allocate(s));
+    if (yuv_cz_on(s) || yuv_padded(s)) {
+        VS_OBJ_TRY(s, scratch_allocate(s));
     } else if (s->batch_active && s->p.border_size > 0) {
         s->pad_frame_bytes = (s->tmp_bytes + 255) & ~(size_t)255;
         VS_OBJ_HIP(s, hipMalloc((void**)&s->d_padB, s->pad_frame_bytes * B));
@@ -265,33 +256,21 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
 }
 
 
-// The three planes of a planar frame (I420 / I010 / I012; 4:2:2, 4:4:4) from one layout to another: rows of w samples, and chroma
-// rows of w >> sx samples, h >> sy of them.
-// (w, h: the size of the surface, where it is not the frame's - the padded result of border pad on a YUV stream)
-int copy_i420(vs_stab* s, uint8_t* dst, const I420Layout& dl, const uint8_t* src, const I420Layout& sl, hipMemcpyKind kind, hipStream_t st, int w = 0,
-              int h = 0) {
-    if (!w) { w = s->w; h = s->h; }
-    const size_t cw = s->pf->chroma_row_bytes(w);
-    const int ch = h >> s->pf->sy;
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, dl.pitch, src, sl.pitch, (size_t)w * s->cn, h, kind, st));
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.u, dl.cpitch, src + sl.u, sl.cpitch, cw, ch, kind, st));
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + dl.v, dl.cpitch, src + sl.v, sl.cpitch, cw, ch, kind, st));
+// A surface from one layout to another, one copy per plane (S and D: the planes of one format and size)
+int copy_planes(vs_stab* s, uint8_t* dst, const Planes& D, const uint8_t* src, const Planes& S, hipMemcpyKind kind, hipStream_t st) {
+    for (int k = 0; k < S.n; k++)
+        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + D[k].off, D[k].pitch, src + S[k].off, S[k].pitch, S.row_bytes(k), S[k].h, kind, st));
     return VS_OK;
 }
 
-// The result of a host call from its staging buffer (rows of `orow` bytes, `orows` of them; I420: the packed layout at that pitch)
-// into the caller's frame.  rw x rh: the size of the frame delivered (vs_stab_last_out_dims), which border pad on a YUV stream goes
-// by: a padded result, or the unpadded last frame of a flush with the default offsets of ITS size.
+// The result of a host call from its staging buffer (rows of `orow` bytes, `orows` of them; three planes: the packed layout at that
+// pitch) into the caller's frame.  rw x rh: the size of the frame delivered (vs_stab_last_out_dims), which a YUV stream goes by: a
+// padded result, or the unpadded last frame of a flush with the default offsets of ITS size.
 int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st, int rw, int rh) {
-    if (yuv_padded(s)) {
-        if (s->pf->three_planes())
-            return copy_i420(s, out, fmt_i420_layout(*s->pf, out_stride, rh), d_src, fmt_i420_layout(*s->pf, orow, rh), hipMemcpyDeviceToHost, st, rw, rh);
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, (size_t)rw * s->cn, s->pf->rows(rh), hipMemcpyDeviceToHost, st));
-        return VS_OK;
-    }
     if (s->pf->three_planes())
-        return copy_i420(s, out, fmt_i420_layout(*s->pf, out_stride, s->h), d_src, fmt_i420_layout(*s->pf, orow, s->h), hipMemcpyDeviceToHost, st);
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, orow, orows, hipMemcpyDeviceToHost, st));
+        return copy_planes(s, out, planes(*s->pf, rw, rh, out_stride), d_src, planes(*s->pf, rw, rh, orow), hipMemcpyDeviceToHost, st);
+    const bool pad = yuv_padded(s);     // (luma and UV plane lie behind each other: one copy)
+    VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, pad ? (size_t)rw * s->cn : orow, pad ? s->pf->rows(rh) : orows, hipMemcpyDeviceToHost, st));
     return VS_OK;
 }
 
@@ -300,20 +279,11 @@ int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMem
     if (s->slot_valid[slot]) VS_OBJ_HIP(s, hipStreamWaitEvent(s->st_pre, s->ev_slot[slot], 0));
     StageScope t(s, VS_STAGE_COPY_IN, s->st_pre);
     uint8_t* dst = s->d_ring + (size_t)slot * s->frame_bytes;
-    if (s->pf->luma_uv() && kind == hipMemcpyDeviceToDevice && s->in.uv_off) {      // decoder surface: planes apart
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->h, kind, s->st_pre));
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + (size_t)s->h * s->row_bytes, s->row_bytes, (const uint8_t*)src + s->in.uv_off, stride,
-                                  s->row_bytes, s->h / 2, kind, s->st_pre));
-        return VS_OK;
-    }
-    if (s->pf->three_planes()) {
-        // three planes into the slot's packed layout: from the caller's layout (device surfaces) or the packed default at the
-        // caller's pitch (host frames)
-        const I420Layout in = fmt_i420_layout(*s->pf, stride, s->h, kind == hipMemcpyDeviceToDevice ? s->in : ChromaLayout());
-        const I420Layout q = fmt_i420_layout(*s->pf, s->row_bytes, s->h);
-        VS_OBJ_TRY(s, copy_i420(s, dst, q, (const uint8_t*)src, in, kind, s->st_pre));
-        return VS_OK;
-    }
+    // plane by plane into the slot's packed layout: three planes, from the caller's layout (device surfaces) or the packed default
+    // at the caller's pitch (host frames), and a decoder's NV12 / P010 surface whose planes lie apart; anything else is ONE copy
+    const ChromaLayout in = kind == hipMemcpyDeviceToDevice ? s->in : ChromaLayout();
+    if (s->pf->three_planes() || (s->pf->luma_uv() && in.uv_off))
+        return copy_planes(s, dst, planes(*s->pf, s->w, s->h, s->row_bytes), (const uint8_t*)src, planes(*s->pf, s->w, s->h, stride, in), kind, s->st_pre);
     VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->rows_total, kind, s->st_pre));
     return VS_OK;
 }
@@ -463,7 +433,6 @@ int warp_frame(const vs_stab* s, const uint8_t* src, size_t sstride, int w, int 
 // (:917-926; also after a change of geometry or format, and after vs_stab_set_yuv_fade), alpha ramps with the count (:953-961), and
 // ONE k_yuvfade launch pads the planes of `frame` and blends them with the history into the scratch surface `psrc`.
 int yuv_fade_blend(vs_stab* s, const uint8_t* frame, uint8_t* psrc, hipStream_t st) {
-    const PixFmt& f = *s->pf;
     const vs_params_c& p = s->p;
     const int b = p.border_size, w = s->w, h = s->h;
     if (!s->d_yfade || s->yfade_w != w || s->yfade_h != h || s->yfade_b != b || s->yfade_fmt != s->fmt) {
@@ -481,38 +450,22 @@ int yuv_fade_blend(vs_stab* s, const uint8_t* frame, uint8_t* psrc, hipStream_t 
         alpha = alpha * (static_cast<float>(s->yfade_count) / p.fade_duration);
         s->yfade_count++;
     }
+    const Planes S = queued_planes(s), D = scratch_planes(s);       // (the history has the scratch surface's planes)
     vs_fade_job jobs[3];
-    int nj = 0;
-    auto add = [&](const uint8_t* src, size_t sstride, int pw, int ph, size_t off, size_t dstride, int bx, int by, int cn, uint16_t f0, uint16_t f1) {
-        jobs[nj++] = vs_fade_job{src, sstride, pw, ph, s->d_yfade + off, dstride, psrc + off, dstride, bx, by, {f0, f1}, cn, 0};
-    };
-    add(frame, s->src_pitch, w, h, 0, s->pad_pitch, b, b, 1, c.y, 0);
-    if (f.luma_uv()) {
-        add(frame + src_uv(s), s->src_pitch, w / 2, h / 2, pad_uv(s), s->pad_pitch, b >> 1, b >> 1, 2, c.u, c.v);
-    } else {
-        const I420Layout L = src_i420(s), D = pad_i420(s);
-        add(frame + L.u, L.cpitch, w >> f.sx, h >> f.sy, D.u, D.cpitch, b >> f.sx, b >> f.sy, 1, c.u, 0);
-        add(frame + L.v, L.cpitch, w >> f.sx, h >> f.sy, D.v, D.cpitch, b >> f.sx, b >> f.sy, 1, c.v, 0);
-    }
-    VS_OBJ_TRY(s, launch_yuvfade_blend(jobs, nj, f.sample_bytes, alpha, 1.0f - alpha, st));
+    for (int k = 0; k < S.n; k++)
+        jobs[k] = vs_fade_job{frame + S[k].off, S[k].pitch, S[k].w, S[k].h, s->d_yfade + D[k].off, D[k].pitch, psrc + D[k].off, D[k].pitch,
+                              b >> S[k].sx, b >> S[k].sy, {plane_fill(c, S, k, 0), plane_fill(c, S, k, 1)}, S[k].cn, 0};
+    VS_OBJ_TRY(s, launch_yuvfade_blend(jobs, S.n, S.sample_bytes, alpha, 1.0f - alpha, st));
     return VS_OK;
 }
 
 // ... and behind it (:1086-1100 per plane): ONE launch folds the planes of the result, read through the output layout, into the history
 int yuv_fade_update(vs_stab* s, const uint8_t* d_out, size_t out_stride, hipStream_t st) {
-    const PixFmt& f = *s->pf;
-    const BorderPlan bp = border_plan(s);
+    const Planes H = scratch_planes(s), D = result_planes(s, d_out, out_stride);
     vs_fade_update_job jobs[3];
-    int nj = 0;
-    jobs[nj++] = vs_fade_update_job{s->d_yfade, s->pad_pitch, d_out, out_stride, bp.pw, bp.ph, 1, 0};
-    if (f.luma_uv()) {
-        jobs[nj++] = vs_fade_update_job{s->d_yfade + pad_uv(s), s->pad_pitch, d_out + dst_uv(s, d_out, out_stride), out_stride, bp.pw / 2, bp.ph / 2, 2, 0};
-    } else {
-        const I420Layout H = pad_i420(s), D = dst_i420(s, d_out, out_stride);
-        jobs[nj++] = vs_fade_update_job{s->d_yfade + H.u, H.cpitch, d_out + D.u, D.cpitch, bp.pw >> f.sx, bp.ph >> f.sy, 1, 0};
-        jobs[nj++] = vs_fade_update_job{s->d_yfade + H.v, H.cpitch, d_out + D.v, D.cpitch, bp.pw >> f.sx, bp.ph >> f.sy, 1, 0};
-    }
-    VS_OBJ_TRY(s, launch_yuvfade_update(jobs, nj, f.sample_bytes, st));
+    for (int k = 0; k < H.n; k++)
+        jobs[k] = vs_fade_update_job{s->d_yfade + H[k].off, H[k].pitch, d_out + D[k].off, D[k].pitch, H[k].w, H[k].h, H[k].cn, 0};
+    VS_OBJ_TRY(s, launch_yuvfade_update(jobs, H.n, H.sample_bytes, st));
     return VS_OK;
 }
 
@@ -546,57 +499,32 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         const bool ypad = yuv_padded(s);
         if (!ypad && (ow != s->w || oh != s->h))
             VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
-        if (s->pf->three_planes())
-            VS_OBJ_TRY(s, copy_i420(s, d_out, ypad ? fmt_i420_layout(*s->pf, out_stride, s->h) : dst_i420(s, d_out, out_stride), frame, src_i420(s),
-                                    hipMemcpyDeviceToDevice, st));
-        else
-            VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out, out_stride, frame, s->src_pitch, s->row_bytes, s->h, hipMemcpyDeviceToDevice, st));
-        if (s->pf->luma_uv())
-            VS_OBJ_HIP(s, hipMemcpy2DAsync(d_out + (ypad ? (size_t)s->h * out_stride : dst_uv(s, d_out, out_stride)), out_stride, frame + src_uv(s),
-                                      s->src_pitch, s->row_bytes, s->h / 2, hipMemcpyDeviceToDevice, st));
+        VS_OBJ_TRY(s, copy_planes(s, d_out, ypad ? planes(*s->pf, s->w, s->h, out_stride) : result_planes(s, d_out, out_stride), frame, queued_planes(s),
+                                  hipMemcpyDeviceToDevice, st));
         s->last_out_w = s->w; s->last_out_h = s->h;
     } else if (canvas_on(s)) {                                                        // :1130-1134
         // the canvas replaces the warped frame, so the warp (and a fade history behind it) cannot be observed and is not run
         if (!s->canvas && !(s->canvas = canvas_new())) return vs_obj_fail(s, VS_ERR_HIP, "out of host memory");
         StageScope t(s, VS_STAGE_WARP, st);
         rc = canvas_apply(s->canvas, p, frame, s->src_pitch, s->w, s->h, s->d_ct, s->d_traj, d_out, out_stride, st);
-    } else if (s->pf->luma_uv()) {
+    } else if (s->pf->kind != PIX_INTERLEAVED) {
         StageScope t(s, VS_STAGE_WARP, st);
         // crop-and-zoom: the warp goes into the stream's scratch surface, whose crops one launch resizes into d_out
-        const bool cz = yuv_cz_on(s);
-        uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
-        // border pad: one launch pads both planes into the stream's scratch surface, which is warped at the padded size, taps
+        // border pad: one launch pads the planes into the stream's scratch surface, which is warped at the padded size, taps
         // outside it taking its edge (the border)
-        // fade: one launch pads both planes and blends them with the history into that surface; one more, behind the warp, folds
+        // fade: one launch pads the planes and blends them with the history into that surface; one more, behind the warp, folds
         // the result into the history
-        const bool fade = yuv_fade_on(s), pad = yuv_padded(s);
-        uint8_t* psrc = pad ? pad_scratch(s, s->pad_own) : nullptr;
-        if (fade) rc = yuv_fade_blend(s, frame, psrc, st);
-        else if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
-        const uint8_t* wsrc = pad ? psrc : frame;
-        const uint8_t* uv = pad ? psrc + pad_uv(s) : frame + src_uv(s);
-        uint8_t* out_uv = wdst + (cz ? cz_uv(s) : dst_uv(s, d_out, out_stride));
-        // (a P010 surface goes through the one-launch kernel even on its own: its tables are built in the stream's scratch)
+        const bool cz = yuv_cz_on(s), fade = yuv_fade_on(s), pad = yuv_padded(s);
+        uint8_t* scr = cz || pad ? scratch(s, s->scratch_own) : nullptr;
+        if (fade) rc = yuv_fade_blend(s, frame, scr, st);
+        else if (pad) rc = pad_launch(s, &frame, &scr, 1, st);
+        const uint8_t* wsrc = pad ? scr : frame;
+        uint8_t* wdst = cz ? scr : d_out;
+        // (P010 and the three-plane formats go through the one-launch kernel even for one surface: its tables are built in the
+        // stream's scratch)
         if (rc == VS_OK)
-            rc = launch_warp_nv12(&wsrc, &wdst, &uv, &out_uv, 1, pad ? s->pad_pitch : s->src_pitch, cz ? s->cz_pitch : out_stride, bp.pw, bp.ph,
-                                  WarpMaps{s->d_Minv, 12, false}, pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK,
-                                  s->fmt == VS_FMT_P010 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}, st, s->pf->sample_bytes);
-        if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
-        if (fade && rc == VS_OK) rc = yuv_fade_update(s, d_out, out_stride, st);
-    } else if (s->pf->three_planes()) {
-        // (all three planes in one launch, even for one surface: its tables are built in the stream's scratch)
-        StageScope t(s, VS_STAGE_WARP, st);
-        const bool cz = yuv_cz_on(s);
-        uint8_t* wdst = cz ? cz_scratch(s, s->cz_own) : d_out;
-        const bool fade = yuv_fade_on(s), pad = yuv_padded(s);      // (as above: pad, or pad and blend, into the scratch surface, warp that)
-        uint8_t* psrc = pad ? pad_scratch(s, s->pad_own) : nullptr;
-        if (fade) rc = yuv_fade_blend(s, frame, psrc, st);
-        else if (pad) rc = pad_launch(s, &frame, &psrc, 1, st);
-        const uint8_t* wsrc = pad ? psrc : frame;
-        if (rc == VS_OK)
-            rc = launch_warp_i420(&wsrc, &wdst, 1, pad ? pad_i420(s) : src_i420(s), cz ? cz_i420(s) : dst_i420(s, d_out, out_stride), bp.pw, bp.ph,
-                                  WarpMaps{s->d_Minv, 12, false}, pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, st,
-                                  s->pf->sample_bytes, s->pf->sx, s->pf->sy);
+            rc = warp_yuv(&wsrc, &wdst, 1, warp_src_planes(s), warp_dst_planes(s, d_out, out_stride), WarpMaps{s->d_Minv, 12, false},
+                          pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK, s->fmt == VS_FMT_NV12 ? WarpTabs{} : WarpTabs{WarpTabs::SCRATCH}, st);
         if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
         if (fade && rc == VS_OK) rc = yuv_fade_update(s, d_out, out_stride, st);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
@@ -829,48 +757,33 @@ int vsd::pad_launch(const vs_stab* s, const uint8_t* const* frames, uint8_t* con
 }
 
 int vsd::pad_planes(const vs_stab* s, const uint8_t* const* frames, uint8_t* const* scratch, int n, int border, const vs_yuv_fill& c, hipStream_t st) {
-    const PixFmt& f = *s->pf;
-    const int b = s->p.border_size, w = s->w, h = s->h;
+    const Planes S = queued_planes(s), D = scratch_planes(s);
+    const int b = s->p.border_size;
     vs_pad_job jobs[YP_MAX_JOBS];
     int nj = 0;
-    auto add = [&](const uint8_t* src, size_t sstride, int pw, int ph, uint8_t* dst, size_t dstride, int bx, int by, int cn, uint16_t f0, uint16_t f1) {
-        jobs[nj++] = vs_pad_job{src, sstride, pw, ph, dst, dstride, bx, by, cn, border, {f0, f1}, 0};
-    };
-    for (int i = 0; i < n; i++) {
-        add(frames[i], s->src_pitch, w, h, scratch[i], s->pad_pitch, b, b, 1, c.y, 0);
-        if (f.luma_uv()) {
-            add(frames[i] + src_uv(s), s->src_pitch, w / 2, h / 2, scratch[i] + pad_uv(s), s->pad_pitch, b >> 1, b >> 1, 2, c.u, c.v);
-            continue;
-        }
-        const I420Layout L = src_i420(s), D = pad_i420(s);
-        add(frames[i] + L.u, L.cpitch, w >> f.sx, h >> f.sy, scratch[i] + D.u, D.cpitch, b >> f.sx, b >> f.sy, 1, c.u, 0);
-        add(frames[i] + L.v, L.cpitch, w >> f.sx, h >> f.sy, scratch[i] + D.v, D.cpitch, b >> f.sx, b >> f.sy, 1, c.v, 0);
-    }
-    return launch_yuvpad(jobs, nj, f.sample_bytes, st);
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < S.n; k++)
+            jobs[nj++] = vs_pad_job{frames[i] + S[k].off, S[k].pitch, S[k].w, S[k].h, scratch[i] + D[k].off, D[k].pitch, b >> S[k].sx, b >> S[k].sy,
+                                    S[k].cn, border, {plane_fill(c, S, k, 0), plane_fill(c, S, k, 1)}, 0};
+    return launch_yuvpad(jobs, nj, S.sample_bytes, st);
 }
 
 int vsd::cz_launch(const vs_stab* s, const uint8_t* const* scratch, uint8_t* const* outs, int n, size_t out_stride, hipStream_t st) {
-    const PixFmt& f = *s->pf;
-    const int b = s->p.border_size, sb = f.sample_bytes, w = s->w, h = s->h;
+    const Planes S = scratch_planes(s);
+    const int b = s->p.border_size;
     vs_scale_job jobs[CZ_MAX_JOBS];
     int nj = 0;
-    // one plane: its crop (x, y, cw, ch) in the scratch surface -> the pw x ph plane of the result
-    auto add = [&](const uint8_t* src, size_t sstride, int x, int y, int cw, int ch, uint8_t* dst, size_t dstride, int pw, int ph, int cn) {
-        jobs[nj++] = vs_scale_job{src + (size_t)y * sstride + (size_t)x * cn * sb, sstride, cw, ch, dst, dstride, pw, ph, cn, 0};
-    };
     for (int i = 0; i < n; i++) {
-        add(scratch[i], s->cz_pitch, b, b, w - 2 * b, h - 2 * b, outs[i], out_stride, w, h, 1);
-        if (f.luma_uv()) {
-            add(scratch[i] + cz_uv(s), s->cz_pitch, b >> 1, b >> 1, (w - 2 * b) >> 1, (h - 2 * b) >> 1, outs[i] + dst_uv(s, outs[i], out_stride), out_stride,
-                w / 2, h / 2, 2);
-            continue;
+        const Planes D = result_planes(s, outs[i], out_stride);
+        // one plane: its crop - the luma crop (b, b, w - 2b, h - 2b) shifted by (sx, sy) - in the scratch surface -> the plane of the result
+        for (int k = 0; k < S.n; k++) {
+            const Plane& p = S[k];
+            const size_t crop = (size_t)(b >> p.sy) * p.pitch + (size_t)(b >> p.sx) * p.cn * S.sample_bytes;
+            jobs[nj++] = vs_scale_job{scratch[i] + p.off + crop, p.pitch, (s->w - 2 * b) >> p.sx, (s->h - 2 * b) >> p.sy, outs[i] + D[k].off, D[k].pitch,
+                                      D[k].w, D[k].h, p.cn, 0};
         }
-        const I420Layout L = cz_i420(s), D = dst_i420(s, outs[i], out_stride);
-        for (int k = 0; k < 2; k++)
-            add(scratch[i] + (k ? L.v : L.u), L.cpitch, b >> f.sx, b >> f.sy, (w - 2 * b) >> f.sx, (h - 2 * b) >> f.sy, outs[i] + (k ? D.v : D.u), D.cpitch,
-                w >> f.sx, h >> f.sy, 1);
     }
-    return launch_cropzoom(jobs, nj, sb, st);
+    return launch_cropzoom(jobs, nj, S.sample_bytes, st);
 }
 
 void vsd::fill_traj_params(const vs_params_c& p, TrajParams& t) {
@@ -1000,7 +913,7 @@ void vs_stab_destroy(vs_stab* s) {
 
 int vs_stab_clean(vs_stab* s) {   // Stabilizer.cpp:221-256
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (s->own && group_failure(s->own).rc != VS_OK) wait_streams(s);     // (a failed private group is not drained: it goes)
     else VS_OBJ_TRY(s, sync_all(s));
     free_all(s);
@@ -1021,7 +934,7 @@ int vs_stab_out_size(const vs_stab* s, int w, int h, int* out_w, int* out_h) {
 int vs_stab_push_dev(vs_stab* s, const void* d_data, int w, int h, size_t stride, int fmt, void* d_out,
                      size_t out_stride, int* produced) {
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     *produced = 0;
     if (!d_data) return VS_OK;   // empty frame -> empty result (Stabilizer.cpp:263-265)
     int rc = prepare(s, w, h, fmt, stride);
@@ -1075,7 +988,7 @@ static int flush_dev_impl(vs_stab* s, void* d_out, size_t out_stride, int* produ
 
 int vs_stab_flush_dev(vs_stab* s, void* d_out, size_t out_stride, int* produced) {   // Stabilizer.cpp:394-400
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     return flush_dev_impl(s, d_out, out_stride, produced, true);
 }
 
@@ -1157,7 +1070,7 @@ static int push_host_pipelined(vs_stab* s, const uint8_t* data, int w, int h, si
 int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, int fmt, uint8_t* out,
                  size_t out_stride, int* produced) {
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     *produced = 0;
     if (!data) return VS_OK;
     int rc = prepare(s, w, h, fmt, stride);
@@ -1203,7 +1116,7 @@ int vs_stab_push(vs_stab* s, const uint8_t* data, int w, int h, size_t stride, i
 
 int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
     if (!s || !produced) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     *produced = 0;
     if (!s->allocated) return VS_OK;
     if (s->hold_valid) {      // host pipeline: the frame the last push computed
@@ -1241,7 +1154,7 @@ int vs_stab_flush(vs_stab* s, uint8_t* out, size_t out_stride, int* produced) {
 // consecutive calls overlap each other and the device work.  To be chosen while no frame is queued.
 int vs_stab_set_host_pipeline(vs_stab* s, int enable) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (!s->q_slot.empty() || s->hold_valid) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_host_pipeline: the frame queue must be empty");
     s->host_pipe = enable != 0;
     return VS_OK;
@@ -1251,7 +1164,7 @@ int vs_stab_set_host_pipeline(vs_stab* s, int enable) {
 // launch.  A result is complete after vs_stab_sync(); every push must then be given its own d_out.
 int vs_stab_set_warp_batch(vs_stab* s, int frames) {
     if (!s || frames < 1 || frames > WARP_BATCH_MAX) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (s->allocated) { VS_OBJ_HIP(s, hipSetDevice(s->device)); VS_OBJ_TRY(s, flush_warps(s)); }
     s->warp_batch = frames;
     return VS_OK;
@@ -1262,7 +1175,7 @@ int vs_stab_set_warp_batch(vs_stab* s, int frames) {
 // vs_stab_set_warp_batch(frames)).  To be chosen before the first frame (or after vs_stab_clean).
 int vs_stab_set_batch(vs_stab* s, int frames) {
     if (!s || frames < 1 || frames > BATCH_MAX) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (s->allocated) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_batch: call before the first frame or after vs_stab_clean");
     s->batch = frames;
     if (frames > 1) s->warp_batch = std::min(frames, WARP_BATCH_MAX);
@@ -1275,7 +1188,7 @@ int vs_stab_set_batch(vs_stab* s, int frames) {
 // the batch depth and a vs_stab_sync, or until vs_stab_flush_dev has drained the queue.  Tightly packed frames.
 int vs_stab_set_zero_copy(vs_stab* s, int enable) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_zero_copy: the frame queue must be empty");
     s->zero_copy = enable != 0;
     s->src_pitch = s->row_bytes;
@@ -1286,7 +1199,7 @@ int vs_stab_set_zero_copy(vs_stab* s, int enable) {
 // UV plane with a common pitch, the UV plane `uv_offset` bytes behind the Y pointer.  0 = contiguous (h * pitch).
 int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offset) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_nv12_layout: the frame queue must be empty");
     if (s->allocated) VS_REFUSE(s, check_set_nv12_layout(*s->pf, in_uv_offset, out_uv_offset));
     s->in.uv_off = in_uv_offset;
@@ -1298,7 +1211,7 @@ int vs_stab_set_nv12_layout(vs_stab* s, size_t in_uv_offset, size_t out_uv_offse
 // for the frames pushed (`in`: zero-copy and copy-in alike) and for the surfaces filled (`out`).  0 = the packed default per field.
 int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t in_c_pitch, size_t out_u_off, size_t out_v_off, size_t out_c_pitch) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_i420_layout: the frame queue must be empty");
     ChromaLayout in = s->in, out = s->out;       // (the NV12 offsets are the other setter's)
     in.u_off = in_u_off; in.v_off = in_v_off; in.c_pitch = in_c_pitch;
@@ -1313,7 +1226,7 @@ int vs_stab_set_i420_layout(vs_stab* s, size_t in_u_off, size_t in_v_off, size_t
 // without it such a stream is refused as ever.
 int vs_stab_set_yuv_crop_zoom(vs_stab* s, int enable) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_crop_zoom: the frame queue must be empty");
     s->yuv_cz = enable != 0;
     return VS_OK;
@@ -1325,7 +1238,7 @@ int vs_stab_set_yuv_crop_zoom(vs_stab* s, int enable) {
 // fill: the colour VS_BORDER_BLACK writes; NULL: the format's video black.
 int vs_stab_set_yuv_border_pad(vs_stab* s, int enable, const vs_yuv_fill* fill) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_border_pad: the frame queue must be empty");
     if (fill && fill->reserved != 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_border_pad: fill->reserved must be 0");
     if (enable && fill && s->allocated && s->pf->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*s->pf, *fill));
@@ -1343,7 +1256,7 @@ int vs_stab_set_yuv_border_pad(vs_stab* s, int enable, const vs_yuv_fill* fill) 
 // the history: the next padded frame is the history, count 0.
 int vs_stab_set_yuv_fade(vs_stab* s, int enable, const vs_yuv_fill* fill) {
     if (!s) return VS_ERR_INVALID_ARG;
-    if (s->member && !s->group_call) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "this stream belongs to a vs_batch: drive it through vs_batch_* (its getters remain available)");
+    VS_CALLER_DRIVES(s);
     if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_fade: the frame queue must be empty");
     if (fill && fill->reserved != 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_fade: fill->reserved must be 0");
     if (enable && fill && s->allocated && s->pf->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*s->pf, *fill, "vs_stab_set_yuv_fade"));
