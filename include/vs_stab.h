@@ -462,7 +462,11 @@ int vs_stab_set_warp_batch(vs_stab* s, int frames);
  * stays per frame, and the warps go out together as with vs_stab_set_warp_batch(frames)
  * (at most 32 frames per warp launch: a batch of 64 is two launches back to back).
  * Results are bit-identical to frames = 1 and complete after vs_stab_sync(); every push must
- * be given its own d_out until then.  Must be chosen before the first frame (or after
+ * be given its own d_out until then.  (The warps of a batch are queued behind the analysis of the
+ * batch after the next one, so that a batch's ordered part runs beside the warps of the batch before
+ * it; up to two batches' warps are pending between syncs, and vs_stab_sync, vs_stab_flush_dev and
+ * vs_stab_clean issue all of them, oldest first.  With frames copied in - zero-copy off - a stream
+ * holds up to 35 + 3 x frames of them: its queue ring has 160 slots, 256 for frames > 32.)  Must be chosen before the first frame (or after
  * vs_stab_clean).  BGR8, GRAY8, NV12, P010, I420 and I010 / I012 frames; border padding and crop-and-zoom (BGR8;
  * crop-and-zoom also on YUV streams that opted in, vs_stab_set_yuv_crop_zoom) run batched too; the "fade" border, the virtual canvas and
  * adaptive smoothing keep the per-frame path (each of their outputs depends on the one
@@ -473,9 +477,9 @@ int vs_stab_set_batch(vs_stab* s, int frames);
  * surface pool, resident clip) instead of being copied into the instance's queue - the
  * reference aliases the caller's cv::Mat the same way (Stabilizer.cpp:376).  The buffer
  * must stay valid and unchanged until the result of the same push count has been produced
- * (clamp(smoothingRadius,5,35) further pushes plus twice the batch depth: the warps of a
- * batch are issued with the next one) and vs_stab_sync has returned, or the queue has been
- * drained with vs_stab_flush_dev.  Rows may be padded (decoder pitch); all frames in flight
+ * (clamp(smoothingRadius,5,35) further pushes plus three times the batch depth: the warps of a
+ * batch are issued with the batch after the next one; a vs_stab_sync issues everything that is
+ * pending) and vs_stab_sync has returned, or the queue has been drained with vs_stab_flush_dev.  Rows may be padded (decoder pitch); all frames in flight
  * share one pitch, which may change only while nothing is queued.  The frame queue must be
  * empty when the mode is switched. */
 int vs_stab_set_zero_copy(vs_stab* s, int enable);

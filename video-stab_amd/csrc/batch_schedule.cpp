@@ -12,15 +12,19 @@
 //
 // One step (group_step: its phases in the order they are issued), three streams and the upload stream:
 //   up  :  the step's tables, ONE copy                                            (a step or two ahead of the GPU)
-//   pre :  gray(n, two parts: re-detecting frames first) -> pyramid level(n) x levels -> [warps of the PREVIOUS step]
+//   pre :  gray(n, two parts: re-detecting frames first) -> pyramid level(n) x levels -> [warps of step k - WARP_LAG]
 //   det :  zero -> min_eigen -> nms -> select                 (starts behind the first gray part)
 //   main:  LK(n x 200 waves) -> RANSAC score -> select(n waves) -> ordered tail (1 WG per stream)
 //          -> releases (1 WG per push) -> coordinate tables of this step's warps
-// `main` waits for `pre` - through the event behind the warps of the step before, which `pre` issues once the wide launches of
-// `det` of this step are through - and for `det`: at that point the rest of pre/det of this step is done (it overlapped the
-// tracking and tail of the step before) and its tracking has not started, and `pre` of the next step lies behind these warps -
-// the HBM-bound warp has the GPU to itself (on a stream of its own it overlapped the tracker, which holds ~90 KB of LDS per CU:
-// 3 warp workgroups per CU instead of 8).  DESIGN.md section 5 lists every buffer two streams touch with the event that orders them.
+// `main` waits for `pre` - through the event behind the warps that `pre` issues in this step once the wide launches of `det` of
+// this step are through - and for `det`: at that point the rest of pre/det of this step is done (it overlapped the tracking and
+// tail of the step before) and its tracking has not started, and `pre` of the next step lies behind these warps - the HBM-bound
+// warp has the GPU to itself (on a stream of its own it overlapped the tracker, which holds ~90 KB of LDS per CU: 3 warp
+// workgroups per CU instead of 8).  The warps in that window are those of step k - WARP_LAG (stab_internal.h), not of the step
+// before: with a lag of 1 they waited for the whole chain tracker -> scoring -> selection -> tail -> releases of step k - 1, launches
+// that keep few compute units busy, and that chain plus the hand-over back to `pre` closed the period.  With a lag of 2 their
+// maps and tables are a period old, and the tail chain of step k runs on `main` beside the warps that `pre` issues in step k + 1.
+// DESIGN.md section 5 lists every buffer two streams touch with the event that orders them.
 #include <cstring>
 #include <new>
 
@@ -69,7 +73,15 @@ struct vs_batch {
         std::vector<uint8_t*> dsts;
         std::vector<int> slots, pad_idx;       // pad_idx: which of its owner's scratch frames (border pad / crop-and-zoom)
         std::vector<vs_stab*> owner;
-    } ready, next;          // ready: the step whose tails are queued (its warps go out with the next step); next: the step being built
+    };
+    // The steps whose tails are queued and whose warps are still to come, oldest first (at most WARP_LAG between two steps), and
+    // behind them the record of the step being built: pending(i), building().
+    static constexpr int NRQ = WARP_LAG + 1;
+    Ready rq[NRQ];
+    int rq_head = 0, rq_n = 0;
+    Ready& pending(int i) { return rq[(rq_head + i) % NRQ]; }
+    Ready& building() { return rq[(rq_head + rq_n) % NRQ]; }
+    void pop_pending() { rq_head = (rq_head + 1) % NRQ; rq_n--; }
 
     // ---- which set or event step k uses, and when it comes free: the only places that turn a step number into an index
     // Host images: four sets.  Step k fills its set once blk_event(k - 4), the same event as its own, has passed: the tail of
@@ -87,8 +99,16 @@ struct vs_batch {
     hipEvent_t det_event(int k) const { return ev_bdet[k % 4]; }
     bool& det_valid(int k) { return bdet_valid[k % 4]; }
     // d_MinvB, d_tabs, ev_warp, ev_rel: two sets, taken in turn by the steps that have outputs (pend_set: the next such step's).
-    // A set comes free when the warps that read it have run: ev_warp[set], waited for on `main` in front of the tail.
+    // A set comes free when the warps that read it have run: ev_warp[set], waited for on `main` in front of the tail.  Two are
+    // enough for a lag of 1 or 2: the step that takes a set again is the second step with outputs after the one that filled it, so
+    // at least two steps later, and the warps of step j are issued in step j + WARP_LAG at the latest, in front of that step's
+    // phase on `main` (DESIGN.md section 5 has the argument in full).
+    static_assert(WARP_LAG >= 1 && WARP_LAG <= 2, "d_MinvB / d_tabs / ev_warp / ev_rel: two sets cover a lag of at most two steps");
     void flip_pend_set() { pend_set ^= 1; }
+    // (WARP_LAG itself stands in stab_internal.h, because the stream sizes its pyramid and frame rings from it.)
+    // The warps of a pending step go out in step k once it lies WARP_LAG steps back (every step is numbered, with or without
+    // outputs: a step without due frames does not hold up an older one's warps).
+    bool warps_due(int k) { return rq_n > 0 && pending(0).step <= k - WARP_LAG; }
 
     template <typename F>
     void each_event(F f) {          // creation and destruction visit the same events
@@ -174,8 +194,8 @@ int group_allocate(vs_batch* g) {
     VS_OBJ_HIP(g, hipHostMalloc((void**)&g->h_tables, 4 * ho));
     memset(g->h_tables, 0, 4 * ho);
     VS_OBJ_HIP(g, hipStreamSynchronize(g->st));
-    for (vs_batch::Ready* r : {&g->ready, &g->next}) {
-        r->srcs.assign(cap, nullptr); r->dsts.assign(cap, nullptr); r->slots.assign(cap, -1); r->pad_idx.assign(cap, 0); r->owner.assign(cap, nullptr);
+    for (vs_batch::Ready& r : g->rq) {
+        r.srcs.assign(cap, nullptr); r.dsts.assign(cap, nullptr); r.slots.assign(cap, -1); r.pad_idx.assign(cap, 0); r.owner.assign(cap, nullptr);
     }
     g->allocated = true;
     return VS_OK;
@@ -189,11 +209,10 @@ WarpEnds warp_ends(const vs_stab* o, const uint8_t* frame, uint8_t* d_out, int p
     return bp.pad ? WarpEnds{scratch(o, pad_idx), d_out} : WarpEnds{frame, scratch(o, pad_idx)};
 }
 
-// The warps of the step whose tails were queued last, 32 frames per launch (`what` = VS_WARP_ONLY / VS_WARP_ALL), or only their
+// The warps of one pending step, 32 frames per launch (`what` = VS_WARP_ONLY / VS_WARP_ALL), or only their
 // coordinate tables (VS_WARP_TABLES_ONLY: steps whose release workgroups have not built them - a Kalman stream's releases stay
 // inside its tail workgroup).  The frames' tables lie tab_ints apart in d_tabs[set].
-int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
-    vs_batch::Ready& R = g->ready;
+int group_ready_launches(vs_batch* g, vs_batch::Ready& R, int what, hipStream_t st) {
     const vs_stab* s0 = g->ref;
     const BorderPlan bp = border_plan(s0);
     const bool cz = yuv_cz_on(s0);      // a YUV stream with crop-and-zoom: bp.crop, the scratch surfaces in their own layout
@@ -235,30 +254,38 @@ int group_ready_launches(vs_batch* g, int what, hipStream_t st) {
     return rc;
 }
 
-// The warps of the step in g->ready.  They run on `pre`, behind the gray / pyramid work of the step that issues them and in front of
+// The warps of the oldest pending step.  They run on `pre`, behind the gray / pyramid work of the step that issues them and in front of
 // the next step's: the cycle warps -> gray -> pyramid -> warps that sets the step time is then the order of ONE stream (as launches
 // on `main` with events in both directions - the pyramid's to `main`, the warps' back to `pre` - every period paid two event hand-overs,
 // 2 x 25 us of 545).  Their maps and tables come from the tail on `main`: ev_rel.
 int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
-    vs_batch::Ready& R = g->ready;
-    if (!R.valid) return VS_OK;
+    if (g->rq_n == 0) return VS_OK;
+    vs_batch::Ready& R = g->pending(0);
     hipStream_t st = g->st_pre;
     int rc;
-    // what the warps wait for - the step's maps and tables (ev_rel), the wide launches of the detector (det_done) - is gathered on the
-    // upload stream into ONE event: one packet in front of the warps on `pre` instead of two
+    // what the warps wait for: the step's maps and tables (ev_rel) and the wide launches of the detector (det_done).  With a lag of
+    // 2 ev_rel is a period old and det_done is the one live event: `pre` waits for both itself, det_done last - one hand-over, det ->
+    // pre, on the loop that closes the period (gathered into ev_go as below: 0.464 ms a step instead of 0.454, DESIGN.md section 8
+    // round 28).  With a lag of 1 both are live, and they are gathered on the upload stream into ONE event: one packet in front of
+    // the warps on `pre` instead of two.
     if (g->rel_valid[R.set] || det_done) {
         hipError_t e = hipSuccess;
-        if (det_done) e = hipStreamWaitEvent(g->st_up, det_done, 0);
-        if (e == hipSuccess && g->rel_valid[R.set]) e = hipStreamWaitEvent(g->st_up, g->ev_rel[R.set], 0);
-        if (e == hipSuccess) e = hipEventRecord(g->ev_go, g->st_up);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, g->ev_go, 0);
+        if (WARP_LAG >= 2) {
+            if (g->rel_valid[R.set]) e = hipStreamWaitEvent(st, g->ev_rel[R.set], 0);
+            if (e == hipSuccess && det_done) e = hipStreamWaitEvent(st, det_done, 0);
+        } else {
+            if (det_done) e = hipStreamWaitEvent(g->st_up, det_done, 0);
+            if (e == hipSuccess && g->rel_valid[R.set]) e = hipStreamWaitEvent(g->st_up, g->ev_rel[R.set], 0);
+            if (e == hipSuccess) e = hipEventRecord(g->ev_go, g->st_up);
+            if (e == hipSuccess) e = hipStreamWaitEvent(st, g->ev_go, 0);
+        }
         if (e != hipSuccess) return vs_obj_fail(g, VS_ERR_HIP, "hipStreamWaitEvent failed");
         if (g->rel_valid[R.set]) g->pre_rel_step = std::max(g->pre_rel_step, R.step);
         g->rel_valid[R.set] = false;
     }
     {
         StageScope t(g->ref, VS_STAGE_WARP, st);   // (stage times of a group are booked on its reference member)
-        rc = group_ready_launches(g, R.tabs_built ? VS_WARP_ONLY : VS_WARP_ALL, st);
+        rc = group_ready_launches(g, R, R.tabs_built ? VS_WARP_ONLY : VS_WARP_ALL, st);
     }
     const hipError_t ew = hipEventRecord(g->ev_warp[R.set], st);
     if (ew == hipSuccess) { g->warp_valid[R.set] = true; g->last_warp_set = R.set; }
@@ -269,6 +296,7 @@ int group_launch_ready(vs_batch* g, hipEvent_t det_done = nullptr) {
         if (rc == VS_OK) rc = rrc;
     }
     R.valid = false;
+    g->pop_pending();
     if (rc != VS_OK) g->err = get_last_error();
     return rc;
 }
@@ -292,7 +320,7 @@ struct StepPlan {
 int fill_stream_items(vs_batch* g, vs_stab* s, const vs_batch::HostSet& H, const BorderPlan& bp, int ndue, int first, StepPlan& P) {
     const vs_params_c& p = s->p;
     const int ns = (int)s->bq.size(), dset = g->dev_set(P.k), set = g->pend_set;
-    vs_batch::Ready& R = g->next;           // (g->ready still holds the warps of the step before)
+    vs_batch::Ready& R = g->building();     // (the pending records still hold the warps of the steps before)
     int npad = 0;
     for (int i = 0; i < ns; i++) {
         const int idx = first + i;
@@ -395,15 +423,17 @@ int step_fill_tables(vs_batch* g, const std::vector<vs_stab*>& act, StepPlan& P)
 }
 
 // Phase 2, `up` and `pre`: the table upload, then gray images and pyramids of all frames of the step, one launch per stage and level.
-int step_issue_pre(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan& P) {
+int step_issue_pre(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan& P, bool warps_go) {
     const vs_stab* s0 = g->ref;
     const int k = P.k, n = P.n, dset = g->dev_set(k);
     hipStream_t pre = g->st_pre;
-    if (k >= 2 && g->pre_rel_step < k - 2) {
-        // ring reuse: these pyramid slots were read by the analysis two steps ago (npyr = 2 * batch + 2).  (When that step had
-        // outputs this stream has waited for its tail already, in front of its warps: nothing to wait for.)
-        VS_OBJ_HIP(g, hipStreamWaitEvent(pre, g->blk_event(k - 2), 0));
-        if (g->det_valid(k - 2)) VS_OBJ_HIP(g, hipStreamWaitEvent(pre, g->det_event(k - 2), 0));
+    if (k >= PYR_STEPS && g->pre_rel_step < k - PYR_STEPS) {
+        // ring reuse: these pyramid slots were read by the analysis PYR_STEPS = WARP_LAG + 1 steps ago (batch_pyr_slots).  (When that
+        // step had outputs this stream has waited for its tail already, in front of its warps, which it issued in the step before
+        // this one: nothing to wait for.  The ring holds one step more than the analysis needs so that this stays true with the
+        // warps a step later: a wait for the tail of step k - 2 would be one more packet in front of the gray kernels every step.)
+        VS_OBJ_HIP(g, hipStreamWaitEvent(pre, g->blk_event(k - PYR_STEPS), 0));
+        if (g->det_valid(k - PYR_STEPS)) VS_OBJ_HIP(g, hipStreamWaitEvent(pre, g->det_event(k - PYR_STEPS), 0));
     }
     // (The HBM-bound warps stay alone on the GPU although the host runs steps ahead: they are launches on this stream, behind the
     // pyramid of the step that issues them and in front of the next step's gray kernels - group_launch_ready.  Round 3 had them on
@@ -444,7 +474,7 @@ int step_issue_pre(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan
             VS_OBJ_TRY(g, launch_pyr_level_batch(nullptr, d_pairs + (size_t)(l + 1) * n, n, s0->lw[l], s0->lw[l], s0->lh[l], s0->lw[l + 1], pre));
     }
     // (`main` waits for the event behind this step's warps when there are any: it covers the pyramid, which lies in front of them)
-    if (!g->ready.valid) VS_OBJ_HIP(g, hipEventRecord(g->ev_bpre, pre));
+    if (!warps_go) VS_OBJ_HIP(g, hipEventRecord(g->ev_bpre, pre));
     return VS_OK;
 }
 
@@ -477,8 +507,8 @@ int step_issue_det(vs_batch* g, const StepPlan& P) {
     return VS_OK;
 }
 
-// Phase 5, `main`: tracking and hypothesis scoring of all frames, one launch each, and the ordered tails.  warps_go: the warps of
-// the step before were issued in front of this phase; kd: the step whose detection selected the corners the tracker reads (-1: none
+// Phase 5, `main`: tracking and hypothesis scoring of all frames, one launch each, and the ordered tails.  warps_go: warps of
+// an earlier step were issued in front of this phase; kd: the step whose detection selected the corners the tracker reads (-1: none
 // that `main` has not waited for).
 int step_issue_main(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan& P, bool warps_go, int kd) {
     const vs_stab* s0 = g->ref;
@@ -517,19 +547,19 @@ int step_issue_main(vs_batch* g, const std::vector<vs_stab*>& act, const StepPla
     return VS_OK;
 }
 
-// Phase 6: the step's due frames become g->ready.  Their warps wait for the next step (or a drain); their maps exist once the
-// tail has run, and the coordinate tables are built right behind it.
+// Phase 6: the step's due frames become the newest pending record.  Their warps wait for step k + WARP_LAG (or a drain); their
+// maps exist once the tail has run, and the coordinate tables are built right behind it.
 int step_publish(vs_batch* g, const std::vector<vs_stab*>& act, const StepPlan& P) {
     const int set = g->pend_set;
-    vs_batch::Ready& R = g->next;
+    vs_batch::Ready& R = g->building();
     R.n = P.npend; R.set = set; R.stride = P.pend_stride; R.valid = P.npend > 0; R.tabs_built = P.all_apart != 0; R.step = P.k;
-    std::swap(g->ready, g->next);            // (the previous step's warps have been issued: g->ready was free)
-    if (g->ready.valid) {
+    if (R.valid) {
+        g->rq_n++;                           // (at most WARP_LAG pending now: this step has issued what lay that far back)
         g->flip_pend_set();
-        if (!g->ready.tabs_built) {          // (a Kalman stream in the step: the tables as a launch behind the tail)
+        if (!R.tabs_built) {                 // (a Kalman stream in the step: the tables as a launch behind the tail)
             StageScope t(g->ref, VS_STAGE_WARP_TABLES, g->st);
-            VS_OBJ_TRY(g, group_ready_launches(g, VS_WARP_TABLES_ONLY, g->st));
-            g->ready.tabs_built = true;
+            VS_OBJ_TRY(g, group_ready_launches(g, R, VS_WARP_TABLES_ONLY, g->st));
+            R.tabs_built = true;
         }
         VS_OBJ_HIP(g, hipEventRecord(g->ev_rel[set], g->st));          // maps and tables of this step's warps exist
         g->rel_valid[set] = true;
@@ -551,22 +581,23 @@ int group_step(vs_batch* g, const std::vector<vs_stab*>& act, int n, int max_n, 
     // the host set of step k-4: its tail has run by now unless the host is four steps ahead of the GPU - then it waits here
     if (k >= 4) VS_OBJ_HIP(g, hipEventSynchronize(g->blk_event(k - 4)));
     VS_OBJ_TRY(g, step_fill_tables(g, act, P));
-    VS_OBJ_TRY(g, step_issue_pre(g, act, P));
+    const bool warps_go = g->warps_due(k);
+    VS_OBJ_TRY(g, step_issue_pre(g, act, P, warps_go));
     VS_OBJ_TRY(g, step_issue_det(g, P));
-    // The warps of the PREVIOUS step go out here, on `pre` behind this step's pyramid, once the wide launches of this step's
-    // detection are through: nothing but the corner selection (a workgroup per image) runs beside them.  (A step without a
-    // detection: once the selection of the step before, whose corners the tracker still needs, is through.)
+    // The warps of step k - WARP_LAG go out here, on `pre` behind this step's pyramid, once the wide launches of this step's
+    // detection are through: nothing but the corner selection (a workgroup per image) and, with a lag of 2, the tail chain of
+    // the step before runs beside them.  (A step without a detection: once the selection of the step before, whose corners the
+    // tracker still needs, is through.)  Their maps and tables (ev_rel) are WARP_LAG - 1 periods old.
     const int kd = (g->last_det_batch >= 0 && g->last_det_batch >= k - 1) ? g->last_det_batch : -1;
     const hipEvent_t det_done = kd == k ? g->ev_bnms : (kd >= 0 ? g->det_event(kd) : (hipEvent_t) nullptr);
-    const bool warps_go = g->ready.valid;
-    VS_OBJ_TRY(g, group_launch_ready(g, det_done));
+    while (g->warps_due(k)) VS_OBJ_TRY(g, group_launch_ready(g, det_done));      // (one record per step: one turn, oldest first)
     VS_OBJ_TRY(g, step_issue_main(g, act, P, warps_go, kd));
     return step_publish(g, act, P);
 }
 
 }  // namespace
 
-bool group_holds_warps(const vs_batch* g) { return g && (g->ready.valid || g->next.valid); }
+bool group_holds_warps(const vs_batch* g) { return g && g->rq_n > 0; }
 
 const FirstFailure& group_failure(const vs_batch* g) { return g->failure; }
 
@@ -606,13 +637,14 @@ int group_run(vs_batch* g) {
     return rc;
 }
 
-// Everything the members have queued is analysed and its warps are issued.  (The warps of a step normally go out with the NEXT
-// step, between its detection and its tracking; group_run issues the pending ones itself, so the step before the drained one is
-// covered too.)
+// Everything the members have queued is analysed and its warps are issued.  (The warps of a step normally go out WARP_LAG steps
+// later, between that step's detection and its tracking; group_run issues the ones that are due on its way, and whatever is
+// still pending then - up to WARP_LAG steps - goes out here, oldest first, each step's warps with their own stage scope and ev_warp.)
 int group_drain(vs_batch* g) {
     VS_OBJ_HIP(g, hipSetDevice(g->device));
-    VS_OBJ_TRY(g, group_run(g));                 // (issues the warps of the step before on its way; nothing queued: nothing done)
-    const int rc = group_launch_ready(g);
+    VS_OBJ_TRY(g, group_run(g));                 // (nothing queued: nothing done)
+    int rc = VS_OK;
+    while (g->rq_n > 0 && rc == VS_OK) rc = group_launch_ready(g);
     g->failure.note(rc, g->err);
     return rc;
 }

@@ -17,13 +17,25 @@
 
 namespace vsd {
 
+constexpr int BATCH_MAX = 64;        // frames analysed per launch in batch mode (vs_stab_set_batch)
+// Batch mode: the warps of a step's due frames are issued WARP_LAG steps after the step that analysed them (batch_schedule.cpp;
+// 1: with the next step, in front of its tracker; 2: one step later still, so that a step's tail runs beside the warps of the
+// step before it).  Everything that must outlive a step because of it is sized from this one constant: the Ready records and
+// the warps_due() test of vs_batch, the pyramid ring (batch_pyr_slots) and the frame queue ring (batch_ring_frames).
+constexpr int WARP_LAG = 2;
 constexpr int FRAME_RING = 128;     // <= 35 queued frames (clamp(smoothingRadius,5,35)) + slack so that a
-                                    // slot is reused several frames after the warp that released it; in batch mode
-                                    // also the batch being collected and the one whose warps are still to come
-constexpr int FRAME_RING_MAX = 192; // the same for batches of more than 32 frames (s->ring_frames)
+                                    // slot is reused several frames after the warp that released it
+constexpr int RING_SLACK = 29;
+// Batch mode (copy-in): a frame's slot is released behind its warp.  Held at worst: 35 queued frames + the batch being
+// collected + WARP_LAG steps whose warps are still to come, + the same slack.  Steps of up to 32 frames and of up to 64 (s->ring_frames).
+constexpr int batch_ring_frames(int B) { return 35 + (1 + WARP_LAG) * (B > 32 ? BATCH_MAX : 32) + RING_SLACK; }
+constexpr int FRAME_RING_MAX = batch_ring_frames(BATCH_MAX);
+// Pyramid ring of a batch stream: the slots step k writes were last read by the analysis of step k - (WARP_LAG + 1), whose tail
+// `pre` has waited for in front of the warps it issued in step k - 1 (step_issue_pre); + 2: the previous frame of a step's first.
+constexpr int PYR_STEPS = WARP_LAG + 1;
+constexpr int batch_pyr_slots(int B) { return PYR_STEPS * B + 2; }
 constexpr int MAX_PYR = 8;
 constexpr int NPYR = 3;             // pyramid buffers: frame k writes k%3 while LK(k-1) still reads (k-1)%3,(k-2)%3
-constexpr int BATCH_MAX = 64;        // frames analysed per launch in batch mode (vs_stab_set_batch)
 constexpr int EVR = 4;              // per-frame event ring
 
 struct Pyramid {
@@ -84,7 +96,7 @@ struct vs_stab {
     int dbg_delay_us = 0;           // VS_STAB_DEBUG_DELAY_US: a spin kernel between tracking and RANSAC (ordering tests)
     // analysis images
     uint8_t* d_first_gray = nullptr;     // 480x270 (Stabilizer.cpp:277)
-    std::vector<vsd::Pyramid> pyr;      // ring: NPYR buffers, 2*batch+2 in batch mode
+    std::vector<vsd::Pyramid> pyr;      // ring: NPYR buffers, batch_pyr_slots(batch) in batch mode
     int npyr = vsd::NPYR;
     bool prev_small = false;
     bool have_prev_gray = false;

@@ -158,7 +158,7 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     // (and the virtual canvas: the window offset and the temporal fill are host decisions on each output's correction)
     s->batch_active = s->batch > 1 && !s->p.adaptive_smoothing && !fade && !canvas_on(s);
     const int B = s->batch_active ? s->batch : 1;
-    s->npyr = s->batch_active ? 2 * B + 2 : NPYR;
+    s->npyr = s->batch_active ? batch_pyr_slots(B) : NPYR;
     // keypoint buffers: one per detection, recycled after two batches' worth of detections
     const int nkp = s->batch_active ? B + 4 : 2, ngw = s->batch_active ? B / 2 + 1 : 1;
     s->pyr.assign(s->npyr, Pyramid());
@@ -170,10 +170,10 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
         if (!s->own) return vs_obj_fail(s, VS_ERR_HIP, get_last_error());
         s->group = s->own;
     }
-    // (the frame queue ring - 128 frames, 3.2 GB at 4K BGR8 - is allocated by the first push that copies a frame in: a
+    // (the frame queue ring - 128 frames and more, 3.2 GB at 4K BGR8 - is allocated by the first push that copies a frame in: a
     // stream that only ever hands over device frames in zero-copy mode never needs it)
     s->free_slots.clear();
-    s->ring_frames = (s->batch_active && B > 32) ? FRAME_RING_MAX : FRAME_RING;
+    s->ring_frames = s->batch_active ? batch_ring_frames(B) : FRAME_RING;      // (batch mode: WARP_LAG more steps of frames wait for their warps)
     for (int i = 0; i < s->ring_frames; i++) { s->free_slots.push_back(i); s->slot_valid[i] = false; }
     s->ncap = std::max(s->p.max_corners, 1);
     const int ncap = s->ncap;
@@ -1184,8 +1184,8 @@ int vs_stab_set_batch(vs_stab* s, int frames) {
 
 // Zero-copy input for vs_stab_push_dev: the frame is not copied into the instance's queue but read where the
 // caller put it (a decoder surface pool, a resident clip).  It must stay valid and unchanged until the result
-// of the SAME push count has been produced, i.e. for clamp(smoothingRadius,5,35) further pushes plus twice
-// the batch depth and a vs_stab_sync, or until vs_stab_flush_dev has drained the queue.  Tightly packed frames.
+// of the SAME push count has been produced, i.e. for clamp(smoothingRadius,5,35) further pushes plus 1 + WARP_LAG
+// times the batch depth and a vs_stab_sync, or until vs_stab_flush_dev has drained the queue.  Tightly packed frames.
 int vs_stab_set_zero_copy(vs_stab* s, int enable) {
     if (!s) return VS_ERR_INVALID_ARG;
     VS_CALLER_DRIVES(s);
