@@ -51,7 +51,8 @@ extern "C" {
  *    vs_yuv_surface_layout; crop-and-zoom on YUV streams: vs_stab_set_yuv_crop_zoom, vs_batch_set_yuv_crop_zoom and vs_op_resize_jobs;
  *    border pad on YUV streams: struct vs_yuv_fill with vs_stab_set_yuv_border_pad, vs_batch_set_yuv_border_pad and
  *    vs_yuv_video_black, struct vs_pad_job with vs_op_pad_jobs; the fade border on YUV streams: vs_stab_set_yuv_fade, struct
- *    vs_fade_job with vs_op_fade_blend_jobs, struct vs_fade_update_job with vs_op_fade_update_jobs
+ *    vs_fade_job with vs_op_fade_blend_jobs, struct vs_fade_update_job with vs_op_fade_update_jobs; edge fill on YUV streams:
+ *    vs_stab_set_yuv_edge_fill, vs_batch_set_yuv_edge_fill and vs_op_warp_affine_yuv_fill
  *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
@@ -599,6 +600,27 @@ int vs_yuv_video_black(int fmt, vs_yuv_fill* out);
  * refusing the fade.  The virtual canvas stays refused on YUV streams.  Zero-copy input, the decoder layouts and the host entry
  * points work as with border pad.  Three launches per frame: blend (pad and blend fused), warp, update. */
 int vs_stab_set_yuv_fade(vs_stab* s, int enable, const vs_yuv_fill* fill);
+/* Edge fill on YUV streams - a constant-colour warp border.  A YUV stream warps its planes with BORDER_CONSTANT 0, and zero samples
+ * are not a colour in YUV: (0, 0, 0) is saturated green.  The most common stream - output at the input's size, border_size = 0, the
+ * picture sliding over its surround - therefore shows green wedges, and so does a crop-and-zoom stream whose correction exceeds
+ * border_size (it warps the unpadded frame before it crops).  The reference has no YUV path, so what the mode does is a DEFINITION
+ * of this library, which a caller opts into with this call (enable != 0; the frame queue must be empty).  Off by default: such a
+ * stream allocates and launches exactly what it does without the call.  With the mode on, every warp of an UNPADDED YUV surface is
+ *   cv::warpAffine(..., INTER_LINEAR, BORDER_CONSTANT, borderValue = fill)   per plane:
+ * a tap outside the plane reads the plane's fill sample - on the interleaved UV plane of NV12 / P010 the (U, V) fill pair -, each
+ * tap decided by itself.  Everything else is what the stream does without the mode: the same coordinates and tables, the 8-bit
+ * arithmetic of vs_op_warp_affine_ex, P010's blend (one rounding, half to even) for 16-bit samples, Y under M and chroma under the
+ * stream's chroma matrix.  fill (0, 0, 0) gives the bytes of the stream without the mode, bit for bit.
+ * The mode applies to the plain stream (border_size == 0; a border_size without crop_n_zoom and without border pad or fade opted
+ * in is refused as before) and to the warp into the scratch surface of a crop-and-zoom stream (vs_stab_set_yuv_crop_zoom), whose
+ * crop is then taken from the fill-warped surface.  Border pad and fade (vs_stab_set_yuv_border_pad, vs_stab_set_yuv_fade) keep
+ * their BORDER_REPLICATE warp of the padded surface: the mode is independent of them and does nothing there.
+ * Analysis, trajectory, matrices and debug records, output size and layouts, and the last frame of a flush (copied with no
+ * transform) do not depend on the mode, bit for bit.  GRAY8 and the interleaved formats are not touched.  Zero-copy input, the
+ * decoder layouts, the host entry points and batch mode work as without the mode; no buffer and no launch is added.
+ * fill: as for vs_stab_set_yuv_border_pad - the samples as they lie in memory, reserved = 0; NULL = vs_yuv_video_black of the
+ * format; a sample above 255 on an 8-bit format is VS_ERR_INVALID_ARG, here when the format is known, else at the next push. */
+int vs_stab_set_yuv_edge_fill(vs_stab* s, int enable, const vs_yuv_fill* fill);
 
 /* ---- several streams of one device scheduled together (BASELINE configs[4]: 64 streams = 8 per GPU) ----------------------
  * The reference runs one Stabilizer per stream, each with its own cv::cuda::Stream objects (src/Stabilizer.cpp:102-104); here a
@@ -641,6 +663,9 @@ int vs_batch_set_i420_layout(vs_batch* b, size_t in_u_off, size_t in_v_off, size
 int vs_batch_set_yuv_crop_zoom(vs_batch* b, int enable);
 /* vs_stab_set_yuv_border_pad for every member (the members of a group must agree on the mode and the fill) */
 int vs_batch_set_yuv_border_pad(vs_batch* b, int enable, const vs_yuv_fill* fill);
+/* vs_stab_set_yuv_edge_fill for every member (the members of a group must agree on the mode and the resolved fill: one warp launch
+ * serves the frames of all of them) */
+int vs_batch_set_yuv_edge_fill(vs_batch* b, int enable, const vs_yuv_fill* fill);
 int vs_batch_push_dev(vs_batch* b, const void* const* d_frames, int w, int h, size_t stride, int fmt, void* const* d_outs,
                       size_t out_stride, int* produced);
 int vs_batch_flush_dev(vs_batch* b, void* const* d_outs, size_t out_stride, int* produced);
@@ -734,6 +759,18 @@ int vs_op_warp_affine_planar(int fmt, const void* d_src, size_t src_stride, size
                              void* d_dst, size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch,
                              int w, int h, const float* M, int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
                              int border, void* stream);
+/* The warp of edge fill on YUV streams (vs_stab_set_yuv_edge_fill) as an operator: cv::warpAffine(..., INTER_LINEAR, BORDER_CONSTANT,
+ * borderValue = fill) per plane.  The arguments of vs_op_warp_affine_planar, with the fill where that takes a border.  fmt: a planar
+ * format, or VS_FMT_NV12 / VS_FMT_P010 - src_u_off / dst_u_off then name the interleaved UV plane (0 = behind the h luma rows), which
+ * is warped in (U, V) pairs under the matrix with the halved translation, and the V offsets and chroma pitches are ignored.  fill:
+ * samples as they lie in memory, reserved = 0; NULL = vs_yuv_video_black(fmt); a sample above 255 on an 8-bit format is
+ * VS_ERR_INVALID_ARG.  (0, 0, 0) gives the bytes of VS_BORDER_BLACK.  Host matrices; up to 32 surfaces per launch, all planes of a
+ * launch in one grid.  Every argument is checked on the host before anything is launched; the format, the fill and null arguments
+ * are refused even without a device. */
+int vs_op_warp_affine_yuv_fill(int fmt, const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch,
+                               void* d_dst, size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch,
+                               int w, int h, const float* M, int batch, size_t src_frame_bytes, size_t dst_frame_bytes,
+                               const vs_yuv_fill* fill, void* stream);
 /* std::cos / std::sin / std::atan2 on float as the reference calls them (Stabilizer.cpp:662, 902-908, 1689: the host libm's
  * cosf / sinf / atan2f), evaluated by the DEVICE build of the library's restatement: the sum over i in [start, start + count) of
  * a 64-bit mix of (i, bits of f(argument i)) - fn 0 cosf, 1 sinf, 2 atanf: argument i = the float with bit pattern (uint32_t)i;

@@ -146,10 +146,18 @@ static bool same_yuv_pad(const vs_stab* a, const vs_stab* b) {
     const vs_yuv_fill x = yuv_pad_fill(a), y = yuv_pad_fill(b);
     return x.y == y.y && x.u == y.u && x.v == y.v;
 }
+// (edge fill on YUV surfaces: whether it acts, and the resolved colour: ONE warp launch serves the frames of all members)
+static bool same_yuv_edge_fill(const vs_stab* a, const vs_stab* b) {
+    const bool on = yuv_edge_fill_on(a);
+    if (on != yuv_edge_fill_on(b)) return false;
+    if (!on) return true;
+    const vs_yuv_fill x = yuv_edge_fill(a), y = yuv_edge_fill(b);
+    return x.y == y.y && x.u == y.u && x.v == y.v;
+}
 bool same_launch_shape(const vs_stab* a, const vs_stab* b) {
     const vs_params_c &p = a->p, &q = b->p;
     return a->w == b->w && a->h == b->h && a->fmt == b->fmt && a->src_pitch == b->src_pitch && a->zero_copy == b->zero_copy &&
-           a->in == b->in && a->out == b->out && a->yuv_cz == b->yuv_cz && same_yuv_pad(a, b) &&
+           a->in == b->in && a->out == b->out && a->yuv_cz == b->yuv_cz && same_yuv_pad(a, b) && same_yuv_edge_fill(a, b) &&
            a->aw == b->aw && a->ah == b->ah && a->levels == b->levels &&
            p.lk_win_size == q.lk_win_size && p.ransac_max_iters == q.ransac_max_iters && p.border_size == q.border_size &&
            p.crop_n_zoom == q.crop_n_zoom && (p.border_size <= 0 || p.border_type == q.border_type);
@@ -217,7 +225,9 @@ int group_ready_launches(vs_batch* g, vs_batch::Ready& R, int what, hipStream_t 
     const BorderPlan bp = border_plan(s0);
     const bool cz = yuv_cz_on(s0);      // a YUV stream with crop-and-zoom: bp.crop, the scratch surfaces in their own layout
     const bool yp = yuv_pad_on(s0);     // a YUV stream with border pad: bp.pad, the padded scratch surfaces in their own layout
-    const int wb = yp ? VS_BORDER_REPLICATE : VS_BORDER_BLACK;      // (the edge of a padded plane is its border)
+    // (the border of a YUV stream's warps - the edge of a padded plane is its border; edge fill - is chosen where the per-frame path
+    // chooses it.  These warps were queued WARP_LAG steps ago: the fill is still theirs, see yuv_warp_border.)
+    const YuvBorder wb = s0->pf->kind != PIX_INTERLEAVED ? yuv_warp_border(s0) : YuvBorder{VS_BORDER_BLACK, WarpFill()};
     int rc = VS_OK;
     // (launch by launch: the pads of a launch's frames are queued right in front of it, their crops right behind it)
     for (int i0 = 0; i0 < R.n && rc == VS_OK; i0 += WARP_BATCH_MAX) {
@@ -764,6 +774,12 @@ int vs_batch_set_yuv_crop_zoom(vs_batch* g, int enable) {
 int vs_batch_set_yuv_border_pad(vs_batch* g, int enable, const vs_yuv_fill* fill) {
     if (!g) return VS_ERR_INVALID_ARG;
     for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_yuv_border_pad(s, enable, fill); if (rc != VS_OK) { g->err = s->err; return rc; } }
+    return VS_OK;
+}
+
+int vs_batch_set_yuv_edge_fill(vs_batch* g, int enable, const vs_yuv_fill* fill) {
+    if (!g) return VS_ERR_INVALID_ARG;
+    for (vs_stab* s : g->m) { MemberCall mc(s); const int rc = vs_stab_set_yuv_edge_fill(s, enable, fill); if (rc != VS_OK) { g->err = s->err; return rc; } }
     return VS_OK;
 }
 

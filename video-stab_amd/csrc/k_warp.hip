@@ -104,6 +104,23 @@ __device__ __forceinline__ uint32_t load_px_checked(const uint8_t* src, size_t s
     return v;
 }
 
+// The same under VS_BORDER_FILL (edge fill on YUV surfaces): outside the plane the pixel is `fillpx`, the plane's fill in the form
+// above - the sample, or the (U, V) pair.  Each tap is decided by itself.
+template <int CN, int SB>
+__device__ __forceinline__ uint32_t load_px_fill(const uint8_t* src, size_t sstride, int sw, int sh, int sx, int sy, uint32_t fillpx) {
+    if ((unsigned)sx >= (unsigned)sw || (unsigned)sy >= (unsigned)sh) return fillpx;
+    if (SB == 2) {
+        const uint16_t* q = reinterpret_cast<const uint16_t*>(src + (size_t)sy * sstride) + (size_t)sx * CN;
+        uint32_t v16 = q[0];
+        if (CN > 1) v16 |= (uint32_t)q[1] << 16;
+        return v16;
+    }
+    const uint8_t* p = src + (size_t)sy * sstride + (size_t)sx * CN;
+    uint32_t v = p[0];
+    if (CN > 1) v |= (uint32_t)p[1] << 8;
+    return v;
+}
+
 // p00/p01 = taps of the upper row, p10/p11 of the lower row (one pixel per dword,
 // channel c in byte c).  Horizontal lerps as byte dot products, vertical in 24 bits.
 template <int CN>
@@ -211,10 +228,11 @@ __device__ __forceinline__ uint4 stage_group(const WarpCore& c, const uint8_t* _
     return px;
 }
 
-template <int CN, bool USE_LDS, int SB = 1>
+// FILL (the VS_BORDER_FILL kernels, direct path only): a tap outside the picture is `fillpx` (load_px_fill)
+template <int CN, bool USE_LDS, int SB = 1, bool FILL = false>
 __device__ __forceinline__ void emit_rows(const WarpCore& c, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                           const uint32_t* tile, const int* s_ad, const int* s_bd, const int* s_x0,
-                                          const int* s_y0, int x0, int y0, int x1, int y1, int bx0a, int by0, int bw, int tid) {
+                                          const int* s_y0, int x0, int y0, int x1, int y1, int bx0a, int by0, int bw, int tid, uint32_t fillpx = 0u) {
     const int tx = tid % TXN, ty = tid / TXN;
     const int x = x0 + PX * tx;
     if (x > x1) return;
@@ -238,6 +256,11 @@ __device__ __forceinline__ void emit_rows(const WarpCore& c, const uint8_t* __re
                 const int idx = y0 + yl <= y1 ? __mul24(sy - by0, bw) + (sx - bx0a) : 0;
                 p00[i] = tile[idx]; p01[i] = tile[idx + 1];
                 p10[i] = tile[idx + bw]; p11[i] = tile[idx + bw + 1];
+            } else if constexpr (FILL) {
+                p00[i] = load_px_fill<CN, SB>(src, c.sstride, c.sw, c.sh, sx, sy, fillpx);
+                p01[i] = load_px_fill<CN, SB>(src, c.sstride, c.sw, c.sh, sx + 1, sy, fillpx);
+                p10[i] = load_px_fill<CN, SB>(src, c.sstride, c.sw, c.sh, sx, sy + 1, fillpx);
+                p11[i] = load_px_fill<CN, SB>(src, c.sstride, c.sw, c.sh, sx + 1, sy + 1, fillpx);
             } else {
                 p00[i] = load_px_checked<CN, SB>(src, c.sstride, c.sw, c.sh, sx, sy, c.border);
                 p01[i] = load_px_checked<CN, SB>(src, c.sstride, c.sw, c.sh, sx + 1, sy, c.border);
@@ -1108,6 +1131,36 @@ __device__ __forceinline__ uint4 load_chunk_straddling(const uint8_t* rowp, int 
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// The same chunk under VS_BORDER_FILL: the row's bytes inside, the bytes of `pat` outside.  pat: the plane's fill as one dword (F x 4,
+// (U, V) x 2, F16 x 2 or (U16, V16)); a chunk starts at a multiple of 4 pixels, so byte k of a chunk's dword is byte k of the pattern.
+__device__ __forceinline__ uint4 load_chunk_straddling_fill(const uint8_t* rowp, int xb, int rowbytes, bool dwords, uint32_t pat) {
+    uint32_t w[4];
+    if (dwords) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int xq = xb + 4 * q;
+            const bool in = xq >= 0 && xq + 4 <= rowbytes;
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(rowp + (in ? xq : 0));
+            w[q] = in ? v : pat;
+        }
+    } else {                 // unaligned rows, or a row length that is no multiple of 4: byte by byte (rolled, as above)
+        uint32_t wq[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 1
+        for (int k = 0; k < 4; k++) {
+            const uint32_t fb = (pat >> (8 * k)) & 0xFFu;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int xx = xb + 4 * q + k;
+                const uint32_t v = rowp[min(max(xx, 0), rowbytes - 1)];
+                wq[q] |= (xx >= 0 && xx < rowbytes ? v : fb) << (8 * k);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) w[q] = wq[q];
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // The same chunk under BORDER_REPLICATE (remapBilinear's clip()): a byte outside the row is the byte of the same channel of the
 // row's first / last pixel.  (Chunks of tiles at the picture's edge only.)
 // CN: the BYTES of a pixel (1, 2 or 4) - the channels of an 8-bit plane, or one / two 16-bit samples (P010 luma / chroma: a byte outside the
@@ -1323,6 +1376,25 @@ __device__ __attribute__((noinline)) void plane_direct_tile(WarpCore c, const ui
                              min(y0 + TH * j + TH - 1, y1), bx0a, by0, bw, tid);
 }
 
+// The direct path of the VS_BORDER_FILL kernels: plane_direct_tile with the fill pixel.  A function of its own (one copy per kernel:
+// OWN), so that plane_direct_tile keeps its arguments and every kernel that calls it its code.
+template <int CN, int SB, int OWN>
+__device__ __attribute__((noinline)) void plane_direct_tile_fill(WarpCore c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
+                                                                 int tid, uint32_t fillpx) {
+    typedef PlaneCfg<CN, SB> P;
+    if (tid < TW) {           // ad[128] bd[128] x0[THP] y0[THP]
+        const int cx = min(x0 + tid, x1);
+        s_tab[tid] = Tg[cx]; s_tab[TW + tid] = Tg[c.dw + cx];
+    } else if (tid < TW + P::THP) {
+        const int r = min(y0 + (tid - TW), y1);
+        s_tab[2 * TW + (tid - TW)] = Tg[2 * c.dw + r]; s_tab[2 * TW + P::THP + (tid - TW)] = Tg[2 * c.dw + c.dh + r];
+    }
+    __syncthreads();
+    for (int j = 0; y0 + TH * j <= y1; j++)
+        emit_rows<CN, false, SB, true>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW + TH * j, s_tab + 2 * TW + P::THP + TH * j, x0, y0 + TH * j, x1,
+                                       min(y0 + TH * j + TH - 1, y1), 0, 0, 0, tid, fillpx);
+}
+
 // Four channels: the tile is ONE 16-row pass of emit_rows, and inlined - the call's saved registers would be the kernel's only
 // scratch.
 __device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
@@ -1346,9 +1418,13 @@ __device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint
 // nearest picture pixel (BORDER_REPLICATE: the roll stage's rotation); a launch whose border is the other one takes the direct path.
 // OWN: the 16-bit BORDER_REPLICATE instance of the kernel that says so calls a plane_direct_tile copy of its own (sharing one copy
 // between two kernels changes the register allocation of both: the kernels that exist keep their code).
+// BORDER = VS_BORDER_FILL (edge fill on YUV surfaces): the VS_BORDER_BLACK instance with `fill` - the plane's fill as one dword pattern, in
+// phase with every staged chunk (they start at a multiple of 4 pixels) - wherever that one holds zeros: rows and chunks outside the
+// picture, the outside bytes of a chunk that straddles its left or right edge (load_chunk_straddling_fill), and, on the direct path
+// (plane_direct_tile_fill, copy OWN), the taps outside.
 template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1, int OWN = 0>
 __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
-                                           uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add = 0, int dst_add = 0) {
+                                           uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add = 0, int dst_add = 0, uint32_t fill = 0u) {
     typedef PlaneCfg<CN, SB> P;
     static_assert(SB == 1 || (SB == 2 && CN <= 2), "16-bit planes: one or two channels");
     typedef __attribute__((address_space(1))) uint8_t* gptr;
@@ -1405,7 +1481,8 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
 #pragma unroll
         for (int k = 0; k < NCH; k++) {
             const int i = tid + NT * k;
-            d[k] = make_uint4(0u, 0u, 0u, 0u);
+            if constexpr (BORDER == VS_BORDER_FILL) d[k] = make_uint4(fill, fill, fill, fill);
+            else d[k] = make_uint4(0u, 0u, 0u, 0u);
             if (i < total) {
                 const int r = i / P::CPR, ch = i - r * P::CPR;
                 const int y = by0 + r;
@@ -1419,7 +1496,8 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
                     if (xb >= 0 && xb + 16 <= rowbytes && c.src_aligned) {
                         d[k] = *reinterpret_cast<const uint4*>(row + xb);       // 4-byte aligned: bx0a is a multiple of 4 pixels
                     } else if (xb + 16 > 0 && xb < rowbytes) {
-                        d[k] = load_chunk_straddling(row, (int)xb, (int)rowbytes, c.src_aligned && (rowbytes & 3) == 0);
+                        if constexpr (BORDER == VS_BORDER_FILL) d[k] = load_chunk_straddling_fill(row, (int)xb, (int)rowbytes, c.src_aligned && (rowbytes & 3) == 0, fill);
+                        else d[k] = load_chunk_straddling(row, (int)xb, (int)rowbytes, c.src_aligned && (rowbytes & 3) == 0);
                     }
                 }
             }
@@ -1456,6 +1534,8 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
     }
     if (!fit) {
         if constexpr (CN == 4) plane_direct_tile4(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        else if constexpr (BORDER == VS_BORDER_FILL)      // (the fill pixel: the pattern's first sample, or its (U, V) pair)
+            plane_direct_tile_fill<CN, SB, OWN>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, tid, P::PXB == 1 ? fill & 0xFFu : P::PXB == 2 ? fill & 0xFFFFu : fill);
         else plane_direct_tile<CN, SB, (SB == 2 && BORDER == VS_BORDER_REPLICATE ? 1 + OWN : 0)>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
         return;
     }
@@ -1765,6 +1845,138 @@ __global__ __launch_bounds__(NT, 7) void warp_i422_tall_kernel(gtab_t tabs, int 
     plane_tile_tall<SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
 }
 
+// ---- edge fill on YUV surfaces: the VS_BORDER_FILL instances ----------------------------------------------------------------------
+// cv::warpAffine(..., INTER_LINEAR, BORDER_CONSTANT, borderValue = fill) per plane: what the VS_BORDER_BLACK instances of the two
+// one-launch kernels compute, with the plane's fill sample where those read zeros (plane_tile<CN, VS_BORDER_FILL, SB>).  The fill
+// travels as two more kernel arguments - Y | U << 16 and V, samples as they lie in memory - behind the arguments of the kernels
+// above (13 and 16 dwords: still preloaded into scalar registers), which is why these are kernels of their own and not two more
+// instances of the templates above: those keep their argument lists, and WarpCore its fields, so that no existing kernel's scalar
+// registers move.  Everything else - tile sequence, grid order, table blocks, flags (border = VS_BORDER_FILL) - is theirs to the letter.
+// A plane's pattern: an 8-bit sample four times, the (U, V) byte pair twice, a 16-bit sample twice, or the (U, V) pair of P010.
+template <int SB>
+__device__ __forceinline__ uint32_t fill_pattern(uint32_t f) { return SB == 2 ? (f & 0xFFFFu) | f << 16 : (f & 0xFFu) * 0x01010101u; }
+
+template <int SB>
+__global__ __launch_bounds__(NT, 8) void warp_nv12_fill_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t swh, uint32_t dwh,
+                                                            uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, uint32_t fill_yu, uint32_t fill_v) {
+    typedef PlaneCfg<1, SB> P1;
+    typedef PlaneCfg<2, SB> P2;
+    constexpr int TILE_BYTES = P1::ROWS * P1::PB > P2::ROWS * P2::PB ? P1::ROWS * P1::PB : P2::ROWS * P2::PB;
+    __shared__ __attribute__((aligned(16))) uint8_t tile[TILE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
+    __shared__ __attribute__((aligned(16))) int2 s_row[P1::THP];
+    typedef const __attribute__((address_space(4))) int32_t* cptr;
+    WarpCore c;
+    c.sstride = sstride; c.dstride = dstride;
+    c.sw = swh & 0xFFFFu; c.sh = swh >> 16; c.dw = dwh & 0xFFFFu; c.dh = dwh >> 16;
+    c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u; c.border = (flags >> 2) & 7u;
+    const uint32_t gx1 = (uint32_t)(c.dw + TW - 1) / TW, gy1 = (uint32_t)(c.dh + P1::THP - 1) / P1::THP;
+    const uint32_t dw2 = (uint32_t)c.dw >> 1, dh2 = (uint32_t)c.dh >> 1;
+    const uint32_t gx2 = (dw2 + TW - 1) / TW, gy2 = (dh2 + P2::THP - 1) / P2::THP;
+    const uint32_t n1 = gx1 * gy1, tpf = n1 + gx2 * gy2, n = tpf * (flags >> 16);
+    const uint32_t lin = blockIdx.x;
+    uint32_t seq = lin;
+    if (flags & 0x100u) {
+        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
+        seq = cx * q + (cx < r ? cx : r) + k;
+    }
+    const uint32_t f = __umulhi(seq, mtpf);
+    uint32_t t = seq - f * tpf;
+    gtab_t T = tabs + (size_t)f * tab_stride;
+    if (t < n1) {
+        const TabLayout L = tab_layout(c.dw, c.dh);
+        const uint32_t row = gx1 == 1 ? t : __umulhi(t, mgx1);
+        plane_tile<1, VS_BORDER_FILL, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx1), (int)row, tile, lut, s_row, threadIdx.x, 0, 0,
+                                          fill_pattern<SB>(fill_yu));
+    } else {
+        t -= n1;
+        T += tab_layout(c.dw, c.dh).stride;
+        c.sw >>= 1; c.sh >>= 1; c.dw = (int)dw2; c.dh = (int)dh2;
+        c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
+        const TabLayout L = tab_layout(c.dw, c.dh);
+        const uint32_t row = gx2 == 1 ? t : __umulhi(t, mgx2);
+        const uint32_t u = fill_yu >> 16;
+        plane_tile<2, VS_BORDER_FILL, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx2), (int)row, tile, lut, s_row, threadIdx.x, 0, 0,
+                                          SB == 2 ? u | fill_v << 16 : ((u & 0xFFu) | (fill_v & 0xFFu) << 8) * 0x00010001u);
+    }
+}
+
+template <int SB, int CSX, int CSY>
+__global__ __launch_bounds__(NT, 8) void warp_i420_fill_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
+                                                            uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu,
+                                                            uint32_t fill_yu, uint32_t fill_v) {
+    typedef PlaneCfg<1, SB> P;
+    __shared__ __attribute__((aligned(16))) uint8_t tile[P::ROWS * P::PB];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
+    __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];
+    typedef const __attribute__((address_space(4))) int32_t* cptr;
+    const int w = wh & 0xFFFFu, h = wh >> 16;
+    const uint32_t gx1 = (uint32_t)(w + TW - 1) / TW, gy1 = (uint32_t)(h + P::THP - 1) / P::THP;
+    const uint32_t w2 = (uint32_t)w >> CSX, h2 = (uint32_t)h >> CSY;
+    const uint32_t gx2 = (w2 + TW - 1) / TW, gy2 = (h2 + P::THP - 1) / P::THP;
+    const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2, n = tpf * (flags >> 16);
+    const uint32_t lin = blockIdx.x;
+    uint32_t seq = lin;
+    if (flags & 0x100u) {
+        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
+        seq = cx * q + (cx < r ? cx : r) + k;
+    }
+    const uint32_t f = __umulhi(seq, mtpf);
+    uint32_t t = seq - f * tpf;
+    gtab_t T = tabs + (size_t)f * tab_stride;
+    // the tile's plane (workgroup-uniform): geometry, pitches, alignment, table and tile columns as above, and the plane's fill sample
+    WarpCore c;
+    c.border = (flags >> 2) & 7u;
+    uint32_t gx, mgx, fs;
+    int sadd = 0, dadd = 0;
+    if (t < n1) {
+        c.sstride = sstride; c.dstride = dstride;
+        c.sw = c.dw = w; c.sh = c.dh = h;
+        c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u;
+        gx = gx1; mgx = mgx1; fs = fill_yu;
+    } else {
+        t -= n1;
+        fs = fill_yu >> 16;
+        if (t >= n2) { t -= n2; sadd = svu; dadd = dvu; fs = fill_v; }
+        T += tab_layout(w, h).stride;
+        c.sstride = scpitch; c.dstride = dcpitch;
+        c.sw = c.dw = (int)w2; c.sh = c.dh = (int)h2;
+        c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
+        gx = gx2; mgx = mgx2;
+    }
+    const TabLayout L = tab_layout(c.dw, c.dh);
+    const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
+    // (a direct-path callee per subsampling, as the 16-bit BORDER_REPLICATE instances above have)
+    plane_tile<1, VS_BORDER_FILL, SB, (CSY == 1 ? 1 : CSX == 1 ? 2 : 3)>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row,
+                                                                         threadIdx.x, sadd, dadd, fill_pattern<SB>(fs));
+}
+
+// Launches without tables (a caller's tables exist for launches of WARP_TAB_MIN surfaces and more only), chroma planes that do not lie
+// one offset behind their luma planes, geometry outside what the two kernels above pack: one plane of 8- or 16-bit samples (CN = 1, or
+// 2: interleaved chroma) under VS_BORDER_FILL, terms from the frame's inverse map, taps read directly - warp_affine16_kernel with the
+// fill pixel.  (The general kernels take their border from WarpCore, which keeps its fields.)
+template <int CN, int SB>
+__global__ __launch_bounds__(NT) void warp_plane_fill_kernel(WarpArgs a, uint32_t fillpx) {
+    __shared__ int s_ad[TW], s_bd[TW], s_x0[TH], s_y0[TH];
+    const int bz = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int x1 = min(x0 + TW, a.c.dw) - 1, y1 = min(y0 + TH, a.c.dh) - 1;
+    double m[6];
+    load_map(a, bz, m);
+    if (tid < TW) {
+        const double dv = (double)min(x0 + tid, x1);
+        s_ad[tid] = coord_term(m[0], 0.0, dv);
+        s_bd[tid] = coord_term(m[3], 0.0, dv);
+    } else if (tid < TW + TH) {
+        const double dv = (double)min(y0 + (tid - TW), y1);
+        s_x0[tid - TW] = coord_term(m[1], m[2], dv) + 16;
+        s_y0[tid - TW] = coord_term(m[4], m[5], dv) + 16;
+    }
+    __syncthreads();
+    emit_rows<CN, false, SB, true>(a.c, a.srcs[bz], a.dsts[bz], nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid, fillpx);
+}
+
 // Ints of table workspace per frame of dw x dh (see warp_tables_kernel).
 inline int tab_stride_of(int dw, int dh) { return tab_layout(dw, dh).stride; }
 
@@ -1842,9 +2054,10 @@ bool odd16(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstri
     return false;
 }
 
-// Validation shared by the two launchers: the border, the table choice, and no null frame in the lists.
-bool bad_call(const uint8_t* const* srcs, uint8_t* const* dsts, int n, int border, const WarpTabs& tabs) {
-    if ((border != VS_BORDER_BLACK && border != VS_BORDER_REPLICATE) || (tabs.kind == WarpTabs::CALLER && !tabs.tabs) ||
+// Validation shared by the launchers: the border, the table choice, and no null frame in the lists.
+// fill_ok: the YUV launchers, which also take VS_BORDER_FILL
+bool bad_call(const uint8_t* const* srcs, uint8_t* const* dsts, int n, int border, const WarpTabs& tabs, bool fill_ok = false) {
+    if ((border != VS_BORDER_BLACK && border != VS_BORDER_REPLICATE && !(fill_ok && border == VS_BORDER_FILL)) || (tabs.kind == WarpTabs::CALLER && !tabs.tabs) ||
         (tabs.kind != WarpTabs::CALLER && tabs.what != VS_WARP_ALL))
         return true;
     for (int i = 0; i < n; i++)
@@ -1882,8 +2095,10 @@ int op_tabs(hipStream_t st, size_t bytes, int32_t** out) {
 WarpMaps maps_from(WarpMaps m, int k) { m.m += (size_t)m.stride * k; return m; }
 
 // ONE launch over n <= MAXB frames of one plane.  d_tabs: the launch's tables (tab_stride ints apart, 0 = packed), or nullptr.
+// border VS_BORDER_FILL (cn 1 or 2): fillpx is the plane's fill pixel - the sample, or the (U, V) pair as load_px_checked forms it -, the
+// tables are built as for any border, and the warp is warp_plane_fill_kernel's.
 int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t sstride, int sw, int sh, size_t dstride, int dw, int dh,
-                 int cn, WarpMaps maps, int border, int32_t* d_tabs, int tab_stride, int what, hipStream_t st, int sb = 1) {
+                 int cn, WarpMaps maps, int border, int32_t* d_tabs, int tab_stride, int what, hipStream_t st, int sb = 1, uint32_t fillpx = 0u) {
     WarpArgs a;
     a.c.sstride = sstride; a.c.dstride = dstride;
     a.c.sw = sw; a.c.sh = sh; a.c.dw = dw; a.c.dh = dh;
@@ -1902,16 +2117,35 @@ int plane_launch(const uint8_t* const* srcs, uint8_t* const* dsts, int n, size_t
     for (int b = 0; b < MAXB; b++)
         for (int i = 0; i < 6; i++) a.Minv_val[6 * b + i] = maps.host && b < n ? maps.m[(size_t)maps.stride * b + i] : 0.;
     dim3 grid((dw + TW - 1) / TW, (dh + TH - 1) / TH, n);
+    if (border == VS_BORDER_FILL) {
+        if (cn > 2) { set_last_error("warp: VS_BORDER_FILL takes planes of one or two channels"); return VS_ERR_INVALID_ARG; }
+        a.tabs = d_tabs;
+        const TabLayout tl = tab_layout(dw, dh);
+        a.tab_stride = tab_stride > 0 ? tab_stride : tl.stride; a.tab_row = tl.row; a.tab_ad = tl.ad;
+        if (d_tabs && what != VS_WARP_ONLY)
+            hipLaunchKernelGGL(warp_tables_kernel, dim3((dw + dh + grid.x + grid.y + NT - 1) / NT, grid.z), dim3(NT), 0, st, a);
+        if (!(d_tabs && what == VS_WARP_TABLES_ONLY)) {
+            if (sb == 2 && cn == 2) hipLaunchKernelGGL((warp_plane_fill_kernel<2, 2>), grid, dim3(NT), 0, st, a, fillpx);
+            else if (sb == 2) hipLaunchKernelGGL((warp_plane_fill_kernel<1, 2>), grid, dim3(NT), 0, st, a, fillpx);
+            else if (cn == 2) hipLaunchKernelGGL((warp_plane_fill_kernel<2, 1>), grid, dim3(NT), 0, st, a, fillpx);
+            else hipLaunchKernelGGL((warp_plane_fill_kernel<1, 1>), grid, dim3(NT), 0, st, a, fillpx);
+        }
+        VS_HIP_TRY(hipGetLastError());
+        return VS_OK;
+    }
     launch_cn(a, grid, cn, d_tabs, st, what, tab_stride, sb);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }
 
+// The fill of a VS_BORDER_FILL launch as the kernels take it: Y | U << 16 and V; 8-bit formats hold 8-bit samples.
+bool bad_fill(const WarpFill& f, int sb) { const uint32_t top = sb == 2 ? 0xFFFFu : 0xFFu; return f.y > top || f.u > top || f.v > top; }
+
 // NV12 surfaces of one geometry and pitch, luma and chroma planes in ONE launch (warp_nv12_kernel), from the frames' table blocks
 // (warp_tab.h: luma table, then chroma table; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  The chroma planes lie src_uv /
 // dst_uv bytes behind the luma planes.  Returns VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstride, size_t dstride, int w, int h, size_t src_uv,
-                size_t dst_uv, const int32_t* d_tabs, int border, hipStream_t st, int sb = 1) {
+                size_t dst_uv, const int32_t* d_tabs, int border, hipStream_t st, int sb = 1, WarpFill fill = WarpFill()) {
     // (sb = 2, P010: tiles of half the rows; BORDER_REPLICATE: the roll stage's rotation of P010 surfaces)
     const int thp1 = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP, thp2 = sb == 2 ? PlaneCfg<2, 2>::THP : PlaneCfg<2>::THP;
     const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp1 - 1) / thp1, gx2 = (w / 2 + TW - 1) / TW, gy2 = (h / 2 + thp2 - 1) / thp2;
@@ -1934,7 +2168,13 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
     const uint32_t flags = (al & 1u) | (al & 2u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    if (sb == 2 && border == VS_BORDER_REPLICATE)
+    if (border == VS_BORDER_FILL && sb == 2)
+        hipLaunchKernelGGL((warp_nv12_fill_kernel<2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
+                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, fill.y | fill.u << 16, fill.v);
+    else if (border == VS_BORDER_FILL)
+        hipLaunchKernelGGL((warp_nv12_fill_kernel<1>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
+                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, fill.y | fill.u << 16, fill.v);
+    else if (sb == 2 && border == VS_BORDER_REPLICATE)
         hipLaunchKernelGGL((warp_nv12_kernel<VS_BORDER_REPLICATE, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
                            (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
     else if (sb == 2)
@@ -1954,7 +2194,7 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
 // table, then the chroma table whose records name the U planes; nv12_tab_ints(w, h) ints per frame), ALREADY BUILT.  Returns
 // VS_ERR_UNSUPPORTED when the geometry is outside what the kernel packs.
 int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420Layout& sl, const I420Layout& dl, int w, int h, const int32_t* d_tabs,
-                int border, hipStream_t st, int sb = 1, int sx = 1, int sy = 1, bool tall = false) {
+                int border, hipStream_t st, int sb = 1, int sx = 1, int sy = 1, bool tall = false, WarpFill fill = WarpFill()) {
     // (sb = 2, I010 / I012: tiles of half the rows; BORDER_REPLICATE: the roll stage's rotation of I010 / I012 surfaces)
     const int thp = sb == 2 ? PlaneCfg<1, 2>::THP : PlaneCfg<1>::THP;
     const unsigned long long gx1 = (w + TW - 1) / TW, gy1 = (h + thp - 1) / thp, gx2 = ((w >> sx) + TW - 1) / TW, gy2 = ((h >> sy) + thp - 1) / thp;
@@ -1994,14 +2234,30 @@ int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420L
     hipLaunchKernelGGL((warp_i422_tall_kernel<S>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, 1, 0), (uint32_t)sl.pitch, \
                        (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,    \
                        (int32_t)dvu)
+    // (VS_BORDER_FILL: the kernel with the fill behind these arguments)
+#define VS_I420_FILL(S, X, Y)                                                                                                                               \
+    hipLaunchKernelGGL((warp_i420_fill_kernel<S, X, Y>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, X, Y), (uint32_t)sl.pitch, \
+                       (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,    \
+                       (int32_t)dvu, fill.y | fill.u << 16, fill.v)
+#define VS_I420_FILL_SUB(S)                                \
+    do {                                                   \
+        if (sx == 1 && sy == 1) VS_I420_FILL(S, 1, 1);     \
+        else if (sx == 1) VS_I420_FILL(S, 1, 0);           \
+        else VS_I420_FILL(S, 0, 0);                        \
+    } while (0)
     const bool use_tall = tall && sx == 1 && sy == 0 && border == VS_BORDER_REPLICATE;
-    if (use_tall) ;      // (below: the instances that came later are instantiated behind the others, which keep their place in the code object)
+    const bool use_fill = border == VS_BORDER_FILL;
+    if (use_tall || use_fill) ;      // (below: the instances that came later are instantiated behind the others, which keep their place in the code object)
     else if (sb == 2 && border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 2);
     else if (sb == 2) VS_I420_SUB(VS_BORDER_BLACK, 2);
     else if (border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 1);
     else VS_I420_SUB(VS_BORDER_BLACK, 1);
     if (use_tall && sb == 2) VS_I422_TALL(2);
     else if (use_tall) VS_I422_TALL(1);
+    else if (use_fill && sb == 2) VS_I420_FILL_SUB(2);
+    else if (use_fill) VS_I420_FILL_SUB(1);
+#undef VS_I420_FILL_SUB
+#undef VS_I420_FILL
 #undef VS_I422_TALL
 #undef VS_I420_SUB
 #undef VS_I420_GO
@@ -2043,10 +2299,10 @@ int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, s
 // ONE grid; plane by plane when the launch has no tables, when the chroma planes do not all lie one offset behind the luma planes
 // (the one-launch kernel and the table launch take one offset), or when the geometry is outside what the one-launch kernel packs.
 int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t* const* us, uint8_t* const* ud, int n, size_t sstride,
-                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sb) {
+                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sb, WarpFill fill) {
     if (n < 1 || !ys || !yd || !us || !ud || w < 2 || h < 2 || (w & 1) || (h & 1) || (sb != 1 && sb != 2) ||
-        bad_args(ys[0], yd[0], maps.m, sstride, w, h, dstride, w, h, sb, n) || bad_call(ys, yd, n, border, tabs) ||
-        bad_call(us, ud, n, border, tabs)) {
+        bad_args(ys[0], yd[0], maps.m, sstride, w, h, dstride, w, h, sb, n) || bad_call(ys, yd, n, border, tabs, true) ||
+        bad_call(us, ud, n, border, tabs, true) || (border == VS_BORDER_FILL && bad_fill(fill, sb))) {
         set_last_error(sb == 2 ? "warp_p010: invalid argument (w and h must be even)" : "warp_nv12: invalid argument (w and h must be even)");
         return VS_ERR_INVALID_ARG;
     }
@@ -2056,7 +2312,9 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
     }
     // (P010 with the scratch tables: every launch builds them - one kernel serves single surfaces and batches alike.  A caller's
     // tables exist for launches of WARP_TAB_MIN frames and more only, whatever the format.)
-    const int tab_min = sb == 2 && tabs.kind == WarpTabs::SCRATCH ? 1 : WARP_TAB_MIN;
+    // (VS_BORDER_FILL likewise: a single surface goes through the one-launch kernel and its staged box)
+    const int tab_min = (sb == 2 || border == VS_BORDER_FILL) && tabs.kind == WarpTabs::SCRATCH ? 1 : WARP_TAB_MIN;
+    const uint32_t fpx_y = fill.y, fpx_uv = sb == 2 ? fill.u | fill.v << 16 : fill.u | fill.v << 8;      // (the planes' fill pixels: plane_launch)
     const int block = nv12_tab_ints(w, h), sy = tab_layout(w, h).stride;
     if (tabs.kind == WarpTabs::SCRATCH && n >= tab_min)
         VS_TRY(op_tabs(st, (size_t)block * std::min(n, MAXB) * sizeof(int32_t), &tabs.tabs));
@@ -2083,20 +2341,20 @@ int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t
                 const int entries = w + h + (w + TW - 1) / TW + (h + TH - 1) / TH;
                 hipLaunchKernelGGL(warp_tables_nv12_kernel, dim3((entries + NT - 1) / NT, nb, 2), dim3(NT), 0, st, t);
             } else {
-                VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, VS_WARP_TABLES_ONLY, st, sb));
+                VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, VS_WARP_TABLES_ONLY, st, sb, fpx_y));
                 VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T + sy, block,
-                                    VS_WARP_TABLES_ONLY, st, sb));
+                                    VS_WARP_TABLES_ONLY, st, sb, fpx_uv));
             }
         }
         if (tabs.what == VS_WARP_TABLES_ONLY) continue;
-        const int one = T && one_uv ? nv12_launch(ys + b0, yd + b0, nb, sstride, dstride, w, h, src_uv, dst_uv, T, border, st, sb) : VS_ERR_UNSUPPORTED;
+        const int one = T && one_uv ? nv12_launch(ys + b0, yd + b0, nb, sstride, dstride, w, h, src_uv, dst_uv, T, border, st, sb, fill) : VS_ERR_UNSUPPORTED;
         if (one != VS_ERR_UNSUPPORTED) {
             VS_TRY(one);
             continue;
         }
         const int what = T ? VS_WARP_ONLY : VS_WARP_ALL;
-        VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, what, st, sb));
-        VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T ? T + sy : nullptr, block, what, st, sb));
+        VS_TRY(plane_launch(ys + b0, yd + b0, nb, sstride, w, h, dstride, w, h, 1, my, border, T, block, what, st, sb, fpx_y));
+        VS_TRY(plane_launch(us + b0, ud + b0, nb, sstride, w / 2, h / 2, dstride, w / 2, h / 2, 2, mu, border, T ? T + sy : nullptr, block, what, st, sb, fpx_uv));
     }
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
@@ -2125,14 +2383,14 @@ static bool i420_needs_tall_box(const WarpMaps& mu, int nb, int cw, int sb) {
 // outside what warp_i420_kernel packs, goes plane by plane through the general kernels: V from the maps, without a table.
 // sb = 2: I010 / I012 surfaces - the layouts stay in bytes.
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout sl, I420Layout dl, int w, int h, WarpMaps maps, int border,
-                     WarpTabs tabs, hipStream_t st, int sb, int sx, int sy) {
+                     WarpTabs tabs, hipStream_t st, int sb, int sx, int sy, WarpFill fill) {
     const int cw = w >> sx, ch = h >> sy;             // a chroma plane's samples per row, and its rows
     const char* const kind = sx == 0 ? "planar 4:4:4" : sy == 0 ? "planar 4:2:2" : sb == 2 ? "warp_i010" : "warp_i420";
     if ((sx != 0 && sx != 1) || (sy != 0 && sy != 1) || sy > sx) { set_last_error("warp_planar: chroma shifts must be (1, 1), (1, 0) or (0, 0)"); return VS_ERR_INVALID_ARG; }
     if (n < 1 || !ys || !yd || w < 1 || h < 1 || cw < 1 || ch < 1 || (w & ((1 << sx) - 1)) || (h & ((1 << sy) - 1)) || (sb != 1 && sb != 2) ||
         bad_args(ys[0], yd[0], maps.m, sl.pitch, w, h, dl.pitch, w, h, sb, n) ||
         sl.cpitch < (size_t)cw * sb || dl.cpitch < (size_t)cw * sb || !sl.u || !sl.v || !dl.u || !dl.v || sl.u == sl.v || dl.u == dl.v ||
-        bad_call(ys, yd, n, border, tabs)) {
+        bad_call(ys, yd, n, border, tabs, true) || (border == VS_BORDER_FILL && bad_fill(fill, sb))) {
         if (sy == 0) set_last_error(std::string("warp_planar: ") + kind + ": invalid argument (4:2:2 needs an even w; chroma pitches must hold a chroma row)");
         else set_last_error(sb == 2 ? "warp_i010: invalid argument (w and h must be even, chroma pitches at least w bytes)"
                                     : "warp_i420: invalid argument (w and h must be even, chroma pitches at least w / 2)");
@@ -2156,9 +2414,9 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
         int32_t* T = tabs.kind != WarpTabs::NONE && nb >= tab_min ? tabs.tabs + b0 * tab_step : nullptr;
         if (!T && tabs.what == VS_WARP_TABLES_ONLY) continue;
         const WarpMaps my = maps_from(maps, b0), mu = maps_from(muv, b0);
-        auto plane = [&](size_t so, size_t d_o, size_t sp, size_t dp, int pw, int ph, WarpMaps m, int32_t* tab, int what) -> int {
+        auto plane = [&](size_t so, size_t d_o, size_t sp, size_t dp, int pw, int ph, WarpMaps m, int32_t* tab, int what, uint32_t fillpx) -> int {
             for (int i = 0; i < nb; i++) { ps[i] = ys[b0 + i] + so; pd[i] = yd[b0 + i] + d_o; }
-            return plane_launch(ps, pd, nb, sp, pw, ph, dp, pw, ph, 1, m, border, tab, block, what, st, sb);
+            return plane_launch(ps, pd, nb, sp, pw, ph, dp, pw, ph, 1, m, border, tab, block, what, st, sb, fillpx);
         };
         if (T && tabs.what != VS_WARP_ONLY) {
             if (maps.host && nb <= NVT_MAX && sx == 1 && sy == 1) {     // (the NV12 table launch halves both sizes)
@@ -2172,21 +2430,21 @@ int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420La
                 const int entries = w + h + (w + TW - 1) / TW + (h + TH - 1) / TH;
                 hipLaunchKernelGGL(warp_tables_nv12_kernel, dim3((entries + NT - 1) / NT, nb, 2), dim3(NT), 0, st, t);
             } else {
-                VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, VS_WARP_TABLES_ONLY));
-                VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, cw, ch, mu, T + ty, VS_WARP_TABLES_ONLY));
+                VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, VS_WARP_TABLES_ONLY, fill.y));
+                VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, cw, ch, mu, T + ty, VS_WARP_TABLES_ONLY, fill.u));
             }
         }
         if (tabs.what == VS_WARP_TABLES_ONLY) continue;
         const bool tall = maps.host && sx == 1 && sy == 0 && border == VS_BORDER_REPLICATE && i420_needs_tall_box(mu, nb, cw, sb);
-        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st, sb, sx, sy, tall) : VS_ERR_UNSUPPORTED;
+        const int one = T ? i420_launch(ys + b0, yd + b0, nb, sl, dl, w, h, T, border, st, sb, sx, sy, tall, fill) : VS_ERR_UNSUPPORTED;
         if (one != VS_ERR_UNSUPPORTED) {
             VS_TRY(one);
             continue;
         }
         const int what = T ? VS_WARP_ONLY : VS_WARP_ALL;
-        VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, what));
-        VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, cw, ch, mu, T ? T + ty : nullptr, what));
-        VS_TRY(plane(sl.v, dl.v, sl.cpitch, dl.cpitch, cw, ch, mu, nullptr, VS_WARP_ALL));
+        VS_TRY(plane(0, 0, sl.pitch, dl.pitch, w, h, my, T, what, fill.y));
+        VS_TRY(plane(sl.u, dl.u, sl.cpitch, dl.cpitch, cw, ch, mu, T ? T + ty : nullptr, what, fill.u));
+        VS_TRY(plane(sl.v, dl.v, sl.cpitch, dl.cpitch, cw, ch, mu, nullptr, VS_WARP_ALL, fill.v));
     }
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;

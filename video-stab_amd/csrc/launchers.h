@@ -58,8 +58,9 @@ int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_si
 // sx, sy: the chroma shifts (4:2:0 needs even w and h, 4:2:2 an even w, 4:4:4 takes any size).
 // Host maps, 4:2:2 and VS_BORDER_REPLICATE (the roll stage, vs_op_warp_affine_planar): a launch in which some surface's chroma tiles may
 // outgrow the staged box and can fit the taller one goes to the instances with THP + 17 staged rows (k_warp.hip, warp_i422_tall_kernel).
+// border VS_BORDER_FILL (vs_common.h): taps outside a plane read that plane's sample of `fill`.
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout src, I420Layout dst, int w, int h, WarpMaps maps, int border,
-                     WarpTabs tabs, hipStream_t st, int sample_bytes = 1, int sx = 1, int sy = 1);
+                     WarpTabs tabs, hipStream_t st, int sample_bytes = 1, int sx = 1, int sy = 1, WarpFill fill = WarpFill());
 
 // ---- k_roll.hip, k_azc.hip: the geometry and layout rules of their three-plane surfaces are planar_layout_check (planar_layout.h)
 

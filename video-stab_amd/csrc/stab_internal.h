@@ -145,6 +145,11 @@ struct vs_stab {
     // the warps read under BORDER_REPLICATE
     bool yuv_pad = false, pad_fill_given = false;
     vs_yuv_fill pad_fill = {0, 0, 0, 0};        // the caller's; not given: the format's video black
+    // edge fill (vs_stab_set_yuv_edge_fill): the warps of UNPADDED surfaces - the plain stream's, and the one into the scratch surface of
+    // crop-and-zoom - read this colour outside the picture (VS_BORDER_FILL) where they otherwise read 0, which in YUV is green.
+    // No buffer, no launch more: the mode picks other instances of the same warp kernels.
+    bool yuv_efill = false, efill_given = false;
+    vs_yuv_fill efill = {0, 0, 0, 0};           // the caller's; not given: the format's video black
     // the fade border (vs_stab_set_yuv_fade): one k_yuvfade launch pads the planes of a frame and blends them with the history
     // into the scratch surface, the warp reads that under BORDER_REPLICATE, and a second launch folds the result into the
     // history.  The history has the scratch surface's layout; like d_fade it outlives vs_stab_clean, so it remembers the geometry
@@ -294,6 +299,10 @@ inline bool yuv_fade_on(const vs_stab* s) { return yuv_fade_wanted(s) && s->pf->
 inline bool yuv_padded(const vs_stab* s) { return yuv_pad_on(s) || yuv_fade_on(s); }
 inline vs_yuv_fill yuv_pad_fill(const vs_stab* s) { return s->pad_fill_given ? s->pad_fill : yuv_video_black(*s->pf); }
 inline vs_yuv_fill yuv_fade_fill(const vs_stab* s) { return s->yfade_fill_given ? s->yfade_fill : yuv_video_black(*s->pf); }
+// Edge fill on a YUV stream: the mode is on and the stream's warp reads an unpadded surface (border pad and fade keep their
+// replicate-warp of the padded one: the mode does nothing there).
+inline bool yuv_edge_fill_on(const vs_stab* s) { return s->yuv_efill && s->pf->kind != PIX_INTERLEAVED && !yuv_padded(s); }
+inline vs_yuv_fill yuv_edge_fill(const vs_stab* s) { return s->efill_given ? s->efill : yuv_video_black(*s->pf); }
 
 inline int build_pyramid(vs_stab* s, int k, hipStream_t st) {
     Pyramid& P = s->pyr[k];
@@ -330,17 +339,33 @@ inline Planes warp_dst_planes(const vs_stab* s, const uint8_t* d_out, size_t out
     return yuv_cz_on(s) ? scratch_planes(s) : result_planes(s, d_out, out_stride);
 }
 
+// The border of a YUV stream's warp, for the per-frame path and the batch schedule alike - the ONE place that chooses it: the edge
+// of a padded scratch surface is its border (border pad, fade); an unpadded surface has zeros around it, or with edge fill the
+// stream's fill colour.
+// (The batch schedule issues a step's warps WARP_LAG steps after it queued their frames and asks here when it issues them.  The
+// answer is still the one the frames were queued under: the setters of these modes take effect only while the frame queue is
+// empty, and a queue only empties through a flush or a clean, which issue every pending warp first.)
+struct YuvBorder { int border; WarpFill fill; };
+inline YuvBorder yuv_warp_border(const vs_stab* s) {
+    if (yuv_padded(s)) return {VS_BORDER_REPLICATE, WarpFill()};
+    if (!yuv_edge_fill_on(s)) return {VS_BORDER_BLACK, WarpFill()};
+    const vs_yuv_fill c = yuv_edge_fill(s);
+    WarpFill f;
+    f.y = c.y; f.u = c.u; f.v = c.v;
+    return {VS_BORDER_FILL, f};
+}
+
 // The warp of n <= WARP_BATCH_MAX YUV surfaces (planes S, at the size of S's luma) into surfaces with planes D, one launch: luma
 // and the interleaved chroma plane - half size, two channels, the map with the halved translation (m + 6) -, or Y, U and V,
 // whose one chroma table serves both U and V.
-inline int warp_yuv(const uint8_t* const* srcs, uint8_t* const* dsts, int n, const Planes& S, const Planes& D, WarpMaps maps, int border, WarpTabs tabs,
+inline int warp_yuv(const uint8_t* const* srcs, uint8_t* const* dsts, int n, const Planes& S, const Planes& D, WarpMaps maps, const YuvBorder& b, WarpTabs tabs,
                     hipStream_t st) {
     if (S.n == 3)
-        return launch_warp_i420(srcs, dsts, n, S.i420(), D.i420(), S[0].w, S[0].h, maps, border, tabs, st, S.sample_bytes, S[1].sx, S[1].sy);
+        return launch_warp_i420(srcs, dsts, n, S.i420(), D.i420(), S[0].w, S[0].h, maps, b.border, tabs, st, S.sample_bytes, S[1].sx, S[1].sy, b.fill);
     const uint8_t* us[WARP_BATCH_MAX];
     uint8_t* ud[WARP_BATCH_MAX];
     for (int i = 0; i < n; i++) { us[i] = srcs[i] + S[1].off; ud[i] = dsts[i] + D[1].off; }
-    return launch_warp_nv12(srcs, dsts, us, ud, n, S[0].pitch, D[0].pitch, S[0].w, S[0].h, maps, border, tabs, st, S.sample_bytes);
+    return launch_warp_nv12(srcs, dsts, us, ud, n, S[0].pitch, D[0].pitch, S[0].w, S[0].h, maps, b.border, tabs, st, S.sample_bytes, b.fill);
 }
 
 // The zoom of n warped scratch surfaces into their results (device surfaces in the caller's output layout, or the staging of the

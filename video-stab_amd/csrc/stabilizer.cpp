@@ -521,10 +521,11 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         const uint8_t* wsrc = pad ? scr : frame;
         uint8_t* wdst = cz ? scr : d_out;
         // (P010 and the three-plane formats go through the one-launch kernel even for one surface: its tables are built in the
-        // stream's scratch)
+        // stream's scratch; so does NV12 under edge fill, whose instances of the general kernels read every tap from memory)
+        const YuvBorder wb = yuv_warp_border(s);
         if (rc == VS_OK)
-            rc = warp_yuv(&wsrc, &wdst, 1, warp_src_planes(s), warp_dst_planes(s, d_out, out_stride), WarpMaps{s->d_Minv, 12, false},
-                          pad ? VS_BORDER_REPLICATE : VS_BORDER_BLACK, s->fmt == VS_FMT_NV12 ? WarpTabs{} : WarpTabs{WarpTabs::SCRATCH}, st);
+            rc = warp_yuv(&wsrc, &wdst, 1, warp_src_planes(s), warp_dst_planes(s, d_out, out_stride), WarpMaps{s->d_Minv, 12, false}, wb,
+                          s->fmt == VS_FMT_NV12 && wb.border != VS_BORDER_FILL ? WarpTabs{} : WarpTabs{WarpTabs::SCRATCH}, st);
         if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
         if (fade && rc == VS_OK) rc = yuv_fade_update(s, d_out, out_stride, st);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
@@ -714,6 +715,7 @@ int prepare(vs_stab* s, int w, int h, int fmt, size_t stride) {
     if (yuv_fade_wanted(s) && s->yfade_fill_given && pixfmt(fmt)->kind != PIX_INTERLEAVED)
         VS_REFUSE(s, check_yuv_fill(*pixfmt(fmt), s->yfade_fill, "vs_stab_set_yuv_fade"));
     if (yuv_pad_wanted(s) && s->pad_fill_given && pixfmt(fmt)->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*pixfmt(fmt), s->pad_fill));
+    if (s->yuv_efill && s->efill_given && pixfmt(fmt)->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*pixfmt(fmt), s->efill, "vs_stab_set_yuv_edge_fill"));
     VS_OBJ_HIP(s, hipSetDevice(s->device));
     if (!s->allocated) return allocate(s, w, h, fmt);
     if (w != s->w || h != s->h || fmt != s->fmt) return vs_obj_fail(s, VS_ERR_SIZE_CHANGED, "frame geometry changed; call vs_stab_clean()");
@@ -1266,6 +1268,24 @@ int vs_stab_set_yuv_fade(vs_stab* s, int enable, const vs_yuv_fill* fill) {
     s->yfade_fill_given = enable && fill;
     if (s->yfade_fill_given) s->yfade_fill = *fill;
     s->yfade_valid = false; s->yfade_count = 0;
+    return VS_OK;
+}
+
+// Edge fill on YUV surfaces (NV12, P010 and the three-plane formats), off by default: with it the warps of a stream's unpadded
+// surfaces - the plain stream's, and the one into the scratch surface of crop-and-zoom - are cv::warpAffine(..., BORDER_CONSTANT,
+// fill) per plane instead of BORDER_CONSTANT 0 (green): the VS_BORDER_FILL instances of the warp kernels (k_warp.hip).  Nothing is
+// allocated and no launch is added; border pad and fade, which warp a padded surface under BORDER_REPLICATE, are not touched.
+// fill: the colour outside the picture; NULL: the format's video black.
+// (The queue rule is also what makes the lagged warps of batch mode use the fill their frames were queued under: yuv_warp_border.)
+int vs_stab_set_yuv_edge_fill(vs_stab* s, int enable, const vs_yuv_fill* fill) {
+    if (!s) return VS_ERR_INVALID_ARG;
+    VS_CALLER_DRIVES(s);
+    if (!s->q_slot.empty()) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_edge_fill: the frame queue must be empty");
+    if (fill && fill->reserved != 0) return vs_obj_fail(s, VS_ERR_INVALID_ARG, "vs_stab_set_yuv_edge_fill: fill->reserved must be 0");
+    if (enable && fill && s->allocated && s->pf->kind != PIX_INTERLEAVED) VS_REFUSE(s, check_yuv_fill(*s->pf, *fill, "vs_stab_set_yuv_edge_fill"));
+    s->yuv_efill = enable != 0;
+    s->efill_given = enable && fill;
+    if (s->efill_given) s->efill = *fill;
     return VS_OK;
 }
 

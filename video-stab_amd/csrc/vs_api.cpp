@@ -215,8 +215,11 @@ int vs_op_warp_affine(const void* d_src, size_t src_stride, size_t src_frame_byt
 }
 
 // NV12 (sample_bytes 1) and P010 (2) surfaces: one body, strides and frame distances in bytes
+// src_uv / dst_uv: bytes from a surface's luma pointer to its UV plane (0: behind the h luma rows); border VS_BORDER_FILL with `fill`:
+// vs_op_warp_affine_yuv_fill
 static int warp_affine_two_planes(const void* d_src, size_t src_stride, void* d_dst, size_t dst_stride, int w, int h, const float* M, int batch,
-                                  size_t src_frame_bytes, size_t dst_frame_bytes, void* stream, int sample_bytes) {
+                                  size_t src_frame_bytes, size_t dst_frame_bytes, void* stream, int sample_bytes, size_t src_uv = 0, size_t dst_uv = 0,
+                                  int border = VS_BORDER_BLACK, WarpFill fill = WarpFill()) {
     VS_TRY(ensure_device());
     if (!d_src || !d_dst || !M || batch <= 0) {
         set_last_error(sample_bytes == 2 ? "warp_affine_p010: invalid argument" : "warp_affine_nv12: invalid argument");
@@ -234,11 +237,11 @@ static int warp_affine_two_planes(const void* d_src, size_t src_stride, void* d_
         warp_invert(m, &Minv[12 * (size_t)b]);
         warp_invert(c, &Minv[12 * (size_t)b + 6]);
     }
-    const size_t suv = (size_t)h * src_stride, duv = (size_t)h * dst_stride;
+    const size_t suv = src_uv ? src_uv : (size_t)h * src_stride, duv = dst_uv ? dst_uv : (size_t)h * dst_stride;
     const auto ys = frame_list((const uint8_t*)d_src, src_frame_bytes, batch), us = frame_list((const uint8_t*)d_src, src_frame_bytes, batch, suv);
     const auto yd = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch), ud = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch, duv);
     return launch_warp_nv12(ys.data(), yd.data(), us.data(), ud.data(), batch, src_stride, dst_stride, w, h, WarpMaps{Minv.data(), 12, true},
-                            VS_BORDER_BLACK, WarpTabs{WarpTabs::SCRATCH}, (hipStream_t)stream, sample_bytes);
+                            border, WarpTabs{WarpTabs::SCRATCH}, (hipStream_t)stream, sample_bytes, fill);
 }
 
 int vs_op_warp_affine_nv12(const void* d_src, size_t src_stride, void* d_dst, size_t dst_stride,
@@ -259,7 +262,8 @@ int vs_op_warp_affine_p010(const void* d_src, size_t src_stride, void* d_dst, si
 // Mc = S^-1 M S, S = diag(2^sx, 2^sy): every product exact in float, then inverted in double like any matrix.
 static int warp_affine_three_planes(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst,
                                     size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch,
-                                    size_t src_frame_bytes, size_t dst_frame_bytes, int border, void* stream, int sample_bytes, int sx = 1, int sy = 1) {
+                                    size_t src_frame_bytes, size_t dst_frame_bytes, int border, void* stream, int sample_bytes, int sx = 1, int sy = 1,
+                                    WarpFill fill = WarpFill()) {
     VS_TRY(ensure_device());
     // (the default chroma pitch is the stride >> sx, and holds whole samples)
     const size_t half = sx ? 2 * (size_t)sample_bytes - 1 : 0;
@@ -288,7 +292,7 @@ static int warp_affine_three_planes(const void* d_src, size_t src_stride, size_t
     const auto ys = frame_list((const uint8_t*)d_src, src_frame_bytes, batch);
     const auto yd = frame_list((uint8_t*)d_dst, dst_frame_bytes, batch);
     return launch_warp_i420(ys.data(), yd.data(), batch, sl, dl, w, h, WarpMaps{Minv.data(), 12, true}, border, WarpTabs{WarpTabs::SCRATCH},
-                            (hipStream_t)stream, sample_bytes, sx, sy);
+                            (hipStream_t)stream, sample_bytes, sx, sy, fill);
 }
 
 int vs_op_warp_affine_i420(const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst, size_t dst_stride,
@@ -317,6 +321,30 @@ int vs_op_warp_affine_planar(int fmt, const void* d_src, size_t src_stride, size
     }
     return warp_affine_three_planes(d_src, src_stride, src_u_off, src_v_off, src_c_pitch, d_dst, dst_stride, dst_u_off, dst_v_off, dst_c_pitch, w, h, M,
                                     batch, src_frame_bytes, dst_frame_bytes, border, stream, pf->sample_bytes, pf->sx, pf->sy);
+}
+
+// The warp of edge fill on YUV streams as an operator: any YUV surface format, BORDER_CONSTANT with the fill colour.  What concerns
+// the format, the fill and null arguments is refused first, without a device; the launchers check the rest before they launch.
+int vs_op_warp_affine_yuv_fill(int fmt, const void* d_src, size_t src_stride, size_t src_u_off, size_t src_v_off, size_t src_c_pitch, void* d_dst,
+                               size_t dst_stride, size_t dst_u_off, size_t dst_v_off, size_t dst_c_pitch, int w, int h, const float* M, int batch,
+                               size_t src_frame_bytes, size_t dst_frame_bytes, const vs_yuv_fill* fill, void* stream) {
+    const PixFmt* pf = pixfmt(fmt);
+    if (!pf || pf->kind == PIX_INTERLEAVED) {
+        set_last_error("vs_op_warp_affine_yuv_fill: fmt must be a YUV surface format (NV12, P010, I420 ... I412)");
+        return VS_ERR_INVALID_ARG;
+    }
+    if (fill && fill->reserved != 0) { set_last_error("vs_op_warp_affine_yuv_fill: fill->reserved must be 0"); return VS_ERR_INVALID_ARG; }
+    const vs_yuv_fill c = fill ? *fill : yuv_video_black(*pf);
+    const Refusal r = check_yuv_fill(*pf, c, "vs_op_warp_affine_yuv_fill");
+    if (r.rc != VS_OK) { set_last_error(r.text); return r.rc; }
+    if (!d_src || !d_dst || !M || batch <= 0 || w < 1 || h < 1) { set_last_error("vs_op_warp_affine_yuv_fill: invalid argument"); return VS_ERR_INVALID_ARG; }
+    WarpFill f;
+    f.y = c.y; f.u = c.u; f.v = c.v;
+    if (pf->luma_uv())
+        return warp_affine_two_planes(d_src, src_stride, d_dst, dst_stride, w, h, M, batch, src_frame_bytes, dst_frame_bytes, stream, pf->sample_bytes,
+                                      src_u_off, dst_u_off, VS_BORDER_FILL, f);
+    return warp_affine_three_planes(d_src, src_stride, src_u_off, src_v_off, src_c_pitch, d_dst, dst_stride, dst_u_off, dst_v_off, dst_c_pitch, w, h, M,
+                                    batch, src_frame_bytes, dst_frame_bytes, VS_BORDER_FILL, stream, pf->sample_bytes, pf->sx, pf->sy, f);
 }
 
 int vs_op_resize_gray(const void* d_src, size_t src_stride, int sw, int sh, int fmt, void* d_dst,

@@ -138,6 +138,13 @@ inline void warp_invert(const T* Mf, double* inv) {
 // them: the coordinate terms are then built once per frame by a small launch in front of the warp instead of once per tile.
 constexpr int WARP_BATCH_MAX = 32;
 constexpr int WARP_TAB_MIN = 4;
+// Edge fill on YUV surfaces (vs_stab_set_yuv_edge_fill, vs_op_warp_affine_yuv_fill): BORDER_CONSTANT with a colour - a tap outside a
+// plane reads the plane's fill sample.  An internal border code of the YUV launchers (launch_warp_nv12, launch_warp_i420) behind the six
+// values of the public border_type enum, which it is not part of; it fits the three border bits of the kernels' flags.
+constexpr int VS_BORDER_FILL = 6;
+static_assert(VS_BORDER_FILL > VS_BORDER_FADE && VS_BORDER_FILL < 8, "an internal code behind the public border types, in three bits");
+// The fill of such a launch, samples as they lie in memory (8-bit formats: at most 255).  (0, 0, 0) gives VS_BORDER_BLACK's bytes.
+struct WarpFill { uint32_t y = 0, u = 0, v = 0; };
 // Ints of table workspace a launch over `frames` frames of dw x dh needs (packed tables).
 size_t warp_tabs_ints(int dw, int dh, int frames);
 // The INVERSE maps (warp_invert of the forward matrices), 6 doubles per frame and `stride` doubles from frame to frame: on the
@@ -167,8 +174,10 @@ int launch_warp_plane(const uint8_t* const* srcs, uint8_t* const* dsts, int n, s
 // planes; other launches go plane by plane.
 // sample_bytes = 2: P010 surfaces - planes of 16-bit samples, pitches and pointers in bytes and even; a call with the scratch tables
 // builds them for any number of surfaces.
+// border VS_BORDER_FILL: taps outside a plane read `fill` (Y; the (U, V) pair); with the scratch tables every launch builds them.
 int launch_warp_nv12(const uint8_t* const* ys, uint8_t* const* yd, const uint8_t* const* us, uint8_t* const* ud, int n, size_t sstride,
-                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sample_bytes = 1);
+                     size_t dstride, int w, int h, WarpMaps maps, int border, WarpTabs tabs, hipStream_t st, int sample_bytes = 1,
+                     WarpFill fill = WarpFill());
 // One warp of a multi-job launch (launch_warp_jobs, k_warp.hip): any geometry, inverse map in double on the host.
 struct WarpJob {
     const uint8_t* src;

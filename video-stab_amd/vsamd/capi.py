@@ -537,6 +537,10 @@ class VsLib:
                                                  C.POINTER(C.c_int64)]
             L.vs_op_scale_jobs_rgb.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, vp]
             L.vs_op_scale_jobs_rgb_plan.argtypes = [C.POINTER(VsScaleJob), C.c_int, i32p]
+            # edge fill on YUV streams
+            L.vs_stab_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
+            L.vs_batch_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
+            L.vs_op_warp_affine_yuv_fill.argtypes = [C.c_int] + list(L.vs_op_warp_affine_i420.argtypes[:-2]) + [C.POINTER(VsYuvFill), vp]
         except AttributeError:      # a library of an earlier build (A/B measurements)
             pass
 
@@ -671,6 +675,25 @@ class VsLib:
         d_out = DevBuf(self, img.nbytes)
         try:
             self.check(self.lib.vs_op_warp_affine_planar(fmt, d_in.ptr, sb * w, 0, 0, 0, d_out.ptr, sb * w, 0, 0, 0, w, h, _p(M, f32p), n, fb, fb, border, None))
+            self.sync()
+            return d_out.download(img.shape, dt)
+        finally:
+            d_in.free(); d_out.free()
+
+    def warp_affine_yuv_fill(self, fmt, img, w, h, M, fill=None):
+        """vs_op_warp_affine_yuv_fill on packed surfaces of any YUV format (NV12, P010, I420 ... I412): one surface and one matrix,
+        or a stack of n surfaces and n matrices.  fill: (y, u, v) samples as they lie in memory; None: the format's video black."""
+        dt = fmt_dtype(fmt)
+        img = np.ascontiguousarray(img, dt)
+        M = np.ascontiguousarray(M, np.float32).reshape(-1, 6)
+        n = M.shape[0]
+        fb = img.nbytes // n
+        sb = img.itemsize
+        c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
+        d_in = DevBuf.from_array(self, img)
+        d_out = DevBuf(self, img.nbytes)
+        try:
+            self.check(self.lib.vs_op_warp_affine_yuv_fill(fmt, d_in.ptr, sb * w, 0, 0, 0, d_out.ptr, sb * w, 0, 0, 0, w, h, _p(M, f32p), n, fb, fb, c, None))
             self.sync()
             return d_out.download(img.shape, dt)
         finally:
@@ -1718,6 +1741,12 @@ class Stabilizer:
         c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
         self.vs.check(self.lib.vs_stab_set_yuv_border_pad(self.h, int(on), c), self.h)
 
+    def set_yuv_edge_fill(self, on=True, fill=None):
+        """vs_stab_set_yuv_edge_fill: the warps of the stream's unpadded YUV surfaces read a colour outside the picture instead of 0
+        (green).  fill: (y, u, v) samples as they lie in memory; None: the format's video black."""
+        c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
+        self.vs.check(self.lib.vs_stab_set_yuv_edge_fill(self.h, int(on), c), self.h)
+
     def set_yuv_fade(self, on=True, fill=None):
         """vs_stab_set_yuv_fade: border_size with borderType "fade" on NV12 / P010 / three-plane streams (off: refused).
         fill: (y, u, v) samples as they lie in memory; None: the format's video black.  Every accepted call drops the history."""
@@ -1830,6 +1859,10 @@ class Batch:
     def set_yuv_border_pad(self, on=True, fill=None):
         c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
         self._check(self.lib.vs_batch_set_yuv_border_pad(self.h, int(on), c))
+
+    def set_yuv_edge_fill(self, on=True, fill=None):
+        c = C.byref(VsYuvFill(*fill, 0)) if fill is not None else None
+        self._check(self.lib.vs_batch_set_yuv_edge_fill(self.h, int(on), c))
 
     def push_dev(self, d_frames, w, h, stride, fmt, d_outs, out_stride):
         """d_frames / d_outs: one device pointer per stream (None: no frame for that stream).  Returns produced[]."""
