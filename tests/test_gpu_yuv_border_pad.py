@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import planar_inputs as pi
+import plane_job_refusals as pjr
 import roi
 import yuvpadref as yp
 from test_gpu_planar import _check_debug, _oracle_nv12_run, bits
@@ -101,40 +102,13 @@ def test_operator_96_mixed_jobs_in_one_launch_equal_the_jobs_one_by_one(gpu, sb)
 
 
 def test_operator_refusals(gpu):
-    d = capi.DevBuf(gpu, 1 << 16)
+    """The tables of tests/plane_job_refusals.py on a real buffer: the accepted calls launch."""
+    d = capi.DevBuf(gpu, pjr.REGION)
     d.zero()
-    S, D = d.ptr, d.ptr + 32768
-    ok = (S, 64, 20, 4, D, 128, 6, 8, 1, yp.BLACK, (16, 0))
-
-    def refused(jobs, sb, n=None, reserved=0):
-        arr = (capi.VsPadJob * max(1, len(jobs)))()
-        for a, (src, ss, sw, sh, dst, ds, bx, by, cn, border, fill) in zip(arr, jobs):
-            a.src, a.src_stride, a.sw, a.sh, a.dst, a.dst_stride, a.bx, a.by, a.cn, a.border = src, ss, sw, sh, dst, ds, bx, by, cn, border
-            a.fill[0], a.fill[1] = fill
-            a.reserved = reserved
-        rc = gpu.lib.vs_op_pad_jobs(arr, len(jobs) if n is None else n, sb, None)
-        return rc, (gpu.lib.vs_last_error() or b"").decode()
-
-    def job(**kw):
-        keys = ("src", "ss", "sw", "sh", "dst", "ds", "bx", "by", "cn", "border", "fill")
-        v = dict(zip(keys, ok))
-        v.update(kw)
-        return tuple(v[k] for k in keys)
-    assert refused([ok], 1)[0] == 0
-    assert refused([job(bx=0, by=0)], 1)[0] == 0                                                # a copy
-    for rc, msg in (refused([ok], 1, n=0), refused([ok] * 97, 1), refused([ok], 4)):
-        assert rc == INVALID and "vs_op_pad_jobs" in msg
-    for bad, word in ((job(src=None), "null"), (job(dst=None), "null"), (job(sw=0), "sizes"), (job(bx=-1), "sizes"), (job(sw=32760, ss=32760, ds=32800), "32767"),
-                      (job(by=16382, sh=4), "32767"), (job(cn=3), "cn"), (job(border=5), "border"), (job(border=-1), "border"), (job(fill=(256, 0)), "255"),
-                      (job(ss=19), "stride"), (job(ds=31), "stride"), (job(dst=S + 32), "overlap"), (job(dst=S - 0 + 64 * 3 + 10), "overlap")):
-        rc, msg = refused([ok, bad], 1)
-        assert rc == INVALID and "vs_op_pad_jobs: job 1" in msg and word in msg, (bad, msg)
-    assert refused([ok], 1, reserved=1)[0] == INVALID
-    rc, msg = refused([job(ss=65)], 2)                                                          # an odd 16-bit pitch
-    assert rc == INVALID and "job 0" in msg and "even" in msg
-    assert refused([job(src=S + 1)], 2)[0] == INVALID
-    assert refused([job(ss=65, ds=129, src=S + 1)], 1)[0] == 0                                  # (fine for bytes)
-    assert refused([job(fill=(4095, 65535))], 2)[0] == 0
+    for make in (pjr.pad,):
+        op = make(d.ptr)
+        pjr.check_accepted(gpu.lib, op, pjr.OK)
+        pjr.check_refusals(gpu.lib, op)
     gpu.sync()
     d.free()
 

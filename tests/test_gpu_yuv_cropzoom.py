@@ -10,6 +10,7 @@ import pytest
 
 import cropzoomref as cz
 import planar_inputs as pi
+import plane_job_refusals as pjr
 import ref16
 import roi
 from test_gpu_planar import _check_debug, _oracle_nv12_run, bits
@@ -89,28 +90,13 @@ def test_operator_96_mixed_jobs_in_one_launch_equal_the_jobs_one_by_one(gpu, sb)
 
 
 def test_operator_refusals(gpu):
-    d = capi.DevBuf(gpu, 1 << 16)
+    """The tables of tests/plane_job_refusals.py on a real buffer: the accepted calls launch."""
+    d = capi.DevBuf(gpu, pjr.REGION)
     d.zero()
-    ok = (d.ptr, 64, 20, 4, d.ptr + 32768, 128, 64, 48, 1)
-
-    def refused(jobs, sb, n=None):
-        arr = gpu._scale_job_array(jobs)
-        rc = gpu.lib.vs_op_resize_jobs(arr, len(jobs) if n is None else n, sb, None)
-        return rc, (gpu.lib.vs_last_error() or b"").decode()
-    assert refused([ok], 1)[0] == 0
-    for rc, msg in (refused([ok], 1, n=0), refused([ok] * 97, 1)):
-        assert rc == INVALID and "vs_op_resize_jobs" in msg
-    rc, msg = refused([ok, (d.ptr, 64, 20, 4, d.ptr + 32768, 128, 19, 48, 1)], 1)            # dw < sw
-    assert rc == UNSUPPORTED and "vs_op_resize_jobs: job 1" in msg and "not a general resize" in msg
-    rc, msg = refused([(d.ptr, 64, 20, 4, d.ptr + 32768, 128, 64, 3, 1)], 1)                  # dh < sh
-    assert rc == UNSUPPORTED and "job 0" in msg
-    rc, msg = refused([(d.ptr, 65, 20, 4, d.ptr + 32768, 128, 64, 48, 1)], 2)                 # an odd 16-bit pitch
-    assert rc == INVALID and "job 0" in msg and "even" in msg
-    assert refused([(d.ptr, 65, 20, 4, d.ptr + 32768, 129, 64, 48, 1)], 1)[0] == 0            # (fine for bytes)
-    rc, msg = refused([ok, ok, (None, 64, 20, 4, d.ptr + 32768, 128, 64, 48, 1)], 1)          # a null entry
-    assert rc == INVALID and "job 2" in msg and "null" in msg
-    assert refused([(d.ptr, 64, 20, 4, d.ptr + 32768, 128, 64, 48, 3)], 1)[0] == INVALID      # cn 3
-    assert refused([ok], 4)[0] == INVALID
+    for make in (pjr.resize,):
+        op = make(d.ptr)
+        pjr.check_accepted(gpu.lib, op, pjr.OK)
+        pjr.check_refusals(gpu.lib, op)
     gpu.sync()
     d.free()
 

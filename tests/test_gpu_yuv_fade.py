@@ -10,6 +10,7 @@ import pytest
 
 import compref
 import planar_inputs as pi
+import plane_job_refusals as pjr
 import roi
 import yuvfaderef as yf
 import yuvpadref as yp
@@ -203,43 +204,13 @@ def test_32_mixed_jobs_in_one_launch_equal_the_jobs_one_by_one(gpu, sb):
 
 
 def test_operator_refusals(gpu):
-    d = capi.DevBuf(gpu, 1 << 16)
+    """The tables of tests/plane_job_refusals.py on a real buffer: the accepted calls launch."""
+    d = capi.DevBuf(gpu, pjr.REGION)
     d.zero()
-    S, H, D = d.ptr, d.ptr + 16384, d.ptr + 32768
-    ok = dict(src=S, src_stride=64, sw=20, sh=4, hist=H, hist_stride=128, dst=D, dst_stride=128, bx=6, by=8, cn=1)
-    uok = dict(hist=H, hist_stride=128, res=D, res_stride=128, w=32, h=20, cn=1)
-
-    def blend(jobs, sb=1, n=None, alpha=0.5, beta=0.5):
-        arr = (capi.VsFadeJob * len(jobs))(*[capi.VsFadeJob(**j) for j in jobs])
-        rc = gpu.lib.vs_op_fade_blend_jobs(arr, len(jobs) if n is None else n, sb, alpha, beta, None)
-        return rc, (gpu.lib.vs_last_error() or b"").decode()
-
-    def update(jobs, sb=1, n=None):
-        arr = (capi.VsFadeUpdateJob * len(jobs))(*[capi.VsFadeUpdateJob(**j) for j in jobs])
-        rc = gpu.lib.vs_op_fade_update_jobs(arr, len(jobs) if n is None else n, sb, None)
-        return rc, (gpu.lib.vs_last_error() or b"").decode()
-    assert blend([ok])[0] == 0 and blend([dict(ok, bx=0, by=0)])[0] == 0 and blend([ok] * 32)[0] == 0 and update([uok])[0] == 0
-    for rc, msg in (blend([ok], n=0), blend([ok] * 33), blend([ok], sb=4), blend([ok], alpha=1.5), blend([ok], beta=-0.25), blend([ok], alpha=float("nan"))):
-        assert rc == INVALID and "vs_op_fade_blend_jobs" in msg
-    assert "weights" in blend([ok], alpha=1.5)[1]
-    for bad, word in ((dict(src=None), "null"), (dict(hist=None), "null"), (dict(dst=None), "null"), (dict(sw=0), "sizes"), (dict(bx=-1), "sizes"),
-                      (dict(sw=32760, src_stride=32760, hist_stride=32800, dst_stride=32800), "32767"), (dict(by=16382), "32767"), (dict(cn=3), "cn"),
-                      (dict(reserved=1), "reserved"), (dict(fill=(C.c_uint16 * 2)(0, 256)), "255"), (dict(src_stride=19), "stride"), (dict(hist_stride=31), "stride"),
-                      (dict(dst_stride=31), "stride"), (dict(dst=S + 32), "overlap"), (dict(dst=H + 128 * 19 + 31), "overlap")):
-        rc, msg = blend([ok, dict(ok, **bad)])
-        assert rc == INVALID and "vs_op_fade_blend_jobs: job 1" in msg and word in msg, (bad, msg)
-    rc, msg = blend([dict(ok, src_stride=65)], sb=2)                                            # an odd 16-bit pitch
-    assert rc == INVALID and "job 0" in msg and "even" in msg
-    assert blend([dict(ok, hist=H + 1)], sb=2)[0] == INVALID
-    assert blend([dict(ok, src_stride=65, hist_stride=129, hist=H + 1)])[0] == 0                # (fine for bytes)
-    assert blend([dict(ok, fill=(C.c_uint16 * 2)(4095, 65535))], sb=2)[0] == 0
-    for rc, msg in (update([uok], n=0), update([uok] * 33), update([uok], sb=0)):
-        assert rc == INVALID and "vs_op_fade_update_jobs" in msg
-    for bad, word in ((dict(hist=None), "null"), (dict(res=None), "null"), (dict(w=0), "sizes"), (dict(h=32768), "sizes"), (dict(cn=3), "cn"), (dict(reserved=1), "reserved"),
-                      (dict(hist_stride=31), "stride"), (dict(res_stride=31), "stride"), (dict(res=H + 64), "overlap")):
-        rc, msg = update([uok, dict(uok, **bad)])
-        assert rc == INVALID and "vs_op_fade_update_jobs: job 1" in msg and word in msg, (bad, msg)
-    assert update([dict(uok, res=D + 1)], sb=2)[0] == INVALID and update([dict(uok, res=D + 1, res_stride=129)])[0] == 0
+    for make in (pjr.fade_blend, pjr.fade_update):
+        op = make(d.ptr)
+        pjr.check_accepted(gpu.lib, op, pjr.OK)
+        pjr.check_refusals(gpu.lib, op)
     gpu.sync()
     d.free()
 

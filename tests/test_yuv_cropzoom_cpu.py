@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import cropzoomref as cz
+import plane_job_refusals as pjr
 import refusal_cases
 from vsamd import capi
 
@@ -194,3 +195,13 @@ def test_the_new_entry_points_are_exported_and_declared():
     assert vs.lib.vs_abi_version() == 2
     # refusals of the operator are decided on the host: no device is needed to get them
     assert vs.lib.vs_op_resize_jobs(None, 1, 1, None) == 1 and b"vs_op_resize_jobs" in vs.lib.vs_last_error()
+
+
+def test_the_operator_refuses_on_the_host_and_needs_a_device_after_that():
+    """A bad argument is answered before a device is looked for, so the addresses of tests/plane_job_refusals.py are never read; with
+    good arguments and no device the answer is VS_ERR_NO_DEVICE."""
+    L = capi.load().lib
+    op = pjr.resize(pjr.FAKE_BASE)
+    pjr.check_refusals(L, op)
+    if L.vs_device_count() <= 0:
+        pjr.check_accepted(L, op, pjr.NO_DEVICE)

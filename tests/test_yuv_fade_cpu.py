@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import compref
+import plane_job_refusals as pjr
 import refusal_cases
 import yuvfaderef as yf
 import yuvpadref as yp
@@ -268,39 +269,10 @@ def test_the_operators_refuse_on_the_host_and_need_a_device_after_that():
     """A bad argument is answered before a device is looked for, so the addresses below are never read; with good arguments and no
     device the answer is VS_ERR_NO_DEVICE.  (A stream cannot be created without a device, so the setter has no object to take: a
     null one is VS_ERR_INVALID_ARG.)"""
-    vs = capi.load()
-    L, S, H, D = vs.lib, 0x10000, 0x20000, 0x30000
-
-    def blend(n=1, sb=1, alpha=0.5, beta=0.5, **kw):
-        j = capi.VsFadeJob(src=S, src_stride=64, sw=20, sh=4, hist=H, hist_stride=128, dst=D, dst_stride=128, bx=6, by=8, cn=1)
-        for k, v in kw.items():
-            setattr(j, k, v)
-        rc = L.vs_op_fade_blend_jobs(C.byref(j), n, sb, alpha, beta, None)
-        return rc, (L.vs_last_error() or b"").decode()
-
-    def update(n=1, sb=1, **kw):
-        j = capi.VsFadeUpdateJob(hist=H, hist_stride=128, res=D, res_stride=128, w=32, h=20, cn=1)
-        for k, v in kw.items():
-            setattr(j, k, v)
-        rc = L.vs_op_fade_update_jobs(C.byref(j), n, sb, None)
-        return rc, (L.vs_last_error() or b"").decode()
-    assert L.vs_op_fade_blend_jobs(None, 1, 1, 0.5, 0.5, None) == 1 and b"vs_op_fade_blend_jobs" in L.vs_last_error()
-    assert L.vs_op_fade_update_jobs(None, 1, 1, None) == 1 and b"vs_op_fade_update_jobs" in L.vs_last_error()
-    for rc, msg in (blend(n=0), blend(n=33), blend(sb=4), blend(alpha=-0.1), blend(beta=1.5), blend(alpha=float("nan"))):
-        assert rc == 1 and "vs_op_fade_blend_jobs" in msg, msg
-    for kw, word in ((dict(src=None), "null"), (dict(hist=None), "null"), (dict(dst=None), "null"), (dict(sw=0), "sizes"), (dict(by=16382), "32767"),
-                     (dict(cn=3), "cn"), (dict(reserved=1), "reserved"), (dict(fill=(C.c_uint16 * 2)(256, 0)), "255"), (dict(src_stride=19), "stride"),
-                     (dict(hist_stride=31), "stride"), (dict(dst_stride=31), "stride"), (dict(dst=S + 32), "overlap"), (dict(dst=H + 128 * 19 + 31), "overlap")):
-        rc, msg = blend(**kw)
-        assert rc == 1 and "vs_op_fade_blend_jobs: job 0" in msg and word in msg, (kw, msg)
-    assert blend(sb=2, src_stride=65)[0] == 1 and "even" in blend(sb=2, src=S + 1)[1] and blend(sb=2, hist_stride=129)[0] == 1
-    for rc, msg in (update(n=0), update(n=33), update(sb=3)):
-        assert rc == 1 and "vs_op_fade_update_jobs" in msg, msg
-    for kw, word in ((dict(hist=None), "null"), (dict(res=None), "null"), (dict(w=0), "sizes"), (dict(h=32768), "sizes"), (dict(cn=0), "cn"),
-                     (dict(reserved=2), "reserved"), (dict(hist_stride=31), "stride"), (dict(res_stride=31), "stride"), (dict(res=H + 64), "overlap")):
-        rc, msg = update(**kw)
-        assert rc == 1 and "vs_op_fade_update_jobs: job 0" in msg and word in msg, (kw, msg)
-    assert update(sb=2, res=D + 1)[0] == 1 and update(sb=2, hist_stride=129)[0] == 1
+    L = capi.load().lib
+    for make in (pjr.fade_blend, pjr.fade_update):
+        op = make(pjr.FAKE_BASE)
+        pjr.check_refusals(L, op)
+        if L.vs_device_count() <= 0:
+            pjr.check_accepted(L, op, pjr.NO_DEVICE)
     assert L.vs_stab_set_yuv_fade(None, 1, None) == 1
-    if L.vs_device_count() <= 0:
-        assert blend()[0] == 2 and blend(sb=2, alpha=0.0, beta=1.0)[0] == 2 and update()[0] == 2 and update(sb=2)[0] == 2

@@ -3,10 +3,8 @@
 // dh >= sh); the definition is in include/vs_stab.h (cv::resize INTER_LINEAR as oracle/vso_resize_linear_u8 states it for 8-bit
 // samples, the same coordinates and coefficients with ONE exact rounding for 16-bit samples; tests/cropzoomref.py in numpy).
 //
-// One launch takes up to CZ_MAX_JOBS jobs of one sample size, cn 1 and 2 mixed.  It is a flat sequence of (job, tile row, tile
-// column) tiles in the XCD-aware order of k_warp.hip (tile_id): workgroup `lin` takes tile seq(lin), XCD c = lin mod 8 the c-th
-// contiguous eighth of the sequence, so that the tiles that share source lines meet in one L2.  The jobs travel as kernel
-// arguments (40 bytes each); a workgroup finds its job by bisection over the jobs' first tiles (scalar loads).
+// One launch takes up to CZ_MAX_JOBS jobs in the scheme of plane_jobs.h (40 bytes of kernel arguments each); the order of the
+// sequence lets the tiles that share source lines meet in one L2.
 //
 // A tile is CZ_TB bytes of CZ_TR destination rows.  A lane owns the CZ_LB bytes at one place of CZ_R consecutive rows (a wave: 64
 // lanes side by side, so a row of a wave is one 256-byte run).  What belongs to its columns - source columns, the coefficient
@@ -26,8 +24,7 @@
 // aligned non-temporal dwords where the lane's four bytes are all inside the row and aligned, else sample by sample.
 #include <hip/hip_runtime.h>
 
-#include "launchers.h"
-#include "vs_common.h"
+#include "plane_jobs.h"
 
 namespace vsd {
 namespace {
@@ -68,12 +65,6 @@ __device__ __forceinline__ int cz_coord(int d, double scale, float* f) {
     return s;
 }
 __device__ __forceinline__ double cz_scale(int s, int d) { return 1. / ((double)d / (double)s); }
-
-template <int SB>
-__device__ __forceinline__ uint32_t cz_ld(const uint8_t* p) {
-    if constexpr (SB == 1) return *p;
-    else return *reinterpret_cast<const uint16_t*>(p);
-}
 
 template <int SB, int CN>
 __device__ __forceinline__ void cz_tile(const CzJob& J, int tx, int ty, uint32_t* s_y, uint32_t* s_b) {
@@ -158,8 +149,8 @@ __device__ __forceinline__ void cz_tile(const CzJob& J, int tx, int ty, uint32_t
                 const uint8_t* p = rp + (size_t)sx[k] * PB;
 #pragma unroll
                 for (int c = 0; c < CN; c++) {
-                    const uint32_t v0 = cz_ld<SB>(p + SB * c);
-                    const uint32_t v1 = a1[k] ? cz_ld<SB>(p + PB + SB * c) : 0u;       // (a1 == 0: at the edge, or a weight of nothing)
+                    const uint32_t v0 = pj_ld<SB>(p + SB * c);
+                    const uint32_t v1 = a1[k] ? pj_ld<SB>(p + PB + SB * c) : 0u;       // (a1 == 0: at the edge, or a weight of nothing)
                     H[k * CN + c] = v0 * a0[k] + v1 * a1[k];
                 }
             }
@@ -226,73 +217,41 @@ __device__ __forceinline__ void cz_tile(const CzJob& J, int tx, int ty, uint32_t
 template <int SB>
 __global__ __launch_bounds__(64 * CZ_WAVES) void cropzoom_kernel(const CzArgs a) {
     __shared__ uint32_t s_y[CZ_TR], s_b[CZ_TR];
-    // XCD-aware order (k_warp.hip, tile_id): XCD c = lin mod 8 takes the c-th contiguous eighth of the sequence
-    const uint32_t lin = blockIdx.x, n = a.tiles;
-    const uint32_t c = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-    const uint32_t seq = c * q + (c < r ? c : r) + k;
-    // the job of tile seq: the last one whose first tile is not behind it
-    uint32_t jl = 0, jh = a.n - 1;
-    while (jl < jh) {
-        const uint32_t mid = (jl + jh + 1) >> 1;
-        if (a.j[mid].tile0 <= seq) jl = mid;
-        else jh = mid - 1;
-    }
-    const CzJob J = a.j[jl];
-    const uint32_t t = seq - J.tile0;
-    const uint32_t gx = ((J.dwh & 0xffffu) * J.cn * SB + CZ_TB - 1) / CZ_TB;
-    const int ty = (int)(t / gx), tx = (int)(t - (uint32_t)ty * gx);
-    if (J.cn == 1) cz_tile<SB, 1>(J, tx, ty, s_y, s_b);
-    else cz_tile<SB, 2>(J, tx, ty, s_y, s_b);
+    const uint32_t seq = pj_seq(blockIdx.x, a.tiles);
+    const CzJob J = a.j[pj_find(a, seq, [](const CzJob& j) { return j.tile0; })];
+    const PjTile t = pj_split(seq - J.tile0, (J.dwh & 0xffffu) * J.cn * SB, CZ_TB);
+    if (J.cn == 1) cz_tile<SB, 1>(J, t.tx, t.ty, s_y, s_b);
+    else cz_tile<SB, 2>(J, t.tx, t.ty, s_y, s_b);
 }
 
-// What the operator refuses about a job, decided before any device call; "" = accepted.
-std::string cz_job_refusal(const vs_scale_job& s, int sample_bytes, int* rc) {
-    *rc = VS_ERR_INVALID_ARG;
+// What the operator refuses about a job, decided before any device call; nullptr = accepted.
+const char* cz_job_refusal(const vs_scale_job& s, int sample_bytes, int* rc) {
     if (!s.src || !s.dst) return "a null src or dst";
-    if (s.sw < 1 || s.sh < 1 || s.dw < 1 || s.dh < 1 || s.sw > 32767 || s.sh > 32767 || s.dw > 32767 || s.dh > 32767) return "sizes must be 1 .. 32767";
-    if ((s.cn != 1 && s.cn != 2) || s.reserved != 0) return "cn must be 1 or 2 and reserved 0";
-    if (s.src_stride > UINT32_MAX || s.dst_stride > UINT32_MAX || s.src_stride < (size_t)s.sw * s.cn * sample_bytes ||
-        s.dst_stride < (size_t)s.dw * s.cn * sample_bytes)
-        return "a stride does not hold a row (or exceeds 32 bits)";
-    if (sample_bytes == 2 && (((uintptr_t)s.src | (uintptr_t)s.dst | s.src_stride | s.dst_stride) & 1)) return "16-bit pointers and strides must be even";
+    if (const char* why = pj_bad_sizes({s.sw, s.sh, s.dw, s.dh})) return why;
+    if (const char* why = pj_bad_cn(s.cn, s.reserved)) return why;
+    if (const char* why = pj_bad_strides({{s.src_stride, (size_t)s.sw * s.cn * sample_bytes}, {s.dst_stride, (size_t)s.dw * s.cn * sample_bytes}})) return why;
+    if (const char* why = pj_bad_parity(sample_bytes, (uintptr_t)s.src | (uintptr_t)s.dst | s.src_stride | s.dst_stride)) return why;
     if (s.dw < s.sw || s.dh < s.sh) {
         *rc = VS_ERR_UNSUPPORTED;
         return "dw >= sw and dh >= sh (this operator is the zoom-in of crop-and-zoom, not a general resize)";
     }
-    *rc = VS_OK;
-    return std::string();
+    return nullptr;
 }
 
 }  // namespace
 
 int launch_cropzoom(const vs_scale_job* jobs, int n, int sample_bytes, hipStream_t st) {
-    if (!jobs || n < 1 || n > CZ_MAX_JOBS || (sample_bytes != 1 && sample_bytes != 2)) {
-        set_last_error("vs_op_resize_jobs: invalid argument (1 .. 96 jobs of one sample size, 1 or 2 bytes)");
-        return VS_ERR_INVALID_ARG;
-    }
     CzArgs a{};
-    uint64_t tiles = 0;
-    for (int i = 0; i < n; i++) {
-        const vs_scale_job& s = jobs[i];
-        int rc;
-        const std::string why = cz_job_refusal(s, sample_bytes, &rc);
-        if (rc != VS_OK) {
-            set_last_error("vs_op_resize_jobs: job " + std::to_string(i) + ": " + why);
-            return rc;
-        }
-        CzJob& j = a.j[i];
-        j.src = (const uint8_t*)s.src; j.dst = (uint8_t*)s.dst;
-        j.sstride = (uint32_t)s.src_stride; j.dstride = (uint32_t)s.dst_stride;
-        j.swh = (uint32_t)s.sw | (uint32_t)s.sh << 16; j.dwh = (uint32_t)s.dw | (uint32_t)s.dh << 16;
-        j.tile0 = (uint32_t)tiles; j.cn = (uint32_t)s.cn;
-        tiles += (uint64_t)(((size_t)s.dw * s.cn * sample_bytes + CZ_TB - 1) / CZ_TB) * (uint64_t)((s.dh + CZ_TR - 1) / CZ_TR);
-    }
-    a.n = (uint32_t)n; a.tiles = (uint32_t)tiles;      // (96 jobs of at most 512 x 1024 tiles)
-    VS_TRY(ensure_device());
-    if (sample_bytes == 1) hipLaunchKernelGGL(cropzoom_kernel<1>, dim3((unsigned)tiles), dim3(64, CZ_WAVES), 0, st, a);
-    else hipLaunchKernelGGL(cropzoom_kernel<2>, dim3((unsigned)tiles), dim3(64, CZ_WAVES), 0, st, a);
-    VS_HIP_TRY(hipGetLastError());
-    return VS_OK;
+    return pj_launch(
+        "vs_op_resize_jobs", jobs, n, CZ_MAX_JOBS, sample_bytes, a, cz_job_refusal,
+        [&](const vs_scale_job& s, CzJob& j, uint32_t tile0) {      // (96 jobs of at most 512 x 1024 tiles)
+            j.src = (const uint8_t*)s.src; j.dst = (uint8_t*)s.dst;
+            j.sstride = (uint32_t)s.src_stride; j.dstride = (uint32_t)s.dst_stride;
+            j.swh = (uint32_t)s.sw | (uint32_t)s.sh << 16; j.dwh = (uint32_t)s.dw | (uint32_t)s.dh << 16;
+            j.tile0 = tile0; j.cn = (uint32_t)s.cn;
+            return pj_tiles((size_t)s.dw * s.cn * sample_bytes, s.dh, CZ_TB, CZ_TR);
+        },
+        [&](auto sb, const CzArgs& args, unsigned tiles) { hipLaunchKernelGGL(cropzoom_kernel<decltype(sb)::value>, dim3(tiles), dim3(64, CZ_WAVES), 0, st, args); });
 }
 
 }  // namespace vsd

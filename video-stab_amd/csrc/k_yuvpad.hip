@@ -3,12 +3,9 @@
 // cv::copyMakeBorder per plane as tests/compref.py states it (border_index), with a fill sample per channel where the reference
 // writes 0 (VS_BORDER_BLACK); tests/yuvpadref.py in numpy.  It is a copy with an index map: no arithmetic on the samples.
 //
-// One launch takes up to YP_MAX_JOBS jobs of one sample size, cn 1 and 2 mixed.  It is a flat sequence of (job, tile row, tile
-// column) tiles in the XCD-aware order of k_warp.hip (tile_id): workgroup `lin` takes tile seq(lin), XCD c = lin mod 8 the c-th
-// contiguous eighth of the sequence.  The jobs travel as kernel arguments (40 bytes each); a workgroup finds its job by bisection
-// over the jobs' first tiles (scalar loads).
+// One launch takes up to YP_MAX_JOBS jobs in the scheme of plane_jobs.h (40 bytes of kernel arguments each).
 //
-// A tile is 128 bytes x 256 destination rows (8-bit samples) or 256 bytes x 128 rows (16-bit).  A lane owns the YP_LB = 16 bytes at
+// A tile is 128 bytes x 256 destination rows (8-bit samples) or 256 bytes x 128 rows (16-bit).  A lane owns the PJ_LB = 16 bytes at
 // one place of YP_R rows; a wave is 8 (16) lanes side by side times 8 (4) rows, so that the lanes that gather - those at the left and
 // right border of a plane - share their waves with few others: with 64 lanes side by side half the waves of a 4K luma plane held such
 // a lane and ran its sample-by-sample path for all.  The source pixel of each of a gathering lane's pixels (or -1: the fill) is computed once per
@@ -23,15 +20,19 @@
 //
 // Stores are 16-byte non-temporal where the lane's 16 bytes are inside the row and the address is 16-byte aligned, else sample by
 // sample.  No load touches a byte outside the sw x sh samples of the source plane, no store a byte outside the padded plane.
+//
+// The sample-by-sample store is plane_jobs.h's pj_scatter written out here: through the shared function the two instances kept their
+// instructions but not their order and registers (about 260 / 100 instructions moved inside their blocks), and the 16-bit launches
+// of scratch/pad_measure.py then took 0.3 - 1 % longer than the parent's in both of two alternated runs (P010 reflect 0.2847 / 0.2844
+// ms against 0.2829 / 0.2814, outside the parent's own windows).  Written out, both instances are the parent's but for one commuted
+// scalar add.
 #include <hip/hip_runtime.h>
 
-#include "launchers.h"
-#include "vs_common.h"
+#include "plane_jobs.h"
 
 namespace vsd {
 namespace {
 
-constexpr int YP_LB = 16;                    // destination bytes per lane and row
 constexpr int YP_R = 8;                      // rows per lane
 constexpr int YP_WAVES = 4;
 // A wave is cl lanes side by side times 64 / cl rows.  8-bit samples: 8 lanes (128 bytes of a row); 16-bit samples: 16 lanes (256
@@ -39,8 +40,8 @@ constexpr int YP_WAVES = 4;
 // 1.46 with 16 and 1.8 - 2.2 with 64; P010 0.95 - 1.00 with 16 against 1.07 - 1.10 with 8 (a gathering lane loads 16 bytes one by
 // one, but only 8 words).
 constexpr int yp_cl(int sb) { return sb == 1 ? 8 : 16; }
-constexpr int yp_tb(int sb) { return yp_cl(sb) * YP_LB; }                        // tile: bytes ...
-constexpr int yp_tr(int sb) { return YP_WAVES * YP_R * (64 / yp_cl(sb)); }       // ... and rows
+constexpr int yp_tb(int sb) { return pj_tb(yp_cl(sb)); }
+constexpr int yp_tr(int sb) { return pj_tr(YP_WAVES, YP_R, yp_cl(sb)); }
 
 struct YpJob {
     const uint8_t* src;
@@ -61,9 +62,6 @@ constexpr uint32_t YP_T0_MASK = 0xffffffu;
 static_assert(96ull * ((32767ull * 2 + yp_tb(1) - 1) / yp_tb(1)) * ((32767 + yp_tr(1) - 1) / yp_tr(1)) <= YP_T0_MASK &&
                   96ull * ((32767ull * 4 + yp_tb(2) - 1) / yp_tb(2)) * ((32767 + yp_tr(2) - 1) / yp_tr(2)) <= YP_T0_MASK,
               "a launch's tiles fit 24 bits");
-
-typedef uint32_t yp_u4 __attribute__((ext_vector_type(4)));
-struct __attribute__((packed, aligned(1))) yp_q1 { uint32_t x, y, z, w; };    // 16 bytes at any address: ONE global_load_dwordx4 (gfx9 global loads take unaligned addresses)
 
 // cv::borderInterpolate in closed form (tests/compref.py, border_index): the source index of coordinate p on an axis of n samples,
 // -1 where the fill applies.  Reflections that fold more than once (an axis shorter than its border) are the same modulus.
@@ -92,15 +90,9 @@ __device__ __forceinline__ int yp_map(int p, int n, int border) {
     return m < n ? m : period - m;
 }
 
-template <int SB>
-__device__ __forceinline__ uint32_t yp_ld(const uint8_t* p) {
-    if constexpr (SB == 1) return *p;
-    else return *reinterpret_cast<const uint16_t*>(p);
-}
-
 template <int SB, int CN>
 __device__ __forceinline__ void yp_tile(const YpJob& J, int tx, int ty) {
-    constexpr int NEL = YP_LB / SB;                   // samples of a lane per row
+    constexpr int NEL = PJ_LB / SB;                   // samples of a lane per row
     constexpr int NPX = NEL / CN;                     // pixels
     constexpr int PB = SB * CN;                       // bytes of a pixel
     constexpr int SPD = 4 / SB;                       // samples per dword
@@ -111,11 +103,10 @@ __device__ __forceinline__ void yp_tile(const YpJob& J, int tx, int ty) {
     const int lane = threadIdx.x & (YP_CL - 1), sub = threadIdx.x / YP_CL, wave = threadIdx.y;
     const uint32_t fills[2] = {J.fill & 0xffffu, J.fill >> 16};
 
-    const int e0 = (tx * YP_CL + lane) * YP_LB;          // first byte of the lane in the destination row
-    const int nvb = min(YP_LB, dw * PB - e0);         // its bytes inside the row (a multiple of PB)
-    if (nvb <= 0) return;
-    const int px0 = e0 / PB;                          // its first pixel
-    const bool interior = px0 >= bx && px0 + NPX <= bx + sw;      // (then nvb == YP_LB)
+    const PjLane L = pj_lane<YP_CL, PB>(tx, lane, dw);      // the lane in the destination row
+    if (L.nvb <= 0) return;
+    const int e0 = L.e0, px0 = L.px0(PB);
+    const bool interior = px0 >= bx && px0 + NPX <= bx + sw;      // (then L.full())
     // the lane's columns, for the lanes that gather: the source pixel of each of its pixels, -1 where the fill applies (pixels past
     // the row repeat its last one; they are not stored).  Waves of interior lanes skip this.
     int cx[NPX];
@@ -126,12 +117,7 @@ __device__ __forceinline__ void yp_tile(const YpJob& J, int tx, int ty) {
         for (int k = 0; k < NPX; k++) cx[k] = yp_map(min(px0 + k, dw - 1) - bx, sw, border);
     }
 
-    // the fill of a lane's 16 bytes
-    uint32_t fq;
-    if constexpr (SB == 1 && CN == 1) fq = fills[0] * 0x01010101u;
-    else if constexpr (SB == 1) fq = (fills[0] | fills[1] << 8) * 0x00010001u;
-    else if constexpr (CN == 1) fq = fills[0] * 0x00010001u;
-    else fq = J.fill;
+    const uint32_t fq = pj_fill_dword<SB, CN>(fills, J.fill);
 
 #pragma unroll 1
     for (int r = 0; r < YP_R; r++) {
@@ -146,8 +132,7 @@ __device__ __forceinline__ void yp_tile(const YpJob& J, int tx, int ty) {
             const uint8_t* __restrict__ rp = J.src + (size_t)sy * J.sstride;
             if (interior) {
                 // exactly the lane's 16 source bytes, wherever they start
-                const yp_q1 q = *reinterpret_cast<const yp_q1*>(rp + (size_t)(px0 - bx) * PB);
-                o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+                pj_load16<pj_q1>(rp + (size_t)(px0 - bx) * PB, o);
             } else {
                 o[0] = o[1] = o[2] = o[3] = 0;
 #pragma unroll
@@ -155,20 +140,19 @@ __device__ __forceinline__ void yp_tile(const YpJob& J, int tx, int ty) {
 #pragma unroll
                     for (int c = 0; c < CN; c++) {
                         const int i = k * CN + c;
-                        const uint32_t v = cx[k] < 0 ? fills[c] : yp_ld<SB>(rp + ((size_t)cx[k] * CN + c) * SB);
+                        const uint32_t v = cx[k] < 0 ? fills[c] : pj_ld<SB>(rp + ((size_t)cx[k] * CN + c) * SB);
                         o[i / SPD] |= v << (8 * SB * (i % SPD));
                     }
                 }
             }
         }
-        if (nvb == YP_LB && ((uintptr_t)dp & 15) == 0) {
-            yp_u4 q;
-            q.x = o[0]; q.y = o[1]; q.z = o[2]; q.w = o[3];
-            __builtin_nontemporal_store(q, reinterpret_cast<yp_u4*>(dp));
+        if (L.full() && ((uintptr_t)dp & 15) == 0) {
+            __builtin_nontemporal_store(pj_pack16(o), reinterpret_cast<pj_u4*>(dp));
         } else {
+            // pj_scatter, written out (see the head of the file)
 #pragma unroll
             for (int i = 0; i < NEL; i++) {
-                if (i * SB < nvb) {
+                if (i * SB < L.nvb) {
                     const uint32_t v = o[i / SPD] >> (8 * SB * (i % SPD));
                     if constexpr (SB == 1) dp[i] = (uint8_t)v;
                     else reinterpret_cast<uint16_t*>(dp)[i] = (uint16_t)v;
@@ -180,78 +164,45 @@ __device__ __forceinline__ void yp_tile(const YpJob& J, int tx, int ty) {
 
 template <int SB>
 __global__ __launch_bounds__(64 * YP_WAVES) void yuvpad_kernel(const YpArgs a) {
-    // XCD-aware order (k_warp.hip, tile_id): XCD c = lin mod 8 takes the c-th contiguous eighth of the sequence
-    const uint32_t lin = blockIdx.x, n = a.tiles;
-    const uint32_t c = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-    const uint32_t seq = c * q + (c < r ? c : r) + k;
-    // the job of tile seq: the last one whose first tile is not behind it
-    uint32_t jl = 0, jh = a.n - 1;
-    while (jl < jh) {
-        const uint32_t mid = (jl + jh + 1) >> 1;
-        if ((a.j[mid].t0f & YP_T0_MASK) <= seq) jl = mid;
-        else jh = mid - 1;
-    }
-    const YpJob J = a.j[jl];
-    const uint32_t t = seq - (J.t0f & YP_T0_MASK);
+    const uint32_t seq = pj_seq(blockIdx.x, a.tiles);
+    const YpJob J = a.j[pj_find(a, seq, [](const YpJob& j) { return j.t0f & YP_T0_MASK; })];
     const uint32_t cn = ((J.t0f >> 24) & 1u) + 1u;
     const uint32_t dw = (J.swh & 0xffffu) + 2u * (J.bxy & 0xffffu);
-    const uint32_t gx = (dw * cn * SB + yp_tb(SB) - 1) / yp_tb(SB);
-    const int ty = (int)(t / gx), tx = (int)(t - (uint32_t)ty * gx);
-    if (cn == 1) yp_tile<SB, 1>(J, tx, ty);
-    else yp_tile<SB, 2>(J, tx, ty);
+    const PjTile t = pj_split(seq - (J.t0f & YP_T0_MASK), dw * cn * SB, yp_tb(SB));
+    if (cn == 1) yp_tile<SB, 1>(J, t.tx, t.ty);
+    else yp_tile<SB, 2>(J, t.tx, t.ty);
 }
 
-// What the operator refuses about a job, decided before any device call; "" = accepted.
-std::string yp_job_refusal(const vs_pad_job& s, int sample_bytes) {
+// What the operator refuses about a job, decided before any device call; nullptr = accepted.
+const char* yp_job_refusal(const vs_pad_job& s, int sample_bytes, int*) {
     if (!s.src || !s.dst) return "a null src or dst";
-    if (s.sw < 1 || s.sh < 1 || s.bx < 0 || s.by < 0 || s.bx > 32767 || s.by > 32767 || (int64_t)s.sw + 2 * (int64_t)s.bx > 32767 ||
-        (int64_t)s.sh + 2 * (int64_t)s.by > 32767)
-        return "sizes must be at least 1, borders at least 0 and padded sizes at most 32767";
-    if ((s.cn != 1 && s.cn != 2) || s.reserved != 0) return "cn must be 1 or 2 and reserved 0";
+    if (const char* why = pj_bad_padded_sizes(s.sw, s.sh, s.bx, s.by)) return why;
+    if (const char* why = pj_bad_cn(s.cn, s.reserved)) return why;
     if (s.border < VS_BORDER_BLACK || s.border > VS_BORDER_WRAP) return "border must be VS_BORDER_BLACK .. VS_BORDER_WRAP";
-    if (sample_bytes == 1 && (s.fill[0] > 255 || s.fill[1] > 255)) return "a fill sample above 255 for 8-bit samples";
+    if (const char* why = pj_bad_fill(s.fill, sample_bytes)) return why;
     const size_t srow = (size_t)s.sw * s.cn * sample_bytes, drow = (size_t)(s.sw + 2 * s.bx) * s.cn * sample_bytes;
-    if (s.src_stride > UINT32_MAX || s.dst_stride > UINT32_MAX || s.src_stride < srow || s.dst_stride < drow)
-        return "a stride does not hold a row (or exceeds 32 bits)";
-    if (sample_bytes == 2 && (((uintptr_t)s.src | (uintptr_t)s.dst | s.src_stride | s.dst_stride) & 1)) return "16-bit pointers and strides must be even";
-    const uintptr_t s0 = (uintptr_t)s.src, s1 = s0 + (size_t)(s.sh - 1) * s.src_stride + srow;
-    const uintptr_t d0 = (uintptr_t)s.dst, d1 = d0 + (size_t)(s.sh + 2 * s.by - 1) * s.dst_stride + drow;
-    if (s0 < d1 && d0 < s1) return "source and destination overlap";
-    return std::string();
+    if (const char* why = pj_bad_strides({{s.src_stride, srow}, {s.dst_stride, drow}})) return why;
+    if (const char* why = pj_bad_parity(sample_bytes, (uintptr_t)s.src | (uintptr_t)s.dst | s.src_stride | s.dst_stride)) return why;
+    if (pj_overlap((uintptr_t)s.src, pj_end(s.src, s.src_stride, s.sh, srow), (uintptr_t)s.dst, pj_end(s.dst, s.dst_stride, s.sh + 2 * s.by, drow)))
+        return "source and destination overlap";
+    return nullptr;
 }
 
 }  // namespace
 
 int launch_yuvpad(const vs_pad_job* jobs, int n, int sample_bytes, hipStream_t st) {
-    if (!jobs || n < 1 || n > YP_MAX_JOBS || (sample_bytes != 1 && sample_bytes != 2)) {
-        set_last_error("vs_op_pad_jobs: invalid argument (1 .. 96 jobs of one sample size, 1 or 2 bytes)");
-        return VS_ERR_INVALID_ARG;
-    }
     YpArgs a{};
-    uint64_t tiles = 0;
-    for (int i = 0; i < n; i++) {
-        const vs_pad_job& s = jobs[i];
-        const std::string why = yp_job_refusal(s, sample_bytes);
-        if (!why.empty()) {
-            set_last_error("vs_op_pad_jobs: job " + std::to_string(i) + ": " + why);
-            return VS_ERR_INVALID_ARG;
-        }
-        YpJob& j = a.j[i];
-        j.src = (const uint8_t*)s.src; j.dst = (uint8_t*)s.dst;
-        j.sstride = (uint32_t)s.src_stride; j.dstride = (uint32_t)s.dst_stride;
-        j.swh = (uint32_t)s.sw | (uint32_t)s.sh << 16; j.bxy = (uint32_t)s.bx | (uint32_t)s.by << 16;
-        j.t0f = (uint32_t)tiles | (uint32_t)(s.cn - 1) << 24 | (uint32_t)s.border << 25;
-        j.fill = (uint32_t)s.fill[0] | (uint32_t)s.fill[1] << 16;
-        const int dw = s.sw + 2 * s.bx, dh = s.sh + 2 * s.by;
-        const int tb = yp_tb(sample_bytes), tr = yp_tr(sample_bytes);
-        tiles += (uint64_t)(((size_t)dw * s.cn * sample_bytes + tb - 1) / tb) * (uint64_t)((dh + tr - 1) / tr);
-    }
-    a.n = (uint32_t)n; a.tiles = (uint32_t)tiles;
-    VS_TRY(ensure_device());
-    if (sample_bytes == 1) hipLaunchKernelGGL(yuvpad_kernel<1>, dim3((unsigned)tiles), dim3(64, YP_WAVES), 0, st, a);
-    else hipLaunchKernelGGL(yuvpad_kernel<2>, dim3((unsigned)tiles), dim3(64, YP_WAVES), 0, st, a);
-    VS_HIP_TRY(hipGetLastError());
-    return VS_OK;
+    return pj_launch(
+        "vs_op_pad_jobs", jobs, n, YP_MAX_JOBS, sample_bytes, a, yp_job_refusal,
+        [&](const vs_pad_job& s, YpJob& j, uint32_t tile0) {
+            j.src = (const uint8_t*)s.src; j.dst = (uint8_t*)s.dst;
+            j.sstride = (uint32_t)s.src_stride; j.dstride = (uint32_t)s.dst_stride;
+            j.swh = (uint32_t)s.sw | (uint32_t)s.sh << 16; j.bxy = (uint32_t)s.bx | (uint32_t)s.by << 16;
+            j.t0f = tile0 | (uint32_t)(s.cn - 1) << 24 | (uint32_t)s.border << 25;
+            j.fill = (uint32_t)s.fill[0] | (uint32_t)s.fill[1] << 16;
+            return pj_tiles((size_t)(s.sw + 2 * s.bx) * s.cn * sample_bytes, s.sh + 2 * s.by, yp_tb(sample_bytes), yp_tr(sample_bytes));
+        },
+        [&](auto sb, const YpArgs& args, unsigned tiles) { hipLaunchKernelGGL(yuvpad_kernel<decltype(sb)::value>, dim3(tiles), dim3(64, YP_WAVES), 0, st, args); });
 }
 
 }  // namespace vsd

@@ -105,6 +105,8 @@ inline YuvDepth yuv_depth(const PixFmt& sf, const PixFmt& df, bool round) {
 int launch_cvt_yuv_to_yuv(const PixFmt& sf, const void* const* src, const I420Layout& in, const PixFmt& df, void* const* dst, const I420Layout& out,
                           int n, int w, int h, const YuvDepth& depth, bool mean, hipStream_t st);
 
+// ---- the plane-job operators on YUV surfaces (k_cropzoom.hip, k_yuvpad.hip, k_yuvfade.hip): what their kernels and launchers share -
+// tile sequence, job search, launch check, the sentences of the refusals - is in plane_jobs.h.
 // ---- k_cropzoom.hip: the zoom of crop-and-zoom on YUV surfaces (vs_op_resize_jobs; a stream with vs_stab_set_yuv_crop_zoom)
 // n <= CZ_MAX_JOBS crops (src = the crop's first sample, sw x sh) resized to their planes (dw x dh, dw >= sw, dh >= sh) in ONE launch:
 // 32 surfaces of up to three planes; cn 1 and 2 may be mixed, the sample size is the launch's.  Checks every job on the host first
