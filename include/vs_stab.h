@@ -52,7 +52,8 @@ extern "C" {
  *    border pad on YUV streams: struct vs_yuv_fill with vs_stab_set_yuv_border_pad, vs_batch_set_yuv_border_pad and
  *    vs_yuv_video_black, struct vs_pad_job with vs_op_pad_jobs; the fade border on YUV streams: vs_stab_set_yuv_fade, struct
  *    vs_fade_job with vs_op_fade_blend_jobs, struct vs_fade_update_job with vs_op_fade_update_jobs; edge fill on YUV streams:
- *    vs_stab_set_yuv_edge_fill, vs_batch_set_yuv_edge_fill and vs_op_warp_affine_yuv_fill
+ *    vs_stab_set_yuv_edge_fill, vs_batch_set_yuv_edge_fill and vs_op_warp_affine_yuv_fill; the packed 4:2:2 capture formats: enum
+ *    vs_packed_fmt with vs_op_cvt_packed_to_yuv, vs_op_cvt_yuv_to_packed and vs_packed_layout
  *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
@@ -1280,6 +1281,60 @@ int vs_op_cvt_yuv_to_yuv(int src_fmt, const void* const* d_src, const vs_i420_la
  * lay == NULL: all defaults at the tight pitch (w samples).  resolved and bytes may each be NULL.  Refuses exactly what
  * vs_op_cvt_yuv_to_rgb refuses about a format, a size and a layout (VS_ERR_INVALID_ARG, the text in vs_last_error). */
 int vs_yuv_surface_layout(int fmt, int w, int h, const vs_i420_layout* lay, vs_i420_layout* resolved, size_t* bytes);
+
+/* ---- packed 4:2:2 capture formats <-> YUV surfaces in HBM (tests/packedref.py states what they compute) ----------------------------
+ * Capture sources deliver none of the surface formats: SDI / HDMI cards UYVY and, at ten bits, v210; UVC cameras and V4L2 devices
+ * YUY2 (YUYV); some hardware paths Y210.  These two calls are the conversion in front of a stage (capture -> NV12 / P010 / I422 ...)
+ * and behind one (-> UYVY / v210 for playout), on the device.  The packed formats have an enum of their own: they are NOT VS_FMT_*
+ * values, and no stream, stage or other operator takes them.
+ *
+ * vs_op_cvt_packed_to_yuv converts n = 1 .. 32 packed frames of w x h pixels, rows src_pitch bytes apart, to n surfaces of dst_fmt
+ * in layout `out`; vs_op_cvt_yuv_to_packed n surfaces of src_fmt in layout `in` to n packed frames, rows dst_pitch bytes apart.  ONE
+ * launch each, asynchronous on `stream`; d_src and d_dst are HOST arrays of n device pointers, read during the call.  The surface
+ * side: any of the eleven non-interleaved formats; its layouts, defaults and rules are those of vs_op_cvt_yuv_to_yuv.  A packed
+ * pitch of 0 is the format's default.  desc: NULL and the all-zero struct mean the same - truncate, top-left.
+ *
+ * Memory of the packed side: words are little-endian, a row starts at ptr + y * pitch, w is even.
+ *  VS_PACKED_YUY2, VS_PACKED_UYVY, VS_PACKED_YVYU: 8-bit samples, two pixels in 4 bytes: Y0 U Y1 V, U Y0 V Y1, Y0 V Y1 U.  Row bytes
+ *   2 w, which is the default pitch; any pitch >= the row bytes and any pointer.
+ *  VS_PACKED_Y210: the YUY2 layout with 16-bit words.  The value is the whole word, its most significant bits meaningful, exactly
+ *   as for P010 (Y216 content passes through).  Row bytes 4 w, the default pitch; pointer and pitch must be even.
+ *  VS_PACKED_V210: a group of 16 bytes holds 6 pixels as four 32-bit words of three 10-bit fields, at bits 0-9, 10-19 and 20-29:
+ *     w0 = Cb0 | Y0 << 10 | Cr0 << 20      w1 = Y1 | Cb1 << 10 | Y2 << 20
+ *     w2 = Cr1 | Y3 << 10 | Cb2 << 20      w3 = Y4 | Cr2 << 10 | Y5 << 20
+ *   Row bytes 16 * ceil(w / 6): a partial last group is still 16 bytes of the row; any even w is taken.  The default pitch is the
+ *   format's convention, 128 * ceil(w / 48); pointer and pitch must be multiples of 4.  Reading: bits 30-31 and the fields of
+ *   pixels >= w are ignored.  Writing: bits 30-31 are 0, and the fields of pixels >= w in the last group are 0.
+ *   (Y = 0x040 .. 0x045, Cb = 0x200, 0x201, 0x202, Cr = 0x300, 0x301, 0x302 are 0x30010200, 0x04280441, 0x20210F01, 0x045C0844.)
+ *
+ * Definition: the two steps of vs_op_cvt_yuv_to_yuv, word for word, with the packed side a 4:2:2 format, (sx, sy) = (1, 0), that
+ * holds values of b = 8 bits (the three 8-bit orders), b = 16 (Y210: the whole word, like P010) or b = 10 (v210).  Step 1, depth:
+ * truncate, or round with saturation; step 2, chroma siting: top-left or the block mean going down (a 4:2:0 destination, a 4:4:4
+ * source), nearest going up.  One addition, to step 1: a v210 field holds ten bits, so a v210 destination takes min(value, 1023) -
+ * also when d = 0 and a low-bit source (I010, I210, I410) carries out-of-range high bits, which the surface formats copy.  SDI-illegal codes
+ * (0 - 3, 1020 - 1023) are not clamped: the calls move samples, they do not legalise them.  So, bit for bit,
+ *   YUY2 / UYVY / YVYU -> X is vs_op_cvt_yuv_to_yuv(I422 -> X) on the de-interleaved planes, v210 -> X is (I210 -> X).
+ * Refusals (VS_ERR_INVALID_ARG, decided before any device call; vs_last_error names the call, the side - "source" / "destination" -
+ * and the format): everything vs_op_cvt_yuv_to_yuv refuses about the surface side (so h must be even for a 4:2:0 format);
+ * packed_fmt outside the enum; an odd w; a packed pitch below the row bytes; a packed pitch or pointer that breaks the alignment
+ * above; a NULL pointer; d_src[i] == d_dst[j] for any i, j; n outside 1 .. 32; a descriptor field outside its enum; a reserved
+ * field that is not 0.  Valid arguments on a machine without a device: VS_ERR_NO_DEVICE.  Nothing outside a row's bytes is written
+ * on either side: pitch padding, gaps between planes and the bytes behind the last row keep their contents.
+ * Not built: packed formats as stream or stage formats, or in the colour conversions and the enhancer's YUV calls (two calls chain
+ * through a surface format); packed 4:4:4 (AYUV, VUYA, Y410); semi-planar 4:2:2 / 4:4:4; big-endian samples; interlaced fields;
+ * interpolating chroma filters; SDI range legalisation. */
+enum vs_packed_fmt { VS_PACKED_YUY2 = 0, VS_PACKED_UYVY = 1, VS_PACKED_YVYU = 2, VS_PACKED_Y210 = 3, VS_PACKED_V210 = 4 };
+int vs_op_cvt_packed_to_yuv(int packed_fmt, const void* const* d_src, size_t src_pitch,
+                            int dst_fmt, void* const* d_dst, const vs_i420_layout* out,
+                            int n, int w, int h, const vs_yuv_cvt_desc* desc, void* stream);
+int vs_op_cvt_yuv_to_packed(int src_fmt, const void* const* d_src, const vs_i420_layout* in,
+                            int packed_fmt, void* const* d_dst, size_t dst_pitch,
+                            int n, int w, int h, const vs_yuv_cvt_desc* desc, void* stream);
+/* Host only, needs no device: the bytes of a row of a w x h packed frame (*row_bytes), its pitch (*resolved_pitch: `pitch`, or the
+ * format's default for 0) and the number of bytes from the frame pointer to the end of its last row's bytes (*bytes =
+ * (h - 1) * pitch + row bytes).  Each result may be NULL.  Refuses exactly what the two calls refuse about a packed format, a size
+ * and a pitch (VS_ERR_INVALID_ARG, the text in vs_last_error). */
+int vs_packed_layout(int packed_fmt, int w, int h, size_t pitch, size_t* row_bytes, size_t* resolved_pitch, size_t* bytes);
 
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */

@@ -1,9 +1,11 @@
 // The compositing stages as operators (include/vs_stab.h): vs_op_copy_make_border, vs_op_fade_blend, vs_op_fade_update, the
 // vs_op_canvas_* object and the colour conversions vs_op_cvt_yuv_to_rgb[_cs] / vs_op_cvt_rgb_to_yuv[_cs], with the integers of
 // their colour spaces (cvt_resolve, vs_cvt_coefficients, vs_cvt_colorimetry_guess), and the conversion between YUV surface formats
-// vs_op_cvt_yuv_to_yuv with vs_yuv_surface_layout.  Nothing is computed here: each
+// vs_op_cvt_yuv_to_yuv with vs_yuv_surface_layout, and between them and the packed 4:2:2 capture formats: vs_op_cvt_packed_to_yuv,
+// vs_op_cvt_yuv_to_packed with vs_packed_layout.  Nothing is computed here: each
 // entry checks its arguments and calls what the pipeline calls (launch_make_border, launch_fade_blend, launch_fade_update of
-// k_traj.hip; canvas_apply of k_canvas.hip; launch_cvt_* of k_cvt.hip; launch_cvt_yuv_to_yuv of k_yuvcvt.hip).
+// k_traj.hip; canvas_apply of k_canvas.hip; launch_cvt_* of k_cvt.hip; launch_cvt_yuv_to_yuv of k_yuvcvt.hip;
+// launch_cvt_packed_to_yuv, launch_cvt_yuv_to_packed of k_yuvpacked.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -33,6 +35,84 @@ int cvt_check_rgb(const char* call, int rgb_fmt, const void* const* rgb, size_t 
     if (rgb_stride < (size_t)w * f->cn) return fail(std::string(f->name) + ": the pitch must hold a row of the picture");
     *rf = f;
     return VS_OK;
+}
+
+// The packed 4:2:2 capture formats (enum vs_packed_fmt), one row per value: what include/vs_stab.h says of each.
+struct PackedFmt {
+    const char* name;
+    int kind;           // PackedKind
+    uint32_t sel;       // 8-bit orders: where Y0, U, Y1, V lie in a macropixel, a byte each
+    int bits;           // of a value: 8; Y210 the whole word; v210 ten
+    int align;          // what pointers and pitches must be multiples of
+    const char* align_text;
+    size_t row_bytes(int w) const { return kind == PACKED_V210 ? 16 * (((size_t)w + 5) / 6) : (size_t)w * (kind == PACKED_16 ? 4 : 2); }
+    size_t default_pitch(int w) const { return kind == PACKED_V210 ? 128 * (((size_t)w + 47) / 48) : row_bytes(w); }
+};
+const PackedFmt PACKED_FMTS[] = {
+    {"YUY2", PACKED_8, 0x03020100u, 8, 1, ""},
+    {"UYVY", PACKED_8, 0x02030001u, 8, 1, ""},
+    {"YVYU", PACKED_8, 0x01020300u, 8, 1, ""},
+    {"Y210", PACKED_16, 0u, 16, 2, ": pointers and the pitch must be even (16-bit words)"},
+    {"v210", PACKED_V210, 0u, 10, 4, ": pointers and the pitch must be multiples of 4 (32-bit words)"},
+};
+
+// The packed side of a conversion: the format, the geometry, the n pointers, the pitch (0 = the format's default; resolved into
+// *pitch).  call: the entry point and the side, as for cvt_check_yuv.
+int cvt_check_packed(const char* call, int packed_fmt, const void* const* ptrs, int n, int w, int h, size_t* pitch, const PackedFmt** pf, std::string* msg) {
+    auto fail = [&](const std::string& what) { *msg = std::string(call) + ": " + what; return (int)VS_ERR_INVALID_ARG; };
+    if (packed_fmt < VS_PACKED_YUY2 || packed_fmt > VS_PACKED_V210)
+        return fail("packed format " + std::to_string(packed_fmt) + " is not a vs_packed_fmt (YUY2, UYVY, YVYU, Y210, v210)");
+    const PackedFmt& f = PACKED_FMTS[packed_fmt];
+    const std::string name = f.name;
+    if (n < 1 || n > CVT_MAX_SURFACES) return fail(name + ": n must be 1 .. 32 surfaces");
+    if (!ptrs) return fail(name + ": null pointer");
+    uintptr_t ptr_bits = 0;
+    for (int k = 0; k < n; k++) {
+        if (!ptrs[k]) return fail(name + ": null pointer");
+        ptr_bits |= (uintptr_t)ptrs[k];
+    }
+    if (w < 1 || h < 1 || w > 65536 || h > 65536) return fail(name + ": size out of range");
+    if (w & 1) return fail(name + ": w must be even (two pixels share a chroma pair)");
+    if (!*pitch) *pitch = f.default_pitch(w);
+    if (*pitch < f.row_bytes(w)) return fail(name + ": the pitch must hold a row of the picture (" + std::to_string(f.row_bytes(w)) + " bytes)");
+    if ((ptr_bits | *pitch) & (size_t)(f.align - 1)) return fail(name + f.align_text);
+    *pf = &f;
+    return VS_OK;
+}
+
+// What vs_op_cvt_yuv_to_yuv refuses about its descriptor, in its words.  pair: the call and both formats.
+int cvt_check_yuv_desc(const std::string& pair, const vs_yuv_cvt_desc* desc, std::string* msg) {
+    auto bad = [&](const char* field, int32_t v, const char* want) {
+        *msg = pair + "descriptor: " + field + " = " + std::to_string(v) + " " + want;
+        return (int)VS_ERR_INVALID_ARG;
+    };
+    if (desc->depth_down < VS_YUV_DEPTH_TRUNCATE || desc->depth_down > VS_YUV_DEPTH_ROUND)
+        return bad("depth_down", desc->depth_down, "is not a vs_yuv_depth_down (0, 1)");
+    if (desc->chroma_down < VS_CVT_CHROMA_TOPLEFT || desc->chroma_down > VS_CVT_CHROMA_MEAN)
+        return bad("chroma_down", desc->chroma_down, "is not a vs_cvt_chroma (0, 1)");
+    for (int k = 0; k < 2; k++)
+        if (desc->reserved[k] != 0) return bad(k ? "reserved[1]" : "reserved[0]", desc->reserved[k], "must be 0");
+    return VS_OK;
+}
+
+// ... and about its pointers: no source is a destination
+int cvt_check_distinct(const std::string& pair, const void* const* d_src, void* const* d_dst, int n, std::string* msg) {
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++)
+            if (d_src[i] == d_dst[j]) {
+                *msg = pair + "source surface " + std::to_string(i) + " is destination surface " + std::to_string(j) + " (surfaces may not overlap)";
+                return (int)VS_ERR_INVALID_ARG;
+            }
+    return VS_OK;
+}
+
+// The depth step between a packed format and a surface format.  A v210 field holds ten bits: a 10-bit low-bit source, whose word
+// is otherwise copied, clamps to them.
+YuvDepth packed_depth(const PackedFmt& pf, const PixFmt& f, bool to_packed, bool round) {
+    if (!to_packed) return yuv_depth_bits(pf.bits, false, yuv_value_bits(f), round);
+    YuvDepth k = yuv_depth_bits(yuv_value_bits(f), yuv_low_bit(f), pf.bits, round);
+    if (pf.kind == PACKED_V210) k.in_max = std::min(k.in_max, yuv_low_bit(f) ? (1u << f.bits) - 1u : 0xffffu);
+    return k;
 }
 
 }  // namespace
@@ -201,24 +281,67 @@ int vs_op_cvt_yuv_to_yuv(int src_fmt, const void* const* d_src, const vs_i420_la
         return refuse(VS_ERR_INVALID_ARG, msg.c_str());
     const PixFmt &sf = *pixfmt(src_fmt), &df = *pixfmt(dst_fmt);
     const std::string pair = std::string(call) + ": source " + sf.name + ", destination " + df.name + ": ";
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++)
-            if (d_src[i] == d_dst[j])
-                return refuse(VS_ERR_INVALID_ARG, (pair + "source surface " + std::to_string(i) + " is destination surface " + std::to_string(j) +
-                                                   " (surfaces may not overlap)").c_str());
     if (!desc) desc = &dflt;
-    auto bad = [&](const char* field, int32_t v, const char* want) {
-        return refuse(VS_ERR_INVALID_ARG, (pair + "descriptor: " + field + " = " + std::to_string(v) + " " + want).c_str());
-    };
-    if (desc->depth_down < VS_YUV_DEPTH_TRUNCATE || desc->depth_down > VS_YUV_DEPTH_ROUND)
-        return bad("depth_down", desc->depth_down, "is not a vs_yuv_depth_down (0, 1)");
-    if (desc->chroma_down < VS_CVT_CHROMA_TOPLEFT || desc->chroma_down > VS_CVT_CHROMA_MEAN)
-        return bad("chroma_down", desc->chroma_down, "is not a vs_cvt_chroma (0, 1)");
-    for (int k = 0; k < 2; k++)
-        if (desc->reserved[k] != 0) return bad(k ? "reserved[1]" : "reserved[0]", desc->reserved[k], "must be 0");
+    if (cvt_check_distinct(pair, d_src, d_dst, n, &msg) != VS_OK || cvt_check_yuv_desc(pair, desc, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
     VS_TRY(ensure_device());
     return launch_cvt_yuv_to_yuv(sf, d_src, li, df, d_dst, lo, n, w, h, yuv_depth(sf, df, desc->depth_down == VS_YUV_DEPTH_ROUND),
                                  desc->chroma_down == VS_CVT_CHROMA_MEAN, (hipStream_t)stream);
+}
+
+int vs_op_cvt_packed_to_yuv(int packed_fmt, const void* const* d_src, size_t src_pitch, int dst_fmt, void* const* d_dst, const vs_i420_layout* out,
+                            int n, int w, int h, const vs_yuv_cvt_desc* desc, void* stream) {
+    static const char call[] = "vs_op_cvt_packed_to_yuv";
+    static const vs_yuv_cvt_desc dflt = {VS_YUV_DEPTH_TRUNCATE, VS_CVT_CHROMA_TOPLEFT, {0, 0}};
+    const PackedFmt* pf = nullptr;
+    I420Layout lo;
+    std::string msg;
+    if (cvt_check_packed("vs_op_cvt_packed_to_yuv: source", packed_fmt, d_src, n, w, h, &src_pitch, &pf, &msg) != VS_OK ||
+        cvt_check_yuv("vs_op_cvt_packed_to_yuv: destination", dst_fmt, d_dst, n, out, w, h, &lo, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    const PixFmt& df = *pixfmt(dst_fmt);
+    const std::string pair = std::string(call) + ": source " + pf->name + ", destination " + df.name + ": ";
+    if (!desc) desc = &dflt;
+    if (cvt_check_distinct(pair, d_src, d_dst, n, &msg) != VS_OK || cvt_check_yuv_desc(pair, desc, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    VS_TRY(ensure_device());
+    return launch_cvt_packed_to_yuv(pf->kind, pf->sel, d_src, src_pitch, df, d_dst, lo, n, w, h,
+                                    packed_depth(*pf, df, false, desc->depth_down == VS_YUV_DEPTH_ROUND), desc->chroma_down == VS_CVT_CHROMA_MEAN,
+                                    (hipStream_t)stream);
+}
+
+int vs_op_cvt_yuv_to_packed(int src_fmt, const void* const* d_src, const vs_i420_layout* in, int packed_fmt, void* const* d_dst, size_t dst_pitch,
+                            int n, int w, int h, const vs_yuv_cvt_desc* desc, void* stream) {
+    static const char call[] = "vs_op_cvt_yuv_to_packed";
+    static const vs_yuv_cvt_desc dflt = {VS_YUV_DEPTH_TRUNCATE, VS_CVT_CHROMA_TOPLEFT, {0, 0}};
+    const PackedFmt* pf = nullptr;
+    I420Layout li;
+    std::string msg;
+    if (cvt_check_yuv("vs_op_cvt_yuv_to_packed: source", src_fmt, d_src, n, in, w, h, &li, &msg) != VS_OK ||
+        cvt_check_packed("vs_op_cvt_yuv_to_packed: destination", packed_fmt, d_dst, n, w, h, &dst_pitch, &pf, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    const PixFmt& sf = *pixfmt(src_fmt);
+    const std::string pair = std::string(call) + ": source " + sf.name + ", destination " + pf->name + ": ";
+    if (!desc) desc = &dflt;
+    if (cvt_check_distinct(pair, d_src, d_dst, n, &msg) != VS_OK || cvt_check_yuv_desc(pair, desc, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    VS_TRY(ensure_device());
+    return launch_cvt_yuv_to_packed(sf, d_src, li, pf->kind, pf->sel, d_dst, dst_pitch, n, w, h,
+                                    packed_depth(*pf, sf, true, desc->depth_down == VS_YUV_DEPTH_ROUND), desc->chroma_down == VS_CVT_CHROMA_MEAN,
+                                    (hipStream_t)stream);
+}
+
+int vs_packed_layout(int packed_fmt, int w, int h, size_t pitch, size_t* row_bytes, size_t* resolved_pitch, size_t* bytes) {
+    // the rules are those of a conversion's side, asked about one surface at an address that no rule objects to
+    static const void* const aligned_surface[1] = {(const void*)(uintptr_t)4096};
+    const PackedFmt* pf = nullptr;
+    std::string msg;
+    if (cvt_check_packed("vs_packed_layout", packed_fmt, aligned_surface, 1, w, h, &pitch, &pf, &msg) != VS_OK)
+        return refuse(VS_ERR_INVALID_ARG, msg.c_str());
+    if (row_bytes) *row_bytes = pf->row_bytes(w);
+    if (resolved_pitch) *resolved_pitch = pitch;
+    if (bytes) *bytes = (size_t)(h - 1) * pitch + pf->row_bytes(w);
+    return VS_OK;
 }
 
 int vs_yuv_surface_layout(int fmt, int w, int h, const vs_i420_layout* lay, vs_i420_layout* resolved, size_t* bytes) {

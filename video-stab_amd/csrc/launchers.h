@@ -88,11 +88,13 @@ int launch_cvt_rgb_to_yuv(const PixFmt& rf, const void* const* rgb, size_t rgb_s
 // vs_yuv_depth_down rule; equal depths copy the word (no clamp).
 struct YuvDepth { uint32_t in_max, add, down, up, out_max; };
 inline int yuv_value_bits(const PixFmt& f) { return f.luma_uv() && f.sample_bytes == 2 ? 16 : f.bits; }
-inline YuvDepth yuv_depth(const PixFmt& sf, const PixFmt& df, bool round) {
-    const int bi = yuv_value_bits(sf), bo = yuv_value_bits(df), d = bi - bo;
+inline bool yuv_low_bit(const PixFmt& f) { return f.three_planes() && f.sample_bytes == 2; }
+// ... for a source of bi bits (low_in: a low-bit format) and a destination of bo bits
+inline YuvDepth yuv_depth_bits(int bi, bool low_in, int bo, bool round) {
+    const int d = bi - bo;
     YuvDepth k = {0xffffu, 0u, 0u, 0u, 0xffffu};
     if (d == 0) return k;
-    if (sf.three_planes() && sf.sample_bytes == 2) k.in_max = (1u << bi) - 1u;      // a low-bit source: bits above its range clamp
+    if (low_in) k.in_max = (1u << bi) - 1u;      // a low-bit source: bits above its range clamp
     if (d < 0) k.up = (uint32_t)-d;
     else {
         k.down = (uint32_t)d;
@@ -101,9 +103,24 @@ inline YuvDepth yuv_depth(const PixFmt& sf, const PixFmt& df, bool round) {
     }
     return k;
 }
+inline YuvDepth yuv_depth(const PixFmt& sf, const PixFmt& df, bool round) {
+    return yuv_depth_bits(yuv_value_bits(sf), yuv_low_bit(sf), yuv_value_bits(df), round);
+}
 // n <= CVT_MAX_SURFACES surfaces of one geometry in one launch (grid z = surface); the layouts as cvt_check_yuv resolved them
 int launch_cvt_yuv_to_yuv(const PixFmt& sf, const void* const* src, const I420Layout& in, const PixFmt& df, void* const* dst, const I420Layout& out,
                           int n, int w, int h, const YuvDepth& depth, bool mean, hipStream_t st);
+
+// ---- k_yuvpacked.hip: packed 4:2:2 capture formats <-> YUV surfaces (vs_op_cvt_packed_to_yuv, vs_op_cvt_yuv_to_packed)
+// What the kernels know of a vs_packed_fmt: its kind, and for the 8-bit orders the v_perm_b32 selector that makes a macropixel
+// Y0 U Y1 V (each order is its own inverse, so the selector also packs).  The rest of a format - name, depth, row bytes, pitch and
+// alignment rules - is host business (comp_op.cpp).
+enum PackedKind { PACKED_8 = 0, PACKED_16 = 1, PACKED_V210 = 2 };
+// n <= CVT_MAX_SURFACES surfaces of one geometry in one launch (grid z = surface); the surface side as cvt_check_yuv resolved it,
+// the packed pitch resolved; depth: yuv_depth_bits with the packed side's bits (a v210 destination of a 10-bit source: in_max 1023)
+int launch_cvt_packed_to_yuv(int kind, uint32_t sel, const void* const* src, size_t src_pitch, const PixFmt& df, void* const* dst, const I420Layout& out,
+                             int n, int w, int h, const YuvDepth& depth, bool mean, hipStream_t st);
+int launch_cvt_yuv_to_packed(const PixFmt& sf, const void* const* src, const I420Layout& in, int kind, uint32_t sel, void* const* dst, size_t dst_pitch,
+                             int n, int w, int h, const YuvDepth& depth, bool mean, hipStream_t st);
 
 // ---- the plane-job operators on YUV surfaces (k_cropzoom.hip, k_yuvpad.hip, k_yuvfade.hip): what their kernels and launchers share -
 // tile sequence, job search, launch check, the sentences of the refusals - is in plane_jobs.h.

@@ -516,6 +516,12 @@ class VsLib:
             L.vs_op_cvt_yuv_to_yuv.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(VsYuvCvtDesc), vp]
             L.vs_yuv_surface_layout.argtypes = [C.c_int, C.c_int, C.c_int, lp, lp, C.POINTER(C.c_size_t)]
+            # packed 4:2:2 capture formats
+            L.vs_op_cvt_packed_to_yuv.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(VsYuvCvtDesc), vp]
+            L.vs_op_cvt_yuv_to_packed.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(VsYuvCvtDesc), vp]
+            L.vs_packed_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t] + [C.POINTER(C.c_size_t)] * 3
             # crop-and-zoom on YUV streams
             L.vs_stab_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
             L.vs_batch_set_yuv_crop_zoom.argtypes = [vp, C.c_int]
@@ -1061,6 +1067,61 @@ class VsLib:
                 outs = [o.reshape(fmt_frame_rows(dst_fmt, h), w) for o in outs]
         return outs[0] if single else outs
 
+    def packed_layout(self, packed_fmt, w, h, pitch=0):
+        """vs_packed_layout (host only): (row_bytes, pitch, bytes) of a w x h frame of a PACKED_* format - the bytes of a row, the
+        pitch (`pitch`, or the format's default for 0) and the bytes from the frame pointer to the end of the last row's bytes."""
+        row, res, nbytes = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self.check(self.lib.vs_packed_layout(packed_fmt, w, h, pitch, C.byref(row), C.byref(res), C.byref(nbytes)))
+        return row.value, res.value, nbytes.value
+
+    def cvt_packed_to_yuv(self, packed_fmt, frames, w, h, dst_fmt, pitch=0, out_layout=None, desc=None, raw=False, fill=0xA5):
+        """vs_op_cvt_packed_to_yuv.  frames: one packed frame of w x h pixels or a list of up to 32, converted in one launch - arrays
+        of any dtype whose bytes are the frame's, rows `pitch` bytes apart (0 = the format's default).  -> per frame what
+        cvt_yuv_to_yuv gives for dst_fmt, out_layout and raw; desc as there."""
+        fo = PIXFMT[dst_fmt]
+        srcs, single = _surface_list(frames)
+        n = len(srcs)
+        lout = I420LayoutC(*(out_layout or (fo.sample_bytes * w, 0, 0, 0)))
+        _, size = self.yuv_surface_layout(dst_fmt, w, h, out_layout)
+        d_in = [DevBuf.from_array(self, s) for s in srcs]
+        d_out = [DevBuf.from_array(self, np.full(size + 16, fill, np.uint8)) for _ in range(n)]
+        try:
+            self.check(self.lib.vs_op_cvt_packed_to_yuv(packed_fmt, _ptr_array(d_in), pitch, dst_fmt, _ptr_array(d_out), C.byref(lout), n, w, h,
+                                                        _yuv_desc_ref(desc), None))
+            self.sync()
+            outs = [d.download((size + 16,), np.uint8) for d in d_out]
+        finally:
+            for d in d_in + d_out:
+                d.free()
+        if not raw:
+            outs = [o[:size].view(fmt_dtype(dst_fmt)) for o in outs]
+            if not out_layout:
+                outs = [o.reshape(fmt_frame_rows(dst_fmt, h), w) for o in outs]
+        return outs[0] if single else outs
+
+    def cvt_yuv_to_packed(self, src_fmt, surfaces, w, h, packed_fmt, in_layout=None, pitch=0, desc=None, raw=False, fill=0xA5):
+        """vs_op_cvt_yuv_to_packed.  surfaces, in_layout, desc: as for cvt_yuv_to_yuv.  -> per surface the (h, row_bytes) uint8 rows
+        of the packed frame, rows `pitch` bytes apart on the device (0 = the format's default); raw=True: the whole destination
+        instead, the bytes of vs_packed_layout + 16 prefilled with `fill`."""
+        fi = PIXFMT[src_fmt]
+        srcs, single = _surface_list(surfaces)
+        n = len(srcs)
+        lin = I420LayoutC(*(in_layout or (fi.sample_bytes * w, 0, 0, 0)))
+        row, res, size = self.packed_layout(packed_fmt, w, h, pitch)
+        d_in = [DevBuf.from_array(self, s) for s in srcs]
+        d_out = [DevBuf.from_array(self, np.full(size + 16, fill, np.uint8)) for _ in range(n)]
+        try:
+            self.check(self.lib.vs_op_cvt_yuv_to_packed(src_fmt, _ptr_array(d_in), C.byref(lin), packed_fmt, _ptr_array(d_out), pitch, n, w, h,
+                                                        _yuv_desc_ref(desc), None))
+            self.sync()
+            outs = [d.download((size + 16,), np.uint8) for d in d_out]
+        finally:
+            for d in d_in + d_out:
+                d.free()
+        if not raw:
+            outs = [np.stack([o[y * res:y * res + row] for y in range(h)]) for o in outs]
+        return outs[0] if single else outs
+
     def enh_yuv_plan(self, params, yuv_fmt, in_place=False):
         """vs_enh_yuv_plan (host only): 1 = Enhancer.apply_yuv_batch_dev would take the fused launch, 0 = the three calls per surface,
         < 0 = minus the status of the refusal.  params: VsEnhParams or None."""
@@ -1150,6 +1211,9 @@ class VsYuvCvtDesc(C.Structure):
 
 
 YUV_DEPTH_TRUNCATE, YUV_DEPTH_ROUND = 0, 1
+# enum vs_packed_fmt: the packed 4:2:2 capture formats of cvt_packed_to_yuv / cvt_yuv_to_packed (not pixel formats of a stream)
+PACKED_YUY2, PACKED_UYVY, PACKED_YVYU, PACKED_Y210, PACKED_V210 = range(5)
+PACKED_BY_NAME = {"YUY2": PACKED_YUY2, "UYVY": PACKED_UYVY, "YVYU": PACKED_YVYU, "Y210": PACKED_Y210, "v210": PACKED_V210}
 
 
 def _yuv_desc_ref(desc):
