@@ -217,7 +217,7 @@ __device__ __forceinline__ void cz_tile(const CzJob& J, int tx, int ty, uint32_t
 template <int SB>
 __global__ __launch_bounds__(64 * CZ_WAVES) void cropzoom_kernel(const CzArgs a) {
     __shared__ uint32_t s_y[CZ_TR], s_b[CZ_TR];
-    const uint32_t seq = pj_seq(blockIdx.x, a.tiles);
+    const uint32_t seq = xcd_seq(blockIdx.x, a.tiles);
     const CzJob J = a.j[pj_find(a, seq, [](const CzJob& j) { return j.tile0; })];
     const PjTile t = pj_split(seq - J.tile0, (J.dwh & 0xffffu) * J.cn * SB, CZ_TB);
     if (J.cn == 1) cz_tile<SB, 1>(J, t.tx, t.ty, s_y, s_b);

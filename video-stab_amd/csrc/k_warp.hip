@@ -458,6 +458,20 @@ __device__ __forceinline__ void load_map(const WarpArgs& a, int bz, double* m) {
     }
 }
 
+// The coordinate terms of the tile (x0, y0) .. (x1, y1) from the inverse map m, in double: the first 128 lanes a column each (adelta,
+// bdelta), the next 16 a row each (X0, Y0).  Columns and rows past the image repeat the last one.
+__device__ __forceinline__ void map_terms(const double (&m)[6], int x0, int y0, int x1, int y1, int tid, int* s_ad, int* s_bd, int* s_x0, int* s_y0) {
+    if (tid < TW) {
+        const double dv = (double)min(x0 + tid, x1);
+        s_ad[tid] = coord_term(m[0], 0.0, dv);
+        s_bd[tid] = coord_term(m[3], 0.0, dv);
+    } else if (tid < TW + TH) {
+        const double dv = (double)min(y0 + (tid - TW), y1);
+        s_x0[tid - TW] = coord_term(m[1], m[2], dv) + 16;
+        s_y0[tid - TW] = coord_term(m[4], m[5], dv) + 16;
+    }
+}
+
 // Coordinate tables of the frames of a launch, once per frame instead of once per tile (layout and arithmetic: warp_tab.h).
 // The batch schedule has them built by the kernel that computes the inverse maps (k_ransac.hip, release workgroups); this
 // launch serves the standalone operator, deferred warps and steps whose maps come out of a one-kernel tail (Kalman).
@@ -548,15 +562,7 @@ __global__ __launch_bounds__(NT) void warp_affine_kernel(WarpArgs a) {
         // wave 2 the rows, in double; the corner terms come back through LDS
         double m[6];
         load_map(a, bz, m);
-        if (wave < 2) {
-            const double dv = (double)min(x0 + tid, x1);
-            s_ad[tid] = coord_term(m[0], 0.0, dv);
-            s_bd[tid] = coord_term(m[3], 0.0, dv);
-        } else if (tid < 2 * 64 + TH) {
-            const double dv = (double)min(y0 + (tid - 128), y1);
-            s_x0[tid - 128] = coord_term(m[1], m[2], dv) + 16;
-            s_y0[tid - 128] = coord_term(m[4], m[5], dv) + 16;
-        }
+        map_terms(m, x0, y0, x1, y1, tid, s_ad, s_bd, s_x0, s_y0);
         __syncthreads();
         const int cl = x1 - x0, rl = y1 - y0;
         ad0 = __builtin_amdgcn_readfirstlane(s_ad[0]); ad1 = __builtin_amdgcn_readfirstlane(s_ad[cl]);
@@ -646,15 +652,7 @@ __global__ __launch_bounds__(NT) void warp_affine16_kernel(WarpArgs a) {
     const int x1 = min(x0 + TW, a.c.dw) - 1, y1 = min(y0 + TH, a.c.dh) - 1;
     double m[6];
     load_map(a, bz, m);
-    if (tid < TW) {
-        const double dv = (double)min(x0 + tid, x1);
-        s_ad[tid] = coord_term(m[0], 0.0, dv);
-        s_bd[tid] = coord_term(m[3], 0.0, dv);
-    } else if (tid < TW + TH) {
-        const double dv = (double)min(y0 + (tid - TW), y1);
-        s_x0[tid - TW] = coord_term(m[1], m[2], dv) + 16;
-        s_y0[tid - TW] = coord_term(m[4], m[5], dv) + 16;
-    }
+    map_terms(m, x0, y0, x1, y1, tid, s_ad, s_bd, s_x0, s_y0);
     __syncthreads();
     emit_rows<CN, false, 2>(a.c, a.srcs[bz], a.dsts[bz], nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid);
 }
@@ -679,15 +677,7 @@ __device__ __forceinline__ void warp_jobs_tile(const WarpJobsArg& a) {
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     if (x0 >= j.dw || y0 >= j.dh) return;                 // (workgroup-uniform)
     const int x1 = min(x0 + TW, j.dw) - 1, y1 = min(y0 + TH, j.dh) - 1;
-    if (tid < TW) {
-        const double dv = (double)min(x0 + tid, x1);
-        s_ad[tid] = coord_term(j.m[0], 0.0, dv);
-        s_bd[tid] = coord_term(j.m[3], 0.0, dv);
-    } else if (tid < TW + TH) {
-        const double dv = (double)min(y0 + (tid - TW), y1);
-        s_x0[tid - TW] = coord_term(j.m[1], j.m[2], dv) + 16;
-        s_y0[tid - TW] = coord_term(j.m[4], j.m[5], dv) + 16;
-    }
+    map_terms(j.m, x0, y0, x1, y1, tid, s_ad, s_bd, s_x0, s_y0);
     __syncthreads();
     WarpCore c;
     c.sstride = j.sstride; c.dstride = j.dstride;
@@ -778,15 +768,7 @@ __device__ __forceinline__ void scale_jobs_tile(const WarpJobsArg& a) {
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     if (x0 >= j.dw || y0 >= j.dh) return;                 // (workgroup-uniform)
     const int x1 = min(x0 + TW, j.dw) - 1, y1 = min(y0 + TH, j.dh) - 1;
-    if (tid < TW) {
-        const double dv = (double)min(x0 + tid, x1);
-        s_ad[tid] = coord_term(j.m[0], 0.0, dv);
-        s_bd[tid] = coord_term(j.m[3], 0.0, dv);
-    } else if (tid < TW + TH) {
-        const double dv = (double)min(y0 + (tid - TW), y1);
-        s_x0[tid - TW] = coord_term(j.m[1], j.m[2], dv) + 16;
-        s_y0[tid - TW] = coord_term(j.m[4], j.m[5], dv) + 16;
-    }
+    map_terms(j.m, x0, y0, x1, y1, tid, s_ad, s_bd, s_x0, s_y0);
     __syncthreads();
     // the tile's box from its corner terms, by emit_rows' expressions (m[1] = m[3] = 0: s_x0 is one value, s_bd is 0)
     const int bx0 = sat_s16(((s_x0[0] + s_ad[0]) >> 5) >> 5), bx1 = sat_s16(((s_x0[0] + s_ad[x1 - x0]) >> 5) >> 5);
@@ -844,6 +826,15 @@ struct TabK {
     int tab_stride, tab_row, tab_ad;
     int gx, gy;
 };
+
+// swh / dwh: width | height << 16 of source and destination; flags: bit 0 / 1 source / destination aligned, bits 2 .. 4 the border
+__device__ __forceinline__ WarpCore unpack_core(uint32_t sstride, uint32_t dstride, uint32_t swh, uint32_t dwh, uint32_t flags) {
+    WarpCore c;
+    c.sstride = sstride; c.dstride = dstride;
+    c.sw = swh & 0xFFFFu; c.sh = swh >> 16; c.dw = dwh & 0xFFFFu; c.dh = dwh >> 16;
+    c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u; c.border = (flags >> 2) & 7u;
+    return c;
+}
 
 struct TileIn {            // wave-uniform inputs of a tile
     const uint8_t* src;
@@ -980,7 +971,7 @@ __device__ __forceinline__ void store_tile(const TabK& k, const TileIn& t, const
     store_terms(tab, tid, pf.tv0, pf.tv1, b.bx0a << 10, b.by0 << 10);
 }
 
-// XCD-aware tile order.  The hardware hands consecutive workgroups to the 8 XCDs in turn (linear id mod 8), and every XCD has
+// XCD-aware tile order (xcd_seq, vs_common.h).  The hardware hands consecutive workgroups to the 8 XCDs in turn (linear id mod 8), and every XCD has
 // an L2 of its own: with the plain (x, y, frame) order the eight neighbours of a tile row sit on eight different XCDs, and every
 // 128-byte line that two tiles share (the box of a tile is 144 / 408 bytes wide at an arbitrary 4- / 12-byte offset, plus the halo
 // rows above and below) is fetched once per XCD - read traffic of 2.28 x (planes) and 1.60 x (BGR) the algorithmic bytes at the
@@ -995,8 +986,7 @@ __device__ __forceinline__ TileId tile_id(uint32_t flags, uint32_t gx, uint32_t 
     if (!(flags & 0x100u)) { t.x = blockIdx.x; t.y = blockIdx.y; t.z = blockIdx.z; return t; }
     const uint32_t n = gx * gy * (flags >> 16);
     const uint32_t lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const uint32_t c = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-    const uint32_t seq = c * q + (c < r ? c : r) + k;
+    const uint32_t seq = xcd_seq(lin, n);
     const uint32_t row = gx == 1 ? seq : __umulhi(seq, mgx);       // (ceil(2^32 / 1) does not fit 32 bits)
     t.x = (int)(seq - row * gx);
     t.z = (int)(gy == 1 ? row : __umulhi(row, mgy));
@@ -1021,9 +1011,7 @@ __global__ __launch_bounds__(NT, 8) void warp_tab_kernel(gtab_t tabs, int tab_st
     typedef __attribute__((address_space(1))) uint8_t* gptr;
     const int tid = threadIdx.x;
     TabK k;
-    k.c.sstride = sstride; k.c.dstride = dstride;
-    k.c.sw = swh & 0xFFFFu; k.c.sh = swh >> 16; k.c.dw = dwh & 0xFFFFu; k.c.dh = dwh >> 16;
-    k.c.src_aligned = flags & 1u; k.c.dst_aligned = (flags >> 1) & 1u; k.c.border = (flags >> 2) & 7u;
+    k.c = unpack_core(sstride, dstride, swh, dwh, flags);
     k.tabs = tabs; k.tab_stride = tab_stride; k.tab_row = tab_row; k.tab_ad = tab_ad;
     k.gx = (k.c.dw + TW - 1) / TW; k.gy = (k.c.dh + TH - 1) / TH;
     TileIn cur;
@@ -1354,41 +1342,42 @@ __device__ __forceinline__ void plane_blend_rows(const WarpCore& c, const uint8_
     }
 }
 
+// The terms of a tile of ROWS rows from the plane's table Tg into s_tab - ad[128] bd[128] x0[ROWS] y0[ROWS] -, for the direct paths
+// below.  Columns and rows past the plane repeat the last one.
+template <int ROWS>
+__device__ __forceinline__ void stage_terms(const WarpCore& c, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1, int tid) {
+    if (tid < TW) {
+        const int cx = min(x0 + tid, x1);
+        s_tab[tid] = Tg[cx]; s_tab[TW + tid] = Tg[c.dw + cx];
+    } else if (tid < TW + ROWS) {
+        const int r = min(y0 + (tid - TW), y1);
+        s_tab[2 * TW + (tid - TW)] = Tg[2 * c.dw + r]; s_tab[2 * TW + ROWS + (tid - TW)] = Tg[2 * c.dw + c.dh + r];
+    }
+}
+
 // A plane tile whose source box does not fit the staging area (large rotations, zooms, saturated coordinates, BORDER_REPLICATE): the
 // general path without staging (emit_rows works on 16 rows, terms as arrays: they go where the box would be).  Not inlined: as
 // part of the kernel body it costs the common path its eighth wave per SIMD or register spills.
-// (OWN: a copy of its own for the kernel that names it - the BORDER_REPLICATE instance for 16-bit samples -, so that the kernels
-// that existed before it keep their callee, and with it their code, as they were.)
+// (OWN: a copy of its own for the kernel that names it.  A noinline callee that two kernels share changes the register allocation of
+// both, so the instances that came later - 16-bit BORDER_REPLICATE per subsampling: copies 1 .. 4, the taller 4:2:2 box: copy 8 - each
+// call their own, and the earlier kernels keep their code.)
 template <int CN, int SB = 1, int OWN = 0>
 __device__ __attribute__((noinline)) void plane_direct_tile(WarpCore c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
                                                             int bx0a, int by0, int bw, int tid) {
     typedef PlaneCfg<CN, SB> P;
-    if (tid < TW) {           // ad[128] bd[128] x0[THP] y0[THP]
-        const int cx = min(x0 + tid, x1);
-        s_tab[tid] = Tg[cx]; s_tab[TW + tid] = Tg[c.dw + cx];
-    } else if (tid < TW + P::THP) {
-        const int r = min(y0 + (tid - TW), y1);
-        s_tab[2 * TW + (tid - TW)] = Tg[2 * c.dw + r]; s_tab[2 * TW + P::THP + (tid - TW)] = Tg[2 * c.dw + c.dh + r];
-    }
+    stage_terms<P::THP>(c, Tg, s_tab, x0, y0, x1, y1, tid);
     __syncthreads();
     for (int j = 0; y0 + TH * j <= y1; j++)
         emit_rows<CN, false, SB>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW + TH * j, s_tab + 2 * TW + P::THP + TH * j, x0, y0 + TH * j, x1,
                              min(y0 + TH * j + TH - 1, y1), bx0a, by0, bw, tid);
 }
 
-// The direct path of the VS_BORDER_FILL kernels: plane_direct_tile with the fill pixel.  A function of its own (one copy per kernel:
-// OWN), so that plane_direct_tile keeps its arguments and every kernel that calls it its code.
+// The direct path of the VS_BORDER_FILL kernels: plane_direct_tile with the fill pixel (one copy per kernel: OWN).
 template <int CN, int SB, int OWN>
 __device__ __attribute__((noinline)) void plane_direct_tile_fill(WarpCore c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
                                                                  int tid, uint32_t fillpx) {
     typedef PlaneCfg<CN, SB> P;
-    if (tid < TW) {           // ad[128] bd[128] x0[THP] y0[THP]
-        const int cx = min(x0 + tid, x1);
-        s_tab[tid] = Tg[cx]; s_tab[TW + tid] = Tg[c.dw + cx];
-    } else if (tid < TW + P::THP) {
-        const int r = min(y0 + (tid - TW), y1);
-        s_tab[2 * TW + (tid - TW)] = Tg[2 * c.dw + r]; s_tab[2 * TW + P::THP + (tid - TW)] = Tg[2 * c.dw + c.dh + r];
-    }
+    stage_terms<P::THP>(c, Tg, s_tab, x0, y0, x1, y1, tid);
     __syncthreads();
     for (int j = 0; y0 + TH * j <= y1; j++)
         emit_rows<CN, false, SB, true>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW + TH * j, s_tab + 2 * TW + P::THP + TH * j, x0, y0 + TH * j, x1,
@@ -1400,13 +1389,7 @@ __device__ __attribute__((noinline)) void plane_direct_tile_fill(WarpCore c, con
 __device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint8_t* src, uint8_t* dst, gtab_t Tg, int* s_tab, int x0, int y0, int x1, int y1,
                                                 int bx0a, int by0, int bw, int tid) {
     static_assert(PlaneCfg<4>::THP == TH, "one pass of emit_rows per tile");
-    if (tid < TW) {
-        const int cx = min(x0 + tid, x1);
-        s_tab[tid] = Tg[cx]; s_tab[TW + tid] = Tg[c.dw + cx];
-    } else if (tid < TW + TH) {
-        const int r = min(y0 + (tid - TW), y1);
-        s_tab[2 * TW + (tid - TW)] = Tg[2 * c.dw + r]; s_tab[2 * TW + TH + (tid - TW)] = Tg[2 * c.dw + c.dh + r];
-    }
+    stage_terms<TH>(c, Tg, s_tab, x0, y0, x1, y1, tid);
     __syncthreads();
     emit_rows<4, false>(c, src, dst, nullptr, s_tab, s_tab + TW, s_tab + 2 * TW, s_tab + 2 * TW + TH, x0, y0, x1, y1, bx0a, by0, bw, tid);
 }
@@ -1416,17 +1399,20 @@ __device__ __forceinline__ void plane_direct_tile4(const WarpCore& c, const uint
 // this tile belongs to (wave-uniform).
 // BORDER: what the staged box holds where it leaves the picture - zeros (cv::warpAffine BORDER_CONSTANT: the stabilizer's warp) or the
 // nearest picture pixel (BORDER_REPLICATE: the roll stage's rotation); a launch whose border is the other one takes the direct path.
-// OWN: the 16-bit BORDER_REPLICATE instance of the kernel that says so calls a plane_direct_tile copy of its own (sharing one copy
-// between two kernels changes the register allocation of both: the kernels that exist keep their code).
+// OWN: the plane_direct_tile / plane_direct_tile_fill copy of the kernel that says so (see plane_direct_tile).
+// XR: extra staged rows - 0, or 8 for the taller box of the 4:2:2 instances (warp_i422_tall_kernel): the box may have ROWS + XR rows, the
+// caller's `tile` holds them, and the direct path is copy 8.
 // BORDER = VS_BORDER_FILL (edge fill on YUV surfaces): the VS_BORDER_BLACK instance with `fill` - the plane's fill as one dword pattern, in
 // phase with every staged chunk (they start at a multiple of 4 pixels) - wherever that one holds zeros: rows and chunks outside the
 // picture, the outside bytes of a chunk that straddles its left or right edge (load_chunk_straddling_fill), and, on the direct path
 // (plane_direct_tile_fill, copy OWN), the taps outside.
-template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1, int OWN = 0>
+template <int CN, int BORDER = VS_BORDER_BLACK, int SB = 1, int OWN = 0, int XR = 0>
 __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
                                            uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add = 0, int dst_add = 0, uint32_t fill = 0u) {
     typedef PlaneCfg<CN, SB> P;
+    constexpr int ROWS = P::ROWS + XR;
     static_assert(SB == 1 || (SB == 2 && CN <= 2), "16-bit planes: one or two channels");
+    static_assert(XR == 0 || (CN == 1 && BORDER == VS_BORDER_REPLICATE), "the taller box: one-channel planes under BORDER_REPLICATE");
     typedef __attribute__((address_space(1))) uint8_t* gptr;
     const int L = tid & 31, ty = tid >> 5;
     int ad[4], bd[4];
@@ -1470,11 +1456,11 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
         bx0a = bx0 & ~3;
         bw = bx1 - bx0a + 1;
         bh = by1 - by0 + 1;
-        fit = !saturated && bw <= 136 && bh <= P::ROWS && c.border == BORDER;
+        fit = !saturated && bw <= 136 && bh <= ROWS && c.border == BORDER;       // (bh <= ROWS: every staged row lies inside `tile`)
     }
     if (fit) {
         // ---- staging: chunks of 16 bytes, (row, chunk) = (i / CPR, i % CPR); all loads of a lane first, then its stores
-        constexpr int NCH = (P::ROWS * P::CPR + NT - 1) / NT;
+        constexpr int NCH = (ROWS * P::CPR + NT - 1) / NT;
         const int total = bh * P::CPR;
         const long long rowbytes = (long long)c.sw * P::PXB;
         uint4 d[NCH];
@@ -1536,7 +1522,7 @@ __device__ __forceinline__ void plane_tile(const WarpCore& c, const __attribute_
         if constexpr (CN == 4) plane_direct_tile4(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
         else if constexpr (BORDER == VS_BORDER_FILL)      // (the fill pixel: the pattern's first sample, or its (U, V) pair)
             plane_direct_tile_fill<CN, SB, OWN>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, tid, P::PXB == 1 ? fill & 0xFFu : P::PXB == 2 ? fill & 0xFFFFu : fill);
-        else plane_direct_tile<CN, SB, (SB == 2 && BORDER == VS_BORDER_REPLICATE ? 1 + OWN : 0)>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
+        else plane_direct_tile<CN, SB, (XR ? 8 : SB == 2 && BORDER == VS_BORDER_REPLICATE ? 1 + OWN : 0)>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
         return;
     }
     __syncthreads();
@@ -1552,27 +1538,61 @@ __global__ __launch_bounds__(NT, 8) void warp_plane_kernel(gtab_t tabs, int tab_
     __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
     __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];                 // (X0, Y0) of the tile's rows
     typedef const __attribute__((address_space(4))) int32_t* cptr;
-    WarpCore c;
-    c.sstride = sstride; c.dstride = dstride;
-    c.sw = swh & 0xFFFFu; c.sh = swh >> 16; c.dw = dwh & 0xFFFFu; c.dh = dwh >> 16;
-    c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u; c.border = (flags >> 2) & 7u;
+    const WarpCore c = unpack_core(sstride, dstride, swh, dwh, flags);
     const TileId tq = tile_id(flags, (uint32_t)(c.dw + TW - 1) / TW, (uint32_t)(c.dh + P::THP - 1) / P::THP, mgx, mgy);
     plane_tile<CN>(c, (cptr)(const int32_t*)(tabs + (size_t)tq.z * tab_stride), tabs + (size_t)tq.z * tab_stride + tab_ad, tab_row, tq.x, tq.y,
                    tile, lut, s_row, threadIdx.x);
 }
 
-// ---- NV12 surfaces: luma and chroma tiles of all frames in ONE launch ---------------------------------------------------------
-// As two launches per 32 surfaces (warp_plane_kernel<1>, then <2>) the warp had two launch tails and two table walks, and the
-// luma launch - bound by its blend's instruction count - never shared a CU with the chroma launch, which is bound by its memory
-// phase.  Here the launch is a sequence of tiles (frame, plane, tile row, tile column): a frame's luma tiles, then its chroma
-// tiles; workgroup `lin` takes tile seq(lin) of that sequence, the XCD-aware order as in tile_id (XCD c = lin mod 8 takes the
-// c-th contiguous eighth).  A frame's tables lie in one block (warp_tab.h): luma table, then chroma table, `tab_stride` ints from
-// frame to frame.  The chroma plane's geometry is the luma plane's halved (surfaces share one pitch); flags as in the plane
-// kernels plus the frame count in bits 16...  mtpf = ceil(2^32 / tiles per frame), mgx1 / mgx2 likewise for the tile columns.
-// SB = 2: P010 surfaces - the same sequence, grid order, table blocks and prologue; planes of 16-bit samples (PlaneCfg<CN, 2>).
-template <int BORDER, int SB = 1>
-__global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t swh, uint32_t dwh,
-                                                       uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2) {
+// ---- YUV surfaces: the tiles of all planes of all frames in ONE launch ---------------------------------------------------------
+// NV12 as two launches per 32 surfaces (warp_plane_kernel<1>, then <2>) had two launch tails and two table walks, and the luma
+// launch - bound by its blend's instruction count - never shared a CU with the chroma launch, which is bound by its memory phase.
+// Here the launch is a sequence of tiles (frame, plane, tile row, tile column): a frame's luma tiles, then its chroma tiles;
+// workgroup `lin` takes tile seq(lin) of that sequence, the XCD-aware order as in tile_id.  A frame's tables lie in one block
+// (warp_tab.h): luma table, then chroma table, `tab_stride` ints from frame to frame.  flags as in the plane kernels, plus bits 5 / 6:
+// chroma source / destination aligned, and the frame count in bits 16...  mtpf = ceil(2^32 / tiles per frame), mgx1 / mgx2 likewise
+// for the tile columns of the luma and the chroma planes.
+//
+// Two bodies: interleaved chroma (NV12, P010) and planar chroma (I420 and its kin).  Each declares the workgroup's LDS, finds the
+// workgroup's frame, plane and tile, and calls plane_tile.  The __global__ templates below them are one call each: their names, launch
+// bounds and argument lists are what the kernarg preload and the launchers see.
+// VS_BORDER_FILL (edge fill on YUV surfaces): cv::warpAffine(..., INTER_LINEAR, BORDER_CONSTANT, borderValue = fill) per plane - the
+// VS_BORDER_BLACK instances with the plane's fill sample where those read zeros (plane_tile<CN, VS_BORDER_FILL, SB>).  The fill travels
+// as two more kernel arguments - Y | U << 16 and V, samples as they lie in memory - behind the others (13 and 16 dwords: still preloaded
+// into scalar registers); only the fill kernels have them, so that the others keep their argument lists and their scalar registers, and
+// only the VS_BORDER_FILL instances of a body read them.
+// A plane's pattern: an 8-bit sample four times, the (U, V) byte pair twice, a 16-bit sample twice, or the (U, V) pair of P010.
+// (Instances of another border have no fill: they read neither argument.)
+template <int BORDER, int SB>
+__device__ __forceinline__ uint32_t fill_pattern(uint32_t f) {
+    if constexpr (BORDER != VS_BORDER_FILL) return 0u;
+    else return SB == 2 ? (f & 0xFFFFu) | f << 16 : (f & 0xFFu) * 0x01010101u;
+}
+template <int BORDER, int SB>
+__device__ __forceinline__ uint32_t fill_pattern_uv(uint32_t fill_yu, uint32_t fill_v) {
+    if constexpr (BORDER != VS_BORDER_FILL) return 0u;
+    else {
+        const uint32_t u = fill_yu >> 16;
+        return SB == 2 ? u | fill_v << 16 : ((u & 0xFFu) | (fill_v & 0xFFu) << 8) * 0x00010001u;
+    }
+}
+
+// Frame f and tile t inside it of this workgroup, in a launch of (flags >> 16) frames of tpf tiles each
+struct SurfTile { uint32_t f, t; };
+__device__ __forceinline__ SurfTile surf_tile(uint32_t flags, uint32_t tpf, uint32_t mtpf) {
+    const uint32_t n = tpf * (flags >> 16);
+    const uint32_t lin = blockIdx.x;
+    uint32_t seq = lin;
+    if (flags & 0x100u) seq = xcd_seq(lin, n);
+    const uint32_t f = __umulhi(seq, mtpf);
+    return {f, seq - f * tpf};
+}
+
+// NV12 (SB = 1) and P010 (SB = 2: planes of 16-bit samples, PlaneCfg<CN, 2>).  The chroma plane's geometry is the luma plane's halved;
+// the surfaces share one pitch.
+template <int BORDER, int SB>
+__device__ __forceinline__ void nv12_surface_tile(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t swh, uint32_t dwh, uint32_t flags,
+                                                  uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, uint32_t fill_yu = 0u, uint32_t fill_v = 0u) {
     typedef PlaneCfg<1, SB> P1;
     typedef PlaneCfg<2, SB> P2;
     constexpr int TILE_BYTES = P1::ROWS * P1::PB > P2::ROWS * P2::PB ? P1::ROWS * P1::PB : P2::ROWS * P2::PB;
@@ -1580,27 +1600,19 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
     __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
     __shared__ __attribute__((aligned(16))) int2 s_row[P1::THP];
     typedef const __attribute__((address_space(4))) int32_t* cptr;
-    WarpCore c;
-    c.sstride = sstride; c.dstride = dstride;
-    c.sw = swh & 0xFFFFu; c.sh = swh >> 16; c.dw = dwh & 0xFFFFu; c.dh = dwh >> 16;
-    c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u; c.border = (flags >> 2) & 7u;
+    WarpCore c = unpack_core(sstride, dstride, swh, dwh, flags);
     const uint32_t gx1 = (uint32_t)(c.dw + TW - 1) / TW, gy1 = (uint32_t)(c.dh + P1::THP - 1) / P1::THP;
     const uint32_t dw2 = (uint32_t)c.dw >> 1, dh2 = (uint32_t)c.dh >> 1;
     const uint32_t gx2 = (dw2 + TW - 1) / TW, gy2 = (dh2 + P2::THP - 1) / P2::THP;
-    const uint32_t n1 = gx1 * gy1, tpf = n1 + gx2 * gy2, n = tpf * (flags >> 16);
-    const uint32_t lin = blockIdx.x;
-    uint32_t seq = lin;
-    if (flags & 0x100u) {
-        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-        seq = cx * q + (cx < r ? cx : r) + k;
-    }
-    const uint32_t f = __umulhi(seq, mtpf);
-    uint32_t t = seq - f * tpf;
-    gtab_t T = tabs + (size_t)f * tab_stride;
+    const uint32_t n1 = gx1 * gy1, tpf = n1 + gx2 * gy2;
+    const SurfTile q = surf_tile(flags, tpf, mtpf);
+    uint32_t t = q.t;
+    gtab_t T = tabs + (size_t)q.f * tab_stride;
     if (t < n1) {
         const TabLayout L = tab_layout(c.dw, c.dh);
         const uint32_t row = gx1 == 1 ? t : __umulhi(t, mgx1);
-        plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx1), (int)row, tile, lut, s_row, threadIdx.x);
+        plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx1), (int)row, tile, lut, s_row, threadIdx.x, 0, 0,
+                                  fill_pattern<BORDER, SB>(fill_yu));
     } else {
         t -= n1;
         T += tab_layout(c.dw, c.dh).stride;
@@ -1608,35 +1620,31 @@ __global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_s
         c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
         const TabLayout L = tab_layout(c.dw, c.dh);
         const uint32_t row = gx2 == 1 ? t : __umulhi(t, mgx2);
-        plane_tile<2, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx2), (int)row, tile, lut, s_row, threadIdx.x);
+        plane_tile<2, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx2), (int)row, tile, lut, s_row, threadIdx.x, 0, 0,
+                                  fill_pattern_uv<BORDER, SB>(fill_yu, fill_v));
     }
 }
 
-// ---- I420 / YV12 surfaces: Y, U and V tiles of all frames in ONE launch --------------------------------------------------------
-// The scheme of warp_nv12_kernel for planar 4:2:0: the launch is a sequence of tiles (frame, plane, tile row, tile column) - a
-// frame's Y tiles, then its U tiles, then its V tiles - in the same XCD-aware order.  All three planes are one-channel planes
-// (PlaneCfg<1>: tiles of 128 x 64 pixels); U and V have the half-size geometry, a pitch of their own (scpitch / dcpitch) and
-// alignment flags of their own (flags bits 5, 6).  A frame keeps the two table blocks of an NV12 surface (warp_tab.h): the luma
-// table and ONE chroma table, in pixels, built from the map with the halved translation; the chroma table's pointer records name
-// the U plane, and a V tile adds the byte distances V - U (svu / dvu: all surfaces of a launch share one layout; negative for
-// YV12).  The release workgroups of the batch schedule therefore build I420 tables exactly as they build NV12 tables.
-// Arguments: 14 dwords - what gfx950 preloads into scalar registers at wave launch - with source and destination geometry in
-// one dword (they are equal) and the plane distances as 32-bit values (the launcher sends surfaces whose V - U does not fit to
-// the per-plane kernels).  mtpf = ceil(2^32 / tiles per frame), mgx1 / mgx2 likewise for the tile columns of Y and of U / V.
-// SB = 2: I010 / I012 surfaces - the same sequence, grid order, table blocks and arguments; three planes of 16-bit samples
-// (PlaneCfg<1, 2>: tiles of 128 x 32 pixels, the staged box of the P010 luma plane).  Pitches, V - U and the alignment flags stay
-// in bytes: plane_tile adds the plane distances to byte pointers.  BORDER_REPLICATE with SB = 2 (the roll stage's rotation of
-// I010 / I012 surfaces) is plane_tile<1, VS_BORDER_REPLICATE, 2>, the luma half of warp_nv12_kernel<VS_BORDER_REPLICATE, 2>.
-// CSX, CSY: the chroma shifts - U and V have (w >> CSX) x (h >> CSY) samples.  (1, 1) is planar 4:2:0, the code above to the letter;
-// (1, 0) is 4:2:2 (I422, I210, I212), (0, 0) is 4:4:4 (I444, I410, I412).  Nothing else differs: the chroma table is sized for that
-// plane and built from the chroma map Mc = S^-1 M S, which for 4:2:2 is not a rotation - its 2 m3 term makes the source box of a
-// chroma tile about 2 sin(angle) x 128 rows taller, so such tiles leave the staging area for plane_direct_tile at a smaller angle
-// than luma tiles do (DESIGN.md section 4 has the figure).
-template <int BORDER, int SB = 1, int CSX = 1, int CSY = 1>
-__global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
-                                                       uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
+// Planar surfaces: a frame's Y tiles, then its U tiles, then its V tiles.  All three planes are one-channel planes (PlaneCfg<1, SB>:
+// tiles of 128 x 64 pixels, of 128 x 32 for the 16-bit formats I010 / I012 and their kin); U and V have (w >> CSX) x (h >> CSY) samples,
+// a pitch of their own (scpitch / dcpitch) and alignment flags of their own (flags bits 5, 6).  A frame keeps the two table blocks of
+// an NV12 surface (warp_tab.h): the luma table and ONE chroma table, in pixels; the chroma table's pointer records name the U plane, and
+// a V tile adds the byte distances V - U (svu / dvu: all surfaces of a launch share one layout; negative for YV12).  The release
+// workgroups of the batch schedule therefore build I420 tables exactly as they build NV12 tables.
+// Arguments: 14 dwords - what gfx950 preloads into scalar registers at wave launch - with source and destination geometry in one
+// dword (they are equal) and the plane distances as 32-bit values (the launcher sends surfaces whose V - U does not fit to the
+// per-plane kernels).  Pitches, V - U and the alignment flags are in bytes for either sample size.
+// (CSX, CSY) = (1, 1) is planar 4:2:0, (1, 0) is 4:2:2 (I422, I210, I212), (0, 0) is 4:4:4 (I444, I410, I412).  Nothing else differs: the
+// chroma table is sized for that plane and built from the chroma map Mc = S^-1 M S, which for 4:2:2 is not a rotation - its 2 m3 term
+// makes the source box of a chroma tile about 2 sin(angle) x 128 rows taller, so such tiles leave the staging area for
+// plane_direct_tile at a smaller angle than luma tiles do (DESIGN.md section 4 has the figure).
+// XR: plane_tile's extra staged rows (warp_i422_tall_kernel).
+template <int BORDER, int SB, int CSX, int CSY, int XR>
+__device__ __forceinline__ void planar_surface_tile(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch, uint32_t wh,
+                                                    uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu, uint32_t fill_yu = 0u,
+                                                    uint32_t fill_v = 0u) {
     typedef PlaneCfg<1, SB> P;
-    __shared__ __attribute__((aligned(16))) uint8_t tile[P::ROWS * P::PB];
+    __shared__ __attribute__((aligned(16))) uint8_t tile[(P::ROWS + XR) * P::PB];
     __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
     __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];
     typedef const __attribute__((address_space(4))) int32_t* cptr;
@@ -1644,29 +1652,28 @@ __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_s
     const uint32_t gx1 = (uint32_t)(w + TW - 1) / TW, gy1 = (uint32_t)(h + P::THP - 1) / P::THP;
     const uint32_t w2 = (uint32_t)w >> CSX, h2 = (uint32_t)h >> CSY;
     const uint32_t gx2 = (w2 + TW - 1) / TW, gy2 = (h2 + P::THP - 1) / P::THP;
-    const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2, n = tpf * (flags >> 16);
-    const uint32_t lin = blockIdx.x;
-    uint32_t seq = lin;
-    if (flags & 0x100u) {
-        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-        seq = cx * q + (cx < r ? cx : r) + k;
-    }
-    const uint32_t f = __umulhi(seq, mtpf);
-    uint32_t t = seq - f * tpf;
-    gtab_t T = tabs + (size_t)f * tab_stride;
-    // the tile's plane (workgroup-uniform): its geometry, pitches, alignment, table, tile columns, and for V the plane distances
+    const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2;
+    const SurfTile q = surf_tile(flags, tpf, mtpf);
+    uint32_t t = q.t;
+    gtab_t T = tabs + (size_t)q.f * tab_stride;
+    // the tile's plane (workgroup-uniform): its geometry, pitches, alignment, table, tile columns, fill sample, and for V the plane distances
     WarpCore c;
     c.border = (flags >> 2) & 7u;
-    uint32_t gx, mgx;
+    uint32_t gx, mgx, fs = 0u;
     int sadd = 0, dadd = 0;
     if (t < n1) {
         c.sstride = sstride; c.dstride = dstride;
         c.sw = c.dw = w; c.sh = c.dh = h;
         c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u;
         gx = gx1; mgx = mgx1;
+        if constexpr (BORDER == VS_BORDER_FILL) fs = fill_yu;
     } else {
         t -= n1;
-        if (t >= n2) { t -= n2; sadd = svu; dadd = dvu; }
+        if constexpr (BORDER == VS_BORDER_FILL) fs = fill_yu >> 16;
+        if (t >= n2) {
+            t -= n2; sadd = svu; dadd = dvu;
+            if constexpr (BORDER == VS_BORDER_FILL) fs = fill_v;
+        }
         T += tab_layout(w, h).stride;
         c.sstride = scpitch; c.dstride = dcpitch;
         c.sw = c.dw = (int)w2; c.sh = c.dh = (int)h2;
@@ -1675,280 +1682,50 @@ __global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_s
     }
     const TabLayout L = tab_layout(c.dw, c.dh);
     const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
-    // (the 16-bit BORDER_REPLICATE instance: a direct-path callee of its own, see plane_tile; the others instantiate what they did)
-    // (the 4:2:2 and 4:4:4 instances of it: a copy each - a callee shared between kernels changes the code of all of them)
-    if constexpr (SB == 2 && BORDER == VS_BORDER_REPLICATE)
-        plane_tile<1, BORDER, SB, (CSY == 1 ? 1 : CSX == 1 ? 2 : 3)>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
-    else
-        plane_tile<1, BORDER, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
+    // (the direct-path callee: the 16-bit BORDER_REPLICATE and the VS_BORDER_FILL instances have one per subsampling, see plane_direct_tile)
+    constexpr int OWN = BORDER == VS_BORDER_FILL || (SB == 2 && BORDER == VS_BORDER_REPLICATE) ? (CSY == 1 ? 1 : CSX == 1 ? 2 : 3) : 0;
+    plane_tile<1, BORDER, SB, OWN, XR>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd,
+                                       fill_pattern<BORDER, SB>(fs));
 }
 
-// ---- planar 4:2:2 surfaces under host maps of a few degrees: a taller staged box ---------------------------------------------------
-// The roll stage and vs_op_warp_affine_planar rotate by degrees, and the 4:2:2 chroma map S^-1 M S has 2 sin(angle) where a rotation
-// has sin(angle): a full-width chroma tile's source box outgrows the THP + 9 rows of PlaneCfg at 1.80 - 2.04 degrees, where luma
-// tiles (and the tiles of a 4:2:0 surface) stay staged up to 3.61 - 4.07.  These instances stage THP + 17 rows: 254 sin(angle) < 16
-// keeps every full-width 4:2:2 chroma tile staged up to 3.61 degrees (and luma tiles up to 7.2).  BORDER_REPLICATE only, (CSX, CSY) =
-// (1, 0) only; the launcher picks them only where the maps are host doubles and some surface's chroma box needs the rows
-// (i420_needs_tall_box) - the stabilizer's launches, whose maps are on the device, keep the instances they have.
+template <int BORDER, int SB = 1>
+__global__ __launch_bounds__(NT, 8) void warp_nv12_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t swh, uint32_t dwh,
+                                                       uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2) {
+    nv12_surface_tile<BORDER, SB>(tabs, tab_stride, sstride, dstride, swh, dwh, flags, mtpf, mgx1, mgx2);
+}
+
+template <int BORDER, int SB = 1, int CSX = 1, int CSY = 1>
+__global__ __launch_bounds__(NT, 8) void warp_i420_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
+                                                       uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
+    planar_surface_tile<BORDER, SB, CSX, CSY, 0>(tabs, tab_stride, sstride, dstride, scpitch, dcpitch, wh, flags, mtpf, mgx1, mgx2, svu, dvu);
+}
+
+// Planar 4:2:2 surfaces under host maps of a few degrees: a taller staged box.  The roll stage and vs_op_warp_affine_planar rotate by
+// degrees, and the 4:2:2 chroma map S^-1 M S has 2 sin(angle) where a rotation has sin(angle): a full-width chroma tile's source box
+// outgrows the THP + 9 rows of PlaneCfg at 1.80 - 2.04 degrees, where luma tiles (and the tiles of a 4:2:0 surface) stay staged up to
+// 3.61 - 4.07.  These instances stage THP + 17 rows: 254 sin(angle) < 16 keeps every full-width 4:2:2 chroma tile staged up to 3.61
+// degrees (and luma tiles up to 7.2).  BORDER_REPLICATE only, (CSX, CSY) = (1, 0) only; the launcher picks them only where the maps are
+// host doubles and some surface's chroma box needs the rows (i420_needs_tall_box) - the stabilizer's launches, whose maps are on the
+// device, keep the instances they have.
 // LDS: 8-bit 81 rows x 256 B + 1536 B = 22 272 B, seven workgroups per CU where the THP + 9 box allows eight; 16-bit 49 x 384 B + 1280 B
-// = 20 096 B, eight.  Everything here is a copy: plane_tile_tall is plane_tile<1, VS_BORDER_REPLICATE, SB> with the taller box and a
-// plane_direct_tile copy of its own (OWN 8), so that no kernel that existed before shares a callee with these.
-template <int SB> struct TallCfg {
-    static constexpr int ROWS = PlaneCfg<1, SB>::THP + 17;
-};
-
-template <int SB>
-__device__ __forceinline__ void plane_tile_tall(const WarpCore& c, const __attribute__((address_space(4))) int32_t* Ts, gtab_t Tg, int tab_row, int tx, int tyl,
-                                                uint8_t* tile, uint8_t* lut, int2* s_row, int tid, int src_add, int dst_add) {
-    typedef PlaneCfg<1, SB> P;
-    constexpr int ROWS = TallCfg<SB>::ROWS;
-    typedef __attribute__((address_space(1))) uint8_t* gptr;
-    const int L = tid & 31, ty = tid >> 5;
-    int ad[4], bd[4];
-    const int x0 = tx * TW, y0 = tyl * P::THP;
-    const int x1 = min(x0 + TW, c.dw) - 1, y1 = min(y0 + P::THP, c.dh) - 1;
-    const uint8_t* src;
-    uint8_t* dst;
-    int ad0, ad1, bd0, bd1, Xa, Xb, Ya, Yb;
-    {
-        typedef int32_t i32x8 __attribute__((ext_vector_type(8)));
-        typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-        const i32x8 cc = *(const __attribute__((address_space(4))) i32x8*)(Ts + TAB_COL * tx);
-        const i32x4 r0 = *(const __attribute__((address_space(4))) i32x4*)(Ts + tab_row + 4 * (y0 / TH));
-        const i32x4 r1 = *(const __attribute__((address_space(4))) i32x4*)(Ts + tab_row + 4 * (y1 / TH));
-        src = (const uint8_t*)(gptr)((unsigned long long)(uint32_t)cc[0] | (unsigned long long)(uint32_t)cc[1] << 32);
-        dst = (uint8_t*)(gptr)((unsigned long long)(uint32_t)cc[2] | (unsigned long long)(uint32_t)cc[3] << 32);
-        ad0 = cc[4]; ad1 = cc[5]; bd0 = cc[6]; bd1 = cc[7];
-        Xa = r0[0]; Ya = r0[2]; Xb = r1[1]; Yb = r1[3];
-    }
-    src += src_add; dst += dst_add;
-    if (tid >= NT - 32) {      // vertical weights, as plane_tile writes them
-        const uint32_t f = tid - (NT - 32);
-        const uint32_t wlo = (32u - f) | (f << 8);
-        *reinterpret_cast<uint4*>(lut + f * LUT_STRIDE) =
-            make_uint4(wlo, wlo << 16, __float_as_uint((float)(32u - f) * 0x1p121f), __float_as_uint((float)f * 0x1p121f));
-        *reinterpret_cast<uint32_t*>(lut + f * LUT_STRIDE + 16) = (32u - f) | (f << 16);
-    }
-    // source box of the tile (the maps are monotone in x and in y separately)
-    int bx0a, by0, bw, bh;
-    bool fit;
-    {
-        const int sx00 = (Xa + ad0) >> 10, sx01 = (Xa + ad1) >> 10, sx10 = (Xb + ad0) >> 10, sx11 = (Xb + ad1) >> 10;
-        const int sy00 = (Ya + bd0) >> 10, sy01 = (Ya + bd1) >> 10, sy10 = (Yb + bd0) >> 10, sy11 = (Yb + bd1) >> 10;
-        const int rx0 = min(min(sx00, sx01), min(sx10, sx11)), rx1 = max(max(sx00, sx01), max(sx10, sx11));
-        const int ry0 = min(min(sy00, sy01), min(sy10, sy11)), ry1 = max(max(sy00, sy01), max(sy10, sy11));
-        const bool saturated = rx0 < -32768 || ry0 < -32768 || rx1 > 32767 || ry1 > 32767;
-        const int bx0 = max(rx0, -32768), bx1 = min(rx1, 32767) + 1;
-        by0 = max(ry0, -32768);
-        const int by1 = min(ry1, 32767) + 1;
-        bx0a = bx0 & ~3;
-        bw = bx1 - bx0a + 1;
-        bh = by1 - by0 + 1;
-        fit = !saturated && bw <= 136 && bh <= ROWS && c.border == VS_BORDER_REPLICATE;       // (bh <= ROWS: every staged row lies inside `tile`)
-    }
-    if (fit) {
-        constexpr int NCH = (ROWS * P::CPR + NT - 1) / NT;
-        const int total = bh * P::CPR;
-        const long long rowbytes = (long long)c.sw * P::PXB;
-        uint4 d[NCH];
-#pragma unroll
-        for (int k = 0; k < NCH; k++) {
-            const int i = tid + NT * k;
-            d[k] = make_uint4(0u, 0u, 0u, 0u);
-            if (i < total) {
-                const int r = i / P::CPR, ch = i - r * P::CPR;
-                const int y = by0 + r;
-                const long long xb = (long long)bx0a * P::PXB + 16 * ch;
-                const uint8_t* row = src + (size_t)min(max(y, 0), c.sh - 1) * c.sstride;
-                if (xb >= 0 && xb + 16 <= rowbytes && c.src_aligned) d[k] = *reinterpret_cast<const uint4*>(row + xb);
-                else d[k] = load_chunk_replicate<P::PXB>(row, (int)max(min(xb, (long long)rowbytes + 64), -64ll), c.sw);
-            }
-        }
-        const int x = x0 + 4 * L;
-        if (x1 - x0 == TW - 1 && (c.dw & 3) == 0) {
-            typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-            typedef const __attribute__((address_space(1))) i32x4* g4;
-            const i32x4 a4 = *(g4)(Tg + x), b4 = *(g4)(Tg + c.dw + x);
-            ad[0] = a4.x; ad[1] = a4.y; ad[2] = a4.z; ad[3] = a4.w;
-            bd[0] = b4.x; bd[1] = b4.y; bd[2] = b4.z; bd[3] = b4.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int cx = min(x + i, x1);
-                ad[i] = Tg[cx]; bd[i] = Tg[c.dw + cx];
-            }
-        }
-        if (tid >= TW && tid < TW + P::THP) {
-            const int r = min(y0 + (tid - TW), y1);
-            s_row[tid - TW] = make_int2(Tg[2 * c.dw + r] - (bx0a << 10), Tg[2 * c.dw + c.dh + r] - (by0 << 10));
-        }
-#pragma unroll
-        for (int k = 0; k < NCH; k++) {
-            const int i = tid + NT * k;
-            if (i < total) {
-                const int r = i / P::CPR;
-                *reinterpret_cast<uint4*>(tile + r * P::PB + 16 * (i - r * P::CPR)) = d[k];
-            }
-        }
-    }
-    if (!fit) {
-        plane_direct_tile<1, SB, 8>(c, src, dst, Tg, reinterpret_cast<int*>(tile), x0, y0, x1, y1, bx0a, by0, bw, tid);
-        return;
-    }
-    __syncthreads();
-    plane_blend_rows<1, SB>(c, tile, lut, s_row, ad, bd, L, ty, dst, (uint32_t)c.dstride, x0, y0, x1, y1);
-}
-
-// warp_i420_kernel<VS_BORDER_REPLICATE, SB, 1, 0> with the taller box: the same tile sequence, grid order, table blocks and arguments.
+// = 20 096 B, eight.
 template <int SB>
 __global__ __launch_bounds__(NT, 7) void warp_i422_tall_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
                                                             uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu) {
-    typedef PlaneCfg<1, SB> P;
-    __shared__ __attribute__((aligned(16))) uint8_t tile[TallCfg<SB>::ROWS * P::PB];
-    __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
-    __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];
-    typedef const __attribute__((address_space(4))) int32_t* cptr;
-    const int w = wh & 0xFFFFu, h = wh >> 16;
-    const uint32_t gx1 = (uint32_t)(w + TW - 1) / TW, gy1 = (uint32_t)(h + P::THP - 1) / P::THP;
-    const uint32_t w2 = (uint32_t)w >> 1, h2 = (uint32_t)h;
-    const uint32_t gx2 = (w2 + TW - 1) / TW, gy2 = (h2 + P::THP - 1) / P::THP;
-    const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2, n = tpf * (flags >> 16);
-    const uint32_t lin = blockIdx.x;
-    uint32_t seq = lin;
-    if (flags & 0x100u) {
-        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-        seq = cx * q + (cx < r ? cx : r) + k;
-    }
-    const uint32_t f = __umulhi(seq, mtpf);
-    uint32_t t = seq - f * tpf;
-    gtab_t T = tabs + (size_t)f * tab_stride;
-    WarpCore c;
-    c.border = (flags >> 2) & 7u;
-    uint32_t gx, mgx;
-    int sadd = 0, dadd = 0;
-    if (t < n1) {
-        c.sstride = sstride; c.dstride = dstride;
-        c.sw = c.dw = w; c.sh = c.dh = h;
-        c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u;
-        gx = gx1; mgx = mgx1;
-    } else {
-        t -= n1;
-        if (t >= n2) { t -= n2; sadd = svu; dadd = dvu; }
-        T += tab_layout(w, h).stride;
-        c.sstride = scpitch; c.dstride = dcpitch;
-        c.sw = c.dw = (int)w2; c.sh = c.dh = (int)h2;
-        c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
-        gx = gx2; mgx = mgx2;
-    }
-    const TabLayout L = tab_layout(c.dw, c.dh);
-    const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
-    plane_tile_tall<SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row, threadIdx.x, sadd, dadd);
+    planar_surface_tile<VS_BORDER_REPLICATE, SB, 1, 0, 8>(tabs, tab_stride, sstride, dstride, scpitch, dcpitch, wh, flags, mtpf, mgx1, mgx2, svu, dvu);
 }
-
-// ---- edge fill on YUV surfaces: the VS_BORDER_FILL instances ----------------------------------------------------------------------
-// cv::warpAffine(..., INTER_LINEAR, BORDER_CONSTANT, borderValue = fill) per plane: what the VS_BORDER_BLACK instances of the two
-// one-launch kernels compute, with the plane's fill sample where those read zeros (plane_tile<CN, VS_BORDER_FILL, SB>).  The fill
-// travels as two more kernel arguments - Y | U << 16 and V, samples as they lie in memory - behind the arguments of the kernels
-// above (13 and 16 dwords: still preloaded into scalar registers), which is why these are kernels of their own and not two more
-// instances of the templates above: those keep their argument lists, and WarpCore its fields, so that no existing kernel's scalar
-// registers move.  Everything else - tile sequence, grid order, table blocks, flags (border = VS_BORDER_FILL) - is theirs to the letter.
-// A plane's pattern: an 8-bit sample four times, the (U, V) byte pair twice, a 16-bit sample twice, or the (U, V) pair of P010.
-template <int SB>
-__device__ __forceinline__ uint32_t fill_pattern(uint32_t f) { return SB == 2 ? (f & 0xFFFFu) | f << 16 : (f & 0xFFu) * 0x01010101u; }
 
 template <int SB>
 __global__ __launch_bounds__(NT, 8) void warp_nv12_fill_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t swh, uint32_t dwh,
                                                             uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, uint32_t fill_yu, uint32_t fill_v) {
-    typedef PlaneCfg<1, SB> P1;
-    typedef PlaneCfg<2, SB> P2;
-    constexpr int TILE_BYTES = P1::ROWS * P1::PB > P2::ROWS * P2::PB ? P1::ROWS * P1::PB : P2::ROWS * P2::PB;
-    __shared__ __attribute__((aligned(16))) uint8_t tile[TILE_BYTES];
-    __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
-    __shared__ __attribute__((aligned(16))) int2 s_row[P1::THP];
-    typedef const __attribute__((address_space(4))) int32_t* cptr;
-    WarpCore c;
-    c.sstride = sstride; c.dstride = dstride;
-    c.sw = swh & 0xFFFFu; c.sh = swh >> 16; c.dw = dwh & 0xFFFFu; c.dh = dwh >> 16;
-    c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u; c.border = (flags >> 2) & 7u;
-    const uint32_t gx1 = (uint32_t)(c.dw + TW - 1) / TW, gy1 = (uint32_t)(c.dh + P1::THP - 1) / P1::THP;
-    const uint32_t dw2 = (uint32_t)c.dw >> 1, dh2 = (uint32_t)c.dh >> 1;
-    const uint32_t gx2 = (dw2 + TW - 1) / TW, gy2 = (dh2 + P2::THP - 1) / P2::THP;
-    const uint32_t n1 = gx1 * gy1, tpf = n1 + gx2 * gy2, n = tpf * (flags >> 16);
-    const uint32_t lin = blockIdx.x;
-    uint32_t seq = lin;
-    if (flags & 0x100u) {
-        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-        seq = cx * q + (cx < r ? cx : r) + k;
-    }
-    const uint32_t f = __umulhi(seq, mtpf);
-    uint32_t t = seq - f * tpf;
-    gtab_t T = tabs + (size_t)f * tab_stride;
-    if (t < n1) {
-        const TabLayout L = tab_layout(c.dw, c.dh);
-        const uint32_t row = gx1 == 1 ? t : __umulhi(t, mgx1);
-        plane_tile<1, VS_BORDER_FILL, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx1), (int)row, tile, lut, s_row, threadIdx.x, 0, 0,
-                                          fill_pattern<SB>(fill_yu));
-    } else {
-        t -= n1;
-        T += tab_layout(c.dw, c.dh).stride;
-        c.sw >>= 1; c.sh >>= 1; c.dw = (int)dw2; c.dh = (int)dh2;
-        c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
-        const TabLayout L = tab_layout(c.dw, c.dh);
-        const uint32_t row = gx2 == 1 ? t : __umulhi(t, mgx2);
-        const uint32_t u = fill_yu >> 16;
-        plane_tile<2, VS_BORDER_FILL, SB>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx2), (int)row, tile, lut, s_row, threadIdx.x, 0, 0,
-                                          SB == 2 ? u | fill_v << 16 : ((u & 0xFFu) | (fill_v & 0xFFu) << 8) * 0x00010001u);
-    }
+    nv12_surface_tile<VS_BORDER_FILL, SB>(tabs, tab_stride, sstride, dstride, swh, dwh, flags, mtpf, mgx1, mgx2, fill_yu, fill_v);
 }
 
 template <int SB, int CSX, int CSY>
 __global__ __launch_bounds__(NT, 8) void warp_i420_fill_kernel(gtab_t tabs, int tab_stride, uint32_t sstride, uint32_t dstride, uint32_t scpitch, uint32_t dcpitch,
                                                             uint32_t wh, uint32_t flags, uint32_t mtpf, uint32_t mgx1, uint32_t mgx2, int32_t svu, int32_t dvu,
                                                             uint32_t fill_yu, uint32_t fill_v) {
-    typedef PlaneCfg<1, SB> P;
-    __shared__ __attribute__((aligned(16))) uint8_t tile[P::ROWS * P::PB];
-    __shared__ __attribute__((aligned(16))) uint8_t lut[32 * LUT_STRIDE];
-    __shared__ __attribute__((aligned(16))) int2 s_row[P::THP];
-    typedef const __attribute__((address_space(4))) int32_t* cptr;
-    const int w = wh & 0xFFFFu, h = wh >> 16;
-    const uint32_t gx1 = (uint32_t)(w + TW - 1) / TW, gy1 = (uint32_t)(h + P::THP - 1) / P::THP;
-    const uint32_t w2 = (uint32_t)w >> CSX, h2 = (uint32_t)h >> CSY;
-    const uint32_t gx2 = (w2 + TW - 1) / TW, gy2 = (h2 + P::THP - 1) / P::THP;
-    const uint32_t n1 = gx1 * gy1, n2 = gx2 * gy2, tpf = n1 + 2 * n2, n = tpf * (flags >> 16);
-    const uint32_t lin = blockIdx.x;
-    uint32_t seq = lin;
-    if (flags & 0x100u) {
-        const uint32_t cx = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-        seq = cx * q + (cx < r ? cx : r) + k;
-    }
-    const uint32_t f = __umulhi(seq, mtpf);
-    uint32_t t = seq - f * tpf;
-    gtab_t T = tabs + (size_t)f * tab_stride;
-    // the tile's plane (workgroup-uniform): geometry, pitches, alignment, table and tile columns as above, and the plane's fill sample
-    WarpCore c;
-    c.border = (flags >> 2) & 7u;
-    uint32_t gx, mgx, fs;
-    int sadd = 0, dadd = 0;
-    if (t < n1) {
-        c.sstride = sstride; c.dstride = dstride;
-        c.sw = c.dw = w; c.sh = c.dh = h;
-        c.src_aligned = flags & 1u; c.dst_aligned = (flags >> 1) & 1u;
-        gx = gx1; mgx = mgx1; fs = fill_yu;
-    } else {
-        t -= n1;
-        fs = fill_yu >> 16;
-        if (t >= n2) { t -= n2; sadd = svu; dadd = dvu; fs = fill_v; }
-        T += tab_layout(w, h).stride;
-        c.sstride = scpitch; c.dstride = dcpitch;
-        c.sw = c.dw = (int)w2; c.sh = c.dh = (int)h2;
-        c.src_aligned = (flags >> 5) & 1u; c.dst_aligned = (flags >> 6) & 1u;
-        gx = gx2; mgx = mgx2;
-    }
-    const TabLayout L = tab_layout(c.dw, c.dh);
-    const uint32_t row = gx == 1 ? t : __umulhi(t, mgx);
-    // (a direct-path callee per subsampling, as the 16-bit BORDER_REPLICATE instances above have)
-    plane_tile<1, VS_BORDER_FILL, SB, (CSY == 1 ? 1 : CSX == 1 ? 2 : 3)>(c, (cptr)(const int32_t*)T, T + L.ad, L.row, (int)(t - row * gx), (int)row, tile, lut, s_row,
-                                                                         threadIdx.x, sadd, dadd, fill_pattern<SB>(fs));
+    planar_surface_tile<VS_BORDER_FILL, SB, CSX, CSY, 0>(tabs, tab_stride, sstride, dstride, scpitch, dcpitch, wh, flags, mtpf, mgx1, mgx2, svu, dvu, fill_yu, fill_v);
 }
 
 // Launches without tables (a caller's tables exist for launches of WARP_TAB_MIN surfaces and more only), chroma planes that do not lie
@@ -1964,15 +1741,7 @@ __global__ __launch_bounds__(NT) void warp_plane_fill_kernel(WarpArgs a, uint32_
     const int x1 = min(x0 + TW, a.c.dw) - 1, y1 = min(y0 + TH, a.c.dh) - 1;
     double m[6];
     load_map(a, bz, m);
-    if (tid < TW) {
-        const double dv = (double)min(x0 + tid, x1);
-        s_ad[tid] = coord_term(m[0], 0.0, dv);
-        s_bd[tid] = coord_term(m[3], 0.0, dv);
-    } else if (tid < TW + TH) {
-        const double dv = (double)min(y0 + (tid - TW), y1);
-        s_x0[tid - TW] = coord_term(m[1], m[2], dv) + 16;
-        s_y0[tid - TW] = coord_term(m[4], m[5], dv) + 16;
-    }
+    map_terms(m, x0, y0, x1, y1, tid, s_ad, s_bd, s_x0, s_y0);
     __syncthreads();
     emit_rows<CN, false, SB, true>(a.c, a.srcs[bz], a.dsts[bz], nullptr, s_ad, s_bd, s_x0, s_y0, x0, y0, x1, y1, 0, 0, 0, tid, fillpx);
 }
@@ -2168,24 +1937,17 @@ int nv12_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, size_t sstr
     const uint32_t flags = (al & 1u) | (al & 2u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    if (border == VS_BORDER_FILL && sb == 2)
-        hipLaunchKernelGGL((warp_nv12_fill_kernel<2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
-                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, fill.y | fill.u << 16, fill.v);
-    else if (border == VS_BORDER_FILL)
-        hipLaunchKernelGGL((warp_nv12_fill_kernel<1>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
-                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, fill.y | fill.u << 16, fill.v);
-    else if (sb == 2 && border == VS_BORDER_REPLICATE)
-        hipLaunchKernelGGL((warp_nv12_kernel<VS_BORDER_REPLICATE, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
-                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
-    else if (sb == 2)
-        hipLaunchKernelGGL((warp_nv12_kernel<VS_BORDER_BLACK, 2>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
-                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
-    else if (border == VS_BORDER_REPLICATE)
-        hipLaunchKernelGGL(warp_nv12_kernel<VS_BORDER_REPLICATE>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
-                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
-    else
-        hipLaunchKernelGGL(warp_nv12_kernel<VS_BORDER_BLACK>, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride,
-                           (uint32_t)dstride, (uint32_t)w | (uint32_t)h << 16, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2);
+    const uint32_t wh = (uint32_t)w | (uint32_t)h << 16;
+    auto go = [&](auto kernel, auto... fills) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, nv12_tab_ints(w, h), (uint32_t)sstride, (uint32_t)dstride, wh, wh, flags,
+                           mtpf, mgx1, mgx2, fills...);
+    };
+    if (border == VS_BORDER_FILL && sb == 2) go(warp_nv12_fill_kernel<2>, fill.y | fill.u << 16, fill.v);
+    else if (border == VS_BORDER_FILL) go(warp_nv12_fill_kernel<1>, fill.y | fill.u << 16, fill.v);
+    else if (sb == 2 && border == VS_BORDER_REPLICATE) go(warp_nv12_kernel<VS_BORDER_REPLICATE, 2>);
+    else if (sb == 2) go(warp_nv12_kernel<VS_BORDER_BLACK, 2>);
+    else if (border == VS_BORDER_REPLICATE) go(warp_nv12_kernel<VS_BORDER_REPLICATE>);
+    else go(warp_nv12_kernel<VS_BORDER_BLACK>);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }
@@ -2218,49 +1980,28 @@ int i420_launch(const uint8_t* const* ys, uint8_t* const* yd, int n, const I420L
     const uint32_t flags = (al & 3u) | (uint32_t)border << 2 | ((al >> 2) & 1u) << 5 | ((al >> 3) & 1u) << 6 | 0x100u | (uint32_t)n << 16;
     const uint32_t mtpf = (uint32_t)((0x100000000ull + tpf - 1) / tpf), mgx1 = (uint32_t)((0x100000000ull + gx1 - 1) / gx1),
                    mgx2 = (uint32_t)((0x100000000ull + gx2 - 1) / gx2);
-    // (one instance per sample size, border and subsampling; 4:2:0 keeps the four it had)
-#define VS_I420_GO(B, S, X, Y)                                                                                                                              \
-    hipLaunchKernelGGL((warp_i420_kernel<B, S, X, Y>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, X, Y), (uint32_t)sl.pitch, \
-                       (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,    \
-                       (int32_t)dvu)
-#define VS_I420_SUB(B, S)                                \
-    do {                                                 \
-        if (sx == 1 && sy == 1) VS_I420_GO(B, S, 1, 1);  \
-        else if (sx == 1) VS_I420_GO(B, S, 1, 0);        \
-        else VS_I420_GO(B, S, 0, 0);                     \
-    } while (0)
+    auto go = [&](auto kernel, auto... fills) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, sx, sy), (uint32_t)sl.pitch, (uint32_t)dl.pitch,
+                           (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu, (int32_t)dvu, fills...);
+    };
+    // a kernel's instance for this launch's subsampling, of its three: 4:2:0, 4:2:2, 4:4:4
+    auto sub = [&](auto k420, auto k422, auto k444) { return sx == 1 && sy == 1 ? k420 : sx == 1 ? k422 : k444; };
     // (tall: 4:2:2, BORDER_REPLICATE, host maps that need the taller staged box - launch_warp_i420 decides)
-#define VS_I422_TALL(S)                                                                                                                                    \
-    hipLaunchKernelGGL((warp_i422_tall_kernel<S>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, 1, 0), (uint32_t)sl.pitch, \
-                       (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,    \
-                       (int32_t)dvu)
-    // (VS_BORDER_FILL: the kernel with the fill behind these arguments)
-#define VS_I420_FILL(S, X, Y)                                                                                                                               \
-    hipLaunchKernelGGL((warp_i420_fill_kernel<S, X, Y>), dim3((unsigned)total), dim3(NT), 0, st, (gtab_t)d_tabs, planar_tab_ints(w, h, X, Y), (uint32_t)sl.pitch, \
-                       (uint32_t)dl.pitch, (uint32_t)sl.cpitch, (uint32_t)dl.cpitch, (uint32_t)w | (uint32_t)h << 16, flags, mtpf, mgx1, mgx2, (int32_t)svu,    \
-                       (int32_t)dvu, fill.y | fill.u << 16, fill.v)
-#define VS_I420_FILL_SUB(S)                                \
-    do {                                                   \
-        if (sx == 1 && sy == 1) VS_I420_FILL(S, 1, 1);     \
-        else if (sx == 1) VS_I420_FILL(S, 1, 0);           \
-        else VS_I420_FILL(S, 0, 0);                        \
-    } while (0)
     const bool use_tall = tall && sx == 1 && sy == 0 && border == VS_BORDER_REPLICATE;
     const bool use_fill = border == VS_BORDER_FILL;
-    if (use_tall || use_fill) ;      // (below: the instances that came later are instantiated behind the others, which keep their place in the code object)
-    else if (sb == 2 && border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 2);
-    else if (sb == 2) VS_I420_SUB(VS_BORDER_BLACK, 2);
-    else if (border == VS_BORDER_REPLICATE) VS_I420_SUB(VS_BORDER_REPLICATE, 1);
-    else VS_I420_SUB(VS_BORDER_BLACK, 1);
-    if (use_tall && sb == 2) VS_I422_TALL(2);
-    else if (use_tall) VS_I422_TALL(1);
-    else if (use_fill && sb == 2) VS_I420_FILL_SUB(2);
-    else if (use_fill) VS_I420_FILL_SUB(1);
-#undef VS_I420_FILL_SUB
-#undef VS_I420_FILL
-#undef VS_I422_TALL
-#undef VS_I420_SUB
-#undef VS_I420_GO
+    // (the instances are named in the order in which they came: a later one is placed behind the earlier ones in the code object, which
+    // keep their place)
+    if (use_tall || use_fill) ;
+    else if (sb == 2 && border == VS_BORDER_REPLICATE)
+        go(sub(warp_i420_kernel<VS_BORDER_REPLICATE, 2, 1, 1>, warp_i420_kernel<VS_BORDER_REPLICATE, 2, 1, 0>, warp_i420_kernel<VS_BORDER_REPLICATE, 2, 0, 0>));
+    else if (sb == 2) go(sub(warp_i420_kernel<VS_BORDER_BLACK, 2, 1, 1>, warp_i420_kernel<VS_BORDER_BLACK, 2, 1, 0>, warp_i420_kernel<VS_BORDER_BLACK, 2, 0, 0>));
+    else if (border == VS_BORDER_REPLICATE)
+        go(sub(warp_i420_kernel<VS_BORDER_REPLICATE, 1, 1, 1>, warp_i420_kernel<VS_BORDER_REPLICATE, 1, 1, 0>, warp_i420_kernel<VS_BORDER_REPLICATE, 1, 0, 0>));
+    else go(sub(warp_i420_kernel<VS_BORDER_BLACK, 1, 1, 1>, warp_i420_kernel<VS_BORDER_BLACK, 1, 1, 0>, warp_i420_kernel<VS_BORDER_BLACK, 1, 0, 0>));
+    if (use_tall && sb == 2) go(warp_i422_tall_kernel<2>);
+    else if (use_tall) go(warp_i422_tall_kernel<1>);
+    else if (use_fill && sb == 2) go(sub(warp_i420_fill_kernel<2, 1, 1>, warp_i420_fill_kernel<2, 1, 0>, warp_i420_fill_kernel<2, 0, 0>), fill.y | fill.u << 16, fill.v);
+    else if (use_fill) go(sub(warp_i420_fill_kernel<1, 1, 1>, warp_i420_fill_kernel<1, 1, 0>, warp_i420_fill_kernel<1, 0, 0>), fill.y | fill.u << 16, fill.v);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }

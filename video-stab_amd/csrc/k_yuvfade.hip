@@ -147,7 +147,7 @@ __device__ __forceinline__ void yf_blend_tile(const YfJob& J, int tx, int ty, fl
 
 template <int SB>
 __global__ __launch_bounds__(64 * YF_WAVES) void yuvfade_blend_kernel(const YfArgs a) {
-    const uint32_t seq = pj_seq(blockIdx.x, a.tiles);
+    const uint32_t seq = xcd_seq(blockIdx.x, a.tiles);
     const YfJob J = a.j[pj_find(a, seq, [](const YfJob& j) { return j.t0f & YF_T0_MASK; })];
     const uint32_t cn = ((J.t0f >> 24) & 1u) + 1u;
     const uint32_t dw = (J.swh & 0xffffu) + 2u * (J.bxy & 0xffffu);
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(64 * YF_WAVES) void yuvfade_update_kernel(const Yfu
     constexpr int NEL = PJ_LB / SB, SPD = 4 / SB;
     constexpr uint32_t SMASK = SB == 1 ? 0xffu : 0xffffu;
     constexpr int CL = yf_cl(SB), RW = 64 / CL, TR = yf_tr(SB);
-    const uint32_t seq = pj_seq(blockIdx.x, a.tiles);
+    const uint32_t seq = xcd_seq(blockIdx.x, a.tiles);
     const YfuJob J = a.j[pj_find(a, seq, [](const YfuJob& j) { return j.t0; })];
     const PjTile t = pj_split(seq - J.t0, J.rowb, yf_tb(SB));
     const int ty = t.ty;

@@ -164,7 +164,7 @@ __device__ __forceinline__ void yp_tile(const YpJob& J, int tx, int ty) {
 
 template <int SB>
 __global__ __launch_bounds__(64 * YP_WAVES) void yuvpad_kernel(const YpArgs a) {
-    const uint32_t seq = pj_seq(blockIdx.x, a.tiles);
+    const uint32_t seq = xcd_seq(blockIdx.x, a.tiles);
     const YpJob J = a.j[pj_find(a, seq, [](const YpJob& j) { return j.t0f & YP_T0_MASK; })];
     const uint32_t cn = ((J.t0f >> 24) & 1u) + 1u;
     const uint32_t dw = (J.swh & 0xffffu) + 2u * (J.bxy & 0xffffu);

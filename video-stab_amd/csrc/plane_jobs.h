@@ -2,8 +2,8 @@
 // k_yuvfade.hip (vs_op_fade_blend_jobs, vs_op_fade_update_jobs).
 //
 // The scheme.  One launch takes up to a limit of jobs (one plane each) of one sample size, cn 1 and 2 mixed.  It is a flat sequence of
-// (job, tile row, tile column) tiles in the XCD-aware order of k_warp.hip (tile_id): workgroup `lin` takes tile pj_seq(lin), XCD
-// c = lin mod 8 the c-th contiguous eighth of the sequence, so that tiles that share lines meet in one L2.  The jobs travel as
+// (job, tile row, tile column) tiles in the XCD-aware order of the warp kernels: workgroup `lin` takes tile xcd_seq(lin, tiles)
+// (vs_common.h), XCD c = lin mod 8 the c-th contiguous eighth of the sequence, so that tiles that share lines meet in one L2.  The jobs travel as
 // kernel arguments, each with its first tile in the sequence; a workgroup finds its job by bisection over them (scalar loads,
 // pj_find) and its tile column and row from the job's row bytes (pj_split).  The job records, their size and their 24-bit tile
 // budget are each file's own.
@@ -29,12 +29,6 @@ namespace vsd {
 constexpr int PJ_LB = 16;                                                         // bytes per lane and row
 constexpr int pj_tb(int cl) { return cl * PJ_LB; }                                // tile: bytes ...
 constexpr int pj_tr(int waves, int r, int cl) { return waves * r * (64 / cl); }   // ... and rows
-
-// The tile of workgroup `lin` of n
-__device__ __forceinline__ uint32_t pj_seq(uint32_t lin, uint32_t n) {
-    const uint32_t c = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
-    return c * q + (c < r ? c : r) + k;
-}
 
 // The job of tile seq: the last of a.j[0 .. a.n - 1] whose first tile is not behind it
 template <class Args, class First>

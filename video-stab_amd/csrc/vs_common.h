@@ -100,6 +100,13 @@ __device__ __forceinline__ int reflect101(int p, int len) {
     } while ((unsigned)p >= (unsigned)len);
     return p;
 }
+// XCD-aware tile order.  The hardware hands consecutive workgroups to the 8 XCDs in turn (linear id mod 8), and every XCD has an L2
+// of its own.  Workgroup `lin` of n takes tile xcd_seq(lin, n) of the launch's tile sequence: XCD c = lin mod 8 takes the c-th
+// contiguous eighth of it, so that tiles that share source lines meet in one L2 (k_warp.hip at tile_id has the traffic figures).
+__device__ __forceinline__ uint32_t xcd_seq(uint32_t lin, uint32_t n) {
+    const uint32_t c = lin & 7u, k = lin >> 3, q = n >> 3, r = n & 7u;
+    return c * q + (c < r ? c : r) + k;
+}
 #endif
 
 // cv::warpAffine's inversion of the forward 2x3 matrix, in double (imgwarp.cpp).  The same
