@@ -11,6 +11,7 @@
 #                     * vs_libm.h (host build) over 2^24 arguments per function against the host libm;
 #                     * the format table and the refusal rules (csrc/pixfmt.h) in tests/cpp/pixfmt_check over the whole case list
 #                       of tests/refusal_cases.py, the plane list of a YUV surface (csrc/planar_layout.h) in tests/cpp/planes_check,
+#                       the frame record of the roll and zoom/crop stages (the same header) in tests/cpp/stage_frame_check,
 #                       and the rules of the fade border on YUV in tests/cpp/yuv_fade_check.
 #                   GPU sanitizers are not available on this pool; device code is covered by the parity tests instead.
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
@@ -39,6 +40,7 @@ asan-host:
 	g++ -O1 -g -std=c++17 -ffp-contract=off -pthread $(SAN) -DLIBM_CHECK_QUICK tests/cpp/libm_check.cpp -o scratch/fuzz/_asan/libm_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/pixfmt_check.cpp -o scratch/fuzz/_asan/pixfmt_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/planes_check.cpp -o scratch/fuzz/_asan/planes_check
+	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/stage_frame_check.cpp -o scratch/fuzz/_asan/stage_frame_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/yuv_fade_check.cpp -o scratch/fuzz/_asan/yuv_fade_check
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/config_fuzz 20000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/azc_fuzz 5000
@@ -48,6 +50,7 @@ asan-host:
 	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/pixfmt_check cases > /dev/null
 	for f in 1 6 7 8 9 10 11 12 13 14 15; do for s in "2 2" "6 4" "66 50"; do for l in "0 0 0 0" "8192 0 0 0" "0 12288 8192 0" "0 0 0 128"; do \
 	  echo "$$f $$s 256 $$l"; done; done; done | ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/planes_check > /dev/null
+	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/stage_frame_check
 	for f in 0 1 2 6 7 8 10 11 12 15; do for b in 0 5 8; do for m in 0 1; do echo "$$f 64 48 128 $$b 0 $$m 1 $$m 1 70"; done; done; done | \
 	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/yuv_fade_check > /dev/null
 

@@ -151,6 +151,78 @@ def test_roll_correct_matches_the_reference(gpu, oracle, fmt, size, tilt):
             check(got[i], lo, want[i], (n, i))
 
 
+def _rows_buffer(planes, offs, pitches, size, canary=0x5A):
+    """A buffer of `size` bytes, canaries everywhere but the rows of the 2-D byte planes at their offsets and pitches."""
+    buf = np.full(size, canary, np.uint8)
+    for p, off, pitch in zip(planes, offs, pitches):
+        rows, rb = p.shape
+        view = np.lib.stride_tricks.as_strided(buf[off:], (rows, rb), (pitch, 1))
+        view[:] = p
+    return buf
+
+
+@pytest.mark.parametrize("kind", ["NV12", "I422", "BGRA8"])
+def test_roll_correct_results_of_one_batch_in_three_layouts(gpu, oracle, kind):
+    """Three surfaces of the smallest size handed over one by one with three result layouts: one batch (one format, geometry and source
+    layout) whose rotations go frame by frame.  Every result is the reference's for the oracle's angle, the whole buffer compared.
+    NV12: the planes of the I420 form with U and V interleaved (an I420 result is the de-interleaved NV12 result); BGRA8: the angles of
+    the oracle's BGR object, every channel - the fourth too - a plane of its own under M (4:4:4)."""
+    size, tilt = inp.SIZES[0], "3deg"
+    w, h = size
+    rg = gpu.roll_correction(inp.roll_params(gpu, size, **inp.FOLLOW))
+    try:
+        if kind == "I422":
+            states = inp.roll_oracle(oracle, size, tilt)[:3]
+            planes = inp.roll_planes(kind, size, tilt)[:3]
+            li, los = Lay(kind, w, h), [Lay(kind, w, h, s) for s in ("packed", "padded", "vfirst")]
+            got = roll_run(gpu, rg, [(kind, p, li, lo) for p, lo in zip(planes, los)])
+            assert rg.state() == states[-1] and all(st[0] != 0.0 for st in states)
+            for i, lo in enumerate(los):
+                check(got[i], lo, ref.rotate_planar(planes[i], kind, states[i][0]), (kind, i))
+            return
+        if kind == "NV12":
+            states = inp.roll_oracle(oracle, size, tilt)[:3]
+            yuv = inp.roll_planes("I420", size, tilt)[:3]
+            want = [ref.rotate_planar(p, "I420", st[0]) for p, st in zip(yuv, states)]
+            two = lambda p: [p[0], np.stack([p[1], p[2]], axis=2).reshape(h // 2, w)]       # Y rows, interleaved (U, V) rows
+            srcs, want = [two(p) for p in yuv], [two(p) for p in want]
+            # (out_pitch, out_uv_offset, bytes): packed with the default offset; padded rows; the chroma plane apart
+            outs = [(w, 0, w * h * 3 // 2), (w + 64, 0, (w + 64) * h * 3 // 2), (w, w * h + 128, w * h + 128 + w * h // 2)]
+            lay = [((0, ouv or h * op), (op, op)) for op, ouv, _ in outs]
+            call = lambda di, do, i: rg.correct_nv12_dev(di.ptr, w, h, w, do.ptr, outs[i][0], 0, outs[i][1])
+        else:
+            frames = inp.roll_frames(size, tilt)[:3]
+            ro = oracle.roll_correction(inp.roll_params(oracle, size, **inp.FOLLOW))
+            states = []
+            for f in frames:
+                ro.correct(f)
+                states.append(ro.state())
+            ro.close()
+            alpha = [np.roll(f[:, :, 1], 7 + i, axis=1) ^ 0x55 for i, f in enumerate(frames)]
+            chans = [[f[:, :, 0], f[:, :, 1], f[:, :, 2], a] for f, a in zip(frames, alpha)]
+            rot = [ref.rotate_planar(c[:3], "I444", st[0]) + [ref.rotate_planar([c[3]] * 3, "I444", st[0])[0]] for c, st in zip(chans, states)]
+            srcs, want = [[np.stack(c, axis=2).reshape(h, w * 4)] for c in chans], [[np.stack(c, axis=2).reshape(h, w * 4)] for c in rot]
+            outs = [(w * 4, 0, w * 4 * h), (w * 4 + 64, 0, (w * 4 + 64) * h), (w * 4 + 128, 0, (w * 4 + 128) * h)]
+            lay = [((0,), (op,)) for op, _, _ in outs]
+            call = lambda di, do, i: rg.correct_rgb_dev(capi.FMT_BGRA8, di.ptr, w, h, w * 4, do.ptr, outs[i][0])
+        assert all(st[0] != 0.0 for st in states), "a surface would pass by not being rotated"
+        d_in = [capi.DevBuf.from_array(gpu, np.concatenate([p.reshape(-1) for p in s])) for s in srcs]
+        d_out = [capi.DevBuf.from_array(gpu, np.full(size_, 0x5A, np.uint8)) for _, _, size_ in outs]
+        try:
+            for i in range(3):
+                call(d_in[i], d_out[i], i)
+            rg.sync()
+            assert rg.state() == states[-1]
+            for i, (_, _, size_) in enumerate(outs):
+                got = d_out[i].download((size_,), np.uint8)
+                assert np.array_equal(got, _rows_buffer(want[i], lay[i][0], lay[i][1], size_)), (kind, i, int((got != _rows_buffer(want[i], lay[i][0], lay[i][1], size_)).sum()))
+        finally:
+            for d in d_in + d_out:
+                d.free()
+    finally:
+        rg.close()
+
+
 # ---- 2. zoom ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("out", inp.ZOOM_OUT, ids=["default_640x360", "own_size", "416x232"])
 @pytest.mark.parametrize("size", inp.SIZES, ids=SIZE_IDS)

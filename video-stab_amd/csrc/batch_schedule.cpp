@@ -248,7 +248,7 @@ int group_ready_launches(vs_batch* g, vs_batch::Ready& R, int what, hipStream_t 
         const WarpTabs tabs{WarpTabs::CALLER, g->d_tabs[R.set] + (size_t)i0 * g->tab_ints, g->tab_ints, what};
         if (s0->pf->kind != PIX_INTERLEAVED) {
             // (one output layout per launch: the due frames of a step are all the caller's surfaces or all the host staging)
-            rc = warp_yuv(srcs, dsts, m, warp_src_planes(s0), warp_dst_planes(s0, dsts[0], R.stride), maps, wb, tabs, st);
+            rc = warp_planes(srcs, dsts, m, warp_src_planes(s0), warp_dst_planes(s0, dsts[0], R.stride), maps, wb.border, wb.fill, tabs, st);
             // crop-and-zoom on YUV surfaces: ONE launch behind the warps resizes the crops of all their planes into the results
             if (cz && what != VS_WARP_TABLES_ONLY && rc == VS_OK) rc = cz_launch(s0, dsts, &R.dsts[i0], m, R.stride, st);
             continue;

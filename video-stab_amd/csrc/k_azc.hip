@@ -240,21 +240,46 @@ __global__ __launch_bounds__(256) void expand_bits_kernel(const u64* __restrict_
     if (x < w && y < h) mask[(size_t)y * mstride + x] = (F[(size_t)y * wpr + (x >> 6)] >> (x & 63)) & 1 ? 255 : 0;
 }
 
+// The pictures a content mask is taken from: what a pixel is, and - for a batch - the table of sources.
+struct MaskSources {
+    int cn = 1;                  // channels of a pixel: 1, or 3 / 4 (interleaved colour pictures)
+    int sb = 1;                  // bytes of a sample; 2 (a table of sources, cn 1): luma planes of 16-bit samples, stride in bytes, everything even
+    int lo_shift = 0;            // 16-bit samples: 0 = the mask of their high bytes (P010), else that of min(sample >> lo_shift, 255) (I010: 2, I012: 4)
+    int bi = 0;                  // the byte of B inside a colour pixel (BGR8 / BGRA8: 0, RGB8 / RGBA8: 2)
+    // the table (optional, d_src == nullptr): `frames` <= SRC_LIST_MAX source pointers on the HOST, one geometry and pitch, aligned:
+    // every one of them is 4-byte aligned; the pictures' bit planes / results lie tfb / ofb words apart
+    const uint8_t* const* srcs = nullptr;
+    int frames = 1, aligned = 0;
+    size_t tfb = 0, ofb = 0;
+};
+// ... the sample part of it for the frames of a format (the roll / zoom stages' formats: the luma plane, or the colour picture)
+MaskSources mask_sources(const PixFmt& f) {
+    MaskSources m;
+    m.cn = f.kind == PIX_INTERLEAVED ? f.cn : 1;
+    m.sb = f.sample_bytes;
+    m.lo_shift = f.lo16_shift();
+    m.bi = f.fmt == VS_FMT_RGB8 || f.fmt == VS_FMT_RGBA8 ? 2 : 0;
+    return m;
+}
+
 // d_T: scratch of ceil(w/64)*h words.  The closed mask goes to d_out with row pitch opitch words, shifted by
 // oframe rows and words (1 for a BitFrame whose frame is already zero, 0 for a plain bit plane).
-// srcs (optional, d_src == nullptr): `frames` <= SRC_LIST_MAX source pointers on the HOST, one geometry and pitch; the pictures'
-// bit planes / results lie tfb / ofb words apart.
-// sb = 2 (a table of sources, cn 1): luma planes of 16-bit samples, the mask of their high bytes - or, lo_shift > 0 (I010: 2, I012: 4),
-// of min(sample >> lo_shift, 255); stride in bytes, everything even.
-// cn 3 or 4 with bi (0 or 2): interleaved colour pictures with B in byte bi of a pixel (BGR8 / BGRA8: 0, RGB8 / RGBA8: 2).
-int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int cn, u64* d_T, u64* d_out, int opitch,
-                        int oframe, hipStream_t st, const uint8_t* const* srcs = nullptr, int frames = 1, size_t tfb = 0, size_t ofb = 0,
-                        int srcs_aligned = 0, int sb = 1, int lo_shift = 0, int bi = 0) {
-    if ((sb != 1 && sb != 2) || lo_shift < 0 || lo_shift > 8 || (lo_shift && sb != 2) || (sb == 2 && (d_src || cn != 1)) || (!d_src && !srcs) || (!d_src && frames > SRC_LIST_MAX) || !d_T || !d_out || w <= 0 || h <= 0 || (cn != 1 && cn != 3 && cn != 4) || (bi != 0 && (bi != 2 || cn < 3)) || frames < 1) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
+// d_src: the one picture, or nullptr: the table of m.
+int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, u64* d_T, u64* d_out, int opitch, int oframe, hipStream_t st,
+                        const MaskSources& m) {
+    const int cn = m.cn, sb = m.sb, lo_shift = m.lo_shift, bi = m.bi, frames = m.frames;
+    const uint8_t* const* srcs = m.srcs;
+    bool ok = d_T && d_out && w > 0 && h > 0 && frames >= 1;
+    ok = ok && (cn == 1 || cn == 3 || cn == 4) && (sb == 1 || sb == 2);
+    ok = ok && lo_shift >= 0 && lo_shift <= 8 && (!lo_shift || sb == 2);
+    ok = ok && (sb == 1 || (!d_src && cn == 1));                     // 16-bit samples: a table of luma planes
+    ok = ok && (d_src || (srcs && frames <= SRC_LIST_MAX));
+    ok = ok && (bi == 0 || (bi == 2 && cn >= 3));
+    if (!ok) { set_last_error("content_mask: invalid argument"); return VS_ERR_INVALID_ARG; }
     if (h > 65535) { set_last_error("content_mask: image too tall"); return VS_ERR_INVALID_ARG; }
     const int wpr = (w + 63) / 64;
     // (a table of sources: srcs_aligned = every one of them is 4-byte aligned; four-byte pixels: a lane's load is 16 bytes, looked up here)
-    int aligned = !d_src ? (srcs_aligned && (stride & 3) == 0) : ((((uintptr_t)d_src | stride) & 3) == 0);
+    int aligned = !d_src ? (m.aligned && (stride & 3) == 0) : ((((uintptr_t)d_src | stride) & 3) == 0);
     if (cn == 4) {
         aligned = (stride & 15) == 0 && ((uintptr_t)d_src & 15) == 0;
         for (int i = 0; !d_src && aligned && i < frames; i++) aligned = ((uintptr_t)srcs[i] & 15) == 0;
@@ -266,20 +291,20 @@ int launch_content_bits(const uint8_t* d_src, size_t stride, int w, int h, int c
     for (int i = 0; wide && i < frames; i++) wide = ((uintptr_t)srcs[i] & 15) == 0;
     if (sb == 2 && lo_shift) {
         const dim3 g((w + 511) / 512, (h + 3) / 4, frames);
-        if (wide) hipLaunchKernelGGL(threshold_bits_lo16_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb, lo_shift);
-        else hipLaunchKernelGGL(threshold_bits_lo16_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb, lo_shift);
+        if (wide) hipLaunchKernelGGL(threshold_bits_lo16_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, m.tfb, lo_shift);
+        else hipLaunchKernelGGL(threshold_bits_lo16_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, m.tfb, lo_shift);
     } else if (sb == 2) {
         const dim3 g((w + 511) / 512, (h + 3) / 4, frames);
-        if (wide) hipLaunchKernelGGL(threshold_bits_p010_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
-        else hipLaunchKernelGGL(threshold_bits_p010_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
-    } else if (wide) hipLaunchKernelGGL(threshold_bits_gray16_kernel, dim3((w + 1023) / 1024, (h + 3) / 4, frames), dim3(256), 0, st, stride, w, h, d_T, wpr, sl, tfb);
-    else if (cn == 4 && bi) hipLaunchKernelGGL((threshold_bits_kernel<4, 2>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
-    else if (cn == 4) hipLaunchKernelGGL((threshold_bits_kernel<4, 0>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
-    else if (cn == 3 && bi) hipLaunchKernelGGL((threshold_bits_kernel<3, 2>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
-    else if (cn == 3) hipLaunchKernelGGL(threshold_bits_kernel<3>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
-    else hipLaunchKernelGGL(threshold_bits_kernel<1>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, tfb);
+        if (wide) hipLaunchKernelGGL(threshold_bits_p010_kernel<true>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, m.tfb);
+        else hipLaunchKernelGGL(threshold_bits_p010_kernel<false>, g, dim3(256), 0, st, stride, w, h, d_T, wpr, sl, m.tfb);
+    } else if (wide) hipLaunchKernelGGL(threshold_bits_gray16_kernel, dim3((w + 1023) / 1024, (h + 3) / 4, frames), dim3(256), 0, st, stride, w, h, d_T, wpr, sl, m.tfb);
+    else if (cn == 4 && bi) hipLaunchKernelGGL((threshold_bits_kernel<4, 2>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, m.tfb);
+    else if (cn == 4) hipLaunchKernelGGL((threshold_bits_kernel<4, 0>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, m.tfb);
+    else if (cn == 3 && bi) hipLaunchKernelGGL((threshold_bits_kernel<3, 2>), g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, m.tfb);
+    else if (cn == 3) hipLaunchKernelGGL(threshold_bits_kernel<3>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, m.tfb);
+    else hipLaunchKernelGGL(threshold_bits_kernel<1>, g1, dim3(256), 0, st, d_src, stride, w, aligned, d_T, wpr, sl, m.tfb);
     dim3 g2(wpr, (h + MC_ROWS - 1) / MC_ROWS, frames);
-    hipLaunchKernelGGL(close5_bits_kernel, g2, dim3(64), 0, st, d_T, wpr, w, h, d_out, opitch, oframe, tfb, ofb);
+    hipLaunchKernelGGL(close5_bits_kernel, g2, dim3(64), 0, st, d_T, wpr, w, h, d_out, opitch, oframe, m.tfb, m.ofb);
     VS_HIP_TRY(hipGetLastError());
     return VS_OK;
 }
@@ -312,12 +337,8 @@ struct vs_azc {
     // one launch.  NBS batches in flight.
     static constexpr int ZB = 8, NBS = 4, NRES = 1024;      // (ZB <= SRC_LIST_MAX, 3 ZB <= WARP_JOBS_MAX: three planes of a planar surface)
     int nw = 12;                         // worker threads (VS_AZC_WORKERS, 1 .. 16): 31 k frames/s alone with eight, 41 k with twelve
-    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420 ...
-    // VS_FMT_I412) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
     // ow, oh: the output size the frame was handed over under, resolved (never 0)
-    // icn: 0, or the bytes of a pixel of an interleaved colour frame (3 BGR8 / RGB8, 4 BGRA8 / RGBA8: one plane, pitch / opitch its rows;
-    // uv / ouv unused), ibi: the byte of B inside such a pixel (0 or 2)
-    struct Frame { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long ticket; int sb; int planar; I420Layout sl, dl; int ow, oh; int icn, ibi; };
+    struct Frame : StageFrame { long ticket; int ow, oh; };
     struct BatchSlot {
         uint8_t* d_masks = nullptr;      // ZB BitFrames
         uint8_t* h_masks = nullptr;      // page-locked
@@ -375,7 +396,9 @@ int vs_op_content_mask(const void* d_src, size_t stride, int w, int h, int cn, v
         VS_HIP_TRY(hipMalloc((void**)&planes, 2 * words * 8));
         plane_words = words;
     }
-    VS_TRY(launch_content_bits((const uint8_t*)d_src, stride, w, h, cn, planes, planes + plane_words, wpr, 0, st));
+    MaskSources m;
+    m.cn = cn;
+    VS_TRY(launch_content_bits((const uint8_t*)d_src, stride, w, h, planes, planes + plane_words, wpr, 0, st, m));
     dim3 grid((w + 255) / 256, h);
     hipLaunchKernelGGL(expand_bits_kernel, grid, dim3(256), 0, st, planes + plane_words, wpr, w, h, (uint8_t*)d_mask, mask_stride);
     VS_HIP_TRY(hipGetLastError());
@@ -466,7 +489,9 @@ static int azc_plan(vs_azc* a, const void* d_data, int w, int h, size_t stride, 
     }
     BitFrame bf;
     bf.w = w; bf.h = h; bf.pitch = BitFrame::pitch_for(w); bf.F = (const uint64_t*)a->h_mask;
-    VS_OBJ_TRY(a, launch_content_bits((const uint8_t*)d_data, stride, w, h, cn, a->d_tbits, (u64*)a->d_mask, bf.pitch, 1, a->st));   // :111-139
+    MaskSources m;
+    m.cn = cn;
+    VS_OBJ_TRY(a, launch_content_bits((const uint8_t*)d_data, stride, w, h, a->d_tbits, (u64*)a->d_mask, bf.pitch, 1, a->st, m));   // :111-139
     VS_OBJ_HIP(a, hipMemcpyAsync(a->h_mask, a->d_mask, mb, hipMemcpyDeviceToHost, a->st));                 // :142-143
     VS_OBJ_HIP(a, hipStreamSynchronize(a->st));
     crop_from_mask(bf, a->scratch, a->info, nullptr);                                                 // :146-228
@@ -546,11 +571,11 @@ static void azc_publish(vs_azc* a, const vs_azc::Result& res) {
 }
 
 // One frame's host part, on a worker thread: the contour logic on the frame's mask once its batch's masks have arrived, then its
-// crop-and-scale job (or, at once, the copy of the fall-back paths) for both planes on st_out; the worker that finishes a batch's
+// crop-and-scale jobs (or, at once, the copy of the fall-back paths) for every plane on st_out; the worker that finishes a batch's
 // last frame queues the batch's jobs as one launch.  The content mask is taken from the luma plane (gray > 1, :121-127 on a picture
-// that is gray already); the crop rectangle applies to the luma plane as it is and, halved, to the half-size chroma plane;
+// that is gray already); the crop rectangle applies to the luma plane as it is and, shifted, to a subsampled chroma plane;
 // each plane is scaled to its share of the frame's output size by the reference's scale matrix (:261-270, ow x oh for 640 x 360).
-// An interleaved colour frame (icn) is one plane of icn channels: the mask from B, G, R where the format has them (:121-127), one job
+// An interleaved colour frame is one plane of cn channels: the mask from B, G, R where the format has them (:121-127), one job
 // with the rectangle as it is, every channel - the fourth too - scaled as a channel of its own.
 static void azc_worker(vs_azc* a) {
     (void)hipSetDevice(a->device);
@@ -600,8 +625,7 @@ static void azc_worker(vs_azc* a) {
         res.ticket = q.ticket;
         int rc = b.arrived == 3 ? VS_ERR_HIP : VS_OK;
         WarpJob wj[3];
-        const int csx = q.planar ? pixfmt(q.planar)->sx : 1, csy = q.planar ? pixfmt(q.planar)->sy : 1;     // the chroma shifts
-        int nscaled = 0;                 // crop-and-scale jobs of this frame: 2 (NV12 / P010), 3 (planar), 0 on the fall-back paths
+        int nscaled = 0;                 // crop-and-scale jobs of this frame: one per plane, 0 on the fall-back paths
         const clk::time_point t_masks = clk::now();
         clk::time_point t_contour = t_masks;
         t_job = t_job > t_masks ? t_masks : t_job;
@@ -613,45 +637,21 @@ static void azc_worker(vs_azc* a) {
             t_contour = clk::now();
             if (!res.info[7]) {                                                                            // :149-152, :238-249
                 res.out_w = q.w; res.out_h = q.h;
-                if (q.icn) {             // the unchanged frame, all channels
-                    if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w * q.icn, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess) rc = VS_ERR_HIP;
-                } else if (q.planar) {   // the unchanged surface, all three planes: each its own row bytes and rows
-                    const size_t cw = (size_t)(q.w >> csx) * q.sb;
-                    const size_t crows = (size_t)(q.h >> csy);
-                    if (hipMemcpy2DAsync(q.dst, q.dl.pitch, q.src, q.sl.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
-                        hipMemcpy2DAsync(q.dst + q.dl.u, q.dl.cpitch, q.src + q.sl.u, q.sl.cpitch, cw, crows, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
-                        hipMemcpy2DAsync(q.dst + q.dl.v, q.dl.cpitch, q.src + q.sl.v, q.sl.cpitch, cw, crows, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
-                        rc = VS_ERR_HIP;
-                } else if (hipMemcpy2DAsync(q.dst, q.opitch, q.src, q.pitch, (size_t)q.w * q.sb, q.h, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess ||
-                    hipMemcpy2DAsync(q.dst + q.ouv, q.opitch, q.src + q.uv, q.pitch, (size_t)q.w * q.sb, q.h / 2, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess)
-                    rc = VS_ERR_HIP;
+                if (copy_planes(q.dst, q.D, q.src, q.S, hipMemcpyDeviceToDevice, a->st_out) != hipSuccess) rc = VS_ERR_HIP;     // the unchanged surface, every plane
             } else {
                 res.out_w = q.ow; res.out_h = q.oh;
-                const int cx = res.info[2], cy = res.info[3], cw = res.info[4], ch = res.info[5];
-                const int ux = cx >> csx, uy = cy >> csy, uw = std::max(1, cw >> csx), uh = std::max(1, ch >> csy);
-                const float My[6] = {(float)((double)q.ow / cw), 0.f, 0.f, 0.f, (float)((double)q.oh / ch), 0.f};
-                const float Mu[6] = {(float)((double)(q.ow >> csx) / uw), 0.f, 0.f, 0.f, (float)((double)(q.oh >> csy) / uh), 0.f};
-                warp_invert(My, wj[0].m);
-                warp_invert(Mu, wj[1].m);
-                wj[0].src = q.src + (size_t)cy * q.pitch + (size_t)cx * (q.icn ? q.icn : q.sb); wj[0].dst = q.dst;
-                wj[0].sw = cw; wj[0].sh = ch; wj[0].dw = q.ow; wj[0].dh = q.oh; wj[0].cn = q.icn ? q.icn : 1;
-                for (WarpJob& w : wj) { w.sstride = (uint32_t)q.pitch; w.dstride = (uint32_t)q.opitch; w.border = VS_BORDER_BLACK; w.sb = q.sb; }
-                if (q.icn) {
-                    nscaled = 1;
-                } else if (q.planar) {          // U and V: one-channel planes of (w >> sx) x (h >> sy), the shifted rectangle, rows of their own pitch
-                    warp_invert(Mu, wj[2].m);
-                    wj[1].src = q.src + q.sl.u + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[1].dst = q.dst + q.dl.u;
-                    wj[2].src = q.src + q.sl.v + (size_t)uy * q.sl.cpitch + (size_t)ux * q.sb; wj[2].dst = q.dst + q.dl.v;
-                    for (int k = 1; k < 3; k++) {
-                        wj[k].sw = uw; wj[k].sh = uh; wj[k].dw = q.ow >> csx; wj[k].dh = q.oh >> csy; wj[k].cn = 1;
-                        wj[k].sstride = (uint32_t)q.sl.cpitch; wj[k].dstride = (uint32_t)q.dl.cpitch;
-                    }
-                    nscaled = 3;
-                } else {
-                    wj[1].src = q.src + q.uv + (size_t)uy * q.pitch + (size_t)ux * 2 * q.sb; wj[1].dst = q.dst + q.ouv;
-                    wj[1].sw = uw; wj[1].sh = uh; wj[1].dw = q.ow / 2; wj[1].dh = q.oh / 2; wj[1].cn = 2;
-                    nscaled = 2;
+                // plane by plane: the rectangle as the plane sees it (luma and a colour frame: as it is), scaled to the plane's share of the
+                // output size with M = [sx 0 0; 0 sy 0] held as CV_32F (:261-262); every channel a channel of its own
+                for (int k = 0; k < q.S.n; k++) {
+                    const PlaneRect c = plane_crop(q.S[k], res.info[2], res.info[3], res.info[4], res.info[5]), o = plane_result(q.S[k], q.ow, q.oh);
+                    const float M[6] = {(float)((double)o.w / c.w), 0.f, 0.f, 0.f, (float)((double)o.h / c.h), 0.f};
+                    warp_invert(M, wj[k].m);
+                    wj[k].src = q.src + plane_crop_offset(q.S, k, c); wj[k].dst = q.dst + q.D[k].off;
+                    wj[k].sstride = (uint32_t)q.S[k].pitch; wj[k].dstride = (uint32_t)q.D[k].pitch;
+                    wj[k].sw = c.w; wj[k].sh = c.h; wj[k].dw = o.w; wj[k].dh = o.h; wj[k].cn = q.S[k].cn;
+                    wj[k].border = VS_BORDER_BLACK; wj[k].sb = q.S.sample_bytes;
                 }
+                nscaled = q.S.n;
             }
         }
         res.rc = rc;
@@ -669,7 +669,7 @@ static void azc_worker(vs_azc* a) {
         }
         a->cv_done.notify_all();          // (vs_azc_result waits for the host part only)
         // (a batch holds one kind of frame: colour jobs go to the colour instances of the two kernels)
-        int lrc = !(last && njobs) ? VS_OK : q.icn ? launch_scale_jobs_rgb(all, njobs, 0, a->st_out) : launch_scale_jobs(all, njobs, 0, a->st_out);
+        int lrc = !(last && njobs) ? VS_OK : q.pf->kind == PIX_INTERLEAVED ? launch_scale_jobs_rgb(all, njobs, 0, a->st_out) : launch_scale_jobs(all, njobs, 0, a->st_out);
         {
             std::lock_guard<std::mutex> g(a->mu);
             const clk::time_point t_end = clk::now();
@@ -724,9 +724,9 @@ static int azc_issue_batch(vs_azc* a, std::unique_lock<std::mutex>& lk) {
         srcs[i] = a->pending[i].src;
         if ((uintptr_t)a->pending[i].src & 3) aligned = 0;
     }
-    VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].pitch, w, h, a->pending[0].icn ? a->pending[0].icn : 1, b.d_tbits, (u64*)b.d_masks,
-                                 BitFrame::pitch_for(w), 1, b.st, srcs, n, tw, mb / 8, aligned, a->pending[0].sb,
-                                 a->pending[0].planar ? pixfmt(a->pending[0].planar)->lo16_shift() : 0, a->pending[0].ibi));      // :111-139 on the luma planes / the colour frames
+    MaskSources m = mask_sources(*a->pending[0].pf);
+    m.srcs = srcs; m.frames = n; m.aligned = aligned; m.tfb = tw; m.ofb = mb / 8;
+    VS_OBJ_TRY(a, launch_content_bits(nullptr, a->pending[0].S[0].pitch, w, h, b.d_tbits, (u64*)b.d_masks, BitFrame::pitch_for(w), 1, b.st, m));   // :111-139 on the luma planes / the colour frames
     VS_OBJ_HIP(a, hipMemcpyAsync(b.h_masks, b.d_masks, mb * n, hipMemcpyDeviceToHost, b.st));                                          // :142-143
     VS_OBJ_HIP(a, hipEventRecord(b.ev, b.st));
     b.t_issue = std::chrono::steady_clock::now();
@@ -764,21 +764,10 @@ static int azc_flush_pending(vs_azc* a, std::unique_lock<std::mutex>& lk) {
 // ticket; eight consecutive frames of one geometry form a batch (vs_azc_sync and vs_azc_result close an incomplete one).
 // vs_azc_result(ticket) tells what came out (it waits for that frame's host part), the pixels are complete after vs_azc_sync.
 // Surface and result buffer must stay untouched until then; results of the last 1024 tickets are kept.
-// (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
-// (planar: 0, or the format of a three-plane surface whose layouts are sl / dl, checked by the caller - uv_offset / out_uv_offset repeat
-// their U offsets)
-// (icn, ibi: an interleaved colour frame, vs_azc::Frame - its caller has checked geometry and strides; there is no second plane)
-static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                         size_t out_uv_offset, int64_t* ticket, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout(),
-                         int icn = 0, int ibi = 0) {
-    if (!a || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
-    if (!icn && (w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb)) return VS_ERR_INVALID_ARG;
-    const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h;
-    if (!icn && (out_pitch < (size_t)std::max(w, ow) * sb || out_uv_offset < (size_t)std::max(h, oh) * out_pitch)) return VS_ERR_INVALID_ARG;
-    if (sb == 2 && !planar && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
-        return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: P010 pointers, pitches and plane offsets must be even");
-    if (w > 65535 || h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
-    if (uv_offset == 0) uv_offset = (size_t)h * pitch;
+// (fr: checked by its entry point, ow / oh still to be set)
+static int azc_hand_over(vs_azc* a, vs_azc::Frame fr, int64_t* ticket) {
+    if (fr.w > 65535 || fr.h > 32767) return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: image too large");
+    fr.ow = a->ow ? a->ow : fr.w; fr.oh = a->oh ? a->oh : fr.h;
     VS_OBJ_HIP(a, hipSetDevice(a->device));
     if (a->workers.empty()) {
         VS_OBJ_HIP(a, hipStreamCreateWithFlags(&a->st_out, hipStreamNonBlocking));
@@ -790,27 +779,57 @@ static int azc_hand_over(vs_azc* a, const void* d_surface, int w, int h, size_t 
         }
     }
     std::unique_lock<std::mutex> lk(a->mu);
-    // (a change of geometry, of sample size, of format or of a planar surface's layouts closes the pending batch: a batch's launches
-    // take one of each; a change of the output size has closed it already, vs_azc_set_output_size)
+    // (a change of format, of geometry or of either layout closes the pending batch: a batch's launches take one of each; a change of
+    // the output size has closed it already, vs_azc_set_output_size)
     if (!a->pending.empty()) {
         const vs_azc::Frame& p0 = a->pending[0];
-        auto same = [](const I420Layout& x, const I420Layout& y) { return x.pitch == y.pitch && x.cpitch == y.cpitch && x.u == y.u && x.v == y.v; };
-        if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar || p0.icn != icn || p0.ibi != ibi ||
-            (planar && (!same(p0.sl, sl) || !same(p0.dl, dl)))) {
+        if (p0.pf != fr.pf || p0.w != fr.w || p0.h != fr.h || !same_layout(p0.S, fr.S) || !same_layout(p0.D, fr.D)) {
             const int rc = azc_flush_pending(a, lk);
             if (rc != VS_OK) return rc;
         }
     }
-    a->pending.push_back(vs_azc::Frame{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, a->issued, sb, planar, sl, dl, ow, oh, icn, ibi});
+    fr.ticket = a->issued;
+    a->pending.push_back(fr);
     if (ticket) *ticket = a->issued;
     a->issued++;
     if ((int)a->pending.size() >= vs_azc::ZB) return azc_flush_pending(a, lk);
     return VS_OK;
 }
 
+// The frame record of an entry point: the result's planes are laid out for the larger of the frame and the output size
+static vs_azc::Frame azc_frame(const PixFmt& f, int w, int h, const void* d_src, void* d_dst, const Planes& S, const Planes& D) {
+    return vs_azc::Frame{StageFrame{&f, w, h, (const uint8_t*)d_src, (uint8_t*)d_dst, S, D}, 0, 0, 0};
+}
+static int azc_max_w(const vs_azc* a, int w) { return std::max(w, a->ow); }       // (an output size of 0: the frame's own)
+static int azc_max_h(const vs_azc* a, int h) { return std::max(h, a->oh); }
+
+// NV12 and P010: luma and the interleaved chroma plane; uv_offset 0 = behind the h luma rows, out_uv_offset has no default
+static int azc_luma_uv(vs_azc* a, int fmt, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                       size_t out_uv_offset, int64_t* ticket) {
+    const PixFmt& f = *pixfmt(fmt);
+    const size_t sb = (size_t)f.sample_bytes;
+    if (!a || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
+    if (w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb) return VS_ERR_INVALID_ARG;
+    const int mw = azc_max_w(a, w), mh = azc_max_h(a, h);
+    if (out_pitch < (size_t)mw * sb || out_uv_offset < (size_t)mh * out_pitch) return VS_ERR_INVALID_ARG;
+    if (sb == 2 && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
+        return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: P010 pointers, pitches and plane offsets must be even");
+    return azc_hand_over(a, azc_frame(f, w, h, d_surface, d_out, planes(f, w, h, pitch, ChromaLayout{uv_offset}),
+                                      planes(f, mw, mh, out_pitch, ChromaLayout{out_uv_offset})), ticket);
+}
+
 int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
                           size_t out_uv_offset, int64_t* ticket) {
-    return azc_hand_over(a, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, ticket, 1);
+    return azc_luma_uv(a, VS_FMT_NV12, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, ticket);
+}
+
+// n surfaces of one layout in call order; tickets (optional) receives n tickets
+int vs_azc_apply_nv12_dev_n(vs_azc* a, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
+                            size_t out_pitch, size_t out_uv_offset, int64_t* tickets) {
+    if (!a || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
+    return each_surface(n, [&](int i) {
+        return vs_azc_apply_nv12_dev(a, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset, tickets ? tickets + i : nullptr);
+    });
 }
 
 // The same for a P010 surface (vs_pixfmt16; pitches and offsets in bytes, everything even: out_pitch >= 2 * max(w, ow)).  The content
@@ -820,17 +839,15 @@ int vs_azc_apply_nv12_dev(vs_azc* a, const void* d_surface, int w, int h, size_t
 // object: a change of sample size closes the pending batch as a change of geometry does.
 int vs_azc_apply_p010_dev(vs_azc* a, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
                           size_t out_uv_offset, int64_t* ticket) {
-    return azc_hand_over(a, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, ticket, 2);
+    return azc_luma_uv(a, VS_FMT_P010, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, ticket);
 }
 
 int vs_azc_apply_p010_dev_n(vs_azc* a, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
                             size_t out_pitch, size_t out_uv_offset, int64_t* tickets) {
     if (!a || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++) {
-        const int rc = vs_azc_apply_p010_dev(a, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset, tickets ? tickets + i : nullptr);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
+    return each_surface(n, [&](int i) {
+        return vs_azc_apply_p010_dev(a, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset, tickets ? tickets + i : nullptr);
+    });
 }
 
 // The same for a three-plane surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010, VS_FMT_I012, or a 4:2:2 / 4:4:4
@@ -849,33 +866,18 @@ int vs_azc_apply_i420_dev(vs_azc* a, int fmt, const void* d_surface, int w, int 
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, "auto zoom/crop: the planar entry point takes a three-plane format (VS_FMT_I420, I010, I012, I422, I444, I210, I212, I410, I412)");
     I420Layout sl, dl;
     std::string msg;
-    const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h;
+    const int ow = a->ow ? a->ow : w, oh = a->oh ? a->oh : h, mw = azc_max_w(a, w), mh = azc_max_h(a, h);
     const std::string what = "auto zoom/crop (result: max(w, " + std::to_string(ow) + ") x max(h, " + std::to_string(oh) + "))";
     if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "auto zoom/crop", &sl, &msg) != VS_OK ||
-        planar_layout_check(fmt, d_out, w, h, out, std::max(w, ow), std::max(h, oh), what.c_str(), &dl, &msg) != VS_OK)
+        planar_layout_check(fmt, d_out, w, h, out, mw, mh, what.c_str(), &dl, &msg) != VS_OK)
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, msg.c_str());
-    return azc_hand_over(a, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, ticket, f->sample_bytes, fmt, sl, dl);
+    return azc_hand_over(a, azc_frame(*f, w, h, d_surface, d_out, planes(*f, w, h, sl), planes(*f, mw, mh, dl)), ticket);
 }
 
 int vs_azc_apply_i420_dev_n(vs_azc* a, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, const vs_i420_layout* in,
                             const vs_i420_layout* out, int64_t* tickets) {
     if (!a || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++) {
-        const int rc = vs_azc_apply_i420_dev(a, fmt, d_surfaces[i], w, h, in, d_outs[i], out, tickets ? tickets + i : nullptr);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
-}
-
-// n surfaces of one layout in call order; tickets (optional) receives n tickets
-int vs_azc_apply_nv12_dev_n(vs_azc* a, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
-                            size_t out_pitch, size_t out_uv_offset, int64_t* tickets) {
-    if (!a || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++) {
-        const int rc = vs_azc_apply_nv12_dev(a, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset, tickets ? tickets + i : nullptr);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
+    return each_surface(n, [&](int i) { return vs_azc_apply_i420_dev(a, fmt, d_surfaces[i], w, h, in, d_outs[i], out, tickets ? tickets + i : nullptr); });
 }
 
 // The same for an interleaved colour frame in HBM: fmt VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8 or VS_FMT_RGBA8, one plane of w x h pixels
@@ -886,7 +888,6 @@ int vs_azc_apply_nv12_dev_n(vs_azc* a, const void* const* d_surfaces, void* cons
 // that of vs_azc_apply_dev on the same frame.  Colour frames, NV12, P010 and planar surfaces may alternate on one object.
 // Refused before any device call, with a text in vs_azc_last_error that names the call and the formats: another fmt, stride < w * cn,
 // out_stride too small, null pointers, w or h < 1, n < 1.
-static const char RGB_FORMATS[] = "VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8, VS_FMT_RGBA8";
 static int azc_rgb_hand_over(vs_azc* a, const char* call, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride,
                              int64_t* ticket) {
     const PixFmt* f = pixfmt(fmt);
@@ -898,8 +899,7 @@ static int azc_rgb_hand_over(vs_azc* a, const char* call, int fmt, const void* d
     if (stride < (size_t)w * f->cn || out_stride < (size_t)std::max(w, ow) * f->cn)
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, head + "stride below w * cn, or out_stride below max(w, " + std::to_string(ow) + ") * cn");
     if (stride > UINT32_MAX || out_stride > UINT32_MAX) return vs_obj_fail(a, VS_ERR_INVALID_ARG, head + "strides must be below 4 GiB");
-    return azc_hand_over(a, d_frame, w, h, stride, 0, d_out, out_stride, 0, ticket, 1, 0, I420Layout(), I420Layout(), f->cn,
-                         fmt == VS_FMT_RGB8 || fmt == VS_FMT_RGBA8 ? 2 : 0);
+    return azc_hand_over(a, azc_frame(*f, w, h, d_frame, d_out, planes(*f, w, h, stride), planes(*f, azc_max_w(a, w), azc_max_h(a, h), out_stride)), ticket);
 }
 
 int vs_azc_apply_rgb_dev(vs_azc* a, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride, int64_t* ticket) {
@@ -912,11 +912,9 @@ int vs_azc_apply_rgb_dev_n(vs_azc* a, int fmt, const void* const* d_frames, void
     if (!a) return VS_ERR_INVALID_ARG;
     if (!d_frames || !d_outs || n < 1)
         return vs_obj_fail(a, VS_ERR_INVALID_ARG, std::string("vs_azc_apply_rgb_dev_n (fmt: one of ") + RGB_FORMATS + "): null pointer lists, or n < 1");
-    for (int i = 0; i < n; i++) {
-        const int rc = azc_rgb_hand_over(a, "vs_azc_apply_rgb_dev_n", fmt, d_frames[i], w, h, stride, d_outs[i], out_stride, tickets ? tickets + i : nullptr);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
+    return each_surface(n, [&](int i) {
+        return azc_rgb_hand_over(a, "vs_azc_apply_rgb_dev_n", fmt, d_frames[i], w, h, stride, d_outs[i], out_stride, tickets ? tickets + i : nullptr);
+    });
 }
 
 // Diagnostics of the asynchronous path: frames through the workers so far and the seconds the workers spent, summed over the

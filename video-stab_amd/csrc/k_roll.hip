@@ -777,11 +777,7 @@ struct vs_roll {
     int nwk = 5;                         // worker threads in use (VS_ROLL_WORKERS, 1 .. NWK): alone three are as fast as eight (36 - 38 k
                                          // frames/s); beside a stabilizer on the same GPU a batch's launches wait behind its workgroups, and five
                                          // batches in flight keep the stage at 3.4 ms per 128 surfaces where three need 5.5 (gpurun_out/r04_ai)
-    // sb: bytes of a sample (1 NV12 / I420, 2 P010 / I010 / I012).  planar: 0, or the format of a three-plane surface (VS_FMT_I420 ...
-    // VS_FMT_I412) whose planes lie where sl / dl say (pitch / opitch repeat their luma pitches; uv / ouv are unused)
-    // icn: 0, or the bytes of a pixel of an interleaved colour frame of format ifmt (VS_FMT_BGR8, RGB8: 3; BGRA8, RGBA8: 4) - one plane,
-    // pitch / opitch its rows; uv / ouv are unused
-    struct Job { const uint8_t* src; uint8_t* dst; int w, h; size_t pitch, uv, opitch, ouv; long seq; int sb; int planar; I420Layout sl, dl; int icn, ifmt; };
+    struct Job : StageFrame { long seq; };
     struct Slot {
         RollWork wk;                     // RB frames
         hipStream_t st = nullptr;
@@ -1011,6 +1007,10 @@ int vs_roll_correct_dev(vs_roll* r, const void* d_data, int w, int h, size_t str
     return vs_op_warp_affine_ex(d_data, stride, w, h, d_out, out_stride, w, h, 3, M, VS_BORDER_REPLICATE, r->st);   // :146-149
 }
 
+// The coordinate tables of a rotation launch: the scratch tables for the batch in one launch; a single surface as the stage has
+// always asked - the scratch tables for three planes, none for NV12 / P010 and colour frames
+static WarpTabs roll_tabs(const Planes& S, bool one_launch) { return one_launch || S.n == 3 ? WarpTabs{WarpTabs::SCRATCH} : WarpTabs{}; }
+
 // One batch of the asynchronous NV12 path: the line searches of its frames as one launch per stage, then - in frame order - the
 // angle recurrence and the rotations.  Returns with r->mu held by `lk` when the ordered part was reached.
 static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_roll::Job>& jobs, std::unique_lock<std::mutex>& lk) {
@@ -1036,8 +1036,7 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
     // the three-plane 16-bit formats: that of min(sample >> (bits - 8), 255), the low-bits kernels; the Y plane of an 8-bit three-plane
     // surface is a gray picture - the chroma subsampling does not enter; an interleaved colour frame: resize + BGR2GRAY on B, G, R where
     // its format has them, :41,:51 - the fourth channel does not enter)
-    const int gfmt = j0.icn ? j0.ifmt : j0.planar && j0.sb == 2 ? j0.planar : j0.sb == 2 ? (int)VS_FMT_P010 : (int)VS_FMT_GRAY8;
-    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.pitch, j0.w, j0.h, gfmt, sw, sw, sh, j0.icn ? src8 : 0, q.st));   // :41
+    VS_TRY(launch_resize_gray_batch(q.d_pairs, n, j0.S[0].pitch, j0.w, j0.h, j0.pf->gray_source, sw, sw, sh, j0.pf->kind == PIX_INTERLEAVED ? src8 : 0, q.st));   // :41
     // (twelve hysteresis passes per batch - a pass whose predecessor changed nothing for its frame returns at once: with four, 40 % of
     // the bench clip's frames had to finish their growth one by one behind the batch, 30 us per frame)
     constexpr int PASSES = 12;
@@ -1074,68 +1073,36 @@ static int roll_worker_batch(vs_roll* r, vs_roll::Slot& q, const std::vector<vs_
     lk.lock();
     r->cv_done.wait(lk, [&] { return r->nv_done == j0.seq; });
     double Minv[vs_roll::RB * 12];       // per frame: luma map, chroma map
-    const uint8_t *ys[vs_roll::RB], *us[vs_roll::RB];
-    uint8_t *yd[vs_roll::RB], *ud[vs_roll::RB];
+    const uint8_t* srcs[vs_roll::RB];
+    uint8_t* dsts[vs_roll::RB];
     bool one_launch = true;
+    // the chroma planes (a batch holds one format): the interleaved UV plane of NV12 / P010 is the half-size picture, the same rotation
+    // with the translation halved; in general Mc = S^-1 M S, S = diag(2^sx, 2^sy) - exact products by powers of two; (1, 1) is the
+    // halved translation, (1, 0) shears (4:2:2), (0, 0) is M itself (4:4:4)
+    const double kx = j0.S[1].sx ? 0.5 : 1.0, ky = j0.S[1].sy ? 0.5 : 1.0;          // 2^-sx, 2^-sy
     for (int f = 0; f < n; f++) {
         const vs_roll::Job& j = jobs[f];
         if (slow[f]) r->slow_frames++;
         roll_update(r, res[f]);
-        // cv::getRotationMatrix2D(center, angle, 1.0) (:141-144); the interleaved chroma plane is the half-size picture: the same
-        // rotation with the translation halved.  A three-plane surface's chroma planes take Mc = S^-1 M S, S = diag(2^sx, 2^sy) - exact
-        // products by powers of two; (1, 1) is the halved translation, (1, 0) shears (4:2:2), (0, 0) is M itself (4:4:4)
+        // cv::getRotationMatrix2D(center, angle, 1.0) (:141-144)
         const float cx = j.w / 2.0f, cy = j.h / 2.0f;
         const double a = r->smoothed * 3.1415926535897932384626433832795 / 180;
         const double alpha = std::cos(a), beta = std::sin(a);
         const double M[6] = {alpha, beta, (1 - alpha) * cx - beta * cy, -beta, alpha, beta * cx + (1 - alpha) * cy};
-        const int csx = j.planar ? pixfmt(j.planar)->sx : 1, csy = j.planar ? pixfmt(j.planar)->sy : 1;
-        const double kx = csx ? 0.5 : 1.0, ky = csy ? 0.5 : 1.0;          // 2^-sx, 2^-sy
         const double Mc[6] = {M[0], M[1] * (kx / ky), M[2] * kx, M[3] * (ky / kx), M[4], M[5] * ky};
         warp_invert(M, Minv + 12 * f);
         warp_invert(Mc, Minv + 12 * f + 6);
-        ys[f] = j.src; us[f] = j.src + j.uv; yd[f] = j.dst; ud[f] = j.dst + j.ouv;
-        one_launch &= j.opitch == j0.opitch && j.uv == j0.uv && j.ouv == j0.ouv;
-        if (j0.planar) one_launch &= j.dl.cpitch == j0.dl.cpitch && j.dl.u == j0.dl.u && j.dl.v == j0.dl.v;
+        srcs[f] = j.src; dsts[f] = j.dst;
+        one_launch &= same_layout(j.D, j0.D);
     }
-    // an interleaved colour frame is one plane of icn channels under M, every channel a channel of its own: the batch's rotations in ONE
-    // launch from the scratch tables when the results share a stride, else frame by frame
-    if (j0.icn) {
-        if (one_launch)
-            return launch_warp_plane(ys, yd, n, j0.pitch, j0.w, j0.h, j0.opitch, j0.w, j0.h, j0.icn, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE,
-                                     WarpTabs{WarpTabs::SCRATCH}, r->st);
-        for (int f = 0; f < n; f++) {
-            const vs_roll::Job& j = jobs[f];
-            VS_TRY(launch_warp_plane(ys + f, yd + f, 1, j.pitch, j.w, j.h, j.opitch, j.w, j.h, j.icn, WarpMaps{Minv + 12 * f, 12, true}, VS_BORDER_REPLICATE,
-                                     WarpTabs{}, r->st));
-        }
-        return VS_OK;
-    }
-    // three planes (a batch holds one format and one source layout): Y, U and V tiles of all its surfaces in ONE grid (warp_i420_kernel
-    // with the BORDER_REPLICATE staging, 8- or 16-bit samples, the instance of the format's chroma shifts) when the results share one
-    // layout, else frame by frame; U and V both take the chroma map
-    if (j0.planar) {
-        const int sx = pixfmt(j0.planar)->sx, sy = pixfmt(j0.planar)->sy;
-        if (one_launch)
-            return launch_warp_i420(ys, yd, n, j0.sl, j0.dl, j0.w, j0.h, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE, WarpTabs{WarpTabs::SCRATCH},
-                                    r->st, j0.sb, sx, sy);
-        for (int f = 0; f < n; f++) {
-            const vs_roll::Job& j = jobs[f];
-            VS_TRY(launch_warp_i420(ys + f, yd + f, 1, j.sl, j.dl, j.w, j.h, WarpMaps{Minv + 12 * f, 12, true}, VS_BORDER_REPLICATE,
-                                    WarpTabs{WarpTabs::SCRATCH}, r->st, j.sb, sx, sy));
-        }
-        return VS_OK;
-    }
-    // the rotations of the batch (:146-149): luma and chroma tiles of all its surfaces in ONE grid (warp_nv12_kernel with the
-    // BORDER_REPLICATE staging; P010: its instance for 16-bit samples) when the results share one layout (the surfaces do), else
-    // frame by frame
+    // the rotations of the batch (:146-149), BORDER_REPLICATE; an interleaved colour frame is one plane under M, every channel a channel
+    // of its own.  A batch holds one format and one source layout: the planes of all its surfaces in ONE grid when the results share
+    // one layout (the surfaces do), else frame by frame
     if (one_launch)
-        return launch_warp_nv12(ys, yd, us, ud, n, j0.pitch, j0.opitch, j0.w, j0.h, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE,
-                                WarpTabs{WarpTabs::SCRATCH}, r->st, j0.sb);
-    for (int f = 0; f < n; f++) {
-        const vs_roll::Job& j = jobs[f];
-        VS_TRY(launch_warp_nv12(ys + f, yd + f, us + f, ud + f, 1, j.pitch, j.opitch, j.w, j.h, WarpMaps{Minv + 12 * f, 12, true},
-                                VS_BORDER_REPLICATE, WarpTabs{}, r->st, j.sb));
-    }
+        return warp_planes(srcs, dsts, n, j0.S, j0.D, WarpMaps{Minv, 12, true}, VS_BORDER_REPLICATE, WarpFill(), roll_tabs(j0.S, true), r->st);
+    for (int f = 0; f < n; f++)
+        VS_TRY(warp_planes(srcs + f, dsts + f, 1, jobs[f].S, jobs[f].D, WarpMaps{Minv + 12 * f, 12, true}, VS_BORDER_REPLICATE, WarpFill(),
+                           roll_tabs(jobs[f].S, false), r->st));
     return VS_OK;
 }
 
@@ -1178,18 +1145,7 @@ static void roll_flush_pending(vs_roll* r) {
 // consecutive frames of one geometry form a batch that a worker thread analyses with one launch per stage.  Results are complete
 // after vs_roll_sync (which also closes an incomplete batch).  The surface and the result buffer of a call must stay untouched
 // until then.
-// (sb: the bytes of a sample - what the NV12 and the P010 entry point share)
-// (planar: 0, or the format of a three-plane surface whose layouts are sl / dl - uv_offset / out_uv_offset are then unused)
-// (icn, ifmt: an interleaved colour frame, vs_roll::Job - its caller has checked geometry and strides; there is no second plane)
-static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
-                          size_t out_uv_offset, int sb, int planar = 0, I420Layout sl = I420Layout(), I420Layout dl = I420Layout(), int icn = 0,
-                          int ifmt = 0) {
-    if (!r || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
-    if (!icn && (w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < (size_t)w * sb || out_pitch < (size_t)w * sb)) return VS_ERR_INVALID_ARG;
-    if (sb == 2 && !planar && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
-        return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: P010 pointers, pitches and plane offsets must be even");
-    if (uv_offset == 0) uv_offset = (size_t)h * pitch;
-    if (out_uv_offset == 0) out_uv_offset = (size_t)h * out_pitch;
+static int roll_hand_over(vs_roll* r, const StageFrame& fr) {
     VS_OBJ_HIP(r, hipSetDevice(r->device));
     if (r->workers.empty()) {
         try {
@@ -1203,15 +1159,12 @@ static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_
         std::unique_lock<std::mutex> lk(r->mu);
         if (r->first) { r->first = false; r->smoothed = 0.0; }                                   // :24-27
         r->cv_done.wait(lk, [&] { return r->nv_in - r->nv_done < vs_roll::QMAX; });
-        // (a change of geometry, of sample size, of format or of a planar surface's source layout closes the pending batch: a batch's
-        // launches take one of each)
+        // (a change of format, of geometry or of the source layout closes the pending batch: a batch's launches take one of each)
         if (!r->pending.empty()) {
             const vs_roll::Job& p0 = r->pending[0];
-            if (p0.w != w || p0.h != h || p0.pitch != pitch || p0.sb != sb || p0.planar != planar || p0.icn != icn || p0.ifmt != ifmt ||
-                (planar && (p0.sl.cpitch != sl.cpitch || p0.sl.u != sl.u || p0.sl.v != sl.v)))
-                roll_flush_pending(r);
+            if (p0.pf != fr.pf || p0.w != fr.w || p0.h != fr.h || !same_layout(p0.S, fr.S)) roll_flush_pending(r);
         }
-        r->pending.push_back(vs_roll::Job{(const uint8_t*)d_surface, (uint8_t*)d_out, w, h, pitch, uv_offset, out_pitch, out_uv_offset, r->nv_in, sb, planar, sl, dl, icn, ifmt});
+        r->pending.push_back(vs_roll::Job{fr, r->nv_in});
         r->nv_in++;
         if ((int)r->pending.size() >= vs_roll::RB) roll_flush_pending(r);
     }
@@ -1219,9 +1172,29 @@ static int roll_hand_over(vs_roll* r, const void* d_surface, int w, int h, size_
     return VS_OK;
 }
 
+// NV12 and P010: luma and the interleaved chroma plane, uv_offset / out_uv_offset 0 = behind the h luma rows
+static int roll_luma_uv(vs_roll* r, int fmt, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
+                        size_t out_uv_offset) {
+    const PixFmt& f = *pixfmt(fmt);
+    const size_t row = (size_t)w * f.sample_bytes;
+    if (!r || !d_surface || !d_out) return VS_ERR_INVALID_ARG;
+    if (w < 2 || h < 2 || (w & 1) || (h & 1) || pitch < row || out_pitch < row) return VS_ERR_INVALID_ARG;
+    if (f.sample_bytes == 2 && (((uintptr_t)d_surface | (uintptr_t)d_out | pitch | uv_offset | out_pitch | out_uv_offset) & 1))
+        return vs_obj_fail(r, VS_ERR_INVALID_ARG, "roll: P010 pointers, pitches and plane offsets must be even");
+    return roll_hand_over(r, StageFrame{&f, w, h, (const uint8_t*)d_surface, (uint8_t*)d_out, planes(f, w, h, pitch, ChromaLayout{uv_offset}),
+                                        planes(f, w, h, out_pitch, ChromaLayout{out_uv_offset})});
+}
+
 int vs_roll_correct_nv12_dev(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
                              size_t out_uv_offset) {
-    return roll_hand_over(r, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, 1);
+    return roll_luma_uv(r, VS_FMT_NV12, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset);
+}
+
+// n surfaces of one layout in call order (what n calls of vs_roll_correct_nv12_dev do, without n trips through a binding)
+int vs_roll_correct_nv12_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
+                               size_t out_pitch, size_t out_uv_offset) {
+    if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
+    return each_surface(n, [&](int i) { return vs_roll_correct_nv12_dev(r, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset); });
 }
 
 // The same for a P010 surface (vs_pixfmt16; pitches and offsets in bytes, everything even): the line search runs on the 8-bit plane
@@ -1230,17 +1203,13 @@ int vs_roll_correct_nv12_dev(vs_roll* r, const void* d_surface, int w, int h, si
 // object: a change of sample size closes the pending batch as a change of geometry does, the smoothed angle carries across.
 int vs_roll_correct_p010_dev(vs_roll* r, const void* d_surface, int w, int h, size_t pitch, size_t uv_offset, void* d_out, size_t out_pitch,
                              size_t out_uv_offset) {
-    return roll_hand_over(r, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset, 2);
+    return roll_luma_uv(r, VS_FMT_P010, d_surface, w, h, pitch, uv_offset, d_out, out_pitch, out_uv_offset);
 }
 
 int vs_roll_correct_p010_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
                                size_t out_pitch, size_t out_uv_offset) {
     if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++) {
-        const int rc = vs_roll_correct_p010_dev(r, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
+    return each_surface(n, [&](int i) { return vs_roll_correct_p010_dev(r, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset); });
 }
 
 // The same for a three-plane surface: fmt VS_FMT_I420 (YV12: the two chroma offsets swapped), VS_FMT_I010, VS_FMT_I012, or a 4:2:2 / 4:4:4
@@ -1259,17 +1228,13 @@ int vs_roll_correct_i420_dev(vs_roll* r, int fmt, const void* d_surface, int w, 
     std::string msg;
     if (planar_layout_check(fmt, d_surface, w, h, in, w, h, "roll", &sl, &msg) != VS_OK || planar_layout_check(fmt, d_out, w, h, out, w, h, "roll (result)", &dl, &msg) != VS_OK)
         return vs_obj_fail(r, VS_ERR_INVALID_ARG, msg.c_str());
-    return roll_hand_over(r, d_surface, w, h, sl.pitch, sl.u, d_out, dl.pitch, dl.u, f->sample_bytes, fmt, sl, dl);
+    return roll_hand_over(r, StageFrame{f, w, h, (const uint8_t*)d_surface, (uint8_t*)d_out, planes(*f, w, h, sl), planes(*f, w, h, dl)});
 }
 
 int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, const vs_i420_layout* in,
                                const vs_i420_layout* out) {
     if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++) {
-        const int rc = vs_roll_correct_i420_dev(r, fmt, d_surfaces[i], w, h, in, d_outs[i], out);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
+    return each_surface(n, [&](int i) { return vs_roll_correct_i420_dev(r, fmt, d_surfaces[i], w, h, in, d_outs[i], out); });
 }
 
 // The same for an interleaved colour frame: fmt VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8 or VS_FMT_RGBA8, one plane of w x h pixels (any
@@ -1280,7 +1245,6 @@ int vs_roll_correct_i420_dev_n(vs_roll* r, int fmt, const void* const* d_surface
 // of format closes the pending batch, the smoothed angle carries across.
 // Refused before any device call, with a text in vs_roll_last_error that names the call and the formats: another fmt, a stride below
 // w * cn, null pointers, w or h < 1, n < 1.
-static const char RGB_FORMATS[] = "VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8, VS_FMT_RGBA8";
 static int roll_rgb_hand_over(vs_roll* r, const char* call, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride) {
     const PixFmt* f = pixfmt(fmt);
     const std::string head = std::string(call) + " (fmt: one of " + RGB_FORMATS + "): ";
@@ -1288,7 +1252,7 @@ static int roll_rgb_hand_over(vs_roll* r, const char* call, int fmt, const void*
     if (!d_frame || !d_out) return vs_obj_fail(r, VS_ERR_INVALID_ARG, head + "null frame or result pointer");
     if (w < 1 || h < 1) return vs_obj_fail(r, VS_ERR_INVALID_ARG, head + "w and h must be at least 1");
     if (stride < (size_t)w * f->cn || out_stride < (size_t)w * f->cn) return vs_obj_fail(r, VS_ERR_INVALID_ARG, head + "stride or out_stride below w * cn");
-    return roll_hand_over(r, d_frame, w, h, stride, 0, d_out, out_stride, 0, 1, 0, I420Layout(), I420Layout(), f->cn, fmt);
+    return roll_hand_over(r, StageFrame{f, w, h, (const uint8_t*)d_frame, (uint8_t*)d_out, planes(*f, w, h, stride), planes(*f, w, h, out_stride)});
 }
 
 int vs_roll_correct_rgb_dev(vs_roll* r, int fmt, const void* d_frame, int w, int h, size_t stride, void* d_out, size_t out_stride) {
@@ -1300,22 +1264,7 @@ int vs_roll_correct_rgb_dev_n(vs_roll* r, int fmt, const void* const* d_frames, 
     if (!r) return VS_ERR_INVALID_ARG;
     if (!d_frames || !d_outs || n < 1)
         return vs_obj_fail(r, VS_ERR_INVALID_ARG, std::string("vs_roll_correct_rgb_dev_n (fmt: one of ") + RGB_FORMATS + "): null pointer lists, or n < 1");
-    for (int i = 0; i < n; i++) {
-        const int rc = roll_rgb_hand_over(r, "vs_roll_correct_rgb_dev_n", fmt, d_frames[i], w, h, stride, d_outs[i], out_stride);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
-}
-
-// n surfaces of one layout in call order (what n calls of vs_roll_correct_nv12_dev do, without n trips through a binding)
-int vs_roll_correct_nv12_dev_n(vs_roll* r, const void* const* d_surfaces, void* const* d_outs, int n, int w, int h, size_t pitch, size_t uv_offset,
-                               size_t out_pitch, size_t out_uv_offset) {
-    if (!r || !d_surfaces || !d_outs || n < 0) return VS_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++) {
-        const int rc = vs_roll_correct_nv12_dev(r, d_surfaces[i], w, h, pitch, uv_offset, d_outs[i], out_pitch, out_uv_offset);
-        if (rc != VS_OK) return rc;
-    }
-    return VS_OK;
+    return each_surface(n, [&](int i) { return roll_rgb_hand_over(r, "vs_roll_correct_rgb_dev_n", fmt, d_frames[i], w, h, stride, d_outs[i], out_stride); });
 }
 
 int vs_roll_sync(vs_roll* r) {

@@ -62,7 +62,42 @@ int launch_gftt_batch(const void* d_table, int items, int w, int h, int block_si
 int launch_warp_i420(const uint8_t* const* ys, uint8_t* const* yd, int n, I420Layout src, I420Layout dst, int w, int h, WarpMaps maps, int border,
                      WarpTabs tabs, hipStream_t st, int sample_bytes = 1, int sx = 1, int sy = 1, WarpFill fill = WarpFill());
 
-// ---- k_roll.hip, k_azc.hip: the geometry and layout rules of their three-plane surfaces are planar_layout_check (planar_layout.h)
+// ---- the plane list (planar_layout.h) on the device: what the stream, the batch schedule and the roll / zoom stages share
+// The warp of n <= WARP_BATCH_MAX surfaces (planes S, at the size of S's luma) into surfaces with planes D, one launch: the one
+// plane of an interleaved format; luma and the interleaved chroma plane - half size, two channels, the map with the halved
+// translation (m + 6) -; or Y, U and V, whose one chroma table serves both U and V.
+inline int warp_planes(const uint8_t* const* srcs, uint8_t* const* dsts, int n, const Planes& S, const Planes& D, WarpMaps maps, int border, WarpFill fill,
+                       WarpTabs tabs, hipStream_t st) {
+    if (S.n == 1) return launch_warp_plane(srcs, dsts, n, S[0].pitch, S[0].w, S[0].h, D[0].pitch, S[0].w, S[0].h, S[0].cn, maps, border, tabs, st, S.sample_bytes);
+    if (S.n == 3)
+        return launch_warp_i420(srcs, dsts, n, S.i420(), D.i420(), S[0].w, S[0].h, maps, border, tabs, st, S.sample_bytes, S[1].sx, S[1].sy, fill);
+    const uint8_t* us[WARP_BATCH_MAX];
+    uint8_t* ud[WARP_BATCH_MAX];
+    for (int i = 0; i < n; i++) { us[i] = srcs[i] + S[1].off; ud[i] = dsts[i] + D[1].off; }
+    return launch_warp_nv12(srcs, dsts, us, ud, n, S[0].pitch, D[0].pitch, S[0].w, S[0].h, maps, border, tabs, st, S.sample_bytes, fill);
+}
+// A surface from one layout to another, one copy per plane (S and D: the planes of one format; S says how much of each)
+inline hipError_t copy_planes(uint8_t* dst, const Planes& D, const uint8_t* src, const Planes& S, hipMemcpyKind kind, hipStream_t st) {
+    for (int k = 0; k < S.n; k++) {
+        const hipError_t e = hipMemcpy2DAsync(dst + D[k].off, D[k].pitch, src + S[k].off, S[k].pitch, S.row_bytes(k), S[k].h, kind, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ---- k_roll.hip, k_azc.hip: the geometry and layout rules of their three-plane surfaces are planar_layout_check, a frame of
+// theirs is a StageFrame (planar_layout.h)
+constexpr char RGB_FORMATS[] = "VS_FMT_BGR8, VS_FMT_RGB8, VS_FMT_BGRA8, VS_FMT_RGBA8";
+// The *_dev_n forms: n surfaces in call order (what n calls of the per-surface entry point do, without n trips through a binding);
+// one(i) hands surface i over, the first refusal ends the call
+template <class One>
+int each_surface(int n, One one) {
+    for (int i = 0; i < n; i++) {
+        const int rc = one(i);
+        if (rc != VS_OK) return rc;
+    }
+    return VS_OK;
+}
 
 // ---- k_cvt.hip: YUV surfaces <-> interleaved 8-bit RGB (vs_op_cvt_yuv_to_rgb, vs_op_cvt_rgb_to_yuv, vs_enh_apply_yuv_dev)
 constexpr int CVT_MAX_SURFACES = 32;        // of one launch: their pointers are kernel arguments

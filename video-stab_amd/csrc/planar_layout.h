@@ -1,7 +1,7 @@
 // Where the planes of a surface lie - the three-plane layout of the launchers (VS_FMT_I420 ... VS_FMT_I412) and the plane list of
-// any format that the stream and the batch schedule walk - and what the roll and zoom/crop stages refuse about a three-plane
-// surface.  Plain C++ over integers like pixfmt.h: no HIP, no object - tests/cpp/planar_layout_check.cpp and tests/cpp/planes_check.cpp
-// compile this header alone and ask it without a device.
+// any format that the stream, the batch schedule and the roll and zoom/crop stages walk -, the frame record of those two stages,
+// and what they refuse about a three-plane surface.  Plain C++ over integers like pixfmt.h: no HIP, no object -
+// tests/cpp/planar_layout_check.cpp, planes_check.cpp and stage_frame_check.cpp compile this header alone and ask it without a device.
 #ifndef VS_PLANAR_LAYOUT_H
 #define VS_PLANAR_LAYOUT_H
 
@@ -59,6 +59,36 @@ inline Planes planes(const PixFmt& f, int w, int h, size_t pitch, const ChromaLa
 inline uint16_t plane_fill(const vs_yuv_fill& c, const Planes& P, int k, int ch) {
     if (P[k].cn == 2) return ch ? c.v : c.u;
     return ch ? 0 : k == 0 ? c.y : k == 1 ? c.u : c.v;
+}
+
+// The inverse of Planes::i420(): the planes of a three-plane surface whose layout has been resolved (planar_layout_check)
+inline Planes planes(const PixFmt& f, int w, int h, const I420Layout& l) { return planes(f, w, h, l.pitch, ChromaLayout{0, l.u, l.v, l.cpitch}); }
+// Offsets and pitches of all planes agree: one launch can take both surfaces
+inline bool same_layout(const Planes& a, const Planes& b) {
+    if (a.n != b.n) return false;
+    for (int k = 0; k < a.n; k++)
+        if (a[k].off != b[k].off || a[k].pitch != b[k].pitch) return false;
+    return true;
+}
+
+// ---- k_roll.hip, k_azc.hip: a frame handed to the stages around the stabilizer, whatever its format - w x h pixels of format *pf
+// at src with planes S, the result at dst with planes D (the zoom stage: laid out for the larger of the frame and its output size)
+struct StageFrame {
+    const PixFmt* pf;
+    int w, h;
+    const uint8_t* src;
+    uint8_t* dst;
+    Planes S, D;
+};
+// The zoom stage's crop (cx, cy, cw, ch) of the picture as plane p sees it, and the size of p's share of an ow x oh result
+struct PlaneRect { int x, y, w, h; };
+inline PlaneRect plane_crop(const Plane& p, int cx, int cy, int cw, int ch) {
+    return PlaneRect{cx >> p.sx, cy >> p.sy, std::max(1, cw >> p.sx), std::max(1, ch >> p.sy)};
+}
+inline PlaneRect plane_result(const Plane& p, int ow, int oh) { return PlaneRect{0, 0, ow >> p.sx, oh >> p.sy}; }
+// ... and where the crop's first sample lies behind the surface pointer
+inline size_t plane_crop_offset(const Planes& P, int k, const PlaneRect& r) {
+    return P[k].off + (size_t)r.y * P[k].pitch + (size_t)r.x * P[k].cn * P.sample_bytes;
 }
 
 // ---- k_roll.hip, k_azc.hip: three-plane surfaces (VS_FMT_I420 ... VS_FMT_I412) of the stages around the stabilizer

@@ -355,18 +355,7 @@ inline YuvBorder yuv_warp_border(const vs_stab* s) {
     return {VS_BORDER_FILL, f};
 }
 
-// The warp of n <= WARP_BATCH_MAX YUV surfaces (planes S, at the size of S's luma) into surfaces with planes D, one launch: luma
-// and the interleaved chroma plane - half size, two channels, the map with the halved translation (m + 6) -, or Y, U and V,
-// whose one chroma table serves both U and V.
-inline int warp_yuv(const uint8_t* const* srcs, uint8_t* const* dsts, int n, const Planes& S, const Planes& D, WarpMaps maps, const YuvBorder& b, WarpTabs tabs,
-                    hipStream_t st) {
-    if (S.n == 3)
-        return launch_warp_i420(srcs, dsts, n, S.i420(), D.i420(), S[0].w, S[0].h, maps, b.border, tabs, st, S.sample_bytes, S[1].sx, S[1].sy, b.fill);
-    const uint8_t* us[WARP_BATCH_MAX];
-    uint8_t* ud[WARP_BATCH_MAX];
-    for (int i = 0; i < n; i++) { us[i] = srcs[i] + S[1].off; ud[i] = dsts[i] + D[1].off; }
-    return launch_warp_nv12(srcs, dsts, us, ud, n, S[0].pitch, D[0].pitch, S[0].w, S[0].h, maps, b.border, tabs, st, S.sample_bytes, b.fill);
-}
+// (the warp itself: warp_planes, launchers.h)
 
 // The zoom of n warped scratch surfaces into their results (device surfaces in the caller's output layout, or the staging of the
 // host entry points): ONE k_cropzoom launch over all their planes (stabilizer.cpp)

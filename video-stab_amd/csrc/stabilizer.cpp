@@ -256,21 +256,13 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
 }
 
 
-// A surface from one layout to another, one copy per plane (S and D: the planes of one format and size)
-int copy_planes(vs_stab* s, uint8_t* dst, const Planes& D, const uint8_t* src, const Planes& S, hipMemcpyKind kind, hipStream_t st) {
-    for (int k = 0; k < S.n; k++)
-        VS_OBJ_HIP(s, hipMemcpy2DAsync(dst + D[k].off, D[k].pitch, src + S[k].off, S[k].pitch, S.row_bytes(k), S[k].h, kind, st));
-    return VS_OK;
-}
-
 // The result of a host call from its staging buffer (rows of `orow` bytes, `orows` of them; three planes: the packed layout at that
 // pitch) into the caller's frame.  rw x rh: the size of the frame delivered (vs_stab_last_out_dims), which a YUV stream goes by: a
 // padded result, or the unpadded last frame of a flush with the default offsets of ITS size.
 int download_result(vs_stab* s, uint8_t* out, size_t out_stride, const uint8_t* d_src, size_t orow, int orows, hipStream_t st, int rw, int rh) {
-    if (s->pf->three_planes())
-        return copy_planes(s, out, planes(*s->pf, rw, rh, out_stride), d_src, planes(*s->pf, rw, rh, orow), hipMemcpyDeviceToHost, st);
     const bool pad = yuv_padded(s);     // (luma and UV plane lie behind each other: one copy)
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, pad ? (size_t)rw * s->cn : orow, pad ? s->pf->rows(rh) : orows, hipMemcpyDeviceToHost, st));
+    if (s->pf->three_planes()) VS_OBJ_HIP(s, copy_planes(out, planes(*s->pf, rw, rh, out_stride), d_src, planes(*s->pf, rw, rh, orow), hipMemcpyDeviceToHost, st));
+    else VS_OBJ_HIP(s, hipMemcpy2DAsync(out, out_stride, d_src, orow, pad ? (size_t)rw * s->cn : orow, pad ? s->pf->rows(rh) : orows, hipMemcpyDeviceToHost, st));
     return VS_OK;
 }
 
@@ -283,8 +275,8 @@ int enqueue_copy_in(vs_stab* s, int slot, const void* src, size_t stride, hipMem
     // at the caller's pitch (host frames), and a decoder's NV12 / P010 surface whose planes lie apart; anything else is ONE copy
     const ChromaLayout in = kind == hipMemcpyDeviceToDevice ? s->in : ChromaLayout();
     if (s->pf->three_planes() || (s->pf->luma_uv() && in.uv_off))
-        return copy_planes(s, dst, planes(*s->pf, s->w, s->h, s->row_bytes), (const uint8_t*)src, planes(*s->pf, s->w, s->h, stride, in), kind, s->st_pre);
-    VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->rows_total, kind, s->st_pre));
+        VS_OBJ_HIP(s, copy_planes(dst, planes(*s->pf, s->w, s->h, s->row_bytes), (const uint8_t*)src, planes(*s->pf, s->w, s->h, stride, in), kind, s->st_pre));
+    else VS_OBJ_HIP(s, hipMemcpy2DAsync(dst, s->row_bytes, src, stride, s->row_bytes, s->rows_total, kind, s->st_pre));
     return VS_OK;
 }
 
@@ -499,7 +491,7 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         const bool ypad = yuv_padded(s);
         if (!ypad && (ow != s->w || oh != s->h))
             VS_OBJ_HIP(s, hipMemset2DAsync(d_out, out_stride, 0, (size_t)ow * s->cn, oh, st));
-        VS_OBJ_TRY(s, copy_planes(s, d_out, ypad ? planes(*s->pf, s->w, s->h, out_stride) : result_planes(s, d_out, out_stride), frame, queued_planes(s),
+        VS_OBJ_HIP(s, copy_planes(d_out, ypad ? planes(*s->pf, s->w, s->h, out_stride) : result_planes(s, d_out, out_stride), frame, queued_planes(s),
                                   hipMemcpyDeviceToDevice, st));
         s->last_out_w = s->w; s->last_out_h = s->h;
     } else if (canvas_on(s)) {                                                        // :1130-1134
@@ -524,8 +516,8 @@ int apply_next(vs_stab* s, uint8_t* d_out, size_t out_stride, bool may_defer) {
         // stream's scratch; so does NV12 under edge fill, whose instances of the general kernels read every tap from memory)
         const YuvBorder wb = yuv_warp_border(s);
         if (rc == VS_OK)
-            rc = warp_yuv(&wsrc, &wdst, 1, warp_src_planes(s), warp_dst_planes(s, d_out, out_stride), WarpMaps{s->d_Minv, 12, false}, wb,
-                          s->fmt == VS_FMT_NV12 && wb.border != VS_BORDER_FILL ? WarpTabs{} : WarpTabs{WarpTabs::SCRATCH}, st);
+            rc = warp_planes(&wsrc, &wdst, 1, warp_src_planes(s), warp_dst_planes(s, d_out, out_stride), WarpMaps{s->d_Minv, 12, false}, wb.border, wb.fill,
+                             s->fmt == VS_FMT_NV12 && wb.border != VS_BORDER_FILL ? WarpTabs{} : WarpTabs{WarpTabs::SCRATCH}, st);
         if (cz && rc == VS_OK) rc = cz_launch(s, &wdst, &d_out, 1, out_stride, st);
         if (fade && rc == VS_OK) rc = yuv_fade_update(s, d_out, out_stride, st);
     } else if (bp.pad && p.border_type == VS_BORDER_FADE) {                               // :914-978, :1069-1106
