@@ -12,7 +12,8 @@
 #                     * the format table and the refusal rules (csrc/pixfmt.h) in tests/cpp/pixfmt_check over the whole case list
 #                       of tests/refusal_cases.py, the plane list of a YUV surface (csrc/planar_layout.h) in tests/cpp/planes_check,
 #                       the frame record of the roll and zoom/crop stages (the same header) in tests/cpp/stage_frame_check,
-#                       and the rules of the fade border on YUV in tests/cpp/yuv_fade_check.
+#                       the rules of the fade border on YUV in tests/cpp/yuv_fade_check, and the axis tables of the resize to an
+#                       output size (csrc/resize_tables.h) in tests/cpp/resize_tables_check.
 #                   GPU sanitizers are not available on this pool; device code is covered by the parity tests instead.
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
 ASAN_LIB := $(shell gcc -print-file-name=libasan.so)
@@ -42,6 +43,7 @@ asan-host:
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/planes_check.cpp -o scratch/fuzz/_asan/planes_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/stage_frame_check.cpp -o scratch/fuzz/_asan/stage_frame_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/yuv_fade_check.cpp -o scratch/fuzz/_asan/yuv_fade_check
+	g++ -O1 -g -std=c++17 -ffp-contract=off $(SAN) tests/cpp/resize_tables_check.cpp -o scratch/fuzz/_asan/resize_tables_check
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/config_fuzz 20000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/azc_fuzz 5000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/libm_check quick
@@ -53,5 +55,8 @@ asan-host:
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/stage_frame_check
 	for f in 0 1 2 6 7 8 10 11 12 15; do for b in 0 5 8; do for m in 0 1; do echo "$$f 64 48 128 $$b 0 $$m 1 $$m 1 70"; done; done; done | \
 	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/yuv_fade_check > /dev/null
+
+	for p in "1 1" "1 7" "7 1" "2 3" "5 4" "64 48" "130 97" "97 322" "3900 3840" "32767 2" "2 32767"; do for i in 0 1; do for a in 0 1; do echo "$$p $$i $$a"; done; done; done | \
+	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/resize_tables_check > /dev/null
 
 .PHONY: all asan asan-oracle asan-host

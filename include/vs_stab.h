@@ -53,7 +53,8 @@ extern "C" {
  *    vs_yuv_video_black, struct vs_pad_job with vs_op_pad_jobs; the fade border on YUV streams: vs_stab_set_yuv_fade, struct
  *    vs_fade_job with vs_op_fade_blend_jobs, struct vs_fade_update_job with vs_op_fade_update_jobs; edge fill on YUV streams:
  *    vs_stab_set_yuv_edge_fill, vs_batch_set_yuv_edge_fill and vs_op_warp_affine_yuv_fill; the packed 4:2:2 capture formats: enum
- *    vs_packed_fmt with vs_op_cvt_packed_to_yuv, vs_op_cvt_yuv_to_packed and vs_packed_layout
+ *    vs_packed_fmt with vs_op_cvt_packed_to_yuv, vs_op_cvt_yuv_to_packed and vs_packed_layout; the resize to an output size: enum
+ *    vs_interp with vs_op_resample_jobs, vs_op_resample_jobs_plan, vs_op_resize_yuv, vs_op_resize_rgb and vs_resize_axis_table
  *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
@@ -1335,6 +1336,78 @@ int vs_op_cvt_yuv_to_packed(int src_fmt, const void* const* d_src, const vs_i420
  * (h - 1) * pitch + row bytes).  Each result may be NULL.  Refuses exactly what the two calls refuse about a packed format, a size
  * and a pitch (VS_ERR_INVALID_ARG, the text in vs_last_error). */
 int vs_packed_layout(int packed_fmt, int w, int h, size_t pitch, size_t* row_bytes, size_t* resolved_pitch, size_t* bytes);
+
+/* ---- resize to an output size: INTER_LINEAR and INTER_LANCZOS4 ----------------------------------------------------------------
+ * A stream in border-pad or fade mode returns surfaces of (w + 2b) x (h + 2b); the reference's shipped main resizes what the
+ * stabilizer returns to the frame size in front of its encoder - cv::resize(..., INTER_LANCZOS4) in processing mode
+ * (examples/vs.cpp:651-652), INTER_LINEAR in passthrough mode and for a camera of another size (:541, :638; vsg.cpp:255).  These
+ * calls do it on the device, in any ratio, up or down: sw x sh -> dw x dh.  (vs_op_resize_jobs is the zoom-in of crop-and-zoom only,
+ * vs_op_scale_jobs is cv::warpAffine arithmetic with a constant-0 border and two taps whatever the ratio.)
+ *
+ * Definition (tests/resizeref.py states it in numpy and `math`).  Per axis src -> dst and destination index d:
+ *   scale = 1.0 / ((double)dst / src), f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f = f - (float)s in float32.
+ * VS_INTERP_LINEAR is cv::resize(INTER_LINEAR) as vs_stab_set_yuv_crop_zoom defines it, for any ratio: columns follow the edge rule
+ *   (s < 0: s = 0, f = 0; s >= src - 1: s = src - 1, f = 0; from the first column whose second tap would leave the source on, the
+ *   result of the horizontal pass is the sample x 2048), rows keep their coefficients and clamp both tap rows; coefficients
+ *   saturate_cast<short>((1 - f) * 2048.f) and (f * 2048.f); 8-bit vertical pass (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2,
+ *   16-bit the exact sum with ONE rounding half to even at bit 22.  The exact 2 : 1 case (sw == 2 dw and sh == 2 dh) is the 2 x 2
+ *   mean (s00 + s01 + s10 + s11 + 2) >> 2 at both depths (cv::resize reroutes it to INTER_AREA).  For dw >= sw and dh >= sh the
+ *   result equals vs_op_resize_jobs' bit for bit.
+ * VS_INTERP_LANCZOS4 is cv::resize(INTER_LANCZOS4) for CV_8U: neither s nor f is clamped; eight taps at clamp(s - 3 + k, 0, src - 1),
+ *   k = 0 .. 7, on both axes; their weights are interpolateLanczos4's - f < FLT_EPSILON: (0,0,0,1,0,0,0,0); otherwise with
+ *   cs = {{1,0},{-r,-r},{0,1},{r,-r},{-1,0},{r,r},{0,-1},{-r,r}}, r = 0.70710678118654752440084436210485, y0 = -(f + 3) * pi / 4,
+ *   s0 = sin(y0), c0 = cos(y0) in double: w[i] = (float)((cs[i][0] * s0 + cs[i][1] * c0) / (y * y)), y = -(f + 3 - i) * pi / 4; the
+ *   float running sum of the w[i]; w[i] *= 1.f / sum - and the coefficient of a tap is saturate_cast<short>(w[i] * 2048.f).  The eight
+ *   coefficients are NOT renormalised (their sum ranges from 2045 to 2051: a flat 255 area may come out as 254).
+ *   out = clamp((S + 2^21) >> 22, 0, max_value), S = the exact integer sum over the 64 taps, arithmetic shift.  16-bit samples: the
+ *   same coefficients and sums with S in 64 bits - a definition of this library (OpenCV's CV_16U path has float coefficients).
+ *   The kernel is not widened for downscales, as in OpenCV: a strong downscale aliases.
+ *   Over a dense scan of f the positive coefficients of an axis sum to at most 2780 and the negative ones to at most 732, so on
+ *   8-bit planes |S| <= 255 * 2780^2 < 2^31 - 2^21.
+ * The same size in and out is the identity at either interpolation.  max_value: every result is clamped to 0 .. max_value, 0 = the
+ * sample type's maximum.
+ * Coefficients are built on the host from the double sin / cos of the C library (never a device libm); the kernels read them as
+ * tables from device memory: one table per (src, dst, interp, axis), built once, uploaded and cached per device (64 MiB of tables
+ * per device; when they are full the device is drained before places are given out anew).  A CALL THAT MEETS A NEW AXIS MAY BLOCK
+ * WHILE ITS TABLE IS UPLOADED; later calls only launch.  A single call whose distinct tables exceed the 64 MiB is VS_ERR_CAPACITY.
+ *
+ * vs_op_resample_jobs - plane jobs: n = 1 .. 96 jobs of one sample size (1 or 2 bytes) in ONE launch per path class; vs_scale_job
+ *   as it is: src = the plane's first sample, sw x sh -> dw x dh, sizes 1 .. 32767, strides in bytes, reserved = 0; cn 1 .. 4 with
+ *   8-bit samples, cn 1 .. 2 with 16-bit samples (every channel a channel of its own), mixed freely; 16-bit pointers and strides even.
+ *   path 0: the staged kernel where the source box of every tile (256 bytes x 16 rows of destination) fits the staging area (40
+ *   rows of 570 bytes: every upscale, downscales to about 2 : 1), the direct kernel otherwise; the exact 2 : 1 LINEAR mean needs no
+ *   staging and rides in the staged launch.  path 1: every job through the direct kernel.  Both give the same bytes.
+ *   vs_op_resample_jobs_plan (host only, needs no device): staged[i] = 1 where path 0 sends job i into the staged launch.
+ * vs_op_resize_yuv - n = 1 .. 32 surfaces of one geometry, any of the eleven YUV surface formats, all planes of all surfaces
+ *   through the job launch above (path 0).  Layouts and their rules are those of vs_op_cvt_yuv_to_yuv, per side.  A chroma plane is
+ *   a plane of its own, (sw >> sx) x (sh >> sy) -> (dw >> sx) x (dh >> sy) with its own scale, resized about its centre; the
+ *   interleaved UV plane of NV12 / P010 goes as cn 2.  sw, sh, dw, dh: multiples of the format's subsampling, 1 .. 32767.
+ *   max_value: with LANCZOS4 (1 << bits) - 1 for the low-bit formats (I010, I012, I210, I212, I410, I412), else the type's maximum.
+ * vs_op_resize_rgb - VS_FMT_BGR8 / RGB8 / BGRA8 / RGBA8 / GRAY8, n = 1 .. 32: the reference's own case (a BGR cv::Mat).  Alpha and
+ *   the fourth channel are channels like the others.
+ * d_src and d_dst are HOST arrays of n device pointers, read during the call.
+ * Refusals: all decided before any device call, VS_ERR_INVALID_ARG with a text in vs_last_error that names the call, the job or
+ * side, and the format: everything vs_op_resize_jobs and vs_op_cvt_yuv_to_yuv refuse about jobs, formats, sizes, layouts, parity
+ * and counts (but no ratio is refused), and interp or path outside its enum; max_value below 0 or above the sample type's
+ * maximum; cn outside the ranges above; reserved != 0; a destination that overlaps its source (surfaces: d_src[i] == d_dst[j], the
+ * part that can be checked).  Valid arguments without a device: VS_ERR_NO_DEVICE.  No byte outside a job's sw x sh samples is
+ * read, none outside dw x dh written.  Asynchronous on `stream`.
+ * Not built: INTER_AREA beyond the 2 : 1 reroute, cubic, nearest, antialiased (widened-kernel) downscaling; packed capture
+ * formats; chroma-siting-aware resampling; a stream or stage that emits another size by itself. */
+enum vs_interp { VS_INTERP_LINEAR = 0, VS_INTERP_LANCZOS4 = 1 };
+int vs_op_resample_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int interp,
+                        int max_value, int path, void* stream);
+int vs_op_resample_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int interp, int32_t* staged);
+int vs_op_resize_yuv(int fmt, const void* const* d_src, const vs_i420_layout* in, int sw, int sh,
+                     void* const* d_dst, const vs_i420_layout* out, int dw, int dh,
+                     int n, int interp, void* stream);
+int vs_op_resize_rgb(int fmt, const void* const* d_src, size_t src_stride, int sw, int sh,
+                     void* const* d_dst, size_t dst_stride, int dw, int dh,
+                     int n, int interp, void* stream);
+/* Host only, needs no device: the table of one axis src -> dst (1 .. 32767 each).  K = 2 (LINEAR) or 8 (LANCZOS4);
+ * idx[d * K + k] = the source index of tap k of destination index d, already clamped; coef[d * K + k] = its 11-bit coefficient.
+ * axis 0 = columns, 1 = rows (they differ for LINEAR: the edge rule above is the columns').  idx and coef hold dst * K entries. */
+int vs_resize_axis_table(int src, int dst, int interp, int axis, int32_t* idx, int16_t* coef);
 
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */

@@ -166,6 +166,15 @@ int launch_cvt_yuv_to_packed(const PixFmt& sf, const void* const* src, const I42
 constexpr int CZ_MAX_JOBS = 96;
 int launch_cropzoom(const vs_scale_job* jobs, int n, int sample_bytes, hipStream_t st);
 
+// ---- k_resize.hip: the resize to an output size (vs_op_resample_jobs, vs_op_resize_yuv, vs_op_resize_rgb)
+// n <= RS_MAX_JOBS planes (sw x sh samples of cn channels: 1 .. 4 with 8-bit samples, 1 or 2 with 16-bit samples) resized to dw x dh
+// in any ratio, interp a vs_interp, results clamped to 0 .. max_value (0: the sample type's maximum); one launch per path class.
+// Checks the launch and every job on the host first (a text in vs_last_error that names `name` and the job).  A call that meets
+// an axis (src, dst, interp) for the first time on its device builds and uploads that axis' table and may block meanwhile.
+constexpr int RS_MAX_JOBS = 96;
+int launch_resample(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int interp, int max_value, int path, hipStream_t st);
+int resample_plan(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int interp, int32_t* staged);     // host only
+
 // ---- k_yuvpad.hip: the pad of border pad on YUV surfaces (vs_op_pad_jobs; a stream with vs_stab_set_yuv_border_pad)
 // n <= YP_MAX_JOBS planes (sw x sh samples) padded by bx columns and by rows on every side in ONE launch: 32 surfaces of up to three
 // planes; cn 1 and 2 may be mixed, the sample size is the launch's.  Checks every job on the host first (a text in vs_last_error

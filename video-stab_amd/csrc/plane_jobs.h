@@ -1,5 +1,6 @@
 // What the batched plane-job operators on YUV surfaces share: k_cropzoom.hip (vs_op_resize_jobs), k_yuvpad.hip (vs_op_pad_jobs) and
-// k_yuvfade.hip (vs_op_fade_blend_jobs, vs_op_fade_update_jobs).
+// k_yuvfade.hip (vs_op_fade_blend_jobs, vs_op_fade_update_jobs); k_resize.hip (vs_op_resample_jobs) uses the sequence, the bisection,
+// the split and pj_launch, once per path class, with a lane shape of its own like the zoom.
 //
 // The scheme.  One launch takes up to a limit of jobs (one plane each) of one sample size, cn 1 and 2 mixed.  It is a flat sequence of
 // (job, tile row, tile column) tiles in the XCD-aware order of the warp kernels: workgroup `lin` takes tile xcd_seq(lin, tiles)

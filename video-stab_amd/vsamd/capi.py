@@ -192,6 +192,9 @@ class VsFadeUpdateJob(C.Structure):
                 ("w", C.c_int32), ("h", C.c_int32), ("cn", C.c_int32), ("reserved", C.c_int32)]
 
 
+INTERP_LINEAR, INTERP_LANCZOS4 = 0, 1          # enum vs_interp
+
+
 class VsScaleJob(C.Structure):
     """struct vs_scale_job (include/vs_stab.h): one crop-and-scale of vs_op_scale_jobs."""
     _fields_ = [("src", C.c_void_p), ("src_stride", C.c_size_t), ("sw", C.c_int32), ("sh", C.c_int32),
@@ -543,6 +546,13 @@ class VsLib:
                                                  C.POINTER(C.c_int64)]
             L.vs_op_scale_jobs_rgb.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, vp]
             L.vs_op_scale_jobs_rgb_plan.argtypes = [C.POINTER(VsScaleJob), C.c_int, i32p]
+            # resize to an output size
+            L.vs_op_resample_jobs.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+            L.vs_op_resample_jobs_plan.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, C.c_int, i32p]
+            L.vs_op_resize_yuv.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+            L.vs_op_resize_rgb.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, vp]
+            L.vs_resize_axis_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.POINTER(C.c_int16)]
             # edge fill on YUV streams
             L.vs_stab_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
             L.vs_batch_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
@@ -861,6 +871,35 @@ class VsLib:
     def resize_jobs(self, jobs, sample_bytes=1, stream=None):
         """vs_op_resize_jobs (the zoom of crop-and-zoom on YUV surfaces): 1 .. 96 jobs, tuples as for scale_jobs; asynchronous."""
         self.check(self.lib.vs_op_resize_jobs(self._scale_job_array(jobs), len(jobs), sample_bytes, stream))
+
+    def resample_jobs(self, jobs, sample_bytes=1, interp=INTERP_LINEAR, max_value=0, path=0, stream=None):
+        """vs_op_resample_jobs (resize to an output size, any ratio): 1 .. 96 jobs, tuples as for scale_jobs; asynchronous."""
+        self.check(self.lib.vs_op_resample_jobs(self._scale_job_array(jobs), len(jobs), sample_bytes, interp, max_value, path, stream))
+
+    def resample_jobs_plan(self, jobs, sample_bytes=1, interp=INTERP_LINEAR):
+        """vs_op_resample_jobs_plan (no device needed): 1 per job that path 0 sends into the staged launch."""
+        staged = np.zeros(max(1, len(jobs)), np.int32)
+        self.check(self.lib.vs_op_resample_jobs_plan(self._scale_job_array(jobs), len(jobs), sample_bytes, interp, _p(staged, i32p)))
+        return staged[:len(jobs)].copy()
+
+    def resize_axis_table(self, src, dst, interp, axis):
+        """vs_resize_axis_table (no device needed): (idx (dst, K) int32, coef (dst, K) int16), K = 2 (LINEAR) or 8 (LANCZOS4)."""
+        k = 8 if interp == INTERP_LANCZOS4 else 2
+        idx, coef = np.zeros((max(dst, 1), k), np.int32), np.zeros((max(dst, 1), k), np.int16)
+        self.check(self.lib.vs_resize_axis_table(src, dst, interp, axis, _p(idx, i32p), coef.ctypes.data_as(C.POINTER(C.c_int16))))
+        return idx, coef
+
+    def resize_yuv(self, fmt, d_src, in_layout, sw, sh, d_dst, out_layout, dw, dh, interp=INTERP_LINEAR, stream=None):
+        """vs_op_resize_yuv on surfaces in device memory: d_src, d_dst lists of device addresses, layouts (pitch[, c_pitch[, u_off[,
+        v_off]]]) in bytes, 0 = the default of a field; asynchronous."""
+        src, dst = (C.c_void_p * len(d_src))(*d_src), (C.c_void_p * len(d_dst))(*d_dst)
+        self.check(self.lib.vs_op_resize_yuv(fmt, src, C.byref(I420LayoutC(*in_layout)), sw, sh, dst, C.byref(I420LayoutC(*out_layout)), dw, dh,
+                                             len(d_src), interp, stream))
+
+    def resize_rgb(self, fmt, d_src, src_stride, sw, sh, d_dst, dst_stride, dw, dh, interp=INTERP_LINEAR, stream=None):
+        """vs_op_resize_rgb on BGR8 / RGB8 / BGRA8 / RGBA8 / GRAY8 frames in device memory (lists of device addresses); asynchronous."""
+        src, dst = (C.c_void_p * len(d_src))(*d_src), (C.c_void_p * len(d_dst))(*d_dst)
+        self.check(self.lib.vs_op_resize_rgb(fmt, src, src_stride, sw, sh, dst, dst_stride, dw, dh, len(d_src), interp, stream))
 
     def pad_jobs(self, jobs, sample_bytes=1, stream=None):
         """vs_op_pad_jobs (the pad of border pad on YUV surfaces): 1 .. 96 jobs, tuples (src, src_stride, sw, sh, dst, dst_stride, bx,
