@@ -761,7 +761,7 @@ int run_gftt_op(const uint8_t* d_gray, size_t stride, int w, int h, int max_corn
                 double min_distance, int block_size, float* d_pts, int32_t* d_count, float* d_eig,
                 hipStream_t st) {
     if (w <= 0 || h <= 0) { set_last_error("gftt: invalid size"); return VS_ERR_INVALID_ARG; }
-    const int cap = w * h / 4 + 64;   // a 3x3 local maximum excludes its 8 neighbours
+    const int cap = gftt_cand_cap(w, h);
     void* scratch = nullptr;
     VS_HIP_TRY(hipMalloc(&scratch, gftt_work_bytes(w, h, cap)));
     GfttWork wk;

@@ -226,7 +226,7 @@ int allocate_buffers(vs_stab* s, int w, int h, int fmt) {
     s->pend.clear(); s->pend_set = 0; s->warp_valid[0] = s->warp_valid[1] = false;
     // GFTT scratch sized for the larger of the two detection images
     const int gmaxw = std::max(s->aw, 480), gmaxh = std::max(s->ah, 270);
-    const int cap = gmaxw * gmaxh / 4 + 64;
+    const int cap = gftt_cand_cap(gmaxw, gmaxh);
     const size_t gwb = (gftt_work_bytes(gmaxw, gmaxh, cap) + 255) & ~(size_t)255;
     VS_OBJ_HIP(s, hipMalloc(&s->d_gftt_scratch, gwb * ngw));
     s->gws.assign(ngw, GfttWork());

@@ -240,6 +240,10 @@ struct GfttWork {            // device scratch owned by the caller
     int32_t* counters;       // [0]=ncand [1]=maxbits [2]=overflow [3]=n_out  (+ spare)
     int cap;
 };
+// Candidates a w x h image can have: the interior.  A candidate is an interior pixel that EQUALS its 3x3 maximum, so on a plateau
+// (a picture of period blockSize has a constant map) every interior pixel is one; only strict maxima exclude their neighbours.
+// The list is never truncated with this cap; a buffer sized for a larger image holds the list of every smaller one.
+inline int gftt_cand_cap(int w, int h) { return w > 2 && h > 2 ? (w - 2) * (h - 2) : 1; }
 size_t gftt_work_bytes(int w, int h, int cap);
 void gftt_work_carve(void* base, int w, int h, int cap, GfttWork* out);
 int launch_gftt(const uint8_t* d_gray, size_t stride, int w, int h, int max_corners,
