@@ -12,8 +12,9 @@
 #                     * the format table and the refusal rules (csrc/pixfmt.h) in tests/cpp/pixfmt_check over the whole case list
 #                       of tests/refusal_cases.py, the plane list of a YUV surface (csrc/planar_layout.h) in tests/cpp/planes_check,
 #                       the frame record of the roll and zoom/crop stages (the same header) in tests/cpp/stage_frame_check,
-#                       the rules of the fade border on YUV in tests/cpp/yuv_fade_check, and the axis tables of the resize to an
-#                       output size (csrc/resize_tables.h) in tests/cpp/resize_tables_check.
+#                       the rules of the fade border on YUV in tests/cpp/yuv_fade_check, the axis tables of the resize to an
+#                       output size (csrc/resize_tables.h) in tests/cpp/resize_tables_check and those of the area-averaging
+#                       downscale (the same header) in tests/cpp/area_tables_check.
 #                   GPU sanitizers are not available on this pool; device code is covered by the parity tests instead.
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
 ASAN_LIB := $(shell gcc -print-file-name=libasan.so)
@@ -44,6 +45,7 @@ asan-host:
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/stage_frame_check.cpp -o scratch/fuzz/_asan/stage_frame_check
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/yuv_fade_check.cpp -o scratch/fuzz/_asan/yuv_fade_check
 	g++ -O1 -g -std=c++17 -ffp-contract=off $(SAN) tests/cpp/resize_tables_check.cpp -o scratch/fuzz/_asan/resize_tables_check
+	g++ -O1 -g -std=c++17 -ffp-contract=off $(SAN) tests/cpp/area_tables_check.cpp -o scratch/fuzz/_asan/area_tables_check
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/config_fuzz 20000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/azc_fuzz 5000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/libm_check quick
@@ -58,5 +60,7 @@ asan-host:
 
 	for p in "1 1" "1 7" "7 1" "2 3" "5 4" "64 48" "130 97" "97 322" "3900 3840" "32767 2" "2 32767"; do for i in 0 1; do for a in 0 1; do echo "$$p $$i $$a"; done; done; done | \
 	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/resize_tables_check > /dev/null
+	for p in "1 1" "5 3" "7 1" "64 3" "131 130" "300 300" "650 271" "1080 720" "2160 720" "3840 1280" "2048 37" "32767 2" "32767 32766"; do echo "$$p"; done | \
+	  ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/area_tables_check > /dev/null
 
 .PHONY: all asan asan-oracle asan-host

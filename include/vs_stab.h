@@ -54,7 +54,8 @@ extern "C" {
  *    vs_fade_job with vs_op_fade_blend_jobs, struct vs_fade_update_job with vs_op_fade_update_jobs; edge fill on YUV streams:
  *    vs_stab_set_yuv_edge_fill, vs_batch_set_yuv_edge_fill and vs_op_warp_affine_yuv_fill; the packed 4:2:2 capture formats: enum
  *    vs_packed_fmt with vs_op_cvt_packed_to_yuv, vs_op_cvt_yuv_to_packed and vs_packed_layout; the resize to an output size: enum
- *    vs_interp with vs_op_resample_jobs, vs_op_resample_jobs_plan, vs_op_resize_yuv, vs_op_resize_rgb and vs_resize_axis_table
+ *    vs_interp with vs_op_resample_jobs, vs_op_resample_jobs_plan, vs_op_resize_yuv, vs_op_resize_rgb and vs_resize_axis_table; the area-averaging downscale:
+ *    vs_op_area_jobs, vs_op_area_jobs_plan, vs_op_area_yuv, vs_op_area_rgb and vs_area_axis_table
  *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
@@ -1392,8 +1393,8 @@ int vs_packed_layout(int packed_fmt, int w, int h, size_t pitch, size_t* row_byt
  * maximum; cn outside the ranges above; reserved != 0; a destination that overlaps its source (surfaces: d_src[i] == d_dst[j], the
  * part that can be checked).  Valid arguments without a device: VS_ERR_NO_DEVICE.  No byte outside a job's sw x sh samples is
  * read, none outside dw x dh written.  Asynchronous on `stream`.
- * Not built: INTER_AREA beyond the 2 : 1 reroute, cubic, nearest, antialiased (widened-kernel) downscaling; packed capture
- * formats; chroma-siting-aware resampling; a stream or stage that emits another size by itself. */
+ * Not built: cubic, nearest, a widened (antialiased) Lanczos or linear kernel - for decimation there is the area-averaging
+ * downscale below; packed capture formats; chroma-siting-aware resampling; a stream or stage that emits another size by itself. */
 enum vs_interp { VS_INTERP_LINEAR = 0, VS_INTERP_LANCZOS4 = 1 };
 int vs_op_resample_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int interp,
                         int max_value, int path, void* stream);
@@ -1408,6 +1409,70 @@ int vs_op_resize_rgb(int fmt, const void* const* d_src, size_t src_stride, int s
  * idx[d * K + k] = the source index of tap k of destination index d, already clamped; coef[d * K + k] = its 11-bit coefficient.
  * axis 0 = columns, 1 = rows (they differ for LINEAR: the edge rule above is the columns').  idx and coef hold dst * K entries. */
 int vs_resize_axis_table(int src, int dst, int interp, int axis, int32_t* idx, int16_t* coef);
+
+/* ---- area-averaging downscale: cv::resize(INTER_AREA) for dw <= sw and dh <= sh ----------------------------------------------
+ * cv::resize(..., INTER_AREA) is what OpenCV's documentation names for decimation: every source sample of a destination sample's
+ * cell enters the result, so 2160p -> 720p, 1080p -> 720p or the (w + 2b) x (h + 2b) surface of a pad or fade stream brought down to
+ * a proxy size do not alias the way a point-sampled LINEAR or LANCZOS4 downscale does.  These calls do it on the device for
+ * dw <= sw and dh <= sh, on every surface the resize calls above take.  enum vs_interp and the resize calls are unchanged (interp
+ * = 2 stays refused there); the feature has entry points of its own.
+ *
+ * Definition (tests/arearef.py states it in numpy and `math`).  Per axis scale = 1.0 / ((double)dst / src) in IEEE doubles and
+ * i = rint(scale); the axis is INTEGER when |scale - i| < DBL_EPSILON (every k d -> d is).  A job has one of three classes:
+ * Class 2, the 2 x 2 mean - both axes integer with i = 2: (s00 + s01 + s10 + s11 + 2) >> 2 at both depths and every cn, byte for
+ *   byte what VS_INTERP_LINEAR gives for the same job.  It is OpenCV's SIMD path for cn 1, 3 and 4; for cn 2 OpenCV's scalar path
+ *   rounds ties to even, and + 2 >> 2 there is this library's choice (docs/opencv_semantics.md).
+ * Class 1, integer box - both axes integer otherwise (the same size included: the identity): S = the exact integer sum of the
+ *   ix x iy samples, out = rint_half_even((float)S * (1.f / (ix * iy))) - one float32 product, then saturate_cast's rounding.
+ *   OpenCV bit for bit on 8-bit planes; on 16-bit planes wherever OpenCV's float running sum is exact (S < 2^24: any area up to 256
+ *   at the full 16-bit range).  Beyond that the exact sum is this library's definition.
+ * Class 0, general - every other job; a job with one integer and one fractional axis is general on BOTH axes.  Per axis the taps of
+ *   destination index d follow computeResizeAreaTab: f1 = d * scale, f2 = f1 + scale, cw = min(scale, src - f1), s1 = ceil(f1),
+ *   s2 = min(floor(f2), src - 1), s1 = min(s1, s2); then, in this order,
+ *     (s1 - 1, (float)((s1 - f1) / cw))                        if s1 - f1 > 1e-3
+ *     (sx, (float)(1.0 / cw))                                  for sx = s1 .. s2 - 1
+ *     (s2, (float)(min(min(f2 - s2, 1.0), cw) / cw))           if f2 - s2 > 1e-3
+ *   The taps of an index are contiguous, at least one, and all middle weights are equal (tests/test_area_cpu.py checks it over
+ *   several hundred pairs), so an axis entry is first, count and three weights: tap 0 takes w_first, tap count - 1 takes w_last
+ *   when count > 1, every other tap w_mid - vs_area_axis_table's output and the device's table, four dwords per destination index
+ *   whatever the ratio.  Accumulation is in float32, every product and every sum rounded on its own, NOTHING fused:
+ *     for each tap row sy, ascending: buf = 0, then buf += (float)S[sx] * alpha over the column taps, ascending;
+ *     first tap row of a destination row: sum = beta * buf; later tap rows: sum += beta * buf;
+ *     out = clamp(rint_half_even(sum), 0, max_value).
+ *   This is OpenCV's order of operations; whether an OpenCV build fuses the vertical multiply-add depends on its SIMD baseline, and
+ *   the unfused form is this library's definition (docs/opencv_semantics.md).  The 1e-3 thresholds are OpenCV's: they drop
+ *   slivers, and the weights of an index then sum to as little as 0.99902 per axis, so a flat 16-bit area can come out a few codes
+ *   low at awkward ratios.  That is INTER_AREA, not a defect to repair here.
+ * max_value: every result is clamped to 0 .. max_value, 0 = the sample type's maximum, as in vs_op_resample_jobs.
+ * The tables are built on the host in doubles (no FMA contraction), one per (src, dst), and live in the resize's table arena under
+ * a key of their own: A CALL THAT MEETS A NEW AXIS MAY BLOCK WHILE ITS TABLE IS UPLOADED; VS_ERR_CAPACITY as above.  Classes 1 and
+ * 2 need no table.
+ *
+ * vs_op_area_jobs - plane jobs as in vs_op_resample_jobs: n = 1 .. 96 jobs of one sample size in ONE launch, whatever their classes;
+ *   cn 1 .. 4 with 8-bit samples, 1 .. 2 with 16-bit samples.  One kernel body, hence no path argument.
+ *   vs_op_area_jobs_plan (host only, needs no device): cls[i] = the class of job i.
+ * vs_op_area_yuv - n = 1 .. 32 surfaces of one geometry, any of the eleven YUV surface formats, layouts and plane rules as in
+ *   vs_op_resize_yuv: every chroma plane a plane of its own with its own ratio (and class), the UV plane of NV12 / P010 as cn 2.
+ *   max_value is (1 << bits) - 1 for the low-bit formats (I010, I012, I210, I212, I410, I412), else the type's maximum.
+ * vs_op_area_rgb - VS_FMT_BGR8 / RGB8 / BGRA8 / RGBA8 / GRAY8, n = 1 .. 32.
+ * Refusals: everything the resize calls refuse about jobs, formats, sizes, strides, layouts, parity, overlap, reserved and counts,
+ * VS_ERR_INVALID_ARG with a text that names the call, the job or side, and the format, decided before any device call.  One more:
+ * dw > sw or dh > sh on a job or surface is VS_ERR_UNSUPPORTED, and the text says so (the same size is accepted).  Valid arguments
+ * without a device: VS_ERR_NO_DEVICE.  No byte outside a job's sw x sh samples is read, none outside dw x dh written.
+ * Asynchronous on `stream`.
+ * Not built: cv::resize's emulation of INTER_AREA for upscales (a variant of bilinear); cubic and nearest; a widened Lanczos;
+ * chroma-siting-aware resampling; routing the zoom/crop stage's 640 x 360 output through this kernel; packed capture formats. */
+int vs_op_area_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int max_value, void* stream);
+int vs_op_area_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int32_t* cls);
+int vs_op_area_yuv(int fmt, const void* const* d_src, const vs_i420_layout* in, int sw, int sh,
+                   void* const* d_dst, const vs_i420_layout* out, int dw, int dh, int n, void* stream);
+int vs_op_area_rgb(int fmt, const void* const* d_src, size_t src_stride, int sw, int sh,
+                   void* const* d_dst, size_t dst_stride, int dw, int dh, int n, void* stream);
+/* Host only, needs no device: the table of one axis src -> dst, 1 <= dst <= src <= 32767 (dst > src: VS_ERR_UNSUPPORTED).  Each
+ * array holds dst entries: the taps of destination index d are the count[d] source samples from first[d] on; tap 0 weighs
+ * w_first[d], tap count[d] - 1 (count[d] > 1) w_last[d], every other tap w_mid[d]. */
+int vs_area_axis_table(int src, int dst, int32_t* first, int32_t* count,
+                       float* w_first, float* w_mid, float* w_last);
 
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */

@@ -24,6 +24,7 @@
 // where the lane's four bytes are all inside the row and aligned, else sample by sample (k_cropzoom.hip).
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -83,6 +84,7 @@ struct RsArgs {
 };
 static_assert(sizeof(RsJob) == 40 && sizeof(RsArgs) <= 4096, "the jobs travel as kernel arguments");
 constexpr uint32_t RS_AT_MASK = 0xffffffu;
+constexpr char AREA_UPSCALE[] = "dw > sw or dh > sh: area averaging only downscales (the upscale emulation of INTER_AREA is not built)";
 
 // One entry of a table: the K tap indices and coefficients of destination index d
 template <int K>
@@ -334,10 +336,161 @@ __global__ __launch_bounds__(RS_THREADS) void resize_kernel(const RsArgs a) {
     }
 }
 
+// ---- area-averaging downscale (vs_op_area_jobs): cv::resize(INTER_AREA), dw <= sw and dh <= sh -----------------------------------
+// The same job record, tile, lane shape and store path.  A job is general (class 0: both axes through an area table of the arena,
+// float32 sums in OpenCV's order, every product and sum rounded on its own), an integer box (class 1: the exact integer sum of
+// ix x iy samples, one float32 product) or the 2 x 2 mean (class 2: rs_mean_tile above); the three ride in ONE launch.  J.xtab: | cn << 24 | class
+// << 28; J.ytab of classes 1 and 2: ix | iy << 16 (then sw = ix dw and sh = iy dh exactly).
+// An area table: RS_TAB_HEAD dwords, then 4 dwords per destination index: first | count << 16, w_first, w_mid, w_last (float bits).
+// The taps of a sample in a source row lie PB bytes apart; a lane walks them through the aligned dwords that hold them, one load
+// per dword (a 3 : 1 luma row: three or four taps from one or two dwords); a dword that would reach outside the row's bytes is put
+// together from the bytes inside.
+struct ArEntry { int first, count; float wf, wm, wl; };
+__device__ __forceinline__ ArEntry ar_entry(const uint32_t* __restrict__ tab, int d) {
+    const pj_u4 q = *reinterpret_cast<const pj_u4*>(tab + RS_TAB_HEAD + (size_t)d * 4);      // (a table's place is 16-byte aligned)
+    return {(int)(q.x & 0xffffu), (int)(q.x >> 16), __uint_as_float(q.y), __uint_as_float(q.z), __uint_as_float(q.w)};
+}
+// (the weights by value: a choice between fields of a record in memory becomes a load through a chosen address, which keeps the
+// record out of registers)
+__device__ __forceinline__ float ar_weight(int count, float wf, float wm, float wl, int k) { return k == 0 ? wf : k == count - 1 ? wl : wm; }
+
+// n samples of the row at r0 (row_bytes bytes), PB bytes apart from byte b0 on, in ascending order: f(k, sample)
+template <int SB, int PB, class F>
+__device__ __forceinline__ void ar_row(uintptr_t r0, uint32_t row_bytes, uint32_t b0, int n, F f) {
+    uintptr_t p = r0 + b0;
+    int k = 0;
+    while (k < n) {
+        const uintptr_t a = p & ~(uintptr_t)3;
+        uint32_t q = 0;
+        if (a >= r0 && a + 4 <= r0 + row_bytes) q = *reinterpret_cast<const uint32_t*>(a);
+        else {
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if (a + b >= r0 && a + b < r0 + row_bytes) q |= (uint32_t)*reinterpret_cast<const uint8_t*>(a + b) << (8 * b);
+        }
+        do {
+            f(k, (q >> (8 * (uint32_t)(p & 3))) & (SB == 1 ? 0xffu : 0xffffu));
+            k++;
+            p += PB;
+        } while (k < n && (p & ~(uintptr_t)3) == a);
+    }
+}
+
+template <int SB, int CN>
+__device__ __forceinline__ void ar_general_tile(const RsJob& J, const uint32_t* __restrict__ xt, const uint32_t* __restrict__ yt, int tx, int ty, int lane,
+                                                int wave, int max_value) {
+    constexpr int NEL = RS_LB / SB, PB = SB * CN;
+    const int dw = J.dwh & 0xffffu, dh = J.dwh >> 16;
+    const int eb = (tx * 64 + lane) * NEL;
+    const int nv = min(NEL, dw * CN - eb);
+    if (nv <= 0) return;
+    const uint32_t row_bytes = xt[0] * PB;
+    ArEntry X[NEL];
+    uint32_t b0[NEL];
+#pragma unroll
+    for (int e = 0; e < NEL; e++) {
+        const int s = min(eb + e, dw * CN - 1), dx = s / CN, c = s - dx * CN;      // (samples past the row repeat its last one; they are not stored)
+        X[e] = ar_entry(xt, dx);
+        b0[e] = (uint32_t)X[e].first * PB + c * SB;
+    }
+#pragma unroll 1
+    for (int r = 0; r < RS_R; r++) {
+        const int dy = ty * RS_TR + wave * RS_R + r;              // (wave-uniform)
+        if (dy >= dh) break;
+        const ArEntry Y = ar_entry(yt, dy);
+        float sum[NEL];
+#pragma unroll
+        for (int e = 0; e < NEL; e++) sum[e] = 0.f;
+#pragma unroll 1
+        for (int ky = 0; ky < Y.count; ky++) {
+            const uintptr_t r0 = (uintptr_t)(J.src + (size_t)(Y.first + ky) * J.sstride);
+            const float beta = ar_weight(Y.count, Y.wf, Y.wm, Y.wl, ky);
+#pragma unroll
+            for (int e = 0; e < NEL; e++) {
+                const int nx = X[e].count;
+                const float wf = X[e].wf, wm = X[e].wm, wl = X[e].wl;
+                float buf = 0.f;
+                ar_row<SB, PB>(r0, row_bytes, b0[e], nx, [&](int k, uint32_t v) { buf = __fadd_rn(buf, __fmul_rn((float)v, ar_weight(nx, wf, wm, wl, k))); });
+                const float t = __fmul_rn(beta, buf);
+                sum[e] = ky == 0 ? t : __fadd_rn(sum[e], t);
+            }
+        }
+        uint32_t o[NEL];
+#pragma unroll
+        for (int e = 0; e < NEL; e++) o[e] = (uint32_t)min(max(__float2int_rn(sum[e]), 0), max_value);
+        rs_store<SB>(J, dy, eb, nv, o);
+    }
+}
+
+template <int SB, int CN>
+__device__ __forceinline__ void ar_box_tile(const RsJob& J, int tx, int ty, int lane, int wave, int max_value) {
+    constexpr int NEL = RS_LB / SB, PB = SB * CN;
+    const int dw = J.dwh & 0xffffu, dh = J.dwh >> 16;
+    const int ix = J.ytab & 0xffffu, iy = J.ytab >> 16;
+    const int eb = (tx * 64 + lane) * NEL;
+    const int nv = min(NEL, dw * CN - eb);
+    if (nv <= 0) return;
+    const uint32_t row_bytes = (uint32_t)(dw * ix) * PB;
+    // 1.f / (ix * iy) as OpenCV computes it, from a division in double: a float quotient rounded from 53 bits is the correctly
+    // rounded one (2 x 24 + 2 <= 53), whatever the device's float division does
+    const float inv = (float)(1.0 / (double)(float)(ix * iy));
+    uint32_t b0[NEL];
+#pragma unroll
+    for (int e = 0; e < NEL; e++) {
+        const int s = min(eb + e, dw * CN - 1), dx = s / CN, c = s - dx * CN;
+        b0[e] = (uint32_t)(dx * ix) * PB + c * SB;
+    }
+#pragma unroll 1
+    for (int r = 0; r < RS_R; r++) {
+        const int dy = ty * RS_TR + wave * RS_R + r;              // (wave-uniform)
+        if (dy >= dh) break;
+        uint64_t S[NEL];
+#pragma unroll
+        for (int e = 0; e < NEL; e++) S[e] = 0;
+#pragma unroll 1
+        for (int ky = 0; ky < iy; ky++) {
+            const uintptr_t r0 = (uintptr_t)(J.src + (size_t)(dy * iy + ky) * J.sstride);
+#pragma unroll
+            for (int e = 0; e < NEL; e++) {
+                uint32_t rs = 0;                                  // (65535 x 32767 < 2^31)
+                ar_row<SB, PB>(r0, row_bytes, b0[e], ix, [&](int, uint32_t v) { rs += v; });
+                S[e] += rs;
+            }
+        }
+        uint32_t o[NEL];
+#pragma unroll
+        for (int e = 0; e < NEL; e++) o[e] = min((uint32_t)__float2int_rn(__fmul_rn((float)S[e], inv)), (uint32_t)max_value);
+        rs_store<SB>(J, dy, eb, nv, o);
+    }
+}
+
+template <int SB, int CN>
+__device__ __forceinline__ void ar_tile(const RsArgs& a, const RsJob& J, int tx, int ty, int lane, int wave) {
+    const uint32_t cls = J.xtab >> 28 & 3u;
+    if (cls == 2) rs_mean_tile<SB, CN>(J, tx, ty, lane, wave, a.max_value);          // the resize's own 2 x 2 mean: the same bytes, the same time
+    else if (cls) ar_box_tile<SB, CN>(J, tx, ty, lane, wave, a.max_value);
+    else ar_general_tile<SB, CN>(J, a.arena + (J.xtab & RS_AT_MASK), a.arena + J.ytab, tx, ty, lane, wave, a.max_value);
+}
+
+template <int SB>
+__global__ __launch_bounds__(RS_THREADS) void area_kernel(const RsArgs a) {
+    const uint32_t seq = xcd_seq(blockIdx.x, a.tiles);
+    const RsJob J = a.j[pj_find(a, seq, [](const RsJob& j) { return j.tile0; })];
+    const uint32_t cn = J.xtab >> 24 & 7u;
+    const PjTile t = pj_split(seq - J.tile0, (J.dwh & 0xffffu) * cn * SB, RS_TB);
+    const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    if (cn == 1) ar_tile<SB, 1>(a, J, t.tx, t.ty, lane, wave);
+    else if (cn == 2) ar_tile<SB, 2>(a, J, t.tx, t.ty, lane, wave);
+    else if constexpr (SB == 1) {
+        if (cn == 3) ar_tile<SB, 3>(a, J, t.tx, t.ty, lane, wave);
+        else ar_tile<SB, 4>(a, J, t.tx, t.ty, lane, wave);
+    }
+}
+
 // ---- host: the tables ------------------------------------------------------------------------------------------------------
 // The table of one axis as the arena holds it
-typedef std::tuple<int, int, int, int> RsKey;              // src, dst, interp, axis (LANCZOS4: one table for both axes)
-RsKey rs_key(int src, int dst, int interp, int axis) { return RsKey(src, dst, interp, interp == RS_LANCZOS4 ? 0 : axis); }
+typedef std::tuple<int, int, int, int> RsKey;              // src, dst, interp (or RS_AREA), axis (LINEAR only: the others have one table for both axes)
+RsKey rs_key(int src, int dst, int interp, int axis) { return RsKey(src, dst, interp, interp == RS_LINEAR ? axis : 0); }
 
 struct RsTable {
     int k = 0, dst = 0;
@@ -346,7 +499,23 @@ struct RsTable {
 };
 
 std::shared_ptr<const RsTable> rs_build_table(const RsKey& key) {
-    const int src = std::get<0>(key), dst = std::get<1>(key), interp = std::get<2>(key), axis = std::get<3>(key), k = rs_taps(interp);
+    const int src = std::get<0>(key), dst = std::get<1>(key), interp = std::get<2>(key), axis = std::get<3>(key);
+    if (interp == RS_AREA) {                               // 4 dwords per destination index (ar_entry)
+        std::vector<int32_t> first(dst), count(dst);
+        std::vector<float> wf(dst), wm(dst), wl(dst);
+        rs_area_axis_table(src, dst, first.data(), count.data(), wf.data(), wm.data(), wl.data());
+        auto t = std::make_shared<RsTable>();
+        t->k = 4; t->dst = dst;
+        t->words.assign(RS_TAB_HEAD + (size_t)dst * 4, 0u);
+        t->words[0] = (uint32_t)src; t->words[1] = (uint32_t)dst; t->words[2] = 4u;
+        for (int d = 0; d < dst; d++) {
+            uint32_t* e = &t->words[RS_TAB_HEAD + (size_t)d * 4];
+            e[0] = (uint32_t)first[d] | (uint32_t)count[d] << 16;
+            std::memcpy(e + 1, &wf[d], 4); std::memcpy(e + 2, &wm[d], 4); std::memcpy(e + 3, &wl[d], 4);
+        }
+        return t;
+    }
+    const int k = rs_taps(interp);
     std::vector<int32_t> idx((size_t)dst * k);
     std::vector<int16_t> coef((size_t)dst * k);
     rs_axis_table(src, dst, interp, axis, idx.data(), coef.data());
@@ -468,6 +637,50 @@ uint32_t rs_place(RsArena& A, const RsKey& key, const RsTable& t, bool* full) {
     return at;
 }
 
+// A table a call needs, and its place in the device's arena
+struct RsNeed {
+    RsKey key;
+    std::shared_ptr<const RsTable> t;
+    uint32_t at = 0;
+};
+
+// The arena of the current device with the call's tables in place, uploaded where they are new (rs_mutex held)
+int rs_place_tables(const char* name, std::vector<RsNeed>& needs, const uint32_t** arena) {
+    size_t need = 0;
+    {
+        std::map<RsKey, size_t> distinct;
+        for (const RsNeed& q : needs) distinct[q.key] = rs_table_dwords(*q.t);
+        for (const auto& d : distinct) need += d.second;
+    }
+    if (need > RS_ARENA_BYTES / 4) {
+        set_last_error(std::string(name) + ": the axis tables of one call exceed the table arena (" + std::to_string(RS_ARENA_BYTES >> 20) + " MiB)");
+        return VS_ERR_CAPACITY;
+    }
+    VS_TRY(ensure_device());
+    int dev = 0;
+    VS_HIP_TRY(hipGetDevice(&dev));
+    RsArena& A = rs_arenas[dev];
+    if (!A.base) VS_HIP_TRY(hipMalloc((void**)&A.base, RS_ARENA_BYTES));
+    // the places of the call's tables; a full arena: drain the device, then give every place out anew (the call's tables fit: `need`)
+    for (int attempt = 0; attempt < 2; attempt++) {
+        bool full = false;
+        const size_t used0 = A.used;
+        for (size_t i = 0; i < needs.size() && !full; i++) needs[i].at = rs_place(A, needs[i].key, *needs[i].t, &full);
+        if (!full) {
+            // upload what is new: places at or behind used0, each written once by a copy that has finished when it returns
+            std::set<uint32_t> done;
+            for (const RsNeed& q : needs)
+                if (q.at >= used0 && done.insert(q.at).second) VS_HIP_TRY(hipMemcpy(A.base + q.at, q.t->words.data(), q.t->words.size() * 4, hipMemcpyHostToDevice));
+            break;
+        }
+        VS_HIP_TRY(hipDeviceSynchronize());
+        A.at.clear();
+        A.used = 0;
+    }
+    *arena = A.base;
+    return VS_OK;
+}
+
 template <int SB, bool STAGED>
 void rs_launch_kernel(int interp, const RsArgs& a, unsigned tiles, hipStream_t st) {
     const size_t lds = STAGED ? (size_t)rs_lds_bytes(SB, a.box_rows) : 0;
@@ -482,53 +695,20 @@ int launch_resample(const char* name, const vs_scale_job* jobs, int n, int sampl
     if (!max_value) max_value = sample_bytes == 1 ? 255 : 65535;
     std::lock_guard<std::mutex> lock(rs_mutex);
     std::vector<RsPlan> plans(n);
-    size_t need = 0;
-    {
-        std::map<RsKey, size_t> distinct;
-        for (int i = 0; i < n; i++) {
-            plans[i] = rs_plan_job(jobs[i], sample_bytes, interp);
-            if (plans[i].mean) continue;
-            distinct[rs_key(jobs[i].sw, jobs[i].dw, interp, 0)] = rs_table_dwords(*plans[i].x);
-            distinct[rs_key(jobs[i].sh, jobs[i].dh, interp, 1)] = rs_table_dwords(*plans[i].y);
-        }
-        for (const auto& d : distinct) need += d.second;
+    std::vector<RsNeed> needs;                             // of job i: needs[at[i]] (columns), needs[at[i] + 1] (rows)
+    std::vector<int> at(n, -1);
+    for (int i = 0; i < n; i++) {
+        plans[i] = rs_plan_job(jobs[i], sample_bytes, interp);
+        if (plans[i].mean) continue;
+        at[i] = (int)needs.size();
+        needs.push_back({rs_key(jobs[i].sw, jobs[i].dw, interp, 0), plans[i].x});
+        needs.push_back({rs_key(jobs[i].sh, jobs[i].dh, interp, 1), plans[i].y});
     }
-    if (need > RS_ARENA_BYTES / 4) {
-        set_last_error(std::string(name) + ": the axis tables of one call exceed the table arena (" + std::to_string(RS_ARENA_BYTES >> 20) + " MiB)");
-        return VS_ERR_CAPACITY;
-    }
-    VS_TRY(ensure_device());
-    int dev = 0;
-    VS_HIP_TRY(hipGetDevice(&dev));
-    RsArena& A = rs_arenas[dev];
-    if (!A.base) VS_HIP_TRY(hipMalloc((void**)&A.base, RS_ARENA_BYTES));
-    // the places of the call's tables; a full arena: drain the device, then give every place out anew (the call's tables fit: `need`)
+    const uint32_t* arena = nullptr;
+    VS_TRY(rs_place_tables(name, needs, &arena));
     std::vector<uint32_t> xat(n, 0u), yat(n, 0u);
-    for (int attempt = 0; attempt < 2; attempt++) {
-        bool full = false;
-        const size_t used0 = A.used;
-        for (int i = 0; i < n && !full; i++) {
-            if (plans[i].mean) continue;
-            xat[i] = rs_place(A, rs_key(jobs[i].sw, jobs[i].dw, interp, 0), *plans[i].x, &full);
-            if (!full) yat[i] = rs_place(A, rs_key(jobs[i].sh, jobs[i].dh, interp, 1), *plans[i].y, &full);
-        }
-        if (!full) {
-            // upload what is new: places at or behind used0, each written once by a copy that has finished when it returns
-            std::set<uint32_t> done;
-            for (int i = 0; i < n; i++) {
-                if (plans[i].mean) continue;
-                for (int ax = 0; ax < 2; ax++) {
-                    const uint32_t at = ax ? yat[i] : xat[i];
-                    const RsTable& t = ax ? *plans[i].y : *plans[i].x;
-                    if (at >= used0 && done.insert(at).second) VS_HIP_TRY(hipMemcpy(A.base + at, t.words.data(), t.words.size() * 4, hipMemcpyHostToDevice));
-                }
-            }
-            break;
-        }
-        VS_HIP_TRY(hipDeviceSynchronize());
-        A.at.clear();
-        A.used = 0;
-    }
+    for (int i = 0; i < n; i++)
+        if (at[i] >= 0) { xat[i] = needs[at[i]].at; yat[i] = needs[at[i] + 1].at; }
     // one launch per class
     for (int cls = 0; cls < 2; cls++) {
         const bool staged = cls == 0;
@@ -543,7 +723,7 @@ int launch_resample(const char* name, const vs_scale_job* jobs, int n, int sampl
             }
         if (sel.empty()) continue;
         RsArgs a{};
-        a.arena = A.base; a.max_value = max_value; a.box_rows = box_rows;
+        a.arena = arena; a.max_value = max_value; a.box_rows = box_rows;
         int k = 0;
         VS_TRY(pj_launch(
             name, sel.data(), (int)sel.size(), RS_MAX_JOBS, sample_bytes, a, [](const vs_scale_job&, int, int*) -> const char* { return nullptr; },
@@ -575,6 +755,65 @@ int resample_plan(const char* name, const vs_scale_job* jobs, int n, int sample_
     return VS_OK;
 }
 
+// ---- area-averaging downscale --------------------------------------------------------------------------------------------------
+// Everything the resize refuses about the launch and its jobs (VS_ERR_INVALID_ARG), then an upscale on either axis of a job
+static int area_check(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int max_value) {
+    VS_TRY(rs_check(name, jobs, n, sample_bytes, VS_INTERP_LINEAR, max_value, 0));
+    for (int i = 0; i < n; i++)
+        if (jobs[i].dw > jobs[i].sw || jobs[i].dh > jobs[i].sh) {
+            set_last_error(std::string(name) + ": job " + std::to_string(i) + ": " + AREA_UPSCALE);
+            return VS_ERR_UNSUPPORTED;
+        }
+    return VS_OK;
+}
+
+int launch_area(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int max_value, hipStream_t st) {
+    VS_TRY(area_check(name, jobs, n, sample_bytes, max_value));
+    if (!max_value) max_value = sample_bytes == 1 ? 255 : 65535;
+    std::lock_guard<std::mutex> lock(rs_mutex);
+    std::vector<RsNeed> needs;                             // of a general job i: needs[at[i]] (columns), needs[at[i] + 1] (rows)
+    std::vector<int> at(n, -1), cls(n), ix(n), iy(n);
+    for (int i = 0; i < n; i++) {
+        const vs_scale_job& s = jobs[i];
+        cls[i] = rs_area_class(s.sw, s.sh, s.dw, s.dh, &ix[i], &iy[i]);
+        if (cls[i]) continue;
+        at[i] = (int)needs.size();
+        const RsKey kx = rs_key(s.sw, s.dw, RS_AREA, 0), ky = rs_key(s.sh, s.dh, RS_AREA, 1);
+        needs.push_back({kx, rs_host_table(kx)});
+        needs.push_back({ky, rs_host_table(ky)});
+    }
+    RsArgs a{};
+    VS_TRY(rs_place_tables(name, needs, &a.arena));
+    a.max_value = max_value;
+    int i = 0;
+    return pj_launch(
+        name, jobs, n, RS_MAX_JOBS, sample_bytes, a, [](const vs_scale_job&, int, int*) -> const char* { return nullptr; },
+        [&](const vs_scale_job& s, RsJob& j, uint32_t tile0) {
+            j.src = (const uint8_t*)s.src; j.dst = (uint8_t*)s.dst;
+            j.sstride = (uint32_t)s.src_stride; j.dstride = (uint32_t)s.dst_stride;
+            j.dwh = (uint32_t)s.dw | (uint32_t)s.dh << 16;
+            j.tile0 = tile0;
+            j.xtab = (cls[i] ? 0u : needs[at[i]].at) | (uint32_t)s.cn << 24 | (uint32_t)cls[i] << 28;
+            j.ytab = cls[i] ? (uint32_t)ix[i] | (uint32_t)iy[i] << 16 : needs[at[i] + 1].at;
+            i++;
+            return pj_tiles((size_t)s.dw * s.cn * sample_bytes, s.dh, RS_TB, RS_TR);
+        },
+        [&](auto sb, const RsArgs& args, unsigned tiles) { hipLaunchKernelGGL((area_kernel<decltype(sb)::value>), dim3(tiles), dim3(64, RS_WAVES), 0, st, args); });
+}
+
+int area_plan(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int32_t* cls) {
+    VS_TRY(area_check(name, jobs, n, sample_bytes, 0));
+    if (!cls) {
+        set_last_error(std::string(name) + ": null pointer");
+        return VS_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n; i++) {
+        int ix, iy;
+        cls[i] = rs_area_class(jobs[i].sw, jobs[i].sh, jobs[i].dw, jobs[i].dh, &ix, &iy);
+    }
+    return VS_OK;
+}
+
 }  // namespace vsd
 
 // ---- the C entry points (include/vs_stab.h) -------------------------------------------------------------------------------
@@ -600,28 +839,24 @@ int rs_check_surfaces(const std::string& head, int sw, int sh, int dw, int dh, i
     return VS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vs_op_resample_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int interp, int max_value, int path, void* stream) {
-    return vsd::launch_resample("vs_op_resample_jobs", jobs, n, sample_bytes, interp, max_value, path, (hipStream_t)stream);
+// The surface calls of the resize (area = false) and of the area-averaging downscale (area = true: no interp; an upscale is
+// VS_ERR_UNSUPPORTED, after everything that is VS_ERR_INVALID_ARG)
+int rs_unsupported(const std::string& why) {
+    set_last_error(why);
+    return VS_ERR_UNSUPPORTED;
 }
 
-int vs_op_resample_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int interp, int32_t* staged) {
-    return vsd::resample_plan("vs_op_resample_jobs_plan", jobs, n, sample_bytes, interp, staged);
-}
-
-int vs_op_resize_yuv(int fmt, const void* const* d_src, const vs_i420_layout* in, int sw, int sh, void* const* d_dst, const vs_i420_layout* out, int dw,
-                     int dh, int n, int interp, void* stream) {
-    static const char call[] = "vs_op_resize_yuv";
+int rs_yuv_call(const char* call, bool area, int fmt, const void* const* d_src, const vs_i420_layout* in, int sw, int sh, void* const* d_dst,
+                const vs_i420_layout* out, int dw, int dh, int n, int interp, void* stream) {
     I420Layout li, lo;
     std::string msg;
-    if (cvt_check_yuv("vs_op_resize_yuv: source", fmt, d_src, n, in, sw, sh, &li, &msg) != VS_OK ||
-        cvt_check_yuv("vs_op_resize_yuv: destination", fmt, d_dst, n, out, dw, dh, &lo, &msg) != VS_OK)
+    if (cvt_check_yuv((std::string(call) + ": source").c_str(), fmt, d_src, n, in, sw, sh, &li, &msg) != VS_OK ||
+        cvt_check_yuv((std::string(call) + ": destination").c_str(), fmt, d_dst, n, out, dw, dh, &lo, &msg) != VS_OK)
         return rs_refuse(msg);
     const PixFmt& f = *pixfmt(fmt);
-    if (rs_check_surfaces(std::string(call) + ": " + f.name + ": ", sw, sh, dw, dh, interp, d_src, d_dst, n, &msg) != VS_OK) return rs_refuse(msg);
+    const std::string head = std::string(call) + ": " + f.name + ": ";
+    if (rs_check_surfaces(head, sw, sh, dw, dh, interp, d_src, d_dst, n, &msg) != VS_OK) return rs_refuse(msg);
+    if (area && (dw > sw || dh > sh)) return rs_unsupported(head + AREA_UPSCALE);
     // the planes of a surface: luma; the interleaved (U, V) plane as cn 2, or U and V as planes of their own
     struct P { size_t soff, spitch, doff, dpitch; int sx, sy, cn; } planes[3] = {{0, li.pitch, 0, lo.pitch, 0, 0, 1}};
     int np = 1;
@@ -637,13 +872,14 @@ int vs_op_resize_yuv(int fmt, const void* const* d_src, const vs_i420_layout* in
             jobs.push_back(vs_scale_job{(const uint8_t*)d_src[i] + p.soff, p.spitch, sw >> p.sx, sh >> p.sy, (uint8_t*)d_dst[i] + p.doff, p.dpitch,
                                         dw >> p.sx, dh >> p.sy, p.cn, 0});
         }
-    const int max_value = interp == VS_INTERP_LANCZOS4 && yuv_low_bit(f) ? (1 << f.bits) - 1 : 0;
-    return launch_resample((std::string(call) + ": " + f.name).c_str(), jobs.data(), (int)jobs.size(), f.sample_bytes, interp, max_value, 0, (hipStream_t)stream);
+    const std::string name = std::string(call) + ": " + f.name;
+    const int max_value = (area || interp == VS_INTERP_LANCZOS4) && yuv_low_bit(f) ? (1 << f.bits) - 1 : 0;
+    if (area) return launch_area(name.c_str(), jobs.data(), (int)jobs.size(), f.sample_bytes, max_value, (hipStream_t)stream);
+    return launch_resample(name.c_str(), jobs.data(), (int)jobs.size(), f.sample_bytes, interp, max_value, 0, (hipStream_t)stream);
 }
 
-int vs_op_resize_rgb(int fmt, const void* const* d_src, size_t src_stride, int sw, int sh, void* const* d_dst, size_t dst_stride, int dw, int dh, int n,
-                     int interp, void* stream) {
-    static const char call[] = "vs_op_resize_rgb";
+int rs_rgb_call(const char* call, bool area, int fmt, const void* const* d_src, size_t src_stride, int sw, int sh, void* const* d_dst, size_t dst_stride,
+                int dw, int dh, int n, int interp, void* stream) {
     const PixFmt* f = pixfmt(fmt);
     if (!f || f->kind != PIX_INTERLEAVED)
         return rs_refuse(std::string(call) + ": " + (f ? std::string(f->name) : "format " + std::to_string(fmt)) +
@@ -657,9 +893,34 @@ int vs_op_resize_rgb(int fmt, const void* const* d_src, size_t src_stride, int s
     if (rs_check_surfaces(head, sw, sh, dw, dh, interp, d_src, d_dst, n, &msg) != VS_OK) return rs_refuse(msg);
     if (src_stride < (size_t)sw * f->cn) return rs_refuse(head + "source: the pitch must hold a row of the picture");
     if (dst_stride < (size_t)dw * f->cn) return rs_refuse(head + "destination: the pitch must hold a row of the picture");
+    if (area && (dw > sw || dh > sh)) return rs_unsupported(head + AREA_UPSCALE);
     std::vector<vs_scale_job> jobs;
     for (int i = 0; i < n; i++) jobs.push_back(vs_scale_job{d_src[i], src_stride, sw, sh, d_dst[i], dst_stride, dw, dh, f->cn, 0});
-    return launch_resample((std::string(call) + ": " + f->name).c_str(), jobs.data(), n, 1, interp, 0, 0, (hipStream_t)stream);
+    const std::string name = std::string(call) + ": " + f->name;
+    if (area) return launch_area(name.c_str(), jobs.data(), n, 1, 0, (hipStream_t)stream);
+    return launch_resample(name.c_str(), jobs.data(), n, 1, interp, 0, 0, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vs_op_resample_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int interp, int max_value, int path, void* stream) {
+    return vsd::launch_resample("vs_op_resample_jobs", jobs, n, sample_bytes, interp, max_value, path, (hipStream_t)stream);
+}
+
+int vs_op_resample_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int interp, int32_t* staged) {
+    return vsd::resample_plan("vs_op_resample_jobs_plan", jobs, n, sample_bytes, interp, staged);
+}
+
+int vs_op_resize_yuv(int fmt, const void* const* d_src, const vs_i420_layout* in, int sw, int sh, void* const* d_dst, const vs_i420_layout* out, int dw,
+                     int dh, int n, int interp, void* stream) {
+    return rs_yuv_call("vs_op_resize_yuv", false, fmt, d_src, in, sw, sh, d_dst, out, dw, dh, n, interp, stream);
+}
+
+int vs_op_resize_rgb(int fmt, const void* const* d_src, size_t src_stride, int sw, int sh, void* const* d_dst, size_t dst_stride, int dw, int dh, int n,
+                     int interp, void* stream) {
+    return rs_rgb_call("vs_op_resize_rgb", false, fmt, d_src, src_stride, sw, sh, d_dst, dst_stride, dw, dh, n, interp, stream);
 }
 
 int vs_resize_axis_table(int src, int dst, int interp, int axis, int32_t* idx, int16_t* coef) {
@@ -669,6 +930,34 @@ int vs_resize_axis_table(int src, int dst, int interp, int axis, int32_t* idx, i
     if (axis != 0 && axis != 1) return rs_refuse(std::string(call) + "axis = " + std::to_string(axis) + " must be 0 (columns) or 1 (rows)");
     if (!idx || !coef) return rs_refuse(std::string(call) + "null pointer");
     rs_axis_table(src, dst, interp, axis, idx, coef);
+    return VS_OK;
+}
+
+// ---- area-averaging downscale ------------------------------------------------------------------------------------------------
+int vs_op_area_jobs(const vs_scale_job* jobs, int n, int sample_bytes, int max_value, void* stream) {
+    return vsd::launch_area("vs_op_area_jobs", jobs, n, sample_bytes, max_value, (hipStream_t)stream);
+}
+
+int vs_op_area_jobs_plan(const vs_scale_job* jobs, int n, int sample_bytes, int32_t* cls) {
+    return vsd::area_plan("vs_op_area_jobs_plan", jobs, n, sample_bytes, cls);
+}
+
+int vs_op_area_yuv(int fmt, const void* const* d_src, const vs_i420_layout* in, int sw, int sh, void* const* d_dst, const vs_i420_layout* out, int dw, int dh,
+                   int n, void* stream) {
+    return rs_yuv_call("vs_op_area_yuv", true, fmt, d_src, in, sw, sh, d_dst, out, dw, dh, n, VS_INTERP_LINEAR, stream);
+}
+
+int vs_op_area_rgb(int fmt, const void* const* d_src, size_t src_stride, int sw, int sh, void* const* d_dst, size_t dst_stride, int dw, int dh, int n,
+                   void* stream) {
+    return rs_rgb_call("vs_op_area_rgb", true, fmt, d_src, src_stride, sw, sh, d_dst, dst_stride, dw, dh, n, VS_INTERP_LINEAR, stream);
+}
+
+int vs_area_axis_table(int src, int dst, int32_t* first, int32_t* count, float* w_first, float* w_mid, float* w_last) {
+    static const char call[] = "vs_area_axis_table: ";
+    if (pj_bad_sizes({src, dst})) return rs_refuse(std::string(call) + "sizes must be 1 .. 32767");
+    if (dst > src) return rs_unsupported(std::string(call) + AREA_UPSCALE);
+    if (!first || !count || !w_first || !w_mid || !w_last) return rs_refuse(std::string(call) + "null pointer");
+    rs_area_axis_table(src, dst, first, count, w_first, w_mid, w_last);
     return VS_OK;
 }
 

@@ -174,6 +174,11 @@ int launch_cropzoom(const vs_scale_job* jobs, int n, int sample_bytes, hipStream
 constexpr int RS_MAX_JOBS = 96;
 int launch_resample(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int interp, int max_value, int path, hipStream_t st);
 int resample_plan(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int interp, int32_t* staged);     // host only
+// ... and the area-averaging downscale (vs_op_area_jobs, vs_op_area_yuv, vs_op_area_rgb): the same jobs with dw <= sw and dh <= sh
+// (an upscale: VS_ERR_UNSUPPORTED), cv::resize(INTER_AREA) arithmetic, ONE launch whatever the jobs' classes; cls[i]: 2 = the
+// 2 x 2 mean, 1 = integer box, 0 = general (tables in the same arena, under a key of their own)
+int launch_area(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int max_value, hipStream_t st);
+int area_plan(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int32_t* cls);                         // host only
 
 // ---- k_yuvpad.hip: the pad of border pad on YUV surfaces (vs_op_pad_jobs; a stream with vs_stab_set_yuv_border_pad)
 // n <= YP_MAX_JOBS planes (sw x sh samples) padded by bx columns and by rows on every side in ONE launch: 32 surfaces of up to three

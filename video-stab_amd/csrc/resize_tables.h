@@ -9,6 +9,7 @@
 #ifndef VS_RESIZE_TABLES_H
 #define VS_RESIZE_TABLES_H
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -90,6 +91,56 @@ inline void rs_axis_table(int src, int dst, int interp, int axis, int32_t* idx, 
             cf[0] = rs_sat_short((1.f - f) * (float)RS_COEF);
             cf[1] = rs_sat_short(f * (float)RS_COEF);
         }
+    }
+}
+
+// ---- area-averaging downscale (vs_op_area_jobs, vs_op_area_yuv, vs_op_area_rgb): cv::resize(INTER_AREA) for dst <= src --------
+// The definition is in include/vs_stab.h and tests/arearef.py states it in numpy and `math`; tests/cpp/area_tables_check.cpp
+// compiles this part alone.  RS_AREA is the arena's key for these tables in k_resize.hip, not a vs_interp.
+constexpr int RS_AREA = 2;
+
+// An axis is integer when scale = 1 / (dst / src) lies within DBL_EPSILON of rint(scale); *i = that integer (then src == i * dst)
+inline bool rs_area_integer(int src, int dst, int* i) {
+    const double scale = rs_scale(src, dst);
+    const long r = std::lrint(scale);
+    *i = (int)r;
+    return std::fabs(scale - (double)r) < DBL_EPSILON;
+}
+
+// The class of a job: 2 = the 2 x 2 mean, 1 = integer box (ix x iy), 0 = general (both axes through the tables)
+inline int rs_area_class(int sw, int sh, int dw, int dh, int* ix, int* iy) {
+    const bool x = rs_area_integer(sw, dw, ix), y = rs_area_integer(sh, dh, iy);
+    if (!x || !y) return 0;
+    return *ix == 2 && *iy == 2 ? 2 : 1;
+}
+
+// computeResizeAreaTab for one axis src -> dst, 1 <= dst <= src <= 32767.  The taps of destination index d are the `count[d]`
+// source samples from first[d] on; tap 0 weighs w_first[d], tap count - 1 (count > 1) w_last[d], every other tap w_mid[d].
+// (count == 1: w_last = w_first.  w_mid is 1 / cellWidth whether or not a tap takes it.)
+inline void rs_area_axis_table(int src, int dst, int32_t* first, int32_t* count, float* w_first, float* w_mid, float* w_last) {
+    const double scale = rs_scale(src, dst);
+    for (int d = 0; d < dst; d++) {
+        const double f1 = (double)d * scale, f2 = f1 + scale;
+        const double cw = std::min(scale, (double)src - f1);
+        int s1 = (int)std::ceil(f1), s2 = (int)std::floor(f2);
+        s2 = std::min(s2, src - 1);
+        s1 = std::min(s1, s2);
+        const float mid = (float)(1.0 / cw);
+        int n = 0, lo = s1;
+        float wf = mid, wl = mid;
+        if ((double)s1 - f1 > 1e-3) {
+            lo = s1 - 1;
+            wf = (float)(((double)s1 - f1) / cw);
+            n = 1;
+        }
+        n += s2 - s1;
+        if (f2 - (double)s2 > 1e-3) {
+            wl = (float)(std::min(std::min(f2 - (double)s2, 1.0), cw) / cw);
+            if (n == 0) { lo = s2; wf = wl; }
+            n++;
+        }
+        first[d] = lo; count[d] = n;
+        w_first[d] = wf; w_mid[d] = mid; w_last[d] = n > 1 ? wl : wf;
     }
 }
 

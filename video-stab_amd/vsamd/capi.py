@@ -553,6 +553,12 @@ class VsLib:
             L.vs_op_resize_rgb.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int,
                                            C.c_int, C.c_int, vp]
             L.vs_resize_axis_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.POINTER(C.c_int16)]
+            # area-averaging downscale
+            L.vs_op_area_jobs.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, C.c_int, vp]
+            L.vs_op_area_jobs_plan.argtypes = [C.POINTER(VsScaleJob), C.c_int, C.c_int, i32p]
+            L.vs_op_area_yuv.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int, vp]
+            L.vs_op_area_rgb.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
+            L.vs_area_axis_table.argtypes = [C.c_int, C.c_int, i32p, i32p, f32p, f32p, f32p]
             # edge fill on YUV streams
             L.vs_stab_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
             L.vs_batch_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
@@ -900,6 +906,35 @@ class VsLib:
         """vs_op_resize_rgb on BGR8 / RGB8 / BGRA8 / RGBA8 / GRAY8 frames in device memory (lists of device addresses); asynchronous."""
         src, dst = (C.c_void_p * len(d_src))(*d_src), (C.c_void_p * len(d_dst))(*d_dst)
         self.check(self.lib.vs_op_resize_rgb(fmt, src, src_stride, sw, sh, dst, dst_stride, dw, dh, len(d_src), interp, stream))
+
+    def area_jobs(self, jobs, sample_bytes=1, max_value=0, stream=None):
+        """vs_op_area_jobs (area-averaging downscale, dw <= sw and dh <= sh): 1 .. 96 jobs, tuples as for scale_jobs; asynchronous."""
+        self.check(self.lib.vs_op_area_jobs(self._scale_job_array(jobs), len(jobs), sample_bytes, max_value, stream))
+
+    def area_jobs_plan(self, jobs, sample_bytes=1):
+        """vs_op_area_jobs_plan (no device needed): the class of every job - 2 the 2 x 2 mean, 1 integer box, 0 general."""
+        cls = np.zeros(max(1, len(jobs)), np.int32)
+        self.check(self.lib.vs_op_area_jobs_plan(self._scale_job_array(jobs), len(jobs), sample_bytes, _p(cls, i32p)))
+        return cls[:len(jobs)].copy()
+
+    def area_axis_table(self, src, dst):
+        """vs_area_axis_table (no device needed): first, count (int32) and w_first, w_mid, w_last (float32), dst entries each."""
+        n = max(dst, 1)
+        first, count = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        w = [np.zeros(n, np.float32) for _ in range(3)]
+        self.check(self.lib.vs_area_axis_table(src, dst, _p(first, i32p), _p(count, i32p), *[_p(x, f32p) for x in w]))
+        return (first, count) + tuple(w)
+
+    def area_yuv(self, fmt, d_src, in_layout, sw, sh, d_dst, out_layout, dw, dh, stream=None):
+        """vs_op_area_yuv on surfaces in device memory: arguments as for resize_yuv, without interp; asynchronous."""
+        src, dst = (C.c_void_p * len(d_src))(*d_src), (C.c_void_p * len(d_dst))(*d_dst)
+        self.check(self.lib.vs_op_area_yuv(fmt, src, C.byref(I420LayoutC(*in_layout)), sw, sh, dst, C.byref(I420LayoutC(*out_layout)), dw, dh,
+                                           len(d_src), stream))
+
+    def area_rgb(self, fmt, d_src, src_stride, sw, sh, d_dst, dst_stride, dw, dh, stream=None):
+        """vs_op_area_rgb on BGR8 / RGB8 / BGRA8 / RGBA8 / GRAY8 frames in device memory (lists of device addresses); asynchronous."""
+        src, dst = (C.c_void_p * len(d_src))(*d_src), (C.c_void_p * len(d_dst))(*d_dst)
+        self.check(self.lib.vs_op_area_rgb(fmt, src, src_stride, sw, sh, dst, dst_stride, dw, dh, len(d_src), stream))
 
     def pad_jobs(self, jobs, sample_bytes=1, stream=None):
         """vs_op_pad_jobs (the pad of border pad on YUV surfaces): 1 .. 96 jobs, tuples (src, src_stride, sw, sh, dst, dst_stride, bx,
