@@ -14,10 +14,14 @@
 #                       the frame record of the roll and zoom/crop stages (the same header) in tests/cpp/stage_frame_check,
 #                       the rules of the fade border on YUV in tests/cpp/yuv_fade_check, the axis tables of the resize to an
 #                       output size (csrc/resize_tables.h) in tests/cpp/resize_tables_check and those of the area-averaging
-#                       downscale (the same header) in tests/cpp/area_tables_check.
+#                       downscale (the same header) in tests/cpp/area_tables_check;
+#                     * the body of the deinterlace / weave kernel (csrc/k_deint.hip) run on the host lane by lane in
+#                       tests/cpp/deint_emul_check against a per-pixel loop, every plane an allocation of exactly its bytes
+#                       (needs clang for the kernel's vector types: CLANGXX).
 #                   GPU sanitizers are not available on this pool; device code is covered by the parity tests instead.
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
 ASAN_LIB := $(shell gcc -print-file-name=libasan.so)
+CLANGXX ?= /opt/rocm/llvm/bin/clang++
 
 all:
 	$(MAKE) -C video-stab_amd/csrc
@@ -46,6 +50,9 @@ asan-host:
 	g++ -O1 -g -std=c++17 $(SAN) -I include tests/cpp/yuv_fade_check.cpp -o scratch/fuzz/_asan/yuv_fade_check
 	g++ -O1 -g -std=c++17 -ffp-contract=off $(SAN) tests/cpp/resize_tables_check.cpp -o scratch/fuzz/_asan/resize_tables_check
 	g++ -O1 -g -std=c++17 -ffp-contract=off $(SAN) tests/cpp/area_tables_check.cpp -o scratch/fuzz/_asan/area_tables_check
+	$(CLANGXX) -O1 -g -std=c++17 $(SAN) -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include -I video-stab_amd/csrc \
+	    tests/cpp/deint_emul_check.cpp -o scratch/fuzz/_asan/deint_emul_check
+	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/deint_emul_check
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/config_fuzz 20000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/azc_fuzz 5000
 	ASAN_OPTIONS=detect_leaks=1 ./scratch/fuzz/_asan/libm_check quick

@@ -55,7 +55,9 @@ extern "C" {
  *    vs_stab_set_yuv_edge_fill, vs_batch_set_yuv_edge_fill and vs_op_warp_affine_yuv_fill; the packed 4:2:2 capture formats: enum
  *    vs_packed_fmt with vs_op_cvt_packed_to_yuv, vs_op_cvt_yuv_to_packed and vs_packed_layout; the resize to an output size: enum
  *    vs_interp with vs_op_resample_jobs, vs_op_resample_jobs_plan, vs_op_resize_yuv, vs_op_resize_rgb and vs_resize_axis_table; the area-averaging downscale:
- *    vs_op_area_jobs, vs_op_area_jobs_plan, vs_op_area_yuv, vs_op_area_rgb and vs_area_axis_table
+ *    vs_op_area_jobs, vs_op_area_jobs_plan, vs_op_area_yuv, vs_op_area_rgb and vs_area_axis_table; interlaced sources: enum
+ *    vs_deint_mode and struct vs_deint_job with vs_op_deint_jobs, vs_op_deint_yuv and vs_op_interlace_yuv (the definition of the
+ *    deinterlacer stands in front of them)
  *    (new entry points, new values and new structs only: no existing struct or entry point changed, so
  *    the version stays). */
 #define VS_STAB_ABI_VERSION 2
@@ -1473,6 +1475,82 @@ int vs_op_area_rgb(int fmt, const void* const* d_src, size_t src_stride, int sw,
  * w_first[d], tap count[d] - 1 (count[d] > 1) w_last[d], every other tap w_mid[d]. */
 int vs_area_axis_table(int src, int dst, int32_t* first, int32_t* count,
                        float* w_first, float* w_mid, float* w_last);
+
+/* ---- interlaced sources: deinterlace (linear, yadif) and re-weave (tests/deintref.py states what they compute) ----------------
+ * A woven interlaced frame (1080i from an SDI card) cannot be stabilized: the analysis sees combing as texture and the warp
+ * rotates the two fields into each other.  These calls turn frames of two fields into progressive frames at single or double rate
+ * in HBM, and weave pairs of progressive frames back into interlaced ones.
+ *
+ * DEFINITION.  The reference project has no deinterlacer, so this is a definition of this library.  It is modelled on the widely
+ * used yadif filter and pinned to no other implementation.
+ *
+ * A plane has h rows of w pixels of cn channels, 8- or 16-bit samples.  Every channel is treated on its own: x +- j below means
+ * the same channel of the pixel j pixels away.  Plane row y belongs to field y & 1; this holds for every plane by its own row
+ * index, and so for the chroma planes of 4:2:0 as well.  Inputs are three frames P (previous), C (current) and N (next), all
+ * read-only, and two job fields:
+ *   keep   in {0, 1}: rows with (y & 1) == keep are copied from C.
+ *   second in {0, 1}: 0 - this output is the first field in time of frame C and the temporal pair is (A, B) = (P, C);
+ *                     1 - the second field, (A, B) = (C, N).
+ * A NULL P or N stands for C (the first and the last frame of a stream).
+ * For a missing row y: up = y > 0 ? y - 1 : y + 1 and dn = y + 1 < h ? y + 1 : y - 1.  Requires h >= 2.
+ *
+ * VS_DEINT_LINEAR uses C only and ignores `second`:  out = (C[up][x] + C[dn][x] + 1) >> 1.
+ *
+ * VS_DEINT_YADIF, in plain integer arithmetic (the largest sum is 3 x 65535: everything fits 32 bits):
+ *
+ *   c = C[up][x];  e = C[dn][x];  d = (A[y][x] + B[y][x]) >> 1
+ *   td0 = |A[y][x] - B[y][x]|
+ *   td1 = (|P[up][x] - c| + |P[dn][x] - e|) >> 1
+ *   td2 = (|N[up][x] - c| + |N[dn][x] - e|) >> 1
+ *   diff = max(td0 >> 1, td1, td2)
+ *   sp = (c + e) >> 1
+ *   if 3 <= x < w - 3:                           edge-directed search; no pixel of a plane with w < 7 has one
+ *       best = |C[up][x-1] - C[dn][x-1]| + |c - e| + |C[up][x+1] - C[dn][x+1]| - 1
+ *       score(j) = |C[up][x-1+j] - C[dn][x-1-j]| + |C[up][x+j] - C[dn][x-j]| + |C[up][x+1+j] - C[dn][x+1-j]|
+ *       for g in (-1, +1), in this order:
+ *           if score(g) < best:  best = score(g); sp = (C[up][x+g] + C[dn][x-g]) >> 1
+ *               if score(2g) < best:  best = score(2g); sp = (C[up][x+2g] + C[dn][x-2g]) >> 1      only after g itself won
+ *   if not (y == 1 or y + 2 == h):               spatial interlacing check; upp / dnn lie inside the plane exactly then
+ *       upp = y + 2 (up - y);  dnn = y + 2 (dn - y)
+ *       b = (A[upp][x] + B[upp][x]) >> 1;  f = (A[dnn][x] + B[dnn][x]) >> 1
+ *       mx = max(d - e, d - c, min(b - c, f - e));  mn = min(d - e, d - c, max(b - c, f - e))
+ *       diff = max(diff, mn, -mx)
+ *   out = sp > d + diff ? d + diff : sp < d - diff ? d - diff : sp
+ *
+ * The result lies between sp and d, so it never leaves the sample range; nothing depends on the bit depth or on where the value
+ * sits in the word (P010 and the low-bit formats alike).
+ *
+ * WEAVE is the inverse step: from two progressive frames F (first in time) and S, destination row y is F's row y where
+ * (y & 1) == (tff ? 0 : 1), and S's row y otherwise.  A copy.  Because kept rows are copies,
+ * weave(deint first field, deint second field) of one frame gives the frame back.
+ *
+ * vs_op_deint_jobs - n = 1 .. 96 plane jobs of one sample size (1 or 2 bytes) in ONE launch; cn 1 .. 4 with 8-bit samples, 1 .. 2
+ *   with 16-bit samples, mixed freely; w 1 .. 32767, h 2 .. 32767; mode a vs_deint_mode.  prev or next NULL stands for cur (its
+ *   stride is then not looked at).
+ * vs_op_deint_yuv - n = 1 .. 16 frames of one geometry, any of the eleven YUV surface formats, all planes of all frames and both
+ *   fields in one launch; the interleaved UV plane of NV12 / P010 goes as cn 2.  Layouts and plane rules as in vs_op_resize_yuv:
+ *   `in` describes d_prev, d_cur and d_next, `out` d_first and d_second.  d_first[i] receives keep = tff ? 0 : 1, second = 0;
+ *   d_second[i] the other field with second = 1.  d_second == NULL: single rate, first fields only.  d_prev / d_next may be NULL
+ *   as arrays or hold NULL entries.  In a batch of consecutive frames prev[i] = cur[i - 1] and next[i] = cur[i + 1].  w and h are
+ *   multiples of the format's subsampling, and every plane has at least 2 rows.
+ * vs_op_interlace_yuv - the weave of n = 1 .. 32 pairs of surfaces, one launch.
+ * Refusals are decided before any device call and are VS_ERR_INVALID_ARG with a text that names the call, the job or side, and
+ * the format: counts, sizes, strides that do not hold a row, 16-bit parity, reserved; keep / second / tff / mode outside their
+ * values; h < 2; a destination that overlaps any source of any job of the call, or another destination.  Sources may alias each
+ * other freely.  Valid arguments without a device: VS_ERR_NO_DEVICE.  No byte outside w x h of a destination is written, none
+ * outside w x h of a source read.  Asynchronous on `stream`.
+ * Not built: bwdif and other filters, field-rate motion search, 3:2 pulldown / telecine detection, the packed capture formats as
+ * direct inputs (vs_op_cvt_packed_to_yuv stays a call in front), a stream that deinterlaces by itself, the C++ classes. */
+typedef enum vs_deint_mode { VS_DEINT_LINEAR = 0, VS_DEINT_YADIF = 1 } vs_deint_mode;
+typedef struct vs_deint_job { const void* prev; size_t prev_stride; const void* cur; size_t cur_stride;
+                              const void* next; size_t next_stride; void* dst; size_t dst_stride;
+                              int32_t w, h, cn, keep, second, reserved; } vs_deint_job;
+int vs_op_deint_jobs(const vs_deint_job* jobs, int n, int sample_bytes, int mode, void* stream);
+int vs_op_deint_yuv(int fmt, const void* const* d_prev, const void* const* d_cur, const void* const* d_next,
+                    const vs_i420_layout* in, int w, int h, void* const* d_first, void* const* d_second,
+                    const vs_i420_layout* out, int tff, int mode, int n, void* stream);
+int vs_op_interlace_yuv(int fmt, const void* const* d_first, const void* const* d_second, const vs_i420_layout* in,
+                        int w, int h, void* const* d_dst, const vs_i420_layout* out, int tff, int n, void* stream);
 
 /* ---- image enhancer: vs::Enhancer (Enhancer.h:10-60, Enhancer.cpp:138-239) ------------ */
 /* Enhancer::Parameters defaults, Enhancer.h:12-43 */

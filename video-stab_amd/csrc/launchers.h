@@ -180,6 +180,13 @@ int resample_plan(const char* name, const vs_scale_job* jobs, int n, int sample_
 int launch_area(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int max_value, hipStream_t st);
 int area_plan(const char* name, const vs_scale_job* jobs, int n, int sample_bytes, int32_t* cls);                         // host only
 
+// ---- k_deint.hip: interlaced sources (vs_op_deint_jobs, vs_op_deint_yuv, vs_op_interlace_yuv)
+// n <= DI_MAX_JOBS planes (w x h pixels of cn channels: 1 .. 4 with 8-bit samples, 1 or 2 with 16-bit samples) deinterlaced in ONE
+// launch, mode a vs_deint_mode, or 2: the weave (cur = the first frame in time, next = the second; rows of parity keep from cur).
+// Checks the launch and every job on the host first (a text in vs_last_error that names `name` and the job).
+constexpr int DI_MAX_JOBS = 96;
+int launch_deint(const char* name, const vs_deint_job* jobs, int n, int sample_bytes, int mode, hipStream_t st);
+
 // ---- k_yuvpad.hip: the pad of border pad on YUV surfaces (vs_op_pad_jobs; a stream with vs_stab_set_yuv_border_pad)
 // n <= YP_MAX_JOBS planes (sw x sh samples) padded by bx columns and by rows on every side in ONE launch: 32 surfaces of up to three
 // planes; cn 1 and 2 may be mixed, the sample size is the launch's.  Checks every job on the host first (a text in vs_last_error

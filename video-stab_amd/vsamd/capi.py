@@ -202,6 +202,16 @@ class VsScaleJob(C.Structure):
                 ("cn", C.c_int32), ("reserved", C.c_int32)]
 
 
+DEINT_LINEAR, DEINT_YADIF = 0, 1               # enum vs_deint_mode
+
+
+class VsDeintJob(C.Structure):
+    """struct vs_deint_job (include/vs_stab.h): one plane of vs_op_deint_jobs."""
+    _fields_ = [("prev", C.c_void_p), ("prev_stride", C.c_size_t), ("cur", C.c_void_p), ("cur_stride", C.c_size_t),
+                ("next", C.c_void_p), ("next_stride", C.c_size_t), ("dst", C.c_void_p), ("dst_stride", C.c_size_t),
+                ("w", C.c_int32), ("h", C.c_int32), ("cn", C.c_int32), ("keep", C.c_int32), ("second", C.c_int32), ("reserved", C.c_int32)]
+
+
 class VsError(RuntimeError):
     pass
 
@@ -559,6 +569,11 @@ class VsLib:
             L.vs_op_area_yuv.argtypes = [C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, C.c_int, vp]
             L.vs_op_area_rgb.argtypes = [C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.POINTER(vp), C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
             L.vs_area_axis_table.argtypes = [C.c_int, C.c_int, i32p, i32p, f32p, f32p, f32p]
+            # interlaced sources
+            L.vs_op_deint_jobs.argtypes = [C.POINTER(VsDeintJob), C.c_int, C.c_int, C.c_int, vp]
+            L.vs_op_deint_yuv.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), lp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), lp,
+                                          C.c_int, C.c_int, C.c_int, vp]
+            L.vs_op_interlace_yuv.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), lp, C.c_int, C.c_int, C.POINTER(vp), lp, C.c_int, C.c_int, vp]
             # edge fill on YUV streams
             L.vs_stab_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
             L.vs_batch_set_yuv_edge_fill.argtypes = [vp, C.c_int, C.POINTER(VsYuvFill)]
@@ -935,6 +950,28 @@ class VsLib:
         """vs_op_area_rgb on BGR8 / RGB8 / BGRA8 / RGBA8 / GRAY8 frames in device memory (lists of device addresses); asynchronous."""
         src, dst = (C.c_void_p * len(d_src))(*d_src), (C.c_void_p * len(d_dst))(*d_dst)
         self.check(self.lib.vs_op_area_rgb(fmt, src, src_stride, sw, sh, dst, dst_stride, dw, dh, len(d_src), stream))
+
+    def deint_jobs(self, jobs, sample_bytes=1, mode=DEINT_YADIF, stream=None):
+        """vs_op_deint_jobs: 1 .. 96 plane jobs, tuples (prev, prev_stride, cur, cur_stride, next, next_stride, dst, dst_stride, w, h,
+        cn, keep, second[, reserved]) of device addresses, prev / next None or 0 = the current frame; asynchronous."""
+        arr = (VsDeintJob * max(1, len(jobs)))()
+        for a, j in zip(arr, jobs):
+            j = tuple(j) + (0,) * (14 - len(j))
+            (a.prev, a.prev_stride, a.cur, a.cur_stride, a.next, a.next_stride, a.dst, a.dst_stride, a.w, a.h, a.cn, a.keep, a.second, a.reserved) = j
+        self.check(self.lib.vs_op_deint_jobs(arr, len(jobs), sample_bytes, mode, stream))
+
+    def deint_yuv(self, fmt, d_prev, d_cur, d_next, in_layout, w, h, d_first, d_second, out_layout, tff=1, mode=DEINT_YADIF, stream=None):
+        """vs_op_deint_yuv on surfaces in device memory: lists of device addresses; d_prev / d_next None or lists that may hold None
+        (the current frame stands in); d_second None = single rate; layouts as for resize_yuv; asynchronous."""
+        def arr(v):
+            return None if v is None else (C.c_void_p * len(v))(*v)
+        self.check(self.lib.vs_op_deint_yuv(fmt, arr(d_prev), arr(d_cur), arr(d_next), C.byref(I420LayoutC(*in_layout)), w, h, arr(d_first), arr(d_second),
+                                            C.byref(I420LayoutC(*out_layout)), tff, mode, len(d_cur), stream))
+
+    def interlace_yuv(self, fmt, d_first, d_second, in_layout, w, h, d_dst, out_layout, tff=1, stream=None):
+        """vs_op_interlace_yuv (the weave of pairs of progressive surfaces): lists of device addresses; asynchronous."""
+        a, b, d = ((C.c_void_p * len(v))(*v) for v in (d_first, d_second, d_dst))
+        self.check(self.lib.vs_op_interlace_yuv(fmt, a, b, C.byref(I420LayoutC(*in_layout)), w, h, d, C.byref(I420LayoutC(*out_layout)), tff, len(d_dst), stream))
 
     def pad_jobs(self, jobs, sample_bytes=1, stream=None):
         """vs_op_pad_jobs (the pad of border pad on YUV surfaces): 1 .. 96 jobs, tuples (src, src_stride, sw, sh, dst, dst_stride, bx,
